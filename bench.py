@@ -3,19 +3,23 @@
 kernels for gfx950) on synthetic translating-sinusoid pairs, with the roofline of the dominant solver
 kernel, the CPU oracle and (N = 1) the reference's own kernels timed beside it.
 
-    python bench.py --gpus N --steps K --warmup W [--workload NAME]
+    python bench.py --gpus N --steps K --warmup W [--workload NAME] [--full] [--dump-outputs DIR]
 
 One "step" = one full coarse-to-fine run over one image pair per rank (inputs already resident in HBM).
 N > 1: one process per GPU (torch.distributed, backend nccl = RCCL), every rank works on its own pairs,
 no data-path collective (independent pairs: SURVEY 8e) -> weak scaling.  Rank 0 prints ONE JSON line.
 
-Order of a run
+A plain run does what the headline figure needs and nothing else: set-up, warm-up, ONE timed region of exactly K steps
+(step 2 below; --repeats R for more), the outputs (--dump-outputs DIR: the last timed step's flow fields as DIR/u.npy and
+DIR/v.npy), the line.  --full adds everything else, in this order:
+
+Order of a --full run
   0. batch leg (BASELINE.json configs[3]), a side figure of the line (`batch`): 8 pairs of 1920x1080 per GPU as one lock-step group
      per step on 4 streams, >= 64 steps, median of three regions; then the flow fields of all ranks are gathered to rank 0 over RCCL
      (timed separately: gather.ms).  It runs first, on an untouched GPU, and is closed before the main job allocates (behind the
      main job it read low by amounts that depended on what had run before it)
   1. warm-up of the main job (records the HIP graphs), barrier
-  2. TIMED REGIONS: `--repeats` (5) regions of exactly K steps each, replayed from the recorded graphs, nothing else; barrier
+  2. TIMED REGIONS: `--repeats` (5 with --full) regions of exactly K steps each, replayed from the recorded graphs, nothing else; barrier
      around each; max over ranks; the line reports the MEDIAN region (ms_per_step, value, pairs_per_s) and the fastest / slowest
   3. output check: the flow fields the timed steps left in HBM are hashed; an eager (un-graphed) recomputation
      must give the same bits, and the first pair's flow must equal the CPU oracle's in every pixel (output_check.oracle);
@@ -584,6 +588,15 @@ class Job:
             self._queue(self.sets, 0)
             self.touched.update(range(len(self.sets)))
 
+    def step_sets(self, index):
+        """Indices into self.sets of the plane sets that step `index` writes (the lane choice of step() and flush())."""
+        if self.step_group > 1:
+            S = self.step_group
+            return [(index // S) % self.n_lanes * S + index % S]
+        if self.rotate:
+            return [index % self.n_lanes]
+        return list(range(len(self.sets)))
+
     def poison(self):
         """Every flow plane of the job filled with 0x7f bytes (3.39e38): what a step does not write stays recognisable."""
         self.sync()
@@ -691,6 +704,41 @@ def output_check(job):
         "fields_hashed": 2 * len(replayed),
         "sha256_u_v_first_pair": list(replayed[min(replayed)]) if replayed else None,
     }
+
+
+DUMP_LIMIT_BYTES = 64 * 2 ** 20  # --dump-outputs: at most this much in all
+DUMP_SAMPLE = 2 ** 22            # pixels kept of each field when the whole fields exceed the limit
+DUMP_SEED = 20240601
+
+
+def dump_fields(fields, directory):
+    """Writes {name: float32 array} as DIR/<name>.npy.  Arrays of more than DUMP_LIMIT_BYTES in all are replaced by the same
+    DUMP_SAMPLE pixels of each (flat indices drawn with DUMP_SEED, ascending; 1-D), so that runs of the same arguments
+    write the same selection."""
+    fields = {k: np.ascontiguousarray(a, np.float32) for k, a in fields.items()}
+    if sum(a.nbytes for a in fields.values()) > DUMP_LIMIT_BYTES:
+        n = next(iter(fields.values())).size
+        assert all(a.size == n for a in fields.values())
+        pick = np.sort(np.random.default_rng(DUMP_SEED).choice(n, min(n, DUMP_SAMPLE), replace=False))
+        fields = {k: a.reshape(-1)[pick] for k, a in fields.items()}
+    os.makedirs(directory, exist_ok=True)
+    for k, a in fields.items():
+        np.save(os.path.join(directory, k + ".npy"), a)
+
+
+def dump_outputs(job, index, directory):
+    """--dump-outputs: the flow fields that step `index` (the last timed step) left in HBM, what a caller of the batch entry
+    receives: u and v, [pairs of the step, H, W] float32 (dump_fields samples them when they exceed the limit)."""
+    job.sync()
+    h = job.cfg["h"]
+    us, vs = [], []
+    for si in job.step_sets(index):
+        _, _, pu, pv, gks = job.sets[si]
+        u, v = pu.download(), pv.download()
+        for k in range(len(gks)):
+            us.append(u[k * h:(k + 1) * h])
+            vs.append(v[k * h:(k + 1) * h])
+    dump_fields({"u": np.stack(us), "v": np.stack(vs)}, directory)
 
 
 def pcie_ceiling(flow2d, local_rank, w=4096, h=4096, copies=16):
@@ -1133,13 +1181,71 @@ def plumbing_check(batch, args):
         sys.exit("bench.py --plumbing-check: a collective delivered the wrong data on rank %d" % rank)
 
 
+def headline(args, cfg, world, regions, levels_run, n_lanes, step_group, algorithm_used=None):
+    """The part of the line every run prints: the timed region's figures and the configuration (--full adds the
+    solver algorithm the finest level ran, which its roofline sample reads from the timing records)."""
+    w, h = cfg["w"], cfg["h"]
+    elapsed = float(np.median(regions))
+    pairs_total = args.steps * cfg["pairs_per_rank"] * world
+    px_iters = float(w) * h * cfg["outer"] * cfg["inner"]
+    return {
+        "metric": "Mpixels*SOR-iters/sec at finest level (whole-pyramid wall time); full-pyramid pairs/sec in pairs_per_s",
+        "value": round(px_iters * pairs_total / elapsed / 1e6, 1),
+        "unit": "Mpixel*iters/s",
+        "n_gpus": world,
+        **({"rehearsal": "%d ranks sharing ONE GPU over gloo (--rehearse-on-one-gpu): a walk through the multi-rank "
+                         "branches, not a measurement" % world} if args.rehearse_on_one_gpu else {}),
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+        "ms_per_step_min": round(min(regions) / args.steps * 1e3, 4),
+        "ms_per_step_max": round(max(regions) / args.steps * 1e3, 4),
+        "timed_regions": len(regions),  # each of exactly `steps` steps; ms_per_step is their median
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic" if cfg.get("frames") != "rub" else "rub1 / rub2, the reference's sample pair (tests/data)",
+        "config": {
+            "workload": args.workload, "width": w, "height": h, "pairs_per_gpu_per_step": cfg["pairs_per_rank"],
+            "pyramid_levels": levels_run,
+            "warp_scale": cfg["scale"], "outer_iterations": cfg["outer"], "inner_iterations": cfg["inner"],
+            "data_constancy": CONSTANCY_NAME[cfg["constancy"]], "median_radius": cfg["median"],
+            "gaussian_sigma": cfg["sigma"], "alpha": cfg["alpha"],
+            **({"solver_algorithm": algorithm_used} if algorithm_used is not None else {}),
+            "relaxation": ("red-black SOR, omega %g (opt-in; no reference parity: the reference is Jacobi)" % cfg["sor_omega"])
+                          if cfg.get("sor_omega") else "Jacobi, reference iteration counts (bit-exact parity mode)",
+            "parallelism": "independent pairs, one process per GPU, no data-path collective",
+            "host_path": "OpticalFlowBatch2D::ComputeFlowBatchDevice (C++): one call per step",
+            "streams_per_gpu": n_lanes, "hip_graph_replay": not args.no_graph,
+            "steps_per_lock_step_group": step_group,
+            "group_planes": None if step_group <= 1 else
+                            ("every plane an allocation of its own: gathered and handed back by the object (two device copies per group)"
+                             if args.scattered_groups else
+                             "a lane's pairs one container apart in four allocations (frame 0, frame 1, u, v): a group as laid out, run in place"),
+            "batch_mode": ("lock-step group" if args.batch_mode == "groups" else "lanes") if cfg["pairs_per_rank"] > 1 else None,
+            "timed_region": "graph-replayed steps only" + ("; output check, roofline sample, batch leg and baselines follow it"
+                                                         if args.full else ""),
+        },
+        "pairs_per_s": round(pairs_total / elapsed, 3),  # inputs and outputs resident in HBM (the bench contract)
+    }
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--repeats", type=int, default=5,
-                    help="timed regions of K steps each after the one warm-up; the line reports their median")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed regions of K steps each after the one warm-up; the line reports their median "
+                         "(default 1, with --full 5)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the rocprofv3 --pmc child passes, the batch leg, the output "
+                         "check (eager recomputation, CPU oracle), the host-entry leg, the roofline / per-sweep / clock / "
+                         "latency samples, the timing probes, the CPU and reference baselines, SOR time-to-residual")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the flow fields of the last timed step as DIR/u.npy and DIR/v.npy "
+                         "(float32; a fixed seeded sample of pixels when the fields exceed 64 MB)")
     ap.add_argument("--workload", default=DEFAULT_WORKLOAD, choices=sorted(WORKLOADS))
     ap.add_argument("--algorithm", type=int, default=0, help="flow2d_solver_algorithm: 0 auto, 1 per-sweep, 2 fused")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -1178,6 +1284,8 @@ def main():
                     help="rank plumbing only (launcher, process group on gloo, broadcast, barriers, gathers) without the "
                          "flow computation; needs no GPU and prints no metric")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
     cfg = WORKLOADS[args.workload]
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         spawn_ranks(args)  # does not return
@@ -1204,7 +1312,7 @@ def main():
             sys.exit("bench.py --rehearse-on-one-gpu: at most 6 ranks may share a GPU")
         local_rank = 0
     # counters of THIS workload, collected by child processes before this one initialises the GPU
-    pmc_run = pmc_passes(args, cfg) if (world == 1 and not args.no_pmc) else {}
+    pmc_run = pmc_passes(args, cfg) if (args.full and world == 1 and not args.no_pmc) else {}
 
     import torch  # device plumbing only: barrier, device-wide synchronise, max-over-ranks, the RCCL gather buffer
 
@@ -1220,7 +1328,7 @@ def main():
     # 8-9 % in rounds 4 and 5; behind a main job of eight-pair groups and its host-entry leg 2 281 against 2 530-2 630 pairs/s:
     # profiles/r05_experiments/batch_leg_bisect.txt, batch_leg_first_ab.txt).  The line's `value` is the main job's region below.
     batch_result = None
-    if not args.no_batch_leg and args.workload != BATCH_WORKLOAD and not args.batch_leg_last:
+    if args.full and not args.no_batch_leg and args.workload != BATCH_WORKLOAD and not args.batch_leg_last:
         batch_result = batch_leg(flow2d, batch, torch, args, rank, local_rank, world)
     job = Job(flow2d, batch, args.workload, cfg, args, rank, local_rank, world)
     free_b, total_b = job.ctx.mem_info()
@@ -1236,6 +1344,19 @@ def main():
     # reports the MEDIAN region (ms_per_step, value, pairs_per_s) with the fastest and slowest beside it
     regions = timed_region(job, batch, torch, args.steps, args.warmup, args.repeats)
     elapsed = float(np.median(regions))
+    if args.dump_outputs and rank == 0:  # before anything else writes the flow planes (the output check's eager pass does)
+        dump_outputs(job, args.steps - 1, args.dump_outputs)
+    levels_run = int(min(cfg["levels"], flow2d.host_lib().flow2d_host_max_warp_level_static(w, h, cfg["scale"])))
+    device_memory = dict({"used_gib": round((total_b - free_b) / 2 ** 30, 3), "total_gib": round(total_b / 2 ** 30, 1)},
+                         **memory_parts)
+    if not args.full:  # a plain run: the headline figure and nothing else
+        n_lanes, step_group = job.n_lanes, job.step_group
+        job.close()
+        if rank == 0:
+            print(json.dumps(dict(headline(args, cfg, world, regions, levels_run, n_lanes, step_group),
+                                  device_memory=device_memory)))
+        batch.shutdown()
+        return
     check = output_check(job)
     oracle_timing = None
     if rank == 0 and not args.no_oracle_check:
@@ -1248,7 +1369,6 @@ def main():
         check["ok"] = False
     first_pair = job.first_pair
     n_lanes, step_group = job.n_lanes, job.step_group
-    levels_run = int(min(cfg["levels"], flow2d.host_lib().flow2d_host_max_warp_level_static(w, h, cfg["scale"])))
     # what the sampling legs below need of the job, which is closed before the batch leg (the legs make contexts of their own)
     import types
     sample = types.SimpleNamespace(flow2d=flow2d, cfg=cfg, local_rank=local_rank, first_pair=first_pair, params=job.params,
@@ -1264,7 +1384,6 @@ def main():
 
     ok = check["ok"] and (batch_result is None or batch_result["output_check"]["ok"])
     if rank == 0:
-        pairs_total = args.steps * cfg["pairs_per_rank"] * world
         px_iters = float(w) * h * cfg["outer"] * cfg["inner"]
         solve_ms = float(np.mean([r[2] for r in finest]))
         launch_ms = [r[3] / r[4] for r in finest]
@@ -1355,44 +1474,8 @@ def main():
                      "(valu_issue_frac of the issue peak; DESIGN.md 3.1)") if temporal else
                     "frac = physical HBM fraction; effective_frac = algorithmic bytes over the launch time",
         }
-        out = {
-            "metric": "Mpixels*SOR-iters/sec at finest level (whole-pyramid wall time); full-pyramid pairs/sec in pairs_per_s",
-            "value": round(px_iters * pairs_total / elapsed / 1e6, 1),
-            "unit": "Mpixel*iters/s",
-            "n_gpus": world,
-            **({"rehearsal": "%d ranks sharing ONE GPU over gloo (--rehearse-on-one-gpu): a walk through the multi-rank "
-                             "branches, not a measurement" % world} if args.rehearse_on_one_gpu else {}),
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-            "ms_per_step_min": round(min(regions) / args.steps * 1e3, 4),
-            "ms_per_step_max": round(max(regions) / args.steps * 1e3, 4),
-            "timed_regions": len(regions),  # each of exactly `steps` steps; ms_per_step is their median
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f32",
-            "data": "synthetic" if cfg.get("frames") != "rub" else "rub1 / rub2, the reference's sample pair (tests/data)",
-            "config": {
-                "workload": args.workload, "width": w, "height": h, "pairs_per_gpu_per_step": cfg["pairs_per_rank"],
-                "pyramid_levels": levels_run,
-                "warp_scale": cfg["scale"], "outer_iterations": cfg["outer"], "inner_iterations": cfg["inner"],
-                "data_constancy": CONSTANCY_NAME[cfg["constancy"]], "median_radius": cfg["median"],
-                "gaussian_sigma": cfg["sigma"], "alpha": cfg["alpha"], "solver_algorithm": algorithm_used,
-                "relaxation": ("red-black SOR, omega %g (opt-in; no reference parity: the reference is Jacobi)" % cfg["sor_omega"])
-                              if cfg.get("sor_omega") else "Jacobi, reference iteration counts (bit-exact parity mode)",
-                "parallelism": "independent pairs, one process per GPU, no data-path collective",
-                "host_path": "OpticalFlowBatch2D::ComputeFlowBatchDevice (C++): one call per step",
-                "streams_per_gpu": n_lanes, "hip_graph_replay": not args.no_graph,
-                "steps_per_lock_step_group": step_group,
-                "group_planes": None if step_group <= 1 else
-                                ("every plane an allocation of its own: gathered and handed back by the object (two device copies per group)"
-                                 if args.scattered_groups else
-                                 "a lane's pairs one container apart in four allocations (frame 0, frame 1, u, v): a group as laid out, run in place"),
-                "batch_mode": ("lock-step group" if args.batch_mode == "groups" else "lanes") if cfg["pairs_per_rank"] > 1 else None,
-                "timed_region": "graph-replayed steps only; output check, roofline sample, batch leg and baselines follow it",
-            },
-            "pairs_per_s": round(pairs_total / elapsed, 3),  # inputs and outputs resident in HBM (the bench contract)
+        out = headline(args, cfg, world, regions, levels_run, n_lanes, step_group, algorithm_used)
+        out.update({
             # SURVEY 8(d) metric 2 as defined: host images in, host flows out, H<->D inside the bracket
             "pairs_per_s_incl_h2d": host_entry["pairs_per_s"] if host_entry else None,
             "host_entry": host_entry,
@@ -1409,9 +1492,8 @@ def main():
             "roofline": roof,
             "output_check": check,
             "batch": batch_result,
-            "device_memory": dict({"used_gib": round((total_b - free_b) / 2 ** 30, 3), "total_gib": round(total_b / 2 ** 30, 1)},
-                                  **memory_parts),
-        }
+            "device_memory": device_memory,
+        })
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(cfg, full_run=oracle_timing)
         else:

@@ -94,7 +94,7 @@ def test_bench_multi_rank_branches_with_two_ranks_on_this_gpu():
     import sys
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--rehearse-on-one-gpu", "--workload",
-                        "cfg2_1024_grey", "--steps", "8", "--warmup", "2", "--repeats", "2", "--no-host-entry-leg"],
+                        "cfg2_1024_grey", "--steps", "8", "--warmup", "2", "--repeats", "2", "--no-host-entry-leg", "--full"],
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=420, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [json.loads(x) for x in p.stdout.splitlines() if x.startswith("{")]
@@ -106,3 +106,48 @@ def test_bench_multi_rank_branches_with_two_ranks_on_this_gpu():
     gather = line["batch"]["gather"]
     assert line["batch"]["pairs_total_per_step"] == 16 and line["batch"]["output_check"]["ok"]
     assert gather["own_block_intact"] and gather["every_pair_present"] and gather["root_equals_all_gather"]
+
+
+def load_bench():
+    """bench.py as a module, without leaving its GPU_MAX_HW_QUEUES default behind in this process's environment."""
+    import importlib.util
+    saved = os.environ.get("GPU_MAX_HW_QUEUES")
+    spec = importlib.util.spec_from_file_location("flow2d_bench", os.path.join(ROOT, "bench.py"))
+    mod = importlib.util.module_from_spec(spec)
+    try:
+        spec.loader.exec_module(mod)
+    finally:
+        if saved is None:
+            os.environ.pop("GPU_MAX_HW_QUEUES", None)
+        else:
+            os.environ["GPU_MAX_HW_QUEUES"] = saved
+    return mod
+
+
+def test_bench_plain_run_and_its_dumped_outputs(oracle, tmp_path):
+    """A plain `bench.py` run (no --full): ONE timed region of exactly --steps steps, the headline fields and none of the
+    --full legs; --dump-outputs writes the flow of the last timed step, which must equal the CPU oracle's flow of that
+    step's pair in every pixel."""
+    import sys
+    out = tmp_path / "outputs"
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--workload", "cfg2_1024_grey",
+                        "--steps", "3", "--warmup", "1", "--dump-outputs", str(out)],
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300, cwd=ROOT)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [json.loads(x) for x in p.stdout.splitlines() if x.startswith("{")]
+    assert len(lines) == 1
+    line = lines[0]
+    assert line["unit"] == "Mpixel*iters/s" and line["higher_is_better"] is True and line["dtype"] == "f32"
+    assert line["steps"] == 3 and line["timed_regions"] == 1 and line["value"] > 0 and line["ms_per_step"] > 0
+    assert line["ms_per_step_min"] == line["ms_per_step"] == line["ms_per_step_max"]
+    assert not {"output_check", "roofline", "batch", "host_entry", "cpu_baseline", "reference_gpu_baseline"} & set(line)
+    assert sorted(os.listdir(out)) == ["u.npy", "v.npy"]
+    u, v = np.load(out / "u.npy"), np.load(out / "v.npy")
+    assert u.dtype == v.dtype == np.float32 and u.shape == v.shape == (1, 1024, 1024)
+    # 1024^2 steps go to the batch entry 32 at a time: steps 0-2 are one group on lane 0, step 2 = plane set 2 = global pair 2
+    bench = load_bench()
+    cfg = bench.WORKLOADS["cfg2_1024_grey"]
+    f0, f1 = bench.workload_pair("cfg2_1024_grey", cfg, 2)
+    ou, ov, _ = oracle.compute_flow(f0, f1, cfg["levels"], cfg["scale"], cfg["outer"], cfg["inner"], cfg["alpha"], 0.001,
+                                    0.001, cfg["median"], cfg["sigma"], cfg["constancy"])
+    assert np.array_equal(u[0], ou) and np.array_equal(v[0], ov)

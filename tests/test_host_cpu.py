@@ -261,6 +261,38 @@ def test_committed_bench_line_has_the_contract_fields():
     assert roof["pmc_source"].startswith("this run")                    # counters measured in the run, not quoted
 
 
+def test_bench_dump_fields_whole_or_a_fixed_sample_within_64_mb(tmp_path):
+    """bench.py --dump-outputs writes fields whole while they fit in 64 MB, otherwise the same seeded sample of each,
+    and the same sample from run to run."""
+    import importlib.util
+    saved = os.environ.get("GPU_MAX_HW_QUEUES")  # (bench.py sets a default for the process that runs it)
+    spec = importlib.util.spec_from_file_location("flow2d_bench", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    try:
+        spec.loader.exec_module(bench)
+    finally:
+        if saved is None:
+            os.environ.pop("GPU_MAX_HW_QUEUES", None)
+        else:
+            os.environ["GPU_MAX_HW_QUEUES"] = saved
+    small = {"u": np.arange(24, dtype=np.float32).reshape(2, 3, 4), "v": -np.arange(24, dtype=np.float64).reshape(2, 3, 4)}
+    bench.dump_fields(small, str(tmp_path / "small"))
+    for k, a in small.items():
+        got = np.load(tmp_path / "small" / (k + ".npy"))
+        assert got.dtype == np.float32 and np.array_equal(got, a)
+    rng = np.random.default_rng(7)
+    big = {"u": rng.random((1, 4096, 4096), np.float32), "v": rng.random((1, 4096, 4096), np.float32)}  # 128 MiB
+    for d in ("a", "b"):
+        bench.dump_fields(big, str(tmp_path / d))
+    files = [tmp_path / d / (k + ".npy") for d in ("a", "b") for k in ("u", "v")]
+    assert sum(os.path.getsize(f) for f in files[:2]) <= 64 * 2 ** 20
+    a_u, a_v, b_u, b_v = (np.load(f) for f in files)
+    assert a_u.dtype == np.float32 and a_u.ndim == 1 and a_u.size == a_v.size > 0
+    assert np.array_equal(a_u, b_u) and np.array_equal(a_v, b_v)
+    pick = np.sort(np.random.default_rng(bench.DUMP_SEED).choice(big["u"].size, a_u.size, replace=False))
+    assert np.array_equal(a_u, big["u"].ravel()[pick]) and np.array_equal(a_v, big["v"].ravel()[pick])
+
+
 # ---- the product's host layer against THE REFERENCE'S OWN host code ---------------------------------------
 # tests/golden/ref_host_golden.npz was produced by running the reference's host sources (compiled where they lie)
 # in the build container: tests/golden/make_ref_host_golden.py.

@@ -8,7 +8,7 @@ WLS=${WLS:-cfg3_4096_gradient cfg3_4096_grey cfg2_1024_grey cfg4_1080p_batch cfg
 for rep in 1 2; do
     for wl in $WLS; do
         for so in $LIBS; do
-            FLOW2D_HIP_LIB="$R/$so" timeout -k 10 300 python3 bench.py --workload $wl --no-pmc --no-oracle-check --no-host-entry-leg \
+            FLOW2D_HIP_LIB="$R/$so" timeout -k 10 300 python3 bench.py --full --workload $wl --no-pmc --no-oracle-check --no-host-entry-leg \
                 --no-cpu-baseline --no-reference-baseline --no-batch-leg --no-probe-builds 2>/dev/null |
                 python3 -c "
 import json,sys

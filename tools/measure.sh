@@ -20,7 +20,7 @@ for what in $WHAT; do
     bench)
         for wl in $WLS; do
             extra="--no-batch-leg"; [ $wl = cfg3_4096_gradient ] && extra=""
-            timeout -k 10 400 python3 bench.py --workload $wl $extra > "$OUT/${ROUND}_${wl}_bench_line.json" 2> "$OUT/${ROUND}_${wl}_bench.err" \
+            timeout -k 10 400 python3 bench.py --full --workload $wl $extra > "$OUT/${ROUND}_${wl}_bench_line.json" 2> "$OUT/${ROUND}_${wl}_bench.err" \
                 || { tail -5 "$OUT/${ROUND}_${wl}_bench.err"; exit 1; }
             python3 -c "
 import json; d=json.load(open('$OUT/${ROUND}_${wl}_bench_line.json'))
@@ -31,7 +31,7 @@ print('$wl', 'value', d['value'], 'pairs/s', d['pairs_per_s'], 'single', d['pair
         for wl in $WLS; do
             rm -rf "$OUT/trace_$wl"
             (cd /tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace_$wl" -- \
-                python3 "$R/bench.py" --workload $wl --no-pmc --no-oracle-check --no-host-entry-leg --no-cpu-baseline --no-reference-baseline --no-batch-leg --no-probe-builds --steps 6 --warmup 2 --pipeline 1 --step-group 1 --no-graph \
+                python3 "$R/bench.py" --full --workload $wl --no-pmc --no-oracle-check --no-host-entry-leg --no-cpu-baseline --no-reference-baseline --no-batch-leg --no-probe-builds --steps 6 --warmup 2 --pipeline 1 --step-group 1 --no-graph \
                 > "$OUT/${ROUND}_${wl}_bench_line_under_rocprof.json" 2> "$OUT/trace_$wl.err") || { tail -5 "$OUT/trace_$wl.err"; exit 1; }
             python3 tools/summarize_trace.py "$(ls -S "$OUT"/trace_$wl/*/*kernel_trace.csv | head -1)" 40 > "$OUT/${ROUND}_${wl}_by_grid.txt"
             cp "$(ls -S "$OUT"/trace_$wl/*/*kernel_stats.csv | head -1)" "$OUT/${ROUND}_${wl}_kernel_stats.csv"
@@ -42,7 +42,7 @@ print('$wl', 'value', d['value'], 'pairs/s', d['pairs_per_s'], 'single', d['pair
         export TMPDIR=/tmp
         rm -rf "$OUT/trace_default"
         (cd /tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace_default" -- \
-            python3 "$R/bench.py" --no-pmc --no-probe-builds > "$OUT/${ROUND}_default_command_bench_line_under_rocprof.json" 2> "$OUT/trace_default.err") || { tail -5 "$OUT/trace_default.err"; exit 1; }
+            python3 "$R/bench.py" --full --no-pmc --no-probe-builds > "$OUT/${ROUND}_default_command_bench_line_under_rocprof.json" 2> "$OUT/trace_default.err") || { tail -5 "$OUT/trace_default.err"; exit 1; }
         python3 tools/summarize_trace.py "$(ls -S "$OUT"/trace_default/*/*kernel_trace.csv | head -1)" 30 > "$OUT/${ROUND}_default_command_by_grid.txt"
         cp "$(ls -S "$OUT"/trace_default/*/*kernel_stats.csv | head -1)" "$OUT/${ROUND}_default_command_kernel_stats.csv"
         rm -rf "$OUT/trace_default"
