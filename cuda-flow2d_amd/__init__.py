@@ -143,6 +143,8 @@ def hip_lib():
         if hasattr(L, "flow2d_fused_plain_waves"):  # (absent from libraries of earlier rounds loaded for an A/B)
             L.flow2d_fused_plain_waves.argtypes = [vp, C.POINTER(C.c_ulonglong)]
         L.flow2d_timing_launch_filter.argtypes = [vp, sz, sz]
+        if hasattr(L, "flow2d_consistency_2d"):  # (absent from libraries of earlier rounds loaded for an A/B)
+            L.flow2d_consistency_2d.argtypes = [vp, vp, vp, vp, vp, sz, sz, sz, f, f, vp]
         L.flow2d_timing_count.argtypes = [vp, C.POINTER(sz)]
         L.flow2d_timing_get.argtypes = [vp, sz, C.POINTER(TimingRecord)]
         L.flow2d_timing_reset.argtypes = [vp]
@@ -353,6 +355,12 @@ class Context:
         _check(hip_lib().flow2d_registration_2d(self.handle, f0.ptr, f1.ptr, u.ptr, v.ptr, w, h, f0.pitch, hx, hy,
                                                 out.ptr), "flow2d_registration_2d")
 
+    def consistency(self, u, v, bu, bv, w, h, out, alpha1=0.01, alpha2=0.5):
+        """Forward-backward consistency mask of the flow (u, v) against the backward flow (bu, bv) into `out`: 1.0 where the
+        pair is inconsistent (occluded, leaving the frame, NaN), 0.0 elsewhere (flow2d_consistency_2d)."""
+        _check(hip_lib().flow2d_consistency_2d(self.handle, u.ptr, v.ptr, bu.ptr, bv.ptr, w, h, u.pitch, alpha1, alpha2,
+                                               out.ptr), "flow2d_consistency_2d")
+
     def resample_x(self, src, dst, out_w, out_h, in_w):
         _check(hip_lib().flow2d_resample_x(self.handle, src.ptr, dst.ptr, out_w, out_h, in_w, src.pitch),
                "flow2d_resample_x")
@@ -501,6 +509,10 @@ def host_lib():
         L.flow2d_host_compute_flow_device.argtypes = [vp, vp, vp, vp, vp, C.POINTER(HostParams), i]
         L.flow2d_host_compute_flow_sequence_device.argtypes = [vp, C.POINTER(vp), sz, C.POINTER(vp), C.POINTER(vp),
                                                                C.POINTER(HostParams)]
+        L.flow2d_host_compute_flow_bidirectional.argtypes = [vp, fp, fp, fp, fp, fp, fp, fp, fp, C.POINTER(HostParams), f, f,
+                                                             fp]
+        L.flow2d_host_compute_flow_bidirectional_device.argtypes = [vp, C.POINTER(vp), sz] + [C.POINTER(vp)] * 6 + [
+            C.POINTER(HostParams), f, f]
         L.flow2d_host_level_timings.restype = sz
         L.flow2d_host_level_timings.argtypes = [vp, fp, sz]
         L.flow2d_host_reset_timings.argtypes = [vp]
@@ -614,6 +626,37 @@ class OpticalFlow:
         rc = host_lib().flow2d_host_compute_flow_sequence_device(self.handle, frames, n, us, vs, C.byref(params))
         if rc:
             raise Flow2DError(rc, "OpticalFlow2D::ComputeFlowSequenceDevice")
+
+    def compute_flow_bidirectional(self, frame_0, frame_1, params, alpha1=0.01, alpha2=0.5):
+        """OpticalFlow2D::ComputeFlowBidirectional: host images in; the forward flow (that of compute_flow), the backward flow
+        frame_1 -> frame_0 and the occlusion masks of frame_0 and frame_1 (1.0 = inconsistent) out.
+        Returns (u, v, back_u, back_v, occ_0, occ_1, device_ms)."""
+        f0 = np.ascontiguousarray(frame_0, np.float32)
+        f1 = np.ascontiguousarray(frame_1, np.float32)
+        assert f0.shape == (self.height, self.width) and f1.shape == f0.shape
+        out = [np.empty_like(f0) for _ in range(6)]
+        ms = C.c_float()
+        rc = host_lib().flow2d_host_compute_flow_bidirectional(self.handle, _fptr(f0), _fptr(f1), *[_fptr(a) for a in out],
+                                                               C.byref(params), alpha1, alpha2, C.byref(ms))
+        if rc:
+            raise Flow2DError(rc, "OpticalFlow2D::ComputeFlowBidirectional")
+        return tuple(out) + (ms.value,)
+
+    def compute_flow_bidirectional_device(self, dev_frames, dev_us, dev_vs, dev_back_us, dev_back_vs, params, dev_occ_fwd=None,
+                                          dev_occ_bwd=None, alpha1=0.01, alpha2=0.5):
+        """Forward flow k (dev_frames[k] -> dev_frames[k + 1]) into (dev_us[k], dev_vs[k]), backward flow k (dev_frames[k + 1] ->
+        dev_frames[k]) into (dev_back_us[k], dev_back_vs[k]) and, when given, the occlusion masks of frame k (dev_occ_fwd[k])
+        and frame k + 1 (dev_occ_bwd[k]).  Every frame's pyramid is built once.  Queued, not synchronised."""
+        n = len(dev_frames)
+        lists = [dev_us, dev_vs, dev_back_us, dev_back_vs] + [q for q in (dev_occ_fwd, dev_occ_bwd) if q is not None]
+        if n < 2 or any(len(q) != n - 1 for q in lists):
+            raise ValueError("a sequence of n frames takes n - 1 planes in every output list")
+        arr = lambda q: None if q is None else (C.c_void_p * len(q))(*q)  # noqa: E731
+        rc = host_lib().flow2d_host_compute_flow_bidirectional_device(
+            self.handle, arr(dev_frames), n, arr(dev_us), arr(dev_vs), arr(dev_back_us), arr(dev_back_vs), arr(dev_occ_fwd),
+            arr(dev_occ_bwd), C.byref(params), alpha1, alpha2)
+        if rc:
+            raise Flow2DError(rc, "OpticalFlow2D::ComputeFlowBidirectionalDevice")
 
     def level_timings(self):
         """[(width, height, solve_ms, kernel_ms, kernel_launches, algorithmic_bytes_per_launch, algorithm)] per level;

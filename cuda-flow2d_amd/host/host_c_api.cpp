@@ -152,6 +152,66 @@ HOST_API int flow2d_host_compute_flow_sequence_device(flow2d_host_flow* h, void*
     return h->flow.ComputeFlowSequenceDevice(frames.data(), frame_count, us.data(), vs.data(), bag) ? 0 : 2;
 }
 
+// OpticalFlow2D::ComputeFlowBidirectional on tight host images (width*height floats each): forward and backward flow and both
+// occlusion masks.  alpha1 / alpha2: the bag keys consistency_alpha1 / consistency_alpha2.  0 on success, 2 when the run
+// delivered no flow.
+HOST_API int flow2d_host_compute_flow_bidirectional(flow2d_host_flow* h, const float* frame_0, const float* frame_1,
+                                                    float* flow_u, float* flow_v, float* back_u, float* back_v,
+                                                    float* occlusion_0, float* occlusion_1, const flow2d_host_params* params,
+                                                    float alpha1, float alpha2, float* total_ms)
+{
+    if (!h || !frame_0 || !frame_1 || !flow_u || !flow_v || !back_u || !back_v || !occlusion_0 || !occlusion_1 || !params)
+        return 1;
+    const size_t n = h->width * h->height;
+    Data2D f0(h->width, h->height), f1(h->width, h->height);
+    std::memcpy(f0.DataPtr(), frame_0, n * sizeof(float));
+    std::memcpy(f1.DataPtr(), frame_1, n * sizeof(float));
+    Data2D out[6] = {Data2D(h->width, h->height), Data2D(h->width, h->height), Data2D(h->width, h->height),
+                     Data2D(h->width, h->height), Data2D(h->width, h->height), Data2D(h->width, h->height)};
+    float* dst[6] = {flow_u, flow_v, back_u, back_v, occlusion_0, occlusion_1};
+    for (Data2D& d : out)  // poisoned, as in flow2d_host_compute_flow
+        for (size_t i = 0; i < n; ++i) d.DataPtr()[i] = -12345.f;
+    flow2d_host_params p = *params;
+    OperationParameters bag;
+    FillBag(bag, p);
+    bag.PushValuePtr("consistency_alpha1", &alpha1);
+    bag.PushValuePtr("consistency_alpha2", &alpha2);
+    h->flow.ComputeFlowBidirectional(f0, f1, out[0], out[1], out[2], out[3], out[4], out[5], bag);
+    for (int i = 0; i < 6; ++i) std::memcpy(dst[i], out[i].DataPtr(), n * sizeof(float));
+    if (total_ms) *total_ms = h->flow.LastTotalMs();
+    return h->flow.LastRunSucceeded() ? 0 : 2;
+}
+
+// OpticalFlow2D::ComputeFlowBidirectionalDevice: frame_count device frames, frame_count - 1 forward and backward flow plane pairs,
+// occlusion planes optional (NULL arrays: no masks).  Queued on the context's stream, no synchronisation.  0 on success.
+HOST_API int flow2d_host_compute_flow_bidirectional_device(flow2d_host_flow* h, void* const* dev_frames, size_t frame_count,
+                                                           void* const* dev_flows_u, void* const* dev_flows_v,
+                                                           void* const* dev_back_us, void* const* dev_back_vs,
+                                                           void* const* dev_occ_fwd, void* const* dev_occ_bwd,
+                                                           const flow2d_host_params* params, float alpha1, float alpha2)
+{
+    if (!h || !params || !dev_frames || !dev_flows_u || !dev_flows_v || !dev_back_us || !dev_back_vs || frame_count < 2)
+        return 1;
+    flow2d_host_params p = *params;
+    OperationParameters bag;
+    FillBag(bag, p);
+    bag.PushValuePtr("consistency_alpha1", &alpha1);
+    bag.PushValuePtr("consistency_alpha2", &alpha2);
+    h->flow.timing_mode = 0;
+    auto dp = [](void* q) { return static_cast<DevicePtr>(reinterpret_cast<uintptr_t>(q)); };
+    const size_t n = frame_count - 1;
+    std::vector<DevicePtr> frames(frame_count), planes[6];
+    void* const* sources[6] = {dev_flows_u, dev_flows_v, dev_back_us, dev_back_vs, dev_occ_fwd, dev_occ_bwd};
+    for (size_t k = 0; k < frame_count; ++k) frames[k] = dp(dev_frames[k]);
+    for (int i = 0; i < 6; ++i)
+        if (sources[i])
+            for (size_t k = 0; k < n; ++k) planes[i].push_back(dp(sources[i][k]));
+    auto arr = [&](int i) { return sources[i] ? planes[i].data() : nullptr; };
+    return h->flow.ComputeFlowBidirectionalDevice(frames.data(), frame_count, arr(0), arr(1), arr(2), arr(3), arr(4), arr(5), bag)
+               ? 0
+               : 2;
+}
+
 // ---- OpticalFlowBatch2D: pairs spread over lanes (stream + OpticalFlow2D + plane pool each) on one GPU -----------
 struct flow2d_host_batch {
     OpticalFlowBatch2D batch;

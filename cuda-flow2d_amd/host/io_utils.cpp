@@ -45,6 +45,22 @@ void WriteMagnitudeToFileF32(Data2D& u, Data2D& v, std::string fileName)
     }
 }
 
+void WriteMaskToImagePGM(Data2D& mask, std::string fileName)
+{
+    std::ofstream out(fileName.c_str(), std::ios::out | std::ios::binary);
+    if (!out.is_open()) {
+        std::cerr << "Error: cannot save file " << std::endl;
+        std::exit(255);
+    }
+    const int nx = static_cast<int>(mask.Width()), ny = static_cast<int>(mask.Height());
+    out << "P5\n" << nx << " " << ny << "\n255\n";
+    std::vector<GRAY> row(static_cast<size_t>(nx));
+    for (int y = 0; y < ny; ++y) {
+        for (int x = 0; x < nx; ++x) row[x] = mask.Data(x, y) != 0.0f ? 255 : 0;
+        out.write(reinterpret_cast<const char*>(row.data()), row.size());
+    }
+}
+
 // Colour wheel of io_utils.cpp:140-225 as a table: the half angle phi/2 in [0, pi] runs through the key
 // colours below; inside a segment the colour is the linear blend of its two ends, scaled by the
 // (clipped) magnitude and floored.  float/double promotions follow the reference expression by

@@ -20,6 +20,9 @@ struct RGBColor {
 // exit(255) when the file cannot be opened, like the reference (io_utils.cpp:47-51,88-92).
 void WriteFlowToImageRGB(Data2D& u, Data2D& v, float flowMaxScale, std::string fileName);
 void WriteMagnitudeToFileF32(Data2D& u, Data2D& v, std::string fileName);
+// An occlusion mask as a binary greyscale image (P5, "P5\n<nx> <ny>\n255\n"): 255 where the mask is non-zero, 0 elsewhere.
+// No reference counterpart; exit(255) when the file cannot be opened, like the writers above.
+void WriteMaskToImagePGM(Data2D& mask, std::string fileName);
 
 // Direction -> hue, magnitude (clipped at 1) -> brightness.
 RGBColor ConvertToRGB(float x, float y);

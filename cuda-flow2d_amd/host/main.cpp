@@ -7,8 +7,11 @@
 // exit codes: 1 no device, 2 frame load failed, 3 settings error, 255 cannot write PPM/amp, 0 otherwise.
 // Documented supersets: imageType="8-bit" selects the u8 reader; inputPath is tried as
 // a prefix before the bare file name; argc == 6 no longer dereferences argv[6]; no blocking getchar();
-// options --u8, --gradient, --log-derivatives, --device N, --verbose, --sor OMEGA (opt-in red-black SOR, no reference parity)
-// may precede the positional arguments.
+// options --u8, --gradient, --log-derivatives, --device N, --verbose, --sor OMEGA (opt-in red-black SOR, no reference parity),
+// --backward (also the backward flow and forward-backward occlusion masks, see below) may precede the positional arguments.
+// --backward writes, besides the unchanged forward files, <prefix>flow-u-backward-W-H.raw, <prefix>flow-v-backward-W-H.raw
+// (the flow frame 2 -> frame 1), <prefix>occlusion-W-H.raw (frame 1's grid) and <prefix>occlusion-backward-W-H.raw (frame 2's
+// grid) as F32 0 / 1 (1 = occluded or leaving the frame), and <prefix>occlusion.pgm (P5, 255 where frame 1 is occluded).
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -42,7 +45,7 @@ static bool LoadFrame(Data2D& frame, const std::string& input_path, const std::s
 int main(int argc, char** argv)
 {
     // optional flags first (supersets), then the reference's positional forms
-    bool force_u8 = false, verbose = false;
+    bool force_u8 = false, verbose = false, backward = false;
     int device = 0;
     float sor_omega = 0.f;
     DataConstancy data_constancy = DataConstancy::Grey;
@@ -53,6 +56,7 @@ int main(int argc, char** argv)
         else if (!std::strcmp(argv[i], "--gradient-untiled")) data_constancy = DataConstancy::GradientUntiled;
         else if (!std::strcmp(argv[i], "--log-derivatives")) data_constancy = DataConstancy::LogDerivatives;
         else if (!std::strcmp(argv[i], "--verbose")) verbose = true;
+        else if (!std::strcmp(argv[i], "--backward")) backward = true;
         else if (!std::strcmp(argv[i], "--device") && i + 1 < argc) device = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--sor") && i + 1 < argc) sor_omega = static_cast<float>(std::atof(argv[++i]));
         else args.push_back(argv[i]);
@@ -152,7 +156,17 @@ int main(int argc, char** argv)
         params.PushValuePtr("median_radius", &median_radius);
         params.PushValuePtr("gaussian_sigma", &gaussian_sigma);
         if (sor_omega != 0.f) params.PushValuePtr("solver_sor_omega", &sor_omega);
-        optical_flow.ComputeFlow(frame_0, frame_1, flow_u, flow_v, params);
+        Data2D back_u, back_v, occlusion_0, occlusion_1;
+        if (backward) {
+            back_u = Data2D(width, height);
+            back_v = Data2D(width, height);
+            occlusion_0 = Data2D(width, height);
+            occlusion_1 = Data2D(width, height);
+            optical_flow.ComputeFlowBidirectional(frame_0, frame_1, flow_u, flow_v, back_u, back_v, occlusion_0, occlusion_1,
+                                                  params);
+        } else {
+            optical_flow.ComputeFlow(frame_0, frame_1, flow_u, flow_v, params);
+        }
         if (!optical_flow.LastRunSucceeded()) {
             // the reference writes whatever its buffers hold after a failed run; no output files here instead
             std::cout << "Error: the flow computation failed, no output written." << std::endl;
@@ -166,6 +180,13 @@ int main(int argc, char** argv)
         flow_v.WriteRAWToFileF32((output_path + counter + "flow-v" + suffix).c_str());
         IOUtils::WriteFlowToImageRGB(flow_u, flow_v, 10, output_path + counter + "res.pgm");
         IOUtils::WriteMagnitudeToFileF32(flow_u, flow_v, output_path + counter + "amp" + suffix);
+        if (backward) {
+            back_u.WriteRAWToFileF32((output_path + counter + "flow-u-backward" + suffix).c_str());
+            back_v.WriteRAWToFileF32((output_path + counter + "flow-v-backward" + suffix).c_str());
+            occlusion_0.WriteRAWToFileF32((output_path + counter + "occlusion" + suffix).c_str());
+            occlusion_1.WriteRAWToFileF32((output_path + counter + "occlusion-backward" + suffix).c_str());
+            IOUtils::WriteMaskToImagePGM(occlusion_0, output_path + counter + "occlusion.pgm");
+        }
         optical_flow.Destroy();
     }
     DestroyDeviceContext();

@@ -159,6 +159,10 @@ void OpticalFlow2D::Destroy()
         }
         if (level_warp_plane_) flow2d_plane_free(context_, AsPlane(level_warp_plane_));
         level_warp_plane_ = 0;
+        for (DevicePtr& p : bidirectional_planes_) {
+            if (p) flow2d_plane_free(context_, AsPlane(p));
+            p = 0;
+        }
     }
     all_planes_.clear();
     free_planes_.clear();
@@ -215,16 +219,10 @@ DevicePtr OpticalFlow2D::SequenceLevelPlane(FramePyramid& pyramid, size_t level,
     return pyramid.levels[level];
 }
 
-bool OpticalFlow2D::ComputeFlowSequenceDevice(const DevicePtr* dev_frames, size_t frame_count, const DevicePtr* dev_flows_u,
-                                              const DevicePtr* dev_flows_v, OperationParameters& params)
+// Every pyramid of the sequence cache invalid (the frames may have changed since the last call); a plane for the blurred
+// frame when there is a pre-blur.
+bool OpticalFlow2D::PrepareSequenceCache(OperationParameters& params)
 {
-    if (!IsInitialized() || !dev_frames || !dev_flows_u || !dev_flows_v || frame_count < 2) return false;
-    if (group_ > 1) {
-        std::printf("Error: '%s': sequences and lock-step groups do not combine.\n", GetName());
-        return false;
-    }
-    for (size_t k = 0; k < frame_count; ++k)
-        if (!dev_frames[k] || (k + 1 < frame_count && (!dev_flows_u[k] || !dev_flows_v[k]))) return false;
     float gaussian_sigma = 0.f;
     params.Read<float>("gaussian_sigma", gaussian_sigma);
     for (FramePyramid& pyramid : sequence_cache_) {
@@ -240,31 +238,163 @@ bool OpticalFlow2D::ComputeFlowSequenceDevice(const DevicePtr* dev_frames, size_
             pyramid.blurred = static_cast<DevicePtr>(reinterpret_cast<uintptr_t>(plane));
         }
     }
+    return true;
+}
+
+bool OpticalFlow2D::RunSequencePair(FramePyramid& first, FramePyramid& second, DevicePtr frame_0, DevicePtr frame_1,
+                                    DevicePtr flow_u, DevicePtr flow_v, OperationParameters& params)
+{
+    sequence_frames_[0] = &first;
+    sequence_frames_[1] = &second;
+    dev_frame_0_ = Acquire();  // unused by a sequence pair, kept for the pool's bookkeeping
+    dev_frame_1_ = Acquire();
+    dev_flow_u_ = Acquire();
+    dev_flow_v_ = Acquire();
+    caller_frame_0_ = frame_0;
+    caller_frame_1_ = frame_1;
+    caller_flow_u_ = flow_u;
+    caller_flow_v_ = flow_v;
+    const bool ok = RunPyramid(params);
+    caller_frame_0_ = caller_frame_1_ = caller_flow_u_ = caller_flow_v_ = 0;
+    sequence_frames_[0] = sequence_frames_[1] = nullptr;
+    Release(dev_frame_0_);
+    Release(dev_frame_1_);
+    Release(dev_flow_u_);
+    Release(dev_flow_v_);
+    if (ok) first.valid = second.valid = true;
+    return ok;
+}
+
+bool OpticalFlow2D::ComputeFlowSequenceDevice(const DevicePtr* dev_frames, size_t frame_count, const DevicePtr* dev_flows_u,
+                                              const DevicePtr* dev_flows_v, OperationParameters& params)
+{
+    if (!IsInitialized() || !dev_frames || !dev_flows_u || !dev_flows_v || frame_count < 2) return false;
+    if (group_ > 1) {
+        std::printf("Error: '%s': sequences and lock-step groups do not combine.\n", GetName());
+        return false;
+    }
+    for (size_t k = 0; k < frame_count; ++k)
+        if (!dev_frames[k] || (k + 1 < frame_count && (!dev_flows_u[k] || !dev_flows_v[k]))) return false;
+    if (!PrepareSequenceCache(params)) return false;
     bool ok = true;
     for (size_t k = 0; ok && k + 1 < frame_count; ++k) {
         FramePyramid& first = sequence_cache_[k % 2];          // frame k: built as the second frame of pair k-1
         FramePyramid& second = sequence_cache_[(k + 1) % 2];   // frame k+1: built by this pair
         second.valid = false;
-        sequence_frames_[0] = &first;
-        sequence_frames_[1] = &second;
-        dev_frame_0_ = Acquire();  // unused by a sequence pair, kept for the pool's bookkeeping
-        dev_frame_1_ = Acquire();
-        dev_flow_u_ = Acquire();
-        dev_flow_v_ = Acquire();
-        caller_frame_0_ = dev_frames[k];
-        caller_frame_1_ = dev_frames[k + 1];
-        caller_flow_u_ = dev_flows_u[k];
-        caller_flow_v_ = dev_flows_v[k];
-        ok = RunPyramid(params);
-        caller_frame_0_ = caller_frame_1_ = caller_flow_u_ = caller_flow_v_ = 0;
-        sequence_frames_[0] = sequence_frames_[1] = nullptr;
-        Release(dev_frame_0_);
-        Release(dev_frame_1_);
-        Release(dev_flow_u_);
-        Release(dev_flow_v_);
-        if (ok) first.valid = second.valid = true;
+        ok = RunSequencePair(first, second, dev_frames[k], dev_frames[k + 1], dev_flows_u[k], dev_flows_v[k], params);
     }
     return ok;
+}
+
+bool OpticalFlow2D::ComputeFlowBidirectionalDevice(const DevicePtr* dev_frames, size_t frame_count, const DevicePtr* dev_flows_u,
+                                                   const DevicePtr* dev_flows_v, const DevicePtr* dev_back_us,
+                                                   const DevicePtr* dev_back_vs, const DevicePtr* dev_occ_fwd,
+                                                   const DevicePtr* dev_occ_bwd, OperationParameters& params)
+{
+    if (!IsInitialized() || !dev_frames || !dev_flows_u || !dev_flows_v || !dev_back_us || !dev_back_vs || frame_count < 2)
+        return false;
+    if (group_ > 1) {
+        std::printf("Error: '%s': sequences and lock-step groups do not combine.\n", GetName());
+        return false;
+    }
+    // every plane written must be distinct from every other one and from the frames (which are only read)
+    std::vector<DevicePtr> outputs;
+    for (size_t k = 0; k + 1 < frame_count; ++k) {
+        for (const DevicePtr* a : {dev_flows_u, dev_flows_v, dev_back_us, dev_back_vs, dev_occ_fwd, dev_occ_bwd})
+            if (a) outputs.push_back(a[k]);
+    }
+    for (size_t k = 0; k < frame_count; ++k)
+        if (!dev_frames[k]) return false;
+    for (size_t i = 0; i < outputs.size(); ++i) {
+        if (!outputs[i]) return false;
+        for (size_t k = 0; k < frame_count; ++k)
+            if (outputs[i] == dev_frames[k]) {
+                std::printf("Error: '%s': an output plane is one of the frames.\n", GetName());
+                return false;
+            }
+        for (size_t j = i + 1; j < outputs.size(); ++j)
+            if (outputs[i] == outputs[j]) {
+                std::printf("Error: '%s': the output planes must be distinct.\n", GetName());
+                return false;
+            }
+    }
+    float alpha1 = 0.01f, alpha2 = 0.5f;  // Sundaram, Brox & Keutzer (ECCV 2010)
+    params.Read<float>("consistency_alpha1", alpha1);
+    params.Read<float>("consistency_alpha2", alpha2);
+    const bool masks = dev_occ_fwd || dev_occ_bwd;
+    if (masks && !(std::isfinite(alpha1) && std::isfinite(alpha2) && alpha1 >= 0.f && alpha2 >= 0.f)) {
+        std::printf("Error: '%s': consistency thresholds %g / %g (finite, >= 0).\n", GetName(), alpha1, alpha2);
+        return false;
+    }
+    if (!PrepareSequenceCache(params)) return false;
+    const size_t W = dev_container_size_.width, H = dev_container_size_.height, pitch = dev_container_size_.pitch;
+    bool ok = true;
+    for (size_t k = 0; ok && k + 1 < frame_count; ++k) {
+        FramePyramid& first = sequence_cache_[k % 2];          // frame k: built as the second frame of pair k-1
+        FramePyramid& second = sequence_cache_[(k + 1) % 2];   // frame k+1: built by the forward run
+        second.valid = false;
+        ok = RunSequencePair(first, second, dev_frames[k], dev_frames[k + 1], dev_flows_u[k], dev_flows_v[k], params) &&
+             RunSequencePair(second, first, dev_frames[k + 1], dev_frames[k], dev_back_us[k], dev_back_vs[k], params);
+        if (ok && dev_occ_fwd)
+            ok = !CheckFlow2DError(flow2d_consistency_2d(context_, AsPlane(dev_flows_u[k]), AsPlane(dev_flows_v[k]),
+                                                         AsPlane(dev_back_us[k]), AsPlane(dev_back_vs[k]), W, H, pitch, alpha1,
+                                                         alpha2, AsPlane(dev_occ_fwd[k])),
+                                   "flow2d_consistency_2d");
+        if (ok && dev_occ_bwd)
+            ok = !CheckFlow2DError(flow2d_consistency_2d(context_, AsPlane(dev_back_us[k]), AsPlane(dev_back_vs[k]),
+                                                         AsPlane(dev_flows_u[k]), AsPlane(dev_flows_v[k]), W, H, pitch, alpha1,
+                                                         alpha2, AsPlane(dev_occ_bwd[k])),
+                                   "flow2d_consistency_2d");
+    }
+    return ok;
+}
+
+void OpticalFlow2D::ComputeFlowBidirectional(Data2D& frame_0, Data2D& frame_1, Data2D& flow_u, Data2D& flow_v, Data2D& back_u,
+                                             Data2D& back_v, Data2D& occlusion_0, Data2D& occlusion_1, OperationParameters& params)
+{
+    last_run_ok_ = false;
+    if (!IsInitialized()) return;
+    if (group_ > 1) {
+        std::printf("Error: '%s': sequences and lock-step groups do not combine.\n", GetName());
+        return;
+    }
+    const size_t W = dev_container_size_.width, H = dev_container_size_.height;
+    Data2D* images[8] = {&frame_0, &frame_1, &flow_u, &flow_v, &back_u, &back_v, &occlusion_0, &occlusion_1};
+    for (Data2D* d : images)
+        if (d->Width() != W || d->Height() != H) {
+            std::printf("Error: '%s': frame / flow sizes do not match the initialised size %zu x %zu.\n", GetName(), W, H);
+            return;
+        }
+    for (DevicePtr& p : bidirectional_planes_) {
+        if (p) continue;
+        void* plane = nullptr;
+        size_t pitch = 0;
+        if (CheckFlow2DError(flow2d_plane_alloc(context_, W, H, &plane, &pitch), "flow2d_plane_alloc")) return;
+        p = static_cast<DevicePtr>(reinterpret_cast<uintptr_t>(plane));
+        if (pitch != dev_container_size_.pitch) {
+            std::printf("Error: '%s': plane pitch %zu differs from the container pitch %zu.\n", GetName(), pitch,
+                        dev_container_size_.pitch);
+            return;
+        }
+    }
+    std::printf("\nStarting optical flow computation...\n");
+    void *ev_start = nullptr, *ev_stop = nullptr;
+    flow2d_event_create(context_, &ev_start);
+    flow2d_event_create(context_, &ev_stop);
+    flow2d_event_record(context_, ev_start);
+
+    const DevicePtr* d = bidirectional_planes_;  // frame 0, frame 1, u, v, back u, back v, occlusion 0, occlusion 1
+    bool ok = CopyData2DtoDevice(frame_0, d[0], H, dev_container_size_.pitch) &&
+              CopyData2DtoDevice(frame_1, d[1], H, dev_container_size_.pitch);
+    ok = ok && ComputeFlowBidirectionalDevice(d, 2, d + 2, d + 3, d + 4, d + 5, d + 6, d + 7, params);
+    for (int i = 2; ok && i < 8; ++i) ok = CopyData2DFromDevice(d[i], *images[i], H, dev_container_size_.pitch);
+    last_run_ok_ = ok;
+    flow2d_event_record(context_, ev_stop);
+    flow2d_event_synchronize(context_, ev_stop);  // the only host wait
+    flow2d_event_elapsed_ms(context_, ev_start, ev_stop, &last_total_ms_);
+    std::printf("Total GPU computation time: % 4.4fs\n", last_total_ms_ / 1000.);
+    flow2d_event_destroy(context_, ev_start);
+    flow2d_event_destroy(context_, ev_stop);
 }
 
 void OpticalFlow2D::ResetLevelTimings()

@@ -8,7 +8,8 @@
 // warp_scale_factor float, outer_iterations_count size_t, inner_iterations_count size_t,
 // equation_alpha float, equation_smoothness float, equation_data float, median_radius size_t,
 // gaussian_sigma float.  Optional superset keys: solver_algorithm int (flow2d_solver_algorithm),
-// solver_sor_omega float (opt-in red-black SOR; the default 0 keeps the reference's Jacobi sweeps).
+// solver_sor_omega float (opt-in red-black SOR; the default 0 keeps the reference's Jacobi sweeps);
+// ComputeFlowBidirectional*: consistency_alpha1, consistency_alpha2 float (occlusion thresholds, default 0.01 / 0.5).
 //
 // MI355X-first differences (results unchanged): every launch of a pair is queued on one HIP stream
 // with no host synchronisation until the flow is copied back (the reference blocks after every
@@ -81,6 +82,23 @@ public:
     // Frames are only read; queued on the context's stream, launched eagerly (no graph).
     bool ComputeFlowSequenceDevice(const DevicePtr* dev_frames, size_t frame_count, const DevicePtr* dev_flows_u,
                                    const DevicePtr* dev_flows_v, OperationParameters& params);
+
+    // Flows of a sequence in both directions (no reference counterpart; frame_count = 2 is a pair): for every k,
+    // (us[k], vs[k]) = the flow frames[k] -> frames[k + 1], bit-identical to ComputeFlowDevice(frames[k], frames[k + 1]), and
+    // (back_us[k], back_vs[k]) = the flow frames[k + 1] -> frames[k], bit-identical to ComputeFlowDevice(frames[k + 1], frames[k]).
+    // The backward run swaps the two roles of the sequence cache: every frame's pyramid is built once and serves every flow that
+    // touches the frame.  With non-null occ_fwd / occ_bwd, occ_fwd[k] (frame k's grid: the forward flow checked against the
+    // backward one) and occ_bwd[k] (frame k+1's grid: roles swapped) get the forward-backward consistency masks of
+    // flow2d_consistency_2d: 1 = occluded / leaves the frame / NaN, 0 = consistent.  Optional bag keys consistency_alpha1 and
+    // consistency_alpha2 (float; 0.01 / 0.5, the paper's values).  Frames are only read; outputs must be distinct from each other
+    // and from the frames.  Queued on the context's stream, launched eagerly (no graph).  Not for lock-step groups.
+    bool ComputeFlowBidirectionalDevice(const DevicePtr* dev_frames, size_t frame_count, const DevicePtr* dev_flows_u,
+                                        const DevicePtr* dev_flows_v, const DevicePtr* dev_back_us, const DevicePtr* dev_back_vs,
+                                        const DevicePtr* dev_occ_fwd, const DevicePtr* dev_occ_bwd, OperationParameters& params);
+    // The host-image form (the CLI's --backward): upload both frames, ComputeFlowBidirectionalDevice with masks, download all six
+    // outputs.  flow_u / flow_v are those of ComputeFlow; LastRunSucceeded and LastTotalMs as for ComputeFlow.
+    void ComputeFlowBidirectional(Data2D& frame_0, Data2D& frame_1, Data2D& flow_u, Data2D& flow_v, Data2D& back_u,
+                                  Data2D& back_v, Data2D& occlusion_0, Data2D& occlusion_1, OperationParameters& params);
 
     // When set, ComputeFlowDevice records the whole pyramid of a pair into a HIP graph the first time it
     // sees a (buffers, parameters) combination and replays it afterwards: one host call instead of
@@ -164,6 +182,12 @@ private:
     FramePyramid* sequence_frames_[2] = {nullptr, nullptr};  // non-null inside a sequence pair: frame 0 / frame 1
     DevicePtr SequenceLevelPlane(FramePyramid& pyramid, size_t level, size_t rows);
     void FreeSequenceCache();
+    bool PrepareSequenceCache(OperationParameters& params);
+    // One pair of a sequence: `first` / `second` are the pyramids of frame_0 / frame_1 (built here unless valid)
+    bool RunSequencePair(FramePyramid& first, FramePyramid& second, DevicePtr frame_0, DevicePtr frame_1, DevicePtr flow_u,
+                         DevicePtr flow_v, OperationParameters& params);
+    // ComputeFlowBidirectional: both frames and the six outputs, outside the pool (allocated on first use)
+    DevicePtr bidirectional_planes_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     flow2d_context* context_ = nullptr;
     // One plane beside the pool: the warped frame of a level, when the levels of both frames are computed up front into plane
     // regions of their own (RunPyramid: "stacked" levels) and therefore cannot be overwritten by the warp

@@ -33,6 +33,8 @@ extern "C" {
 
 #define FLOW2D_API __attribute__((visibility("default")))
 
+/* Additions that leave every existing entry as it was keep the version: flow2d_consistency_2d (forward-backward occlusion
+ * masks) was added under 1. */
 #define FLOW2D_ABI_VERSION 1
 
 typedef enum flow2d_status {
@@ -198,6 +200,25 @@ FLOW2D_API int flow2d_median_2d(flow2d_context* ctx, const float* input, size_t 
 FLOW2D_API int flow2d_registration_2d(flow2d_context* ctx, const float* frame_0, const float* frame_1,
                                       const float* flow_u, const float* flow_v, size_t width, size_t height,
                                       size_t pitch_bytes, float hx, float hy, float* output);
+
+/* Forward-backward consistency check (Sundaram, Brox & Keutzer, ECCV 2010; no reference counterpart; added to ABI version 1
+ * without changing any existing entry).  (flow_u, flow_v): the flow of frame 0 to frame 1; (back_u, back_v): the flow of
+ * frame 1 to frame 0.  For every pixel (x, y), 0 <= x < width, 0 <= y < height, `mask` gets 1.0f where the pair is
+ * inconsistent -- occluded, leaving the frame, or NaN -- and 0.0f elsewhere, by exactly these fp32 operations:
+ *   xf = x + u0, yf = y + v0                          (u0 = flow_u[p], v0 = flow_v[p])
+ *   not (0 <= xf <= width - 1 and 0 <= yf <= height - 1)  -> 1          (a NaN lands here)
+ *   xi = floor(xf), yi = floor(yf), dx = xf - xi, dy = yf - yi, x1 = min(width - 1, xi + 1), y1 = min(height - 1, yi + 1)
+ *   S(P) = (1-dx)*(1-dy)*P[yi,xi] + dx*(1-dy)*P[yi,x1] + (1-dx)*dy*P[y1,xi] + dx*dy*P[y1,x1]  (left to right: the bilinear
+ *          sample of flow2d_registration_2d)
+ *   bu = S(back_u), bv = S(back_v), eu = u0 + bu, ev = v0 + bv
+ *   mask = (eu*eu + ev*ev <= alpha1 * ((u0*u0 + v0*v0) + (bu*bu + bv*bv)) + alpha2) ? 0 : 1   (a NaN sample -> 1)
+ * The paper's values are alpha1 = 0.01, alpha2 = 0.5.  FLOW2D_ERR_INVALID_ARGUMENT for a null plane, a zero size, a negative or
+ * non-finite alpha, or a `mask` whose bytes [mask, mask + height * pitch_bytes) -- over every instance of a batch -- overlap
+ * those of any input plane.  Honours flow2d_context_set_batch.  Pitch at least 4 floats (the bilinear sample reads column pairs;
+ * at width 1 the second column is row padding and never selected). */
+FLOW2D_API int flow2d_consistency_2d(flow2d_context* ctx, const float* flow_u, const float* flow_v, const float* back_u,
+                                     const float* back_v, size_t width, size_t height, size_t pitch_bytes, float alpha1,
+                                     float alpha2, float* mask);
 
 /* The flow of the previous pyramid level resampled to this level's size (the bits of flow2d_resample_xy_pair into out_u / out_v)
  * and frame_1 warped by it (the bits of flow2d_registration_2d into `output`) in one launch: replaces the
