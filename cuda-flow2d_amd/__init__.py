@@ -61,6 +61,63 @@ class TimingRecord(C.Structure):
     ]
 
 
+class FlowErrorClass(C.Structure):
+    """flow2d_flow_error_class of include/flow2d_c_abi.h: one class (all / noc / occ) of a flow2d_flow_error_2d record."""
+    _fields_ = [
+        ("count", C.c_ulonglong), ("above", C.c_ulonglong * 4), ("fl", C.c_ulonglong),
+        ("sum_epe", C.c_double), ("sum_epe_sq", C.c_double), ("sum_ae", C.c_double), ("max_epe", C.c_double),
+    ]
+
+
+class FlowErrorStats(C.Structure):
+    """flow2d_flow_error_stats: the record flow2d_flow_error_2d writes per instance."""
+    _fields_ = [
+        ("all", FlowErrorClass), ("noc", FlowErrorClass), ("occ", FlowErrorClass),
+        ("invalid_ground_truth", C.c_ulonglong), ("nonfinite_estimate", C.c_ulonglong),
+    ]
+
+
+FLOW_ERROR_STATS_BYTES = 256  # FLOW2D_FLOW_ERROR_STATS_BYTES, checked by a static_assert in the header
+assert C.sizeof(FlowErrorStats) == FLOW_ERROR_STATS_BYTES
+FLOW_ERROR_CLASSES = ("all", "noc", "occ")
+
+
+def _stats_dict(rec):
+    """A FlowErrorStats as plain Python: {"all" / "noc" / "occ": {count, above (list of 4), fl, sum_epe, sum_epe_sq, sum_ae,
+    max_epe}, "invalid_ground_truth", "nonfinite_estimate"}."""
+    out = {}
+    for name in FLOW_ERROR_CLASSES:
+        c = getattr(rec, name)
+        out[name] = {"count": c.count, "above": list(c.above), "fl": c.fl, "sum_epe": c.sum_epe, "sum_epe_sq": c.sum_epe_sq,
+                     "sum_ae": c.sum_ae, "max_epe": c.max_epe}
+    out["invalid_ground_truth"] = rec.invalid_ground_truth
+    out["nonfinite_estimate"] = rec.nonfinite_estimate
+    return out
+
+
+def flow_error_metrics(record):
+    """The metrics of a flow_error / evaluate_flow record, as the CLI prints them after --ground-truth (FlowErrorJson): per
+    class count, epe (mean), rmse, ae (mean, degrees), r0.5 / r1 / r2 / r3 / fl (fractions) and max_epe; None for the means
+    and fractions of an empty class.  Same double operations as the C++ side."""
+    out = {}
+    for name in FLOW_ERROR_CLASSES:
+        c = record[name]
+        n = float(c["count"])
+        empty = c["count"] == 0
+        m = {"count": c["count"]}
+        m["epe"] = None if empty else c["sum_epe"] / n
+        m["rmse"] = None if empty else float(np.sqrt(c["sum_epe_sq"] / n))
+        m["ae"] = None if empty else c["sum_ae"] / n
+        for key, k in (("r0.5", 0), ("r1", 1), ("r2", 2), ("r3", 3)):
+            m[key] = None if empty else c["above"][k] / n
+        m["fl"] = None if empty else c["fl"] / n
+        m["max_epe"] = c["max_epe"]
+        out[name] = m
+    out["invalid_ground_truth"] = record["invalid_ground_truth"]
+    out["nonfinite_estimate"] = record["nonfinite_estimate"]
+    return out
+
+
 _hip = None
 
 
@@ -145,6 +202,10 @@ def hip_lib():
         L.flow2d_timing_launch_filter.argtypes = [vp, sz, sz]
         if hasattr(L, "flow2d_consistency_2d"):  # (absent from libraries of earlier rounds loaded for an A/B)
             L.flow2d_consistency_2d.argtypes = [vp, vp, vp, vp, vp, sz, sz, sz, f, f, vp]
+        if hasattr(L, "flow2d_flow_error_2d"):  # (absent from libraries of earlier rounds loaded for an A/B)
+            L.flow2d_flow_error_workspace_bytes.restype = sz
+            L.flow2d_flow_error_workspace_bytes.argtypes = [sz, sz, sz]
+            L.flow2d_flow_error_2d.argtypes = [vp] * 6 + [sz, sz, sz, vp, vp, vp, vp, sz]
         L.flow2d_timing_count.argtypes = [vp, C.POINTER(sz)]
         L.flow2d_timing_get.argtypes = [vp, sz, C.POINTER(TimingRecord)]
         L.flow2d_timing_reset.argtypes = [vp]
@@ -361,6 +422,29 @@ class Context:
         _check(hip_lib().flow2d_consistency_2d(self.handle, u.ptr, v.ptr, bu.ptr, bv.ptr, w, h, u.pitch, alpha1, alpha2,
                                                out.ptr), "flow2d_consistency_2d")
 
+    def flow_error(self, u, v, gt_u, gt_v, w, h, occlusion=None, epe=None, ae=None, instances=1):
+        """Error of the flow (u, v) against ground truth (gt_u, gt_v), all planes of one pitch (flow2d_flow_error_2d): returns
+        one record per lock-step instance (`instances` = the count of flow2d_context_set_batch) as dicts (see _stats_dict);
+        `occlusion` (non-zero or NaN = occluded) splits noc / occ; `epe` / `ae` planes get the per-pixel errors.  The device
+        planes stay where they are: only the records are downloaded (synchronises)."""
+        L = hip_lib()
+        need = L.flow2d_flow_error_workspace_bytes(w, h, instances)
+        cached = getattr(self, "_flow_error_buffers", None)
+        if cached is None or cached[0] < need or cached[1] < instances:
+            if cached is not None:
+                for q in cached[2:]:
+                    q.free()
+                    self._planes.remove(q)
+            self._flow_error_buffers = cached = (need, instances, self.plane(max(need // 4, 4), 1),
+                                                 self.plane(instances * FLOW_ERROR_STATS_BYTES // 4, 1))
+        ws, stats = cached[2], cached[3]
+        _check(L.flow2d_flow_error_2d(self.handle, u.ptr, v.ptr, gt_u.ptr, gt_v.ptr, occlusion.ptr if occlusion else None, w, h,
+                                      u.pitch, epe.ptr if epe else None, ae.ptr if ae else None, stats.ptr, ws.ptr, cached[0]),
+               "flow2d_flow_error_2d")
+        raw = stats.download(instances * FLOW_ERROR_STATS_BYTES // 4, 1)
+        recs = (FlowErrorStats * instances).from_buffer_copy(raw.tobytes())
+        return [_stats_dict(r) for r in recs]
+
     def resample_x(self, src, dst, out_w, out_h, in_w):
         _check(hip_lib().flow2d_resample_x(self.handle, src.ptr, dst.ptr, out_w, out_h, in_w, src.pitch),
                "flow2d_resample_x")
@@ -513,6 +597,9 @@ def host_lib():
                                                              fp]
         L.flow2d_host_compute_flow_bidirectional_device.argtypes = [vp, C.POINTER(vp), sz] + [C.POINTER(vp)] * 6 + [
             C.POINTER(HostParams), f, f]
+        L.flow2d_host_read_flo.argtypes = [C.c_char_p, C.POINTER(sz), C.POINTER(sz), fp, fp, sz]
+        L.flow2d_host_write_flo.argtypes = [fp, fp, sz, sz, C.c_char_p]
+        L.flow2d_host_flow_error.argtypes = [fp] * 5 + [sz, sz, fp, fp, C.POINTER(FlowErrorStats)]
         L.flow2d_host_level_timings.restype = sz
         L.flow2d_host_level_timings.argtypes = [vp, fp, sz]
         L.flow2d_host_reset_timings.argtypes = [vp]
@@ -780,6 +867,51 @@ def read_raw(path, width, height, u8):
 def write_raw(image, path, u8):
     a = np.ascontiguousarray(image, np.float32)
     return host_lib().flow2d_host_write_raw(_fptr(a), a.shape[1], a.shape[0], int(u8), path.encode()) == 0
+
+
+def read_flo(path):
+    """A Middlebury .flo file (IOUtils::ReadFlowFLO) -> (u, v) float32 arrays.  ValueError when the file is refused."""
+    L = host_lib()
+    w, h = C.c_size_t(), C.c_size_t()
+    if L.flow2d_host_read_flo(os.fsencode(path), C.byref(w), C.byref(h), None, None, 0):
+        raise ValueError("%s: not a readable .flo file (bad magic, size or truncated)" % path)
+    u = np.empty((h.value, w.value), np.float32)
+    v = np.empty_like(u)
+    if L.flow2d_host_read_flo(os.fsencode(path), C.byref(w), C.byref(h), _fptr(u), _fptr(v), u.size):
+        raise ValueError("%s: changed while being read" % path)
+    return u, v
+
+
+def write_flo(path, u, v):
+    """(u, v) as a Middlebury .flo file (IOUtils::WriteFlowFLO).  OSError when it cannot be written."""
+    u = np.ascontiguousarray(u, np.float32)
+    v = np.ascontiguousarray(v, np.float32)
+    if u.ndim != 2 or u.shape != v.shape:
+        raise ValueError("u and v must be 2-D arrays of one shape")
+    if host_lib().flow2d_host_write_flo(_fptr(u), _fptr(v), u.shape[1], u.shape[0], os.fsencode(path)):
+        raise OSError("cannot write %s" % path)
+
+
+def evaluate_flow(u, v, gt_u, gt_v, occlusion=None, planes=False, device=0):
+    """EvaluateFlow of the host layer on host arrays: uploads them, runs flow2d_flow_error_2d on the process-wide context
+    (created on `device` when there is none) and returns the record as a dict (see Context.flow_error); planes=True also
+    returns the per-pixel (epe, ae) arrays: (record, epe, ae)."""
+    L = host_lib()
+    arrays = [np.ascontiguousarray(a, np.float32) for a in (u, v, gt_u, gt_v)]
+    occ = None if occlusion is None else np.ascontiguousarray(occlusion, np.float32)
+    if arrays[0].ndim != 2 or any(a.shape != arrays[0].shape for a in arrays + ([occ] if occ is not None else [])):
+        raise ValueError("every plane must be a 2-D array of one shape")
+    if not L.flow2d_host_context() and L.flow2d_host_init_device(device) != 0:
+        raise Flow2DError(2, "InitDeviceContext")
+    h, w = arrays[0].shape
+    epe = np.empty((h, w), np.float32) if planes else None
+    ae = np.empty((h, w), np.float32) if planes else None
+    rec = FlowErrorStats()
+    rc = L.flow2d_host_flow_error(*[_fptr(a) for a in arrays], None if occ is None else _fptr(occ), w, h,
+                                  None if epe is None else _fptr(epe), None if ae is None else _fptr(ae), C.byref(rec))
+    if rc:
+        raise Flow2DError(1 if rc == 1 else 3, "EvaluateFlow")
+    return (_stats_dict(rec), epe, ae) if planes else _stats_dict(rec)
 
 
 def max_warp_level(width, height, scale):

@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "device_utils.h"
+#include "flow_evaluation.h"
 #include "io_utils.h"
 #include "optical_flow_2d.h"
 #include "optical_flow_batch_2d.h"
@@ -388,6 +389,57 @@ HOST_API int flow2d_host_write_raw(const float* data, size_t width, size_t heigh
     Data2D d(width, height);
     std::memcpy(d.DataPtr(), data, width * height * sizeof(float));
     return (u8 ? d.WriteRAWToFileU8(path) : d.WriteRAWToFileF32(path)) ? 0 : 1;
+}
+
+// IOUtils::ReadFlowFLO: *width / *height get the file's size; the flow goes to u / v (width * height floats each) when both are
+// given and capacity (in floats) holds it -- call with u = v = NULL first to learn the size.  0 on success, 1 when the file is
+// refused, 2 when the buffers are too small.
+HOST_API int flow2d_host_read_flo(const char* path, size_t* width, size_t* height, float* u, float* v, size_t capacity)
+{
+    if (!path || !width || !height) return 1;
+    Data2D du, dv;
+    if (!IOUtils::ReadFlowFLO(path, du, dv)) return 1;
+    *width = du.Width();
+    *height = du.Height();
+    const size_t n = du.Width() * du.Height();
+    if (!u && !v) return 0;
+    if (!u || !v || capacity < n) return 2;
+    std::memcpy(u, du.DataPtr(), n * sizeof(float));
+    std::memcpy(v, dv.DataPtr(), n * sizeof(float));
+    return 0;
+}
+
+// IOUtils::WriteFlowFLO of tight width x height planes.  0 on success.
+HOST_API int flow2d_host_write_flo(const float* u, const float* v, size_t width, size_t height, const char* path)
+{
+    if (!u || !v || !path || width == 0 || height == 0) return 1;
+    Data2D du(width, height), dv(width, height);
+    std::memcpy(du.DataPtr(), u, width * height * sizeof(float));
+    std::memcpy(dv.DataPtr(), v, width * height * sizeof(float));
+    return IOUtils::WriteFlowFLO(du, dv, path) ? 0 : 1;
+}
+
+// EvaluateFlow on tight host planes (occlusion, epe and ae may be NULL) on the process-wide context: the record into *out.
+// 0 on success, 1 for a bad argument, 2 when there is no context or a device call failed.
+HOST_API int flow2d_host_flow_error(const float* u, const float* v, const float* gt_u, const float* gt_v, const float* occlusion,
+                                    size_t width, size_t height, float* epe, float* ae, flow2d_flow_error_stats* out)
+{
+    if (!u || !v || !gt_u || !gt_v || !out || width == 0 || height == 0) return 1;
+    const size_t n = width * height;
+    Data2D planes[5];
+    const float* sources[5] = {u, v, gt_u, gt_v, occlusion};
+    for (int i = 0; i < 5; ++i) {
+        if (!sources[i]) continue;
+        planes[i] = Data2D(width, height);
+        std::memcpy(planes[i].DataPtr(), sources[i], n * sizeof(float));
+    }
+    Data2D de, da;
+    if (!EvaluateFlow(planes[0], planes[1], planes[2], planes[3], occlusion ? &planes[4] : nullptr, *out, epe ? &de : nullptr,
+                      ae ? &da : nullptr))
+        return 2;
+    if (epe) std::memcpy(epe, de.DataPtr(), n * sizeof(float));
+    if (ae) std::memcpy(ae, da.DataPtr(), n * sizeof(float));
+    return 0;
 }
 
 HOST_API int flow2d_host_write_outputs(const float* u, const float* v, size_t width, size_t height,

@@ -1,6 +1,7 @@
 #include "io_utils.h"
 
 #include <cmath>
+#include <cstdint>
 #include <cstdlib>
 #include <fstream>
 #include <iostream>
@@ -59,6 +60,57 @@ void WriteMaskToImagePGM(Data2D& mask, std::string fileName)
         for (int x = 0; x < nx; ++x) row[x] = mask.Data(x, y) != 0.0f ? 255 : 0;
         out.write(reinterpret_cast<const char*>(row.data()), row.size());
     }
+}
+
+namespace {
+constexpr float kFloMagic = 202021.25f;
+}
+
+bool ReadFlowFLO(const std::string& fileName, Data2D& u, Data2D& v)
+{
+    std::ifstream in(fileName.c_str(), std::ios::in | std::ios::binary);
+    if (!in.is_open()) return false;
+    in.seekg(0, std::ios::end);
+    const std::streamoff file_bytes = in.tellg();
+    in.seekg(0, std::ios::beg);
+    float magic = 0.f;
+    int32_t header[2] = {0, 0};
+    if (file_bytes < 12 || !in.read(reinterpret_cast<char*>(&magic), 4) || !in.read(reinterpret_cast<char*>(header), 8))
+        return false;
+    if (magic != kFloMagic || header[0] <= 0 || header[1] <= 0) return false;
+    const size_t nx = static_cast<size_t>(header[0]), ny = static_cast<size_t>(header[1]);
+    if (nx > kFloMaxSide || ny > kFloMaxSide || nx * ny > kFloMaxPixels) return false;
+    if (static_cast<size_t>(file_bytes) - 12 < nx * ny * 8) return false;  // truncated: refused before reading a sample
+    std::vector<float> pairs(nx * ny * 2);
+    if (!in.read(reinterpret_cast<char*>(pairs.data()), static_cast<std::streamsize>(pairs.size() * sizeof(float)))) return false;
+    Data2D du(nx, ny), dv(nx, ny);
+    for (size_t i = 0; i < nx * ny; ++i) {
+        du.DataPtr()[i] = pairs[2 * i];
+        dv.DataPtr()[i] = pairs[2 * i + 1];
+    }
+    u = std::move(du);
+    v = std::move(dv);
+    return true;
+}
+
+bool WriteFlowFLO(Data2D& u, Data2D& v, const std::string& fileName)
+{
+    if (u.Width() != v.Width() || u.Height() != v.Height() || u.Width() == 0 || u.Height() == 0 ||
+        u.Width() > kFloMaxSide || u.Height() > kFloMaxSide)
+        return false;
+    std::ofstream out(fileName.c_str(), std::ios::out | std::ios::binary);
+    if (!out.is_open()) return false;
+    const int32_t header[2] = {static_cast<int32_t>(u.Width()), static_cast<int32_t>(u.Height())};
+    out.write(reinterpret_cast<const char*>(&kFloMagic), 4);
+    out.write(reinterpret_cast<const char*>(header), 8);
+    const size_t n = u.Width() * u.Height();
+    std::vector<float> pairs(2 * n);
+    for (size_t i = 0; i < n; ++i) {
+        pairs[2 * i] = u.DataPtr()[i];
+        pairs[2 * i + 1] = v.DataPtr()[i];
+    }
+    out.write(reinterpret_cast<const char*>(pairs.data()), static_cast<std::streamsize>(pairs.size() * sizeof(float)));
+    return static_cast<bool>(out.flush());
 }
 
 // Colour wheel of io_utils.cpp:140-225 as a table: the half angle phi/2 in [0, pi] runs through the key

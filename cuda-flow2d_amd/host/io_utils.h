@@ -24,6 +24,16 @@ void WriteMagnitudeToFileF32(Data2D& u, Data2D& v, std::string fileName);
 // No reference counterpart; exit(255) when the file cannot be opened, like the writers above.
 void WriteMaskToImagePGM(Data2D& mask, std::string fileName);
 
+// Middlebury .flo (Baker et al., IJCV 2011): the float magic 202021.25 ("PIEH"), int32 width, int32 height, then width * height
+// interleaved little-endian float32 (u, v) pairs in row-major order.  No reference counterpart.  ReadFlowFLO refuses -- false,
+// u and v left as they were -- a file it cannot open, a bad magic, a size outside 1 .. kFloMaxSide per side or beyond
+// kFloMaxPixels in all, and a file shorter than its header says (checked before any sample is read); trailing bytes are
+// ignored.  WriteFlowFLO returns false when the file cannot be written or u and v differ in size.
+constexpr size_t kFloMaxSide = size_t(1) << 20;
+constexpr size_t kFloMaxPixels = size_t(1) << 28;
+bool ReadFlowFLO(const std::string& fileName, Data2D& u, Data2D& v);
+bool WriteFlowFLO(Data2D& u, Data2D& v, const std::string& fileName);
+
 // Direction -> hue, magnitude (clipped at 1) -> brightness.
 RGBColor ConvertToRGB(float x, float y);
 

@@ -12,6 +12,11 @@
 // --backward writes, besides the unchanged forward files, <prefix>flow-u-backward-W-H.raw, <prefix>flow-v-backward-W-H.raw
 // (the flow frame 2 -> frame 1), <prefix>occlusion-W-H.raw (frame 1's grid) and <prefix>occlusion-backward-W-H.raw (frame 2's
 // grid) as F32 0 / 1 (1 = occluded or leaving the frame), and <prefix>occlusion.pgm (P5, 255 where frame 1 is occluded).
+// --flo also writes the flow as Middlebury .flo: <prefix>flow.flo, and <prefix>flow-backward.flo with --backward.
+// --ground-truth FILE.flo loads the true flow of frame 1 -> frame 2 before computing (exit code 2 when it is missing, malformed
+// or not of the frames' size) and after the run prints one line "Flow error: {json}": the flow2d_flow_error_2d metrics of the
+// forward flow (FlowErrorJson, flow_evaluation.h) over all pixels and split into noc / occ by the forward occlusion mask of
+// --backward (without it every pixel is noc).  Neither option changes any other file or output.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -20,6 +25,7 @@
 #include <vector>
 
 #include "device_utils.h"
+#include "flow_evaluation.h"
 #include "io_utils.h"
 #include "optical_flow_2d.h"
 #include "settings.h"
@@ -45,7 +51,8 @@ static bool LoadFrame(Data2D& frame, const std::string& input_path, const std::s
 int main(int argc, char** argv)
 {
     // optional flags first (supersets), then the reference's positional forms
-    bool force_u8 = false, verbose = false, backward = false;
+    bool force_u8 = false, verbose = false, backward = false, write_flo = false;
+    std::string ground_truth_file;
     int device = 0;
     float sor_omega = 0.f;
     DataConstancy data_constancy = DataConstancy::Grey;
@@ -57,6 +64,8 @@ int main(int argc, char** argv)
         else if (!std::strcmp(argv[i], "--log-derivatives")) data_constancy = DataConstancy::LogDerivatives;
         else if (!std::strcmp(argv[i], "--verbose")) verbose = true;
         else if (!std::strcmp(argv[i], "--backward")) backward = true;
+        else if (!std::strcmp(argv[i], "--flo")) write_flo = true;
+        else if (!std::strcmp(argv[i], "--ground-truth") && i + 1 < argc) ground_truth_file = argv[++i];
         else if (!std::strcmp(argv[i], "--device") && i + 1 < argc) device = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--sor") && i + 1 < argc) sor_omega = static_cast<float>(std::atof(argv[++i]));
         else args.push_back(argv[i]);
@@ -140,6 +149,18 @@ int main(int argc, char** argv)
         !LoadFrame(frame_1, input_path, file_name2, u8, width, height)) {
         return 2;
     }
+    Data2D gt_u, gt_v;
+    if (!ground_truth_file.empty()) {
+        if (!IOUtils::ReadFlowFLO(ground_truth_file, gt_u, gt_v)) {
+            std::printf("Cannot read ground truth '%s' (a Middlebury .flo file).\n", ground_truth_file.c_str());
+            return 2;
+        }
+        if (gt_u.Width() != width || gt_u.Height() != height) {
+            std::printf("Ground truth '%s' is %zu x %zu, the frames %zu x %zu.\n", ground_truth_file.c_str(), gt_u.Width(),
+                        gt_u.Height(), width, height);
+            return 2;
+        }
+    }
 
     OpticalFlow2D optical_flow;
     optical_flow.silent = !verbose;
@@ -186,6 +207,23 @@ int main(int argc, char** argv)
             occlusion_0.WriteRAWToFileF32((output_path + counter + "occlusion" + suffix).c_str());
             occlusion_1.WriteRAWToFileF32((output_path + counter + "occlusion-backward" + suffix).c_str());
             IOUtils::WriteMaskToImagePGM(occlusion_0, output_path + counter + "occlusion.pgm");
+        }
+        if (write_flo) {
+            bool ok = IOUtils::WriteFlowFLO(flow_u, flow_v, output_path + counter + "flow.flo");
+            if (backward) ok = ok && IOUtils::WriteFlowFLO(back_u, back_v, output_path + counter + "flow-backward.flo");
+            if (!ok) {
+                std::cerr << "Error: cannot save file " << std::endl;
+                std::exit(255);
+            }
+        }
+        if (!ground_truth_file.empty()) {
+            flow2d_flow_error_stats stats;
+            if (!EvaluateFlow(flow_u, flow_v, gt_u, gt_v, backward ? &occlusion_0 : nullptr, stats)) {
+                optical_flow.Destroy();
+                DestroyDeviceContext();
+                return 4;
+            }
+            std::printf("Flow error: %s\n", FlowErrorJson(stats).c_str());
         }
         optical_flow.Destroy();
     }

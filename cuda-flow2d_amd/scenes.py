@@ -1,0 +1,113 @@
+"""Seeded frame pairs with analytic ground-truth flow, for accuracy measurements (tools/accuracy_table.py, the flow-error tests).
+
+Every frame is sampled exactly -- in double, stored float32 -- from a smooth analytic texture, a sum of sinusoids like
+oracle.synthetic_pair's, at the inverse-mapped coordinates.  With the project's convention (flow2d_consistency_2d) the
+ground truth w of frame 0 satisfies  I1(x + w(x)) = I0(x)  at every pixel x that is not occluded.
+
+Scenes (make_scene(name, width, height, seed)):
+  translation  a sub-pixel translation
+  rotation     a rotation about the centre
+  zoom         a zoom about the centre
+  affine       a general affine motion
+  two_layer    a textured square moving over a static textured background, with the exact occlusion map of frame 0: the
+               background pixels the square covers in frame 1, and the square's pixels that leave the frame
+
+Each Scene carries frame_0, frame_1, gt_u, gt_v (float32, height x width), occlusion (float32 0 / 1, or None where the scene
+has no occlusion) and frame_1_at(x, y): the analytic frame 1 at any real coordinates (double), for checking the ground truth.
+Pure numpy: no device, no library.
+"""
+import numpy as np
+
+SCENES = ("translation", "rotation", "zoom", "affine", "two_layer")
+
+
+class Texture:
+    """128 + sum of three sinusoids with seeded phases and orientations; smooth, with gradients in every direction."""
+
+    def __init__(self, rng, amplitude=(55.0, 30.0, 18.0), periods=(61.0, 23.7, 37.3)):
+        self.terms = []
+        for a, p in zip(amplitude, periods):
+            theta = rng.uniform(0, np.pi)
+            self.terms.append((a, 2 * np.pi * np.cos(theta) / p, 2 * np.pi * np.sin(theta) / p, rng.uniform(0, 2 * np.pi)))
+
+    def __call__(self, x, y):
+        out = np.full(np.broadcast(x, y).shape, 128.0)
+        for a, kx, ky, phase in self.terms:
+            out += a * np.sin(kx * x + ky * y + phase)
+        return out
+
+
+class Scene:
+    def __init__(self, name, frame_0, frame_1, gt_u, gt_v, occlusion, frame_1_at):
+        self.name = name
+        self.frame_0, self.frame_1 = frame_0, frame_1
+        self.gt_u, self.gt_v = gt_u, gt_v
+        self.occlusion = occlusion
+        self.frame_1_at = frame_1_at
+
+    @property
+    def shape(self):
+        return self.frame_0.shape
+
+
+def _affine_scene(name, width, height, texture, a, t):
+    """W(x) = A (x - c) + c + t about the centre c; frame 1 = texture at W^-1, ground truth W(x) - x."""
+    a = np.asarray(a, np.float64)
+    t = np.asarray(t, np.float64)
+    c = np.array([(width - 1) / 2.0, (height - 1) / 2.0])
+    inv = np.linalg.inv(a)
+    ys, xs = np.mgrid[0:height, 0:width].astype(np.float64)
+
+    def frame_1_at(x, y):
+        px, py = np.asarray(x, np.float64) - c[0] - t[0], np.asarray(y, np.float64) - c[1] - t[1]
+        return texture(inv[0, 0] * px + inv[0, 1] * py + c[0], inv[1, 0] * px + inv[1, 1] * py + c[1])
+
+    dx, dy = xs - c[0], ys - c[1]
+    gt_u = (a[0, 0] - 1) * dx + a[0, 1] * dy + t[0]
+    gt_v = a[1, 0] * dx + (a[1, 1] - 1) * dy + t[1]
+    return Scene(name, texture(xs, ys).astype(np.float32), frame_1_at(xs, ys).astype(np.float32), gt_u.astype(np.float32),
+                 gt_v.astype(np.float32), None, frame_1_at)
+
+
+def _two_layer_scene(width, height, background, square, t):
+    """A side-n square at (x0, y0) in frame 0 moves by t (dyadic: x + t is exact in float32) over a static background."""
+    n = max(4, min(width, height) // 4)
+    x0, y0 = (width - n) // 2 - n // 4, (height - n) // 2
+    tx, ty = t
+
+    def in_square(x, y, sx, sy):
+        return (x >= x0 + sx) & (x < x0 + n + sx) & (y >= y0 + sy) & (y < y0 + n + sy)
+
+    def frame_1_at(x, y):
+        x, y = np.asarray(x, np.float64), np.asarray(y, np.float64)
+        return np.where(in_square(x, y, tx, ty), square(x - tx, y - ty), background(x, y))
+
+    ys, xs = np.mgrid[0:height, 0:width].astype(np.float64)
+    moving = in_square(xs, ys, 0.0, 0.0)
+    frame_0 = np.where(moving, square(xs, ys), background(xs, ys))
+    gt_u = np.where(moving, tx, 0.0)
+    gt_v = np.where(moving, ty, 0.0)
+    covered = ~moving & in_square(xs, ys, tx, ty)
+    leaving = moving & ((xs + tx < 0) | (xs + tx > width - 1) | (ys + ty < 0) | (ys + ty > height - 1))
+    occlusion = (covered | leaving).astype(np.float32)
+    return Scene("two_layer", frame_0.astype(np.float32), frame_1_at(xs, ys).astype(np.float32), gt_u.astype(np.float32),
+                 gt_v.astype(np.float32), occlusion, frame_1_at)
+
+
+def make_scene(name, width=256, height=256, seed=0):
+    """The scene `name` (one of SCENES) at width x height; `seed` draws the textures."""
+    rng = np.random.default_rng(seed)
+    texture = Texture(rng)
+    if name == "translation":
+        return _affine_scene(name, width, height, texture, np.eye(2), (2.3, -1.4))
+    if name == "rotation":
+        phi = np.radians(3.0)
+        return _affine_scene(name, width, height, texture, [[np.cos(phi), -np.sin(phi)], [np.sin(phi), np.cos(phi)]], (0, 0))
+    if name == "zoom":
+        return _affine_scene(name, width, height, texture, 1.03 * np.eye(2), (0, 0))
+    if name == "affine":
+        return _affine_scene(name, width, height, texture, [[1.02, 0.03], [-0.02, 0.985]], (1.25, -0.6))
+    if name == "two_layer":
+        square = Texture(rng, amplitude=(50.0, 35.0, 20.0), periods=(29.0, 13.1, 19.7))
+        return _two_layer_scene(width, height, texture, square, (4.5, -2.25))
+    raise ValueError("unknown scene %r (one of %s)" % (name, ", ".join(SCENES)))

@@ -34,7 +34,8 @@ extern "C" {
 #define FLOW2D_API __attribute__((visibility("default")))
 
 /* Additions that leave every existing entry as it was keep the version: flow2d_consistency_2d (forward-backward occlusion
- * masks) was added under 1. */
+ * masks) and flow2d_flow_error_2d / flow2d_flow_error_workspace_bytes (error statistics against ground truth) were added
+ * under 1. */
 #define FLOW2D_ABI_VERSION 1
 
 typedef enum flow2d_status {
@@ -219,6 +220,64 @@ FLOW2D_API int flow2d_registration_2d(flow2d_context* ctx, const float* frame_0,
 FLOW2D_API int flow2d_consistency_2d(flow2d_context* ctx, const float* flow_u, const float* flow_v, const float* back_u,
                                      const float* back_v, size_t width, size_t height, size_t pitch_bytes, float alpha1,
                                      float alpha2, float* mask);
+
+/* Error of a flow estimate against ground truth (Barron et al. 1994, Baker et al. 2011 -- Middlebury --, Menze & Geiger 2015 --
+ * KITTI --; no reference counterpart; added to ABI version 1 without changing any existing entry).
+ * For every pixel p, 0 <= x < width, 0 <= y < height, with u = flow_u[p], v = flow_v[p], gu = gt_u[p], gv = gt_v[p], all fp32:
+ *   valid ground truth      |gu| <= 1e9 and |gv| <= 1e9 (finite; larger values are Middlebury's UNKNOWN_FLOW_THRESH)
+ *                           otherwise counted in invalid_ground_truth and nothing else
+ *   non-finite estimate     u or v infinite or NaN at a valid pixel: counted in nonfinite_estimate and nothing else
+ *   du = u - gu, dv = v - gv, epe = sqrtf(du*du + dv*dv)                              (correctly rounded sqrtf)
+ *   cx = v - gv, cy = gu - u, cz = u*gv - v*gu, cross = sqrtf((cx*cx + cy*cy) + cz*cz), dot = (u*gu + v*gv) + 1
+ *   ae = atan2f(cross, dot) * 57.29577951308232f      (degrees between (u, v, 1) and (gu, gv, 1): the atan2 form, which keeps
+ *                                                     its precision at small angles; within 1e-4 degrees of the exact angle
+ *                                                     for |flow| <= 1e3; meaningless -- 90 degrees or NaN -- once the
+ *                                                     products overflow, for estimates beyond ~1e19)
+ *   gmag = sqrtf(gu*gu + gv*gv)
+ *   class                   occ where occlusion != NULL and occlusion[p] != 0 (NaN included: what flow2d_consistency_2d
+ *                           writes, and what a ground-truth occlusion map holds), noc elsewhere; all = noc + occ
+ * Per class: count; above[k] = pixels with epe > 0.5, 1, 2, 3 (Middlebury R0.5 / R1 / R2 and the 3-px rate); fl = pixels with
+ * epe > 3 and epe > 0.05f * gmag (KITTI Fl); sum_epe, sum_epe_sq (= sum of (double)epe * (double)epe) and sum_ae in double;
+ * max_epe (0 for an empty class).  An infinite epe (a finite estimate whose du*du overflows) enters the sums as inf.
+ * Outputs: `epe` / `ae` (either may be NULL) get the per-pixel values, NaN where the pixel is invalid or the estimate
+ * non-finite; stats[b] (DEVICE memory) gets the record of instance b of a lock-step batch.
+ * Deterministic: counts are exact and the double sums run in a fixed order that depends only on (width, height), so repeated
+ * calls and an instance of a batch alone or in its group give the same bytes.  No allocation, no synchronisation: two launches
+ * on the context's stream (graph-capturable) into the caller's `workspace`, which holds at least
+ * flow2d_flow_error_workspace_bytes(width, height, instances) bytes (16-byte aligned; instances = the batch count).
+ * FLOW2D_ERR_INVALID_ARGUMENT for a null required plane, a zero size, a bad pitch, a null or misaligned `stats` or
+ * `workspace`, a workspace too small, or an `epe` / `ae` whose bytes [p, p + height * pitch_bytes) -- over every instance of a
+ * batch -- overlap those of any input plane or of each other, or those of `stats` or the workspace. */
+typedef struct flow2d_flow_error_class {
+    unsigned long long count;
+    unsigned long long above[4]; /* epe > 0.5, 1, 2, 3 */
+    unsigned long long fl;       /* epe > 3 and epe > 0.05 |gt| */
+    double sum_epe;
+    double sum_epe_sq;
+    double sum_ae;               /* degrees */
+    double max_epe;
+} flow2d_flow_error_class;
+
+typedef struct flow2d_flow_error_stats {
+    flow2d_flow_error_class all, noc, occ;
+    unsigned long long invalid_ground_truth;
+    unsigned long long nonfinite_estimate;
+} flow2d_flow_error_stats;
+
+#define FLOW2D_FLOW_ERROR_STATS_BYTES 256
+#ifdef __cplusplus
+static_assert(sizeof(flow2d_flow_error_stats) == FLOW2D_FLOW_ERROR_STATS_BYTES, "flow2d_flow_error_stats layout");
+#else
+_Static_assert(sizeof(flow2d_flow_error_stats) == FLOW2D_FLOW_ERROR_STATS_BYTES, "flow2d_flow_error_stats layout");
+#endif
+
+/* Workspace bytes flow2d_flow_error_2d needs for `instances` lock-step instances of a width x height pair (0 for a zero size).
+ * Host logic only, needs no device. */
+FLOW2D_API size_t flow2d_flow_error_workspace_bytes(size_t width, size_t height, size_t instances);
+FLOW2D_API int flow2d_flow_error_2d(flow2d_context* ctx, const float* flow_u, const float* flow_v, const float* gt_u,
+                                    const float* gt_v, const float* occlusion, size_t width, size_t height, size_t pitch_bytes,
+                                    float* epe, float* ae, flow2d_flow_error_stats* stats, void* workspace,
+                                    size_t workspace_bytes);
 
 /* The flow of the previous pyramid level resampled to this level's size (the bits of flow2d_resample_xy_pair into out_u / out_v)
  * and frame_1 warped by it (the bits of flow2d_registration_2d into `output`) in one launch: replaces the
