@@ -202,6 +202,8 @@ def hip_lib():
         L.flow2d_timing_launch_filter.argtypes = [vp, sz, sz]
         if hasattr(L, "flow2d_consistency_2d"):  # (absent from libraries of earlier rounds loaded for an A/B)
             L.flow2d_consistency_2d.argtypes = [vp, vp, vp, vp, vp, sz, sz, sz, f, f, vp]
+        if hasattr(L, "flow2d_interpolate_2d"):  # (absent from libraries of earlier rounds loaded for an A/B)
+            L.flow2d_interpolate_2d.argtypes = [vp] * 9 + [sz, sz, sz, f, i, f, vp]
         if hasattr(L, "flow2d_flow_error_2d"):  # (absent from libraries of earlier rounds loaded for an A/B)
             L.flow2d_flow_error_workspace_bytes.restype = sz
             L.flow2d_flow_error_workspace_bytes.argtypes = [sz, sz, sz]
@@ -422,6 +424,13 @@ class Context:
         _check(hip_lib().flow2d_consistency_2d(self.handle, u.ptr, v.ptr, bu.ptr, bv.ptr, w, h, u.pitch, alpha1, alpha2,
                                                out.ptr), "flow2d_consistency_2d")
 
+    def interpolate(self, f0, f1, u, v, bu, bv, w, h, t, out, occ_0=None, occ_1=None, iterations=2, max_residual=0.5):
+        """The frame at time t (0 <= t <= 1) between f0 and f1 into `out`, from the flow (u, v) of f0 -> f1, the flow (bu, bv) of
+        f1 -> f0 and, when given, the occlusion masks occ_0 / occ_1 of the two frames (flow2d_interpolate_2d)."""
+        _check(hip_lib().flow2d_interpolate_2d(self.handle, f0.ptr, f1.ptr, u.ptr, v.ptr, bu.ptr, bv.ptr,
+                                               occ_0.ptr if occ_0 else None, occ_1.ptr if occ_1 else None, w, h, u.pitch, t,
+                                               iterations, max_residual, out.ptr), "flow2d_interpolate_2d")
+
     def flow_error(self, u, v, gt_u, gt_v, w, h, occlusion=None, epe=None, ae=None, instances=1):
         """Error of the flow (u, v) against ground truth (gt_u, gt_v), all planes of one pitch (flow2d_flow_error_2d): returns
         one record per lock-step instance (`instances` = the count of flow2d_context_set_batch) as dicts (see _stats_dict);
@@ -597,6 +606,9 @@ def host_lib():
                                                              fp]
         L.flow2d_host_compute_flow_bidirectional_device.argtypes = [vp, C.POINTER(vp), sz] + [C.POINTER(vp)] * 6 + [
             C.POINTER(HostParams), f, f]
+        L.flow2d_host_interpolate_frames.argtypes = [vp, fp, fp, fp, sz, fp, C.POINTER(HostParams), i, f, i, fp]
+        L.flow2d_host_interpolate_frames_device.argtypes = [vp, C.POINTER(vp), sz, fp, sz, C.POINTER(vp), C.POINTER(HostParams),
+                                                            i, f, i]
         L.flow2d_host_read_flo.argtypes = [C.c_char_p, C.POINTER(sz), C.POINTER(sz), fp, fp, sz]
         L.flow2d_host_write_flo.argtypes = [fp, fp, sz, sz, C.c_char_p]
         L.flow2d_host_flow_error.argtypes = [fp] * 5 + [sz, sz, fp, fp, C.POINTER(FlowErrorStats)]
@@ -744,6 +756,37 @@ class OpticalFlow:
             arr(dev_occ_bwd), C.byref(params), alpha1, alpha2)
         if rc:
             raise Flow2DError(rc, "OpticalFlow2D::ComputeFlowBidirectionalDevice")
+
+    def interpolate_frames(self, frame_0, frame_1, params, times, iterations=2, max_residual=0.5, masks=True):
+        """OpticalFlow2D::InterpolateFrames: host images in; the frames at `times` (each 0 <= t <= 1) between them out, from both
+        flows of compute_flow_bidirectional and, with masks, both occlusion masks (flow2d_interpolate_2d).
+        Returns (frames, device_ms): frames[j] is the frame at times[j]."""
+        f0 = np.ascontiguousarray(frame_0, np.float32)
+        f1 = np.ascontiguousarray(frame_1, np.float32)
+        assert f0.shape == (self.height, self.width) and f1.shape == f0.shape
+        ts = np.ascontiguousarray(np.atleast_1d(times), np.float32)
+        out = np.empty((len(ts),) + f0.shape, np.float32)
+        ms = C.c_float()
+        rc = host_lib().flow2d_host_interpolate_frames(self.handle, _fptr(f0), _fptr(f1), _fptr(ts), len(ts), _fptr(out),
+                                                       C.byref(params), int(iterations), max_residual, int(bool(masks)),
+                                                       C.byref(ms))
+        if rc:
+            raise Flow2DError(rc, "OpticalFlow2D::InterpolateFrames")
+        return out, ms.value
+
+    def interpolate_frames_device(self, dev_frames, times, dev_outputs, params, iterations=2, max_residual=0.5, masks=True):
+        """The frames at `times` between every consecutive pair of dev_frames: dev_outputs[k * len(times) + j] gets the frame at
+        times[j] between dev_frames[k] and dev_frames[k + 1].  Queued, not synchronised."""
+        n = len(dev_frames)
+        ts = np.ascontiguousarray(np.atleast_1d(times), np.float32)
+        if n < 2 or len(ts) < 1 or len(dev_outputs) != (n - 1) * len(ts):
+            raise ValueError("n frames and m times take (n - 1) * m output planes")
+        frames = (C.c_void_p * n)(*dev_frames)
+        outs = (C.c_void_p * len(dev_outputs))(*dev_outputs)
+        rc = host_lib().flow2d_host_interpolate_frames_device(self.handle, frames, n, _fptr(ts), len(ts), outs, C.byref(params),
+                                                              int(iterations), max_residual, int(bool(masks)))
+        if rc:
+            raise Flow2DError(rc, "OpticalFlow2D::InterpolateFramesDevice")
 
     def level_timings(self):
         """[(width, height, solve_ms, kernel_ms, kernel_launches, algorithmic_bytes_per_launch, algorithm)] per level;

@@ -183,6 +183,54 @@ HOST_API int flow2d_host_compute_flow_bidirectional(flow2d_host_flow* h, const f
     return h->flow.LastRunSucceeded() ? 0 : 2;
 }
 
+// OpticalFlow2D::InterpolateFrames on tight host images (width*height floats each): the time_count frames of `times` between
+// frame_0 and frame_1 into outputs (time_count * width * height floats, frame j at j * width * height).  use_masks = 0: without
+// occlusion masks.  0 on success, 1 for a null argument, 2 when the run delivered no frames.
+HOST_API int flow2d_host_interpolate_frames(flow2d_host_flow* h, const float* frame_0, const float* frame_1, const float* times,
+                                            size_t time_count, float* outputs, const flow2d_host_params* params, int iterations,
+                                            float max_residual, int use_masks, float* total_ms)
+{
+    if (!h || !frame_0 || !frame_1 || !times || !outputs || !params || time_count == 0) return 1;
+    const size_t n = h->width * h->height;
+    Data2D f0(h->width, h->height), f1(h->width, h->height);
+    std::memcpy(f0.DataPtr(), frame_0, n * sizeof(float));
+    std::memcpy(f1.DataPtr(), frame_1, n * sizeof(float));
+    std::vector<Data2D> out;
+    for (size_t j = 0; j < time_count; ++j) {
+        out.emplace_back(h->width, h->height);
+        for (size_t i = 0; i < n; ++i) out.back().DataPtr()[i] = -12345.f;  // poisoned, as in flow2d_host_compute_flow
+    }
+    flow2d_host_params p = *params;
+    OperationParameters bag;
+    FillBag(bag, p);
+    h->flow.InterpolateFrames(f0, f1, times, time_count, out.data(), iterations, max_residual, use_masks != 0, bag);
+    for (size_t j = 0; j < time_count; ++j) std::memcpy(outputs + j * n, out[j].DataPtr(), n * sizeof(float));
+    if (total_ms) *total_ms = h->flow.LastTotalMs();
+    return h->flow.LastRunSucceeded() ? 0 : 2;
+}
+
+// OpticalFlow2D::InterpolateFramesDevice: frame_count device frames, (frame_count - 1) * time_count device output planes (pair k,
+// time j at k * time_count + j).  Queued on the context's stream, no synchronisation.  0 on success.
+HOST_API int flow2d_host_interpolate_frames_device(flow2d_host_flow* h, void* const* dev_frames, size_t frame_count,
+                                                   const float* times, size_t time_count, void* const* dev_outputs,
+                                                   const flow2d_host_params* params, int iterations, float max_residual,
+                                                   int use_masks)
+{
+    if (!h || !params || !dev_frames || !dev_outputs || !times || frame_count < 2 || time_count == 0) return 1;
+    flow2d_host_params p = *params;
+    OperationParameters bag;
+    FillBag(bag, p);
+    h->flow.timing_mode = 0;
+    auto dp = [](void* q) { return static_cast<DevicePtr>(reinterpret_cast<uintptr_t>(q)); };
+    std::vector<DevicePtr> frames(frame_count), outputs((frame_count - 1) * time_count);
+    for (size_t k = 0; k < frames.size(); ++k) frames[k] = dp(dev_frames[k]);
+    for (size_t k = 0; k < outputs.size(); ++k) outputs[k] = dp(dev_outputs[k]);
+    return h->flow.InterpolateFramesDevice(frames.data(), frame_count, times, time_count, outputs.data(), iterations, max_residual,
+                                           use_masks != 0, bag)
+               ? 0
+               : 2;
+}
+
 // OpticalFlow2D::ComputeFlowBidirectionalDevice: frame_count device frames, frame_count - 1 forward and backward flow plane pairs,
 // occlusion planes optional (NULL arrays: no masks).  Queued on the context's stream, no synchronisation.  0 on success.
 HOST_API int flow2d_host_compute_flow_bidirectional_device(flow2d_host_flow* h, void* const* dev_frames, size_t frame_count,

@@ -4,7 +4,8 @@
 //   flow2d <settings.xml>
 //   flow2d <file1> <file2> <width> <height> <prefix> <outdir/> [<alpha> <sigma>]     (argc 7 / 9)
 //   flow2d <file1> <file2> <width> <height> <outdir/>                                (argc 6)
-// exit codes: 1 no device, 2 frame load failed, 3 settings error, 255 cannot write PPM/amp, 0 otherwise.
+// exit codes: 1 no device, 2 frame load failed, 3 settings error, 4 the flow computation failed, 5 bad option value (refused
+// before the device is opened), 255 cannot write PPM/amp, 0 otherwise.
 // Documented supersets: imageType="8-bit" selects the u8 reader; inputPath is tried as
 // a prefix before the bare file name; argc == 6 no longer dereferences argv[6]; no blocking getchar();
 // options --u8, --gradient, --log-derivatives, --device N, --verbose, --sor OMEGA (opt-in red-black SOR, no reference parity),
@@ -17,6 +18,10 @@
 // or not of the frames' size) and after the run prints one line "Flow error: {json}": the flow2d_flow_error_2d metrics of the
 // forward flow (FlowErrorJson, flow_evaluation.h) over all pixels and split into noc / occ by the forward occlusion mask of
 // --backward (without it every pixel is noc).  Neither option changes any other file or output.
+// --interpolate N (an integer >= 2) also writes the N - 1 frames between frame 1 and frame 2 at t = k / N, k = 1 .. N - 1, as
+// F32 <prefix>interp-<k>-of-<N>-W-H.raw: OpticalFlow2D::InterpolateFrames (flow2d_interpolate_2d) with both flows, both
+// occlusion masks, 2 fixed-point iterations and a residual bound of 0.5 px.  The forward files do not change; the backward
+// files are written only with --backward.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -52,6 +57,7 @@ int main(int argc, char** argv)
 {
     // optional flags first (supersets), then the reference's positional forms
     bool force_u8 = false, verbose = false, backward = false, write_flo = false;
+    int interpolate = 0;  // --interpolate N: N - 1 frames between the two (0: off)
     std::string ground_truth_file;
     int device = 0;
     float sor_omega = 0.f;
@@ -66,6 +72,16 @@ int main(int argc, char** argv)
         else if (!std::strcmp(argv[i], "--backward")) backward = true;
         else if (!std::strcmp(argv[i], "--flo")) write_flo = true;
         else if (!std::strcmp(argv[i], "--ground-truth") && i + 1 < argc) ground_truth_file = argv[++i];
+        else if (!std::strcmp(argv[i], "--interpolate")) {
+            char* end = nullptr;
+            const long n = (i + 1 < argc) ? std::strtol(argv[i + 1], &end, 10) : 0;
+            if (i + 1 >= argc || end == argv[i + 1] || *end != '\0' || n < 2 || n > 1000000) {
+                std::printf("--interpolate takes an integer N >= 2 (the frames at t = k / N, k = 1 .. N - 1).\n");
+                return 5;
+            }
+            interpolate = static_cast<int>(n);
+            ++i;
+        }
         else if (!std::strcmp(argv[i], "--device") && i + 1 < argc) device = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--sor") && i + 1 < argc) sor_omega = static_cast<float>(std::atof(argv[++i]));
         else args.push_back(argv[i]);
@@ -178,11 +194,24 @@ int main(int argc, char** argv)
         params.PushValuePtr("gaussian_sigma", &gaussian_sigma);
         if (sor_omega != 0.f) params.PushValuePtr("solver_sor_omega", &sor_omega);
         Data2D back_u, back_v, occlusion_0, occlusion_1;
-        if (backward) {
+        std::vector<Data2D> between;
+        std::vector<float> times;
+        if (interpolate) {
+            for (int k = 1; k < interpolate; ++k) {
+                between.emplace_back(width, height);
+                times.push_back(static_cast<float>(k) / static_cast<float>(interpolate));
+            }
+        }
+        if (backward || interpolate) {
             back_u = Data2D(width, height);
             back_v = Data2D(width, height);
             occlusion_0 = Data2D(width, height);
             occlusion_1 = Data2D(width, height);
+        }
+        if (interpolate) {
+            optical_flow.InterpolateFrames(frame_0, frame_1, times.data(), times.size(), between.data(), 2, 0.5f, true, params,
+                                           &flow_u, &flow_v, &back_u, &back_v, &occlusion_0, &occlusion_1);
+        } else if (backward) {
             optical_flow.ComputeFlowBidirectional(frame_0, frame_1, flow_u, flow_v, back_u, back_v, occlusion_0, occlusion_1,
                                                   params);
         } else {
@@ -208,6 +237,9 @@ int main(int argc, char** argv)
             occlusion_1.WriteRAWToFileF32((output_path + counter + "occlusion-backward" + suffix).c_str());
             IOUtils::WriteMaskToImagePGM(occlusion_0, output_path + counter + "occlusion.pgm");
         }
+        for (int k = 1; k < interpolate; ++k)
+            between[k - 1].WriteRAWToFileF32((output_path + counter + "interp-" + std::to_string(k) + "-of-" +
+                                              std::to_string(interpolate) + suffix).c_str());
         if (write_flo) {
             bool ok = IOUtils::WriteFlowFLO(flow_u, flow_v, output_path + counter + "flow.flo");
             if (backward) ok = ok && IOUtils::WriteFlowFLO(back_u, back_v, output_path + counter + "flow-backward.flo");

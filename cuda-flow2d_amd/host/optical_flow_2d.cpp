@@ -163,6 +163,12 @@ void OpticalFlow2D::Destroy()
             if (p) flow2d_plane_free(context_, AsPlane(p));
             p = 0;
         }
+        for (DevicePtr& p : interpolation_planes_) {
+            if (p) flow2d_plane_free(context_, AsPlane(p));
+            p = 0;
+        }
+        for (DevicePtr p : interpolation_outputs_) flow2d_plane_free(context_, AsPlane(p));
+        interpolation_outputs_.clear();
     }
     all_planes_.clear();
     free_planes_.clear();
@@ -388,6 +394,144 @@ void OpticalFlow2D::ComputeFlowBidirectional(Data2D& frame_0, Data2D& frame_1, D
               CopyData2DtoDevice(frame_1, d[1], H, dev_container_size_.pitch);
     ok = ok && ComputeFlowBidirectionalDevice(d, 2, d + 2, d + 3, d + 4, d + 5, d + 6, d + 7, params);
     for (int i = 2; ok && i < 8; ++i) ok = CopyData2DFromDevice(d[i], *images[i], H, dev_container_size_.pitch);
+    last_run_ok_ = ok;
+    flow2d_event_record(context_, ev_stop);
+    flow2d_event_synchronize(context_, ev_stop);  // the only host wait
+    flow2d_event_elapsed_ms(context_, ev_start, ev_stop, &last_total_ms_);
+    std::printf("Total GPU computation time: % 4.4fs\n", last_total_ms_ / 1000.);
+    flow2d_event_destroy(context_, ev_start);
+    flow2d_event_destroy(context_, ev_stop);
+}
+
+bool OpticalFlow2D::EnsurePlanes(DevicePtr* planes, size_t count)
+{
+    const size_t W = dev_container_size_.width, H = dev_container_size_.height;
+    for (size_t i = 0; i < count; ++i) {
+        if (planes[i]) continue;
+        void* plane = nullptr;
+        size_t pitch = 0;
+        if (CheckFlow2DError(flow2d_plane_alloc(context_, W, H, &plane, &pitch), "flow2d_plane_alloc")) return false;
+        planes[i] = static_cast<DevicePtr>(reinterpret_cast<uintptr_t>(plane));
+        if (pitch != dev_container_size_.pitch) {
+            std::printf("Error: '%s': plane pitch %zu differs from the container pitch %zu.\n", GetName(), pitch,
+                        dev_container_size_.pitch);
+            return false;
+        }
+    }
+    return true;
+}
+
+bool OpticalFlow2D::InterpolationArgsOk(const float* times, size_t time_count, int iterations, float max_residual)
+{
+    if (!times || time_count == 0) return false;
+    for (size_t j = 0; j < time_count; ++j)
+        if (!(std::isfinite(times[j]) && times[j] >= 0.f && times[j] <= 1.f)) {
+            std::printf("Error: '%s': interpolation time %g (0 <= t <= 1).\n", GetName(), times[j]);
+            return false;
+        }
+    if (iterations < 1 || iterations > 16 || !std::isfinite(max_residual) || max_residual < 0.f) {
+        std::printf("Error: '%s': interpolation iterations %d (1 .. 16) / max residual %g (finite, >= 0).\n", GetName(),
+                    iterations, max_residual);
+        return false;
+    }
+    return true;
+}
+
+bool OpticalFlow2D::QueueInterpolation(DevicePtr frame_0, DevicePtr frame_1, const DevicePtr* flows, bool use_masks,
+                                       const float* times, size_t time_count, const DevicePtr* outputs, int iterations,
+                                       float max_residual)
+{
+    const size_t W = dev_container_size_.width, H = dev_container_size_.height, pitch = dev_container_size_.pitch;
+    for (size_t j = 0; j < time_count; ++j)
+        if (CheckFlow2DError(flow2d_interpolate_2d(context_, AsPlane(frame_0), AsPlane(frame_1), AsPlane(flows[0]), AsPlane(flows[1]),
+                                                   AsPlane(flows[2]), AsPlane(flows[3]), use_masks ? AsPlane(flows[4]) : nullptr,
+                                                   use_masks ? AsPlane(flows[5]) : nullptr, W, H, pitch, times[j], iterations,
+                                                   max_residual, AsPlane(outputs[j])),
+                             "flow2d_interpolate_2d"))
+            return false;
+    return true;
+}
+
+bool OpticalFlow2D::InterpolateFramesDevice(const DevicePtr* dev_frames, size_t frame_count, const float* times, size_t time_count,
+                                            const DevicePtr* dev_outputs, int iterations, float max_residual, bool use_masks,
+                                            OperationParameters& params)
+{
+    if (!IsInitialized() || !dev_frames || !dev_outputs || frame_count < 2) return false;
+    if (group_ > 1) {
+        std::printf("Error: '%s': sequences and lock-step groups do not combine.\n", GetName());
+        return false;
+    }
+    if (!InterpolationArgsOk(times, time_count, iterations, max_residual)) return false;
+    // every output must be distinct from every other one and from the frames (which are only read)
+    const size_t n = (frame_count - 1) * time_count;
+    for (size_t k = 0; k < frame_count; ++k)
+        if (!dev_frames[k]) return false;
+    for (size_t i = 0; i < n; ++i) {
+        if (!dev_outputs[i]) return false;
+        for (size_t k = 0; k < frame_count; ++k)
+            if (dev_outputs[i] == dev_frames[k]) {
+                std::printf("Error: '%s': an output plane is one of the frames.\n", GetName());
+                return false;
+            }
+        for (size_t j = i + 1; j < n; ++j)
+            if (dev_outputs[i] == dev_outputs[j]) {
+                std::printf("Error: '%s': the output planes must be distinct.\n", GetName());
+                return false;
+            }
+    }
+    if (!EnsurePlanes(interpolation_planes_, 6)) return false;
+    const DevicePtr* p = interpolation_planes_;  // u, v, back u, back v, occlusion 0, occlusion 1
+    bool ok = true;
+    for (size_t k = 0; ok && k + 1 < frame_count; ++k) {
+        ok = ComputeFlowBidirectionalDevice(dev_frames + k, 2, p, p + 1, p + 2, p + 3, use_masks ? p + 4 : nullptr,
+                                            use_masks ? p + 5 : nullptr, params) &&
+             QueueInterpolation(dev_frames[k], dev_frames[k + 1], p, use_masks, times, time_count, dev_outputs + k * time_count,
+                                iterations, max_residual);
+    }
+    return ok;
+}
+
+void OpticalFlow2D::InterpolateFrames(Data2D& frame_0, Data2D& frame_1, const float* times, size_t time_count, Data2D* outputs,
+                                      int iterations, float max_residual, bool use_masks, OperationParameters& params,
+                                      Data2D* flow_u, Data2D* flow_v, Data2D* back_u, Data2D* back_v, Data2D* occlusion_0,
+                                      Data2D* occlusion_1)
+{
+    last_run_ok_ = false;
+    if (!IsInitialized() || !outputs) return;
+    if (group_ > 1) {
+        std::printf("Error: '%s': sequences and lock-step groups do not combine.\n", GetName());
+        return;
+    }
+    if (!InterpolationArgsOk(times, time_count, iterations, max_residual)) return;
+    const size_t W = dev_container_size_.width, H = dev_container_size_.height;
+    Data2D* flows[6] = {flow_u, flow_v, back_u, back_v, use_masks ? occlusion_0 : nullptr, use_masks ? occlusion_1 : nullptr};
+    std::vector<Data2D*> images = {&frame_0, &frame_1};
+    for (size_t j = 0; j < time_count; ++j) images.push_back(outputs + j);
+    for (Data2D* d : flows)
+        if (d) images.push_back(d);
+    for (Data2D* d : images)
+        if (d->Width() != W || d->Height() != H) {
+            std::printf("Error: '%s': frame / output sizes do not match the initialised size %zu x %zu.\n", GetName(), W, H);
+            return;
+        }
+    if (interpolation_outputs_.size() < time_count) interpolation_outputs_.resize(time_count, 0);
+    if (!EnsurePlanes(bidirectional_planes_, 2) || !EnsurePlanes(interpolation_planes_, 6) ||
+        !EnsurePlanes(interpolation_outputs_.data(), time_count))
+        return;
+    std::printf("\nStarting optical flow computation...\n");
+    void *ev_start = nullptr, *ev_stop = nullptr;
+    flow2d_event_create(context_, &ev_start);
+    flow2d_event_create(context_, &ev_stop);
+    flow2d_event_record(context_, ev_start);
+
+    const size_t pitch = dev_container_size_.pitch;
+    const DevicePtr* f = bidirectional_planes_;  // frame 0, frame 1
+    bool ok = CopyData2DtoDevice(frame_0, f[0], H, pitch) && CopyData2DtoDevice(frame_1, f[1], H, pitch) &&
+              InterpolateFramesDevice(f, 2, times, time_count, interpolation_outputs_.data(), iterations, max_residual, use_masks,
+                                      params);
+    for (size_t j = 0; ok && j < time_count; ++j) ok = CopyData2DFromDevice(interpolation_outputs_[j], outputs[j], H, pitch);
+    for (int i = 0; ok && i < 6; ++i)
+        if (flows[i]) ok = CopyData2DFromDevice(interpolation_planes_[i], *flows[i], H, pitch);
     last_run_ok_ = ok;
     flow2d_event_record(context_, ev_stop);
     flow2d_event_synchronize(context_, ev_stop);  // the only host wait

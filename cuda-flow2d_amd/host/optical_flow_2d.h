@@ -100,6 +100,25 @@ public:
     void ComputeFlowBidirectional(Data2D& frame_0, Data2D& frame_1, Data2D& flow_u, Data2D& flow_v, Data2D& back_u,
                                   Data2D& back_v, Data2D& occlusion_0, Data2D& occlusion_1, OperationParameters& params);
 
+    // Frames between the frames of a sequence (no reference counterpart): for every consecutive pair k it runs
+    // ComputeFlowBidirectionalDevice (with the occlusion masks when use_masks) into planes of its own, then one
+    // flow2d_interpolate_2d per time: dev_outputs[k * time_count + j] gets the frame at times[j] (0 <= t <= 1) between
+    // frames[k] and frames[k + 1], (frame_count - 1) * time_count outputs.  iterations (1 .. 16) and max_residual (finite,
+    // >= 0) are those of flow2d_interpolate_2d; use_masks = false interpolates without occlusion masks.  The flows are those of
+    // ComputeFlowBidirectionalDevice, bit for bit.  Frames are only read; outputs must be distinct from each other and from the
+    // frames.  Queued on the context's stream, launched eagerly (no graph).  Not for lock-step groups.
+    bool InterpolateFramesDevice(const DevicePtr* dev_frames, size_t frame_count, const float* times, size_t time_count,
+                                 const DevicePtr* dev_outputs, int iterations, float max_residual, bool use_masks,
+                                 OperationParameters& params);
+    // The host-image form (the CLI's --interpolate): upload both frames, compute both flows (and the masks when use_masks) and
+    // the time_count frames of `times` into outputs[0 .. time_count - 1], download.  Non-null flow_u .. occlusion_1 also get
+    // the flows and masks of ComputeFlowBidirectional (the masks only with use_masks).  LastRunSucceeded and LastTotalMs as for
+    // ComputeFlow.
+    void InterpolateFrames(Data2D& frame_0, Data2D& frame_1, const float* times, size_t time_count, Data2D* outputs,
+                           int iterations, float max_residual, bool use_masks, OperationParameters& params,
+                           Data2D* flow_u = nullptr, Data2D* flow_v = nullptr, Data2D* back_u = nullptr,
+                           Data2D* back_v = nullptr, Data2D* occlusion_0 = nullptr, Data2D* occlusion_1 = nullptr);
+
     // When set, ComputeFlowDevice records the whole pyramid of a pair into a HIP graph the first time it
     // sees a (buffers, parameters) combination and replays it afterwards: one host call instead of
     // several hundred launches.  Ignored while timing_mode != 0 (events are not captured).
@@ -188,6 +207,16 @@ private:
                          DevicePtr flow_v, OperationParameters& params);
     // ComputeFlowBidirectional: both frames and the six outputs, outside the pool (allocated on first use)
     DevicePtr bidirectional_planes_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    // InterpolateFrames*: the flows and masks of a pair (u, v, back u, back v, occlusion 0, occlusion 1) and the host form's
+    // output frames, outside the pool (allocated on first use)
+    DevicePtr interpolation_planes_[6] = {0, 0, 0, 0, 0, 0};
+    std::vector<DevicePtr> interpolation_outputs_;
+    bool EnsurePlanes(DevicePtr* planes, size_t count);
+    bool InterpolationArgsOk(const float* times, size_t time_count, int iterations, float max_residual);
+    // the flow2d_interpolate_2d launches of one pair: flows = u, v, back u, back v, occlusion 0, occlusion 1 (masks unused when
+    // !use_masks)
+    bool QueueInterpolation(DevicePtr frame_0, DevicePtr frame_1, const DevicePtr* flows, bool use_masks, const float* times,
+                            size_t time_count, const DevicePtr* outputs, int iterations, float max_residual);
     flow2d_context* context_ = nullptr;
     // One plane beside the pool: the warped frame of a level, when the levels of both frames are computed up front into plane
     // regions of their own (RunPyramid: "stacked" levels) and therefore cannot be overwritten by the warp

@@ -14,6 +14,11 @@ Scenes (make_scene(name, width, height, seed)):
 
 Each Scene carries frame_0, frame_1, gt_u, gt_v (float32, height x width), occlusion (float32 0 / 1, or None where the scene
 has no occlusion) and frame_1_at(x, y): the analytic frame 1 at any real coordinates (double), for checking the ground truth.
+For frame interpolation (flow2d_interpolate_2d) it also carries gt_back_u, gt_back_v -- the true flow of frame 1 to frame 0,
+I0(y + w_b(y)) = I1(y) at every pixel y of frame 1 that is not occluded --, occlusion_1 (frame 1's occlusion map, None where
+the scene has none), frame_0_at(x, y) (the analytic frame 0), back_flow_at(x, y) (the backward flow at any real coordinates,
+double) and frame_at_time(t): the exact frame at time t, 0 <= t <= 1, on
+the linear trajectories x + t * w(x) (frame_0 at t = 0, frame_1 at t = 1).
 Pure numpy: no device, no library.
 """
 import numpy as np
@@ -38,12 +43,24 @@ class Texture:
 
 
 class Scene:
-    def __init__(self, name, frame_0, frame_1, gt_u, gt_v, occlusion, frame_1_at):
+    def __init__(self, name, frame_0, frame_1, gt_u, gt_v, occlusion, frame_1_at, frame_0_at=None, frame_at_time=None,
+                 back_flow_at=None, occlusion_1=None):
         self.name = name
         self.frame_0, self.frame_1 = frame_0, frame_1
         self.gt_u, self.gt_v = gt_u, gt_v
         self.occlusion = occlusion
         self.frame_1_at = frame_1_at
+        self.frame_0_at = frame_0_at
+        self._frame_at_time = frame_at_time
+        self.back_flow_at = back_flow_at
+        self.occlusion_1 = occlusion_1
+        ys, xs = np.mgrid[0:frame_0.shape[0], 0:frame_0.shape[1]].astype(np.float64)
+        back_u, back_v = back_flow_at(xs, ys)
+        self.gt_back_u, self.gt_back_v = back_u.astype(np.float32), back_v.astype(np.float32)
+
+    def frame_at_time(self, t):
+        """The exact frame at time t (float32, height x width): frame_0 at t = 0, frame_1 at t = 1."""
+        return self._frame_at_time(float(t)).astype(np.float32)
 
     @property
     def shape(self):
@@ -65,8 +82,22 @@ def _affine_scene(name, width, height, texture, a, t):
     dx, dy = xs - c[0], ys - c[1]
     gt_u = (a[0, 0] - 1) * dx + a[0, 1] * dy + t[0]
     gt_v = a[1, 0] * dx + (a[1, 1] - 1) * dy + t[1]
+
+    def frame_at_time(tau):
+        # x -> x + tau * w(x) = c + (I + tau (A - I)) (x - c) + tau t: the texture at its inverse
+        inv_t = np.linalg.inv(np.eye(2) + tau * (a - np.eye(2)))
+        px, py = xs - c[0] - tau * t[0], ys - c[1] - tau * t[1]
+        return texture(inv_t[0, 0] * px + inv_t[0, 1] * py + c[0], inv_t[1, 0] * px + inv_t[1, 1] * py + c[1])
+
+    def back_flow_at(x, y):
+        # y -> W^-1(y) = A^-1 (y - c - t) + c, so w_b(y) = W^-1(y) - y
+        x, y = np.asarray(x, np.float64), np.asarray(y, np.float64)
+        px, py = x - c[0] - t[0], y - c[1] - t[1]
+        return inv[0, 0] * px + inv[0, 1] * py + c[0] - x, inv[1, 0] * px + inv[1, 1] * py + c[1] - y
+
     return Scene(name, texture(xs, ys).astype(np.float32), frame_1_at(xs, ys).astype(np.float32), gt_u.astype(np.float32),
-                 gt_v.astype(np.float32), None, frame_1_at)
+                 gt_v.astype(np.float32), None, frame_1_at, frame_0_at=texture, frame_at_time=frame_at_time,
+                 back_flow_at=back_flow_at, occlusion_1=None)
 
 
 def _two_layer_scene(width, height, background, square, t):
@@ -90,8 +121,28 @@ def _two_layer_scene(width, height, background, square, t):
     covered = ~moving & in_square(xs, ys, tx, ty)
     leaving = moving & ((xs + tx < 0) | (xs + tx > width - 1) | (ys + ty < 0) | (ys + ty > height - 1))
     occlusion = (covered | leaving).astype(np.float32)
+
+    def frame_0_at(x, y):
+        x, y = np.asarray(x, np.float64), np.asarray(y, np.float64)
+        return np.where(in_square(x, y, 0.0, 0.0), square(x, y), background(x, y))
+
+    def frame_at_time(tau):
+        sx, sy = tau * tx, tau * ty
+        return np.where(in_square(xs, ys, sx, sy), square(xs - sx, ys - sy), background(xs, ys))
+
+    # frame 1: the square's pixels move back by -t, the background stays; frame 1's occlusion: the background the square
+    # uncovered, and square pixels whose backward vector leaves the frame
+    def back_flow_at(x, y):
+        shown = in_square(np.asarray(x, np.float64), np.asarray(y, np.float64), tx, ty)
+        return np.where(shown, -tx, 0.0), np.where(shown, -ty, 0.0)
+
+    shown = in_square(xs, ys, tx, ty)
+    uncovered = ~shown & moving
+    leaving_1 = shown & ((xs - tx < 0) | (xs - tx > width - 1) | (ys - ty < 0) | (ys - ty > height - 1))
+    occlusion_1 = (uncovered | leaving_1).astype(np.float32)
     return Scene("two_layer", frame_0.astype(np.float32), frame_1_at(xs, ys).astype(np.float32), gt_u.astype(np.float32),
-                 gt_v.astype(np.float32), occlusion, frame_1_at)
+                 gt_v.astype(np.float32), occlusion, frame_1_at, frame_0_at=frame_0_at, frame_at_time=frame_at_time,
+                 back_flow_at=back_flow_at, occlusion_1=occlusion_1)
 
 
 def make_scene(name, width=256, height=256, seed=0):

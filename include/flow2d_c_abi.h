@@ -34,8 +34,8 @@ extern "C" {
 #define FLOW2D_API __attribute__((visibility("default")))
 
 /* Additions that leave every existing entry as it was keep the version: flow2d_consistency_2d (forward-backward occlusion
- * masks) and flow2d_flow_error_2d / flow2d_flow_error_workspace_bytes (error statistics against ground truth) were added
- * under 1. */
+ * masks), flow2d_flow_error_2d / flow2d_flow_error_workspace_bytes (error statistics against ground truth) and
+ * flow2d_interpolate_2d (occlusion-aware frame interpolation) were added under 1. */
 #define FLOW2D_ABI_VERSION 1
 
 typedef enum flow2d_status {
@@ -220,6 +220,36 @@ FLOW2D_API int flow2d_registration_2d(flow2d_context* ctx, const float* frame_0,
 FLOW2D_API int flow2d_consistency_2d(flow2d_context* ctx, const float* flow_u, const float* flow_v, const float* back_u,
                                      const float* back_v, size_t width, size_t height, size_t pitch_bytes, float alpha1,
                                      float alpha2, float* mask);
+
+/* Occlusion-aware frame interpolation from a bidirectional flow (no reference counterpart; added to ABI version 1 without
+ * changing any existing entry).  (flow_u, flow_v): the flow of frame_0 to frame_1; (back_u, back_v): the flow of frame_1 to
+ * frame_0; occlusion_0 / occlusion_1: the occlusion masks of frame_0 / frame_1 (1 = no match in the other frame, as
+ * flow2d_consistency_2d writes them), each may be NULL on its own.  `output` gets the frame at time t, 0 <= t <= 1, by exactly
+ * these fp32 operations, in this order, for every pixel x = (x, y):
+ *   S(P, p)   the bilinear sample of flow2d_consistency_2d at p, where p is first replaced by x when either coordinate is not
+ *             finite and then clamped to [0, width - 1] x [0, height - 1]; both components of a flow are sampled at one p
+ *   side 0    p_0 = x;  p_k = x - t * S(flow, p_{k-1}) for k = 1 .. K (K = iterations; per component);
+ *             r = x - t * S(flow, p_K) - p_K;
+ *             ok0 = p_K finite and inside [0, width - 1] x [0, height - 1] and r.x*r.x + r.y*r.y <= max_residual*max_residual;
+ *             a0 = S(frame_0, p_K)
+ *   side 1    the same with (back_u, back_v) and s = 1 - t in place of t: q_K, ok1, a1 = S(frame_1, q_K)
+ *   masks     c0 = ok0 ? S(occlusion_0, p_K) : 0 (0 when occlusion_0 is NULL); then if (!(c0 <= 1)) c0 = 1;
+ *             if (!(c0 >= 0)) c0 = 0 (a NaN counts as occluded); c1 likewise with occlusion_1 at q_K
+ *   weights   v0 = ok0 * (1 - c0), v1 = ok1 * (1 - c1)   (ok as 0.0f / 1.0f);
+ *             v0 + v1 > 0:  w0 = s * v0, w1 = t * v1   (content seen in both frames wins over content seen in one)
+ *             otherwise:    w0 = s * ok0, w1 = t * ok1
+ *   output    w0 + w1 > 0:  (w0*a0 + w1*a1) / (w0 + w1)   (correctly rounded division)
+ *             otherwise:    s*a0 + t*a1
+ * With finite flows, no masks and frames without negative zeros the output is frame_0 bit for bit at t = 0 and frame_1 at t = 1.
+ * FLOW2D_ERR_INVALID_ARGUMENT for a null required plane, a zero size, a bad pitch (a multiple of 16 bytes, at least 4 floats:
+ * the sample reads column pairs), a t that is not finite or outside [0, 1], iterations outside [1, 16], a negative or
+ * non-finite max_residual, or an `output` whose bytes [output, output + height * pitch_bytes) -- over every instance of a
+ * batch -- overlap those of any input plane.  Honours flow2d_context_set_batch.  One launch, no allocation, no
+ * synchronisation (graph-capturable). */
+FLOW2D_API int flow2d_interpolate_2d(flow2d_context* ctx, const float* frame_0, const float* frame_1, const float* flow_u,
+                                     const float* flow_v, const float* back_u, const float* back_v, const float* occlusion_0,
+                                     const float* occlusion_1, size_t width, size_t height, size_t pitch_bytes, float t,
+                                     int iterations, float max_residual, float* output);
 
 /* Error of a flow estimate against ground truth (Barron et al. 1994, Baker et al. 2011 -- Middlebury --, Menze & Geiger 2015 --
  * KITTI --; no reference counterpart; added to ABI version 1 without changing any existing entry).
