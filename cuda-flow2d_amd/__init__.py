@@ -25,6 +25,9 @@ CLI_PATH = os.path.join(_HERE, "host", "flow2d")
 GREY, GRADIENT, GRADIENT_UNTILED, LOG_DERIVATIVES = 0, 1, 2, 3
 _HOST_CONSTANCY = {GREY: 0, GRADIENT: 1, GRADIENT_UNTILED: 3, LOG_DERIVATIVES: 2}  # enum class DataConstancy
 SOLVER_AUTO, SOLVER_PER_SWEEP, SOLVER_FUSED, SOLVER_SINGLE_WORKGROUP, SOLVER_TILED = 0, 1, 2, 3, 4
+# flow2d_track_reason; DEFAULT_MIN_EIGENVALUE: the seeding threshold of OpticalFlow.track_points and the CLI's --track
+TRACK_ALIVE, TRACK_INACTIVE, TRACK_MOTION_BOUNDARY, TRACK_LEFT_FRAME, TRACK_OCCLUDED = 0, 1, 2, 3, 4
+DEFAULT_MIN_EIGENVALUE = 1.0
 
 STATUS = {0: "ok", 1: "invalid argument", 2: "no usable HIP device", 3: "HIP runtime error",
           4: "out of device memory", 5: "unsupported parameter"}
@@ -204,6 +207,11 @@ def hip_lib():
             L.flow2d_consistency_2d.argtypes = [vp, vp, vp, vp, vp, sz, sz, sz, f, f, vp]
         if hasattr(L, "flow2d_interpolate_2d"):  # (absent from libraries of earlier rounds loaded for an A/B)
             L.flow2d_interpolate_2d.argtypes = [vp] * 9 + [sz, sz, sz, f, i, f, vp]
+        if hasattr(L, "flow2d_track_points_2d"):  # (absent from libraries of earlier rounds loaded for an A/B)
+            L.flow2d_track_points_2d.argtypes = [vp] * 5 + [sz, sz, sz, vp, vp, vp, sz, f, f, i, f, f, vp, vp, vp]
+            L.flow2d_seed_points_workspace_bytes.restype = sz
+            L.flow2d_seed_points_workspace_bytes.argtypes = [sz, sz, sz]
+            L.flow2d_seed_points_2d.argtypes = [vp, vp, sz, sz, sz, sz, f, vp, vp, vp, sz, vp, vp, sz]
         if hasattr(L, "flow2d_flow_error_2d"):  # (absent from libraries of earlier rounds loaded for an A/B)
             L.flow2d_flow_error_workspace_bytes.restype = sz
             L.flow2d_flow_error_workspace_bytes.argtypes = [sz, sz, sz]
@@ -431,6 +439,44 @@ class Context:
                                                occ_0.ptr if occ_0 else None, occ_1.ptr if occ_1 else None, w, h, u.pitch, t,
                                                iterations, max_residual, out.ptr), "flow2d_interpolate_2d")
 
+    def track_points(self, u, v, bu, bv, w, h, x, y, count, capacity, out_x, out_y, reason=None, alpha1=0.01, alpha2=0.5,
+                     boundaries=True, beta1=0.01, beta2=0.002):
+        """One step of the track table (x, y) along the flow (u, v) into (out_x, out_y) (flow2d_track_points_2d).  Tables are
+        Planes of height 1 and width >= capacity; `count` is a device counter (see counter()); (bu, bv) the backward flow, or
+        both None for no forward-backward check; `reason` an optional Plane whose first `capacity` bytes get the reason codes
+        (TRACK_ALIVE ... TRACK_OCCLUDED)."""
+        _check(hip_lib().flow2d_track_points_2d(self.handle, u.ptr, v.ptr, bu.ptr if bu else None, bv.ptr if bv else None, w, h,
+                                                u.pitch, x.ptr, y.ptr, count.ptr, capacity, alpha1, alpha2, int(bool(boundaries)),
+                                                beta1, beta2, out_x.ptr, out_y.ptr, reason.ptr if reason else None),
+               "flow2d_track_points_2d")
+
+    def seed_points(self, frame, w, h, spacing, x, y, count, capacity, min_eigenvalue=0.0, dropped=None):
+        """Append tracks in the uncovered, textured cells of `frame` to the table (x, y) (flow2d_seed_points_2d): `count` (a
+        device counter) grows by the seeds written, `dropped` (a counter, optional) gets the cells that did not fit.  The
+        workspace is the context's own (kept between calls)."""
+        L = hip_lib()
+        need = L.flow2d_seed_points_workspace_bytes(w, h, spacing)
+        cached = getattr(self, "_seed_workspace", None)
+        if cached is None or cached[0] < need:
+            if cached is not None:
+                cached[1].free()
+                self._planes.remove(cached[1])
+            self._seed_workspace = cached = (need, self.plane(max((need + 3) // 4, 4), 1))
+        _check(L.flow2d_seed_points_2d(self.handle, frame.ptr, w, h, frame.pitch, spacing, min_eigenvalue, x.ptr, y.ptr,
+                                       count.ptr, capacity, dropped.ptr if dropped else None, cached[1].ptr, cached[0]),
+               "flow2d_seed_points_2d")
+
+    def counter(self, value=0):
+        """A device counter (one unsigned 64-bit integer, in a Plane) holding `value`: the `count` / `dropped` of the tracking
+        entries."""
+        p = self.plane(4, 1)
+        p.upload(np.frombuffer(np.array([value, 0], np.uint64).tobytes(), np.float32).reshape(1, 4))
+        return p
+
+    def read_count(self, counter):
+        """The value of a device counter (synchronises)."""
+        return int(counter.download(4, 1).view(np.uint64)[0, 0])
+
     def flow_error(self, u, v, gt_u, gt_v, w, h, occlusion=None, epe=None, ae=None, instances=1):
         """Error of the flow (u, v) against ground truth (gt_u, gt_v), all planes of one pitch (flow2d_flow_error_2d): returns
         one record per lock-step instance (`instances` = the count of flow2d_context_set_batch) as dicts (see _stats_dict);
@@ -609,6 +655,11 @@ def host_lib():
         L.flow2d_host_interpolate_frames.argtypes = [vp, fp, fp, fp, sz, fp, C.POINTER(HostParams), i, f, i, fp]
         L.flow2d_host_interpolate_frames_device.argtypes = [vp, C.POINTER(vp), sz, fp, sz, C.POINTER(vp), C.POINTER(HostParams),
                                                             i, f, i]
+        if hasattr(L, "flow2d_host_track_points"):
+            ull = C.POINTER(C.c_ulonglong)
+            L.flow2d_host_track_points.argtypes = [vp, fp, sz, sz, f, i, f, f, fp, fp, sz, ull, C.POINTER(HostParams), f, f, fp]
+            L.flow2d_host_track_points_device.argtypes = [vp, C.POINTER(vp), sz, sz, f, i, f, f, C.POINTER(vp), C.POINTER(vp), sz,
+                                                          ull, C.POINTER(HostParams), f, f]
         L.flow2d_host_read_flo.argtypes = [C.c_char_p, C.POINTER(sz), C.POINTER(sz), fp, fp, sz]
         L.flow2d_host_write_flo.argtypes = [fp, fp, sz, sz, C.c_char_p]
         L.flow2d_host_flow_error.argtypes = [fp] * 5 + [sz, sz, fp, fp, C.POINTER(FlowErrorStats)]
@@ -787,6 +838,50 @@ class OpticalFlow:
                                                               int(iterations), max_residual, int(bool(masks)))
         if rc:
             raise Flow2DError(rc, "OpticalFlow2D::InterpolateFramesDevice")
+
+    def track_points(self, frames, params, spacing=4, min_eigenvalue=DEFAULT_MIN_EIGENVALUE, boundaries=True, capacity=None,
+                     alpha1=0.01, alpha2=0.5, beta1=0.01, beta2=0.002):
+        """OpticalFlow2D::TrackPoints: dense point trajectories through the host frames `frames` ([frame_count, h, w]).  Frame
+        0 is seeded on a grid of `spacing`, every track is carried by the forward flow and ends at an occlusion
+        (forward-backward check at its sub-pixel position, alpha1 / alpha2), at a motion boundary (boundaries, beta1 / beta2)
+        or where it leaves the frame, and uncovered cells of every later frame get new tracks.  min_eigenvalue is the seeding
+        threshold on the smaller eigenvalue of the 5x5 structure tensor: unnormalised sums of grey-level gradients, so it is
+        scale-dependent (the default keeps the analytic scenes' textures; 0 seeds every uncovered cell).  capacity: the table
+        size (default: every cell of every frame).  Returns (xs, ys): float32 [frame_count, N], N the final track count; NaN
+        where a track has not started or has ended."""
+        fr = np.ascontiguousarray(frames, np.float32)
+        assert fr.ndim == 3 and fr.shape[1:] == (self.height, self.width) and fr.shape[0] >= 2
+        n = fr.shape[0]
+        if capacity is None:
+            capacity = n * (-(-self.width // spacing)) * (-(-self.height // spacing))
+        xs = np.empty((n, capacity), np.float32)
+        ys = np.empty((n, capacity), np.float32)
+        counts = (C.c_ulonglong * n)()
+        ms = C.c_float()
+        rc = host_lib().flow2d_host_track_points(self.handle, _fptr(fr), n, spacing, min_eigenvalue, int(bool(boundaries)), beta1,
+                                                 beta2, _fptr(xs), _fptr(ys), capacity, counts, C.byref(params), alpha1, alpha2,
+                                                 C.byref(ms))
+        if rc:
+            raise Flow2DError(rc, "OpticalFlow2D::TrackPoints")
+        last = int(counts[n - 1])
+        return xs[:, :last].copy(), ys[:, :last].copy()
+
+    def track_points_device(self, dev_frames, dev_xs, dev_ys, capacity, params, spacing=4,
+                            min_eigenvalue=DEFAULT_MIN_EIGENVALUE, boundaries=True, alpha1=0.01, alpha2=0.5, beta1=0.01,
+                            beta2=0.002):
+        """OpticalFlow2D::TrackPointsDevice: device frames in, the track table of frame k into (dev_xs[k], dev_ys[k]) (device
+        addresses of `capacity` floats each).  Returns the track count after each frame's seeding (synchronises once)."""
+        n = len(dev_frames)
+        if n < 2 or len(dev_xs) != n or len(dev_ys) != n:
+            raise ValueError("n frames take n x and n y tables")
+        arr = lambda q: (C.c_void_p * len(q))(*q)  # noqa: E731
+        counts = (C.c_ulonglong * n)()
+        rc = host_lib().flow2d_host_track_points_device(self.handle, arr(dev_frames), n, spacing, min_eigenvalue,
+                                                        int(bool(boundaries)), beta1, beta2, arr(dev_xs), arr(dev_ys), capacity,
+                                                        counts, C.byref(params), alpha1, alpha2)
+        if rc:
+            raise Flow2DError(rc, "OpticalFlow2D::TrackPointsDevice")
+        return [int(c) for c in counts]
 
     def level_timings(self):
         """[(width, height, solve_ms, kernel_ms, kernel_launches, algorithmic_bytes_per_launch, algorithm)] per level;

@@ -231,6 +231,62 @@ HOST_API int flow2d_host_interpolate_frames_device(flow2d_host_flow* h, void* co
                : 2;
 }
 
+// OpticalFlow2D::TrackPoints on tight host images: frames = frame_count * width * height floats (frame k at k * width * height);
+// xs / ys get frame_count * capacity floats (table k at k * capacity), counts frame_count entries.  alpha1 / alpha2: the bag keys
+// consistency_alpha1 / consistency_alpha2.  0 on success, 1 for a null argument, 2 when the run delivered no tracks.
+HOST_API int flow2d_host_track_points(flow2d_host_flow* h, const float* frames, size_t frame_count, size_t spacing,
+                                      float min_eigenvalue, int check_boundaries, float beta1, float beta2, float* xs, float* ys,
+                                      size_t capacity, unsigned long long* counts, const flow2d_host_params* params, float alpha1,
+                                      float alpha2, float* total_ms)
+{
+    if (!h || !frames || !xs || !ys || !counts || !params || frame_count < 2 || capacity == 0) return 1;
+    const size_t n = h->width * h->height;
+    std::vector<Data2D> f;
+    for (size_t k = 0; k < frame_count; ++k) {
+        f.emplace_back(h->width, h->height);
+        std::memcpy(f.back().DataPtr(), frames + k * n, n * sizeof(float));
+    }
+    flow2d_host_params p = *params;
+    OperationParameters bag;
+    FillBag(bag, p);
+    bag.PushValuePtr("consistency_alpha1", &alpha1);
+    bag.PushValuePtr("consistency_alpha2", &alpha2);
+    std::vector<Data2D*> fp;
+    for (Data2D& d : f) fp.push_back(&d);
+    h->flow.TrackPoints(fp.data(), frame_count, spacing, min_eigenvalue, check_boundaries != 0, beta1, beta2, xs, ys, capacity,
+                        counts, bag);
+    if (total_ms) *total_ms = h->flow.LastTotalMs();
+    return h->flow.LastRunSucceeded() ? 0 : 2;
+}
+
+// OpticalFlow2D::TrackPointsDevice: frame_count device frames and frame_count device tables of `capacity` floats per
+// coordinate; counts (host) gets frame_count entries.  Synchronises once at the end.  0 on success.
+HOST_API int flow2d_host_track_points_device(flow2d_host_flow* h, void* const* dev_frames, size_t frame_count, size_t spacing,
+                                             float min_eigenvalue, int check_boundaries, float beta1, float beta2,
+                                             void* const* dev_xs, void* const* dev_ys, size_t capacity,
+                                             unsigned long long* counts, const flow2d_host_params* params, float alpha1,
+                                             float alpha2)
+{
+    if (!h || !params || !dev_frames || !dev_xs || !dev_ys || !counts || frame_count < 2 || capacity == 0) return 1;
+    flow2d_host_params p = *params;
+    OperationParameters bag;
+    FillBag(bag, p);
+    bag.PushValuePtr("consistency_alpha1", &alpha1);
+    bag.PushValuePtr("consistency_alpha2", &alpha2);
+    h->flow.timing_mode = 0;
+    auto dp = [](void* q) { return static_cast<DevicePtr>(reinterpret_cast<uintptr_t>(q)); };
+    std::vector<DevicePtr> frames(frame_count), xs(frame_count), ys(frame_count);
+    for (size_t k = 0; k < frame_count; ++k) {
+        frames[k] = dp(dev_frames[k]);
+        xs[k] = dp(dev_xs[k]);
+        ys[k] = dp(dev_ys[k]);
+    }
+    return h->flow.TrackPointsDevice(frames.data(), frame_count, spacing, min_eigenvalue, check_boundaries != 0, beta1, beta2,
+                                     xs.data(), ys.data(), capacity, counts, bag)
+               ? 0
+               : 2;
+}
+
 // OpticalFlow2D::ComputeFlowBidirectionalDevice: frame_count device frames, frame_count - 1 forward and backward flow plane pairs,
 // occlusion planes optional (NULL arrays: no masks).  Queued on the context's stream, no synchronisation.  0 on success.
 HOST_API int flow2d_host_compute_flow_bidirectional_device(flow2d_host_flow* h, void* const* dev_frames, size_t frame_count,

@@ -22,6 +22,11 @@
 // F32 <prefix>interp-<k>-of-<N>-W-H.raw: OpticalFlow2D::InterpolateFrames (flow2d_interpolate_2d) with both flows, both
 // occlusion masks, 2 fixed-point iterations and a residual bound of 0.5 px.  The forward files do not change; the backward
 // files are written only with --backward.
+// --track S (an integer >= 1) also seeds frame 1 on a grid of spacing S and tracks the points into frame 2
+// (OpticalFlow2D::TrackPoints: flow2d_seed_points_2d with the default texture threshold, flow2d_track_points_2d with the paper's
+// thresholds), writes <prefix>tracks.txt -- one line per track, "x1 y1 x2 y2", nan where the track has no position -- and prints
+// the alive, ended and seeded counts.  The other files do not change.
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -58,6 +63,7 @@ int main(int argc, char** argv)
     // optional flags first (supersets), then the reference's positional forms
     bool force_u8 = false, verbose = false, backward = false, write_flo = false;
     int interpolate = 0;  // --interpolate N: N - 1 frames between the two (0: off)
+    long track_spacing = 0;  // --track S: seed frame 1 at spacing S and track into frame 2 (0: off)
     std::string ground_truth_file;
     int device = 0;
     float sor_omega = 0.f;
@@ -80,6 +86,16 @@ int main(int argc, char** argv)
                 return 5;
             }
             interpolate = static_cast<int>(n);
+            ++i;
+        }
+        else if (!std::strcmp(argv[i], "--track")) {
+            char* end = nullptr;
+            const long n = (i + 1 < argc) ? std::strtol(argv[i + 1], &end, 10) : 0;
+            if (i + 1 >= argc || end == argv[i + 1] || *end != '\0' || n < 1 || n > 1000000) {
+                std::printf("--track takes an integer spacing S >= 1 (the seeding grid of frame 1).\n");
+                return 5;
+            }
+            track_spacing = n;
             ++i;
         }
         else if (!std::strcmp(argv[i], "--device") && i + 1 < argc) device = std::atoi(argv[++i]);
@@ -247,6 +263,41 @@ int main(int argc, char** argv)
                 std::cerr << "Error: cannot save file " << std::endl;
                 std::exit(255);
             }
+        }
+        if (track_spacing) {
+            const size_t s = static_cast<size_t>(track_spacing);
+            const size_t capacity = 2 * ((width + s - 1) / s) * ((height + s - 1) / s);  // seeds of both frames at most
+            std::vector<float> xs(2 * capacity), ys(2 * capacity);
+            unsigned long long counts[2] = {0, 0};
+            Data2D* frames[2] = {&frame_0, &frame_1};
+            optical_flow.TrackPoints(frames, 2, s, OpticalFlow2D::kDefaultTrackMinEigenvalue, true, 0.01f, 0.002f, xs.data(),
+                                     ys.data(), capacity, counts, params);
+            if (!optical_flow.LastRunSucceeded()) {
+                std::cout << "Error: point tracking failed." << std::endl;
+                optical_flow.Destroy();
+                DestroyDeviceContext();
+                return 4;
+            }
+            std::FILE* out = std::fopen((output_path + counter + "tracks.txt").c_str(), "w");
+            if (!out) {
+                std::cerr << "Error: cannot save file " << std::endl;
+                std::exit(255);
+            }
+            size_t alive = 0;
+            auto put = [out](float v, const char* sep) {
+                if (std::isnan(v)) std::fprintf(out, "nan%s", sep);
+                else std::fprintf(out, "%.9g%s", v, sep);
+            };
+            for (size_t i = 0; i < counts[1]; ++i) {
+                put(xs[i], " ");
+                put(ys[i], " ");
+                put(xs[capacity + i], " ");
+                put(ys[capacity + i], "\n");
+                if (i < counts[0] && !std::isnan(xs[capacity + i])) ++alive;
+            }
+            std::fclose(out);
+            std::printf("Tracks: %zu alive, %zu ended, %llu seeded in frame 2\n", alive, static_cast<size_t>(counts[0]) - alive,
+                        counts[1] - counts[0]);
         }
         if (!ground_truth_file.empty()) {
             flow2d_flow_error_stats stats;

@@ -169,6 +169,11 @@ void OpticalFlow2D::Destroy()
         }
         for (DevicePtr p : interpolation_outputs_) flow2d_plane_free(context_, AsPlane(p));
         interpolation_outputs_.clear();
+        for (DevicePtr p : tracking_flows_) flow2d_plane_free(context_, AsPlane(p));
+        tracking_flows_.clear();
+        if (tracking_scratch_) flow2d_plane_free(context_, AsPlane(tracking_scratch_));
+        tracking_scratch_ = 0;
+        tracking_scratch_bytes_ = 0;
     }
     all_planes_.clear();
     free_planes_.clear();
@@ -539,6 +544,171 @@ void OpticalFlow2D::InterpolateFrames(Data2D& frame_0, Data2D& frame_1, const fl
     std::printf("Total GPU computation time: % 4.4fs\n", last_total_ms_ / 1000.);
     flow2d_event_destroy(context_, ev_start);
     flow2d_event_destroy(context_, ev_stop);
+}
+
+// `bytes` of device memory (a one-row plane, 16-byte aligned); 0 on failure
+DevicePtr OpticalFlow2D::AllocBytes(size_t bytes)
+{
+    void* plane = nullptr;
+    size_t pitch = 0;
+    if (CheckFlow2DError(flow2d_plane_alloc(context_, (bytes + 3) / 4, 1, &plane, &pitch), "flow2d_plane_alloc")) return 0;
+    return static_cast<DevicePtr>(reinterpret_cast<uintptr_t>(plane));
+}
+
+bool OpticalFlow2D::TrackPointsDevice(const DevicePtr* dev_frames, size_t frame_count, size_t spacing, float min_eigenvalue,
+                                      bool check_boundaries, float beta1, float beta2, const DevicePtr* dev_xs,
+                                      const DevicePtr* dev_ys, size_t capacity, unsigned long long* counts_out,
+                                      OperationParameters& params)
+{
+    if (!IsInitialized() || !dev_frames || !dev_xs || !dev_ys || !counts_out || frame_count < 2 || capacity == 0) return false;
+    if (group_ > 1) {
+        std::printf("Error: '%s': sequences and lock-step groups do not combine.\n", GetName());
+        return false;
+    }
+    if (spacing == 0 || !(std::isfinite(min_eigenvalue) && min_eigenvalue >= 0.f) ||
+        !(std::isfinite(beta1) && beta1 >= 0.f && std::isfinite(beta2) && beta2 >= 0.f)) {
+        std::printf("Error: '%s': tracking spacing %zu (>= 1), min eigenvalue %g, boundary thresholds %g / %g (finite, >= 0).\n",
+                    GetName(), spacing, min_eigenvalue, beta1, beta2);
+        return false;
+    }
+    float alpha1 = 0.01f, alpha2 = 0.5f;  // Sundaram, Brox & Keutzer (ECCV 2010)
+    params.Read<float>("consistency_alpha1", alpha1);
+    params.Read<float>("consistency_alpha2", alpha2);
+    if (!(std::isfinite(alpha1) && std::isfinite(alpha2) && alpha1 >= 0.f && alpha2 >= 0.f)) {
+        std::printf("Error: '%s': consistency thresholds %g / %g (finite, >= 0).\n", GetName(), alpha1, alpha2);
+        return false;
+    }
+    // every table is written: distinct from each other and from the frames
+    std::vector<DevicePtr> tables;
+    for (size_t k = 0; k < frame_count; ++k) {
+        if (!dev_frames[k] || !dev_xs[k] || !dev_ys[k]) return false;
+        tables.push_back(dev_xs[k]);
+        tables.push_back(dev_ys[k]);
+    }
+    for (size_t i = 0; i < tables.size(); ++i) {
+        for (size_t k = 0; k < frame_count; ++k)
+            if (tables[i] == dev_frames[k]) {
+                std::printf("Error: '%s': a track table is one of the frames.\n", GetName());
+                return false;
+            }
+        for (size_t j = i + 1; j < tables.size(); ++j)
+            if (tables[i] == tables[j]) {
+                std::printf("Error: '%s': the track tables must be distinct.\n", GetName());
+                return false;
+            }
+    }
+    const size_t W = dev_container_size_.width, H = dev_container_size_.height, pitch = dev_container_size_.pitch;
+    const size_t window = std::min(kTrackWindow, frame_count - 1);
+    if (tracking_flows_.size() < 4 * window) tracking_flows_.resize(4 * window, 0);
+    if (!EnsurePlanes(tracking_flows_.data(), 4 * window)) return false;
+    // the device count (16 bytes) and the seeding workspace behind it
+    const size_t workspace_bytes = flow2d_seed_points_workspace_bytes(W, H, spacing);
+    if (tracking_scratch_bytes_ < 16 + workspace_bytes) {
+        if (tracking_scratch_) {
+            flow2d_synchronize(context_);  // queued work may still use the old one
+            flow2d_plane_free(context_, AsPlane(tracking_scratch_));
+        }
+        tracking_scratch_bytes_ = 0;
+        tracking_scratch_ = AllocBytes(16 + workspace_bytes);
+        if (!tracking_scratch_) return false;
+        tracking_scratch_bytes_ = 16 + workspace_bytes;
+    }
+    unsigned long long* dev_count = reinterpret_cast<unsigned long long*>(static_cast<uintptr_t>(tracking_scratch_));
+    void* workspace = reinterpret_cast<char*>(dev_count) + 16;
+    void* host_counts = nullptr;  // page-locked: the per-frame counts are copied into it on the stream
+    if (CheckFlow2DError(flow2d_host_alloc(context_, frame_count * sizeof(unsigned long long), &host_counts), "flow2d_host_alloc"))
+        return false;
+    unsigned long long* counts = static_cast<unsigned long long*>(host_counts);
+    const size_t table_bytes = capacity * sizeof(float);
+    auto seed = [&](size_t k) {
+        return !CheckFlow2DError(flow2d_seed_points_2d(context_, AsPlane(dev_frames[k]), W, H, pitch, spacing, min_eigenvalue,
+                                                       AsPlane(dev_xs[k]), AsPlane(dev_ys[k]), dev_count, capacity, nullptr,
+                                                       workspace, workspace_bytes),
+                                 "flow2d_seed_points_2d") &&
+               !CheckFlow2DError(flow2d_copy_d2h_2d(context_, counts + k, sizeof(unsigned long long), dev_count,
+                                                    sizeof(unsigned long long), sizeof(unsigned long long), 1),
+                                 "flow2d_copy_d2h_2d");
+    };
+    // table 0: no track yet (all NaN: 0xff bytes), count 0, then the initial seeding
+    bool ok = !CheckFlow2DError(flow2d_memset_2d(context_, AsPlane(dev_xs[0]), table_bytes, 0xff, table_bytes, 1), "flow2d_memset_2d") &&
+              !CheckFlow2DError(flow2d_memset_2d(context_, AsPlane(dev_ys[0]), table_bytes, 0xff, table_bytes, 1), "flow2d_memset_2d") &&
+              !CheckFlow2DError(flow2d_memset_2d(context_, dev_count, 16, 0, 16, 1), "flow2d_memset_2d") && seed(0);
+    const DevicePtr* f = tracking_flows_.data();  // pair j of a window: u, v, back u, back v at 4 j
+    for (size_t start = 0; ok && start + 1 < frame_count; start += window) {
+        const size_t pairs = std::min(window, frame_count - 1 - start);
+        std::vector<DevicePtr> us(pairs), vs(pairs), bus(pairs), bvs(pairs);
+        for (size_t j = 0; j < pairs; ++j) {
+            us[j] = f[4 * j];
+            vs[j] = f[4 * j + 1];
+            bus[j] = f[4 * j + 2];
+            bvs[j] = f[4 * j + 3];
+        }
+        ok = ComputeFlowBidirectionalDevice(dev_frames + start, pairs + 1, us.data(), vs.data(), bus.data(), bvs.data(), nullptr,
+                                            nullptr, params);
+        for (size_t j = 0; ok && j < pairs; ++j) {
+            const size_t k = start + j;
+            ok = !CheckFlow2DError(flow2d_track_points_2d(context_, AsPlane(us[j]), AsPlane(vs[j]), AsPlane(bus[j]), AsPlane(bvs[j]),
+                                                          W, H, pitch, AsPlane(dev_xs[k]), AsPlane(dev_ys[k]), dev_count,
+                                                          capacity, alpha1, alpha2, check_boundaries ? 1 : 0, beta1, beta2,
+                                                          AsPlane(dev_xs[k + 1]), AsPlane(dev_ys[k + 1]), nullptr),
+                                   "flow2d_track_points_2d") &&
+                 seed(k + 1);
+        }
+    }
+    ok = !CheckFlow2DError(flow2d_synchronize(context_), "flow2d_synchronize") && ok;  // the only host wait
+    if (ok)
+        for (size_t k = 0; k < frame_count; ++k) counts_out[k] = counts[k];
+    flow2d_host_free(context_, host_counts);
+    return ok;
+}
+
+void OpticalFlow2D::TrackPoints(Data2D* const* frames, size_t frame_count, size_t spacing, float min_eigenvalue,
+                                bool check_boundaries, float beta1, float beta2, float* xs, float* ys, size_t capacity,
+                                unsigned long long* counts_out, OperationParameters& params)
+{
+    last_run_ok_ = false;
+    if (!IsInitialized() || !frames || !xs || !ys || !counts_out || frame_count < 2 || capacity == 0) return;
+    if (group_ > 1) {
+        std::printf("Error: '%s': sequences and lock-step groups do not combine.\n", GetName());
+        return;
+    }
+    const size_t W = dev_container_size_.width, H = dev_container_size_.height, pitch = dev_container_size_.pitch;
+    for (size_t k = 0; k < frame_count; ++k)
+        if (!frames[k] || frames[k]->Width() != W || frames[k]->Height() != H) {
+            std::printf("Error: '%s': frame sizes do not match the initialised size %zu x %zu.\n", GetName(), W, H);
+            return;
+        }
+    // the frames and the tables of this call (freed at its end)
+    std::vector<DevicePtr> dev_frames(frame_count, 0), dev_xs(frame_count, 0), dev_ys(frame_count, 0);
+    bool ok = EnsurePlanes(dev_frames.data(), frame_count);
+    for (size_t k = 0; ok && k < frame_count; ++k) ok = (dev_xs[k] = AllocBytes(capacity * 4)) && (dev_ys[k] = AllocBytes(capacity * 4));
+    std::printf("\nStarting optical flow computation...\n");
+    void *ev_start = nullptr, *ev_stop = nullptr;
+    flow2d_event_create(context_, &ev_start);
+    flow2d_event_create(context_, &ev_stop);
+    flow2d_event_record(context_, ev_start);
+    for (size_t k = 0; ok && k < frame_count; ++k) ok = CopyData2DtoDevice(*frames[k], dev_frames[k], H, pitch);
+    ok = ok && TrackPointsDevice(dev_frames.data(), frame_count, spacing, min_eigenvalue, check_boundaries, beta1, beta2,
+                                 dev_xs.data(), dev_ys.data(), capacity, counts_out, params);
+    const size_t table_bytes = capacity * sizeof(float);
+    for (size_t k = 0; ok && k < frame_count; ++k)
+        ok = !CheckFlow2DError(flow2d_copy_d2h_2d(context_, xs + k * capacity, table_bytes, AsPlane(dev_xs[k]), table_bytes,
+                                                  table_bytes, 1),
+                               "flow2d_copy_d2h_2d") &&
+             !CheckFlow2DError(flow2d_copy_d2h_2d(context_, ys + k * capacity, table_bytes, AsPlane(dev_ys[k]), table_bytes,
+                                                  table_bytes, 1),
+                               "flow2d_copy_d2h_2d");
+    flow2d_event_record(context_, ev_stop);
+    flow2d_event_synchronize(context_, ev_stop);  // the downloads
+    flow2d_event_elapsed_ms(context_, ev_start, ev_stop, &last_total_ms_);
+    std::printf("Total GPU computation time: % 4.4fs\n", last_total_ms_ / 1000.);
+    flow2d_event_destroy(context_, ev_start);
+    flow2d_event_destroy(context_, ev_stop);
+    flow2d_synchronize(context_);
+    for (const std::vector<DevicePtr>* planes : {&dev_frames, &dev_xs, &dev_ys})
+        for (DevicePtr p : *planes)
+            if (p) flow2d_plane_free(context_, AsPlane(p));
+    last_run_ok_ = ok;
 }
 
 void OpticalFlow2D::ResetLevelTimings()

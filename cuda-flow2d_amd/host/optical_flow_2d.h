@@ -119,6 +119,29 @@ public:
                            Data2D* flow_u = nullptr, Data2D* flow_v = nullptr, Data2D* back_u = nullptr,
                            Data2D* back_v = nullptr, Data2D* occlusion_0 = nullptr, Data2D* occlusion_1 = nullptr);
 
+    // Dense point trajectories through a sequence (Sundaram, Brox & Keutzer, ECCV 2010; no reference counterpart).
+    // dev_xs[k] / dev_ys[k] (k < frame_count) are the track table of frame k: `capacity` floats each, slot i = track i's
+    // position in frame k, NaN where the track has not started or has ended (a track never restarts).  Frame 0 is seeded
+    // (flow2d_seed_points_2d, grid `spacing`, threshold min_eigenvalue); then for every pair k both flows are computed --
+    // bit-identical to ComputeFlowBidirectionalDevice on the sequence --, flow2d_track_points_2d carries table k into table
+    // k + 1 (forward-backward thresholds: the bag keys consistency_alpha1 / consistency_alpha2, 0.01 / 0.5; motion boundaries
+    // with beta1 / beta2 when check_boundaries) and frame k + 1 is seeded.  counts_out[k] (host, frame_count entries) gets the
+    // track count after frame k's seeding, read back once at the end (the call synchronises).  Flows are computed in windows
+    // of kTrackWindow pairs (pyramids shared inside a window) in planes allocated once: the device memory beyond the caller's
+    // tables does not grow with frame_count.  The tables must be distinct and not frames.  Eager; not for lock-step groups.
+    static constexpr size_t kTrackWindow = 4;
+    // The CLI's seeding threshold (lambda_min of unnormalised 5x5 sums of grey-level gradients; scale-dependent): it keeps
+    // the analytic scenes' textures (profiles/tracking/) and drops flat areas.
+    static constexpr float kDefaultTrackMinEigenvalue = 1.0f;
+    bool TrackPointsDevice(const DevicePtr* dev_frames, size_t frame_count, size_t spacing, float min_eigenvalue,
+                           bool check_boundaries, float beta1, float beta2, const DevicePtr* dev_xs, const DevicePtr* dev_ys,
+                           size_t capacity, unsigned long long* counts_out, OperationParameters& params);
+    // The host-image form (the CLI's --track): upload the frames (frames[k] -> frame k), TrackPointsDevice, download the tables into xs / ys (frame_count * capacity
+    // floats each, table k at k * capacity).  LastRunSucceeded and LastTotalMs as for ComputeFlow.
+    void TrackPoints(Data2D* const* frames, size_t frame_count, size_t spacing, float min_eigenvalue, bool check_boundaries,
+                     float beta1, float beta2, float* xs, float* ys, size_t capacity, unsigned long long* counts_out,
+                     OperationParameters& params);
+
     // When set, ComputeFlowDevice records the whole pyramid of a pair into a HIP graph the first time it
     // sees a (buffers, parameters) combination and replays it afterwards: one host call instead of
     // several hundred launches.  Ignored while timing_mode != 0 (events are not captured).
@@ -217,6 +240,12 @@ private:
     // !use_masks)
     bool QueueInterpolation(DevicePtr frame_0, DevicePtr frame_1, const DevicePtr* flows, bool use_masks, const float* times,
                             size_t time_count, const DevicePtr* outputs, int iterations, float max_residual);
+    // TrackPointsDevice: the flows of a window (u, v, back u, back v per pair) and, in one allocation, the device count and the
+    // seeding workspace (allocated on first use, the scratch regrown when a call needs more)
+    std::vector<DevicePtr> tracking_flows_;
+    DevicePtr tracking_scratch_ = 0;
+    size_t tracking_scratch_bytes_ = 0;
+    DevicePtr AllocBytes(size_t bytes);
     flow2d_context* context_ = nullptr;
     // One plane beside the pool: the warped frame of a level, when the levels of both frames are computed up front into plane
     // regions of their own (RunPyramid: "stacked" levels) and therefore cannot be overwritten by the warp

@@ -19,6 +19,14 @@ I0(y + w_b(y)) = I1(y) at every pixel y of frame 1 that is not occluded --, occl
 the scene has none), frame_0_at(x, y) (the analytic frame 0), back_flow_at(x, y) (the backward flow at any real coordinates,
 double) and frame_at_time(t): the exact frame at time t, 0 <= t <= 1, on
 the linear trajectories x + t * w(x) (frame_0 at t = 0, frame_1 at t = 1).
+Sequences (make_sequence(name, frame_count, width, height, seed)), for point tracking (flow2d_track_points_2d): the same scenes
+carried on for frame_count frames with the same textures (frames 0 and 1 are make_scene's).  Affine scenes: frame k is the
+texture at W^-k(x), W the scene's motion; two_layer: the square has moved by k * t in frame k.  Each Sequence carries frames
+[frame_count, h, w], the true flows of every pair k -- gt_u[k], gt_v[k] (frame k -> k+1) and gt_back_u[k], gt_back_v[k]
+(frame k+1 -> k) --, frame_at(k, x, y) (the analytic frame k, double), trajectory(x, y, k, start=0) (where the point at (x, y)
+in frame `start` is in frame k, double) and visible(x, y, k, start=0): whether that point is seen in frame k (affine scenes:
+inside the frame; two_layer: a background point is hidden while the square covers it, a square point is lost once it has left
+the frame).
 Pure numpy: no device, no library.
 """
 import numpy as np
@@ -161,4 +169,116 @@ def make_scene(name, width=256, height=256, seed=0):
     if name == "two_layer":
         square = Texture(rng, amplitude=(50.0, 35.0, 20.0), periods=(29.0, 13.1, 19.7))
         return _two_layer_scene(width, height, texture, square, (4.5, -2.25))
+    raise ValueError("unknown scene %r (one of %s)" % (name, ", ".join(SCENES)))
+
+
+class Sequence:
+    def __init__(self, name, frame_count, width, height, frame_at, step, back_step, in_square=None):
+        self.name = name
+        self.frame_count = frame_count
+        self.width, self.height = width, height
+        self.frame_at = frame_at
+        self._step = step            # (x, y, k, on) -> position in frame k + 1 of the point at (x, y) in frame k (on: two_layer,
+                                     # the point lies on the square)
+        self._in_square = in_square  # two_layer: (x, y, k) -> the point lies on the square in frame k
+        ys, xs = np.mgrid[0:height, 0:width].astype(np.float64)
+        self.frames = np.stack([frame_at(k, xs, ys) for k in range(frame_count)]).astype(np.float32)
+        fwd = [step(xs, ys, k, None if in_square is None else in_square(xs, ys, k)) for k in range(frame_count - 1)]
+        bwd = [back_step(xs, ys, k) for k in range(frame_count - 1)]
+        self.gt_u = np.stack([p[0] - xs for p in fwd]).astype(np.float32)
+        self.gt_v = np.stack([p[1] - ys for p in fwd]).astype(np.float32)
+        self.gt_back_u = np.stack([p[0] - xs for p in bwd]).astype(np.float32)
+        self.gt_back_v = np.stack([p[1] - ys for p in bwd]).astype(np.float32)
+
+    def _inside(self, x, y):
+        return (x >= 0) & (x <= self.width - 1) & (y >= 0) & (y <= self.height - 1)
+
+    def trajectory(self, x, y, k, start=0):
+        """(x, y) in frame k (k >= start) of the point at (x, y) in frame `start`, in double."""
+        x, y = np.asarray(x, np.float64), np.asarray(y, np.float64)
+        on = None if self._in_square is None else self._in_square(x, y, start)  # two_layer: the point's layer
+        for j in range(start, k):
+            x, y = self._step(x, y, j, on)
+        return x, y
+
+    def visible(self, x, y, k, start=0):
+        """Whether the point at (x, y) in frame `start` is seen in frame k: inside the frame in every frame start .. k and, on
+        two_layer, a background point not covered by the square in frame k."""
+        x, y = np.asarray(x, np.float64), np.asarray(y, np.float64)
+        seen = self._inside(x, y)
+        square = None if self._in_square is None else self._in_square(x, y, start)
+        for j in range(start, k):
+            x, y = self._step(x, y, j, square)
+            seen = seen & self._inside(x, y)
+        if square is not None:
+            seen = seen & (square | ~self._in_square(x, y, k))
+        return seen
+
+
+def _affine_sequence(name, frame_count, width, height, texture, a, t):
+    a = np.asarray(a, np.float64)
+    t = np.asarray(t, np.float64)
+    c = np.array([(width - 1) / 2.0, (height - 1) / 2.0])
+    inv = np.linalg.inv(a)
+
+    def back_step(x, y, k):  # W^-1, the operation order of _affine_scene's frame_1_at
+        px, py = np.asarray(x, np.float64) - c[0] - t[0], np.asarray(y, np.float64) - c[1] - t[1]
+        return inv[0, 0] * px + inv[0, 1] * py + c[0], inv[1, 0] * px + inv[1, 1] * py + c[1]
+
+    def step(x, y, k, on=None):  # W
+        dx, dy = np.asarray(x, np.float64) - c[0], np.asarray(y, np.float64) - c[1]
+        return a[0, 0] * dx + a[0, 1] * dy + c[0] + t[0], a[1, 0] * dx + a[1, 1] * dy + c[1] + t[1]
+
+    def frame_at(k, x, y):
+        for _ in range(k):
+            x, y = back_step(x, y, 0)
+        return texture(x, y)
+
+    return Sequence(name, frame_count, width, height, frame_at, step, back_step)
+
+
+def _two_layer_sequence(frame_count, width, height, background, square, t):
+    n = max(4, min(width, height) // 4)
+    x0, y0 = (width - n) // 2 - n // 4, (height - n) // 2
+    tx, ty = t
+
+    def in_square(x, y, k):
+        sx, sy = k * tx, k * ty
+        return (x >= x0 + sx) & (x < x0 + n + sx) & (y >= y0 + sy) & (y < y0 + n + sy)
+
+    def frame_at(k, x, y):
+        x, y = np.asarray(x, np.float64), np.asarray(y, np.float64)
+        return np.where(in_square(x, y, k), square(x - k * tx, y - k * ty), background(x, y))
+
+    def step(x, y, k, on):
+        x, y = np.asarray(x, np.float64), np.asarray(y, np.float64)
+        return np.where(on, x + tx, x), np.where(on, y + ty, y)
+
+    def back_step(x, y, k):  # frame k + 1 -> frame k
+        x, y = np.asarray(x, np.float64), np.asarray(y, np.float64)
+        on = in_square(x, y, k + 1)
+        return np.where(on, x - tx, x), np.where(on, y - ty, y)
+
+    return Sequence("two_layer", frame_count, width, height, frame_at, step, back_step, in_square)
+
+
+def make_sequence(name, frame_count=10, width=256, height=256, seed=0):
+    """The scene `name` (one of SCENES) carried on for frame_count (>= 2) frames; frames 0 and 1 are those of make_scene."""
+    if frame_count < 2:
+        raise ValueError("a sequence has at least two frames")
+    rng = np.random.default_rng(seed)
+    texture = Texture(rng)
+    if name == "translation":
+        return _affine_sequence(name, frame_count, width, height, texture, np.eye(2), (2.3, -1.4))
+    if name == "rotation":
+        phi = np.radians(3.0)
+        return _affine_sequence(name, frame_count, width, height, texture,
+                                [[np.cos(phi), -np.sin(phi)], [np.sin(phi), np.cos(phi)]], (0, 0))
+    if name == "zoom":
+        return _affine_sequence(name, frame_count, width, height, texture, 1.03 * np.eye(2), (0, 0))
+    if name == "affine":
+        return _affine_sequence(name, frame_count, width, height, texture, [[1.02, 0.03], [-0.02, 0.985]], (1.25, -0.6))
+    if name == "two_layer":
+        square = Texture(rng, amplitude=(50.0, 35.0, 20.0), periods=(29.0, 13.1, 19.7))
+        return _two_layer_sequence(frame_count, width, height, texture, square, (4.5, -2.25))
     raise ValueError("unknown scene %r (one of %s)" % (name, ", ".join(SCENES)))

@@ -34,8 +34,9 @@ extern "C" {
 #define FLOW2D_API __attribute__((visibility("default")))
 
 /* Additions that leave every existing entry as it was keep the version: flow2d_consistency_2d (forward-backward occlusion
- * masks), flow2d_flow_error_2d / flow2d_flow_error_workspace_bytes (error statistics against ground truth) and
- * flow2d_interpolate_2d (occlusion-aware frame interpolation) were added under 1. */
+ * masks), flow2d_flow_error_2d / flow2d_flow_error_workspace_bytes (error statistics against ground truth),
+ * flow2d_interpolate_2d (occlusion-aware frame interpolation) and flow2d_track_points_2d / flow2d_seed_points_2d /
+ * flow2d_seed_points_workspace_bytes (dense point trajectories) were added under 1. */
 #define FLOW2D_ABI_VERSION 1
 
 typedef enum flow2d_status {
@@ -250,6 +251,76 @@ FLOW2D_API int flow2d_interpolate_2d(flow2d_context* ctx, const float* frame_0, 
                                      const float* flow_v, const float* back_u, const float* back_v, const float* occlusion_0,
                                      const float* occlusion_1, size_t width, size_t height, size_t pitch_bytes, float t,
                                      int iterations, float max_residual, float* output);
+
+/* Dense point trajectories (Sundaram, Brox & Keutzer, ECCV 2010; no reference counterpart; added to ABI version 1 without
+ * changing any existing entry).  A track table is `capacity` floats of x and `capacity` floats of y (device memory); slot i
+ * holds a track's position in one frame, NaN where the track has not started or has ended.  `count` (DEVICE memory, read on
+ * the device, never by the host) is the number of slots in use.
+ *
+ * flow2d_track_points_2d advances a table by one flow step.  (flow_u, flow_v): the flow of frame k to frame k+1; (back_u,
+ * back_v): the flow of frame k+1 to frame k, or both NULL (no forward-backward check).  For every slot i < capacity, with
+ * n = *count, the first of these that applies gives `reason[i]` (when `reason` is not NULL), in fp32 and in this order:
+ *   1 INACTIVE         i >= n, or x[i] or y[i] is not finite
+ *   3 LEFT_FRAME       p = (x[i], y[i]) outside [0, width - 1] x [0, height - 1]
+ *                      u0 = S(flow_u, p), v0 = S(flow_v, p)   (S: the bilinear sample of flow2d_consistency_2d, same order)
+ *   2 MOTION_BOUNDARY  only when check_boundaries != 0:  (ix, iy) = ((int)floorf(px + 0.5f), (int)floorf(py + 0.5f));
+ *                      ux = 0.5f * (U[iy][min(ix+1, width-1)] - U[iy][max(ix-1, 0)]),
+ *                      uy = 0.5f * (U[min(iy+1, height-1)][ix] - U[max(iy-1, 0)][ix]), vx, vy likewise on V;
+ *                      g = (ux*ux + uy*uy) + (vx*vx + vy*vy);  !(g <= beta1 * (u0*u0 + v0*v0) + beta2)  (a NaN lands here;
+ *                      the paper's values are beta1 = 0.01, beta2 = 0.002)
+ *                      q = (px + u0, py + v0)
+ *   4 OCCLUDED         q not finite
+ *   3 LEFT_FRAME       q outside the frame
+ *   4 OCCLUDED         only with back planes: bu = S(back_u, q), bv = S(back_v, q), eu = u0 + bu, ev = v0 + bv;
+ *                      !(eu*eu + ev*ev <= alpha1 * ((u0*u0 + v0*v0) + (bu*bu + bv*bv)) + alpha2)  (the inequality of
+ *                      flow2d_consistency_2d at the track's sub-pixel position)
+ *   0 ALIVE            out_x[i] = qx, out_y[i] = qy
+ * Whenever the reason is not 0, out_x[i] = out_y[i] = NaN.  Every slot below `capacity` is written.
+ * FLOW2D_ERR_INVALID_ARGUMENT for a null required pointer or only one back plane, a zero size or capacity, a bad pitch (the
+ * rule of flow2d_interpolate_2d), a negative or non-finite alpha or beta, or outputs (out_x, out_y, reason) whose bytes overlap
+ * those of any input (planes: height * pitch_bytes; tables: 4 * capacity; count: 8) or each other.
+ * FLOW2D_ERR_UNSUPPORTED under a lock-step batch (flow2d_context_set_batch count above 1) and for capacity >= 2^40.  Slot
+ * offsets are 64-bit.  One launch, no allocation, no synchronisation (graph-capturable). */
+typedef enum flow2d_track_reason {
+    FLOW2D_TRACK_ALIVE = 0,
+    FLOW2D_TRACK_INACTIVE = 1,
+    FLOW2D_TRACK_MOTION_BOUNDARY = 2,
+    FLOW2D_TRACK_LEFT_FRAME = 3,
+    FLOW2D_TRACK_OCCLUDED = 4
+} flow2d_track_reason;
+FLOW2D_API int flow2d_track_points_2d(flow2d_context* ctx, const float* flow_u, const float* flow_v, const float* back_u,
+                                      const float* back_v, size_t width, size_t height, size_t pitch_bytes, const float* x,
+                                      const float* y, const unsigned long long* count /* device */, size_t capacity,
+                                      float alpha1, float alpha2, int check_boundaries, float beta1, float beta2, float* out_x,
+                                      float* out_y, unsigned char* reason /* may be NULL */);
+
+/* flow2d_seed_points_2d appends new tracks in uncovered, textured cells of `frame`.  With s = spacing:
+ *   cells          ceil(width / s) x ceil(height / s); cell (i, j) holds the pixels [i*s, (i+1)*s) x [j*s, (j+1)*s); its seed
+ *                  pixel is (min(i*s + s/2, width - 1), min(j*s + s/2, height - 1)) (integer division; s = 1: every pixel)
+ *   covered        some slot k < *count has finite x[k], y[k] inside [0, width - 1] x [0, height - 1] with
+ *                  ((int)floorf(x[k]) / s, (int)floorf(y[k]) / s) == (i, j)
+ *   seedable       min_eigenvalue == 0, or lambda_min >= min_eigenvalue at the seed pixel, where
+ *                  gx = 0.5f * (F[y][min(x+1, width-1)] - F[y][max(x-1, 0)]), gy likewise along y (clamped neighbours);
+ *                  a = sum gx*gx, b = sum gx*gy, c = sum gy*gy over the 5x5 window around the seed pixel, coordinates
+ *                  clamped to the frame (edge-replicated), each sum from 0.0f in row-major order;
+ *                  lambda_min = 0.5f*(a + c) - sqrtf(0.25f*(a - c)*(a - c) + b*b)   (correctly rounded sqrtf)
+ * Every uncovered, seedable cell, in row-major cell order, gets slot *count + m (m = 0, 1, ...) with x, y = its seed pixel,
+ * until `capacity` is reached; *count grows by the number written and *dropped (when not NULL, DEVICE memory) gets the number
+ * of cells that did not fit.  Slots below the old *count are not touched.  Deterministic: the slot of a seed depends only on
+ * the cell order (per-block counts, a scan in block order, the writes; no atomics), so repeats and graph replays write the
+ * same bytes.  *count == 0 is the initial seeding of a sequence.  Five launches into the caller's `workspace` (16-byte
+ * aligned, at least flow2d_seed_points_workspace_bytes(width, height, spacing) bytes), no allocation, no synchronisation
+ * (graph-capturable).  min_eigenvalue is in the units of unnormalised sums of squared grey-level gradients.
+ * FLOW2D_ERR_INVALID_ARGUMENT for a null required pointer, a zero size, spacing or capacity, a bad pitch, a negative or
+ * non-finite min_eigenvalue, a misaligned count / dropped / workspace, a workspace too small, or overlapping bytes among
+ * frame, x, y, count, dropped and the workspace.  FLOW2D_ERR_UNSUPPORTED under a lock-step batch, for capacity >= 2^40 and
+ * for 2^32 cells or more. */
+FLOW2D_API size_t flow2d_seed_points_workspace_bytes(size_t width, size_t height, size_t spacing);
+FLOW2D_API int flow2d_seed_points_2d(flow2d_context* ctx, const float* frame, size_t width, size_t height, size_t pitch_bytes,
+                                     size_t spacing, float min_eigenvalue, float* x, float* y,
+                                     unsigned long long* count /* device, read and updated */, size_t capacity,
+                                     unsigned long long* dropped /* device, may be NULL */, void* workspace,
+                                     size_t workspace_bytes);
 
 /* Error of a flow estimate against ground truth (Barron et al. 1994, Baker et al. 2011 -- Middlebury --, Menze & Geiger 2015 --
  * KITTI --; no reference counterpart; added to ABI version 1 without changing any existing entry).
