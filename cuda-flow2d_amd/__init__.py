@@ -149,6 +149,7 @@ def hip_lib():
         L.flow2d_context_device.argtypes = [vp, C.POINTER(i)]
         L.flow2d_context_stream.argtypes = [vp, C.POINTER(vp)]
         L.flow2d_synchronize.argtypes = [vp]
+        L.flow2d_context_set_batch.argtypes = [vp, sz, sz]
         L.flow2d_mem_info.argtypes = [vp, C.POINTER(sz), C.POINTER(sz)]
         L.flow2d_device_name.argtypes = [vp, C.c_char_p, sz]
         L.flow2d_plane_pitch_bytes.restype = sz
@@ -281,6 +282,19 @@ class Plane:
             self.ptr = None
 
 
+class _BatchScope:
+    """What Context.set_batch returns: leaving the `with` block switches the lock-step batch off again."""
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+
+    def __enter__(self):
+        return self.ctx
+
+    def __exit__(self, *exc):
+        _check(hip_lib().flow2d_context_set_batch(self.ctx.handle, 1, 0), "flow2d_context_set_batch")
+
+
 class Context:
     """One device + stream (reference: the CUcontext of main.cpp:51 plus the NULL stream)."""
 
@@ -326,6 +340,13 @@ class Context:
     def set_lone(self, lone):
         """flow2d_context_set_lone: this context's launches run alone on the device (packed strip build for under-filled launches)"""
         _check(hip_lib().flow2d_context_set_lone(self.handle, int(bool(lone))), "flow2d_context_set_lone")
+
+    def set_batch(self, count, stride_bytes=0):
+        """flow2d_context_set_batch: from now on every batch-aware launcher of this context acts on `count` instances of its
+        planes, `stride_bytes` apart (count = 1: off).  The switch is made at once; the value returned is a context manager
+        that goes back to count = 1 on exit:  `with ctx.set_batch(3, stride): ...`."""
+        _check(hip_lib().flow2d_context_set_batch(self.handle, count, stride_bytes), "flow2d_context_set_batch")
+        return _BatchScope(self)
 
     def resample_y_levels(self, packed_a, out_a, in_height, widths, heights, columns, rows, packed_b=None, out_b=None):
         """the y passes of several pyramid levels in one launch (flow2d_resample_y_levels)"""

@@ -96,7 +96,12 @@ FLOW2D_API int flow2d_synchronize(flow2d_context* ctx); /* cuStreamSynchronize(N
  * multiple of 16).  One launch then holds the work of all instances (grid.z), so a level of a mid-size frame fills the
  * chip and the launch-bound coarse levels cost one launch per batch instead of one per pair.  count = 1 switches it
  * off (the default).  Results per instance are those of the unbatched call.  At most FLOW2D_BATCH_MAX instances (the
- * two-plane launches put 2 x count into grid.z). */
+ * two-plane launches put 2 x count into grid.z).  count > 1 needs a non-zero stride that is a multiple of 16; count = 1
+ * accepts any stride and ignores it.
+ * Exceptions, which act as without a batch or refuse it: flow2d_copy_planes (its tables name every plane),
+ * flow2d_copy_h2d_2d / flow2d_copy_d2h_2d (they move the one region asked for; a caller moves a whole group with
+ * height = count x rows when the instances lie one below the other), flow2d_plane_alloc / flow2d_plane_free, and
+ * flow2d_track_points_2d / flow2d_seed_points_2d, which return FLOW2D_ERR_UNSUPPORTED under a batch. */
 #define FLOW2D_BATCH_MAX 32767
 FLOW2D_API int flow2d_context_set_batch(flow2d_context* ctx, size_t count, size_t stride_bytes);
 /* A hint, not a mode: lone != 0 says that the caller runs this context's launches alone on the device -- one pair after the

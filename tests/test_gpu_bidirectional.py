@@ -80,15 +80,12 @@ def test_kernel_lock_step_batch(flow2d, ctx):
     out = ctx.plane(w, 2 * h)
     out.fill_bytes(0x7F)
     stride = planes[0].pitch * h
-    assert lib.flow2d_context_set_batch(ctx.handle, ctypes.c_size_t(2), ctypes.c_size_t(stride)) == 0
-    try:
+    with ctx.set_batch(2, stride):
         ctx.consistency(*planes, w, h, out, 0.02, 0.75)
         # the mask must not meet the second instance of an input either: a base inside u's second instance is refused
         assert lib.flow2d_consistency_2d(ctx.handle, planes[0].ptr, planes[1].ptr, planes[2].ptr, planes[3].ptr, w, h,
                                          planes[0].pitch, ctypes.c_float(0.01), ctypes.c_float(0.5),
                                          planes[0].ptr + stride) == 1
-    finally:
-        assert lib.flow2d_context_set_batch(ctx.handle, ctypes.c_size_t(1), ctypes.c_size_t(0)) == 0
     ctx.synchronize()
     got = out.download()
     for k, c in enumerate(cases):

@@ -160,15 +160,12 @@ def test_lock_step_group_equals_lone_calls(flow2d, ctx):
     planes = [ctx.plane(w, n * h, np.vstack([c[i] for c in cases])) for i in range(5)]
     epe, ae = ctx.plane(w, n * h), ctx.plane(w, n * h)
     stride = planes[0].pitch * h
-    assert lib.flow2d_context_set_batch(ctx.handle, ctypes.c_size_t(n), ctypes.c_size_t(stride)) == 0
-    try:
+    with ctx.set_batch(n, stride):
         group = ctx.flow_error(*planes[:4], w, h, occlusion=planes[4], epe=epe, ae=ae, instances=n)
         # the outputs must not meet another instance of an input either: an epe plane inside u's second instance is refused
         ws = ctx._flow_error_buffers
         assert lib.flow2d_flow_error_2d(ctx.handle, planes[0].ptr, planes[1].ptr, planes[2].ptr, planes[3].ptr, None, w, h,
                                         planes[0].pitch, planes[0].ptr + stride, None, ws[3].ptr, ws[2].ptr, ws[0]) == 1
-    finally:
-        assert lib.flow2d_context_set_batch(ctx.handle, ctypes.c_size_t(1), ctypes.c_size_t(0)) == 0
     ge, ga = epe.download(), ae.download()
     assert len(group) == n
     for k, c in enumerate(cases):

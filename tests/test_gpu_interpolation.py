@@ -121,14 +121,11 @@ def test_lock_step_batch(flow2d, ctx):
     out = ctx.plane(w, n * h)
     out.fill_bytes(0x7F)
     stride = planes[0].pitch * h
-    assert lib.flow2d_context_set_batch(ctx.handle, ctypes.c_size_t(n), ctypes.c_size_t(stride)) == 0
-    try:
+    with ctx.set_batch(n, stride):
         ctx.interpolate(*planes[:6], w, h, 0.3, out, planes[6], planes[7], 2, 0.5)
         # the output must not meet a later instance of an input either
         assert lib.flow2d_interpolate_2d(ctx.handle, *[p.ptr for p in planes], w, h, planes[0].pitch, ctypes.c_float(0.3), 2,
                                          ctypes.c_float(0.5), planes[7].ptr + 2 * stride) == 1
-    finally:
-        assert lib.flow2d_context_set_batch(ctx.handle, ctypes.c_size_t(1), ctypes.c_size_t(0)) == 0
     ctx.synchronize()
     got = out.download()
     for k, c in enumerate(cases):

@@ -372,6 +372,34 @@ def test_host_library_exports_the_batch_entry(flow2d):
     assert not host.flow2d_host_batch_create(64, 64, 0, 0, 0, 1)         # zero lanes
 
 
+def test_set_batch_limits_without_a_device(flow2d):
+    """flow2d_context_set_batch on a zeroed stand-in for a context (host logic only): FLOW2D_BATCH_MAX = 32767 instances are
+    accepted -- two planes x 32767 is the last grid.z that fits --, no instances, one more than the limit, a zero stride and a
+    stride that is no multiple of 16 are refused for a group; count = 1 takes any stride and switches the mode off.  The mode is
+    read back through an entry that refuses a batch before it touches the device (flow2d_track_points_2d)."""
+    import ctypes
+    lib = flow2d.hip_lib()
+    fake = ctypes.create_string_buffer(4096)
+    ctx = ctypes.addressof(fake)
+
+    def batched():
+        p = [0x1000000 * (k + 1) for k in range(10)]
+        return lib.flow2d_track_points_2d(ctx, p[0], p[1], p[2], p[3], 64, 8, 256, p[4], p[5], p[6], 1000, 0.01, 0.5, 1, 0.01, 0.002,
+                                          p[7], p[8], p[9])
+
+    assert lib.flow2d_context_set_batch(ctx, 32767, 2048) == 0 and batched() == 5
+    for count, stride in ((0, 2048), (32768, 2048), (1 << 40, 2048), (2, 0), (2, 24), (2, 2056), (32767, 4)):
+        assert lib.flow2d_context_set_batch(ctx, count, stride) == 1, (count, stride)
+        assert batched() == 5  # a refused call leaves the group as it was
+    assert lib.flow2d_context_set_batch(ctx, 2, 16) == 0 and batched() == 5  # the contract asks for 16 bytes, no more
+    for stride in (0, 24, 4, 2048):
+        assert lib.flow2d_context_set_batch(ctx, 3, 4096) == 0 and batched() == 5
+        assert lib.flow2d_context_set_batch(ctx, 1, stride) == 0, stride
+        if flow2d.device_count() == 0:  # past the refusal the entry reaches the device guard: a device error, not a refusal
+            assert batched() == 3, stride
+    assert flow2d.Context.set_batch.__doc__ and lib.flow2d_context_set_batch(None, 1, 0) == 1
+
+
 def test_plain_c_client_links_and_runs_without_a_device(flow2d, tmp_path):
     """tests/c/abi_link.c: a C99 program against include/flow2d_c_abi.h and libflow2d_hip.so (no C++ in between)."""
     exe = tmp_path / "abi_link"
