@@ -213,6 +213,10 @@ def hip_lib():
             L.flow2d_seed_points_workspace_bytes.restype = sz
             L.flow2d_seed_points_workspace_bytes.argtypes = [sz, sz, sz]
             L.flow2d_seed_points_2d.argtypes = [vp, vp, sz, sz, sz, sz, f, vp, vp, vp, sz, vp, vp, sz]
+        if hasattr(L, "flow2d_denoise_2d"):  # (absent from libraries of earlier rounds loaded for an A/B)
+            L.flow2d_denoise_2d.argtypes = [vp, vp, sz, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), sz, sz, sz, f,
+                                            vp, vp]
+            L.flow2d_compose_flow_2d.argtypes = [vp] * 7 + [sz, sz, sz, vp, vp, vp]
         if hasattr(L, "flow2d_flow_error_2d"):  # (absent from libraries of earlier rounds loaded for an A/B)
             L.flow2d_flow_error_workspace_bytes.restype = sz
             L.flow2d_flow_error_workspace_bytes.argtypes = [sz, sz, sz]
@@ -460,6 +464,24 @@ class Context:
                                                occ_0.ptr if occ_0 else None, occ_1.ptr if occ_1 else None, w, h, u.pitch, t,
                                                iterations, max_residual, out.ptr), "flow2d_interpolate_2d")
 
+    def denoise(self, centre, frames, us, vs, w, h, out, occs=None, range_sigma=0.0, weight_sum=None):
+        """`centre` fused with the neighbour frames `frames` into `out` (flow2d_denoise_2d): (us[n], vs[n]) is the flow from the
+        centre to frames[n] on the centre's grid, occs[n] (the list, or any entry, may be None) its occlusion mask; range_sigma
+        (grey levels, 0 = off) the scale of the photometric weight; `weight_sum` an optional Plane for the sum of weights."""
+        n = len(frames)
+        arr = lambda q: (C.c_void_p * max(n, 1))(*[p.ptr if p is not None else None for p in q])  # noqa: E731
+        _check(hip_lib().flow2d_denoise_2d(self.handle, centre.ptr, n, arr(frames), arr(us), arr(vs),
+                                           None if occs is None else arr(occs), w, h, centre.pitch, range_sigma, out.ptr,
+                                           weight_sum.ptr if weight_sum else None), "flow2d_denoise_2d")
+
+    def compose_flow(self, ab_u, ab_v, bc_u, bc_v, w, h, out_u, out_v, mask_ab=None, mask_bc=None, out_mask=None):
+        """The flow a -> c on a's grid into (out_u, out_v) from the flows a -> b and b -> c (flow2d_compose_flow_2d): NaN where
+        a -> b leaves the frame.  With out_mask, the union of mask_ab, mask_bc carried along a -> b and the pixels that leave."""
+        _check(hip_lib().flow2d_compose_flow_2d(self.handle, ab_u.ptr, ab_v.ptr, bc_u.ptr, bc_v.ptr,
+                                                mask_ab.ptr if mask_ab else None, mask_bc.ptr if mask_bc else None, w, h,
+                                                ab_u.pitch, out_u.ptr, out_v.ptr, out_mask.ptr if out_mask else None),
+               "flow2d_compose_flow_2d")
+
     def track_points(self, u, v, bu, bv, w, h, x, y, count, capacity, out_x, out_y, reason=None, alpha1=0.01, alpha2=0.5,
                      boundaries=True, beta1=0.01, beta2=0.002):
         """One step of the track table (x, y) along the flow (u, v) into (out_x, out_y) (flow2d_track_points_2d).  Tables are
@@ -681,6 +703,11 @@ def host_lib():
             L.flow2d_host_track_points.argtypes = [vp, fp, sz, sz, f, i, f, f, fp, fp, sz, ull, C.POINTER(HostParams), f, f, fp]
             L.flow2d_host_track_points_device.argtypes = [vp, C.POINTER(vp), sz, sz, f, i, f, f, C.POINTER(vp), C.POINTER(vp), sz,
                                                           ull, C.POINTER(HostParams), f, f]
+        if hasattr(L, "flow2d_host_denoise_sequence"):
+            L.flow2d_host_denoise_args_ok.argtypes = [sz, sz, f]
+            L.flow2d_host_denoise_sequence.argtypes = [vp, fp, sz, sz, f, i, fp, fp, C.POINTER(HostParams), fp]
+            L.flow2d_host_denoise_sequence_device.argtypes = [vp, C.POINTER(vp), sz, sz, f, i, C.POINTER(vp), C.POINTER(vp),
+                                                              C.POINTER(HostParams)]
         L.flow2d_host_read_flo.argtypes = [C.c_char_p, C.POINTER(sz), C.POINTER(sz), fp, fp, sz]
         L.flow2d_host_write_flo.argtypes = [fp, fp, sz, sz, C.c_char_p]
         L.flow2d_host_flow_error.argtypes = [fp] * 5 + [sz, sz, fp, fp, C.POINTER(FlowErrorStats)]
@@ -903,6 +930,39 @@ class OpticalFlow:
         if rc:
             raise Flow2DError(rc, "OpticalFlow2D::TrackPointsDevice")
         return [int(c) for c in counts]
+
+    def denoise_sequence(self, frames, params, radius=1, range_sigma=0.0, masks=True, weight_sums=False):
+        """OpticalFlow2D::DenoiseSequence: motion-compensated temporal denoising of the host frames `frames` ([frame_count, h,
+        w]).  Frame k is averaged with the frames k - radius .. k + radius that exist, each sampled along the flow from frame k
+        (compute_flow_bidirectional on consecutive pairs, chained for distances of 2 and more), without what the occlusion masks
+        mark (masks) and, with range_sigma > 0 (grey levels), weighted by sigma^2 / (sigma^2 + difference^2)
+        (flow2d_denoise_2d).  Returns the fused frames [frame_count, h, w]; with weight_sums, (frames, sums of weights)."""
+        fr = np.ascontiguousarray(frames, np.float32)
+        if fr.ndim != 3 or fr.shape[1:] != (self.height, self.width):
+            raise ValueError("frames: [frame_count, %d, %d]" % (self.height, self.width))
+        out = np.empty_like(fr)
+        sums = np.empty_like(fr) if weight_sums else None
+        ms = C.c_float()
+        rc = host_lib().flow2d_host_denoise_sequence(self.handle, _fptr(fr), fr.shape[0], int(radius), range_sigma,
+                                                     int(bool(masks)), _fptr(out), None if sums is None else _fptr(sums),
+                                                     C.byref(params), C.byref(ms))
+        if rc:
+            raise Flow2DError(rc, "OpticalFlow2D::DenoiseSequence")
+        return (out, sums) if weight_sums else out
+
+    def denoise_sequence_device(self, dev_frames, dev_outputs, params, radius=1, range_sigma=0.0, masks=True,
+                                dev_weight_sums=None):
+        """OpticalFlow2D::DenoiseSequenceDevice: device frames in, frame k fused with its neighbours into dev_outputs[k] (and the
+        sum of weights into dev_weight_sums[k], when given).  Queued, not synchronised."""
+        n = len(dev_frames)
+        if len(dev_outputs) != n or (dev_weight_sums is not None and len(dev_weight_sums) != n):
+            raise ValueError("n frames take n output planes")
+        arr = lambda q: None if q is None else (C.c_void_p * max(len(q), 1))(*q)  # noqa: E731
+        rc = host_lib().flow2d_host_denoise_sequence_device(self.handle, arr(dev_frames), n, int(radius), range_sigma,
+                                                            int(bool(masks)), arr(dev_outputs), arr(dev_weight_sums),
+                                                            C.byref(params))
+        if rc:
+            raise Flow2DError(rc, "OpticalFlow2D::DenoiseSequenceDevice")
 
     def level_timings(self):
         """[(width, height, solve_ms, kernel_ms, kernel_launches, algorithmic_bytes_per_launch, algorithm)] per level;

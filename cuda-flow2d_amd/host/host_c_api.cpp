@@ -287,6 +287,68 @@ HOST_API int flow2d_host_track_points_device(flow2d_host_flow* h, void* const* d
                : 2;
 }
 
+// OpticalFlow2D::DenoiseArgsOk: 1 when frame_count, radius and range_sigma are what DenoiseSequence* accept.  Needs no device.
+HOST_API int flow2d_host_denoise_args_ok(size_t frame_count, size_t radius, float range_sigma)
+{
+    return OpticalFlow2D::DenoiseArgsOk(frame_count, radius, range_sigma) ? 1 : 0;
+}
+
+// OpticalFlow2D::DenoiseSequence on tight host images: frames = frame_count * width * height floats (frame k at k * width *
+// height); outputs, and weight_sums when not NULL, get the same layout.  0 on success, 1 for a null or refused argument, 2 when the
+// run delivered no frames.
+HOST_API int flow2d_host_denoise_sequence(flow2d_host_flow* h, const float* frames, size_t frame_count, size_t radius,
+                                          float range_sigma, int use_masks, float* outputs, float* weight_sums,
+                                          const flow2d_host_params* params, float* total_ms)
+{
+    if (!OpticalFlow2D::DenoiseArgsOk(frame_count, radius, range_sigma) || !h || !frames || !outputs || !params) return 1;
+    const size_t n = h->width * h->height;
+    std::vector<Data2D> f, out, sums;
+    for (size_t k = 0; k < frame_count; ++k) {
+        f.emplace_back(h->width, h->height);
+        std::memcpy(f.back().DataPtr(), frames + k * n, n * sizeof(float));
+        out.emplace_back(h->width, h->height);
+        for (size_t i = 0; i < n; ++i) out.back().DataPtr()[i] = -12345.f;  // poisoned, as in flow2d_host_compute_flow
+        if (weight_sums) sums.emplace_back(h->width, h->height);
+    }
+    flow2d_host_params p = *params;
+    OperationParameters bag;
+    FillBag(bag, p);
+    std::vector<Data2D*> fp;
+    for (Data2D& d : f) fp.push_back(&d);
+    h->flow.DenoiseSequence(fp.data(), frame_count, radius, range_sigma, use_masks != 0, out.data(),
+                            weight_sums ? sums.data() : nullptr, bag);
+    for (size_t k = 0; k < frame_count; ++k) {
+        std::memcpy(outputs + k * n, out[k].DataPtr(), n * sizeof(float));
+        if (weight_sums && h->flow.LastRunSucceeded()) std::memcpy(weight_sums + k * n, sums[k].DataPtr(), n * sizeof(float));
+    }
+    if (total_ms) *total_ms = h->flow.LastTotalMs();
+    return h->flow.LastRunSucceeded() ? 0 : 2;
+}
+
+// OpticalFlow2D::DenoiseSequenceDevice: frame_count device frames and output planes, weight-sum planes optional (NULL: none).
+// Queued on the context's stream, no synchronisation.  0 on success, 1 for a null or refused argument.
+HOST_API int flow2d_host_denoise_sequence_device(flow2d_host_flow* h, void* const* dev_frames, size_t frame_count, size_t radius,
+                                                 float range_sigma, int use_masks, void* const* dev_outputs,
+                                                 void* const* dev_weight_sums, const flow2d_host_params* params)
+{
+    if (!OpticalFlow2D::DenoiseArgsOk(frame_count, radius, range_sigma) || !h || !params || !dev_frames || !dev_outputs) return 1;
+    flow2d_host_params p = *params;
+    OperationParameters bag;
+    FillBag(bag, p);
+    h->flow.timing_mode = 0;
+    auto dp = [](void* q) { return static_cast<DevicePtr>(reinterpret_cast<uintptr_t>(q)); };
+    std::vector<DevicePtr> frames(frame_count), outputs(frame_count), sums(dev_weight_sums ? frame_count : 0);
+    for (size_t k = 0; k < frame_count; ++k) {
+        frames[k] = dp(dev_frames[k]);
+        outputs[k] = dp(dev_outputs[k]);
+        if (dev_weight_sums) sums[k] = dp(dev_weight_sums[k]);
+    }
+    return h->flow.DenoiseSequenceDevice(frames.data(), frame_count, radius, range_sigma, use_masks != 0, outputs.data(),
+                                         dev_weight_sums ? sums.data() : nullptr, bag)
+               ? 0
+               : 2;
+}
+
 // OpticalFlow2D::ComputeFlowBidirectionalDevice: frame_count device frames, frame_count - 1 forward and backward flow plane pairs,
 // occlusion planes optional (NULL arrays: no masks).  Queued on the context's stream, no synchronisation.  0 on success.
 HOST_API int flow2d_host_compute_flow_bidirectional_device(flow2d_host_flow* h, void* const* dev_frames, size_t frame_count,

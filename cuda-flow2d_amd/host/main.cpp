@@ -26,6 +26,10 @@
 // (OpticalFlow2D::TrackPoints: flow2d_seed_points_2d with the default texture threshold, flow2d_track_points_2d with the paper's
 // thresholds), writes <prefix>tracks.txt -- one line per track, "x1 y1 x2 y2", nan where the track has no position -- and prints
 // the alive, ended and seeded counts.  The other files do not change.
+// --denoise SIGMA (a finite number >= 0, grey levels; 0 = no photometric weight) also fuses each of the two frames with the other
+// along the flow between them (OpticalFlow2D::DenoiseSequence: radius 1, occlusion masks on, flow2d_denoise_2d) and writes
+// <prefix>denoised-1-W-H.raw and <prefix>denoised-2-W-H.raw in the input's raw type (u8 or F32).  The other files do not change.
+// It is a run of its own after the files above are written: the pair's flows are computed a second time, in both directions.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -64,6 +68,8 @@ int main(int argc, char** argv)
     bool force_u8 = false, verbose = false, backward = false, write_flo = false;
     int interpolate = 0;  // --interpolate N: N - 1 frames between the two (0: off)
     long track_spacing = 0;  // --track S: seed frame 1 at spacing S and track into frame 2 (0: off)
+    bool denoise = false;  // --denoise SIGMA: each frame fused with the other
+    float denoise_sigma = 0.f;
     std::string ground_truth_file;
     int device = 0;
     float sor_omega = 0.f;
@@ -96,6 +102,17 @@ int main(int argc, char** argv)
                 return 5;
             }
             track_spacing = n;
+            ++i;
+        }
+        else if (!std::strcmp(argv[i], "--denoise")) {
+            char* end = nullptr;
+            const float sigma = (i + 1 < argc) ? std::strtof(argv[i + 1], &end) : 0.f;
+            if (i + 1 >= argc || end == argv[i + 1] || *end != '\0' || !std::isfinite(sigma) || sigma < 0.f) {
+                std::printf("--denoise takes a finite SIGMA >= 0 (grey levels; 0: no photometric weight).\n");
+                return 5;
+            }
+            denoise = true;
+            denoise_sigma = sigma;
             ++i;
         }
         else if (!std::strcmp(argv[i], "--device") && i + 1 < argc) device = std::atoi(argv[++i]);
@@ -298,6 +315,26 @@ int main(int argc, char** argv)
             std::fclose(out);
             std::printf("Tracks: %zu alive, %zu ended, %llu seeded in frame 2\n", alive, static_cast<size_t>(counts[0]) - alive,
                         counts[1] - counts[0]);
+        }
+        if (denoise) {
+            Data2D* frames[2] = {&frame_0, &frame_1};
+            std::vector<Data2D> denoised;
+            denoised.emplace_back(width, height);
+            denoised.emplace_back(width, height);
+            optical_flow.DenoiseSequence(frames, 2, 1, denoise_sigma, true, denoised.data(), nullptr, params);
+            if (!optical_flow.LastRunSucceeded()) {
+                std::cout << "Error: denoising failed." << std::endl;
+                optical_flow.Destroy();
+                DestroyDeviceContext();
+                return 4;
+            }
+            for (int k = 0; k < 2; ++k) {
+                const std::string name = output_path + counter + "denoised-" + std::to_string(k + 1) + suffix;
+                if (!(u8 ? denoised[k].WriteRAWToFileU8(name.c_str()) : denoised[k].WriteRAWToFileF32(name.c_str()))) {
+                    std::cerr << "Error: cannot save file " << std::endl;
+                    std::exit(255);
+                }
+            }
         }
         if (!ground_truth_file.empty()) {
             flow2d_flow_error_stats stats;

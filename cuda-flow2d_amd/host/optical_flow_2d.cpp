@@ -174,6 +174,11 @@ void OpticalFlow2D::Destroy()
         if (tracking_scratch_) flow2d_plane_free(context_, AsPlane(tracking_scratch_));
         tracking_scratch_ = 0;
         tracking_scratch_bytes_ = 0;
+        for (std::vector<DevicePtr>* planes : {&denoise_pairs_, &denoise_chains_}) {
+            for (DevicePtr p : *planes)
+                if (p) flow2d_plane_free(context_, AsPlane(p));
+            planes->clear();
+        }
     }
     all_planes_.clear();
     free_planes_.clear();
@@ -706,6 +711,170 @@ void OpticalFlow2D::TrackPoints(Data2D* const* frames, size_t frame_count, size_
     flow2d_event_destroy(context_, ev_stop);
     flow2d_synchronize(context_);
     for (const std::vector<DevicePtr>* planes : {&dev_frames, &dev_xs, &dev_ys})
+        for (DevicePtr p : *planes)
+            if (p) flow2d_plane_free(context_, AsPlane(p));
+    last_run_ok_ = ok;
+}
+
+bool OpticalFlow2D::DenoiseArgsOk(size_t frame_count, size_t radius, float range_sigma)
+{
+    if (frame_count < 2 || radius < 1 || radius > kDenoiseMaxRadius || !std::isfinite(range_sigma) || range_sigma < 0.f) {
+        std::printf("Error: denoising takes at least 2 frames (%zu), a radius of 1 .. %zu (%zu) and a finite range sigma >= 0 (%g).\n",
+                    frame_count, kDenoiseMaxRadius, radius, range_sigma);
+        return false;
+    }
+    return true;
+}
+
+bool OpticalFlow2D::DenoiseSequenceDevice(const DevicePtr* dev_frames, size_t frame_count, size_t radius, float range_sigma,
+                                          bool use_masks, const DevicePtr* dev_outputs, const DevicePtr* dev_weight_sums,
+                                          OperationParameters& params)
+{
+    if (!DenoiseArgsOk(frame_count, radius, range_sigma)) return false;
+    if (!IsInitialized() || !dev_frames || !dev_outputs) return false;
+    if (group_ > 1) {
+        std::printf("Error: '%s': sequences and lock-step groups do not combine.\n", GetName());
+        return false;
+    }
+    // every plane written must be distinct from every other one and from the frames (which are only read)
+    std::vector<DevicePtr> written(dev_outputs, dev_outputs + frame_count);
+    if (dev_weight_sums) written.insert(written.end(), dev_weight_sums, dev_weight_sums + frame_count);
+    for (size_t k = 0; k < frame_count; ++k)
+        if (!dev_frames[k]) return false;
+    for (size_t i = 0; i < written.size(); ++i) {
+        if (!written[i]) return false;
+        for (size_t k = 0; k < frame_count; ++k)
+            if (written[i] == dev_frames[k]) {
+                std::printf("Error: '%s': an output plane is one of the frames.\n", GetName());
+                return false;
+            }
+        for (size_t j = i + 1; j < written.size(); ++j)
+            if (written[i] == written[j]) {
+                std::printf("Error: '%s': the output planes must be distinct.\n", GetName());
+                return false;
+            }
+    }
+    // the ring: pair j lives in slot j % slots as u, v, back u, back v, occlusion forward, occlusion backward
+    const size_t slots = 2 * radius + kDenoiseWindow;
+    const size_t per_slot = use_masks ? 6 : 4;
+    if (denoise_pairs_.size() < 6 * slots) denoise_pairs_.resize(6 * slots, 0);
+    for (size_t s = 0; s < slots; ++s)
+        if (!EnsurePlanes(denoise_pairs_.data() + 6 * s, per_slot)) return false;
+    // the composed flows of one centre: direction (0 backwards, 1 forwards), distance d >= 2: u, v, mask
+    const size_t far = kDenoiseMaxRadius - 1;
+    if (denoise_chains_.size() < 2 * far * 3) denoise_chains_.resize(2 * far * 3, 0);
+    for (size_t dir = 0; dir < 2; ++dir)
+        for (size_t d = 2; d <= radius; ++d)
+            if (!EnsurePlanes(denoise_chains_.data() + (dir * far + d - 2) * 3, use_masks ? 3 : 2)) return false;
+    const size_t W = dev_container_size_.width, H = dev_container_size_.height, pitch = dev_container_size_.pitch;
+    auto pair_plane = [&](size_t j, size_t i) { return denoise_pairs_[6 * (j % slots) + i]; };
+    auto chain_plane = [&](size_t dir, size_t d, size_t i) { return denoise_chains_[(dir * far + d - 2) * 3 + i]; };
+
+    auto fuse = [&](size_t k) {
+        // the flow from frame k to frame k -+ d and its mask: distance 1 from the ring, further ones chained outwards
+        DevicePtr flow[2][kDenoiseMaxRadius][3];
+        size_t reach[2] = {std::min(radius, k), std::min(radius, frame_count - 1 - k)};
+        for (size_t dir = 0; dir < 2; ++dir) {
+            for (size_t d = 1; d <= reach[dir]; ++d) {
+                // the step that ends at distance d: backwards the backward flow of pair k - d, forwards the forward flow of
+                // pair k + d - 1, each with the mask on its own first frame's grid
+                const size_t j = dir ? k + d - 1 : k - d;
+                const DevicePtr step[3] = {pair_plane(j, dir ? 0 : 2), pair_plane(j, dir ? 1 : 3),
+                                           use_masks ? pair_plane(j, dir ? 4 : 5) : 0};
+                if (d == 1) {
+                    for (int i = 0; i < 3; ++i) flow[dir][0][i] = step[i];
+                    continue;
+                }
+                DevicePtr* out = flow[dir][d - 1];
+                for (int i = 0; i < 3; ++i) out[i] = (i < 2 || use_masks) ? chain_plane(dir, d, i) : 0;
+                const DevicePtr* prev = flow[dir][d - 2];
+                if (CheckFlow2DError(flow2d_compose_flow_2d(context_, AsPlane(prev[0]), AsPlane(prev[1]), AsPlane(step[0]),
+                                                            AsPlane(step[1]), use_masks ? AsPlane(prev[2]) : nullptr,
+                                                            use_masks ? AsPlane(step[2]) : nullptr, W, H, pitch, AsPlane(out[0]),
+                                                            AsPlane(out[1]), use_masks ? AsPlane(out[2]) : nullptr),
+                                     "flow2d_compose_flow_2d"))
+                    return false;
+            }
+        }
+        // ascending frame order: k - reach .. k - 1, k + 1 .. k + reach
+        const float *frames[2 * kDenoiseMaxRadius], *us[2 * kDenoiseMaxRadius], *vs[2 * kDenoiseMaxRadius],
+            *occs[2 * kDenoiseMaxRadius];
+        size_t n = 0;
+        auto add = [&](size_t dir, size_t d) {
+            frames[n] = AsPlane(dev_frames[dir ? k + d : k - d]);
+            us[n] = AsPlane(flow[dir][d - 1][0]);
+            vs[n] = AsPlane(flow[dir][d - 1][1]);
+            occs[n] = use_masks ? AsPlane(flow[dir][d - 1][2]) : nullptr;
+            ++n;
+        };
+        for (size_t d = reach[0]; d >= 1; --d) add(0, d);
+        for (size_t d = 1; d <= reach[1]; ++d) add(1, d);
+        return !CheckFlow2DError(flow2d_denoise_2d(context_, AsPlane(dev_frames[k]), n, frames, us, vs, use_masks ? occs : nullptr, W,
+                                                   H, pitch, range_sigma, AsPlane(dev_outputs[k]),
+                                                   dev_weight_sums ? AsPlane(dev_weight_sums[k]) : nullptr),
+                                 "flow2d_denoise_2d");
+    };
+
+    const size_t pairs = frame_count - 1;
+    size_t done = 0, centre = 0;  // pairs in the ring so far; the next frame to fuse
+    bool ok = true;
+    while (ok && centre < frame_count) {
+        if (done < pairs) {
+            const size_t chunk = std::min(kDenoiseWindow, pairs - done);
+            std::vector<DevicePtr> p[6];
+            for (size_t j = done; j < done + chunk; ++j)
+                for (size_t i = 0; i < 6; ++i) p[i].push_back(pair_plane(j, i));
+            ok = ComputeFlowBidirectionalDevice(dev_frames + done, chunk + 1, p[0].data(), p[1].data(), p[2].data(), p[3].data(),
+                                                use_masks ? p[4].data() : nullptr, use_masks ? p[5].data() : nullptr, params);
+            done += chunk;
+        }
+        // every frame whose furthest forward pair is in the ring (a slot is overwritten only 2 * radius + kDenoiseWindow pairs later)
+        while (ok && centre < frame_count && std::min(centre + radius, pairs) <= done) ok = fuse(centre++);
+    }
+    return ok;
+}
+
+void OpticalFlow2D::DenoiseSequence(Data2D* const* frames, size_t frame_count, size_t radius, float range_sigma, bool use_masks,
+                                    Data2D* outputs, Data2D* weight_sums, OperationParameters& params)
+{
+    last_run_ok_ = false;
+    if (!DenoiseArgsOk(frame_count, radius, range_sigma)) return;
+    if (!IsInitialized() || !frames || !outputs) return;
+    if (group_ > 1) {
+        std::printf("Error: '%s': sequences and lock-step groups do not combine.\n", GetName());
+        return;
+    }
+    const size_t W = dev_container_size_.width, H = dev_container_size_.height, pitch = dev_container_size_.pitch;
+    for (size_t k = 0; k < frame_count; ++k)
+        if (!frames[k] || frames[k]->Width() != W || frames[k]->Height() != H || outputs[k].Width() != W || outputs[k].Height() != H ||
+            (weight_sums && (weight_sums[k].Width() != W || weight_sums[k].Height() != H))) {
+            std::printf("Error: '%s': frame / output sizes do not match the initialised size %zu x %zu.\n", GetName(), W, H);
+            return;
+        }
+    // the frames and the outputs of this call (freed at its end)
+    std::vector<DevicePtr> dev_frames(frame_count, 0), dev_outputs(frame_count, 0), dev_sums(weight_sums ? frame_count : 0, 0);
+    bool ok = EnsurePlanes(dev_frames.data(), frame_count) && EnsurePlanes(dev_outputs.data(), frame_count) &&
+              EnsurePlanes(dev_sums.data(), dev_sums.size());
+    std::printf("\nStarting optical flow computation...\n");
+    void *ev_start = nullptr, *ev_stop = nullptr;
+    flow2d_event_create(context_, &ev_start);
+    flow2d_event_create(context_, &ev_stop);
+    flow2d_event_record(context_, ev_start);
+    for (size_t k = 0; ok && k < frame_count; ++k) ok = CopyData2DtoDevice(*frames[k], dev_frames[k], H, pitch);
+    ok = ok && DenoiseSequenceDevice(dev_frames.data(), frame_count, radius, range_sigma, use_masks, dev_outputs.data(),
+                                     weight_sums ? dev_sums.data() : nullptr, params);
+    for (size_t k = 0; ok && k < frame_count; ++k) {
+        ok = CopyData2DFromDevice(dev_outputs[k], outputs[k], H, pitch);
+        if (ok && weight_sums) ok = CopyData2DFromDevice(dev_sums[k], weight_sums[k], H, pitch);
+    }
+    flow2d_event_record(context_, ev_stop);
+    flow2d_event_synchronize(context_, ev_stop);  // the downloads
+    flow2d_event_elapsed_ms(context_, ev_start, ev_stop, &last_total_ms_);
+    std::printf("Total GPU computation time: % 4.4fs\n", last_total_ms_ / 1000.);
+    flow2d_event_destroy(context_, ev_start);
+    flow2d_event_destroy(context_, ev_stop);
+    flow2d_synchronize(context_);
+    for (const std::vector<DevicePtr>* planes : {&dev_frames, &dev_outputs, &dev_sums})
         for (DevicePtr p : *planes)
             if (p) flow2d_plane_free(context_, AsPlane(p));
     last_run_ok_ = ok;

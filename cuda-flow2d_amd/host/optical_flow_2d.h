@@ -142,6 +142,32 @@ public:
                      float beta1, float beta2, float* xs, float* ys, size_t capacity, unsigned long long* counts_out,
                      OperationParameters& params);
 
+    // Motion-compensated temporal denoising of a sequence (no reference counterpart): dev_outputs[k] (k < frame_count) gets frame k
+    // fused by flow2d_denoise_2d with the frames k - radius .. k + radius that exist (fewer at the ends of the sequence), passed
+    // in ascending frame order; dev_weight_sums (optional, frame_count planes) get the sums of weights.  The flows and masks are
+    // those of ComputeFlowBidirectionalDevice on consecutive pairs, bit for bit: frame k's forward flow and occ_fwd[k] serve
+    // neighbour k + 1, the backward flow and occ_bwd[k - 1] of pair k - 1 serve neighbour k - 1; distances of 2 and more are
+    // chained outwards from the centre by flow2d_compose_flow_2d (with the masks when use_masks), a broken chain (NaN) dropping
+    // out.  range_sigma (grey levels, finite, >= 0; 0 = off) is the scale of the photometric weight; use_masks = false fuses
+    // without occlusion masks.  Pairs are computed kDenoiseWindow at a time (pyramids shared inside a window) into a ring of
+    // 2 * radius + kDenoiseWindow pairs' planes allocated once: the device memory beyond the caller's planes depends on radius
+    // and use_masks, not on frame_count.  frame_count >= 2, radius 1 .. kDenoiseMaxRadius.  Frames are only read; outputs must be
+    // distinct from each other and from the frames.  Queued on the context's stream, launched eagerly (no graph).  Not for
+    // lock-step groups.
+    // (Two pairs per window: a window's last frame is the next window's first, and its pyramid -- a blur and the resampled levels,
+    // a few per cent of a pair's flow -- is built again there: one pyramid in three is redundant.  A longer window would share more
+    // and cost six planes of ring per pair; not measured.)
+    static constexpr size_t kDenoiseWindow = 2;
+    static constexpr size_t kDenoiseMaxRadius = 4;
+    // frame_count, radius and range_sigma as above (prints what is wrong); needs no device
+    static bool DenoiseArgsOk(size_t frame_count, size_t radius, float range_sigma);
+    bool DenoiseSequenceDevice(const DevicePtr* dev_frames, size_t frame_count, size_t radius, float range_sigma, bool use_masks,
+                               const DevicePtr* dev_outputs, const DevicePtr* dev_weight_sums, OperationParameters& params);
+    // The host-image form (the CLI's --denoise): upload the frames (frames[k] -> frame k), DenoiseSequenceDevice, download into
+    // outputs[0 .. frame_count - 1] (and weight_sums[...] when not null).  LastRunSucceeded and LastTotalMs as for ComputeFlow.
+    void DenoiseSequence(Data2D* const* frames, size_t frame_count, size_t radius, float range_sigma, bool use_masks,
+                         Data2D* outputs, Data2D* weight_sums, OperationParameters& params);
+
     // When set, ComputeFlowDevice records the whole pyramid of a pair into a HIP graph the first time it
     // sees a (buffers, parameters) combination and replays it afterwards: one host call instead of
     // several hundred launches.  Ignored while timing_mode != 0 (events are not captured).
@@ -246,6 +272,10 @@ private:
     DevicePtr tracking_scratch_ = 0;
     size_t tracking_scratch_bytes_ = 0;
     DevicePtr AllocBytes(size_t bytes);
+    // DenoiseSequenceDevice: the ring of pairs (u, v, back u, back v, occlusion forward, occlusion backward per slot; the masks
+    // allocated on the first call with use_masks) and the composed flows of a centre (u, v, mask per direction and distance >= 2)
+    std::vector<DevicePtr> denoise_pairs_;
+    std::vector<DevicePtr> denoise_chains_;
     flow2d_context* context_ = nullptr;
     // One plane beside the pool: the warped frame of a level, when the levels of both frames are computed up front into plane
     // regions of their own (RunPyramid: "stacked" levels) and therefore cannot be overwritten by the warp

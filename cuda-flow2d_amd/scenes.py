@@ -26,7 +26,9 @@ texture at W^-k(x), W the scene's motion; two_layer: the square has moved by k *
 (frame k+1 -> k) --, frame_at(k, x, y) (the analytic frame k, double), trajectory(x, y, k, start=0) (where the point at (x, y)
 in frame `start` is in frame k, double) and visible(x, y, k, start=0): whether that point is seen in frame k (affine scenes:
 inside the frame; two_layer: a background point is hidden while the square covers it, a square point is lost once it has left
-the frame).
+the frame).  For temporal denoising (flow2d_denoise_2d) the same between any two frames, backwards too:
+trajectory_between(x, y, start, k), visible_between(x, y, start, k) and flow_between(start, k) -> (u, v, visible) on frame
+`start`'s grid.
 Pure numpy: no device, no library.
 """
 import numpy as np
@@ -173,8 +175,10 @@ def make_scene(name, width=256, height=256, seed=0):
 
 
 class Sequence:
-    def __init__(self, name, frame_count, width, height, frame_at, step, back_step, in_square=None):
+    def __init__(self, name, frame_count, width, height, frame_at, step, back_step, in_square=None, back_step_on=None):
         self.name = name
+        # (x, y, k, on) -> position in frame k of the point at (x, y) in frame k + 1 (on: two_layer, the point's layer)
+        self._back_step_on = back_step_on if back_step_on is not None else (lambda x, y, k, on: back_step(x, y, k))
         self.frame_count = frame_count
         self.width, self.height = width, height
         self.frame_at = frame_at
@@ -213,6 +217,39 @@ class Sequence:
         if square is not None:
             seen = seen & (square | ~self._in_square(x, y, k))
         return seen
+
+    def trajectory_between(self, x, y, start, k):
+        """trajectory for any pair of frames: (x, y) in frame k of the point at (x, y) in frame `start`, backwards (k < start)
+        too -- the point keeps its layer on two_layer --, in double."""
+        if k >= start:
+            return self.trajectory(x, y, k, start)
+        x, y = np.asarray(x, np.float64), np.asarray(y, np.float64)
+        on = None if self._in_square is None else self._in_square(x, y, start)
+        for j in range(start - 1, k - 1, -1):
+            x, y = self._back_step_on(x, y, j, on)
+        return x, y
+
+    def visible_between(self, x, y, start, k):
+        """visible for any pair of frames: whether the point at (x, y) in frame `start` is seen in frame k, backwards too."""
+        if k >= start:
+            return self.visible(x, y, k, start)
+        x, y = np.asarray(x, np.float64), np.asarray(y, np.float64)
+        seen = self._inside(x, y)
+        square = None if self._in_square is None else self._in_square(x, y, start)
+        for j in range(start - 1, k - 1, -1):
+            x, y = self._back_step_on(x, y, j, square)
+            seen = seen & self._inside(x, y)
+        if square is not None:
+            seen = seen & (square | ~self._in_square(x, y, k))
+        return seen
+
+    def flow_between(self, start, k):
+        """The true flow of frame `start` to frame k on frame `start`'s grid, (u, v) float32 -- for neighbouring frames the
+        values of gt_u / gt_v and gt_back_u / gt_back_v --, and the true visibility (bool): the pixel's content is seen in
+        frame k."""
+        ys, xs = np.mgrid[0:self.height, 0:self.width].astype(np.float64)
+        px, py = self.trajectory_between(xs, ys, start, k)
+        return (px - xs).astype(np.float32), (py - ys).astype(np.float32), self.visible_between(xs, ys, start, k)
 
 
 def _affine_sequence(name, frame_count, width, height, texture, a, t):
@@ -259,7 +296,11 @@ def _two_layer_sequence(frame_count, width, height, background, square, t):
         on = in_square(x, y, k + 1)
         return np.where(on, x - tx, x), np.where(on, y - ty, y)
 
-    return Sequence("two_layer", frame_count, width, height, frame_at, step, back_step, in_square)
+    def back_step_on(x, y, k, on):  # frame k + 1 -> frame k for a point of a known layer
+        x, y = np.asarray(x, np.float64), np.asarray(y, np.float64)
+        return np.where(on, x - tx, x), np.where(on, y - ty, y)
+
+    return Sequence("two_layer", frame_count, width, height, frame_at, step, back_step, in_square, back_step_on)
 
 
 def make_sequence(name, frame_count=10, width=256, height=256, seed=0):

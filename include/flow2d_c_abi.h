@@ -35,8 +35,9 @@ extern "C" {
 
 /* Additions that leave every existing entry as it was keep the version: flow2d_consistency_2d (forward-backward occlusion
  * masks), flow2d_flow_error_2d / flow2d_flow_error_workspace_bytes (error statistics against ground truth),
- * flow2d_interpolate_2d (occlusion-aware frame interpolation) and flow2d_track_points_2d / flow2d_seed_points_2d /
- * flow2d_seed_points_workspace_bytes (dense point trajectories) were added under 1. */
+ * flow2d_interpolate_2d (occlusion-aware frame interpolation), flow2d_track_points_2d / flow2d_seed_points_2d /
+ * flow2d_seed_points_workspace_bytes (dense point trajectories) and flow2d_denoise_2d / flow2d_compose_flow_2d
+ * (motion-compensated temporal denoising) were added under 1. */
 #define FLOW2D_ABI_VERSION 1
 
 typedef enum flow2d_status {
@@ -326,6 +327,55 @@ FLOW2D_API int flow2d_seed_points_2d(flow2d_context* ctx, const float* frame, si
                                      unsigned long long* count /* device, read and updated */, size_t capacity,
                                      unsigned long long* dropped /* device, may be NULL */, void* workspace,
                                      size_t workspace_bytes);
+
+/* Motion-compensated temporal denoising (no reference counterpart; added to ABI version 1 without changing any existing
+ * entry).  flow2d_denoise_2d fuses `centre` with N = neighbour_count (1 .. FLOW2D_DENOISE_MAX_NEIGHBOURS) neighbour frames in one
+ * launch.  frames, flows_u, flows_v and occlusions are HOST arrays of N device planes: (flows_u[n], flows_v[n]) is the flow from
+ * the centre frame to frames[n] on the centre's grid; occlusions[n] is the occlusion mask of that flow on the centre's grid (1 =
+ * no match in frames[n], as flow2d_consistency_2d writes it) -- the array, or any entry of it, may be NULL (nothing occluded).
+ * For every pixel x = (x, y), with c = centre[x], by exactly these fp32 operations, in this order:
+ *   num = c;  den = 1
+ *   for n = 0 .. N - 1:
+ *     q   = x + (flows_u[n][x], flows_v[n][x])                                  (per component)
+ *     ok  = 0 <= q.x <= width - 1 and 0 <= q.y <= height - 1                    (a NaN or an infinity fails)
+ *     s   = S(frames[n], ok ? q : x)         (S: the bilinear sample of flow2d_consistency_2d, same order; every read stays
+ *                                            inside the plane)
+ *     m   = occlusions[n] ? occlusions[n][x] : 0;  if (!(m <= 1)) m = 1;  if (!(m >= 0)) m = 0    (a NaN counts as occluded)
+ *     d   = s - c
+ *     g   = range_sigma == 0 ? 1 : (range_sigma*range_sigma) / (range_sigma*range_sigma + d*d)    (correctly rounded division)
+ *     wgt = ok ? (1 - m) * g : 0;   t = wgt * s;   if t is not finite: wgt = 0, t = 0   (a NaN or infinite sample, a NaN weight)
+ *     num = num + t;  den = den + wgt                                            (separate multiply and add)
+ *   output[x] = num / den   (correctly rounded division);   weight_sum[x] = den   (when weight_sum is not NULL)
+ * range_sigma is in grey levels; 0 switches the photometric weight g off.  den is at least 1 and at most N + 1; where every
+ * neighbour is occluded, has a NaN flow or points out of the frame, output is the centre bit for bit (frames without negative
+ * zeros).  A NaN flow is what flow2d_compose_flow_2d writes for a broken chain: such a neighbour contributes nothing.
+ * FLOW2D_ERR_INVALID_ARGUMENT for neighbour_count outside 1 .. 8, a null array or required plane, a zero size, a bad pitch (the
+ * rule of flow2d_consistency_2d), a negative or non-finite range_sigma, or an `output` / `weight_sum` whose bytes [p, p + height *
+ * pitch_bytes) -- over every instance of a batch -- overlap those of any input plane or of each other.  Honours
+ * flow2d_context_set_batch (the pointers are those of instance 0).  One launch, no allocation, no synchronisation
+ * (graph-capturable). */
+#define FLOW2D_DENOISE_MAX_NEIGHBOURS 8
+FLOW2D_API int flow2d_denoise_2d(flow2d_context* ctx, const float* centre, size_t neighbour_count, const float* const* frames,
+                                 const float* const* flows_u, const float* const* flows_v,
+                                 const float* const* occlusions /* may be NULL, and so may its entries */, size_t width,
+                                 size_t height, size_t pitch_bytes, float range_sigma, float* output,
+                                 float* weight_sum /* may be NULL */);
+
+/* Flow concatenation: (ab_u, ab_v), the flow of frame a to frame b on a's grid, followed by (bc_u, bc_v), the flow of frame b to
+ * frame c on b's grid, gives the flow of a to c on a's grid -- how flow2d_denoise_2d reaches neighbours further than one frame
+ * away, and the accumulated displacement against a reference frame.  For every pixel x, in fp32:
+ *   q = x + (ab_u[x], ab_v[x]);  ok = 0 <= q.x <= width - 1 and 0 <= q.y <= height - 1     (a NaN or an infinity fails)
+ *   out_u[x] = ok ? ab_u[x] + S(bc_u, q) : NaN,  out_v likewise   (S as above; every NaN written is the quiet NaN 0x7fc00000)
+ *   out_mask[x] = (!ok || !(mask_ab[x] == 0) || !(S(mask_bc, q) <= 0)) ? 1 : 0
+ * mask_ab (a's grid, the mask of a -> b), mask_bc (b's grid, the mask of b -> c) and out_mask are optional: a NULL input mask
+ * counts as 0 everywhere, and without out_mask no mask is read.  FLOW2D_ERR_INVALID_ARGUMENT for a null required plane, a zero
+ * size, a bad pitch (the rule of flow2d_consistency_2d), or a written plane whose bytes -- over every instance of a batch --
+ * overlap those of any input plane or of another written one.  Honours flow2d_context_set_batch.  One launch, no allocation, no
+ * synchronisation (graph-capturable). */
+FLOW2D_API int flow2d_compose_flow_2d(flow2d_context* ctx, const float* ab_u, const float* ab_v, const float* bc_u,
+                                      const float* bc_v, const float* mask_ab /* may be NULL */,
+                                      const float* mask_bc /* may be NULL */, size_t width, size_t height, size_t pitch_bytes,
+                                      float* out_u, float* out_v, float* out_mask /* may be NULL */);
 
 /* Error of a flow estimate against ground truth (Barron et al. 1994, Baker et al. 2011 -- Middlebury --, Menze & Geiger 2015 --
  * KITTI --; no reference counterpart; added to ABI version 1 without changing any existing entry).
