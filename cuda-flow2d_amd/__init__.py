@@ -28,6 +28,9 @@ SOLVER_AUTO, SOLVER_PER_SWEEP, SOLVER_FUSED, SOLVER_SINGLE_WORKGROUP, SOLVER_TIL
 # flow2d_track_reason; DEFAULT_MIN_EIGENVALUE: the seeding threshold of OpticalFlow.track_points and the CLI's --track
 TRACK_ALIVE, TRACK_INACTIVE, TRACK_MOTION_BOUNDARY, TRACK_LEFT_FRAME, TRACK_OCCLUDED = 0, 1, 2, 3, 4
 DEFAULT_MIN_EIGENVALUE = 1.0
+# flow2d_motion_model; MOTION_MODELS: the names the CLI's --global-motion takes
+MOTION_TRANSLATION, MOTION_SIMILARITY, MOTION_AFFINE = 0, 1, 2
+MOTION_MODELS = {"translation": MOTION_TRANSLATION, "similarity": MOTION_SIMILARITY, "affine": MOTION_AFFINE}
 
 STATUS = {0: "ok", 1: "invalid argument", 2: "no usable HIP device", 3: "HIP runtime error",
           4: "out of device memory", 5: "unsupported parameter"}
@@ -120,6 +123,27 @@ def flow_error_metrics(record):
     out["nonfinite_estimate"] = record["nonfinite_estimate"]
     return out
 
+
+class GlobalMotion(C.Structure):
+    """flow2d_global_motion of include/flow2d_c_abi.h: the record flow2d_global_motion_2d writes per instance.  In centred
+    coordinates xc = x - (width - 1) / 2, yc = y - (height - 1) / 2:  u = (p0 + p1*xc) + p2*yc,  v = (p3 + p4*xc) + p5*yc."""
+    _fields_ = [
+        ("p", C.c_double * 6), ("weight_sum", C.c_double), ("support", C.c_ulonglong), ("model_used", C.c_int),
+        ("reserved", C.c_int * 3),
+    ]
+
+    @classmethod
+    def from_parameters(cls, p, model_used=MOTION_AFFINE):
+        """A record holding the six parameters `p` (to upload: Context.upload_motion)."""
+        return cls((C.c_double * 6)(*[float(q) for q in p]), 0.0, 0, int(model_used))
+
+    @property
+    def parameters(self):
+        return np.array(self.p[:], np.float64)
+
+
+GLOBAL_MOTION_BYTES = 80  # FLOW2D_GLOBAL_MOTION_BYTES, checked by a static_assert in the header
+assert C.sizeof(GlobalMotion) == GLOBAL_MOTION_BYTES
 
 _hip = None
 
@@ -217,6 +241,13 @@ def hip_lib():
             L.flow2d_denoise_2d.argtypes = [vp, vp, sz, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), sz, sz, sz, f,
                                             vp, vp]
             L.flow2d_compose_flow_2d.argtypes = [vp] * 7 + [sz, sz, sz, vp, vp, vp]
+        if hasattr(L, "flow2d_global_motion_2d"):  # (absent from libraries of earlier rounds loaded for an A/B)
+            d = C.c_double
+            L.flow2d_global_motion_workspace_bytes.restype = sz
+            L.flow2d_global_motion_workspace_bytes.argtypes = [sz, sz, sz]
+            L.flow2d_global_motion_2d.argtypes = [vp, vp, vp, vp, sz, sz, sz, i, d, i, vp, vp, sz]
+            L.flow2d_global_flow_2d.argtypes = [vp, vp, vp, vp, vp, sz, sz, sz, d, vp, vp, vp, vp, vp]
+            L.flow2d_warp_global_2d.argtypes = [vp, vp, vp, sz, sz, sz, f, vp, vp]
         if hasattr(L, "flow2d_flow_error_2d"):  # (absent from libraries of earlier rounds loaded for an A/B)
             L.flow2d_flow_error_workspace_bytes.restype = sz
             L.flow2d_flow_error_workspace_bytes.argtypes = [sz, sz, sz]
@@ -543,6 +574,61 @@ class Context:
         recs = (FlowErrorStats * instances).from_buffer_copy(raw.tobytes())
         return [_stats_dict(r) for r in recs]
 
+    def motion_records(self, instances=1):
+        """A Plane for `instances` flow2d_global_motion records (device memory; read_motion / upload_motion move them)."""
+        return self.plane(instances * GLOBAL_MOTION_BYTES // 4, 1)
+
+    def read_motion(self, motion, instances=1):
+        """The records of a motion_records Plane as GlobalMotion structures (synchronises)."""
+        raw = motion.download(instances * GLOBAL_MOTION_BYTES // 4, 1)
+        return list((GlobalMotion * instances).from_buffer_copy(raw.tobytes()))
+
+    def upload_motion(self, records, motion=None):
+        """GlobalMotion structures into a motion_records Plane (a new one unless given), byte for byte."""
+        records = list(records)
+        motion = motion or self.motion_records(len(records))
+        raw = b"".join(bytes(r) for r in records)
+        return motion.upload(np.frombuffer(raw, np.float32).reshape(1, -1))
+
+    def global_motion(self, u, v, w, h, model=MOTION_AFFINE, sigma=0.0, iterations=0, mask=None, instances=1, motion=None):
+        """The global motion of the flow (u, v) (flow2d_global_motion_2d): `model` fitted by least squares and, with sigma > 0
+        (pixels), `iterations` reweighted passes; `mask` (1 = leave out) optional; `instances` = the count of
+        flow2d_context_set_batch.  With `motion` (a motion_records Plane) the records stay on the device and nothing is
+        returned or synchronised; without, the context's own records are downloaded and returned as GlobalMotion structures.
+        The workspace is the context's own (kept between calls)."""
+        L = hip_lib()
+        need = L.flow2d_global_motion_workspace_bytes(w, h, instances)
+        cached = getattr(self, "_global_motion_buffers", None)
+        if cached is None or cached[0] < need or cached[1] < instances:
+            if cached is not None:
+                for q in cached[2:]:
+                    q.free()
+                    self._planes.remove(q)
+            self._global_motion_buffers = cached = (need, instances, self.plane(max(need // 4, 4), 1),
+                                                    self.motion_records(instances))
+        records = motion or cached[3]
+        _check(L.flow2d_global_motion_2d(self.handle, u.ptr, v.ptr, mask.ptr if mask else None, w, h, u.pitch, int(model),
+                                         float(sigma), int(iterations), records.ptr, cached[2].ptr, cached[0]),
+               "flow2d_global_motion_2d")
+        return None if motion else self.read_motion(records, instances)
+
+    def global_flow(self, motion, w, h, u=None, v=None, mask=None, sigma=0.0, model_u=None, model_v=None, residual_u=None,
+                    residual_v=None, weight=None):
+        """The model of the records `motion` (a motion_records Plane) as planes (model_u, model_v), the flow (u, v) without it
+        (residual_u, residual_v; NaN where the flow is not valid) and the inlier map of a reweighted pass with `sigma` and
+        `mask` (weight): every output optional, one at least (flow2d_global_flow_2d)."""
+        ptr = lambda q: q.ptr if q else None  # noqa: E731
+        pitch = next(q.pitch for q in (u, model_u, residual_u, weight) if q)
+        _check(hip_lib().flow2d_global_flow_2d(self.handle, motion.ptr, ptr(u), ptr(v), ptr(mask), w, h, pitch, float(sigma),
+                                               ptr(model_u), ptr(model_v), ptr(residual_u), ptr(residual_v), ptr(weight)),
+               "flow2d_global_flow_2d")
+
+    def warp_global(self, motion, frame, w, h, out, valid=None, fill=0.0):
+        """`frame` resampled along the global motion of the records `motion` into `out`: out(x) = frame(x + model(x)), `fill`
+        where that leaves the frame; `valid` (optional) gets 1 / 0 (flow2d_warp_global_2d)."""
+        _check(hip_lib().flow2d_warp_global_2d(self.handle, motion.ptr, frame.ptr, w, h, frame.pitch, fill, out.ptr,
+                                               valid.ptr if valid else None), "flow2d_warp_global_2d")
+
     def resample_x(self, src, dst, out_w, out_h, in_w):
         _check(hip_lib().flow2d_resample_x(self.handle, src.ptr, dst.ptr, out_w, out_h, in_w, src.pitch),
                "flow2d_resample_x")
@@ -708,6 +794,16 @@ def host_lib():
             L.flow2d_host_denoise_sequence.argtypes = [vp, fp, sz, sz, f, i, fp, fp, C.POINTER(HostParams), fp]
             L.flow2d_host_denoise_sequence_device.argtypes = [vp, C.POINTER(vp), sz, sz, f, i, C.POINTER(vp), C.POINTER(vp),
                                                               C.POINTER(HostParams)]
+        if hasattr(L, "flow2d_host_stabilise_sequence"):
+            d, gm = C.c_double, C.POINTER(GlobalMotion)
+            L.flow2d_host_global_motion_args_ok.argtypes = [i, d, i]
+            L.flow2d_host_compose_global_motion.argtypes = [gm, gm, gm]
+            L.flow2d_host_estimate_global_motion.argtypes = [vp, fp, fp, i, d, i, i, gm, C.POINTER(HostParams), fp, fp, fp, fp, fp]
+            L.flow2d_host_estimate_global_motion_device.argtypes = [vp, vp, vp, i, d, i, i, gm, C.POINTER(HostParams), vp, vp, vp,
+                                                                    vp]
+            L.flow2d_host_stabilise_sequence.argtypes = [vp, fp, sz, sz, i, d, i, i, f, fp, gm, C.POINTER(HostParams), fp]
+            L.flow2d_host_stabilise_sequence_device.argtypes = [vp, C.POINTER(vp), sz, sz, i, d, i, i, f, C.POINTER(vp), gm,
+                                                                C.POINTER(HostParams)]
         L.flow2d_host_read_flo.argtypes = [C.c_char_p, C.POINTER(sz), C.POINTER(sz), fp, fp, sz]
         L.flow2d_host_write_flo.argtypes = [fp, fp, sz, sz, C.c_char_p]
         L.flow2d_host_flow_error.argtypes = [fp] * 5 + [sz, sz, fp, fp, C.POINTER(FlowErrorStats)]
@@ -964,6 +1060,74 @@ class OpticalFlow:
         if rc:
             raise Flow2DError(rc, "OpticalFlow2D::DenoiseSequenceDevice")
 
+    def estimate_global_motion(self, frame_0, frame_1, params, model=MOTION_AFFINE, sigma=0.5, iterations=5, masks=False,
+                               flow=False, residual=False):
+        """OpticalFlow2D::EstimateGlobalMotion: the global motion of the host pair -- the flow frame_0 -> frame_1 (with masks:
+        through the bidirectional flow, the forward occlusion mask leaving its vectors out), `model` fitted by
+        flow2d_global_motion_2d.  Returns the GlobalMotion record; with flow / residual, (record, (u, v) and / or (ru, rv))."""
+        f0, f1 = (np.ascontiguousarray(a, np.float32) for a in (frame_0, frame_1))
+        if f0.shape != (self.height, self.width) or f1.shape != f0.shape:
+            raise ValueError("frames: [%d, %d]" % (self.height, self.width))
+        rec, ms = GlobalMotion(), C.c_float()
+        fl = [np.empty_like(f0) for _ in range(2)] if flow else [None, None]
+        rs = [np.empty_like(f0) for _ in range(2)] if residual else [None, None]
+        opt = lambda a: None if a is None else _fptr(a)  # noqa: E731
+        rc = host_lib().flow2d_host_estimate_global_motion(self.handle, _fptr(f0), _fptr(f1), int(model), float(sigma),
+                                                           int(iterations), int(bool(masks)), C.byref(rec), C.byref(params),
+                                                           opt(fl[0]), opt(fl[1]), opt(rs[0]), opt(rs[1]), C.byref(ms))
+        if rc:
+            raise Flow2DError(rc, "OpticalFlow2D::EstimateGlobalMotion")
+        extra = ([tuple(fl)] if flow else []) + ([tuple(rs)] if residual else [])
+        return (rec, *extra) if extra else rec
+
+    def estimate_global_motion_device(self, dev_frame_0, dev_frame_1, params, model=MOTION_AFFINE, sigma=0.5, iterations=5,
+                                      masks=False, dev_flow=None, dev_residual=None):
+        """OpticalFlow2D::EstimateGlobalMotionDevice: two device frames in, the GlobalMotion record out (synchronises);
+        dev_flow / dev_residual: optional (u, v) pairs of device planes for the flow and the residual flow."""
+        rec = GlobalMotion()
+        fl, rs = dev_flow or (None, None), dev_residual or (None, None)
+        rc = host_lib().flow2d_host_estimate_global_motion_device(self.handle, dev_frame_0, dev_frame_1, int(model), float(sigma),
+                                                                  int(iterations), int(bool(masks)), C.byref(rec),
+                                                                  C.byref(params), fl[0], fl[1], rs[0], rs[1])
+        if rc:
+            raise Flow2DError(rc, "OpticalFlow2D::EstimateGlobalMotionDevice")
+        return rec
+
+    def stabilise_sequence(self, frames, params, reference_index=0, model=MOTION_AFFINE, sigma=0.5, iterations=5, masks=False,
+                           fill=0.0):
+        """OpticalFlow2D::StabiliseSequence: every host frame of `frames` ([frame_count, h, w]) brought onto the grid of
+        frames[reference_index] along the composed global motions of consecutive pairs (flow2d_global_motion_2d,
+        flow2d_warp_global_2d); `fill` where a frame has nothing to show.  Returns (frames [frame_count, h, w], the GlobalMotion
+        records M(reference -> k))."""
+        fr = np.ascontiguousarray(frames, np.float32)
+        if fr.ndim != 3 or fr.shape[1:] != (self.height, self.width):
+            raise ValueError("frames: [frame_count, %d, %d]" % (self.height, self.width))
+        out = np.empty_like(fr)
+        motions = (GlobalMotion * max(fr.shape[0], 1))()
+        ms = C.c_float()
+        rc = host_lib().flow2d_host_stabilise_sequence(self.handle, _fptr(fr), fr.shape[0], int(reference_index), int(model),
+                                                       float(sigma), int(iterations), int(bool(masks)), fill, _fptr(out), motions,
+                                                       C.byref(params), C.byref(ms))
+        if rc:
+            raise Flow2DError(rc, "OpticalFlow2D::StabiliseSequence")
+        return out, list(motions)[:fr.shape[0]]
+
+    def stabilise_sequence_device(self, dev_frames, dev_outputs, params, reference_index=0, model=MOTION_AFFINE, sigma=0.5,
+                                  iterations=5, masks=False, fill=0.0):
+        """OpticalFlow2D::StabiliseSequenceDevice: device frames in, frame k on the reference's grid into dev_outputs[k].
+        Returns the GlobalMotion records M(reference -> k) (synchronises)."""
+        n = len(dev_frames)
+        if len(dev_outputs) != n:
+            raise ValueError("n frames take n output planes")
+        arr = lambda q: (C.c_void_p * max(len(q), 1))(*q)  # noqa: E731
+        motions = (GlobalMotion * max(n, 1))()
+        rc = host_lib().flow2d_host_stabilise_sequence_device(self.handle, arr(dev_frames), n, int(reference_index), int(model),
+                                                              float(sigma), int(iterations), int(bool(masks)), fill,
+                                                              arr(dev_outputs), motions, C.byref(params))
+        if rc:
+            raise Flow2DError(rc, "OpticalFlow2D::StabiliseSequenceDevice")
+        return list(motions)[:n]
+
     def level_timings(self):
         """[(width, height, solve_ms, kernel_ms, kernel_launches, algorithmic_bytes_per_launch, algorithm)] per level;
         algorithm = the flow2d_solver_algorithm the level actually ran (never AUTO)."""
@@ -1131,6 +1295,15 @@ def evaluate_flow(u, v, gt_u, gt_v, occlusion=None, planes=False, device=0):
     if rc:
         raise Flow2DError(1 if rc == 1 else 3, "EvaluateFlow")
     return (_stats_dict(rec), epe, ae) if planes else _stats_dict(rec)
+
+
+def compose_global_motion(first, second):
+    """OpticalFlow2D::ComposeGlobalMotion: the GlobalMotion record of `second` after `first` (centred coordinates, double)."""
+    out = GlobalMotion()
+    rc = host_lib().flow2d_host_compose_global_motion(C.byref(first), C.byref(second), C.byref(out))
+    if rc:
+        raise Flow2DError(rc, "OpticalFlow2D::ComposeGlobalMotion")
+    return out
 
 
 def max_warp_level(width, height, scale):

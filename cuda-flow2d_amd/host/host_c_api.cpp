@@ -349,6 +349,127 @@ HOST_API int flow2d_host_denoise_sequence_device(flow2d_host_flow* h, void* cons
                : 2;
 }
 
+// OpticalFlow2D::GlobalMotionArgsOk: 1 when model, sigma and iterations are what the global-motion entries accept.  Needs no device.
+HOST_API int flow2d_host_global_motion_args_ok(int model, double sigma, int iterations)
+{
+    return OpticalFlow2D::GlobalMotionArgsOk(model, sigma, iterations) ? 1 : 0;
+}
+
+// OpticalFlow2D::ComposeGlobalMotion: `second` after `first` into `out`.  Needs no device.  0 on success, 1 for a null argument.
+HOST_API int flow2d_host_compose_global_motion(const flow2d_global_motion* first, const flow2d_global_motion* second,
+                                               flow2d_global_motion* out)
+{
+    if (!first || !second || !out) return 1;
+    *out = OpticalFlow2D::ComposeGlobalMotion(*first, *second);
+    return 0;
+}
+
+// OpticalFlow2D::EstimateGlobalMotion on tight host images (width*height floats each): the record of the pair into `motion`;
+// flow_u / flow_v and residual_u / residual_v (each pair optional) get the flow and the residual flow.  0 on success, 1 for a
+// null or refused argument, 2 when the run delivered nothing.
+HOST_API int flow2d_host_estimate_global_motion(flow2d_host_flow* h, const float* frame_0, const float* frame_1, int model,
+                                                double sigma, int iterations, int use_masks, flow2d_global_motion* motion,
+                                                const flow2d_host_params* params, float* flow_u, float* flow_v,
+                                                float* residual_u, float* residual_v, float* total_ms)
+{
+    if (!OpticalFlow2D::GlobalMotionArgsOk(model, sigma, iterations) || !h || !frame_0 || !frame_1 || !motion || !params ||
+        (flow_u == nullptr) != (flow_v == nullptr) || (residual_u == nullptr) != (residual_v == nullptr))
+        return 1;
+    const size_t n = h->width * h->height;
+    Data2D f0(h->width, h->height), f1(h->width, h->height);
+    std::memcpy(f0.DataPtr(), frame_0, n * sizeof(float));
+    std::memcpy(f1.DataPtr(), frame_1, n * sizeof(float));
+    Data2D out[4] = {Data2D(h->width, h->height), Data2D(h->width, h->height), Data2D(h->width, h->height),
+                     Data2D(h->width, h->height)};
+    float* dst[4] = {flow_u, flow_v, residual_u, residual_v};
+    flow2d_host_params p = *params;
+    OperationParameters bag;
+    FillBag(bag, p);
+    h->flow.EstimateGlobalMotion(f0, f1, model, sigma, iterations, use_masks != 0, motion, bag, flow_u ? &out[0] : nullptr,
+                                 flow_u ? &out[1] : nullptr, residual_u ? &out[2] : nullptr, residual_u ? &out[3] : nullptr);
+    if (h->flow.LastRunSucceeded())
+        for (int i = 0; i < 4; ++i)
+            if (dst[i]) std::memcpy(dst[i], out[i].DataPtr(), n * sizeof(float));
+    if (total_ms) *total_ms = h->flow.LastTotalMs();
+    return h->flow.LastRunSucceeded() ? 0 : 2;
+}
+
+// OpticalFlow2D::EstimateGlobalMotionDevice: two device frames, the record into `motion` (host); the optional device planes
+// get the flow and the residual flow.  Synchronises.  0 on success, 1 for a null or refused argument.
+HOST_API int flow2d_host_estimate_global_motion_device(flow2d_host_flow* h, void* dev_frame_0, void* dev_frame_1, int model,
+                                                       double sigma, int iterations, int use_masks, flow2d_global_motion* motion,
+                                                       const flow2d_host_params* params, void* dev_flow_u, void* dev_flow_v,
+                                                       void* dev_residual_u, void* dev_residual_v)
+{
+    if (!OpticalFlow2D::GlobalMotionArgsOk(model, sigma, iterations) || !h || !dev_frame_0 || !dev_frame_1 || !motion || !params)
+        return 1;
+    flow2d_host_params p = *params;
+    OperationParameters bag;
+    FillBag(bag, p);
+    h->flow.timing_mode = 0;
+    auto dp = [](void* q) { return static_cast<DevicePtr>(reinterpret_cast<uintptr_t>(q)); };
+    return h->flow.EstimateGlobalMotionDevice(dp(dev_frame_0), dp(dev_frame_1), model, sigma, iterations, use_masks != 0, motion, bag,
+                                              dp(dev_flow_u), dp(dev_flow_v), dp(dev_residual_u), dp(dev_residual_v))
+               ? 0
+               : 2;
+}
+
+// OpticalFlow2D::StabiliseSequence on tight host images: frames = frame_count * width * height floats (frame k at k * width *
+// height); outputs get the same layout, motions (optional) frame_count records.  0 on success, 1 for a null or refused argument,
+// 2 when the run delivered no frames.
+HOST_API int flow2d_host_stabilise_sequence(flow2d_host_flow* h, const float* frames, size_t frame_count, size_t reference_index,
+                                            int model, double sigma, int iterations, int use_masks, float fill, float* outputs,
+                                            flow2d_global_motion* motions, const flow2d_host_params* params, float* total_ms)
+{
+    if (!OpticalFlow2D::GlobalMotionArgsOk(model, sigma, iterations) || !h || !frames || !outputs || !params || frame_count < 2 ||
+        reference_index >= frame_count)
+        return 1;
+    const size_t n = h->width * h->height;
+    std::vector<Data2D> f, out;
+    for (size_t k = 0; k < frame_count; ++k) {
+        f.emplace_back(h->width, h->height);
+        std::memcpy(f.back().DataPtr(), frames + k * n, n * sizeof(float));
+        out.emplace_back(h->width, h->height);
+        for (size_t i = 0; i < n; ++i) out.back().DataPtr()[i] = -12345.f;  // poisoned, as in flow2d_host_compute_flow
+    }
+    flow2d_host_params p = *params;
+    OperationParameters bag;
+    FillBag(bag, p);
+    std::vector<Data2D*> fp;
+    for (Data2D& d : f) fp.push_back(&d);
+    h->flow.StabiliseSequence(fp.data(), frame_count, reference_index, model, sigma, iterations, use_masks != 0, fill, out.data(),
+                              motions, bag);
+    for (size_t k = 0; k < frame_count; ++k) std::memcpy(outputs + k * n, out[k].DataPtr(), n * sizeof(float));
+    if (total_ms) *total_ms = h->flow.LastTotalMs();
+    return h->flow.LastRunSucceeded() ? 0 : 2;
+}
+
+// OpticalFlow2D::StabiliseSequenceDevice: frame_count device frames and output planes, motions (host, optional) frame_count
+// records.  Synchronises.  0 on success, 1 for a null or refused argument.
+HOST_API int flow2d_host_stabilise_sequence_device(flow2d_host_flow* h, void* const* dev_frames, size_t frame_count,
+                                                   size_t reference_index, int model, double sigma, int iterations, int use_masks,
+                                                   float fill, void* const* dev_outputs, flow2d_global_motion* motions,
+                                                   const flow2d_host_params* params)
+{
+    if (!OpticalFlow2D::GlobalMotionArgsOk(model, sigma, iterations) || !h || !params || !dev_frames || !dev_outputs ||
+        frame_count < 2 || reference_index >= frame_count)
+        return 1;
+    flow2d_host_params p = *params;
+    OperationParameters bag;
+    FillBag(bag, p);
+    h->flow.timing_mode = 0;
+    auto dp = [](void* q) { return static_cast<DevicePtr>(reinterpret_cast<uintptr_t>(q)); };
+    std::vector<DevicePtr> frames(frame_count), outputs(frame_count);
+    for (size_t k = 0; k < frame_count; ++k) {
+        frames[k] = dp(dev_frames[k]);
+        outputs[k] = dp(dev_outputs[k]);
+    }
+    return h->flow.StabiliseSequenceDevice(frames.data(), frame_count, reference_index, model, sigma, iterations, use_masks != 0, fill,
+                                           outputs.data(), motions, bag)
+               ? 0
+               : 2;
+}
+
 // OpticalFlow2D::ComputeFlowBidirectionalDevice: frame_count device frames, frame_count - 1 forward and backward flow plane pairs,
 // occlusion planes optional (NULL arrays: no masks).  Queued on the context's stream, no synchronisation.  0 on success.
 HOST_API int flow2d_host_compute_flow_bidirectional_device(flow2d_host_flow* h, void* const* dev_frames, size_t frame_count,

@@ -30,6 +30,13 @@
 // along the flow between them (OpticalFlow2D::DenoiseSequence: radius 1, occlusion masks on, flow2d_denoise_2d) and writes
 // <prefix>denoised-1-W-H.raw and <prefix>denoised-2-W-H.raw in the input's raw type (u8 or F32).  The other files do not change.
 // It is a run of its own after the files above are written: the pair's flows are computed a second time, in both directions.
+// --global-motion MODEL (translation, similarity or affine) [--global-sigma S, a finite number >= 0 in pixels, default 0.5; 0:
+// plain least squares] [--global-iterations K, 0 .. 16, default 5] also fits the global motion of the pair
+// (OpticalFlow2D::EstimateGlobalMotion: flow2d_global_motion_2d on the forward flow; with --backward the forward occlusion
+// mask leaves its vectors out) and prints one line "Global motion: {json}" -- "model", "model_used", the six parameters "p" of
+// u = (p0 + p1*xc) + p2*yc, v = (p3 + p4*xc) + p5*yc in centred coordinates with 17 significant digits, "weight_sum" and
+// "support" --, writes the flow without the global motion as <prefix>residual-u-W-H.raw and <prefix>residual-v-W-H.raw (F32, NaN
+// where the flow is not finite) and, with --flo, <prefix>residual.flo.  The other files do not change; a run of its own, too.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -70,6 +77,9 @@ int main(int argc, char** argv)
     long track_spacing = 0;  // --track S: seed frame 1 at spacing S and track into frame 2 (0: off)
     bool denoise = false;  // --denoise SIGMA: each frame fused with the other
     float denoise_sigma = 0.f;
+    int global_model = -1;  // --global-motion MODEL (-1: off)
+    double global_sigma = 0.5;
+    int global_iterations = 5;
     std::string ground_truth_file;
     int device = 0;
     float sor_omega = 0.f;
@@ -113,6 +123,36 @@ int main(int argc, char** argv)
             }
             denoise = true;
             denoise_sigma = sigma;
+            ++i;
+        }
+        else if (!std::strcmp(argv[i], "--global-motion")) {
+            static const char* const names[3] = {"translation", "similarity", "affine"};
+            for (int m = 0; m < 3 && i + 1 < argc; ++m)
+                if (!std::strcmp(argv[i + 1], names[m])) global_model = m;
+            if (global_model < 0) {
+                std::printf("--global-motion takes a MODEL: translation, similarity or affine.\n");
+                return 5;
+            }
+            ++i;
+        }
+        else if (!std::strcmp(argv[i], "--global-sigma")) {
+            char* end = nullptr;
+            const double sigma = (i + 1 < argc) ? std::strtod(argv[i + 1], &end) : 0.0;
+            if (i + 1 >= argc || end == argv[i + 1] || *end != '\0' || !std::isfinite(sigma) || sigma < 0.0) {
+                std::printf("--global-sigma takes a finite S >= 0 (pixels; 0: plain least squares).\n");
+                return 5;
+            }
+            global_sigma = sigma;
+            ++i;
+        }
+        else if (!std::strcmp(argv[i], "--global-iterations")) {
+            char* end = nullptr;
+            const long n = (i + 1 < argc) ? std::strtol(argv[i + 1], &end, 10) : 0;
+            if (i + 1 >= argc || end == argv[i + 1] || *end != '\0' || n < 0 || n > FLOW2D_GLOBAL_MOTION_MAX_ITERATIONS) {
+                std::printf("--global-iterations takes an integer K, 0 .. %d (reweighted passes).\n", FLOW2D_GLOBAL_MOTION_MAX_ITERATIONS);
+                return 5;
+            }
+            global_iterations = static_cast<int>(n);
             ++i;
         }
         else if (!std::strcmp(argv[i], "--device") && i + 1 < argc) device = std::atoi(argv[++i]);
@@ -334,6 +374,29 @@ int main(int argc, char** argv)
                     std::cerr << "Error: cannot save file " << std::endl;
                     std::exit(255);
                 }
+            }
+        }
+        if (global_model >= 0) {
+            flow2d_global_motion motion;
+            Data2D residual_u(width, height), residual_v(width, height);
+            optical_flow.EstimateGlobalMotion(frame_0, frame_1, global_model, global_sigma, global_iterations, backward, &motion, params,
+                                              nullptr, nullptr, &residual_u, &residual_v);
+            if (!optical_flow.LastRunSucceeded()) {
+                std::cout << "Error: the global motion estimation failed." << std::endl;
+                optical_flow.Destroy();
+                DestroyDeviceContext();
+                return 4;
+            }
+            std::printf("Global motion: {\"model\": %d, \"model_used\": %d, \"p\": [%.17g, %.17g, %.17g, %.17g, %.17g, %.17g], "
+                        "\"weight_sum\": %.17g, \"support\": %llu}\n",
+                        global_model, motion.model_used, motion.p[0], motion.p[1], motion.p[2], motion.p[3], motion.p[4], motion.p[5],
+                        motion.weight_sum, motion.support);
+            bool ok = residual_u.WriteRAWToFileF32((output_path + counter + "residual-u" + suffix).c_str()) &&
+                      residual_v.WriteRAWToFileF32((output_path + counter + "residual-v" + suffix).c_str());
+            if (write_flo) ok = ok && IOUtils::WriteFlowFLO(residual_u, residual_v, output_path + counter + "residual.flo");
+            if (!ok) {
+                std::cerr << "Error: cannot save file " << std::endl;
+                std::exit(255);
             }
         }
         if (!ground_truth_file.empty()) {

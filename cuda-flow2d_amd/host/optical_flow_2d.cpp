@@ -174,7 +174,9 @@ void OpticalFlow2D::Destroy()
         if (tracking_scratch_) flow2d_plane_free(context_, AsPlane(tracking_scratch_));
         tracking_scratch_ = 0;
         tracking_scratch_bytes_ = 0;
-        for (std::vector<DevicePtr>* planes : {&denoise_pairs_, &denoise_chains_}) {
+        if (stabilise_scratch_) flow2d_plane_free(context_, AsPlane(stabilise_scratch_));
+        stabilise_scratch_ = 0;
+        for (std::vector<DevicePtr>* planes : {&denoise_pairs_, &denoise_chains_, &stabilise_planes_}) {
             for (DevicePtr p : *planes)
                 if (p) flow2d_plane_free(context_, AsPlane(p));
             planes->clear();
@@ -711,6 +713,258 @@ void OpticalFlow2D::TrackPoints(Data2D* const* frames, size_t frame_count, size_
     flow2d_event_destroy(context_, ev_stop);
     flow2d_synchronize(context_);
     for (const std::vector<DevicePtr>* planes : {&dev_frames, &dev_xs, &dev_ys})
+        for (DevicePtr p : *planes)
+            if (p) flow2d_plane_free(context_, AsPlane(p));
+    last_run_ok_ = ok;
+}
+
+bool OpticalFlow2D::GlobalMotionArgsOk(int model, double sigma, int iterations)
+{
+    if ((model != FLOW2D_MOTION_TRANSLATION && model != FLOW2D_MOTION_SIMILARITY && model != FLOW2D_MOTION_AFFINE) ||
+        !std::isfinite(sigma) || sigma < 0.0 || iterations < 0 || iterations > FLOW2D_GLOBAL_MOTION_MAX_ITERATIONS) {
+        std::printf("Error: global motion takes a model of 0 (translation), 1 (similarity) or 2 (affine) (%d), a finite sigma >= 0 (%g) "
+                    "and 0 .. %d iterations (%d).\n",
+                    model, sigma, FLOW2D_GLOBAL_MOTION_MAX_ITERATIONS, iterations);
+        return false;
+    }
+    return true;
+}
+
+flow2d_global_motion OpticalFlow2D::ComposeGlobalMotion(const flow2d_global_motion& first, const flow2d_global_motion& second)
+{
+    const double a1[4] = {1.0 + first.p[1], first.p[2], first.p[4], 1.0 + first.p[5]};
+    const double a2[4] = {1.0 + second.p[1], second.p[2], second.p[4], 1.0 + second.p[5]};
+    flow2d_global_motion out = second;  // weight_sum, support: the newest fit's
+    const double a11 = a2[0] * a1[0] + a2[1] * a1[2], a12 = a2[0] * a1[1] + a2[1] * a1[3];
+    const double a21 = a2[2] * a1[0] + a2[3] * a1[2], a22 = a2[2] * a1[1] + a2[3] * a1[3];
+    out.p[0] = (a2[0] * first.p[0] + a2[1] * first.p[3]) + second.p[0];
+    out.p[1] = a11 - 1.0;
+    out.p[2] = a12;
+    out.p[3] = (a2[2] * first.p[0] + a2[3] * first.p[3]) + second.p[3];
+    out.p[4] = a21;
+    out.p[5] = a22 - 1.0;
+    out.model_used = std::max(first.model_used, second.model_used);
+    return out;
+}
+
+bool OpticalFlow2D::EnsureStabiliseScratch()
+{
+    if (stabilise_scratch_) return true;
+    const size_t records = (kStabiliseWindow + 1) * sizeof(flow2d_global_motion);  // a multiple of 16
+    stabilise_scratch_ = AllocBytes(records + flow2d_global_motion_workspace_bytes(dev_container_size_.width,
+                                                                                   dev_container_size_.height, 1));
+    return stabilise_scratch_ != 0;
+}
+
+flow2d_global_motion* OpticalFlow2D::StabiliseRecord(size_t slot) const
+{
+    return reinterpret_cast<flow2d_global_motion*>(static_cast<uintptr_t>(stabilise_scratch_)) + slot;
+}
+
+bool OpticalFlow2D::FitConsecutivePairs(const DevicePtr* frames, size_t count, int model, double sigma, int iterations,
+                                        bool use_masks, flow2d_global_motion* records, OperationParameters& params)
+{
+    if (count < 2) return true;
+    const size_t W = dev_container_size_.width, H = dev_container_size_.height, pitch = dev_container_size_.pitch;
+    const size_t per_pair = use_masks ? 6 : 2;
+    if (stabilise_planes_.size() < 6 * kStabiliseWindow) stabilise_planes_.resize(6 * kStabiliseWindow, 0);
+    for (size_t j = 0; j < kStabiliseWindow; ++j)
+        if (!EnsurePlanes(stabilise_planes_.data() + 6 * j, per_pair)) return false;
+    if (!EnsureStabiliseScratch()) return false;
+    void* workspace = StabiliseRecord(kStabiliseWindow + 1);
+    const size_t workspace_bytes = flow2d_global_motion_workspace_bytes(W, H, 1);
+    bool ok = true;
+    for (size_t start = 0; ok && start + 1 < count; start += kStabiliseWindow) {
+        const size_t pairs = std::min(kStabiliseWindow, count - 1 - start);
+        std::vector<DevicePtr> p[6];
+        for (size_t j = 0; j < pairs; ++j)
+            for (size_t i = 0; i < 6; ++i) p[i].push_back(stabilise_planes_[6 * j + i]);
+        ok = use_masks ? ComputeFlowBidirectionalDevice(frames + start, pairs + 1, p[0].data(), p[1].data(), p[2].data(), p[3].data(),
+                                                        p[4].data(), p[5].data(), params)
+                       : ComputeFlowSequenceDevice(frames + start, pairs + 1, p[0].data(), p[1].data(), params);
+        for (size_t j = 0; ok && j < pairs; ++j)
+            ok = !CheckFlow2DError(flow2d_global_motion_2d(context_, AsPlane(p[0][j]), AsPlane(p[1][j]),
+                                                           use_masks ? AsPlane(p[4][j]) : nullptr, W, H, pitch, model, sigma,
+                                                           iterations, StabiliseRecord(j), workspace, workspace_bytes),
+                                   "flow2d_global_motion_2d") &&
+                 !CheckFlow2DError(flow2d_copy_d2h_2d(context_, records + start + j, sizeof(flow2d_global_motion), StabiliseRecord(j),
+                                                      sizeof(flow2d_global_motion), sizeof(flow2d_global_motion), 1),
+                                   "flow2d_copy_d2h_2d");
+        // the records are read by the host next, and the window's planes and record slots are reused
+        ok = !CheckFlow2DError(flow2d_synchronize(context_), "flow2d_synchronize") && ok;
+    }
+    return ok;
+}
+
+bool OpticalFlow2D::EstimateGlobalMotionDevice(DevicePtr dev_frame_0, DevicePtr dev_frame_1, int model, double sigma,
+                                               int iterations, bool use_masks, flow2d_global_motion* motion_out,
+                                               OperationParameters& params, DevicePtr dev_flow_u, DevicePtr dev_flow_v,
+                                               DevicePtr dev_residual_u, DevicePtr dev_residual_v)
+{
+    if (!GlobalMotionArgsOk(model, sigma, iterations)) return false;
+    if (!IsInitialized() || !dev_frame_0 || !dev_frame_1 || !motion_out) return false;
+    if (group_ > 1) {
+        std::printf("Error: '%s': global motion and lock-step groups do not combine.\n", GetName());
+        return false;
+    }
+    if ((dev_flow_u == 0) != (dev_flow_v == 0) || (dev_residual_u == 0) != (dev_residual_v == 0)) return false;
+    const DevicePtr frames[2] = {dev_frame_0, dev_frame_1};
+    if (!FitConsecutivePairs(frames, 2, model, sigma, iterations, use_masks, motion_out, params)) return false;
+    // the pair's flow and record are still in slot 0
+    const size_t W = dev_container_size_.width, H = dev_container_size_.height, pitch = dev_container_size_.pitch;
+    bool ok = true;
+    if (dev_flow_u) {
+        const void* src[2] = {AsPlane(stabilise_planes_[0]), AsPlane(stabilise_planes_[1])};
+        void* dst[2] = {AsPlane(dev_flow_u), AsPlane(dev_flow_v)};
+        ok = !CheckFlow2DError(flow2d_copy_planes(context_, 2, src, dst, pitch, W, H), "flow2d_copy_planes");
+    }
+    if (ok && dev_residual_u)
+        ok = !CheckFlow2DError(flow2d_global_flow_2d(context_, StabiliseRecord(0), AsPlane(stabilise_planes_[0]),
+                                                     AsPlane(stabilise_planes_[1]), nullptr, W, H, pitch, 0.0, nullptr, nullptr,
+                                                     AsPlane(dev_residual_u), AsPlane(dev_residual_v), nullptr),
+                               "flow2d_global_flow_2d");
+    return !CheckFlow2DError(flow2d_synchronize(context_), "flow2d_synchronize") && ok;
+}
+
+void OpticalFlow2D::EstimateGlobalMotion(Data2D& frame_0, Data2D& frame_1, int model, double sigma, int iterations, bool use_masks,
+                                         flow2d_global_motion* motion_out, OperationParameters& params, Data2D* flow_u,
+                                         Data2D* flow_v, Data2D* residual_u, Data2D* residual_v)
+{
+    last_run_ok_ = false;
+    if (!GlobalMotionArgsOk(model, sigma, iterations)) return;
+    if (!IsInitialized() || !motion_out) return;
+    const size_t W = dev_container_size_.width, H = dev_container_size_.height, pitch = dev_container_size_.pitch;
+    Data2D* images[6] = {&frame_0, &frame_1, flow_u, flow_v, residual_u, residual_v};
+    for (Data2D* d : images)
+        if (d && (d->Width() != W || d->Height() != H)) {
+            std::printf("Error: '%s': frame / flow sizes do not match the initialised size %zu x %zu.\n", GetName(), W, H);
+            return;
+        }
+    DevicePtr d[6] = {0, 0, 0, 0, 0, 0};  // the planes of this call (freed at its end)
+    bool ok = EnsurePlanes(d, 6);
+    std::printf("\nStarting optical flow computation...\n");
+    void *ev_start = nullptr, *ev_stop = nullptr;
+    flow2d_event_create(context_, &ev_start);
+    flow2d_event_create(context_, &ev_stop);
+    flow2d_event_record(context_, ev_start);
+    ok = ok && CopyData2DtoDevice(frame_0, d[0], H, pitch) && CopyData2DtoDevice(frame_1, d[1], H, pitch);
+    ok = ok && EstimateGlobalMotionDevice(d[0], d[1], model, sigma, iterations, use_masks, motion_out, params, d[2], d[3], d[4], d[5]);
+    for (int i = 2; ok && i < 6; ++i)
+        if (images[i]) ok = CopyData2DFromDevice(d[i], *images[i], H, pitch);
+    flow2d_event_record(context_, ev_stop);
+    flow2d_event_synchronize(context_, ev_stop);  // the downloads
+    flow2d_event_elapsed_ms(context_, ev_start, ev_stop, &last_total_ms_);
+    std::printf("Total GPU computation time: % 4.4fs\n", last_total_ms_ / 1000.);
+    flow2d_event_destroy(context_, ev_start);
+    flow2d_event_destroy(context_, ev_stop);
+    flow2d_synchronize(context_);
+    for (DevicePtr p : d)
+        if (p) flow2d_plane_free(context_, AsPlane(p));
+    last_run_ok_ = ok;
+}
+
+bool OpticalFlow2D::StabiliseSequenceDevice(const DevicePtr* dev_frames, size_t frame_count, size_t reference_index, int model,
+                                            double sigma, int iterations, bool use_masks, float fill,
+                                            const DevicePtr* dev_outputs, flow2d_global_motion* motions_out,
+                                            OperationParameters& params)
+{
+    if (!GlobalMotionArgsOk(model, sigma, iterations)) return false;
+    if (frame_count < 2 || reference_index >= frame_count) {
+        std::printf("Error: stabilisation takes at least 2 frames (%zu) and a reference frame among them (%zu).\n", frame_count,
+                    reference_index);
+        return false;
+    }
+    if (!IsInitialized() || !dev_frames || !dev_outputs) return false;
+    if (group_ > 1) {
+        std::printf("Error: '%s': sequences and lock-step groups do not combine.\n", GetName());
+        return false;
+    }
+    for (size_t k = 0; k < frame_count; ++k) {
+        if (!dev_frames[k] || !dev_outputs[k]) return false;
+        for (size_t j = 0; j < frame_count; ++j)
+            if (dev_outputs[k] == dev_frames[j]) {
+                std::printf("Error: '%s': an output plane is one of the frames.\n", GetName());
+                return false;
+            }
+        for (size_t j = k + 1; j < frame_count; ++j)
+            if (dev_outputs[k] == dev_outputs[j]) {
+                std::printf("Error: '%s': the output planes must be distinct.\n", GetName());
+                return false;
+            }
+    }
+    const size_t W = dev_container_size_.width, H = dev_container_size_.height, pitch = dev_container_size_.pitch;
+    const size_t ref = reference_index;
+    // steps[k]: above the reference M(k - 1 -> k), below it M(k + 1 -> k)
+    std::vector<flow2d_global_motion> steps(frame_count), composed(frame_count);
+    std::vector<DevicePtr> reversed(dev_frames, dev_frames + ref + 1);
+    std::reverse(reversed.begin(), reversed.end());  // frame ref, ref - 1, ..., 0
+    std::vector<flow2d_global_motion> below(ref);
+    if (!FitConsecutivePairs(dev_frames + ref, frame_count - ref, model, sigma, iterations, use_masks, steps.data() + ref + 1, params) ||
+        !FitConsecutivePairs(reversed.data(), ref + 1, model, sigma, iterations, use_masks, below.data(), params))
+        return false;
+    for (size_t i = 0; i < ref; ++i) steps[ref - 1 - i] = below[i];
+    flow2d_global_motion identity = {};
+    identity.model_used = model;
+    composed[ref] = identity;
+    for (size_t k = ref + 1; k < frame_count; ++k)
+        composed[k] = k == ref + 1 ? steps[k] : ComposeGlobalMotion(composed[k - 1], steps[k]);
+    for (size_t k = ref; k-- > 0;) composed[k] = k + 1 == ref ? steps[k] : ComposeGlobalMotion(composed[k + 1], steps[k]);
+    if (!EnsureStabiliseScratch()) return false;
+    bool ok = true;
+    for (size_t k = 0; ok && k < frame_count; ++k) {
+        if (k == ref) {
+            const void* src[1] = {AsPlane(dev_frames[k])};
+            void* dst[1] = {AsPlane(dev_outputs[k])};
+            ok = !CheckFlow2DError(flow2d_copy_planes(context_, 1, src, dst, pitch, W, H), "flow2d_copy_planes");
+            continue;
+        }
+        // (one record slot: the upload of the next record is ordered behind this warp on the stream)
+        ok = !CheckFlow2DError(flow2d_copy_h2d_2d(context_, StabiliseRecord(kStabiliseWindow), sizeof(flow2d_global_motion), &composed[k],
+                                                  sizeof(flow2d_global_motion), sizeof(flow2d_global_motion), 1),
+                               "flow2d_copy_h2d_2d") &&
+             !CheckFlow2DError(flow2d_warp_global_2d(context_, StabiliseRecord(kStabiliseWindow), AsPlane(dev_frames[k]), W, H, pitch,
+                                                     fill, AsPlane(dev_outputs[k]), nullptr),
+                               "flow2d_warp_global_2d");
+    }
+    ok = !CheckFlow2DError(flow2d_synchronize(context_), "flow2d_synchronize") && ok;  // `composed` is the uploads' source
+    if (ok && motions_out)
+        for (size_t k = 0; k < frame_count; ++k) motions_out[k] = composed[k];
+    return ok;
+}
+
+void OpticalFlow2D::StabiliseSequence(Data2D* const* frames, size_t frame_count, size_t reference_index, int model, double sigma,
+                                      int iterations, bool use_masks, float fill, Data2D* outputs,
+                                      flow2d_global_motion* motions_out, OperationParameters& params)
+{
+    last_run_ok_ = false;
+    if (!GlobalMotionArgsOk(model, sigma, iterations)) return;
+    if (!IsInitialized() || !frames || !outputs || frame_count < 2 || reference_index >= frame_count) return;
+    const size_t W = dev_container_size_.width, H = dev_container_size_.height, pitch = dev_container_size_.pitch;
+    for (size_t k = 0; k < frame_count; ++k)
+        if (!frames[k] || frames[k]->Width() != W || frames[k]->Height() != H || outputs[k].Width() != W || outputs[k].Height() != H) {
+            std::printf("Error: '%s': frame / output sizes do not match the initialised size %zu x %zu.\n", GetName(), W, H);
+            return;
+        }
+    // the frames and the outputs of this call (freed at its end)
+    std::vector<DevicePtr> dev_frames(frame_count, 0), dev_outputs(frame_count, 0);
+    bool ok = EnsurePlanes(dev_frames.data(), frame_count) && EnsurePlanes(dev_outputs.data(), frame_count);
+    std::printf("\nStarting optical flow computation...\n");
+    void *ev_start = nullptr, *ev_stop = nullptr;
+    flow2d_event_create(context_, &ev_start);
+    flow2d_event_create(context_, &ev_stop);
+    flow2d_event_record(context_, ev_start);
+    for (size_t k = 0; ok && k < frame_count; ++k) ok = CopyData2DtoDevice(*frames[k], dev_frames[k], H, pitch);
+    ok = ok && StabiliseSequenceDevice(dev_frames.data(), frame_count, reference_index, model, sigma, iterations, use_masks, fill,
+                                       dev_outputs.data(), motions_out, params);
+    for (size_t k = 0; ok && k < frame_count; ++k) ok = CopyData2DFromDevice(dev_outputs[k], outputs[k], H, pitch);
+    flow2d_event_record(context_, ev_stop);
+    flow2d_event_synchronize(context_, ev_stop);  // the downloads
+    flow2d_event_elapsed_ms(context_, ev_start, ev_stop, &last_total_ms_);
+    std::printf("Total GPU computation time: % 4.4fs\n", last_total_ms_ / 1000.);
+    flow2d_event_destroy(context_, ev_start);
+    flow2d_event_destroy(context_, ev_stop);
+    flow2d_synchronize(context_);
+    for (const std::vector<DevicePtr>* planes : {&dev_frames, &dev_outputs})
         for (DevicePtr p : *planes)
             if (p) flow2d_plane_free(context_, AsPlane(p));
     last_run_ok_ = ok;

@@ -168,6 +168,48 @@ public:
     void DenoiseSequence(Data2D* const* frames, size_t frame_count, size_t radius, float range_sigma, bool use_masks,
                          Data2D* outputs, Data2D* weight_sums, OperationParameters& params);
 
+    // Global motion of a pair and reference-locked stabilisation of a sequence (no reference counterpart).
+    // model: flow2d_motion_model; sigma (pixels, finite, >= 0; 0 = plain least squares) and iterations (0 .. 16) are those of
+    // flow2d_global_motion_2d.  GlobalMotionArgsOk prints what is wrong; needs no device.
+    static bool GlobalMotionArgsOk(int model, double sigma, int iterations);
+    // The composition `second` after `first` of two records, in centred coordinates and in double, in exactly this order:
+    //   A = [[1 + p1, p2], [p4, 1 + p5]], t = (p0, p3) of each record;
+    //   a11 = A2_11*A1_11 + A2_12*A1_21, a12 = A2_11*A1_12 + A2_12*A1_22, a21 = A2_21*A1_11 + A2_22*A1_21, a22 = A2_21*A1_12 + A2_22*A1_22,
+    //   tx = (A2_11*t1x + A2_12*t1y) + t2x,  ty = (A2_21*t1x + A2_22*t1y) + t2y;   p = (tx, a11 - 1, a12, ty, a21, a22 - 1)
+    // Translations stay translations and similarities similarities, bit for bit (p1 == p5, p2 == -p4).  weight_sum and support
+    // are those of `second` (the newest fit), model_used the larger of the two.
+    static flow2d_global_motion ComposeGlobalMotion(const flow2d_global_motion& first, const flow2d_global_motion& second);
+    // One pair: the flow frame_0 -> frame_1 (ComputeFlowDevice's bits; with use_masks through ComputeFlowBidirectionalDevice, the
+    // forward occlusion mask leaving its vectors out of the fit), flow2d_global_motion_2d, and the record returned to the host
+    // (the call synchronises).  Optional planes: dev_flow_u / dev_flow_v get the flow, dev_residual_u / dev_residual_v the flow
+    // without the global motion (flow2d_global_flow_2d).
+    bool EstimateGlobalMotionDevice(DevicePtr dev_frame_0, DevicePtr dev_frame_1, int model, double sigma, int iterations,
+                                    bool use_masks, flow2d_global_motion* motion_out, OperationParameters& params,
+                                    DevicePtr dev_flow_u = 0, DevicePtr dev_flow_v = 0, DevicePtr dev_residual_u = 0,
+                                    DevicePtr dev_residual_v = 0);
+    // The host-image form (the CLI's --global-motion).  LastRunSucceeded and LastTotalMs as for ComputeFlow.
+    void EstimateGlobalMotion(Data2D& frame_0, Data2D& frame_1, int model, double sigma, int iterations, bool use_masks,
+                              flow2d_global_motion* motion_out, OperationParameters& params, Data2D* flow_u = nullptr,
+                              Data2D* flow_v = nullptr, Data2D* residual_u = nullptr, Data2D* residual_v = nullptr);
+    // Every frame of a sequence brought onto the grid of frames[reference_index]: for every consecutive pair the flow towards
+    // the far side of the reference is fitted -- frame k -> k + 1 for k >= reference_index, frame k + 1 -> k below it; only
+    // those directions are computed, both with use_masks (the consistency check needs them) --, each record is downloaded, the
+    // records are composed on the host outwards from the reference, M(ref -> k) = M(k - 1 -> k) o M(ref -> k - 1) above it and
+    // M(ref -> k) = M(k + 1 -> k) o M(ref -> k + 1) below it (ComposeGlobalMotion), and dev_outputs[k] = frame k resampled by
+    // flow2d_warp_global_2d along M(ref -> k), `fill` where that leaves frame k.  The reference frame is copied bit for bit.
+    // motions_out (optional, frame_count records) gets M(ref -> k); the reference's is the identity.  The flows are those of
+    // ComputeFlowDevice on each ordered pair, bit for bit, computed kStabiliseWindow pairs at a time into planes allocated
+    // once: the device memory beyond the caller's planes does not depend on frame_count.  frame_count >= 2.  Frames are only
+    // read; outputs must be distinct from each other and from the frames.  The call synchronises.  Not for lock-step groups.
+    static constexpr size_t kStabiliseWindow = 2;
+    bool StabiliseSequenceDevice(const DevicePtr* dev_frames, size_t frame_count, size_t reference_index, int model, double sigma,
+                                 int iterations, bool use_masks, float fill, const DevicePtr* dev_outputs,
+                                 flow2d_global_motion* motions_out, OperationParameters& params);
+    // The host-image form: upload the frames, StabiliseSequenceDevice, download into outputs[0 .. frame_count - 1].
+    void StabiliseSequence(Data2D* const* frames, size_t frame_count, size_t reference_index, int model, double sigma,
+                           int iterations, bool use_masks, float fill, Data2D* outputs, flow2d_global_motion* motions_out,
+                           OperationParameters& params);
+
     // When set, ComputeFlowDevice records the whole pyramid of a pair into a HIP graph the first time it
     // sees a (buffers, parameters) combination and replays it afterwards: one host call instead of
     // several hundred launches.  Ignored while timing_mode != 0 (events are not captured).
@@ -276,6 +318,15 @@ private:
     // allocated on the first call with use_masks) and the composed flows of a centre (u, v, mask per direction and distance >= 2)
     std::vector<DevicePtr> denoise_pairs_;
     std::vector<DevicePtr> denoise_chains_;
+    // EstimateGlobalMotion* / StabiliseSequence*: the flows of a window (u, v, back u, back v, occlusion forward, occlusion
+    // backward per pair; allocated as needed) and, in one allocation, kStabiliseWindow + 1 records and the fit's workspace
+    std::vector<DevicePtr> stabilise_planes_;
+    DevicePtr stabilise_scratch_ = 0;
+    bool EnsureStabiliseScratch();
+    flow2d_global_motion* StabiliseRecord(size_t slot) const;
+    // the records of the flows frames[i] -> frames[i + 1], i < count - 1, of an ordered list of frames into records[i]
+    bool FitConsecutivePairs(const DevicePtr* frames, size_t count, int model, double sigma, int iterations, bool use_masks,
+                             flow2d_global_motion* records, OperationParameters& params);
     flow2d_context* context_ = nullptr;
     // One plane beside the pool: the warped frame of a level, when the levels of both frames are computed up front into plane
     // regions of their own (RunPyramid: "stacked" levels) and therefore cannot be overwritten by the warp

@@ -36,8 +36,9 @@ extern "C" {
 /* Additions that leave every existing entry as it was keep the version: flow2d_consistency_2d (forward-backward occlusion
  * masks), flow2d_flow_error_2d / flow2d_flow_error_workspace_bytes (error statistics against ground truth),
  * flow2d_interpolate_2d (occlusion-aware frame interpolation), flow2d_track_points_2d / flow2d_seed_points_2d /
- * flow2d_seed_points_workspace_bytes (dense point trajectories) and flow2d_denoise_2d / flow2d_compose_flow_2d
- * (motion-compensated temporal denoising) were added under 1. */
+ * flow2d_seed_points_workspace_bytes (dense point trajectories), flow2d_denoise_2d / flow2d_compose_flow_2d
+ * (motion-compensated temporal denoising) and flow2d_global_motion_2d / flow2d_global_motion_workspace_bytes /
+ * flow2d_global_flow_2d / flow2d_warp_global_2d (robust global motion and stabilisation) were added under 1. */
 #define FLOW2D_ABI_VERSION 1
 
 typedef enum flow2d_status {
@@ -434,6 +435,120 @@ FLOW2D_API int flow2d_flow_error_2d(flow2d_context* ctx, const float* flow_u, co
                                     const float* gt_v, const float* occlusion, size_t width, size_t height, size_t pitch_bytes,
                                     float* epe, float* ae, flow2d_flow_error_stats* stats, void* workspace,
                                     size_t workspace_bytes);
+
+/* Robust global motion of a flow field, and what it is good for (no reference counterpart; added to ABI version 1 without
+ * changing any existing entry): the parametric motion of the whole frame fitted to a flow by iteratively reweighted least
+ * squares (flow2d_global_motion_2d), that model as planes with the residual flow and the inlier map (flow2d_global_flow_2d),
+ * and a frame resampled along a model (flow2d_warp_global_2d: stabilisation).
+ *
+ * The model, in coordinates centred on the frame, xc = x - (width - 1) / 2, yc = y - (height - 1) / 2:
+ *   mu(x) = (p0 + p1*xc) + p2*yc,   mv(x) = (p3 + p4*xc) + p5*yc
+ * All arithmetic of the three entries is IEEE double, every operation rounded on its own (no fused multiply-add), in the order
+ * written here; x, y, width - 1 and height - 1 convert exactly and the halves are exact.
+ *
+ * flow2d_global_motion_2d fits `model` to (flow_u, flow_v).  Per pixel, with u = flow_u[p], v = flow_v[p] (fp32, converted):
+ *   valid = |u| <= 1e9 and |v| <= 1e9                 (finite: the rule of flow2d_flow_error_2d's ground truth)
+ *   m     = mask ? mask[p] : 0;  if (!(m <= 1)) m = 1;  if (!(m >= 0)) m = 0      (fp32, the clamp of flow2d_denoise_2d: NaN = 1;
+ *           `mask` is 1 where the vector is to be left out, as flow2d_consistency_2d writes it)
+ *   b     = valid ? 1 - m : 0   (1 - m in fp32, then converted);   an invalid pixel takes part with u = v = 0 and w = 0
+ *   pass 0:                       w = b
+ *   pass k = 1 .. iterations, only when sigma > 0, with the parameters p of pass k - 1:
+ *                                 du = u - ((p0 + p1*xc) + p2*yc),  dv = v - ((p3 + p4*xc) + p5*yc),
+ *                                 w = b * (s2 / (s2 + (du*du + dv*dv))),   s2 = sigma*sigma
+ *   (the rational weight of flow2d_denoise_2d; sigma in pixels; with sigma == 0 only pass 0 runs: plain least squares)
+ * Every pass forms twelve sums over the frame, with wx = w*xc, wy = w*yc:
+ *   S0 = sum w, Sx = sum wx, Sy = sum wy, Sxx = sum wx*xc, Sxy = sum wx*yc, Syy = sum wy*yc,
+ *   Su = sum w*u, Sxu = sum wx*u, Syu = sum wy*u, Sv = sum w*v, Sxv = sum wx*v, Syv = sum wy*v
+ * and solves about the weighted centroid:
+ *   !(S0 > 0):  p = 0, model_used = -1, done
+ *   mx = Sx/S0, my = Sy/S0, mu = Su/S0, mv = Sv/S0
+ *   cxx = Sxx/S0 - mx*mx, cxy = Sxy/S0 - mx*my, cyy = Syy/S0 - my*my
+ *   cxu = Sxu/S0 - mx*mu, cyu = Syu/S0 - my*mu, cxv = Sxv/S0 - mx*mv, cyv = Syv/S0 - my*mv
+ *   spread = cxx + cyy,  det = cxx*cyy - cxy*cxy
+ *   used = model;  AFFINE and !(spread > 1e-9 and det > 1e-9 * (spread*spread)) -> SIMILARITY;
+ *                  SIMILARITY and !(spread > 1e-9) -> TRANSLATION
+ *   AFFINE:       p1 = (cxu*cyy - cyu*cxy)/det,  p2 = (cyu*cxx - cxu*cxy)/det,
+ *                 p4 = (cxv*cyy - cyv*cxy)/det,  p5 = (cyv*cxx - cxv*cxy)/det
+ *   SIMILARITY:   a = (cxu + cyv)/spread,  b = (cxv - cyu)/spread;  p1 = a, p2 = -b, p4 = b, p5 = a
+ *                 (u = tx + a*xc - b*yc, v = ty + b*xc + a*yc: rotation and isotropic zoom)
+ *   TRANSLATION:  p1 = p2 = p4 = p5 = 0
+ *   p0 = mu - (p1*mx + p2*my),  p3 = mv - (p4*mx + p5*my)
+ * motion[b] (DEVICE memory) gets the record of instance b of a lock-step batch after the last pass: p, weight_sum = S0 of that
+ * pass, support = the number of pixels with b > 0, model_used = the model that ran (a model whose rank condition fails falls
+ * back to the next simpler one) or -1.
+ * Deterministic: the sums run in a fixed order that depends only on (width, height) -- per workgroup of 256 columns x 32 rows
+ * a slab of partial sums in the caller's `workspace`, then one workgroup per instance adds the slabs in block order and solves
+ * --, so repeated calls, a replayed graph and an instance alone or in its batch give the same bytes.  A pass reads the record
+ * of the pass before from `motion` on the device: 2 * (passes) launches on the context's stream, passes = 1 + (sigma > 0 ?
+ * iterations : 0), no host round trip, no allocation, no synchronisation, no atomics (graph-capturable).  `workspace` holds at
+ * least flow2d_global_motion_workspace_bytes(width, height, instances) bytes, 16-byte aligned.
+ * FLOW2D_ERR_INVALID_ARGUMENT for a null flow plane, `motion` or `workspace`, a zero size, a bad pitch, a negative or
+ * non-finite sigma, iterations outside [0, 16], an unknown model, a misaligned `motion` (8) or `workspace` (16), a workspace
+ * too small, or `motion` / `workspace` bytes -- over every instance of a batch -- that overlap an input plane or each other.
+ * Honours flow2d_context_set_batch. */
+typedef enum flow2d_motion_model {
+    FLOW2D_MOTION_TRANSLATION = 0,
+    FLOW2D_MOTION_SIMILARITY = 1,
+    FLOW2D_MOTION_AFFINE = 2
+} flow2d_motion_model;
+
+typedef struct flow2d_global_motion {
+    double p[6];                /* u = (p0 + p1*xc) + p2*yc, v = (p3 + p4*xc) + p5*yc, centred coordinates */
+    double weight_sum;          /* S0 of the last pass */
+    unsigned long long support; /* pixels with b > 0 */
+    int model_used;             /* flow2d_motion_model, or -1: nothing to fit */
+    int reserved[3];            /* 0 */
+} flow2d_global_motion;
+
+#define FLOW2D_GLOBAL_MOTION_BYTES 80
+#define FLOW2D_GLOBAL_MOTION_MAX_ITERATIONS 16
+#ifdef __cplusplus
+static_assert(sizeof(flow2d_global_motion) == FLOW2D_GLOBAL_MOTION_BYTES, "flow2d_global_motion layout");
+#else
+_Static_assert(sizeof(flow2d_global_motion) == FLOW2D_GLOBAL_MOTION_BYTES, "flow2d_global_motion layout");
+#endif
+
+/* Workspace bytes flow2d_global_motion_2d needs for `instances` lock-step instances of a width x height flow (0 for a zero
+ * size).  Host logic only, needs no device. */
+FLOW2D_API size_t flow2d_global_motion_workspace_bytes(size_t width, size_t height, size_t instances);
+FLOW2D_API int flow2d_global_motion_2d(flow2d_context* ctx, const float* flow_u, const float* flow_v,
+                                       const float* mask /* may be NULL */, size_t width, size_t height, size_t pitch_bytes,
+                                       int model, double sigma, int iterations, flow2d_global_motion* motion /* device */,
+                                       void* workspace, size_t workspace_bytes);
+
+/* The model of a record as planes, and what is left of a flow once it is taken out.  motion: DEVICE memory, record b for
+ * instance b.  Every output is optional, at least one is required; for every pixel, with (mu, mv) the model above in double:
+ *   model_u = (float)mu, model_v = (float)mv                                 (one rounding)
+ *   residual_u = valid ? (float)((double)u - mu) : NaN, residual_v likewise  (valid, u, v as above; NaN = 0x7fc00000; what moves
+ *                relative to the global motion)
+ *   weight = (float)(sigma > 0 ? b * (s2 / (s2 + (du*du + dv*dv))) : b)      (b, du, dv, s2 as above with the caller's mask and
+ *                sigma: the inlier map of a pass that uses this record; a NaN is written as 0x7fc00000)
+ * residual_* and weight need both flow planes; model_* alone needs none (flow_u = flow_v = NULL).  Full statistics of the
+ * residual: pass model_u / model_v as the "ground truth" of flow2d_flow_error_2d.  One launch, no allocation, no
+ * synchronisation (graph-capturable); honours flow2d_context_set_batch.  FLOW2D_ERR_INVALID_ARGUMENT for a null or misaligned
+ * `motion`, no output at all, only one plane of a pair (flow, model, residual), residual or weight without the flow, a zero
+ * size, a bad pitch, a negative or non-finite sigma, or a written plane whose bytes -- over every instance of a batch --
+ * overlap those of an input plane, of the records or of another written plane (the rules of flow2d_compose_flow_2d). */
+FLOW2D_API int flow2d_global_flow_2d(flow2d_context* ctx, const flow2d_global_motion* motion /* device */,
+                                     const float* flow_u /* may be NULL */, const float* flow_v /* may be NULL */,
+                                     const float* mask /* may be NULL */, size_t width, size_t height, size_t pitch_bytes,
+                                     double sigma, float* model_u, float* model_v, float* residual_u, float* residual_v,
+                                     float* weight);
+
+/* One frame resampled along a global motion (stabilisation): for every pixel x = (x, y)
+ *   q = ((float)((double)x + mu), (float)((double)y + mv))          (the model in double, one rounding per component)
+ *   ok = 0 <= q.x <= width - 1 and 0 <= q.y <= height - 1           (fp32 comparisons; a NaN or an infinity fails)
+ *   output[x] = ok ? S(frame, q) : fill;   valid[x] = ok ? 1 : 0    (when `valid` is not NULL)
+ * S: the bilinear sample of flow2d_consistency_2d, the same fp32 operations in the same order; every read stays inside the
+ * plane.  With the record of the motion frame a -> frame b and frame = b, output is b brought back onto a's grid.  No flow plane
+ * is read: 4 bytes gathered and 4 - 8 written per pixel.  motion: DEVICE memory, record b for instance b.  One launch, no
+ * allocation, no synchronisation (graph-capturable); honours flow2d_context_set_batch.  FLOW2D_ERR_INVALID_ARGUMENT for a null
+ * or misaligned `motion`, a null `frame` or `output`, a zero size, a bad pitch (the rule of flow2d_consistency_2d), or
+ * `output` / `valid` bytes -- over every instance of a batch -- that overlap `frame`, the records or each other.  `fill` may be
+ * any float, a NaN included. */
+FLOW2D_API int flow2d_warp_global_2d(flow2d_context* ctx, const flow2d_global_motion* motion /* device */, const float* frame,
+                                     size_t width, size_t height, size_t pitch_bytes, float fill, float* output,
+                                     float* valid /* may be NULL */);
 
 /* The flow of the previous pyramid level resampled to this level's size (the bits of flow2d_resample_xy_pair into out_u / out_v)
  * and frame_1 warped by it (the bits of flow2d_registration_2d into `output`) in one launch: replaces the
