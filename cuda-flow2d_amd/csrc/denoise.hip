@@ -7,80 +7,23 @@
 // bilinear sample is the operation order of flow2d_consistency_2d (consistency.hip).  Built -ffp-contract=off and with the
 // correctly rounded fp32 division: the bits follow those definitions exactly.
 //
-// Geometry of consistency.hip: 64 x 4 threads, kRows rows per thread, one byte offset per lane (32 bits when the plane's span
-// allows) against scalar plane bases, column-pair dwordx2 gathers.  There is no dependent gather chain: the coalesced loads
+// Geometry and sampler of plane_sample.hpp: 64 x 4 threads, kRows rows per thread, one byte offset per lane (32 bits when the
+// plane's span allows) against scalar plane bases, column-pair dwordx2 gathers.  There is no dependent gather chain: the coalesced loads
 // (flow, mask) of all neighbours and rows of a thread are issued first, then all gathers, then the sums in neighbour order.
 // The kernel is templated on N so that the loops unroll and the pointer table stays in scalar registers; rows per thread fall
 // with N (rows x N <= 8) so that the loads in flight fit the register file without scratch.
 // Per pixel 8 + 16 N algorithmic bytes (12 N without masks): memory-bound.
 #include <cmath>
 
-#include "common.hpp"
+#include "plane_sample.hpp"
 
 namespace {
 
-constexpr int kBlockX = 64;
-constexpr int kBlockY = 4;
-constexpr int kComposeRows = 4;  // rows per thread: the geometry of consistency_kernel
+constexpr int kComposeRows = 4;  // rows per thread
 constexpr int kMaxNeighbours = FLOW2D_DENOISE_MAX_NEIGHBOURS;
 constexpr unsigned kQuietNaN = 0x7fc00000u;
 
 constexpr int denoise_rows(int n) { return n <= 2 ? 4 : (n <= 4 ? 2 : 1); }
-
-// Offset: unsigned (the plane's span fits 32 bits: per-lane 32-bit offsets against scalar bases) or size_t.
-template <typename Offset>
-__device__ __forceinline__ float2 column_pair(const float* base, Offset byte_offset)
-{
-    const float* p = reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + byte_offset);
-    return make_float2(p[0], p[1]);
-}
-
-template <typename Offset>
-__device__ __forceinline__ float load_at(const float* base, Offset byte_offset)
-{
-    return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + byte_offset);
-}
-
-template <typename Offset>
-__device__ __forceinline__ void store_at(float* base, Offset byte_offset, float value)
-{
-    *reinterpret_cast<float*>(reinterpret_cast<char*>(base) + byte_offset) = value;
-}
-
-// Where S(P, q) reads, for q inside [0, w - 1] x [0, h - 1]
-template <typename Offset>
-struct Tap {
-    Offset o0, o1;  // byte offsets of the column pairs (xb, xb + 1) in rows y and y1
-    float dx, dy;
-    bool x_second, x1_second;
-};
-
-template <typename Offset>
-__device__ __forceinline__ Tap<Offset> make_tap(float qx, float qy, int w, int h, int pitch)
-{
-    const int x = static_cast<int>(floorf(qx));
-    const int y = static_cast<int>(floorf(qy));
-    const int x1 = min(w - 1, x + 1);
-    const int y1 = min(h - 1, y + 1);
-    // the column pair (xb, xb + 1), xb = min(x, w - 2), holds x and x1 (w = 1: the second column is row padding, never selected)
-    const int xb = max(min(x, w - 2), 0);
-    Tap<Offset> t;
-    t.o0 = (static_cast<Offset>(y) * static_cast<Offset>(pitch) + static_cast<Offset>(xb)) * sizeof(float);
-    t.o1 = (static_cast<Offset>(y1) * static_cast<Offset>(pitch) + static_cast<Offset>(xb)) * sizeof(float);
-    t.dx = qx - static_cast<float>(x);
-    t.dy = qy - static_cast<float>(y);
-    t.x_second = x != xb;
-    t.x1_second = x1 != xb;
-    return t;
-}
-
-template <typename Offset>
-__device__ __forceinline__ float blend(const Tap<Offset>& t, float2 a, float2 b)
-{
-    const float w00 = (1.f - t.dx) * (1.f - t.dy), w01 = (t.dx) * (1.f - t.dy), w10 = (1.f - t.dx) * (t.dy), w11 = (t.dx) * (t.dy);
-    return w00 * (t.x_second ? a.y : a.x) + w01 * (t.x1_second ? a.y : a.x) + w10 * (t.x_second ? b.y : b.x) +
-           w11 * (t.x1_second ? b.y : b.x);
-}
 
 template <int N>
 struct DenoiseNeighbours {
@@ -100,7 +43,7 @@ __global__ __launch_bounds__(256) void denoise_kernel(const float* __restrict__ 
     centre += inst;
     output += inst;
     if (weight_sum) weight_sum += inst;
-    const int gx = blockIdx.x * kBlockX + threadIdx.x;
+    const int gx = pixel_column();
     if (gx >= w) return;
     const float cx = static_cast<float>(gx);
     const float x_max = static_cast<float>(w - 1), y_max = static_cast<float>(h - 1);
@@ -110,9 +53,9 @@ __global__ __launch_bounds__(256) void denoise_kernel(const float* __restrict__ 
     Offset at[R];
 #pragma unroll
     for (int i = 0; i < R; ++i) {
-        const int gy = min((blockIdx.y * R + i) * kBlockY + threadIdx.y, h - 1);
+        const int gy = min(pixel_row(R, i), h - 1);
         cy[i] = static_cast<float>(gy);
-        at[i] = (static_cast<Offset>(gy) * static_cast<Offset>(pitch) + static_cast<Offset>(gx)) * sizeof(float);
+        at[i] = pixel_offset<Offset>(gx, gy, pitch);
         c[i] = load_at(centre, at[i]);
 #pragma unroll
         for (int n = 0; n < N; ++n) {
@@ -168,7 +111,7 @@ __global__ __launch_bounds__(256) void denoise_kernel(const float* __restrict__ 
     }
 #pragma unroll
     for (int i = 0; i < R; ++i) {
-        const int gy = (blockIdx.y * R + i) * kBlockY + threadIdx.y;
+        const int gy = pixel_row(R, i);
         if (gy >= h) return;
         store_at(output, at[i], out[i]);
         if (weight_sum) store_at(weight_sum, at[i], den_out[i]);
@@ -198,7 +141,7 @@ __global__ __launch_bounds__(256) void compose_kernel(const float* __restrict__ 
     out_u += inst;
     out_v += inst;
     if (out_mask) out_mask += inst;
-    const int gx = blockIdx.x * kBlockX + threadIdx.x;
+    const int gx = pixel_column();
     if (gx >= w) return;
     const float cx = static_cast<float>(gx);
     const float x_max = static_cast<float>(w - 1), y_max = static_cast<float>(h - 1);
@@ -208,9 +151,9 @@ __global__ __launch_bounds__(256) void compose_kernel(const float* __restrict__ 
     Offset at[kComposeRows];
 #pragma unroll
     for (int i = 0; i < kComposeRows; ++i) {
-        const int gy = min((blockIdx.y * kComposeRows + i) * kBlockY + threadIdx.y, h - 1);
+        const int gy = min(pixel_row(kComposeRows, i), h - 1);
         cy[i] = static_cast<float>(gy);
-        at[i] = (static_cast<Offset>(gy) * static_cast<Offset>(pitch) + static_cast<Offset>(gx)) * sizeof(float);
+        at[i] = pixel_offset<Offset>(gx, gy, pitch);
         fu[i] = load_at(ab_u, at[i]);
         fv[i] = load_at(ab_v, at[i]);
         ma[i] = (masks && mask_ab) ? load_at(mask_ab, at[i]) : 0.f;
@@ -240,7 +183,7 @@ __global__ __launch_bounds__(256) void compose_kernel(const float* __restrict__ 
     }
 #pragma unroll
     for (int i = 0; i < kComposeRows; ++i) {
-        const int gy = (blockIdx.y * kComposeRows + i) * kBlockY + threadIdx.y;
+        const int gy = pixel_row(kComposeRows, i);
         if (gy >= h) return;
         const float nan = __uint_as_float(kQuietNaN);
         const float su = blend(tap[i], ga[i][0], gb[i][0]);
@@ -252,12 +195,6 @@ __global__ __launch_bounds__(256) void compose_kernel(const float* __restrict__ 
             store_at(out_mask, at[i], (!ok[i] || !(ma[i] == 0.f) || !(sm <= 0.f)) ? 1.f : 0.f);
         }
     }
-}
-
-inline bool ranges_overlap(const void* a, const void* b, size_t bytes)
-{
-    const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
-    return pa < pb + bytes && pb < pa + bytes;
 }
 
 template <int N>
@@ -272,16 +209,11 @@ void launch_denoise(flow2d_context* ctx, const float* centre, const float* const
         nb.flow_v[n] = flows_v[n];
         nb.occlusion[n] = occlusions ? occlusions[n] : nullptr;
     }
-    dim3 grid(flow2d::div_up(width, kBlockX), flow2d::div_up(flow2d::div_up(height, denoise_rows(N)), kBlockY),
-              flow2d::batch_z(ctx, 1));
-    const BatchArg batch = flow2d::batch_arg(ctx, 1);
-    // 32-bit per-lane offsets when the largest one a lane forms -- (height - 1) * pitch + width + 1 floats, in bytes -- fits
-    if (height * pitch_bytes < (size_t(1) << 32))
-        denoise_kernel<N, unsigned><<<grid, dim3(kBlockX, kBlockY), 0, ctx->stream>>>(
-            centre, nb, (int)width, (int)height, (int)(pitch_bytes / 4), range_sigma, output, weight_sum, batch);
-    else
-        denoise_kernel<N, size_t><<<grid, dim3(kBlockX, kBlockY), 0, ctx->stream>>>(
-            centre, nb, (int)width, (int)height, (int)(pitch_bytes / 4), range_sigma, output, weight_sum, batch);
+    flow2d::launch_by_span(height * pitch_bytes, [&](auto offset) {
+        denoise_kernel<N, decltype(offset)><<<flow2d::pixel_grid(ctx, width, height, denoise_rows(N)), flow2d::pixel_block(), 0,
+                                              ctx->stream>>>(centre, nb, (int)width, (int)height, (int)(pitch_bytes / 4), range_sigma,
+                                                             output, weight_sum, flow2d::batch_arg(ctx, 1));
+    });
 }
 
 }  // namespace
@@ -311,20 +243,15 @@ int flow2d_denoise_2d(flow2d_context* ctx, const float* centre, size_t neighbour
         (weight_sum && !flow2d::plane_args_ok(weight_sum, width, height, pitch_bytes)))
         return FLOW2D_ERR_INVALID_ARGUMENT;
     // the written byte ranges must not meet any read one (not only its base), nor each other
-    float* const written[2] = {output, weight_sum};
     auto aliased = [&](size_t span) {
-        for (float* o : written) {
-            if (!o) continue;
-            for (size_t k = 0; k < input_count; ++k)
-                if (ranges_overlap(o, inputs[k], span)) return true;
-        }
-        return weight_sum && ranges_overlap(output, weight_sum, span);
+        const flow2d::ByteRange written[] = {{output, span}, {weight_sum, span}};
+        flow2d::ByteRange read[1 + 4 * kMaxNeighbours];
+        for (size_t k = 0; k < input_count; ++k) read[k] = {inputs[k], span};
+        return flow2d::any_overlap(written, 2, read, input_count);
     };
     if (aliased(height * pitch_bytes)) return FLOW2D_ERR_INVALID_ARGUMENT;
     FLOW2D_ENTER(ctx);
-    // a lock-step batch: instance b of every plane at + b * stride, so each plane spans all instances
-    if (aliased(height * pitch_bytes + (ctx->batch_count - 1) * ctx->batch_stride_floats * sizeof(float)))
-        return FLOW2D_ERR_INVALID_ARGUMENT;
+    if (aliased(flow2d::batch_span(ctx, height * pitch_bytes))) return FLOW2D_ERR_INVALID_ARGUMENT;
 #define FLOW2D_DENOISE_CASE(N)                                                                                              \
     case N:                                                                                                                 \
         launch_denoise<N>(ctx, centre, frames, flows_u, flows_v, occlusions, width, height, pitch_bytes, range_sigma, output, \
@@ -361,29 +288,19 @@ int flow2d_compose_flow_2d(flow2d_context* ctx, const float* ab_u, const float* 
             return FLOW2D_ERR_INVALID_ARGUMENT;
     // the written byte ranges must not meet any read one (not only its base), nor each other
     auto aliased = [&](size_t span) {
-        for (int i = 0; i < 3; ++i) {
-            if (!written[i]) continue;
-            for (const float* p : inputs)
-                if (p && ranges_overlap(written[i], p, span)) return true;
-            for (int j = i + 1; j < 3; ++j)
-                if (written[j] && ranges_overlap(written[i], written[j], span)) return true;
-        }
-        return false;
+        flow2d::ByteRange out[3], in[6];
+        for (int i = 0; i < 3; ++i) out[i] = {written[i], span};
+        for (int i = 0; i < 6; ++i) in[i] = {inputs[i], span};
+        return flow2d::any_overlap(out, in);
     };
     if (aliased(height * pitch_bytes)) return FLOW2D_ERR_INVALID_ARGUMENT;
     FLOW2D_ENTER(ctx);
-    // a lock-step batch: instance b of every plane at + b * stride, so each plane spans all instances
-    if (aliased(height * pitch_bytes + (ctx->batch_count - 1) * ctx->batch_stride_floats * sizeof(float)))
-        return FLOW2D_ERR_INVALID_ARGUMENT;
-    dim3 grid(flow2d::div_up(width, kBlockX), flow2d::div_up(flow2d::div_up(height, kComposeRows), kBlockY), flow2d::batch_z(ctx, 1));
-    const BatchArg batch = flow2d::batch_arg(ctx, 1);
-    // 32-bit per-lane offsets when the largest one a lane forms -- (height - 1) * pitch + width + 1 floats, in bytes -- fits
-    if (height * pitch_bytes < (size_t(1) << 32))
-        compose_kernel<unsigned><<<grid, dim3(kBlockX, kBlockY), 0, ctx->stream>>>(
-            ab_u, ab_v, bc_u, bc_v, mask_ab, mask_bc, (int)width, (int)height, (int)(pitch_bytes / 4), out_u, out_v, out_mask, batch);
-    else
-        compose_kernel<size_t><<<grid, dim3(kBlockX, kBlockY), 0, ctx->stream>>>(
-            ab_u, ab_v, bc_u, bc_v, mask_ab, mask_bc, (int)width, (int)height, (int)(pitch_bytes / 4), out_u, out_v, out_mask, batch);
+    if (aliased(flow2d::batch_span(ctx, height * pitch_bytes))) return FLOW2D_ERR_INVALID_ARGUMENT;
+    flow2d::launch_by_span(height * pitch_bytes, [&](auto offset) {
+        compose_kernel<decltype(offset)><<<flow2d::pixel_grid(ctx, width, height, kComposeRows), flow2d::pixel_block(), 0, ctx->stream>>>(
+            ab_u, ab_v, bc_u, bc_v, mask_ab, mask_bc, (int)width, (int)height, (int)(pitch_bytes / 4), out_u, out_v, out_mask,
+            flow2d::batch_arg(ctx, 1));
+    });
     FLOW2D_CHECK_LAUNCH();
     return FLOW2D_OK;
 }

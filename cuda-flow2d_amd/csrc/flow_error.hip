@@ -6,13 +6,15 @@
 //
 // Memory-bound: 16 bytes of flow and ground truth per pixel (20 with an occlusion plane), read as dwordx4 per lane -- a wave
 // covers 256 columns of one row --, and 4 bytes per per-pixel plane written.  Two launches, no atomics: every workgroup
-// reduces its 256 x 32 pixels in a fixed order (rows, then the four columns of a lane, then a lane butterfly, then the four
-// waves) into a slab of the workspace, and one workgroup per instance sums the slabs in block order.  The grid, and with it
-// the order of every double addition, depends only on (width, height): repeated calls and batch instances give the same bytes.
+// reduces its 256 x 32 pixels in a fixed order (rows, then the four columns of a lane, then the reduction of
+// ordered_reduce.hpp) into a slab of the workspace, and one workgroup per instance sums the slabs in block order.  The grid,
+// and with it the order of every double addition, depends only on (width, height): repeated calls and batch instances give
+// the same bytes.
 #include <cfloat>
 #include <cmath>
 
-#include "common.hpp"
+#include "ordered_reduce.hpp"
+#include "plane_sample.hpp"
 
 namespace {
 
@@ -24,13 +26,41 @@ constexpr int kBlockRows = kWavesY * kRowsPerThread;    // 32
 constexpr int kFinalThreads = 256;
 constexpr float kDegrees = 57.29577951308232f;
 
-// Per-workgroup slab: classes noc (0) and occ (1); all = noc + occ is formed by the final kernel.
-struct FlowErrorPartial {
-    double sum[2][3];        // epe, epe^2, ae
+// Sums over pixels, classes noc (0) and occ (1); all = noc + occ is formed by the final kernel.  Count: unsigned in a
+// per-workgroup slab (FlowErrorPartial), 64 bits in the final kernel.
+template <typename Count>
+struct FlowErrorSums {
+    double sum[2][3];     // epe, epe^2, ae
     float max_epe[2];
-    unsigned count[2][6];    // count, above 0.5 / 1 / 2 / 3, fl
-    unsigned invalid, nonfinite;
+    Count count[2][6];    // count, above 0.5 / 1 / 2 / 3, fl
+    Count invalid, nonfinite;
+
+    template <typename Other>
+    __device__ __forceinline__ void combine(const Other& q)
+    {
+        for (int k = 0; k < 2; ++k) {
+            for (int j = 0; j < 3; ++j) sum[k][j] += q.sum[k][j];
+            max_epe[k] = fmaxf(max_epe[k], q.max_epe[k]);
+            for (int j = 0; j < 6; ++j) count[k][j] += q.count[k][j];
+        }
+        invalid += q.invalid;
+        nonfinite += q.nonfinite;
+    }
+    __device__ __forceinline__ void across_lanes()
+    {
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+#pragma unroll
+            for (int j = 0; j < 3; ++j) sum[k][j] = wave_sum(sum[k][j]);
+            max_epe[k] = wave_max(max_epe[k]);
+#pragma unroll
+            for (int j = 0; j < 6; ++j) count[k][j] = wave_sum(count[k][j]);
+        }
+        invalid = wave_sum(invalid);
+        nonfinite = wave_sum(nonfinite);
+    }
 };
+using FlowErrorPartial = FlowErrorSums<unsigned>;
 static_assert(sizeof(FlowErrorPartial) % 16 == 0, "slabs stay 16-byte aligned");
 
 struct ClassAcc {
@@ -85,21 +115,6 @@ __device__ __forceinline__ void error_pixel(float u, float v, float gu, float gv
     acc.occ.add_if(occluded, epe, ae, gmag);
     epe_out = epe;
     ae_out = ae;
-}
-
-template <typename T>
-__device__ __forceinline__ T wave_sum(T x)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-    return x;
-}
-
-__device__ __forceinline__ float wave_max(float x)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x = fmaxf(x, __shfl_xor(x, o, 64));
-    return x;
 }
 
 // Offset: unsigned (a plane's whole extent fits 32 bits) or size_t; HasMask: an occlusion plane is read.
@@ -157,90 +172,32 @@ __global__ __launch_bounds__(256) void flow_error_partials_kernel(const float* _
             }
         }
     }
-    // lane butterfly (every lane ends with the same bits: IEEE addition commutes), then the four waves in order
-    __shared__ FlowErrorPartial waves[kWavesY];
-    const int lane = threadIdx.x;
     FlowErrorPartial mine;
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
         const ClassAcc& c = k ? acc.occ : acc.noc;
-        mine.sum[k][0] = wave_sum(c.s_epe);
-        mine.sum[k][1] = wave_sum(c.s_epe_sq);
-        mine.sum[k][2] = wave_sum(c.s_ae);
-        mine.max_epe[k] = wave_max(c.max_epe);
-        mine.count[k][0] = wave_sum(c.n);
-        mine.count[k][1] = wave_sum(c.a05);
-        mine.count[k][2] = wave_sum(c.a1);
-        mine.count[k][3] = wave_sum(c.a2);
-        mine.count[k][4] = wave_sum(c.a3);
-        mine.count[k][5] = wave_sum(c.fl);
+        mine.sum[k][0] = c.s_epe;
+        mine.sum[k][1] = c.s_epe_sq;
+        mine.sum[k][2] = c.s_ae;
+        mine.max_epe[k] = c.max_epe;
+        const unsigned counts[6] = {c.n, c.a05, c.a1, c.a2, c.a3, c.fl};
+#pragma unroll
+        for (int j = 0; j < 6; ++j) mine.count[k][j] = counts[j];
     }
-    mine.invalid = wave_sum(acc.invalid);
-    mine.nonfinite = wave_sum(acc.nonfinite);
-    if (lane == 0) waves[threadIdx.y] = mine;
-    __syncthreads();
-    if (threadIdx.y == 0 && lane == 0) {
-        FlowErrorPartial out = waves[0];
-        for (int wv = 1; wv < kWavesY; ++wv) {
-            const FlowErrorPartial& q = waves[wv];
-            for (int k = 0; k < 2; ++k) {
-                for (int j = 0; j < 3; ++j) out.sum[k][j] += q.sum[k][j];
-                out.max_epe[k] = fmaxf(out.max_epe[k], q.max_epe[k]);
-                for (int j = 0; j < 6; ++j) out.count[k][j] += q.count[k][j];
-            }
-            out.invalid += q.invalid;
-            out.nonfinite += q.nonfinite;
-        }
-        partials[static_cast<size_t>(blockIdx.z) * gridDim.x * gridDim.y + blockIdx.y * gridDim.x + blockIdx.x] = out;
-    }
+    mine.invalid = acc.invalid;
+    mine.nonfinite = acc.nonfinite;
+    if (workgroup_reduce<kWavesY>(mine, threadIdx.x, threadIdx.y))
+        partials[static_cast<size_t>(blockIdx.z) * gridDim.x * gridDim.y + blockIdx.y * gridDim.x + blockIdx.x] = mine;
 }
 
-struct FinalAcc {
-    double sum[2][3];
-    float max_epe[2];
-    unsigned long long count[2][6];
-    unsigned long long invalid, nonfinite;
-};
-
-// One workgroup per instance: thread t sums slabs t, t + 256, ... in order, then a lane butterfly and the four waves in order.
+// One workgroup per instance: thread t sums slabs t, t + 256, ... in order, then the reduction of ordered_reduce.hpp.
 __global__ __launch_bounds__(kFinalThreads) void flow_error_final_kernel(const FlowErrorPartial* __restrict__ partials,
                                                                          unsigned blocks, flow2d_flow_error_stats* __restrict__ stats)
 {
     const FlowErrorPartial* slab = partials + static_cast<size_t>(blockIdx.x) * blocks;
-    FinalAcc a = {};
-    for (unsigned j = threadIdx.x; j < blocks; j += kFinalThreads) {
-        const FlowErrorPartial& q = slab[j];
-        for (int k = 0; k < 2; ++k) {
-            for (int i = 0; i < 3; ++i) a.sum[k][i] += q.sum[k][i];
-            a.max_epe[k] = fmaxf(a.max_epe[k], q.max_epe[k]);
-            for (int i = 0; i < 6; ++i) a.count[k][i] += q.count[k][i];
-        }
-        a.invalid += q.invalid;
-        a.nonfinite += q.nonfinite;
-    }
-    for (int k = 0; k < 2; ++k) {
-        for (int i = 0; i < 3; ++i) a.sum[k][i] = wave_sum(a.sum[k][i]);
-        a.max_epe[k] = wave_max(a.max_epe[k]);
-        for (int i = 0; i < 6; ++i) a.count[k][i] = wave_sum(a.count[k][i]);
-    }
-    a.invalid = wave_sum(a.invalid);
-    a.nonfinite = wave_sum(a.nonfinite);
-    __shared__ FinalAcc waves[kFinalThreads / 64];
-    const int wave = threadIdx.x / 64;
-    if (threadIdx.x % 64 == 0) waves[wave] = a;
-    __syncthreads();
-    if (threadIdx.x != 0) return;
-    FinalAcc t = waves[0];
-    for (int wv = 1; wv < kFinalThreads / 64; ++wv) {
-        const FinalAcc& q = waves[wv];
-        for (int k = 0; k < 2; ++k) {
-            for (int i = 0; i < 3; ++i) t.sum[k][i] += q.sum[k][i];
-            t.max_epe[k] = fmaxf(t.max_epe[k], q.max_epe[k]);
-            for (int i = 0; i < 6; ++i) t.count[k][i] += q.count[k][i];
-        }
-        t.invalid += q.invalid;
-        t.nonfinite += q.nonfinite;
-    }
+    FlowErrorSums<unsigned long long> t = {};
+    for (unsigned j = threadIdx.x; j < blocks; j += kFinalThreads) t.combine(slab[j]);
+    if (!workgroup_reduce<kFinalThreads / 64>(t, threadIdx.x % 64, threadIdx.x / 64)) return;
     flow2d_flow_error_stats rec;
     flow2d_flow_error_class* cls[2] = {&rec.noc, &rec.occ};
     for (int k = 0; k < 2; ++k) {
@@ -265,34 +222,9 @@ __global__ __launch_bounds__(kFinalThreads) void flow_error_final_kernel(const F
     stats[blockIdx.x] = rec;
 }
 
-inline bool ranges_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes)
-{
-    const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
-    return pa < pb + b_bytes && pb < pa + a_bytes;
-}
-
 inline size_t partial_blocks(size_t width, size_t height)
 {
     return static_cast<size_t>(flow2d::div_up(width, kBlockCols)) * flow2d::div_up(height, kBlockRows);
-}
-
-// The written ranges (epe, ae: `plane` bytes each; stats, workspace) against every read plane and each other.
-bool outputs_overlap(const float* const* inputs, int n_inputs, const float* epe, const float* ae, size_t plane,
-                     const void* stats, size_t stats_bytes, const void* workspace, size_t workspace_bytes)
-{
-    const float* outs[2] = {epe, ae};
-    for (const float* o : outs) {
-        if (!o) continue;
-        for (int i = 0; i < n_inputs; ++i)
-            if (inputs[i] && ranges_overlap(o, plane, inputs[i], plane)) return true;
-        if (ranges_overlap(o, plane, stats, stats_bytes) || ranges_overlap(o, plane, workspace, workspace_bytes)) return true;
-    }
-    if (epe && ae && ranges_overlap(epe, plane, ae, plane)) return true;
-    for (int i = 0; i < n_inputs; ++i)
-        if (inputs[i] && (ranges_overlap(stats, stats_bytes, inputs[i], plane) ||
-                          ranges_overlap(workspace, workspace_bytes, inputs[i], plane)))
-            return true;
-    return ranges_overlap(stats, stats_bytes, workspace, workspace_bytes);
 }
 
 }  // namespace
@@ -321,39 +253,33 @@ int flow2d_flow_error_2d(flow2d_context* ctx, const float* flow_u, const float* 
         workspace_bytes < flow2d_flow_error_workspace_bytes(width, height, 1))
         return FLOW2D_ERR_INVALID_ARGUMENT;
     // the kernels mark every plane __restrict__: no written byte range may meet a read one or another written one
-    if (outputs_overlap(inputs, 5, epe, ae, height * pitch_bytes, stats, sizeof(flow2d_flow_error_stats), workspace,
-                        workspace_bytes))
-        return FLOW2D_ERR_INVALID_ARGUMENT;
+    auto aliased = [&](size_t span, size_t instances) {
+        const flow2d::ByteRange written[] = {{epe, span}, {ae, span}, {stats, instances * sizeof(flow2d_flow_error_stats)},
+                                             {workspace, workspace_bytes}};
+        flow2d::ByteRange read[5];
+        for (int i = 0; i < 5; ++i) read[i] = {inputs[i], span};
+        return flow2d::any_overlap(written, read);
+    };
+    if (aliased(height * pitch_bytes, 1)) return FLOW2D_ERR_INVALID_ARGUMENT;
     FLOW2D_ENTER(ctx);
     const size_t instances = ctx->batch_count;
     if (workspace_bytes < flow2d_flow_error_workspace_bytes(width, height, instances)) return FLOW2D_ERR_INVALID_ARGUMENT;
-    // a lock-step batch: instance b of every plane at + b * stride, so each plane spans all instances
-    const size_t span = height * pitch_bytes + (instances - 1) * ctx->batch_stride_floats * sizeof(float);
-    if (outputs_overlap(inputs, 5, epe, ae, span, stats, instances * sizeof(flow2d_flow_error_stats), workspace,
-                        workspace_bytes))
-        return FLOW2D_ERR_INVALID_ARGUMENT;
+    if (aliased(flow2d::batch_span(ctx, height * pitch_bytes), instances)) return FLOW2D_ERR_INVALID_ARGUMENT;
     const dim3 grid(flow2d::div_up(width, kBlockCols), flow2d::div_up(height, kBlockRows), flow2d::batch_z(ctx, 1));
     const BatchArg batch = flow2d::batch_arg(ctx, 1);
     FlowErrorPartial* partials = static_cast<FlowErrorPartial*>(workspace);
     const int w = static_cast<int>(width), h = static_cast<int>(height), pitch = static_cast<int>(pitch_bytes / 4);
-    // 32-bit per-lane offsets when the largest one a lane forms -- below height * pitch floats -- fits (bytes: a margin)
-    const bool small = height * pitch_bytes < (size_t(1) << 32);
-    const dim3 block(kLanesX, kWavesY);
-    if (occlusion) {
-        if (small)
-            flow_error_partials_kernel<unsigned, true><<<grid, block, 0, ctx->stream>>>(flow_u, flow_v, gt_u, gt_v, occlusion, w, h,
-                                                                                       pitch, epe, ae, partials, batch);
-        else
-            flow_error_partials_kernel<size_t, true><<<grid, block, 0, ctx->stream>>>(flow_u, flow_v, gt_u, gt_v, occlusion, w, h,
+    // (the largest offset a lane forms is below height * pitch floats: taking the bytes leaves a margin)
+    flow2d::launch_by_span(height * pitch_bytes, [&](auto offset) {
+        using Offset = decltype(offset);
+        const dim3 block(kLanesX, kWavesY);
+        if (occlusion)
+            flow_error_partials_kernel<Offset, true><<<grid, block, 0, ctx->stream>>>(flow_u, flow_v, gt_u, gt_v, occlusion, w, h,
                                                                                      pitch, epe, ae, partials, batch);
-    } else {
-        if (small)
-            flow_error_partials_kernel<unsigned, false><<<grid, block, 0, ctx->stream>>>(flow_u, flow_v, gt_u, gt_v, nullptr, w, h,
-                                                                                        pitch, epe, ae, partials, batch);
         else
-            flow_error_partials_kernel<size_t, false><<<grid, block, 0, ctx->stream>>>(flow_u, flow_v, gt_u, gt_v, nullptr, w, h,
+            flow_error_partials_kernel<Offset, false><<<grid, block, 0, ctx->stream>>>(flow_u, flow_v, gt_u, gt_v, nullptr, w, h,
                                                                                       pitch, epe, ae, partials, batch);
-    }
+    });
     FLOW2D_CHECK_LAUNCH();
     flow_error_final_kernel<<<dim3(static_cast<unsigned>(instances)), dim3(kFinalThreads), 0, ctx->stream>>>(
         partials, static_cast<unsigned>(partial_blocks(width, height)), stats);

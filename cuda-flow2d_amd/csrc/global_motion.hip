@@ -13,11 +13,13 @@
 // slab of the workspace, and one workgroup per instance sums the slabs in block order, solves and writes the record.  The next
 // pass reads that record from device memory (uniform loads: scalar registers).  The grid, and with it the order of every
 // addition, depends only on (width, height): repeated calls and batch instances give the same bytes.
-// The warp has the geometry of consistency.hip / denoise.hip: 64 x 4 threads, four rows per thread, one byte offset per lane
-// (32 bits when the plane's span allows) against scalar bases, column-pair dwordx2 gathers; it reads no flow plane.
+// The per-pixel kernels have the geometry and the sampler of plane_sample.hpp: 64 x 4 threads, four rows per thread, one byte
+// offset per lane (32 bits when the plane's span allows) against scalar bases, column-pair dwordx2 gathers; the warp reads no
+// flow plane.
 #include <cmath>
 
-#include "common.hpp"
+#include "ordered_reduce.hpp"
+#include "plane_sample.hpp"
 
 namespace {
 
@@ -28,7 +30,7 @@ constexpr int kBlockCols = kLanesX * 4;                 // 256
 constexpr int kBlockRows = kWavesY * kRowsPerThread;    // 32
 constexpr int kFinalThreads = 256;
 constexpr int kSums = 12;  // S0 Sx Sy Sxx Sxy Syy Su Sxu Syu Sv Sxv Syv
-constexpr int kBlockX = 64, kBlockY = 4, kPlaneRows = 4;  // the per-pixel kernels
+constexpr int kPlaneRows = 4;  // rows per thread of the per-pixel kernels
 constexpr unsigned kQuietNaN = 0x7fc00000u;
 
 struct MotionPartial {
@@ -94,14 +96,6 @@ __device__ __forceinline__ void fit_pixel(float uf, float vf, float mf, double x
     a.s[11] += wy * v;
 }
 
-template <typename T>
-__device__ __forceinline__ T wave_sum(T x)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-    return x;
-}
-
 // Offset: unsigned (a plane's whole extent fits 32 bits) or size_t; HasMask: a mask plane is read; Weighted: see fit_pixel.
 template <typename Offset, bool HasMask, bool Weighted>
 __global__ __launch_bounds__(256) void motion_partials_kernel(const float* __restrict__ u, const float* __restrict__ v,
@@ -139,7 +133,8 @@ __global__ __launch_bounds__(256) void motion_partials_kernel(const float* __res
             if (n > 3) fit_pixel<Weighted>(fu.w, fv.w, m.w, xc + 3.0, yc, model, s2, acc);
         }
     }
-    // lane butterfly (every lane ends with the same bits: IEEE addition commutes), then the four waves in order
+    // lane butterfly (every lane ends with the same bits: IEEE addition commutes), then the four waves in order.  The steps of
+    // workgroup_reduce (ordered_reduce.hpp), kept spelled out here and in motion_final_kernel: see that header.
     __shared__ MotionPartial waves[kWavesY];
     MotionPartial mine;
 #pragma unroll
@@ -232,18 +227,6 @@ __global__ __launch_bounds__(kFinalThreads) void motion_final_kernel(const Motio
     motion[blockIdx.x] = rec;
 }
 
-template <typename Offset>
-__device__ __forceinline__ float load_at(const float* base, Offset byte_offset)
-{
-    return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + byte_offset);
-}
-
-template <typename Offset>
-__device__ __forceinline__ void store_at(float* base, Offset byte_offset, float value)
-{
-    *reinterpret_cast<float*>(reinterpret_cast<char*>(base) + byte_offset) = value;
-}
-
 __device__ __forceinline__ float canonical_nan(float r)
 {
     const unsigned bits = __float_as_uint(r);
@@ -261,15 +244,15 @@ __global__ __launch_bounds__(256) void global_flow_kernel(const flow2d_global_mo
 {
     const size_t inst = batch_offset(batch);
     const Model model = load_model(motion + blockIdx.z);
-    const int gx = blockIdx.x * kBlockX + threadIdx.x;
+    const int gx = pixel_column();
     if (gx >= w) return;
     const double xc = static_cast<double>(gx) - static_cast<double>(w - 1) * 0.5;
     const double cy = static_cast<double>(h - 1) * 0.5;
 #pragma unroll
     for (int i = 0; i < kPlaneRows; ++i) {
-        const int gy = (blockIdx.y * kPlaneRows + i) * kBlockY + threadIdx.y;
+        const int gy = pixel_row(kPlaneRows, i);
         if (gy >= h) return;
-        const Offset at = (static_cast<Offset>(gy) * static_cast<Offset>(pitch) + static_cast<Offset>(gx)) * sizeof(float);
+        const Offset at = pixel_offset<Offset>(gx, gy, pitch);
         const double yc = static_cast<double>(gy) - cy;
         const double mu = model_u(model, xc, yc), mv = model_v(model, xc, yc);
         if (out_mu) {
@@ -296,13 +279,6 @@ __global__ __launch_bounds__(256) void global_flow_kernel(const flow2d_global_mo
     }
 }
 
-template <typename Offset>
-__device__ __forceinline__ float2 column_pair(const float* base, Offset byte_offset)
-{
-    const float* p = reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + byte_offset);
-    return make_float2(p[0], p[1]);
-}
-
 // One frame resampled along the model: the sample of consistency_kernel at q = x + model(x).
 template <typename Offset>
 __global__ __launch_bounds__(256) void warp_global_kernel(const flow2d_global_motion* __restrict__ motion,
@@ -314,7 +290,7 @@ __global__ __launch_bounds__(256) void warp_global_kernel(const flow2d_global_mo
     output += inst;
     if (valid) valid += inst;
     const Model model = load_model(motion + blockIdx.z);
-    const int gx = blockIdx.x * kBlockX + threadIdx.x;
+    const int gx = pixel_column();
     if (gx >= w) return;
     const double xd = static_cast<double>(gx), xc = xd - static_cast<double>(w - 1) * 0.5;
     const double cy = static_cast<double>(h - 1) * 0.5;
@@ -322,13 +298,13 @@ __global__ __launch_bounds__(256) void warp_global_kernel(const flow2d_global_mo
 
     // every position and gather first (rows past the frame run on the last row and write nothing), then the blends
     Offset at[kPlaneRows];
-    float dx[kPlaneRows], dy[kPlaneRows];
+    Tap<Offset> tap[kPlaneRows];
     float2 ga[kPlaneRows], gb[kPlaneRows];
-    bool ok[kPlaneRows], x_second[kPlaneRows], x1_second[kPlaneRows];
+    bool ok[kPlaneRows];
 #pragma unroll
     for (int i = 0; i < kPlaneRows; ++i) {
-        const int gy = min((blockIdx.y * kPlaneRows + i) * kBlockY + threadIdx.y, h - 1);
-        at[i] = (static_cast<Offset>(gy) * static_cast<Offset>(pitch) + static_cast<Offset>(gx)) * sizeof(float);
+        const int gy = min(pixel_row(kPlaneRows, i), h - 1);
+        at[i] = pixel_offset<Offset>(gx, gy, pitch);
         const double yd = static_cast<double>(gy), yc = yd - cy;
         float qx = static_cast<float>(xd + model_u(model, xc, yc));
         float qy = static_cast<float>(yd + model_v(model, xc, yc));
@@ -337,61 +313,23 @@ __global__ __launch_bounds__(256) void warp_global_kernel(const flow2d_global_mo
             qx = static_cast<float>(gx);
             qy = static_cast<float>(gy);
         }
-        const int x = static_cast<int>(floorf(qx));
-        const int y = static_cast<int>(floorf(qy));
-        const int x1 = min(w - 1, x + 1);
-        const int y1 = min(h - 1, y + 1);
-        // the column pair (xb, xb + 1), xb = min(x, w - 2), holds x and x1 (w = 1: the second column is row padding, never selected)
-        const int xb = max(min(x, w - 2), 0);
-        const Offset o0 = (static_cast<Offset>(y) * static_cast<Offset>(pitch) + static_cast<Offset>(xb)) * sizeof(float);
-        const Offset o1 = (static_cast<Offset>(y1) * static_cast<Offset>(pitch) + static_cast<Offset>(xb)) * sizeof(float);
-        dx[i] = qx - static_cast<float>(x);
-        dy[i] = qy - static_cast<float>(y);
-        x_second[i] = x != xb;
-        x1_second[i] = x1 != xb;
-        ga[i] = column_pair(frame, o0);
-        gb[i] = column_pair(frame, o1);
+        tap[i] = make_tap<Offset>(qx, qy, w, h, pitch);
+        ga[i] = column_pair(frame, tap[i].o0);
+        gb[i] = column_pair(frame, tap[i].o1);
     }
 #pragma unroll
     for (int i = 0; i < kPlaneRows; ++i) {
-        const int gy = (blockIdx.y * kPlaneRows + i) * kBlockY + threadIdx.y;
+        const int gy = pixel_row(kPlaneRows, i);
         if (gy >= h) return;
-        const float w00 = (1.f - dx[i]) * (1.f - dy[i]), w01 = (dx[i]) * (1.f - dy[i]), w10 = (1.f - dx[i]) * (dy[i]),
-                    w11 = (dx[i]) * (dy[i]);
-        const float s = w00 * (x_second[i] ? ga[i].y : ga[i].x) + w01 * (x1_second[i] ? ga[i].y : ga[i].x) +
-                        w10 * (x_second[i] ? gb[i].y : gb[i].x) + w11 * (x1_second[i] ? gb[i].y : gb[i].x);
+        const float s = blend(tap[i], ga[i], gb[i]);
         store_at(output, at[i], ok[i] ? s : fill);
         if (valid) store_at(valid, at[i], ok[i] ? 1.f : 0.f);
     }
 }
 
-inline bool ranges_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes)
-{
-    const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
-    return pa < pb + b_bytes && pb < pa + a_bytes;
-}
-
 inline size_t partial_blocks(size_t width, size_t height)
 {
     return static_cast<size_t>(flow2d::div_up(width, kBlockCols)) * flow2d::div_up(height, kBlockRows);
-}
-
-struct Range {
-    const void* p;
-    size_t bytes;
-};
-
-// Whether any written range meets a read one or another written one (null entries are skipped).
-bool any_overlap(const Range* written, int n_written, const Range* read, int n_read)
-{
-    for (int i = 0; i < n_written; ++i) {
-        if (!written[i].p) continue;
-        for (int j = 0; j < n_read; ++j)
-            if (read[j].p && ranges_overlap(written[i].p, written[i].bytes, read[j].p, read[j].bytes)) return true;
-        for (int j = i + 1; j < n_written; ++j)
-            if (written[j].p && ranges_overlap(written[i].p, written[i].bytes, written[j].p, written[j].bytes)) return true;
-    }
-    return false;
 }
 
 inline bool record_ok(const void* motion) { return motion && (reinterpret_cast<uintptr_t>(motion) % 8) == 0; }
@@ -445,32 +383,29 @@ int flow2d_global_motion_2d(flow2d_context* ctx, const float* flow_u, const floa
         workspace_bytes < flow2d_global_motion_workspace_bytes(width, height, 1))
         return FLOW2D_ERR_INVALID_ARGUMENT;
     auto aliased = [&](size_t span, size_t instances) {
-        const Range written[] = {{motion, instances * sizeof(flow2d_global_motion)}, {workspace, workspace_bytes}};
-        const Range read[] = {{flow_u, span}, {flow_v, span}, {mask, span}};
-        return any_overlap(written, 2, read, 3);
+        const flow2d::ByteRange written[] = {{motion, instances * sizeof(flow2d_global_motion)}, {workspace, workspace_bytes}};
+        const flow2d::ByteRange read[] = {{flow_u, span}, {flow_v, span}, {mask, span}};
+        return flow2d::any_overlap(written, read);
     };
     if (aliased(height * pitch_bytes, 1)) return FLOW2D_ERR_INVALID_ARGUMENT;
     FLOW2D_ENTER(ctx);
     const size_t instances = ctx->batch_count;
     if (workspace_bytes < flow2d_global_motion_workspace_bytes(width, height, instances)) return FLOW2D_ERR_INVALID_ARGUMENT;
-    // a lock-step batch: instance b of every plane at + b * stride, so each plane spans all instances
-    if (aliased(height * pitch_bytes + (instances - 1) * ctx->batch_stride_floats * sizeof(float), instances))
+    if (aliased(flow2d::batch_span(ctx, height * pitch_bytes), instances))
         return FLOW2D_ERR_INVALID_ARGUMENT;
     const dim3 grid(flow2d::div_up(width, kBlockCols), flow2d::div_up(height, kBlockRows), flow2d::batch_z(ctx, 1));
     const BatchArg batch = flow2d::batch_arg(ctx, 1);
     MotionPartial* partials = static_cast<MotionPartial*>(workspace);
     const int w = static_cast<int>(width), h = static_cast<int>(height), pitch = static_cast<int>(pitch_bytes / 4);
     const unsigned blocks = static_cast<unsigned>(partial_blocks(width, height));
-    // 32-bit per-lane offsets when the largest one a lane forms -- below height * pitch floats -- fits (bytes: a margin)
-    const bool small = height * pitch_bytes < (size_t(1) << 32);
     const double s2 = sigma * sigma;
     const int passes = 1 + (sigma > 0.0 ? iterations : 0);
     for (int pass = 0; pass < passes; ++pass) {
         const flow2d_global_motion* previous = pass > 0 ? motion : nullptr;
-        if (small)
-            launch_partials<unsigned>(ctx, grid, flow_u, flow_v, mask, w, h, pitch, previous, s2, partials, batch);
-        else
-            launch_partials<size_t>(ctx, grid, flow_u, flow_v, mask, w, h, pitch, previous, s2, partials, batch);
+        // (the largest offset a lane forms is below height * pitch floats: taking the bytes leaves a margin)
+        flow2d::launch_by_span(height * pitch_bytes, [&](auto offset) {
+            launch_partials<decltype(offset)>(ctx, grid, flow_u, flow_v, mask, w, h, pitch, previous, s2, partials, batch);
+        });
         FLOW2D_CHECK_LAUNCH();
         motion_final_kernel<<<dim3(static_cast<unsigned>(instances)), dim3(kFinalThreads), 0, ctx->stream>>>(partials, blocks,
                                                                                                              model, motion);
@@ -499,39 +434,31 @@ int flow2d_global_flow_2d(flow2d_context* ctx, const flow2d_global_motion* motio
     for (const float* p : written)
         if (p && !flow2d::plane_args_ok(p, width, height, pitch_bytes)) return FLOW2D_ERR_INVALID_ARGUMENT;
     auto aliased = [&](size_t span, size_t instances) {
-        Range out[5], in[4];
-        for (int i = 0; i < 5; ++i) out[i] = Range{written[i], span};
-        for (int i = 0; i < 3; ++i) in[i] = Range{inputs[i], span};
-        in[3] = Range{motion, instances * sizeof(flow2d_global_motion)};
-        return any_overlap(out, 5, in, 4);
+        flow2d::ByteRange out[5], in[4];
+        for (int i = 0; i < 5; ++i) out[i] = flow2d::ByteRange{written[i], span};
+        for (int i = 0; i < 3; ++i) in[i] = flow2d::ByteRange{inputs[i], span};
+        in[3] = flow2d::ByteRange{motion, instances * sizeof(flow2d_global_motion)};
+        return flow2d::any_overlap(out, in);
     };
     if (aliased(height * pitch_bytes, 1)) return FLOW2D_ERR_INVALID_ARGUMENT;
     FLOW2D_ENTER(ctx);
-    // a lock-step batch: instance b of every plane at + b * stride, so each plane spans all instances
-    if (aliased(height * pitch_bytes + (ctx->batch_count - 1) * ctx->batch_stride_floats * sizeof(float), ctx->batch_count))
+    if (aliased(flow2d::batch_span(ctx, height * pitch_bytes), ctx->batch_count))
         return FLOW2D_ERR_INVALID_ARGUMENT;
-    const dim3 grid(flow2d::div_up(width, kBlockX), flow2d::div_up(flow2d::div_up(height, kPlaneRows), kBlockY),
-                    flow2d::batch_z(ctx, 1));
-    const dim3 block(kBlockX, kBlockY);
+    const dim3 grid = flow2d::pixel_grid(ctx, width, height, kPlaneRows);
     const BatchArg batch = flow2d::batch_arg(ctx, 1);
     const int w = static_cast<int>(width), h = static_cast<int>(height), pitch = static_cast<int>(pitch_bytes / 4);
     const double s2 = sigma * sigma;
-    const bool small = height * pitch_bytes < (size_t(1) << 32);
-#define FLOW2D_GLOBAL_FLOW_LAUNCH(OFFSET, HAS_FLOW)                                                                         \
-    global_flow_kernel<OFFSET, HAS_FLOW><<<grid, block, 0, ctx->stream>>>(motion, flow_u, flow_v, mask, w, h, pitch, s2, model_u, \
-                                                                          model_v, residual_u, residual_v, weight, batch)
-    if (flow_u && (residual_u || weight)) {
-        if (small)
-            FLOW2D_GLOBAL_FLOW_LAUNCH(unsigned, true);
+    flow2d::launch_by_span(height * pitch_bytes, [&](auto offset) {
+        using Offset = decltype(offset);
+#define FLOW2D_GLOBAL_FLOW_LAUNCH(HAS_FLOW)                                                                                 \
+    global_flow_kernel<Offset, HAS_FLOW><<<grid, flow2d::pixel_block(), 0, ctx->stream>>>(                                  \
+        motion, flow_u, flow_v, mask, w, h, pitch, s2, model_u, model_v, residual_u, residual_v, weight, batch)
+        if (flow_u && (residual_u || weight))
+            FLOW2D_GLOBAL_FLOW_LAUNCH(true);
         else
-            FLOW2D_GLOBAL_FLOW_LAUNCH(size_t, true);
-    } else {
-        if (small)
-            FLOW2D_GLOBAL_FLOW_LAUNCH(unsigned, false);
-        else
-            FLOW2D_GLOBAL_FLOW_LAUNCH(size_t, false);
-    }
+            FLOW2D_GLOBAL_FLOW_LAUNCH(false);
 #undef FLOW2D_GLOBAL_FLOW_LAUNCH
+    });
     FLOW2D_CHECK_LAUNCH();
     return FLOW2D_OK;
 }
@@ -546,25 +473,19 @@ int flow2d_warp_global_2d(flow2d_context* ctx, const flow2d_global_motion* motio
         (valid && !flow2d::plane_args_ok(valid, width, height, pitch_bytes)))
         return FLOW2D_ERR_INVALID_ARGUMENT;
     auto aliased = [&](size_t span, size_t instances) {
-        const Range out[] = {{output, span}, {valid, span}};
-        const Range in[] = {{frame, span}, {motion, instances * sizeof(flow2d_global_motion)}};
-        return any_overlap(out, 2, in, 2);
+        const flow2d::ByteRange out[] = {{output, span}, {valid, span}};
+        const flow2d::ByteRange in[] = {{frame, span}, {motion, instances * sizeof(flow2d_global_motion)}};
+        return flow2d::any_overlap(out, in);
     };
     if (aliased(height * pitch_bytes, 1)) return FLOW2D_ERR_INVALID_ARGUMENT;
     FLOW2D_ENTER(ctx);
-    // a lock-step batch: instance b of every plane at + b * stride, so each plane spans all instances
-    if (aliased(height * pitch_bytes + (ctx->batch_count - 1) * ctx->batch_stride_floats * sizeof(float), ctx->batch_count))
+    if (aliased(flow2d::batch_span(ctx, height * pitch_bytes), ctx->batch_count))
         return FLOW2D_ERR_INVALID_ARGUMENT;
-    const dim3 grid(flow2d::div_up(width, kBlockX), flow2d::div_up(flow2d::div_up(height, kPlaneRows), kBlockY),
-                    flow2d::batch_z(ctx, 1));
-    const BatchArg batch = flow2d::batch_arg(ctx, 1);
-    // 32-bit per-lane offsets when the largest one a lane forms -- (height - 1) * pitch + width + 1 floats, in bytes -- fits
-    if (height * pitch_bytes < (size_t(1) << 32))
-        warp_global_kernel<unsigned><<<grid, dim3(kBlockX, kBlockY), 0, ctx->stream>>>(
-            motion, frame, (int)width, (int)height, (int)(pitch_bytes / 4), fill, output, valid, batch);
-    else
-        warp_global_kernel<size_t><<<grid, dim3(kBlockX, kBlockY), 0, ctx->stream>>>(
-            motion, frame, (int)width, (int)height, (int)(pitch_bytes / 4), fill, output, valid, batch);
+    flow2d::launch_by_span(height * pitch_bytes, [&](auto offset) {
+        warp_global_kernel<decltype(offset)><<<flow2d::pixel_grid(ctx, width, height, kPlaneRows), flow2d::pixel_block(), 0,
+                                               ctx->stream>>>(motion, frame, (int)width, (int)height, (int)(pitch_bytes / 4), fill,
+                                                              output, valid, flow2d::batch_arg(ctx, 1));
+    });
     FLOW2D_CHECK_LAUNCH();
     return FLOW2D_OK;
 }

@@ -6,39 +6,23 @@
 // flow2d_c_abi.h; the bilinear sample is the operation order of flow2d_consistency_2d (consistency.hip).  Built
 // -ffp-contract=off and with the correctly rounded fp32 division: the bits follow that definition exactly.
 //
-// Geometry of consistency.hip: 64 x 4 threads, four rows per thread.  Each side's fixed point is a chain of K + 1 dependent
+// Geometry and sampler of plane_sample.hpp: 64 x 4 threads, four rows per thread.  Each side's fixed point is a chain of K + 1 dependent
 // flow-pair gathers; the four rows and the two sides of a thread are eight independent chains, advanced step by step together
 // so that a wave keeps eight gathers in flight instead of one.  One 32-bit byte offset per lane and chain serves the dwordx2
 // column-pair gathers of both planes of a flow -- and, at the end, of the frame and the occlusion plane of that side -- against
 // scalar plane bases.
 #include <cmath>
 
-#include "common.hpp"
+#include "plane_sample.hpp"
 
 namespace {
 
-constexpr int kBlockX = 64;
-constexpr int kBlockY = 4;
-constexpr int kRows = 4;     // rows per thread: the geometry of consistency_kernel
+constexpr int kRows = 4;            // rows per thread
 constexpr int kChains = 2 * kRows;  // chain r + kRows * side
 
+// Where S(P, p) reads: p is replaced by the pixel itself when not finite, then clamped to the frame.
 template <typename Offset>
-__device__ __forceinline__ float2 column_pair(const float* __restrict__ base, Offset byte_offset)
-{
-    const float* p = reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + byte_offset);
-    return make_float2(p[0], p[1]);
-}
-
-// Where S(P, p) reads and with which weights: p is replaced by the pixel itself when not finite, then clamped to the frame.
-template <typename Offset>
-struct Tap {
-    Offset o0, o1;       // byte offsets of the column pairs (xb, xb + 1) in rows y and y1
-    float w00, w01, w10, w11;
-    bool x_second, x1_second;
-};
-
-template <typename Offset>
-__device__ __forceinline__ Tap<Offset> make_tap(float px, float py, float cx, float cy, int w, int h, int pitch)
+__device__ __forceinline__ Tap<Offset> clamped_tap(float px, float py, float cx, float cy, int w, int h, int pitch)
 {
     if (!(isfinite(px) && isfinite(py))) {
         px = cx;
@@ -47,31 +31,7 @@ __device__ __forceinline__ Tap<Offset> make_tap(float px, float py, float cx, fl
     const float x_max = static_cast<float>(w - 1), y_max = static_cast<float>(h - 1);
     px = px < 0.f ? 0.f : (px > x_max ? x_max : px);
     py = py < 0.f ? 0.f : (py > y_max ? y_max : py);
-    const int x = static_cast<int>(floorf(px));
-    const int y = static_cast<int>(floorf(py));
-    const float dx = px - static_cast<float>(x);
-    const float dy = py - static_cast<float>(y);
-    const int x1 = min(w - 1, x + 1);
-    const int y1 = min(h - 1, y + 1);
-    // the column pair (xb, xb + 1), xb = min(x, w - 2), holds x and x1 (w = 1: the second column is row padding, never selected)
-    const int xb = max(min(x, w - 2), 0);
-    Tap<Offset> t;
-    t.o0 = (static_cast<Offset>(y) * static_cast<Offset>(pitch) + static_cast<Offset>(xb)) * sizeof(float);
-    t.o1 = (static_cast<Offset>(y1) * static_cast<Offset>(pitch) + static_cast<Offset>(xb)) * sizeof(float);
-    t.w00 = (1.f - dx) * (1.f - dy);
-    t.w01 = (dx) * (1.f - dy);
-    t.w10 = (1.f - dx) * (dy);
-    t.w11 = (dx) * (dy);
-    t.x_second = x != xb;
-    t.x1_second = x1 != xb;
-    return t;
-}
-
-template <typename Offset>
-__device__ __forceinline__ float blend(const Tap<Offset>& t, float2 a, float2 b)
-{
-    return t.w00 * (t.x_second ? a.y : a.x) + t.w01 * (t.x1_second ? a.y : a.x) + t.w10 * (t.x_second ? b.y : b.x) +
-           t.w11 * (t.x1_second ? b.y : b.x);
+    return make_tap<Offset>(px, py, w, h, pitch);
 }
 
 template <typename Offset>
@@ -92,13 +52,13 @@ __global__ __launch_bounds__(256) void interpolate_kernel(const float* __restric
     if (occ_0) occ_0 += inst;
     if (occ_1) occ_1 += inst;
     output += inst;
-    const int gx = blockIdx.x * kBlockX + threadIdx.x;
+    const int gx = pixel_column();
     if (gx >= w) return;
     const float cx = static_cast<float>(gx);
     float cy[kRows];
 #pragma unroll
     for (int i = 0; i < kRows; ++i)  // rows past the frame run on the last row and write nothing
-        cy[i] = static_cast<float>(min((blockIdx.y * kRows + i) * kBlockY + threadIdx.y, h - 1));
+        cy[i] = static_cast<float>(min(pixel_row(kRows, i), h - 1));
 
     // chain c: row c % kRows, side c / kRows (0: the forward flow and factor t, 1: the backward flow and factor s)
     float px[kChains], py[kChains], su[kChains], sv[kChains];
@@ -113,7 +73,7 @@ __global__ __launch_bounds__(256) void interpolate_kernel(const float* __restric
         float2 ga[kChains][2], gb[kChains][2];
 #pragma unroll
         for (int c = 0; c < kChains; ++c) {
-            tap[c] = make_tap<Offset>(px[c], py[c], cx, cy[c % kRows], w, h, pitch);
+            tap[c] = clamped_tap<Offset>(px[c], py[c], cx, cy[c % kRows], w, h, pitch);
             const float* pu = c < kRows ? flow_u : back_u;
             const float* pv = c < kRows ? flow_v : back_v;
             ga[c][0] = column_pair(pu, tap[c].o0);
@@ -159,7 +119,7 @@ __global__ __launch_bounds__(256) void interpolate_kernel(const float* __restric
     }
 #pragma unroll
     for (int i = 0; i < kRows; ++i) {
-        const int gy = (blockIdx.y * kRows + i) * kBlockY + threadIdx.y;
+        const int gy = pixel_row(kRows, i);
         if (gy >= h) return;
         const float ok0 = ok[i] ? 1.f : 0.f, ok1 = ok[i + kRows] ? 1.f : 0.f;
         const float a0 = a[i], a1 = a[i + kRows];
@@ -175,12 +135,6 @@ __global__ __launch_bounds__(256) void interpolate_kernel(const float* __restric
         const float out = (w0 + w1 > 0.f) ? (w0 * a0 + w1 * a1) / (w0 + w1) : s * a0 + t * a1;
         output[static_cast<Offset>(gy) * static_cast<Offset>(pitch) + static_cast<Offset>(gx)] = out;
     }
-}
-
-inline bool ranges_overlap(const void* a, const void* b, size_t bytes)
-{
-    const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
-    return pa < pb + bytes && pb < pa + bytes;
 }
 
 }  // namespace
@@ -201,27 +155,23 @@ int flow2d_interpolate_2d(flow2d_context* ctx, const float* frame_0, const float
     if (!flow2d::plane_args_ok(output, width, height, pitch_bytes) || !std::isfinite(t) || t < 0.f || t > 1.f ||
         iterations < 1 || iterations > 16 || !std::isfinite(max_residual) || max_residual < 0.f)
         return FLOW2D_ERR_INVALID_ARGUMENT;
-    // the kernel marks every plane __restrict__: the written byte range must not meet any read one (not only its base)
-    for (const float* p : inputs)
-        if (p && ranges_overlap(output, p, height * pitch_bytes)) return FLOW2D_ERR_INVALID_ARGUMENT;
+    // the kernel marks every plane __restrict__: the written byte range must not meet any read one
+    auto aliased = [&](size_t span) {
+        const flow2d::ByteRange written[] = {{output, span}};
+        flow2d::ByteRange read[8];
+        for (int i = 0; i < 8; ++i) read[i] = {inputs[i], span};
+        return flow2d::any_overlap(written, read);
+    };
+    if (aliased(height * pitch_bytes)) return FLOW2D_ERR_INVALID_ARGUMENT;
     FLOW2D_ENTER(ctx);
-    // a lock-step batch: instance b of every plane at + b * stride, so each plane spans all instances
-    const size_t span = height * pitch_bytes + (ctx->batch_count - 1) * ctx->batch_stride_floats * sizeof(float);
-    for (const float* p : inputs)
-        if (p && ranges_overlap(output, p, span)) return FLOW2D_ERR_INVALID_ARGUMENT;
+    if (aliased(flow2d::batch_span(ctx, height * pitch_bytes))) return FLOW2D_ERR_INVALID_ARGUMENT;
     const float s = 1.f - t;
     const float max_residual_sq = max_residual * max_residual;
-    dim3 grid(flow2d::div_up(width, kBlockX), flow2d::div_up(flow2d::div_up(height, kRows), kBlockY), flow2d::batch_z(ctx, 1));
-    const BatchArg batch = flow2d::batch_arg(ctx, 1);
-    // 32-bit per-lane offsets when the largest one a lane forms -- (height - 1) * pitch + width + 1 floats, in bytes -- fits
-    if (height * pitch_bytes < (size_t(1) << 32))
-        interpolate_kernel<unsigned><<<grid, dim3(kBlockX, kBlockY), 0, ctx->stream>>>(
+    flow2d::launch_by_span(height * pitch_bytes, [&](auto offset) {
+        interpolate_kernel<decltype(offset)><<<flow2d::pixel_grid(ctx, width, height, kRows), flow2d::pixel_block(), 0, ctx->stream>>>(
             frame_0, frame_1, flow_u, flow_v, back_u, back_v, occlusion_0, occlusion_1, (int)width, (int)height,
-            (int)(pitch_bytes / 4), t, s, iterations, max_residual_sq, output, batch);
-    else
-        interpolate_kernel<size_t><<<grid, dim3(kBlockX, kBlockY), 0, ctx->stream>>>(
-            frame_0, frame_1, flow_u, flow_v, back_u, back_v, occlusion_0, occlusion_1, (int)width, (int)height,
-            (int)(pitch_bytes / 4), t, s, iterations, max_residual_sq, output, batch);
+            (int)(pitch_bytes / 4), t, s, iterations, max_residual_sq, output, flow2d::batch_arg(ctx, 1));
+    });
     FLOW2D_CHECK_LAUNCH();
     return FLOW2D_OK;
 }

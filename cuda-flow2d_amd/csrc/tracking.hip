@@ -318,12 +318,6 @@ __global__ __launch_bounds__(kThreads) void seed_write_kernel(const unsigned cha
     ys[slot] = static_cast<float>(sy);
 }
 
-inline bool overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes)
-{
-    const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
-    return pa < pb + b_bytes && pb < pa + a_bytes;
-}
-
 inline bool aligned(const void* p, size_t alignment) { return (reinterpret_cast<uintptr_t>(p) % alignment) == 0; }
 
 inline bool finite_non_negative(float f) { return std::isfinite(f) && f >= 0.f; }
@@ -360,21 +354,10 @@ int flow2d_track_points_2d(flow2d_context* ctx, const float* flow_u, const float
     if (capacity >= kMaxCapacity) return FLOW2D_ERR_UNSUPPORTED;
     // the kernel marks every pointer __restrict__: no written byte may meet a read one or another written one
     const size_t plane = height * pitch_bytes, table = capacity * sizeof(float);
-    struct Range {
-        const void* p;
-        size_t bytes;
-    };
-    const Range inputs[] = {{flow_u, plane}, {flow_v, plane}, {back_u, plane}, {back_v, plane}, {x, table}, {y, table},
-                            {count, sizeof(unsigned long long)}};
-    const Range outputs[] = {{out_x, table}, {out_y, table}, {reason, capacity}};
-    for (int o = 0; o < 3; ++o) {
-        if (!outputs[o].p) continue;
-        for (const Range& in : inputs)
-            if (in.p && overlap(outputs[o].p, outputs[o].bytes, in.p, in.bytes)) return FLOW2D_ERR_INVALID_ARGUMENT;
-        for (int p = o + 1; p < 3; ++p)
-            if (outputs[p].p && overlap(outputs[o].p, outputs[o].bytes, outputs[p].p, outputs[p].bytes))
-                return FLOW2D_ERR_INVALID_ARGUMENT;
-    }
+    const flow2d::ByteRange read[] = {{flow_u, plane}, {flow_v, plane}, {back_u, plane}, {back_v, plane}, {x, table}, {y, table},
+                                      {count, sizeof(unsigned long long)}};
+    const flow2d::ByteRange written[] = {{out_x, table}, {out_y, table}, {reason, capacity}};
+    if (flow2d::any_overlap(written, read)) return FLOW2D_ERR_INVALID_ARGUMENT;
     if (ctx->batch_count > 1) return FLOW2D_ERR_UNSUPPORTED;  // lock-step batches are not supported
     FLOW2D_ENTER(ctx);
     TrackArgs a;
@@ -415,17 +398,12 @@ int flow2d_seed_points_2d(flow2d_context* ctx, const float* frame, size_t width,
         return FLOW2D_ERR_INVALID_ARGUMENT;
     if (workspace_bytes < flow2d_seed_points_workspace_bytes(width, height, spacing)) return FLOW2D_ERR_INVALID_ARGUMENT;
     const size_t plane = height * pitch_bytes, table = capacity * sizeof(float);
-    struct Range {
-        const void* p;
-        size_t bytes;
-    };
-    const Range ranges[] = {{frame, plane}, {x, table}, {y, table}, {count, sizeof(unsigned long long)},
-                            {dropped, sizeof(unsigned long long)}, {workspace, workspace_bytes}};
-    if (capacity < kMaxCapacity)  // (a larger capacity is refused below; its byte size may not even be representable)
-        for (int i = 0; i < 6; ++i)
-            for (int j = i + 1; j < 6; ++j)
-                if (ranges[i].p && ranges[j].p && overlap(ranges[i].p, ranges[i].bytes, ranges[j].p, ranges[j].bytes))
-                    return FLOW2D_ERR_INVALID_ARGUMENT;
+    // the frame is read, everything else is written: no two of the six ranges may meet
+    const flow2d::ByteRange read[] = {{frame, plane}};
+    const flow2d::ByteRange written[] = {{x, table}, {y, table}, {count, sizeof(unsigned long long)},
+                                         {dropped, sizeof(unsigned long long)}, {workspace, workspace_bytes}};
+    // (a larger capacity is refused below; its byte size may not even be representable)
+    if (capacity < kMaxCapacity && flow2d::any_overlap(written, read)) return FLOW2D_ERR_INVALID_ARGUMENT;
     const SeedLayout l = seed_layout(width, height, spacing);
     if (capacity >= kMaxCapacity || l.cells >= kMaxCells || spacing >= (size_t(1) << 30)) return FLOW2D_ERR_UNSUPPORTED;
     if (ctx->batch_count > 1) return FLOW2D_ERR_UNSUPPORTED;  // lock-step batches are not supported

@@ -6,6 +6,77 @@
 
 #include "device_utils.h"
 
+namespace {
+// The frame of a host-image entry.  From its construction to its destruction: the start line, two events around the uploads,
+// the device work and the downloads, the entry's one host wait (on the second event), the total printed and left in
+// `total_ms`.  An entry that allocated planes for this call alone names them in `per_call`: the stream is then drained and
+// they are freed (the arrays must outlive the scope).
+struct PlaneList {
+    const DevicePtr* planes;
+    size_t count;
+};
+
+class HostCall {
+public:
+    HostCall(flow2d_context* context, float& total_ms, PlaneList a = {nullptr, 0}, PlaneList b = {nullptr, 0},
+             PlaneList c = {nullptr, 0})
+        : context_(context), total_ms_(total_ms), per_call_{a, b, c}
+    {
+        std::printf("\nStarting optical flow computation...\n");
+        flow2d_event_create(context_, &start_);
+        flow2d_event_create(context_, &stop_);
+        flow2d_event_record(context_, start_);
+    }
+    ~HostCall()
+    {
+        flow2d_event_record(context_, stop_);
+        flow2d_event_synchronize(context_, stop_);
+        flow2d_event_elapsed_ms(context_, start_, stop_, &total_ms_);
+        std::printf("Total GPU computation time: % 4.4fs\n", total_ms_ / 1000.);
+        flow2d_event_destroy(context_, start_);
+        flow2d_event_destroy(context_, stop_);
+        if (!per_call_[0].planes) return;
+        flow2d_synchronize(context_);
+        for (const PlaneList& list : per_call_)
+            for (size_t i = 0; i < list.count; ++i)
+                if (list.planes[i]) flow2d_plane_free(context_, AsPlane(list.planes[i]));
+    }
+    HostCall(const HostCall&) = delete;
+    HostCall& operator=(const HostCall&) = delete;
+
+private:
+    flow2d_context* context_;
+    float& total_ms_;
+    PlaneList per_call_[3];
+    void *start_ = nullptr, *stop_ = nullptr;
+};
+
+// Whether every image has the initialised size (a null entry does not); prints the entries' message otherwise.
+struct SizeCheck {
+    DataSize3 size;
+    const char *name, *what;
+
+    bool operator()(Data2D* const* images, size_t count) const
+    {
+        for (size_t i = 0; i < count; ++i)
+            if (!images[i] || images[i]->Width() != size.width || images[i]->Height() != size.height) {
+                std::printf("Error: '%s': %s sizes do not match the initialised size %zu x %zu.\n", name, what, size.width,
+                            size.height);
+                return false;
+            }
+        return true;
+    }
+    bool operator()(Data2D* images, size_t count) const  // an array of images
+    {
+        for (size_t i = 0; i < count; ++i) {
+            Data2D* one = images + i;
+            if (!(*this)(&one, 1)) return false;
+        }
+        return true;
+    }
+};
+}  // namespace
+
 // ---- base ------------------------------------------------------------------------------------------
 size_t OpticalFlowBase2D::GetMaxWarpLevel(size_t width, size_t height, float scale_factor) const
 {
@@ -376,43 +447,17 @@ void OpticalFlow2D::ComputeFlowBidirectional(Data2D& frame_0, Data2D& frame_1, D
         std::printf("Error: '%s': sequences and lock-step groups do not combine.\n", GetName());
         return;
     }
-    const size_t W = dev_container_size_.width, H = dev_container_size_.height;
+    const size_t H = dev_container_size_.height;
     Data2D* images[8] = {&frame_0, &frame_1, &flow_u, &flow_v, &back_u, &back_v, &occlusion_0, &occlusion_1};
-    for (Data2D* d : images)
-        if (d->Width() != W || d->Height() != H) {
-            std::printf("Error: '%s': frame / flow sizes do not match the initialised size %zu x %zu.\n", GetName(), W, H);
-            return;
-        }
-    for (DevicePtr& p : bidirectional_planes_) {
-        if (p) continue;
-        void* plane = nullptr;
-        size_t pitch = 0;
-        if (CheckFlow2DError(flow2d_plane_alloc(context_, W, H, &plane, &pitch), "flow2d_plane_alloc")) return;
-        p = static_cast<DevicePtr>(reinterpret_cast<uintptr_t>(plane));
-        if (pitch != dev_container_size_.pitch) {
-            std::printf("Error: '%s': plane pitch %zu differs from the container pitch %zu.\n", GetName(), pitch,
-                        dev_container_size_.pitch);
-            return;
-        }
-    }
-    std::printf("\nStarting optical flow computation...\n");
-    void *ev_start = nullptr, *ev_stop = nullptr;
-    flow2d_event_create(context_, &ev_start);
-    flow2d_event_create(context_, &ev_stop);
-    flow2d_event_record(context_, ev_start);
-
+    if (!SizeCheck{dev_container_size_, GetName(), "frame / flow"}(images, 8)) return;
+    if (!EnsurePlanes(bidirectional_planes_, 8)) return;
+    HostCall call(context_, last_total_ms_);
     const DevicePtr* d = bidirectional_planes_;  // frame 0, frame 1, u, v, back u, back v, occlusion 0, occlusion 1
     bool ok = CopyData2DtoDevice(frame_0, d[0], H, dev_container_size_.pitch) &&
               CopyData2DtoDevice(frame_1, d[1], H, dev_container_size_.pitch);
     ok = ok && ComputeFlowBidirectionalDevice(d, 2, d + 2, d + 3, d + 4, d + 5, d + 6, d + 7, params);
     for (int i = 2; ok && i < 8; ++i) ok = CopyData2DFromDevice(d[i], *images[i], H, dev_container_size_.pitch);
     last_run_ok_ = ok;
-    flow2d_event_record(context_, ev_stop);
-    flow2d_event_synchronize(context_, ev_stop);  // the only host wait
-    flow2d_event_elapsed_ms(context_, ev_start, ev_stop, &last_total_ms_);
-    std::printf("Total GPU computation time: % 4.4fs\n", last_total_ms_ / 1000.);
-    flow2d_event_destroy(context_, ev_start);
-    flow2d_event_destroy(context_, ev_stop);
 }
 
 bool OpticalFlow2D::EnsurePlanes(DevicePtr* planes, size_t count)
@@ -515,27 +560,18 @@ void OpticalFlow2D::InterpolateFrames(Data2D& frame_0, Data2D& frame_1, const fl
         return;
     }
     if (!InterpolationArgsOk(times, time_count, iterations, max_residual)) return;
-    const size_t W = dev_container_size_.width, H = dev_container_size_.height;
+    const size_t H = dev_container_size_.height;
     Data2D* flows[6] = {flow_u, flow_v, back_u, back_v, use_masks ? occlusion_0 : nullptr, use_masks ? occlusion_1 : nullptr};
     std::vector<Data2D*> images = {&frame_0, &frame_1};
     for (size_t j = 0; j < time_count; ++j) images.push_back(outputs + j);
     for (Data2D* d : flows)
         if (d) images.push_back(d);
-    for (Data2D* d : images)
-        if (d->Width() != W || d->Height() != H) {
-            std::printf("Error: '%s': frame / output sizes do not match the initialised size %zu x %zu.\n", GetName(), W, H);
-            return;
-        }
+    if (!SizeCheck{dev_container_size_, GetName(), "frame / output"}(images.data(), images.size())) return;
     if (interpolation_outputs_.size() < time_count) interpolation_outputs_.resize(time_count, 0);
     if (!EnsurePlanes(bidirectional_planes_, 2) || !EnsurePlanes(interpolation_planes_, 6) ||
         !EnsurePlanes(interpolation_outputs_.data(), time_count))
         return;
-    std::printf("\nStarting optical flow computation...\n");
-    void *ev_start = nullptr, *ev_stop = nullptr;
-    flow2d_event_create(context_, &ev_start);
-    flow2d_event_create(context_, &ev_stop);
-    flow2d_event_record(context_, ev_start);
-
+    HostCall call(context_, last_total_ms_);
     const size_t pitch = dev_container_size_.pitch;
     const DevicePtr* f = bidirectional_planes_;  // frame 0, frame 1
     bool ok = CopyData2DtoDevice(frame_0, f[0], H, pitch) && CopyData2DtoDevice(frame_1, f[1], H, pitch) &&
@@ -545,12 +581,6 @@ void OpticalFlow2D::InterpolateFrames(Data2D& frame_0, Data2D& frame_1, const fl
     for (int i = 0; ok && i < 6; ++i)
         if (flows[i]) ok = CopyData2DFromDevice(interpolation_planes_[i], *flows[i], H, pitch);
     last_run_ok_ = ok;
-    flow2d_event_record(context_, ev_stop);
-    flow2d_event_synchronize(context_, ev_stop);  // the only host wait
-    flow2d_event_elapsed_ms(context_, ev_start, ev_stop, &last_total_ms_);
-    std::printf("Total GPU computation time: % 4.4fs\n", last_total_ms_ / 1000.);
-    flow2d_event_destroy(context_, ev_start);
-    flow2d_event_destroy(context_, ev_stop);
 }
 
 // `bytes` of device memory (a one-row plane, 16-byte aligned); 0 on failure
@@ -679,42 +709,27 @@ void OpticalFlow2D::TrackPoints(Data2D* const* frames, size_t frame_count, size_
         std::printf("Error: '%s': sequences and lock-step groups do not combine.\n", GetName());
         return;
     }
-    const size_t W = dev_container_size_.width, H = dev_container_size_.height, pitch = dev_container_size_.pitch;
-    for (size_t k = 0; k < frame_count; ++k)
-        if (!frames[k] || frames[k]->Width() != W || frames[k]->Height() != H) {
-            std::printf("Error: '%s': frame sizes do not match the initialised size %zu x %zu.\n", GetName(), W, H);
-            return;
-        }
+    const size_t H = dev_container_size_.height, pitch = dev_container_size_.pitch;
+    if (!SizeCheck{dev_container_size_, GetName(), "frame"}(frames, frame_count)) return;
     // the frames and the tables of this call (freed at its end)
     std::vector<DevicePtr> dev_frames(frame_count, 0), dev_xs(frame_count, 0), dev_ys(frame_count, 0);
     bool ok = EnsurePlanes(dev_frames.data(), frame_count);
     for (size_t k = 0; ok && k < frame_count; ++k) ok = (dev_xs[k] = AllocBytes(capacity * 4)) && (dev_ys[k] = AllocBytes(capacity * 4));
-    std::printf("\nStarting optical flow computation...\n");
-    void *ev_start = nullptr, *ev_stop = nullptr;
-    flow2d_event_create(context_, &ev_start);
-    flow2d_event_create(context_, &ev_stop);
-    flow2d_event_record(context_, ev_start);
-    for (size_t k = 0; ok && k < frame_count; ++k) ok = CopyData2DtoDevice(*frames[k], dev_frames[k], H, pitch);
-    ok = ok && TrackPointsDevice(dev_frames.data(), frame_count, spacing, min_eigenvalue, check_boundaries, beta1, beta2,
-                                 dev_xs.data(), dev_ys.data(), capacity, counts_out, params);
-    const size_t table_bytes = capacity * sizeof(float);
-    for (size_t k = 0; ok && k < frame_count; ++k)
-        ok = !CheckFlow2DError(flow2d_copy_d2h_2d(context_, xs + k * capacity, table_bytes, AsPlane(dev_xs[k]), table_bytes,
-                                                  table_bytes, 1),
-                               "flow2d_copy_d2h_2d") &&
-             !CheckFlow2DError(flow2d_copy_d2h_2d(context_, ys + k * capacity, table_bytes, AsPlane(dev_ys[k]), table_bytes,
-                                                  table_bytes, 1),
-                               "flow2d_copy_d2h_2d");
-    flow2d_event_record(context_, ev_stop);
-    flow2d_event_synchronize(context_, ev_stop);  // the downloads
-    flow2d_event_elapsed_ms(context_, ev_start, ev_stop, &last_total_ms_);
-    std::printf("Total GPU computation time: % 4.4fs\n", last_total_ms_ / 1000.);
-    flow2d_event_destroy(context_, ev_start);
-    flow2d_event_destroy(context_, ev_stop);
-    flow2d_synchronize(context_);
-    for (const std::vector<DevicePtr>* planes : {&dev_frames, &dev_xs, &dev_ys})
-        for (DevicePtr p : *planes)
-            if (p) flow2d_plane_free(context_, AsPlane(p));
+    {
+        HostCall call(context_, last_total_ms_, {dev_frames.data(), frame_count}, {dev_xs.data(), frame_count},
+                      {dev_ys.data(), frame_count});
+        for (size_t k = 0; ok && k < frame_count; ++k) ok = CopyData2DtoDevice(*frames[k], dev_frames[k], H, pitch);
+        ok = ok && TrackPointsDevice(dev_frames.data(), frame_count, spacing, min_eigenvalue, check_boundaries, beta1, beta2,
+                                     dev_xs.data(), dev_ys.data(), capacity, counts_out, params);
+        const size_t table_bytes = capacity * sizeof(float);
+        for (size_t k = 0; ok && k < frame_count; ++k)
+            ok = !CheckFlow2DError(flow2d_copy_d2h_2d(context_, xs + k * capacity, table_bytes, AsPlane(dev_xs[k]), table_bytes,
+                                                      table_bytes, 1),
+                                   "flow2d_copy_d2h_2d") &&
+                 !CheckFlow2DError(flow2d_copy_d2h_2d(context_, ys + k * capacity, table_bytes, AsPlane(dev_ys[k]), table_bytes,
+                                                      table_bytes, 1),
+                                   "flow2d_copy_d2h_2d");
+    }
     last_run_ok_ = ok;
 }
 
@@ -833,33 +848,22 @@ void OpticalFlow2D::EstimateGlobalMotion(Data2D& frame_0, Data2D& frame_1, int m
     last_run_ok_ = false;
     if (!GlobalMotionArgsOk(model, sigma, iterations)) return;
     if (!IsInitialized() || !motion_out) return;
-    const size_t W = dev_container_size_.width, H = dev_container_size_.height, pitch = dev_container_size_.pitch;
+    const size_t H = dev_container_size_.height, pitch = dev_container_size_.pitch;
     Data2D* images[6] = {&frame_0, &frame_1, flow_u, flow_v, residual_u, residual_v};
+    Data2D* given[6];
+    size_t given_count = 0;
     for (Data2D* d : images)
-        if (d && (d->Width() != W || d->Height() != H)) {
-            std::printf("Error: '%s': frame / flow sizes do not match the initialised size %zu x %zu.\n", GetName(), W, H);
-            return;
-        }
+        if (d) given[given_count++] = d;
+    if (!SizeCheck{dev_container_size_, GetName(), "frame / flow"}(given, given_count)) return;
     DevicePtr d[6] = {0, 0, 0, 0, 0, 0};  // the planes of this call (freed at its end)
     bool ok = EnsurePlanes(d, 6);
-    std::printf("\nStarting optical flow computation...\n");
-    void *ev_start = nullptr, *ev_stop = nullptr;
-    flow2d_event_create(context_, &ev_start);
-    flow2d_event_create(context_, &ev_stop);
-    flow2d_event_record(context_, ev_start);
-    ok = ok && CopyData2DtoDevice(frame_0, d[0], H, pitch) && CopyData2DtoDevice(frame_1, d[1], H, pitch);
-    ok = ok && EstimateGlobalMotionDevice(d[0], d[1], model, sigma, iterations, use_masks, motion_out, params, d[2], d[3], d[4], d[5]);
-    for (int i = 2; ok && i < 6; ++i)
-        if (images[i]) ok = CopyData2DFromDevice(d[i], *images[i], H, pitch);
-    flow2d_event_record(context_, ev_stop);
-    flow2d_event_synchronize(context_, ev_stop);  // the downloads
-    flow2d_event_elapsed_ms(context_, ev_start, ev_stop, &last_total_ms_);
-    std::printf("Total GPU computation time: % 4.4fs\n", last_total_ms_ / 1000.);
-    flow2d_event_destroy(context_, ev_start);
-    flow2d_event_destroy(context_, ev_stop);
-    flow2d_synchronize(context_);
-    for (DevicePtr p : d)
-        if (p) flow2d_plane_free(context_, AsPlane(p));
+    {
+        HostCall call(context_, last_total_ms_, {d, 6});
+        ok = ok && CopyData2DtoDevice(frame_0, d[0], H, pitch) && CopyData2DtoDevice(frame_1, d[1], H, pitch);
+        ok = ok && EstimateGlobalMotionDevice(d[0], d[1], model, sigma, iterations, use_masks, motion_out, params, d[2], d[3], d[4], d[5]);
+        for (int i = 2; ok && i < 6; ++i)
+            if (images[i]) ok = CopyData2DFromDevice(d[i], *images[i], H, pitch);
+    }
     last_run_ok_ = ok;
 }
 
@@ -939,34 +943,19 @@ void OpticalFlow2D::StabiliseSequence(Data2D* const* frames, size_t frame_count,
     last_run_ok_ = false;
     if (!GlobalMotionArgsOk(model, sigma, iterations)) return;
     if (!IsInitialized() || !frames || !outputs || frame_count < 2 || reference_index >= frame_count) return;
-    const size_t W = dev_container_size_.width, H = dev_container_size_.height, pitch = dev_container_size_.pitch;
-    for (size_t k = 0; k < frame_count; ++k)
-        if (!frames[k] || frames[k]->Width() != W || frames[k]->Height() != H || outputs[k].Width() != W || outputs[k].Height() != H) {
-            std::printf("Error: '%s': frame / output sizes do not match the initialised size %zu x %zu.\n", GetName(), W, H);
-            return;
-        }
+    const size_t H = dev_container_size_.height, pitch = dev_container_size_.pitch;
+    const SizeCheck sizes_match{dev_container_size_, GetName(), "frame / output"};
+    if (!sizes_match(frames, frame_count) || !sizes_match(outputs, frame_count)) return;
     // the frames and the outputs of this call (freed at its end)
     std::vector<DevicePtr> dev_frames(frame_count, 0), dev_outputs(frame_count, 0);
     bool ok = EnsurePlanes(dev_frames.data(), frame_count) && EnsurePlanes(dev_outputs.data(), frame_count);
-    std::printf("\nStarting optical flow computation...\n");
-    void *ev_start = nullptr, *ev_stop = nullptr;
-    flow2d_event_create(context_, &ev_start);
-    flow2d_event_create(context_, &ev_stop);
-    flow2d_event_record(context_, ev_start);
-    for (size_t k = 0; ok && k < frame_count; ++k) ok = CopyData2DtoDevice(*frames[k], dev_frames[k], H, pitch);
-    ok = ok && StabiliseSequenceDevice(dev_frames.data(), frame_count, reference_index, model, sigma, iterations, use_masks, fill,
-                                       dev_outputs.data(), motions_out, params);
-    for (size_t k = 0; ok && k < frame_count; ++k) ok = CopyData2DFromDevice(dev_outputs[k], outputs[k], H, pitch);
-    flow2d_event_record(context_, ev_stop);
-    flow2d_event_synchronize(context_, ev_stop);  // the downloads
-    flow2d_event_elapsed_ms(context_, ev_start, ev_stop, &last_total_ms_);
-    std::printf("Total GPU computation time: % 4.4fs\n", last_total_ms_ / 1000.);
-    flow2d_event_destroy(context_, ev_start);
-    flow2d_event_destroy(context_, ev_stop);
-    flow2d_synchronize(context_);
-    for (const std::vector<DevicePtr>* planes : {&dev_frames, &dev_outputs})
-        for (DevicePtr p : *planes)
-            if (p) flow2d_plane_free(context_, AsPlane(p));
+    {
+        HostCall call(context_, last_total_ms_, {dev_frames.data(), frame_count}, {dev_outputs.data(), frame_count});
+        for (size_t k = 0; ok && k < frame_count; ++k) ok = CopyData2DtoDevice(*frames[k], dev_frames[k], H, pitch);
+        ok = ok && StabiliseSequenceDevice(dev_frames.data(), frame_count, reference_index, model, sigma, iterations, use_masks,
+                                           fill, dev_outputs.data(), motions_out, params);
+        for (size_t k = 0; ok && k < frame_count; ++k) ok = CopyData2DFromDevice(dev_outputs[k], outputs[k], H, pitch);
+    }
     last_run_ok_ = ok;
 }
 
@@ -1098,39 +1087,26 @@ void OpticalFlow2D::DenoiseSequence(Data2D* const* frames, size_t frame_count, s
         std::printf("Error: '%s': sequences and lock-step groups do not combine.\n", GetName());
         return;
     }
-    const size_t W = dev_container_size_.width, H = dev_container_size_.height, pitch = dev_container_size_.pitch;
-    for (size_t k = 0; k < frame_count; ++k)
-        if (!frames[k] || frames[k]->Width() != W || frames[k]->Height() != H || outputs[k].Width() != W || outputs[k].Height() != H ||
-            (weight_sums && (weight_sums[k].Width() != W || weight_sums[k].Height() != H))) {
-            std::printf("Error: '%s': frame / output sizes do not match the initialised size %zu x %zu.\n", GetName(), W, H);
-            return;
-        }
+    const size_t H = dev_container_size_.height, pitch = dev_container_size_.pitch;
+    const SizeCheck sizes_match{dev_container_size_, GetName(), "frame / output"};
+    if (!sizes_match(frames, frame_count) || !sizes_match(outputs, frame_count) ||
+        (weight_sums && !sizes_match(weight_sums, frame_count)))
+        return;
     // the frames and the outputs of this call (freed at its end)
     std::vector<DevicePtr> dev_frames(frame_count, 0), dev_outputs(frame_count, 0), dev_sums(weight_sums ? frame_count : 0, 0);
     bool ok = EnsurePlanes(dev_frames.data(), frame_count) && EnsurePlanes(dev_outputs.data(), frame_count) &&
               EnsurePlanes(dev_sums.data(), dev_sums.size());
-    std::printf("\nStarting optical flow computation...\n");
-    void *ev_start = nullptr, *ev_stop = nullptr;
-    flow2d_event_create(context_, &ev_start);
-    flow2d_event_create(context_, &ev_stop);
-    flow2d_event_record(context_, ev_start);
-    for (size_t k = 0; ok && k < frame_count; ++k) ok = CopyData2DtoDevice(*frames[k], dev_frames[k], H, pitch);
-    ok = ok && DenoiseSequenceDevice(dev_frames.data(), frame_count, radius, range_sigma, use_masks, dev_outputs.data(),
-                                     weight_sums ? dev_sums.data() : nullptr, params);
-    for (size_t k = 0; ok && k < frame_count; ++k) {
-        ok = CopyData2DFromDevice(dev_outputs[k], outputs[k], H, pitch);
-        if (ok && weight_sums) ok = CopyData2DFromDevice(dev_sums[k], weight_sums[k], H, pitch);
+    {
+        HostCall call(context_, last_total_ms_, {dev_frames.data(), frame_count}, {dev_outputs.data(), frame_count},
+                      {dev_sums.data(), dev_sums.size()});
+        for (size_t k = 0; ok && k < frame_count; ++k) ok = CopyData2DtoDevice(*frames[k], dev_frames[k], H, pitch);
+        ok = ok && DenoiseSequenceDevice(dev_frames.data(), frame_count, radius, range_sigma, use_masks, dev_outputs.data(),
+                                         weight_sums ? dev_sums.data() : nullptr, params);
+        for (size_t k = 0; ok && k < frame_count; ++k) {
+            ok = CopyData2DFromDevice(dev_outputs[k], outputs[k], H, pitch);
+            if (ok && weight_sums) ok = CopyData2DFromDevice(dev_sums[k], weight_sums[k], H, pitch);
+        }
     }
-    flow2d_event_record(context_, ev_stop);
-    flow2d_event_synchronize(context_, ev_stop);  // the downloads
-    flow2d_event_elapsed_ms(context_, ev_start, ev_stop, &last_total_ms_);
-    std::printf("Total GPU computation time: % 4.4fs\n", last_total_ms_ / 1000.);
-    flow2d_event_destroy(context_, ev_start);
-    flow2d_event_destroy(context_, ev_stop);
-    flow2d_synchronize(context_);
-    for (const std::vector<DevicePtr>* planes : {&dev_frames, &dev_outputs, &dev_sums})
-        for (DevicePtr p : *planes)
-            if (p) flow2d_plane_free(context_, AsPlane(p));
     last_run_ok_ = ok;
 }
 
@@ -1162,37 +1138,24 @@ void OpticalFlow2D::ComputeFlow(Data2D& frame_0, Data2D& frame_1, Data2D& flow_u
         std::printf("Error: '%s': ComputeFlow takes one pair; lock-step groups go through ComputeFlowDevice.\n", GetName());
         return;
     }
-    const size_t W = dev_container_size_.width, H = dev_container_size_.height;
-    if (frame_0.Width() != W || frame_0.Height() != H || frame_1.Width() != W || frame_1.Height() != H ||
-        flow_u.Width() != W || flow_u.Height() != H || flow_v.Width() != W || flow_v.Height() != H) {
-        std::printf("Error: '%s': frame / flow sizes do not match the initialised size %zu x %zu.\n", GetName(), W, H);
-        return;
+    const size_t H = dev_container_size_.height;
+    Data2D* images[4] = {&frame_0, &frame_1, &flow_u, &flow_v};
+    if (!SizeCheck{dev_container_size_, GetName(), "frame / flow"}(images, 4)) return;
+    {
+        HostCall call(context_, last_total_ms_);
+        dev_frame_0_ = Acquire();
+        dev_frame_1_ = Acquire();
+        dev_flow_u_ = Acquire();
+        dev_flow_v_ = Acquire();
+        bool ok = CopyData2DtoDevice(frame_0, dev_frame_0_, H, dev_container_size_.pitch) &&
+                  CopyData2DtoDevice(frame_1, dev_frame_1_, H, dev_container_size_.pitch);
+        ok = ok && RunPyramid(params);
+        if (ok) {
+            ok = CopyData2DFromDevice(dev_flow_u_, flow_u, H, dev_container_size_.pitch) &&
+                 CopyData2DFromDevice(dev_flow_v_, flow_v, H, dev_container_size_.pitch);
+        }
+        last_run_ok_ = ok;
     }
-    std::printf("\nStarting optical flow computation...\n");
-    void *ev_start = nullptr, *ev_stop = nullptr;
-    flow2d_event_create(context_, &ev_start);
-    flow2d_event_create(context_, &ev_stop);
-    flow2d_event_record(context_, ev_start);
-
-    dev_frame_0_ = Acquire();
-    dev_frame_1_ = Acquire();
-    dev_flow_u_ = Acquire();
-    dev_flow_v_ = Acquire();
-    bool ok = CopyData2DtoDevice(frame_0, dev_frame_0_, H, dev_container_size_.pitch) &&
-              CopyData2DtoDevice(frame_1, dev_frame_1_, H, dev_container_size_.pitch);
-    ok = ok && RunPyramid(params);
-    if (ok) {
-        ok = CopyData2DFromDevice(dev_flow_u_, flow_u, H, dev_container_size_.pitch) &&
-             CopyData2DFromDevice(dev_flow_v_, flow_v, H, dev_container_size_.pitch);
-    }
-    last_run_ok_ = ok;
-    flow2d_event_record(context_, ev_stop);
-    flow2d_event_synchronize(context_, ev_stop);  // the only host wait of a pair
-    flow2d_event_elapsed_ms(context_, ev_start, ev_stop, &last_total_ms_);
-    std::printf("Total GPU computation time: % 4.4fs\n", last_total_ms_ / 1000.);
-    flow2d_event_destroy(context_, ev_start);
-    flow2d_event_destroy(context_, ev_stop);
-
     Release(dev_frame_0_);
     Release(dev_frame_1_);
     Release(dev_flow_u_);
