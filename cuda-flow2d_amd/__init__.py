@@ -145,6 +145,41 @@ class GlobalMotion(C.Structure):
 GLOBAL_MOTION_BYTES = 80  # FLOW2D_GLOBAL_MOTION_BYTES, checked by a static_assert in the header
 assert C.sizeof(GlobalMotion) == GLOBAL_MOTION_BYTES
 
+
+
+class MotionRegion(C.Structure):
+    """flow2d_motion_region of include/flow2d_c_abi.h: the record flow2d_segment_motion_2d writes per region."""
+    _fields_ = [
+        ("area", C.c_ulonglong), ("sum_x", C.c_ulonglong), ("sum_y", C.c_ulonglong), ("sum_u_q16", C.c_longlong),
+        ("sum_v_q16", C.c_longlong), ("x0", C.c_int), ("y0", C.c_int), ("x1", C.c_int), ("y1", C.c_int), ("first", C.c_ulonglong),
+    ]
+
+    @property
+    def bbox(self):
+        return (self.x0, self.y0, self.x1, self.y1)
+
+    @property
+    def centroid(self):
+        return (self.sum_x / self.area, self.sum_y / self.area)
+
+    @property
+    def mean_motion(self):
+        """The mean residual motion of the region in pixels (the Q16 sums divided out)."""
+        return (self.sum_u_q16 / 65536.0 / self.area, self.sum_v_q16 / 65536.0 / self.area)
+
+
+class SegmentSummary(C.Structure):
+    """flow2d_segment_summary: what flow2d_segment_motion_2d writes per instance."""
+    _fields_ = [
+        ("region_count", C.c_ulonglong), ("foreground", C.c_ulonglong), ("dropped", C.c_ulonglong), ("recorded", C.c_uint),
+        ("reserved", C.c_uint),
+    ]
+
+
+MOTION_REGION_BYTES, SEGMENT_SUMMARY_BYTES = 64, 32  # FLOW2D_MOTION_REGION_BYTES, FLOW2D_SEGMENT_SUMMARY_BYTES
+assert C.sizeof(MotionRegion) == MOTION_REGION_BYTES and C.sizeof(SegmentSummary) == SEGMENT_SUMMARY_BYTES
+DEFAULT_MAX_REGIONS = 4096
+
 _hip = None
 
 
@@ -248,6 +283,10 @@ def hip_lib():
             L.flow2d_global_motion_2d.argtypes = [vp, vp, vp, vp, sz, sz, sz, i, d, i, vp, vp, sz]
             L.flow2d_global_flow_2d.argtypes = [vp, vp, vp, vp, vp, sz, sz, sz, d, vp, vp, vp, vp, vp]
             L.flow2d_warp_global_2d.argtypes = [vp, vp, vp, sz, sz, sz, f, vp, vp]
+        if hasattr(L, "flow2d_segment_motion_2d"):  # (absent from libraries of earlier rounds loaded for an A/B)
+            L.flow2d_segment_motion_workspace_bytes.restype = sz
+            L.flow2d_segment_motion_workspace_bytes.argtypes = [sz, sz, sz]
+            L.flow2d_segment_motion_2d.argtypes = [vp, vp, vp, vp, sz, sz, sz, f, f, C.c_uint, vp, vp, sz, vp, vp, sz]
         if hasattr(L, "flow2d_flow_error_2d"):  # (absent from libraries of earlier rounds loaded for an A/B)
             L.flow2d_flow_error_workspace_bytes.restype = sz
             L.flow2d_flow_error_workspace_bytes.argtypes = [sz, sz, sz]
@@ -629,6 +668,65 @@ class Context:
         _check(hip_lib().flow2d_warp_global_2d(self.handle, motion.ptr, frame.ptr, w, h, frame.pitch, fill, out.ptr,
                                                valid.ptr if valid else None), "flow2d_warp_global_2d")
 
+    def region_records(self, max_regions=DEFAULT_MAX_REGIONS, instances=1):
+        """A Plane for `instances` tables of `max_regions` flow2d_motion_region records (device memory)."""
+        return self.plane(max(instances * max_regions, 1) * MOTION_REGION_BYTES // 4, 1)
+
+    def segment_summaries(self, instances=1):
+        """A Plane for `instances` flow2d_segment_summary records (device memory)."""
+        return self.plane(instances * SEGMENT_SUMMARY_BYTES // 4, 1)
+
+    def read_regions(self, regions, count, max_regions=None, instance=0):
+        """The first `count` records of instance `instance` of a region_records Plane whose tables hold `max_regions` records
+        each, as MotionRegion structures (synchronises)."""
+        if count == 0:
+            return []
+        stride = (count if max_regions is None else max_regions) * MOTION_REGION_BYTES // 4
+        raw = regions.download((instance + 1) * stride, 1)[0, instance * stride:]
+        return list((MotionRegion * count).from_buffer_copy(raw[:count * MOTION_REGION_BYTES // 4].tobytes()))
+
+    def read_segment_summary(self, summary, instances=1):
+        """The records of a segment_summaries Plane as SegmentSummary structures (synchronises)."""
+        raw = summary.download(instances * SEGMENT_SUMMARY_BYTES // 4, 1)
+        return list((SegmentSummary * instances).from_buffer_copy(raw.tobytes()))
+
+    def segment_motion(self, ru, rv, w, h, threshold, join=float("inf"), min_area=1, mask=None, max_regions=DEFAULT_MAX_REGIONS,
+                       instances=1, labels=None, regions=None, summary=None):
+        """The independently moving regions of the residual flow (ru, rv) (flow2d_segment_motion_2d): the pixels with
+        |r| > threshold (and mask < 0.5) form the foreground, 4-neighbours whose residuals differ by at most `join` are joined,
+        components below `min_area` pixels are dropped and the rest numbered from 1 in raster order of their first pixel.
+        `labels` (a Plane, read as int32), `regions` (region_records) and `summary` (segment_summaries) stay on the device; the
+        ones not given are the context's own.  With none of the three given the call downloads and returns
+        (labels [h, w] int32 of instance 0, [MotionRegion] of instance 0, [SegmentSummary per instance]); otherwise nothing is
+        returned or synchronised.  The workspace is the context's own (kept between calls)."""
+        L = hip_lib()
+        need = L.flow2d_segment_motion_workspace_bytes(w, h, instances)
+        cached = getattr(self, "_segment_buffers", None)
+        if cached is None or cached[0] < need:
+            if cached is not None:
+                cached[1].free()
+                self._planes.remove(cached[1])
+            self._segment_buffers = cached = (need, self.plane(max(need // 4, 4), 1))
+        own = labels is None and regions is None and summary is None
+        if own and instances != 1:
+            raise ValueError("a lock-step batch takes the caller's labels, regions and summary")
+        labels = labels or self.plane(ru.width, ru.height)
+        if regions is None and max_regions > 0:
+            regions = self.region_records(max_regions, instances)
+        summary = summary or self.segment_summaries(instances)
+        _check(L.flow2d_segment_motion_2d(self.handle, ru.ptr, rv.ptr, mask.ptr if mask else None, w, h, ru.pitch, float(threshold),
+                                          float(join), int(min_area), labels.ptr, regions.ptr if max_regions > 0 else None,
+                                          int(max_regions), summary.ptr, cached[1].ptr, cached[0]), "flow2d_segment_motion_2d")
+        if not own:
+            return None
+        s = self.read_segment_summary(summary, 1)
+        out = labels.download(w, h).view(np.int32), self.read_regions(regions, s[0].recorded, max_regions) if regions else [], s
+        for q in (labels, regions, summary):
+            if q:
+                q.free()
+                self._planes.remove(q)
+        return out
+
     def resample_x(self, src, dst, out_w, out_h, in_w):
         _check(hip_lib().flow2d_resample_x(self.handle, src.ptr, dst.ptr, out_w, out_h, in_w, src.pitch),
                "flow2d_resample_x")
@@ -804,6 +902,14 @@ def host_lib():
             L.flow2d_host_stabilise_sequence.argtypes = [vp, fp, sz, sz, i, d, i, i, f, fp, gm, C.POINTER(HostParams), fp]
             L.flow2d_host_stabilise_sequence_device.argtypes = [vp, C.POINTER(vp), sz, sz, i, d, i, i, f, C.POINTER(vp), gm,
                                                                 C.POINTER(HostParams)]
+        if hasattr(L, "flow2d_host_segment_motion"):
+            d, u32 = C.c_double, C.c_uint
+            head = [i, d, i, i, f, f, u32, C.POINTER(GlobalMotion), C.POINTER(SegmentSummary), C.POINTER(MotionRegion),
+                    C.POINTER(HostParams)]
+            L.flow2d_host_segment_motion_args_ok.argtypes = [f, f, u32]
+            L.flow2d_host_segment_max_regions.restype = sz
+            L.flow2d_host_segment_motion.argtypes = [vp, fp, fp] + head + [C.POINTER(C.c_int), fp, fp]
+            L.flow2d_host_segment_motion_device.argtypes = [vp, vp, vp] + head + [vp, vp, vp]
         L.flow2d_host_read_flo.argtypes = [C.c_char_p, C.POINTER(sz), C.POINTER(sz), fp, fp, sz]
         L.flow2d_host_write_flo.argtypes = [fp, fp, sz, sz, C.c_char_p]
         L.flow2d_host_flow_error.argtypes = [fp] * 5 + [sz, sz, fp, fp, C.POINTER(FlowErrorStats)]
@@ -1092,6 +1198,45 @@ class OpticalFlow:
         if rc:
             raise Flow2DError(rc, "OpticalFlow2D::EstimateGlobalMotionDevice")
         return rec
+
+    def segment_motion(self, frame_0, frame_1, params, model=MOTION_AFFINE, sigma=0.5, iterations=5, threshold=0.5,
+                       join=float("inf"), min_area=16, masks=False, residual=False):
+        """OpticalFlow2D::SegmentMotion: the independently moving regions of the host pair -- the flow frame_0 -> frame_1
+        (bidirectional with masks, the forward occlusion mask leaving its pixels out), the global motion `model`, the residual
+        flow and flow2d_segment_motion_2d on it.  Returns (GlobalMotion, SegmentSummary, [MotionRegion] -- the recorded ones --,
+        labels [h, w] int32); with residual, also (ru, rv)."""
+        f0, f1 = (np.ascontiguousarray(a, np.float32) for a in (frame_0, frame_1))
+        if f0.shape != (self.height, self.width) or f1.shape != f0.shape:
+            raise ValueError("frames: [%d, %d]" % (self.height, self.width))
+        H = host_lib()
+        rec, summary = GlobalMotion(), SegmentSummary()
+        regions = (MotionRegion * H.flow2d_host_segment_max_regions())()
+        labels = np.empty(f0.shape, np.int32)
+        rs = [np.empty_like(f0) for _ in range(2)] if residual else [None, None]
+        opt = lambda a: None if a is None else _fptr(a)  # noqa: E731
+        rc = H.flow2d_host_segment_motion(self.handle, _fptr(f0), _fptr(f1), int(model), float(sigma), int(iterations),
+                                          int(bool(masks)), float(threshold), float(join), int(min_area), C.byref(rec),
+                                          C.byref(summary), regions, C.byref(params), labels.ctypes.data_as(C.POINTER(C.c_int)),
+                                          opt(rs[0]), opt(rs[1]))
+        if rc:
+            raise Flow2DError(rc, "OpticalFlow2D::SegmentMotion")
+        out = (rec, summary, list(regions)[:summary.recorded], labels)
+        return out + (tuple(rs),) if residual else out
+
+    def segment_motion_device(self, dev_frame_0, dev_frame_1, params, model=MOTION_AFFINE, sigma=0.5, iterations=5, threshold=0.5,
+                              join=float("inf"), min_area=16, masks=False, dev_labels=None, dev_residual=None):
+        """OpticalFlow2D::SegmentMotionDevice: two device frames in; (GlobalMotion, SegmentSummary, [MotionRegion]) out
+        (synchronises); dev_labels / dev_residual (a (u, v) pair): optional device planes for the labels and the residual flow."""
+        H = host_lib()
+        rec, summary = GlobalMotion(), SegmentSummary()
+        regions = (MotionRegion * H.flow2d_host_segment_max_regions())()
+        rs = dev_residual or (None, None)
+        rc = H.flow2d_host_segment_motion_device(self.handle, dev_frame_0, dev_frame_1, int(model), float(sigma), int(iterations),
+                                                 int(bool(masks)), float(threshold), float(join), int(min_area), C.byref(rec),
+                                                 C.byref(summary), regions, C.byref(params), dev_labels, rs[0], rs[1])
+        if rc:
+            raise Flow2DError(rc, "OpticalFlow2D::SegmentMotionDevice")
+        return rec, summary, list(regions)[:summary.recorded]
 
     def stabilise_sequence(self, frames, params, reference_index=0, model=MOTION_AFFINE, sigma=0.5, iterations=5, masks=False,
                            fill=0.0):

@@ -414,6 +414,65 @@ HOST_API int flow2d_host_estimate_global_motion_device(flow2d_host_flow* h, void
                : 2;
 }
 
+// OpticalFlow2D::SegmentMotionArgsOk: 1 when threshold, join and min_area are what flow2d_segment_motion_2d accepts.  Needs no device.
+HOST_API int flow2d_host_segment_motion_args_ok(float threshold, float join, unsigned min_area)
+{
+    return OpticalFlow2D::SegmentMotionArgsOk(threshold, join, min_area) ? 1 : 0;
+}
+
+// How many records flow2d_host_segment_motion* write into `regions` (OpticalFlow2D::kSegmentMaxRegions).
+HOST_API size_t flow2d_host_segment_max_regions() { return OpticalFlow2D::kSegmentMaxRegions; }
+
+// OpticalFlow2D::SegmentMotion on tight host images: the record, the summary and the region table (regions: optional,
+// flow2d_host_segment_max_regions() records); labels (width*height ints) and residual_u / residual_v (optional) get the planes.
+// 0 on success, 1 for a null or refused argument, 2 when the run delivered nothing.
+HOST_API int flow2d_host_segment_motion(flow2d_host_flow* h, const float* frame_0, const float* frame_1, int model, double sigma,
+                                        int iterations, int use_masks, float threshold, float join, unsigned min_area,
+                                        flow2d_global_motion* motion, flow2d_segment_summary* summary, flow2d_motion_region* regions,
+                                        const flow2d_host_params* params, int* labels, float* residual_u, float* residual_v)
+{
+    if (!OpticalFlow2D::GlobalMotionArgsOk(model, sigma, iterations) || !OpticalFlow2D::SegmentMotionArgsOk(threshold, join, min_area) ||
+        !h || !frame_0 || !frame_1 || !motion || !summary || !params || (residual_u == nullptr) != (residual_v == nullptr))
+        return 1;
+    const size_t n = h->width * h->height;
+    Data2D f0(h->width, h->height), f1(h->width, h->height);
+    std::memcpy(f0.DataPtr(), frame_0, n * sizeof(float));
+    std::memcpy(f1.DataPtr(), frame_1, n * sizeof(float));
+    Data2D out[3] = {Data2D(h->width, h->height), Data2D(h->width, h->height), Data2D(h->width, h->height)};
+    void* dst[3] = {labels, residual_u, residual_v};
+    flow2d_host_params p = *params;
+    OperationParameters bag;
+    FillBag(bag, p);
+    h->flow.SegmentMotion(f0, f1, model, sigma, iterations, use_masks != 0, threshold, join, min_area, motion, summary, regions, bag,
+                          labels ? &out[0] : nullptr, residual_u ? &out[1] : nullptr, residual_u ? &out[2] : nullptr);
+    if (h->flow.LastRunSucceeded())
+        for (int i = 0; i < 3; ++i)
+            if (dst[i]) std::memcpy(dst[i], out[i].DataPtr(), n * sizeof(float));
+    return h->flow.LastRunSucceeded() ? 0 : 2;
+}
+
+// OpticalFlow2D::SegmentMotionDevice: two device frames; the optional device planes get the labels and the residual flow.
+// Synchronises.  0 on success, 1 for a null or refused argument.
+HOST_API int flow2d_host_segment_motion_device(flow2d_host_flow* h, void* dev_frame_0, void* dev_frame_1, int model, double sigma,
+                                               int iterations, int use_masks, float threshold, float join, unsigned min_area,
+                                               flow2d_global_motion* motion, flow2d_segment_summary* summary,
+                                               flow2d_motion_region* regions, const flow2d_host_params* params, void* dev_labels,
+                                               void* dev_residual_u, void* dev_residual_v)
+{
+    if (!OpticalFlow2D::GlobalMotionArgsOk(model, sigma, iterations) || !OpticalFlow2D::SegmentMotionArgsOk(threshold, join, min_area) ||
+        !h || !dev_frame_0 || !dev_frame_1 || !motion || !summary || !params)
+        return 1;
+    flow2d_host_params p = *params;
+    OperationParameters bag;
+    FillBag(bag, p);
+    h->flow.timing_mode = 0;
+    auto dp = [](void* q) { return static_cast<DevicePtr>(reinterpret_cast<uintptr_t>(q)); };
+    return h->flow.SegmentMotionDevice(dp(dev_frame_0), dp(dev_frame_1), model, sigma, iterations, use_masks != 0, threshold, join,
+                                       min_area, motion, summary, regions, bag, dp(dev_labels), dp(dev_residual_u), dp(dev_residual_v))
+               ? 0
+               : 2;
+}
+
 // OpticalFlow2D::StabiliseSequence on tight host images: frames = frame_count * width * height floats (frame k at k * width *
 // height); outputs get the same layout, motions (optional) frame_count records.  0 on success, 1 for a null or refused argument,
 // 2 when the run delivered no frames.

@@ -37,6 +37,12 @@
 // u = (p0 + p1*xc) + p2*yc, v = (p3 + p4*xc) + p5*yc in centred coordinates with 17 significant digits, "weight_sum" and
 // "support" --, writes the flow without the global motion as <prefix>residual-u-W-H.raw and <prefix>residual-v-W-H.raw (F32, NaN
 // where the flow is not finite) and, with --flo, <prefix>residual.flo.  The other files do not change; a run of its own, too.
+// --segment-motion THRESHOLD (pixels, >= 0; needs --global-motion) [--segment-join J, >= 0 or inf, default inf] [--segment-min-area
+// A, >= 1, default 16] also labels the independently moving regions of the pair (OpticalFlow2D::SegmentMotion:
+// flow2d_segment_motion_2d on the residual flow; with --backward the forward occlusion mask is left out) and prints one line
+// "Motion segmentation: {json}" -- "regions", "foreground", "dropped", "recorded" -- and one line "Region k: {json}" per recorded
+// region -- "area", "bbox" [x0, y0, x1, y1], "centroid" and "motion" (the mean residual motion in pixels) with 17 significant
+// digits --, and writes the labels as <prefix>labels-W-H.raw (32-bit integers).  The other files do not change; a run of its own.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -80,6 +86,9 @@ int main(int argc, char** argv)
     int global_model = -1;  // --global-motion MODEL (-1: off)
     double global_sigma = 0.5;
     int global_iterations = 5;
+    bool segment = false;  // --segment-motion THRESHOLD
+    float segment_threshold = 0.f, segment_join = INFINITY;
+    unsigned segment_min_area = 16;
     std::string ground_truth_file;
     int device = 0;
     float sor_omega = 0.f;
@@ -155,11 +164,41 @@ int main(int argc, char** argv)
             global_iterations = static_cast<int>(n);
             ++i;
         }
+        else if (!std::strcmp(argv[i], "--segment-motion") || !std::strcmp(argv[i], "--segment-join")) {
+            const bool is_join = !std::strcmp(argv[i], "--segment-join");
+            char* end = nullptr;
+            const float value = (i + 1 < argc) ? std::strtof(argv[i + 1], &end) : 0.f;
+            if (i + 1 >= argc || end == argv[i + 1] || *end != '\0' || !(value >= 0.f) || (!is_join && !std::isfinite(value))) {
+                std::printf(is_join ? "--segment-join takes a J >= 0 (pixels; inf: plain labelling).\n"
+                                    : "--segment-motion takes a finite THRESHOLD >= 0 (pixels).\n");
+                return 5;
+            }
+            if (is_join) segment_join = value;
+            else {
+                segment = true;
+                segment_threshold = value;
+            }
+            ++i;
+        }
+        else if (!std::strcmp(argv[i], "--segment-min-area")) {
+            char* end = nullptr;
+            const long n = (i + 1 < argc) ? std::strtol(argv[i + 1], &end, 10) : 0;
+            if (i + 1 >= argc || end == argv[i + 1] || *end != '\0' || n < 1 || n > 2147483647L) {
+                std::printf("--segment-min-area takes an integer A >= 1 (pixels).\n");
+                return 5;
+            }
+            segment_min_area = static_cast<unsigned>(n);
+            ++i;
+        }
         else if (!std::strcmp(argv[i], "--device") && i + 1 < argc) device = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--sor") && i + 1 < argc) sor_omega = static_cast<float>(std::atof(argv[++i]));
         else args.push_back(argv[i]);
     }
     const int nargs = static_cast<int>(args.size());
+    if (segment && global_model < 0) {
+        std::printf("--segment-motion needs --global-motion MODEL (the regions are those of the residual flow).\n");
+        return 5;
+    }
 
     if (!InitDeviceContext(device)) return 1;
     // the reference's ALLOCATE_PINNED_MEMORY option (data2d.cpp:34), on: frames and flows live in page-locked memory
@@ -395,6 +434,34 @@ int main(int argc, char** argv)
                       residual_v.WriteRAWToFileF32((output_path + counter + "residual-v" + suffix).c_str());
             if (write_flo) ok = ok && IOUtils::WriteFlowFLO(residual_u, residual_v, output_path + counter + "residual.flo");
             if (!ok) {
+                std::cerr << "Error: cannot save file " << std::endl;
+                std::exit(255);
+            }
+        }
+        if (segment) {
+            flow2d_global_motion motion;
+            flow2d_segment_summary summary;
+            std::vector<flow2d_motion_region> regions(OpticalFlow2D::kSegmentMaxRegions);
+            Data2D labels(width, height);
+            optical_flow.SegmentMotion(frame_0, frame_1, global_model, global_sigma, global_iterations, backward, segment_threshold,
+                                       segment_join, segment_min_area, &motion, &summary, regions.data(), params, &labels);
+            if (!optical_flow.LastRunSucceeded()) {
+                std::cout << "Error: the motion segmentation failed." << std::endl;
+                optical_flow.Destroy();
+                DestroyDeviceContext();
+                return 4;
+            }
+            std::printf("Motion segmentation: {\"regions\": %llu, \"foreground\": %llu, \"dropped\": %llu, \"recorded\": %u}\n",
+                        summary.region_count, summary.foreground, summary.dropped, summary.recorded);
+            for (unsigned k = 0; k < summary.recorded; ++k) {
+                const flow2d_motion_region& r = regions[k];
+                const double a = static_cast<double>(r.area);
+                std::printf("Region %u: {\"area\": %llu, \"bbox\": [%d, %d, %d, %d], \"centroid\": [%.17g, %.17g], "
+                            "\"motion\": [%.17g, %.17g]}\n",
+                            k + 1, r.area, r.x0, r.y0, r.x1, r.y1, static_cast<double>(r.sum_x) / a, static_cast<double>(r.sum_y) / a,
+                            static_cast<double>(r.sum_u_q16) / 65536.0 / a, static_cast<double>(r.sum_v_q16) / 65536.0 / a);
+            }
+            if (!labels.WriteRAWToFileF32((output_path + counter + "labels" + suffix).c_str())) {
                 std::cerr << "Error: cannot save file " << std::endl;
                 std::exit(255);
             }

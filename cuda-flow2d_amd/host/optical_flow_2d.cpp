@@ -247,6 +247,12 @@ void OpticalFlow2D::Destroy()
         tracking_scratch_bytes_ = 0;
         if (stabilise_scratch_) flow2d_plane_free(context_, AsPlane(stabilise_scratch_));
         stabilise_scratch_ = 0;
+        if (segment_scratch_) flow2d_plane_free(context_, AsPlane(segment_scratch_));
+        segment_scratch_ = 0;
+        for (DevicePtr& p : segment_planes_) {
+            if (p) flow2d_plane_free(context_, AsPlane(p));
+            p = 0;
+        }
         for (std::vector<DevicePtr>* planes : {&denoise_pairs_, &denoise_chains_, &stabilise_planes_}) {
             for (DevicePtr p : *planes)
                 if (p) flow2d_plane_free(context_, AsPlane(p));
@@ -862,6 +868,88 @@ void OpticalFlow2D::EstimateGlobalMotion(Data2D& frame_0, Data2D& frame_1, int m
         ok = ok && CopyData2DtoDevice(frame_0, d[0], H, pitch) && CopyData2DtoDevice(frame_1, d[1], H, pitch);
         ok = ok && EstimateGlobalMotionDevice(d[0], d[1], model, sigma, iterations, use_masks, motion_out, params, d[2], d[3], d[4], d[5]);
         for (int i = 2; ok && i < 6; ++i)
+            if (images[i]) ok = CopyData2DFromDevice(d[i], *images[i], H, pitch);
+    }
+    last_run_ok_ = ok;
+}
+
+bool OpticalFlow2D::SegmentMotionArgsOk(float threshold, float join, unsigned min_area)
+{
+    if (!(threshold >= 0.f) || !(join >= 0.f) || min_area == 0) {
+        std::printf("Error: motion segmentation takes a threshold >= 0 (%g), a join >= 0, infinity allowed (%g), and a min_area >= 1 (%u).\n",
+                    threshold, join, min_area);
+        return false;
+    }
+    return true;
+}
+
+bool OpticalFlow2D::SegmentMotionDevice(DevicePtr dev_frame_0, DevicePtr dev_frame_1, int model, double sigma, int iterations,
+                                        bool use_masks, float threshold, float join, unsigned min_area,
+                                        flow2d_global_motion* motion_out, flow2d_segment_summary* summary_out,
+                                        flow2d_motion_region* regions_out, OperationParameters& params, DevicePtr dev_labels,
+                                        DevicePtr dev_residual_u, DevicePtr dev_residual_v)
+{
+    if (!GlobalMotionArgsOk(model, sigma, iterations) || !SegmentMotionArgsOk(threshold, join, min_area)) return false;
+    if (!IsInitialized() || !dev_frame_0 || !dev_frame_1 || !motion_out || !summary_out) return false;
+    if ((dev_residual_u == 0) != (dev_residual_v == 0)) return false;
+    const size_t W = dev_container_size_.width, H = dev_container_size_.height, pitch = dev_container_size_.pitch;
+    constexpr size_t kTableOffset = 64;  // the summary comes first
+    const size_t table_bytes = kSegmentMaxRegions * sizeof(flow2d_motion_region);
+    const size_t workspace_bytes = flow2d_segment_motion_workspace_bytes(W, H, 1);
+    if (!EnsurePlanes(segment_planes_, 3)) return false;
+    if (!segment_scratch_ && !(segment_scratch_ = AllocBytes(kTableOffset + table_bytes + workspace_bytes))) return false;
+    // the flow, the fit and the residual planes (group_ > 1 is refused there); with use_masks the forward occlusion mask of
+    // the pair is still in the window's slot 0 afterwards
+    if (!EstimateGlobalMotionDevice(dev_frame_0, dev_frame_1, model, sigma, iterations, use_masks, motion_out, params, 0, 0,
+                                    segment_planes_[0], segment_planes_[1]))
+        return false;
+    char* scratch = reinterpret_cast<char*>(static_cast<uintptr_t>(segment_scratch_));
+    flow2d_segment_summary* summary = reinterpret_cast<flow2d_segment_summary*>(scratch);
+    flow2d_motion_region* table = reinterpret_cast<flow2d_motion_region*>(scratch + kTableOffset);
+    bool ok = !CheckFlow2DError(
+        flow2d_segment_motion_2d(context_, AsPlane(segment_planes_[0]), AsPlane(segment_planes_[1]),
+                                 use_masks ? AsPlane(stabilise_planes_[4]) : nullptr, W, H, pitch, threshold, join, min_area,
+                                 reinterpret_cast<int*>(AsPlane(segment_planes_[2])), table, kSegmentMaxRegions, summary,
+                                 scratch + kTableOffset + table_bytes, workspace_bytes),
+        "flow2d_segment_motion_2d");
+    ok = ok && !CheckFlow2DError(flow2d_copy_d2h_2d(context_, summary_out, sizeof(*summary_out), summary, sizeof(*summary_out),
+                                                    sizeof(*summary_out), 1),
+                                 "flow2d_copy_d2h_2d");
+    if (ok && regions_out)
+        ok = !CheckFlow2DError(flow2d_copy_d2h_2d(context_, regions_out, table_bytes, table, table_bytes, table_bytes, 1),
+                               "flow2d_copy_d2h_2d");
+    const void* src[3] = {AsPlane(segment_planes_[2]), AsPlane(segment_planes_[0]), AsPlane(segment_planes_[1])};
+    void* dst[3] = {AsPlane(dev_labels), AsPlane(dev_residual_u), AsPlane(dev_residual_v)};
+    if (ok && dev_labels) ok = !CheckFlow2DError(flow2d_copy_planes(context_, 1, src, dst, pitch, W, H), "flow2d_copy_planes");
+    if (ok && dev_residual_u)
+        ok = !CheckFlow2DError(flow2d_copy_planes(context_, 2, src + 1, dst + 1, pitch, W, H), "flow2d_copy_planes");
+    return !CheckFlow2DError(flow2d_synchronize(context_), "flow2d_synchronize") && ok;
+}
+
+void OpticalFlow2D::SegmentMotion(Data2D& frame_0, Data2D& frame_1, int model, double sigma, int iterations, bool use_masks,
+                                  float threshold, float join, unsigned min_area, flow2d_global_motion* motion_out,
+                                  flow2d_segment_summary* summary_out, flow2d_motion_region* regions_out,
+                                  OperationParameters& params, Data2D* labels, Data2D* residual_u, Data2D* residual_v)
+{
+    last_run_ok_ = false;
+    if (!GlobalMotionArgsOk(model, sigma, iterations) || !SegmentMotionArgsOk(threshold, join, min_area)) return;
+    if (!IsInitialized() || !motion_out || !summary_out || (residual_u == nullptr) != (residual_v == nullptr)) return;
+    const size_t H = dev_container_size_.height, pitch = dev_container_size_.pitch;
+    Data2D* images[5] = {&frame_0, &frame_1, labels, residual_u, residual_v};
+    Data2D* given[5];
+    size_t given_count = 0;
+    for (Data2D* d : images)
+        if (d) given[given_count++] = d;
+    if (!SizeCheck{dev_container_size_, GetName(), "frame / labels / residual"}(given, given_count)) return;
+    DevicePtr d[5] = {0, 0, 0, 0, 0};  // the planes of this call (freed at its end)
+    bool ok = EnsurePlanes(d, 5);
+    {
+        HostCall call(context_, last_total_ms_, {d, 5});
+        ok = ok && CopyData2DtoDevice(frame_0, d[0], H, pitch) && CopyData2DtoDevice(frame_1, d[1], H, pitch);
+        ok = ok && SegmentMotionDevice(d[0], d[1], model, sigma, iterations, use_masks, threshold, join, min_area, motion_out,
+                                       summary_out, regions_out, params, labels ? d[2] : 0, residual_u ? d[3] : 0,
+                                       residual_u ? d[4] : 0);
+        for (int i = 2; ok && i < 5; ++i)
             if (images[i]) ok = CopyData2DFromDevice(d[i], *images[i], H, pitch);
     }
     last_run_ok_ = ok;

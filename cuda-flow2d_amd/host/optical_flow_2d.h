@@ -210,6 +210,27 @@ public:
                            int iterations, bool use_masks, float fill, Data2D* outputs, flow2d_global_motion* motions_out,
                            OperationParameters& params);
 
+    // Motion segmentation of a pair (no reference counterpart): the flow frame_0 -> frame_1 (bidirectional with use_masks, as in
+    // EstimateGlobalMotion), flow2d_global_motion_2d, flow2d_global_flow_2d (the residual planes) and flow2d_segment_motion_2d on
+    // them -- with use_masks the forward occlusion mask also keeps its pixels out of the foreground.  threshold (>= 0), join (>= 0,
+    // +infinity allowed) and min_area (>= 1) are those of flow2d_segment_motion_2d; SegmentMotionArgsOk prints what is wrong and
+    // needs no device.  Returns the global-motion record, the summary and the first min(region_count, kSegmentMaxRegions) records
+    // (regions_out: kSegmentMaxRegions records, zero beyond the recorded ones).  The label plane (int labels in a container of
+    // the flow's pitch) and the residual planes stay on the device in dev_labels / dev_residual_u / dev_residual_v when given.
+    // The object's own planes, table and workspace are allocated at the first call and kept.  The call synchronises.  Not for
+    // lock-step groups.
+    static constexpr size_t kSegmentMaxRegions = 4096;
+    static bool SegmentMotionArgsOk(float threshold, float join, unsigned min_area);
+    bool SegmentMotionDevice(DevicePtr dev_frame_0, DevicePtr dev_frame_1, int model, double sigma, int iterations, bool use_masks,
+                             float threshold, float join, unsigned min_area, flow2d_global_motion* motion_out,
+                             flow2d_segment_summary* summary_out, flow2d_motion_region* regions_out, OperationParameters& params,
+                             DevicePtr dev_labels = 0, DevicePtr dev_residual_u = 0, DevicePtr dev_residual_v = 0);
+    // The host-image form (the CLI's --segment-motion): `labels` gets the int labels in its float storage, bit for bit.
+    void SegmentMotion(Data2D& frame_0, Data2D& frame_1, int model, double sigma, int iterations, bool use_masks, float threshold,
+                       float join, unsigned min_area, flow2d_global_motion* motion_out, flow2d_segment_summary* summary_out,
+                       flow2d_motion_region* regions_out, OperationParameters& params, Data2D* labels = nullptr,
+                       Data2D* residual_u = nullptr, Data2D* residual_v = nullptr);
+
     // When set, ComputeFlowDevice records the whole pyramid of a pair into a HIP graph the first time it
     // sees a (buffers, parameters) combination and replays it afterwards: one host call instead of
     // several hundred launches.  Ignored while timing_mode != 0 (events are not captured).
@@ -327,6 +348,10 @@ private:
     // the records of the flows frames[i] -> frames[i + 1], i < count - 1, of an ordered list of frames into records[i]
     bool FitConsecutivePairs(const DevicePtr* frames, size_t count, int model, double sigma, int iterations, bool use_masks,
                              flow2d_global_motion* records, OperationParameters& params);
+    // SegmentMotion*: residual u, residual v and labels, and in one allocation the summary, kSegmentMaxRegions records and the
+    // workspace (allocated on first use)
+    DevicePtr segment_planes_[3] = {0, 0, 0};
+    DevicePtr segment_scratch_ = 0;
     flow2d_context* context_ = nullptr;
     // One plane beside the pool: the warped frame of a level, when the levels of both frames are computed up front into plane
     // regions of their own (RunPyramid: "stacked" levels) and therefore cannot be overwritten by the warp

@@ -38,7 +38,8 @@ extern "C" {
  * flow2d_interpolate_2d (occlusion-aware frame interpolation), flow2d_track_points_2d / flow2d_seed_points_2d /
  * flow2d_seed_points_workspace_bytes (dense point trajectories), flow2d_denoise_2d / flow2d_compose_flow_2d
  * (motion-compensated temporal denoising) and flow2d_global_motion_2d / flow2d_global_motion_workspace_bytes /
- * flow2d_global_flow_2d / flow2d_warp_global_2d (robust global motion and stabilisation) were added under 1. */
+ * flow2d_global_flow_2d / flow2d_warp_global_2d (robust global motion and stabilisation) and flow2d_segment_motion_2d /
+ * flow2d_segment_motion_workspace_bytes (motion segmentation) were added under 1. */
 #define FLOW2D_ABI_VERSION 1
 
 typedef enum flow2d_status {
@@ -549,6 +550,83 @@ FLOW2D_API int flow2d_global_flow_2d(flow2d_context* ctx, const flow2d_global_mo
 FLOW2D_API int flow2d_warp_global_2d(flow2d_context* ctx, const flow2d_global_motion* motion /* device */, const float* frame,
                                      size_t width, size_t height, size_t pitch_bytes, float fill, float* output,
                                      float* valid /* may be NULL */);
+
+/* Motion segmentation: the independently moving regions of a residual flow, labelled on the device (no reference counterpart;
+ * added to ABI version 1 without changing any existing entry).  Connected components of the foreground of a residual flow --
+ * what flow2d_global_flow_2d writes as residual_u / residual_v --, numbered, with one record per region.
+ *
+ * Foreground.  All of this is fp32, each operation rounded on its own (no fused multiply-add).  Per pixel p:
+ *   ru = residual_u[p], rv = residual_v[p]
+ *   m  = mask ? mask[p] : 0;  if (!(m <= 1)) m = 1;  if (!(m >= 0)) m = 0        (the clamp of flow2d_global_motion_2d: NaN = 1)
+ *   fg(p) = (ru*ru + rv*rv > threshold*threshold) && (m < 0.5f)
+ * A NaN residual (an invalid vector of flow2d_global_flow_2d) fails the comparison and is background.
+ * Edges.  Two 4-neighbours p and q that are both foreground are joined when
+ *   (ru_p - ru_q)*(ru_p - ru_q) + (rv_p - rv_q)*(rv_p - rv_q) <= join*join
+ * join = +infinity joins every foreground neighbour pair with finite residuals (plain labelling); a finite join keeps two
+ * touching objects with different motions apart.  The relation is on edges: a component is a connected component of that
+ * graph, so a smooth ramp of residuals is one component even when its two ends differ by far more than `join`.
+ * Numbering.  A component's area is its pixel count; components with area < min_area become background (label 0).  The
+ * remaining regions are numbered 1, 2, ... in increasing order of their smallest linear index y*width + x.  `labels` is an
+ * int plane with the pitch and the batch stride of the float planes; it is always complete, even when there are more regions
+ * than max_regions.
+ * Records.  regions[k - 1] (DEVICE memory) describes region k for k <= max_regions: area, the sums of the pixel coordinates
+ * (centroid = sum / area, done by the caller), the sums over the region's pixels of
+ *   llrint((double)clamp(r, -32768.f, 32768.f) * 65536.0)         (round to nearest even; r = ru for sum_u_q16, rv for sum_v_q16)
+ * -- the mean residual motion as an exact integer sum, the same bytes in any order of addition; at 2^31 per pixel it cannot
+ * overflow below 2^31 pixels --, the inclusive bounding box and the smallest linear index.  Records from
+ * min(region_count, max_regions) up to max_regions are zero.  summary[0] (DEVICE memory): region_count (kept regions; may
+ * exceed max_regions), foreground (pixels with fg), dropped (foreground pixels in components below min_area), recorded =
+ * min(region_count, max_regions), reserved = 0.
+ * How: union-find with equivalence by smallest index.  Seven launches on the context's stream whatever the arguments: 64 x 16
+ * tiles labelled in LDS, the pairs across tile edges united, the tile roots flattened and the areas summed, the kept roots
+ * counted per band of 2048 consecutive indices, one workgroup per instance scanning the bands in order, the records of the
+ * roots written, and the labels written with the sums, boxes accumulated per tile in LDS first.  Integer atomics only -- min,
+ * max and add on 32- and 64-bit integers: they commute and associate, so the bytes do not depend on the order of arrival; no
+ * float atomic anywhere.  No workgroup waits for another.  No host round trip, no allocation, no synchronisation
+ * (graph-capturable); repeated calls, a replayed graph and an instance alone or in its batch give the same bytes.  Honours
+ * flow2d_context_set_batch: labels and planes at b * stride, regions + b * max_regions, summary + b, one workspace slice per
+ * instance.  `workspace` holds at least flow2d_segment_motion_workspace_bytes(width, height, instances) bytes (8 bytes per
+ * pixel and 32 per band), 16-byte aligned.
+ * FLOW2D_ERR_INVALID_ARGUMENT for a null plane, `labels`, `summary` or `workspace`, regions == NULL with max_regions > 0, a
+ * zero size, width*height >= 2^31, a bad pitch (the rule of flow2d_consistency_2d), a negative or NaN threshold, a negative or
+ * NaN join (+infinity is allowed), min_area == 0, a misaligned `regions` or `summary` (8) or `workspace` (16), a workspace too
+ * small, or a written range -- labels, table, summary, workspace, over every instance of a batch -- that overlaps an input
+ * plane or another written range. */
+typedef struct flow2d_motion_region {
+    unsigned long long area;          /* pixel count */
+    unsigned long long sum_x, sum_y;  /* sums of the pixel coordinates */
+    long long sum_u_q16, sum_v_q16;   /* sums of the residuals in units of 2^-16 pixel */
+    int x0, y0, x1, y1;               /* inclusive bounding box */
+    unsigned long long first;         /* smallest linear index y*width + x */
+} flow2d_motion_region;
+
+typedef struct flow2d_segment_summary {
+    unsigned long long region_count;  /* kept regions; may exceed max_regions */
+    unsigned long long foreground;    /* pixels with fg */
+    unsigned long long dropped;       /* foreground pixels in components below min_area */
+    unsigned recorded;                /* min(region_count, max_regions) */
+    unsigned reserved;                /* 0 */
+} flow2d_segment_summary;
+
+#define FLOW2D_MOTION_REGION_BYTES 64
+#define FLOW2D_SEGMENT_SUMMARY_BYTES 32
+#ifdef __cplusplus
+static_assert(sizeof(flow2d_motion_region) == FLOW2D_MOTION_REGION_BYTES, "flow2d_motion_region layout");
+static_assert(sizeof(flow2d_segment_summary) == FLOW2D_SEGMENT_SUMMARY_BYTES, "flow2d_segment_summary layout");
+#else
+_Static_assert(sizeof(flow2d_motion_region) == FLOW2D_MOTION_REGION_BYTES, "flow2d_motion_region layout");
+_Static_assert(sizeof(flow2d_segment_summary) == FLOW2D_SEGMENT_SUMMARY_BYTES, "flow2d_segment_summary layout");
+#endif
+
+/* Workspace bytes flow2d_segment_motion_2d needs for `instances` lock-step instances of a width x height plane (0 for a zero
+ * size; a multiple of 16).  Host logic only, needs no device. */
+FLOW2D_API size_t flow2d_segment_motion_workspace_bytes(size_t width, size_t height, size_t instances);
+FLOW2D_API int flow2d_segment_motion_2d(flow2d_context* ctx, const float* residual_u, const float* residual_v,
+                                        const float* mask /* may be NULL */, size_t width, size_t height, size_t pitch_bytes,
+                                        float threshold, float join, unsigned min_area, int* labels,
+                                        flow2d_motion_region* regions /* device, may be NULL iff max_regions == 0 */,
+                                        size_t max_regions, flow2d_segment_summary* summary /* device */, void* workspace,
+                                        size_t workspace_bytes);
 
 /* The flow of the previous pyramid level resampled to this level's size (the bits of flow2d_resample_xy_pair into out_u / out_v)
  * and frame_1 warped by it (the bits of flow2d_registration_2d into `output`) in one launch: replaces the
