@@ -9,6 +9,7 @@ The directory name carries a hyphen, so import it with
     importlib.import_module("cuda-flow2d_amd")
 """
 import ctypes as C
+import math
 import os
 import subprocess
 
@@ -180,6 +181,41 @@ MOTION_REGION_BYTES, SEGMENT_SUMMARY_BYTES = 64, 32  # FLOW2D_MOTION_REGION_BYTE
 assert C.sizeof(MotionRegion) == MOTION_REGION_BYTES and C.sizeof(SegmentSummary) == SEGMENT_SUMMARY_BYTES
 DEFAULT_MAX_REGIONS = 4096
 
+
+STRAIN_SMALL, STRAIN_GREEN_LAGRANGE = 0, 1  # flow2d_strain_measure
+# the planes of flow2d_deformation_2d in the order of flow2d_deformation_planes, and the quantities of its record in theirs
+DEFORMATION_PLANES = ("divergence", "vorticity", "dilatation", "exx", "eyy", "exy", "e1", "e2", "max_shear")
+DEFORMATION_STATS = ("divergence", "vorticity", "dilatation", "e1", "e2", "max_shear")
+
+
+class DeformationPlanes(C.Structure):
+    """flow2d_deformation_planes: a host struct of nine device pointers, NULL = not requested."""
+    _fields_ = [(name, C.c_void_p) for name in DEFORMATION_PLANES]
+
+
+class DeformationMoments(C.Structure):
+    """flow2d_deformation_moments: sum, sum of squares, min and max of one quantity over the valid pixels."""
+    _fields_ = [("sum", C.c_double), ("sum_sq", C.c_double), ("min", C.c_float), ("max", C.c_float)]
+
+
+class DeformationStats(C.Structure):
+    """flow2d_deformation_stats of include/flow2d_c_abi.h: what flow2d_deformation_2d writes per instance."""
+    _fields_ = ([("valid", C.c_ulonglong), ("invalid", C.c_ulonglong)] + [(name, DeformationMoments) for name in DEFORMATION_STATS] +
+                [("reserved", C.c_ulonglong * 12)])
+
+    def summary(self):
+        """{quantity: {"mean", "rms", "min", "max"}} over the valid pixels (None for an empty set), with "valid" and "invalid"."""
+        out = {"valid": self.valid, "invalid": self.invalid}
+        for name in DEFORMATION_STATS:
+            m = getattr(self, name)
+            out[name] = None if self.valid == 0 else {"mean": m.sum / self.valid, "rms": math.sqrt(m.sum_sq / self.valid),
+                                                      "min": m.min, "max": m.max}
+        return out
+
+
+DEFORMATION_STATS_BYTES = 256  # FLOW2D_DEFORMATION_STATS_BYTES, checked by a static_assert in the header
+assert C.sizeof(DeformationStats) == DEFORMATION_STATS_BYTES
+
 _hip = None
 
 
@@ -283,6 +319,10 @@ def hip_lib():
             L.flow2d_global_motion_2d.argtypes = [vp, vp, vp, vp, sz, sz, sz, i, d, i, vp, vp, sz]
             L.flow2d_global_flow_2d.argtypes = [vp, vp, vp, vp, vp, sz, sz, sz, d, vp, vp, vp, vp, vp]
             L.flow2d_warp_global_2d.argtypes = [vp, vp, vp, sz, sz, sz, f, vp, vp]
+        if hasattr(L, "flow2d_deformation_2d"):  # (absent from libraries of earlier rounds loaded for an A/B)
+            L.flow2d_deformation_workspace_bytes.restype = sz
+            L.flow2d_deformation_workspace_bytes.argtypes = [sz, sz, sz]
+            L.flow2d_deformation_2d.argtypes = [vp, vp, vp, vp, sz, sz, sz, i, C.POINTER(DeformationPlanes), vp, vp, sz]
         if hasattr(L, "flow2d_segment_motion_2d"):  # (absent from libraries of earlier rounds loaded for an A/B)
             L.flow2d_segment_motion_workspace_bytes.restype = sz
             L.flow2d_segment_motion_workspace_bytes.argtypes = [sz, sz, sz]
@@ -727,6 +767,56 @@ class Context:
                 self._planes.remove(q)
         return out
 
+    def deformation_records(self, instances=1):
+        """A Plane for `instances` flow2d_deformation_stats records (device memory)."""
+        return self.plane(instances * DEFORMATION_STATS_BYTES // 4, 1)
+
+    def read_deformation_stats(self, stats, instances=1):
+        """The records of a deformation_records Plane as DeformationStats structures (synchronises)."""
+        raw = stats.download(instances * DEFORMATION_STATS_BYTES // 4, 1)
+        return list((DeformationStats * instances).from_buffer_copy(raw.tobytes()))
+
+    def deformation(self, pu, pv, w, h, measure=STRAIN_SMALL, mask=None, planes=DEFORMATION_PLANES, stats=True, instances=1):
+        """How the flow (pu, pv) deforms the material (flow2d_deformation_2d): divergence, vorticity, dilatation, the strain
+        tensor of `measure` (STRAIN_SMALL or STRAIN_GREEN_LAGRANGE) and its principal values from differences that never reach
+        across a pixel with mask >= 0.5 or a non-finite vector; NaN where a pixel has no derivative.
+        planes: names from DEFORMATION_PLANES -- the call allocates those planes, downloads them and returns {name: [h, w]
+        array} --, or a {name: Plane} dict of the caller's device planes, which are written and stay on the device.
+        stats: True -- the record is read back (synchronises) --, a deformation_records Plane of the caller's, which is written
+        and stays on the device, or False / None.  Returns (planes dict, DeformationStats or None); with the caller's planes and
+        record nothing is downloaded or synchronised.  The workspace is the context's own (kept between calls)."""
+        L = hip_lib()
+        own_planes = not isinstance(planes, dict)
+        held = {name: self.plane(pu.width, pu.height) for name in planes} if own_planes else dict(planes)
+        unknown = [name for name in held if name not in DEFORMATION_PLANES]
+        if unknown:
+            raise ValueError("deformation planes are %s, not %s" % (", ".join(DEFORMATION_PLANES), unknown))
+        out = DeformationPlanes(**{name: q.ptr for name, q in held.items()})
+        own_stats = stats is True
+        if own_stats and instances != 1:
+            raise ValueError("a lock-step batch takes the caller's records")
+        record = self.deformation_records(instances) if own_stats else (stats or None)
+        workspace, need = None, 0
+        if record is not None:
+            need = L.flow2d_deformation_workspace_bytes(w, h, instances)
+            cached = getattr(self, "_deformation_workspace", None)
+            if cached is None or cached[0] < need:
+                if cached is not None:
+                    cached[1].free()
+                    self._planes.remove(cached[1])
+                self._deformation_workspace = cached = (need, self.plane(max(need // 4, 4), 1))
+            workspace = cached[1]
+        try:
+            _check(L.flow2d_deformation_2d(self.handle, pu.ptr, pv.ptr, mask.ptr if mask else None, w, h, pu.pitch, int(measure),
+                                           C.byref(out), record.ptr if record is not None else None,
+                                           workspace.ptr if workspace else None, need), "flow2d_deformation_2d")
+            result = {name: q.download(w, h) for name, q in held.items()} if own_planes else held
+            return result, (self.read_deformation_stats(record, 1)[0] if own_stats else None)
+        finally:
+            for q in (list(held.values()) if own_planes else []) + ([record] if own_stats else []):
+                q.free()
+                self._planes.remove(q)
+
     def resample_x(self, src, dst, out_w, out_h, in_w):
         _check(hip_lib().flow2d_resample_x(self.handle, src.ptr, dst.ptr, out_w, out_h, in_w, src.pitch),
                "flow2d_resample_x")
@@ -902,6 +992,12 @@ def host_lib():
             L.flow2d_host_stabilise_sequence.argtypes = [vp, fp, sz, sz, i, d, i, i, f, fp, gm, C.POINTER(HostParams), fp]
             L.flow2d_host_stabilise_sequence_device.argtypes = [vp, C.POINTER(vp), sz, sz, i, d, i, i, f, C.POINTER(vp), gm,
                                                                 C.POINTER(HostParams)]
+        if hasattr(L, "flow2d_host_analyse_deformation"):
+            L.flow2d_host_deformation_args_ok.argtypes = [i, f]
+            L.flow2d_host_analyse_deformation.argtypes = [vp, fp, fp, i, f, i, C.POINTER(fp), C.POINTER(DeformationStats),
+                                                          C.POINTER(HostParams), fp, fp, fp]
+            L.flow2d_host_analyse_deformation_device.argtypes = [vp, vp, vp, i, f, i, C.POINTER(vp), C.POINTER(DeformationStats),
+                                                                 C.POINTER(HostParams), vp, vp, vp]
         if hasattr(L, "flow2d_host_segment_motion"):
             d, u32 = C.c_double, C.c_uint
             head = [i, d, i, i, f, f, u32, C.POINTER(GlobalMotion), C.POINTER(SegmentSummary), C.POINTER(MotionRegion),
@@ -1237,6 +1333,48 @@ class OpticalFlow:
         if rc:
             raise Flow2DError(rc, "OpticalFlow2D::SegmentMotionDevice")
         return rec, summary, list(regions)[:summary.recorded]
+
+    def analyse_deformation(self, frame_0, frame_1, params, measure=STRAIN_SMALL, smoothing_sigma=0.0, masks=False,
+                            planes=DEFORMATION_PLANES, flow=False):
+        """OpticalFlow2D::AnalyseDeformation: how the material deforms between the host pair -- the flow frame_0 -> frame_1
+        (bidirectional with masks, the forward occlusion mask then keeping differences from reaching across an occlusion
+        boundary), a Gaussian of smoothing_sigma pixels over both flow planes when > 0, and flow2d_deformation_2d.  Returns
+        ({name: [h, w] array} for the names of `planes`, DeformationStats); with flow, also the (u, v) that was analysed."""
+        f0, f1 = (np.ascontiguousarray(a, np.float32) for a in (frame_0, frame_1))
+        if f0.shape != (self.height, self.width) or f1.shape != f0.shape:
+            raise ValueError("frames: [%d, %d]" % (self.height, self.width))
+        out = {name: np.empty_like(f0) for name in planes}
+        fp = C.POINTER(C.c_float)
+        table = (fp * 9)(*[_fptr(out[name]) if name in out else fp() for name in DEFORMATION_PLANES])
+        uv = [np.empty_like(f0) for _ in range(2)] if flow else [None, None]
+        opt = lambda a: None if a is None else _fptr(a)  # noqa: E731
+        stats = DeformationStats()
+        rc = host_lib().flow2d_host_analyse_deformation(self.handle, _fptr(f0), _fptr(f1), int(measure), float(smoothing_sigma),
+                                                        int(bool(masks)), table, C.byref(stats), C.byref(params), opt(uv[0]),
+                                                        opt(uv[1]), None)
+        if rc:
+            raise Flow2DError(rc, "OpticalFlow2D::AnalyseDeformation")
+        return (out, stats, tuple(uv)) if flow else (out, stats)
+
+    def analyse_deformation_device(self, dev_frame_0, dev_frame_1, params, measure=STRAIN_SMALL, smoothing_sigma=0.0, masks=False,
+                                   dev_planes=None, stats=True, dev_flow=None, dev_mask=None):
+        """OpticalFlow2D::AnalyseDeformationDevice: two device frames in; dev_planes = {name: device address} of the planes
+        wanted (names from DEFORMATION_PLANES), dev_flow (a (u, v) pair) and dev_mask: optional device planes for the flow that
+        was analysed and the occlusion mask.  Returns the DeformationStats (None without stats); synchronises."""
+        dev_planes = dev_planes or {}
+        unknown = [name for name in dev_planes if name not in DEFORMATION_PLANES]
+        if unknown:
+            raise ValueError("deformation planes are %s, not %s" % (", ".join(DEFORMATION_PLANES), unknown))
+        table = (C.c_void_p * 9)(*[dev_planes.get(name) for name in DEFORMATION_PLANES])
+        record = DeformationStats() if stats else None
+        fl = dev_flow or (None, None)
+        rc = host_lib().flow2d_host_analyse_deformation_device(self.handle, dev_frame_0, dev_frame_1, int(measure),
+                                                               float(smoothing_sigma), int(bool(masks)), table,
+                                                               C.byref(record) if stats else None, C.byref(params), fl[0], fl[1],
+                                                               dev_mask)
+        if rc:
+            raise Flow2DError(rc, "OpticalFlow2D::AnalyseDeformationDevice")
+        return record
 
     def stabilise_sequence(self, frames, params, reference_index=0, model=MOTION_AFFINE, sigma=0.5, iterations=5, masks=False,
                            fill=0.0):

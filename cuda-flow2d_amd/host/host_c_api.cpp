@@ -473,6 +473,71 @@ HOST_API int flow2d_host_segment_motion_device(flow2d_host_flow* h, void* dev_fr
                : 2;
 }
 
+// OpticalFlow2D::DeformationArgsOk: 1 when measure and smoothing_sigma are what AnalyseDeformation accepts.  Needs no device.
+HOST_API int flow2d_host_deformation_args_ok(int measure, float smoothing_sigma)
+{
+    return OpticalFlow2D::DeformationArgsOk(measure, smoothing_sigma) ? 1 : 0;
+}
+
+// OpticalFlow2D::AnalyseDeformation on tight host images: planes = nine pointers in the order of flow2d_deformation_planes (each
+// may be null, as may the array), width*height floats each; stats (optional) gets the record, flow_u / flow_v (optional) the flow
+// that was analysed, mask (optional, use_masks only) the occlusion mask.  0 on success, 1 for a null or refused argument, 2 when
+// the run delivered nothing.
+HOST_API int flow2d_host_analyse_deformation(flow2d_host_flow* h, const float* frame_0, const float* frame_1, int measure,
+                                             float smoothing_sigma, int use_masks, float* const* planes,
+                                             flow2d_deformation_stats* stats, const flow2d_host_params* params, float* flow_u,
+                                             float* flow_v, float* mask)
+{
+    if (!OpticalFlow2D::DeformationArgsOk(measure, smoothing_sigma) || !h || !frame_0 || !frame_1 || !params ||
+        (flow_u == nullptr) != (flow_v == nullptr) || (mask && !use_masks))
+        return 1;
+    const size_t n = h->width * h->height;
+    Data2D f0(h->width, h->height), f1(h->width, h->height);
+    std::memcpy(f0.DataPtr(), frame_0, n * sizeof(float));
+    std::memcpy(f1.DataPtr(), frame_1, n * sizeof(float));
+    float* dst[12] = {flow_u, flow_v, mask};
+    for (int k = 0; k < 9; ++k) dst[3 + k] = planes ? planes[k] : nullptr;
+    std::vector<Data2D> out;
+    out.reserve(12);
+    Data2D* images[12];
+    for (int i = 0; i < 12; ++i) {
+        images[i] = nullptr;
+        if (!dst[i]) continue;
+        out.emplace_back(h->width, h->height);
+        images[i] = &out.back();
+    }
+    flow2d_host_params p = *params;
+    OperationParameters bag;
+    FillBag(bag, p);
+    h->flow.AnalyseDeformation(f0, f1, measure, smoothing_sigma, use_masks != 0, images + 3, stats, bag, images[0], images[1], images[2]);
+    if (h->flow.LastRunSucceeded())
+        for (int i = 0; i < 12; ++i)
+            if (dst[i]) std::memcpy(dst[i], images[i]->DataPtr(), n * sizeof(float));
+    return h->flow.LastRunSucceeded() ? 0 : 2;
+}
+
+// OpticalFlow2D::AnalyseDeformationDevice: two device frames; dev_planes = nine device planes (each may be null, as may the
+// array); the optional device planes get the analysed flow and the mask.  Synchronises.  0 on success, 1 for a null or refused
+// argument.
+HOST_API int flow2d_host_analyse_deformation_device(flow2d_host_flow* h, void* dev_frame_0, void* dev_frame_1, int measure,
+                                                    float smoothing_sigma, int use_masks, void* const* dev_planes,
+                                                    flow2d_deformation_stats* stats, const flow2d_host_params* params,
+                                                    void* dev_flow_u, void* dev_flow_v, void* dev_mask)
+{
+    if (!OpticalFlow2D::DeformationArgsOk(measure, smoothing_sigma) || !h || !dev_frame_0 || !dev_frame_1 || !params) return 1;
+    flow2d_host_params p = *params;
+    OperationParameters bag;
+    FillBag(bag, p);
+    h->flow.timing_mode = 0;
+    auto dp = [](void* q) { return static_cast<DevicePtr>(reinterpret_cast<uintptr_t>(q)); };
+    DevicePtr planes[9];
+    for (int k = 0; k < 9; ++k) planes[k] = dev_planes ? dp(dev_planes[k]) : 0;
+    return h->flow.AnalyseDeformationDevice(dp(dev_frame_0), dp(dev_frame_1), measure, smoothing_sigma, use_masks != 0, planes, stats,
+                                            bag, dp(dev_flow_u), dp(dev_flow_v), dp(dev_mask))
+               ? 0
+               : 2;
+}
+
 // OpticalFlow2D::StabiliseSequence on tight host images: frames = frame_count * width * height floats (frame k at k * width *
 // height); outputs get the same layout, motions (optional) frame_count records.  0 on success, 1 for a null or refused argument,
 // 2 when the run delivered no frames.

@@ -43,6 +43,13 @@
 // "Motion segmentation: {json}" -- "regions", "foreground", "dropped", "recorded" -- and one line "Region k: {json}" per recorded
 // region -- "area", "bbox" [x0, y0, x1, y1], "centroid" and "motion" (the mean residual motion in pixels) with 17 significant
 // digits --, and writes the labels as <prefix>labels-W-H.raw (32-bit integers).  The other files do not change; a run of its own.
+// --deformation [--strain small|green, default small] [--deformation-sigma S, a number in [0, 8.66] in pixels, default 0: no
+// smoothing] also analyses how the material deforms between the two frames (OpticalFlow2D::AnalyseDeformation: the forward flow,
+// smoothed by a Gaussian of S pixels when S > 0, through flow2d_deformation_2d; with --backward the forward occlusion mask keeps
+// differences from reaching across an occlusion boundary), writes the nine planes as <prefix>divergence-W-H.raw, vorticity,
+// dilatation, exx, eyy, exy, e1, e2 and max-shear likewise (F32, NaN where a pixel has no derivative) and prints one line
+// "Deformation: {json}" -- "measure", "sigma", "valid", "invalid" and per quantity "mean", "rms", "min", "max" with 17 significant
+// digits.  The other files do not change; a run of its own.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -89,6 +96,9 @@ int main(int argc, char** argv)
     bool segment = false;  // --segment-motion THRESHOLD
     float segment_threshold = 0.f, segment_join = INFINITY;
     unsigned segment_min_area = 16;
+    bool deformation = false;  // --deformation
+    int strain_measure = FLOW2D_STRAIN_SMALL;
+    float deformation_sigma = 0.f;
     std::string ground_truth_file;
     int device = 0;
     float sor_omega = 0.f;
@@ -188,6 +198,26 @@ int main(int argc, char** argv)
                 return 5;
             }
             segment_min_area = static_cast<unsigned>(n);
+            ++i;
+        }
+        else if (!std::strcmp(argv[i], "--deformation")) deformation = true;
+        else if (!std::strcmp(argv[i], "--strain")) {
+            if (i + 1 < argc && !std::strcmp(argv[i + 1], "small")) strain_measure = FLOW2D_STRAIN_SMALL;
+            else if (i + 1 < argc && !std::strcmp(argv[i + 1], "green")) strain_measure = FLOW2D_STRAIN_GREEN_LAGRANGE;
+            else {
+                std::printf("--strain takes small or green (the small-strain tensor or the Green-Lagrange one).\n");
+                return 5;
+            }
+            ++i;
+        }
+        else if (!std::strcmp(argv[i], "--deformation-sigma")) {
+            char* end = nullptr;
+            const float value = (i + 1 < argc) ? std::strtof(argv[i + 1], &end) : 0.f;
+            if (i + 1 >= argc || end == argv[i + 1] || *end != '\0' || !(value >= 0.f) || !(value < 26.f / 3.f)) {
+                std::printf("--deformation-sigma takes an S in [0, 8.66] (pixels; 0: no smoothing).\n");
+                return 5;
+            }
+            deformation_sigma = value;
             ++i;
         }
         else if (!std::strcmp(argv[i], "--device") && i + 1 < argc) device = std::atoi(argv[++i]);
@@ -465,6 +495,36 @@ int main(int argc, char** argv)
                 std::cerr << "Error: cannot save file " << std::endl;
                 std::exit(255);
             }
+        }
+        if (deformation) {
+            static const char* const kNames[9] = {"divergence", "vorticity", "dilatation", "exx", "eyy", "exy", "e1", "e2", "max-shear"};
+            std::vector<Data2D> planes;
+            for (int k = 0; k < 9; ++k) planes.emplace_back(width, height);
+            Data2D* wanted[9];
+            for (int k = 0; k < 9; ++k) wanted[k] = &planes[k];
+            flow2d_deformation_stats stats;
+            optical_flow.AnalyseDeformation(frame_0, frame_1, strain_measure, deformation_sigma, backward, wanted, &stats, params);
+            if (!optical_flow.LastRunSucceeded()) {
+                std::cout << "Error: the deformation analysis failed." << std::endl;
+                optical_flow.Destroy();
+                DestroyDeviceContext();
+                return 4;
+            }
+            std::printf("Deformation: {\"measure\": \"%s\", \"sigma\": %.9g, \"valid\": %llu, \"invalid\": %llu",
+                        strain_measure == FLOW2D_STRAIN_SMALL ? "small" : "green", deformation_sigma, stats.valid, stats.invalid);
+            const flow2d_deformation_moments* moments[6] = {&stats.divergence, &stats.vorticity, &stats.dilatation,
+                                                            &stats.e1,         &stats.e2,        &stats.max_shear};
+            static const char* const kStatNames[6] = {"divergence", "vorticity", "dilatation", "e1", "e2", "max_shear"};
+            const double n = stats.valid ? static_cast<double>(stats.valid) : 1.0;
+            for (int k = 0; k < 6; ++k)
+                std::printf(", \"%s\": {\"mean\": %.17g, \"rms\": %.17g, \"min\": %.9g, \"max\": %.9g}", kStatNames[k],
+                            moments[k]->sum / n, std::sqrt(moments[k]->sum_sq / n), moments[k]->min, moments[k]->max);
+            std::printf("}\n");
+            for (int k = 0; k < 9; ++k)
+                if (!planes[k].WriteRAWToFileF32((output_path + counter + kNames[k] + suffix).c_str())) {
+                    std::cerr << "Error: cannot save file " << std::endl;
+                    std::exit(255);
+                }
         }
         if (!ground_truth_file.empty()) {
             flow2d_flow_error_stats stats;

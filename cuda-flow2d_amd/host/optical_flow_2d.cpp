@@ -253,6 +253,12 @@ void OpticalFlow2D::Destroy()
             if (p) flow2d_plane_free(context_, AsPlane(p));
             p = 0;
         }
+        if (deformation_scratch_) flow2d_plane_free(context_, AsPlane(deformation_scratch_));
+        deformation_scratch_ = 0;
+        for (DevicePtr& p : deformation_planes_) {
+            if (p) flow2d_plane_free(context_, AsPlane(p));
+            p = 0;
+        }
         for (std::vector<DevicePtr>* planes : {&denoise_pairs_, &denoise_chains_, &stabilise_planes_}) {
             for (DevicePtr p : *planes)
                 if (p) flow2d_plane_free(context_, AsPlane(p));
@@ -950,6 +956,103 @@ void OpticalFlow2D::SegmentMotion(Data2D& frame_0, Data2D& frame_1, int model, d
                                        summary_out, regions_out, params, labels ? d[2] : 0, residual_u ? d[3] : 0,
                                        residual_u ? d[4] : 0);
         for (int i = 2; ok && i < 5; ++i)
+            if (images[i]) ok = CopyData2DFromDevice(d[i], *images[i], H, pitch);
+    }
+    last_run_ok_ = ok;
+}
+
+bool OpticalFlow2D::DeformationArgsOk(int measure, float smoothing_sigma)
+{
+    // (the blur runs with up to 51 taps, 3 sigma to each side: flow2d_gaussian_kernel)
+    if ((measure != FLOW2D_STRAIN_SMALL && measure != FLOW2D_STRAIN_GREEN_LAGRANGE) || !(smoothing_sigma >= 0.f) ||
+        !(smoothing_sigma < 26.f / 3.f)) {
+        std::printf("Error: deformation analysis takes a strain measure 0 (small) or 1 (Green-Lagrange) (%d) and a smoothing sigma in [0, 8.66] (%g).\n",
+                    measure, smoothing_sigma);
+        return false;
+    }
+    return true;
+}
+
+bool OpticalFlow2D::AnalyseDeformationDevice(DevicePtr dev_frame_0, DevicePtr dev_frame_1, int measure, float smoothing_sigma,
+                                             bool use_masks, const DevicePtr* dev_planes, flow2d_deformation_stats* stats_out,
+                                             OperationParameters& params, DevicePtr dev_flow_u, DevicePtr dev_flow_v,
+                                             DevicePtr dev_mask)
+{
+    if (!DeformationArgsOk(measure, smoothing_sigma)) return false;
+    if (!IsInitialized() || !dev_frame_0 || !dev_frame_1 || (dev_flow_u == 0) != (dev_flow_v == 0) || (dev_mask && !use_masks))
+        return false;
+    flow2d_deformation_planes out = {};
+    float** slots[9] = {&out.divergence, &out.vorticity, &out.dilatation, &out.exx, &out.eyy, &out.exy, &out.e1, &out.e2, &out.max_shear};
+    bool any = stats_out != nullptr;
+    for (int k = 0; dev_planes && k < 9; ++k) {
+        *slots[k] = AsPlane(dev_planes[k]);
+        any = any || dev_planes[k];
+    }
+    if (!any) return false;
+    const size_t W = dev_container_size_.width, H = dev_container_size_.height, pitch = dev_container_size_.pitch;
+    const bool smooth = smoothing_sigma > 0.f;
+    DevicePtr* p = deformation_planes_;
+    if (!EnsurePlanes(p, use_masks ? 6 : 2) || (smooth && !EnsurePlanes(p + 6, 2))) return false;
+    constexpr size_t kWorkspaceOffset = sizeof(flow2d_deformation_stats);  // the record comes first
+    const size_t workspace_bytes = flow2d_deformation_workspace_bytes(W, H, 1);
+    if (stats_out && !deformation_scratch_ && !(deformation_scratch_ = AllocBytes(kWorkspaceOffset + workspace_bytes))) return false;
+    // (group_ > 1 is refused by both)
+    const DevicePtr frames[2] = {dev_frame_0, dev_frame_1};
+    if (!(use_masks ? ComputeFlowBidirectionalDevice(frames, 2, p, p + 1, p + 2, p + 3, p + 4, p + 5, params)
+                    : ComputeFlowSequenceDevice(frames, 2, p, p + 1, params)))
+        return false;
+    bool ok = true;
+    if (smooth) {
+        float taps[51];
+        int radius = 0;
+        ok = !CheckFlow2DError(flow2d_gaussian_kernel(smoothing_sigma, taps, &radius), "flow2d_gaussian_kernel");
+        for (int i = 0; ok && i < 2; ++i)
+            ok = !CheckFlow2DError(flow2d_gaussian_blur(context_, AsPlane(p[6 + i]), AsPlane(p[i]), W, H, pitch, taps, radius),
+                                   "flow2d_gaussian_blur");
+    }
+    const DevicePtr* flow = smooth ? p + 6 : p;
+    char* scratch = reinterpret_cast<char*>(static_cast<uintptr_t>(deformation_scratch_));
+    flow2d_deformation_stats* record = stats_out ? reinterpret_cast<flow2d_deformation_stats*>(scratch) : nullptr;
+    ok = ok && !CheckFlow2DError(flow2d_deformation_2d(context_, AsPlane(flow[0]), AsPlane(flow[1]), use_masks ? AsPlane(p[4]) : nullptr,
+                                                       W, H, pitch, measure, &out, record,
+                                                       stats_out ? scratch + kWorkspaceOffset : nullptr, workspace_bytes),
+                                 "flow2d_deformation_2d");
+    if (ok && stats_out)
+        ok = !CheckFlow2DError(flow2d_copy_d2h_2d(context_, stats_out, sizeof(*stats_out), record, sizeof(*stats_out),
+                                                  sizeof(*stats_out), 1),
+                               "flow2d_copy_d2h_2d");
+    const void* src[3] = {AsPlane(flow[0]), AsPlane(flow[1]), AsPlane(p[4])};
+    void* dst[3] = {AsPlane(dev_flow_u), AsPlane(dev_flow_v), AsPlane(dev_mask)};
+    if (ok && dev_flow_u) ok = !CheckFlow2DError(flow2d_copy_planes(context_, 2, src, dst, pitch, W, H), "flow2d_copy_planes");
+    if (ok && dev_mask) ok = !CheckFlow2DError(flow2d_copy_planes(context_, 1, src + 2, dst + 2, pitch, W, H), "flow2d_copy_planes");
+    return !CheckFlow2DError(flow2d_synchronize(context_), "flow2d_synchronize") && ok;
+}
+
+void OpticalFlow2D::AnalyseDeformation(Data2D& frame_0, Data2D& frame_1, int measure, float smoothing_sigma, bool use_masks,
+                                       Data2D* const* planes, flow2d_deformation_stats* stats_out, OperationParameters& params,
+                                       Data2D* flow_u, Data2D* flow_v, Data2D* mask)
+{
+    last_run_ok_ = false;
+    if (!DeformationArgsOk(measure, smoothing_sigma)) return;
+    if (!IsInitialized() || (flow_u == nullptr) != (flow_v == nullptr) || (mask && !use_masks)) return;
+    const size_t H = dev_container_size_.height, pitch = dev_container_size_.pitch;
+    Data2D* images[14] = {&frame_0, &frame_1, flow_u, flow_v, mask};
+    for (int k = 0; k < 9; ++k) images[5 + k] = planes ? planes[k] : nullptr;
+    Data2D* given[14];
+    size_t given_count = 0;
+    for (Data2D* d : images)
+        if (d) given[given_count++] = d;
+    if (!SizeCheck{dev_container_size_, GetName(), "frame / flow / deformation"}(given, given_count)) return;
+    // the planes of this call (freed at its end): only those that are asked for
+    DevicePtr d[14] = {};
+    bool ok = true;
+    for (int i = 0; ok && i < 14; ++i)
+        if (images[i]) ok = EnsurePlanes(d + i, 1);
+    {
+        HostCall call(context_, last_total_ms_, {d, 14});
+        ok = ok && CopyData2DtoDevice(frame_0, d[0], H, pitch) && CopyData2DtoDevice(frame_1, d[1], H, pitch);
+        ok = ok && AnalyseDeformationDevice(d[0], d[1], measure, smoothing_sigma, use_masks, d + 5, stats_out, params, d[2], d[3], d[4]);
+        for (int i = 2; ok && i < 14; ++i)
             if (images[i]) ok = CopyData2DFromDevice(d[i], *images[i], H, pitch);
     }
     last_run_ok_ = ok;

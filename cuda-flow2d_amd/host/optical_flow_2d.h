@@ -231,6 +231,25 @@ public:
                        flow2d_motion_region* regions_out, OperationParameters& params, Data2D* labels = nullptr,
                        Data2D* residual_u = nullptr, Data2D* residual_v = nullptr);
 
+    // Deformation analysis of a pair (no reference counterpart): the flow frame_0 -> frame_1 (ComputeFlowDevice's bits; with
+    // use_masks through ComputeFlowBidirectionalDevice, the forward occlusion mask then being the `mask` of the analysis),
+    // optionally flow2d_gaussian_blur of both flow planes with smoothing_sigma > 0 into planes of the object's own (a computed
+    // flow is noisy at the pixel scale and strain differentiates that noise: the sigma is the caller's resolution choice; 0 =
+    // off), and flow2d_deformation_2d.  measure: flow2d_strain_measure.  dev_planes: nine device planes in the order of
+    // flow2d_deformation_planes, 0 = not wanted (the array itself may be null); stats_out (host, optional) gets the record.
+    // dev_flow_u / dev_flow_v (optional) get the flow that was analysed -- the smoothed one when there is a sigma --, dev_mask
+    // (optional, use_masks only) the occlusion mask.  DeformationArgsOk prints what is wrong and needs no device.  The object's own
+    // planes, record and workspace are allocated at the first call and kept.  The call synchronises.  Not for lock-step groups.
+    static bool DeformationArgsOk(int measure, float smoothing_sigma);
+    bool AnalyseDeformationDevice(DevicePtr dev_frame_0, DevicePtr dev_frame_1, int measure, float smoothing_sigma, bool use_masks,
+                                  const DevicePtr* dev_planes, flow2d_deformation_stats* stats_out, OperationParameters& params,
+                                  DevicePtr dev_flow_u = 0, DevicePtr dev_flow_v = 0, DevicePtr dev_mask = 0);
+    // The host-image form (the CLI's --deformation): planes = nine images in the order of flow2d_deformation_planes, null = not
+    // wanted.  LastRunSucceeded and LastTotalMs as for ComputeFlow.
+    void AnalyseDeformation(Data2D& frame_0, Data2D& frame_1, int measure, float smoothing_sigma, bool use_masks,
+                            Data2D* const* planes, flow2d_deformation_stats* stats_out, OperationParameters& params,
+                            Data2D* flow_u = nullptr, Data2D* flow_v = nullptr, Data2D* mask = nullptr);
+
     // When set, ComputeFlowDevice records the whole pyramid of a pair into a HIP graph the first time it
     // sees a (buffers, parameters) combination and replays it afterwards: one host call instead of
     // several hundred launches.  Ignored while timing_mode != 0 (events are not captured).
@@ -352,6 +371,10 @@ private:
     // workspace (allocated on first use)
     DevicePtr segment_planes_[3] = {0, 0, 0};
     DevicePtr segment_scratch_ = 0;
+    // AnalyseDeformation*: the pair's flow (u, v, back u, back v, occlusion forward, occlusion backward; the last four with
+    // use_masks only), the smoothed flow (u, v; with a sigma only) and, in one allocation, the record and the workspace
+    DevicePtr deformation_planes_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    DevicePtr deformation_scratch_ = 0;
     flow2d_context* context_ = nullptr;
     // One plane beside the pool: the warped frame of a level, when the levels of both frames are computed up front into plane
     // regions of their own (RunPyramid: "stacked" levels) and therefore cannot be overwritten by the warp

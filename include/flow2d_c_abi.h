@@ -38,8 +38,9 @@ extern "C" {
  * flow2d_interpolate_2d (occlusion-aware frame interpolation), flow2d_track_points_2d / flow2d_seed_points_2d /
  * flow2d_seed_points_workspace_bytes (dense point trajectories), flow2d_denoise_2d / flow2d_compose_flow_2d
  * (motion-compensated temporal denoising) and flow2d_global_motion_2d / flow2d_global_motion_workspace_bytes /
- * flow2d_global_flow_2d / flow2d_warp_global_2d (robust global motion and stabilisation) and flow2d_segment_motion_2d /
- * flow2d_segment_motion_workspace_bytes (motion segmentation) were added under 1. */
+ * flow2d_global_flow_2d / flow2d_warp_global_2d (robust global motion and stabilisation), flow2d_segment_motion_2d /
+ * flow2d_segment_motion_workspace_bytes (motion segmentation) and flow2d_deformation_2d / flow2d_deformation_workspace_bytes
+ * (strain, divergence and vorticity of a flow) were added under 1. */
 #define FLOW2D_ABI_VERSION 1
 
 typedef enum flow2d_status {
@@ -627,6 +628,98 @@ FLOW2D_API int flow2d_segment_motion_2d(flow2d_context* ctx, const float* residu
                                         flow2d_motion_region* regions /* device, may be NULL iff max_regions == 0 */,
                                         size_t max_regions, flow2d_segment_summary* summary /* device */, void* workspace,
                                         size_t workspace_bytes);
+
+/* Deformation analysis: how the material a flow describes deforms -- divergence, vorticity, dilatation and the strain tensor
+ * with its principal values, from masked differences of the flow (no reference counterpart; added to ABI version 1 without
+ * changing any existing entry).  All arithmetic is fp32, every operation rounded on its own (no fused multiply-add), in the
+ * order written; sqrtf is correctly rounded.
+ *
+ * Validity.  For a pixel q inside the frame, with u_q = flow_u[q], v_q = flow_v[q]:
+ *   m     = mask ? mask[q] : 0;  if (!(m <= 1)) m = 1;  if (!(m >= 0)) m = 0         (the clamp of flow2d_global_motion_2d: NaN = 1;
+ *           `mask` is 1 where the vector is to be left out, as flow2d_consistency_2d writes it)
+ *   ok(q) = |u_q| <= 1e9 and |v_q| <= 1e9 and (mask == NULL or m < 0.5f)             (a NaN or an infinity fails)
+ * A pixel outside the frame is not ok.
+ * Masked differences.  For f in {u, v} at p = (x, y), with L = ok(x-1, y) and R = ok(x+1, y):
+ *   L and R:   f_x = (f[x+1] - f[x-1]) * 0.5f
+ *   R only:    f_x = f[x+1] - f[x]
+ *   L only:    f_x = f[x] - f[x-1]
+ *   neither:   no derivative
+ * and f_y likewise from (x, y-1) and (x, y+1).  A pixel is valid when ok(p) holds and both axes have a derivative; on an
+ * unmasked finite flow this is numpy.gradient(f, edge_order=1) evaluated in fp32.  No difference takes a vector that is not ok
+ * into a result: what the caller masked out, and a NaN or an infinity, stay where they are.
+ * Quantities.  With a = u_x, b = u_y, c = v_x, d = v_y at a valid pixel:
+ *   divergence = a + d
+ *   vorticity  = c - b
+ *   dilatation = (a + d) + (a*d - b*c)                  (det F - 1 with F = I + grad w: the relative change of area)
+ *   measure == FLOW2D_STRAIN_SMALL:           exx = a,  eyy = d,  exy = 0.5f*(b + c)
+ *   measure == FLOW2D_STRAIN_GREEN_LAGRANGE:  exx = a + 0.5f*(a*a + c*c),  eyy = d + 0.5f*(b*b + d*d),
+ *                                             exy = 0.5f*((b + c) + (a*b + c*d))               (E = (F^T F - I) / 2)
+ *   mean = 0.5f*(exx + eyy),  half = 0.5f*(exx - eyy),  max_shear = sqrtf(half*half + exy*exy)
+ *   e1 = mean + max_shear,  e2 = mean - max_shear       (the principal strains, e1 >= e2)
+ * Outputs.  `out` is a HOST struct of nine device pointers, each of which may be NULL; a requested plane gets its quantity at
+ * every valid pixel and NaN (0x7fc00000) at every other pixel of width x height.  Row padding and the container beyond
+ * width x height are neither read into a result nor written.  stats[b] (DEVICE memory, may be NULL) gets the record of instance
+ * b of a lock-step batch: the counts of valid and invalid pixels and, for each of divergence, vorticity, dilatation, e1, e2 and
+ * max_shear over the valid pixels, sum and sum_sq (= the sum of (double)x * (double)x) in double, min and max (updated by
+ * x < min and x > max from +inf and -inf; 0 for an empty set); the reserved bytes are 0.  At least one plane or `stats` is
+ * required.
+ * Deterministic: per workgroup of 64 columns x 16 rows a slab of partial sums in the caller's `workspace`, in a fixed order, then
+ * one workgroup per instance adds the slabs in block order; no atomics.  The grid depends only on (width, height), so repeated
+ * calls, a replayed graph and an instance alone or in its batch give the same bytes.  Two launches on the context's stream, one
+ * when stats == NULL (the workspace is then not used and may be NULL); no allocation, no synchronisation, no host round trip
+ * (graph-capturable).  `workspace` holds at least flow2d_deformation_workspace_bytes(width, height, instances) bytes, 16-byte
+ * aligned.  Honours flow2d_context_set_batch: planes at b * stride, stats + b.
+ * FLOW2D_ERR_INVALID_ARGUMENT for a null flow plane, out == NULL with stats == NULL or an `out` with no plane and no stats,
+ * width < 2 or height < 2 (no derivative exists), a bad pitch (the rule of flow2d_consistency_2d), an unknown measure, a
+ * misaligned `stats` (8) or `workspace` (16), a null or too small workspace when stats != NULL, or a written range -- a
+ * requested plane, the records, the workspace, over every instance of a batch -- that overlaps an input plane or another
+ * written range. */
+typedef enum flow2d_strain_measure {
+    FLOW2D_STRAIN_SMALL = 0,
+    FLOW2D_STRAIN_GREEN_LAGRANGE = 1
+} flow2d_strain_measure;
+
+typedef struct flow2d_deformation_planes {
+    float* divergence;
+    float* vorticity;
+    float* dilatation;
+    float* exx;
+    float* eyy;
+    float* exy;
+    float* e1;
+    float* e2;
+    float* max_shear;
+} flow2d_deformation_planes;
+
+typedef struct flow2d_deformation_moments {
+    double sum;
+    double sum_sq; /* sum of (double)x * (double)x */
+    float min;     /* 0 for an empty set */
+    float max;
+} flow2d_deformation_moments;
+
+typedef struct flow2d_deformation_stats {
+    unsigned long long valid;
+    unsigned long long invalid; /* width * height - valid */
+    flow2d_deformation_moments divergence, vorticity, dilatation, e1, e2, max_shear;
+    unsigned long long reserved[12]; /* 0 */
+} flow2d_deformation_stats;
+
+#define FLOW2D_DEFORMATION_STATS_BYTES 256
+#ifdef __cplusplus
+static_assert(sizeof(flow2d_deformation_stats) == FLOW2D_DEFORMATION_STATS_BYTES, "flow2d_deformation_stats layout");
+#else
+_Static_assert(sizeof(flow2d_deformation_stats) == FLOW2D_DEFORMATION_STATS_BYTES, "flow2d_deformation_stats layout");
+#endif
+
+/* Workspace bytes flow2d_deformation_2d needs for `instances` lock-step instances of a width x height flow when it writes
+ * statistics (0 for a zero size; a multiple of 16).  Host logic only, needs no device. */
+FLOW2D_API size_t flow2d_deformation_workspace_bytes(size_t width, size_t height, size_t instances);
+FLOW2D_API int flow2d_deformation_2d(flow2d_context* ctx, const float* flow_u, const float* flow_v,
+                                     const float* mask /* may be NULL */, size_t width, size_t height, size_t pitch_bytes,
+                                     int measure, const flow2d_deformation_planes* out /* host, may be NULL */,
+                                     flow2d_deformation_stats* stats /* device, may be NULL */, void* workspace,
+                                     size_t workspace_bytes);
 
 /* The flow of the previous pyramid level resampled to this level's size (the bits of flow2d_resample_xy_pair into out_u / out_v)
  * and frame_1 warped by it (the bits of flow2d_registration_2d into `output`) in one launch: replaces the
