@@ -1061,6 +1061,16 @@ def _fptr(a):
     return a.ctypes.data_as(C.POINTER(C.c_float))
 
 
+def _opt_fptr(a):
+    """_fptr of an optional array: None (a null pointer) for None."""
+    return None if a is None else _fptr(a)
+
+
+def _ptr_array(q):
+    """A list of device addresses as a void* array: None (a null pointer) for None."""
+    return None if q is None else (C.c_void_p * max(len(q), 1))(*q)
+
+
 class OpticalFlow:
     """OpticalFlow2D of the host layer (Initialize / ComputeFlow / ComputeFlowDevice / Destroy)."""
 
@@ -1084,6 +1094,20 @@ class OpticalFlow:
                sor_omega=0.0):
         return HostParams(levels, scale, outer, inner, alpha, e_smooth, e_data, median_radius, sigma, algorithm,
                           sor_omega)
+
+    def _pair(self, frame_0, frame_1):
+        """Both frames as contiguous float32 arrays; ValueError unless each is [height, width]."""
+        f0, f1 = (np.ascontiguousarray(a, np.float32) for a in (frame_0, frame_1))
+        if f0.shape != (self.height, self.width) or f1.shape != f0.shape:
+            raise ValueError("frames: [%d, %d]" % (self.height, self.width))
+        return f0, f1
+
+    def _stack(self, frames):
+        """A sequence as one contiguous float32 array; ValueError unless it is [frame_count, height, width]."""
+        fr = np.ascontiguousarray(frames, np.float32)
+        if fr.ndim != 3 or fr.shape[1:] != (self.height, self.width):
+            raise ValueError("frames: [frame_count, %d, %d]" % (self.height, self.width))
+        return fr
 
     def max_warp_level(self, width, height, scale):
         return host_lib().flow2d_host_max_warp_level(self.handle, width, height, scale)
@@ -1116,10 +1140,8 @@ class OpticalFlow:
         n = len(dev_frames)
         if n < 2 or len(dev_us) != n - 1 or len(dev_vs) != n - 1:
             raise ValueError("a sequence of n frames takes n - 1 flow plane pairs")
-        frames = (C.c_void_p * n)(*dev_frames)
-        us = (C.c_void_p * (n - 1))(*dev_us)
-        vs = (C.c_void_p * (n - 1))(*dev_vs)
-        rc = host_lib().flow2d_host_compute_flow_sequence_device(self.handle, frames, n, us, vs, C.byref(params))
+        rc = host_lib().flow2d_host_compute_flow_sequence_device(self.handle, _ptr_array(dev_frames), n, _ptr_array(dev_us),
+                                                                 _ptr_array(dev_vs), C.byref(params))
         if rc:
             raise Flow2DError(rc, "OpticalFlow2D::ComputeFlowSequenceDevice")
 
@@ -1147,10 +1169,9 @@ class OpticalFlow:
         lists = [dev_us, dev_vs, dev_back_us, dev_back_vs] + [q for q in (dev_occ_fwd, dev_occ_bwd) if q is not None]
         if n < 2 or any(len(q) != n - 1 for q in lists):
             raise ValueError("a sequence of n frames takes n - 1 planes in every output list")
-        arr = lambda q: None if q is None else (C.c_void_p * len(q))(*q)  # noqa: E731
-        rc = host_lib().flow2d_host_compute_flow_bidirectional_device(
-            self.handle, arr(dev_frames), n, arr(dev_us), arr(dev_vs), arr(dev_back_us), arr(dev_back_vs), arr(dev_occ_fwd),
-            arr(dev_occ_bwd), C.byref(params), alpha1, alpha2)
+        planes = [_ptr_array(q) for q in (dev_us, dev_vs, dev_back_us, dev_back_vs, dev_occ_fwd, dev_occ_bwd)]
+        rc = host_lib().flow2d_host_compute_flow_bidirectional_device(self.handle, _ptr_array(dev_frames), n, *planes,
+                                                                      C.byref(params), alpha1, alpha2)
         if rc:
             raise Flow2DError(rc, "OpticalFlow2D::ComputeFlowBidirectionalDevice")
 
@@ -1178,10 +1199,9 @@ class OpticalFlow:
         ts = np.ascontiguousarray(np.atleast_1d(times), np.float32)
         if n < 2 or len(ts) < 1 or len(dev_outputs) != (n - 1) * len(ts):
             raise ValueError("n frames and m times take (n - 1) * m output planes")
-        frames = (C.c_void_p * n)(*dev_frames)
-        outs = (C.c_void_p * len(dev_outputs))(*dev_outputs)
-        rc = host_lib().flow2d_host_interpolate_frames_device(self.handle, frames, n, _fptr(ts), len(ts), outs, C.byref(params),
-                                                              int(iterations), max_residual, int(bool(masks)))
+        rc = host_lib().flow2d_host_interpolate_frames_device(self.handle, _ptr_array(dev_frames), n, _fptr(ts), len(ts),
+                                                              _ptr_array(dev_outputs), C.byref(params), int(iterations),
+                                                              max_residual, int(bool(masks)))
         if rc:
             raise Flow2DError(rc, "OpticalFlow2D::InterpolateFramesDevice")
 
@@ -1220,11 +1240,10 @@ class OpticalFlow:
         n = len(dev_frames)
         if n < 2 or len(dev_xs) != n or len(dev_ys) != n:
             raise ValueError("n frames take n x and n y tables")
-        arr = lambda q: (C.c_void_p * len(q))(*q)  # noqa: E731
         counts = (C.c_ulonglong * n)()
-        rc = host_lib().flow2d_host_track_points_device(self.handle, arr(dev_frames), n, spacing, min_eigenvalue,
-                                                        int(bool(boundaries)), beta1, beta2, arr(dev_xs), arr(dev_ys), capacity,
-                                                        counts, C.byref(params), alpha1, alpha2)
+        rc = host_lib().flow2d_host_track_points_device(self.handle, _ptr_array(dev_frames), n, spacing, min_eigenvalue,
+                                                        int(bool(boundaries)), beta1, beta2, _ptr_array(dev_xs),
+                                                        _ptr_array(dev_ys), capacity, counts, C.byref(params), alpha1, alpha2)
         if rc:
             raise Flow2DError(rc, "OpticalFlow2D::TrackPointsDevice")
         return [int(c) for c in counts]
@@ -1235,14 +1254,12 @@ class OpticalFlow:
         (compute_flow_bidirectional on consecutive pairs, chained for distances of 2 and more), without what the occlusion masks
         mark (masks) and, with range_sigma > 0 (grey levels), weighted by sigma^2 / (sigma^2 + difference^2)
         (flow2d_denoise_2d).  Returns the fused frames [frame_count, h, w]; with weight_sums, (frames, sums of weights)."""
-        fr = np.ascontiguousarray(frames, np.float32)
-        if fr.ndim != 3 or fr.shape[1:] != (self.height, self.width):
-            raise ValueError("frames: [frame_count, %d, %d]" % (self.height, self.width))
+        fr = self._stack(frames)
         out = np.empty_like(fr)
         sums = np.empty_like(fr) if weight_sums else None
         ms = C.c_float()
         rc = host_lib().flow2d_host_denoise_sequence(self.handle, _fptr(fr), fr.shape[0], int(radius), range_sigma,
-                                                     int(bool(masks)), _fptr(out), None if sums is None else _fptr(sums),
+                                                     int(bool(masks)), _fptr(out), _opt_fptr(sums),
                                                      C.byref(params), C.byref(ms))
         if rc:
             raise Flow2DError(rc, "OpticalFlow2D::DenoiseSequence")
@@ -1255,9 +1272,8 @@ class OpticalFlow:
         n = len(dev_frames)
         if len(dev_outputs) != n or (dev_weight_sums is not None and len(dev_weight_sums) != n):
             raise ValueError("n frames take n output planes")
-        arr = lambda q: None if q is None else (C.c_void_p * max(len(q), 1))(*q)  # noqa: E731
-        rc = host_lib().flow2d_host_denoise_sequence_device(self.handle, arr(dev_frames), n, int(radius), range_sigma,
-                                                            int(bool(masks)), arr(dev_outputs), arr(dev_weight_sums),
+        rc = host_lib().flow2d_host_denoise_sequence_device(self.handle, _ptr_array(dev_frames), n, int(radius), range_sigma,
+                                                            int(bool(masks)), _ptr_array(dev_outputs), _ptr_array(dev_weight_sums),
                                                             C.byref(params))
         if rc:
             raise Flow2DError(rc, "OpticalFlow2D::DenoiseSequenceDevice")
@@ -1267,16 +1283,13 @@ class OpticalFlow:
         """OpticalFlow2D::EstimateGlobalMotion: the global motion of the host pair -- the flow frame_0 -> frame_1 (with masks:
         through the bidirectional flow, the forward occlusion mask leaving its vectors out), `model` fitted by
         flow2d_global_motion_2d.  Returns the GlobalMotion record; with flow / residual, (record, (u, v) and / or (ru, rv))."""
-        f0, f1 = (np.ascontiguousarray(a, np.float32) for a in (frame_0, frame_1))
-        if f0.shape != (self.height, self.width) or f1.shape != f0.shape:
-            raise ValueError("frames: [%d, %d]" % (self.height, self.width))
+        f0, f1 = self._pair(frame_0, frame_1)
         rec, ms = GlobalMotion(), C.c_float()
         fl = [np.empty_like(f0) for _ in range(2)] if flow else [None, None]
         rs = [np.empty_like(f0) for _ in range(2)] if residual else [None, None]
-        opt = lambda a: None if a is None else _fptr(a)  # noqa: E731
         rc = host_lib().flow2d_host_estimate_global_motion(self.handle, _fptr(f0), _fptr(f1), int(model), float(sigma),
                                                            int(iterations), int(bool(masks)), C.byref(rec), C.byref(params),
-                                                           opt(fl[0]), opt(fl[1]), opt(rs[0]), opt(rs[1]), C.byref(ms))
+                                                           *[_opt_fptr(a) for a in fl + rs], C.byref(ms))
         if rc:
             raise Flow2DError(rc, "OpticalFlow2D::EstimateGlobalMotion")
         extra = ([tuple(fl)] if flow else []) + ([tuple(rs)] if residual else [])
@@ -1301,19 +1314,16 @@ class OpticalFlow:
         (bidirectional with masks, the forward occlusion mask leaving its pixels out), the global motion `model`, the residual
         flow and flow2d_segment_motion_2d on it.  Returns (GlobalMotion, SegmentSummary, [MotionRegion] -- the recorded ones --,
         labels [h, w] int32); with residual, also (ru, rv)."""
-        f0, f1 = (np.ascontiguousarray(a, np.float32) for a in (frame_0, frame_1))
-        if f0.shape != (self.height, self.width) or f1.shape != f0.shape:
-            raise ValueError("frames: [%d, %d]" % (self.height, self.width))
+        f0, f1 = self._pair(frame_0, frame_1)
         H = host_lib()
         rec, summary = GlobalMotion(), SegmentSummary()
         regions = (MotionRegion * H.flow2d_host_segment_max_regions())()
         labels = np.empty(f0.shape, np.int32)
         rs = [np.empty_like(f0) for _ in range(2)] if residual else [None, None]
-        opt = lambda a: None if a is None else _fptr(a)  # noqa: E731
         rc = H.flow2d_host_segment_motion(self.handle, _fptr(f0), _fptr(f1), int(model), float(sigma), int(iterations),
                                           int(bool(masks)), float(threshold), float(join), int(min_area), C.byref(rec),
                                           C.byref(summary), regions, C.byref(params), labels.ctypes.data_as(C.POINTER(C.c_int)),
-                                          opt(rs[0]), opt(rs[1]))
+                                          _opt_fptr(rs[0]), _opt_fptr(rs[1]))
         if rc:
             raise Flow2DError(rc, "OpticalFlow2D::SegmentMotion")
         out = (rec, summary, list(regions)[:summary.recorded], labels)
@@ -1340,18 +1350,15 @@ class OpticalFlow:
         (bidirectional with masks, the forward occlusion mask then keeping differences from reaching across an occlusion
         boundary), a Gaussian of smoothing_sigma pixels over both flow planes when > 0, and flow2d_deformation_2d.  Returns
         ({name: [h, w] array} for the names of `planes`, DeformationStats); with flow, also the (u, v) that was analysed."""
-        f0, f1 = (np.ascontiguousarray(a, np.float32) for a in (frame_0, frame_1))
-        if f0.shape != (self.height, self.width) or f1.shape != f0.shape:
-            raise ValueError("frames: [%d, %d]" % (self.height, self.width))
+        f0, f1 = self._pair(frame_0, frame_1)
         out = {name: np.empty_like(f0) for name in planes}
         fp = C.POINTER(C.c_float)
         table = (fp * 9)(*[_fptr(out[name]) if name in out else fp() for name in DEFORMATION_PLANES])
         uv = [np.empty_like(f0) for _ in range(2)] if flow else [None, None]
-        opt = lambda a: None if a is None else _fptr(a)  # noqa: E731
         stats = DeformationStats()
         rc = host_lib().flow2d_host_analyse_deformation(self.handle, _fptr(f0), _fptr(f1), int(measure), float(smoothing_sigma),
-                                                        int(bool(masks)), table, C.byref(stats), C.byref(params), opt(uv[0]),
-                                                        opt(uv[1]), None)
+                                                        int(bool(masks)), table, C.byref(stats), C.byref(params),
+                                                        _opt_fptr(uv[0]), _opt_fptr(uv[1]), None)
         if rc:
             raise Flow2DError(rc, "OpticalFlow2D::AnalyseDeformation")
         return (out, stats, tuple(uv)) if flow else (out, stats)
@@ -1382,9 +1389,7 @@ class OpticalFlow:
         frames[reference_index] along the composed global motions of consecutive pairs (flow2d_global_motion_2d,
         flow2d_warp_global_2d); `fill` where a frame has nothing to show.  Returns (frames [frame_count, h, w], the GlobalMotion
         records M(reference -> k))."""
-        fr = np.ascontiguousarray(frames, np.float32)
-        if fr.ndim != 3 or fr.shape[1:] != (self.height, self.width):
-            raise ValueError("frames: [frame_count, %d, %d]" % (self.height, self.width))
+        fr = self._stack(frames)
         out = np.empty_like(fr)
         motions = (GlobalMotion * max(fr.shape[0], 1))()
         ms = C.c_float()
@@ -1402,11 +1407,10 @@ class OpticalFlow:
         n = len(dev_frames)
         if len(dev_outputs) != n:
             raise ValueError("n frames take n output planes")
-        arr = lambda q: (C.c_void_p * max(len(q), 1))(*q)  # noqa: E731
         motions = (GlobalMotion * max(n, 1))()
-        rc = host_lib().flow2d_host_stabilise_sequence_device(self.handle, arr(dev_frames), n, int(reference_index), int(model),
-                                                              float(sigma), int(iterations), int(bool(masks)), fill,
-                                                              arr(dev_outputs), motions, C.byref(params))
+        rc = host_lib().flow2d_host_stabilise_sequence_device(self.handle, _ptr_array(dev_frames), n, int(reference_index),
+                                                              int(model), float(sigma), int(iterations), int(bool(masks)), fill,
+                                                              _ptr_array(dev_outputs), motions, C.byref(params))
         if rc:
             raise Flow2DError(rc, "OpticalFlow2D::StabiliseSequenceDevice")
         return list(motions)[:n]

@@ -2,6 +2,7 @@
 // It drives the same OpticalFlow2D / OperationParameters objects a C++ caller would.
 #include <cstdint>
 #include <cstring>
+#include <deque>
 #include <new>
 #include <vector>
 
@@ -34,19 +35,109 @@ struct flow2d_host_flow {
 };
 
 namespace {
-void FillBag(OperationParameters& bag, flow2d_host_params& p)
+// The parameter bag of one call.  The bag holds pointers, so the object owns what they point to: a copy of the caller's block and,
+// for the entries that take them, the consistency thresholds (the bag keys consistency_alpha1 / consistency_alpha2).
+struct Bag {
+    explicit Bag(const flow2d_host_params& params) : p(params)
+    {
+        bag.PushValuePtr("warp_levels_count", &p.warp_levels_count);
+        bag.PushValuePtr("warp_scale_factor", &p.warp_scale_factor);
+        bag.PushValuePtr("outer_iterations_count", &p.outer_iterations_count);
+        bag.PushValuePtr("inner_iterations_count", &p.inner_iterations_count);
+        bag.PushValuePtr("equation_alpha", &p.equation_alpha);
+        bag.PushValuePtr("equation_smoothness", &p.equation_smoothness);
+        bag.PushValuePtr("equation_data", &p.equation_data);
+        bag.PushValuePtr("median_radius", &p.median_radius);
+        bag.PushValuePtr("gaussian_sigma", &p.gaussian_sigma);
+        bag.PushValuePtr("solver_algorithm", &p.solver_algorithm);
+        bag.PushValuePtr("solver_sor_omega", &p.sor_omega);
+    }
+    Bag(const flow2d_host_params& params, float consistency_alpha1, float consistency_alpha2)
+        : Bag(params)
+    {
+        alpha1 = consistency_alpha1;
+        alpha2 = consistency_alpha2;
+        bag.PushValuePtr("consistency_alpha1", &alpha1);
+        bag.PushValuePtr("consistency_alpha2", &alpha2);
+    }
+    Bag(const Bag&) = delete;
+    Bag& operator=(const Bag&) = delete;
+    operator OperationParameters&() { return bag; }
+
+    flow2d_host_params p;
+    float alpha1 = 0.f, alpha2 = 0.f;
+    OperationParameters bag;
+};
+
+DevicePtr dp(void* q) { return static_cast<DevicePtr>(reinterpret_cast<uintptr_t>(q)); }
+
+// the `n` device addresses of `q` (none for a null array)
+std::vector<DevicePtr> DevicePtrs(void* const* q, size_t n)
 {
-    bag.PushValuePtr("warp_levels_count", &p.warp_levels_count);
-    bag.PushValuePtr("warp_scale_factor", &p.warp_scale_factor);
-    bag.PushValuePtr("outer_iterations_count", &p.outer_iterations_count);
-    bag.PushValuePtr("inner_iterations_count", &p.inner_iterations_count);
-    bag.PushValuePtr("equation_alpha", &p.equation_alpha);
-    bag.PushValuePtr("equation_smoothness", &p.equation_smoothness);
-    bag.PushValuePtr("equation_data", &p.equation_data);
-    bag.PushValuePtr("median_radius", &p.median_radius);
-    bag.PushValuePtr("gaussian_sigma", &p.gaussian_sigma);
-    bag.PushValuePtr("solver_algorithm", &p.solver_algorithm);
-    bag.PushValuePtr("solver_sor_omega", &p.sor_omega);
+    std::vector<DevicePtr> out;
+    for (size_t k = 0; q && k < n; ++k) out.push_back(dp(q[k]));
+    return out;
+}
+
+// The images of a host-image entry on tight arrays (width * height floats per image, image k of an array at k * width * height).
+class HostImages {
+public:
+    enum CopyBack { Always, AfterSuccess };
+
+    explicit HostImages(const flow2d_host_flow* h) : width_(h->width), height_(h->height), n_(h->width * h->height) {}
+    // `count` images holding copies of `src`: the first one (the others follow it in memory)
+    Data2D* In(const float* src, size_t count = 1)
+    {
+        std::vector<Data2D>& images = Block(count);
+        for (size_t k = 0; k < count; ++k) std::memcpy(images[k].DataPtr(), src + k * n_, n_ * sizeof(float));
+        return images.data();
+    }
+    // `count` images that Finish() copies to `dst`: the first one, or null for a null `dst` (not wanted).  They are poisoned, and
+    // those that are copied back Always show the poison to the caller after a run that was refused or failed.
+    Data2D* Out(void* dst, CopyBack when, size_t count = 1)
+    {
+        if (!dst) return nullptr;
+        std::vector<Data2D>& images = Block(count);
+        for (size_t k = 0; k < count; ++k) {
+            for (size_t i = 0; i < n_; ++i) images[k].DataPtr()[i] = -12345.f;
+            outputs_.push_back({&images[k], static_cast<float*>(dst) + k * n_, when});
+        }
+        return images.data();
+    }
+    // After the run: the outputs into the caller's arrays, the device time into `total_ms` (optional); 0, or 2 when the run was
+    // refused or an operator failed.
+    int Finish(OpticalFlow2D& flow, float* total_ms = nullptr)
+    {
+        const bool ok = flow.LastRunSucceeded();
+        for (const Output& o : outputs_)
+            if (ok || o.when == Always) std::memcpy(o.dst, o.image->DataPtr(), n_ * sizeof(float));
+        if (total_ms) *total_ms = flow.LastTotalMs();
+        return ok ? 0 : 2;
+    }
+
+private:
+    std::vector<Data2D>& Block(size_t count)
+    {
+        blocks_.emplace_back();
+        for (size_t k = 0; k < count; ++k) blocks_.back().emplace_back(width_, height_);
+        return blocks_.back();
+    }
+    struct Output {
+        Data2D* image;
+        float* dst;
+        CopyBack when;
+    };
+    size_t width_, height_, n_;
+    std::deque<std::vector<Data2D>> blocks_;  // (a deque: the blocks stay where they are)
+    std::vector<Output> outputs_;
+};
+
+// the pointers to `count` images that follow each other
+std::vector<Data2D*> Pointers(Data2D* images, size_t count)
+{
+    std::vector<Data2D*> out;
+    for (size_t k = 0; k < count; ++k) out.push_back(images + k);
+    return out;
 }
 }  // namespace
 
@@ -102,20 +193,12 @@ HOST_API int flow2d_host_compute_flow(flow2d_host_flow* h, const float* frame_0,
                                       float* flow_v, const flow2d_host_params* params, float* total_ms)
 {
     if (!h || !frame_0 || !frame_1 || !flow_u || !flow_v || !params) return 1;
-    const size_t n = h->width * h->height;
-    Data2D f0(h->width, h->height), f1(h->width, h->height), u(h->width, h->height), v(h->width, h->height);
-    std::memcpy(f0.DataPtr(), frame_0, n * sizeof(float));
-    std::memcpy(f1.DataPtr(), frame_1, n * sizeof(float));
-    // poison the outputs so that an aborted run (missing key, bad parameter) is visible to the caller
-    for (size_t i = 0; i < n; ++i) u.DataPtr()[i] = v.DataPtr()[i] = -12345.f;
-    flow2d_host_params p = *params;
-    OperationParameters bag;
-    FillBag(bag, p);
-    h->flow.ComputeFlow(f0, f1, u, v, bag);
-    std::memcpy(flow_u, u.DataPtr(), n * sizeof(float));
-    std::memcpy(flow_v, v.DataPtr(), n * sizeof(float));
-    if (total_ms) *total_ms = h->flow.LastTotalMs();
-    return h->flow.LastRunSucceeded() ? 0 : 2;  // 2: the run was refused or an operator failed (outputs keep the poison)
+    // the outputs are poisoned so that an aborted run (missing key, bad parameter) is visible to the caller
+    HostImages im(h);
+    Data2D *f0 = im.In(frame_0), *f1 = im.In(frame_1), *u = im.Out(flow_u, im.Always), *v = im.Out(flow_v, im.Always);
+    Bag bag(*params);
+    h->flow.ComputeFlow(*f0, *f1, *u, *v, bag);
+    return im.Finish(h->flow, total_ms);  // 2: the run was refused or an operator failed (outputs keep the poison)
 }
 
 // OpticalFlow2D::ComputeFlowDevice: frames and flow already in pitched device containers.  Queued on
@@ -125,11 +208,8 @@ HOST_API int flow2d_host_compute_flow_device(flow2d_host_flow* h, void* dev_fram
                                              int timing_mode)
 {
     if (!h || !params) return 1;
-    flow2d_host_params p = *params;
-    OperationParameters bag;
-    FillBag(bag, p);
+    Bag bag(*params);
     h->flow.timing_mode = timing_mode;
-    auto dp = [](void* q) { return static_cast<DevicePtr>(reinterpret_cast<uintptr_t>(q)); };
     return h->flow.ComputeFlowDevice(dp(dev_frame_0), dp(dev_frame_1), dp(dev_flow_u), dp(dev_flow_v), bag) ? 0 : 2;
 }
 
@@ -139,17 +219,10 @@ HOST_API int flow2d_host_compute_flow_sequence_device(flow2d_host_flow* h, void*
                                                       const flow2d_host_params* params)
 {
     if (!h || !params || !dev_frames || !dev_flows_u || !dev_flows_v || frame_count < 2) return 1;
-    flow2d_host_params p = *params;
-    OperationParameters bag;
-    FillBag(bag, p);
+    Bag bag(*params);
     h->flow.timing_mode = 0;
-    auto dp = [](void* q) { return static_cast<DevicePtr>(reinterpret_cast<uintptr_t>(q)); };
-    std::vector<DevicePtr> frames(frame_count), us(frame_count - 1), vs(frame_count - 1);
-    for (size_t k = 0; k < frame_count; ++k) frames[k] = dp(dev_frames[k]);
-    for (size_t k = 0; k + 1 < frame_count; ++k) {
-        us[k] = dp(dev_flows_u[k]);
-        vs[k] = dp(dev_flows_v[k]);
-    }
+    const std::vector<DevicePtr> frames = DevicePtrs(dev_frames, frame_count), us = DevicePtrs(dev_flows_u, frame_count - 1),
+                                 vs = DevicePtrs(dev_flows_v, frame_count - 1);
     return h->flow.ComputeFlowSequenceDevice(frames.data(), frame_count, us.data(), vs.data(), bag) ? 0 : 2;
 }
 
@@ -163,24 +236,13 @@ HOST_API int flow2d_host_compute_flow_bidirectional(flow2d_host_flow* h, const f
 {
     if (!h || !frame_0 || !frame_1 || !flow_u || !flow_v || !back_u || !back_v || !occlusion_0 || !occlusion_1 || !params)
         return 1;
-    const size_t n = h->width * h->height;
-    Data2D f0(h->width, h->height), f1(h->width, h->height);
-    std::memcpy(f0.DataPtr(), frame_0, n * sizeof(float));
-    std::memcpy(f1.DataPtr(), frame_1, n * sizeof(float));
-    Data2D out[6] = {Data2D(h->width, h->height), Data2D(h->width, h->height), Data2D(h->width, h->height),
-                     Data2D(h->width, h->height), Data2D(h->width, h->height), Data2D(h->width, h->height)};
+    HostImages im(h);
+    Data2D *f0 = im.In(frame_0), *f1 = im.In(frame_1), *out[6];
     float* dst[6] = {flow_u, flow_v, back_u, back_v, occlusion_0, occlusion_1};
-    for (Data2D& d : out)  // poisoned, as in flow2d_host_compute_flow
-        for (size_t i = 0; i < n; ++i) d.DataPtr()[i] = -12345.f;
-    flow2d_host_params p = *params;
-    OperationParameters bag;
-    FillBag(bag, p);
-    bag.PushValuePtr("consistency_alpha1", &alpha1);
-    bag.PushValuePtr("consistency_alpha2", &alpha2);
-    h->flow.ComputeFlowBidirectional(f0, f1, out[0], out[1], out[2], out[3], out[4], out[5], bag);
-    for (int i = 0; i < 6; ++i) std::memcpy(dst[i], out[i].DataPtr(), n * sizeof(float));
-    if (total_ms) *total_ms = h->flow.LastTotalMs();
-    return h->flow.LastRunSucceeded() ? 0 : 2;
+    for (int i = 0; i < 6; ++i) out[i] = im.Out(dst[i], im.Always);
+    Bag bag(*params, alpha1, alpha2);
+    h->flow.ComputeFlowBidirectional(*f0, *f1, *out[0], *out[1], *out[2], *out[3], *out[4], *out[5], bag);
+    return im.Finish(h->flow, total_ms);
 }
 
 // OpticalFlow2D::InterpolateFrames on tight host images (width*height floats each): the time_count frames of `times` between
@@ -191,22 +253,11 @@ HOST_API int flow2d_host_interpolate_frames(flow2d_host_flow* h, const float* fr
                                             float max_residual, int use_masks, float* total_ms)
 {
     if (!h || !frame_0 || !frame_1 || !times || !outputs || !params || time_count == 0) return 1;
-    const size_t n = h->width * h->height;
-    Data2D f0(h->width, h->height), f1(h->width, h->height);
-    std::memcpy(f0.DataPtr(), frame_0, n * sizeof(float));
-    std::memcpy(f1.DataPtr(), frame_1, n * sizeof(float));
-    std::vector<Data2D> out;
-    for (size_t j = 0; j < time_count; ++j) {
-        out.emplace_back(h->width, h->height);
-        for (size_t i = 0; i < n; ++i) out.back().DataPtr()[i] = -12345.f;  // poisoned, as in flow2d_host_compute_flow
-    }
-    flow2d_host_params p = *params;
-    OperationParameters bag;
-    FillBag(bag, p);
-    h->flow.InterpolateFrames(f0, f1, times, time_count, out.data(), iterations, max_residual, use_masks != 0, bag);
-    for (size_t j = 0; j < time_count; ++j) std::memcpy(outputs + j * n, out[j].DataPtr(), n * sizeof(float));
-    if (total_ms) *total_ms = h->flow.LastTotalMs();
-    return h->flow.LastRunSucceeded() ? 0 : 2;
+    HostImages im(h);
+    Data2D *f0 = im.In(frame_0), *f1 = im.In(frame_1), *out = im.Out(outputs, im.Always, time_count);
+    Bag bag(*params);
+    h->flow.InterpolateFrames(*f0, *f1, times, time_count, out, iterations, max_residual, use_masks != 0, bag);
+    return im.Finish(h->flow, total_ms);
 }
 
 // OpticalFlow2D::InterpolateFramesDevice: frame_count device frames, (frame_count - 1) * time_count device output planes (pair k,
@@ -217,14 +268,10 @@ HOST_API int flow2d_host_interpolate_frames_device(flow2d_host_flow* h, void* co
                                                    int use_masks)
 {
     if (!h || !params || !dev_frames || !dev_outputs || !times || frame_count < 2 || time_count == 0) return 1;
-    flow2d_host_params p = *params;
-    OperationParameters bag;
-    FillBag(bag, p);
+    Bag bag(*params);
     h->flow.timing_mode = 0;
-    auto dp = [](void* q) { return static_cast<DevicePtr>(reinterpret_cast<uintptr_t>(q)); };
-    std::vector<DevicePtr> frames(frame_count), outputs((frame_count - 1) * time_count);
-    for (size_t k = 0; k < frames.size(); ++k) frames[k] = dp(dev_frames[k]);
-    for (size_t k = 0; k < outputs.size(); ++k) outputs[k] = dp(dev_outputs[k]);
+    const std::vector<DevicePtr> frames = DevicePtrs(dev_frames, frame_count),
+                                 outputs = DevicePtrs(dev_outputs, (frame_count - 1) * time_count);
     return h->flow.InterpolateFramesDevice(frames.data(), frame_count, times, time_count, outputs.data(), iterations, max_residual,
                                            use_masks != 0, bag)
                ? 0
@@ -240,23 +287,12 @@ HOST_API int flow2d_host_track_points(flow2d_host_flow* h, const float* frames, 
                                       float alpha2, float* total_ms)
 {
     if (!h || !frames || !xs || !ys || !counts || !params || frame_count < 2 || capacity == 0) return 1;
-    const size_t n = h->width * h->height;
-    std::vector<Data2D> f;
-    for (size_t k = 0; k < frame_count; ++k) {
-        f.emplace_back(h->width, h->height);
-        std::memcpy(f.back().DataPtr(), frames + k * n, n * sizeof(float));
-    }
-    flow2d_host_params p = *params;
-    OperationParameters bag;
-    FillBag(bag, p);
-    bag.PushValuePtr("consistency_alpha1", &alpha1);
-    bag.PushValuePtr("consistency_alpha2", &alpha2);
-    std::vector<Data2D*> fp;
-    for (Data2D& d : f) fp.push_back(&d);
+    HostImages im(h);
+    const std::vector<Data2D*> fp = Pointers(im.In(frames, frame_count), frame_count);
+    Bag bag(*params, alpha1, alpha2);
     h->flow.TrackPoints(fp.data(), frame_count, spacing, min_eigenvalue, check_boundaries != 0, beta1, beta2, xs, ys, capacity,
                         counts, bag);
-    if (total_ms) *total_ms = h->flow.LastTotalMs();
-    return h->flow.LastRunSucceeded() ? 0 : 2;
+    return im.Finish(h->flow, total_ms);
 }
 
 // OpticalFlow2D::TrackPointsDevice: frame_count device frames and frame_count device tables of `capacity` floats per
@@ -268,19 +304,10 @@ HOST_API int flow2d_host_track_points_device(flow2d_host_flow* h, void* const* d
                                              float alpha2)
 {
     if (!h || !params || !dev_frames || !dev_xs || !dev_ys || !counts || frame_count < 2 || capacity == 0) return 1;
-    flow2d_host_params p = *params;
-    OperationParameters bag;
-    FillBag(bag, p);
-    bag.PushValuePtr("consistency_alpha1", &alpha1);
-    bag.PushValuePtr("consistency_alpha2", &alpha2);
+    Bag bag(*params, alpha1, alpha2);
     h->flow.timing_mode = 0;
-    auto dp = [](void* q) { return static_cast<DevicePtr>(reinterpret_cast<uintptr_t>(q)); };
-    std::vector<DevicePtr> frames(frame_count), xs(frame_count), ys(frame_count);
-    for (size_t k = 0; k < frame_count; ++k) {
-        frames[k] = dp(dev_frames[k]);
-        xs[k] = dp(dev_xs[k]);
-        ys[k] = dp(dev_ys[k]);
-    }
+    const std::vector<DevicePtr> frames = DevicePtrs(dev_frames, frame_count), xs = DevicePtrs(dev_xs, frame_count),
+                                 ys = DevicePtrs(dev_ys, frame_count);
     return h->flow.TrackPointsDevice(frames.data(), frame_count, spacing, min_eigenvalue, check_boundaries != 0, beta1, beta2,
                                      xs.data(), ys.data(), capacity, counts, bag)
                ? 0
@@ -301,28 +328,12 @@ HOST_API int flow2d_host_denoise_sequence(flow2d_host_flow* h, const float* fram
                                           const flow2d_host_params* params, float* total_ms)
 {
     if (!OpticalFlow2D::DenoiseArgsOk(frame_count, radius, range_sigma) || !h || !frames || !outputs || !params) return 1;
-    const size_t n = h->width * h->height;
-    std::vector<Data2D> f, out, sums;
-    for (size_t k = 0; k < frame_count; ++k) {
-        f.emplace_back(h->width, h->height);
-        std::memcpy(f.back().DataPtr(), frames + k * n, n * sizeof(float));
-        out.emplace_back(h->width, h->height);
-        for (size_t i = 0; i < n; ++i) out.back().DataPtr()[i] = -12345.f;  // poisoned, as in flow2d_host_compute_flow
-        if (weight_sums) sums.emplace_back(h->width, h->height);
-    }
-    flow2d_host_params p = *params;
-    OperationParameters bag;
-    FillBag(bag, p);
-    std::vector<Data2D*> fp;
-    for (Data2D& d : f) fp.push_back(&d);
-    h->flow.DenoiseSequence(fp.data(), frame_count, radius, range_sigma, use_masks != 0, out.data(),
-                            weight_sums ? sums.data() : nullptr, bag);
-    for (size_t k = 0; k < frame_count; ++k) {
-        std::memcpy(outputs + k * n, out[k].DataPtr(), n * sizeof(float));
-        if (weight_sums && h->flow.LastRunSucceeded()) std::memcpy(weight_sums + k * n, sums[k].DataPtr(), n * sizeof(float));
-    }
-    if (total_ms) *total_ms = h->flow.LastTotalMs();
-    return h->flow.LastRunSucceeded() ? 0 : 2;
+    HostImages im(h);
+    const std::vector<Data2D*> fp = Pointers(im.In(frames, frame_count), frame_count);
+    Data2D *out = im.Out(outputs, im.Always, frame_count), *sums = im.Out(weight_sums, im.AfterSuccess, frame_count);
+    Bag bag(*params);
+    h->flow.DenoiseSequence(fp.data(), frame_count, radius, range_sigma, use_masks != 0, out, sums, bag);
+    return im.Finish(h->flow, total_ms);
 }
 
 // OpticalFlow2D::DenoiseSequenceDevice: frame_count device frames and output planes, weight-sum planes optional (NULL: none).
@@ -332,17 +343,10 @@ HOST_API int flow2d_host_denoise_sequence_device(flow2d_host_flow* h, void* cons
                                                  void* const* dev_weight_sums, const flow2d_host_params* params)
 {
     if (!OpticalFlow2D::DenoiseArgsOk(frame_count, radius, range_sigma) || !h || !params || !dev_frames || !dev_outputs) return 1;
-    flow2d_host_params p = *params;
-    OperationParameters bag;
-    FillBag(bag, p);
+    Bag bag(*params);
     h->flow.timing_mode = 0;
-    auto dp = [](void* q) { return static_cast<DevicePtr>(reinterpret_cast<uintptr_t>(q)); };
-    std::vector<DevicePtr> frames(frame_count), outputs(frame_count), sums(dev_weight_sums ? frame_count : 0);
-    for (size_t k = 0; k < frame_count; ++k) {
-        frames[k] = dp(dev_frames[k]);
-        outputs[k] = dp(dev_outputs[k]);
-        if (dev_weight_sums) sums[k] = dp(dev_weight_sums[k]);
-    }
+    const std::vector<DevicePtr> frames = DevicePtrs(dev_frames, frame_count), outputs = DevicePtrs(dev_outputs, frame_count),
+                                 sums = DevicePtrs(dev_weight_sums, frame_count);
     return h->flow.DenoiseSequenceDevice(frames.data(), frame_count, radius, range_sigma, use_masks != 0, outputs.data(),
                                          dev_weight_sums ? sums.data() : nullptr, bag)
                ? 0
@@ -375,23 +379,13 @@ HOST_API int flow2d_host_estimate_global_motion(flow2d_host_flow* h, const float
     if (!OpticalFlow2D::GlobalMotionArgsOk(model, sigma, iterations) || !h || !frame_0 || !frame_1 || !motion || !params ||
         (flow_u == nullptr) != (flow_v == nullptr) || (residual_u == nullptr) != (residual_v == nullptr))
         return 1;
-    const size_t n = h->width * h->height;
-    Data2D f0(h->width, h->height), f1(h->width, h->height);
-    std::memcpy(f0.DataPtr(), frame_0, n * sizeof(float));
-    std::memcpy(f1.DataPtr(), frame_1, n * sizeof(float));
-    Data2D out[4] = {Data2D(h->width, h->height), Data2D(h->width, h->height), Data2D(h->width, h->height),
-                     Data2D(h->width, h->height)};
+    HostImages im(h);
+    Data2D *f0 = im.In(frame_0), *f1 = im.In(frame_1), *out[4];
     float* dst[4] = {flow_u, flow_v, residual_u, residual_v};
-    flow2d_host_params p = *params;
-    OperationParameters bag;
-    FillBag(bag, p);
-    h->flow.EstimateGlobalMotion(f0, f1, model, sigma, iterations, use_masks != 0, motion, bag, flow_u ? &out[0] : nullptr,
-                                 flow_u ? &out[1] : nullptr, residual_u ? &out[2] : nullptr, residual_u ? &out[3] : nullptr);
-    if (h->flow.LastRunSucceeded())
-        for (int i = 0; i < 4; ++i)
-            if (dst[i]) std::memcpy(dst[i], out[i].DataPtr(), n * sizeof(float));
-    if (total_ms) *total_ms = h->flow.LastTotalMs();
-    return h->flow.LastRunSucceeded() ? 0 : 2;
+    for (int i = 0; i < 4; ++i) out[i] = im.Out(dst[i], im.AfterSuccess);
+    Bag bag(*params);
+    h->flow.EstimateGlobalMotion(*f0, *f1, model, sigma, iterations, use_masks != 0, motion, bag, out[0], out[1], out[2], out[3]);
+    return im.Finish(h->flow, total_ms);
 }
 
 // OpticalFlow2D::EstimateGlobalMotionDevice: two device frames, the record into `motion` (host); the optional device planes
@@ -403,11 +397,8 @@ HOST_API int flow2d_host_estimate_global_motion_device(flow2d_host_flow* h, void
 {
     if (!OpticalFlow2D::GlobalMotionArgsOk(model, sigma, iterations) || !h || !dev_frame_0 || !dev_frame_1 || !motion || !params)
         return 1;
-    flow2d_host_params p = *params;
-    OperationParameters bag;
-    FillBag(bag, p);
+    Bag bag(*params);
     h->flow.timing_mode = 0;
-    auto dp = [](void* q) { return static_cast<DevicePtr>(reinterpret_cast<uintptr_t>(q)); };
     return h->flow.EstimateGlobalMotionDevice(dp(dev_frame_0), dp(dev_frame_1), model, sigma, iterations, use_masks != 0, motion, bag,
                                               dp(dev_flow_u), dp(dev_flow_v), dp(dev_residual_u), dp(dev_residual_v))
                ? 0
@@ -434,21 +425,14 @@ HOST_API int flow2d_host_segment_motion(flow2d_host_flow* h, const float* frame_
     if (!OpticalFlow2D::GlobalMotionArgsOk(model, sigma, iterations) || !OpticalFlow2D::SegmentMotionArgsOk(threshold, join, min_area) ||
         !h || !frame_0 || !frame_1 || !motion || !summary || !params || (residual_u == nullptr) != (residual_v == nullptr))
         return 1;
-    const size_t n = h->width * h->height;
-    Data2D f0(h->width, h->height), f1(h->width, h->height);
-    std::memcpy(f0.DataPtr(), frame_0, n * sizeof(float));
-    std::memcpy(f1.DataPtr(), frame_1, n * sizeof(float));
-    Data2D out[3] = {Data2D(h->width, h->height), Data2D(h->width, h->height), Data2D(h->width, h->height)};
+    HostImages im(h);
+    Data2D *f0 = im.In(frame_0), *f1 = im.In(frame_1), *out[3];
     void* dst[3] = {labels, residual_u, residual_v};
-    flow2d_host_params p = *params;
-    OperationParameters bag;
-    FillBag(bag, p);
-    h->flow.SegmentMotion(f0, f1, model, sigma, iterations, use_masks != 0, threshold, join, min_area, motion, summary, regions, bag,
-                          labels ? &out[0] : nullptr, residual_u ? &out[1] : nullptr, residual_u ? &out[2] : nullptr);
-    if (h->flow.LastRunSucceeded())
-        for (int i = 0; i < 3; ++i)
-            if (dst[i]) std::memcpy(dst[i], out[i].DataPtr(), n * sizeof(float));
-    return h->flow.LastRunSucceeded() ? 0 : 2;
+    for (int i = 0; i < 3; ++i) out[i] = im.Out(dst[i], im.AfterSuccess);
+    Bag bag(*params);
+    h->flow.SegmentMotion(*f0, *f1, model, sigma, iterations, use_masks != 0, threshold, join, min_area, motion, summary, regions, bag,
+                          out[0], out[1], out[2]);
+    return im.Finish(h->flow);
 }
 
 // OpticalFlow2D::SegmentMotionDevice: two device frames; the optional device planes get the labels and the residual flow.
@@ -462,11 +446,8 @@ HOST_API int flow2d_host_segment_motion_device(flow2d_host_flow* h, void* dev_fr
     if (!OpticalFlow2D::GlobalMotionArgsOk(model, sigma, iterations) || !OpticalFlow2D::SegmentMotionArgsOk(threshold, join, min_area) ||
         !h || !dev_frame_0 || !dev_frame_1 || !motion || !summary || !params)
         return 1;
-    flow2d_host_params p = *params;
-    OperationParameters bag;
-    FillBag(bag, p);
+    Bag bag(*params);
     h->flow.timing_mode = 0;
-    auto dp = [](void* q) { return static_cast<DevicePtr>(reinterpret_cast<uintptr_t>(q)); };
     return h->flow.SegmentMotionDevice(dp(dev_frame_0), dp(dev_frame_1), model, sigma, iterations, use_masks != 0, threshold, join,
                                        min_area, motion, summary, regions, bag, dp(dev_labels), dp(dev_residual_u), dp(dev_residual_v))
                ? 0
@@ -491,29 +472,14 @@ HOST_API int flow2d_host_analyse_deformation(flow2d_host_flow* h, const float* f
     if (!OpticalFlow2D::DeformationArgsOk(measure, smoothing_sigma) || !h || !frame_0 || !frame_1 || !params ||
         (flow_u == nullptr) != (flow_v == nullptr) || (mask && !use_masks))
         return 1;
-    const size_t n = h->width * h->height;
-    Data2D f0(h->width, h->height), f1(h->width, h->height);
-    std::memcpy(f0.DataPtr(), frame_0, n * sizeof(float));
-    std::memcpy(f1.DataPtr(), frame_1, n * sizeof(float));
+    HostImages im(h);
+    Data2D *f0 = im.In(frame_0), *f1 = im.In(frame_1), *out[12];
     float* dst[12] = {flow_u, flow_v, mask};
     for (int k = 0; k < 9; ++k) dst[3 + k] = planes ? planes[k] : nullptr;
-    std::vector<Data2D> out;
-    out.reserve(12);
-    Data2D* images[12];
-    for (int i = 0; i < 12; ++i) {
-        images[i] = nullptr;
-        if (!dst[i]) continue;
-        out.emplace_back(h->width, h->height);
-        images[i] = &out.back();
-    }
-    flow2d_host_params p = *params;
-    OperationParameters bag;
-    FillBag(bag, p);
-    h->flow.AnalyseDeformation(f0, f1, measure, smoothing_sigma, use_masks != 0, images + 3, stats, bag, images[0], images[1], images[2]);
-    if (h->flow.LastRunSucceeded())
-        for (int i = 0; i < 12; ++i)
-            if (dst[i]) std::memcpy(dst[i], images[i]->DataPtr(), n * sizeof(float));
-    return h->flow.LastRunSucceeded() ? 0 : 2;
+    for (int i = 0; i < 12; ++i) out[i] = im.Out(dst[i], im.AfterSuccess);
+    Bag bag(*params);
+    h->flow.AnalyseDeformation(*f0, *f1, measure, smoothing_sigma, use_masks != 0, out + 3, stats, bag, out[0], out[1], out[2]);
+    return im.Finish(h->flow);
 }
 
 // OpticalFlow2D::AnalyseDeformationDevice: two device frames; dev_planes = nine device planes (each may be null, as may the
@@ -525,11 +491,8 @@ HOST_API int flow2d_host_analyse_deformation_device(flow2d_host_flow* h, void* d
                                                     void* dev_flow_u, void* dev_flow_v, void* dev_mask)
 {
     if (!OpticalFlow2D::DeformationArgsOk(measure, smoothing_sigma) || !h || !dev_frame_0 || !dev_frame_1 || !params) return 1;
-    flow2d_host_params p = *params;
-    OperationParameters bag;
-    FillBag(bag, p);
+    Bag bag(*params);
     h->flow.timing_mode = 0;
-    auto dp = [](void* q) { return static_cast<DevicePtr>(reinterpret_cast<uintptr_t>(q)); };
     DevicePtr planes[9];
     for (int k = 0; k < 9; ++k) planes[k] = dev_planes ? dp(dev_planes[k]) : 0;
     return h->flow.AnalyseDeformationDevice(dp(dev_frame_0), dp(dev_frame_1), measure, smoothing_sigma, use_masks != 0, planes, stats,
@@ -548,24 +511,12 @@ HOST_API int flow2d_host_stabilise_sequence(flow2d_host_flow* h, const float* fr
     if (!OpticalFlow2D::GlobalMotionArgsOk(model, sigma, iterations) || !h || !frames || !outputs || !params || frame_count < 2 ||
         reference_index >= frame_count)
         return 1;
-    const size_t n = h->width * h->height;
-    std::vector<Data2D> f, out;
-    for (size_t k = 0; k < frame_count; ++k) {
-        f.emplace_back(h->width, h->height);
-        std::memcpy(f.back().DataPtr(), frames + k * n, n * sizeof(float));
-        out.emplace_back(h->width, h->height);
-        for (size_t i = 0; i < n; ++i) out.back().DataPtr()[i] = -12345.f;  // poisoned, as in flow2d_host_compute_flow
-    }
-    flow2d_host_params p = *params;
-    OperationParameters bag;
-    FillBag(bag, p);
-    std::vector<Data2D*> fp;
-    for (Data2D& d : f) fp.push_back(&d);
-    h->flow.StabiliseSequence(fp.data(), frame_count, reference_index, model, sigma, iterations, use_masks != 0, fill, out.data(),
-                              motions, bag);
-    for (size_t k = 0; k < frame_count; ++k) std::memcpy(outputs + k * n, out[k].DataPtr(), n * sizeof(float));
-    if (total_ms) *total_ms = h->flow.LastTotalMs();
-    return h->flow.LastRunSucceeded() ? 0 : 2;
+    HostImages im(h);
+    const std::vector<Data2D*> fp = Pointers(im.In(frames, frame_count), frame_count);
+    Data2D* out = im.Out(outputs, im.Always, frame_count);
+    Bag bag(*params);
+    h->flow.StabiliseSequence(fp.data(), frame_count, reference_index, model, sigma, iterations, use_masks != 0, fill, out, motions, bag);
+    return im.Finish(h->flow, total_ms);
 }
 
 // OpticalFlow2D::StabiliseSequenceDevice: frame_count device frames and output planes, motions (host, optional) frame_count
@@ -578,16 +529,9 @@ HOST_API int flow2d_host_stabilise_sequence_device(flow2d_host_flow* h, void* co
     if (!OpticalFlow2D::GlobalMotionArgsOk(model, sigma, iterations) || !h || !params || !dev_frames || !dev_outputs ||
         frame_count < 2 || reference_index >= frame_count)
         return 1;
-    flow2d_host_params p = *params;
-    OperationParameters bag;
-    FillBag(bag, p);
+    Bag bag(*params);
     h->flow.timing_mode = 0;
-    auto dp = [](void* q) { return static_cast<DevicePtr>(reinterpret_cast<uintptr_t>(q)); };
-    std::vector<DevicePtr> frames(frame_count), outputs(frame_count);
-    for (size_t k = 0; k < frame_count; ++k) {
-        frames[k] = dp(dev_frames[k]);
-        outputs[k] = dp(dev_outputs[k]);
-    }
+    const std::vector<DevicePtr> frames = DevicePtrs(dev_frames, frame_count), outputs = DevicePtrs(dev_outputs, frame_count);
     return h->flow.StabiliseSequenceDevice(frames.data(), frame_count, reference_index, model, sigma, iterations, use_masks != 0, fill,
                                            outputs.data(), motions, bag)
                ? 0
@@ -604,20 +548,12 @@ HOST_API int flow2d_host_compute_flow_bidirectional_device(flow2d_host_flow* h, 
 {
     if (!h || !params || !dev_frames || !dev_flows_u || !dev_flows_v || !dev_back_us || !dev_back_vs || frame_count < 2)
         return 1;
-    flow2d_host_params p = *params;
-    OperationParameters bag;
-    FillBag(bag, p);
-    bag.PushValuePtr("consistency_alpha1", &alpha1);
-    bag.PushValuePtr("consistency_alpha2", &alpha2);
+    Bag bag(*params, alpha1, alpha2);
     h->flow.timing_mode = 0;
-    auto dp = [](void* q) { return static_cast<DevicePtr>(reinterpret_cast<uintptr_t>(q)); };
-    const size_t n = frame_count - 1;
-    std::vector<DevicePtr> frames(frame_count), planes[6];
+    const std::vector<DevicePtr> frames = DevicePtrs(dev_frames, frame_count);
     void* const* sources[6] = {dev_flows_u, dev_flows_v, dev_back_us, dev_back_vs, dev_occ_fwd, dev_occ_bwd};
-    for (size_t k = 0; k < frame_count; ++k) frames[k] = dp(dev_frames[k]);
-    for (int i = 0; i < 6; ++i)
-        if (sources[i])
-            for (size_t k = 0; k < n; ++k) planes[i].push_back(dp(sources[i][k]));
+    std::vector<DevicePtr> planes[6];
+    for (int i = 0; i < 6; ++i) planes[i] = DevicePtrs(sources[i], frame_count - 1);
     auto arr = [&](int i) { return sources[i] ? planes[i].data() : nullptr; };
     return h->flow.ComputeFlowBidirectionalDevice(frames.data(), frame_count, arr(0), arr(1), arr(2), arr(3), arr(4), arr(5), bag)
                ? 0
@@ -667,17 +603,9 @@ HOST_API int flow2d_host_batch_compute(flow2d_host_batch* h, size_t count, void*
                                        const flow2d_host_params* params, size_t first_lane)
 {
     if (!h || !params || (count && (!dev_frames_0 || !dev_frames_1 || !dev_flows_u || !dev_flows_v))) return 1;
-    flow2d_host_params p = *params;
-    OperationParameters bag;
-    FillBag(bag, p);
-    auto dp = [](void* q) { return static_cast<DevicePtr>(reinterpret_cast<uintptr_t>(q)); };
-    std::vector<DevicePtr> f0(count), f1(count), u(count), v(count);
-    for (size_t k = 0; k < count; ++k) {
-        f0[k] = dp(dev_frames_0[k]);
-        f1[k] = dp(dev_frames_1[k]);
-        u[k] = dp(dev_flows_u[k]);
-        v[k] = dp(dev_flows_v[k]);
-    }
+    Bag bag(*params);
+    const std::vector<DevicePtr> f0 = DevicePtrs(dev_frames_0, count), f1 = DevicePtrs(dev_frames_1, count),
+                                 u = DevicePtrs(dev_flows_u, count), v = DevicePtrs(dev_flows_v, count);
     return h->batch.ComputeFlowBatchDevice(count, f0.data(), f1.data(), u.data(), v.data(), bag, first_lane) ? 0 : 2;
 }
 
@@ -688,17 +616,9 @@ HOST_API int flow2d_host_batch_compute_grouped(flow2d_host_batch* h, size_t coun
                                                size_t first_lane)
 {
     if (!h || !params || (count && (!dev_frames_0 || !dev_frames_1 || !dev_flows_u || !dev_flows_v))) return 1;
-    flow2d_host_params p = *params;
-    OperationParameters bag;
-    FillBag(bag, p);
-    auto dp = [](void* q) { return static_cast<DevicePtr>(reinterpret_cast<uintptr_t>(q)); };
-    std::vector<DevicePtr> f0(count), f1(count), u(count), v(count);
-    for (size_t k = 0; k < count; ++k) {
-        f0[k] = dp(dev_frames_0[k]);
-        f1[k] = dp(dev_frames_1[k]);
-        u[k] = dp(dev_flows_u[k]);
-        v[k] = dp(dev_flows_v[k]);
-    }
+    Bag bag(*params);
+    const std::vector<DevicePtr> f0 = DevicePtrs(dev_frames_0, count), f1 = DevicePtrs(dev_frames_1, count),
+                                 u = DevicePtrs(dev_flows_u, count), v = DevicePtrs(dev_flows_v, count);
     return h->batch.ComputeFlowBatchDeviceGrouped(count, f0.data(), f1.data(), u.data(), v.data(), bag, first_lane) ? 0 : 2;
 }
 
@@ -725,9 +645,7 @@ HOST_API int flow2d_host_batch_compute_host(flow2d_host_batch* h, size_t count, 
                                             const flow2d_host_params* params, size_t first_lane)
 {
     if (!h || !params) return 1;
-    flow2d_host_params p = *params;
-    OperationParameters bag;
-    FillBag(bag, p);
+    Bag bag(*params);
     return h->batch.ComputeFlowBatch(count, frames_0, frames_1, flows_u, flows_v, bag, first_lane) ? 0 : 2;
 }
 
@@ -770,14 +688,13 @@ HOST_API int flow2d_host_missing_key_leaves_outputs(flow2d_host_flow* h, const c
     Data2D f0(h->width, h->height), f1(h->width, h->height), u(h->width, h->height), v(h->width, h->height);
     const size_t n = h->width * h->height;
     for (size_t i = 0; i < n; ++i) u.DataPtr()[i] = v.DataPtr()[i] = 77.f;
-    flow2d_host_params p = {3, 0.5f, 1, 1, 3.5f, 0.001f, 0.001f, 5, 0.45f, 0, 0.f};
-    OperationParameters full, bag;
-    FillBag(full, p);
+    Bag full(flow2d_host_params{3, 0.5f, 1, 1, 3.5f, 0.001f, 0.001f, 5, 0.45f, 0, 0.f});
+    OperationParameters bag;
     const char* keys[] = {"warp_levels_count", "warp_scale_factor", "outer_iterations_count",
                           "inner_iterations_count", "equation_alpha", "equation_smoothness",
                           "equation_data", "median_radius", "gaussian_sigma"};
     for (const char* k : keys)
-        if (std::strcmp(k, omitted_key) != 0) bag.PushValuePtr(k, full.GetValuePtr(k));
+        if (std::strcmp(k, omitted_key) != 0) bag.PushValuePtr(k, full.bag.GetValuePtr(k));
     h->flow.ComputeFlow(f0, f1, u, v, bag);
     for (size_t i = 0; i < n; ++i)
         if (u.DataPtr()[i] != 77.f || v.DataPtr()[i] != 77.f) return 0;

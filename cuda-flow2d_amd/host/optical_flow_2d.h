@@ -293,6 +293,45 @@ public:
     bool lone = true;
 
 private:
+    // Device planes beside the pool that the object keeps until Destroy(); an entry of 0 is a plane not allocated yet.
+    // Constructing one registers it with the object (`owned_`), and Destroy() frees every registered plane in one loop: a new
+    // member cannot be forgotten there.
+    class OwnedPlanes {
+    public:
+        explicit OwnedPlanes(std::vector<OwnedPlanes*>& registry, size_t count = 0) : planes_(count, 0) { registry.push_back(this); }
+        OwnedPlanes(const OwnedPlanes&) = delete;
+        OwnedPlanes& operator=(const OwnedPlanes&) = delete;
+        // the array, grown to `count` entries when it has fewer
+        DevicePtr* AtLeast(size_t count)
+        {
+            if (planes_.size() < count) planes_.resize(count, 0);
+            return planes_.data();
+        }
+        DevicePtr& operator[](size_t i) { return planes_[i]; }
+        DevicePtr operator[](size_t i) const { return planes_[i]; }
+        const DevicePtr* data() const { return planes_.data(); }
+        DevicePtr* begin() { return planes_.data(); }
+        DevicePtr* end() { return planes_.data() + planes_.size(); }
+
+    private:
+        std::vector<DevicePtr> planes_;
+    };
+    // One device allocation addressed by byte offsets: an entry's record first, its workspace behind it.
+    struct DeviceScratch {
+        explicit DeviceScratch(std::vector<OwnedPlanes*>& registry) : block(registry, 1) {}
+        // At least `bytes`.  Grows only when a call asks for more than there is: the stream is drained (queued work may still use
+        // the old block), the old block freed and a new one allocated.
+        bool Ensure(flow2d_context* context, size_t bytes);
+        template <class T = char>
+        T* At(size_t offset = 0) const
+        {
+            return reinterpret_cast<T*>(static_cast<size_t>(block[0]) + offset);
+        }
+        OwnedPlanes block;
+        size_t bytes = 0;
+    };
+    std::vector<OwnedPlanes*> owned_;  // (declared before the planes that register with it)
+
     bool InitMemory();
     bool InitOperations();
     bool RunPyramid(OperationParameters& params);
@@ -309,13 +348,13 @@ private:
     DataSize3 dev_container_size_{0, 0, 0};
     size_t group_ = 1;  // group_size as it was at Initialize
     size_t active_group_ = 1;  // pairs of the group being queued (a scattered group may be smaller than group_)
-    DevicePtr group_staging_[4] = {0, 0, 0, 0};  // ComputeFlowGroupDevice: tall frame 0, frame 1, flow u, flow v (first use)
+    OwnedPlanes group_staging_{owned_, 4};  // ComputeFlowGroupDevice: tall frame 0, frame 1, flow u, flow v (first use)
     std::vector<DevicePtr> all_planes_;
     std::vector<DevicePtr> free_planes_;
     DevicePtr dev_frame_0_ = 0, dev_frame_1_ = 0, dev_flow_u_ = 0, dev_flow_v_ = 0;  // valid inside a run
     // Two planes beside the pool: the x-resampled rows of all pyramid levels of frame 0 / frame 1, side by side
     // (flow2d_resample_x_levels: one read of each frame for the x passes of the whole pyramid)
-    DevicePtr packed_frames_[2] = {0, 0};
+    OwnedPlanes packed_frames_{owned_, 2};
     // ComputeFlowDevice only: the caller's planes.  With a pre-blur the frames are read once (by the blur), so
     // they are read in place instead of copied; the last level's median writes the caller's flow planes.
     DevicePtr caller_frame_0_ = 0, caller_frame_1_ = 0, caller_flow_u_ = 0, caller_flow_v_ = 0;
@@ -337,12 +376,20 @@ private:
     bool RunSequencePair(FramePyramid& first, FramePyramid& second, DevicePtr frame_0, DevicePtr frame_1, DevicePtr flow_u,
                          DevicePtr flow_v, OperationParameters& params);
     // ComputeFlowBidirectional: both frames and the six outputs, outside the pool (allocated on first use)
-    DevicePtr bidirectional_planes_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    OwnedPlanes bidirectional_planes_{owned_, 8};
     // InterpolateFrames*: the flows and masks of a pair (u, v, back u, back v, occlusion 0, occlusion 1) and the host form's
     // output frames, outside the pool (allocated on first use)
-    DevicePtr interpolation_planes_[6] = {0, 0, 0, 0, 0, 0};
-    std::vector<DevicePtr> interpolation_outputs_;
+    OwnedPlanes interpolation_planes_{owned_, 6};
+    OwnedPlanes interpolation_outputs_{owned_};
+    // full-size planes where `planes` has none yet (0); the second form grows the array to `count` entries first
     bool EnsurePlanes(DevicePtr* planes, size_t count);
+    bool EnsurePlanes(OwnedPlanes& planes, size_t count) { return EnsurePlanes(planes.AtLeast(count), count); }
+    // "... and lock-step groups do not combine": prints that and returns true for an object initialised with a group size > 1
+    bool RefuseGroup(const char* what) const;
+    // `bytes` from device memory into host memory, queued on the stream
+    bool ReadRecord(void* host, const void* device, size_t bytes);
+    // `count` (1 or 2) planes src[i] -> dst[i] with one launch; nothing when the caller gave no planes to fill (dst[0] == 0)
+    bool HandBack(size_t count, const DevicePtr* src, const DevicePtr* dst);
     bool InterpolationArgsOk(const float* times, size_t time_count, int iterations, float max_residual);
     // the flow2d_interpolate_2d launches of one pair: flows = u, v, back u, back v, occlusion 0, occlusion 1 (masks unused when
     // !use_masks)
@@ -350,35 +397,33 @@ private:
                             size_t time_count, const DevicePtr* outputs, int iterations, float max_residual);
     // TrackPointsDevice: the flows of a window (u, v, back u, back v per pair) and, in one allocation, the device count and the
     // seeding workspace (allocated on first use, the scratch regrown when a call needs more)
-    std::vector<DevicePtr> tracking_flows_;
-    DevicePtr tracking_scratch_ = 0;
-    size_t tracking_scratch_bytes_ = 0;
-    DevicePtr AllocBytes(size_t bytes);
+    OwnedPlanes tracking_flows_{owned_};
+    DeviceScratch tracking_scratch_{owned_};
     // DenoiseSequenceDevice: the ring of pairs (u, v, back u, back v, occlusion forward, occlusion backward per slot; the masks
     // allocated on the first call with use_masks) and the composed flows of a centre (u, v, mask per direction and distance >= 2)
-    std::vector<DevicePtr> denoise_pairs_;
-    std::vector<DevicePtr> denoise_chains_;
+    OwnedPlanes denoise_pairs_{owned_, 6 * (2 * kDenoiseMaxRadius + kDenoiseWindow)};
+    OwnedPlanes denoise_chains_{owned_, 2 * (kDenoiseMaxRadius - 1) * 3};
     // EstimateGlobalMotion* / StabiliseSequence*: the flows of a window (u, v, back u, back v, occlusion forward, occlusion
     // backward per pair; allocated as needed) and, in one allocation, kStabiliseWindow + 1 records and the fit's workspace
-    std::vector<DevicePtr> stabilise_planes_;
-    DevicePtr stabilise_scratch_ = 0;
+    OwnedPlanes stabilise_planes_{owned_, 6 * kStabiliseWindow};
+    DeviceScratch stabilise_scratch_{owned_};
     bool EnsureStabiliseScratch();
-    flow2d_global_motion* StabiliseRecord(size_t slot) const;
+    flow2d_global_motion* StabiliseRecord(size_t slot) const { return stabilise_scratch_.At<flow2d_global_motion>() + slot; }
     // the records of the flows frames[i] -> frames[i + 1], i < count - 1, of an ordered list of frames into records[i]
     bool FitConsecutivePairs(const DevicePtr* frames, size_t count, int model, double sigma, int iterations, bool use_masks,
                              flow2d_global_motion* records, OperationParameters& params);
     // SegmentMotion*: residual u, residual v and labels, and in one allocation the summary, kSegmentMaxRegions records and the
     // workspace (allocated on first use)
-    DevicePtr segment_planes_[3] = {0, 0, 0};
-    DevicePtr segment_scratch_ = 0;
+    OwnedPlanes segment_planes_{owned_, 3};
+    DeviceScratch segment_scratch_{owned_};
     // AnalyseDeformation*: the pair's flow (u, v, back u, back v, occlusion forward, occlusion backward; the last four with
     // use_masks only), the smoothed flow (u, v; with a sigma only) and, in one allocation, the record and the workspace
-    DevicePtr deformation_planes_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    DevicePtr deformation_scratch_ = 0;
+    OwnedPlanes deformation_planes_{owned_, 8};
+    DeviceScratch deformation_scratch_{owned_};
     flow2d_context* context_ = nullptr;
     // One plane beside the pool: the warped frame of a level, when the levels of both frames are computed up front into plane
     // regions of their own (RunPyramid: "stacked" levels) and therefore cannot be overwritten by the warp
-    DevicePtr level_warp_plane_ = 0;
+    OwnedPlanes level_warp_plane_{owned_, 1};
     float last_total_ms_ = 0.f;
     bool last_run_ok_ = false;
     // recorded pyramids, keyed by the caller buffers and parameters they were recorded for

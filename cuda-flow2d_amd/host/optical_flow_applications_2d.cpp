@@ -1,0 +1,633 @@
+// The applications built on the flow: frame interpolation, point trajectories, global motion and stabilisation, motion
+// segmentation, deformation analysis and temporal denoising.  Each has a ...Device entry on planes that already sit on the device
+// and a host-image entry that uploads, calls it and downloads (CallPlanes + HostCall, host_entry.h).  The flow itself -- the
+// pyramid, the sequence cache, ComputeFlow* -- is optical_flow_2d.cpp.
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+
+#include "host_entry.h"
+#include "optical_flow_2d.h"
+
+bool OpticalFlow2D::InterpolationArgsOk(const float* times, size_t time_count, int iterations, float max_residual)
+{
+    if (!times || time_count == 0) return false;
+    for (size_t j = 0; j < time_count; ++j)
+        if (!(std::isfinite(times[j]) && times[j] >= 0.f && times[j] <= 1.f)) {
+            std::printf("Error: '%s': interpolation time %g (0 <= t <= 1).\n", GetName(), times[j]);
+            return false;
+        }
+    if (iterations < 1 || iterations > 16 || !std::isfinite(max_residual) || max_residual < 0.f) {
+        std::printf("Error: '%s': interpolation iterations %d (1 .. 16) / max residual %g (finite, >= 0).\n", GetName(),
+                    iterations, max_residual);
+        return false;
+    }
+    return true;
+}
+
+bool OpticalFlow2D::QueueInterpolation(DevicePtr frame_0, DevicePtr frame_1, const DevicePtr* flows, bool use_masks,
+                                       const float* times, size_t time_count, const DevicePtr* outputs, int iterations,
+                                       float max_residual)
+{
+    const size_t W = dev_container_size_.width, H = dev_container_size_.height, pitch = dev_container_size_.pitch;
+    for (size_t j = 0; j < time_count; ++j)
+        if (CheckFlow2DError(flow2d_interpolate_2d(context_, AsPlane(frame_0), AsPlane(frame_1), AsPlane(flows[0]), AsPlane(flows[1]),
+                                                   AsPlane(flows[2]), AsPlane(flows[3]), use_masks ? AsPlane(flows[4]) : nullptr,
+                                                   use_masks ? AsPlane(flows[5]) : nullptr, W, H, pitch, times[j], iterations,
+                                                   max_residual, AsPlane(outputs[j])),
+                             "flow2d_interpolate_2d"))
+            return false;
+    return true;
+}
+
+bool OpticalFlow2D::InterpolateFramesDevice(const DevicePtr* dev_frames, size_t frame_count, const float* times, size_t time_count,
+                                            const DevicePtr* dev_outputs, int iterations, float max_residual, bool use_masks,
+                                            OperationParameters& params)
+{
+    if (!IsInitialized() || !dev_frames || !dev_outputs || frame_count < 2) return false;
+    if (RefuseGroup("sequences")) return false;
+    if (!InterpolationArgsOk(times, time_count, iterations, max_residual)) return false;
+    // every output must be distinct from every other one and from the frames (which are only read)
+    if (!WrittenPlanesOk(dev_frames, frame_count, dev_outputs, (frame_count - 1) * time_count, "output plane")) return false;
+    if (!EnsurePlanes(interpolation_planes_, 6)) return false;
+    const DevicePtr* p = interpolation_planes_.data();  // u, v, back u, back v, occlusion 0, occlusion 1
+    bool ok = true;
+    for (size_t k = 0; ok && k + 1 < frame_count; ++k) {
+        ok = ComputeFlowBidirectionalDevice(dev_frames + k, 2, p, p + 1, p + 2, p + 3, use_masks ? p + 4 : nullptr,
+                                            use_masks ? p + 5 : nullptr, params) &&
+             QueueInterpolation(dev_frames[k], dev_frames[k + 1], p, use_masks, times, time_count, dev_outputs + k * time_count,
+                                iterations, max_residual);
+    }
+    return ok;
+}
+
+void OpticalFlow2D::InterpolateFrames(Data2D& frame_0, Data2D& frame_1, const float* times, size_t time_count, Data2D* outputs,
+                                      int iterations, float max_residual, bool use_masks, OperationParameters& params,
+                                      Data2D* flow_u, Data2D* flow_v, Data2D* back_u, Data2D* back_v, Data2D* occlusion_0,
+                                      Data2D* occlusion_1)
+{
+    last_run_ok_ = false;
+    if (!IsInitialized() || !outputs) return;
+    if (RefuseGroup("sequences")) return;
+    if (!InterpolationArgsOk(times, time_count, iterations, max_residual)) return;
+    const size_t H = dev_container_size_.height;
+    Data2D* flows[6] = {flow_u, flow_v, back_u, back_v, use_masks ? occlusion_0 : nullptr, use_masks ? occlusion_1 : nullptr};
+    std::vector<Data2D*> images = {&frame_0, &frame_1};
+    for (size_t j = 0; j < time_count; ++j) images.push_back(outputs + j);
+    for (Data2D* d : flows)
+        if (d) images.push_back(d);
+    if (!SizeCheck{dev_container_size_, GetName(), "frame / output"}(images.data(), images.size())) return;
+    if (!EnsurePlanes(bidirectional_planes_, 2) || !EnsurePlanes(interpolation_planes_, 6) ||
+        !EnsurePlanes(interpolation_outputs_, time_count))
+        return;
+    HostCall call(context_, last_total_ms_);
+    const size_t pitch = dev_container_size_.pitch;
+    const DevicePtr* f = bidirectional_planes_.data();  // frame 0, frame 1
+    bool ok = CopyData2DtoDevice(frame_0, f[0], H, pitch) && CopyData2DtoDevice(frame_1, f[1], H, pitch) &&
+              InterpolateFramesDevice(f, 2, times, time_count, interpolation_outputs_.data(), iterations, max_residual, use_masks,
+                                      params);
+    for (size_t j = 0; ok && j < time_count; ++j) ok = CopyData2DFromDevice(interpolation_outputs_[j], outputs[j], H, pitch);
+    for (int i = 0; ok && i < 6; ++i)
+        if (flows[i]) ok = CopyData2DFromDevice(interpolation_planes_[i], *flows[i], H, pitch);
+    last_run_ok_ = ok;
+}
+
+bool OpticalFlow2D::TrackPointsDevice(const DevicePtr* dev_frames, size_t frame_count, size_t spacing, float min_eigenvalue,
+                                      bool check_boundaries, float beta1, float beta2, const DevicePtr* dev_xs,
+                                      const DevicePtr* dev_ys, size_t capacity, unsigned long long* counts_out,
+                                      OperationParameters& params)
+{
+    if (!IsInitialized() || !dev_frames || !dev_xs || !dev_ys || !counts_out || frame_count < 2 || capacity == 0) return false;
+    if (RefuseGroup("sequences")) return false;
+    if (spacing == 0 || !(std::isfinite(min_eigenvalue) && min_eigenvalue >= 0.f) ||
+        !(std::isfinite(beta1) && beta1 >= 0.f && std::isfinite(beta2) && beta2 >= 0.f)) {
+        std::printf("Error: '%s': tracking spacing %zu (>= 1), min eigenvalue %g, boundary thresholds %g / %g (finite, >= 0).\n",
+                    GetName(), spacing, min_eigenvalue, beta1, beta2);
+        return false;
+    }
+    float alpha1 = 0.01f, alpha2 = 0.5f;  // Sundaram, Brox & Keutzer (ECCV 2010)
+    params.Read<float>("consistency_alpha1", alpha1);
+    params.Read<float>("consistency_alpha2", alpha2);
+    if (!(std::isfinite(alpha1) && std::isfinite(alpha2) && alpha1 >= 0.f && alpha2 >= 0.f)) {
+        std::printf("Error: '%s': consistency thresholds %g / %g (finite, >= 0).\n", GetName(), alpha1, alpha2);
+        return false;
+    }
+    // every table is written: distinct from each other and from the frames
+    std::vector<DevicePtr> tables(dev_xs, dev_xs + frame_count);
+    tables.insert(tables.end(), dev_ys, dev_ys + frame_count);
+    if (!WrittenPlanesOk(dev_frames, frame_count, tables.data(), tables.size(), "track table")) return false;
+    const size_t W = dev_container_size_.width, H = dev_container_size_.height, pitch = dev_container_size_.pitch;
+    const size_t window = std::min(kTrackWindow, frame_count - 1);
+    if (!EnsurePlanes(tracking_flows_, 4 * window)) return false;
+    // the device count (16 bytes) and the seeding workspace behind it
+    const size_t workspace_bytes = flow2d_seed_points_workspace_bytes(W, H, spacing);
+    if (!tracking_scratch_.Ensure(context_, 16 + workspace_bytes)) return false;
+    unsigned long long* dev_count = tracking_scratch_.At<unsigned long long>();
+    void* workspace = tracking_scratch_.At(16);
+    void* host_counts = nullptr;  // page-locked: the per-frame counts are copied into it on the stream
+    if (CheckFlow2DError(flow2d_host_alloc(context_, frame_count * sizeof(unsigned long long), &host_counts), "flow2d_host_alloc"))
+        return false;
+    unsigned long long* counts = static_cast<unsigned long long*>(host_counts);
+    const size_t table_bytes = capacity * sizeof(float);
+    auto seed = [&](size_t k) {
+        return !CheckFlow2DError(flow2d_seed_points_2d(context_, AsPlane(dev_frames[k]), W, H, pitch, spacing, min_eigenvalue,
+                                                       AsPlane(dev_xs[k]), AsPlane(dev_ys[k]), dev_count, capacity, nullptr,
+                                                       workspace, workspace_bytes),
+                                 "flow2d_seed_points_2d") &&
+               ReadRecord(counts + k, dev_count, sizeof(unsigned long long));
+    };
+    // table 0: no track yet (all NaN: 0xff bytes), count 0, then the initial seeding
+    bool ok = !CheckFlow2DError(flow2d_memset_2d(context_, AsPlane(dev_xs[0]), table_bytes, 0xff, table_bytes, 1), "flow2d_memset_2d") &&
+              !CheckFlow2DError(flow2d_memset_2d(context_, AsPlane(dev_ys[0]), table_bytes, 0xff, table_bytes, 1), "flow2d_memset_2d") &&
+              !CheckFlow2DError(flow2d_memset_2d(context_, dev_count, 16, 0, 16, 1), "flow2d_memset_2d") && seed(0);
+    const DevicePtr* f = tracking_flows_.data();  // pair j of a window: u, v, back u, back v at 4 j
+    for (size_t start = 0; ok && start + 1 < frame_count; start += window) {
+        const size_t pairs = std::min(window, frame_count - 1 - start);
+        std::vector<DevicePtr> us(pairs), vs(pairs), bus(pairs), bvs(pairs);
+        for (size_t j = 0; j < pairs; ++j) {
+            us[j] = f[4 * j];
+            vs[j] = f[4 * j + 1];
+            bus[j] = f[4 * j + 2];
+            bvs[j] = f[4 * j + 3];
+        }
+        ok = ComputeFlowBidirectionalDevice(dev_frames + start, pairs + 1, us.data(), vs.data(), bus.data(), bvs.data(), nullptr,
+                                            nullptr, params);
+        for (size_t j = 0; ok && j < pairs; ++j) {
+            const size_t k = start + j;
+            ok = !CheckFlow2DError(flow2d_track_points_2d(context_, AsPlane(us[j]), AsPlane(vs[j]), AsPlane(bus[j]), AsPlane(bvs[j]),
+                                                          W, H, pitch, AsPlane(dev_xs[k]), AsPlane(dev_ys[k]), dev_count,
+                                                          capacity, alpha1, alpha2, check_boundaries ? 1 : 0, beta1, beta2,
+                                                          AsPlane(dev_xs[k + 1]), AsPlane(dev_ys[k + 1]), nullptr),
+                                   "flow2d_track_points_2d") &&
+                 seed(k + 1);
+        }
+    }
+    ok = !CheckFlow2DError(flow2d_synchronize(context_), "flow2d_synchronize") && ok;  // the only host wait
+    if (ok)
+        for (size_t k = 0; k < frame_count; ++k) counts_out[k] = counts[k];
+    flow2d_host_free(context_, host_counts);
+    return ok;
+}
+
+void OpticalFlow2D::TrackPoints(Data2D* const* frames, size_t frame_count, size_t spacing, float min_eigenvalue,
+                                bool check_boundaries, float beta1, float beta2, float* xs, float* ys, size_t capacity,
+                                unsigned long long* counts_out, OperationParameters& params)
+{
+    last_run_ok_ = false;
+    if (!IsInitialized() || !frames || !xs || !ys || !counts_out || frame_count < 2 || capacity == 0) return;
+    if (RefuseGroup("sequences")) return;
+    // the planes of this call: the frames, then the x tables, then the y tables
+    const size_t n = frame_count, table_bytes = capacity * sizeof(float);
+    CallPlanes planes(context_, dev_container_size_, GetName(), "frame");
+    planes.Add(frames, n, CallPlanes::In).AddBytes(table_bytes, 2 * n);
+    if (!planes.SizesMatch()) return;
+    HostCall call(context_, last_total_ms_, planes.Allocate());
+    const DevicePtr *d = planes.data(), *dev_xs = d + n, *dev_ys = d + 2 * n;
+    bool ok = planes.Upload() && TrackPointsDevice(d, n, spacing, min_eigenvalue, check_boundaries, beta1, beta2, dev_xs, dev_ys,
+                                                   capacity, counts_out, params);
+    for (size_t k = 0; ok && k < n; ++k)
+        ok = ReadRecord(xs + k * capacity, AsPlane(dev_xs[k]), table_bytes) && ReadRecord(ys + k * capacity, AsPlane(dev_ys[k]), table_bytes);
+    last_run_ok_ = ok;
+}
+
+bool OpticalFlow2D::GlobalMotionArgsOk(int model, double sigma, int iterations)
+{
+    if ((model != FLOW2D_MOTION_TRANSLATION && model != FLOW2D_MOTION_SIMILARITY && model != FLOW2D_MOTION_AFFINE) ||
+        !std::isfinite(sigma) || sigma < 0.0 || iterations < 0 || iterations > FLOW2D_GLOBAL_MOTION_MAX_ITERATIONS) {
+        std::printf("Error: global motion takes a model of 0 (translation), 1 (similarity) or 2 (affine) (%d), a finite sigma >= 0 (%g) "
+                    "and 0 .. %d iterations (%d).\n",
+                    model, sigma, FLOW2D_GLOBAL_MOTION_MAX_ITERATIONS, iterations);
+        return false;
+    }
+    return true;
+}
+
+flow2d_global_motion OpticalFlow2D::ComposeGlobalMotion(const flow2d_global_motion& first, const flow2d_global_motion& second)
+{
+    const double a1[4] = {1.0 + first.p[1], first.p[2], first.p[4], 1.0 + first.p[5]};
+    const double a2[4] = {1.0 + second.p[1], second.p[2], second.p[4], 1.0 + second.p[5]};
+    flow2d_global_motion out = second;  // weight_sum, support: the newest fit's
+    const double a11 = a2[0] * a1[0] + a2[1] * a1[2], a12 = a2[0] * a1[1] + a2[1] * a1[3];
+    const double a21 = a2[2] * a1[0] + a2[3] * a1[2], a22 = a2[2] * a1[1] + a2[3] * a1[3];
+    out.p[0] = (a2[0] * first.p[0] + a2[1] * first.p[3]) + second.p[0];
+    out.p[1] = a11 - 1.0;
+    out.p[2] = a12;
+    out.p[3] = (a2[2] * first.p[0] + a2[3] * first.p[3]) + second.p[3];
+    out.p[4] = a21;
+    out.p[5] = a22 - 1.0;
+    out.model_used = std::max(first.model_used, second.model_used);
+    return out;
+}
+
+bool OpticalFlow2D::EnsureStabiliseScratch()
+{
+    const size_t records = (kStabiliseWindow + 1) * sizeof(flow2d_global_motion);  // a multiple of 16
+    return stabilise_scratch_.Ensure(context_, records + flow2d_global_motion_workspace_bytes(dev_container_size_.width,
+                                                                                               dev_container_size_.height, 1));
+}
+
+bool OpticalFlow2D::FitConsecutivePairs(const DevicePtr* frames, size_t count, int model, double sigma, int iterations,
+                                        bool use_masks, flow2d_global_motion* records, OperationParameters& params)
+{
+    if (count < 2) return true;
+    const size_t W = dev_container_size_.width, H = dev_container_size_.height, pitch = dev_container_size_.pitch;
+    const size_t per_pair = use_masks ? 6 : 2;
+    for (size_t j = 0; j < kStabiliseWindow; ++j)
+        if (!EnsurePlanes(&stabilise_planes_[6 * j], per_pair)) return false;
+    if (!EnsureStabiliseScratch()) return false;
+    void* workspace = StabiliseRecord(kStabiliseWindow + 1);
+    const size_t workspace_bytes = flow2d_global_motion_workspace_bytes(W, H, 1);
+    bool ok = true;
+    for (size_t start = 0; ok && start + 1 < count; start += kStabiliseWindow) {
+        const size_t pairs = std::min(kStabiliseWindow, count - 1 - start);
+        std::vector<DevicePtr> p[6];
+        for (size_t j = 0; j < pairs; ++j)
+            for (size_t i = 0; i < 6; ++i) p[i].push_back(stabilise_planes_[6 * j + i]);
+        ok = use_masks ? ComputeFlowBidirectionalDevice(frames + start, pairs + 1, p[0].data(), p[1].data(), p[2].data(), p[3].data(),
+                                                        p[4].data(), p[5].data(), params)
+                       : ComputeFlowSequenceDevice(frames + start, pairs + 1, p[0].data(), p[1].data(), params);
+        for (size_t j = 0; ok && j < pairs; ++j)
+            ok = !CheckFlow2DError(flow2d_global_motion_2d(context_, AsPlane(p[0][j]), AsPlane(p[1][j]),
+                                                           use_masks ? AsPlane(p[4][j]) : nullptr, W, H, pitch, model, sigma,
+                                                           iterations, StabiliseRecord(j), workspace, workspace_bytes),
+                                   "flow2d_global_motion_2d") &&
+                 ReadRecord(records + start + j, StabiliseRecord(j), sizeof(flow2d_global_motion));
+        // the records are read by the host next, and the window's planes and record slots are reused
+        ok = !CheckFlow2DError(flow2d_synchronize(context_), "flow2d_synchronize") && ok;
+    }
+    return ok;
+}
+
+bool OpticalFlow2D::EstimateGlobalMotionDevice(DevicePtr dev_frame_0, DevicePtr dev_frame_1, int model, double sigma,
+                                               int iterations, bool use_masks, flow2d_global_motion* motion_out,
+                                               OperationParameters& params, DevicePtr dev_flow_u, DevicePtr dev_flow_v,
+                                               DevicePtr dev_residual_u, DevicePtr dev_residual_v)
+{
+    if (!GlobalMotionArgsOk(model, sigma, iterations)) return false;
+    if (!IsInitialized() || !dev_frame_0 || !dev_frame_1 || !motion_out) return false;
+    if (RefuseGroup("global motion")) return false;
+    if ((dev_flow_u == 0) != (dev_flow_v == 0) || (dev_residual_u == 0) != (dev_residual_v == 0)) return false;
+    const DevicePtr frames[2] = {dev_frame_0, dev_frame_1};
+    if (!FitConsecutivePairs(frames, 2, model, sigma, iterations, use_masks, motion_out, params)) return false;
+    // the pair's flow and record are still in slot 0
+    const size_t W = dev_container_size_.width, H = dev_container_size_.height, pitch = dev_container_size_.pitch;
+    const DevicePtr flow[2] = {dev_flow_u, dev_flow_v};
+    bool ok = HandBack(2, stabilise_planes_.data(), flow);
+    if (ok && dev_residual_u)
+        ok = !CheckFlow2DError(flow2d_global_flow_2d(context_, StabiliseRecord(0), AsPlane(stabilise_planes_[0]),
+                                                     AsPlane(stabilise_planes_[1]), nullptr, W, H, pitch, 0.0, nullptr, nullptr,
+                                                     AsPlane(dev_residual_u), AsPlane(dev_residual_v), nullptr),
+                               "flow2d_global_flow_2d");
+    return !CheckFlow2DError(flow2d_synchronize(context_), "flow2d_synchronize") && ok;
+}
+
+void OpticalFlow2D::EstimateGlobalMotion(Data2D& frame_0, Data2D& frame_1, int model, double sigma, int iterations, bool use_masks,
+                                         flow2d_global_motion* motion_out, OperationParameters& params, Data2D* flow_u,
+                                         Data2D* flow_v, Data2D* residual_u, Data2D* residual_v)
+{
+    last_run_ok_ = false;
+    if (!GlobalMotionArgsOk(model, sigma, iterations)) return;
+    if (!IsInitialized() || !motion_out) return;
+    // (the device entry is handed all four output planes, wanted or not)
+    CallPlanes planes(context_, dev_container_size_, GetName(), "frame / flow");
+    planes.Add(&frame_0, CallPlanes::In).Add(&frame_1, CallPlanes::In);
+    for (Data2D* image : {flow_u, flow_v, residual_u, residual_v}) planes.Add(image, CallPlanes::Out, true);
+    if (!planes.SizesMatch()) return;
+    HostCall call(context_, last_total_ms_, planes.Allocate());
+    const DevicePtr* d = planes.data();
+    last_run_ok_ = planes.Upload() &&
+                   EstimateGlobalMotionDevice(d[0], d[1], model, sigma, iterations, use_masks, motion_out, params, d[2], d[3], d[4], d[5]) &&
+                   planes.Download();
+}
+
+bool OpticalFlow2D::SegmentMotionArgsOk(float threshold, float join, unsigned min_area)
+{
+    if (!(threshold >= 0.f) || !(join >= 0.f) || min_area == 0) {
+        std::printf("Error: motion segmentation takes a threshold >= 0 (%g), a join >= 0, infinity allowed (%g), and a min_area >= 1 (%u).\n",
+                    threshold, join, min_area);
+        return false;
+    }
+    return true;
+}
+
+bool OpticalFlow2D::SegmentMotionDevice(DevicePtr dev_frame_0, DevicePtr dev_frame_1, int model, double sigma, int iterations,
+                                        bool use_masks, float threshold, float join, unsigned min_area,
+                                        flow2d_global_motion* motion_out, flow2d_segment_summary* summary_out,
+                                        flow2d_motion_region* regions_out, OperationParameters& params, DevicePtr dev_labels,
+                                        DevicePtr dev_residual_u, DevicePtr dev_residual_v)
+{
+    if (!GlobalMotionArgsOk(model, sigma, iterations) || !SegmentMotionArgsOk(threshold, join, min_area)) return false;
+    if (!IsInitialized() || !dev_frame_0 || !dev_frame_1 || !motion_out || !summary_out) return false;
+    if ((dev_residual_u == 0) != (dev_residual_v == 0)) return false;
+    const size_t W = dev_container_size_.width, H = dev_container_size_.height, pitch = dev_container_size_.pitch;
+    constexpr size_t kTableOffset = 64;  // the summary comes first
+    const size_t table_bytes = kSegmentMaxRegions * sizeof(flow2d_motion_region);
+    const size_t workspace_bytes = flow2d_segment_motion_workspace_bytes(W, H, 1);
+    if (!EnsurePlanes(segment_planes_, 3)) return false;
+    if (!segment_scratch_.Ensure(context_, kTableOffset + table_bytes + workspace_bytes)) return false;
+    // the flow, the fit and the residual planes (group_ > 1 is refused there); with use_masks the forward occlusion mask of
+    // the pair is still in the window's slot 0 afterwards
+    if (!EstimateGlobalMotionDevice(dev_frame_0, dev_frame_1, model, sigma, iterations, use_masks, motion_out, params, 0, 0,
+                                    segment_planes_[0], segment_planes_[1]))
+        return false;
+    flow2d_segment_summary* summary = segment_scratch_.At<flow2d_segment_summary>();
+    flow2d_motion_region* table = segment_scratch_.At<flow2d_motion_region>(kTableOffset);
+    bool ok = !CheckFlow2DError(
+        flow2d_segment_motion_2d(context_, AsPlane(segment_planes_[0]), AsPlane(segment_planes_[1]),
+                                 use_masks ? AsPlane(stabilise_planes_[4]) : nullptr, W, H, pitch, threshold, join, min_area,
+                                 reinterpret_cast<int*>(AsPlane(segment_planes_[2])), table, kSegmentMaxRegions, summary,
+                                 segment_scratch_.At(kTableOffset + table_bytes), workspace_bytes),
+        "flow2d_segment_motion_2d");
+    ok = ok && ReadRecord(summary_out, summary, sizeof(*summary_out)) && (!regions_out || ReadRecord(regions_out, table, table_bytes));
+    const DevicePtr own[3] = {segment_planes_[2], segment_planes_[0], segment_planes_[1]};
+    const DevicePtr callers[3] = {dev_labels, dev_residual_u, dev_residual_v};
+    ok = ok && HandBack(1, own, callers) && HandBack(2, own + 1, callers + 1);
+    return !CheckFlow2DError(flow2d_synchronize(context_), "flow2d_synchronize") && ok;
+}
+
+void OpticalFlow2D::SegmentMotion(Data2D& frame_0, Data2D& frame_1, int model, double sigma, int iterations, bool use_masks,
+                                  float threshold, float join, unsigned min_area, flow2d_global_motion* motion_out,
+                                  flow2d_segment_summary* summary_out, flow2d_motion_region* regions_out,
+                                  OperationParameters& params, Data2D* labels, Data2D* residual_u, Data2D* residual_v)
+{
+    last_run_ok_ = false;
+    if (!GlobalMotionArgsOk(model, sigma, iterations) || !SegmentMotionArgsOk(threshold, join, min_area)) return;
+    if (!IsInitialized() || !motion_out || !summary_out || (residual_u == nullptr) != (residual_v == nullptr)) return;
+    CallPlanes planes(context_, dev_container_size_, GetName(), "frame / labels / residual");
+    planes.Add(&frame_0, CallPlanes::In).Add(&frame_1, CallPlanes::In);
+    planes.Add(labels, CallPlanes::Out).Add(residual_u, CallPlanes::Out).Add(residual_v, CallPlanes::Out);
+    if (!planes.SizesMatch()) return;
+    HostCall call(context_, last_total_ms_, planes.Allocate());
+    const DevicePtr* d = planes.data();
+    last_run_ok_ = planes.Upload() &&
+                   SegmentMotionDevice(d[0], d[1], model, sigma, iterations, use_masks, threshold, join, min_area, motion_out, summary_out,
+                                       regions_out, params, d[2], d[3], d[4]) &&
+                   planes.Download();
+}
+
+bool OpticalFlow2D::DeformationArgsOk(int measure, float smoothing_sigma)
+{
+    // (the blur runs with up to 51 taps, 3 sigma to each side: flow2d_gaussian_kernel)
+    if ((measure != FLOW2D_STRAIN_SMALL && measure != FLOW2D_STRAIN_GREEN_LAGRANGE) || !(smoothing_sigma >= 0.f) ||
+        !(smoothing_sigma < 26.f / 3.f)) {
+        std::printf("Error: deformation analysis takes a strain measure 0 (small) or 1 (Green-Lagrange) (%d) and a smoothing sigma in [0, 8.66] (%g).\n",
+                    measure, smoothing_sigma);
+        return false;
+    }
+    return true;
+}
+
+bool OpticalFlow2D::AnalyseDeformationDevice(DevicePtr dev_frame_0, DevicePtr dev_frame_1, int measure, float smoothing_sigma,
+                                             bool use_masks, const DevicePtr* dev_planes, flow2d_deformation_stats* stats_out,
+                                             OperationParameters& params, DevicePtr dev_flow_u, DevicePtr dev_flow_v,
+                                             DevicePtr dev_mask)
+{
+    if (!DeformationArgsOk(measure, smoothing_sigma)) return false;
+    if (!IsInitialized() || !dev_frame_0 || !dev_frame_1 || (dev_flow_u == 0) != (dev_flow_v == 0) || (dev_mask && !use_masks))
+        return false;
+    flow2d_deformation_planes out = {};
+    float** slots[9] = {&out.divergence, &out.vorticity, &out.dilatation, &out.exx, &out.eyy, &out.exy, &out.e1, &out.e2, &out.max_shear};
+    bool any = stats_out != nullptr;
+    for (int k = 0; dev_planes && k < 9; ++k) {
+        *slots[k] = AsPlane(dev_planes[k]);
+        any = any || dev_planes[k];
+    }
+    if (!any) return false;
+    const size_t W = dev_container_size_.width, H = dev_container_size_.height, pitch = dev_container_size_.pitch;
+    const bool smooth = smoothing_sigma > 0.f;
+    DevicePtr* p = deformation_planes_.begin();
+    if (!EnsurePlanes(p, use_masks ? 6 : 2) || (smooth && !EnsurePlanes(p + 6, 2))) return false;
+    constexpr size_t kWorkspaceOffset = sizeof(flow2d_deformation_stats);  // the record comes first
+    const size_t workspace_bytes = flow2d_deformation_workspace_bytes(W, H, 1);
+    if (stats_out && !deformation_scratch_.Ensure(context_, kWorkspaceOffset + workspace_bytes)) return false;
+    // (group_ > 1 is refused by both)
+    const DevicePtr frames[2] = {dev_frame_0, dev_frame_1};
+    if (!(use_masks ? ComputeFlowBidirectionalDevice(frames, 2, p, p + 1, p + 2, p + 3, p + 4, p + 5, params)
+                    : ComputeFlowSequenceDevice(frames, 2, p, p + 1, params)))
+        return false;
+    bool ok = true;
+    if (smooth) {
+        float taps[51];
+        int radius = 0;
+        ok = !CheckFlow2DError(flow2d_gaussian_kernel(smoothing_sigma, taps, &radius), "flow2d_gaussian_kernel");
+        for (int i = 0; ok && i < 2; ++i)
+            ok = !CheckFlow2DError(flow2d_gaussian_blur(context_, AsPlane(p[6 + i]), AsPlane(p[i]), W, H, pitch, taps, radius),
+                                   "flow2d_gaussian_blur");
+    }
+    const DevicePtr* flow = smooth ? p + 6 : p;
+    flow2d_deformation_stats* record = stats_out ? deformation_scratch_.At<flow2d_deformation_stats>() : nullptr;
+    ok = ok && !CheckFlow2DError(flow2d_deformation_2d(context_, AsPlane(flow[0]), AsPlane(flow[1]), use_masks ? AsPlane(p[4]) : nullptr,
+                                                       W, H, pitch, measure, &out, record,
+                                                       stats_out ? deformation_scratch_.At(kWorkspaceOffset) : nullptr, workspace_bytes),
+                                 "flow2d_deformation_2d");
+    ok = ok && (!stats_out || ReadRecord(stats_out, record, sizeof(*stats_out)));
+    const DevicePtr own[3] = {flow[0], flow[1], p[4]}, callers[3] = {dev_flow_u, dev_flow_v, dev_mask};
+    ok = ok && HandBack(2, own, callers) && HandBack(1, own + 2, callers + 2);
+    return !CheckFlow2DError(flow2d_synchronize(context_), "flow2d_synchronize") && ok;
+}
+
+void OpticalFlow2D::AnalyseDeformation(Data2D& frame_0, Data2D& frame_1, int measure, float smoothing_sigma, bool use_masks,
+                                       Data2D* const* deformation, flow2d_deformation_stats* stats_out, OperationParameters& params,
+                                       Data2D* flow_u, Data2D* flow_v, Data2D* mask)
+{
+    last_run_ok_ = false;
+    if (!DeformationArgsOk(measure, smoothing_sigma)) return;
+    if (!IsInitialized() || (flow_u == nullptr) != (flow_v == nullptr) || (mask && !use_masks)) return;
+    // the planes of this call: only those that are asked for
+    CallPlanes planes(context_, dev_container_size_, GetName(), "frame / flow / deformation");
+    planes.Add(&frame_0, CallPlanes::In).Add(&frame_1, CallPlanes::In);
+    planes.Add(flow_u, CallPlanes::Out).Add(flow_v, CallPlanes::Out).Add(mask, CallPlanes::Out).Add(deformation, 9, CallPlanes::Out);
+    if (!planes.SizesMatch()) return;
+    HostCall call(context_, last_total_ms_, planes.Allocate());
+    const DevicePtr* d = planes.data();
+    last_run_ok_ = planes.Upload() &&
+                   AnalyseDeformationDevice(d[0], d[1], measure, smoothing_sigma, use_masks, d + 5, stats_out, params, d[2], d[3], d[4]) &&
+                   planes.Download();
+}
+
+bool OpticalFlow2D::StabiliseSequenceDevice(const DevicePtr* dev_frames, size_t frame_count, size_t reference_index, int model,
+                                            double sigma, int iterations, bool use_masks, float fill,
+                                            const DevicePtr* dev_outputs, flow2d_global_motion* motions_out,
+                                            OperationParameters& params)
+{
+    if (!GlobalMotionArgsOk(model, sigma, iterations)) return false;
+    if (frame_count < 2 || reference_index >= frame_count) {
+        std::printf("Error: stabilisation takes at least 2 frames (%zu) and a reference frame among them (%zu).\n", frame_count,
+                    reference_index);
+        return false;
+    }
+    if (!IsInitialized() || !dev_frames || !dev_outputs) return false;
+    if (RefuseGroup("sequences")) return false;
+    if (!WrittenPlanesOk(dev_frames, frame_count, dev_outputs, frame_count, "output plane")) return false;
+    const size_t W = dev_container_size_.width, H = dev_container_size_.height, pitch = dev_container_size_.pitch;
+    const size_t ref = reference_index;
+    // steps[k]: above the reference M(k - 1 -> k), below it M(k + 1 -> k)
+    std::vector<flow2d_global_motion> steps(frame_count), composed(frame_count);
+    std::vector<DevicePtr> reversed(dev_frames, dev_frames + ref + 1);
+    std::reverse(reversed.begin(), reversed.end());  // frame ref, ref - 1, ..., 0
+    std::vector<flow2d_global_motion> below(ref);
+    if (!FitConsecutivePairs(dev_frames + ref, frame_count - ref, model, sigma, iterations, use_masks, steps.data() + ref + 1, params) ||
+        !FitConsecutivePairs(reversed.data(), ref + 1, model, sigma, iterations, use_masks, below.data(), params))
+        return false;
+    for (size_t i = 0; i < ref; ++i) steps[ref - 1 - i] = below[i];
+    flow2d_global_motion identity = {};
+    identity.model_used = model;
+    composed[ref] = identity;
+    for (size_t k = ref + 1; k < frame_count; ++k)
+        composed[k] = k == ref + 1 ? steps[k] : ComposeGlobalMotion(composed[k - 1], steps[k]);
+    for (size_t k = ref; k-- > 0;) composed[k] = k + 1 == ref ? steps[k] : ComposeGlobalMotion(composed[k + 1], steps[k]);
+    if (!EnsureStabiliseScratch()) return false;
+    bool ok = true;
+    for (size_t k = 0; ok && k < frame_count; ++k) {
+        if (k == ref) {
+            ok = HandBack(1, dev_frames + k, dev_outputs + k);
+            continue;
+        }
+        // (one record slot: the upload of the next record is ordered behind this warp on the stream)
+        ok = !CheckFlow2DError(flow2d_copy_h2d_2d(context_, StabiliseRecord(kStabiliseWindow), sizeof(flow2d_global_motion), &composed[k],
+                                                  sizeof(flow2d_global_motion), sizeof(flow2d_global_motion), 1),
+                               "flow2d_copy_h2d_2d") &&
+             !CheckFlow2DError(flow2d_warp_global_2d(context_, StabiliseRecord(kStabiliseWindow), AsPlane(dev_frames[k]), W, H, pitch,
+                                                     fill, AsPlane(dev_outputs[k]), nullptr),
+                               "flow2d_warp_global_2d");
+    }
+    ok = !CheckFlow2DError(flow2d_synchronize(context_), "flow2d_synchronize") && ok;  // `composed` is the uploads' source
+    if (ok && motions_out)
+        for (size_t k = 0; k < frame_count; ++k) motions_out[k] = composed[k];
+    return ok;
+}
+
+void OpticalFlow2D::StabiliseSequence(Data2D* const* frames, size_t frame_count, size_t reference_index, int model, double sigma,
+                                      int iterations, bool use_masks, float fill, Data2D* outputs,
+                                      flow2d_global_motion* motions_out, OperationParameters& params)
+{
+    last_run_ok_ = false;
+    if (!GlobalMotionArgsOk(model, sigma, iterations)) return;
+    if (!IsInitialized() || !frames || !outputs || frame_count < 2 || reference_index >= frame_count) return;
+    const size_t n = frame_count;
+    CallPlanes planes(context_, dev_container_size_, GetName(), "frame / output");
+    planes.Add(frames, n, CallPlanes::In).Add(outputs, n, CallPlanes::Out);
+    if (!planes.SizesMatch()) return;
+    HostCall call(context_, last_total_ms_, planes.Allocate());
+    const DevicePtr* d = planes.data();
+    last_run_ok_ = planes.Upload() &&
+                   StabiliseSequenceDevice(d, n, reference_index, model, sigma, iterations, use_masks, fill, d + n, motions_out, params) &&
+                   planes.Download();
+}
+
+bool OpticalFlow2D::DenoiseArgsOk(size_t frame_count, size_t radius, float range_sigma)
+{
+    if (frame_count < 2 || radius < 1 || radius > kDenoiseMaxRadius || !std::isfinite(range_sigma) || range_sigma < 0.f) {
+        std::printf("Error: denoising takes at least 2 frames (%zu), a radius of 1 .. %zu (%zu) and a finite range sigma >= 0 (%g).\n",
+                    frame_count, kDenoiseMaxRadius, radius, range_sigma);
+        return false;
+    }
+    return true;
+}
+
+bool OpticalFlow2D::DenoiseSequenceDevice(const DevicePtr* dev_frames, size_t frame_count, size_t radius, float range_sigma,
+                                          bool use_masks, const DevicePtr* dev_outputs, const DevicePtr* dev_weight_sums,
+                                          OperationParameters& params)
+{
+    if (!DenoiseArgsOk(frame_count, radius, range_sigma)) return false;
+    if (!IsInitialized() || !dev_frames || !dev_outputs) return false;
+    if (RefuseGroup("sequences")) return false;
+    // every plane written must be distinct from every other one and from the frames (which are only read)
+    std::vector<DevicePtr> written(dev_outputs, dev_outputs + frame_count);
+    if (dev_weight_sums) written.insert(written.end(), dev_weight_sums, dev_weight_sums + frame_count);
+    if (!WrittenPlanesOk(dev_frames, frame_count, written.data(), written.size(), "output plane")) return false;
+    // the ring: pair j lives in slot j % slots as u, v, back u, back v, occlusion forward, occlusion backward
+    const size_t slots = 2 * radius + kDenoiseWindow;
+    const size_t per_slot = use_masks ? 6 : 4;
+    for (size_t s = 0; s < slots; ++s)
+        if (!EnsurePlanes(&denoise_pairs_[6 * s], per_slot)) return false;
+    // the composed flows of one centre: direction (0 backwards, 1 forwards), distance d >= 2: u, v, mask
+    const size_t far = kDenoiseMaxRadius - 1;
+    for (size_t dir = 0; dir < 2; ++dir)
+        for (size_t d = 2; d <= radius; ++d)
+            if (!EnsurePlanes(&denoise_chains_[(dir * far + d - 2) * 3], use_masks ? 3 : 2)) return false;
+    const size_t W = dev_container_size_.width, H = dev_container_size_.height, pitch = dev_container_size_.pitch;
+    auto pair_plane = [&](size_t j, size_t i) { return denoise_pairs_[6 * (j % slots) + i]; };
+    auto chain_plane = [&](size_t dir, size_t d, size_t i) { return denoise_chains_[(dir * far + d - 2) * 3 + i]; };
+
+    auto fuse = [&](size_t k) {
+        // the flow from frame k to frame k -+ d and its mask: distance 1 from the ring, further ones chained outwards
+        DevicePtr flow[2][kDenoiseMaxRadius][3];
+        size_t reach[2] = {std::min(radius, k), std::min(radius, frame_count - 1 - k)};
+        for (size_t dir = 0; dir < 2; ++dir) {
+            for (size_t d = 1; d <= reach[dir]; ++d) {
+                // the step that ends at distance d: backwards the backward flow of pair k - d, forwards the forward flow of
+                // pair k + d - 1, each with the mask on its own first frame's grid
+                const size_t j = dir ? k + d - 1 : k - d;
+                const DevicePtr step[3] = {pair_plane(j, dir ? 0 : 2), pair_plane(j, dir ? 1 : 3),
+                                           use_masks ? pair_plane(j, dir ? 4 : 5) : 0};
+                if (d == 1) {
+                    for (int i = 0; i < 3; ++i) flow[dir][0][i] = step[i];
+                    continue;
+                }
+                DevicePtr* out = flow[dir][d - 1];
+                for (int i = 0; i < 3; ++i) out[i] = (i < 2 || use_masks) ? chain_plane(dir, d, i) : 0;
+                const DevicePtr* prev = flow[dir][d - 2];
+                if (CheckFlow2DError(flow2d_compose_flow_2d(context_, AsPlane(prev[0]), AsPlane(prev[1]), AsPlane(step[0]),
+                                                            AsPlane(step[1]), use_masks ? AsPlane(prev[2]) : nullptr,
+                                                            use_masks ? AsPlane(step[2]) : nullptr, W, H, pitch, AsPlane(out[0]),
+                                                            AsPlane(out[1]), use_masks ? AsPlane(out[2]) : nullptr),
+                                     "flow2d_compose_flow_2d"))
+                    return false;
+            }
+        }
+        // ascending frame order: k - reach .. k - 1, k + 1 .. k + reach
+        const float *frames[2 * kDenoiseMaxRadius], *us[2 * kDenoiseMaxRadius], *vs[2 * kDenoiseMaxRadius],
+            *occs[2 * kDenoiseMaxRadius];
+        size_t n = 0;
+        auto add = [&](size_t dir, size_t d) {
+            frames[n] = AsPlane(dev_frames[dir ? k + d : k - d]);
+            us[n] = AsPlane(flow[dir][d - 1][0]);
+            vs[n] = AsPlane(flow[dir][d - 1][1]);
+            occs[n] = use_masks ? AsPlane(flow[dir][d - 1][2]) : nullptr;
+            ++n;
+        };
+        for (size_t d = reach[0]; d >= 1; --d) add(0, d);
+        for (size_t d = 1; d <= reach[1]; ++d) add(1, d);
+        return !CheckFlow2DError(flow2d_denoise_2d(context_, AsPlane(dev_frames[k]), n, frames, us, vs, use_masks ? occs : nullptr, W,
+                                                   H, pitch, range_sigma, AsPlane(dev_outputs[k]),
+                                                   dev_weight_sums ? AsPlane(dev_weight_sums[k]) : nullptr),
+                                 "flow2d_denoise_2d");
+    };
+
+    const size_t pairs = frame_count - 1;
+    size_t done = 0, centre = 0;  // pairs in the ring so far; the next frame to fuse
+    bool ok = true;
+    while (ok && centre < frame_count) {
+        if (done < pairs) {
+            const size_t chunk = std::min(kDenoiseWindow, pairs - done);
+            std::vector<DevicePtr> p[6];
+            for (size_t j = done; j < done + chunk; ++j)
+                for (size_t i = 0; i < 6; ++i) p[i].push_back(pair_plane(j, i));
+            ok = ComputeFlowBidirectionalDevice(dev_frames + done, chunk + 1, p[0].data(), p[1].data(), p[2].data(), p[3].data(),
+                                                use_masks ? p[4].data() : nullptr, use_masks ? p[5].data() : nullptr, params);
+            done += chunk;
+        }
+        // every frame whose furthest forward pair is in the ring (a slot is overwritten only 2 * radius + kDenoiseWindow pairs later)
+        while (ok && centre < frame_count && std::min(centre + radius, pairs) <= done) ok = fuse(centre++);
+    }
+    return ok;
+}
+
+void OpticalFlow2D::DenoiseSequence(Data2D* const* frames, size_t frame_count, size_t radius, float range_sigma, bool use_masks,
+                                    Data2D* outputs, Data2D* weight_sums, OperationParameters& params)
+{
+    last_run_ok_ = false;
+    if (!DenoiseArgsOk(frame_count, radius, range_sigma)) return;
+    if (!IsInitialized() || !frames || !outputs) return;
+    if (RefuseGroup("sequences")) return;
+    const size_t n = frame_count;
+    CallPlanes planes(context_, dev_container_size_, GetName(), "frame / output");
+    planes.Add(frames, n, CallPlanes::In).Add(outputs, n, CallPlanes::Out).Add(weight_sums, n, CallPlanes::Out);
+    if (!planes.SizesMatch()) return;
+    HostCall call(context_, last_total_ms_, planes.Allocate());
+    const DevicePtr* d = planes.data();
+    bool ok = planes.Upload() && DenoiseSequenceDevice(d, n, radius, range_sigma, use_masks, d + n, weight_sums ? d + 2 * n : nullptr, params);
+    for (size_t k = 0; ok && k < n; ++k) ok = planes.Download(n + k) && planes.Download(2 * n + k);  // output k, then its sum of weights
+    last_run_ok_ = ok;
+}

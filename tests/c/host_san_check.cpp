@@ -1,5 +1,5 @@
 // host_san_check -- the CPU-only parts of the host layer (settings reader, Data2D raw I/O with its error paths, the
-// output writers, the parameter bag) driven once under -fsanitize=address,undefined (`make san`; tests/test_sanitizers.py).
+// output writers, the parameter bag, the alias check of the entries that write caller planes) driven once under -fsanitize=address,undefined (`make san`; tests/test_sanitizers.py).
 // GPU sanitizers do not exist on the pool, so this is what a sanitizer can see of the host layer without a device.
 // usage: host_san_check <settings.xml> <scratch dir>     prints "host_san_check ok" and exits 0
 #include <cmath>
@@ -7,6 +7,7 @@
 #include <string>
 
 #include "data2d.h"
+#include "host_entry.h"
 #include "io_utils.h"
 #include "operation_parameters.h"
 #include "settings.h"
@@ -72,6 +73,19 @@ int main(int argc, char** argv)
     EXPECT(!bag.Read("missing", out));
     bag.Clear();
     EXPECT(bag.GetValuePtr("warp_levels_count") == nullptr);
+
+    {  // WrittenPlanesOk: what the ...Device entries ask of the planes they write
+        const DevicePtr frames[3] = {0x1000, 0x2000, 0x3000}, disjoint[4] = {0x4000, 0x5000, 0x6000, 0x7000};
+        const DevicePtr on_a_frame[2] = {0x4000, 0x2000}, twice[3] = {0x4000, 0x5000, 0x4000}, with_null[2] = {0x4000, 0};
+        const DevicePtr null_frame[2] = {0x1000, 0};
+        EXPECT(WrittenPlanesOk(frames, 3, disjoint, 4, "output plane"));
+        EXPECT(!WrittenPlanesOk(frames, 3, on_a_frame, 2, "output plane"));
+        EXPECT(!WrittenPlanesOk(frames, 3, twice, 3, "output plane"));
+        EXPECT(!WrittenPlanesOk(frames, 3, with_null, 2, "output plane"));
+        EXPECT(!WrittenPlanesOk(null_frame, 2, disjoint, 4, "output plane"));
+        EXPECT(WrittenPlanesOk(frames, 3, nullptr, 0, "output plane"));  // nothing written: nothing to refuse
+        EXPECT(WrittenPlanesOk(frames, 3, disjoint, 0, "output plane"));
+    }
     std::printf("host_san_check ok\n");
     return 0;
 }
