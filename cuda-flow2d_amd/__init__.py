@@ -293,6 +293,9 @@ def hip_lib():
         L.flow2d_fused_fallbacks.argtypes = [vp, C.POINTER(C.c_ulonglong)]
         L.flow2d_context_set_lone.argtypes = [vp, i]
         L.flow2d_resample_y_levels.argtypes = [vp, vp, vp, vp, vp, sz, sz, sz, C.POINTER(sz), C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]
+        L.flow2d_resample_xy_levels.argtypes = [vp, vp, vp, vp, vp, sz, sz, sz, sz, C.POINTER(sz), C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]
+        L.flow2d_resample_xy_levels_launches.argtypes = []
+        L.flow2d_resample_xy_levels_launches.restype = C.c_ulonglong
         L.flow2d_clock_probe_start.argtypes = [vp, C.c_double]
         L.flow2d_clock_probe_read.argtypes = [vp, C.POINTER(C.c_double)]
         L.flow2d_fused_block_order.argtypes = [vp, sz, sz, sz, sz, C.POINTER(i), sz, C.POINTER(sz)]
@@ -341,6 +344,11 @@ def hip_lib():
 def _check(status, where):
     if status != 0:
         raise Flow2DError(status, where, hip_lib().flow2d_last_error().decode(errors="replace"))
+
+
+def resample_xy_levels_launches():
+    """launches of the one-launch frame pyramid queued by this process so far (flow2d_resample_xy_levels_launches)"""
+    return int(hip_lib().flow2d_resample_xy_levels_launches())
 
 
 def device_count():
@@ -469,6 +477,17 @@ class Context:
         _check(hip_lib().flow2d_resample_y_levels(self.handle, packed_a.ptr, out_a.ptr, packed_b.ptr if packed_b else None,
                                                   out_b.ptr if out_b else None, in_height, packed_a.pitch, n, arr(widths), arr(heights),
                                                   arr(columns), arr(rows)), "flow2d_resample_y_levels")
+
+    def resample_xy_levels(self, src_a, out_a, in_width, in_height, widths, heights, rows, columns=None, src_b=None, out_b=None,
+                           pitch=None):
+        """the x and y passes of all levels of a halving pyramid in one launch (flow2d_resample_xy_levels).  Planes, or raw device
+        addresses together with `pitch` (bytes)."""
+        n = len(widths)
+        arr = lambda v: (C.c_size_t * n)(*v)
+        ptr = lambda p: None if p is None else (p if isinstance(p, int) else p.ptr)
+        _check(hip_lib().flow2d_resample_xy_levels(self.handle, ptr(src_a), ptr(out_a), ptr(src_b), ptr(out_b), in_width, in_height,
+                                                   src_a.pitch if pitch is None else pitch, n, arr(widths), arr(heights), arr(rows),
+                                                   arr(columns) if columns is not None else None), "flow2d_resample_xy_levels")
 
     def clock_probe_start(self, duration_us):
         """queues one sleeping wave per XCD on this context's stream that brackets duration_us with the 100 MHz and the shader clock"""

@@ -6,6 +6,7 @@
 // every global access of a wave is one contiguous 256-byte row segment; blocks are 64x4.
 // All arithmetic follows the reference's operation order (no FMA contraction) -- see each kernel.
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <type_traits>
 #include <utility>
@@ -959,6 +960,254 @@ __global__ __launch_bounds__(256) void resample_y_levels_kernel(const float* __r
     }
 }
 
+// ---- the x AND the y passes of all levels in one trip over the frames (flow2d_resample_xy_levels) ---------------------------
+// For the halving pyramid (every level's ratio R = 2^k in both directions) the two launches above move the frames three times
+// more than the result needs: the x-reduced rows of every level, one more full frame per frame, are written and read straight
+// back.  Here a wave walks kXYRows rows of a 1024-cell column range downwards, a lane owning kXYCells consecutive cells of each
+// row (four 16-byte loads, the rows after the next ones already requested), and nothing but the levels leaves the chip:
+//  * x sums: ((0 + c[0]) + c[1] + ... + c[R-1]) * (1 / R), the chain of pow2_emit.  A level's chain is a prefix of the next
+//    level's, so the chains of R <= 16 cost 40 additions per lane and row.
+//  * y sums: (0 + X[0]) + X[1] + ... + X[R-1] over the level's own x values, times 1 / R -- resample_y_levels_kernel's chain
+//    at an integer ratio (its two fraction multiplies are by exactly 1.0 there).  For R <= 16 the running sums are registers
+//    of the lane that made the x values (8 + 4 + 2 + 1 of them), stored and cleared every R rows.
+//  * R >= 32 (chains longer than a lane's cells): the wave's cells of the row go to its own stretch of LDS (the padding of
+//    the x kernel) and lane i walks one chain there -- 32 of R = 32, 16 of 64, 8 of 128 and 4 of 256 are 60 chains per 1024
+//    cells, one per lane -- and leaves the x value in LDS, one 64-word line per row of the workgroup's band.  The band is as
+//    high as the deepest ratio (one wave per 16 rows), so after a barrier each of its deep outputs is one thread's walk down
+//    that table.
+// The same additions on the same values in the same order as the two launches: the same bits, for NaN, infinities, signed
+// zeros and denormals too (the chains start from +0 as theirs do).
+constexpr int kXYCells = 16;                  // cells per lane and row
+constexpr int kXYRows = 16;                   // rows per wave
+constexpr int kXYWaveCols = 64 * kXYCells;    // columns per workgroup
+constexpr int kXYMaxLog = 8;                  // deepest ratio 256: a band of 256 rows, sixteen waves
+constexpr int kXYDeepLog = 5;                 // ratios from 32 on take the LDS path
+constexpr int kXYStageWords = kXYWaveCols + 4 * (kXYWaveCols / 32 + kXYWaveCols / 256) + 8;  // pow2_lds_index of a wave's cells
+
+struct ResampleXYLevels {
+    unsigned present;                                // bit k: there is a level of ratio 1 << k
+    int col[kXYMaxLog + 1], row[kXYMaxLog + 1];      // first column and row of that level's region in the output planes
+};
+
+__device__ __forceinline__ float xy_norm(int k) { return __int_as_float((127 - k) << 23); }  // 1 / 2^k
+
+// the compiler may not move LDS accesses across; the hardware executes one wave's LDS instructions in order
+__device__ __forceinline__ void xy_wave_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// the slot of deep chain (k, g) among a wave's 64: [0, 32) R = 32, [32, 48) R = 64, [48, 56) R = 128, [56, 60) R = 256
+__device__ __forceinline__ int xy_deep_slot(int k) { return 64 - (64 >> (k - kXYDeepLog)); }
+
+template <int MAX_THREADS>
+__global__ __launch_bounds__(MAX_THREADS) void resample_xy_levels_kernel(const float* __restrict__ in_a, float* __restrict__ out_a,
+                                                                         const float* __restrict__ in_b, float* __restrict__ out_b,
+                                                                         int in_w, int in_h, int pitch, int band_rows, int col_ranges,
+                                                                         ResampleXYLevels lv, BatchArg batch)
+{
+    extern __shared__ float xy_lds[];
+    const float* __restrict__ in = (batch_plane(batch) ? in_b : in_a) + batch_offset(batch);
+    float* __restrict__ out = (batch_plane(batch) ? out_b : out_a) + batch_offset(batch);
+    const int lane = static_cast<int>(threadIdx.x) & 63, wave = static_cast<int>(threadIdx.x) >> 6;
+    const int waves = static_cast<int>(blockDim.x) >> 6;
+    const int band = static_cast<int>(blockIdx.x) / col_ranges;
+    const int c0 = (static_cast<int>(blockIdx.x) - band * col_ranges) * kXYWaveCols;  // first column of the workgroup
+    const unsigned present = lv.present;
+    const bool deep = (present >> kXYDeepLog) != 0;
+    float* __restrict__ stage = xy_lds + wave * kXYStageWords;    // this wave's cells of the current row
+    float* __restrict__ table = xy_lds + waves * kXYStageWords;   // [band row][slot]: the deep x values
+
+    const int x = c0 + lane * kXYCells;      // the lane's first cell
+    const bool active = x < in_w;            // (in_w is a multiple of 16: whole lanes)
+    const int y0 = band * band_rows + wave * kXYRows;
+    const int rows = min(kXYRows, in_h - y0);  // (a band without deep levels may end below the frame)
+    const float* __restrict__ src = in + static_cast<size_t>(y0) * pitch + x;
+
+    // the lane's deep chain: level k, output g of the workgroup's column range
+    int deep_k = 0, deep_g = 0;
+    if (lane < 32) deep_k = 5, deep_g = lane;
+    else if (lane < 48) deep_k = 6, deep_g = lane - 32;
+    else if (lane < 56) deep_k = 7, deep_g = lane - 48;
+    else if (lane < 60) deep_k = 8, deep_g = lane - 56;
+    const bool chain = deep_k != 0 && ((present >> deep_k) & 1u) != 0 && c0 + ((deep_g + 1) << deep_k) <= in_w;
+
+    float acc1[8], acc2[4], acc3[2], acc4 = 0.f;
+#pragma unroll
+    for (int o = 0; o < 8; ++o) acc1[o] = 0.f;
+#pragma unroll
+    for (int o = 0; o < 4; ++o) acc2[o] = 0.f;
+    acc3[0] = acc3[1] = 0.f;
+
+    float4 buf[4][kXYCells / 4];
+    auto load = [&](float4 (&dst)[kXYCells / 4], int r) {
+        const float4* __restrict__ p = reinterpret_cast<const float4*>(src + static_cast<size_t>(r) * pitch);
+#pragma unroll
+        for (int q = 0; q < kXYCells / 4; ++q) dst[q] = p[q];
+    };
+    auto process = [&](const float4 (&cells)[kXYCells / 4], int r) {
+        const int y = y0 + r;
+        if (active) {
+            float c[kXYCells];
+#pragma unroll
+            for (int q = 0; q < kXYCells / 4; ++q) c[4 * q] = cells[q].x, c[4 * q + 1] = cells[q].y, c[4 * q + 2] = cells[q].z, c[4 * q + 3] = cells[q].w;
+            if (deep) {
+                float4* __restrict__ mine = reinterpret_cast<float4*>(stage + pow2_lds_index(lane * kXYCells));
+#pragma unroll
+                for (int q = 0; q < kXYCells / 4; ++q) mine[q] = cells[q];
+            }
+            // the x chains of R = 2, 4, 8, 16, each the continuation of the one before
+            float s2[8], s4[4], s8[2], s16;
+#pragma unroll
+            for (int o = 0; o < 8; ++o) s2[o] = (0.f + c[2 * o]) + c[2 * o + 1];
+#pragma unroll
+            for (int o = 0; o < 4; ++o) s4[o] = (s2[2 * o] + c[4 * o + 2]) + c[4 * o + 3];
+#pragma unroll
+            for (int o = 0; o < 2; ++o) s8[o] = (((s4[2 * o] + c[8 * o + 4]) + c[8 * o + 5]) + c[8 * o + 6]) + c[8 * o + 7];
+            s16 = s8[0];
+#pragma unroll
+            for (int j = 8; j < 16; ++j) s16 += c[j];
+            if (present & 2u) {
+#pragma unroll
+                for (int o = 0; o < 8; ++o) acc1[o] += s2[o] * 0.5f;
+                if ((r & 1) == 1) {
+                    float4* __restrict__ dst = reinterpret_cast<float4*>(out + static_cast<size_t>(lv.row[1] + (y >> 1)) * pitch + lv.col[1] + (x >> 1));
+                    dst[0] = make_float4(acc1[0] * 0.5f, acc1[1] * 0.5f, acc1[2] * 0.5f, acc1[3] * 0.5f);
+                    dst[1] = make_float4(acc1[4] * 0.5f, acc1[5] * 0.5f, acc1[6] * 0.5f, acc1[7] * 0.5f);
+#pragma unroll
+                    for (int o = 0; o < 8; ++o) acc1[o] = 0.f;
+                }
+            }
+            if (present & 4u) {
+#pragma unroll
+                for (int o = 0; o < 4; ++o) acc2[o] += s4[o] * 0.25f;
+                if ((r & 3) == 3) {
+                    *reinterpret_cast<float4*>(out + static_cast<size_t>(lv.row[2] + (y >> 2)) * pitch + lv.col[2] + (x >> 2)) =
+                        make_float4(acc2[0] * 0.25f, acc2[1] * 0.25f, acc2[2] * 0.25f, acc2[3] * 0.25f);
+#pragma unroll
+                    for (int o = 0; o < 4; ++o) acc2[o] = 0.f;
+                }
+            }
+            if (present & 8u) {
+                acc3[0] += s8[0] * 0.125f, acc3[1] += s8[1] * 0.125f;
+                if ((r & 7) == 7) {
+                    *reinterpret_cast<float2*>(out + static_cast<size_t>(lv.row[3] + (y >> 3)) * pitch + lv.col[3] + (x >> 3)) =
+                        make_float2(acc3[0] * 0.125f, acc3[1] * 0.125f);
+                    acc3[0] = acc3[1] = 0.f;
+                }
+            }
+            if (present & 16u) {
+                acc4 += s16 * 0.0625f;
+                if ((r & 15) == 15) {
+                    out[static_cast<size_t>(lv.row[4] + (y >> 4)) * pitch + lv.col[4] + (x >> 4)] = acc4 * 0.0625f;
+                    acc4 = 0.f;
+                }
+            }
+        }
+        if (!deep) return;
+        xy_wave_sync();  // the row's cells are in LDS
+        if (chain) {
+            const int blocks = (1 << deep_k) / kXYCells;  // an even number of 16-cell blocks
+            const float* __restrict__ first = stage;
+            const int cell0 = deep_g << deep_k;
+            float value = 0.f;
+            auto read = [&](float4 (&dst)[kXYCells / 4], int b) {
+                const float4* __restrict__ block = reinterpret_cast<const float4*>(first + pow2_lds_index(cell0 + b * kXYCells));
+#pragma unroll
+                for (int q = 0; q < kXYCells / 4; ++q) dst[q] = block[q];
+            };
+            auto add = [&](const float4 (&v)[kXYCells / 4]) {
+#pragma unroll
+                for (int q = 0; q < kXYCells / 4; ++q) {
+                    value += v[q].x;
+                    value += v[q].y;
+                    value += v[q].z;
+                    value += v[q].w;
+                }
+            };
+            // (the reads of the next block in front of the additions of this one, as in resample_x_levels_pow2_kernel)
+            float4 a[kXYCells / 4], n[kXYCells / 4];
+            read(a, 0);
+            for (int b = 0; b < blocks; b += 2) {
+                read(n, b + 1);
+                __builtin_amdgcn_sched_barrier(0);
+                add(a);
+                __builtin_amdgcn_sched_barrier(0);
+                read(a, min(b + 2, blocks - 1));  // (after the last pair: a read nothing uses)
+                __builtin_amdgcn_sched_barrier(0);
+                add(n);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            table[(wave * kXYRows + r) * 64 + lane] = value * xy_norm(deep_k);
+        }
+        xy_wave_sync();  // the chains have read the row: the next one may overwrite it
+    };
+
+    // three rows requested ahead of the one at work
+    if (active) {
+#pragma unroll
+        for (int p = 0; p < 3; ++p)
+            if (p < rows) load(buf[p], p);
+    }
+    for (int r0 = 0; r0 < rows; r0 += 4) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int r = r0 + u;
+            if (r < rows) {
+                if (active && r + 3 < rows) load(buf[(u + 3) & 3], r + 3);
+                __builtin_amdgcn_sched_barrier(0);
+                process(buf[u], r);
+            }
+        }
+    }
+    if (!deep) return;
+    __syncthreads();
+    // the deep outputs of the band: item -> (level k, output row j, output gl of the column range); there are fewer than
+    // 2 * band_rows of them and the workgroup has 4 * band_rows threads
+    int item = static_cast<int>(threadIdx.x);
+#pragma unroll
+    for (int k = kXYDeepLog; k <= kXYMaxLog; ++k) {
+        if (((present >> k) & 1u) == 0 || item < 0) continue;
+        const int per_row = kXYWaveCols >> k, count = per_row * (band_rows >> k);
+        if (item >= count) {
+            item -= count;
+            continue;
+        }
+        const int j = item / per_row, gl = item - j * per_row;
+        item = -1;
+        if (c0 + ((gl + 1) << k) > in_w) continue;  // (a chain right of the frame)
+        const float* __restrict__ column = table + (j << k) * 64 + xy_deep_slot(k) + gl;
+        float value = 0.f;
+        for (int rr = 0; rr < (1 << k); rr += 16) {
+            float v[16];
+#pragma unroll
+            for (int i = 0; i < 16; ++i) v[i] = column[(rr + i) * 64];
+#pragma unroll
+            for (int i = 0; i < 16; ++i) value += v[i];
+        }
+        out[static_cast<size_t>(lv.row[k] + band * (band_rows >> k) + j) * pitch + lv.col[k] + (c0 >> k) + gl] = value * xy_norm(k);
+    }
+}
+
+// The workgroups of resample_xy_levels_kernel need up to 138 KB of LDS (a 256-row band): allowed once per device and instantiation.
+// launches of resample_xy_levels_kernel queued by this process (flow2d_resample_xy_levels_launches: which path a pyramid took)
+std::atomic<unsigned long long> xy_levels_launches{0};
+
+template <int MAX_THREADS>
+hipError_t xy_levels_allow_lds(int device)
+{
+    static std::atomic<unsigned long long> allowed{0};
+    const bool tracked = device >= 0 && device < 64;
+    if (tracked && ((allowed.load() >> device) & 1ull)) return hipSuccess;
+    constexpr int kBytes = ((MAX_THREADS / 64) * kXYStageWords + (MAX_THREADS / 4) * 64) * static_cast<int>(sizeof(float));
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&resample_xy_levels_kernel<MAX_THREADS>),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, kBytes);
+    if (e == hipSuccess && tracked) allowed.fetch_or(1ull << device);
+    return e;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1267,6 +1516,91 @@ int flow2d_resample_y_levels(flow2d_context* ctx, const float* packed_a, float* 
     FLOW2D_CHECK_LAUNCH();
     return FLOW2D_OK;
 }
+
+int flow2d_resample_xy_levels(flow2d_context* ctx, const float* input_a, float* output_a, const float* input_b, float* output_b,
+                              size_t in_width, size_t in_height, size_t pitch_bytes, size_t level_count, const size_t* out_widths,
+                              const size_t* out_heights, const size_t* output_rows, const size_t* output_columns)
+{
+    FLOW2D_ENTER(ctx);
+    if (!out_widths || !out_heights || !output_rows || level_count == 0) return FLOW2D_ERR_INVALID_ARGUMENT;
+    const bool pair = input_b || output_b;
+    if (!flow2d::plane_args_ok(input_a, in_width, in_height, pitch_bytes) || !output_a || (reinterpret_cast<uintptr_t>(output_a) % 16) != 0)
+        return FLOW2D_ERR_INVALID_ARGUMENT;
+    if (pair && (!flow2d::plane_args_ok(input_b, in_width, in_height, pitch_bytes) || !output_b || (reinterpret_cast<uintptr_t>(output_b) % 16) != 0))
+        return FLOW2D_ERR_INVALID_ARGUMENT;
+    // eligibility: the width conditions of the register kernel of the x pass, and every level the same power of two in both directions
+    if (level_count > FLOW2D_RESAMPLE_MAX_LEVELS || in_width % kPow2Cells != 0 || in_width > 256 * kPow2Cells) return FLOW2D_ERR_UNSUPPORTED;
+    const size_t pitch = pitch_bytes / 4;
+    ResampleXYLevels lv{};
+    int level_of[kXYMaxLog + 1];
+    for (int& l : level_of) l = -1;
+    int deepest = 0;
+    for (size_t l = 0; l < level_count; ++l) {
+        if (out_widths[l] == 0 || out_heights[l] == 0) return FLOW2D_ERR_INVALID_ARGUMENT;
+        const size_t ratio = in_width / out_widths[l];
+        if (ratio < 2 || ratio > (1u << kXYMaxLog) || (ratio & (ratio - 1)) != 0 || ratio * out_widths[l] != in_width ||
+            ratio * out_heights[l] != in_height)
+            return FLOW2D_ERR_UNSUPPORTED;
+        int k = 0;
+        while ((size_t{1} << k) < ratio) ++k;
+        if (level_of[k] >= 0) return FLOW2D_ERR_UNSUPPORTED;  // (two levels of one size)
+        level_of[k] = static_cast<int>(l);
+        deepest = std::max(deepest, k);
+    }
+    // the level regions: inside the pitch, 16-byte aligned, disjoint in each plane
+    size_t first_row = ~size_t{0}, end_row = 0;
+    for (size_t l = 0; l < level_count; ++l) {
+        const size_t column = output_columns ? output_columns[l] : 0;
+        if (column % 4 != 0 || column + out_widths[l] > pitch || output_rows[l] >= (1u << 30)) return FLOW2D_ERR_INVALID_ARGUMENT;
+        for (size_t m = 0; m < l; ++m) {
+            const size_t column_m = output_columns ? output_columns[m] : 0;
+            const bool rows_meet = output_rows[l] < output_rows[m] + out_heights[m] && output_rows[m] < output_rows[l] + out_heights[l];
+            const bool columns_meet = column < column_m + out_widths[m] && column_m < column + out_widths[l];
+            if (rows_meet && columns_meet) return FLOW2D_ERR_INVALID_ARGUMENT;
+        }
+        first_row = std::min(first_row, output_rows[l]);
+        end_row = std::max(end_row, output_rows[l] + out_heights[l]);
+    }
+    {   // the kernel marks every plane __restrict__: no written byte range [p, p + rows * pitch) may meet a read one or the other written one
+        const size_t written_span = flow2d::batch_span(ctx, (end_row - first_row) * pitch_bytes);
+        const size_t read_span = flow2d::batch_span(ctx, in_height * pitch_bytes);
+        const flow2d::ByteRange written[] = {{output_a + first_row * pitch, written_span}, {pair ? output_b + first_row * pitch : nullptr, written_span}};
+        const flow2d::ByteRange read[] = {{input_a, read_span}, {input_b, read_span}};
+        if (flow2d::any_overlap(written, read)) return FLOW2D_ERR_INVALID_ARGUMENT;
+    }
+    for (int k = 1; k <= kXYMaxLog; ++k) {
+        if (level_of[k] < 0) continue;
+        lv.present |= 1u << k;
+        lv.col[k] = static_cast<int>(output_columns ? output_columns[level_of[k]] : 0);
+        lv.row[k] = static_cast<int>(output_rows[level_of[k]]);
+    }
+    // a band as high as the deepest ratio (the frame is a whole number of them), one wave per 16 rows
+    const bool deep = deepest >= kXYDeepLog;
+    const int band_rows = deep ? 1 << deepest : kXYRows;
+    const int waves = band_rows / kXYRows;
+    const unsigned col_ranges = flow2d::div_up(in_width, kXYWaveCols);
+    const size_t blocks = static_cast<size_t>(col_ranges) * flow2d::div_up(in_height, band_rows);
+    if (blocks >= 0x7fffffffull) return FLOW2D_ERR_UNSUPPORTED;
+    const size_t lds_bytes = deep ? (static_cast<size_t>(waves) * kXYStageWords + static_cast<size_t>(band_rows) * 64) * sizeof(float) : 0;
+    const unsigned planes = pair ? 2 : 1;
+    const dim3 grid(static_cast<unsigned>(blocks), 1, flow2d::batch_z(ctx, planes));
+    if (waves <= 8) {
+        FLOW2D_HIP_TRY(xy_levels_allow_lds<512>(ctx->device));
+        resample_xy_levels_kernel<512><<<grid, 64 * waves, lds_bytes, ctx->stream>>>(
+            input_a, output_a, input_b, output_b, static_cast<int>(in_width), static_cast<int>(in_height), static_cast<int>(pitch), band_rows,
+            static_cast<int>(col_ranges), lv, flow2d::batch_arg(ctx, planes));
+    } else {
+        FLOW2D_HIP_TRY(xy_levels_allow_lds<1024>(ctx->device));
+        resample_xy_levels_kernel<1024><<<grid, 64 * waves, lds_bytes, ctx->stream>>>(
+            input_a, output_a, input_b, output_b, static_cast<int>(in_width), static_cast<int>(in_height), static_cast<int>(pitch), band_rows,
+            static_cast<int>(col_ranges), lv, flow2d::batch_arg(ctx, planes));
+    }
+    FLOW2D_CHECK_LAUNCH();
+    xy_levels_launches.fetch_add(1, std::memory_order_relaxed);
+    return FLOW2D_OK;
+}
+
+unsigned long long flow2d_resample_xy_levels_launches(void) { return xy_levels_launches.load(std::memory_order_relaxed); }
 
 int flow2d_resample_x(flow2d_context* ctx, const float* input, float* output, size_t out_width, size_t out_height,
                       size_t in_width, size_t pitch_bytes)

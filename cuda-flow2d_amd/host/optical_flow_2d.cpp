@@ -803,7 +803,31 @@ bool OpticalFlow2D::RunPyramid(OperationParameters& params)
         Release(temp);
     }
 
-    if (packed) {
+    // The halving pyramid (every level a power-of-two fraction of the frame in both directions): the x and the y passes of all
+    // levels in ONE launch that never writes the x-resampled rows (flow2d_resample_xy_levels; the same sums in the same order,
+    // the same bits).  Whether it applies is the entry's own answer, given before any launch, to the geometry
+    // (FLOW2D_ERR_UNSUPPORTED) and to where the planes lie (FLOW2D_ERR_INVALID_ARGUMENT: its alias check compares byte ranges,
+    // the two launches below compare base pointers) -- neither changes between recording a graph and an eager run, so both take
+    // the same path.  Everything else keeps the two launches, and the packed planes stay allocated for them (nothing else reads
+    // them); a device error fails the run.
+    std::vector<size_t> widths, heights, rows;  // the levels' regions in the stacked planes, from the finest to the coarsest
+    if (stacked) {
+        for (int l = first_level; l >= 1; --l) {
+            widths.push_back(level_width[static_cast<size_t>(l)]);
+            heights.push_back(level_height[static_cast<size_t>(l)]);
+            rows.push_back(level_row[static_cast<size_t>(l)]);
+        }
+    }
+    bool fused_levels = false;
+    if (stacked) {
+        const int status = flow2d_resample_xy_levels(context_, AsPlane(frame_0), AsPlane(frame_0_res), AsPlane(frame_1), AsPlane(frame_1_res),
+                                                     original_size.width, original_size.height, dev_container_size_.pitch,
+                                                     widths.size(), widths.data(), heights.data(), rows.data(), nullptr);
+        fused_levels = status != FLOW2D_ERR_UNSUPPORTED && status != FLOW2D_ERR_INVALID_ARGUMENT;
+        if (fused_levels && CheckFlow2DError(status, "flow2d_resample_xy_levels")) failed = true;
+    }
+
+    if (packed && !fused_levels) {
         if (CheckFlow2DError(flow2d_resample_x_levels(context_, AsPlane(frame_0), AsPlane(packed_frames_[0]),
                                                       AsPlane(frame_1), AsPlane(packed_frames_[1]),
                                                       original_size.width, original_size.height,
@@ -811,19 +835,12 @@ bool OpticalFlow2D::RunPyramid(OperationParameters& params)
                                                       packed_width.data(), packed_column.data()),
                              "flow2d_resample_x_levels"))
             failed = true;
-        if (stacked) {  // every level's y pass, both frames, one launch
-            std::vector<size_t> widths, heights, rows;
-            for (int l = first_level; l >= 1; --l) {
-                widths.push_back(level_width[static_cast<size_t>(l)]);
-                heights.push_back(level_height[static_cast<size_t>(l)]);
-                rows.push_back(level_row[static_cast<size_t>(l)]);
-            }
-            if (CheckFlow2DError(flow2d_resample_y_levels(context_, AsPlane(packed_frames_[0]), AsPlane(frame_0_res), AsPlane(packed_frames_[1]),
-                                                          AsPlane(frame_1_res), original_size.height, dev_container_size_.pitch, widths.size(),
-                                                          widths.data(), heights.data(), packed_column.data(), rows.data()),
-                                 "flow2d_resample_y_levels"))
-                failed = true;
-        }
+        if (stacked &&  // every level's y pass, both frames, one launch
+            CheckFlow2DError(flow2d_resample_y_levels(context_, AsPlane(packed_frames_[0]), AsPlane(frame_0_res), AsPlane(packed_frames_[1]),
+                                                      AsPlane(frame_1_res), original_size.height, dev_container_size_.pitch, widths.size(),
+                                                      widths.data(), heights.data(), packed_column.data(), rows.data()),
+                             "flow2d_resample_y_levels"))
+            failed = true;
     }
 
     DataSize3 current_size = {0, 0, 0}, prev_size = {0, 0, 0};

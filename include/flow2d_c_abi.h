@@ -795,6 +795,27 @@ FLOW2D_API int flow2d_resample_y_levels(flow2d_context* ctx, const float* packed
                                         const size_t* out_widths, const size_t* out_heights, const size_t* column_offsets,
                                         const size_t* output_rows);
 
+/* flow2d_resample_x_levels followed by flow2d_resample_y_levels as ONE launch that never stores the x-resampled rows: every source
+ * row is read once and only the levels are written.  Level l becomes an out_widths[l] x out_heights[l] region of the output plane
+ * whose first row is output_rows[l] and whose first column is output_columns[l] (in floats, a multiple of 4; output_columns may be
+ * NULL: every region starts at column 0).  Each output is bit-identical to the two calls composed: the left-to-right x sum
+ * times 1 / R, then the top-to-bottom y sum of those values times 1 / R.
+ * Eligible geometry (FLOW2D_ERR_UNSUPPORTED otherwise, before anything is launched): what a halving pyramid produces -- every
+ * level's ratio R is one power of two, 2 ... 256, in BOTH directions (out_widths[l] * R == in_width and out_heights[l] * R ==
+ * in_height), no two levels share a ratio, in_width is a multiple of 32 and at most 8192, at most 16 levels.
+ * Ranges: inputs are in_height rows of pitch_bytes (a multiple of 16, pointers 16-byte aligned); an output plane is written
+ * between its first and its last region row, [output + min(output_rows) * pitch, output + max(output_rows + out_heights) * pitch),
+ * and the caller owns those rows.  These byte ranges (with a batch: of all instances) must not meet each other or an input, and
+ * the regions of one plane must be disjoint rectangles inside the pitch: FLOW2D_ERR_INVALID_ARGUMENT otherwise, whatever the base
+ * pointers are.  input_b / output_b: optional second plane (both or neither). */
+FLOW2D_API int flow2d_resample_xy_levels(flow2d_context* ctx, const float* input_a, float* output_a, const float* input_b,
+                                         float* output_b, size_t in_width, size_t in_height, size_t pitch_bytes, size_t level_count,
+                                         const size_t* out_widths, const size_t* out_heights, const size_t* output_rows,
+                                         const size_t* output_columns);
+/* How many launches flow2d_resample_xy_levels has queued in this process, all contexts together (a launch recorded into a graph
+ * counts once, its replays do not): tells a caller or a test which path a pyramid took. */
+FLOW2D_API unsigned long long flow2d_resample_xy_levels_launches(void);
+
 /* compute_phi_ksi (src/kernels/solve_2d.cu:43-198). */
 FLOW2D_API int flow2d_compute_phi_ksi(flow2d_context* ctx, const float* frame_0, const float* frame_1,
                                       const float* flow_u, const float* flow_v, const float* flow_du,
