@@ -216,6 +216,21 @@ class DeformationStats(C.Structure):
 DEFORMATION_STATS_BYTES = 256  # FLOW2D_DEFORMATION_STATS_BYTES, checked by a static_assert in the header
 assert C.sizeof(DeformationStats) == DEFORMATION_STATS_BYTES
 
+
+REFINE_MAX_RADIUS = 7  # FLOW2D_REFINE_MAX_RADIUS
+
+
+class RefineRecord(C.Structure):
+    """flow2d_refine_record of include/flow2d_c_abi.h: the four counts flow2d_refine_flow_2d writes per instance."""
+    _fields_ = [("pixels", C.c_ulonglong), ("unfilled", C.c_ulonglong), ("filled", C.c_ulonglong), ("changed", C.c_ulonglong)]
+
+    def summary(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+REFINE_RECORD_BYTES = 32  # FLOW2D_REFINE_RECORD_BYTES, checked by a static_assert in the header
+assert C.sizeof(RefineRecord) == REFINE_RECORD_BYTES
+
 _hip = None
 
 
@@ -326,6 +341,8 @@ def hip_lib():
             L.flow2d_deformation_workspace_bytes.restype = sz
             L.flow2d_deformation_workspace_bytes.argtypes = [sz, sz, sz]
             L.flow2d_deformation_2d.argtypes = [vp, vp, vp, vp, sz, sz, sz, i, C.POINTER(DeformationPlanes), vp, vp, sz]
+        if hasattr(L, "flow2d_refine_flow_2d"):  # (absent from libraries of earlier rounds loaded for an A/B)
+            L.flow2d_refine_flow_2d.argtypes = [vp, vp, vp, vp, vp, sz, sz, sz, i, f, f, vp, vp, vp]
         if hasattr(L, "flow2d_segment_motion_2d"):  # (absent from libraries of earlier rounds loaded for an A/B)
             L.flow2d_segment_motion_workspace_bytes.restype = sz
             L.flow2d_segment_motion_workspace_bytes.argtypes = [sz, sz, sz]
@@ -836,6 +853,44 @@ class Context:
                 q.free()
                 self._planes.remove(q)
 
+    def refine_records(self, instances=1):
+        """A Plane for `instances` flow2d_refine_record records (device memory)."""
+        return self.plane(max(instances * REFINE_RECORD_BYTES // 4, 4), 1)
+
+    def read_refine_record(self, record, instances=1):
+        """The records of a refine_records Plane as RefineRecord structures (synchronises)."""
+        raw = record.download(instances * REFINE_RECORD_BYTES // 4, 1)
+        return list((RefineRecord * instances).from_buffer_copy(raw.tobytes()))
+
+    def refine_flow(self, pu, pv, w, h, radius, guide=None, mask=None, sigma_guide=0.0, sigma_space=0.0, out_u=None, out_v=None,
+                    record=True, instances=1):
+        """The edge-aware weighted median of the flow (pu, pv) over a (2 radius + 1)^2 window (flow2d_refine_flow_2d): a sample
+        weighs 1 - mask (mask: 1 where the vector is unreliable), times sigma_guide^2 / (sigma_guide^2 + d^2) for the
+        difference d of the `guide` plane when there is one and sigma_guide > 0, times sigma_space^2 / (sigma_space^2 +
+        distance^2) when sigma_space > 0; a pixel with nothing usable in its window keeps its vector.
+        out_u, out_v: the caller's Planes, which are written and stay on the device; without them the call allocates both,
+        downloads them and returns arrays.  record: True -- the counts are read back (synchronises) --, a refine_records Plane
+        of the caller's, or False / None.  Returns (u, v, RefineRecord or None)."""
+        own_planes = out_u is None and out_v is None
+        if not own_planes and (out_u is None or out_v is None):
+            raise ValueError("refine_flow takes both output planes or neither")
+        own_record = record is True
+        if own_record and instances != 1:
+            raise ValueError("a lock-step batch takes the caller's records")
+        held = [self.plane(pu.width, pu.height), self.plane(pu.width, pu.height)] if own_planes else [out_u, out_v]
+        rec = self.refine_records(instances) if own_record else (record or None)
+        try:
+            _check(hip_lib().flow2d_refine_flow_2d(self.handle, pu.ptr, pv.ptr, guide.ptr if guide else None,
+                                                   mask.ptr if mask else None, w, h, pu.pitch, int(radius), float(sigma_guide),
+                                                   float(sigma_space), held[0].ptr, held[1].ptr,
+                                                   rec.ptr if rec is not None else None), "flow2d_refine_flow_2d")
+            u, v = (q.download(w, h) for q in held) if own_planes else held
+            return u, v, (self.read_refine_record(rec, 1)[0] if own_record else None)
+        finally:
+            for q in (held if own_planes else []) + ([rec] if own_record else []):
+                q.free()
+                self._planes.remove(q)
+
     def resample_x(self, src, dst, out_w, out_h, in_w):
         _check(hip_lib().flow2d_resample_x(self.handle, src.ptr, dst.ptr, out_w, out_h, in_w, src.pitch),
                "flow2d_resample_x")
@@ -1017,6 +1072,11 @@ def host_lib():
                                                           C.POINTER(HostParams), fp, fp, fp]
             L.flow2d_host_analyse_deformation_device.argtypes = [vp, vp, vp, i, f, i, C.POINTER(vp), C.POINTER(DeformationStats),
                                                                  C.POINTER(HostParams), vp, vp, vp]
+        if hasattr(L, "flow2d_host_refine_flow"):
+            rr = C.POINTER(RefineRecord)
+            L.flow2d_host_refine_args_ok.argtypes = [i, f, f, i]
+            L.flow2d_host_refine_flow.argtypes = [vp, fp, fp, i, f, f, i, i, fp, fp, rr, C.POINTER(HostParams), fp, fp, fp]
+            L.flow2d_host_refine_flow_device.argtypes = [vp, vp, vp, i, f, f, i, i, vp, vp, rr, C.POINTER(HostParams), vp, vp, vp, i]
         if hasattr(L, "flow2d_host_segment_motion"):
             d, u32 = C.c_double, C.c_uint
             head = [i, d, i, i, f, f, u32, C.POINTER(GlobalMotion), C.POINTER(SegmentSummary), C.POINTER(MotionRegion),
@@ -1401,6 +1461,39 @@ class OpticalFlow:
         if rc:
             raise Flow2DError(rc, "OpticalFlow2D::AnalyseDeformationDevice")
         return record
+
+    def refine_flow(self, frame_0, frame_1, params, radius=5, sigma_guide=25.0, sigma_space=0.0, iterations=1, masks=True,
+                    flow=False):
+        """OpticalFlow2D::RefineFlow: the flow frame_0 -> frame_1 of the host pair (bidirectional with masks) refined by
+        `iterations` passes of flow2d_refine_flow_2d -- the weighted median over a (2 radius + 1)^2 window with frame_0 as the
+        guide and, with masks, the forward occlusion mask taking unreliable vectors out.  Returns (u, v, RefineRecord of the last
+        pass); with flow, also the (u, v) before the refinement."""
+        f0, f1 = self._pair(frame_0, frame_1)
+        u, v = np.empty_like(f0), np.empty_like(f0)
+        uv = [np.empty_like(f0) for _ in range(2)] if flow else [None, None]
+        record = RefineRecord()
+        rc = host_lib().flow2d_host_refine_flow(self.handle, _fptr(f0), _fptr(f1), int(radius), float(sigma_guide), float(sigma_space),
+                                                int(iterations), int(bool(masks)), _fptr(u), _fptr(v), C.byref(record),
+                                                C.byref(params), _opt_fptr(uv[0]), _opt_fptr(uv[1]), None)
+        if rc:
+            raise Flow2DError(rc, "OpticalFlow2D::RefineFlow")
+        return (u, v, record, tuple(uv)) if flow else (u, v, record)
+
+    def refine_flow_device(self, dev_frame_0, dev_frame_1, dev_refined, params, radius=5, sigma_guide=25.0, sigma_space=0.0,
+                           iterations=1, masks=True, dev_flow=None, dev_mask=None, flow_given=False, record=True):
+        """OpticalFlow2D::RefineFlowDevice: device frames in, dev_refined (a (u, v) pair of device planes) out.  dev_flow (a
+        (u, v) pair) and dev_mask: optional device planes that get the flow before the refinement and the occlusion mask -- or,
+        with flow_given, that hold the flow to refine and (optionally) its mask, computed elsewhere (dev_frame_1 may then be
+        None).  Returns the RefineRecord of the last pass (None without record); synchronises."""
+        rec = RefineRecord() if record else None
+        fl = dev_flow or (None, None)
+        rc = host_lib().flow2d_host_refine_flow_device(self.handle, dev_frame_0, dev_frame_1, int(radius), float(sigma_guide),
+                                                       float(sigma_space), int(iterations), int(bool(masks)), dev_refined[0],
+                                                       dev_refined[1], C.byref(rec) if record else None, C.byref(params), fl[0], fl[1],
+                                                       dev_mask, int(bool(flow_given)))
+        if rc:
+            raise Flow2DError(rc, "OpticalFlow2D::RefineFlowDevice")
+        return rec
 
     def stabilise_sequence(self, frames, params, reference_index=0, model=MOTION_AFFINE, sigma=0.5, iterations=5, masks=False,
                            fill=0.0):

@@ -501,6 +501,52 @@ HOST_API int flow2d_host_analyse_deformation_device(flow2d_host_flow* h, void* d
                : 2;
 }
 
+// OpticalFlow2D::RefineArgsOk: 1 when the arguments are what RefineFlow accepts.  Needs no device.
+HOST_API int flow2d_host_refine_args_ok(int radius, float sigma_guide, float sigma_space, int iterations)
+{
+    return OpticalFlow2D::RefineArgsOk(radius, sigma_guide, sigma_space, iterations) ? 1 : 0;
+}
+
+// OpticalFlow2D::RefineFlow on tight host images: refined_u / refined_v get the refined flow, record (optional) the counts of the
+// last pass, flow_u / flow_v (optional) the flow before the refinement, mask (optional, use_masks only) the occlusion mask.  0 on
+// success, 1 for a null or refused argument, 2 when the run delivered nothing.
+HOST_API int flow2d_host_refine_flow(flow2d_host_flow* h, const float* frame_0, const float* frame_1, int radius, float sigma_guide,
+                                     float sigma_space, int iterations, int use_masks, float* refined_u, float* refined_v,
+                                     flow2d_refine_record* record, const flow2d_host_params* params, float* flow_u, float* flow_v,
+                                     float* mask)
+{
+    if (!OpticalFlow2D::RefineArgsOk(radius, sigma_guide, sigma_space, iterations) || !h || !frame_0 || !frame_1 || !refined_u ||
+        !refined_v || !params || (flow_u == nullptr) != (flow_v == nullptr) || (mask && !use_masks))
+        return 1;
+    HostImages im(h);
+    Data2D *f0 = im.In(frame_0), *f1 = im.In(frame_1), *out[5];
+    float* dst[5] = {refined_u, refined_v, flow_u, flow_v, mask};
+    for (int i = 0; i < 5; ++i) out[i] = im.Out(dst[i], im.AfterSuccess);
+    Bag bag(*params);
+    h->flow.RefineFlow(*f0, *f1, radius, sigma_guide, sigma_space, iterations, use_masks != 0, *out[0], *out[1], record, bag, out[2],
+                       out[3], out[4]);
+    return im.Finish(h->flow);
+}
+
+// OpticalFlow2D::RefineFlowDevice: device planes; with flow_given the flow planes (and the optional mask) are the flow to refine
+// and dev_frame_1 may be null.  Synchronises.  0 on success, 1 for a null or refused argument, 2 when the run failed.
+HOST_API int flow2d_host_refine_flow_device(flow2d_host_flow* h, void* dev_frame_0, void* dev_frame_1, int radius, float sigma_guide,
+                                            float sigma_space, int iterations, int use_masks, void* dev_refined_u,
+                                            void* dev_refined_v, flow2d_refine_record* record, const flow2d_host_params* params,
+                                            void* dev_flow_u, void* dev_flow_v, void* dev_mask, int flow_given)
+{
+    if (!OpticalFlow2D::RefineArgsOk(radius, sigma_guide, sigma_space, iterations) || !h || !dev_frame_0 || !dev_refined_u ||
+        !dev_refined_v || !params)
+        return 1;
+    Bag bag(*params);
+    h->flow.timing_mode = 0;
+    return h->flow.RefineFlowDevice(dp(dev_frame_0), dp(dev_frame_1), radius, sigma_guide, sigma_space, iterations, use_masks != 0,
+                                    dp(dev_refined_u), dp(dev_refined_v), record, bag, dp(dev_flow_u), dp(dev_flow_v), dp(dev_mask),
+                                    flow_given != 0)
+               ? 0
+               : 2;
+}
+
 // OpticalFlow2D::StabiliseSequence on tight host images: frames = frame_count * width * height floats (frame k at k * width *
 // height); outputs get the same layout, motions (optional) frame_count records.  0 on success, 1 for a null or refused argument,
 // 2 when the run delivered no frames.

@@ -50,6 +50,14 @@
 // dilatation, exx, eyy, exy, e1, e2 and max-shear likewise (F32, NaN where a pixel has no derivative) and prints one line
 // "Deformation: {json}" -- "measure", "sigma", "valid", "invalid" and per quantity "mean", "rms", "min", "max" with 17 significant
 // digits.  The other files do not change; a run of its own.
+// --refine R (a radius of 1 .. 7) [--refine-sigma S, grey levels, finite and >= 0, default 25; 0: no guide weight] [--refine-space P,
+// pixels, finite and >= 0, default 0: no spatial weight] [--refine-iterations K, 1 .. 16, default 1] refines the forward flow
+// before it is written (OpticalFlow2D::RefineFlow: K passes of flow2d_refine_flow_2d, the weighted median over a (2R + 1)^2
+// window guided by frame 1; with --backward the forward occlusion mask takes unreliable vectors out and they are filled in from
+// their surroundings): the forward files -- flow-u, flow-v, res.pgm, amp, flow.flo -- then hold the refined flow, and one line
+// "Refinement: {json}" -- "radius", "sigma", "space", "iterations" and the last pass's "pixels", "unfilled", "filled", "changed" --
+// is printed.  With --ground-truth the line "Flow error: {json}" scores the refined flow and a second line "Flow error before
+// refinement: {json}" the flow as computed.  The other files do not change; a run of its own.  Without --refine nothing changes.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -99,6 +107,9 @@ int main(int argc, char** argv)
     bool deformation = false;  // --deformation
     int strain_measure = FLOW2D_STRAIN_SMALL;
     float deformation_sigma = 0.f;
+    int refine_radius = 0;  // --refine R (0: off)
+    float refine_sigma = 25.f, refine_space = 0.f;
+    int refine_iterations = 1;
     std::string ground_truth_file;
     int device = 0;
     float sor_omega = 0.f;
@@ -218,6 +229,30 @@ int main(int argc, char** argv)
                 return 5;
             }
             deformation_sigma = value;
+            ++i;
+        }
+        else if (!std::strcmp(argv[i], "--refine") || !std::strcmp(argv[i], "--refine-iterations")) {
+            const bool radius = !std::strcmp(argv[i], "--refine");
+            char* end = nullptr;
+            const long n = (i + 1 < argc) ? std::strtol(argv[i + 1], &end, 10) : 0;
+            if (i + 1 >= argc || end == argv[i + 1] || *end != '\0' || n < 1 ||
+                n > (radius ? FLOW2D_REFINE_MAX_RADIUS : OpticalFlow2D::kRefineMaxIterations)) {
+                if (radius) std::printf("--refine takes a window radius R of 1 .. %d.\n", FLOW2D_REFINE_MAX_RADIUS);
+                else std::printf("--refine-iterations takes an integer K of 1 .. %d.\n", OpticalFlow2D::kRefineMaxIterations);
+                return 5;
+            }
+            (radius ? refine_radius : refine_iterations) = static_cast<int>(n);
+            ++i;
+        }
+        else if (!std::strcmp(argv[i], "--refine-sigma") || !std::strcmp(argv[i], "--refine-space")) {
+            const bool guide = !std::strcmp(argv[i], "--refine-sigma");
+            char* end = nullptr;
+            const float value = (i + 1 < argc) ? std::strtof(argv[i + 1], &end) : 0.f;
+            if (i + 1 >= argc || end == argv[i + 1] || *end != '\0' || !std::isfinite(value) || value < 0.f) {
+                std::printf("%s takes a finite number >= 0 (%s; 0: that weight is off).\n", argv[i], guide ? "grey levels" : "pixels");
+                return 5;
+            }
+            (guide ? refine_sigma : refine_space) = value;
             ++i;
         }
         else if (!std::strcmp(argv[i], "--device") && i + 1 < argc) device = std::atoi(argv[++i]);
@@ -367,11 +402,34 @@ int main(int argc, char** argv)
             return 4;  // superset of the reference's exit codes (0, 1, 2, 3, 255)
         }
 
+        // --refine: the forward files hold the refined flow; flow_u / flow_v keep the flow as computed
+        Data2D refined_u, refined_v;
+        if (refine_radius) {
+            refined_u = Data2D(width, height);
+            refined_v = Data2D(width, height);
+            flow2d_refine_record record;
+            optical_flow.RefineFlow(frame_0, frame_1, refine_radius, refine_sigma, refine_space, refine_iterations, backward, refined_u,
+                                    refined_v, &record, params);
+            if (!optical_flow.LastRunSucceeded()) {
+                std::cout << "Error: the flow refinement failed, no output written." << std::endl;
+                optical_flow.Destroy();
+                DestroyDeviceContext();
+                return 4;
+            }
+            std::printf("Refinement: {\"radius\": %d, \"sigma\": %.9g, \"space\": %.9g, \"iterations\": %d, \"pixels\": %llu, "
+                        "\"unfilled\": %llu, \"filled\": %llu, \"changed\": %llu}\n",
+                        refine_radius, refine_sigma, refine_space, refine_iterations, record.pixels, record.unfilled, record.filled,
+                        record.changed);
+        }
+        Data2D& computed_u = flow_u;
+        Data2D& computed_v = flow_v;
+        Data2D& written_u = refine_radius ? refined_u : flow_u;
+        Data2D& written_v = refine_radius ? refined_v : flow_v;
         const std::string suffix = "-" + std::to_string(width) + "-" + std::to_string(height) + ".raw";
-        flow_u.WriteRAWToFileF32((output_path + counter + "flow-u" + suffix).c_str());
-        flow_v.WriteRAWToFileF32((output_path + counter + "flow-v" + suffix).c_str());
-        IOUtils::WriteFlowToImageRGB(flow_u, flow_v, 10, output_path + counter + "res.pgm");
-        IOUtils::WriteMagnitudeToFileF32(flow_u, flow_v, output_path + counter + "amp" + suffix);
+        written_u.WriteRAWToFileF32((output_path + counter + "flow-u" + suffix).c_str());
+        written_v.WriteRAWToFileF32((output_path + counter + "flow-v" + suffix).c_str());
+        IOUtils::WriteFlowToImageRGB(written_u, written_v, 10, output_path + counter + "res.pgm");
+        IOUtils::WriteMagnitudeToFileF32(written_u, written_v, output_path + counter + "amp" + suffix);
         if (backward) {
             back_u.WriteRAWToFileF32((output_path + counter + "flow-u-backward" + suffix).c_str());
             back_v.WriteRAWToFileF32((output_path + counter + "flow-v-backward" + suffix).c_str());
@@ -383,7 +441,7 @@ int main(int argc, char** argv)
             between[k - 1].WriteRAWToFileF32((output_path + counter + "interp-" + std::to_string(k) + "-of-" +
                                               std::to_string(interpolate) + suffix).c_str());
         if (write_flo) {
-            bool ok = IOUtils::WriteFlowFLO(flow_u, flow_v, output_path + counter + "flow.flo");
+            bool ok = IOUtils::WriteFlowFLO(written_u, written_v, output_path + counter + "flow.flo");
             if (backward) ok = ok && IOUtils::WriteFlowFLO(back_u, back_v, output_path + counter + "flow-backward.flo");
             if (!ok) {
                 std::cerr << "Error: cannot save file " << std::endl;
@@ -528,12 +586,20 @@ int main(int argc, char** argv)
         }
         if (!ground_truth_file.empty()) {
             flow2d_flow_error_stats stats;
-            if (!EvaluateFlow(flow_u, flow_v, gt_u, gt_v, backward ? &occlusion_0 : nullptr, stats)) {
+            if (!EvaluateFlow(written_u, written_v, gt_u, gt_v, backward ? &occlusion_0 : nullptr, stats)) {
                 optical_flow.Destroy();
                 DestroyDeviceContext();
                 return 4;
             }
             std::printf("Flow error: %s\n", FlowErrorJson(stats).c_str());
+            if (refine_radius) {
+                if (!EvaluateFlow(computed_u, computed_v, gt_u, gt_v, backward ? &occlusion_0 : nullptr, stats)) {
+                    optical_flow.Destroy();
+                    DestroyDeviceContext();
+                    return 4;
+                }
+                std::printf("Flow error before refinement: %s\n", FlowErrorJson(stats).c_str());
+            }
         }
         optical_flow.Destroy();
     }

@@ -250,6 +250,25 @@ public:
                             Data2D* const* planes, flow2d_deformation_stats* stats_out, OperationParameters& params,
                             Data2D* flow_u = nullptr, Data2D* flow_v = nullptr, Data2D* mask = nullptr);
 
+    // Edge-aware refinement of a pair's flow (no reference counterpart): the flow frame_0 -> frame_1 (ComputeFlowDevice's bits;
+    // with use_masks through ComputeFlowBidirectionalDevice, the forward occlusion mask then being the `mask` of the filter), then
+    // `iterations` passes of flow2d_refine_flow_2d with frame 0 as the guide, the mask applied in every pass, ping-ponging between
+    // planes of the object's own; the last pass writes dev_refined_u / dev_refined_v.  record_out (host, optional) gets the record
+    // of the last pass.  dev_flow_u / dev_flow_v (optional) get the flow before the refinement and dev_mask (optional, use_masks
+    // only) the occlusion mask -- or, with flow_given, they ARE the flow to refine, computed elsewhere by the caller, and (optional)
+    // its mask: no flow is computed then and dev_frame_1 is not used.  RefineArgsOk prints what is wrong and needs no device.  The
+    // object's own planes and record are allocated at the first call and kept.  The call synchronises.  Not for lock-step groups.
+    static constexpr int kRefineMaxIterations = 16;
+    static bool RefineArgsOk(int radius, float sigma_guide, float sigma_space, int iterations);
+    bool RefineFlowDevice(DevicePtr dev_frame_0, DevicePtr dev_frame_1, int radius, float sigma_guide, float sigma_space,
+                          int iterations, bool use_masks, DevicePtr dev_refined_u, DevicePtr dev_refined_v,
+                          flow2d_refine_record* record_out, OperationParameters& params, DevicePtr dev_flow_u = 0,
+                          DevicePtr dev_flow_v = 0, DevicePtr dev_mask = 0, bool flow_given = false);
+    // The host-image form (the CLI's --refine).  LastRunSucceeded and LastTotalMs as for ComputeFlow.
+    void RefineFlow(Data2D& frame_0, Data2D& frame_1, int radius, float sigma_guide, float sigma_space, int iterations,
+                    bool use_masks, Data2D& refined_u, Data2D& refined_v, flow2d_refine_record* record_out,
+                    OperationParameters& params, Data2D* flow_u = nullptr, Data2D* flow_v = nullptr, Data2D* mask = nullptr);
+
     // When set, ComputeFlowDevice records the whole pyramid of a pair into a HIP graph the first time it
     // sees a (buffers, parameters) combination and replays it afterwards: one host call instead of
     // several hundred launches.  Ignored while timing_mode != 0 (events are not captured).
@@ -420,6 +439,10 @@ private:
     // use_masks only), the smoothed flow (u, v; with a sigma only) and, in one allocation, the record and the workspace
     OwnedPlanes deformation_planes_{owned_, 8};
     DeviceScratch deformation_scratch_{owned_};
+    // RefineFlow*: the pair's flow (u, v, back u, back v, occlusion forward, occlusion backward; the last four with use_masks
+    // only), the two ping-pong pairs of the passes before the last (from the second and the third iteration on) and the record
+    OwnedPlanes refine_planes_{owned_, 10};
+    DeviceScratch refine_scratch_{owned_};
     flow2d_context* context_ = nullptr;
     // One plane beside the pool: the warped frame of a level, when the levels of both frames are computed up front into plane
     // regions of their own (RunPyramid: "stacked" levels) and therefore cannot be overwritten by the warp

@@ -1,5 +1,5 @@
 // The applications built on the flow: frame interpolation, point trajectories, global motion and stabilisation, motion
-// segmentation, deformation analysis and temporal denoising.  Each has a ...Device entry on planes that already sit on the device
+// segmentation, deformation analysis, flow refinement and temporal denoising.  Each has a ...Device entry on planes that already sit on the device
 // and a host-image entry that uploads, calls it and downloads (CallPlanes + HostCall, host_entry.h).  The flow itself -- the
 // pyramid, the sequence cache, ComputeFlow* -- is optical_flow_2d.cpp.
 #include <algorithm>
@@ -442,6 +442,82 @@ void OpticalFlow2D::AnalyseDeformation(Data2D& frame_0, Data2D& frame_1, int mea
     const DevicePtr* d = planes.data();
     last_run_ok_ = planes.Upload() &&
                    AnalyseDeformationDevice(d[0], d[1], measure, smoothing_sigma, use_masks, d + 5, stats_out, params, d[2], d[3], d[4]) &&
+                   planes.Download();
+}
+
+bool OpticalFlow2D::RefineArgsOk(int radius, float sigma_guide, float sigma_space, int iterations)
+{
+    if (radius < 1 || radius > FLOW2D_REFINE_MAX_RADIUS || !(std::isfinite(sigma_guide) && sigma_guide >= 0.f) ||
+        !(std::isfinite(sigma_space) && sigma_space >= 0.f) || iterations < 1 || iterations > kRefineMaxIterations) {
+        std::printf("Error: flow refinement takes a radius of 1 .. %d (%d), finite sigmas >= 0 (guide %g, space %g) and 1 .. %d iterations (%d).\n",
+                    FLOW2D_REFINE_MAX_RADIUS, radius, sigma_guide, sigma_space, kRefineMaxIterations, iterations);
+        return false;
+    }
+    return true;
+}
+
+bool OpticalFlow2D::RefineFlowDevice(DevicePtr dev_frame_0, DevicePtr dev_frame_1, int radius, float sigma_guide, float sigma_space,
+                                     int iterations, bool use_masks, DevicePtr dev_refined_u, DevicePtr dev_refined_v,
+                                     flow2d_refine_record* record_out, OperationParameters& params, DevicePtr dev_flow_u,
+                                     DevicePtr dev_flow_v, DevicePtr dev_mask, bool flow_given)
+{
+    if (!RefineArgsOk(radius, sigma_guide, sigma_space, iterations)) return false;
+    if (!IsInitialized() || !dev_frame_0 || !dev_refined_u || !dev_refined_v || (dev_flow_u == 0) != (dev_flow_v == 0)) return false;
+    if (flow_given ? !dev_flow_u : (!dev_frame_1 || (dev_mask && !use_masks))) return false;
+    if (RefuseGroup("flow refinement")) return false;
+    const size_t W = dev_container_size_.width, H = dev_container_size_.height, pitch = dev_container_size_.pitch;
+    DevicePtr* p = refine_planes_.begin();
+    const size_t middle = iterations > 2 ? 4 : iterations > 1 ? 2 : 0;  // ping-pong planes of the passes before the last
+    if ((!flow_given && !EnsurePlanes(p, use_masks ? 6 : 2)) || !EnsurePlanes(p + 6, middle)) return false;
+    if (record_out && !refine_scratch_.Ensure(context_, sizeof(flow2d_refine_record))) return false;
+    DevicePtr flow[2] = {dev_flow_u, dev_flow_v}, mask = dev_mask;
+    if (!flow_given) {
+        // (group_ > 1 is refused by both)
+        const DevicePtr frames[2] = {dev_frame_0, dev_frame_1};
+        if (!(use_masks ? ComputeFlowBidirectionalDevice(frames, 2, p, p + 1, p + 2, p + 3, p + 4, p + 5, params)
+                        : ComputeFlowSequenceDevice(frames, 2, p, p + 1, params)))
+            return false;
+        flow[0] = p[0];
+        flow[1] = p[1];
+        mask = use_masks ? p[4] : 0;
+    }
+    flow2d_refine_record* record = record_out ? refine_scratch_.At<flow2d_refine_record>() : nullptr;
+    bool ok = true;
+    const DevicePtr* in = flow;
+    for (int k = 0; ok && k < iterations; ++k) {
+        const bool last = k + 1 == iterations;
+        const DevicePtr refined[2] = {dev_refined_u, dev_refined_v};
+        const DevicePtr* out = last ? refined : p + 6 + 2 * (k % 2);
+        ok = !CheckFlow2DError(flow2d_refine_flow_2d(context_, AsPlane(in[0]), AsPlane(in[1]), AsPlane(dev_frame_0),
+                                                     mask ? AsPlane(mask) : nullptr, W, H, pitch, radius, sigma_guide, sigma_space,
+                                                     AsPlane(out[0]), AsPlane(out[1]), last ? record : nullptr),
+                               "flow2d_refine_flow_2d");
+        in = p + 6 + 2 * (k % 2);
+    }
+    ok = ok && (!record_out || ReadRecord(record_out, record, sizeof(*record_out)));
+    if (ok && !flow_given) {
+        const DevicePtr own[3] = {flow[0], flow[1], mask}, callers[3] = {dev_flow_u, dev_flow_v, dev_mask};
+        ok = HandBack(2, own, callers) && (!mask || HandBack(1, own + 2, callers + 2));
+    }
+    return !CheckFlow2DError(flow2d_synchronize(context_), "flow2d_synchronize") && ok;
+}
+
+void OpticalFlow2D::RefineFlow(Data2D& frame_0, Data2D& frame_1, int radius, float sigma_guide, float sigma_space, int iterations,
+                               bool use_masks, Data2D& refined_u, Data2D& refined_v, flow2d_refine_record* record_out,
+                               OperationParameters& params, Data2D* flow_u, Data2D* flow_v, Data2D* mask)
+{
+    last_run_ok_ = false;
+    if (!RefineArgsOk(radius, sigma_guide, sigma_space, iterations)) return;
+    if (!IsInitialized() || (flow_u == nullptr) != (flow_v == nullptr) || (mask && !use_masks)) return;
+    CallPlanes planes(context_, dev_container_size_, GetName(), "frame / flow");
+    planes.Add(&frame_0, CallPlanes::In).Add(&frame_1, CallPlanes::In).Add(&refined_u, CallPlanes::Out).Add(&refined_v, CallPlanes::Out);
+    planes.Add(flow_u, CallPlanes::Out).Add(flow_v, CallPlanes::Out).Add(mask, CallPlanes::Out);
+    if (!planes.SizesMatch()) return;
+    HostCall call(context_, last_total_ms_, planes.Allocate());
+    const DevicePtr* d = planes.data();
+    last_run_ok_ = planes.Upload() &&
+                   RefineFlowDevice(d[0], d[1], radius, sigma_guide, sigma_space, iterations, use_masks, d[2], d[3], record_out, params,
+                                    d[4], d[5], d[6]) &&
                    planes.Download();
 }
 

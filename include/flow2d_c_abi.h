@@ -39,8 +39,8 @@ extern "C" {
  * flow2d_seed_points_workspace_bytes (dense point trajectories), flow2d_denoise_2d / flow2d_compose_flow_2d
  * (motion-compensated temporal denoising) and flow2d_global_motion_2d / flow2d_global_motion_workspace_bytes /
  * flow2d_global_flow_2d / flow2d_warp_global_2d (robust global motion and stabilisation), flow2d_segment_motion_2d /
- * flow2d_segment_motion_workspace_bytes (motion segmentation) and flow2d_deformation_2d / flow2d_deformation_workspace_bytes
- * (strain, divergence and vorticity of a flow) were added under 1. */
+ * flow2d_segment_motion_workspace_bytes (motion segmentation), flow2d_deformation_2d / flow2d_deformation_workspace_bytes
+ * (strain, divergence and vorticity of a flow) and flow2d_refine_flow_2d (edge-aware refinement of a flow) were added under 1. */
 #define FLOW2D_ABI_VERSION 1
 
 typedef enum flow2d_status {
@@ -720,6 +720,57 @@ FLOW2D_API int flow2d_deformation_2d(flow2d_context* ctx, const float* flow_u, c
                                      int measure, const flow2d_deformation_planes* out /* host, may be NULL */,
                                      flow2d_deformation_stats* stats /* device, may be NULL */, void* workspace,
                                      size_t workspace_bytes);
+
+/* Edge-aware refinement of a flow: a weighted median over a (2 radius + 1)^2 window, guided by an image, that skips unreliable
+ * vectors and so gives an occluded pixel the motion of the surface it belongs to (the non-local term of Sun, Roth & Black, CVPR
+ * 2010; no reference counterpart; added to ABI version 1 without changing any existing entry).  All arithmetic is fp32, every
+ * operation rounded on its own (no fused multiply-add; division correctly rounded), in the order written; no transcendental.
+ *
+ * Weight of a sample.  For the output pixel x and a window offset (dx, dy), |dx|, |dy| <= radius, the sample is the pixel
+ * p = x + (dx, dy).  It takes part when p is inside the frame and |flow_u[p]| <= 1e9 and |flow_v[p]| <= 1e9 (a NaN, an infinity
+ * and the unknown-flow value of .flo files fail: the rule of flow2d_flow_error_2d).  Its weight:
+ *   m = mask ? mask[p] : 0;  if (!(m <= 1)) m = 1;  if (!(m >= 0)) m = 0            (the clamp of flow2d_global_motion_2d: NaN = 1;
+ *                                                                                    `mask` is 1 where the vector is unreliable)
+ *   w = 1 - m
+ *   guide != NULL and sigma_guide > 0:   d = guide[p] - guide[x];   w = w * sg2 / (sg2 + d*d),   sg2 = sigma_guide * sigma_guide
+ *   sigma_space > 0:                     w = w * ss2 / (ss2 + (float)(dx*dx + dy*dy)),            ss2 = sigma_space * sigma_space
+ *   q = (int)floorf(4096.f * w), and q = 0 when w is not finite or the sample takes no part
+ * The weights are integers of at most 4096: their sum over the window, Q, is exact in 32 bits, and the result depends neither on
+ * an order of summation nor on the selection algorithm.
+ * Result.  Each component is filtered on its own with the same weights: the output is the smallest sample value x_k among the
+ * samples with q > 0 for which 2 * (the summed q of the samples with value <= x_k) >= Q.  A -0 result is written as +0.  Where
+ * Q = 0 -- nothing usable in the window -- the input vector is copied bit for bit.  With no guide, no mask and sigma_space = 0 this
+ * is the plain median over the part of the window inside the frame (the lower one of an even count).
+ * Record.  record[b] (DEVICE memory, may be NULL) gets four counts for instance b of a lock-step batch: pixels (width * height),
+ * unfilled (Q = 0), filled (the pixel's own clamped mask value is >= 0.5 and Q > 0; 0 without a mask) and changed (the output
+ * differs from the input in the bits of either component).  Integers, added by integer atomics after the entry has zeroed the
+ * record on the stream: repeated calls, a replayed graph and an instance alone or in its batch give the same bytes.
+ * Row padding and the container beyond width x height are neither read into a result nor written.  One launch on the context's
+ * stream (and a 32-byte memset per instance with a record); no allocation, no synchronisation, no host round trip
+ * (graph-capturable).  Honours flow2d_context_set_batch: planes at b * stride, record + b.
+ * FLOW2D_ERR_INVALID_ARGUMENT for a null flow or output plane, a zero size, a bad pitch (the rule of flow2d_consistency_2d), a
+ * radius outside 1 .. FLOW2D_REFINE_MAX_RADIUS, a negative, NaN or infinite sigma, a misaligned `record` (8), or a written range
+ * -- out_u, out_v, the records, over every instance of a batch -- that overlaps an input plane or another written range: the
+ * filter reads a window, so it cannot run in place. */
+#define FLOW2D_REFINE_MAX_RADIUS 7
+typedef struct flow2d_refine_record {
+    unsigned long long pixels;   /* width * height */
+    unsigned long long unfilled; /* Q = 0: the input was copied */
+    unsigned long long filled;   /* masked (>= 0.5) pixels that got a value from their window */
+    unsigned long long changed;  /* outputs that differ from the input by bits */
+} flow2d_refine_record;
+
+#define FLOW2D_REFINE_RECORD_BYTES 32
+#ifdef __cplusplus
+static_assert(sizeof(flow2d_refine_record) == FLOW2D_REFINE_RECORD_BYTES, "flow2d_refine_record layout");
+#else
+_Static_assert(sizeof(flow2d_refine_record) == FLOW2D_REFINE_RECORD_BYTES, "flow2d_refine_record layout");
+#endif
+
+FLOW2D_API int flow2d_refine_flow_2d(flow2d_context* ctx, const float* flow_u, const float* flow_v,
+                                     const float* guide /* may be NULL */, const float* mask /* may be NULL */, size_t width,
+                                     size_t height, size_t pitch_bytes, int radius, float sigma_guide, float sigma_space,
+                                     float* out_u, float* out_v, flow2d_refine_record* record /* device, may be NULL */);
 
 /* The flow of the previous pyramid level resampled to this level's size (the bits of flow2d_resample_xy_pair into out_u / out_v)
  * and frame_1 warped by it (the bits of flow2d_registration_2d into `output`) in one launch: replaces the
