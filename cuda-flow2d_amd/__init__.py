@@ -231,6 +231,30 @@ class RefineRecord(C.Structure):
 REFINE_RECORD_BYTES = 32  # FLOW2D_REFINE_RECORD_BYTES, checked by a static_assert in the header
 assert C.sizeof(RefineRecord) == REFINE_RECORD_BYTES
 
+
+CORRELATION_MAX_RADIUS, CORRELATION_MAX_RANGE, CORRELATION_MAX_SPACING = 15, 32, 64  # FLOW2D_CORRELATION_MAX_*
+
+
+class CorrelationRecord(C.Structure):
+    """flow2d_correlation_record of include/flow2d_c_abi.h: the four counts flow2d_correlate_2d writes per instance."""
+    _fields_ = [("nodes", C.c_ulonglong), ("invalid", C.c_ulonglong), ("rejected", C.c_ulonglong), ("unrefined", C.c_ulonglong)]
+
+    def summary(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+CORRELATION_RECORD_BYTES = 32  # FLOW2D_CORRELATION_RECORD_BYTES, checked by a static_assert in the header
+assert C.sizeof(CorrelationRecord) == CORRELATION_RECORD_BYTES
+
+
+def correlation_grid(width, height, radius, spacing):
+    """(nw, nh): the node grid of flow2d_correlate_2d (flow2d_correlation_grid).  Needs no device."""
+    nw, nh = C.c_size_t(), C.c_size_t()
+    _check(hip_lib().flow2d_correlation_grid(width, height, int(radius), int(spacing), C.byref(nw), C.byref(nh)),
+           "flow2d_correlation_grid")
+    return nw.value, nh.value
+
+
 _hip = None
 
 
@@ -343,6 +367,10 @@ def hip_lib():
             L.flow2d_deformation_2d.argtypes = [vp, vp, vp, vp, sz, sz, sz, i, C.POINTER(DeformationPlanes), vp, vp, sz]
         if hasattr(L, "flow2d_refine_flow_2d"):  # (absent from libraries of earlier rounds loaded for an A/B)
             L.flow2d_refine_flow_2d.argtypes = [vp, vp, vp, vp, vp, sz, sz, sz, i, f, f, vp, vp, vp]
+        if hasattr(L, "flow2d_correlate_2d"):  # (absent from libraries of earlier rounds loaded for an A/B)
+            L.flow2d_correlation_grid.argtypes = [sz, sz, i, i, C.POINTER(sz), C.POINTER(sz)]
+            L.flow2d_correlate_2d.argtypes = [vp, vp, vp, sz, sz, sz, f, f, i, i, i, f, vp, vp, vp, sz, vp]
+            L.flow2d_expand_nodes_2d.argtypes = [vp, vp, vp, sz, sz, sz, i, i, vp, vp, sz, sz, sz]
         if hasattr(L, "flow2d_segment_motion_2d"):  # (absent from libraries of earlier rounds loaded for an A/B)
             L.flow2d_segment_motion_workspace_bytes.restype = sz
             L.flow2d_segment_motion_workspace_bytes.argtypes = [sz, sz, sz]
@@ -891,6 +919,52 @@ class Context:
                 q.free()
                 self._planes.remove(q)
 
+    def correlation_records(self, instances=1):
+        """A Plane for `instances` flow2d_correlation_record records (device memory)."""
+        return self.plane(max(instances * CORRELATION_RECORD_BYTES // 4, 4), 1)
+
+    def read_correlation_record(self, record, instances=1):
+        """The records of a correlation_records Plane as CorrelationRecord structures (synchronises)."""
+        raw = record.download(instances * CORRELATION_RECORD_BYTES // 4, 1)
+        return list((CorrelationRecord * instances).from_buffer_copy(raw.tobytes()))
+
+    def correlate(self, f0, f1, w, h, lo, scale, radius, search, spacing, min_score=-1.0, node_u=None, node_v=None,
+                  node_score=None, record=True, instances=1):
+        """Window correlation of the frames f0 -> f1 (flow2d_correlate_2d): both are quantised to 8 bits by (I - lo) * scale, and
+        every node of the grid correlation_grid(w, h, radius, spacing) gets the displacement, |dx|, |dy| <= `search` (the
+        header's `range`), at which its (2 radius + 1)^2 window of f0 correlates best with f1, refined to sub-pixel by a parabola
+        through the peak's neighbours; NaN where a node has no texture or no candidate, or scores below min_score.
+        node_u, node_v (and optionally node_score): the caller's Planes, at least nw x nh, which are written and stay on the
+        device; without them the call allocates all three, downloads them and returns arrays.  record: True -- the counts are read
+        back (synchronises) --, a correlation_records Plane of the caller's, or False / None.
+        Returns (u, v, score or None, CorrelationRecord or None)."""
+        own_planes = node_u is None and node_v is None
+        if not own_planes and (node_u is None or node_v is None):
+            raise ValueError("correlate takes both node planes or neither")
+        own_record = record is True
+        if own_record and instances != 1:
+            raise ValueError("a lock-step batch takes the caller's records")
+        nw, nh = correlation_grid(w, h, radius, spacing)
+        held = [self.plane(nw, nh) for _ in range(3)] if own_planes else [node_u, node_v, node_score]
+        rec = self.correlation_records(instances) if own_record else (record or None)
+        try:
+            _check(hip_lib().flow2d_correlate_2d(self.handle, f0.ptr, f1.ptr, w, h, f0.pitch, float(lo), float(scale), int(radius),
+                                                 int(search), int(spacing), float(min_score), held[0].ptr, held[1].ptr,
+                                                 held[2].ptr if held[2] is not None else None, held[0].pitch,
+                                                 rec.ptr if rec is not None else None), "flow2d_correlate_2d")
+            u, v, score = (q.download(nw, nh) for q in held) if own_planes else held
+            return u, v, score, (self.read_correlation_record(rec, 1)[0] if own_record else None)
+        finally:
+            for q in (held if own_planes else []) + ([rec] if own_record else []):
+                q.free()
+                self._planes.remove(q)
+
+    def expand_nodes(self, node_u, node_v, nw, nh, radius, spacing, out_u, out_v, w, h):
+        """A node field brought onto the w x h grid of the frame (flow2d_expand_nodes_2d): bilinear between the surrounding valid
+        nodes, constant beyond the outermost ones, NaN where none of the four is valid."""
+        _check(hip_lib().flow2d_expand_nodes_2d(self.handle, node_u.ptr, node_v.ptr, nw, nh, node_u.pitch, int(radius), int(spacing),
+                                                out_u.ptr, out_v.ptr, w, h, out_u.pitch), "flow2d_expand_nodes_2d")
+
     def resample_x(self, src, dst, out_w, out_h, in_w):
         _check(hip_lib().flow2d_resample_x(self.handle, src.ptr, dst.ptr, out_w, out_h, in_w, src.pitch),
                "flow2d_resample_x")
@@ -1077,6 +1151,11 @@ def host_lib():
             L.flow2d_host_refine_args_ok.argtypes = [i, f, f, i]
             L.flow2d_host_refine_flow.argtypes = [vp, fp, fp, i, f, f, i, i, fp, fp, rr, C.POINTER(HostParams), fp, fp, fp]
             L.flow2d_host_refine_flow_device.argtypes = [vp, vp, vp, i, f, f, i, i, vp, vp, rr, C.POINTER(HostParams), vp, vp, vp, i]
+        if hasattr(L, "flow2d_host_correlate"):
+            cr = C.POINTER(CorrelationRecord)
+            L.flow2d_host_correlation_args_ok.argtypes = [sz, sz, f, f, i, i, i, f]
+            L.flow2d_host_correlate.argtypes = [vp, fp, fp, i, i, i, f, fp, fp, fp, cr, fp, fp, fp]
+            L.flow2d_host_correlate_device.argtypes = [vp, vp, vp, f, f, i, i, i, f, vp, vp, vp, cr, vp, vp]
         if hasattr(L, "flow2d_host_segment_motion"):
             d, u32 = C.c_double, C.c_uint
             head = [i, d, i, i, f, f, u32, C.POINTER(GlobalMotion), C.POINTER(SegmentSummary), C.POINTER(MotionRegion),
@@ -1493,6 +1572,39 @@ class OpticalFlow:
                                                        dev_mask, int(bool(flow_given)))
         if rc:
             raise Flow2DError(rc, "OpticalFlow2D::RefineFlowDevice")
+        return rec
+
+    def correlate(self, frame_0, frame_1, radius=7, search=8, spacing=8, min_score=-1.0, flow=False):
+        """OpticalFlow2D::Correlate: window correlation of the host pair (flow2d_correlate_2d; no part of the variational flow).  The
+        frames are quantised to 8 bits over their common finite range -- as they are when that lies in [0, 255].  Returns (node_u,
+        node_v, node_score, CorrelationRecord, (lo, scale)) on the grid correlation_grid(width, height, radius, spacing); with flow,
+        also the (u, v) of the field expanded to the frame's grid."""
+        f0, f1 = self._pair(frame_0, frame_1)
+        nw, nh = correlation_grid(self.width, self.height, radius, spacing)
+        nodes = [np.empty((nh, nw), np.float32) for _ in range(3)]
+        uv = [np.empty_like(f0) for _ in range(2)] if flow else [None, None]
+        record = CorrelationRecord()
+        lo_scale = (C.c_float * 2)()
+        rc = host_lib().flow2d_host_correlate(self.handle, _fptr(f0), _fptr(f1), int(radius), int(search), int(spacing), float(min_score),
+                                              _fptr(nodes[0]), _fptr(nodes[1]), _fptr(nodes[2]), C.byref(record), _opt_fptr(uv[0]),
+                                              _opt_fptr(uv[1]), lo_scale)
+        if rc:
+            raise Flow2DError(rc, "OpticalFlow2D::Correlate")
+        out = (nodes[0], nodes[1], nodes[2], record, (lo_scale[0], lo_scale[1]))
+        return out + (tuple(uv),) if flow else out
+
+    def correlate_device(self, dev_frame_0, dev_frame_1, lo, scale, radius=7, search=8, spacing=8, min_score=-1.0, dev_nodes=None,
+                         dev_score=None, dev_flow=None, record=True):
+        """OpticalFlow2D::CorrelateDevice: device frames in.  dev_nodes (a (u, v) pair) and dev_score: optional device planes of the
+        container's size whose first nw x nh floats get the node field; dev_flow (a (u, v) pair, optional) gets the field expanded
+        to the frame's grid.  Returns the CorrelationRecord (None without record); synchronises."""
+        rec = CorrelationRecord() if record else None
+        nd, fl = dev_nodes or (None, None), dev_flow or (None, None)
+        rc = host_lib().flow2d_host_correlate_device(self.handle, dev_frame_0, dev_frame_1, float(lo), float(scale), int(radius),
+                                                     int(search), int(spacing), float(min_score), nd[0], nd[1], dev_score,
+                                                     C.byref(rec) if record else None, fl[0], fl[1])
+        if rc:
+            raise Flow2DError(rc, "OpticalFlow2D::CorrelateDevice")
         return rec
 
     def stabilise_sequence(self, frames, params, reference_index=0, model=MOTION_AFFINE, sigma=0.5, iterations=5, masks=False,

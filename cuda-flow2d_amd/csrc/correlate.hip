@@ -1,0 +1,404 @@
+// Window correlation for gfx950: the displacement of a (2r + 1)^2 window of frame 0 found by an exhaustive search of frame 1 for
+// the largest zero-normalised cross-correlation, and the expansion of the node field to the frame's grid.  The body of the
+// reference's Methods::Correlation, which it declares (data_structs.h) and never shipped.
+//
+// The normative definition is the one of flow2d_correlate_2d / flow2d_expand_nodes_2d in flow2d_c_abi.h.  Built
+// -ffp-contract=off.  The frames are quantised to 8 bits while they are staged, so S0, S00, S1, S11 and S01 are exact integers in
+// any order of summation; the score is three double operations on them.
+//
+// flow2d_correlate_2d.  A workgroup of four waves owns a tile of T x T nodes, T = corr_tile_nodes(spacing) = 32 / spacing held to
+// 2 .. 8, and stages in LDS, one byte per pixel, the part of frame 0 its nodes' windows cover (at most 95 x 95) and the part of
+// frame 1 their searches can reach (at most 159 x 159; what lies outside frame 1 is staged as 0 and never scored: a candidate's
+// window lies inside the frame).  34.3 KB of LDS at the limits: four workgroups per CU.  Each wave then takes nodes of the tile in
+// turn, alone -- no barrier after the staging:
+//   1. S0 and S00: the lanes share the window's pixels, one butterfly;
+//   2. the lanes share the (2d + 1)^2 displacements; a lane sums S1, S11 and S01 of its displacement over the window, four
+//      pixels of a row at a time -- per patch the two aligned dwords around them (ds_read2_b32) and a byte funnel shift, then
+//      three v_dot4_u32_u8; lanes of neighbouring dx read the same or neighbouring dwords and the frame-0 pair is a broadcast
+//      --, scores it and keeps its best under the order of the header
+//      (a total order: every lane of the butterfly that follows ends with the same peak);
+//   3. lanes 0 .. 3 score the peak's four neighbours once more (the same integers, so the same doubles) instead of a table of up
+//      to 4225 scores per node in LDS; lane 0 interpolates, writes the node and counts.
+// The counts go to the record by 64-bit integer atomics, one set per wave; the entry zeroes the record on the stream first.
+// This is the direct form: N multiply-adds per candidate and node.  It is the right body for sparse grids (spacing >= radius),
+// where the windows of neighbouring nodes barely overlap; a dense grid would gain from sliding sums of the product image
+// (DESIGN.md 3.13 says what that would take and why it is not here yet).
+//
+// flow2d_expand_nodes_2d: per pixel, the 64 x 4 geometry of plane_sample.hpp, four gathers from each node plane.
+#include <cmath>
+
+#include "ordered_reduce.hpp"
+#include "plane_sample.hpp"
+
+namespace {
+
+constexpr int kCorrThreads = 256, kCorrWaves = 4;
+constexpr int kCorrTileSpan = 32;                  // T = kCorrTileSpan / spacing ...
+constexpr int kCorrTileMin = 2, kCorrTileMax = 8;  // ... held to kCorrTileMin .. kCorrTileMax nodes per axis
+// the farthest two nodes of a tile are (T - 1) * spacing pixels apart: 64 at most (T = 2, spacing 64)
+constexpr int kCorrPatch0 = FLOW2D_CORRELATION_MAX_SPACING + 2 * FLOW2D_CORRELATION_MAX_RADIUS + 1;  // 95
+constexpr int kCorrPatch1 = kCorrPatch0 + 2 * FLOW2D_CORRELATION_MAX_RANGE;                          // 159
+constexpr int kExpandRows = 4;
+
+inline int corr_tile_nodes(int spacing)
+{
+    const int t = kCorrTileSpan / spacing;
+    return t < kCorrTileMin ? kCorrTileMin : t > kCorrTileMax ? kCorrTileMax : t;
+}
+
+struct CorrArgs {
+    const float *f0, *f1;
+    float *nu, *nv, *ns;         // ns: null = absent
+    unsigned long long* record;  // four counts per instance, or null
+    int w, h, pitch;             // the frames; pitch in floats
+    int nw, nh, npitch;          // the node planes
+    int r, d, s, tile;           // tile: nodes per tile axis
+    unsigned tiles_x;
+    float lo, scale, min_score;
+};
+
+__device__ __forceinline__ unsigned quantise(float sample, float lo, float scale)
+{
+    const float t = (sample - lo) * scale;
+    if (!(t > 0.f)) return 0u;
+    if (t >= 255.f) return 255u;
+    return static_cast<unsigned>(static_cast<int>(t + 0.5f));
+}
+
+// whether (c1, dx1, dy1) comes before (c2, dx2, dy2) in the order of the peak
+__device__ __forceinline__ bool comes_first(double c1, int dx1, int dy1, double c2, int dx2, int dy2)
+{
+    if (c1 != c2) return c1 > c2;
+    const int n1 = dx1 * dx1 + dy1 * dy1, n2 = dx2 * dx2 + dy2 * dy2;
+    if (n1 != n2) return n1 < n2;
+    if (dy1 != dy2) return dy1 < dy2;
+    return dx1 < dx2;
+}
+
+// One node's view of the staged patches: q0 at its window's first pixel, q1 at the pixel displacement (0, 0) puts there.
+struct CorrNode {
+    const unsigned char *q0, *q1;
+    int p0w, p1w;      // row lengths of the patches
+    int left, top;     // the window's first pixel in the frame
+    int w, h, side;    // the frame; side = 2r + 1
+    long long n, s0, v0;
+};
+
+// The four bytes at p, which may have any alignment: the two aligned dwords around them (one ds_read2_b32) and a byte funnel
+// shift.  (One dword load at a byte address is legal in LDS and gives the same bytes; measured, the whole kernel is 5.6 times
+// slower with it: 13.3 against 2.4 ms on the PIV grid at 4096^2.)
+__device__ __forceinline__ unsigned four_pixels(const unsigned char* p)
+{
+    const unsigned shift = static_cast<unsigned>(reinterpret_cast<uintptr_t>(p)) & 3u;
+    const unsigned* q = reinterpret_cast<const unsigned*>(p - shift);
+    return __builtin_amdgcn_alignbyte(q[1], q[0], shift);
+}
+
+// The score of displacement (dx, dy); false when it is no candidate.
+__device__ __forceinline__ bool score_at(const CorrNode& nd, int dx, int dy, double& c)
+{
+    const int lx = nd.left + dx, ly = nd.top + dy;
+    if (lx < 0 || ly < 0 || lx + nd.side > nd.w || ly + nd.side > nd.h) return false;
+    const unsigned char* p0 = nd.q0;
+    const unsigned char* p1 = nd.q1 + dy * nd.p1w + dx;
+    unsigned s1 = 0, s11 = 0, s01 = 0;  // at most 961 * 255^2 < 2^26
+    // four pixels of a row at a time: four bytes of each patch (four_pixels) and three packed byte dot products.  A row has an odd
+    // number of pixels: its last one or three come from four bytes of which the others -- the next pixels of the patch, or the
+    // arrays' padding -- are masked off.
+    const int quads = nd.side >> 2;
+    const unsigned tail = (1u << (8 * (nd.side & 3))) - 1u;
+    for (int wy = 0; wy < nd.side; ++wy) {
+        for (int q = 0; q < quads; ++q) {
+            const unsigned a = four_pixels(p0 + 4 * q), b = four_pixels(p1 + 4 * q);
+            s1 = __builtin_amdgcn_udot4(b, 0x01010101u, s1, false);
+            s11 = __builtin_amdgcn_udot4(b, b, s11, false);
+            s01 = __builtin_amdgcn_udot4(a, b, s01, false);
+        }
+        const unsigned a = four_pixels(p0 + 4 * quads) & tail, b = four_pixels(p1 + 4 * quads) & tail;
+        s1 = __builtin_amdgcn_udot4(b, 0x01010101u, s1, false);
+        s11 = __builtin_amdgcn_udot4(b, b, s11, false);
+        s01 = __builtin_amdgcn_udot4(a, b, s01, false);
+        p0 += nd.p0w;
+        p1 += nd.p1w;
+    }
+    const long long l1 = s1;
+    const long long v1 = nd.n * static_cast<long long>(s11) - l1 * l1;
+    if (v1 <= 0) return false;
+    const long long cov = nd.n * static_cast<long long>(s01) - nd.s0 * l1;
+    c = static_cast<double>(cov) / sqrt(static_cast<double>(nd.v0) * static_cast<double>(v1));
+    return true;
+}
+
+template <typename Offset>
+__global__ __launch_bounds__(kCorrThreads) void correlate_kernel(CorrArgs a, BatchArg batch)
+{
+    // (+ 8: the aligned dword pair of the last row's masked bytes may reach seven bytes past the patch)
+    __shared__ __attribute__((aligned(16))) unsigned char s_q0[kCorrPatch0 * kCorrPatch0 + 8];
+    __shared__ __attribute__((aligned(16))) unsigned char s_q1[kCorrPatch1 * kCorrPatch1 + 8];
+
+    const size_t inst = batch_offset(batch);
+    const float* __restrict__ f0 = a.f0 + inst;
+    const float* __restrict__ f1 = a.f1 + inst;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tile_y = blockIdx.x / a.tiles_x, tile_x = blockIdx.x - tile_y * a.tiles_x;
+    const int i_first = tile_x * a.tile, j_first = tile_y * a.tile;
+    const int ni = min(a.tile, a.nw - i_first), nj = min(a.tile, a.nh - j_first);
+    const int side = 2 * a.r + 1, d = a.d, s = a.s;
+    const int p0w = (ni - 1) * s + side, p0h = (nj - 1) * s + side;  // <= kCorrPatch0
+    const int p1w = p0w + 2 * d, p1h = p0h + 2 * d;                  // <= kCorrPatch1
+    const int x0 = i_first * s, y0 = j_first * s;                    // the first pixel of the first node's window
+
+    // frame 0: the windows of existing nodes lie inside the frame
+    for (int i = tid; i < p0w * p0h; i += kCorrThreads) {
+        const int y = i / p0w, x = i - y * p0w;
+        s_q0[i] = static_cast<unsigned char>(quantise(load_at(f0, pixel_offset<Offset>(x0 + x, y0 + y, a.pitch)), a.lo, a.scale));
+    }
+    // frame 1: what lies outside the frame is not loaded, and never scored
+    for (int i = tid; i < p1w * p1h; i += kCorrThreads) {
+        const int y = i / p1w, x = i - y * p1w;
+        const int gx = x0 - d + x, gy = y0 - d + y;
+        unsigned q = 0;
+        if (gx >= 0 && gy >= 0 && gx < a.w && gy < a.h) q = quantise(load_at(f1, pixel_offset<Offset>(gx, gy, a.pitch)), a.lo, a.scale);
+        s_q1[i] = static_cast<unsigned char>(q);
+    }
+    __syncthreads();
+
+    const int reach = 2 * d + 1, candidates = reach * reach, pixels = side * side;
+    const float nan = __uint_as_float(0x7FC00000u);
+    unsigned n_nodes = 0, n_invalid = 0, n_rejected = 0, n_unrefined = 0;  // the same in every lane of a wave
+    for (int node = wave; node < ni * nj; node += kCorrWaves) {
+        const int jn = node / ni, in = node - jn * ni;
+        CorrNode nd;
+        nd.q0 = s_q0 + jn * s * p0w + in * s;
+        nd.q1 = s_q1 + (jn * s + d) * p1w + in * s + d;
+        nd.p0w = p0w;
+        nd.p1w = p1w;
+        nd.left = x0 + in * s;
+        nd.top = y0 + jn * s;
+        nd.w = a.w;
+        nd.h = a.h;
+        nd.side = side;
+        nd.n = pixels;
+
+        unsigned s0 = 0, s00 = 0;
+        for (int k = lane; k < pixels; k += 64) {
+            const int wy = k / side, wx = k - wy * side;
+            const unsigned q = nd.q0[wy * p0w + wx];
+            s0 += q;
+            s00 += q * q;
+        }
+        s0 = wave_sum(s0);
+        s00 = wave_sum(s00);
+        nd.s0 = s0;
+        nd.v0 = nd.n * static_cast<long long>(s00) - nd.s0 * nd.s0;
+
+        double best = -INFINITY;  // no candidate yet
+        int bx = 0, by = 0;
+        if (nd.v0 > 0) {
+            for (int k = lane; k < candidates; k += 64) {
+                const int ky = k / reach, dx = k - ky * reach - d, dy = ky - d;
+                double c;
+                if (score_at(nd, dx, dy, c) && comes_first(c, dx, dy, best, bx, by)) {
+                    best = c;
+                    bx = dx;
+                    by = dy;
+                }
+            }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                const double oc = __shfl_xor(best, o, 64);
+                const int ox = __shfl_xor(bx, o, 64), oy = __shfl_xor(by, o, 64);
+                if (comes_first(oc, ox, oy, best, bx, by)) {
+                    best = oc;
+                    bx = ox;
+                    by = oy;
+                }
+            }
+        }
+        const bool found = best > -INFINITY;  // (a score is finite: V0 > 0 and V1 > 0)
+
+        // the four neighbours of the peak, by lanes 0 .. 3: (-1, 0), (+1, 0), (0, -1), (0, +1)
+        const bool inner = found && abs(bx) < d && abs(by) < d;
+        double cn = 0.0;
+        bool has = false;
+        if (inner && lane < 4) has = score_at(nd, bx + (lane == 0 ? -1 : lane == 1 ? 1 : 0), by + (lane == 2 ? -1 : lane == 3 ? 1 : 0), cn);
+        const bool refined = inner && (__ballot(has) & 0xFull) == 0xFull;
+        const double cxm = __shfl(cn, 0, 64), cxp = __shfl(cn, 1, 64), cym = __shfl(cn, 2, 64), cyp = __shfl(cn, 3, 64);
+
+        float u = nan, v = nan, score = 0.f;
+        bool rejected = false;
+        if (found) {
+            double delta_x = 0.0, delta_y = 0.0;
+            if (refined) {
+                const double den_x = (cxm - 2.0 * best) + cxp, den_y = (cym - 2.0 * best) + cyp;
+                delta_x = den_x < 0.0 ? (cxm - cxp) / (2.0 * den_x) : 0.0;
+                delta_y = den_y < 0.0 ? (cym - cyp) / (2.0 * den_y) : 0.0;
+            }
+            score = static_cast<float>(best);
+            rejected = score < a.min_score;
+            if (!rejected) {
+                u = static_cast<float>(static_cast<double>(bx) + delta_x);
+                v = static_cast<float>(static_cast<double>(by) + delta_y);
+            }
+        }
+        n_nodes += 1;
+        n_invalid += !found;
+        n_rejected += rejected;
+        n_unrefined += found && !rejected && !refined;
+        if (lane == 0) {
+            const size_t at = inst + static_cast<size_t>(j_first + jn) * static_cast<size_t>(a.npitch) + static_cast<size_t>(i_first + in);
+            a.nu[at] = u;
+            a.nv[at] = v;
+            if (a.ns) a.ns[at] = score;
+        }
+    }
+    if (a.record && lane == 0) {
+        unsigned long long* rec = a.record + 4 * static_cast<size_t>(blockIdx.z);
+        const unsigned counts[4] = {n_nodes, n_invalid, n_rejected, n_unrefined};
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (counts[k]) atomicAdd(rec + k, static_cast<unsigned long long>(counts[k]));
+    }
+}
+
+struct ExpandArgs {
+    const float *nu, *nv;
+    float *u_out, *v_out;
+    int nw, nh, npitch;
+    int w, h, pitch;
+    float r, s;
+};
+
+template <typename Offset>
+__global__ __launch_bounds__(flow2d::kPixelBlockX* flow2d::kPixelBlockY) void expand_kernel(ExpandArgs a, BatchArg batch)
+{
+    const size_t inst = batch_offset(batch);
+    const float* __restrict__ nu = a.nu + inst;
+    const float* __restrict__ nv = a.nv + inst;
+    const int x = pixel_column();
+    if (x >= a.w) return;
+    float fx = (static_cast<float>(x) - a.r) / a.s;
+    fx = fminf(fmaxf(fx, 0.f), static_cast<float>(a.nw - 1));
+    const int i0 = static_cast<int>(floorf(fx)), i1 = min(i0 + 1, a.nw - 1);
+    const float ax = fx - static_cast<float>(i0);
+#pragma unroll
+    for (int i = 0; i < kExpandRows; ++i) {
+        const int y = pixel_row(kExpandRows, i);
+        if (y >= a.h) continue;
+        float fy = (static_cast<float>(y) - a.r) / a.s;
+        fy = fminf(fmaxf(fy, 0.f), static_cast<float>(a.nh - 1));
+        const int j0 = static_cast<int>(floorf(fy)), j1 = min(j0 + 1, a.nh - 1);
+        const float ay = fy - static_cast<float>(j0);
+        const float wt[4] = {(1.f - ax) * (1.f - ay), ax * (1.f - ay), (1.f - ax) * ay, ax * ay};
+        const Offset at[4] = {pixel_offset<Offset>(i0, j0, a.npitch), pixel_offset<Offset>(i1, j0, a.npitch),
+                              pixel_offset<Offset>(i0, j1, a.npitch), pixel_offset<Offset>(i1, j1, a.npitch)};
+        float sw = 0.f, su = 0.f, sv = 0.f;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float u = load_at(nu, at[k]), v = load_at(nv, at[k]);
+            if (fabsf(u) < INFINITY && fabsf(v) < INFINITY) {
+                sw += wt[k];
+                su += wt[k] * u;
+                sv += wt[k] * v;
+            }
+        }
+        const float nan = __uint_as_float(0x7FC00000u);
+        const Offset o = pixel_offset<Offset>(x, y, a.pitch);
+        store_at(a.u_out + inst, o, sw > 0.f ? su / sw : nan);
+        store_at(a.v_out + inst, o, sw > 0.f ? sv / sw : nan);
+    }
+}
+
+bool grid_ok(size_t width, size_t height, int radius, int spacing)
+{
+    return radius >= 1 && radius <= FLOW2D_CORRELATION_MAX_RADIUS && spacing >= 1 && spacing <= FLOW2D_CORRELATION_MAX_SPACING &&
+           width >= static_cast<size_t>(2 * radius + 1) && height >= static_cast<size_t>(2 * radius + 1);
+}
+
+}  // namespace
+
+extern "C" {
+
+int flow2d_correlation_grid(size_t width, size_t height, int radius, int spacing, size_t* nw, size_t* nh)
+{
+    if (!nw || !nh || !grid_ok(width, height, radius, spacing)) return FLOW2D_ERR_INVALID_ARGUMENT;
+    *nw = (width - 2 * radius - 1) / spacing + 1;
+    *nh = (height - 2 * radius - 1) / spacing + 1;
+    return FLOW2D_OK;
+}
+
+int flow2d_correlate_2d(flow2d_context* ctx, const float* frame_0, const float* frame_1, size_t width, size_t height,
+                        size_t pitch_bytes, float lo, float scale, int radius, int range, int spacing, float min_score, float* node_u,
+                        float* node_v, float* node_score, size_t node_pitch_bytes, flow2d_correlation_record* record)
+{
+    if (ctx == nullptr) return FLOW2D_ERR_INVALID_ARGUMENT;
+    // (every check that needs no context field comes first: they hold without a device)
+    if (!flow2d::plane_args_ok(frame_0, width, height, pitch_bytes) || !flow2d::plane_args_ok(frame_1, width, height, pitch_bytes))
+        return FLOW2D_ERR_INVALID_ARGUMENT;
+    if (!grid_ok(width, height, radius, spacing) || range < 1 || range > FLOW2D_CORRELATION_MAX_RANGE)
+        return FLOW2D_ERR_INVALID_ARGUMENT;
+    if (!(std::isfinite(scale) && scale > 0.f) || !std::isfinite(lo) || std::isnan(min_score)) return FLOW2D_ERR_INVALID_ARGUMENT;
+    const size_t nw = (width - 2 * radius - 1) / spacing + 1, nh = (height - 2 * radius - 1) / spacing + 1;
+    if (!flow2d::plane_args_ok(node_u, nw, nh, node_pitch_bytes) || !flow2d::plane_args_ok(node_v, nw, nh, node_pitch_bytes) ||
+        (node_score && !flow2d::plane_args_ok(node_score, nw, nh, node_pitch_bytes)))
+        return FLOW2D_ERR_INVALID_ARGUMENT;
+    if ((reinterpret_cast<uintptr_t>(record) % alignof(flow2d_correlation_record)) != 0) return FLOW2D_ERR_INVALID_ARGUMENT;
+    // the kernel marks the frames __restrict__: no written byte range may meet a frame or another written one
+    auto aliased = [&](size_t frame_span, size_t node_span, size_t instances) {
+        const flow2d::ByteRange written[] = {{node_u, node_span}, {node_v, node_span}, {node_score, node_span},
+                                             {record, instances * sizeof(flow2d_correlation_record)}};
+        const flow2d::ByteRange read[] = {{frame_0, frame_span}, {frame_1, frame_span}};
+        return flow2d::any_overlap(written, read);
+    };
+    if (aliased(height * pitch_bytes, nh * node_pitch_bytes, 1)) return FLOW2D_ERR_INVALID_ARGUMENT;
+    FLOW2D_ENTER(ctx);
+    const size_t instances = ctx->batch_count;
+    if (aliased(flow2d::batch_span(ctx, height * pitch_bytes), flow2d::batch_span(ctx, nh * node_pitch_bytes), instances))
+        return FLOW2D_ERR_INVALID_ARGUMENT;
+    if (record) FLOW2D_HIP_TRY(hipMemsetAsync(record, 0, instances * sizeof(flow2d_correlation_record), ctx->stream));
+    const int tile = corr_tile_nodes(spacing);
+    const unsigned tiles_x = flow2d::div_up(nw, tile), tiles_y = flow2d::div_up(nh, tile);
+    const CorrArgs a = {frame_0, frame_1, node_u, node_v, node_score, reinterpret_cast<unsigned long long*>(record),
+                        static_cast<int>(width), static_cast<int>(height), static_cast<int>(pitch_bytes / 4),
+                        static_cast<int>(nw), static_cast<int>(nh), static_cast<int>(node_pitch_bytes / 4),
+                        radius, range, spacing, tile, tiles_x, lo, scale, min_score};
+    // (the largest offset a lane forms into a frame is below height * pitch_bytes; the node planes are addressed in 64 bits)
+    flow2d::launch_by_span(height * pitch_bytes, [&](auto offset) {
+        correlate_kernel<decltype(offset)>
+            <<<dim3(tiles_x * tiles_y, 1, flow2d::batch_z(ctx, 1)), dim3(kCorrThreads), 0, ctx->stream>>>(a, flow2d::batch_arg(ctx, 1));
+    });
+    FLOW2D_CHECK_LAUNCH();
+    return FLOW2D_OK;
+}
+
+int flow2d_expand_nodes_2d(flow2d_context* ctx, const float* node_u, const float* node_v, size_t nw, size_t nh, size_t node_pitch_bytes,
+                           int radius, int spacing, float* out_u, float* out_v, size_t width, size_t height, size_t pitch_bytes)
+{
+    if (ctx == nullptr) return FLOW2D_ERR_INVALID_ARGUMENT;
+    if (!flow2d::plane_args_ok(node_u, nw, nh, node_pitch_bytes) || !flow2d::plane_args_ok(node_v, nw, nh, node_pitch_bytes) ||
+        !flow2d::plane_args_ok(out_u, width, height, pitch_bytes) || !flow2d::plane_args_ok(out_v, width, height, pitch_bytes))
+        return FLOW2D_ERR_INVALID_ARGUMENT;
+    if (radius < 0 || radius > FLOW2D_CORRELATION_MAX_RADIUS || spacing < 1 || spacing > FLOW2D_CORRELATION_MAX_SPACING)
+        return FLOW2D_ERR_INVALID_ARGUMENT;
+    auto aliased = [&](size_t span, size_t node_span) {
+        const flow2d::ByteRange written[] = {{out_u, span}, {out_v, span}};
+        const flow2d::ByteRange read[] = {{node_u, node_span}, {node_v, node_span}};
+        return flow2d::any_overlap(written, read);
+    };
+    if (aliased(height * pitch_bytes, nh * node_pitch_bytes)) return FLOW2D_ERR_INVALID_ARGUMENT;
+    FLOW2D_ENTER(ctx);
+    if (aliased(flow2d::batch_span(ctx, height * pitch_bytes), flow2d::batch_span(ctx, nh * node_pitch_bytes)))
+        return FLOW2D_ERR_INVALID_ARGUMENT;
+    const ExpandArgs a = {node_u, node_v, out_u, out_v, static_cast<int>(nw), static_cast<int>(nh),
+                          static_cast<int>(node_pitch_bytes / 4), static_cast<int>(width), static_cast<int>(height),
+                          static_cast<int>(pitch_bytes / 4), static_cast<float>(radius), static_cast<float>(spacing)};
+    const size_t span = height * pitch_bytes > nh * node_pitch_bytes ? height * pitch_bytes : nh * node_pitch_bytes;
+    flow2d::launch_by_span(span, [&](auto offset) {
+        expand_kernel<decltype(offset)><<<flow2d::pixel_grid(ctx, width, height, kExpandRows), flow2d::pixel_block(), 0, ctx->stream>>>(
+            a, flow2d::batch_arg(ctx, 1));
+    });
+    FLOW2D_CHECK_LAUNCH();
+    return FLOW2D_OK;
+}
+
+}  // extern "C"

@@ -547,6 +547,61 @@ HOST_API int flow2d_host_refine_flow_device(flow2d_host_flow* h, void* dev_frame
                : 2;
 }
 
+// OpticalFlow2D::CorrelationArgsOk: 1 when the arguments are what Correlate* accepts for a width x height frame.  Needs no device.
+HOST_API int flow2d_host_correlation_args_ok(size_t width, size_t height, float lo, float scale, int radius, int range, int spacing,
+                                             float min_score)
+{
+    return OpticalFlow2D::CorrelationArgsOk(width, height, lo, scale, radius, range, spacing, min_score) ? 1 : 0;
+}
+
+// OpticalFlow2D::Correlate on tight host images: node_u / node_v / node_score (optional) get nw * nh floats each (the grid of
+// flow2d_correlation_grid), record (optional) the counts, flow_u / flow_v (optional, both or neither) the field on the frame's
+// grid, lo_scale (optional) the two numbers of OpticalFlow2D::CorrelationRange the frames were quantised with.  0 on success, 1 for
+// a null or refused argument, 2 when the run delivered nothing.
+HOST_API int flow2d_host_correlate(flow2d_host_flow* h, const float* frame_0, const float* frame_1, int radius, int range, int spacing,
+                                   float min_score, float* node_u, float* node_v, float* node_score, flow2d_correlation_record* record,
+                                   float* flow_u, float* flow_v, float* lo_scale)
+{
+    size_t nw = 0, nh = 0;
+    if (!h || !frame_0 || !frame_1 || !node_u || !node_v || (flow_u == nullptr) != (flow_v == nullptr) ||
+        flow2d_correlation_grid(h->width, h->height, radius, spacing, &nw, &nh) != FLOW2D_OK)
+        return 1;
+    HostImages im(h);
+    Data2D *f0 = im.In(frame_0), *f1 = im.In(frame_1);
+    Data2D *fu = im.Out(flow_u, im.AfterSuccess), *fv = im.Out(flow_v, im.AfterSuccess);
+    float lo = 0.f, scale = 1.f;
+    OpticalFlow2D::CorrelationRange(*f0, *f1, lo, scale);
+    if (!OpticalFlow2D::CorrelationArgsOk(h->width, h->height, lo, scale, radius, range, spacing, min_score)) return 1;
+    Data2D nodes[3] = {Data2D(nw, nh), Data2D(nw, nh), Data2D(nw, nh)};
+    h->flow.Correlate(*f0, *f1, radius, range, spacing, min_score, nodes[0], nodes[1], node_score ? &nodes[2] : nullptr, record, fu, fv);
+    const int rc = im.Finish(h->flow);
+    if (rc) return rc;
+    float* dst[3] = {node_u, node_v, node_score};
+    for (int k = 0; k < 3; ++k)
+        if (dst[k]) std::memcpy(dst[k], nodes[k].DataPtr(), nw * nh * sizeof(float));
+    if (lo_scale) {
+        lo_scale[0] = lo;
+        lo_scale[1] = scale;
+    }
+    return 0;
+}
+
+// OpticalFlow2D::CorrelateDevice: device planes of the container's size (the node planes optional).  Synchronises.  0 on success, 1
+// for a null or refused argument, 2 when the run failed.
+HOST_API int flow2d_host_correlate_device(flow2d_host_flow* h, void* dev_frame_0, void* dev_frame_1, float lo, float scale, int radius,
+                                          int range, int spacing, float min_score, void* dev_node_u, void* dev_node_v,
+                                          void* dev_node_score, flow2d_correlation_record* record, void* dev_flow_u, void* dev_flow_v)
+{
+    if (!h || !dev_frame_0 || !dev_frame_1 || (dev_flow_u == nullptr) != (dev_flow_v == nullptr) ||
+        !OpticalFlow2D::CorrelationArgsOk(h->width, h->height, lo, scale, radius, range, spacing, min_score))
+        return 1;
+    h->flow.timing_mode = 0;
+    return h->flow.CorrelateDevice(dp(dev_frame_0), dp(dev_frame_1), lo, scale, radius, range, spacing, min_score, dp(dev_node_u),
+                                   dp(dev_node_v), dp(dev_node_score), record, dp(dev_flow_u), dp(dev_flow_v))
+               ? 0
+               : 2;
+}
+
 // OpticalFlow2D::StabiliseSequence on tight host images: frames = frame_count * width * height floats (frame k at k * width *
 // height); outputs get the same layout, motions (optional) frame_count records.  0 on success, 1 for a null or refused argument,
 // 2 when the run delivered no frames.

@@ -58,6 +58,15 @@
 // "Refinement: {json}" -- "radius", "sigma", "space", "iterations" and the last pass's "pixels", "unfilled", "filled", "changed" --
 // is printed.  With --ground-truth the line "Flow error: {json}" scores the refined flow and a second line "Flow error before
 // refinement: {json}" the flow as computed.  The other files do not change; a run of its own.  Without --refine nothing changes.
+// --correlation R (a window radius of 1 .. 15) [--correlation-range D, 1 .. 32, default 8] [--correlation-spacing S, 1 .. 64,
+// default 8] [--correlation-min-score C, a number, default -1: off] selects Methods::Correlation instead of the variational flow
+// (OpticalFlow2D::Correlate: flow2d_correlate_2d on the frames quantised to 8 bits over their common range, as they are when that
+// lies in [0, 255]): the forward files -- flow-u, flow-v, res.pgm, amp, flow.flo -- hold the node field expanded to the frame's
+// grid (NaN where no surrounding node is valid), node-u, node-v and node-score (F32, nw x nh, the sizes in the names) the nodes,
+// and one line "Correlation: {json}" -- "radius", "range", "spacing", "min_score", "lo", "scale", "nw", "nh" and the record's
+// "nodes", "invalid", "rejected", "unrefined" -- is printed.  With --ground-truth the line "Flow error: {json}" scores the expanded
+// field.  It does not combine with the options that run the variational flow (--backward, --interpolate, --track, --denoise,
+// --global-motion, --segment-motion, --deformation, --refine).  Without --correlation nothing changes.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -110,6 +119,9 @@ int main(int argc, char** argv)
     int refine_radius = 0;  // --refine R (0: off)
     float refine_sigma = 25.f, refine_space = 0.f;
     int refine_iterations = 1;
+    Methods method = Methods::OpticalFlow;  // --correlation R: Methods::Correlation
+    int correlation_radius = 0, correlation_range = 8, correlation_spacing = 8;
+    float correlation_min_score = -1.f;
     std::string ground_truth_file;
     int device = 0;
     float sor_omega = 0.f;
@@ -255,6 +267,30 @@ int main(int argc, char** argv)
             (guide ? refine_sigma : refine_space) = value;
             ++i;
         }
+        else if (!std::strcmp(argv[i], "--correlation") || !std::strcmp(argv[i], "--correlation-range") ||
+                 !std::strcmp(argv[i], "--correlation-spacing")) {
+            const int which = !std::strcmp(argv[i], "--correlation") ? 0 : !std::strcmp(argv[i], "--correlation-range") ? 1 : 2;
+            const int limit[3] = {FLOW2D_CORRELATION_MAX_RADIUS, FLOW2D_CORRELATION_MAX_RANGE, FLOW2D_CORRELATION_MAX_SPACING};
+            char* end = nullptr;
+            const long n = (i + 1 < argc) ? std::strtol(argv[i + 1], &end, 10) : 0;
+            if (i + 1 >= argc || end == argv[i + 1] || *end != '\0' || n < 1 || n > limit[which]) {
+                std::printf("%s takes an integer of 1 .. %d.\n", argv[i], limit[which]);
+                return 5;
+            }
+            (which == 0 ? correlation_radius : which == 1 ? correlation_range : correlation_spacing) = static_cast<int>(n);
+            if (which == 0) method = Methods::Correlation;
+            ++i;
+        }
+        else if (!std::strcmp(argv[i], "--correlation-min-score")) {
+            char* end = nullptr;
+            const float value = (i + 1 < argc) ? std::strtof(argv[i + 1], &end) : 0.f;
+            if (i + 1 >= argc || end == argv[i + 1] || *end != '\0' || std::isnan(value)) {
+                std::printf("--correlation-min-score takes a number (a score is -1 .. 1; -1: nothing is rejected).\n");
+                return 5;
+            }
+            correlation_min_score = value;
+            ++i;
+        }
         else if (!std::strcmp(argv[i], "--device") && i + 1 < argc) device = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--sor") && i + 1 < argc) sor_omega = static_cast<float>(std::atof(argv[++i]));
         else args.push_back(argv[i]);
@@ -262,6 +298,12 @@ int main(int argc, char** argv)
     const int nargs = static_cast<int>(args.size());
     if (segment && global_model < 0) {
         std::printf("--segment-motion needs --global-motion MODEL (the regions are those of the residual flow).\n");
+        return 5;
+    }
+
+    if (method == Methods::Correlation &&
+        (backward || interpolate || track_spacing || denoise || global_model >= 0 || segment || deformation || refine_radius)) {
+        std::printf("--correlation replaces the variational flow and does not combine with the options that run it.\n");
         return 5;
     }
 
@@ -385,7 +427,36 @@ int main(int argc, char** argv)
             occlusion_0 = Data2D(width, height);
             occlusion_1 = Data2D(width, height);
         }
-        if (interpolate) {
+        Data2D node_u, node_v, node_score;
+        if (method == Methods::Correlation) {
+            size_t nw = 0, nh = 0;
+            if (flow2d_correlation_grid(width, height, correlation_radius, correlation_spacing, &nw, &nh) != FLOW2D_OK) {
+                std::printf("Error: a %zu x %zu frame is smaller than one correlation window of radius %d.\n", width, height,
+                            correlation_radius);
+                optical_flow.Destroy();
+                DestroyDeviceContext();
+                return 4;
+            }
+            node_u = Data2D(nw, nh);
+            node_v = Data2D(nw, nh);
+            node_score = Data2D(nw, nh);
+            flow2d_correlation_record record = {0, 0, 0, 0};
+            float lo = 0.f, scale = 1.f;
+            OpticalFlow2D::CorrelationRange(frame_0, frame_1, lo, scale);
+            optical_flow.Correlate(frame_0, frame_1, correlation_radius, correlation_range, correlation_spacing, correlation_min_score,
+                                   node_u, node_v, &node_score, &record, &flow_u, &flow_v);
+            if (optical_flow.LastRunSucceeded()) {
+                const std::string nodes = "-" + std::to_string(nw) + "-" + std::to_string(nh) + ".raw";
+                node_u.WriteRAWToFileF32((output_path + counter + "node-u" + nodes).c_str());
+                node_v.WriteRAWToFileF32((output_path + counter + "node-v" + nodes).c_str());
+                node_score.WriteRAWToFileF32((output_path + counter + "node-score" + nodes).c_str());
+                std::printf("Correlation: {\"radius\": %d, \"range\": %d, \"spacing\": %d, \"min_score\": %.9g, \"lo\": %.9g, "
+                            "\"scale\": %.9g, \"nw\": %zu, \"nh\": %zu, \"nodes\": %llu, \"invalid\": %llu, \"rejected\": %llu, "
+                            "\"unrefined\": %llu}\n",
+                            correlation_radius, correlation_range, correlation_spacing, correlation_min_score, lo, scale, nw, nh,
+                            record.nodes, record.invalid, record.rejected, record.unrefined);
+            }
+        } else if (interpolate) {
             optical_flow.InterpolateFrames(frame_0, frame_1, times.data(), times.size(), between.data(), 2, 0.5f, true, params,
                                            &flow_u, &flow_v, &back_u, &back_v, &occlusion_0, &occlusion_1);
         } else if (backward) {

@@ -269,6 +269,29 @@ public:
                     bool use_masks, Data2D& refined_u, Data2D& refined_v, flow2d_refine_record* record_out,
                     OperationParameters& params, Data2D* flow_u = nullptr, Data2D* flow_v = nullptr, Data2D* mask = nullptr);
 
+    // Window correlation (the reference's Methods::Correlation, which it declares and never shipped): flow2d_correlate_2d on the
+    // pair -- both frames quantised to 8 bits by (I - lo) * scale; every node of the grid of flow2d_correlation_grid gets the
+    // displacement, within `range`, at which its (2 radius + 1)^2 window of frame 0 correlates best with frame 1 --, no part of the
+    // variational pyramid.  dev_node_u / dev_node_v / dev_node_score (each optional) are planes of the CONTAINER's size and pitch
+    // whose first nw x nh floats get the node field; without them planes of the object's own are used.  record_out (host,
+    // optional) gets the counts.  dev_flow_u / dev_flow_v (optional, both or neither) get the field on the frame's grid
+    // (flow2d_expand_nodes_2d), ready for every consumer of a dense flow.  CorrelationArgsOk prints what is wrong and needs no
+    // device.  The object's own planes and record are allocated at the first call and kept.  The call synchronises.  Not for
+    // lock-step groups.
+    static bool CorrelationArgsOk(size_t width, size_t height, float lo, float scale, int radius, int range, int spacing,
+                                  float min_score);
+    bool CorrelateDevice(DevicePtr dev_frame_0, DevicePtr dev_frame_1, float lo, float scale, int radius, int range, int spacing,
+                         float min_score, DevicePtr dev_node_u, DevicePtr dev_node_v, DevicePtr dev_node_score,
+                         flow2d_correlation_record* record_out, DevicePtr dev_flow_u = 0, DevicePtr dev_flow_v = 0);
+    // lo and scale as Correlate chooses them, from the finite minimum and maximum of the two images: 0 and 1 when they lie in
+    // [0, 255] already (8-bit data is taken as it is), else the range onto 0 .. 255.  Needs no device.
+    static void CorrelationRange(Data2D& frame_0, Data2D& frame_1, float& lo, float& scale);
+    // The host-image form (the CLI's --correlation): node_u / node_v (and node_score, optional) are nw x nh images.
+    // LastRunSucceeded and LastTotalMs as for ComputeFlow.
+    void Correlate(Data2D& frame_0, Data2D& frame_1, int radius, int range, int spacing, float min_score, Data2D& node_u,
+                   Data2D& node_v, Data2D* node_score, flow2d_correlation_record* record_out, Data2D* flow_u = nullptr,
+                   Data2D* flow_v = nullptr);
+
     // When set, ComputeFlowDevice records the whole pyramid of a pair into a HIP graph the first time it
     // sees a (buffers, parameters) combination and replays it afterwards: one host call instead of
     // several hundred launches.  Ignored while timing_mode != 0 (events are not captured).
@@ -443,6 +466,9 @@ private:
     // only), the two ping-pong pairs of the passes before the last (from the second and the third iteration on) and the record
     OwnedPlanes refine_planes_{owned_, 10};
     DeviceScratch refine_scratch_{owned_};
+    // Correlate*: the node planes the caller did not give (u, v) and the record
+    OwnedPlanes correlation_planes_{owned_, 2};
+    DeviceScratch correlation_scratch_{owned_};
     flow2d_context* context_ = nullptr;
     // One plane beside the pool: the warped frame of a level, when the levels of both frames are computed up front into plane
     // regions of their own (RunPyramid: "stacked" levels) and therefore cannot be overwritten by the warp

@@ -1,5 +1,6 @@
 // The applications built on the flow: frame interpolation, point trajectories, global motion and stabilisation, motion
-// segmentation, deformation analysis, flow refinement and temporal denoising.  Each has a ...Device entry on planes that already sit on the device
+// segmentation, deformation analysis, flow refinement and temporal denoising, and window correlation, which stands beside it.  Each has a
+// ...Device entry on planes that already sit on the device
 // and a host-image entry that uploads, calls it and downloads (CallPlanes + HostCall, host_entry.h).  The flow itself -- the
 // pyramid, the sequence cache, ComputeFlow* -- is optical_flow_2d.cpp.
 #include <algorithm>
@@ -519,6 +520,108 @@ void OpticalFlow2D::RefineFlow(Data2D& frame_0, Data2D& frame_1, int radius, flo
                    RefineFlowDevice(d[0], d[1], radius, sigma_guide, sigma_space, iterations, use_masks, d[2], d[3], record_out, params,
                                     d[4], d[5], d[6]) &&
                    planes.Download();
+}
+
+bool OpticalFlow2D::CorrelationArgsOk(size_t width, size_t height, float lo, float scale, int radius, int range, int spacing,
+                                      float min_score)
+{
+    size_t nw = 0, nh = 0;
+    if (radius < 1 || radius > FLOW2D_CORRELATION_MAX_RADIUS || range < 1 || range > FLOW2D_CORRELATION_MAX_RANGE || spacing < 1 ||
+        spacing > FLOW2D_CORRELATION_MAX_SPACING || !(std::isfinite(scale) && scale > 0.f) || !std::isfinite(lo) || std::isnan(min_score)) {
+        std::printf("Error: window correlation takes a radius of 1 .. %d (%d), a range of 1 .. %d (%d), a spacing of 1 .. %d (%d), a "
+                    "finite lo (%g), a finite scale > 0 (%g) and a minimum score that is a number (%g).\n",
+                    FLOW2D_CORRELATION_MAX_RADIUS, radius, FLOW2D_CORRELATION_MAX_RANGE, range, FLOW2D_CORRELATION_MAX_SPACING, spacing,
+                    lo, scale, min_score);
+        return false;
+    }
+    if (flow2d_correlation_grid(width, height, radius, spacing, &nw, &nh) != FLOW2D_OK) {
+        std::printf("Error: a %zu x %zu frame is smaller than one correlation window of radius %d.\n", width, height, radius);
+        return false;
+    }
+    return true;
+}
+
+bool OpticalFlow2D::CorrelateDevice(DevicePtr dev_frame_0, DevicePtr dev_frame_1, float lo, float scale, int radius, int range,
+                                    int spacing, float min_score, DevicePtr dev_node_u, DevicePtr dev_node_v, DevicePtr dev_node_score,
+                                    flow2d_correlation_record* record_out, DevicePtr dev_flow_u, DevicePtr dev_flow_v)
+{
+    const size_t W = dev_container_size_.width, H = dev_container_size_.height, pitch = dev_container_size_.pitch;
+    if (!CorrelationArgsOk(W, H, lo, scale, radius, range, spacing, min_score)) return false;
+    if (!IsInitialized() || !dev_frame_0 || !dev_frame_1 || (dev_flow_u == 0) != (dev_flow_v == 0)) return false;
+    if (RefuseGroup("window correlation")) return false;
+    DevicePtr* own = correlation_planes_.begin();
+    DevicePtr node[2] = {dev_node_u, dev_node_v};
+    for (int k = 0; k < 2; ++k) {
+        if (node[k]) continue;
+        if (!EnsurePlanes(own + k, 1)) return false;
+        node[k] = own[k];
+    }
+    if (record_out && !correlation_scratch_.Ensure(context_, sizeof(flow2d_correlation_record))) return false;
+    flow2d_correlation_record* record = record_out ? correlation_scratch_.At<flow2d_correlation_record>() : nullptr;
+    size_t nw = 0, nh = 0;
+    flow2d_correlation_grid(W, H, radius, spacing, &nw, &nh);
+    // (the node planes are containers: the frames' pitch)
+    bool ok = !CheckFlow2DError(flow2d_correlate_2d(context_, AsPlane(dev_frame_0), AsPlane(dev_frame_1), W, H, pitch, lo, scale, radius,
+                                                    range, spacing, min_score, AsPlane(node[0]), AsPlane(node[1]),
+                                                    dev_node_score ? AsPlane(dev_node_score) : nullptr, pitch, record),
+                                "flow2d_correlate_2d");
+    if (ok && dev_flow_u)
+        ok = !CheckFlow2DError(flow2d_expand_nodes_2d(context_, AsPlane(node[0]), AsPlane(node[1]), nw, nh, pitch, radius, spacing,
+                                                      AsPlane(dev_flow_u), AsPlane(dev_flow_v), W, H, pitch),
+                               "flow2d_expand_nodes_2d");
+    ok = ok && (!record_out || ReadRecord(record_out, record, sizeof(*record_out)));
+    return !CheckFlow2DError(flow2d_synchronize(context_), "flow2d_synchronize") && ok;
+}
+
+void OpticalFlow2D::CorrelationRange(Data2D& frame_0, Data2D& frame_1, float& lo, float& scale)
+{
+    float low = INFINITY, high = -INFINITY;
+    for (Data2D* image : {&frame_0, &frame_1}) {
+        const float* p = image->DataPtr();
+        const size_t n = image->Width() * image->Height();
+        for (size_t i = 0; i < n; ++i) {
+            if (!std::isfinite(p[i])) continue;
+            low = std::min(low, p[i]);
+            high = std::max(high, p[i]);
+        }
+    }
+    lo = 0.f;
+    scale = 1.f;
+    if (!(low <= high) || (low >= 0.f && high <= 255.f) || !(high - low > 0.f)) return;  // nothing finite, 8-bit data, or flat
+    lo = low;
+    scale = 255.f / (high - low);
+}
+
+void OpticalFlow2D::Correlate(Data2D& frame_0, Data2D& frame_1, int radius, int range, int spacing, float min_score, Data2D& node_u,
+                              Data2D& node_v, Data2D* node_score, flow2d_correlation_record* record_out, Data2D* flow_u, Data2D* flow_v)
+{
+    last_run_ok_ = false;
+    if (!IsInitialized() || (flow_u == nullptr) != (flow_v == nullptr)) return;
+    CallPlanes planes(context_, dev_container_size_, GetName(), "frame / flow");
+    planes.Add(&frame_0, CallPlanes::In).Add(&frame_1, CallPlanes::In).Add(flow_u, CallPlanes::Out).Add(flow_v, CallPlanes::Out);
+    // the node planes: containers with no image of their size behind them, downloaded below
+    planes.Add(nullptr, CallPlanes::Out, true).Add(nullptr, CallPlanes::Out, true).Add(nullptr, CallPlanes::Out, node_score != nullptr);
+    if (!planes.SizesMatch()) return;
+    float lo = 0.f, scale = 1.f;
+    CorrelationRange(frame_0, frame_1, lo, scale);
+    const size_t W = dev_container_size_.width, H = dev_container_size_.height;
+    if (!CorrelationArgsOk(W, H, lo, scale, radius, range, spacing, min_score)) return;
+    size_t nw = 0, nh = 0;
+    flow2d_correlation_grid(W, H, radius, spacing, &nw, &nh);
+    Data2D* nodes[3] = {&node_u, &node_v, node_score};
+    for (Data2D* image : nodes)
+        if (image && (image->Width() != nw || image->Height() != nh)) {
+            std::printf("Error: '%s': the node images are not %zu x %zu.\n", GetName(), nw, nh);
+            return;
+        }
+    HostCall call(context_, last_total_ms_, planes.Allocate());
+    const DevicePtr* d = planes.data();
+    bool ok = planes.Upload() &&
+              CorrelateDevice(d[0], d[1], lo, scale, radius, range, spacing, min_score, d[4], d[5], d[6], record_out, d[2], d[3]) &&
+              planes.Download();
+    for (int k = 0; ok && k < 3; ++k)
+        if (nodes[k]) ok = CopyData2DFromDevice(d[4 + k], *nodes[k], H, dev_container_size_.pitch);
+    last_run_ok_ = ok;
 }
 
 bool OpticalFlow2D::StabiliseSequenceDevice(const DevicePtr* dev_frames, size_t frame_count, size_t reference_index, int model,

@@ -29,6 +29,10 @@ inside the frame; two_layer: a background point is hidden while the square cover
 the frame).  For temporal denoising (flow2d_denoise_2d) the same between any two frames, backwards too:
 trajectory_between(x, y, start, k), visible_between(x, y, start, k) and flow_between(start, k) -> (u, v, visible) on frame
 `start`'s grid.
+Speckle scenes (make_speckle_scene(motion, width, height, seed), motion one of SPECKLE_MOTIONS), for window correlation
+(flow2d_correlate_2d): the affine scenes' machinery on a Speckle texture, a seeded sum of Gaussian blobs as sprayed on a specimen
+for digital image correlation -- fine, aperiodic detail in every window, which the long sinusoids of Texture do not have.  They
+are NOT in SCENES: the tables and tests that iterate over that tuple are about the variational flow.
 Pure numpy: no device, no library.
 """
 import numpy as np
@@ -50,6 +54,57 @@ class Texture:
         for a, kx, ky, phase in self.terms:
             out += a * np.sin(kx * x + ky * y + phase)
         return out
+
+
+SPECKLE_MOTIONS = ("translation", "affine", "large_translation")
+
+
+class Speckle:
+    """A dark ground plus one Gaussian blob per cell of a `pitch`-pixel grid, on the whole plane: the blob of cell (i, j) has its
+    centre at a seeded position inside the cell and a seeded amplitude, both drawn from a hash of (i, j, seed), so nothing is
+    stored and any real coordinate can be sampled.  A sample sums the blobs of the (2 * reach + 1)^2 cells around its own: the
+    nearest blob left out is reach * pitch = 12 pixels = 8 sigma away, below 1e-11 grey levels."""
+
+    def __init__(self, seed, pitch=4.0, sigma=1.5, ground=20.0, amplitude=(20.0, 110.0), reach=3):
+        self.seed, self.pitch, self.sigma, self.ground, self.amplitude, self.reach = int(seed), pitch, sigma, ground, amplitude, reach
+
+    def _uniform(self, i, j, stream):
+        """[0, 1) from the cell and the stream number: the splitmix64 finaliser of a linear combination (wrapping uint64)."""
+        with np.errstate(over="ignore"):
+            z = (i.astype(np.int64).astype(np.uint64) * np.uint64(0x9E3779B97F4A7C15) +
+                 j.astype(np.int64).astype(np.uint64) * np.uint64(0xC2B2AE3D27D4EB4F) +
+                 np.uint64((self.seed * 3 + stream) * 0x165667B19E3779F9 % 2 ** 64))
+            z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+            z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+            z = z ^ (z >> np.uint64(31))
+        return (z >> np.uint64(11)).astype(np.float64) * 2.0 ** -53
+
+    def __call__(self, x, y):
+        x, y = np.broadcast_arrays(np.asarray(x, np.float64), np.asarray(y, np.float64))
+        ci, cj = np.floor(x / self.pitch), np.floor(y / self.pitch)
+        out = np.full(x.shape, self.ground)
+        lo, hi = self.amplitude
+        for dj in range(-self.reach, self.reach + 1):
+            for di in range(-self.reach, self.reach + 1):
+                i, j = ci + di, cj + dj
+                bx = (i + self._uniform(i, j, 0)) * self.pitch
+                by = (j + self._uniform(i, j, 1)) * self.pitch
+                amp = lo + (hi - lo) * self._uniform(i, j, 2)
+                out += amp * np.exp(-((x - bx) ** 2 + (y - by) ** 2) / (2.0 * self.sigma ** 2))
+        return out
+
+
+def make_speckle_scene(motion, width=96, height=80, seed=0):
+    """A speckle pattern under `motion` (one of SPECKLE_MOTIONS): the translation and the affine motion of make_scene, and a
+    translation by (11.25, -7.5) -- almost three blob spacings, and more than a coarse-to-fine solver's finest levels reach."""
+    texture = Speckle(seed)
+    if motion == "translation":
+        return _affine_scene("speckle_translation", width, height, texture, np.eye(2), (2.3, -1.4))
+    if motion == "affine":
+        return _affine_scene("speckle_affine", width, height, texture, [[1.02, 0.03], [-0.02, 0.985]], (1.25, -0.6))
+    if motion == "large_translation":
+        return _affine_scene("speckle_large_translation", width, height, texture, np.eye(2), (11.25, -7.5))
+    raise ValueError("unknown speckle motion %r (one of %s)" % (motion, ", ".join(SPECKLE_MOTIONS)))
 
 
 class Scene:

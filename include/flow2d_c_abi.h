@@ -40,7 +40,8 @@ extern "C" {
  * (motion-compensated temporal denoising) and flow2d_global_motion_2d / flow2d_global_motion_workspace_bytes /
  * flow2d_global_flow_2d / flow2d_warp_global_2d (robust global motion and stabilisation), flow2d_segment_motion_2d /
  * flow2d_segment_motion_workspace_bytes (motion segmentation), flow2d_deformation_2d / flow2d_deformation_workspace_bytes
- * (strain, divergence and vorticity of a flow) and flow2d_refine_flow_2d (edge-aware refinement of a flow) were added under 1. */
+ * (strain, divergence and vorticity of a flow), flow2d_refine_flow_2d (edge-aware refinement of a flow) and flow2d_correlate_2d /
+ * flow2d_correlation_grid / flow2d_expand_nodes_2d (window correlation) were added under 1. */
 #define FLOW2D_ABI_VERSION 1
 
 typedef enum flow2d_status {
@@ -771,6 +772,92 @@ FLOW2D_API int flow2d_refine_flow_2d(flow2d_context* ctx, const float* flow_u, c
                                      const float* guide /* may be NULL */, const float* mask /* may be NULL */, size_t width,
                                      size_t height, size_t pitch_bytes, int radius, float sigma_guide, float sigma_space,
                                      float* out_u, float* out_v, flow2d_refine_record* record /* device, may be NULL */);
+
+/* Window correlation (digital image correlation, PIV): the displacement of a (2 radius + 1)^2 window of frame 0 found by an
+ * exhaustive search over frame 1 for the largest zero-normalised cross-correlation.  The body of the reference's
+ * Methods::Correlation, which it declares and never shipped; added to ABI version 1 without changing any existing entry.
+ * The frames are quantised to 8 bits first, so every window sum is an exact integer that depends on no order of summation; only
+ * the final score is floating point, a handful of correctly rounded double operations.
+ *
+ * Quantisation.  For a sample I (fp32), every operation rounded on its own, no fused multiply-add:
+ *   t = (I - lo) * scale;   q = 0 when !(t > 0) (a NaN lands here),  q = 255 when t >= 255,  else q = (int)(t + 0.5f)
+ * q0 is the quantised frame 0, q1 the quantised frame 1.
+ * Nodes.  r = radius (1 .. FLOW2D_CORRELATION_MAX_RADIUS), s = spacing (1 .. FLOW2D_CORRELATION_MAX_SPACING), d = range
+ * (1 .. FLOW2D_CORRELATION_MAX_RANGE); N = (2r + 1)^2.  Node (i, j) is centred on pixel (r + i*s, r + j*s);
+ * nw = (width - 2r - 1) / s + 1 and nh = (height - 2r - 1) / s + 1 (integer division): flow2d_correlation_grid.  A frame with
+ * width < 2r + 1 or height < 2r + 1 holds no node and is an invalid argument.
+ * Candidates.  A displacement (dx, dy), |dx| <= d and |dy| <= d, is a candidate of a node when the window centred on
+ * (r + i*s + dx, r + j*s + dy) lies inside frame 1 and its V1 > 0.  With S0, S00 the sums of q0 and q0^2 over the node's window,
+ * S1, S11 the sums of q1 and q1^2 over the displaced window and S01 the sum of the products q0 * q1 of corresponding pixels, in
+ * 64-bit integers
+ *   A = N*S01 - S0*S1,   V0 = N*S00 - S0*S0,   V1 = N*S11 - S1*S1,
+ *   c = (double)A / sqrt((double)V0 * (double)V1)           (one multiplication, one square root, one division, in double)
+ * Peak.  The candidate with the largest c; among equal c the one with the smaller dx*dx + dy*dy, then the smaller dy, then the
+ * smaller dx.  Its score is c0.  Per axis, with cm and cp the scores of the neighbours at -1 and +1 along that axis, in double:
+ *   den = (cm - 2*c0) + cp;   delta = den < 0 ? (cm - cp) / (2*den) : 0
+ * The node is *unrefined* -- delta_x = delta_y = 0 -- when |dx| = d or |dy| = d or any of the four neighbours (dx -+ 1, dy),
+ * (dx, dy -+ 1) is not a candidate.  u = (float)((double)dx + delta_x), v = (float)((double)dy + delta_y), score = (float)c0.
+ * Invalid and rejected nodes.  V0 = 0 or no candidate at all: u = v = NaN (0x7FC00000), score = 0; the node is *invalid*.
+ * Otherwise, score < min_score (compared in fp32; a min_score of -1 rejects nothing): u = v = NaN, the score is kept; the node is
+ * *rejected*.
+ * Record.  record[b] (DEVICE memory, may be NULL) gets four counts for instance b of a lock-step batch: nodes (nw * nh), invalid,
+ * rejected, and unrefined -- the nodes that are neither invalid nor rejected and whose vector is the integer peak for one of the
+ * reasons above.  Integers, added by integer atomics after the entry has zeroed the record on the stream: repeated calls, a
+ * replayed graph and an instance alone or in its batch give the same bytes.
+ * node_u, node_v and node_score (may be NULL) are planes of nw x nh floats with node_pitch_bytes per row (the pitch rule of the
+ * frames).  Row padding and the containers beyond width x height and nw x nh are neither read into a result nor written.  One
+ * launch on the context's stream (and a 32-byte memset per instance with a record); no allocation, no synchronisation, no host
+ * round trip (graph-capturable).  Honours flow2d_context_set_batch: the frames AND the node planes of instance b at b * stride
+ * floats from their pointers -- the node planes are laid out like every other plane of the batch, so a stride that holds a frame
+ * holds them --, record + b.
+ * FLOW2D_ERR_INVALID_ARGUMENT for a null frame, node_u or node_v, a zero size, a bad pitch (the rule of flow2d_consistency_2d,
+ * for node_pitch_bytes against nw), a frame smaller than one window, a radius, range or spacing outside its limits, a scale that
+ * is not finite and > 0, a lo that is not finite, a NaN min_score, a misaligned record (8), or a written range -- the node planes,
+ * the records, over every instance of a batch -- that overlaps a frame or another written range. */
+#define FLOW2D_CORRELATION_MAX_RADIUS 15
+#define FLOW2D_CORRELATION_MAX_RANGE 32
+#define FLOW2D_CORRELATION_MAX_SPACING 64
+typedef struct flow2d_correlation_record {
+    unsigned long long nodes;     /* nw * nh */
+    unsigned long long invalid;   /* V0 = 0 or no candidate: NaN, score 0 */
+    unsigned long long rejected;  /* score < min_score: NaN, score kept */
+    unsigned long long unrefined; /* delivered vectors without a sub-pixel part */
+} flow2d_correlation_record;
+
+#define FLOW2D_CORRELATION_RECORD_BYTES 32
+#ifdef __cplusplus
+static_assert(sizeof(flow2d_correlation_record) == FLOW2D_CORRELATION_RECORD_BYTES, "flow2d_correlation_record layout");
+#else
+_Static_assert(sizeof(flow2d_correlation_record) == FLOW2D_CORRELATION_RECORD_BYTES, "flow2d_correlation_record layout");
+#endif
+
+/* The node grid of a width x height frame into *nw, *nh (neither may be NULL).  Needs no device.  FLOW2D_ERR_INVALID_ARGUMENT --
+ * and nothing written -- for a radius or spacing outside its limits or a frame smaller than one window. */
+FLOW2D_API int flow2d_correlation_grid(size_t width, size_t height, int radius, int spacing, size_t* nw, size_t* nh);
+
+FLOW2D_API int flow2d_correlate_2d(flow2d_context* ctx, const float* frame_0, const float* frame_1, size_t width, size_t height,
+                                   size_t pitch_bytes, float lo, float scale, int radius, int range, int spacing, float min_score,
+                                   float* node_u, float* node_v, float* node_score /* may be NULL */, size_t node_pitch_bytes,
+                                   flow2d_correlation_record* record /* device, may be NULL */);
+
+/* A node field of flow2d_correlate_2d brought onto the frame's grid, so that it can feed every consumer of a dense flow
+ * (flow2d_flow_error_2d, flow2d_deformation_2d, flow2d_segment_motion_2d, flow2d_refine_flow_2d): bilinear between the four
+ * surrounding nodes, over the valid ones only, constant beyond the outermost nodes.  Per pixel (x, y), fp32, every operation
+ * rounded on its own (no fused multiply-add; division correctly rounded), with r = radius, s = spacing:
+ *   fx = ((float)x - (float)r) / (float)s, clamped to [0, nw - 1];  i0 = (int)floorf(fx);  i1 = min(i0 + 1, nw - 1);
+ *   ax = fx - (float)i0;  the same in y with nh (fy, j0, j1, ay)
+ *   weights w00 = (1 - ax)*(1 - ay), w10 = ax*(1 - ay), w01 = (1 - ax)*ay, w11 = ax*ay of the nodes (i0, j0), (i1, j0), (i0, j1),
+ *   (i1, j1); only nodes whose u and v are both finite take part, in that order:  sw += w;  su += w*u;  sv += w*v  (from 0)
+ *   out_u = su / sw, out_v = sv / sw, or NaN (0x7FC00000) for both where !(sw > 0)
+ * nw, nh >= 1 are the caller's (any node plane, not only a grid flow2d_correlation_grid would give).  Row padding and the
+ * containers beyond nw x nh and width x height are neither read into a result nor written.  One launch on the context's stream;
+ * graph-capturable.  Honours flow2d_context_set_batch: node planes and outputs of instance b at b * stride floats.
+ * FLOW2D_ERR_INVALID_ARGUMENT for a null plane, a zero size, a bad pitch, a radius outside 0 .. FLOW2D_CORRELATION_MAX_RADIUS, a
+ * spacing outside 1 .. FLOW2D_CORRELATION_MAX_SPACING, or an output that overlaps a node plane or the other output, over every
+ * instance of a batch. */
+FLOW2D_API int flow2d_expand_nodes_2d(flow2d_context* ctx, const float* node_u, const float* node_v, size_t nw, size_t nh,
+                                      size_t node_pitch_bytes, int radius, int spacing, float* out_u, float* out_v, size_t width,
+                                      size_t height, size_t pitch_bytes);
 
 /* The flow of the previous pyramid level resampled to this level's size (the bits of flow2d_resample_xy_pair into out_u / out_v)
  * and frame_1 warped by it (the bits of flow2d_registration_2d into `output`) in one launch: replaces the
