@@ -57,6 +57,7 @@ class SolveParams(C.Structure):
         ("equation_alpha", C.c_float), ("equation_smoothness", C.c_float), ("equation_data", C.c_float),
         ("outer_iterations_count", C.c_size_t), ("inner_iterations_count", C.c_size_t),
         ("data_constancy", C.c_int), ("algorithm", C.c_int), ("sor_omega", C.c_float),
+        ("base_flow_shift", C.c_int),
     ]
 
 
@@ -316,6 +317,11 @@ def hip_lib():
         L.flow2d_add_2d_pair.argtypes = [vp, vp, vp, vp, vp, sz, sz, sz]
         L.flow2d_median_2d_pair.argtypes = [vp, vp, vp, sz, sz, sz, sz, vp, vp]
         L.flow2d_add_median_2d_pair.argtypes = [vp, vp, vp, vp, vp, sz, sz, sz, sz, vp, vp]
+        L.flow2d_add_median_2d_pair_half.argtypes = [vp, vp, vp, vp, vp, sz, sz, sz, sz, vp, vp]
+        L.flow2d_upsample_registration_half_2d.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp, sz, sz, sz, f, f, vp]
+        L.flow2d_solve_level_takes_half_base.argtypes = [vp, C.POINTER(SolveParams)]
+        L.flow2d_half_base_flow_launches.argtypes = []
+        L.flow2d_half_base_flow_launches.restype = C.c_ulonglong
         L.flow2d_resample_x_pair.argtypes = [vp, vp, vp, vp, vp, sz, sz, sz, sz]
         L.flow2d_resample_y_pair.argtypes = [vp, vp, vp, vp, vp, sz, sz, sz, sz]
         L.flow2d_resample_xy_pair.argtypes = [vp, vp, vp, vp, vp, sz, sz, sz, sz, sz]
@@ -389,6 +395,11 @@ def hip_lib():
 def _check(status, where):
     if status != 0:
         raise Flow2DError(status, where, hip_lib().flow2d_last_error().decode(errors="replace"))
+
+
+def half_base_flow_launches():
+    """launches of the half-size up-sample + warp queued by this process so far (flow2d_half_base_flow_launches)"""
+    return int(hip_lib().flow2d_half_base_flow_launches())
 
 
 def resample_xy_levels_launches():
@@ -986,6 +997,11 @@ class Context:
                                                          out_v.ptr, f0.ptr, f1.ptr,
                                                          w, h, f0.pitch, hx, hy, out.ptr), "flow2d_upsample_registration_2d")
 
+    def upsample_registration_half(self, u, v, in_w, in_h, out_u, out_v, f0, f1, w, h, hx, hy, out):
+        """upsample_registration at an exactly doubled level with out_u / out_v kept at in_w x in_h (read as [y >> 1][x >> 1])."""
+        _check(hip_lib().flow2d_upsample_registration_half_2d(self.handle, u.ptr, v.ptr, in_w, in_h, out_u.ptr, out_v.ptr, f0.ptr, f1.ptr,
+                                                              w, h, f0.pitch, hx, hy, out.ptr), "flow2d_upsample_registration_half_2d")
+
     def resample_x_levels(self, src, packed, in_w, h, widths, columns, src_b=None, packed_b=None):
         """x pass for several output widths in one trip over `src`; level l lands in columns[l] .. of `packed`."""
         n = len(widths)
@@ -1009,6 +1025,12 @@ class Context:
         _check(hip_lib().flow2d_add_median_2d_pair(self.handle, src_a.ptr, add_a.ptr, src_b.ptr if src_b else None,
                                                    add_b.ptr if add_b else None, w, h, src_a.pitch, window, dst_a.ptr,
                                                    dst_b.ptr if dst_b else None), "flow2d_add_median_2d_pair")
+
+    def add_median_half(self, src_a, add_a, w, h, window, dst_a, src_b=None, add_b=None, dst_b=None):
+        """add_median with the src planes at half the size in both directions (read as [y >> 1][x >> 1])."""
+        _check(hip_lib().flow2d_add_median_2d_pair_half(self.handle, src_a.ptr, add_a.ptr, src_b.ptr if src_b else None,
+                                                        add_b.ptr if add_b else None, w, h, add_a.pitch, window, dst_a.ptr,
+                                                        dst_b.ptr if dst_b else None), "flow2d_add_median_2d_pair_half")
 
     def resample_x_pair(self, src_a, dst_a, src_b, dst_b, out_w, out_h, in_w):
         _check(hip_lib().flow2d_resample_x_pair(self.handle, src_a.ptr, dst_a.ptr, src_b.ptr, dst_b.ptr, out_w, out_h,
@@ -1035,10 +1057,10 @@ class Context:
                                              w, h, f0.pitch, hx, hy, alpha, omega, constancy), "flow2d_solve_2d_sor")
 
     def solve_level(self, f0, f1, u, v, du, dv, phi, ksi, tdu, tdv, w, h, hx, hy, alpha, e_smooth, e_data, outer,
-                    inner, constancy=GREY, algorithm=SOLVER_AUTO, container_height=None, sor_omega=0.0):
+                    inner, constancy=GREY, algorithm=SOLVER_AUTO, container_height=None, sor_omega=0.0, base_flow_shift=0):
         """Returns (du_plane, dv_plane) holding the result (the library owns the ping-pong)."""
         p = SolveParams(w, h, f0.pitch, container_height or f0.height, hx, hy, alpha, e_smooth, e_data, outer, inner,
-                        constancy, algorithm, sor_omega)
+                        constancy, algorithm, sor_omega, base_flow_shift)
         flag = C.c_int(0)
         _check(hip_lib().flow2d_solve_level(self.handle, f0.ptr, f1.ptr, u.ptr, v.ptr, du.ptr, dv.ptr, phi.ptr,
                                             ksi.ptr, tdu.ptr, tdv.ptr, C.byref(p), C.byref(flag)),

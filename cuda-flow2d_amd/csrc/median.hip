@@ -92,16 +92,33 @@ __device__ __forceinline__ void run_network(float (&v)[N], std::index_sequence<I
 // What the filter reads: a plane, or (ADD) the sum of two planes formed on the fly -- the pyramid's `u += du` followed
 // by the median of u (optical_flow_2d.cpp:414-446) in one pass: add_2d's sum is a single rounded addition
 // (add_2d.cu:33-46), so the median of the sums is the same value, and the plane of sums is neither written nor re-read.
-template <bool ADD>
+// ADD == kAddHalfBase: the first plane is held at half the size in both directions -- pixel (row, col) reads it at
+// (row >> 1, col >> 1), after mirroring, in the same pitch -- and the addend at full size (an exactly doubled pyramid level, whose
+// base flow is a replication of the previous level's: flow2d_upsample_registration_half_2d).  The same sums, the same bits.
+enum { kPlain = 0, kAdd = 1, kAddHalfBase = 2 };
+template <int ADD>
 struct Source {
     const float* __restrict__ in;
     const float* __restrict__ add;
-    __device__ __forceinline__ float operator[](size_t i) const
+    // element (row, col) of the image, both inside it
+    __device__ __forceinline__ float at(int row, int col, int pitch) const
     {
+        const size_t i = static_cast<size_t>(row) * pitch + col;
+        if (ADD == kAddHalfBase) return in[static_cast<size_t>(row >> 1) * pitch + (col >> 1)] + add[i];
         if (ADD) return in[i] + add[i];
         return in[i];
     }
 };
+// byte offset of (row, col) in the first plane of a Source
+template <int ADD>
+__device__ __forceinline__ unsigned base_byte_offset(unsigned row, unsigned col, unsigned pitch)
+{
+    if (ADD != kAddHalfBase) return (row * pitch + col) * 4u;
+    // (the column's shift stays at the load: hoisted out of the row loop, the shifted columns -- five or seven of a wave on the image's
+    //  left or right border -- are registers the 5 x 5 kernel does not have at four waves per SIMD)
+    asm volatile("" : "+v"(col));
+    return ((row >> 1) * pitch + (col >> 1)) * 4u;
+}
 
 // The streaming kernels address a plane as base pointer (wave-uniform: a scalar register pair) + one 32-bit per-lane BYTE offset
 // (global_load / global_store ... saddr), like the strip kernel of the solver: a 64-bit address per access was two to three
@@ -126,13 +143,13 @@ __device__ __forceinline__ bool is_special(float v) { return __builtin_amdgcn_cl
 //  * equal values (and -0 / +0, which compare equal) keep their gather order (the sort is stable).
 // So the result is the NaN sitting at r*r/2, or the element of stable rank r*r/2 - a in the run [a, b) of gather
 // positions between the nearest NaNs on either side.  O(n^2) loads (L1 hits); only rare windows come here.
-template <int R, bool ADD>
+template <int R, int ADD>
 __device__ __noinline__ float exact_median(const Source<ADD> in, int x, int y, int w, int h, int pitch)
 {
     constexpr int N = R * R, R2 = R / 2, M = N / 2;
     auto at = [&](int k) {
         const int iy = k / R, ix = k - iy * R;
-        return in[static_cast<size_t>(mirror_index(y - iy + R2, h)) * pitch + mirror_index(x - ix + R2, w)];
+        return in.at(mirror_index(y - iy + R2, h), mirror_index(x - ix + R2, w), pitch);
     };
     const float vm = at(M);
     if (vm != vm) return vm;
@@ -158,7 +175,7 @@ __device__ __noinline__ float exact_median(const Source<ADD> in, int x, int y, i
 }
 
 // (grid.z = 2 filters a second, independent plane in the same launch: the flow's u and v)
-template <int R, bool ADD>
+template <int R, int ADD>
 __global__ __launch_bounds__(256) void median_kernel(const float* __restrict__ in_a, const float* __restrict__ in_b,
                                                      const float* __restrict__ add_a, const float* __restrict__ add_b, int w,
                                                      int h, int pitch, float* __restrict__ out_a,
@@ -179,10 +196,10 @@ __global__ __launch_bounds__(256) void median_kernel(const float* __restrict__ i
     bool special = false;
 #pragma unroll
     for (int j = 0; j < R; ++j) {
-        const size_t row = static_cast<size_t>(mirror_index(y + j - R2, h)) * pitch;
+        const int row = mirror_index(y + j - R2, h);
 #pragma unroll
         for (int i = 0; i < R; ++i) {
-            v[j * R + i] = in[row + xs[i]];
+            v[j * R + i] = in.at(row, xs[i], pitch);
             special |= is_special(v[j * R + i]);
         }
     }
@@ -242,23 +259,24 @@ constexpr int kStreamValid = 60;  // lanes 2..61 of a wave have both neighbours 
 // the values a lane loads for one image row: its own column, or (EDGE) the five mirrored columns -- RAW, as they come
 // from memory: the sum with the addend and the NaN / -0 check happen where the row is consumed (sorted_tuple), two
 // steps later, so that nothing waits for a load at the place it is issued
-template <bool EDGE, bool ADD>
+template <bool EDGE, int ADD>
 struct RowLoad {
     float v[EDGE ? 5 : 1];
     float a[ADD ? (EDGE ? 5 : 1) : 1];
 };
 
-template <bool EDGE, bool ADD>
+template <bool EDGE, int ADD>
 __device__ __forceinline__ RowLoad<EDGE, ADD> load_row(const Source<ADD> in, int row, int h, int pitch, int xc,
                                                        const int (&xm)[5])
 {
-    const unsigned line = static_cast<unsigned>(min(max(mirror_index(row, h), 0), h - 1)) * static_cast<unsigned>(pitch);
+    const unsigned line_row = static_cast<unsigned>(min(max(mirror_index(row, h), 0), h - 1));
+    const unsigned line = line_row * static_cast<unsigned>(pitch);
     RowLoad<EDGE, ADD> r;
     r.a[0] = 0.f;
 #pragma unroll
     for (int i = 0; i < (EDGE ? 5 : 1); ++i) {
         const unsigned at = (line + static_cast<unsigned>(EDGE ? xm[i] : xc)) * 4u;
-        r.v[i] = plane_load(in.in, at);
+        r.v[i] = plane_load(in.in, base_byte_offset<ADD>(line_row, static_cast<unsigned>(EDGE ? xm[i] : xc), static_cast<unsigned>(pitch)));
         if (ADD) r.a[i] = plane_load(in.add, at);
     }
     return r;
@@ -266,7 +284,7 @@ __device__ __forceinline__ RowLoad<EDGE, ADD> load_row(const Source<ADD> in, int
 
 // sorted 5-tuple (x-2 .. x+2) of the loaded row.  `special` collects whether any value this lane loaded is a NaN or a
 // -0 (one v_cmp_class per value; the strip is re-checked per pixel only when some lane of the wave saw one)
-template <bool EDGE, bool ADD>
+template <bool EDGE, int ADD>
 __device__ __forceinline__ void sorted_tuple(const RowLoad<EDGE, ADD>& r, float (&t)[5], bool& special)
 {
     if (EDGE) {
@@ -290,7 +308,7 @@ __device__ __forceinline__ void sorted_tuple(const RowLoad<EDGE, ADD>& r, float 
 
 // One wave, one strip of 64 columns, rows [y0, y1).  Step I of three (the ring of six row slots advances by
 // two rows per step, so three steps bring every slot back to its place and all indices are constants).
-template <bool EDGE, int I, bool ADD>
+template <bool EDGE, int I, int ADD>
 __device__ __forceinline__ void median5_step(float (&ring)[6][5], RowLoad<EDGE, ADD> (&next)[4], const Source<ADD> in,
                                              float* __restrict__ out, int ya, int y1, int h, int pitch, int x, int xc,
                                              const int (&xm)[5], bool lane_stores, bool& special)
@@ -316,7 +334,7 @@ __device__ __forceinline__ void median5_step(float (&ring)[6][5], RowLoad<EDGE, 
     }
 }
 
-template <bool EDGE, bool ADD>
+template <bool EDGE, int ADD>
 __device__ __forceinline__ void median5_strip(const Source<ADD> in, float* __restrict__ out, int w, int h, int pitch,
                                               int x, int y0, int y1, bool lane_stores)
 {
@@ -351,21 +369,19 @@ __device__ __forceinline__ void median5_strip(const Source<ADD> in, float* __res
         for (int y = y0; y < y1; ++y) {
             bool hit = false;
             for (int j = -2; j <= 2; ++j) {
-                const size_t line = static_cast<size_t>(mirror_index(y + j, h)) * pitch;
-                for (int i = -2; i <= 2; ++i) hit |= is_special(in[line + mirror_index(x + i, w)]);
+                const int line = mirror_index(y + j, h);
+                for (int i = -2; i <= 2; ++i) hit |= is_special(in.at(line, mirror_index(x + i, w), pitch));
             }
             if (hit) out[static_cast<size_t>(y) * pitch + x] = exact_median<5, ADD>(in, x, y, w, h, pitch);
         }
     }
 }
 
-template <bool ADD>
-__global__ __launch_bounds__(256) void median5_stream_kernel(const float* __restrict__ in_a,
-                                                             const float* __restrict__ in_b,
-                                                             const float* __restrict__ add_a,
-                                                             const float* __restrict__ add_b, int w, int h, int pitch,
-                                                             int rows_per_strip, float* __restrict__ out_a,
-                                                             float* __restrict__ out_b, BatchArg batch)
+template <int ADD>
+__device__ __forceinline__ void median5_stream_body(const float* __restrict__ in_a, const float* __restrict__ in_b,
+                                                    const float* __restrict__ add_a, const float* __restrict__ add_b, int w, int h,
+                                                    int pitch, int rows_per_strip, float* __restrict__ out_a,
+                                                    float* __restrict__ out_b, BatchArg batch)
 {
     const Source<ADD> in{(batch_plane(batch) ? in_b : in_a) + batch_offset(batch),
                          ADD ? (batch_plane(batch) ? add_b : add_a) + batch_offset(batch) : nullptr};
@@ -387,6 +403,28 @@ __global__ __launch_bounds__(256) void median5_stream_kernel(const float* __rest
         median5_strip<false, ADD>(in, out, w, h, pitch, x, y0, y1, lane_stores);
 }
 
+template <int ADD>
+__global__ __launch_bounds__(256) void median5_stream_kernel(const float* __restrict__ in_a,
+                                                             const float* __restrict__ in_b,
+                                                             const float* __restrict__ add_a,
+                                                             const float* __restrict__ add_b, int w, int h, int pitch,
+                                                             int rows_per_strip, float* __restrict__ out_a,
+                                                             float* __restrict__ out_b, BatchArg batch)
+{
+    median5_stream_body<ADD>(in_a, in_b, add_a, add_b, w, h, pitch, rows_per_strip, out_a, out_b, batch);
+}
+// The half-size base's instance alone is held to four waves per SIMD, where the other two are by themselves (108 and 128 vector
+// registers): left alone it takes 134 and runs three -- 104 us instead of the full-size form's 92 per 4096^2 plane pair.  The price is
+// 32 bytes of scratch per lane: six registers of the border body stored once before its row loop and loaded after it, none inside a
+// loop; the interior body has none.
+template <>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void median5_stream_kernel<kAddHalfBase>(
+    const float* __restrict__ in_a, const float* __restrict__ in_b, const float* __restrict__ add_a, const float* __restrict__ add_b, int w,
+    int h, int pitch, int rows_per_strip, float* __restrict__ out_a, float* __restrict__ out_b, BatchArg batch)
+{
+    median5_stream_body<kAddHalfBase>(in_a, in_b, add_a, add_b, w, h, pitch, rows_per_strip, out_a, out_b, batch);
+}
+
 // ---- r = 3, streaming (round 6) -----------------------------------------------------------------------------------
 // The same scheme one size down: a lane loads ONE value per image row, takes its two horizontal neighbours from the adjacent
 // lanes (DPP) and sorts the triple with three instructions (v_min3 / v_med3 / v_max3 of the same three values); with the
@@ -395,29 +433,30 @@ __global__ __launch_bounds__(256) void median5_stream_kernel(const float* __rest
 // values per pixel: 66 us per 4096^2 plane, slower than the 5 x 5 filter.
 constexpr int kStream3Valid = 62;  // lanes 1..62 of a wave have a neighbour on either side
 
-template <bool EDGE, bool ADD>
+template <bool EDGE, int ADD>
 struct Row3Load {
     float v[EDGE ? 3 : 1];
     float a[ADD ? (EDGE ? 3 : 1) : 1];
 };
 
-template <bool EDGE, bool ADD>
+template <bool EDGE, int ADD>
 __device__ __forceinline__ Row3Load<EDGE, ADD> load_row3(const Source<ADD> in, int row, int h, int pitch, int xc, const int (&xm)[3])
 {
-    const unsigned line = static_cast<unsigned>(min(max(mirror_index(row, h), 0), h - 1)) * static_cast<unsigned>(pitch);
+    const unsigned line_row = static_cast<unsigned>(min(max(mirror_index(row, h), 0), h - 1));
+    const unsigned line = line_row * static_cast<unsigned>(pitch);
     Row3Load<EDGE, ADD> r;
     r.a[0] = 0.f;
 #pragma unroll
     for (int i = 0; i < (EDGE ? 3 : 1); ++i) {
         const unsigned at = (line + static_cast<unsigned>(EDGE ? xm[i] : xc)) * 4u;
-        r.v[i] = plane_load(in.in, at);
+        r.v[i] = plane_load(in.in, base_byte_offset<ADD>(line_row, static_cast<unsigned>(EDGE ? xm[i] : xc), static_cast<unsigned>(pitch)));
         if (ADD) r.a[i] = plane_load(in.add, at);
     }
     return r;
 }
 
 // (minimum, median, maximum) of the row's three values x-1, x, x+1
-template <bool EDGE, bool ADD>
+template <bool EDGE, int ADD>
 __device__ __forceinline__ void sorted_triple(const Row3Load<EDGE, ADD>& r, float (&t)[3], bool& special)
 {
     float a, b, c;
@@ -440,7 +479,7 @@ __device__ __forceinline__ float median_of_sorted_rows(const float (&p)[3], cons
 }
 
 // Step I of two (the ring of four row slots advances by two rows per step): output rows ya, ya + 1 from rows ya-1 .. ya+2.
-template <bool EDGE, int I, bool ADD>
+template <bool EDGE, int I, int ADD>
 __device__ __forceinline__ void median3_step(float (&ring)[4][3], Row3Load<EDGE, ADD> (&next)[4], const Source<ADD> in,
                                              float* __restrict__ out, int ya, int y1, int h, int pitch, int x, int xc,
                                              const int (&xm)[3], bool lane_stores, bool& special)
@@ -461,7 +500,7 @@ __device__ __forceinline__ void median3_step(float (&ring)[4][3], Row3Load<EDGE,
     }
 }
 
-template <bool EDGE, bool ADD>
+template <bool EDGE, int ADD>
 __device__ __forceinline__ void median3_strip(const Source<ADD> in, float* __restrict__ out, int w, int h, int pitch,
                                               int x, int y0, int y1, bool lane_stores)
 {
@@ -491,15 +530,15 @@ __device__ __forceinline__ void median3_strip(const Source<ADD> in, float* __res
         for (int y = y0; y < y1; ++y) {
             bool hit = false;
             for (int j = -1; j <= 1; ++j) {
-                const size_t line = static_cast<size_t>(mirror_index(y + j, h)) * pitch;
-                for (int i = -1; i <= 1; ++i) hit |= is_special(in[line + mirror_index(x + i, w)]);
+                const int line = mirror_index(y + j, h);
+                for (int i = -1; i <= 1; ++i) hit |= is_special(in.at(line, mirror_index(x + i, w), pitch));
             }
             if (hit) out[static_cast<size_t>(y) * pitch + x] = exact_median<3, ADD>(in, x, y, w, h, pitch);
         }
     }
 }
 
-template <bool ADD>
+template <int ADD>
 __global__ __launch_bounds__(256) void median3_stream_kernel(const float* __restrict__ in_a, const float* __restrict__ in_b,
                                                              const float* __restrict__ add_a, const float* __restrict__ add_b, int w, int h,
                                                              int pitch, int rows_per_strip, float* __restrict__ out_a,
@@ -544,29 +583,30 @@ __device__ __forceinline__ void sort7(float (&t)[7])
 
 constexpr int kStream7Valid = 58;  // lanes 3..60 of a wave have three neighbours on either side
 
-template <bool EDGE, bool ADD>
+template <bool EDGE, int ADD>
 struct Row7Load {
     float v[EDGE ? 7 : 1];
     float a[ADD ? (EDGE ? 7 : 1) : 1];
 };
 
-template <bool EDGE, bool ADD>
+template <bool EDGE, int ADD>
 __device__ __forceinline__ Row7Load<EDGE, ADD> load_row7(const Source<ADD> in, int row, int h, int pitch, int xc,
                                                          const int (&xm)[7])
 {
-    const unsigned line = static_cast<unsigned>(min(max(mirror_index(row, h), 0), h - 1)) * static_cast<unsigned>(pitch);
+    const unsigned line_row = static_cast<unsigned>(min(max(mirror_index(row, h), 0), h - 1));
+    const unsigned line = line_row * static_cast<unsigned>(pitch);
     Row7Load<EDGE, ADD> r;
     r.a[0] = 0.f;
 #pragma unroll
     for (int i = 0; i < (EDGE ? 7 : 1); ++i) {
         const unsigned at = (line + static_cast<unsigned>(EDGE ? xm[i] : xc)) * 4u;
-        r.v[i] = plane_load(in.in, at);
+        r.v[i] = plane_load(in.in, base_byte_offset<ADD>(line_row, static_cast<unsigned>(EDGE ? xm[i] : xc), static_cast<unsigned>(pitch)));
         if (ADD) r.a[i] = plane_load(in.add, at);
     }
     return r;
 }
 
-template <bool EDGE, bool ADD>
+template <bool EDGE, int ADD>
 __device__ __forceinline__ void sorted_tuple7(const Row7Load<EDGE, ADD>& r, float (&t)[7], bool& special)
 {
     if (EDGE) {
@@ -592,7 +632,7 @@ __device__ __forceinline__ void sorted_tuple7(const Row7Load<EDGE, ADD>& r, floa
 }
 
 // Step I of four: the ring of eight row slots advances by two rows per step.
-template <bool EDGE, int I, bool ADD>
+template <bool EDGE, int I, int ADD>
 __device__ __forceinline__ void median7_step(float (&ring)[8][7], Row7Load<EDGE, ADD> (&next)[4], const Source<ADD> in,
                                              float* __restrict__ out, int ya, int y1, int h, int pitch, int x, int xc,
                                              const int (&xm)[7], bool lane_stores, bool& special)
@@ -617,7 +657,7 @@ __device__ __forceinline__ void median7_step(float (&ring)[8][7], Row7Load<EDGE,
     }
 }
 
-template <bool EDGE, bool ADD>
+template <bool EDGE, int ADD>
 __device__ __forceinline__ void median7_strip(const Source<ADD> in, float* __restrict__ out, int w, int h, int pitch,
                                               int x, int y0, int y1, bool lane_stores)
 {
@@ -653,15 +693,15 @@ __device__ __forceinline__ void median7_strip(const Source<ADD> in, float* __res
         for (int y = y0; y < y1; ++y) {
             bool hit = false;
             for (int j = -3; j <= 3; ++j) {
-                const size_t line = static_cast<size_t>(mirror_index(y + j, h)) * pitch;
-                for (int i = -3; i <= 3; ++i) hit |= is_special(in[line + mirror_index(x + i, w)]);
+                const int line = mirror_index(y + j, h);
+                for (int i = -3; i <= 3; ++i) hit |= is_special(in.at(line, mirror_index(x + i, w), pitch));
             }
             if (hit) out[static_cast<size_t>(y) * pitch + x] = exact_median<7, ADD>(in, x, y, w, h, pitch);
         }
     }
 }
 
-template <bool ADD>
+template <int ADD>
 __global__ __launch_bounds__(256) void median7_stream_kernel(const float* __restrict__ in_a,
                                                              const float* __restrict__ in_b,
                                                              const float* __restrict__ add_a,
@@ -699,17 +739,19 @@ int median5_rows_per_strip(const flow2d_context* ctx, size_t w, size_t h)
 
 }  // namespace
 
-template <bool ADD>
+template <int ADD>
 static int launch_median(flow2d_context* ctx, const float* input, const float* input_b, const float* addend,
                          const float* addend_b, size_t width, size_t height, size_t pitch_bytes, size_t window,
                          float* output, float* output_b)
 {
     FLOW2D_ENTER(ctx);
-    if (!flow2d::plane_args_ok(input, width, height, pitch_bytes) ||
+    // (a half-size base: (height + 1) / 2 rows of (width + 1) / 2 pixels, in the same pitch)
+    const size_t in_width = ADD == kAddHalfBase ? (width + 1) / 2 : width, in_height = ADD == kAddHalfBase ? (height + 1) / 2 : height;
+    if (!flow2d::plane_args_ok(input, in_width, in_height, pitch_bytes) ||
         !flow2d::plane_args_ok(output, width, height, pitch_bytes) || input == output)
         return FLOW2D_ERR_INVALID_ARGUMENT;
     const bool pair = input_b || output_b;
-    if (pair && (!flow2d::plane_args_ok(input_b, width, height, pitch_bytes) ||
+    if (pair && (!flow2d::plane_args_ok(input_b, in_width, in_height, pitch_bytes) ||
                  !flow2d::plane_args_ok(output_b, width, height, pitch_bytes) || input_b == output_b ||
                  output_b == output || output_b == input || output == input_b))
         return FLOW2D_ERR_INVALID_ARGUMENT;
@@ -717,6 +759,12 @@ static int launch_median(flow2d_context* ctx, const float* input, const float* i
                 (pair && (!flow2d::plane_args_ok(addend_b, width, height, pitch_bytes) || addend_b == output ||
                           addend_b == output_b))))
         return FLOW2D_ERR_INVALID_ARGUMENT;
+    if (ADD == kAddHalfBase && ctx->batch_count > 1) {  // the entry's byte-range check again, over every instance of a lock-step group
+        const size_t half_span = flow2d::batch_span(ctx, in_height * pitch_bytes), full_span = flow2d::batch_span(ctx, height * pitch_bytes);
+        const flow2d::ByteRange written[] = {{output, full_span}, {output_b, full_span}};
+        const flow2d::ByteRange read[] = {{input, half_span}, {input_b, half_span}, {addend, full_span}, {addend_b, full_span}};
+        if (flow2d::any_overlap(written, read)) return FLOW2D_ERR_INVALID_ARGUMENT;
+    }
     if (window != 3 && window != 5 && window != 7) return FLOW2D_ERR_UNSUPPORTED;
     // the mirror rule needs every reflected index inside the image
     if (width <= window / 2 || height <= window / 2) return FLOW2D_ERR_UNSUPPORTED;
@@ -763,14 +811,14 @@ static int launch_median(flow2d_context* ctx, const float* input, const float* i
 extern "C" int flow2d_median_2d(flow2d_context* ctx, const float* input, size_t width, size_t height,
                                 size_t pitch_bytes, size_t window, float* output)
 {
-    return launch_median<false>(ctx, input, nullptr, nullptr, nullptr, width, height, pitch_bytes, window, output, nullptr);
+    return launch_median<kPlain>(ctx, input, nullptr, nullptr, nullptr, width, height, pitch_bytes, window, output, nullptr);
 }
 
 extern "C" int flow2d_median_2d_pair(flow2d_context* ctx, const float* input_a, const float* input_b, size_t width,
                                      size_t height, size_t pitch_bytes, size_t window, float* output_a, float* output_b)
 {
     if (!input_b || !output_b) return FLOW2D_ERR_INVALID_ARGUMENT;
-    return launch_median<false>(ctx, input_a, input_b, nullptr, nullptr, width, height, pitch_bytes, window, output_a, output_b);
+    return launch_median<kPlain>(ctx, input_a, input_b, nullptr, nullptr, width, height, pitch_bytes, window, output_a, output_b);
 }
 
 extern "C" int flow2d_add_median_2d_pair(flow2d_context* ctx, const float* input_a, const float* addend_a, const float* input_b,
@@ -778,5 +826,21 @@ extern "C" int flow2d_add_median_2d_pair(flow2d_context* ctx, const float* input
                                          float* output_a, float* output_b)
 {
     if (!addend_a || ((input_b || output_b || addend_b) && !(input_b && output_b && addend_b))) return FLOW2D_ERR_INVALID_ARGUMENT;
-    return launch_median<true>(ctx, input_a, input_b, addend_a, addend_b, width, height, pitch_bytes, window, output_a, output_b);
+    return launch_median<kAdd>(ctx, input_a, input_b, addend_a, addend_b, width, height, pitch_bytes, window, output_a, output_b);
+}
+
+// flow2d_add_median_2d_pair with the input planes at half the size in both directions: the filter runs over
+// input[y >> 1][x >> 1] + addend[y][x] -- the same sums as that entry's over the replicated input, the same bits.
+extern "C" int flow2d_add_median_2d_pair_half(flow2d_context* ctx, const float* input_a, const float* addend_a, const float* input_b,
+                                              const float* addend_b, size_t width, size_t height, size_t pitch_bytes, size_t window,
+                                              float* output_a, float* output_b)
+{
+    if (!addend_a || ((input_b || output_b || addend_b) && !(input_b && output_b && addend_b))) return FLOW2D_ERR_INVALID_ARGUMENT;
+    {   // a written plane may not reach into the rows of an input (base pointers alone do not tell: the inputs hold half the rows)
+        const size_t half_bytes = (height + 1) / 2 * pitch_bytes, full_bytes = height * pitch_bytes;
+        const flow2d::ByteRange written[] = {{output_a, full_bytes}, {output_b, full_bytes}};
+        const flow2d::ByteRange read[] = {{input_a, half_bytes}, {input_b, half_bytes}, {addend_a, full_bytes}, {addend_b, full_bytes}};
+        if (flow2d::any_overlap(written, read)) return FLOW2D_ERR_INVALID_ARGUMENT;
+    }
+    return launch_median<kAddHalfBase>(ctx, input_a, input_b, addend_a, addend_b, width, height, pitch_bytes, window, output_a, output_b);
 }

@@ -771,7 +771,11 @@ __global__ __launch_bounds__(256) void registration_kernel(const float* __restri
 // goes through the general form's operations for one cell -- ((0 + a * delta_x) * norm_x, 0 + that * delta_y, * norm_y) -- bit for bit.
 // ZERO: the coarsest level -- no previous flow: (u, v) = 0 is stored and warped by (the reference fills both planes with two memsets
 // of the whole container first, optical_flow_2d.cpp:308-313; what lies outside the level's region of a plane is never read).
-enum { kUpsampleGeneral = 0, kUpsampleDouble = 1, kUpsampleZero = 2 };
+// DOUBLE_HALF: DOUBLE whose (u, v) planes stay at the INPUT size -- at an exactly doubled level the level's flow is a replication, every
+// 2 x 2 block of pixels the value of one input pixel after the chain above (not the identity: -0 becomes +0, denormals round) -- so the
+// chain's result is stored once per input pixel, out[y >> 1][x >> 1], and the readers of the level (the strip solver, the median with
+// addend) index it that way: a quarter of the bytes written here and read eleven times after.  The warp is DOUBLE's, from registers.
+enum { kUpsampleGeneral = 0, kUpsampleDouble = 1, kUpsampleZero = 2, kUpsampleDoubleHalf = 3 };
 template <int MODE>
 __global__ __launch_bounds__(256) void upsample_registration_kernel(const float* __restrict__ in_u, const float* __restrict__ in_v,
                                                                     float* __restrict__ out_u, float* __restrict__ out_v,
@@ -790,7 +794,8 @@ __global__ __launch_bounds__(256) void upsample_registration_kernel(const float*
     warped += batch_offset(batch);
     const int gx = blockIdx.x * kBlockX + threadIdx.x;
     if (gx >= w) return;
-    constexpr bool DOUBLE = MODE == kUpsampleDouble;
+    constexpr bool HALF = MODE == kUpsampleDoubleHalf;
+    constexpr bool DOUBLE = MODE == kUpsampleDouble || HALF;
     const ResampleXCells cells = resample_x_cells(gx, in_w, k);
     float uu[kRegistrationRows], vv[kRegistrationRows];
     int rows[kRegistrationRows];
@@ -832,8 +837,16 @@ __global__ __launch_bounds__(256) void upsample_registration_kernel(const float*
         const int gy = rows[i];
         if (gy >= h) return;
         const size_t c = static_cast<size_t>(gy) * pitch + gx;
-        out_u[c] = uu[i];
-        out_v[c] = vv[i];
+        if (HALF) {  // one store per input pixel: the thread of its first column, at the first of its two rows (h is even)
+            if ((i & 1) == 0 && (gx & 1) == 0) {
+                const size_t half = static_cast<size_t>(gy >> 1) * pitch + (gx >> 1);
+                out_u[half] = uu[i];
+                out_v[half] = vv[i];
+            }
+        } else {
+            out_u[c] = uu[i];
+            out_v[c] = vv[i];
+        }
         warped[c] = registered_value(f0, f1, gx, gy, c, uu[i], vv[i], w, h, pitch, inv_hx, inv_hy);
     }
 }
@@ -1721,5 +1734,47 @@ int flow2d_upsample_registration_2d(flow2d_context* ctx, const float* flow_u, co
     return FLOW2D_OK;
 }
 
+// launches of the half-size form queued by this process (flow2d_half_base_flow_launches: which path a pyramid took)
+static std::atomic<unsigned long long> half_base_flow_launches{0};
+
+// flow2d_upsample_registration_2d at an exactly doubled level (width = 2 in_width, height = 2 in_height) with out_u / out_v kept at
+// in_width x in_height: out[y][x] holds what that entry stores at the four pixels (2y .. 2y + 1, 2x .. 2x + 1); `output` is its
+// warped frame, bit for bit.
+int flow2d_upsample_registration_half_2d(flow2d_context* ctx, const float* flow_u, const float* flow_v, size_t in_width, size_t in_height,
+                                         float* out_u, float* out_v, const float* frame_0, const float* frame_1, size_t width,
+                                         size_t height, size_t pitch_bytes, float hx, float hy, float* output)
+{
+    if (!flow2d::plane_args_ok(flow_u, in_width, in_height, pitch_bytes) || !flow2d::plane_args_ok(flow_v, in_width, in_height, pitch_bytes) ||
+        !flow2d::plane_args_ok(out_u, in_width, in_height, pitch_bytes) || !flow2d::plane_args_ok(out_v, in_width, in_height, pitch_bytes) ||
+        !flow2d::plane_args_ok(frame_0, width, height, pitch_bytes) || !flow2d::plane_args_ok(frame_1, width, height, pitch_bytes) ||
+        !flow2d::plane_args_ok(output, width, height, pitch_bytes) || !(hx > 0.f) || !(hy > 0.f))
+        return FLOW2D_ERR_INVALID_ARGUMENT;
+    if (width != 2 * in_width || height != 2 * in_height) return FLOW2D_ERR_UNSUPPORTED;
+    const size_t half_bytes = in_height * pitch_bytes, full_bytes = height * pitch_bytes;
+    {   // the kernel marks every plane __restrict__: no written byte range may meet a read one or another written one
+        const flow2d::ByteRange written[] = {{out_u, half_bytes}, {out_v, half_bytes}, {output, full_bytes}};
+        const flow2d::ByteRange read[] = {{flow_u, half_bytes}, {flow_v, half_bytes}, {frame_0, full_bytes}, {frame_1, full_bytes}};
+        if (flow2d::any_overlap(written, read)) return FLOW2D_ERR_INVALID_ARGUMENT;
+    }
+    FLOW2D_ENTER(ctx);
+    {   // ... over every instance of a lock-step group
+        const size_t half_span = flow2d::batch_span(ctx, half_bytes), full_span = flow2d::batch_span(ctx, full_bytes);
+        const flow2d::ByteRange written[] = {{out_u, half_span}, {out_v, half_span}, {output, full_span}};
+        const flow2d::ByteRange read[] = {{flow_u, half_span}, {flow_v, half_span}, {frame_0, full_span}, {frame_1, full_span}};
+        if (ctx->batch_count > 1 && flow2d::any_overlap(written, read)) return FLOW2D_ERR_INVALID_ARGUMENT;
+    }
+    dim3 grid = grid_for(width, flow2d::div_up(height, kRegistrationRows));
+    grid.z = flow2d::batch_z(ctx, 1);
+    const ResampleXY k{static_cast<float>(in_width) / static_cast<float>(width), static_cast<float>(width) / static_cast<float>(in_width),
+                       static_cast<float>(in_height) / static_cast<float>(height), static_cast<float>(height) / static_cast<float>(in_height)};
+    upsample_registration_kernel<kUpsampleDoubleHalf><<<grid, dim3(kBlockX, kBlockY), 0, ctx->stream>>>(
+        flow_u, flow_v, out_u, out_v, frame_0, frame_1, output, (int)width, (int)height, (int)in_width, (int)in_height,
+        (int)(pitch_bytes / 4), k, 1.f / hx, 1.f / hy, flow2d::batch_arg(ctx, 1));
+    FLOW2D_CHECK_LAUNCH();
+    half_base_flow_launches.fetch_add(1, std::memory_order_relaxed);
+    return FLOW2D_OK;
+}
+
+unsigned long long flow2d_half_base_flow_launches(void) { return half_base_flow_launches.load(std::memory_order_relaxed); }
 
 }  // extern "C"

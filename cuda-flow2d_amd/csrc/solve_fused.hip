@@ -227,10 +227,11 @@ int launch_fused_outer(flow2d_context* ctx, int constancy, const float* f0, cons
                        const float* v, const float* du, const float* dv, size_t w, size_t h, size_t pitch_bytes,
                        float hx, float hy, float alpha, float e_smooth, float e_data, size_t inner, float* out_du,
                        float* out_dv, int rows_per_strip, bool zero_increment, const float* start_du,
-                       const float* start_dv, float sor_omega)
+                       const float* start_dv, float sor_omega, int base_flow_shift)
 {
     // sor_omega != 0: the `inner` stages are red-black half-sweeps (2 or 4: one or two iterations per launch)
     if (!fused_supports(inner) || !fused_addressable(h, pitch_bytes)) return FLOW2D_ERR_UNSUPPORTED;
+    if (base_flow_shift != 0 && base_flow_shift != 1) return FLOW2D_ERR_UNSUPPORTED;
     if (sor_omega != 0.f && (inner != 2 && inner != 4)) return FLOW2D_ERR_UNSUPPORTED;
     if (!fused_weights_ok(hx, hy, alpha)) return FLOW2D_ERR_UNSUPPORTED;
     // rows_per_strip > 0: uniform strips of that height (developer override); 0: the planner's choice
@@ -252,13 +253,14 @@ int launch_fused_outer(flow2d_context* ctx, int constancy, const float* f0, cons
                 static_cast<float>(1.0 / (2.0 * hx)), static_cast<float>(1.0 / (2.0 * hy)), alpha / (hx * hx), alpha / (hy * hy),
                 0.5f * (alpha / (hx * hx)), 0.5f * (alpha / (hy * hy)),
                 sor_omega, 1.f - sor_omega,
-                0, plan.blocks, 0, 0, static_cast<unsigned long long>(ctx->batch_stride_floats),
+                0, plan.blocks, 0, 0, static_cast<unsigned long long>(ctx->batch_stride_floats), base_flow_shift,
                 nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
                 ctx->fused_fallbacks};
     // The first outer iteration of a level starts from du = dv = 0: the kernel loads the increment planes all the same (no branch
     // around two loads in every row step) and selects the zero -- so let those loads go to (u, v), whose lines the same step has just
     // fetched, instead of dragging two planes of stale data through HBM (a 4096^2 launch 583 -> 450 MB; round 6).
-    if (zero_increment) a.du = u, a.dv = v;
+    // With (u, v) at half the size (base_flow_shift) the full-size offsets would leave their region: the frames serve the same way.
+    if (zero_increment) a.du = base_flow_shift ? f0 : u, a.dv = base_flow_shift ? f1 : v;
 #ifdef FLOW2D_DEV_BUILD
     if (probe::kStamps) a.stamps = stamp_buffer(), a.stamp_count = stamp_counter(), a.stalls = stall_buffer();
     const size_t plane_floats = h * (pitch_bytes / 4);

@@ -53,6 +53,10 @@ struct FusedArgs {
     int side_blocks;                  // border-aware plans: the blocks of the first and last block column (the last side_blocks of
                                       // the plan's order), dealt evenly over the XCDs' runs; 0: every XCD a plain run of the order
     unsigned long long batch_stride;  // floats between the instances of a batched launch (blockIdx.z)
+    // 0: u and v are w x h planes like the others.  1: they are held at half the size in both directions, in the same pitch -- an
+    // exactly doubled pyramid level, whose base flow is a replication of the previous level's -- and pixel (y, x) reads them at
+    // (y >> 1, x >> 1); every other plane is addressed as before.  Wave-uniform; the same values, so the same results.
+    int uv_shift;
     // developer probes (solve_fused_probes.hpp; null in the product library, whose kernels never read them): per-wave time stamps
     // with their counter and stall histograms; the frames and the flow of a pixel as one float4 plane, the increment as float2 planes
     unsigned long long* stamps;

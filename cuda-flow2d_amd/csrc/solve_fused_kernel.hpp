@@ -74,8 +74,9 @@ struct RowFetch {
     v2f uv, duv;
 };
 typedef float v4f __attribute__((ext_vector_type(4)));
-// byte_offset: (row * pitch + column) * 4, the offset all planes share
-__device__ __forceinline__ RowFetch fetch_row(const FusedArgs& a, unsigned byte_offset)
+// byte_offset: (row * pitch + column) * 4, the offset all planes share -- but (u, v), which a level may hold at half the size in both
+// directions (FusedArgs::uv_shift): uv_offset = ((row >> uv_shift) * pitch + (column >> uv_shift)) * 4
+__device__ __forceinline__ RowFetch fetch_row(const FusedArgs& a, unsigned byte_offset, unsigned uv_offset)
 {
     if constexpr (probe::kPackedPlanes) {  // probe: (f0, f1, u, v) of a pixel side by side in one plane, (du, dv) in another
         const v4f q = *reinterpret_cast<const v4f*>(reinterpret_cast<const char*>(a.pack_in) + static_cast<size_t>(byte_offset * 4u));
@@ -84,7 +85,7 @@ __device__ __forceinline__ RowFetch fetch_row(const FusedArgs& a, unsigned byte_
     } else {
         // the increment planes are read whether or not the launch treats them as zero (first outer iteration: they are valid planes
         // with stale contents) and the zero is selected when the row is committed: no branch around two loads in every step
-        return RowFetch{plane_load(a.f0, byte_offset), plane_load(a.f1, byte_offset), v2f{plane_load(a.u, byte_offset), plane_load(a.v, byte_offset)},
+        return RowFetch{plane_load(a.f0, byte_offset), plane_load(a.f1, byte_offset), v2f{plane_load(a.u, uv_offset), plane_load(a.v, uv_offset)},
                         v2f{plane_load(a.du, byte_offset), plane_load(a.dv, byte_offset)}};
     }
 }
@@ -100,6 +101,11 @@ __device__ __forceinline__ void store_row(const FusedArgs& a, unsigned byte_offs
 __device__ __forceinline__ unsigned row_offset(const FusedArgs& a, int row, int xc)
 {
     return (static_cast<unsigned>(row) * static_cast<unsigned>(a.pitch) + static_cast<unsigned>(xc)) * 4u;
+}
+// the same for (u, v): the shift applies to the row and the column AFTER their clamps (xch = xc >> uv_shift)
+__device__ __forceinline__ unsigned uv_row_offset(const FusedArgs& a, int row, int xch)
+{
+    return ((static_cast<unsigned>(row) >> a.uv_shift) * static_cast<unsigned>(a.pitch) + static_cast<unsigned>(xch)) * 4u;
 }
 
 // lane i receives lane i-1 (wave_shr:1) / lane i+1 (wave_shl:1); the end lanes of the wave receive 0
@@ -331,6 +337,12 @@ struct Strip {
     // continue_sweeps only: the sweeps' starting increment of row r-2 (start_cur) and the row fetched for the
     // next step (n_start)
     v2f start_cur, n_start;
+    // (u, v) of the row the next step fetches: its byte offset (a strip without EDGE: per lane, advanced by uv_step[parity of the step]
+    // -- the pitch in every step at full size, in every other step at half size, zero in the steps between; the row loop covers an
+    // even number of steps per turn, or swaps the two after a turn of an odd number, so the parity of a step is a constant of its
+    // body) or the lane's shifted column (EDGE: the row is clamped anew in every step)
+    unsigned uv_off, uv_step[2];
+    int xch;
     DivGuard guard;  // three-step division: operands outside the proven range leave their mark here
     // stamps probe: the wave's stalls at the row commit -- lane b of stall[0] counts those of floor(log2(cycles)) == b, lane b of
     // stall[1] adds their cycles up, lane p of stall[2] the cycles of the row steps 4 p .. 4 p + 3 of the strip
@@ -432,7 +444,16 @@ __device__ __forceinline__ void strip_step(Strip<INNER, GRAD>& s, const FusedArg
         //  its prefetch row needs no clamp: two scalar instructions less per step, each of which costs the wave an issue turn)
         // compute-only probe: every row folded onto eight cache-resident rows
         const int rn = probe::kComputeOnly ? (r + kAhead) & 7 : EDGE ? min(max(r + kAhead, 0), h - 1) : r + kAhead;
-        s.m = fetch_row(a, row_offset(a, rn, xc));
+        if (EDGE || probe::kComputeOnly) {
+            s.m = fetch_row(a, row_offset(a, rn, xc), uv_row_offset(a, rn, s.xch));
+        } else {
+            // step t of the strip (t = T in the start-up; in the row loop kPeel + i, i the step's place in the ring turn, up to whole
+            // turns) fetches row r_first + t + 2
+            constexpr int kPeel = 2 * INNER + 3;
+            constexpr int t_parity = (T >= 0 ? T : kPeel + (J - kPeel % kRing + kRing) % kRing) & 1;
+            s.m = fetch_row(a, row_offset(a, rn, xc), s.uv_off);
+            s.uv_off += s.uv_step[t_parity];
+        }
     }
     if constexpr (probe::kMemoryOnly) {  // the strip's loads and stores without its arithmetic
         const int rk = r - 2 - INNER;
@@ -776,8 +797,16 @@ __device__ __forceinline__ bool run_strip(const FusedArgs& a, int x, int xc, boo
     // first input row: the strip's first stored row needs INNER+1 rows of halo above it
     const int r_first = y0 - S::kHalo;
     {
-        s.n = fetch_row(a, row_offset(a, min(max(r_first, 0), a.h - 1), xc));
-        s.m = fetch_row(a, row_offset(a, min(max(r_first + 1, 0), a.h - 1), xc));
+        s.xch = xc >> a.uv_shift;
+        const int ra = min(max(r_first, 0), a.h - 1), rb = min(max(r_first + 1, 0), a.h - 1);
+        s.n = fetch_row(a, row_offset(a, ra, xc), uv_row_offset(a, ra, s.xch));
+        s.m = fetch_row(a, row_offset(a, rb, xc), uv_row_offset(a, rb, s.xch));
+        // a strip without EDGE fetches unclamped rows: step t takes row r_first + t + 2 and moves on to the next row's (u, v), which
+        // is the same row of a half-size plane when r_first + t + 3 is odd
+        s.uv_off = uv_row_offset(a, r_first + 2, s.xch);
+        const unsigned pitch_bytes = static_cast<unsigned>(a.pitch) * 4u;
+        s.uv_step[0] = (a.uv_shift == 0 || (r_first & 1) != 0) ? pitch_bytes : 0u;
+        s.uv_step[1] = (a.uv_shift == 0 || (r_first & 1) == 0) ? pitch_bytes : 0u;
         s.start_cur = s.n_start = v2f{0.f, 0.f};
         if (CONT) {  // the first step commits row r_first - 2 of the starting increment
             const size_t os = static_cast<size_t>(min(max(r_first - 2, 0), a.h - 1)) * a.pitch + xc;
@@ -797,6 +826,11 @@ __device__ __forceinline__ bool run_strip(const FusedArgs& a, int x, int xc, boo
     for (; r + S::kRing - 1 <= r_last; r += S::kRing) {
         strip_steps<INNER, GRAD, EDGE, POW2, CONT, FAST, SOR, kJ0>(s, a, r, x, xc, at_l, at_r, lane_stores, y0, y1, hx_2, hy_2,
                                                               std::make_index_sequence<S::kRing>{});
+        if constexpr ((S::kRing & 1) != 0) {  // (an odd turn: the next one starts at the other parity)
+            const unsigned other = s.uv_step[0];
+            s.uv_step[0] = s.uv_step[1];
+            s.uv_step[1] = other;
+        }
     }
     strip_tail<INNER, GRAD, EDGE, POW2, CONT, FAST, SOR, kJ0>(s, a, r, r_last, x, xc, at_l, at_r, lane_stores, y0, y1, hx_2, hy_2,
                                                          std::make_index_sequence<S::kRing - 1>{});

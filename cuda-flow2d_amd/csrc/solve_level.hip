@@ -35,7 +35,7 @@ int launch_fused_outer(flow2d_context* ctx, int constancy, const float* f0, cons
                        const float* v, const float* du, const float* dv, size_t w, size_t h, size_t pitch_bytes,
                        float hx, float hy, float alpha, float e_smooth, float e_data, size_t inner, float* out_du,
                        float* out_dv, int rows_per_strip, bool zero_increment, const float* start_du,
-                       const float* start_dv, float sor_omega);
+                       const float* start_dv, float sor_omega, int base_flow_shift);
 }  // namespace flow2d
 
 namespace {
@@ -112,6 +112,53 @@ static int solver_algorithm_for(int requested, size_t width, size_t height, size
     return requested;
 }
 
+// The algorithm flow2d_solve_level runs for these parameters (never AUTO), or the status it returns instead: everything it checks but
+// the planes, for flow2d_solve_level and flow2d_solve_level_takes_half_base alike.  Pure host logic: the
+// same answer for an eager run and while a graph is recorded.
+static int resolve_level_algorithm(const flow2d_solve_params* p, size_t instances, int& algorithm)
+{
+    if (p->width < 2 || p->height < 2 || p->container_height < p->height || !(p->hx > 0.f) || !(p->hy > 0.f))
+        return FLOW2D_ERR_INVALID_ARGUMENT;
+    if (p->data_constancy != FLOW2D_CONSTANCY_GREY && p->data_constancy != FLOW2D_CONSTANCY_GRADIENT &&
+        p->data_constancy != FLOW2D_CONSTANCY_GRADIENT_UNTILED && p->data_constancy != FLOW2D_CONSTANCY_LOG_DERIVATIVES)
+        return FLOW2D_ERR_UNSUPPORTED;
+    if (p->algorithm < FLOW2D_SOLVER_AUTO || p->algorithm > FLOW2D_SOLVER_TILED)
+        return FLOW2D_ERR_INVALID_ARGUMENT;
+    const bool sor = p->sor_omega != 0.f;
+    if (sor && (!(p->sor_omega > 0.f) || !(p->sor_omega < 2.f))) return FLOW2D_ERR_INVALID_ARGUMENT;
+    if (sor && p->data_constancy == FLOW2D_CONSTANCY_LOG_DERIVATIVES) return FLOW2D_ERR_UNSUPPORTED;
+    algorithm = solver_algorithm_for(p->algorithm, p->width, p->height, p->pitch_bytes, p->outer_iterations_count,
+                                     p->inner_iterations_count, p->data_constancy, instances);
+    // Red-black SOR (opt-in): temporally blocked in the strip kernel and in the LDS tiles with half-sweeps for stages (round 5: one
+    // launch per two iterations instead of a phi / ksi launch and two half-sweep launches per iteration).  AUTO picks tiles or
+    // strips by the level's size like for Jacobi (the tiles up to two iterations per outer iteration; the single-workgroup kernel
+    // has no such stages); only what the strips cannot address, or an explicit request, takes the half-sweep launches.
+    if (sor) {
+        // stages of a launch = half-sweeps: the tiles hold up to four (two iterations), the strips chain launches of four
+        const size_t stages = 2 * p->inner_iterations_count;
+        const bool can_fuse = p->inner_iterations_count >= 1 && flow2d::fused_addressable(p->height, p->pitch_bytes);
+        const bool can_tile = p->inner_iterations_count >= 1 && stages <= 4 && flow2d::tiled_supports(p->data_constancy, stages);
+        const bool auto_tiles = can_tile && solver_algorithm_for(FLOW2D_SOLVER_AUTO, p->width, p->height, p->pitch_bytes,
+                                                                 p->outer_iterations_count, stages, p->data_constancy,
+                                                                 instances) == FLOW2D_SOLVER_TILED;
+        if (p->algorithm == FLOW2D_SOLVER_FUSED && !can_fuse) return FLOW2D_ERR_UNSUPPORTED;
+        if (p->algorithm == FLOW2D_SOLVER_TILED && !can_tile) return FLOW2D_ERR_UNSUPPORTED;
+        if (p->algorithm == FLOW2D_SOLVER_SINGLE_WORKGROUP) return FLOW2D_ERR_UNSUPPORTED;
+        if (p->algorithm == FLOW2D_SOLVER_AUTO)
+            algorithm = auto_tiles ? FLOW2D_SOLVER_TILED : (can_fuse ? FLOW2D_SOLVER_FUSED : FLOW2D_SOLVER_PER_SWEEP);
+        else
+            algorithm = p->algorithm;
+    }
+    if (algorithm < 0) return FLOW2D_ERR_UNSUPPORTED;
+    // the strips multiply with half the neighbour weight alpha / h^2, which must be exactly representable (solve_fused.hip)
+    if (algorithm == FLOW2D_SOLVER_FUSED && !flow2d::fused_weights_ok(p->hx, p->hy, p->equation_alpha)) {
+        if (p->algorithm == FLOW2D_SOLVER_FUSED) return FLOW2D_ERR_UNSUPPORTED;
+        algorithm = FLOW2D_SOLVER_PER_SWEEP;
+    }
+
+    return FLOW2D_OK;
+}
+
 extern "C" {
 
 // The algorithm flow2d_solve_level runs for a request (never AUTO) on a single pair, or -1 when the requested one cannot
@@ -130,49 +177,19 @@ int flow2d_solve_level(flow2d_context* ctx, const float* frame_0, const float* f
     if (!p || !result_in_temp) return FLOW2D_ERR_INVALID_ARGUMENT;
     const float* planes[] = {frame_0, frame_1, flow_u, flow_v, flow_du, flow_dv, phi, ksi, temp_du, temp_dv};
     for (int i = 0; i < 10; ++i) {
+        // (flow_u and flow_v hold fewer rows and columns with base_flow_shift = 1; what is checked here does not depend on that)
         if (!flow2d::plane_args_ok(planes[i], p->width, p->height, p->pitch_bytes)) return FLOW2D_ERR_INVALID_ARGUMENT;
         for (int j = 4; j < 10; ++j)  // the six written planes must be distinct from everything else
             if (i != j && planes[i] == planes[j]) return FLOW2D_ERR_INVALID_ARGUMENT;
     }
-    if (p->width < 2 || p->height < 2 || p->container_height < p->height || !(p->hx > 0.f) || !(p->hy > 0.f))
-        return FLOW2D_ERR_INVALID_ARGUMENT;
-    if (p->data_constancy != FLOW2D_CONSTANCY_GREY && p->data_constancy != FLOW2D_CONSTANCY_GRADIENT &&
-        p->data_constancy != FLOW2D_CONSTANCY_GRADIENT_UNTILED && p->data_constancy != FLOW2D_CONSTANCY_LOG_DERIVATIVES)
-        return FLOW2D_ERR_UNSUPPORTED;
-    if (p->algorithm < FLOW2D_SOLVER_AUTO || p->algorithm > FLOW2D_SOLVER_TILED)
-        return FLOW2D_ERR_INVALID_ARGUMENT;
-
     const bool sor = p->sor_omega != 0.f;
-    if (sor && (!(p->sor_omega > 0.f) || !(p->sor_omega < 2.f))) return FLOW2D_ERR_INVALID_ARGUMENT;
-    if (sor && p->data_constancy == FLOW2D_CONSTANCY_LOG_DERIVATIVES) return FLOW2D_ERR_UNSUPPORTED;
-    int algorithm = solver_algorithm_for(p->algorithm, p->width, p->height, p->pitch_bytes, p->outer_iterations_count,
-                                         p->inner_iterations_count, p->data_constancy, ctx->batch_count);
-    // Red-black SOR (opt-in): temporally blocked in the strip kernel and in the LDS tiles with half-sweeps for stages (round 5: one
-    // launch per two iterations instead of a phi / ksi launch and two half-sweep launches per iteration).  AUTO picks tiles or
-    // strips by the level's size like for Jacobi (the tiles up to two iterations per outer iteration; the single-workgroup kernel
-    // has no such stages); only what the strips cannot address, or an explicit request, takes the half-sweep launches.
-    if (sor) {
-        // stages of a launch = half-sweeps: the tiles hold up to four (two iterations), the strips chain launches of four
-        const size_t stages = 2 * p->inner_iterations_count;
-        const bool can_fuse = p->inner_iterations_count >= 1 && flow2d::fused_addressable(p->height, p->pitch_bytes);
-        const bool can_tile = p->inner_iterations_count >= 1 && stages <= 4 && flow2d::tiled_supports(p->data_constancy, stages);
-        const bool auto_tiles = can_tile && solver_algorithm_for(FLOW2D_SOLVER_AUTO, p->width, p->height, p->pitch_bytes,
-                                                                 p->outer_iterations_count, stages, p->data_constancy,
-                                                                 ctx->batch_count) == FLOW2D_SOLVER_TILED;
-        if (p->algorithm == FLOW2D_SOLVER_FUSED && !can_fuse) return FLOW2D_ERR_UNSUPPORTED;
-        if (p->algorithm == FLOW2D_SOLVER_TILED && !can_tile) return FLOW2D_ERR_UNSUPPORTED;
-        if (p->algorithm == FLOW2D_SOLVER_SINGLE_WORKGROUP) return FLOW2D_ERR_UNSUPPORTED;
-        if (p->algorithm == FLOW2D_SOLVER_AUTO)
-            algorithm = auto_tiles ? FLOW2D_SOLVER_TILED : (can_fuse ? FLOW2D_SOLVER_FUSED : FLOW2D_SOLVER_PER_SWEEP);
-        else
-            algorithm = p->algorithm;
+    int algorithm = -1;
+    {
+        const int status = resolve_level_algorithm(p, ctx->batch_count, algorithm);
+        if (status != FLOW2D_OK) return status;
     }
-    if (algorithm < 0) return FLOW2D_ERR_UNSUPPORTED;
-    // the strips multiply with half the neighbour weight alpha / h^2, which must be exactly representable (solve_fused.hip)
-    if (algorithm == FLOW2D_SOLVER_FUSED && !flow2d::fused_weights_ok(p->hx, p->hy, p->equation_alpha)) {
-        if (p->algorithm == FLOW2D_SOLVER_FUSED) return FLOW2D_ERR_UNSUPPORTED;
-        algorithm = FLOW2D_SOLVER_PER_SWEEP;
-    }
+    // a half-size base flow is read by the strips only
+    if (p->base_flow_shift != 0 && (p->base_flow_shift != 1 || algorithm != FLOW2D_SOLVER_FUSED)) return FLOW2D_ERR_UNSUPPORTED;
 
     flow2d_timing_slot* slot = nullptr;
     if (ctx->timing) {
@@ -241,7 +258,7 @@ int flow2d_solve_level(flow2d_context* ctx, const float* frame_0, const float* f
                                                 p->equation_alpha, p->equation_smoothness, p->equation_data,
                                                 sor ? 2 * sweeps : sweeps, pair_u[out], pair_v[out], rows, i == 0,
                                                 c == 0 ? nullptr : pair_u[in], c == 0 ? nullptr : pair_v[in],
-                                                sor ? p->sor_omega : 0.f);
+                                                sor ? p->sor_omega : 0.f, p->base_flow_shift);
             if (st != FLOW2D_OK) return st;
             if (per_launch) FLOW2D_HIP_TRY(mark(ctx, slot));
             in = out;
@@ -325,6 +342,16 @@ int flow2d_solve_level(flow2d_context* ctx, const float* frame_0, const float* f
         slot->rec.algorithmic_bytes_per_launch = per_px * static_cast<double>(p->width) * static_cast<double>(p->height);
     }
     return FLOW2D_OK;
+}
+
+// Whether flow2d_solve_level would run these parameters with base_flow_shift = 1 (the field itself is not looked at): the level
+// resolves to the strips on this context -- its lock-step group counts -- and its planes are within their 32-bit offsets.
+int flow2d_solve_level_takes_half_base(flow2d_context* ctx, const flow2d_solve_params* p)
+{
+    if (!ctx || !p || p->outer_iterations_count == 0) return 0;  // (no outer iteration: no strip launch at all)
+    int algorithm = -1;
+    if (resolve_level_algorithm(p, ctx->batch_count, algorithm) != FLOW2D_OK) return 0;
+    return algorithm == FLOW2D_SOLVER_FUSED && flow2d::fused_addressable(p->height, p->pitch_bytes) ? 1 : 0;
 }
 
 int flow2d_timing_enable(flow2d_context* ctx, int mode)

@@ -111,6 +111,15 @@ void CudaOperationMedian2D::Execute(OperationParameters& params)
     DevicePtr dev_addend = 0, dev_addend_b = 0;
     const bool sum = params.Read<DevicePtr>("dev_addend", dev_addend) && (!pair || params.Read<DevicePtr>("dev_addend_b", dev_addend_b));
     const size_t window = (radius != 1 && radius % 2 == 0) ? radius - 1 : radius;
+    // optional (not in the reference's bag): dev_input / dev_input_b are held at half the size in both directions and read at
+    // [y >> 1][x >> 1] (an exactly doubled pyramid level: flow2d_upsample_registration_half_2d); with addends and a window only
+    int base_flow_shift = 0;
+    params.Read<int>("base_flow_shift", base_flow_shift);
+    if (base_flow_shift != 0 && !(base_flow_shift == 1 && sum && window >= 3 && window <= 7)) {
+        std::printf("Operation '%s': Error. A half-size input needs addends and a window of 3, 5 or 7.", GetName());
+        failed_ = true;
+        return;
+    }
     if (sum && !(window >= 3 && window <= 7)) {  // nothing to fuse into: add in place, then the plain path
         if (pair)
             Failed(flow2d_add_2d_pair(context_, AsPlane(dev_input), AsPlane(dev_addend), AsPlane(dev_input_b), AsPlane(dev_addend_b),
@@ -133,7 +142,13 @@ void CudaOperationMedian2D::Execute(OperationParameters& params)
         std::printf("Warning. Median raduis is even (%zu), decresaing by 1...\n", radius);
         radius -= 1;
     }
-    if (radius >= 3 && radius <= 7 && sum) {
+    if (radius >= 3 && radius <= 7 && sum && base_flow_shift) {
+        Failed(flow2d_add_median_2d_pair_half(context_, AsPlane(dev_input), AsPlane(dev_addend), pair ? AsPlane(dev_input_b) : nullptr,
+                                              pair ? AsPlane(dev_addend_b) : nullptr, data_size.width, data_size.height,
+                                              dev_container_size_.pitch, radius, AsPlane(dev_output),
+                                              pair ? AsPlane(dev_output_b) : nullptr),
+               "flow2d_add_median_2d_pair_half");
+    } else if (radius >= 3 && radius <= 7 && sum) {
         Failed(flow2d_add_median_2d_pair(context_, AsPlane(dev_input), AsPlane(dev_addend), pair ? AsPlane(dev_input_b) : nullptr,
                                          pair ? AsPlane(dev_addend_b) : nullptr, data_size.width, data_size.height,
                                          dev_container_size_.pitch, radius, AsPlane(dev_output),
@@ -278,6 +293,8 @@ void CudaOperationSolve2D::Execute(OperationParameters& params)
     params.Read<int>("solver_algorithm", algorithm);
     float sor_omega = 0.f;  // superset key: opt-in red-black SOR instead of the reference's Jacobi sweeps
     params.Read<float>("solver_sor_omega", sor_omega);
+    // superset key: dev_flow_u / dev_flow_v are held at half the size in both directions (flow2d_solve_params::base_flow_shift)
+    params.Read<int>("base_flow_shift", p.base_flow_shift);
 
     // The reference picks the sweep kernel at Initialize and only the LDS size at Execute
     // (cuda_operation_solve_2d.cpp:65-82,181-198); the kernel chosen at Initialize wins.

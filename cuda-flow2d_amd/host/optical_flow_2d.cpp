@@ -914,14 +914,34 @@ bool OpticalFlow2D::RunPyramid(OperationParameters& params)
         // same values in one launch -- (u, v) handed on in registers instead of through their planes; at the coarsest level the
         // zeros, over the level's region instead of two memsets of the whole container).
         const bool upsample = prev_size.width != 0;
+        // A level exactly twice the previous one whose solver is the strips keeps its base flow (u, v) at the PREVIOUS level's size: at
+        // such a level the up-sampled flow is a replication, so the warp stores one value per 2 x 2 block and the strips and the
+        // median read [y >> 1][x >> 1] -- the same values, the same bits, a quarter of the bytes written once and read eleven times.
+        // Decided here, from the geometry and the solver's own answer, before any launch: the same for an eager run and a recording.
+        int base_flow_shift = 0;
+        if (upsample && current_size.width == 2 * prev_size.width && current_size.height == 2 * prev_size.height) {
+            flow2d_solve_params probe{};
+            probe.width = current_size.width, probe.height = current_size.height;
+            probe.pitch_bytes = dev_container_size_.pitch, probe.container_height = dev_container_size_.height;
+            probe.hx = hx, probe.hy = hy;
+            probe.equation_alpha = equation_alpha, probe.equation_smoothness = equation_smoothness, probe.equation_data = equation_data;
+            probe.outer_iterations_count = outer_iterations_count, probe.inner_iterations_count = inner_iterations_count;
+            probe.data_constancy = data_constancy_ == DataConstancy::Gradient          ? FLOW2D_CONSTANCY_GRADIENT
+                                   : data_constancy_ == DataConstancy::LogDerivatives  ? FLOW2D_CONSTANCY_LOG_DERIVATIVES
+                                   : data_constancy_ == DataConstancy::GradientUntiled ? FLOW2D_CONSTANCY_GRADIENT_UNTILED
+                                                                                       : FLOW2D_CONSTANCY_GREY;
+            probe.algorithm = solver_algorithm, probe.sor_omega = solver_sor_omega;
+            const size_t window = (median_radius != 1 && median_radius % 2 == 0) ? median_radius - 1 : median_radius;
+            if (window >= 3 && window <= 7 && flow2d_solve_level_takes_half_base(context_, &probe)) base_flow_shift = 1;
+        }
         // backward registration of `level_1` by the level's flow into `output` (after bringing the flow to the level's size)
         auto warp = [&](DevicePtr level_0, DevicePtr level_1, DevicePtr output) {
             int err;
             if (upsample) {
-                err = flow2d_upsample_registration_2d(context_, AsPlane(flow_u), AsPlane(flow_v), prev_size.width, prev_size.height,
-                                                      AsPlane(flow_du), AsPlane(flow_dv), AsPlane(level_0), AsPlane(level_1),
-                                                      current_size.width, current_size.height, dev_container_size_.pitch, hx, hy,
-                                                      AsPlane(output));
+                err = (base_flow_shift ? flow2d_upsample_registration_half_2d : flow2d_upsample_registration_2d)(
+                    context_, AsPlane(flow_u), AsPlane(flow_v), prev_size.width, prev_size.height, AsPlane(flow_du), AsPlane(flow_dv),
+                    AsPlane(level_0), AsPlane(level_1), current_size.width, current_size.height, dev_container_size_.pitch, hx, hy,
+                    AsPlane(output));
                 std::swap(flow_u, flow_du);
                 std::swap(flow_v, flow_dv);
             } else {
@@ -929,7 +949,8 @@ bool OpticalFlow2D::RunPyramid(OperationParameters& params)
                                                       AsPlane(level_1), current_size.width, current_size.height,
                                                       dev_container_size_.pitch, hx, hy, AsPlane(output));
             }
-            if (CheckFlow2DError(err, "flow2d_upsample_registration_2d")) failed = true;
+            if (CheckFlow2DError(err, upsample && base_flow_shift ? "flow2d_upsample_registration_half_2d" : "flow2d_upsample_registration_2d"))
+                failed = true;
         };
 
         DevicePtr solve_frame_0 = frame_0_res;  // what the solver reads as frame 0 of this level
@@ -974,6 +995,7 @@ bool OpticalFlow2D::RunPyramid(OperationParameters& params)
             op.PushValuePtr("hy", &hy);
             op.PushValuePtr("solver_algorithm", &solver_algorithm);
             op.PushValuePtr("solver_sor_omega", &solver_sor_omega);
+            if (base_flow_shift) op.PushValuePtr("base_flow_shift", &base_flow_shift);
             cuop_solve_.silent = true;  // per-level printing would need a host wait; timings are collected instead
             cuop_solve_.Execute(op);
             failed |= cuop_solve_.TakeFailure();
@@ -1001,6 +1023,7 @@ bool OpticalFlow2D::RunPyramid(OperationParameters& params)
             op.PushValuePtr("dev_addend_b", &flow_dv);
             op.PushValuePtr("data_size", &current_size);
             op.PushValuePtr("radius", &median_radius);
+            if (base_flow_shift) op.PushValuePtr("base_flow_shift", &base_flow_shift);
             cuop_median_.Execute(op);
             failed |= cuop_median_.TakeFailure();
             if (!deliver) {

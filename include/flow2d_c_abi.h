@@ -869,6 +869,20 @@ FLOW2D_API int flow2d_upsample_registration_2d(flow2d_context* ctx, const float*
                                                size_t in_height, float* out_u, float* out_v, const float* frame_0,
                                                const float* frame_1, size_t width, size_t height, size_t pitch_bytes, float hx,
                                                float hy, float* output);
+/* The same at an exactly doubled level (width = 2 in_width, height = 2 in_height; anything else FLOW2D_ERR_UNSUPPORTED) with
+ * out_u / out_v kept at in_width x in_height.  At such a level the resampled flow is a replication: each 2 x 2 block of pixels
+ * holds one input pixel's value after the resample's four multiplications (not the identity: -0 becomes +0, denormals round).
+ * out[y][x] is that value, i.e. what flow2d_upsample_registration_2d stores at (2y .. 2y + 1, 2x .. 2x + 1); `output` is that
+ * entry's warped frame bit for bit.  Readers of the level index the planes with (y >> 1, x >> 1): flow2d_solve_level with
+ * base_flow_shift = 1, flow2d_add_median_2d_pair_half.  No written byte range may meet a read one or another written one, over
+ * every instance of a batch (FLOW2D_ERR_INVALID_ARGUMENT). */
+FLOW2D_API int flow2d_upsample_registration_half_2d(flow2d_context* ctx, const float* flow_u, const float* flow_v, size_t in_width,
+                                                    size_t in_height, float* out_u, float* out_v, const float* frame_0,
+                                                    const float* frame_1, size_t width, size_t height, size_t pitch_bytes,
+                                                    float hx, float hy, float* output);
+/* launches of flow2d_upsample_registration_half_2d queued by this process so far: tells which path a pyramid took (the host
+ * layer takes it at every level that is exactly twice the previous one and solved by the strips) */
+FLOW2D_API unsigned long long flow2d_half_base_flow_launches(void);
 
 /* resample_x / resample_y (src/kernels/resample_2d.cu:34-75,77-118): area-weighted 1-D resample. */
 FLOW2D_API int flow2d_resample_x(flow2d_context* ctx, const float* input, float* output, size_t out_width,
@@ -894,6 +908,15 @@ FLOW2D_API int flow2d_median_2d_pair(flow2d_context* ctx, const float* input_a, 
 FLOW2D_API int flow2d_add_median_2d_pair(flow2d_context* ctx, const float* input_a, const float* addend_a,
                                          const float* input_b, const float* addend_b, size_t width, size_t height,
                                          size_t pitch_bytes, size_t window, float* output_a, float* output_b);
+/* flow2d_add_median_2d_pair with the INPUT planes held at half the size in both directions, (height + 1) / 2 rows of
+ * (width + 1) / 2 pixels in the same pitch: pixel (y, x) of the sum is input[y >> 1][x >> 1] + addend[y][x], the borders mirrored
+ * before the shift.  What that entry returns for the input replicated to width x height, bit for bit (NaN and -0 windows
+ * included), without the replicated planes: the median after an exactly doubled pyramid level, whose base flow
+ * flow2d_upsample_registration_half_2d left at the previous level's size.  No output byte range may meet an input's or an
+ * addend's, over every instance of a batch (FLOW2D_ERR_INVALID_ARGUMENT). */
+FLOW2D_API int flow2d_add_median_2d_pair_half(flow2d_context* ctx, const float* input_a, const float* addend_a,
+                                              const float* input_b, const float* addend_b, size_t width, size_t height,
+                                              size_t pitch_bytes, size_t window, float* output_a, float* output_b);
 FLOW2D_API int flow2d_resample_x_pair(flow2d_context* ctx, const float* input_a, float* output_a,
                                       const float* input_b, float* output_b, size_t out_width, size_t out_height,
                                       size_t in_width, size_t pitch_bytes);
@@ -1038,6 +1061,11 @@ typedef struct flow2d_solve_params {
                                     FUSED / TILED (at most two iterations per outer iteration) ask for one of the two,
                                     PER_SWEEP for two half-sweep launches per iteration, in place; SINGLE_WORKGROUP and
                                     the LogDerivatives term have no red-black form (FLOW2D_ERR_UNSUPPORTED). */
+    int base_flow_shift;         /* 0 (default): flow_u / flow_v are width x height planes.  1: they are held at half the size
+                                    in both directions -- pixel (y, x) reads them at (y >> 1, x >> 1), same pitch -- as
+                                    flow2d_upsample_registration_half_2d leaves them; the same result as with the replicated
+                                    planes, bit for bit.  With the strips only (algorithm resolves to FLOW2D_SOLVER_FUSED);
+                                    anything else, or another value, FLOW2D_ERR_UNSUPPORTED before any launch. */
 } flow2d_solve_params;
 
 /* Which algorithm flow2d_solve_level runs for a request: `requested` resolved (AUTO -> one of the four), or -1 when the
@@ -1052,6 +1080,11 @@ FLOW2D_API int flow2d_solve_level(flow2d_context* ctx, const float* frame_0, con
                                   const float* flow_u, const float* flow_v, float* flow_du, float* flow_dv,
                                   float* phi, float* ksi, float* temp_du, float* temp_dv,
                                   const flow2d_solve_params* params, int* result_in_temp);
+
+/* Whether flow2d_solve_level runs these parameters with base_flow_shift = 1 (the field itself is not looked at): 1 when the level
+ * resolves to the strips on this context -- AUTO gives a lock-step group fewer levels to the tiles, so the context's group
+ * counts --, 0 otherwise.  Host logic only: the same answer for an eager run and while a graph is recorded. */
+FLOW2D_API int flow2d_solve_level_takes_half_base(flow2d_context* ctx, const flow2d_solve_params* params);
 
 /* ---- launch timing of the solver (measurement only; bench.py's roofline leg) ----------------
  * mode 1: every flow2d_solve_level call is bracketed by a pair of events on the context's stream
