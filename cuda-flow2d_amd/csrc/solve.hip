@@ -15,7 +15,7 @@
 #include <algorithm>
 #include <cstdlib>
 
-#include "common.hpp"
+#include "solver.hpp"
 #include "solver_math.hpp"
 
 namespace {
@@ -609,163 +609,145 @@ bool solver_planes_ok(const float* const* planes, int count, size_t w, size_t h,
     return w >= 2 && h >= 2;
 }
 
-}  // namespace
-
-namespace flow2d {
-
-int launch_phi_ksi(flow2d_context* ctx, const float* f0, const float* f1, const float* u, const float* v,
-                   const float* du, const float* dv, size_t w, size_t h, size_t pitch_bytes, float hx, float hy,
-                   float e_smooth, float e_data, float* phi, float* ksi)
-{
-    if (ctx->batch_count > 1) {  // the per-sweep kernels are not batched: one launch per instance
-        const unsigned n = ctx->batch_count;
-        const size_t s = ctx->batch_stride_floats;
-        ctx->batch_count = 1;
-        int st = FLOW2D_OK;
-        for (unsigned b = 0; b < n && st == FLOW2D_OK; ++b)
-            st = launch_phi_ksi(ctx, f0 + b * s, f1 + b * s, u + b * s, v + b * s, du + b * s, dv + b * s, w, h,
-                                pitch_bytes, hx, hy, e_smooth, e_data, phi + b * s, ksi + b * s);
-        ctx->batch_count = n;
-        return st;
-    }
-    const XcdTiles tiles = xcd_tiles(div_up(w, kBlockX), div_up(h, kBlockY));
-        const dim3 grid(xcd_grid(tiles));
-    phi_ksi_kernel<<<grid, dim3(kBlockX, kBlockY), 0, ctx->stream>>>(f0, f1, u, v, du, dv, tiles, (int)w, (int)h,
-                                                                     (int)(pitch_bytes / 4), hx, hy, e_smooth, e_data,
-                                                                     phi, ksi);
-    FLOW2D_CHECK_LAUNCH();
-    return FLOW2D_OK;
-}
+// The tile forms of a data term, Jacobi and red-black half-sweep: the kernel and its block height (the block is kBlockX wide).
+using SweepKernel = void (*)(const float*, const float*, const float*, const float*, const float*, const float*, const float*,
+                             const float*, XcdTiles, int, int, int, float, float, float, float*, float*);
+using SorKernel = void (*)(const float*, const float*, const float*, const float*, float*, float*, const float*, const float*,
+                           XcdTiles, int, int, int, float, float, float, float, int);
+struct SweepForm {
+    SweepKernel sweep;
+    SorKernel sor;  // (none of the log-derivative term: the entries refuse it)
+    int block_y;
+};
+const SweepForm kSweepForms[4] = {
+    {sweep_grey_kernel, sor_grey_kernel, kBlockY},                  // FLOW2D_CONSTANCY_GREY
+    {sweep_grad_kernel, sor_grad_kernel, kGradTileY},               // FLOW2D_CONSTANCY_GRADIENT
+    {sweep_grad_untiled_kernel, sor_grad_untiled_kernel, kBlockY},  // FLOW2D_CONSTANCY_GRADIENT_UNTILED
+    {sweep_log_kernel, nullptr, kGradTileY},                        // FLOW2D_CONSTANCY_LOG_DERIVATIVES
+};
 
 // levels of 8 Mpixel and more (below, the ten planes sit in the Infinity Cache and the short-lived waves of the tile forms are faster)
-static bool sweep_streams(size_t w, size_t h) { return w >= 2 * kSweepValid && h >= 8 && w * h >= kSweepStreamMinPixels; }
+bool sweep_streams(size_t w, size_t h) { return w >= 2 * kSweepValid && h >= 8 && w * h >= kSweepStreamMinPixels; }
 // (rows per strip, round 6: 16 / 32 / 64 rows fetch 718 / 655 / 626 MB per 4096^2 sweep -- the halo rows of a strip are re-read by
 //  its neighbour -- for 537 MB of algorithmic reads, and take 155.6 / 152.7-155.8 / 165-167 us on one box, 158-161 / 162-165 us on
 //  another (8192^2: 555-573 / 569-602 us): the bytes 32 rows save come out of the caches, the time they cost does not -- 16 stays;
 //  profiles/r06_experiments/per_sweep_strip_rows_ab*.txt)
-static unsigned sweep_strip_rows()
+unsigned sweep_strip_rows()
 {
 #ifdef FLOW2D_DEV_BUILD  // (developer builds: strip height override, a multiple of 16)
     if (const char* e = std::getenv("FLOW2D_SWEEP_ROWS")) return std::max(16, std::atoi(e) / 16 * 16);
 #endif
     return 16;
 }
-static XcdTiles sweep_stream_tiles(size_t w, size_t h, int constancy)
+
+// The streaming form of a data term: the constancy as the kernel's MODE.
+template <bool SOR>
+auto sweep_stream_for(int constancy) -> decltype(&sweep_stream_kernel<0, SOR>)
 {
-    const unsigned valid = constancy == FLOW2D_CONSTANCY_GREY ? kSweepValid : kSweepValid - 2;  // (the gradient terms: two halo lanes per side)
-    return xcd_tiles(div_up(div_up(w, valid), 4), div_up(h, sweep_strip_rows()));
+    if (constancy == FLOW2D_CONSTANCY_GRADIENT) return sweep_stream_kernel<1, SOR>;
+    if (constancy == FLOW2D_CONSTANCY_GRADIENT_UNTILED) return sweep_stream_kernel<2, SOR>;
+    if constexpr (!SOR)
+        if (constancy == FLOW2D_CONSTANCY_LOG_DERIVATIVES) return sweep_stream_kernel<3, false>;
+    return sweep_stream_kernel<0, SOR>;
 }
 
-int launch_sweep(flow2d_context* ctx, int constancy, const float* f0, const float* f1, const float* u, const float* v,
-                 const float* du, const float* dv, const float* phi, const float* ksi, size_t w, size_t h,
-                 size_t pitch_bytes, float hx, float hy, float alpha, float* tdu, float* tdv)
+// streaming form: strips of 62 columns (60: the gradient terms), four to a workgroup, 16 rows to a strip: the two halo
+// rows of a strip are its y neighbours' rows, which the XCD-aware tile order keeps in the same L2.  (us per 4096^2 /
+// 8192^2 Grey sweep by strip height, one box: 8 rows 169 / 570, 16 160 / 564, 24 160 / 615, 33 167 / 610, 64 168 / 617,
+// 128 171 / 599, 256 190 / 630.)
+template <bool SOR>
+void launch_sweep_stream(const flow2d_context* ctx, const flow2d::SolveLevel& l, flow2d::ConstPair d, flow2d::ConstPair coeff,
+                         flow2d::Pair out, float omega, int colour)
 {
-    if (ctx->batch_count > 1) {
-        const unsigned n = ctx->batch_count;
-        const size_t s = ctx->batch_stride_floats;
-        ctx->batch_count = 1;
-        int st = FLOW2D_OK;
-        for (unsigned b = 0; b < n && st == FLOW2D_OK; ++b)
-            st = launch_sweep(ctx, constancy, f0 + b * s, f1 + b * s, u + b * s, v + b * s, du + b * s, dv + b * s,
-                              phi + b * s, ksi + b * s, w, h, pitch_bytes, hx, hy, alpha, tdu + b * s, tdv + b * s);
-        ctx->batch_count = n;
-        return st;
-    }
-    if (sweep_streams(w, h)) {
-        // streaming form: strips of 62 columns (60: the gradient terms), four to a workgroup, 16 rows to a strip: the two halo
-        // rows of a strip are its y neighbours' rows, which the XCD-aware tile order keeps in the same L2.  (us per 4096^2 /
-        // 8192^2 Grey sweep by strip height, one box: 8 rows 169 / 570, 16 160 / 564, 24 160 / 615, 33 167 / 610, 64 168 / 617,
-        // 128 171 / 599, 256 190 / 630.)
-        const XcdTiles tiles = sweep_stream_tiles(w, h, constancy);
-        const SweepPlanes planes{f0, f1, u, v, du, dv, phi, ksi};
-        const dim3 grid(xcd_grid(tiles));
-        const int iw = (int)w, ih = (int)h, ip = (int)(pitch_bytes / 4), rows = (int)sweep_strip_rows();
-        if (constancy == FLOW2D_CONSTANCY_GRADIENT)
-            sweep_stream_kernel<1, false><<<grid, 256, 0, ctx->stream>>>(planes, tiles, iw, ih, ip, rows, hx, hy, alpha, tdu, tdv, 1.f, 0);
-        else if (constancy == FLOW2D_CONSTANCY_GRADIENT_UNTILED)
-            sweep_stream_kernel<2, false><<<grid, 256, 0, ctx->stream>>>(planes, tiles, iw, ih, ip, rows, hx, hy, alpha, tdu, tdv, 1.f, 0);
-        else if (constancy == FLOW2D_CONSTANCY_LOG_DERIVATIVES)
-            sweep_stream_kernel<3, false><<<grid, 256, 0, ctx->stream>>>(planes, tiles, iw, ih, ip, rows, hx, hy, alpha, tdu, tdv, 1.f, 0);
-        else
-            sweep_stream_kernel<0, false><<<grid, 256, 0, ctx->stream>>>(planes, tiles, iw, ih, ip, rows, hx, hy, alpha, tdu, tdv, 1.f, 0);
-    } else if (constancy == FLOW2D_CONSTANCY_GRADIENT) {
-        const XcdTiles tiles = xcd_tiles(div_up(w, kBlockX), div_up(h, kGradTileY));
-        const dim3 grid(xcd_grid(tiles));
-        sweep_grad_kernel<<<grid, dim3(kBlockX, kGradTileY), 0, ctx->stream>>>(
-            f0, f1, u, v, du, dv, phi, ksi, tiles, (int)w, (int)h, (int)(pitch_bytes / 4), hx, hy, alpha, tdu, tdv);
-    } else if (constancy == FLOW2D_CONSTANCY_LOG_DERIVATIVES) {
-        const XcdTiles tiles = xcd_tiles(div_up(w, kBlockX), div_up(h, kGradTileY));
-        const dim3 grid(xcd_grid(tiles));
-        sweep_log_kernel<<<grid, dim3(kBlockX, kGradTileY), 0, ctx->stream>>>(
-            f0, f1, u, v, du, dv, phi, ksi, tiles, (int)w, (int)h, (int)(pitch_bytes / 4), hx, hy, alpha, tdu, tdv);
-    } else if (constancy == FLOW2D_CONSTANCY_GRADIENT_UNTILED) {
-        const XcdTiles tiles = xcd_tiles(div_up(w, kBlockX), div_up(h, kBlockY));
-        const dim3 grid(xcd_grid(tiles));
-        sweep_grad_untiled_kernel<<<grid, dim3(kBlockX, kBlockY), 0, ctx->stream>>>(
-            f0, f1, u, v, du, dv, phi, ksi, tiles, (int)w, (int)h, (int)(pitch_bytes / 4), hx, hy, alpha, tdu, tdv);
+    using flow2d::div_up;
+    const unsigned valid = l.constancy == FLOW2D_CONSTANCY_GREY ? kSweepValid : kSweepValid - 2;  // (the gradient terms: two halo lanes per side)
+    const XcdTiles tiles = xcd_tiles(div_up(div_up(l.w, valid), 4), div_up(l.h, sweep_strip_rows()));
+    const SweepPlanes planes{l.f0, l.f1, l.u, l.v, d.du, d.dv, coeff.du, coeff.dv};
+    const auto kernel = sweep_stream_for<SOR>(l.constancy);
+    kernel<<<dim3(xcd_grid(tiles)), 256, 0, ctx->stream>>>(
+        planes, tiles, (int)l.w, (int)l.h, (int)(l.pitch_bytes / 4), (int)sweep_strip_rows(), l.hx, l.hy, l.alpha, out.du, out.dv,
+        omega, colour);
+}
+
+// the tile forms' grid: one workgroup per kBlockX x block_y pixels, XCD-aware
+XcdTiles sweep_tiles(const flow2d::SolveLevel& l, int block_y)
+{
+    return xcd_tiles(flow2d::div_up(l.w, kBlockX), flow2d::div_up(l.h, block_y));
+}
+
+const SweepForm& sweep_form(int constancy)
+{
+    return kSweepForms[constancy >= 0 && constancy < 4 ? constancy : FLOW2D_CONSTANCY_GREY];
+}
+
+// The launches of ONE pair (the per-sweep kernels are not batched: flow2d::for_each_instance).
+int phi_ksi_one(const flow2d_context* ctx, const flow2d::SolveLevel& l, flow2d::ConstPair d, flow2d::Pair coeff)
+{
+    const XcdTiles tiles = sweep_tiles(l, kBlockY);
+    phi_ksi_kernel<<<dim3(xcd_grid(tiles)), dim3(kBlockX, kBlockY), 0, ctx->stream>>>(
+        l.f0, l.f1, l.u, l.v, d.du, d.dv, tiles, (int)l.w, (int)l.h, (int)(l.pitch_bytes / 4), l.hx, l.hy, l.e_smooth, l.e_data,
+        coeff.du, coeff.dv);
+    FLOW2D_CHECK_LAUNCH();
+    return FLOW2D_OK;
+}
+
+int sweep_one(const flow2d_context* ctx, const flow2d::SolveLevel& l, flow2d::ConstPair d, flow2d::ConstPair coeff, flow2d::Pair out)
+{
+    if (sweep_streams(l.w, l.h)) {
+        launch_sweep_stream<false>(ctx, l, d, coeff, out, 1.f, 0);
     } else {
-        const XcdTiles tiles = xcd_tiles(div_up(w, kBlockX), div_up(h, kBlockY));
-        const dim3 grid(xcd_grid(tiles));
-        sweep_grey_kernel<<<grid, dim3(kBlockX, kBlockY), 0, ctx->stream>>>(
-            f0, f1, u, v, du, dv, phi, ksi, tiles, (int)w, (int)h, (int)(pitch_bytes / 4), hx, hy, alpha, tdu, tdv);
+        const SweepForm& form = sweep_form(l.constancy);
+        const XcdTiles tiles = sweep_tiles(l, form.block_y);
+        form.sweep<<<dim3(xcd_grid(tiles)), dim3(kBlockX, form.block_y), 0, ctx->stream>>>(
+            l.f0, l.f1, l.u, l.v, d.du, d.dv, coeff.du, coeff.dv, tiles, (int)l.w, (int)l.h, (int)(l.pitch_bytes / 4), l.hx, l.hy,
+            l.alpha, out.du, out.dv);
     }
     FLOW2D_CHECK_LAUNCH();
     return FLOW2D_OK;
 }
 
-// One red-black SOR iteration (two half-sweeps) in place on du / dv.
-int launch_sor_iteration(flow2d_context* ctx, int constancy, const float* f0, const float* f1, const float* u,
-                         const float* v, float* du, float* dv, const float* phi, const float* ksi, size_t w, size_t h,
-                         size_t pitch_bytes, float hx, float hy, float alpha, float omega)
+int sor_iteration_one(const flow2d_context* ctx, const flow2d::SolveLevel& l, flow2d::Pair d, flow2d::ConstPair coeff)
 {
-    if (ctx->batch_count > 1) {
-        const unsigned n = ctx->batch_count;
-        const size_t s = ctx->batch_stride_floats;
-        ctx->batch_count = 1;
-        int st = FLOW2D_OK;
-        for (unsigned b = 0; b < n && st == FLOW2D_OK; ++b)
-            st = launch_sor_iteration(ctx, constancy, f0 + b * s, f1 + b * s, u + b * s, v + b * s, du + b * s, dv + b * s,
-                                      phi + b * s, ksi + b * s, w, h, pitch_bytes, hx, hy, alpha, omega);
-        ctx->batch_count = n;
-        return st;
-    }
+    const SweepForm& form = sweep_form(l.constancy);
+    if (!form.sor) return FLOW2D_ERR_UNSUPPORTED;  // (the entries refuse the term before they come here)
     for (int colour = 0; colour < 2; ++colour) {
-        if (sweep_streams(w, h)) {
+        if (sweep_streams(l.w, l.h)) {
             // (round 5) the half-sweep as a streaming strip kernel, in place: the same strips as the Jacobi form.
             // Invariant of the in-place form (tdu == du, tdv == dv): the halo lanes and halo rows of a strip load pixels
             // of the colour being relaxed that a NEIGHBOURING wave stores in this launch -- formally a race, in effect none: a
             // relaxed pixel's update reads its four neighbours, which have the OTHER colour and are only read in this launch, and
             // its own old value, which the owning wave loads itself; own-colour values from halo lanes / rows are dead (the kernel's
             // du / dv pointers carry no __restrict__, so the compiler may not merge or hoist those loads across the stores).
-            const XcdTiles tiles = sweep_stream_tiles(w, h, constancy);
-            const SweepPlanes planes{f0, f1, u, v, du, dv, phi, ksi};
-            const dim3 grid(xcd_grid(tiles));
-            const int iw = (int)w, ih = (int)h, ip = (int)(pitch_bytes / 4), rows = (int)sweep_strip_rows();
-            if (constancy == FLOW2D_CONSTANCY_GRADIENT)
-                sweep_stream_kernel<1, true><<<grid, 256, 0, ctx->stream>>>(planes, tiles, iw, ih, ip, rows, hx, hy, alpha, du, dv, omega, colour);
-            else if (constancy == FLOW2D_CONSTANCY_GRADIENT_UNTILED)
-                sweep_stream_kernel<2, true><<<grid, 256, 0, ctx->stream>>>(planes, tiles, iw, ih, ip, rows, hx, hy, alpha, du, dv, omega, colour);
-            else
-                sweep_stream_kernel<0, true><<<grid, 256, 0, ctx->stream>>>(planes, tiles, iw, ih, ip, rows, hx, hy, alpha, du, dv, omega, colour);
-        } else if (constancy == FLOW2D_CONSTANCY_GRADIENT) {
-            const XcdTiles tiles = xcd_tiles(div_up(w, kBlockX), div_up(h, kGradTileY));
-        const dim3 grid(xcd_grid(tiles));
-            sor_grad_kernel<<<grid, dim3(kBlockX, kGradTileY), 0, ctx->stream>>>(
-                f0, f1, u, v, du, dv, phi, ksi, tiles, (int)w, (int)h, (int)(pitch_bytes / 4), hx, hy, alpha, omega, colour);
-        } else if (constancy == FLOW2D_CONSTANCY_GRADIENT_UNTILED) {
-            const XcdTiles tiles = xcd_tiles(div_up(w, kBlockX), div_up(h, kBlockY));
-        const dim3 grid(xcd_grid(tiles));
-            sor_grad_untiled_kernel<<<grid, dim3(kBlockX, kBlockY), 0, ctx->stream>>>(
-                f0, f1, u, v, du, dv, phi, ksi, tiles, (int)w, (int)h, (int)(pitch_bytes / 4), hx, hy, alpha, omega, colour);
+            launch_sweep_stream<true>(ctx, l, d, coeff, d, l.sor_omega, colour);
         } else {
-            const XcdTiles tiles = xcd_tiles(div_up(w, kBlockX), div_up(h, kBlockY));
-        const dim3 grid(xcd_grid(tiles));
-            sor_grey_kernel<<<grid, dim3(kBlockX, kBlockY), 0, ctx->stream>>>(
-                f0, f1, u, v, du, dv, phi, ksi, tiles, (int)w, (int)h, (int)(pitch_bytes / 4), hx, hy, alpha, omega, colour);
+            const XcdTiles tiles = sweep_tiles(l, form.block_y);
+            form.sor<<<dim3(xcd_grid(tiles)), dim3(kBlockX, form.block_y), 0, ctx->stream>>>(
+                l.f0, l.f1, l.u, l.v, d.du, d.dv, coeff.du, coeff.dv, tiles, (int)l.w, (int)l.h, (int)(l.pitch_bytes / 4), l.hx, l.hy,
+                l.alpha, l.sor_omega, colour);
         }
         FLOW2D_CHECK_LAUNCH();
     }
     return FLOW2D_OK;
+}
+
+}  // namespace
+
+namespace flow2d {
+
+int launch_phi_ksi(const flow2d_context* ctx, const SolveLevel& level, ConstPair d, Pair coeff)
+{
+    return for_each_instance(ctx, level, phi_ksi_one, d, coeff);
+}
+
+int launch_sweep(const flow2d_context* ctx, const SolveLevel& level, ConstPair d, ConstPair coeff, Pair out)
+{
+    return for_each_instance(ctx, level, sweep_one, d, coeff, out);
+}
+
+// One red-black SOR iteration (two half-sweeps) in place on du / dv.
+int launch_sor_iteration(const flow2d_context* ctx, const SolveLevel& level, Pair d, ConstPair coeff)
+{
+    return for_each_instance(ctx, level, sor_iteration_one, d, coeff);
 }
 
 }  // namespace flow2d
@@ -783,8 +765,9 @@ int flow2d_compute_phi_ksi(flow2d_context* ctx, const float* frame_0, const floa
         return FLOW2D_ERR_INVALID_ARGUMENT;
     for (int i = 0; i < 6; ++i)
         if (planes[i] == phi || planes[i] == ksi) return FLOW2D_ERR_INVALID_ARGUMENT;
-    return flow2d::launch_phi_ksi(ctx, frame_0, frame_1, flow_u, flow_v, flow_du, flow_dv, width, height, pitch_bytes,
-                                  hx, hy, equation_smoothness, equation_data, phi, ksi);
+    const flow2d::SolveLevel level{FLOW2D_CONSTANCY_GREY, frame_0, frame_1, flow_u, flow_v, width, height, pitch_bytes, hx, hy, 0.f,
+                                   equation_smoothness, equation_data, 0.f, 0};  // (neither data term nor alpha enter phi, ksi)
+    return flow2d::launch_phi_ksi(ctx, level, {flow_du, flow_dv}, {phi, ksi});
 }
 
 static int sweep_entry(flow2d_context* ctx, int constancy, const float* frame_0, const float* frame_1,
@@ -799,8 +782,8 @@ static int sweep_entry(flow2d_context* ctx, int constancy, const float* frame_0,
         return FLOW2D_ERR_INVALID_ARGUMENT;
     for (int i = 0; i < 8; ++i)  // Jacobi: the sweep must not write a plane it reads
         if (planes[i] == temp_du || planes[i] == temp_dv) return FLOW2D_ERR_INVALID_ARGUMENT;
-    return flow2d::launch_sweep(ctx, constancy, frame_0, frame_1, flow_u, flow_v, flow_du, flow_dv, phi, ksi, width,
-                                height, pitch_bytes, hx, hy, alpha, temp_du, temp_dv);
+    const flow2d::SolveLevel level{constancy, frame_0, frame_1, flow_u, flow_v, width, height, pitch_bytes, hx, hy, alpha, 0.f, 0.f, 0.f, 0};
+    return flow2d::launch_sweep(ctx, level, {flow_du, flow_dv}, {phi, ksi}, {temp_du, temp_dv});
 }
 
 int flow2d_solve_2d_sor(flow2d_context* ctx, const float* frame_0, const float* frame_1, const float* flow_u,
@@ -818,8 +801,9 @@ int flow2d_solve_2d_sor(flow2d_context* ctx, const float* frame_0, const float* 
     if (data_constancy != FLOW2D_CONSTANCY_GREY && data_constancy != FLOW2D_CONSTANCY_GRADIENT &&
         data_constancy != FLOW2D_CONSTANCY_GRADIENT_UNTILED)
         return FLOW2D_ERR_UNSUPPORTED;
-    return flow2d::launch_sor_iteration(ctx, data_constancy, frame_0, frame_1, flow_u, flow_v, flow_du, flow_dv, phi,
-                                        ksi, width, height, pitch_bytes, hx, hy, equation_alpha, omega);
+    const flow2d::SolveLevel level{data_constancy, frame_0, frame_1, flow_u, flow_v, width, height, pitch_bytes, hx, hy, equation_alpha,
+                                   0.f, 0.f, omega, 0};
+    return flow2d::launch_sor_iteration(ctx, level, {flow_du, flow_dv}, {phi, ksi});
 }
 
 int flow2d_solve_2d(flow2d_context* ctx, const float* frame_0, const float* frame_1, const float* flow_u,

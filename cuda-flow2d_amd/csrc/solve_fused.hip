@@ -7,20 +7,9 @@
 #include <cstring>
 #include <map>
 
-#include "common.hpp"
+#include "solver.hpp"
 #include "solve_fused_args.hpp"
 #include "solve_fused_probes.hpp"
-
-namespace {
-
-// true when x is a normal power of two whose reciprocal (and 1/(2x), 1/(4x)) is exactly representable
-bool is_power_of_two(float x)
-{
-    int e = 0;
-    return x > 0.f && std::frexp(x, &e) == 0.5f && e > -100 && e < 100;
-}
-
-}  // namespace
 
 namespace flow2d {
 
@@ -222,19 +211,24 @@ void fused_rows_of(const FusedArgs& a, int bx, int by, int& y0, int& y1)
     }
 }
 
-// One outer iteration: reads du/dv (previous outer iteration), writes out_du/out_dv (after `inner` sweeps).
-int launch_fused_outer(flow2d_context* ctx, int constancy, const float* f0, const float* f1, const float* u,
-                       const float* v, const float* du, const float* dv, size_t w, size_t h, size_t pitch_bytes,
-                       float hx, float hy, float alpha, float e_smooth, float e_data, size_t inner, float* out_du,
-                       float* out_dv, int rows_per_strip, bool zero_increment, const float* start_du,
-                       const float* start_dv, float sor_omega, int base_flow_shift)
+// The instance objects by [build: 0 the pipeline's, 1 the packed one for a lone context][data term][POW2]; null: no such build.
+static FusedLaunch* const kFusedBuilds[2][4][2] = {
+    {{fused_launch_g0_p0, fused_launch_g0_p1}, {fused_launch_g1_p0, fused_launch_g1_p1},
+     {fused_launch_g2_p0, fused_launch_g2_p1}, {fused_launch_g3_p0, fused_launch_g3_p1}},
+    {{fused_launch_g0_p0_k, fused_launch_g0_p1_k}, {fused_launch_g1_p0_k, fused_launch_g1_p1_k},
+     {fused_launch_g2_p0_k, fused_launch_g2_p1_k}, {nullptr, nullptr}}};
+
+// One outer iteration: reads `in` (previous outer iteration), writes `out` (after `stages` sweeps).
+int launch_fused_outer(const flow2d_context* ctx, const SolveLevel& l, ConstPair in, Pair out, size_t stages, bool zero_increment,
+                       ConstPair start, int rows_per_strip)
 {
+    const size_t w = l.w, h = l.h, pitch_bytes = l.pitch_bytes, inner = stages;
+    const float hx = l.hx, hy = l.hy, alpha = l.alpha, sor_omega = l.sor_omega;
     // sor_omega != 0: the `inner` stages are red-black half-sweeps (2 or 4: one or two iterations per launch)
     if (!fused_supports(inner) || !fused_addressable(h, pitch_bytes)) return FLOW2D_ERR_UNSUPPORTED;
-    if (base_flow_shift != 0 && base_flow_shift != 1) return FLOW2D_ERR_UNSUPPORTED;
+    if (l.base_flow_shift != 0 && l.base_flow_shift != 1) return FLOW2D_ERR_UNSUPPORTED;
     if (sor_omega != 0.f && (inner != 2 && inner != 4)) return FLOW2D_ERR_UNSUPPORTED;
     if (!fused_weights_ok(hx, hy, alpha)) return FLOW2D_ERR_UNSUPPORTED;
-    // rows_per_strip > 0: uniform strips of that height (developer override); 0: the planner's choice
     // A lock-step group whose every instance fills the chip on its own with long strips (128 rows and more: 4096^2 and
     // up) is launched instance by instance: nothing is gained by one launch of several rounds, and the strips are then
     // planned -- and show in a kernel trace -- exactly as for a single pair.  Smaller levels share a launch (grid.z),
@@ -245,22 +239,22 @@ int launch_fused_outer(flow2d_context* ctx, int constancy, const float* f0, cons
     if (rows_per_strip > 0)
         plan = FusedPlan{rows_per_strip, rows_per_strip, (int)div_up(h, rows_per_strip), plan.blocks_x,
                          plan.blocks_x * (int)div_up(h, rows_per_strip)};
-    FusedArgs a{f0, f1, u, v, du, dv, out_du, out_dv, (int)w, (int)h, (int)(pitch_bytes / 4), plan.rows_interior,
+    FusedArgs a{l.f0, l.f1, l.u, l.v, in.du, in.dv, out.du, out.dv, (int)w, (int)h, (int)(pitch_bytes / 4), plan.rows_interior,
                 plan.rows_edge, plan.strips_interior, plan.blocks_x,
-                zero_increment ? 1 : 0, start_du, start_dv, (start_du && start_dv) ? 1 : 0, hx, hy, alpha, e_smooth,
-                e_data,
+                zero_increment ? 1 : 0, start.du, start.dv, (start.du && start.dv) ? 1 : 0, hx, hy, alpha, l.e_smooth,
+                l.e_data,
                 2.f * hx, 2.f * hy, 4.f * hx, 4.f * hy, 1.f / (2.f * hx), 1.f / (2.f * hy), 1.f / (4.f * hx), 1.f / (4.f * hy),
                 static_cast<float>(1.0 / (2.0 * hx)), static_cast<float>(1.0 / (2.0 * hy)), alpha / (hx * hx), alpha / (hy * hy),
                 0.5f * (alpha / (hx * hx)), 0.5f * (alpha / (hy * hy)),
                 sor_omega, 1.f - sor_omega,
-                0, plan.blocks, 0, 0, static_cast<unsigned long long>(ctx->batch_stride_floats), base_flow_shift,
+                0, plan.blocks, 0, 0, static_cast<unsigned long long>(ctx->batch_stride_floats), l.base_flow_shift,
                 nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
                 ctx->fused_fallbacks};
     // The first outer iteration of a level starts from du = dv = 0: the kernel loads the increment planes all the same (no branch
     // around two loads in every row step) and selects the zero -- so let those loads go to (u, v), whose lines the same step has just
     // fetched, instead of dragging two planes of stale data through HBM (a 4096^2 launch 583 -> 450 MB; round 6).
     // With (u, v) at half the size (base_flow_shift) the full-size offsets would leave their region: the frames serve the same way.
-    if (zero_increment) a.du = base_flow_shift ? f0 : u, a.dv = base_flow_shift ? f1 : v;
+    if (zero_increment) a.du = l.base_flow_shift ? l.f0 : l.u, a.dv = l.base_flow_shift ? l.f1 : l.v;
 #ifdef FLOW2D_DEV_BUILD
     if (probe::kStamps) a.stamps = stamp_buffer(), a.stamp_count = stamp_counter(), a.stalls = stall_buffer();
     const size_t plane_floats = h * (pitch_bytes / 4);
@@ -268,7 +262,7 @@ int launch_fused_outer(flow2d_context* ctx, int constancy, const float* f0, cons
         if (ctx->batch_count > 1 || a.continue_sweeps || plane_floats * 16 > 0xffffffffull) return FLOW2D_ERR_UNSUPPORTED;
         PackedPlanes& pp = packed_planes(plane_floats);
         a.pack_in = pp.in, a.pack_duv = pp.duv, a.pack_out = pp.out;
-        pack_planes_kernel<<<(unsigned)div_up(plane_floats, 256), 256, 0, ctx->stream>>>(f0, f1, u, v, du, dv, reinterpret_cast<float4*>(pp.in),
+        pack_planes_kernel<<<(unsigned)div_up(plane_floats, 256), 256, 0, ctx->stream>>>(l.f0, l.f1, l.u, l.v, in.du, in.dv, reinterpret_cast<float4*>(pp.in),
                                                                                     reinterpret_cast<float2*>(pp.duv), plane_floats);
     }
 #endif
@@ -281,40 +275,26 @@ int launch_fused_outer(flow2d_context* ctx, int constancy, const float* f0, cons
     // is within reach of the memory system).
     fused_order_for(plan, a);
     const dim3 grid(a.blocks_per_xcd ? a.blocks_per_xcd * 8 : plan.blocks, 1, instances_per_launch);
-    const bool pow2 = is_power_of_two(hx) && is_power_of_two(hy);
-    int rc = 0;
-    for (unsigned first = 0; first < ctx->batch_count && rc == 0; first += instances_per_launch) {
-    if (first) {  // the next instance of a split group: every plane one batch stride further
-        const size_t off = static_cast<size_t>(ctx->batch_stride_floats) * instances_per_launch;
-        a.f0 += off, a.f1 += off, a.u += off, a.v += off, a.du += off, a.dv += off, a.out_du += off, a.out_dv += off;
-        if (a.continue_sweeps) a.start_du += off, a.start_dv += off;
-    }
-    const int in = static_cast<int>(inner);
+    const int term = l.constancy >= 1 && l.constancy <= 3 ? l.constancy : 0, pow2 = is_power_of_two(hx) && is_power_of_two(hy);
     // A context that runs alone (flow2d_context_set_lone) and a launch of at most one workgroup per CU -- one wave per SIMD: nothing
     // to share issue turns with -- take the build with packed arithmetic: fewer, wider instructions (the same IEEE operations).
-    const bool packed_build = ctx->lone && (long)plan.blocks * (long)instances_per_launch <= (long)(ctx->num_cus > 0 ? ctx->num_cus : 256);
-    rc = 1;
-    if (packed_build && constancy == FLOW2D_CONSTANCY_GRADIENT)
-        rc = pow2 ? fused_launch_g1_p1_k(in, grid, ctx->stream, a) : fused_launch_g1_p0_k(in, grid, ctx->stream, a);
-    else if (packed_build && constancy == FLOW2D_CONSTANCY_GRADIENT_UNTILED)
-        rc = pow2 ? fused_launch_g2_p1_k(in, grid, ctx->stream, a) : fused_launch_g2_p0_k(in, grid, ctx->stream, a);
-    else if (packed_build && constancy != FLOW2D_CONSTANCY_LOG_DERIVATIVES)
-        rc = pow2 ? fused_launch_g0_p1_k(in, grid, ctx->stream, a) : fused_launch_g0_p0_k(in, grid, ctx->stream, a);
-    if (rc == 0)  // (the packed build ran; it holds no kernels for continued sweeps: those fall through to the pipeline's build)
-        ;
-    else if (constancy == FLOW2D_CONSTANCY_GRADIENT)
-        rc = pow2 ? fused_launch_g1_p1(in, grid, ctx->stream, a) : fused_launch_g1_p0(in, grid, ctx->stream, a);
-    else if (constancy == FLOW2D_CONSTANCY_GRADIENT_UNTILED)
-        rc = pow2 ? fused_launch_g2_p1(in, grid, ctx->stream, a) : fused_launch_g2_p0(in, grid, ctx->stream, a);
-    else if (constancy == FLOW2D_CONSTANCY_LOG_DERIVATIVES)
-        rc = pow2 ? fused_launch_g3_p1(in, grid, ctx->stream, a) : fused_launch_g3_p0(in, grid, ctx->stream, a);
-    else
-        rc = pow2 ? fused_launch_g0_p1(in, grid, ctx->stream, a) : fused_launch_g0_p0(in, grid, ctx->stream, a);
+    const bool lone = ctx->lone && (long)plan.blocks * (long)instances_per_launch <= (long)(ctx->num_cus > 0 ? ctx->num_cus : 256);
+    FusedLaunch* const lone_build = lone ? kFusedBuilds[1][term][pow2] : nullptr;
+    int rc = 0;
+    for (unsigned first = 0; first < ctx->batch_count && rc == 0; first += instances_per_launch) {
+        if (first) {  // the next instance of a split group: every plane one batch stride further
+            const size_t off = static_cast<size_t>(ctx->batch_stride_floats) * instances_per_launch;
+            a.f0 += off, a.f1 += off, a.u += off, a.v += off, a.du += off, a.dv += off, a.out_du += off, a.out_dv += off;
+            if (a.continue_sweeps) a.start_du += off, a.start_dv += off;
+        }
+        // (the packed build holds no kernels for continued sweeps: those are the pipeline's build's, like everything it lacks)
+        rc = lone_build ? lone_build((int)inner, grid, ctx->stream, a) : 1;
+        if (rc) rc = kFusedBuilds[0][term][pow2]((int)inner, grid, ctx->stream, a);
     }
     if (rc) return FLOW2D_ERR_UNSUPPORTED;
 #ifdef FLOW2D_DEV_BUILD
     if (probe::kPackedPlanes)
-        unpack_planes_kernel<<<(unsigned)div_up(plane_floats, 256), 256, 0, ctx->stream>>>(reinterpret_cast<const float2*>(a.pack_out), out_du, out_dv,
+        unpack_planes_kernel<<<(unsigned)div_up(plane_floats, 256), 256, 0, ctx->stream>>>(reinterpret_cast<const float2*>(a.pack_out), out.du, out.dv,
                                                                                       plane_floats);
 #endif
     FLOW2D_CHECK_LAUNCH();

@@ -110,24 +110,4 @@ __host__ __device__ inline bool fused_block_of(const FusedArgs& a, int launch_id
     return true;
 }
 
-// One entry per instance object: launches fused_outer_kernel<inner, GRAD, POW2, CONT> (CONT from a.continue_sweeps); returns
-// non-zero when the object holds no such instantiation (inner outside 1..5, or a developer build's reduced set).
-#define FLOW2D_FUSED_LAUNCHER(g, p) int fused_launch_g##g##_p##p(int inner, dim3 grid, hipStream_t stream, const FusedArgs& a)
-FLOW2D_FUSED_LAUNCHER(0, 0);
-FLOW2D_FUSED_LAUNCHER(0, 1);
-FLOW2D_FUSED_LAUNCHER(1, 0);
-FLOW2D_FUSED_LAUNCHER(1, 1);
-FLOW2D_FUSED_LAUNCHER(2, 0);
-FLOW2D_FUSED_LAUNCHER(2, 1);
-FLOW2D_FUSED_LAUNCHER(3, 0);
-FLOW2D_FUSED_LAUNCHER(3, 1);
-// the packed build of the same kernels (not of the log-derivative term, whose one build is packed already)
-#define FLOW2D_FUSED_LONE_LAUNCHER(g, p) int fused_launch_g##g##_p##p##_k(int inner, dim3 grid, hipStream_t stream, const FusedArgs& a)
-FLOW2D_FUSED_LONE_LAUNCHER(0, 0);
-FLOW2D_FUSED_LONE_LAUNCHER(0, 1);
-FLOW2D_FUSED_LONE_LAUNCHER(1, 0);
-FLOW2D_FUSED_LONE_LAUNCHER(1, 1);
-FLOW2D_FUSED_LONE_LAUNCHER(2, 0);
-FLOW2D_FUSED_LONE_LAUNCHER(2, 1);
-
 }  // namespace flow2d

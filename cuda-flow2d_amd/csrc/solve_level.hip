@@ -4,39 +4,8 @@
 // synchronisation (:291): everything is queued on the context's stream.
 #include <algorithm>
 #include <cstdlib>
-#include <utility>
 
-#include "common.hpp"
-
-namespace flow2d {
-int launch_phi_ksi(flow2d_context* ctx, const float* f0, const float* f1, const float* u, const float* v,
-                   const float* du, const float* dv, size_t w, size_t h, size_t pitch_bytes, float hx, float hy,
-                   float e_smooth, float e_data, float* phi, float* ksi);
-int launch_sweep(flow2d_context* ctx, int constancy, const float* f0, const float* f1, const float* u, const float* v,
-                 const float* du, const float* dv, const float* phi, const float* ksi, size_t w, size_t h,
-                 size_t pitch_bytes, float hx, float hy, float alpha, float* tdu, float* tdv);
-int launch_sor_iteration(flow2d_context* ctx, int constancy, const float* f0, const float* f1, const float* u,
-                         const float* v, float* du, float* dv, const float* phi, const float* ksi, size_t w, size_t h,
-                         size_t pitch_bytes, float hx, float hy, float alpha, float omega);
-bool small_level_supports(size_t w, size_t h);
-int launch_small_level(flow2d_context* ctx, int constancy, const float* f0, const float* f1, const float* u,
-                       const float* v, size_t w, size_t h, size_t pitch_bytes, float hx, float hy, float alpha,
-                       float e_smooth, float e_data, size_t outer, size_t inner, float* out_du, float* out_dv);
-bool fused_supports(size_t inner);
-bool fused_addressable(size_t h, size_t pitch_bytes);
-bool fused_weights_ok(float hx, float hy, float alpha);
-bool tiled_supports(int constancy, size_t inner);
-int launch_tiled_outer(flow2d_context* ctx, int constancy, const float* f0, const float* f1, const float* u,
-                       const float* v, const float* du, const float* dv, size_t w, size_t h, size_t pitch_bytes, float hx,
-                       float hy, float alpha, float e_smooth, float e_data, size_t inner, float* out_du, float* out_dv,
-                       bool zero_increment, float sor_omega);
-
-int launch_fused_outer(flow2d_context* ctx, int constancy, const float* f0, const float* f1, const float* u,
-                       const float* v, const float* du, const float* dv, size_t w, size_t h, size_t pitch_bytes,
-                       float hx, float hy, float alpha, float e_smooth, float e_data, size_t inner, float* out_du,
-                       float* out_dv, int rows_per_strip, bool zero_increment, const float* start_du,
-                       const float* start_dv, float sor_omega, int base_flow_shift);
-}  // namespace flow2d
+#include "solver.hpp"
 
 namespace {
 // mode-2 timing: one more event on the stream, appended to the slot's start/stop list
@@ -57,6 +26,140 @@ hipError_t mark(flow2d_context* ctx, flow2d_timing_slot* slot)
     if (e != hipSuccess) return e;
     slot->kernel_events.push_back(ev);
     return hipEventRecord(ev, ctx->stream);
+}
+
+// An event before and one behind a launch of the level's dominant kernel; nothing but the launch when `slot` is null (mode 2 is
+// off, or the level is below the launch filter).
+struct LaunchMarks {
+    flow2d_context* ctx;
+    flow2d_timing_slot* slot;
+    template <class Launch>
+    int around(Launch launch) const
+    {
+        if (slot) FLOW2D_HIP_TRY(mark(ctx, slot));
+        const int status = launch();
+        if (status != FLOW2D_OK) return status;
+        if (slot) FLOW2D_HIP_TRY(mark(ctx, slot));
+        return FLOW2D_OK;
+    }
+};
+
+using flow2d::ConstPair;
+using flow2d::Pair;
+using flow2d::SolveLevel;
+
+// The caller's planes as pairs: 0 (flow_du, flow_dv), 1 (temp_du, temp_dv), 2 (phi, ksi).  What a run_* function reports:
+struct LevelRun {
+    int result_pair = 0;  // 0 or 1: the pair that holds the level's increment
+    int launches = 0;     // kernel launches queued (per instance of a group where the kernel is not batched: once)
+};
+
+// The reference's loop: phi / ksi, then `inner` Jacobi sweeps that ping-pong between the two pairs, or red-black iterations in place.
+int run_per_sweep(const flow2d_context* ctx, const SolveLevel& level, const Pair* pairs, size_t outer, size_t inner,
+                  const LaunchMarks& marks, LevelRun& run)
+{
+    int at = 0;  // the pair holding du, dv
+    for (size_t i = 0; i < outer; ++i) {
+        int st = flow2d::launch_phi_ksi(ctx, level, pairs[at], pairs[2]);
+        if (st != FLOW2D_OK) return st;
+        for (size_t j = 0; j < inner; ++j) {
+            if (level.sor_omega != 0.f) {  // opt-in: in place, no ping-pong
+                st = flow2d::launch_sor_iteration(ctx, level, pairs[at], pairs[2]);
+                if (st != FLOW2D_OK) return st;
+                run.launches += 2;
+            } else {
+                st = marks.around([&] { return flow2d::launch_sweep(ctx, level, pairs[at], pairs[2], pairs[1 - at]); });
+                if (st != FLOW2D_OK) return st;
+                at = 1 - at;
+                ++run.launches;
+            }
+        }
+    }
+    run.result_pair = at;
+    return FLOW2D_OK;
+}
+
+// launches per outer iteration of the strips: five sweeps at most in one (red-black iterations: two half-sweep stages each, at
+// most two iterations per launch)
+size_t fused_chunks(size_t inner, bool sor)
+{
+    const size_t per_launch_max = sor ? 2 : 5;
+    return std::max<size_t>(1, (inner + per_launch_max - 1) / per_launch_max);
+}
+
+// Fused path: one launch per outer iteration does phi/ksi and up to 5 sweeps (solve_fused_kernel.hpp); phi and ksi
+// are not materialised, so their planes serve as a third (du, dv) pair.  More than 5 sweeps per outer
+// iteration are split into equal chunks: every chunk rebuilds the coefficients from the outer iteration's
+// starting pair (same arithmetic, same values) and continues the sweeps from the previous chunk's result.
+int run_fused(const flow2d_context* ctx, const SolveLevel& level, const Pair* pairs, size_t outer, size_t inner,
+              const LaunchMarks& marks, LevelRun& run)
+{
+#ifdef FLOW2D_DEV_BUILD  // uniform strips of that many rows instead of the planner's choice
+    static const int rows_env = std::getenv("FLOW2D_FUSED_ROWS") ? std::atoi(std::getenv("FLOW2D_FUSED_ROWS")) : 0;
+    const int rows = rows_env > 0 ? rows_env : 0;
+#else
+    const int rows = 0;  // the launcher plans the strip heights (solve_fused.hip, FusedPlan)
+#endif
+    const bool sor = level.sor_omega != 0.f;
+    const size_t chunks = fused_chunks(inner, sor);
+    int source = 0;  // pair holding du, dv at the start of the outer iteration
+    for (size_t i = 0; i < outer; ++i) {
+        int in = source;
+        for (size_t c = 0; c < chunks; ++c) {
+            const size_t sweeps = inner / chunks + (c < inner % chunks ? 1 : 0);
+            int out = 0;
+            while (out == source || out == in) ++out;
+            const int st = marks.around([&] {
+                return flow2d::launch_fused_outer(ctx, level, pairs[source], pairs[out], sor ? 2 * sweeps : sweeps, i == 0,
+                                                  c == 0 ? ConstPair{nullptr, nullptr} : ConstPair(pairs[in]), rows);
+            });
+            if (st != FLOW2D_OK) return st;
+            in = out;
+            ++run.launches;
+        }
+        source = in;
+    }
+    if (source == 2) {  // the caller only knows two pairs: hand the result over
+        for (unsigned b = 0; b < ctx->batch_count; ++b) {
+            const Pair from = shifted(pairs[2], b * ctx->batch_stride_floats), to = shifted(pairs[0], b * ctx->batch_stride_floats);
+            FLOW2D_HIP_TRY(hipMemcpy2DAsync(to.du, level.pitch_bytes, from.du, level.pitch_bytes, level.w * sizeof(float), level.h,
+                                            hipMemcpyDeviceToDevice, ctx->stream));
+            FLOW2D_HIP_TRY(hipMemcpy2DAsync(to.dv, level.pitch_bytes, from.dv, level.pitch_bytes, level.w * sizeof(float), level.h,
+                                            hipMemcpyDeviceToDevice, ctx->stream));
+        }
+        source = 0;
+    }
+    run.result_pair = source;
+    return FLOW2D_OK;
+}
+
+// Tiled path: one launch per outer iteration, ping-pong between the caller's two pairs.  (Round 5 tried TWO outer
+// iterations per launch of the 8 x 8 and 16 x 16 tiles over a halo of 2 (inner + 1) pixels -- half the launches of the
+// launch-bound levels: the regions of 32 x 32 / 40 x 40 pixels recompute 16x / 6x the tile and a lone 1024^2 pair took 0.76
+// instead of 0.71 ms, a lone 4096^2 pair 4.24 instead of 4.08-4.17, the pipelined rates 1 % less:
+// profiles/r05_experiments/tile_two_outer_ab.txt.  Not kept.)
+int run_tiled(const flow2d_context* ctx, const SolveLevel& level, const Pair* pairs, size_t outer, size_t inner,
+              const LaunchMarks& marks, LevelRun& run)
+{
+    const size_t stages = level.sor_omega != 0.f ? 2 * inner : inner;
+    int source = 0;
+    for (size_t i = 0; i < outer; ++i) {
+        const int st = marks.around(
+            [&] { return flow2d::launch_tiled_outer(ctx, level, pairs[source], pairs[1 - source], stages, i == 0); });
+        if (st != FLOW2D_OK) return st;
+        source = 1 - source;
+        ++run.launches;
+    }
+    run.result_pair = source;
+    return FLOW2D_OK;
+}
+
+// The whole level in one launch (per instance), written to the caller's first pair.
+int run_single_workgroup(const flow2d_context* ctx, const SolveLevel& level, const Pair* pairs, size_t outer, size_t inner,
+                         const LaunchMarks& marks, LevelRun& run)
+{
+    run.launches = 1;
+    return marks.around([&] { return flow2d::launch_small_level(ctx, level, outer, inner, pairs[0]); });
 }
 }  // namespace
 
@@ -214,113 +317,21 @@ int flow2d_solve_level(flow2d_context* ctx, const float* frame_0, const float* f
     }
 
     const bool per_launch = slot && ctx->timing >= 2 && p->width >= ctx->timing_min_w && p->height >= ctx->timing_min_h;
-    float* du = flow_du;
-    float* dv = flow_dv;
-    float* tdu = temp_du;
-    float* tdv = temp_dv;
-    int launches = 0;
-    if (algorithm == FLOW2D_SOLVER_SINGLE_WORKGROUP) {
-        if (per_launch) FLOW2D_HIP_TRY(mark(ctx, slot));
-        int st = flow2d::launch_small_level(ctx, p->data_constancy, frame_0, frame_1, flow_u, flow_v, p->width, p->height,
-                                            p->pitch_bytes, p->hx, p->hy, p->equation_alpha, p->equation_smoothness,
-                                            p->equation_data, p->outer_iterations_count, p->inner_iterations_count,
-                                            du, dv);
-        if (st != FLOW2D_OK) return st;
-        if (per_launch) FLOW2D_HIP_TRY(mark(ctx, slot));
-        ++launches;
+    const LaunchMarks marks{ctx, per_launch ? slot : nullptr};
+    const SolveLevel level{p->data_constancy, frame_0, frame_1, flow_u, flow_v, p->width, p->height, p->pitch_bytes,
+                           p->hx, p->hy, p->equation_alpha, p->equation_smoothness, p->equation_data,
+                           sor ? p->sor_omega : 0.f, p->base_flow_shift};
+    const Pair pairs[3] = {{flow_du, flow_dv}, {temp_du, temp_dv}, {phi, ksi}};
+    const auto run_algorithm = algorithm == FLOW2D_SOLVER_FUSED   ? run_fused
+                               : algorithm == FLOW2D_SOLVER_TILED ? run_tiled
+                               : algorithm == FLOW2D_SOLVER_SINGLE_WORKGROUP ? run_single_workgroup
+                                                                             : run_per_sweep;
+    LevelRun run;
+    {
+        const int status = run_algorithm(ctx, level, pairs, p->outer_iterations_count, p->inner_iterations_count, marks, run);
+        if (status != FLOW2D_OK) return status;
     }
-#ifdef FLOW2D_DEV_BUILD  // uniform strips of that many rows instead of the planner's choice
-    static const int rows_env = std::getenv("FLOW2D_FUSED_ROWS") ? std::atoi(std::getenv("FLOW2D_FUSED_ROWS")) : 0;
-#else
-    const int rows_env = 0;
-#endif
-    // Fused path: one launch per outer iteration does phi/ksi and up to 5 sweeps (solve_fused_kernel.hpp); phi and ksi
-    // are not materialised, so their planes serve as a third (du, dv) pair.  More than 5 sweeps per outer
-    // iteration are split into equal chunks: every chunk rebuilds the coefficients from the outer iteration's
-    // starting pair (same arithmetic, same values) and continues the sweeps from the previous chunk's result.
-    float* pair_u[3] = {flow_du, temp_du, phi};
-    float* pair_v[3] = {flow_dv, temp_dv, ksi};
-    int source = 0;  // pair holding du, dv at the start of the outer iteration
-    const size_t inner = p->inner_iterations_count;
-    // (red-black iterations: two half-sweep stages each, at most two iterations per launch)
-    const size_t per_launch_max = sor ? 2 : 5;
-    const size_t chunks = algorithm == FLOW2D_SOLVER_FUSED ? std::max<size_t>(1, (inner + per_launch_max - 1) / per_launch_max) : 0;
-    for (size_t i = 0; algorithm == FLOW2D_SOLVER_FUSED && i < p->outer_iterations_count; ++i) {
-        int in = source;
-        for (size_t c = 0; c < chunks; ++c) {
-            const size_t sweeps = inner / chunks + (c < inner % chunks ? 1 : 0);
-            int out = 0;
-            while (out == source || out == in) ++out;
-            const int rows = rows_env > 0 ? rows_env : 0;  // 0: the launcher plans the strip heights (solve_fused.hip, FusedPlan)
-            if (per_launch) FLOW2D_HIP_TRY(mark(ctx, slot));
-            int st = flow2d::launch_fused_outer(ctx, p->data_constancy, frame_0, frame_1, flow_u, flow_v, pair_u[source],
-                                                pair_v[source], p->width, p->height, p->pitch_bytes, p->hx, p->hy,
-                                                p->equation_alpha, p->equation_smoothness, p->equation_data,
-                                                sor ? 2 * sweeps : sweeps, pair_u[out], pair_v[out], rows, i == 0,
-                                                c == 0 ? nullptr : pair_u[in], c == 0 ? nullptr : pair_v[in],
-                                                sor ? p->sor_omega : 0.f, p->base_flow_shift);
-            if (st != FLOW2D_OK) return st;
-            if (per_launch) FLOW2D_HIP_TRY(mark(ctx, slot));
-            in = out;
-            ++launches;
-        }
-        source = in;
-    }
-    // Tiled path: one launch per outer iteration, ping-pong between the caller's two pairs.  (Round 5 tried TWO outer
-    // iterations per launch of the 8 x 8 and 16 x 16 tiles over a halo of 2 (inner + 1) pixels -- half the launches of the
-    // launch-bound levels: the regions of 32 x 32 / 40 x 40 pixels recompute 16x / 6x the tile and a lone 1024^2 pair took 0.76
-    // instead of 0.71 ms, a lone 4096^2 pair 4.24 instead of 4.08-4.17, the pipelined rates 1 % less:
-    // profiles/r05_experiments/tile_two_outer_ab.txt.  Not kept.)
-    for (size_t i = 0; algorithm == FLOW2D_SOLVER_TILED && i < p->outer_iterations_count; ++i) {
-        const int out = source == 0 ? 1 : 0;
-        if (per_launch) FLOW2D_HIP_TRY(mark(ctx, slot));
-        int st = flow2d::launch_tiled_outer(ctx, p->data_constancy, frame_0, frame_1, flow_u, flow_v, pair_u[source],
-                                            pair_v[source], p->width, p->height, p->pitch_bytes, p->hx, p->hy,
-                                            p->equation_alpha, p->equation_smoothness, p->equation_data,
-                                            sor ? 2 * inner : inner, pair_u[out], pair_v[out], i == 0, sor ? p->sor_omega : 0.f);
-        if (st != FLOW2D_OK) return st;
-        if (per_launch) FLOW2D_HIP_TRY(mark(ctx, slot));
-        source = out;
-        ++launches;
-    }
-    if (algorithm == FLOW2D_SOLVER_FUSED && source == 2) {  // the caller only knows two pairs: hand the result over
-        for (unsigned b = 0; b < ctx->batch_count; ++b) {
-            const size_t off = b * ctx->batch_stride_floats;
-            FLOW2D_HIP_TRY(hipMemcpy2DAsync(flow_du + off, p->pitch_bytes, phi + off, p->pitch_bytes,
-                                            p->width * sizeof(float), p->height, hipMemcpyDeviceToDevice, ctx->stream));
-            FLOW2D_HIP_TRY(hipMemcpy2DAsync(flow_dv + off, p->pitch_bytes, ksi + off, p->pitch_bytes,
-                                            p->width * sizeof(float), p->height, hipMemcpyDeviceToDevice, ctx->stream));
-        }
-        source = 0;
-    }
-    if (one_per_outer && source == 1) {
-        std::swap(du, tdu);
-        std::swap(dv, tdv);
-    }
-    for (size_t i = 0; algorithm == FLOW2D_SOLVER_PER_SWEEP && i < p->outer_iterations_count; ++i) {
-        int st = flow2d::launch_phi_ksi(ctx, frame_0, frame_1, flow_u, flow_v, du, dv, p->width, p->height,
-                                        p->pitch_bytes, p->hx, p->hy, p->equation_smoothness, p->equation_data, phi,
-                                        ksi);
-        if (st != FLOW2D_OK) return st;
-        for (size_t j = 0; sor && j < p->inner_iterations_count; ++j) {  // opt-in: in place, no ping-pong
-            st = flow2d::launch_sor_iteration(ctx, p->data_constancy, frame_0, frame_1, flow_u, flow_v, du, dv, phi, ksi,
-                                              p->width, p->height, p->pitch_bytes, p->hx, p->hy, p->equation_alpha,
-                                              p->sor_omega);
-            if (st != FLOW2D_OK) return st;
-            launches += 2;
-        }
-        for (size_t j = 0; !sor && j < p->inner_iterations_count; ++j) {
-            if (per_launch) FLOW2D_HIP_TRY(mark(ctx, slot));
-            st = flow2d::launch_sweep(ctx, p->data_constancy, frame_0, frame_1, flow_u, flow_v, du, dv, phi, ksi,
-                                      p->width, p->height, p->pitch_bytes, p->hx, p->hy, p->equation_alpha, tdu, tdv);
-            if (st != FLOW2D_OK) return st;
-            if (per_launch) FLOW2D_HIP_TRY(mark(ctx, slot));
-            std::swap(du, tdu);
-            std::swap(dv, tdv);
-            ++launches;
-        }
-    }
-    *result_in_temp = (du != flow_du) ? 1 : 0;
+    *result_in_temp = run.result_pair;
 
     if (slot) {
         FLOW2D_HIP_TRY(hipEventRecord(slot->stop, ctx->stream));
@@ -330,12 +341,12 @@ int flow2d_solve_level(flow2d_context* ctx, const float* frame_0, const float* f
         slot->rec.inner = p->inner_iterations_count;
         slot->rec.data_constancy = p->data_constancy;
         slot->rec.algorithm = algorithm;
-        slot->rec.kernel_launches = launches;
+        slot->rec.kernel_launches = run.launches;
         slot->rec.elapsed_ms = -1.f;
         slot->rec.kernel_ms = -1.f;
         double per_px = 40.0;  // one Jacobi sweep
         if (algorithm == FLOW2D_SOLVER_FUSED)  // an outer iteration's bytes, spread over its launches
-            per_px = (32.0 + 40.0 * p->inner_iterations_count) / static_cast<double>(std::max<size_t>(1, chunks));
+            per_px = (32.0 + 40.0 * p->inner_iterations_count) / static_cast<double>(fused_chunks(p->inner_iterations_count, sor));
         if (algorithm == FLOW2D_SOLVER_TILED) per_px = 32.0 + 40.0 * p->inner_iterations_count;
         if (algorithm == FLOW2D_SOLVER_SINGLE_WORKGROUP)
             per_px = p->outer_iterations_count * (32.0 + 40.0 * p->inner_iterations_count);

@@ -10,7 +10,7 @@
 // boundary.  All outer and inner iterations run inside the launch.
 //
 // Arithmetic: the same solver_math.hpp expressions as the per-sweep and fused kernels, hence the same bits.
-#include "common.hpp"
+#include "solver.hpp"
 #include "solver_math.hpp"
 
 namespace {
@@ -291,47 +291,34 @@ __global__ __launch_bounds__(1024) void small_level_kernel(SmallArgs a)
         }
 }
 
+// One workgroup, one pair.
+int small_level_one(const flow2d_context* ctx, const flow2d::SolveLevel& l, size_t outer, size_t inner, flow2d::Pair out)
+{
+    const SmallArgs a{l.f0, l.f1, l.u, l.v, out.du, out.dv, (int)l.w, (int)l.h, (int)(l.pitch_bytes / 4), (int)outer, (int)inner,
+                      l.hx, l.hy, l.alpha, l.e_smooth, l.e_data, l.constancy == FLOW2D_CONSTANCY_GRADIENT_UNTILED ? 1 : 0,
+                      l.constancy == FLOW2D_CONSTANCY_LOG_DERIVATIVES ? 1 : 0};
+    // [gradient-type term][pixels per thread: 1, 2 or 4 for levels up to 16, 32, 64 rows]
+    static void (*const kernels[2][3])(SmallArgs) = {
+        {small_level_kernel<false, 1>, small_level_kernel<false, 2>, small_level_kernel<false, 4>},
+        {small_level_kernel<true, 1>, small_level_kernel<true, 2>, small_level_kernel<true, 4>}};
+    kernels[l.constancy != FLOW2D_CONSTANCY_GREY][l.h <= 16 ? 0 : (l.h <= 32 ? 1 : 2)]<<<1, dim3(kMaxSide, 1024 / kMaxSide), 0,
+                                                                                         ctx->stream>>>(a);
+    FLOW2D_CHECK_LAUNCH();
+    return FLOW2D_OK;
+}
+
 }  // namespace
 
 namespace flow2d {
 
 bool small_level_supports(size_t w, size_t h) { return w >= 2 && h >= 2 && w <= kMaxSide && h <= kMaxSide; }
 
-// All outer x inner iterations of one level in a single launch; the result is written to out_du / out_dv.
-int launch_small_level(flow2d_context* ctx, int constancy, const float* f0, const float* f1, const float* u,
-                       const float* v, size_t w, size_t h, size_t pitch_bytes, float hx, float hy, float alpha,
-                       float e_smooth, float e_data, size_t outer, size_t inner, float* out_du, float* out_dv)
+// All outer x inner iterations of one level in a single launch per instance; the result is written to `out`.
+int launch_small_level(const flow2d_context* ctx, const SolveLevel& level, size_t outer, size_t inner, Pair out)
 {
-    if (!small_level_supports(w, h)) return FLOW2D_ERR_UNSUPPORTED;
-    if (ctx->batch_count > 1) {  // one workgroup per instance, one launch each
-        const unsigned n = ctx->batch_count;
-        const size_t s = ctx->batch_stride_floats;
-        ctx->batch_count = 1;
-        int st = FLOW2D_OK;
-        for (unsigned b = 0; b < n && st == FLOW2D_OK; ++b)
-            st = launch_small_level(ctx, constancy, f0 + b * s, f1 + b * s, u + b * s, v + b * s, w, h, pitch_bytes, hx, hy,
-                                    alpha, e_smooth, e_data, outer, inner, out_du + b * s, out_dv + b * s);
-        ctx->batch_count = n;
-        return st;
-    }
-    SmallArgs a{f0, f1, u, v, out_du, out_dv, (int)w, (int)h, (int)(pitch_bytes / 4), (int)outer, (int)inner,
-                hx, hy, alpha, e_smooth, e_data, 0, 0};
-    const dim3 block(kMaxSide, 1024 / kMaxSide);
-    const bool grad = constancy != FLOW2D_CONSTANCY_GREY;
-    a.untiled = constancy == FLOW2D_CONSTANCY_GRADIENT_UNTILED ? 1 : 0;
-    a.log = constancy == FLOW2D_CONSTANCY_LOG_DERIVATIVES ? 1 : 0;
-    const int px = h <= 16 ? 1 : (h <= 32 ? 2 : 4);
-    if (px == 1)
-        grad ? small_level_kernel<true, 1><<<1, block, 0, ctx->stream>>>(a)
-             : small_level_kernel<false, 1><<<1, block, 0, ctx->stream>>>(a);
-    else if (px == 2)
-        grad ? small_level_kernel<true, 2><<<1, block, 0, ctx->stream>>>(a)
-             : small_level_kernel<false, 2><<<1, block, 0, ctx->stream>>>(a);
-    else
-        grad ? small_level_kernel<true, 4><<<1, block, 0, ctx->stream>>>(a)
-             : small_level_kernel<false, 4><<<1, block, 0, ctx->stream>>>(a);
-    FLOW2D_CHECK_LAUNCH();
-    return FLOW2D_OK;
+    if (!small_level_supports(level.w, level.h)) return FLOW2D_ERR_UNSUPPORTED;
+    return for_each_instance(
+        ctx, level, [=](const flow2d_context* c, const SolveLevel& l, Pair out) { return small_level_one(c, l, outer, inner, out); }, out);
 }
 
 }  // namespace flow2d

@@ -16,7 +16,7 @@
 #include <cmath>
 #include <cstdlib>
 
-#include "common.hpp"
+#include "solver.hpp"
 #include "solver_math.hpp"
 
 namespace {
@@ -265,39 +265,18 @@ __global__ __launch_bounds__(kThreads, 8) void tile_outer_kernel(TileArgs a)
     }
 }
 
-template <int TX, int TY, int kThreads, bool POW2, bool SOR>
-void launch_tiles_sor(int grad, dim3 grid, hipStream_t stream, const TileArgs& a)
-{
-    if (grad == 1)
-        tile_outer_kernel<TX, TY, 1, kThreads, POW2, SOR><<<grid, kThreads, 0, stream>>>(a);
-    else if (grad == 2)
-        tile_outer_kernel<TX, TY, 2, kThreads, POW2, SOR><<<grid, kThreads, 0, stream>>>(a);
-    else
-        tile_outer_kernel<TX, TY, 0, kThreads, POW2, SOR><<<grid, kThreads, 0, stream>>>(a);
-}
-template <int TX, int TY, int kThreads, bool POW2>
-void launch_tiles_pow2(int grad, dim3 grid, hipStream_t stream, const TileArgs& a)
-{
-    if (a.sor_omega != 0.f)
-        launch_tiles_sor<TX, TY, kThreads, POW2, true>(grad, grid, stream, a);
-    else
-        launch_tiles_sor<TX, TY, kThreads, POW2, false>(grad, grid, stream, a);
-}
-
-// true when x is a normal power of two whose reciprocal (and 1/(2x), 1/(4x)) is exactly representable
-bool is_power_of_two(float x)
-{
-    int e = 0;
-    return x > 0.f && std::frexp(x, &e) == 0.5f && e > -100 && e < 100;
-}
-
+// One launch of TX x TY tiles: the kernel by [data term: GRAD 0, 1, 2][POW2][SOR].
 template <int TX, int TY, int kThreads>
-void launch_tiles(int grad, dim3 grid, hipStream_t stream, const TileArgs& a)
+void launch_tiles(const flow2d_context* ctx, int grad, const TileArgs& a)
 {
-    if (is_power_of_two(a.hx) && is_power_of_two(a.hy))
-        launch_tiles_pow2<TX, TY, kThreads, true>(grad, grid, stream, a);
-    else
-        launch_tiles_pow2<TX, TY, kThreads, false>(grad, grid, stream, a);
+#define FLOW2D_TILE_ROW(G)                                                                                                        \
+    {{tile_outer_kernel<TX, TY, G, kThreads, false, false>, tile_outer_kernel<TX, TY, G, kThreads, false, true>},                \
+     {tile_outer_kernel<TX, TY, G, kThreads, true, false>, tile_outer_kernel<TX, TY, G, kThreads, true, true>}}
+    static void (*const kernels[3][2][2])(TileArgs) = {FLOW2D_TILE_ROW(0), FLOW2D_TILE_ROW(1), FLOW2D_TILE_ROW(2)};
+#undef FLOW2D_TILE_ROW
+    const bool pow2 = flow2d::is_power_of_two(a.hx) && flow2d::is_power_of_two(a.hy);
+    const dim3 grid(flow2d::div_up(a.w, TX), flow2d::div_up(a.h, TY), ctx->batch_count);
+    kernels[grad][pow2][a.sor_omega != 0.f]<<<grid, kThreads, 0, ctx->stream>>>(a);
 }
 
 }  // namespace
@@ -311,18 +290,16 @@ bool tiled_supports(int constancy, size_t inner)
             constancy == FLOW2D_CONSTANCY_GRADIENT_UNTILED);
 }
 
-// One outer iteration: reads du/dv (previous outer iteration, unless zero_increment), writes out_du/out_dv.
-// sor_omega != 0: the `inner` stages are red-black half-sweeps (an even number: inner / 2 iterations).
-int launch_tiled_outer(flow2d_context* ctx, int constancy, const float* f0, const float* f1, const float* u,
-                       const float* v, const float* du, const float* dv, size_t w, size_t h, size_t pitch_bytes, float hx,
-                       float hy, float alpha, float e_smooth, float e_data, size_t inner, float* out_du, float* out_dv,
-                       bool zero_increment, float sor_omega)
+// One outer iteration: reads `in` (previous outer iteration, unless zero_increment), writes `out`.
+// level.sor_omega != 0: the `stages` are red-black half-sweeps (an even number: stages / 2 iterations).
+int launch_tiled_outer(const flow2d_context* ctx, const SolveLevel& l, ConstPair in, Pair out, size_t stages, bool zero_increment)
 {
-    if (!tiled_supports(constancy, inner) || (sor_omega != 0.f && (inner & 1))) return FLOW2D_ERR_UNSUPPORTED;
-    TileArgs a{f0, f1, u, v, du, dv, out_du, out_dv, (int)w, (int)h, (int)(pitch_bytes / 4), (int)inner,
-               zero_increment ? 1 : 0, hx, hy, alpha, e_smooth, e_data, sor_omega,
-               static_cast<unsigned long long>(ctx->batch_stride_floats)};
-    const int grad = constancy == FLOW2D_CONSTANCY_GRADIENT ? 1 : (constancy == FLOW2D_CONSTANCY_GRADIENT_UNTILED ? 2 : 0);
+    if (!tiled_supports(l.constancy, stages) || (l.sor_omega != 0.f && (stages & 1))) return FLOW2D_ERR_UNSUPPORTED;
+    const size_t w = l.w, h = l.h;
+    const TileArgs a{l.f0, l.f1, l.u, l.v, in.du, in.dv, out.du, out.dv, (int)w, (int)h, (int)(l.pitch_bytes / 4), (int)stages,
+                     zero_increment ? 1 : 0, l.hx, l.hy, l.alpha, l.e_smooth, l.e_data, l.sor_omega,
+                     static_cast<unsigned long long>(ctx->batch_stride_floats)};
+    const int grad = l.constancy == FLOW2D_CONSTANCY_GRADIENT ? 1 : (l.constancy == FLOW2D_CONSTANCY_GRADIENT_UNTILED ? 2 : 0);
     // Tile size by level size (measured on MI355X, level solve of 10 x 5, Grey / Gradient, ms; fused strips for comparison):
     //            8x8            16x16          32x32          strips
     //   64^2     0.052 / 0.055  0.061 / 0.064                 0.110 / 0.120
@@ -345,11 +322,11 @@ int launch_tiled_outer(flow2d_context* ctx, int constancy, const float* f0, cons
 #endif
     const bool tiny = w * h <= 160 * 160, mid = w * h <= 352 * 352;
     if (variant == 1 || (variant == 0 && tiny))
-        launch_tiles<8, 8, 512>(grad, dim3(div_up(w, 8), div_up(h, 8), ctx->batch_count), ctx->stream, a);
+        launch_tiles<8, 8, 512>(ctx, grad, a);
     else if (variant == 2 || (variant == 0 && mid))
-        launch_tiles<16, 16, 1024>(grad, dim3(div_up(w, 16), div_up(h, 16), ctx->batch_count), ctx->stream, a);
+        launch_tiles<16, 16, 1024>(ctx, grad, a);
     else
-        launch_tiles<32, 32, 1024>(grad, dim3(div_up(w, 32), div_up(h, 32), ctx->batch_count), ctx->stream, a);
+        launch_tiles<32, 32, 1024>(ctx, grad, a);
     FLOW2D_CHECK_LAUNCH();
     return FLOW2D_OK;
 }

@@ -28,7 +28,9 @@ Which test holds which entry of include/flow2d_c_abi.h (every FLOW2D_API functio
   flow2d_solve_2d_log                                    test_solve_2d_log_against_the_reference_kernel (levels on the 16 x 8
                                                          grid), test_solve_2d_log_batch_equals_lone_calls (off it: a
                                                          consistency check of product against product, not a correctness one)
-  flow2d_solve_level                                     test_solve_level, test_solve_level_auto_leaves_the_tiles_in_a_group
+  flow2d_solve_level                                     test_solve_level, test_solve_level_auto_leaves_the_tiles_in_a_group,
+                                                         test_solve_level_log_batch_equals_lone_calls (the LogDerivatives term:
+                                                         product against product, as for flow2d_solve_2d_log)
   flow2d_memset_2d, flow2d_copy_d2d                      test_memset_2d, test_copy_d2d
   flow2d_consistency_2d, flow2d_interpolate_2d,
   flow2d_flow_error_2d                                   test_newest_entries_padded_strides (contiguous strides: their own files)
@@ -564,6 +566,62 @@ def test_solve_level_auto_leaves_the_tiles_in_a_group(ctx, flow2d, oracle, const
     used = [r.algorithm for r in ctx.timing_records()]
     assert used == [flow2d.SOLVER_FUSED, flow2d.SOLVER_TILED], used  # the group's call, then the lone one
     ctx.timing_enable(0)
+
+
+_LONE_LOG_LEVELS = {}  # (algorithm, outer, inner, instance) -> (du, dv, result_in_temp) of the lone call, shared by the layouts
+
+
+@pytest.mark.parametrize("omega", [0.0, 1.4])
+@pytest.mark.parametrize("count,kind", [(3, "rows"), (2, "bytes")])
+@pytest.mark.parametrize("outer,inner", ITERATIONS[:2])
+@pytest.mark.parametrize("algorithm", [1, 2, 3, 4, 0])
+def test_solve_level_log_batch_equals_lone_calls(ctx, flow2d, oracle, algorithm, outer, inner, count, kind, omega):
+    """The level loop with the LogDerivatives term under a batch.  The oracle takes its log from the CPU's libm, so like
+    test_solve_2d_log_batch_equals_lone_calls this is a CONSISTENCY check (lone calls are held to the reference's own kernel
+    by tests/test_gpu_reference.py::test_solve_level): every instance of the group's call is the lone call on that instance's
+    planes, bit for bit, *result_in_temp is the lone call's, and nothing outside the level rectangles is written
+    (check_level).  The term has neither LDS tiles nor a red-black form: those requests are refused with
+    FLOW2D_ERR_UNSUPPORTED and leave the context in batch mode."""
+    w, h, cw, ch = LEVEL_SIZES[1]
+    stride, lone_stride = stride_of(kind, pitch_of(cw), ch), pitch_of(cw) * ch
+    f0, f1, u, v, _, _ = fields(oracle, w, h, count, 29)
+    what = "solve_level, log term, algorithm %d %dx%d omega %g" % (algorithm, outer, inner, omega)
+
+    def solve(planes, written):
+        return ctx.solve_level(*planes, *written, w, h, HX, HY, 3.5, 0.001, 0.001, outer, inner, flow2d.LOG_DERIVATIVES, algorithm,
+                               container_height=ch, sor_omega=omega)
+
+    d = [t.fill(x) for t, x in zip(talls(ctx, cw, ch, count, stride, 4), (f0, f1, u, v))]
+    written = talls(ctx, cw, ch, count, stride, 6)  # du, dv, phi, ksi, tdu, tdv
+    if algorithm == 4 or omega:
+        x, y = Tall(ctx, cw, ch, count, stride).fill(u), Tall(ctx, cw, ch, count, stride).fill(v)
+        with ctx.set_batch(count, stride):
+            with pytest.raises(flow2d.Flow2DError) as e:
+                solve(d, written)
+            assert e.value.status == 5
+            ctx.add(x, y, w, h)  # count and stride are still in force: every instance gets its sum
+        ctx.synchronize()
+        x.check([oracle.add(a, b, w, h) for a, b in zip(u, v)], what + ": add_2d behind the refusal")
+        return
+    for b in range(count):  # (instance b's planes do not depend on the count: fields() seeds every instance by its index)
+        if (algorithm, outer, inner, b) not in _LONE_LOG_LEVELS:
+            one = [t.fill([x[b]]) for t, x in zip(talls(ctx, cw, ch, 1, lone_stride, 4), (f0, f1, u, v))]
+            o = talls(ctx, cw, ch, 1, lone_stride, 6)
+            pair = solve(one, o)
+            ctx.synchronize()
+            assert pair in ((o[0], o[1]), (o[4], o[5]))
+            _LONE_LOG_LEVELS[algorithm, outer, inner, b] = tuple(t.rects(t.download())[0, :h, :w].view(F32).copy() for t in pair) + (pair[0] is o[4],)
+    lone = [_LONE_LOG_LEVELS[algorithm, outer, inner, b] for b in range(count)]
+    with ctx.set_batch(count, stride):
+        pair = solve(d, written)
+    ctx.synchronize()
+    du, dv, phi, ksi, tdu, tdv = written
+    assert pair in ((du, dv), (tdu, tdv))
+    in_temp = pair[0] is tdu
+    assert [q[2] for q in lone] == [in_temp] * count, what + ": *result_in_temp of the group's call and of the lone calls"
+    check_level(pair, (du, dv) if in_temp else (tdu, tdv), (phi, ksi), [[q[0] for q in lone], [q[1] for q in lone]], w, h, ch, what)
+    for t in d:
+        t.check(None, what + ": an input")
 
 
 # ---- memory ---------------------------------------------------------------------------------------------------------------
