@@ -248,6 +248,29 @@ CORRELATION_RECORD_BYTES = 32  # FLOW2D_CORRELATION_RECORD_BYTES, checked by a s
 assert C.sizeof(CorrelationRecord) == CORRELATION_RECORD_BYTES
 
 
+class PriorReport(C.Structure):
+    """OpticalFlow2D::PriorReport: what a pyramid started from a prior flow reports -- the level it started at, the levels it ran
+    and the count of prior pixels that were not finite (they entered as zero)."""
+    _fields_ = [("start_level", C.c_size_t), ("levels_run", C.c_size_t), ("not_finite", C.c_ulonglong)]
+
+    def summary(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+def prior_start_level(width, height, levels, scale, reach=2.0, level=None):
+    """The level at which a pyramid of `levels` levels with scale factor `scale` over a width x height frame starts from a prior
+    flow (OpticalFlow2D::PriorStartLevel): the smallest l with reach * scale^l <= 1 in the float arithmetic of the level geometry,
+    at most the top level of the unseeded run; `level` (>= 0) replaces the rule and is clamped alike.  ValueError for a reach that
+    is not finite and > 0, a negative level, or parameters with which no level runs.  Needs no device."""
+    start = C.c_size_t()
+    if level is not None and int(level) < 0:
+        raise ValueError("prior level %d (>= 0)" % int(level))
+    if host_lib().flow2d_host_prior_start_level(width, height, levels, scale, float(reach), -1 if level is None else int(level),
+                                                C.byref(start)):
+        raise ValueError("no start level for reach %g, level %s, %d levels at scale %g" % (reach, level, levels, scale))
+    return start.value
+
+
 def correlation_grid(width, height, radius, spacing):
     """(nw, nh): the node grid of flow2d_correlate_2d (flow2d_correlation_grid).  Needs no device."""
     nw, nh = C.c_size_t(), C.c_size_t()
@@ -377,6 +400,8 @@ def hip_lib():
             L.flow2d_correlation_grid.argtypes = [sz, sz, i, i, C.POINTER(sz), C.POINTER(sz)]
             L.flow2d_correlate_2d.argtypes = [vp, vp, vp, sz, sz, sz, f, f, i, i, i, f, vp, vp, vp, sz, vp]
             L.flow2d_expand_nodes_2d.argtypes = [vp, vp, vp, sz, sz, sz, i, i, vp, vp, sz, sz, sz]
+        if hasattr(L, "flow2d_prior_registration_2d"):  # (absent from libraries of earlier rounds loaded for an A/B)
+            L.flow2d_prior_registration_2d.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp, sz, sz, sz, f, f, vp, vp]
         if hasattr(L, "flow2d_segment_motion_2d"):  # (absent from libraries of earlier rounds loaded for an A/B)
             L.flow2d_segment_motion_workspace_bytes.restype = sz
             L.flow2d_segment_motion_workspace_bytes.argtypes = [sz, sz, sz]
@@ -1002,6 +1027,32 @@ class Context:
         _check(hip_lib().flow2d_upsample_registration_half_2d(self.handle, u.ptr, v.ptr, in_w, in_h, out_u.ptr, out_v.ptr, f0.ptr, f1.ptr,
                                                               w, h, f0.pitch, hx, hy, out.ptr), "flow2d_upsample_registration_half_2d")
 
+    def prior_records(self, instances=1):
+        """A Plane for the `instances` counts (one unsigned 64-bit integer each) of prior_registration, device memory."""
+        return self.plane(max(2 * instances, 4), 1)
+
+    def read_prior_records(self, record, instances=1):
+        """The counts of a prior_records Plane as a list of ints (synchronises)."""
+        return [int(c) for c in record.download(max(2 * instances, 4), 1).view(np.uint64)[0, :instances]]
+
+    def prior_registration(self, prior_u, prior_v, in_w, in_h, out_u, out_v, f0, f1, w, h, hx, hy, out, record=True):
+        """The first level of a pyramid started from a prior flow (flow2d_prior_registration_2d): the in_w x in_h prior (prior_u,
+        prior_v), in full-resolution pixels, made finite -- a pixel where either component is not finite counts as (0, 0) --,
+        resampled to w x h into out_u / out_v, and f1 warped by that into `out`: one launch.  record: True -- the count of prior
+        pixels that were not finite is read back and returned (synchronises) --, or a prior_records Plane of the caller's (a
+        lock-step batch takes one count per instance), which stays on the device."""
+        own = record is True
+        rec = self.prior_records(1) if own else record
+        try:
+            _check(hip_lib().flow2d_prior_registration_2d(self.handle, prior_u.ptr, prior_v.ptr, in_w, in_h, out_u.ptr, out_v.ptr, f0.ptr,
+                                                          f1.ptr, w, h, f0.pitch, hx, hy, out.ptr, rec.ptr if rec is not None else None),
+                   "flow2d_prior_registration_2d")
+            return self.read_prior_records(rec, 1)[0] if own else None
+        finally:
+            if own:
+                rec.free()
+                self._planes.remove(rec)
+
     def resample_x_levels(self, src, packed, in_w, h, widths, columns, src_b=None, packed_b=None):
         """x pass for several output widths in one trip over `src`; level l lands in columns[l] .. of `packed`."""
         n = len(widths)
@@ -1178,6 +1229,18 @@ def host_lib():
             L.flow2d_host_correlation_args_ok.argtypes = [sz, sz, f, f, i, i, i, f]
             L.flow2d_host_correlate.argtypes = [vp, fp, fp, i, i, i, f, fp, fp, fp, cr, fp, fp, fp]
             L.flow2d_host_correlate_device.argtypes = [vp, vp, vp, f, f, i, i, i, f, vp, vp, vp, cr, vp, vp]
+        if hasattr(L, "flow2d_host_compute_flow_from_prior"):
+            cr, pr, hp = C.POINTER(CorrelationRecord), C.POINTER(PriorReport), C.POINTER(HostParams)
+            L.flow2d_host_prior_start_level.argtypes = [sz, sz, sz, f, f, i, C.POINTER(sz)]
+            L.flow2d_host_compute_flow_from_prior_device.argtypes = [vp] * 7 + [hp, f, i, pr]
+            L.flow2d_host_compute_flow_from_prior.argtypes = [vp, fp, fp, fp, fp, fp, fp, hp, f, i, pr, fp]
+            L.flow2d_host_compute_flow_correlation_seeded_device.argtypes = [vp, vp, vp, f, f, i, i, i, f, vp, vp, hp, f, i, vp, vp, vp, cr,
+                                                                             pr, vp, vp]
+            L.flow2d_host_compute_flow_correlation_seeded.argtypes = [vp, fp, fp, i, i, i, f, fp, fp, hp, f, i, fp, fp, fp, cr, pr, fp, fp,
+                                                                      fp, fp]
+            L.flow2d_host_bidirectional_refuses_prior.argtypes = [vp, hp]
+            L.flow2d_host_flow_create_group.restype = vp
+            L.flow2d_host_flow_create_group.argtypes = [sz, sz, i, sz]
         if hasattr(L, "flow2d_host_segment_motion"):
             d, u32 = C.c_double, C.c_uint
             head = [i, d, i, i, f, f, u32, C.POINTER(GlobalMotion), C.POINTER(SegmentSummary), C.POINTER(MotionRegion),
@@ -1254,7 +1317,9 @@ def _ptr_array(q):
 class OpticalFlow:
     """OpticalFlow2D of the host layer (Initialize / ComputeFlow / ComputeFlowDevice / Destroy)."""
 
-    def __init__(self, width, height, constancy=GREY, device=0, ctx=None, silent=True, lone=True):
+    def __init__(self, width, height, constancy=GREY, device=0, ctx=None, silent=True, lone=True, group_size=1):
+        """group_size > 1: an object initialised for lock-step groups (OpticalFlow2D::group_size; every device plane it is handed is
+        then group_size containers tall)."""
         L = host_lib()
         self._adopted = ctx is not None
         if ctx is not None:
@@ -1262,7 +1327,10 @@ class OpticalFlow:
         elif L.flow2d_host_init_device(device) != 0:
             raise Flow2DError(2, "InitDeviceContext")
         self.width, self.height = width, height
-        self.handle = L.flow2d_host_flow_create(width, height, _HOST_CONSTANCY[constancy], int(silent), int(bool(lone)))
+        if group_size > 1:
+            self.handle = L.flow2d_host_flow_create_group(width, height, _HOST_CONSTANCY[constancy], int(group_size))
+        else:
+            self.handle = L.flow2d_host_flow_create(width, height, _HOST_CONSTANCY[constancy], int(silent), int(bool(lone)))
         if not self.handle:
             if self._adopted:
                 L.flow2d_host_adopt_context(None)
@@ -1628,6 +1696,78 @@ class OpticalFlow:
         if rc:
             raise Flow2DError(rc, "OpticalFlow2D::CorrelateDevice")
         return rec
+
+    @staticmethod
+    def _prior_level(level):
+        if level is not None and int(level) < 0:
+            raise ValueError("prior level %d (>= 0)" % int(level))
+        return -1 if level is None else int(level)
+
+    def compute_flow_from_prior(self, frame_0, frame_1, prior_u, prior_v, params, reach=2.0, level=None):
+        """OpticalFlow2D::ComputeFlowFromPrior: the flow of the host pair from a pyramid that starts from the prior flow (prior_u,
+        prior_v) -- full-resolution pixels, [height, width]; pixels that are not finite enter as zero -- at the level
+        prior_start_level(..., reach, level).  Returns (u, v, PriorReport, device_ms)."""
+        f0, f1 = self._pair(frame_0, frame_1)
+        pu, pv = self._pair(prior_u, prior_v)
+        u, v = np.empty_like(f0), np.empty_like(f0)
+        report, ms = PriorReport(), C.c_float()
+        rc = host_lib().flow2d_host_compute_flow_from_prior(self.handle, _fptr(f0), _fptr(f1), _fptr(pu), _fptr(pv), _fptr(u), _fptr(v),
+                                                            C.byref(params), float(reach), self._prior_level(level), C.byref(report),
+                                                            C.byref(ms))
+        if rc:
+            raise Flow2DError(rc, "OpticalFlow2D::ComputeFlowFromPrior")
+        return u, v, report, ms.value
+
+    def compute_flow_from_prior_device(self, dev_f0, dev_f1, dev_prior_u, dev_prior_v, dev_u, dev_v, params, reach=2.0, level=None,
+                                       report=True):
+        """OpticalFlow2D::ComputeFlowFromPriorDevice: raw device addresses of pitched containers.  With report the count of
+        non-finite prior pixels is read back and the PriorReport returned (synchronises); without, the call only queues."""
+        rep = PriorReport() if report else None
+        rc = host_lib().flow2d_host_compute_flow_from_prior_device(self.handle, dev_f0, dev_f1, dev_prior_u, dev_prior_v, dev_u, dev_v,
+                                                                   C.byref(params), float(reach), self._prior_level(level),
+                                                                   C.byref(rep) if report else None)
+        if rc:
+            raise Flow2DError(rc, "OpticalFlow2D::ComputeFlowFromPriorDevice")
+        return rep
+
+    def compute_flow_correlation_seeded(self, frame_0, frame_1, params, radius=7, search=8, spacing=8, min_score=-1.0, reach=2.0,
+                                        level=None):
+        """OpticalFlow2D::ComputeFlowCorrelationSeeded: window correlation of the host pair (as correlate), its node field expanded
+        to the frame's grid, and the flow from a pyramid that starts from that field (as compute_flow_from_prior; pixels the
+        expansion leaves NaN enter as zero and are counted).  Returns a dict: u, v, report (PriorReport), nodes (u, v, score),
+        record (CorrelationRecord), prior (u, v: the expanded field), lo_scale, ms."""
+        f0, f1 = self._pair(frame_0, frame_1)
+        nw, nh = correlation_grid(self.width, self.height, radius, spacing)
+        nodes = [np.empty((nh, nw), np.float32) for _ in range(3)]
+        u, v, pu, pv = (np.empty_like(f0) for _ in range(4))
+        record, report, lo_scale, ms = CorrelationRecord(), PriorReport(), (C.c_float * 2)(), C.c_float()
+        rc = host_lib().flow2d_host_compute_flow_correlation_seeded(
+            self.handle, _fptr(f0), _fptr(f1), int(radius), int(search), int(spacing), float(min_score), _fptr(u), _fptr(v),
+            C.byref(params), float(reach), self._prior_level(level), _fptr(nodes[0]), _fptr(nodes[1]), _fptr(nodes[2]), C.byref(record),
+            C.byref(report), _fptr(pu), _fptr(pv), lo_scale, C.byref(ms))
+        if rc:
+            raise Flow2DError(rc, "OpticalFlow2D::ComputeFlowCorrelationSeeded")
+        return {"u": u, "v": v, "report": report, "nodes": tuple(nodes), "record": record, "prior": (pu, pv),
+                "lo_scale": (lo_scale[0], lo_scale[1]), "ms": ms.value}
+
+    def compute_flow_correlation_seeded_device(self, dev_f0, dev_f1, dev_u, dev_v, params, lo, scale, radius=7, search=8, spacing=8,
+                                               min_score=-1.0, reach=2.0, level=None, dev_nodes=None, dev_score=None, dev_prior=None):
+        """OpticalFlow2D::ComputeFlowCorrelationSeededDevice: device frames in, the flow into (dev_u, dev_v).  dev_nodes (a (u, v)
+        pair), dev_score and dev_prior (a (u, v) pair for the expanded field) are optional device planes of the container's size.
+        Returns (PriorReport, CorrelationRecord); synchronises."""
+        report, record = PriorReport(), CorrelationRecord()
+        nd, pr = dev_nodes or (None, None), dev_prior or (None, None)
+        rc = host_lib().flow2d_host_compute_flow_correlation_seeded_device(
+            self.handle, dev_f0, dev_f1, float(lo), float(scale), int(radius), int(search), int(spacing), float(min_score), dev_u, dev_v,
+            C.byref(params), float(reach), self._prior_level(level), nd[0], nd[1], dev_score, C.byref(record), C.byref(report), pr[0],
+            pr[1])
+        if rc:
+            raise Flow2DError(rc, "OpticalFlow2D::ComputeFlowCorrelationSeededDevice")
+        return report, record
+
+    def bidirectional_refuses_prior(self, params):
+        """Whether ComputeFlowBidirectional refuses a bag that carries the keys of a prior flow (it has no backward prior)."""
+        return host_lib().flow2d_host_bidirectional_refuses_prior(self.handle, C.byref(params)) == 1
 
     def stabilise_sequence(self, frames, params, reference_index=0, model=MOTION_AFFINE, sigma=0.5, iterations=5, masks=False,
                            fill=0.0):

@@ -69,6 +69,18 @@ struct Bag {
     OperationParameters bag;
 };
 
+// ... with the keys of a run from a prior flow: prior_reach, and prior_level when one is given (>= 0 from a caller; -1 = not given;
+// anything below is passed on so that the entry refuses it)
+struct PriorBag : Bag {
+    PriorBag(const flow2d_host_params& params, float prior_reach, int prior_level) : Bag(params), reach(prior_reach), level(prior_level)
+    {
+        bag.PushValuePtr("prior_reach", &reach);
+        if (level != -1) bag.PushValuePtr("prior_level", &level);
+    }
+    float reach;
+    int level;
+};
+
 DevicePtr dp(void* q) { return static_cast<DevicePtr>(reinterpret_cast<uintptr_t>(q)); }
 
 // the `n` device addresses of `q` (none for a null array)
@@ -156,6 +168,23 @@ HOST_API flow2d_host_flow* flow2d_host_flow_create(size_t width, size_t height, 
     if (!h) return nullptr;
     h->flow.silent = silent != 0;
     h->flow.lone = lone != 0;
+    DataSize3 size = {width, height, 1};
+    if (!h->flow.Initialize(size, static_cast<DataConstancy>(constancy))) {
+        delete h;
+        return nullptr;
+    }
+    h->width = width;
+    h->height = height;
+    return h;
+}
+
+// ... initialised for lock-step groups of `group_size` pairs (OpticalFlow2D::group_size): what the entries that refuse groups refuse
+HOST_API flow2d_host_flow* flow2d_host_flow_create_group(size_t width, size_t height, int constancy, size_t group_size)
+{
+    flow2d_host_flow* h = new (std::nothrow) flow2d_host_flow();
+    if (!h) return nullptr;
+    h->flow.silent = true;
+    h->flow.group_size = group_size;
     DataSize3 size = {width, height, 1};
     if (!h->flow.Initialize(size, static_cast<DataConstancy>(constancy))) {
         delete h;
@@ -600,6 +629,137 @@ HOST_API int flow2d_host_correlate_device(flow2d_host_flow* h, void* dev_frame_0
                                    dp(dev_node_v), dp(dev_node_score), record, dp(dev_flow_u), dp(dev_flow_v))
                ? 0
                : 2;
+}
+
+// ---- the pyramid started from a prior flow ------------------------------------------------------------------------------------
+// OpticalFlow2D::PriorReport as the facade hands it out
+struct flow2d_host_prior_report {
+    size_t start_level, levels_run;
+    unsigned long long not_finite;
+};
+
+namespace {
+void Report(flow2d_host_prior_report* out, const OpticalFlow2D::PriorReport& r)
+{
+    if (out) *out = {r.start_level, r.levels_run, r.not_finite};
+}
+}  // namespace
+
+// OpticalFlow2D::PriorStartLevel: the level a pyramid from a prior starts at (prior_level -1: the rule from `reach`).  0 and *start
+// written, or 1 when the arguments are refused.  Needs no device.
+HOST_API int flow2d_host_prior_start_level(size_t width, size_t height, size_t warp_levels_count, float warp_scale_factor, float reach,
+                                           int prior_level, size_t* start)
+{
+    return OpticalFlow2D::PriorStartLevel(width, height, warp_levels_count, warp_scale_factor, reach, prior_level, start) ? 0 : 1;
+}
+
+// OpticalFlow2D::ComputeFlowFromPriorDevice: frames, prior and flow in pitched device containers.  reach / prior_level: the bag keys
+// prior_reach / prior_level (-1: not given).  With `report` the call synchronises, otherwise it only queues.  0 on success.
+HOST_API int flow2d_host_compute_flow_from_prior_device(flow2d_host_flow* h, void* dev_frame_0, void* dev_frame_1, void* dev_prior_u,
+                                                        void* dev_prior_v, void* dev_flow_u, void* dev_flow_v,
+                                                        const flow2d_host_params* params, float reach, int prior_level,
+                                                        flow2d_host_prior_report* report)
+{
+    if (!h || !params) return 1;
+    PriorBag bag(*params, reach, prior_level);
+    h->flow.timing_mode = 0;
+    OpticalFlow2D::PriorReport r;
+    if (!h->flow.ComputeFlowFromPriorDevice(dp(dev_frame_0), dp(dev_frame_1), dp(dev_prior_u), dp(dev_prior_v), dp(dev_flow_u),
+                                            dp(dev_flow_v), bag, report ? &r : nullptr))
+        return 2;
+    Report(report, r);
+    return 0;
+}
+
+// OpticalFlow2D::ComputeFlowFromPrior on tight host images.  0 on success, 2 when the run delivered no flow.
+HOST_API int flow2d_host_compute_flow_from_prior(flow2d_host_flow* h, const float* frame_0, const float* frame_1, const float* prior_u,
+                                                 const float* prior_v, float* flow_u, float* flow_v, const flow2d_host_params* params,
+                                                 float reach, int prior_level, flow2d_host_prior_report* report, float* total_ms)
+{
+    if (!h || !frame_0 || !frame_1 || !prior_u || !prior_v || !flow_u || !flow_v || !params) return 1;
+    HostImages im(h);
+    Data2D *f0 = im.In(frame_0), *f1 = im.In(frame_1), *pu = im.In(prior_u), *pv = im.In(prior_v);
+    Data2D *u = im.Out(flow_u, im.Always), *v = im.Out(flow_v, im.Always);
+    PriorBag bag(*params, reach, prior_level);
+    OpticalFlow2D::PriorReport r;
+    h->flow.ComputeFlowFromPrior(*f0, *f1, *pu, *pv, *u, *v, bag, &r);
+    Report(report, r);
+    return im.Finish(h->flow, total_ms);
+}
+
+// OpticalFlow2D::ComputeFlowCorrelationSeededDevice: the correlation's arguments as for flow2d_host_correlate_device; node planes,
+// records and the copy of the expanded field (dev_prior_u / dev_prior_v) optional.  Synchronises.  0 on success, 1 for a null or
+// refused argument, 2 when the run failed.
+HOST_API int flow2d_host_compute_flow_correlation_seeded_device(flow2d_host_flow* h, void* dev_frame_0, void* dev_frame_1, float lo,
+                                                                float scale, int radius, int range, int spacing, float min_score,
+                                                                void* dev_flow_u, void* dev_flow_v, const flow2d_host_params* params,
+                                                                float reach, int prior_level, void* dev_node_u, void* dev_node_v,
+                                                                void* dev_node_score, flow2d_correlation_record* record,
+                                                                flow2d_host_prior_report* report, void* dev_prior_u, void* dev_prior_v)
+{
+    if (!h || !params || !dev_frame_0 || !dev_frame_1 || !dev_flow_u || !dev_flow_v || (dev_prior_u == nullptr) != (dev_prior_v == nullptr) ||
+        !OpticalFlow2D::CorrelationArgsOk(h->width, h->height, lo, scale, radius, range, spacing, min_score))
+        return 1;
+    PriorBag bag(*params, reach, prior_level);
+    h->flow.timing_mode = 0;
+    OpticalFlow2D::PriorReport r;
+    if (!h->flow.ComputeFlowCorrelationSeededDevice(dp(dev_frame_0), dp(dev_frame_1), lo, scale, radius, range, spacing, min_score,
+                                                    dp(dev_flow_u), dp(dev_flow_v), bag, dp(dev_node_u), dp(dev_node_v), dp(dev_node_score),
+                                                    record, &r, dp(dev_prior_u), dp(dev_prior_v)))
+        return 2;
+    Report(report, r);
+    return 0;
+}
+
+// OpticalFlow2D::ComputeFlowCorrelationSeeded on tight host images: node_u / node_v / node_score (each optional) get nw * nh floats,
+// prior_u / prior_v (optional, both or neither) the expanded field, lo_scale (optional) the two numbers of CorrelationRange.
+HOST_API int flow2d_host_compute_flow_correlation_seeded(flow2d_host_flow* h, const float* frame_0, const float* frame_1, int radius,
+                                                         int range, int spacing, float min_score, float* flow_u, float* flow_v,
+                                                         const flow2d_host_params* params, float reach, int prior_level, float* node_u,
+                                                         float* node_v, float* node_score, flow2d_correlation_record* record,
+                                                         flow2d_host_prior_report* report, float* prior_u, float* prior_v,
+                                                         float* lo_scale, float* total_ms)
+{
+    size_t nw = 0, nh = 0;
+    if (!h || !params || !frame_0 || !frame_1 || !flow_u || !flow_v || (prior_u == nullptr) != (prior_v == nullptr) ||
+        flow2d_correlation_grid(h->width, h->height, radius, spacing, &nw, &nh) != FLOW2D_OK)
+        return 1;
+    HostImages im(h);
+    Data2D *f0 = im.In(frame_0), *f1 = im.In(frame_1);
+    Data2D *u = im.Out(flow_u, im.Always), *v = im.Out(flow_v, im.Always);
+    Data2D *pu = im.Out(prior_u, im.AfterSuccess), *pv = im.Out(prior_v, im.AfterSuccess);
+    float lo = 0.f, scale = 1.f;
+    OpticalFlow2D::CorrelationRange(*f0, *f1, lo, scale);
+    if (!OpticalFlow2D::CorrelationArgsOk(h->width, h->height, lo, scale, radius, range, spacing, min_score)) return 1;
+    Data2D nodes[3] = {Data2D(nw, nh), Data2D(nw, nh), Data2D(nw, nh)};
+    PriorBag bag(*params, reach, prior_level);
+    OpticalFlow2D::PriorReport r;
+    h->flow.ComputeFlowCorrelationSeeded(*f0, *f1, radius, range, spacing, min_score, *u, *v, bag, node_u ? &nodes[0] : nullptr,
+                                         node_v ? &nodes[1] : nullptr, node_score ? &nodes[2] : nullptr, record, &r, pu, pv);
+    const int rc = im.Finish(h->flow, total_ms);
+    if (rc) return rc;
+    Report(report, r);
+    float* dst[3] = {node_u, node_v, node_score};
+    for (int k = 0; k < 3; ++k)
+        if (dst[k]) std::memcpy(dst[k], nodes[k].DataPtr(), nw * nh * sizeof(float));
+    if (lo_scale) {
+        lo_scale[0] = lo;
+        lo_scale[1] = scale;
+    }
+    return 0;
+}
+
+// Whether ComputeFlowBidirectional refuses a bag that carries the keys of a prior (there is no prior for the backward flow): runs it
+// on two zero frames with prior_reach in the bag; 1 when no flow was delivered.
+HOST_API int flow2d_host_bidirectional_refuses_prior(flow2d_host_flow* h, const flow2d_host_params* params)
+{
+    if (!h || !params) return -1;
+    std::vector<Data2D> images;
+    for (int i = 0; i < 8; ++i) images.emplace_back(h->width, h->height);
+    for (size_t i = 0; i < h->width * h->height; ++i) images[0].DataPtr()[i] = images[1].DataPtr()[i] = 0.f;
+    PriorBag bag(*params, 2.f, -1);
+    h->flow.ComputeFlowBidirectional(images[0], images[1], images[2], images[3], images[4], images[5], images[6], images[7], bag);
+    return h->flow.LastRunSucceeded() ? 0 : 1;
 }
 
 // OpticalFlow2D::StabiliseSequence on tight host images: frames = frame_count * width * height floats (frame k at k * width *

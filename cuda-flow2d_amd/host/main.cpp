@@ -67,6 +67,16 @@
 // "nodes", "invalid", "rejected", "unrefined" -- is printed.  With --ground-truth the line "Flow error: {json}" scores the expanded
 // field.  It does not combine with the options that run the variational flow (--backward, --interpolate, --track, --denoise,
 // --global-motion, --segment-motion, --deformation, --refine).  Without --correlation nothing changes.
+// --initial-flow FILE.flo | --correlation-prior R  [--prior-reach P, pixels, finite and > 0, default 2] [--prior-level L, >= 0]
+// start the variational pyramid from a prior flow instead of from zero at its coarsest level (OpticalFlow2D::ComputeFlowFromPrior /
+// ComputeFlowCorrelationSeeded): the prior is a Middlebury file of the frames' size, or the window correlation of the pair with
+// radius R (and --correlation-range / --correlation-spacing / --correlation-min-score as for --correlation) expanded to the frame's
+// grid.  The pyramid starts at the smallest level l with P * scale^l <= 1 (or at L), prior pixels that are not finite enter as zero.
+// The forward files are the usual ones, and one line "Prior: {json}" -- "source", "reach", "start_level", "levels_run",
+// "not_finite" and, for the correlation, "radius", "range", "spacing", "min_score", "lo", "scale", "nw", "nh" and the record's
+// "nodes", "invalid", "rejected", "unrefined" -- is printed.  The two sources exclude each other, and both exclude --correlation
+// and every option that runs flows of its own (--backward, --interpolate, --track, --denoise, --global-motion, --segment-motion,
+// --deformation, --refine): there is no prior for a backward flow.  Without these options nothing changes.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -122,6 +132,11 @@ int main(int argc, char** argv)
     Methods method = Methods::OpticalFlow;  // --correlation R: Methods::Correlation
     int correlation_radius = 0, correlation_range = 8, correlation_spacing = 8;
     float correlation_min_score = -1.f;
+    std::string initial_flow_file;  // --initial-flow FILE.flo
+    int prior_radius = 0;           // --correlation-prior R (0: off)
+    float prior_reach = 2.f;
+    int prior_level = -1;
+    bool prior_option = false;  // --prior-reach or --prior-level was given
     std::string ground_truth_file;
     int device = 0;
     float sor_omega = 0.f;
@@ -267,6 +282,31 @@ int main(int argc, char** argv)
             (guide ? refine_sigma : refine_space) = value;
             ++i;
         }
+        else if (!std::strcmp(argv[i], "--initial-flow") && i + 1 < argc) initial_flow_file = argv[++i];
+        else if (!std::strcmp(argv[i], "--prior-reach")) {
+            char* end = nullptr;
+            const float value = (i + 1 < argc) ? std::strtof(argv[i + 1], &end) : 0.f;
+            if (i + 1 >= argc || end == argv[i + 1] || *end != '\0' || !std::isfinite(value) || !(value > 0.f)) {
+                std::printf("--prior-reach takes a finite number > 0 (pixels the solver is trusted to correct the prior by).\n");
+                return 5;
+            }
+            prior_reach = value;
+            prior_option = true;
+            ++i;
+        }
+        else if (!std::strcmp(argv[i], "--prior-level") || !std::strcmp(argv[i], "--correlation-prior")) {
+            const bool level = !std::strcmp(argv[i], "--prior-level");
+            char* end = nullptr;
+            const long n = (i + 1 < argc) ? std::strtol(argv[i + 1], &end, 10) : 0;
+            if (i + 1 >= argc || end == argv[i + 1] || *end != '\0' || n < (level ? 0 : 1) || n > (level ? 1000 : FLOW2D_CORRELATION_MAX_RADIUS)) {
+                if (level) std::printf("--prior-level takes an integer L >= 0 (the pyramid level the prior enters at).\n");
+                else std::printf("--correlation-prior takes a window radius of 1 .. %d.\n", FLOW2D_CORRELATION_MAX_RADIUS);
+                return 5;
+            }
+            (level ? prior_level : prior_radius) = static_cast<int>(n);
+            if (level) prior_option = true;
+            ++i;
+        }
         else if (!std::strcmp(argv[i], "--correlation") || !std::strcmp(argv[i], "--correlation-range") ||
                  !std::strcmp(argv[i], "--correlation-spacing")) {
             const int which = !std::strcmp(argv[i], "--correlation") ? 0 : !std::strcmp(argv[i], "--correlation-range") ? 1 : 2;
@@ -304,6 +344,22 @@ int main(int argc, char** argv)
     if (method == Methods::Correlation &&
         (backward || interpolate || track_spacing || denoise || global_model >= 0 || segment || deformation || refine_radius)) {
         std::printf("--correlation replaces the variational flow and does not combine with the options that run it.\n");
+        return 5;
+    }
+
+    const bool from_prior = !initial_flow_file.empty() || prior_radius != 0;
+    if (!initial_flow_file.empty() && prior_radius != 0) {
+        std::printf("--initial-flow and --correlation-prior are two sources of one prior: give one of them.\n");
+        return 5;
+    }
+    if (from_prior && (method == Methods::Correlation || backward || interpolate || track_spacing || denoise || global_model >= 0 || segment ||
+                       deformation || refine_radius)) {
+        std::printf("A prior flow seeds the forward flow of the pair: it does not combine with --correlation or with the options that run "
+                    "flows of their own (there is no prior for a backward flow).\n");
+        return 5;
+    }
+    if (prior_option && !from_prior) {
+        std::printf("--prior-reach and --prior-level need a prior: --initial-flow FILE.flo or --correlation-prior R.\n");
         return 5;
     }
 
@@ -397,6 +453,19 @@ int main(int argc, char** argv)
         }
     }
 
+    Data2D prior_u, prior_v;
+    if (!initial_flow_file.empty()) {
+        if (!IOUtils::ReadFlowFLO(initial_flow_file, prior_u, prior_v)) {
+            std::printf("Cannot read the initial flow '%s' (a Middlebury .flo file).\n", initial_flow_file.c_str());
+            return 2;
+        }
+        if (prior_u.Width() != width || prior_u.Height() != height) {
+            std::printf("The initial flow '%s' is %zu x %zu, the frames %zu x %zu.\n", initial_flow_file.c_str(), prior_u.Width(),
+                        prior_u.Height(), width, height);
+            return 2;
+        }
+    }
+
     OpticalFlow2D optical_flow;
     optical_flow.silent = !verbose;
     if (optical_flow.Initialize(data_size, data_constancy)) {
@@ -412,6 +481,10 @@ int main(int argc, char** argv)
         params.PushValuePtr("median_radius", &median_radius);
         params.PushValuePtr("gaussian_sigma", &gaussian_sigma);
         if (sor_omega != 0.f) params.PushValuePtr("solver_sor_omega", &sor_omega);
+        if (from_prior) {
+            params.PushValuePtr("prior_reach", &prior_reach);
+            if (prior_level >= 0) params.PushValuePtr("prior_level", &prior_level);
+        }
         Data2D back_u, back_v, occlusion_0, occlusion_1;
         std::vector<Data2D> between;
         std::vector<float> times;
@@ -456,6 +529,36 @@ int main(int argc, char** argv)
                             correlation_radius, correlation_range, correlation_spacing, correlation_min_score, lo, scale, nw, nh,
                             record.nodes, record.invalid, record.rejected, record.unrefined);
             }
+        } else if (!initial_flow_file.empty()) {
+            OpticalFlow2D::PriorReport report;
+            optical_flow.ComputeFlowFromPrior(frame_0, frame_1, prior_u, prior_v, flow_u, flow_v, params, &report);
+            if (optical_flow.LastRunSucceeded())
+                std::printf("Prior: {\"source\": \"initial-flow\", \"reach\": %.9g, \"start_level\": %zu, \"levels_run\": %zu, "
+                            "\"not_finite\": %llu}\n",
+                            prior_reach, report.start_level, report.levels_run, report.not_finite);
+        } else if (prior_radius) {
+            size_t nw = 0, nh = 0;
+            if (flow2d_correlation_grid(width, height, prior_radius, correlation_spacing, &nw, &nh) != FLOW2D_OK) {
+                std::printf("Error: a %zu x %zu frame is smaller than one correlation window of radius %d.\n", width, height, prior_radius);
+                optical_flow.Destroy();
+                DestroyDeviceContext();
+                return 4;
+            }
+            OpticalFlow2D::PriorReport report;
+            flow2d_correlation_record record = {0, 0, 0, 0};
+            float lo = 0.f, scale = 1.f;
+            OpticalFlow2D::CorrelationRange(frame_0, frame_1, lo, scale);
+            optical_flow.ComputeFlowCorrelationSeeded(frame_0, frame_1, prior_radius, correlation_range, correlation_spacing,
+                                                      correlation_min_score, flow_u, flow_v, params, nullptr, nullptr, nullptr, &record,
+                                                      &report);
+            if (optical_flow.LastRunSucceeded())
+                std::printf("Prior: {\"source\": \"correlation\", \"reach\": %.9g, \"start_level\": %zu, \"levels_run\": %zu, "
+                            "\"not_finite\": %llu, \"radius\": %d, \"range\": %d, \"spacing\": %d, \"min_score\": %.9g, \"lo\": %.9g, "
+                            "\"scale\": %.9g, \"nw\": %zu, \"nh\": %zu, \"nodes\": %llu, \"invalid\": %llu, \"rejected\": %llu, "
+                            "\"unrefined\": %llu}\n",
+                            prior_reach, report.start_level, report.levels_run, report.not_finite, prior_radius, correlation_range,
+                            correlation_spacing, correlation_min_score, lo, scale, nw, nh, record.nodes, record.invalid, record.rejected,
+                            record.unrefined);
         } else if (interpolate) {
             optical_flow.InterpolateFrames(frame_0, frame_1, times.data(), times.size(), between.data(), 2, 0.5f, true, params,
                                            &flow_u, &flow_v, &back_u, &back_v, &occlusion_0, &occlusion_1);

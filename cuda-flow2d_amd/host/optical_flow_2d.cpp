@@ -282,6 +282,15 @@ bool OpticalFlow2D::ComputeFlowBidirectionalDevice(const DevicePtr* dev_frames, 
     if (!IsInitialized() || !dev_frames || !dev_flows_u || !dev_flows_v || !dev_back_us || !dev_back_vs || frame_count < 2)
         return false;
     if (RefuseGroup("sequences")) return false;
+    {  // a prior is the prior of ONE direction: there is none for the backward flow
+        float reach = 0.f;
+        int prior_level = 0;
+        if (params.Read<float>("prior_reach", reach) || params.Read<int>("prior_level", prior_level)) {
+            std::printf("Error: '%s': a prior flow and bidirectional flow do not combine (there is no prior for the backward flow).\n",
+                        GetName());
+            return false;
+        }
+    }
     // every plane written must be distinct from every other one and from the frames (which are only read)
     std::vector<DevicePtr> outputs;
     for (size_t k = 0; k + 1 < frame_count; ++k) {
@@ -516,6 +525,170 @@ bool OpticalFlow2D::ComputeFlowDevice(DevicePtr dev_frame_0, DevicePtr dev_frame
     });
 }
 
+bool OpticalFlow2D::PriorStartLevel(size_t width, size_t height, size_t warp_levels_count, float warp_scale_factor, float reach,
+                                    int prior_level, size_t* start_level)
+{
+    if (!start_level) return false;
+    if (!(std::isfinite(reach) && reach > 0.f) || prior_level < -1) {
+        std::printf("Error: a prior flow takes a reach that is finite and > 0 (%g) and a start level >= 0 (%d).\n", reach, prior_level);
+        return false;
+    }
+    OpticalFlow2D geometry;  // (GetMaxWarpLevel is pure host arithmetic)
+    const size_t levels = std::min(warp_levels_count, geometry.GetMaxWarpLevel(width, height, warp_scale_factor));
+    if (levels == 0 || !(warp_scale_factor < 1.f) || !(warp_scale_factor > 0.f)) {
+        std::printf("Error: no pyramid level to run (levels %zu, scale %g).\n", warp_levels_count, warp_scale_factor);
+        return false;
+    }
+    const size_t top = levels - 1;
+    size_t level = 0;
+    if (prior_level >= 0) {
+        level = static_cast<size_t>(prior_level);
+    } else {
+        // a level whose pixels are `reach` full-resolution pixels or more: what the prior leaves to correct is a pixel there
+        while (level < top && !(reach * std::pow(warp_scale_factor, static_cast<float>(level)) <= 1.f)) ++level;
+    }
+    *start_level = std::min(level, top);
+    return true;
+}
+
+bool OpticalFlow2D::MeetsOwnPlane(DevicePtr plane) const
+{
+    const size_t bytes = GroupStrideBytes() * group_;
+    auto meets = [&](DevicePtr own) { return own && plane < own + bytes && own < plane + bytes; };
+    for (DevicePtr own : all_planes_)
+        if (meets(own)) return true;
+    return meets(packed_frames_[0]) || meets(packed_frames_[1]) || meets(level_warp_plane_[0]);
+}
+
+bool OpticalFlow2D::ComputeFlowFromPriorDevice(DevicePtr dev_frame_0, DevicePtr dev_frame_1, DevicePtr dev_prior_u, DevicePtr dev_prior_v,
+                                               DevicePtr dev_flow_u, DevicePtr dev_flow_v, OperationParameters& params,
+                                               PriorReport* report_out)
+{
+    if (!IsInitialized() || !dev_frame_0 || !dev_frame_1 || !dev_prior_u || !dev_prior_v || !dev_flow_u || !dev_flow_v) return false;
+    if (RefuseGroup("a prior flow")) return false;
+    size_t warp_levels_count = 0;
+    float warp_scale_factor = 0.f, reach = 2.f;
+    int prior_level = -1;
+    if (!params.Read<size_t>("warp_levels_count", warp_levels_count) || !params.Read<float>("warp_scale_factor", warp_scale_factor)) {
+        std::printf("Operation: '%s'. Missing parameter 'warp_levels_count' / 'warp_scale_factor'.\n", GetName());
+        return false;
+    }
+    params.Read<float>("prior_reach", reach);
+    if (params.Read<int>("prior_level", prior_level) && prior_level < 0) prior_level = -2;  // (a level that was given is >= 0)
+    size_t start = 0;
+    if (!PriorStartLevel(dev_container_size_.width, dev_container_size_.height, warp_levels_count, warp_scale_factor, reach, prior_level,
+                         &start))
+        return false;
+    {  // the prior is read while the flow planes and the object's own planes are written
+        const size_t bytes = GroupStrideBytes();
+        const DevicePtr prior[2] = {dev_prior_u, dev_prior_v}, flow[2] = {dev_flow_u, dev_flow_v};
+        for (DevicePtr p : prior) {
+            bool meets = MeetsOwnPlane(p);
+            for (DevicePtr f : flow) meets = meets || (p < f + bytes && f < p + bytes);
+            if (meets) {
+                std::printf("Error: '%s': a prior plane overlaps a flow plane or a plane of the object's own.\n", GetName());
+                return false;
+            }
+        }
+    }
+    if (!prior_scratch_.Ensure(context_, sizeof(unsigned long long))) return false;
+    active_group_ = group_;
+    prior_u_ = dev_prior_u;
+    prior_v_ = dev_prior_v;
+    prior_start_level_ = start;
+    bool ok;
+    if (!use_graph || timing_mode != 0) {
+        ok = QueuePair(dev_frame_0, dev_frame_1, dev_flow_u, dev_flow_v, params);
+    } else {  // a recording holds the prior's addresses and the level it starts at
+        std::vector<unsigned char> key = GraphKey('R', group_, {dev_frame_0, dev_frame_1, dev_flow_u, dev_flow_v, dev_prior_u, dev_prior_v}, params);
+        const unsigned char* level_bytes = reinterpret_cast<const unsigned char*>(&start);
+        key.insert(key.end(), level_bytes, level_bytes + sizeof(start));
+        ok = ReplayOrRecord(std::move(key), [&] { return QueuePair(dev_frame_0, dev_frame_1, dev_flow_u, dev_flow_v, params); });
+    }
+    prior_u_ = prior_v_ = 0;
+    prior_start_level_ = 0;
+    if (ok && report_out) {
+        report_out->start_level = start;
+        report_out->levels_run = start + 1;
+        ok = ReadRecord(&report_out->not_finite, prior_scratch_.At<>(), sizeof(report_out->not_finite));
+        ok = !CheckFlow2DError(flow2d_synchronize(context_), "flow2d_synchronize") && ok;
+    }
+    return ok;
+}
+
+void OpticalFlow2D::ComputeFlowFromPrior(Data2D& frame_0, Data2D& frame_1, Data2D& prior_u, Data2D& prior_v, Data2D& flow_u,
+                                         Data2D& flow_v, OperationParameters& params, PriorReport* report_out)
+{
+    last_run_ok_ = false;
+    if (!IsInitialized()) return;
+    if (RefuseGroup("a prior flow")) return;
+    CallPlanes planes(context_, dev_container_size_, GetName(), "frame / prior / flow");
+    planes.Add(&frame_0, CallPlanes::In).Add(&frame_1, CallPlanes::In).Add(&prior_u, CallPlanes::In).Add(&prior_v, CallPlanes::In);
+    planes.Add(&flow_u, CallPlanes::Out).Add(&flow_v, CallPlanes::Out);
+    if (!planes.SizesMatch()) return;
+    HostCall call(context_, last_total_ms_, planes.Allocate());
+    const DevicePtr* d = planes.data();
+    last_run_ok_ = planes.Upload() && ComputeFlowFromPriorDevice(d[0], d[1], d[2], d[3], d[4], d[5], params, report_out) && planes.Download();
+}
+
+bool OpticalFlow2D::ComputeFlowCorrelationSeededDevice(DevicePtr dev_frame_0, DevicePtr dev_frame_1, float lo, float scale, int radius,
+                                                       int range, int spacing, float min_score, DevicePtr dev_flow_u, DevicePtr dev_flow_v,
+                                                       OperationParameters& params, DevicePtr dev_node_u, DevicePtr dev_node_v,
+                                                       DevicePtr dev_node_score, flow2d_correlation_record* correlation_out,
+                                                       PriorReport* report_out, DevicePtr dev_prior_u, DevicePtr dev_prior_v)
+{
+    if (!IsInitialized() || !dev_flow_u || !dev_flow_v || (dev_prior_u == 0) != (dev_prior_v == 0)) return false;
+    if (RefuseGroup("a prior flow")) return false;
+    if (!EnsurePlanes(prior_planes_, 2)) return false;
+    const DevicePtr* prior = prior_planes_.data();
+    PriorReport report;
+    const bool ok = CorrelateDevice(dev_frame_0, dev_frame_1, lo, scale, radius, range, spacing, min_score, dev_node_u, dev_node_v,
+                                    dev_node_score, correlation_out, prior[0], prior[1]) &&
+                    ComputeFlowFromPriorDevice(dev_frame_0, dev_frame_1, prior[0], prior[1], dev_flow_u, dev_flow_v, params, &report);
+    if (!ok) return false;
+    if (report_out) *report_out = report;
+    if (!dev_prior_u) return true;
+    const DevicePtr copies[2] = {dev_prior_u, dev_prior_v};
+    return HandBack(2, prior, copies) && !CheckFlow2DError(flow2d_synchronize(context_), "flow2d_synchronize");
+}
+
+void OpticalFlow2D::ComputeFlowCorrelationSeeded(Data2D& frame_0, Data2D& frame_1, int radius, int range, int spacing, float min_score,
+                                                 Data2D& flow_u, Data2D& flow_v, OperationParameters& params, Data2D* node_u,
+                                                 Data2D* node_v, Data2D* node_score, flow2d_correlation_record* correlation_out,
+                                                 PriorReport* report_out, Data2D* prior_u, Data2D* prior_v)
+{
+    last_run_ok_ = false;
+    if (!IsInitialized() || (prior_u == nullptr) != (prior_v == nullptr)) return;
+    if (RefuseGroup("a prior flow")) return;
+    CallPlanes planes(context_, dev_container_size_, GetName(), "frame / flow");
+    planes.Add(&frame_0, CallPlanes::In).Add(&frame_1, CallPlanes::In).Add(&flow_u, CallPlanes::Out).Add(&flow_v, CallPlanes::Out);
+    planes.Add(prior_u, CallPlanes::Out).Add(prior_v, CallPlanes::Out);
+    // the node planes: containers with no image of their size behind them, downloaded below
+    planes.Add(nullptr, CallPlanes::Out, true).Add(nullptr, CallPlanes::Out, true).Add(nullptr, CallPlanes::Out, node_score != nullptr);
+    if (!planes.SizesMatch()) return;
+    float lo = 0.f, scale = 1.f;
+    CorrelationRange(frame_0, frame_1, lo, scale);
+    const size_t W = dev_container_size_.width, H = dev_container_size_.height;
+    if (!CorrelationArgsOk(W, H, lo, scale, radius, range, spacing, min_score)) return;
+    size_t nw = 0, nh = 0;
+    flow2d_correlation_grid(W, H, radius, spacing, &nw, &nh);
+    Data2D* nodes[3] = {node_u, node_v, node_score};
+    for (Data2D* image : nodes)
+        if (image && (image->Width() != nw || image->Height() != nh)) {
+            std::printf("Error: '%s': the node images are not %zu x %zu.\n", GetName(), nw, nh);
+            return;
+        }
+    HostCall call(context_, last_total_ms_, planes.Allocate());
+    const DevicePtr* d = planes.data();
+    bool ok = planes.Upload() &&
+              ComputeFlowCorrelationSeededDevice(d[0], d[1], lo, scale, radius, range, spacing, min_score, d[2], d[3], params, d[6], d[7],
+                                                 d[8], correlation_out, report_out, d[4], d[5]) &&
+              planes.Download();
+    for (int k = 0; ok && k < 3; ++k)
+        if (nodes[k]) ok = CopyData2DFromDevice(d[6 + k], *nodes[k], H, dev_container_size_.pitch);
+    last_run_ok_ = ok;
+}
+
 bool OpticalFlow2D::ComputeFlowGroupDevice(size_t count, const DevicePtr* dev_frames_0, const DevicePtr* dev_frames_1,
                                            const DevicePtr* dev_flows_u, const DevicePtr* dev_flows_v,
                                            OperationParameters& params)
@@ -685,6 +858,11 @@ bool OpticalFlow2D::RunPyramid(OperationParameters& params)
                     warp_scale_factor);
         return false;
     }
+    // A run from a prior flow (ComputeFlowFromPriorDevice): the loop starts at the start level instead of at the top one, and that
+    // level's warp takes the prior.  Everything decided from `level` below -- which frame pyramid path, the levels' plane regions --
+    // is decided for the levels that run; every path gives a level's frames the same bits.
+    const bool from_prior = prior_u_ != 0;
+    if (from_prior) level = std::min(level, static_cast<int>(prior_start_level_));
 
     {  // widths the median operator accepts: 1 (copy), 3..8 (even widths use width - 1); anything else would
        // make the reference swap in a stale buffer (cuda_operation_median_2d.cpp:150-152)
@@ -944,12 +1122,18 @@ bool OpticalFlow2D::RunPyramid(OperationParameters& params)
                     AsPlane(output));
                 std::swap(flow_u, flow_du);
                 std::swap(flow_v, flow_dv);
+            } else if (from_prior) {  // the first level of a run from a prior: the prior at this level's size instead of zero
+                err = flow2d_prior_registration_2d(context_, AsPlane(prior_u_), AsPlane(prior_v_), original_size.width, original_size.height,
+                                                   AsPlane(flow_u), AsPlane(flow_v), AsPlane(level_0), AsPlane(level_1), current_size.width,
+                                                   current_size.height, dev_container_size_.pitch, hx, hy, AsPlane(output),
+                                                   prior_scratch_.At<unsigned long long>());
             } else {
                 err = flow2d_upsample_registration_2d(context_, nullptr, nullptr, 0, 0, AsPlane(flow_u), AsPlane(flow_v), AsPlane(level_0),
                                                       AsPlane(level_1), current_size.width, current_size.height,
                                                       dev_container_size_.pitch, hx, hy, AsPlane(output));
             }
-            if (CheckFlow2DError(err, upsample && base_flow_shift ? "flow2d_upsample_registration_half_2d" : "flow2d_upsample_registration_2d"))
+            if (CheckFlow2DError(err, upsample ? (base_flow_shift ? "flow2d_upsample_registration_half_2d" : "flow2d_upsample_registration_2d")
+                                               : (from_prior ? "flow2d_prior_registration_2d" : "flow2d_upsample_registration_2d")))
                 failed = true;
         };
 

@@ -292,6 +292,53 @@ public:
                    Data2D& node_v, Data2D* node_score, flow2d_correlation_record* record_out, Data2D* flow_u = nullptr,
                    Data2D* flow_v = nullptr);
 
+    // The pyramid started from a prior flow instead of from zero at the coarsest level (no reference counterpart; Brox & Malik's
+    // large-displacement flow and the predictor-corrector passes of PIV start the variational solver from matches in the same
+    // way).  dev_prior_u / dev_prior_v: a flow in full-resolution pixels in planes of the container's size, only read; a pixel
+    // where either component is not finite enters as (0, 0) and is counted.  The level loop starts at the level
+    // PriorStartLevel gives instead of at the top one, and that level's warp is flow2d_prior_registration_2d -- the prior brought
+    // to the level's size, stored as its base flow and frame 1 warped by it -- instead of the zero-fill form; the frame pyramid,
+    // the later levels and the delivery are those of ComputeFlowDevice (an all-zero prior started at the top level gives its
+    // bytes).  Optional bag keys: prior_reach (float, pixels, default 2: how far the solver is trusted to correct the prior) and
+    // prior_level (int: the start level itself, overriding the rule).  With use_graph the recorded pyramid is keyed by the prior's
+    // planes and the start level as well.  report_out (optional) gets the start level, the number of levels run and the count of
+    // prior pixels that were not finite; the call then synchronises, otherwise it only queues.  The prior planes must not meet
+    // the flow planes or any plane of the object's own.  Not for lock-step groups; there is no prior for a backward flow, so
+    // ComputeFlowBidirectional* refuse a bag that carries prior_reach or prior_level.
+    struct PriorReport {
+        size_t start_level = 0, levels_run = 0;
+        unsigned long long not_finite = 0;
+    };
+    // The start level: the smallest l >= 0 with reach * std::pow(warp_scale_factor, (float)l) <= 1 -- the float pow of the level
+    // geometry --, at most the top level min(warp_levels_count, GetMaxWarpLevel(...)) - 1 of the unseeded run; prior_level >= 0
+    // replaces the rule (clamped alike), -1 = not given.  False (and a message) for a reach that is not finite and > 0, a
+    // prior_level below -1, or parameters with which no level runs.  Needs no device.
+    static bool PriorStartLevel(size_t width, size_t height, size_t warp_levels_count, float warp_scale_factor, float reach,
+                                int prior_level, size_t* start_level);
+    bool ComputeFlowFromPriorDevice(DevicePtr dev_frame_0, DevicePtr dev_frame_1, DevicePtr dev_prior_u, DevicePtr dev_prior_v,
+                                    DevicePtr dev_flow_u, DevicePtr dev_flow_v, OperationParameters& params,
+                                    PriorReport* report_out = nullptr);
+    // The host-image form (the CLI's --initial-flow).  LastRunSucceeded and LastTotalMs as for ComputeFlow.
+    void ComputeFlowFromPrior(Data2D& frame_0, Data2D& frame_1, Data2D& prior_u, Data2D& prior_v, Data2D& flow_u, Data2D& flow_v,
+                              OperationParameters& params, PriorReport* report_out = nullptr);
+    // Window correlation as the prior: CorrelateDevice (arguments as there) with its field expanded to the frame's grid
+    // (flow2d_expand_nodes_2d) into planes of the object's own, then ComputeFlowFromPriorDevice from that field.  No refinement
+    // pass in between: pixels whose four nodes are all invalid are NaN in the expansion, enter as 0 and are counted.  The node
+    // planes (optional, as for CorrelateDevice) and correlation_out keep the correlation's own result; dev_prior_u / dev_prior_v
+    // (optional, both or neither) get a copy of the expanded field.  The call synchronises.
+    bool ComputeFlowCorrelationSeededDevice(DevicePtr dev_frame_0, DevicePtr dev_frame_1, float lo, float scale, int radius, int range,
+                                            int spacing, float min_score, DevicePtr dev_flow_u, DevicePtr dev_flow_v,
+                                            OperationParameters& params, DevicePtr dev_node_u = 0, DevicePtr dev_node_v = 0,
+                                            DevicePtr dev_node_score = 0, flow2d_correlation_record* correlation_out = nullptr,
+                                            PriorReport* report_out = nullptr, DevicePtr dev_prior_u = 0, DevicePtr dev_prior_v = 0);
+    // The host-image form (the CLI's --correlation-prior): lo and scale from CorrelationRange; node_u / node_v / node_score and
+    // prior_u / prior_v are optional images (nw x nh and the frame's size).
+    void ComputeFlowCorrelationSeeded(Data2D& frame_0, Data2D& frame_1, int radius, int range, int spacing, float min_score,
+                                      Data2D& flow_u, Data2D& flow_v, OperationParameters& params, Data2D* node_u = nullptr,
+                                      Data2D* node_v = nullptr, Data2D* node_score = nullptr,
+                                      flow2d_correlation_record* correlation_out = nullptr, PriorReport* report_out = nullptr,
+                                      Data2D* prior_u = nullptr, Data2D* prior_v = nullptr);
+
     // When set, ComputeFlowDevice records the whole pyramid of a pair into a HIP graph the first time it
     // sees a (buffers, parameters) combination and replays it afterwards: one host call instead of
     // several hundred launches.  Ignored while timing_mode != 0 (events are not captured).
@@ -469,6 +516,14 @@ private:
     // Correlate*: the node planes the caller did not give (u, v) and the record
     OwnedPlanes correlation_planes_{owned_, 2};
     DeviceScratch correlation_scratch_{owned_};
+    // ComputeFlowFromPrior*: inside such a run the prior's planes and the start level (RunPyramid starts there, from them); the
+    // device count of the prior's non-finite pixels; the expanded field of ComputeFlowCorrelationSeeded* (u, v; first use)
+    DevicePtr prior_u_ = 0, prior_v_ = 0;
+    size_t prior_start_level_ = 0;
+    DeviceScratch prior_scratch_{owned_};
+    OwnedPlanes prior_planes_{owned_, 2};
+    // whether [plane, plane + one container of the group) meets a plane of the object's own
+    bool MeetsOwnPlane(DevicePtr plane) const;
     flow2d_context* context_ = nullptr;
     // One plane beside the pool: the warped frame of a level, when the levels of both frames are computed up front into plane
     // regions of their own (RunPyramid: "stacked" levels) and therefore cannot be overwritten by the warp

@@ -40,8 +40,9 @@ extern "C" {
  * (motion-compensated temporal denoising) and flow2d_global_motion_2d / flow2d_global_motion_workspace_bytes /
  * flow2d_global_flow_2d / flow2d_warp_global_2d (robust global motion and stabilisation), flow2d_segment_motion_2d /
  * flow2d_segment_motion_workspace_bytes (motion segmentation), flow2d_deformation_2d / flow2d_deformation_workspace_bytes
- * (strain, divergence and vorticity of a flow), flow2d_refine_flow_2d (edge-aware refinement of a flow) and flow2d_correlate_2d /
- * flow2d_correlation_grid / flow2d_expand_nodes_2d (window correlation) were added under 1. */
+ * (strain, divergence and vorticity of a flow), flow2d_refine_flow_2d (edge-aware refinement of a flow), flow2d_correlate_2d /
+ * flow2d_correlation_grid / flow2d_expand_nodes_2d (window correlation) and flow2d_prior_registration_2d (the first level of a
+ * pyramid started from a prior flow) were added under 1. */
 #define FLOW2D_ABI_VERSION 1
 
 typedef enum flow2d_status {
@@ -883,6 +884,37 @@ FLOW2D_API int flow2d_upsample_registration_half_2d(flow2d_context* ctx, const f
 /* launches of flow2d_upsample_registration_half_2d queued by this process so far: tells which path a pyramid took (the host
  * layer takes it at every level that is exactly twice the previous one and solved by the strips) */
 FLOW2D_API unsigned long long flow2d_half_base_flow_launches(void);
+
+/* The first level of a pyramid that starts from a prior flow instead of from zero (no reference counterpart): the counterpart of
+ * flow2d_upsample_registration_2d with a full-resolution prior in place of the previous level's flow, in one launch; added to ABI
+ * version 1 without changing any existing entry.  prior_u / prior_v are in_width x in_height planes holding a flow in
+ * full-resolution pixels; frame_0 / frame_1 are the level's frames, width x height, width <= in_width and height <= in_height
+ * (equal sizes: the prior enters at level 0).  All planes share pitch_bytes.  fp32, every operation rounded on its own, no fused
+ * multiply-add:
+ *   Sanitising.  A prior pixel where u or v is not finite (NaN, +Inf, -Inf) counts as (0, 0) -- the vector the unseeded pyramid
+ *     starts from -- in BOTH planes, and is counted once in the record, whether or not an output's cells reach it.
+ *   Resample.  The sanitised planes are brought to width x height exactly as flow2d_resample_xy_pair does it (resample_2d.cu:34-118):
+ *     per output the x pass over the cells of every prior row its y cells touch -- cells summed left to right from 0, the first and
+ *     the last with their fractions, the sum times width / (float)in_width, rounded to float like the temp plane of the two-launch
+ *     form --, then the y pass over those values, times height / (float)in_height.  No magnitude scaling: the vectors stay in
+ *     full-resolution pixels and the level's hx / hy carry the units, as everywhere in the pyramid.  The result goes to out_u / out_v.
+ *   Registration.  `output` is exactly what flow2d_registration_2d gives for frame_0, frame_1, out_u, out_v, hx, hy
+ *     (registration_2d.cu:34-73: a vector that leaves the frame, or a NaN position, takes frame_0's pixel).
+ * Record.  record[b] (DEVICE memory, 8-byte aligned, one unsigned long long per instance of a lock-step batch) gets the number of
+ * prior pixels of instance b that were not finite.  An integer, added by integer atomics after the entry has zeroed the record on
+ * the stream: repeated calls, a replayed graph and an instance alone or in its batch give the same bytes.
+ * Row padding and the containers beyond in_width x in_height and width x height are neither read into a result nor written.  One
+ * launch on the context's stream (and an 8-byte memset per instance); no allocation, no synchronisation, no host round trip
+ * (graph-capturable).  Honours flow2d_context_set_batch: every plane of instance b at b * stride floats, record + b.  Per-lane
+ * offsets are 32-bit while in_height * pitch_bytes fits them, else 64-bit.
+ * FLOW2D_ERR_INVALID_ARGUMENT, before any launch, for a null plane or record (or a misaligned one), a zero size, a level larger than
+ * the prior in either direction, a bad pitch (the rule of flow2d_consistency_2d), an hx or hy that is not finite and > 0, or a
+ * written byte range -- out_u, out_v, output, the records -- that meets a read one or another written one, over every instance of
+ * a batch. */
+FLOW2D_API int flow2d_prior_registration_2d(flow2d_context* ctx, const float* prior_u, const float* prior_v, size_t in_width,
+                                            size_t in_height, float* out_u, float* out_v, const float* frame_0, const float* frame_1,
+                                            size_t width, size_t height, size_t pitch_bytes, float hx, float hy, float* output,
+                                            unsigned long long* record /* device */);
 
 /* resample_x / resample_y (src/kernels/resample_2d.cu:34-75,77-118): area-weighted 1-D resample. */
 FLOW2D_API int flow2d_resample_x(flow2d_context* ctx, const float* input, float* output, size_t out_width,
