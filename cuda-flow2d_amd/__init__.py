@@ -257,6 +257,64 @@ class PriorReport(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+PROPAGATE_MAX_FILL = 64  # FLOW2D_PROPAGATE_MAX_FILL
+
+
+class PropagateRecord(C.Structure):
+    """flow2d_propagate_record of include/flow2d_c_abi.h: the counts flow2d_propagate_flow_2d writes per instance."""
+    _fields_ = [(name, C.c_ulonglong) for name in ("pixels", "unusable", "left", "landed", "holes", "filled", "unfilled", "reserved")]
+
+    def summary(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
+
+
+PROPAGATE_RECORD_BYTES = 64  # FLOW2D_PROPAGATE_RECORD_BYTES, checked by a static_assert in the header
+assert C.sizeof(PropagateRecord) == PROPAGATE_RECORD_BYTES
+
+
+class WarmOptions(C.Structure):
+    """OpticalFlow2D::WarmOptions: the fill passes and the photometric scale of the propagation, and the tail of the adaptive rule
+    (< 0: no adaptation)."""
+    _fields_ = [("fill_passes", C.c_int), ("photo_scale", C.c_float), ("tail", C.c_float)]
+
+
+WARM_MODES = ("unseeded", "seeded", "redone")
+
+
+class WarmReport(C.Structure):
+    """OpticalFlow2D::WarmReport: how a pair of a warm-started sequence ran -- mode (0 unseeded, 1 seeded, 2 redone: seeded, then
+    computed again unseeded because the prediction did not hold), the reach it was seeded with (adaptive mode; 0 unseeded), the
+    PriorReport fields of the seeded run, the propagation's record, and the shares of pixels where the final flow differs from the
+    prediction by more than 1, 2, 3 px (adaptive mode; -1: not measured)."""
+    _fields_ = [("mode", C.c_int), ("reach", C.c_int), ("start_level", C.c_size_t), ("levels_run", C.c_size_t),
+                ("not_finite", C.c_ulonglong), ("propagation", PropagateRecord), ("share", C.c_double * 3)]
+
+    def summary(self):
+        return {"mode": WARM_MODES[self.mode], "reach": self.reach, "start_level": self.start_level, "levels_run": self.levels_run,
+                "not_finite": self.not_finite, "propagation": self.propagation.summary(), "share": list(self.share)}
+
+
+def warm_options(fill_passes=4, photo_scale=1.0, tail=None):
+    """WarmOptions; tail None: no adaptation.  ValueError for what OpticalFlow2D::WarmOptionsOk refuses.  Needs no device."""
+    options = WarmOptions(int(fill_passes), float(photo_scale), -1.0 if tail is None else float(tail))
+    if (tail is not None and not 0.0 <= float(tail) < 1.0) or not host_lib().flow2d_host_warm_options_ok(C.byref(options)):
+        raise ValueError("warm start: fill_passes %r (0 .. %d), photo_scale %r (finite, >= 0), tail %r (None or in [0, 1))" %
+                         (fill_passes, PROPAGATE_MAX_FILL, photo_scale, tail))
+    return options
+
+
+def warm_next_reach(count, above, tail, reach_used):
+    """OpticalFlow2D::WarmNextReach, the adaptive rule of a warm sequence: from `count` compared pixels of which above[t - 1] lie
+    further than t px (t = 1, 2, 3) from the prediction, returns (redo, next_reach) -- whether a pair seeded with reach_used (0:
+    it ran unseeded) is to be computed again unseeded, and the reach of the next pair (0: unseeded).  ValueError for refused
+    arguments.  Needs no device."""
+    redo, nxt = C.c_int(), C.c_int()
+    a = (C.c_ulonglong * 3)(*[int(x) for x in above])
+    if host_lib().flow2d_host_warm_next_reach(int(count), a, float(tail), int(reach_used), C.byref(redo), C.byref(nxt)):
+        raise ValueError("warm_next_reach(%r, %r, %r, %r)" % (count, list(above), tail, reach_used))
+    return bool(redo.value), nxt.value
+
+
 def prior_start_level(width, height, levels, scale, reach=2.0, level=None):
     """The level at which a pyramid of `levels` levels with scale factor `scale` over a width x height frame starts from a prior
     flow (OpticalFlow2D::PriorStartLevel): the smallest l with reach * scale^l <= 1 in the float arithmetic of the level geometry,
@@ -402,6 +460,10 @@ def hip_lib():
             L.flow2d_expand_nodes_2d.argtypes = [vp, vp, vp, sz, sz, sz, i, i, vp, vp, sz, sz, sz]
         if hasattr(L, "flow2d_prior_registration_2d"):  # (absent from libraries of earlier rounds loaded for an A/B)
             L.flow2d_prior_registration_2d.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp, sz, sz, sz, f, f, vp, vp]
+        if hasattr(L, "flow2d_propagate_flow_2d"):  # (absent from libraries of earlier rounds loaded for an A/B)
+            L.flow2d_propagate_flow_workspace_bytes.restype = sz
+            L.flow2d_propagate_flow_workspace_bytes.argtypes = [sz, sz, sz]
+            L.flow2d_propagate_flow_2d.argtypes = [vp] * 6 + [sz, sz, sz, f, f, i, vp, vp, vp, vp]
         if hasattr(L, "flow2d_segment_motion_2d"):  # (absent from libraries of earlier rounds loaded for an A/B)
             L.flow2d_segment_motion_workspace_bytes.restype = sz
             L.flow2d_segment_motion_workspace_bytes.argtypes = [sz, sz, sz]
@@ -1053,6 +1115,56 @@ class Context:
                 rec.free()
                 self._planes.remove(rec)
 
+    def propagate_records(self, instances=1):
+        """A Plane for `instances` flow2d_propagate_record records (device memory)."""
+        return self.plane(max(instances * PROPAGATE_RECORD_BYTES // 4, 4), 1)
+
+    def read_propagate_record(self, record, instances=1):
+        """The records of a propagate_records Plane as PropagateRecord structures (synchronises)."""
+        raw = record.download(instances * PROPAGATE_RECORD_BYTES // 4, 1)
+        return list((PropagateRecord * instances).from_buffer_copy(raw.tobytes()))
+
+    def propagate_workspace(self, w, h, instances=1):
+        """A Plane of flow2d_propagate_flow_workspace_bytes(w, h, instances) bytes (device memory)."""
+        return self.plane(max(hip_lib().flow2d_propagate_flow_workspace_bytes(w, h, instances) // 4, 4), 1)
+
+    def propagate_flow(self, pu, pv, w, h, mask=None, frame_from=None, frame_to=None, step=1.0, photo_scale=1.0, fill_passes=4,
+                       out_u=None, out_v=None, record=True, workspace=None, instances=1):
+        """The flow (pu, pv) carried `step` times along itself onto the grid of the frame it leads to (flow2d_propagate_flow_2d): a
+        deterministic forward splat -- where several vectors land on one pixel the one whose source matches best photometrically
+        (frame_from at the source against frame_to at the landing point, times photo_scale; both frames or neither) wins, then the one
+        that lands nearest to the pixel's centre, then the lowest source index --, a pixel no vector reaches is NaN, and fill_passes
+        passes fill such holes with the mean of their finite neighbours.  mask: 1 where a vector is not to be carried.
+        out_u, out_v: the caller's Planes, which are written and stay on the device; without them the call allocates both, downloads
+        them and returns arrays.  record: True -- the counts are read back (synchronises) --, a propagate_records Plane of the
+        caller's, or False / None.  workspace: a propagate_workspace Plane of the caller's (a captured launch needs one that
+        outlives the call).  Returns (u, v, PropagateRecord or None)."""
+        own_planes = out_u is None and out_v is None
+        if not own_planes and (out_u is None or out_v is None):
+            raise ValueError("propagate_flow takes both output planes or neither")
+        own_record = record is True
+        if own_record and instances != 1:
+            raise ValueError("a lock-step batch takes the caller's records")
+        held = [self.plane(pu.width, pu.height), self.plane(pu.width, pu.height)] if own_planes else [out_u, out_v]
+        rec = self.propagate_records(instances) if own_record else (record or None)
+        own_workspace = workspace is None
+        work = self.propagate_workspace(w, h, instances) if own_workspace else workspace
+        try:
+            _check(hip_lib().flow2d_propagate_flow_2d(self.handle, pu.ptr, pv.ptr, mask.ptr if mask else None,
+                                                      frame_from.ptr if frame_from else None, frame_to.ptr if frame_to else None, w, h,
+                                                      pu.pitch, float(step), float(photo_scale), int(fill_passes), held[0].ptr,
+                                                      held[1].ptr, rec.ptr if rec is not None else None, work.ptr),
+                   "flow2d_propagate_flow_2d")
+            u, v = (q.download(w, h) for q in held) if own_planes else held
+            result = u, v, (self.read_propagate_record(rec, 1)[0] if own_record else None)
+            if own_workspace and not (own_planes or own_record):
+                self.synchronize()  # the workspace is freed below: the queued launches must have used it
+            return result
+        finally:
+            for q in (held if own_planes else []) + ([rec] if own_record else []) + ([work] if own_workspace else []):
+                q.free()
+                self._planes.remove(q)
+
     def resample_x_levels(self, src, packed, in_w, h, widths, columns, src_b=None, packed_b=None):
         """x pass for several output widths in one trip over `src`; level l lands in columns[l] .. of `packed`."""
         n = len(widths)
@@ -1241,6 +1353,16 @@ def host_lib():
             L.flow2d_host_bidirectional_refuses_prior.argtypes = [vp, hp]
             L.flow2d_host_flow_create_group.restype = vp
             L.flow2d_host_flow_create_group.argtypes = [sz, sz, i, sz]
+        if hasattr(L, "flow2d_host_compute_flow_sequence_warm"):
+            hp, wo, wr = C.POINTER(HostParams), C.POINTER(WarmOptions), C.POINTER(WarmReport)
+            L.flow2d_host_warm_next_reach.argtypes = [C.c_ulonglong, C.POINTER(C.c_ulonglong), f, i, C.POINTER(i), C.POINTER(i)]
+            L.flow2d_host_warm_options_ok.argtypes = [wo]
+            L.flow2d_host_propagate_flow_device.argtypes = [vp] * 6 + [f, wo, vp, vp, C.POINTER(PropagateRecord)]
+            L.flow2d_host_compute_flow_from_previous_device.argtypes = [vp] * 9 + [hp, f, i, wo, wr]
+            L.flow2d_host_compute_flow_from_previous.argtypes = [vp] + [fp] * 8 + [hp, f, i, wo, wr, fp]
+            L.flow2d_host_compute_flow_sequence_warm_device.argtypes = [vp, C.POINTER(vp), sz, C.POINTER(vp), C.POINTER(vp), hp, f, i, wo,
+                                                                        wr]
+            L.flow2d_host_compute_flow_sequence_warm.argtypes = [vp, fp, sz, fp, fp, hp, f, i, wo, wr, fp]
         if hasattr(L, "flow2d_host_segment_motion"):
             d, u32 = C.c_double, C.c_uint
             head = [i, d, i, i, f, f, u32, C.POINTER(GlobalMotion), C.POINTER(SegmentSummary), C.POINTER(MotionRegion),
@@ -1764,6 +1886,90 @@ class OpticalFlow:
         if rc:
             raise Flow2DError(rc, "OpticalFlow2D::ComputeFlowCorrelationSeededDevice")
         return report, record
+
+    def propagate_flow_device(self, dev_u, dev_v, dev_out_u, dev_out_v, dev_mask=None, dev_frame_from=None, dev_frame_to=None, step=1.0,
+                              photo_scale=1.0, fill_passes=4, record=True):
+        """OpticalFlow2D::PropagateFlowDevice: raw device addresses of pitched containers; workspace and record are the object's
+        own.  With record the PropagateRecord is read back and returned (synchronises); without, the call only queues."""
+        options = warm_options(fill_passes, photo_scale)
+        rec = PropagateRecord() if record else None
+        rc = host_lib().flow2d_host_propagate_flow_device(self.handle, dev_u, dev_v, dev_mask, dev_frame_from, dev_frame_to, float(step),
+                                                          C.byref(options), dev_out_u, dev_out_v, C.byref(rec) if record else None)
+        if rc:
+            raise Flow2DError(rc, "OpticalFlow2D::PropagateFlowDevice")
+        return rec
+
+    def compute_flow_from_previous(self, frame_0, frame_1, prev_u, prev_v, params, prev_mask=None, prev_frame=None, reach=2.0,
+                                   level=None, fill_passes=4, photo_scale=1.0):
+        """OpticalFlow2D::ComputeFlowFromPrevious: the flow of the host pair, warm-started from the previous pair's flow (prev_u,
+        prev_v) -- the flow into frame_0 from the frame before it --, which is propagated onto frame_0's grid and then seeds the
+        pyramid as in compute_flow_from_prior.  prev_frame: that earlier frame, which switches the photometric term on.
+        Returns (u, v, WarmReport, device_ms)."""
+        f0, f1 = self._pair(frame_0, frame_1)
+        pu, pv = self._pair(prev_u, prev_v)
+        mask = None if prev_mask is None else self._pair(prev_mask, prev_mask)[0]
+        frame = None if prev_frame is None else self._pair(prev_frame, prev_frame)[0]
+        options = warm_options(fill_passes, photo_scale)
+        u, v = np.empty_like(f0), np.empty_like(f0)
+        report, ms = WarmReport(), C.c_float()
+        rc = host_lib().flow2d_host_compute_flow_from_previous(self.handle, _fptr(f0), _fptr(f1), _fptr(pu), _fptr(pv), _opt_fptr(mask),
+                                                               _opt_fptr(frame), _fptr(u), _fptr(v), C.byref(params), float(reach),
+                                                               self._prior_level(level), C.byref(options), C.byref(report), C.byref(ms))
+        if rc:
+            raise Flow2DError(rc, "OpticalFlow2D::ComputeFlowFromPrevious")
+        return u, v, report, ms.value
+
+    def compute_flow_from_previous_device(self, dev_f0, dev_f1, dev_prev_u, dev_prev_v, dev_u, dev_v, params, dev_prev_mask=None,
+                                          dev_prev_frame=None, reach=2.0, level=None, fill_passes=4, photo_scale=1.0, report=True):
+        """OpticalFlow2D::ComputeFlowFromPreviousDevice: raw device addresses of pitched containers.  With report the WarmReport is
+        returned (synchronises); without, the call only queues."""
+        options = warm_options(fill_passes, photo_scale)
+        rep = WarmReport() if report else None
+        rc = host_lib().flow2d_host_compute_flow_from_previous_device(self.handle, dev_f0, dev_f1, dev_prev_u, dev_prev_v, dev_prev_mask,
+                                                                      dev_prev_frame, dev_u, dev_v, C.byref(params), float(reach),
+                                                                      self._prior_level(level), C.byref(options),
+                                                                      C.byref(rep) if report else None)
+        if rc:
+            raise Flow2DError(rc, "OpticalFlow2D::ComputeFlowFromPreviousDevice")
+        return rep
+
+    def compute_flow_sequence_warm(self, frames, params, reach=2.0, level=None, fill_passes=4, photo_scale=1.0, tail=None):
+        """OpticalFlow2D::ComputeFlowSequenceWarm: the flows of the host sequence [frame_count, height, width], pair 0 from zero
+        and every later pair from its predecessor's flow propagated onto its grid.  tail: None -- every later pair is seeded with
+        reach / level --, or the share in [0, 1) of the adaptive rule (warm_next_reach), which picks every pair's reach from how
+        well the last prediction held and computes a pair again unseeded when its prior did not hold (reach <= 3, no level).
+        The default is None: no table of measured sequences supports a particular tail yet.
+        Returns (us, vs, [WarmReport], device_ms)."""
+        fr = self._stack(frames)
+        n = fr.shape[0]
+        if n < 2:
+            raise ValueError("a sequence has at least two frames")
+        options = warm_options(fill_passes, photo_scale, tail)
+        us, vs = np.empty((n - 1,) + fr.shape[1:], np.float32), np.empty((n - 1,) + fr.shape[1:], np.float32)
+        reports, ms = (WarmReport * (n - 1))(), C.c_float()
+        rc = host_lib().flow2d_host_compute_flow_sequence_warm(self.handle, _fptr(fr), n, _fptr(us), _fptr(vs), C.byref(params),
+                                                               float(reach), self._prior_level(level), C.byref(options), reports,
+                                                               C.byref(ms))
+        if rc:
+            raise Flow2DError(rc, "OpticalFlow2D::ComputeFlowSequenceWarm")
+        return us, vs, list(reports), ms.value
+
+    def compute_flow_sequence_warm_device(self, dev_frames, dev_us, dev_vs, params, reach=2.0, level=None, fill_passes=4, photo_scale=1.0,
+                                          tail=None, reports=False):
+        """OpticalFlow2D::ComputeFlowSequenceWarmDevice: raw device addresses; flow k goes from dev_frames[k] to dev_frames[k + 1]
+        into (dev_us[k], dev_vs[k]).  Without adaptation and without reports the call only queues.  Returns the list of WarmReport
+        with reports, else None."""
+        n = len(dev_frames)
+        if n < 2 or len(dev_us) != n - 1 or len(dev_vs) != n - 1:
+            raise ValueError("a sequence of n frames takes n - 1 flow plane pairs")
+        options = warm_options(fill_passes, photo_scale, tail)
+        reps = (WarmReport * (n - 1))() if reports else None
+        rc = host_lib().flow2d_host_compute_flow_sequence_warm_device(self.handle, _ptr_array(dev_frames), n, _ptr_array(dev_us),
+                                                                      _ptr_array(dev_vs), C.byref(params), float(reach),
+                                                                      self._prior_level(level), C.byref(options), reps)
+        if rc:
+            raise Flow2DError(rc, "OpticalFlow2D::ComputeFlowSequenceWarmDevice")
+        return list(reps) if reports else None
 
     def bidirectional_refuses_prior(self, params):
         """Whether ComputeFlowBidirectional refuses a bag that carries the keys of a prior flow (it has no backward prior)."""

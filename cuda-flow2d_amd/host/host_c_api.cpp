@@ -749,6 +749,147 @@ HOST_API int flow2d_host_compute_flow_correlation_seeded(flow2d_host_flow* h, co
     return 0;
 }
 
+// ---- warm starts: the previous pair's flow as the prior ----------------------------------------------------------------------------
+// OpticalFlow2D::WarmOptions / WarmReport as the facade takes and hands them out
+struct flow2d_host_warm_options {
+    int fill_passes;
+    float photo_scale;
+    float tail;  // < 0: no adaptation
+};
+struct flow2d_host_warm_report {
+    int mode;   // 0 unseeded, 1 seeded, 2 redone
+    int reach;  // adaptive mode: the reach the pair was seeded with, 0 unseeded
+    size_t start_level, levels_run;
+    unsigned long long not_finite;
+    flow2d_propagate_record propagation;
+    double share[3];
+};
+
+namespace {
+OpticalFlow2D::WarmOptions Options(const flow2d_host_warm_options& o)
+{
+    OpticalFlow2D::WarmOptions out;
+    out.fill_passes = o.fill_passes;
+    out.photo_scale = o.photo_scale;
+    out.tail = o.tail;
+    return out;
+}
+void Report(flow2d_host_warm_report* out, const OpticalFlow2D::WarmReport* r, size_t count)
+{
+    for (size_t k = 0; out && k < count; ++k) {
+        out[k] = {r[k].mode, r[k].reach, r[k].prior.start_level, r[k].prior.levels_run, r[k].prior.not_finite, r[k].propagation,
+                  {r[k].share[0], r[k].share[1], r[k].share[2]}};
+    }
+}
+}  // namespace
+
+// OpticalFlow2D::WarmNextReach: the adaptive rule of a warm sequence over one record (above: the counts beyond 1, 2, 3 px).  0 and
+// *redo / *next_reach written, or 1 when the arguments are refused.  Needs no device.
+HOST_API int flow2d_host_warm_next_reach(unsigned long long count, const unsigned long long* above, float tail, int reach_used, int* redo,
+                                         int* next_reach)
+{
+    bool again = false;
+    int next = 0;
+    if (!redo || !next_reach || !OpticalFlow2D::WarmNextReach(count, above, tail, reach_used, &again, &next)) return 1;
+    *redo = again ? 1 : 0;
+    *next_reach = next;
+    return 0;
+}
+
+// OpticalFlow2D::WarmOptionsOk: 1 when the options are acceptable.  Needs no device.
+HOST_API int flow2d_host_warm_options_ok(const flow2d_host_warm_options* options)
+{
+    return options && OpticalFlow2D::WarmOptionsOk(Options(*options)) ? 1 : 0;
+}
+
+// OpticalFlow2D::PropagateFlowDevice: planes in pitched device containers; mask and the two frames optional.  With `record` the call
+// synchronises, otherwise it only queues.  0 on success.
+HOST_API int flow2d_host_propagate_flow_device(flow2d_host_flow* h, void* dev_flow_u, void* dev_flow_v, void* dev_mask, void* dev_frame_from,
+                                               void* dev_frame_to, float step, const flow2d_host_warm_options* options, void* dev_out_u,
+                                               void* dev_out_v, flow2d_propagate_record* record)
+{
+    if (!h || !options) return 1;
+    return h->flow.PropagateFlowDevice(dp(dev_flow_u), dp(dev_flow_v), dp(dev_mask), dp(dev_frame_from), dp(dev_frame_to), step,
+                                       Options(*options), dp(dev_out_u), dp(dev_out_v), record)
+               ? 0
+               : 2;
+}
+
+// OpticalFlow2D::ComputeFlowFromPreviousDevice.  reach / prior_level as for flow2d_host_compute_flow_from_prior_device.  With `report`
+// the call synchronises.  0 on success.
+HOST_API int flow2d_host_compute_flow_from_previous_device(flow2d_host_flow* h, void* dev_frame_0, void* dev_frame_1, void* dev_prev_u,
+                                                           void* dev_prev_v, void* dev_prev_mask, void* dev_prev_frame, void* dev_flow_u,
+                                                           void* dev_flow_v, const flow2d_host_params* params, float reach, int prior_level,
+                                                           const flow2d_host_warm_options* options, flow2d_host_warm_report* report)
+{
+    if (!h || !params || !options) return 1;
+    PriorBag bag(*params, reach, prior_level);
+    h->flow.timing_mode = 0;
+    OpticalFlow2D::WarmReport r;
+    if (!h->flow.ComputeFlowFromPreviousDevice(dp(dev_frame_0), dp(dev_frame_1), dp(dev_prev_u), dp(dev_prev_v), dp(dev_prev_mask),
+                                               dp(dev_prev_frame), dp(dev_flow_u), dp(dev_flow_v), bag, Options(*options),
+                                               report ? &r : nullptr))
+        return 2;
+    Report(report, &r, 1);
+    return 0;
+}
+
+// OpticalFlow2D::ComputeFlowFromPrevious on tight host images; prev_mask and prev_frame optional.
+HOST_API int flow2d_host_compute_flow_from_previous(flow2d_host_flow* h, const float* frame_0, const float* frame_1, const float* prev_u,
+                                                    const float* prev_v, const float* prev_mask, const float* prev_frame, float* flow_u,
+                                                    float* flow_v, const flow2d_host_params* params, float reach, int prior_level,
+                                                    const flow2d_host_warm_options* options, flow2d_host_warm_report* report,
+                                                    float* total_ms)
+{
+    if (!h || !frame_0 || !frame_1 || !prev_u || !prev_v || !flow_u || !flow_v || !params || !options) return 1;
+    HostImages im(h);
+    Data2D *f0 = im.In(frame_0), *f1 = im.In(frame_1), *pu = im.In(prev_u), *pv = im.In(prev_v);
+    Data2D *mask = prev_mask ? im.In(prev_mask) : nullptr, *frame = prev_frame ? im.In(prev_frame) : nullptr;
+    Data2D *u = im.Out(flow_u, im.Always), *v = im.Out(flow_v, im.Always);
+    PriorBag bag(*params, reach, prior_level);
+    OpticalFlow2D::WarmReport r;
+    h->flow.ComputeFlowFromPrevious(*f0, *f1, *pu, *pv, mask, frame, *u, *v, bag, Options(*options), &r);
+    Report(report, &r, 1);
+    return im.Finish(h->flow, total_ms);
+}
+
+// OpticalFlow2D::ComputeFlowSequenceWarmDevice: frame_count frames, frame_count - 1 flows; reports: frame_count - 1 entries or null.
+HOST_API int flow2d_host_compute_flow_sequence_warm_device(flow2d_host_flow* h, void* const* dev_frames, size_t frame_count,
+                                                           void* const* dev_flows_u, void* const* dev_flows_v,
+                                                           const flow2d_host_params* params, float reach, int prior_level,
+                                                           const flow2d_host_warm_options* options, flow2d_host_warm_report* reports)
+{
+    if (!h || !params || !options || !dev_frames || !dev_flows_u || !dev_flows_v || frame_count < 2) return 1;
+    PriorBag bag(*params, reach, prior_level);
+    h->flow.timing_mode = 0;
+    const std::vector<DevicePtr> frames = DevicePtrs(dev_frames, frame_count), us = DevicePtrs(dev_flows_u, frame_count - 1),
+                                 vs = DevicePtrs(dev_flows_v, frame_count - 1);
+    std::vector<OpticalFlow2D::WarmReport> r(frame_count - 1);
+    if (!h->flow.ComputeFlowSequenceWarmDevice(frames.data(), frame_count, us.data(), vs.data(), bag, Options(*options),
+                                               reports ? r.data() : nullptr))
+        return 2;
+    Report(reports, r.data(), r.size());
+    return 0;
+}
+
+// OpticalFlow2D::ComputeFlowSequenceWarm on tight host images: frames = frame_count images, flows_u / flows_v = frame_count - 1 each.
+HOST_API int flow2d_host_compute_flow_sequence_warm(flow2d_host_flow* h, const float* frames, size_t frame_count, float* flows_u,
+                                                    float* flows_v, const flow2d_host_params* params, float reach, int prior_level,
+                                                    const flow2d_host_warm_options* options, flow2d_host_warm_report* reports,
+                                                    float* total_ms)
+{
+    if (!h || !frames || !flows_u || !flows_v || !params || !options || frame_count < 2) return 1;
+    HostImages im(h);
+    Data2D* in = im.In(frames, frame_count);
+    Data2D *us = im.Out(flows_u, im.Always, frame_count - 1), *vs = im.Out(flows_v, im.Always, frame_count - 1);
+    const std::vector<Data2D*> frame_ptrs = Pointers(in, frame_count);
+    PriorBag bag(*params, reach, prior_level);
+    std::vector<OpticalFlow2D::WarmReport> r(frame_count - 1);
+    h->flow.ComputeFlowSequenceWarm(frame_ptrs.data(), frame_count, us, vs, bag, Options(*options), r.data());
+    Report(reports, r.data(), r.size());
+    return im.Finish(h->flow, total_ms);
+}
+
 // Whether ComputeFlowBidirectional refuses a bag that carries the keys of a prior (there is no prior for the backward flow): runs it
 // on two zero frames with prior_reach in the bag; 1 when no flow was delivered.
 HOST_API int flow2d_host_bidirectional_refuses_prior(flow2d_host_flow* h, const flow2d_host_params* params)

@@ -77,6 +77,14 @@
 // "nodes", "invalid", "rejected", "unrefined" -- is printed.  The two sources exclude each other, and both exclude --correlation
 // and every option that runs flows of its own (--backward, --interpolate, --track, --denoise, --global-motion, --segment-motion,
 // --deformation, --refine): there is no prior for a backward flow.  Without these options nothing changes.
+// --previous-flow FILE.flo [--previous-frame FILE] [--propagate-fill N, 0 .. 64, default 4] [--prior-reach P] [--prior-level L] is the
+// warm start of a pair inside a sequence (OpticalFlow2D::ComputeFlowFromPrevious): FILE.flo is the flow of the PREVIOUS pair -- from
+// the frame before frame 1 into frame 1 --, which is carried along itself onto frame 1's grid (flow2d_propagate_flow_2d, N fill
+// passes) and then seeds the pyramid like --initial-flow.  --previous-frame names that earlier frame (a raw file like the frames):
+// where two vectors land on one pixel, the one whose source matches frame 1 better wins.  Two lines are printed: "Propagation:
+// {json}" -- "fill", "photometric" and the record's "pixels", "unusable", "left", "landed", "holes", "filled", "unfilled" -- and
+// "Prior: {json}" with the source "previous-flow".  It excludes --initial-flow, --correlation-prior, --correlation and every option
+// that runs flows of its own, as --initial-flow does.  Without these options nothing changes.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -137,6 +145,9 @@ int main(int argc, char** argv)
     float prior_reach = 2.f;
     int prior_level = -1;
     bool prior_option = false;  // --prior-reach or --prior-level was given
+    std::string previous_flow_file, previous_frame_file;  // --previous-flow FILE.flo, --previous-frame FILE
+    int propagate_fill = 4;
+    bool previous_option = false;  // --previous-frame or --propagate-fill was given
     std::string ground_truth_file;
     int device = 0;
     float sor_omega = 0.f;
@@ -283,6 +294,23 @@ int main(int argc, char** argv)
             ++i;
         }
         else if (!std::strcmp(argv[i], "--initial-flow") && i + 1 < argc) initial_flow_file = argv[++i];
+        else if (!std::strcmp(argv[i], "--previous-flow") && i + 1 < argc) previous_flow_file = argv[++i];
+        else if (!std::strcmp(argv[i], "--previous-frame") && i + 1 < argc) {
+            previous_frame_file = argv[++i];
+            previous_option = true;
+        }
+        else if (!std::strcmp(argv[i], "--propagate-fill")) {
+            char* end = nullptr;
+            const long n = (i + 1 < argc) ? std::strtol(argv[i + 1], &end, 10) : 0;
+            if (i + 1 >= argc || end == argv[i + 1] || *end != '\0' || n < 0 || n > FLOW2D_PROPAGATE_MAX_FILL) {
+                std::printf("--propagate-fill takes an integer of 0 .. %d (passes that fill the holes of the propagated flow).\n",
+                            FLOW2D_PROPAGATE_MAX_FILL);
+                return 5;
+            }
+            propagate_fill = static_cast<int>(n);
+            previous_option = true;
+            ++i;
+        }
         else if (!std::strcmp(argv[i], "--prior-reach")) {
             char* end = nullptr;
             const float value = (i + 1 < argc) ? std::strtof(argv[i + 1], &end) : 0.f;
@@ -347,9 +375,17 @@ int main(int argc, char** argv)
         return 5;
     }
 
-    const bool from_prior = !initial_flow_file.empty() || prior_radius != 0;
+    const bool from_prior = !initial_flow_file.empty() || prior_radius != 0 || !previous_flow_file.empty();
     if (!initial_flow_file.empty() && prior_radius != 0) {
         std::printf("--initial-flow and --correlation-prior are two sources of one prior: give one of them.\n");
+        return 5;
+    }
+    if (!previous_flow_file.empty() && (!initial_flow_file.empty() || prior_radius != 0)) {
+        std::printf("--previous-flow, --initial-flow and --correlation-prior are sources of one prior: give one of them.\n");
+        return 5;
+    }
+    if (previous_option && previous_flow_file.empty()) {
+        std::printf("--previous-frame and --propagate-fill need --previous-flow FILE.flo.\n");
         return 5;
     }
     if (from_prior && (method == Methods::Correlation || backward || interpolate || track_spacing || denoise || global_model >= 0 || segment ||
@@ -359,7 +395,7 @@ int main(int argc, char** argv)
         return 5;
     }
     if (prior_option && !from_prior) {
-        std::printf("--prior-reach and --prior-level need a prior: --initial-flow FILE.flo or --correlation-prior R.\n");
+        std::printf("--prior-reach and --prior-level need a prior: --initial-flow FILE.flo, --previous-flow FILE.flo or --correlation-prior R.\n");
         return 5;
     }
 
@@ -466,6 +502,20 @@ int main(int argc, char** argv)
         }
     }
 
+    Data2D previous_frame;
+    if (!previous_flow_file.empty()) {
+        if (!IOUtils::ReadFlowFLO(previous_flow_file, prior_u, prior_v)) {
+            std::printf("Cannot read the previous flow '%s' (a Middlebury .flo file).\n", previous_flow_file.c_str());
+            return 2;
+        }
+        if (prior_u.Width() != width || prior_u.Height() != height) {
+            std::printf("The previous flow '%s' is %zu x %zu, the frames %zu x %zu.\n", previous_flow_file.c_str(), prior_u.Width(),
+                        prior_u.Height(), width, height);
+            return 2;
+        }
+        if (!previous_frame_file.empty() && !LoadFrame(previous_frame, input_path, previous_frame_file, u8, width, height)) return 2;
+    }
+
     OpticalFlow2D optical_flow;
     optical_flow.silent = !verbose;
     if (optical_flow.Initialize(data_size, data_constancy)) {
@@ -536,6 +586,23 @@ int main(int argc, char** argv)
                 std::printf("Prior: {\"source\": \"initial-flow\", \"reach\": %.9g, \"start_level\": %zu, \"levels_run\": %zu, "
                             "\"not_finite\": %llu}\n",
                             prior_reach, report.start_level, report.levels_run, report.not_finite);
+        } else if (!previous_flow_file.empty()) {
+            OpticalFlow2D::WarmOptions options;
+            options.fill_passes = propagate_fill;
+            OpticalFlow2D::WarmReport report;
+            const bool photometric = !previous_frame_file.empty();
+            optical_flow.ComputeFlowFromPrevious(frame_0, frame_1, prior_u, prior_v, nullptr, photometric ? &previous_frame : nullptr, flow_u,
+                                                 flow_v, params, options, &report);
+            if (optical_flow.LastRunSucceeded()) {
+                const flow2d_propagate_record& r = report.propagation;
+                std::printf("Propagation: {\"fill\": %d, \"photometric\": %s, \"pixels\": %llu, \"unusable\": %llu, \"left\": %llu, "
+                            "\"landed\": %llu, \"holes\": %llu, \"filled\": %llu, \"unfilled\": %llu}\n",
+                            propagate_fill, photometric ? "true" : "false", r.pixels, r.unusable, r.left, r.landed, r.holes, r.filled,
+                            r.unfilled);
+                std::printf("Prior: {\"source\": \"previous-flow\", \"reach\": %.9g, \"start_level\": %zu, \"levels_run\": %zu, "
+                            "\"not_finite\": %llu}\n",
+                            prior_reach, report.prior.start_level, report.prior.levels_run, report.prior.not_finite);
+            }
         } else if (prior_radius) {
             size_t nw = 0, nh = 0;
             if (flow2d_correlation_grid(width, height, prior_radius, correlation_spacing, &nw, &nh) != FLOW2D_OK) {

@@ -217,7 +217,7 @@ bool OpticalFlow2D::PrepareSequenceCache(OperationParameters& params)
     float gaussian_sigma = 0.f;
     params.Read<float>("gaussian_sigma", gaussian_sigma);
     for (FramePyramid& pyramid : sequence_cache_) {
-        pyramid.valid = false;
+        pyramid.built = 0;
         if (gaussian_sigma > 0.f && !pyramid.blurred) {  // a plane for the blurred frame
             void* plane = nullptr;
             size_t pitch = 0;
@@ -233,10 +233,15 @@ bool OpticalFlow2D::PrepareSequenceCache(OperationParameters& params)
 }
 
 bool OpticalFlow2D::RunSequencePair(FramePyramid& first, FramePyramid& second, DevicePtr frame_0, DevicePtr frame_1,
-                                    DevicePtr flow_u, DevicePtr flow_v, OperationParameters& params)
+                                    DevicePtr flow_u, DevicePtr flow_v, OperationParameters& params, DevicePtr prior_u, DevicePtr prior_v,
+                                    size_t start_level)
 {
     sequence_frames_[0] = &first;
     sequence_frames_[1] = &second;
+    sequence_levels_run_ = 0;
+    prior_u_ = prior_u;
+    prior_v_ = prior_v;
+    prior_start_level_ = start_level;
     dev_frame_0_ = Acquire();  // unused by a sequence pair, kept for the pool's bookkeeping
     dev_frame_1_ = Acquire();
     dev_flow_u_ = Acquire();
@@ -248,11 +253,17 @@ bool OpticalFlow2D::RunSequencePair(FramePyramid& first, FramePyramid& second, D
     const bool ok = RunPyramid(params);
     caller_frame_0_ = caller_frame_1_ = caller_flow_u_ = caller_flow_v_ = 0;
     sequence_frames_[0] = sequence_frames_[1] = nullptr;
+    prior_u_ = prior_v_ = 0;
+    prior_start_level_ = 0;
     Release(dev_frame_0_);
     Release(dev_frame_1_);
     Release(dev_flow_u_);
     Release(dev_flow_v_);
-    if (ok) first.valid = second.valid = true;
+    // the pair ran its levels from the top one down: with what was there before, the levels below that one are all built
+    if (ok) {
+        first.built = std::max(first.built, sequence_levels_run_);
+        second.built = std::max(second.built, sequence_levels_run_);
+    }
     return ok;
 }
 
@@ -268,7 +279,7 @@ bool OpticalFlow2D::ComputeFlowSequenceDevice(const DevicePtr* dev_frames, size_
     for (size_t k = 0; ok && k + 1 < frame_count; ++k) {
         FramePyramid& first = sequence_cache_[k % 2];          // frame k: built as the second frame of pair k-1
         FramePyramid& second = sequence_cache_[(k + 1) % 2];   // frame k+1: built by this pair
-        second.valid = false;
+        second.built = 0;
         ok = RunSequencePair(first, second, dev_frames[k], dev_frames[k + 1], dev_flows_u[k], dev_flows_v[k], params);
     }
     return ok;
@@ -312,7 +323,7 @@ bool OpticalFlow2D::ComputeFlowBidirectionalDevice(const DevicePtr* dev_frames, 
     for (size_t k = 0; ok && k + 1 < frame_count; ++k) {
         FramePyramid& first = sequence_cache_[k % 2];          // frame k: built as the second frame of pair k-1
         FramePyramid& second = sequence_cache_[(k + 1) % 2];   // frame k+1: built by the forward run
-        second.valid = false;
+        second.built = 0;
         ok = RunSequencePair(first, second, dev_frames[k], dev_frames[k + 1], dev_flows_u[k], dev_flows_v[k], params) &&
              RunSequencePair(second, first, dev_frames[k + 1], dev_frames[k], dev_back_us[k], dev_back_vs[k], params);
         if (ok && dev_occ_fwd)
@@ -689,6 +700,235 @@ void OpticalFlow2D::ComputeFlowCorrelationSeeded(Data2D& frame_0, Data2D& frame_
     last_run_ok_ = ok;
 }
 
+// ---- warm starts: the previous pair's flow as the prior --------------------------------------------------------------------------
+bool OpticalFlow2D::WarmOptionsOk(const WarmOptions& options)
+{
+    const bool ok = options.fill_passes >= 0 && options.fill_passes <= FLOW2D_PROPAGATE_MAX_FILL && std::isfinite(options.photo_scale) &&
+                    options.photo_scale >= 0.f && (options.tail < 0.f || options.tail < 1.f);  // (a NaN tail fails both)
+    if (!ok)
+        std::printf("Error: a warm start takes 0 .. %d fill passes (%d), a photometric scale that is finite and >= 0 (%g) and a tail < 0 "
+                    "(no adaptation) or in [0, 1) (%g).\n",
+                    FLOW2D_PROPAGATE_MAX_FILL, options.fill_passes, options.photo_scale, options.tail);
+    return ok;
+}
+
+bool OpticalFlow2D::WarmNextReach(unsigned long long count, const unsigned long long* above, float tail, int reach_used, bool* redo,
+                                  int* next_reach)
+{
+    if (!above || !redo || !next_reach || !(tail >= 0.f && tail < 1.f) || reach_used < 0 || reach_used > 3) return false;
+    if (above[0] > count || above[1] > above[0] || above[2] > above[1]) return false;
+    auto holds = [&](int t) { return count > 0 && static_cast<double>(above[t - 1]) / static_cast<double>(count) <= static_cast<double>(tail); };
+    *redo = reach_used > 0 && !holds(reach_used);
+    *next_reach = 0;
+    for (int t = 3; t >= 1; --t)
+        if (holds(t)) *next_reach = t;
+    return true;
+}
+
+bool OpticalFlow2D::EnsureWarmScratch(WarmScratch& scratch)
+{
+    const size_t W = dev_container_size_.width, H = dev_container_size_.height;
+    auto round_up = [](size_t bytes) { return (bytes + 15) / 16 * 16; };
+    const size_t records = round_up(sizeof(flow2d_propagate_record)) + round_up(sizeof(flow2d_flow_error_stats));
+    const size_t propagate_bytes = round_up(flow2d_propagate_flow_workspace_bytes(W, H, 1));
+    const size_t error_bytes = round_up(flow2d_flow_error_workspace_bytes(W, H, 1));
+    if (!warm_scratch_.Ensure(context_, records + propagate_bytes + error_bytes)) return false;
+    scratch.record = warm_scratch_.At<flow2d_propagate_record>();
+    scratch.stats = warm_scratch_.At<flow2d_flow_error_stats>(round_up(sizeof(flow2d_propagate_record)));
+    scratch.propagate_workspace = warm_scratch_.At<>(records);
+    scratch.error_workspace = warm_scratch_.At<>(records + propagate_bytes);
+    scratch.error_workspace_bytes = error_bytes;
+    return true;
+}
+
+bool OpticalFlow2D::QueuePropagation(DevicePtr flow_u, DevicePtr flow_v, DevicePtr mask, DevicePtr frame_from, DevicePtr frame_to, float step,
+                                     const WarmOptions& options, DevicePtr out_u, DevicePtr out_v, const WarmScratch& scratch)
+{
+    return !CheckFlow2DError(flow2d_propagate_flow_2d(context_, AsPlane(flow_u), AsPlane(flow_v), mask ? AsPlane(mask) : nullptr,
+                                                      frame_from ? AsPlane(frame_from) : nullptr, frame_to ? AsPlane(frame_to) : nullptr,
+                                                      dev_container_size_.width, dev_container_size_.height, dev_container_size_.pitch, step,
+                                                      options.photo_scale, options.fill_passes, AsPlane(out_u), AsPlane(out_v),
+                                                      reinterpret_cast<unsigned long long*>(scratch.record), scratch.propagate_workspace),
+                             "flow2d_propagate_flow_2d");
+}
+
+bool OpticalFlow2D::PropagateFlowDevice(DevicePtr dev_flow_u, DevicePtr dev_flow_v, DevicePtr dev_mask, DevicePtr dev_frame_from,
+                                        DevicePtr dev_frame_to, float step, const WarmOptions& options, DevicePtr dev_out_u,
+                                        DevicePtr dev_out_v, flow2d_propagate_record* record_out)
+{
+    if (!IsInitialized() || !dev_flow_u || !dev_flow_v || !dev_out_u || !dev_out_v) return false;
+    if (RefuseGroup("a propagated flow")) return false;
+    if (!WarmOptionsOk(options)) return false;
+    if ((dev_frame_from == 0) != (dev_frame_to == 0)) {
+        std::printf("Error: '%s': the photometric term takes both frames or neither.\n", GetName());
+        return false;
+    }
+    WarmScratch scratch;
+    if (!EnsureWarmScratch(scratch)) return false;
+    bool ok = QueuePropagation(dev_flow_u, dev_flow_v, dev_mask, dev_frame_from, dev_frame_to, step, options, dev_out_u, dev_out_v, scratch);
+    if (ok && record_out) {
+        ok = ReadRecord(record_out, scratch.record, sizeof(*record_out));
+        ok = !CheckFlow2DError(flow2d_synchronize(context_), "flow2d_synchronize") && ok;
+    }
+    return ok;
+}
+
+bool OpticalFlow2D::ComputeFlowFromPreviousDevice(DevicePtr dev_frame_0, DevicePtr dev_frame_1, DevicePtr dev_prev_u, DevicePtr dev_prev_v,
+                                                  DevicePtr dev_prev_mask, DevicePtr dev_prev_frame, DevicePtr dev_flow_u,
+                                                  DevicePtr dev_flow_v, OperationParameters& params, const WarmOptions& options,
+                                                  WarmReport* report_out)
+{
+    if (!IsInitialized() || !dev_frame_0 || !dev_frame_1 || !dev_prev_u || !dev_prev_v || !dev_flow_u || !dev_flow_v) return false;
+    if (RefuseGroup("a warm start")) return false;
+    if (!WarmOptionsOk(options)) return false;
+    if (!EnsurePlanes(warm_planes_, 2)) return false;
+    WarmScratch scratch;
+    if (!EnsureWarmScratch(scratch)) return false;
+    WarmReport report;
+    report.mode = kWarmSeeded;
+    bool ok = QueuePropagation(dev_prev_u, dev_prev_v, dev_prev_mask, dev_prev_frame, dev_prev_frame ? dev_frame_0 : 0, 1.f, options,
+                               warm_planes_[0], warm_planes_[1], scratch);
+    if (ok && report_out) ok = ReadRecord(&report.propagation, scratch.record, sizeof(report.propagation));
+    ok = ok && ComputeFlowFromPriorDevice(dev_frame_0, dev_frame_1, warm_planes_[0], warm_planes_[1], dev_flow_u, dev_flow_v, params,
+                                          report_out ? &report.prior : nullptr);  // (with a report it synchronises)
+    if (ok && report_out) *report_out = report;
+    return ok;
+}
+
+void OpticalFlow2D::ComputeFlowFromPrevious(Data2D& frame_0, Data2D& frame_1, Data2D& prev_u, Data2D& prev_v, Data2D* prev_mask,
+                                            Data2D* prev_frame, Data2D& flow_u, Data2D& flow_v, OperationParameters& params,
+                                            const WarmOptions& options, WarmReport* report_out)
+{
+    last_run_ok_ = false;
+    if (!IsInitialized()) return;
+    if (RefuseGroup("a warm start")) return;
+    if (!WarmOptionsOk(options)) return;
+    CallPlanes planes(context_, dev_container_size_, GetName(), "frame / previous flow / flow");
+    planes.Add(&frame_0, CallPlanes::In).Add(&frame_1, CallPlanes::In).Add(&prev_u, CallPlanes::In).Add(&prev_v, CallPlanes::In);
+    planes.Add(&flow_u, CallPlanes::Out).Add(&flow_v, CallPlanes::Out);
+    size_t next = 6, mask_at = 0, frame_at = 0;  // the optional inputs: a plane only where there is an image
+    if (prev_mask) planes.Add(prev_mask, CallPlanes::In), mask_at = next++;
+    if (prev_frame) planes.Add(prev_frame, CallPlanes::In), frame_at = next++;
+    if (!planes.SizesMatch()) return;
+    HostCall call(context_, last_total_ms_, planes.Allocate());
+    const DevicePtr* d = planes.data();
+    last_run_ok_ = planes.Upload() &&
+                   ComputeFlowFromPreviousDevice(d[0], d[1], d[2], d[3], mask_at ? d[mask_at] : 0, frame_at ? d[frame_at] : 0, d[4], d[5],
+                                                 params, options, report_out) &&
+                   planes.Download();
+}
+
+bool OpticalFlow2D::ComputeFlowSequenceWarmDevice(const DevicePtr* dev_frames, size_t frame_count, const DevicePtr* dev_flows_u,
+                                                  const DevicePtr* dev_flows_v, OperationParameters& params, const WarmOptions& options,
+                                                  WarmReport* reports)
+{
+    if (!IsInitialized() || !dev_frames || !dev_flows_u || !dev_flows_v || frame_count < 2) return false;
+    if (RefuseGroup("sequences")) return false;
+    if (!WarmOptionsOk(options)) return false;
+    const size_t pairs = frame_count - 1;
+    std::vector<DevicePtr> outputs(dev_flows_u, dev_flows_u + pairs);
+    outputs.insert(outputs.end(), dev_flows_v, dev_flows_v + pairs);
+    if (!WrittenPlanesOk(dev_frames, frame_count, outputs.data(), outputs.size(), "flow plane")) return false;
+    const bool adaptive = options.tail >= 0.f;
+    size_t warp_levels_count = 0;
+    float warp_scale_factor = 0.f, prior_reach = 2.f;
+    int prior_level = -1;
+    if (!params.Read<size_t>("warp_levels_count", warp_levels_count) || !params.Read<float>("warp_scale_factor", warp_scale_factor)) {
+        std::printf("Operation: '%s'. Missing parameter 'warp_levels_count' / 'warp_scale_factor'.\n", GetName());
+        return false;
+    }
+    params.Read<float>("prior_reach", prior_reach);
+    if (params.Read<int>("prior_level", prior_level) && prior_level < 0) prior_level = -2;  // (a level that was given is >= 0)
+    int reach = 0;  // adaptive: the reach of the next seeded pair (0: it runs unseeded)
+    if (adaptive) {
+        if (prior_level != -1 || !(std::isfinite(prior_reach) && prior_reach > 0.f && prior_reach <= 3.f)) {
+            std::printf("Error: '%s': an adaptive warm sequence takes a prior_reach in (0, 3] (%g) and no prior_level.\n", GetName(),
+                        prior_reach);
+            return false;
+        }
+        reach = static_cast<int>(std::ceil(prior_reach));
+    }
+    const size_t W = dev_container_size_.width, H = dev_container_size_.height, pitch = dev_container_size_.pitch;
+    auto start_level = [&](float r, int level, size_t* start) { return PriorStartLevel(W, H, warp_levels_count, warp_scale_factor, r, level, start); };
+    size_t fixed_start = 0;
+    if (!adaptive && pairs > 1 && !start_level(prior_reach, prior_level, &fixed_start)) return false;
+    if (!PrepareSequenceCache(params) || !EnsurePlanes(warm_planes_, 2) || !prior_scratch_.Ensure(context_, sizeof(unsigned long long)))
+        return false;
+    WarmScratch scratch;
+    if (!EnsureWarmScratch(scratch)) return false;
+    const DevicePtr prior[2] = {warm_planes_[0], warm_planes_[1]};
+    // flow k against its prediction: the record of flow2d_flow_error_2d with the prediction as the ground truth (one host wait)
+    auto score = [&](size_t k, flow2d_flow_error_stats& stats) {
+        return !CheckFlow2DError(flow2d_flow_error_2d(context_, AsPlane(dev_flows_u[k]), AsPlane(dev_flows_v[k]), AsPlane(prior[0]),
+                                                      AsPlane(prior[1]), nullptr, W, H, pitch, nullptr, nullptr, scratch.stats,
+                                                      scratch.error_workspace, scratch.error_workspace_bytes),
+                                 "flow2d_flow_error_2d") &&
+               ReadRecord(&stats, scratch.stats, sizeof(stats)) && !CheckFlow2DError(flow2d_synchronize(context_), "flow2d_synchronize");
+    };
+    bool ok = true;
+    for (size_t k = 0; ok && k < pairs; ++k) {
+        FramePyramid& first = sequence_cache_[k % 2];          // frame k: built, as far as pair k - 1 needed it, as its second frame
+        FramePyramid& second = sequence_cache_[(k + 1) % 2];   // frame k + 1: built by this pair
+        second.built = 0;
+        WarmReport unasked;
+        WarmReport& report = reports ? reports[k] : unasked;  // (the queued copies of the records land in the caller's entry itself)
+        report = WarmReport();
+        if (k == 0) {
+            ok = RunSequencePair(first, second, dev_frames[0], dev_frames[1], dev_flows_u[0], dev_flows_v[0], params);
+            continue;
+        }
+        // the prediction: flow k - 1 along itself onto frame k's grid, the frames k - 1 and k deciding between colliding vectors
+        ok = QueuePropagation(dev_flows_u[k - 1], dev_flows_v[k - 1], 0, dev_frames[k - 1], dev_frames[k], 1.f, options, prior[0], prior[1],
+                              scratch);
+        if (ok && reports) ok = ReadRecord(&report.propagation, scratch.record, sizeof(report.propagation));
+        if (!ok) break;
+        size_t start = fixed_start;
+        const bool seeded = !adaptive || reach > 0;
+        if (adaptive && seeded && !start_level(static_cast<float>(reach), -1, &start)) return false;
+        ok = seeded ? RunSequencePair(first, second, dev_frames[k], dev_frames[k + 1], dev_flows_u[k], dev_flows_v[k], params, prior[0],
+                                      prior[1], start)
+                    : RunSequencePair(first, second, dev_frames[k], dev_frames[k + 1], dev_flows_u[k], dev_flows_v[k], params);
+        if (!ok) break;
+        report.mode = seeded ? kWarmSeeded : kWarmUnseeded;
+        if (seeded) {
+            report.prior.start_level = start;
+            report.prior.levels_run = start + 1;
+            if (reports) ok = ReadRecord(&report.prior.not_finite, prior_scratch_.At<>(), sizeof(report.prior.not_finite));
+        }
+        if (adaptive) {
+            report.reach = seeded ? reach : 0;
+            flow2d_flow_error_stats stats;
+            bool redo = false;
+            ok = ok && score(k, stats) && WarmNextReach(stats.all.count, stats.all.above + 1, options.tail, report.reach, &redo, &reach);
+            if (ok && redo) {  // the prior did not hold: the pair again, unseeded, into the same planes; then what that flow says
+                report.mode = kWarmRedone;
+                ok = RunSequencePair(first, second, dev_frames[k], dev_frames[k + 1], dev_flows_u[k], dev_flows_v[k], params) &&
+                     score(k, stats) && WarmNextReach(stats.all.count, stats.all.above + 1, options.tail, 0, &redo, &reach);
+            }
+            for (int t = 0; ok && t < 3; ++t)
+                report.share[t] = stats.all.count ? static_cast<double>(stats.all.above[t + 1]) / static_cast<double>(stats.all.count) : -1.0;
+        }
+    }
+    // the reports are filled by copies queued on the stream: they are there once it has drained
+    if (ok && reports && !adaptive) ok = !CheckFlow2DError(flow2d_synchronize(context_), "flow2d_synchronize");
+    return ok;
+}
+
+void OpticalFlow2D::ComputeFlowSequenceWarm(Data2D* const* frames, size_t frame_count, Data2D* flows_u, Data2D* flows_v,
+                                            OperationParameters& params, const WarmOptions& options, WarmReport* reports)
+{
+    last_run_ok_ = false;
+    if (!IsInitialized() || !frames || !flows_u || !flows_v || frame_count < 2) return;
+    if (RefuseGroup("sequences")) return;
+    const size_t n = frame_count;
+    CallPlanes planes(context_, dev_container_size_, GetName(), "frame / flow");
+    planes.Add(frames, n, CallPlanes::In).Add(flows_u, n - 1, CallPlanes::Out).Add(flows_v, n - 1, CallPlanes::Out);
+    if (!planes.SizesMatch()) return;
+    HostCall call(context_, last_total_ms_, planes.Allocate());
+    const DevicePtr* d = planes.data();
+    last_run_ok_ = planes.Upload() && ComputeFlowSequenceWarmDevice(d, n, d + n, d + 2 * n - 1, params, options, reports) && planes.Download();
+}
+
 bool OpticalFlow2D::ComputeFlowGroupDevice(size_t count, const DevicePtr* dev_frames_0, const DevicePtr* dev_frames_1,
                                            const DevicePtr* dev_flows_u, const DevicePtr* dev_flows_v,
                                            OperationParameters& params)
@@ -887,6 +1127,7 @@ bool OpticalFlow2D::RunPyramid(OperationParameters& params)
     bool failed = false;
 
     const bool sequence = sequence_frames_[0] != nullptr;
+    if (sequence) sequence_levels_run_ = static_cast<size_t>(level) + 1;
 
     // The reference resamples both frames from FULL resolution at every level (optical_flow_2d.cpp:284-303): one read
     // of each frame per level.  Here the x passes of all levels > 0 are one trip over the frames (every row read once,
@@ -933,7 +1174,7 @@ bool OpticalFlow2D::RunPyramid(OperationParameters& params)
             FramePyramid& pyramid = *sequence_frames_[i];
             if (gaussian_sigma > 0.0) {
                 pyramid.level0 = pyramid.blurred;
-                if (!pyramid.valid) {
+                if (pyramid.built == 0) {
                     op.Clear();
                     op.PushValuePtr("dev_input", &callers[i]);
                     op.PushValuePtr("dev_output", &pyramid.level0);
@@ -1045,7 +1286,7 @@ bool OpticalFlow2D::RunPyramid(OperationParameters& params)
                     Release(flow_dv);
                     return false;
                 }
-                if (!pyramid.valid) {
+                if (pyramid.built <= static_cast<size_t>(level)) {
                     op.Clear();
                     op.PushValuePtr("dev_input", i == 0 ? &frame_0 : &frame_1);
                     op.PushValuePtr("dev_output", &plane);

@@ -339,6 +339,79 @@ public:
                                       flow2d_correlation_record* correlation_out = nullptr, PriorReport* report_out = nullptr,
                                       Data2D* prior_u = nullptr, Data2D* prior_v = nullptr);
 
+    // Warm starts: the previous pair's flow, carried along itself onto this pair's grid (flow2d_propagate_flow_2d), as the prior of
+    // ComputeFlowFromPriorDevice (no reference counterpart).  In a sequence the prior costs a splat and no correlation, and the
+    // pyramid runs from PriorStartLevel down instead of from the top.
+    //   fill_passes, photo_scale: those of flow2d_propagate_flow_2d (photo_scale acts only where both frames are there).
+    //   tail: < 0 -- no adaptation: every seeded pair uses the bag's prior_reach / prior_level.  In [0, 1) -- the adaptive mode of
+    //   ComputeFlowSequenceWarmDevice: the share of pixels a prediction may miss by more than the reach (WarmNextReach).
+    struct WarmOptions {
+        int fill_passes = 4;
+        float photo_scale = 1.f;
+        float tail = -1.f;
+    };
+    enum WarmMode { kWarmUnseeded = 0, kWarmSeeded = 1, kWarmRedone = 2 };
+    struct WarmReport {
+        int mode = kWarmUnseeded;
+        int reach = 0;  // adaptive mode: the reach the pair was seeded with (1 .. 3), 0 when it ran unseeded
+        PriorReport prior;  // of the seeded run (zeros for an unseeded pair)
+        flow2d_propagate_record propagation = {};  // of the prediction (zeros where none was made: pair 0)
+        double share[3] = {-1.0, -1.0, -1.0};  // adaptive mode: the shares of pixels where the final flow and the prediction differ by
+                                               // more than 1, 2, 3 px; -1 where nothing was measured
+    };
+    // fill_passes in [0, FLOW2D_PROPAGATE_MAX_FILL], photo_scale finite and >= 0, tail < 0 or in [0, 1) (prints what is wrong);
+    // needs no device
+    static bool WarmOptionsOk(const WarmOptions& options);
+    // The adaptive rule, from the record of flow2d_flow_error_2d with the prediction as the ground truth (its non-finite pixels are
+    // invalid there): count = the pixels compared, above[t - 1] = those further than t px from the prediction, t = 1, 2, 3;
+    // share(t) = above[t - 1] / count in double.  reach_used: the reach the pair was seeded with, 0 for an unseeded pair.
+    //   *redo        reach_used > 0 and (count == 0 or share(reach_used) > tail): the prior did not hold, the pair is to be computed
+    //                again unseeded.
+    //   *next_reach  the smallest t in {1, 2, 3} with share(t) <= tail; 0 -- the next pair runs unseeded -- when there is none or
+    //                count == 0 (a scene cut).
+    // False for a tail outside [0, 1), a reach_used outside 0 .. 3, an above[] that is not descending from count, or a null pointer.
+    // Needs no device.
+    static bool WarmNextReach(unsigned long long count, const unsigned long long* above, float tail, int reach_used, bool* redo,
+                              int* next_reach);
+    // flow2d_propagate_flow_2d on planes of the container's size with workspace and record of the object's own (allocated at the
+    // first call, regrown when needed): (dev_flow_u, dev_flow_v) carried `step` times along itself into dev_out_u / dev_out_v.
+    // dev_mask (optional): 1 where a vector is not to be carried; dev_frame_from / dev_frame_to (optional, both or neither) switch
+    // the photometric term on.  record_out (optional): the counts, read back -- the call then synchronises, otherwise it only
+    // queues.  Not for lock-step groups.
+    bool PropagateFlowDevice(DevicePtr dev_flow_u, DevicePtr dev_flow_v, DevicePtr dev_mask, DevicePtr dev_frame_from,
+                             DevicePtr dev_frame_to, float step, const WarmOptions& options, DevicePtr dev_out_u, DevicePtr dev_out_v,
+                             flow2d_propagate_record* record_out = nullptr);
+    // One pair from the previous pair's flow: (dev_prev_u, dev_prev_v), the flow INTO dev_frame_0 from the frame before it, is
+    // propagated into two planes of the object's own and ComputeFlowFromPriorDevice runs from them (bag keys prior_reach /
+    // prior_level as there).  dev_prev_mask (optional) as for PropagateFlowDevice; dev_prev_frame (optional): the previous pair's
+    // frame 0, which switches the photometric term against dev_frame_0 on.  report_out (optional): mode (seeded), the prior's
+    // report and the propagation's record; the call then synchronises, otherwise it only queues.  options.tail is not used.
+    bool ComputeFlowFromPreviousDevice(DevicePtr dev_frame_0, DevicePtr dev_frame_1, DevicePtr dev_prev_u, DevicePtr dev_prev_v,
+                                       DevicePtr dev_prev_mask, DevicePtr dev_prev_frame, DevicePtr dev_flow_u, DevicePtr dev_flow_v,
+                                       OperationParameters& params, const WarmOptions& options, WarmReport* report_out = nullptr);
+    // The host-image form (the CLI's --previous-flow): prev_mask and prev_frame may be null.
+    void ComputeFlowFromPrevious(Data2D& frame_0, Data2D& frame_1, Data2D& prev_u, Data2D& prev_v, Data2D* prev_mask, Data2D* prev_frame,
+                                 Data2D& flow_u, Data2D& flow_v, OperationParameters& params, const WarmOptions& options,
+                                 WarmReport* report_out = nullptr);
+    // The flows of a sequence, every pair after the first started from its predecessor's flow.  Pair 0 is ComputeFlowSequenceDevice's
+    // pair 0; pair k >= 1 runs from PropagateFlowDevice(flow k - 1, frames k - 1 and k) through the sequence cache -- every frame's
+    // pyramid levels are built once, those above a pair's start level only when a later pair needs them.  Its bytes are those of
+    // ComputeFlowFromPriorDevice on the pair from that prior.
+    // Without adaptation (options.tail < 0) every pair k >= 1 is seeded with the bag's prior_reach / prior_level and the call only
+    // queues unless reports are asked for.  With options.tail in [0, 1) (one host wait per pair): after pair k its flow is scored
+    // against its prediction (flow2d_flow_error_2d) and WarmNextReach decides whether the pair is computed again unseeded into the
+    // same planes (mode redone) and with which reach pair k + 1 is seeded, if at all; the first seeded pair uses prior_reach
+    // rounded up to 1, 2 or 3 (a larger one, and a prior_level, are refused in this mode).  A prediction is made and scored for an
+    // unseeded pair k >= 1 too: that is how a sequence finds back to warm starts after a scene cut.
+    // reports (optional): frame_count - 1 entries.  Frames are only read; the flow planes must be distinct from each other and
+    // from the frames.  Eager; not for lock-step groups.
+    bool ComputeFlowSequenceWarmDevice(const DevicePtr* dev_frames, size_t frame_count, const DevicePtr* dev_flows_u,
+                                       const DevicePtr* dev_flows_v, OperationParameters& params, const WarmOptions& options,
+                                       WarmReport* reports = nullptr);
+    // The host-image form: frames[k] -> frame k, flows_u / flows_v: frame_count - 1 images each.
+    void ComputeFlowSequenceWarm(Data2D* const* frames, size_t frame_count, Data2D* flows_u, Data2D* flows_v, OperationParameters& params,
+                                 const WarmOptions& options, WarmReport* reports = nullptr);
+
     // When set, ComputeFlowDevice records the whole pyramid of a pair into a HIP graph the first time it
     // sees a (buffers, parameters) combination and replays it afterwards: one host call instead of
     // several hundred launches.  Ignored while timing_mode != 0 (events are not captured).
@@ -454,16 +527,21 @@ private:
         DevicePtr level0 = 0;              // what level 0 reads: `blurred`, or the caller's plane without a pre-blur
         std::vector<DevicePtr> levels;     // [l] for l >= 1, container width x level height
         std::vector<size_t> level_rows;
-        bool valid = false;
+        // Levels 0 .. built - 1 hold the frame (0: nothing does).  A pair builds, from its first level down, what is missing: a pair
+        // started from a prior at level s leaves s + 1 levels, and a later pair that starts higher adds the rest.
+        size_t built = 0;
     };
     FramePyramid sequence_cache_[2];
     FramePyramid* sequence_frames_[2] = {nullptr, nullptr};  // non-null inside a sequence pair: frame 0 / frame 1
+    size_t sequence_levels_run_ = 0;  // RunPyramid's sequence branch: the levels of the pair it ran last (first level + 1)
     DevicePtr SequenceLevelPlane(FramePyramid& pyramid, size_t level, size_t rows);
     void FreeSequenceCache();
     bool PrepareSequenceCache(OperationParameters& params);
-    // One pair of a sequence: `first` / `second` are the pyramids of frame_0 / frame_1 (built here unless valid)
+    // One pair of a sequence: `first` / `second` are the pyramids of frame_0 / frame_1 (the levels they lack are built here).
+    // With prior planes the pair starts from them at start_level (ComputeFlowFromPriorDevice's run, through the cache).
     bool RunSequencePair(FramePyramid& first, FramePyramid& second, DevicePtr frame_0, DevicePtr frame_1, DevicePtr flow_u,
-                         DevicePtr flow_v, OperationParameters& params);
+                         DevicePtr flow_v, OperationParameters& params, DevicePtr prior_u = 0, DevicePtr prior_v = 0,
+                         size_t start_level = 0);
     // ComputeFlowBidirectional: both frames and the six outputs, outside the pool (allocated on first use)
     OwnedPlanes bidirectional_planes_{owned_, 8};
     // InterpolateFrames*: the flows and masks of a pair (u, v, back u, back v, occlusion 0, occlusion 1) and the host form's
@@ -522,6 +600,20 @@ private:
     size_t prior_start_level_ = 0;
     DeviceScratch prior_scratch_{owned_};
     OwnedPlanes prior_planes_{owned_, 2};
+    // Warm starts: the propagated flow (u, v) and, in one allocation, the propagation's record, the record of the score, and the
+    // workspaces of both (WarmScratch)
+    OwnedPlanes warm_planes_{owned_, 2};
+    DeviceScratch warm_scratch_{owned_};
+    struct WarmScratch {
+        flow2d_propagate_record* record;
+        flow2d_flow_error_stats* stats;
+        void* propagate_workspace;
+        void* error_workspace;
+        size_t error_workspace_bytes;
+    };
+    bool EnsureWarmScratch(WarmScratch& scratch);
+    bool QueuePropagation(DevicePtr flow_u, DevicePtr flow_v, DevicePtr mask, DevicePtr frame_from, DevicePtr frame_to, float step,
+                          const WarmOptions& options, DevicePtr out_u, DevicePtr out_v, const WarmScratch& scratch);
     // whether [plane, plane + one container of the group) meets a plane of the object's own
     bool MeetsOwnPlane(DevicePtr plane) const;
     flow2d_context* context_ = nullptr;

@@ -378,3 +378,18 @@ def make_sequence(name, frame_count=10, width=256, height=256, seed=0):
         square = Texture(rng, amplitude=(50.0, 35.0, 20.0), periods=(29.0, 13.1, 19.7))
         return _two_layer_sequence(frame_count, width, height, texture, square, (4.5, -2.25))
     raise ValueError("unknown scene %r (one of %s)" % (name, ", ".join(SCENES)))
+
+
+def make_speckle_sequence(motion, frame_count=4, width=96, height=80, seed=0):
+    """The speckle scene `motion` (one of SPECKLE_MOTIONS) carried on for frame_count (>= 2) frames; frames 0 and 1 are those of
+    make_speckle_scene.  With "large_translation" every pair moves by (11.25, -7.5): the case a warm-started sequence is for."""
+    if frame_count < 2:
+        raise ValueError("a sequence has at least two frames")
+    texture = Speckle(seed)
+    if motion == "translation":
+        return _affine_sequence("speckle_translation", frame_count, width, height, texture, np.eye(2), (2.3, -1.4))
+    if motion == "affine":
+        return _affine_sequence("speckle_affine", frame_count, width, height, texture, [[1.02, 0.03], [-0.02, 0.985]], (1.25, -0.6))
+    if motion == "large_translation":
+        return _affine_sequence("speckle_large_translation", frame_count, width, height, texture, np.eye(2), (11.25, -7.5))
+    raise ValueError("unknown speckle motion %r (one of %s)" % (motion, ", ".join(SPECKLE_MOTIONS)))

@@ -42,7 +42,8 @@ extern "C" {
  * flow2d_segment_motion_workspace_bytes (motion segmentation), flow2d_deformation_2d / flow2d_deformation_workspace_bytes
  * (strain, divergence and vorticity of a flow), flow2d_refine_flow_2d (edge-aware refinement of a flow), flow2d_correlate_2d /
  * flow2d_correlation_grid / flow2d_expand_nodes_2d (window correlation) and flow2d_prior_registration_2d (the first level of a
- * pyramid started from a prior flow) were added under 1. */
+ * pyramid started from a prior flow) and flow2d_propagate_flow_2d (a flow carried along itself: the prior of a warm-started
+ * sequence) were added under 1. */
 #define FLOW2D_ABI_VERSION 1
 
 typedef enum flow2d_status {
@@ -915,6 +916,65 @@ FLOW2D_API int flow2d_prior_registration_2d(flow2d_context* ctx, const float* pr
                                             size_t in_height, float* out_u, float* out_v, const float* frame_0, const float* frame_1,
                                             size_t width, size_t height, size_t pitch_bytes, float hx, float hy, float* output,
                                             unsigned long long* record /* device */);
+
+/* A flow carried along itself onto the next frame's grid (no reference counterpart; added to ABI version 1 without changing any
+ * existing entry): the prior of a warm-started sequence.  (flow_u, flow_v) is the flow of the pair (k, k + 1) on frame k's grid; the
+ * content of pixel p has moved to p + step * flow(p), and that is where the vector belongs on frame k + 1's grid.  A deterministic
+ * forward splat; fp32, every operation rounded on its own, no fused multiply-add.  All planes are width x height with pitch_bytes.
+ * For the source pixel p = (x, y) with index i = y * width + x (width * height <= 2^32 - 1):
+ *   usable    u = flow_u[p] and v = flow_v[p] are finite, and mask == NULL or mask[p] == 0 (a NaN in the mask: not usable).
+ *             Otherwise p is counted in `unusable` and takes no further part.
+ *   landing   lx = (float)x + step * u,  ly = (float)y + step * v
+ *   target    tx = floorf(lx + 0.5f),  ty = floorf(ly + 0.5f);  unless 0 <= tx <= width - 1 and 0 <= ty <= height - 1 -- compared
+ *             as floats, so that a NaN or an infinity fails and no such value is converted to an integer -- p is counted in `left`.
+ *             Otherwise p is counted in `landed`.
+ *   distance  ex = lx - tx, ey = ly - ty, d2 = ex*ex + ey*ey, dq = min((unsigned)(d2 * 4194304.0f), 0x7FFFFF)
+ *   match     with frame_from and frame_to and photo_scale != 0:  g = S(frame_to, (min(max(lx, 0), width - 1), min(max(ly, 0),
+ *             height - 1))), S the bilinear sample of flow2d_consistency_2d;  diff = fabsf(frame_from[p] - g) * photo_scale;
+ *             q = 255 when diff is not finite, else min(255, (unsigned)diff).  Without frames or with photo_scale == 0: q = 0.
+ *   key       (u64)(255 - q) << 56 | (u64)(0x7FFFFF - dq) << 32 | (u64)(0xFFFFFFFF - i)       (never zero: i <= 2^32 - 2)
+ * Every target keeps the LARGEST key offered to it (one 64-bit integer atomic max per landed pixel on a word of the workspace,
+ * which the entry zeroes on the stream first; max commutes, so the winner depends on no arrival order): the candidate that matches
+ * photometrically best, then the one that lands nearest to the pixel's centre, then the one with the lowest source index.
+ * Resolve.  A target takes its winner's (u, v) bit for bit -- the vector is NOT scaled by step --; a target without a winner is a
+ * hole, counted in `holes`, and holds the quiet NaN 0x7fc00000 in both planes.
+ * Fill.  fill_passes (0 .. FLOW2D_PROPAGATE_MAX_FILL) passes, each over the result of the one before: a pixel that is not finite in
+ * both components and has, among its eight neighbours inside the frame, at least one that is, takes the mean of those -- per
+ * component the sum from 0 in the order (-1,-1), (0,-1), (1,-1), (-1,0), (1,0), (-1,1), (0,1), (1,1), divided by the count as a
+ * float -- and is counted in `filled`; every other pixel is copied.  The pixels still not finite after the last pass (the holes,
+ * when fill_passes == 0) are counted in `unfilled`.  The passes ping-pong between out_u / out_v and two planes of the workspace;
+ * the last one writes out_u / out_v.
+ * Record.  record (DEVICE memory, 8-byte aligned, NULL: no counts) gets per instance b of a lock-step batch, at record +
+ * 8 * b, eight unsigned long long: pixels (= width * height = unusable + left + landed), unusable, left, landed, holes, filled,
+ * unfilled, and a reserved zero.  Integers, summed per wave and added by integer atomics after the entry has zeroed the record on
+ * the stream: repeated calls, a replayed graph and an instance alone or in its batch give the same bytes.
+ * `workspace` (16-byte aligned) holds at least flow2d_propagate_flow_workspace_bytes(width, height, instances) bytes (instances =
+ * the batch count): 16 bytes per pixel and instance -- the keys of all instances first, then two dense planes per instance.
+ * 2 + fill_passes launches and two memsets on the context's stream; no allocation, no synchronisation, no host round trip
+ * (graph-capturable).  Honours flow2d_context_set_batch: every plane of instance b at b * stride floats.  Per-lane offsets are
+ * 32-bit while height * pitch_bytes fits them, else 64-bit.  Row padding is read only as the unselected half of a column pair and
+ * never written.
+ * FLOW2D_ERR_INVALID_ARGUMENT, before any launch, for a null flow or output plane, a zero size, width * height > 2^32 - 1, a bad
+ * pitch (the rule of flow2d_consistency_2d), one frame without the other, a step that is not finite or is zero, a photo_scale that
+ * is not finite or is negative, fill_passes out of range, a null or misaligned workspace, a misaligned record, or a written byte
+ * range -- out_u, out_v, the records, the workspace -- that meets a read one or another written one, over every instance of a
+ * batch. */
+#define FLOW2D_PROPAGATE_MAX_FILL 64
+#define FLOW2D_PROPAGATE_RECORD_BYTES 64
+typedef struct flow2d_propagate_record { /* the eight counts of one instance, as they lie in `record` */
+    unsigned long long pixels, unusable, left, landed, holes, filled, unfilled, reserved;
+} flow2d_propagate_record;
+#ifdef __cplusplus
+static_assert(sizeof(flow2d_propagate_record) == FLOW2D_PROPAGATE_RECORD_BYTES, "flow2d_propagate_record layout");
+#else
+_Static_assert(sizeof(flow2d_propagate_record) == FLOW2D_PROPAGATE_RECORD_BYTES, "flow2d_propagate_record layout");
+#endif
+/* Host logic only, needs no device; 0 for a zero size. */
+FLOW2D_API size_t flow2d_propagate_flow_workspace_bytes(size_t width, size_t height, size_t instances);
+FLOW2D_API int flow2d_propagate_flow_2d(flow2d_context* ctx, const float* flow_u, const float* flow_v, const float* mask,
+                                        const float* frame_from, const float* frame_to, size_t width, size_t height,
+                                        size_t pitch_bytes, float step, float photo_scale, int fill_passes, float* out_u,
+                                        float* out_v, unsigned long long* record /* device */, void* workspace);
 
 /* resample_x / resample_y (src/kernels/resample_2d.cu:34-75,77-118): area-weighted 1-D resample. */
 FLOW2D_API int flow2d_resample_x(flow2d_context* ctx, const float* input, float* output, size_t out_width,
