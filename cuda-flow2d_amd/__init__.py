@@ -403,6 +403,8 @@ def hip_lib():
         L.flow2d_solve_level_takes_half_base.argtypes = [vp, C.POINTER(SolveParams)]
         L.flow2d_half_base_flow_launches.argtypes = []
         L.flow2d_half_base_flow_launches.restype = C.c_ulonglong
+        L.flow2d_fused_packed_launches.argtypes = []
+        L.flow2d_fused_packed_launches.restype = C.c_ulonglong
         L.flow2d_resample_x_pair.argtypes = [vp, vp, vp, vp, vp, sz, sz, sz, sz]
         L.flow2d_resample_y_pair.argtypes = [vp, vp, vp, vp, vp, sz, sz, sz, sz]
         L.flow2d_resample_xy_pair.argtypes = [vp, vp, vp, vp, vp, sz, sz, sz, sz, sz]
@@ -487,6 +489,11 @@ def _check(status, where):
 def half_base_flow_launches():
     """launches of the half-size up-sample + warp queued by this process so far (flow2d_half_base_flow_launches)"""
     return int(hip_lib().flow2d_half_base_flow_launches())
+
+
+def fused_packed_launches():
+    """strip launches of this process so far that the packed build of the strip kernel served (flow2d_fused_packed_launches)"""
+    return int(hip_lib().flow2d_fused_packed_launches())
 
 
 def resample_xy_levels_launches():

@@ -2,6 +2,7 @@
 // (solve_fused_instance.hip; the kernel itself is solve_fused_kernel.hpp).
 #include <algorithm>
 #include <array>
+#include <atomic>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -218,6 +219,9 @@ static FusedLaunch* const kFusedBuilds[2][4][2] = {
     {{fused_launch_g0_p0_k, fused_launch_g0_p1_k}, {fused_launch_g1_p0_k, fused_launch_g1_p1_k},
      {fused_launch_g2_p0_k, fused_launch_g2_p1_k}, {nullptr, nullptr}}};
 
+// strip launches of this process that an object of the packed build accepted (flow2d_fused_packed_launches: which build ran)
+static std::atomic<unsigned long long> fused_packed_launches{0};
+
 // One outer iteration: reads `in` (previous outer iteration), writes `out` (after `stages` sweeps).
 int launch_fused_outer(const flow2d_context* ctx, const SolveLevel& l, ConstPair in, Pair out, size_t stages, bool zero_increment,
                        ConstPair start, int rows_per_strip)
@@ -289,6 +293,7 @@ int launch_fused_outer(const flow2d_context* ctx, const SolveLevel& l, ConstPair
         }
         // (the packed build holds no kernels for continued sweeps: those are the pipeline's build's, like everything it lacks)
         rc = lone_build ? lone_build((int)inner, grid, ctx->stream, a) : 1;
+        if (rc == 0) fused_packed_launches.fetch_add(1, std::memory_order_relaxed);
         if (rc) rc = kFusedBuilds[0][term][pow2]((int)inner, grid, ctx->stream, a);
     }
     if (rc) return FLOW2D_ERR_UNSUPPORTED;
@@ -326,6 +331,11 @@ extern "C" FLOW2D_API int flow2d_fused_block_order(flow2d_context* ctx, size_t w
         out[4 * id + 0] = bx, out[4 * id + 1] = by, out[4 * id + 2] = y0, out[4 * id + 3] = y1;
     }
     return FLOW2D_OK;
+}
+
+extern "C" FLOW2D_API unsigned long long flow2d_fused_packed_launches(void)
+{
+    return flow2d::fused_packed_launches.load(std::memory_order_relaxed);
 }
 
 #ifdef FLOW2D_DEV_BUILD

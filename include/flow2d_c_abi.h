@@ -43,7 +43,7 @@ extern "C" {
  * (strain, divergence and vorticity of a flow), flow2d_refine_flow_2d (edge-aware refinement of a flow), flow2d_correlate_2d /
  * flow2d_correlation_grid / flow2d_expand_nodes_2d (window correlation) and flow2d_prior_registration_2d (the first level of a
  * pyramid started from a prior flow) and flow2d_propagate_flow_2d (a flow carried along itself: the prior of a warm-started
- * sequence) were added under 1. */
+ * sequence) and flow2d_fused_packed_launches (a test hook: which build of the strip kernel a launch took) were added under 1. */
 #define FLOW2D_ABI_VERSION 1
 
 typedef enum flow2d_status {
@@ -1222,6 +1222,12 @@ FLOW2D_API int flow2d_clock_probe_read(flow2d_context* ctx, double* ghz_per_xcd)
  * (*grid_blocks is set).  A test hook: the order must be a permutation of the plan, the strips a partition of the level. */
 FLOW2D_API int flow2d_fused_block_order(flow2d_context* ctx, size_t width, size_t height, size_t inner, size_t instances,
                                         int* out, size_t capacity_blocks, size_t* grid_blocks);
+/* Strip launches queued by this process so far that the packed build of the strip kernel served: the launches of a lone context
+ * (flow2d_context_set_lone) with at most one workgroup per CU whose data term, sweep count and kind the packed build holds -- a
+ * launch it does not hold (the LogDerivatives term, the continued sweeps of an outer iteration) goes to the pipeline's build and
+ * is not counted.  A lock-step group that shares a launch counts once.  A test hook: the two builds must give the same bits, and
+ * this is what tells a test which of them it compared. */
+FLOW2D_API unsigned long long flow2d_fused_packed_launches(void);
 
 FLOW2D_API int flow2d_timing_enable(flow2d_context* ctx, int mode);
 /* mode 2 brackets individual launches only for levels of at least min_width x min_height pixels

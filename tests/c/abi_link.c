@@ -21,6 +21,7 @@ int main(void)
                                     FLOW2D_CONSTANCY_GRADIENT) != FLOW2D_SOLVER_FUSED)
         return 16;
     if (flow2d_context_set_batch(NULL, 2, 4096) != FLOW2D_ERR_INVALID_ARGUMENT) return 17;
+    if (flow2d_fused_packed_launches() != 0 || flow2d_half_base_flow_launches() != 0) return 18; /* nothing was launched */
     printf("flow2d C-ABI v%d, %d device(s), sigma 1.5 -> radius %d\n", flow2d_abi_version(), count < 0 ? 0 : count, radius);
     return 0;
 }

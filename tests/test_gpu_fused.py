@@ -31,19 +31,45 @@ def bits(a):
     return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
+class Build:
+    """Which build of the strip kernel a test's launches must take: "pipeline" (a context as it is created) or "packed" (the
+    context marked lone: flow2d_context_set_lone; strip launches of at most one workgroup per CU).  flow2d_fused_packed_launches
+    is the evidence: served(n) asserts that the packed build took exactly n strip launches since the last look -- none on the
+    pipeline build -- so a shape whose plan outgrows the packed build fails its test instead of comparing the pipeline build
+    with itself."""
+
+    def __init__(self, flow2d, ctx, name):
+        self.flow2d, self.name = flow2d, name
+        ctx.set_lone(name == "packed")
+        self.seen = flow2d.fused_packed_launches()
+
+    def served(self, launches):
+        now = self.flow2d.fused_packed_launches()
+        rose, self.seen = now - self.seen, now
+        assert rose == (launches if self.name == "packed" else 0), (self.name, rose, launches)
+
+
+@pytest.fixture
+def build(flow2d, ctx):
+    """The tests of this file that take it run on the pipeline build here, under the names they have always had; tests/
+    test_gpu_fused_packed.py collects the same functions with a `build` of its own that hands them the packed build."""
+    return Build(flow2d, ctx, "pipeline")
+
+
 @pytest.mark.parametrize("constancy", [0, 1])
 @pytest.mark.parametrize("w,h", [(640, 520), (300, 200)])
-def test_ordinary_operands_do_not_fall_back(ctx, oracle, w, h, constancy):
+def test_ordinary_operands_do_not_fall_back(ctx, oracle, build, w, h, constancy):
     f0, f1, u, v, _, _ = level_fields(oracle, w, h, 11)
     before = ctx.fused_fallbacks()
     a, b, odu, odv = fused_vs_oracle(ctx, oracle, f0, f1, u, v, w, h, w, h, np.float32(1.0), np.float32(1.0), 35.0, 3, 5,
                                      constancy)
     assert np.array_equal(a, odu) and np.array_equal(b, odv)
     assert ctx.fused_fallbacks() == before  # the three-step division served every wave
+    build.served(3)
 
 
 @pytest.mark.parametrize("inner", [5, 3])
-def test_tiny_numerators_fall_back_to_the_plain_division(ctx, oracle, inner):
+def test_tiny_numerators_fall_back_to_the_plain_division(ctx, oracle, build, inner):
     """Flat frames (no data term) and a flow of magnitude 1e-30: every numerator of the point update is a sum of
     weight x (difference of 1e-30 numbers), far below 2^-80, where the residual of the three-step division leaves the
     normal range.  The guard sends every wave to the plain division and the result equals the oracle's."""
@@ -58,9 +84,10 @@ def test_tiny_numerators_fall_back_to_the_plain_division(ctx, oracle, inner):
     assert float(np.abs(odu).max()) > 0 and float(np.abs(odu).max()) < 1e-25
     assert np.array_equal(bits(a), bits(odu)) and np.array_equal(bits(b), bits(odv))
     assert ctx.fused_fallbacks() > before
+    build.served(2)
 
 
-def test_a_diffusion_front_trips_the_guard_only_where_it_is(ctx, oracle):
+def test_a_diffusion_front_trips_the_guard_only_where_it_is(ctx, oracle, build):
     """Flat frames and one bump in the flow: the increment spreads one pixel per sweep and decays by orders of magnitude
     per pixel, so the waves on the front see tiny non-zero numerators (fallback), the others exact zeros or ordinary
     numbers (no fallback).  Every pixel equals the oracle either way."""
@@ -77,9 +104,10 @@ def test_a_diffusion_front_trips_the_guard_only_where_it_is(ctx, oracle):
     assert tripped > 0
     nonzero = np.abs(odu[odu != 0])
     assert nonzero.min() < 2.0 ** -80 < nonzero.max()  # the front did pass below the guard's threshold
+    build.served(8)
 
 
-def test_denominators_outside_the_proven_range_fall_back(ctx, oracle):
+def test_denominators_outside_the_proven_range_fall_back(ctx, oracle, build):
     """alpha = 1e22 puts the denominators (ksi J + sum of the face weights) near 1e25, above 2^40: fallback, same bits."""
     w, h = 640, 200
     f0, f1, u, v, _, _ = level_fields(oracle, w, h, 21)
@@ -87,6 +115,7 @@ def test_denominators_outside_the_proven_range_fall_back(ctx, oracle):
     a, b, odu, odv = fused_vs_oracle(ctx, oracle, f0, f1, u, v, w, h, w, h, np.float32(1.0), np.float32(1.0), 1e22, 2, 5, 0)
     assert np.array_equal(bits(a), bits(odu)) and np.array_equal(bits(b), bits(odv))
     assert ctx.fused_fallbacks() > before
+    build.served(2)
 
 
 @pytest.mark.parametrize("alpha,fuses", [(1e-29, True), (1e-31, False), (0.0, True), (3e-36, False)])
@@ -109,7 +138,7 @@ def test_neighbour_weights_the_strips_cannot_halve_exactly(ctx, flow2d, oracle, 
         assert e.value.status == 5
 
 
-def test_overflowing_results_match_the_per_sweep_kernels(ctx, flow2d, oracle):
+def test_overflowing_results_match_the_per_sweep_kernels(ctx, flow2d, oracle, build):
     """An infinite patch in the flow: the sweeps around it produce infinities and NaNs.  Non-finite results trip the
     output guard, and the repeat with the plain division delivers what the per-sweep kernels (one launch per reference
     launch) deliver: the same pixels NaN, the same infinite, every finite one identical."""
@@ -132,26 +161,34 @@ def test_overflowing_results_match_the_per_sweep_kernels(ctx, flow2d, oracle):
         fin = np.isfinite(y)
         assert np.array_equal(bits(x[fin]), bits(y[fin]))
     assert ctx.fused_fallbacks() > before
+    build.served(2)  # (the strips' two outer iterations; the per-sweep kernels have one build)
 
 
-@pytest.mark.parametrize("constancy", [0, 1])
-@pytest.mark.parametrize("w,h,cw,ch", [
+BORDER_AWARE_LEVELS = [
     (1111, 777, 1120, 780),    # 6 block columns: border-aware plan with a ragged last middle strip
     (640, 1000, 640, 1000),    # 4 block columns, tall
     (2048, 1536, 2048, 1536),  # 10 block columns
     (417, 900, 448, 900),      # 3 block columns: one interior column only
     (416, 300, 416, 300),      # 2 block columns: uniform strips
     (1300, 64, 1312, 64),      # 7 block columns, level lower than two border strips
-])
-def test_border_aware_strip_plan_covers_every_pixel(ctx, oracle, w, h, cw, ch, constancy):
+]
+# (2048 x 1536 is planned as 488 blocks, more than one workgroup per CU: that level is the pipeline build's on any context, and the
+#  only one of this list the packed build's run of this test leaves out)
+BORDER_AWARE_LEVELS_OF_THE_PACKED_BUILD = [level for level in BORDER_AWARE_LEVELS if level[:2] != (2048, 1536)]
+
+
+@pytest.mark.parametrize("constancy", [0, 1])
+@pytest.mark.parametrize("w,h,cw,ch", BORDER_AWARE_LEVELS)
+def test_border_aware_strip_plan_covers_every_pixel(ctx, oracle, build, w, h, cw, ch, constancy):
     """Poisoned output planes (0x7f bytes): a row or column no strip stores would differ from the oracle."""
     f0, f1, u, v, _, _ = level_fields(oracle, w, h, 31)
     hx, hy = np.float32(cw / w), np.float32(ch / h)
     a, b, odu, odv = fused_vs_oracle(ctx, oracle, f0, f1, u, v, w, h, cw, ch, hx, hy, 3.5, 2, 5, constancy)
     assert np.array_equal(a, odu) and np.array_equal(b, odv)
+    build.served(2)
 
 
-def test_negative_zero_in_the_flow_falls_back(ctx, oracle):
+def test_negative_zero_in_the_flow_falls_back(ctx, oracle, build):
     """A numerator of exactly -0 is the one zero the three-step division gets wrong (+0 where the quotient is -0).  It
     takes a -0 in the flow planes to make one: flat frames and a flow plane of -0 do (every face term is -0, the data
     term too).  The guard sees the -0 entries as they are read and sends the waves to the plain division: same bits as
@@ -165,6 +202,7 @@ def test_negative_zero_in_the_flow_falls_back(ctx, oracle):
     a, b, odu, odv = fused_vs_oracle(ctx, oracle, f0, f1, u, v, w, h, w, h, np.float32(1.0), np.float32(1.0), 35.0, 2, 5, 0)
     assert np.array_equal(bits(a), bits(odu)) and np.array_equal(bits(b), bits(odv))
     assert ctx.fused_fallbacks() > before
+    build.served(2)
 
 
 @pytest.mark.parametrize("constancy", [0, 1])
@@ -174,7 +212,7 @@ def test_negative_zero_in_the_flow_falls_back(ctx, oracle):
     (0.001, 1e-20, 1.0, True),    # the same for the data term where the frames agree
     (0.001, 0.001, 1e16, True),   # frames of magnitude 1e18: the data term's argument is far above 2^78
 ])
-def test_robustifier_arguments_outside_the_proven_range_fall_back(ctx, oracle, constancy, e_smooth, e_data, scale, trips):
+def test_robustifier_arguments_outside_the_proven_range_fall_back(ctx, oracle, build, constancy, e_smooth, e_data, scale, trips):
     """phi and ksi are 1 / (2 sqrt(s)) through the hardware root and reciprocal plus residual steps, proven for every s
     with 2 sqrt(s) in [2^-30, 2^40] (tools/ubench/rcp_sqrt_exhaustive.hip).  Regularisers so small that s is a denormal
     on flat regions, or frames so large that s overflows the range, trip the guard; either way every bit is the oracle's."""
@@ -193,9 +231,10 @@ def test_robustifier_arguments_outside_the_proven_range_fall_back(ctx, oracle, c
     assert same and np.array_equal(bits(a[fin_a]), bits(odu[fin_a])) and np.array_equal(bits(b[fin_b]), bits(odv[fin_b]))
     if trips:
         assert ctx.fused_fallbacks() > before
+    build.served(2)
 
 
-def test_zero_regularisers_match_the_per_sweep_kernels(ctx, flow2d, oracle):
+def test_zero_regularisers_match_the_per_sweep_kernels(ctx, flow2d, oracle, build):
     """e_smooth = e_data = 0 on a flat flow over agreeing frames: both arguments are exactly 0, the reference's phi and
     ksi are infinite and the sweeps produce NaNs.  The short forms give NaN for a zero argument, which trips the guard;
     the repeat with the plain expressions delivers what the per-sweep kernels deliver."""
@@ -220,11 +259,12 @@ def test_zero_regularisers_match_the_per_sweep_kernels(ctx, flow2d, oracle):
         fin = np.isfinite(y)
         assert np.array_equal(bits(x[fin]), bits(y[fin]))
     assert ctx.fused_fallbacks() > before
+    build.served(2)  # (the strips' two outer iterations; the per-sweep kernels have one build)
 
 
 @pytest.mark.parametrize("constancy", [0, 1, 2])  # (solve_2d_log with such spacings: test_gpu_reference.py, against the reference's kernel)
 @pytest.mark.parametrize("hx,hy", [(1.1, 0.9), (3.7, 1.0), (0.013, 0.02)])
-def test_spacings_that_are_no_powers_of_two(ctx, oracle, hx, hy, constancy):
+def test_spacings_that_are_no_powers_of_two(ctx, oracle, build, hx, hy, constancy):
     """The six divisions by 2h and 4h of a row step go through the three-step division with the host's RN(1 / (2h)),
     RN(1 / (4h)) when the spacing is no power of two (pyramids with a scale factor other than 0.5); same bits as the
     oracle's plain divisions, and ordinary operands do not fall back."""
@@ -235,9 +275,10 @@ def test_spacings_that_are_no_powers_of_two(ctx, oracle, hx, hy, constancy):
     assert np.array_equal(bits(a), bits(odu)) and np.array_equal(bits(b), bits(odv))
     if hx >= 1.0:  # (h = 0.013 makes second derivatives of 1e5 and more: some denominators leave the guarded range)
         assert ctx.fused_fallbacks() == before
+    build.served(2)
 
 
-def test_tiny_differences_over_a_non_power_of_two_spacing_fall_back(ctx, oracle):
+def test_tiny_differences_over_a_non_power_of_two_spacing_fall_back(ctx, oracle, build):
     """A flow of magnitude 1e-30 over h = 1.1: the numerators of the flow derivatives (differences of such values) are
     below 2^-80, where the three-step division by 2h is not proven -- the guard sends the waves to the plain division."""
     w, h = 640, 200
@@ -249,9 +290,10 @@ def test_tiny_differences_over_a_non_power_of_two_spacing_fall_back(ctx, oracle)
     a, b, odu, odv = fused_vs_oracle(ctx, oracle, f0, f1, u, v, w, h, w, h, np.float32(1.1), np.float32(1.1), 35.0, 1, 5, 0)
     assert np.array_equal(bits(a), bits(odu)) and np.array_equal(bits(b), bits(odv))
     assert ctx.fused_fallbacks() > before
+    build.served(1)
 
 
-def test_a_spacing_outside_the_guarded_range_takes_the_plain_divisions(ctx, oracle):
+def test_a_spacing_outside_the_guarded_range_takes_the_plain_divisions(ctx, oracle, build):
     """h = 3 * 2^40: 2h is above 2^40, outside the range the three-step division is proven for; the launch runs the
     plain pass throughout -- every wave counted as a plain-only wave, none as a guard trip -- and equals the oracle."""
     w, h = 640, 200
@@ -262,6 +304,7 @@ def test_a_spacing_outside_the_guarded_range_takes_the_plain_divisions(ctx, orac
     assert np.array_equal(bits(a), bits(odu)) and np.array_equal(bits(b), bits(odv))
     assert ctx.fused_plain_waves() > plain_before
     assert ctx.fused_fallbacks() == before  # the guard counter is for guard trips only
+    build.served(1)
 
 
 @pytest.mark.parametrize("inner", [1, 2, 5])
@@ -313,10 +356,14 @@ def test_lone_context_uses_the_packed_build_with_the_same_bits(flow2d, ctx, orac
     and the oracle, including a launch that continues an outer iteration's sweeps (no packed kernels for those: falls through)."""
     w, h = 1024, 512   # 20 strips wide, few strips per column: under one workgroup per CU
     f0, f1, u, v, _, _ = level_fields(oracle, w, h, 21)
-    results = []
+    outer = 2
     for lone in (False, True):
         ctx.set_lone(lone)
         for inner in (5, 8):
-            a, b, odu, odv = fused_vs_oracle(ctx, oracle, f0, f1, u, v, w, h, w, h, np.float32(1.0), np.float32(1.0), 35.0, 2, inner, constancy)
+            before = flow2d.fused_packed_launches()
+            a, b, odu, odv = fused_vs_oracle(ctx, oracle, f0, f1, u, v, w, h, w, h, np.float32(1.0), np.float32(1.0), 35.0, outer, inner, constancy)
             assert np.array_equal(bits(a), bits(odu)) and np.array_equal(bits(b), bits(odv)), (lone, inner)
+            # the packed build served the launch that starts each outer iteration (inner 8: 4 + 4 sweeps, the second launch continues
+            # the first one's and is the pipeline build's), and nothing on a context that is not lone
+            assert flow2d.fused_packed_launches() - before == (outer if lone else 0), (lone, inner)
     ctx.set_lone(False)
