@@ -248,6 +248,39 @@ CORRELATION_RECORD_BYTES = 32  # FLOW2D_CORRELATION_RECORD_BYTES, checked by a s
 assert C.sizeof(CorrelationRecord) == CORRELATION_RECORD_BYTES
 
 
+class CorrelationPassRecord(C.Structure):
+    """flow2d_correlation_pass_record of include/flow2d_c_abi.h: the six counts flow2d_correlate_offset_2d writes per instance."""
+    _fields_ = [("nodes", C.c_ulonglong), ("invalid", C.c_ulonglong), ("rejected", C.c_ulonglong), ("unrefined", C.c_ulonglong),
+                ("unpredicted", C.c_ulonglong), ("candidates", C.c_ulonglong), ("reserved", C.c_ulonglong * 2)]
+
+    def summary(self):
+        return {name: getattr(self, name) for name, _ in self._fields_[:6]}
+
+
+class ValidationRecord(C.Structure):
+    """flow2d_validation_record of include/flow2d_c_abi.h: the six counts flow2d_validate_nodes_2d writes per instance."""
+    _fields_ = [("nodes", C.c_ulonglong), ("judged", C.c_ulonglong), ("outliers", C.c_ulonglong), ("filled", C.c_ulonglong),
+                ("unjudged", C.c_ulonglong), ("remaining_invalid", C.c_ulonglong), ("reserved", C.c_ulonglong * 2)]
+
+    def summary(self):
+        return {name: getattr(self, name) for name, _ in self._fields_[:6]}
+
+
+CORRELATION_PASS_RECORD_BYTES = VALIDATION_RECORD_BYTES = 64  # FLOW2D_*_RECORD_BYTES, checked by static_asserts in the header
+assert C.sizeof(CorrelationPassRecord) == CORRELATION_PASS_RECORD_BYTES and C.sizeof(ValidationRecord) == VALIDATION_RECORD_BYTES
+CORRELATION_MAX_PASSES = 6  # FLOW2D_CORRELATION_MAX_PASSES
+
+
+class CorrelationPassReport(C.Structure):
+    """OpticalFlow2D::CorrelationPassReport: one pass of correlate_multipass -- its grid, the correlation's record and the
+    validation's (zero where the pass was not validated)."""
+    _fields_ = [("nw", C.c_size_t), ("nh", C.c_size_t), ("correlation", CorrelationPassRecord), ("validation", ValidationRecord)]
+
+    def summary(self):
+        return {"nw": self.nw, "nh": self.nh, "correlation": self.correlation.summary(), "validation": self.validation.summary()}
+VALIDATE_FLAG, VALIDATE_REPLACE = 0, 1  # FLOW2D_VALIDATE_*
+
+
 class PriorReport(C.Structure):
     """OpticalFlow2D::PriorReport: what a pyramid started from a prior flow reports -- the level it started at, the levels it ran
     and the count of prior pixels that were not finite (they entered as zero)."""
@@ -460,6 +493,9 @@ def hip_lib():
             L.flow2d_correlation_grid.argtypes = [sz, sz, i, i, C.POINTER(sz), C.POINTER(sz)]
             L.flow2d_correlate_2d.argtypes = [vp, vp, vp, sz, sz, sz, f, f, i, i, i, f, vp, vp, vp, sz, vp]
             L.flow2d_expand_nodes_2d.argtypes = [vp, vp, vp, sz, sz, sz, i, i, vp, vp, sz, sz, sz]
+        if hasattr(L, "flow2d_correlate_offset_2d"):
+            L.flow2d_correlate_offset_2d.argtypes = [vp, vp, vp, vp, vp, sz, sz, sz, f, f, i, i, i, f, vp, vp, vp, sz, vp]
+            L.flow2d_validate_nodes_2d.argtypes = [vp, vp, vp, sz, sz, sz, f, f, i, i, vp, vp, vp, vp]
         if hasattr(L, "flow2d_prior_registration_2d"):  # (absent from libraries of earlier rounds loaded for an A/B)
             L.flow2d_prior_registration_2d.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp, sz, sz, sz, f, f, vp, vp]
         if hasattr(L, "flow2d_propagate_flow_2d"):  # (absent from libraries of earlier rounds loaded for an A/B)
@@ -1070,6 +1106,79 @@ class Context:
         _check(hip_lib().flow2d_expand_nodes_2d(self.handle, node_u.ptr, node_v.ptr, nw, nh, node_u.pitch, int(radius), int(spacing),
                                                 out_u.ptr, out_v.ptr, w, h, out_u.pitch), "flow2d_expand_nodes_2d")
 
+    def pass_records(self, instances=1):
+        """A Plane for `instances` 64-byte records (flow2d_correlation_pass_record or flow2d_validation_record; device memory)."""
+        return self.plane(instances * CORRELATION_PASS_RECORD_BYTES // 4, 1)
+
+    def _read_records(self, record, instances, kind):
+        raw = record.download(instances * C.sizeof(kind) // 4, 1)
+        return list((kind * instances).from_buffer_copy(raw.tobytes()))
+
+    def read_correlation_pass_record(self, record, instances=1):
+        """The records of a pass_records Plane as CorrelationPassRecord structures (synchronises)."""
+        return self._read_records(record, instances, CorrelationPassRecord)
+
+    def read_validation_record(self, record, instances=1):
+        """The records of a pass_records Plane as ValidationRecord structures (synchronises)."""
+        return self._read_records(record, instances, ValidationRecord)
+
+    def correlate_offset(self, f0, f1, w, h, lo, scale, radius, search, spacing, min_score=-1.0, predictor=None, node_u=None,
+                         node_v=None, node_score=None, record=True, instances=1):
+        """One pass of a multi-pass window correlation (flow2d_correlate_offset_2d): Context.correlate with the search of every node
+        centred on the offset its pixel of the dense `predictor` -- a (u, v) pair of Planes of the frames' size, or None: no
+        offset -- rounds to.  Node planes and record as for correlate; the record is a pass_records Plane or True.
+        Returns (u, v, score or None, CorrelationPassRecord or None)."""
+        own_planes = node_u is None and node_v is None
+        if not own_planes and (node_u is None or node_v is None):
+            raise ValueError("correlate_offset takes both node planes or neither")
+        own_record = record is True
+        if own_record and instances != 1:
+            raise ValueError("a lock-step batch takes the caller's records")
+        pu, pv = predictor if predictor is not None else (None, None)
+        nw, nh = correlation_grid(w, h, radius, spacing)
+        held = [self.plane(nw, nh) for _ in range(3)] if own_planes else [node_u, node_v, node_score]
+        rec = self.pass_records(instances) if own_record else (record or None)
+        try:
+            _check(hip_lib().flow2d_correlate_offset_2d(self.handle, f0.ptr, f1.ptr, pu.ptr if pu is not None else None,
+                                                        pv.ptr if pv is not None else None, w, h, f0.pitch, float(lo), float(scale),
+                                                        int(radius), int(search), int(spacing), float(min_score), held[0].ptr,
+                                                        held[1].ptr, held[2].ptr if held[2] is not None else None, held[0].pitch,
+                                                        rec.ptr if rec is not None else None), "flow2d_correlate_offset_2d")
+            u, v, score = (q.download(nw, nh) for q in held) if own_planes else held
+            return u, v, score, (self.read_correlation_pass_record(rec, 1)[0] if own_record else None)
+        finally:
+            for q in (held if own_planes else []) + ([rec] if own_record else []):
+                q.free()
+                self._planes.remove(q)
+
+    def validate_nodes(self, node_u, node_v, nw, nh, threshold=2.0, epsilon=0.1, min_neighbours=3, mode=VALIDATE_REPLACE, out_u=None,
+                       out_v=None, out_flag=None, record=True, instances=1):
+        """The normalised median test of a node field (flow2d_validate_nodes_2d), out of place: a node whose u or v lies more than
+        `threshold` normalised residuals from the median of its finite neighbours is an outlier -- NaN with VALIDATE_FLAG, the
+        neighbours' median with VALIDATE_REPLACE, which also fills invalid nodes; nodes with fewer than min_neighbours finite
+        neighbours are copied.  out_u, out_v (and optionally out_flag): the caller's Planes, which stay on the device; without
+        them the call allocates all three, downloads them and returns arrays.  record as for correlate_offset.
+        Returns (u, v, flag or None, ValidationRecord or None)."""
+        own_planes = out_u is None and out_v is None
+        if not own_planes and (out_u is None or out_v is None):
+            raise ValueError("validate_nodes takes both output planes or neither")
+        own_record = record is True
+        if own_record and instances != 1:
+            raise ValueError("a lock-step batch takes the caller's records")
+        held = [self.plane(node_u.pitch // 4, nh) for _ in range(3)] if own_planes else [out_u, out_v, out_flag]
+        rec = self.pass_records(instances) if own_record else (record or None)
+        try:
+            _check(hip_lib().flow2d_validate_nodes_2d(self.handle, node_u.ptr, node_v.ptr, nw, nh, node_u.pitch, float(threshold),
+                                                      float(epsilon), int(min_neighbours), int(mode), held[0].ptr, held[1].ptr,
+                                                      held[2].ptr if held[2] is not None else None,
+                                                      rec.ptr if rec is not None else None), "flow2d_validate_nodes_2d")
+            u, v, flag = (q.download(nw, nh) for q in held) if own_planes else held
+            return u, v, flag, (self.read_validation_record(rec, 1)[0] if own_record else None)
+        finally:
+            for q in (held if own_planes else []) + ([rec] if own_record else []):
+                q.free()
+                self._planes.remove(q)
+
     def resample_x(self, src, dst, out_w, out_h, in_w):
         _check(hip_lib().flow2d_resample_x(self.handle, src.ptr, dst.ptr, out_w, out_h, in_w, src.pitch),
                "flow2d_resample_x")
@@ -1343,6 +1452,11 @@ def host_lib():
             L.flow2d_host_refine_args_ok.argtypes = [i, f, f, i]
             L.flow2d_host_refine_flow.argtypes = [vp, fp, fp, i, f, f, i, i, fp, fp, rr, C.POINTER(HostParams), fp, fp, fp]
             L.flow2d_host_refine_flow_device.argtypes = [vp, vp, vp, i, f, f, i, i, vp, vp, rr, C.POINTER(HostParams), vp, vp, vp, i]
+        if hasattr(L, "flow2d_host_correlate_multipass_device"):
+            ip, rp = C.POINTER(C.c_int), C.POINTER(CorrelationPassReport)
+            L.flow2d_host_correlation_passes_ok.argtypes = [sz, sz, f, f, ip, i, f, f, f, i]
+            L.flow2d_host_correlate_multipass_device.argtypes = [vp, vp, vp, f, f, ip, i, f, f, f, i, i, i, vp, vp, vp, vp, vp, rp, vp, vp]
+            L.flow2d_host_correlate_multipass.argtypes = [vp, fp, fp, ip, i, f, f, f, i, i, i, fp, fp, fp, fp, fp, rp, fp, fp, fp]
         if hasattr(L, "flow2d_host_correlate"):
             cr = C.POINTER(CorrelationRecord)
             L.flow2d_host_correlation_args_ok.argtypes = [sz, sz, f, f, i, i, i, f]
@@ -1825,6 +1939,62 @@ class OpticalFlow:
         if rc:
             raise Flow2DError(rc, "OpticalFlow2D::CorrelateDevice")
         return rec
+
+    @staticmethod
+    def _passes(passes):
+        flat = [int(x) for p in passes for x in p]
+        if len(flat) != 3 * len(passes):
+            raise ValueError("a pass is (radius, range, spacing)")
+        return (C.c_int * max(len(flat), 1))(*flat), len(passes)
+
+    @staticmethod
+    def correlation_passes_ok(width, height, lo, scale, passes, min_score=-1.0, threshold=2.0, epsilon=0.1, min_neighbours=3):
+        """OpticalFlow2D::CorrelationPassesOk: whether correlate_multipass* accepts the schedule.  Needs no device."""
+        arr, n = OpticalFlow._passes(passes)
+        return bool(host_lib().flow2d_host_correlation_passes_ok(width, height, float(lo), float(scale), arr, n, float(min_score),
+                                                                 float(threshold), float(epsilon), int(min_neighbours)))
+
+    def correlate_multipass(self, frame_0, frame_1, passes, min_score=-1.0, threshold=2.0, epsilon=0.1, min_neighbours=3, replace=True,
+                            validate_last=True, predictor=None, flow=False):
+        """OpticalFlow2D::CorrelateMultiPass: the host pair through `passes` -- 1 .. CORRELATION_MAX_PASSES triples (radius, range,
+        spacing), coarse to fine --, every pass searching around the validated, expanded field of the one before (the first around
+        `predictor`, a (u, v) pair of images, or around nothing).  Returns (node_u, node_v, node_score, [CorrelationPassReport],
+        (lo, scale)) on the last pass's grid; with flow, also the (u, v) of the field expanded to the frame's grid."""
+        f0, f1 = self._pair(frame_0, frame_1)
+        arr, n = self._passes(passes)
+        if not 1 <= n <= CORRELATION_MAX_PASSES:
+            raise Flow2DError(1, "OpticalFlow2D::CorrelateMultiPass")
+        nw, nh = correlation_grid(self.width, self.height, passes[-1][0], passes[-1][2])
+        nodes = [np.empty((nh, nw), np.float32) for _ in range(3)]
+        uv = [np.empty_like(f0) for _ in range(2)] if flow else [None, None]
+        pred = [np.ascontiguousarray(q, np.float32) for q in predictor] if predictor is not None else [None, None]
+        reports = (CorrelationPassReport * n)()
+        lo_scale = (C.c_float * 2)()
+        rc = host_lib().flow2d_host_correlate_multipass(self.handle, _fptr(f0), _fptr(f1), arr, n, float(min_score), float(threshold),
+                                                        float(epsilon), int(min_neighbours), int(bool(replace)), int(bool(validate_last)),
+                                                        _opt_fptr(pred[0]), _opt_fptr(pred[1]), _fptr(nodes[0]), _fptr(nodes[1]),
+                                                        _fptr(nodes[2]), reports, _opt_fptr(uv[0]), _opt_fptr(uv[1]), lo_scale)
+        if rc:
+            raise Flow2DError(rc, "OpticalFlow2D::CorrelateMultiPass")
+        out = (nodes[0], nodes[1], nodes[2], list(reports), (lo_scale[0], lo_scale[1]))
+        return out + (tuple(uv),) if flow else out
+
+    def correlate_multipass_device(self, dev_frame_0, dev_frame_1, lo, scale, passes, min_score=-1.0, threshold=2.0, epsilon=0.1,
+                                   min_neighbours=3, replace=True, validate_last=True, dev_predictor=None, dev_nodes=None, dev_score=None,
+                                   dev_flow=None):
+        """OpticalFlow2D::CorrelateMultiPassDevice: device frames in.  dev_predictor (a (u, v) pair of planes of the container's
+        size, optional): the first pass's predictor; dev_nodes, dev_score, dev_flow as for correlate_device, from the last pass.
+        Returns one CorrelationPassReport per pass; synchronises."""
+        arr, n = self._passes(passes)
+        reports = (CorrelationPassReport * max(n, 1))()
+        pr, nd, fl = dev_predictor or (None, None), dev_nodes or (None, None), dev_flow or (None, None)
+        rc = host_lib().flow2d_host_correlate_multipass_device(self.handle, dev_frame_0, dev_frame_1, float(lo), float(scale), arr, n,
+                                                               float(min_score), float(threshold), float(epsilon), int(min_neighbours),
+                                                               int(bool(replace)), int(bool(validate_last)), pr[0], pr[1], nd[0], nd[1],
+                                                               dev_score, reports, fl[0], fl[1])
+        if rc:
+            raise Flow2DError(rc, "OpticalFlow2D::CorrelateMultiPassDevice")
+        return list(reports)[:n]
 
     @staticmethod
     def _prior_level(level):

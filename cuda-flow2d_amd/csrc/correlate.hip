@@ -27,6 +27,7 @@
 // flow2d_expand_nodes_2d: per pixel, the 64 x 4 geometry of plane_sample.hpp, four gathers from each node plane.
 #include <cmath>
 
+#include "correlate_score.hpp"
 #include "ordered_reduce.hpp"
 #include "plane_sample.hpp"
 
@@ -56,78 +57,6 @@ struct CorrArgs {
     unsigned tiles_x;
     float lo, scale, min_score;
 };
-
-__device__ __forceinline__ unsigned quantise(float sample, float lo, float scale)
-{
-    const float t = (sample - lo) * scale;
-    if (!(t > 0.f)) return 0u;
-    if (t >= 255.f) return 255u;
-    return static_cast<unsigned>(static_cast<int>(t + 0.5f));
-}
-
-// whether (c1, dx1, dy1) comes before (c2, dx2, dy2) in the order of the peak
-__device__ __forceinline__ bool comes_first(double c1, int dx1, int dy1, double c2, int dx2, int dy2)
-{
-    if (c1 != c2) return c1 > c2;
-    const int n1 = dx1 * dx1 + dy1 * dy1, n2 = dx2 * dx2 + dy2 * dy2;
-    if (n1 != n2) return n1 < n2;
-    if (dy1 != dy2) return dy1 < dy2;
-    return dx1 < dx2;
-}
-
-// One node's view of the staged patches: q0 at its window's first pixel, q1 at the pixel displacement (0, 0) puts there.
-struct CorrNode {
-    const unsigned char *q0, *q1;
-    int p0w, p1w;      // row lengths of the patches
-    int left, top;     // the window's first pixel in the frame
-    int w, h, side;    // the frame; side = 2r + 1
-    long long n, s0, v0;
-};
-
-// The four bytes at p, which may have any alignment: the two aligned dwords around them (one ds_read2_b32) and a byte funnel
-// shift.  (One dword load at a byte address is legal in LDS and gives the same bytes; measured, the whole kernel is 5.6 times
-// slower with it: 13.3 against 2.4 ms on the PIV grid at 4096^2.)
-__device__ __forceinline__ unsigned four_pixels(const unsigned char* p)
-{
-    const unsigned shift = static_cast<unsigned>(reinterpret_cast<uintptr_t>(p)) & 3u;
-    const unsigned* q = reinterpret_cast<const unsigned*>(p - shift);
-    return __builtin_amdgcn_alignbyte(q[1], q[0], shift);
-}
-
-// The score of displacement (dx, dy); false when it is no candidate.
-__device__ __forceinline__ bool score_at(const CorrNode& nd, int dx, int dy, double& c)
-{
-    const int lx = nd.left + dx, ly = nd.top + dy;
-    if (lx < 0 || ly < 0 || lx + nd.side > nd.w || ly + nd.side > nd.h) return false;
-    const unsigned char* p0 = nd.q0;
-    const unsigned char* p1 = nd.q1 + dy * nd.p1w + dx;
-    unsigned s1 = 0, s11 = 0, s01 = 0;  // at most 961 * 255^2 < 2^26
-    // four pixels of a row at a time: four bytes of each patch (four_pixels) and three packed byte dot products.  A row has an odd
-    // number of pixels: its last one or three come from four bytes of which the others -- the next pixels of the patch, or the
-    // arrays' padding -- are masked off.
-    const int quads = nd.side >> 2;
-    const unsigned tail = (1u << (8 * (nd.side & 3))) - 1u;
-    for (int wy = 0; wy < nd.side; ++wy) {
-        for (int q = 0; q < quads; ++q) {
-            const unsigned a = four_pixels(p0 + 4 * q), b = four_pixels(p1 + 4 * q);
-            s1 = __builtin_amdgcn_udot4(b, 0x01010101u, s1, false);
-            s11 = __builtin_amdgcn_udot4(b, b, s11, false);
-            s01 = __builtin_amdgcn_udot4(a, b, s01, false);
-        }
-        const unsigned a = four_pixels(p0 + 4 * quads) & tail, b = four_pixels(p1 + 4 * quads) & tail;
-        s1 = __builtin_amdgcn_udot4(b, 0x01010101u, s1, false);
-        s11 = __builtin_amdgcn_udot4(b, b, s11, false);
-        s01 = __builtin_amdgcn_udot4(a, b, s01, false);
-        p0 += nd.p0w;
-        p1 += nd.p1w;
-    }
-    const long long l1 = s1;
-    const long long v1 = nd.n * static_cast<long long>(s11) - l1 * l1;
-    if (v1 <= 0) return false;
-    const long long cov = nd.n * static_cast<long long>(s01) - nd.s0 * l1;
-    c = static_cast<double>(cov) / sqrt(static_cast<double>(nd.v0) * static_cast<double>(v1));
-    return true;
-}
 
 template <typename Offset>
 __global__ __launch_bounds__(kCorrThreads) void correlate_kernel(CorrArgs a, BatchArg batch)
@@ -164,7 +93,6 @@ __global__ __launch_bounds__(kCorrThreads) void correlate_kernel(CorrArgs a, Bat
     __syncthreads();
 
     const int reach = 2 * d + 1, candidates = reach * reach, pixels = side * side;
-    const float nan = __uint_as_float(0x7FC00000u);
     unsigned n_nodes = 0, n_invalid = 0, n_rejected = 0, n_unrefined = 0;  // the same in every lane of a wave
     for (int node = wave; node < ni * nj; node += kCorrWaves) {
         const int jn = node / ni, in = node - jn * ni;
@@ -215,41 +143,16 @@ __global__ __launch_bounds__(kCorrThreads) void correlate_kernel(CorrArgs a, Bat
                 }
             }
         }
-        const bool found = best > -INFINITY;  // (a score is finite: V0 > 0 and V1 > 0)
-
-        // the four neighbours of the peak, by lanes 0 .. 3: (-1, 0), (+1, 0), (0, -1), (0, +1)
-        const bool inner = found && abs(bx) < d && abs(by) < d;
-        double cn = 0.0;
-        bool has = false;
-        if (inner && lane < 4) has = score_at(nd, bx + (lane == 0 ? -1 : lane == 1 ? 1 : 0), by + (lane == 2 ? -1 : lane == 3 ? 1 : 0), cn);
-        const bool refined = inner && (__ballot(has) & 0xFull) == 0xFull;
-        const double cxm = __shfl(cn, 0, 64), cxp = __shfl(cn, 1, 64), cym = __shfl(cn, 2, 64), cyp = __shfl(cn, 3, 64);
-
-        float u = nan, v = nan, score = 0.f;
-        bool rejected = false;
-        if (found) {
-            double delta_x = 0.0, delta_y = 0.0;
-            if (refined) {
-                const double den_x = (cxm - 2.0 * best) + cxp, den_y = (cym - 2.0 * best) + cyp;
-                delta_x = den_x < 0.0 ? (cxm - cxp) / (2.0 * den_x) : 0.0;
-                delta_y = den_y < 0.0 ? (cym - cyp) / (2.0 * den_y) : 0.0;
-            }
-            score = static_cast<float>(best);
-            rejected = score < a.min_score;
-            if (!rejected) {
-                u = static_cast<float>(static_cast<double>(bx) + delta_x);
-                v = static_cast<float>(static_cast<double>(by) + delta_y);
-            }
-        }
+        const CorrResult res = finish_node(nd, d, lane, best, bx, by, 0, 0, a.min_score);
         n_nodes += 1;
-        n_invalid += !found;
-        n_rejected += rejected;
-        n_unrefined += found && !rejected && !refined;
+        n_invalid += !res.found;
+        n_rejected += res.rejected;
+        n_unrefined += res.found && !res.rejected && !res.refined;
         if (lane == 0) {
             const size_t at = inst + static_cast<size_t>(j_first + jn) * static_cast<size_t>(a.npitch) + static_cast<size_t>(i_first + in);
-            a.nu[at] = u;
-            a.nv[at] = v;
-            if (a.ns) a.ns[at] = score;
+            a.nu[at] = res.u;
+            a.nv[at] = res.v;
+            if (a.ns) a.ns[at] = res.score;
         }
     }
     if (a.record && lane == 0) {

@@ -631,6 +631,99 @@ HOST_API int flow2d_host_correlate_device(flow2d_host_flow* h, void* dev_frame_0
                : 2;
 }
 
+// ---- multi-pass window correlation -----------------------------------------------------------------------------------------------
+// passes: three ints per pass (radius, range, spacing).
+static std::vector<OpticalFlow2D::CorrelationPass> correlation_passes(const int* passes, int count)
+{
+    std::vector<OpticalFlow2D::CorrelationPass> out;
+    for (int k = 0; passes && k < count; ++k) out.push_back({passes[3 * k], passes[3 * k + 1], passes[3 * k + 2]});
+    return out;
+}
+
+static OpticalFlow2D::ValidationOptions validation_options(float threshold, float epsilon, int min_neighbours, int replace, int validate_last)
+{
+    OpticalFlow2D::ValidationOptions v;
+    v.threshold = threshold;
+    v.epsilon = epsilon;
+    v.min_neighbours = min_neighbours;
+    v.replace = replace != 0;
+    v.validate_last = validate_last != 0;
+    return v;
+}
+
+// OpticalFlow2D::CorrelationPassesOk: 1 when the schedule and the validation options are what CorrelateMultiPass* accepts for a
+// width x height frame.  Needs no device.
+HOST_API int flow2d_host_correlation_passes_ok(size_t width, size_t height, float lo, float scale, const int* passes, int count,
+                                               float min_score, float threshold, float epsilon, int min_neighbours)
+{
+    const auto list = correlation_passes(passes, count);
+    return count >= 0 && OpticalFlow2D::CorrelationPassesOk(width, height, lo, scale, list.data(), list.size(), min_score,
+                                                            validation_options(threshold, epsilon, min_neighbours, 1, 1))
+               ? 1
+               : 0;
+}
+
+// OpticalFlow2D::CorrelateMultiPassDevice: device planes of the container's size (predictor, node planes, score and flow optional);
+// reports (optional): one OpticalFlow2D::CorrelationPassReport per pass.  Synchronises.  0 on success, 1 for a null or refused
+// argument, 2 when the run failed.
+HOST_API int flow2d_host_correlate_multipass_device(flow2d_host_flow* h, void* dev_frame_0, void* dev_frame_1, float lo, float scale,
+                                                    const int* passes, int count, float min_score, float threshold, float epsilon,
+                                                    int min_neighbours, int replace, int validate_last, void* dev_predictor_u,
+                                                    void* dev_predictor_v, void* dev_node_u, void* dev_node_v, void* dev_node_score,
+                                                    OpticalFlow2D::CorrelationPassReport* reports, void* dev_flow_u, void* dev_flow_v)
+{
+    const auto list = correlation_passes(passes, count);
+    const auto validation = validation_options(threshold, epsilon, min_neighbours, replace, validate_last);
+    if (!h || !dev_frame_0 || !dev_frame_1 || count < 0 || (dev_flow_u == nullptr) != (dev_flow_v == nullptr) ||
+        (dev_predictor_u == nullptr) != (dev_predictor_v == nullptr) || (dev_node_u == nullptr) != (dev_node_v == nullptr) ||
+        !OpticalFlow2D::CorrelationPassesOk(h->width, h->height, lo, scale, list.data(), list.size(), min_score, validation))
+        return 1;
+    h->flow.timing_mode = 0;
+    return h->flow.CorrelateMultiPassDevice(dp(dev_frame_0), dp(dev_frame_1), lo, scale, list.data(), list.size(), min_score, validation,
+                                            dp(dev_predictor_u), dp(dev_predictor_v), dp(dev_node_u), dp(dev_node_v), dp(dev_node_score),
+                                            reports, dp(dev_flow_u), dp(dev_flow_v))
+               ? 0
+               : 2;
+}
+
+// OpticalFlow2D::CorrelateMultiPass on tight host images: node_u / node_v / node_score (optional) get the last pass's nw * nh
+// floats each, flow_u / flow_v (optional, both or neither) its field on the frame's grid, predictor_u / predictor_v (optional,
+// both or neither) are the initial predictor, lo_scale (optional) the two numbers of CorrelationRange.
+HOST_API int flow2d_host_correlate_multipass(flow2d_host_flow* h, const float* frame_0, const float* frame_1, const int* passes, int count,
+                                             float min_score, float threshold, float epsilon, int min_neighbours, int replace,
+                                             int validate_last, const float* predictor_u, const float* predictor_v, float* node_u,
+                                             float* node_v, float* node_score, OpticalFlow2D::CorrelationPassReport* reports,
+                                             float* flow_u, float* flow_v, float* lo_scale)
+{
+    const auto list = correlation_passes(passes, count);
+    const auto validation = validation_options(threshold, epsilon, min_neighbours, replace, validate_last);
+    if (!h || !frame_0 || !frame_1 || !node_u || !node_v || count < 0 || (flow_u == nullptr) != (flow_v == nullptr) ||
+        (predictor_u == nullptr) != (predictor_v == nullptr))
+        return 1;
+    HostImages im(h);
+    Data2D *f0 = im.In(frame_0), *f1 = im.In(frame_1);
+    Data2D *pu = predictor_u ? im.In(predictor_u) : nullptr, *pv = predictor_v ? im.In(predictor_v) : nullptr;
+    Data2D *fu = im.Out(flow_u, im.AfterSuccess), *fv = im.Out(flow_v, im.AfterSuccess);
+    float lo = 0.f, scale = 1.f;
+    OpticalFlow2D::CorrelationRange(*f0, *f1, lo, scale);
+    if (!OpticalFlow2D::CorrelationPassesOk(h->width, h->height, lo, scale, list.data(), list.size(), min_score, validation)) return 1;
+    size_t nw = 0, nh = 0;
+    flow2d_correlation_grid(h->width, h->height, list.back().radius, list.back().spacing, &nw, &nh);
+    Data2D nodes[3] = {Data2D(nw, nh), Data2D(nw, nh), Data2D(nw, nh)};
+    h->flow.CorrelateMultiPass(*f0, *f1, list.data(), list.size(), min_score, validation, nodes[0], nodes[1],
+                               node_score ? &nodes[2] : nullptr, reports, fu, fv, pu, pv);
+    const int rc = im.Finish(h->flow);
+    if (rc) return rc;
+    float* dst[3] = {node_u, node_v, node_score};
+    for (int k = 0; k < 3; ++k)
+        if (dst[k]) std::memcpy(dst[k], nodes[k].DataPtr(), nw * nh * sizeof(float));
+    if (lo_scale) {
+        lo_scale[0] = lo;
+        lo_scale[1] = scale;
+    }
+    return 0;
+}
+
 // ---- the pyramid started from a prior flow ------------------------------------------------------------------------------------
 // OpticalFlow2D::PriorReport as the facade hands it out
 struct flow2d_host_prior_report {

@@ -67,6 +67,13 @@
 // "nodes", "invalid", "rejected", "unrefined" -- is printed.  With --ground-truth the line "Flow error: {json}" scores the expanded
 // field.  It does not combine with the options that run the variational flow (--backward, --interpolate, --track, --denoise,
 // --global-motion, --segment-motion, --deformation, --refine).  Without --correlation nothing changes.
+// --correlation-passes R:D:S[,R:D:S...] (1 .. 6 passes, coarse to fine) [--validate-threshold T, default 2] [--validate-epsilon E,
+// default 0.1] [--validate-min-neighbours K, 1 .. 8, default 3] [--validate-flag-only] [--correlation-min-score C] runs the multi-pass
+// window correlation (OpticalFlow2D::CorrelateMultiPass: every pass searches around the validated, expanded field of the one
+// before; --initial-flow FILE.flo, accepted with it, is the first pass's predictor) instead of the variational flow.  The files are
+// those of --correlation, from the last pass (whose outliers --validate-flag-only leaves as NaN instead of replacing them), and
+// one line "CorrelationPasses: {json}" -- the options and, per pass, the grid and both records -- is printed.  It excludes
+// --correlation and everything that runs or seeds the variational flow.  Without it nothing changes.
 // --initial-flow FILE.flo | --correlation-prior R  [--prior-reach P, pixels, finite and > 0, default 2] [--prior-level L, >= 0]
 // start the variational pyramid from a prior flow instead of from zero at its coarsest level (OpticalFlow2D::ComputeFlowFromPrior /
 // ComputeFlowCorrelationSeeded): the prior is a Middlebury file of the frames' size, or the window correlation of the pair with
@@ -140,6 +147,9 @@ int main(int argc, char** argv)
     Methods method = Methods::OpticalFlow;  // --correlation R: Methods::Correlation
     int correlation_radius = 0, correlation_range = 8, correlation_spacing = 8;
     float correlation_min_score = -1.f;
+    std::vector<OpticalFlow2D::CorrelationPass> correlation_passes;  // --correlation-passes R:D:S[,R:D:S...]
+    OpticalFlow2D::ValidationOptions validation;                     // --validate-threshold / -epsilon / -min-neighbours / -flag-only
+    bool validate_option = false;
     std::string initial_flow_file;  // --initial-flow FILE.flo
     int prior_radius = 0;           // --correlation-prior R (0: off)
     float prior_reach = 2.f;
@@ -349,6 +359,54 @@ int main(int argc, char** argv)
             if (which == 0) method = Methods::Correlation;
             ++i;
         }
+        else if (!std::strcmp(argv[i], "--correlation-passes")) {
+            const char* p = (i + 1 < argc) ? argv[i + 1] : "";
+            bool ok = *p != '\0';
+            while (ok && *p) {
+                int value[3] = {0, 0, 0};
+                for (int k = 0; ok && k < 3; ++k) {
+                    char* end = nullptr;
+                    const long n = std::strtol(p, &end, 10);
+                    ok = end != p && n >= 1 && n <= 64 && *end == (k < 2 ? ':' : (*end == ',' ? ',' : '\0'));
+                    value[k] = static_cast<int>(n);
+                    p = ok && *end ? end + 1 : end;
+                }
+                ok = ok && (*p || p[-1] != ',');
+                if (ok) correlation_passes.push_back({value[0], value[1], value[2]});
+            }
+            if (!ok || correlation_passes.size() > FLOW2D_CORRELATION_MAX_PASSES) {
+                std::printf("--correlation-passes takes 1 .. %d passes RADIUS:RANGE:SPACING separated by commas, coarse to fine.\n",
+                            FLOW2D_CORRELATION_MAX_PASSES);
+                return 5;
+            }
+            ++i;
+        }
+        else if (!std::strcmp(argv[i], "--validate-threshold") || !std::strcmp(argv[i], "--validate-epsilon")) {
+            char* end = nullptr;
+            const float value = (i + 1 < argc) ? std::strtof(argv[i + 1], &end) : 0.f;
+            if (i + 1 >= argc || end == argv[i + 1] || *end != '\0' || !(std::isfinite(value) && value > 0.f)) {
+                std::printf("%s takes a finite number > 0.\n", argv[i]);
+                return 5;
+            }
+            (!std::strcmp(argv[i], "--validate-threshold") ? validation.threshold : validation.epsilon) = value;
+            validate_option = true;
+            ++i;
+        }
+        else if (!std::strcmp(argv[i], "--validate-min-neighbours")) {
+            char* end = nullptr;
+            const long n = (i + 1 < argc) ? std::strtol(argv[i + 1], &end, 10) : 0;
+            if (i + 1 >= argc || end == argv[i + 1] || *end != '\0' || n < 1 || n > 8) {
+                std::printf("--validate-min-neighbours takes an integer of 1 .. 8.\n");
+                return 5;
+            }
+            validation.min_neighbours = static_cast<int>(n);
+            validate_option = true;
+            ++i;
+        }
+        else if (!std::strcmp(argv[i], "--validate-flag-only")) {
+            validation.replace = false;
+            validate_option = true;
+        }
         else if (!std::strcmp(argv[i], "--correlation-min-score")) {
             char* end = nullptr;
             const float value = (i + 1 < argc) ? std::strtof(argv[i + 1], &end) : 0.f;
@@ -375,7 +433,20 @@ int main(int argc, char** argv)
         return 5;
     }
 
-    const bool from_prior = !initial_flow_file.empty() || prior_radius != 0 || !previous_flow_file.empty();
+    const bool multipass = !correlation_passes.empty();
+    if (validate_option && !multipass) {
+        std::printf("The --validate-* options belong to --correlation-passes.\n");
+        return 5;
+    }
+    if (multipass && (method == Methods::Correlation || backward || interpolate || track_spacing || denoise || global_model >= 0 || segment ||
+                      deformation || refine_radius || prior_radius != 0 || !previous_flow_file.empty() || prior_option)) {
+        std::printf("--correlation-passes replaces the variational flow: it does not combine with --correlation or with the options that "
+                    "run or seed the flow (--initial-flow FILE.flo is its first pass's predictor).\n");
+        return 5;
+    }
+
+    // (with --correlation-passes the initial flow is the first pass's predictor, not the prior of a pyramid)
+    const bool from_prior = (!initial_flow_file.empty() && !multipass) || prior_radius != 0 || !previous_flow_file.empty();
     if (!initial_flow_file.empty() && prior_radius != 0) {
         std::printf("--initial-flow and --correlation-prior are two sources of one prior: give one of them.\n");
         return 5;
@@ -551,7 +622,49 @@ int main(int argc, char** argv)
             occlusion_1 = Data2D(width, height);
         }
         Data2D node_u, node_v, node_score;
-        if (method == Methods::Correlation) {
+        if (multipass) {
+            const OpticalFlow2D::CorrelationPass& fine = correlation_passes.back();
+            float lo = 0.f, scale = 1.f;
+            OpticalFlow2D::CorrelationRange(frame_0, frame_1, lo, scale);
+            size_t nw = 0, nh = 0;
+            if (!OpticalFlow2D::CorrelationPassesOk(width, height, lo, scale, correlation_passes.data(), correlation_passes.size(),
+                                                    correlation_min_score, validation) ||
+                flow2d_correlation_grid(width, height, fine.radius, fine.spacing, &nw, &nh) != FLOW2D_OK) {
+                optical_flow.Destroy();
+                DestroyDeviceContext();
+                return 4;
+            }
+            node_u = Data2D(nw, nh);
+            node_v = Data2D(nw, nh);
+            node_score = Data2D(nw, nh);
+            std::vector<OpticalFlow2D::CorrelationPassReport> reports(correlation_passes.size());
+            const bool predicted = !initial_flow_file.empty();
+            optical_flow.CorrelateMultiPass(frame_0, frame_1, correlation_passes.data(), correlation_passes.size(), correlation_min_score,
+                                            validation, node_u, node_v, &node_score, reports.data(), &flow_u, &flow_v,
+                                            predicted ? &prior_u : nullptr, predicted ? &prior_v : nullptr);
+            if (optical_flow.LastRunSucceeded()) {
+                const std::string nodes = "-" + std::to_string(nw) + "-" + std::to_string(nh) + ".raw";
+                node_u.WriteRAWToFileF32((output_path + counter + "node-u" + nodes).c_str());
+                node_v.WriteRAWToFileF32((output_path + counter + "node-v" + nodes).c_str());
+                node_score.WriteRAWToFileF32((output_path + counter + "node-score" + nodes).c_str());
+                std::printf("CorrelationPasses: {\"min_score\": %.9g, \"lo\": %.9g, \"scale\": %.9g, \"threshold\": %.9g, \"epsilon\": %.9g, "
+                            "\"min_neighbours\": %d, \"replace\": %s, \"predictor\": %s, \"passes\": [",
+                            correlation_min_score, lo, scale, validation.threshold, validation.epsilon, validation.min_neighbours,
+                            validation.replace ? "true" : "false", predicted ? "true" : "false");
+                for (size_t k = 0; k < reports.size(); ++k) {
+                    const flow2d_correlation_pass_record& c = reports[k].correlation;
+                    const flow2d_validation_record& v = reports[k].validation;
+                    std::printf("%s{\"radius\": %d, \"range\": %d, \"spacing\": %d, \"nw\": %zu, \"nh\": %zu, \"correlation\": {\"nodes\": %llu, "
+                                "\"invalid\": %llu, \"rejected\": %llu, \"unrefined\": %llu, \"unpredicted\": %llu, \"candidates\": %llu}, "
+                                "\"validation\": {\"nodes\": %llu, \"judged\": %llu, \"outliers\": %llu, \"filled\": %llu, \"unjudged\": %llu, "
+                                "\"remaining_invalid\": %llu}}",
+                                k ? ", " : "", correlation_passes[k].radius, correlation_passes[k].range, correlation_passes[k].spacing,
+                                reports[k].nw, reports[k].nh, c.nodes, c.invalid, c.rejected, c.unrefined, c.unpredicted, c.candidates,
+                                v.nodes, v.judged, v.outliers, v.filled, v.unjudged, v.remaining_invalid);
+                }
+                std::printf("]}\n");
+            }
+        } else if (method == Methods::Correlation) {
             size_t nw = 0, nh = 0;
             if (flow2d_correlation_grid(width, height, correlation_radius, correlation_spacing, &nw, &nh) != FLOW2D_OK) {
                 std::printf("Error: a %zu x %zu frame is smaller than one correlation window of radius %d.\n", width, height,

@@ -292,6 +292,42 @@ public:
                    Data2D& node_v, Data2D* node_score, flow2d_correlation_record* record_out, Data2D* flow_u = nullptr,
                    Data2D* flow_v = nullptr);
 
+    // Multi-pass window correlation (multi-grid interrogation with a discrete window offset; the normalised median test between
+    // passes): 1 .. FLOW2D_CORRELATION_MAX_PASSES passes, each flow2d_correlate_offset_2d around the current predictor -- NULL in
+    // pass 1 unless dev_predictor_u / dev_predictor_v (optional, both or neither: a dense flow in planes of the container's size,
+    // only read) are given --, then flow2d_validate_nodes_2d in REPLACE mode and flow2d_expand_nodes_2d into planes of the
+    // object's own, which are the next pass's predictor.  After the last pass the test runs in the caller's mode
+    // (validation.replace; not at all without validation.validate_last); node planes (optional, as for CorrelateDevice) and score
+    // come from that pass, dev_flow_u / dev_flow_v (optional, both or neither) get its field on the frame's grid.  reports_out
+    // (host, optional, one per pass): the grid and both records; the validation record of a last pass that was not validated is
+    // zero.  CorrelationPassesOk prints what is wrong and needs no device.  Planes and records are allocated at the first call
+    // and kept.  The call synchronises once, at the end.  Not for lock-step groups.
+    struct CorrelationPass {
+        int radius, range, spacing;
+    };
+    struct ValidationOptions {
+        float threshold = 2.f, epsilon = 0.1f;
+        int min_neighbours = 3;
+        bool replace = true, validate_last = true;
+    };
+    struct CorrelationPassReport {
+        size_t nw, nh;
+        flow2d_correlation_pass_record correlation;
+        flow2d_validation_record validation;
+    };
+    static bool CorrelationPassesOk(size_t width, size_t height, float lo, float scale, const CorrelationPass* passes, size_t count,
+                                    float min_score, const ValidationOptions& validation);
+    bool CorrelateMultiPassDevice(DevicePtr dev_frame_0, DevicePtr dev_frame_1, float lo, float scale, const CorrelationPass* passes,
+                                  size_t count, float min_score, const ValidationOptions& validation, DevicePtr dev_predictor_u,
+                                  DevicePtr dev_predictor_v, DevicePtr dev_node_u, DevicePtr dev_node_v, DevicePtr dev_node_score,
+                                  CorrelationPassReport* reports_out, DevicePtr dev_flow_u = 0, DevicePtr dev_flow_v = 0);
+    // The host-image form (the CLI's --correlation-passes): lo and scale from CorrelationRange; node_u / node_v (and node_score,
+    // optional) are images of the LAST pass's grid; predictor_u / predictor_v (optional, both or neither): the initial predictor.
+    void CorrelateMultiPass(Data2D& frame_0, Data2D& frame_1, const CorrelationPass* passes, size_t count, float min_score,
+                            const ValidationOptions& validation, Data2D& node_u, Data2D& node_v, Data2D* node_score,
+                            CorrelationPassReport* reports_out, Data2D* flow_u = nullptr, Data2D* flow_v = nullptr,
+                            Data2D* predictor_u = nullptr, Data2D* predictor_v = nullptr);
+
     // The pyramid started from a prior flow instead of from zero at the coarsest level (no reference counterpart; Brox & Malik's
     // large-displacement flow and the predictor-corrector passes of PIV start the variational solver from matches in the same
     // way).  dev_prior_u / dev_prior_v: a flow in full-resolution pixels in planes of the container's size, only read; a pixel
@@ -594,6 +630,9 @@ private:
     // Correlate*: the node planes the caller did not give (u, v) and the record
     OwnedPlanes correlation_planes_{owned_, 2};
     DeviceScratch correlation_scratch_{owned_};
+    // CorrelateMultiPass*: a pass's raw nodes (u, v), its validated nodes (u, v), the predictor (u, v); the passes' records
+    OwnedPlanes multipass_planes_{owned_, 6};
+    DeviceScratch multipass_scratch_{owned_};
     // ComputeFlowFromPrior*: inside such a run the prior's planes and the start level (RunPyramid starts there, from them); the
     // device count of the prior's non-finite pixels; the expanded field of ComputeFlowCorrelationSeeded* (u, v; first use)
     DevicePtr prior_u_ = 0, prior_v_ = 0;

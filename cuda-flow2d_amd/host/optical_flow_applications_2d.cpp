@@ -624,6 +624,141 @@ void OpticalFlow2D::Correlate(Data2D& frame_0, Data2D& frame_1, int radius, int 
     last_run_ok_ = ok;
 }
 
+bool OpticalFlow2D::CorrelationPassesOk(size_t width, size_t height, float lo, float scale, const CorrelationPass* passes, size_t count,
+                                        float min_score, const ValidationOptions& validation)
+{
+    if (!passes || count < 1 || count > FLOW2D_CORRELATION_MAX_PASSES) {
+        std::printf("Error: multi-pass window correlation takes 1 .. %d passes (%zu).\n", FLOW2D_CORRELATION_MAX_PASSES, count);
+        return false;
+    }
+    if (!(std::isfinite(validation.threshold) && validation.threshold > 0.f) ||
+        !(std::isfinite(validation.epsilon) && validation.epsilon > 0.f) || validation.min_neighbours < 1 ||
+        validation.min_neighbours > 8) {
+        std::printf("Error: the validation between passes takes a finite threshold > 0 (%g), a finite epsilon > 0 (%g) and 1 .. 8 "
+                    "neighbours at least (%d).\n",
+                    validation.threshold, validation.epsilon, validation.min_neighbours);
+        return false;
+    }
+    for (size_t k = 0; k < count; ++k) {
+        if (CorrelationArgsOk(width, height, lo, scale, passes[k].radius, passes[k].range, passes[k].spacing, min_score)) continue;
+        std::printf("Error: pass %zu of %zu (radius %d : range %d : spacing %d) is refused.\n", k + 1, count, passes[k].radius,
+                    passes[k].range, passes[k].spacing);
+        return false;
+    }
+    return true;
+}
+
+bool OpticalFlow2D::CorrelateMultiPassDevice(DevicePtr dev_frame_0, DevicePtr dev_frame_1, float lo, float scale,
+                                             const CorrelationPass* passes, size_t count, float min_score,
+                                             const ValidationOptions& validation, DevicePtr dev_predictor_u, DevicePtr dev_predictor_v,
+                                             DevicePtr dev_node_u, DevicePtr dev_node_v, DevicePtr dev_node_score,
+                                             CorrelationPassReport* reports_out, DevicePtr dev_flow_u, DevicePtr dev_flow_v)
+{
+    const size_t W = dev_container_size_.width, H = dev_container_size_.height, pitch = dev_container_size_.pitch;
+    if (!CorrelationPassesOk(W, H, lo, scale, passes, count, min_score, validation)) return false;
+    if (!IsInitialized() || !dev_frame_0 || !dev_frame_1 || (dev_flow_u == 0) != (dev_flow_v == 0) ||
+        (dev_predictor_u == 0) != (dev_predictor_v == 0) || (dev_node_u == 0) != (dev_node_v == 0))
+        return false;
+    if (RefuseGroup("multi-pass window correlation")) return false;
+    {
+        // the caller's written planes pass through the validation and the expansion, which know no frame: checked here
+        std::vector<DevicePtr> read = {dev_frame_0, dev_frame_1}, written;
+        for (DevicePtr p : {dev_predictor_u, dev_predictor_v})
+            if (p) read.push_back(p);
+        for (DevicePtr p : {dev_node_u, dev_node_v, dev_node_score, dev_flow_u, dev_flow_v})
+            if (p) written.push_back(p);
+        if (!WrittenPlanesOk(read.data(), read.size(), written.data(), written.size(), "node, score or flow plane")) return false;
+    }
+    if (!EnsurePlanes(multipass_planes_, 6)) return false;
+    const DevicePtr* own = multipass_planes_.data();
+    // per pass: the correlation's record, then the validation's
+    const size_t pair = sizeof(flow2d_correlation_pass_record) + sizeof(flow2d_validation_record);
+    if (!multipass_scratch_.Ensure(context_, count * pair)) return false;
+    const float* predictor[2] = {dev_predictor_u ? AsPlane(dev_predictor_u) : nullptr, dev_predictor_u ? AsPlane(dev_predictor_v) : nullptr};
+    bool ok = true;
+    for (size_t k = 0; ok && k < count; ++k) {
+        const bool last = k + 1 == count, validated = !last || validation.validate_last;
+        const CorrelationPass& pass = passes[k];
+        auto* record = multipass_scratch_.At<flow2d_correlation_pass_record>(k * pair);
+        auto* checked = multipass_scratch_.At<flow2d_validation_record>(k * pair + sizeof(flow2d_correlation_pass_record));
+        size_t nw = 0, nh = 0;
+        flow2d_correlation_grid(W, H, pass.radius, pass.spacing, &nw, &nh);
+        // where the pass's final nodes go: the caller's planes after the last pass, when there are any
+        DevicePtr final_u = last && dev_node_u ? dev_node_u : own[validated ? 2 : 0];
+        DevicePtr final_v = last && dev_node_v ? dev_node_v : own[validated ? 3 : 1];
+        DevicePtr raw_u = validated ? own[0] : final_u, raw_v = validated ? own[1] : final_v;
+        // (the node planes are containers: the frames' pitch)
+        ok = !CheckFlow2DError(flow2d_correlate_offset_2d(context_, AsPlane(dev_frame_0), AsPlane(dev_frame_1), predictor[0], predictor[1], W,
+                                                          H, pitch, lo, scale, pass.radius, pass.range, pass.spacing, min_score,
+                                                          AsPlane(raw_u), AsPlane(raw_v),
+                                                          last && dev_node_score ? AsPlane(dev_node_score) : nullptr, pitch, record),
+                               "flow2d_correlate_offset_2d");
+        if (ok && validated)
+            ok = !CheckFlow2DError(flow2d_validate_nodes_2d(context_, AsPlane(raw_u), AsPlane(raw_v), nw, nh, pitch, validation.threshold,
+                                                            validation.epsilon, validation.min_neighbours,
+                                                            !last || validation.replace ? FLOW2D_VALIDATE_REPLACE : FLOW2D_VALIDATE_FLAG,
+                                                            AsPlane(final_u), AsPlane(final_v), nullptr, checked),
+                                   "flow2d_validate_nodes_2d");
+        if (ok && !last) {
+            ok = !CheckFlow2DError(flow2d_expand_nodes_2d(context_, AsPlane(final_u), AsPlane(final_v), nw, nh, pitch, pass.radius,
+                                                          pass.spacing, AsPlane(own[4]), AsPlane(own[5]), W, H, pitch),
+                                   "flow2d_expand_nodes_2d");
+            predictor[0] = AsPlane(own[4]);
+            predictor[1] = AsPlane(own[5]);
+        } else if (ok && dev_flow_u) {
+            ok = !CheckFlow2DError(flow2d_expand_nodes_2d(context_, AsPlane(final_u), AsPlane(final_v), nw, nh, pitch, pass.radius,
+                                                          pass.spacing, AsPlane(dev_flow_u), AsPlane(dev_flow_v), W, H, pitch),
+                                   "flow2d_expand_nodes_2d");
+        }
+        if (ok && reports_out) {
+            CorrelationPassReport& report = reports_out[k];
+            report = CorrelationPassReport{};
+            report.nw = nw;
+            report.nh = nh;
+            ok = ReadRecord(&report.correlation, record, sizeof(report.correlation)) &&
+                 (!validated || ReadRecord(&report.validation, checked, sizeof(report.validation)));
+        }
+    }
+    return !CheckFlow2DError(flow2d_synchronize(context_), "flow2d_synchronize") && ok;
+}
+
+void OpticalFlow2D::CorrelateMultiPass(Data2D& frame_0, Data2D& frame_1, const CorrelationPass* passes, size_t count, float min_score,
+                                       const ValidationOptions& validation, Data2D& node_u, Data2D& node_v, Data2D* node_score,
+                                       CorrelationPassReport* reports_out, Data2D* flow_u, Data2D* flow_v, Data2D* predictor_u,
+                                       Data2D* predictor_v)
+{
+    last_run_ok_ = false;
+    if (!IsInitialized() || (flow_u == nullptr) != (flow_v == nullptr) || (predictor_u == nullptr) != (predictor_v == nullptr)) return;
+    CallPlanes planes(context_, dev_container_size_, GetName(), "frame / flow");
+    planes.Add(&frame_0, CallPlanes::In).Add(&frame_1, CallPlanes::In).Add(flow_u, CallPlanes::Out).Add(flow_v, CallPlanes::Out);
+    // the node planes: containers with no image of their size behind them, downloaded below
+    planes.Add(nullptr, CallPlanes::Out, true).Add(nullptr, CallPlanes::Out, true).Add(nullptr, CallPlanes::Out, node_score != nullptr);
+    if (predictor_u) planes.Add(predictor_u, CallPlanes::In).Add(predictor_v, CallPlanes::In);
+    if (!planes.SizesMatch()) return;
+    float lo = 0.f, scale = 1.f;
+    CorrelationRange(frame_0, frame_1, lo, scale);
+    const size_t W = dev_container_size_.width, H = dev_container_size_.height;
+    if (!CorrelationPassesOk(W, H, lo, scale, passes, count, min_score, validation)) return;
+    size_t nw = 0, nh = 0;
+    flow2d_correlation_grid(W, H, passes[count - 1].radius, passes[count - 1].spacing, &nw, &nh);
+    Data2D* nodes[3] = {&node_u, &node_v, node_score};
+    for (Data2D* image : nodes)
+        if (image && (image->Width() != nw || image->Height() != nh)) {
+            std::printf("Error: '%s': the node images are not %zu x %zu.\n", GetName(), nw, nh);
+            return;
+        }
+    HostCall call(context_, last_total_ms_, planes.Allocate());
+    const DevicePtr* d = planes.data();
+    bool ok = planes.Upload() &&
+              CorrelateMultiPassDevice(d[0], d[1], lo, scale, passes, count, min_score, validation, predictor_u ? d[7] : 0, predictor_u ? d[8] : 0, d[4],
+                                       d[5], d[6],
+                                       reports_out, d[2], d[3]) &&
+              planes.Download();
+    for (int k = 0; ok && k < 3; ++k)
+        if (nodes[k]) ok = CopyData2DFromDevice(d[4 + k], *nodes[k], H, dev_container_size_.pitch);
+    last_run_ok_ = ok;
+}
+
 bool OpticalFlow2D::StabiliseSequenceDevice(const DevicePtr* dev_frames, size_t frame_count, size_t reference_index, int model,
                                             double sigma, int iterations, bool use_masks, float fill,
                                             const DevicePtr* dev_outputs, flow2d_global_motion* motions_out,

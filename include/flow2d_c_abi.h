@@ -43,7 +43,9 @@ extern "C" {
  * (strain, divergence and vorticity of a flow), flow2d_refine_flow_2d (edge-aware refinement of a flow), flow2d_correlate_2d /
  * flow2d_correlation_grid / flow2d_expand_nodes_2d (window correlation) and flow2d_prior_registration_2d (the first level of a
  * pyramid started from a prior flow) and flow2d_propagate_flow_2d (a flow carried along itself: the prior of a warm-started
- * sequence) and flow2d_fused_packed_launches (a test hook: which build of the strip kernel a launch took) were added under 1. */
+ * sequence) and flow2d_fused_packed_launches (a test hook: which build of the strip kernel a launch took) and
+ * flow2d_correlate_offset_2d / flow2d_validate_nodes_2d (multi-pass window correlation: the search around a predictor's
+ * offset and the normalised median test between passes) were added under 1. */
 #define FLOW2D_ABI_VERSION 1
 
 typedef enum flow2d_status {
@@ -860,6 +862,116 @@ FLOW2D_API int flow2d_correlate_2d(flow2d_context* ctx, const float* frame_0, co
 FLOW2D_API int flow2d_expand_nodes_2d(flow2d_context* ctx, const float* node_u, const float* node_v, size_t nw, size_t nh,
                                       size_t node_pitch_bytes, int radius, int spacing, float* out_u, float* out_v, size_t width,
                                       size_t height, size_t pitch_bytes);
+
+/* Multi-pass window correlation (multi-grid interrogation with a discrete window offset, Westerweel 1997; the normalised median
+ * test, Westerweel & Scarano 2005): the two steps a chain of passes is made of besides flow2d_expand_nodes_2d.  A coarse pass
+ * with large windows finds the motion; its validated node field, expanded to the frame's grid, is the *predictor* of the next
+ * pass, which searches a small range around it with smaller windows on a denser grid.  Added to ABI version 1 without changing
+ * any existing entry.
+ *
+ * flow2d_correlate_offset_2d: flow2d_correlate_2d with the search of every node centred on an integer offset read from a dense
+ * predictor.  Everything not restated here -- quantisation, nodes and grid, the sums, the score, the order of the peak, the
+ * parabola, invalid and rejected nodes, the node planes, the pitch rules -- is that entry's text.
+ * Predictor.  predictor_u, predictor_v: planes of width x height floats with the frames' pitch, in pixels of the frames; both
+ * NULL or both given.  Node (i, j), centred on pixel (cx, cy) = (r + i*s, r + j*s), reads pu = predictor_u[cy][cx] and
+ * pv = predictor_v[cy][cx] (a node centre is a pixel: nothing is interpolated).  When pu and pv are both finite, in fp32, every
+ * operation rounded on its own:
+ *   ox = (int)floorf(fminf(fmaxf(pu, -32768.f), 32768.f) + 0.5f),   oy likewise from pv
+ * Otherwise ox = oy = 0 and the node is *unpredicted*.  With NULL predictors every offset is 0 and no node is unpredicted: the
+ * node planes and the first four counts are then the bytes of flow2d_correlate_2d.
+ * Candidates.  (dx, dy), |dx| <= d and |dy| <= d, is a candidate of the node when the window centred on (cx + ox + dx,
+ * cy + oy + dy) lies inside frame 1 and its V1 > 0; S1, S11 and S01 are taken over that window.  The order of the peak compares
+ * dx and dy *relative to the offset*, and the node is unrefined when |dx| = d, |dy| = d or one of the four neighbours
+ * (dx -+ 1, dy), (dx, dy -+ 1) is no candidate.  Then
+ *   u = (float)((double)(ox + dx) + delta_x),   v = (float)((double)(oy + dy) + delta_y),   score = (float)c0
+ * (ox + dx in int: exact).  An offset that pushes every candidate out of frame 1 leaves the node invalid.
+ * Record.  record[b] (DEVICE memory, may be NULL), 64 bytes: nodes, invalid, rejected, unrefined as in flow2d_correlation_record;
+ * unpredicted; candidates -- the number of (node, displacement) pairs that are candidates, over the nodes with V0 > 0 (the work
+ * the pass did: each costs N multiply-adds); two reserved words, written as 0.  Integers, added by integer atomics after the
+ * entry has zeroed the record on the stream.
+ * One launch on the context's stream (and a 64-byte memset per instance with a record); no allocation, no synchronisation, no
+ * host round trip (graph-capturable).  Honours flow2d_context_set_batch: frames, predictor planes and node planes of instance b
+ * at b * stride floats from their pointers, record + b.
+ * FLOW2D_ERR_INVALID_ARGUMENT, and nothing written, for everything flow2d_correlate_2d refuses, one predictor without the other,
+ * a predictor that breaks the frames' plane rules, or a written range -- the node planes, the records, over every instance of a
+ * batch -- that overlaps a frame, a predictor or another written range; FLOW2D_ERR_UNSUPPORTED for a grid of 2^31 nodes or
+ * more. */
+typedef struct flow2d_correlation_pass_record {
+    unsigned long long nodes;       /* nw * nh */
+    unsigned long long invalid;     /* V0 = 0 or no candidate: NaN, score 0 */
+    unsigned long long rejected;    /* score < min_score: NaN, score kept */
+    unsigned long long unrefined;   /* delivered vectors without a sub-pixel part */
+    unsigned long long unpredicted; /* nodes whose predictor was not finite: offset 0 */
+    unsigned long long candidates;  /* (node, displacement) pairs scored */
+    unsigned long long reserved[2]; /* 0 */
+} flow2d_correlation_pass_record;
+
+#define FLOW2D_CORRELATION_PASS_RECORD_BYTES 64
+#define FLOW2D_CORRELATION_MAX_PASSES 6 /* of the host layer's chain (OpticalFlow2D::CorrelateMultiPass) */
+#ifdef __cplusplus
+static_assert(sizeof(flow2d_correlation_pass_record) == FLOW2D_CORRELATION_PASS_RECORD_BYTES, "flow2d_correlation_pass_record layout");
+#else
+_Static_assert(sizeof(flow2d_correlation_pass_record) == FLOW2D_CORRELATION_PASS_RECORD_BYTES, "flow2d_correlation_pass_record layout");
+#endif
+
+FLOW2D_API int flow2d_correlate_offset_2d(flow2d_context* ctx, const float* frame_0, const float* frame_1,
+                                          const float* predictor_u /* may be NULL */, const float* predictor_v /* with predictor_u */,
+                                          size_t width, size_t height, size_t pitch_bytes, float lo, float scale, int radius,
+                                          int range, int spacing, float min_score, float* node_u, float* node_v,
+                                          float* node_score /* may be NULL */, size_t node_pitch_bytes,
+                                          flow2d_correlation_pass_record* record /* device, may be NULL */);
+
+/* The normalised median test of a node field, out of place: every node is judged against the input's neighbours, so the result
+ * depends on no order.  Per node (i, j) of the nw x nh field:
+ * Neighbours.  The up to eight nodes of the 3 x 3 ring around it that lie inside the grid and whose u and v are both finite; k
+ * of them.  A node is *valid* when its own u and v are both finite.
+ * Median of k floats (k >= 1): sorted by the floats' order-preserving integer key (b = the float's bits as int32;
+ * key = b ^ ((b >> 31) & 0x7FFFFFFF), so -0 < +0) into a[0 .. k-1], the median is (a[(k-1)/2] + a[k/2]) * 0.5f.
+ * In fp32, every operation rounded on its own (no fused multiply-add; division correctly rounded):
+ *   mu, mv = the medians of the neighbours' u and of their v;   ru = the median of |u_i - mu| over the neighbours, rv alike
+ *   for a valid node:  tu = |u - mu| / (ru + epsilon),  tv = |v - mv| / (rv + epsilon);  an *outlier* when tu > threshold || tv > threshold
+ * Outcome (out_u, out_v; flag):
+ *   k < min_neighbours                                      the node's own bits; 0      -- *unjudged*, valid or not
+ *   valid, no outlier                                       the node's own bits; 0
+ *   outlier, mode FLOW2D_VALIDATE_FLAG                      NaN (0x7FC00000), NaN; 1
+ *   outlier, mode FLOW2D_VALIDATE_REPLACE                   mu, mv; 1
+ *   not valid, k >= min_neighbours, FLOW2D_VALIDATE_REPLACE mu, mv; 2           -- *filled*
+ *   not valid, k >= min_neighbours, FLOW2D_VALIDATE_FLAG    the node's own bits; 0
+ * out_flag (may be NULL) is a float plane that gets 0, 1 or 2.  All planes are nw x nh floats with node_pitch_bytes per row.
+ * Record.  record[b] (DEVICE memory, may be NULL), 64 bytes: nodes (nw * nh); judged -- valid nodes with k >= min_neighbours;
+ * outliers; filled; unjudged; remaining_invalid -- the nodes whose out_u and out_v are not both finite; two reserved words,
+ * written as 0.  Integers, added by integer atomics after the entry has zeroed the record on the stream: alone, in a batch and
+ * in a replayed graph the same bytes.
+ * Row padding and the containers beyond nw x nh are neither read into a result nor written.  One launch on the context's stream
+ * (and a 64-byte memset per instance with a record); no allocation, no synchronisation (graph-capturable).  Honours
+ * flow2d_context_set_batch: every plane of instance b at b * stride floats, record + b.
+ * FLOW2D_ERR_INVALID_ARGUMENT, and nothing written, for a null node_u, node_v, out_u or out_v, a zero size, a bad pitch, a
+ * min_neighbours outside 1 .. 8, a threshold or an epsilon that is not finite and > 0, an unknown mode, a misaligned record (8),
+ * or a written range -- outputs, flag, records, over every instance of a batch -- that overlaps an input or another written
+ * range; FLOW2D_ERR_UNSUPPORTED for 2^31 nodes or more. */
+#define FLOW2D_VALIDATE_FLAG 0
+#define FLOW2D_VALIDATE_REPLACE 1
+typedef struct flow2d_validation_record {
+    unsigned long long nodes;             /* nw * nh */
+    unsigned long long judged;            /* valid nodes with k >= min_neighbours */
+    unsigned long long outliers;          /* judged nodes that failed the test: flag 1 */
+    unsigned long long filled;            /* invalid nodes that took their neighbours' median: flag 2 */
+    unsigned long long unjudged;          /* k < min_neighbours: copied */
+    unsigned long long remaining_invalid; /* output nodes that are not finite */
+    unsigned long long reserved[2];       /* 0 */
+} flow2d_validation_record;
+
+#define FLOW2D_VALIDATION_RECORD_BYTES 64
+#ifdef __cplusplus
+static_assert(sizeof(flow2d_validation_record) == FLOW2D_VALIDATION_RECORD_BYTES, "flow2d_validation_record layout");
+#else
+_Static_assert(sizeof(flow2d_validation_record) == FLOW2D_VALIDATION_RECORD_BYTES, "flow2d_validation_record layout");
+#endif
+
+FLOW2D_API int flow2d_validate_nodes_2d(flow2d_context* ctx, const float* node_u, const float* node_v, size_t nw, size_t nh,
+                                        size_t node_pitch_bytes, float threshold, float epsilon, int min_neighbours, int mode,
+                                        float* out_u, float* out_v, float* out_flag /* may be NULL */,
+                                        flow2d_validation_record* record /* device, may be NULL */);
 
 /* The flow of the previous pyramid level resampled to this level's size (the bits of flow2d_resample_xy_pair into out_u / out_v)
  * and frame_1 warped by it (the bits of flow2d_registration_2d into `output`) in one launch: replaces the
