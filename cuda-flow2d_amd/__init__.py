@@ -271,6 +271,21 @@ assert C.sizeof(CorrelationPassRecord) == CORRELATION_PASS_RECORD_BYTES and C.si
 CORRELATION_MAX_PASSES = 6  # FLOW2D_CORRELATION_MAX_PASSES
 
 
+class SubsetRecord(C.Structure):
+    """flow2d_subset_record of include/flow2d_c_abi.h: the seven counts flow2d_subset_refine_2d writes per instance."""
+    _fields_ = [("nodes", C.c_ulonglong), ("converged", C.c_ulonglong), ("unconverged", C.c_ulonglong), ("strayed", C.c_ulonglong),
+                ("flat", C.c_ulonglong), ("no_input", C.c_ulonglong), ("iterations", C.c_ulonglong), ("reserved", C.c_ulonglong)]
+
+    def summary(self):
+        return {name: getattr(self, name) for name, _ in self._fields_[:7]}
+
+
+SUBSET_RECORD_BYTES = 64  # FLOW2D_SUBSET_RECORD_BYTES, checked by a static_assert in the header
+assert C.sizeof(SubsetRecord) == SUBSET_RECORD_BYTES
+SUBSET_MAX_RADIUS, SUBSET_MAX_ITERATIONS = 15, 64  # FLOW2D_SUBSET_MAX_*
+SUBSET_NO_INPUT, SUBSET_FLAT, SUBSET_STRAYED = -1, -2, -3  # the negative states of flow2d_subset_refine_2d
+
+
 class CorrelationPassReport(C.Structure):
     """OpticalFlow2D::CorrelationPassReport: one pass of correlate_multipass -- its grid, the correlation's record and the
     validation's (zero where the pass was not validated)."""
@@ -496,6 +511,8 @@ def hip_lib():
         if hasattr(L, "flow2d_correlate_offset_2d"):
             L.flow2d_correlate_offset_2d.argtypes = [vp, vp, vp, vp, vp, sz, sz, sz, f, f, i, i, i, f, vp, vp, vp, sz, vp]
             L.flow2d_validate_nodes_2d.argtypes = [vp, vp, vp, sz, sz, sz, f, f, i, i, vp, vp, vp, vp]
+        if hasattr(L, "flow2d_subset_refine_2d"):  # (absent from libraries of earlier rounds loaded for an A/B)
+            L.flow2d_subset_refine_2d.argtypes = [vp, vp, vp, sz, sz, sz, vp, vp, sz, sz, sz, i, i, i, i, f, f, f] + [vp] * 9
         if hasattr(L, "flow2d_prior_registration_2d"):  # (absent from libraries of earlier rounds loaded for an A/B)
             L.flow2d_prior_registration_2d.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp, sz, sz, sz, f, f, vp, vp]
         if hasattr(L, "flow2d_propagate_flow_2d"):  # (absent from libraries of earlier rounds loaded for an A/B)
@@ -1179,6 +1196,52 @@ class Context:
                 q.free()
                 self._planes.remove(q)
 
+    def subset_records(self, instances=1):
+        """A Plane for `instances` flow2d_subset_record records (device memory)."""
+        return self.plane(instances * SUBSET_RECORD_BYTES // 4, 1)
+
+    def read_subset_record(self, record, instances=1):
+        """The records of a subset_records Plane as SubsetRecord structures (synchronises)."""
+        return self._read_records(record, instances, SubsetRecord)
+
+    def subset_refine(self, f0, f1, w, h, node_u0, node_v0, nw, nh, grid_radius, spacing, subset_radius, max_iterations=20,
+                      epsilon=1e-3, max_shift=2.0, max_gradient=0.5, out_u=None, out_v=None, out_gradients=None, out_score=None,
+                      out_state=None, record=True, instances=1):
+        """Subset refinement of a node field (flow2d_subset_refine_2d): every node (i, j) of the Planes node_u0, node_v0 -- centred
+        on pixel (grid_radius + i * spacing, grid_radius + j * spacing), as correlate, correlate_offset and validate_nodes deliver
+        them -- is refined on the fp32 frames by the inverse-compositional Gauss-Newton iteration with an affine shape function
+        over its (2 subset_radius + 1)^2 subset: the displacement to a few hundredths of a pixel and its four gradients.  A node
+        stops when its step falls below `epsilon` (state: the iteration), after max_iterations (state 0), or as SUBSET_NO_INPUT,
+        SUBSET_FLAT or SUBSET_STRAYED (more than max_shift from its start, a gradient beyond max_gradient, or out of the frame).
+        out_u, out_v (and optionally out_gradients = (ux, uy, vx, vy), out_score, out_state): the caller's Planes, which are
+        written and stay on the device; without them the call allocates all eight, downloads them and returns arrays.  record:
+        True -- the counts are read back (synchronises) --, a subset_records Plane of the caller's, or False / None.
+        Returns (u, v, (ux, uy, vx, vy) or None, score or None, state or None, SubsetRecord or None)."""
+        own_planes = out_u is None and out_v is None
+        if not own_planes and (out_u is None or out_v is None):
+            raise ValueError("subset_refine takes both output planes or neither")
+        own_record = record is True
+        if own_record and instances != 1:
+            raise ValueError("a lock-step batch takes the caller's records")
+        if own_planes:
+            held = [self.plane(node_u0.pitch // 4, nh) for _ in range(8)]
+        else:
+            held = [out_u, out_v] + list(out_gradients if out_gradients is not None else (None,) * 4) + [out_score, out_state]
+        rec = self.subset_records(instances) if own_record else (record or None)
+        try:
+            _check(hip_lib().flow2d_subset_refine_2d(self.handle, f0.ptr, f1.ptr, w, h, f0.pitch, node_u0.ptr, node_v0.ptr, nw, nh,
+                                                     node_u0.pitch, int(grid_radius), int(spacing), int(subset_radius),
+                                                     int(max_iterations), float(epsilon), float(max_shift), float(max_gradient),
+                                                     *[q.ptr if q is not None else None for q in held],
+                                                     rec.ptr if rec is not None else None), "flow2d_subset_refine_2d")
+            got = [q.download(nw, nh) for q in held] if own_planes else held
+            gradients = tuple(got[2:6]) if got[2] is not None else None
+            return got[0], got[1], gradients, got[6], got[7], (self.read_subset_record(rec, 1)[0] if own_record else None)
+        finally:
+            for q in (held if own_planes else []) + ([rec] if own_record else []):
+                q.free()
+                self._planes.remove(q)
+
     def resample_x(self, src, dst, out_w, out_h, in_w):
         _check(hip_lib().flow2d_resample_x(self.handle, src.ptr, dst.ptr, out_w, out_h, in_w, src.pitch),
                "flow2d_resample_x")
@@ -1457,6 +1520,13 @@ def host_lib():
             L.flow2d_host_correlation_passes_ok.argtypes = [sz, sz, f, f, ip, i, f, f, f, i]
             L.flow2d_host_correlate_multipass_device.argtypes = [vp, vp, vp, f, f, ip, i, f, f, f, i, i, i, vp, vp, vp, vp, vp, rp, vp, vp]
             L.flow2d_host_correlate_multipass.argtypes = [vp, fp, fp, ip, i, f, f, f, i, i, i, fp, fp, fp, fp, fp, rp, fp, fp, fp]
+        if hasattr(L, "flow2d_host_correlate_subset_device"):
+            ip, rp, sr = C.POINTER(C.c_int), C.POINTER(CorrelationPassReport), C.POINTER(SubsetRecord)
+            L.flow2d_host_subset_options_ok.argtypes = [i, i, f, f, f]
+            L.flow2d_host_refine_nodes_device.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, f, f, f, C.POINTER(vp), sr]
+            L.flow2d_host_correlate_subset_device.argtypes = [vp, vp, vp, f, f, ip, i, f, f, f, i, i, i, f, f, f, vp, vp, C.POINTER(vp), rp, sr,
+                                                              vp, vp]
+            L.flow2d_host_correlate_subset.argtypes = [vp, fp, fp, ip, i, f, f, f, i, i, i, f, f, f, fp, fp, C.POINTER(fp), rp, sr, fp, fp, fp]
         if hasattr(L, "flow2d_host_correlate"):
             cr = C.POINTER(CorrelationRecord)
             L.flow2d_host_correlation_args_ok.argtypes = [sz, sz, f, f, i, i, i, f]
@@ -1995,6 +2065,79 @@ class OpticalFlow:
         if rc:
             raise Flow2DError(rc, "OpticalFlow2D::CorrelateMultiPassDevice")
         return list(reports)[:n]
+
+    SUBSET_PLANES = ("u", "v", "ux", "uy", "vx", "vy", "score", "state")
+
+    @staticmethod
+    def subset_options_ok(radius, iterations=20, epsilon=1e-3, max_shift=2.0, max_gradient=0.5):
+        """OpticalFlow2D::SubsetOptionsOk: whether refine_nodes_device / correlate_subset* accept the options.  Needs no device."""
+        return bool(host_lib().flow2d_host_subset_options_ok(int(radius), int(iterations), float(epsilon), float(max_shift), float(max_gradient)))
+
+    @staticmethod
+    def _subset_planes(dev_out):
+        """The eight device planes of SUBSET_PLANES from a dict name -> address (absent or None: not wanted)."""
+        dev_out = dev_out or {}
+        unknown = set(dev_out) - set(OpticalFlow.SUBSET_PLANES)
+        if unknown:
+            raise ValueError("unknown subset planes %s (of %s)" % (sorted(unknown), ", ".join(OpticalFlow.SUBSET_PLANES)))
+        return (C.c_void_p * 8)(*[dev_out.get(name) for name in OpticalFlow.SUBSET_PLANES])
+
+    def refine_nodes_device(self, dev_frame_0, dev_frame_1, dev_node_u0, dev_node_v0, grid_radius, spacing, radius, iterations=20,
+                            epsilon=1e-3, max_shift=2.0, max_gradient=0.5, dev_out=None, record=True):
+        """OpticalFlow2D::RefineNodesDevice: the node field (dev_node_u0, dev_node_v0) of the grid (grid_radius, spacing) -- planes of
+        the container's size -- refined by subsets of `radius` (flow2d_subset_refine_2d).  dev_out: a dict of device planes by the
+        names of SUBSET_PLANES (u and v both or neither, the four gradients all or none).  Returns the SubsetRecord (the call then
+        synchronises) or, without record, None (it only queues)."""
+        rec = SubsetRecord()
+        rc = host_lib().flow2d_host_refine_nodes_device(self.handle, dev_frame_0, dev_frame_1, dev_node_u0, dev_node_v0, int(grid_radius),
+                                                        int(spacing), int(radius), int(iterations), float(epsilon), float(max_shift),
+                                                        float(max_gradient), self._subset_planes(dev_out), C.byref(rec) if record else None)
+        if rc:
+            raise Flow2DError(rc, "OpticalFlow2D::RefineNodesDevice")
+        return rec if record else None
+
+    def correlate_subset(self, frame_0, frame_1, passes, radius, iterations=20, epsilon=1e-3, max_shift=2.0, max_gradient=0.5,
+                         min_score=-1.0, threshold=2.0, validate_epsilon=0.1, min_neighbours=3, predictor=None, flow=False):
+        """OpticalFlow2D::CorrelateSubset: the host pair through `passes` as in correlate_multipass -- the last pass validated with
+        replacement, so that every node has a start --, then every node of the last pass's grid refined by subsets of `radius` on
+        the unquantised frames.  Returns (nodes, [CorrelationPassReport], SubsetRecord, (lo, scale)), nodes a dict of [nh, nw]
+        arrays by the names of SUBSET_PLANES; with flow, also the (u, v) of the refined field expanded to the frame's grid."""
+        f0, f1 = self._pair(frame_0, frame_1)
+        arr, n = self._passes(passes)
+        if not 1 <= n <= CORRELATION_MAX_PASSES:
+            raise Flow2DError(1, "OpticalFlow2D::CorrelateSubset")
+        nw, nh = correlation_grid(self.width, self.height, passes[-1][0], passes[-1][2])
+        nodes = [np.empty((nh, nw), np.float32) for _ in range(8)]
+        uv = [np.empty_like(f0) for _ in range(2)] if flow else [None, None]
+        pred = [np.ascontiguousarray(q, np.float32) for q in predictor] if predictor is not None else [None, None]
+        reports, rec, lo_scale = (CorrelationPassReport * n)(), SubsetRecord(), (C.c_float * 2)()
+        rc = host_lib().flow2d_host_correlate_subset(self.handle, _fptr(f0), _fptr(f1), arr, n, float(min_score), float(threshold),
+                                                     float(validate_epsilon), int(min_neighbours), int(radius), int(iterations),
+                                                     float(epsilon), float(max_shift), float(max_gradient), _opt_fptr(pred[0]),
+                                                     _opt_fptr(pred[1]), (C.POINTER(C.c_float) * 8)(*[_fptr(q) for q in nodes]), reports,
+                                                     C.byref(rec), _opt_fptr(uv[0]), _opt_fptr(uv[1]), lo_scale)
+        if rc:
+            raise Flow2DError(rc, "OpticalFlow2D::CorrelateSubset")
+        out = (dict(zip(self.SUBSET_PLANES, nodes)), list(reports), rec, (lo_scale[0], lo_scale[1]))
+        return out + (tuple(uv),) if flow else out
+
+    def correlate_subset_device(self, dev_frame_0, dev_frame_1, lo, scale, passes, radius, iterations=20, epsilon=1e-3, max_shift=2.0,
+                                max_gradient=0.5, min_score=-1.0, threshold=2.0, validate_epsilon=0.1, min_neighbours=3, dev_predictor=None,
+                                dev_out=None, dev_flow=None):
+        """OpticalFlow2D::CorrelateSubsetDevice: device frames in; dev_predictor and dev_flow as for correlate_multipass_device (the
+        flow is the refined field's), dev_out as for refine_nodes_device.  Returns ([CorrelationPassReport], SubsetRecord);
+        synchronises once."""
+        arr, n = self._passes(passes)
+        reports, rec = (CorrelationPassReport * max(n, 1))(), SubsetRecord()
+        pr, fl = dev_predictor or (None, None), dev_flow or (None, None)
+        rc = host_lib().flow2d_host_correlate_subset_device(self.handle, dev_frame_0, dev_frame_1, float(lo), float(scale), arr, n,
+                                                            float(min_score), float(threshold), float(validate_epsilon), int(min_neighbours),
+                                                            int(radius), int(iterations), float(epsilon), float(max_shift),
+                                                            float(max_gradient), pr[0], pr[1], self._subset_planes(dev_out), reports,
+                                                            C.byref(rec), fl[0], fl[1])
+        if rc:
+            raise Flow2DError(rc, "OpticalFlow2D::CorrelateSubsetDevice")
+        return list(reports)[:n], rec
 
     @staticmethod
     def _prior_level(level):

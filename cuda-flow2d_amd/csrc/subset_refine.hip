@@ -1,0 +1,410 @@
+// Subset refinement of correlation nodes for gfx950: the inverse-compositional Gauss-Newton iteration with an affine shape
+// function on the zero-mean normalised sum of squared differences, one node per wave.
+//
+// The normative definition is the one of flow2d_subset_refine_2d in flow2d_c_abi.h, in IEEE double.  Built -ffp-contract=off.
+//
+// As in correlate_offset_kernel a wave owns a node and shares nothing with the other waves of its workgroup (no barrier at all
+// here).  A lane owns the subset's pixels lane, lane + 64, ... (at most 16 at R = 15; with N < 64 lanes idle).  What is constant
+// over the iterations -- fd, fx, fy of a lane's pixels -- and the samples g of the current iteration live in the wave's slice
+// of dynamic LDS, four doubles per pixel, each element read and written by its own lane only: 7.2 KB per wave at R = 7, 30.8 KB
+// at R = 15.  The entry sizes the workgroup so that the slices fit the 64 KB every launch may ask for without an attribute
+// call: four waves up to R = 11, three at R = 12, two from R = 13.
+// A *sum over the subset* is the lane's partial over its pixels in ascending order, from 0, then wave_sum's butterfly: every
+// lane ends with the same bits, so H, its Cholesky factor, b and p are the same in every lane -- the 6 x 6 algebra runs
+// redundantly in all lanes, nothing is broadcast, and every branch on a node's state is uniform over the wave.
+// Frame 1 is gathered from global memory, 16 taps per pixel and iteration, clamped to the frame; nothing of it is staged (a patch
+// per node in LDS was built and measured no faster: DESIGN.md 3.17).
+#include <algorithm>
+#include <cmath>
+
+#include "ordered_reduce.hpp"
+#include "plane_sample.hpp"
+
+namespace {
+
+constexpr int kSubsetMaxWaves = 4;
+constexpr int kSubsetCounts = 7;   // the counts of flow2d_subset_record that are written
+constexpr int kSubsetRecordWords = 8;
+constexpr unsigned kSubsetLdsBytes = 64u * 1024u;  // what a launch may ask for without hipFuncSetAttribute
+constexpr int kStateNoInput = -1, kStateFlat = -2, kStateStrayed = -3;
+
+struct SubsetArgs {
+    const float *f0, *f1;
+    const float *u0, *v0;
+    float *u, *v, *ux, *uy, *vx, *vy;  // the gradient planes: all or none
+    float *score, *state;              // null = absent
+    unsigned long long* record;        // eight words per instance, or null
+    int w, h, pitch;                   // the frames; pitch in floats
+    int nw, nh, npitch;                // the node planes
+    int r, s, R, K;
+    unsigned slice;  // doubles of one of a wave's four LDS arrays: N rounded up to a multiple of 2
+    double epsilon, max_shift, max_gradient;
+};
+
+struct SubsetNode {
+    const float* f0;
+    const float* f1;
+    double *fd, *fx, *fy, *g;  // the wave's LDS arrays
+    int w, h, pitch;
+    int cx, cy, R, side, n;
+    int lane;
+};
+
+template <typename Offset>
+__device__ __forceinline__ double sample_at(const float* f, int x, int y, int pitch)
+{
+    return static_cast<double>(load_at(f, pixel_offset<Offset>(x, y, pitch)));
+}
+
+// The four Catmull-Rom weights of the header for t in [0, 1).
+__device__ __forceinline__ void cubic_weights(double t, double (&wt)[4])
+{
+    wt[0] = ((-0.5 * t + 1.0) * t - 0.5) * t;
+    wt[1] = ((1.5 * t - 2.5) * t) * t + 1.0;
+    wt[2] = ((-1.5 * t + 2.0) * t + 0.5) * t;
+    wt[3] = ((0.5 * t - 0.5) * t) * t;
+}
+
+// g of the header at (X, Y), which lies inside [0, w - 1] x [0, h - 1].
+template <typename Offset>
+__device__ __forceinline__ double cubic_sample(const SubsetNode& nd, double X, double Y)
+{
+    const double fx = floor(X), fy = floor(Y);
+    const int ix = static_cast<int>(fx), iy = static_cast<int>(fy);
+    double wx[4], wy[4];
+    cubic_weights(X - fx, wx);
+    cubic_weights(Y - fy, wy);
+    int col[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) col[i] = min(max(ix - 1 + i, 0), nd.w - 1);
+    double rows[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int y = min(max(iy - 1 + j, 0), nd.h - 1);
+        const double a0 = sample_at<Offset>(nd.f1, col[0], y, nd.pitch), a1 = sample_at<Offset>(nd.f1, col[1], y, nd.pitch),
+                     a2 = sample_at<Offset>(nd.f1, col[2], y, nd.pitch), a3 = sample_at<Offset>(nd.f1, col[3], y, nd.pitch);
+        rows[j] = ((wx[0] * a0 + wx[1] * a1) + wx[2] * a2) + wx[3] * a3;
+    }
+    return ((wy[0] * rows[0] + wy[1] * rows[1]) + wy[2] * rows[2]) + wy[3] * rows[3];
+}
+
+// J of the header for pixel k.
+__device__ __forceinline__ void jacobian(const SubsetNode& nd, int k, double (&J)[6])
+{
+    const int ky = k / nd.side, kx = k - ky * nd.side;
+    const double xi = static_cast<double>(kx - nd.R), eta = static_cast<double>(ky - nd.R);
+    const double fx = nd.fx[k], fy = nd.fy[k];
+    J[0] = fx;
+    J[1] = fx * xi;
+    J[2] = fx * eta;
+    J[3] = fy;
+    J[4] = fy * xi;
+    J[5] = fy * eta;
+}
+
+// Solve(b) of the header with the factor L (lower triangle).
+__device__ __forceinline__ void cholesky_solve(const double (&L)[6][6], const double (&b)[6], double (&x)[6])
+{
+    double y[6];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+        double sum = 0.0;
+#pragma unroll
+        for (int m = 0; m < i; ++m) sum += L[i][m] * y[m];
+        y[i] = (b[i] - sum) / L[i][i];
+    }
+#pragma unroll
+    for (int i = 5; i >= 0; --i) {
+        double sum = 0.0;
+#pragma unroll
+        for (int m = i + 1; m < 6; ++m) sum += L[m][i] * x[m];
+        x[i] = (y[i] - sum) / L[i][i];
+    }
+}
+
+// The node from the frame-0 quantities on: the state, with p, the last c and the iterations begun.  p = (u, ux, uy, v, vx, vy)
+// holds (u0, 0, 0, v0, 0, 0) on entry.  Every lane of the wave returns the same values.
+template <typename Offset>
+__device__ __forceinline__ int refine_node(const SubsetNode& nd, const SubsetArgs& a, double (&p)[6], double& score, unsigned& iterations)
+{
+    const double u0 = p[0], v0 = p[3];
+    const double count = static_cast<double>(nd.n);
+    const int left = nd.cx - nd.R, top = nd.cy - nd.R;
+
+    // frame 0: f into the fd array first, its gradients, the mean
+    double sum_f = 0.0;
+    for (int k = nd.lane; k < nd.n; k += 64) {
+        const int ky = k / nd.side, kx = k - ky * nd.side;
+        const int x = left + kx, y = top + ky;
+        const double f = sample_at<Offset>(nd.f0, x, y, nd.pitch);
+        nd.fd[k] = f;
+        nd.fx[k] = (sample_at<Offset>(nd.f0, min(x + 1, nd.w - 1), y, nd.pitch) - sample_at<Offset>(nd.f0, max(x - 1, 0), y, nd.pitch)) * 0.5;
+        nd.fy[k] = (sample_at<Offset>(nd.f0, x, min(y + 1, nd.h - 1), nd.pitch) - sample_at<Offset>(nd.f0, x, max(y - 1, 0), nd.pitch)) * 0.5;
+        sum_f += f;
+    }
+    const double fm = wave_sum(sum_f) / count;
+
+    double df2 = 0.0;
+    double hs[21];
+#pragma unroll
+    for (int i = 0; i < 21; ++i) hs[i] = 0.0;
+    for (int k = nd.lane; k < nd.n; k += 64) {
+        const double fd = nd.fd[k] - fm;
+        nd.fd[k] = fd;
+        df2 += fd * fd;
+        double J[6];
+        jacobian(nd, k, J);
+        int at = 0;
+#pragma unroll
+        for (int i = 0; i < 6; ++i)
+#pragma unroll
+            for (int j = 0; j <= i; ++j) hs[at++] += J[i] * J[j];
+    }
+    df2 = wave_sum(df2);
+    if (!(df2 > 0.0)) return kStateFlat;
+    const double df = sqrt(df2);
+    double L[6][6];  // H's lower triangle, replaced column by column by the factor's
+    {
+        int at = 0;
+#pragma unroll
+        for (int i = 0; i < 6; ++i)
+#pragma unroll
+            for (int j = 0; j <= i; ++j) L[i][j] = wave_sum(hs[at++]);
+    }
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        const double hkk = L[k][k];
+        double sum = 0.0;
+#pragma unroll
+        for (int m = 0; m < k; ++m) sum += L[k][m] * L[k][m];
+        const double d = hkk - sum;
+        if (!(d > 1e-10 * hkk)) return kStateFlat;
+        L[k][k] = sqrt(d);
+#pragma unroll
+        for (int i = k + 1; i < 6; ++i) {
+            double inner = 0.0;
+#pragma unroll
+            for (int m = 0; m < k; ++m) inner += L[i][m] * L[k][m];
+            L[i][k] = (L[i][k] - inner) / L[k][k];
+        }
+    }
+
+    const double xmax = static_cast<double>(nd.w - 1), ymax = static_cast<double>(nd.h - 1);
+    const double radius = static_cast<double>(nd.R);
+    for (int n = 1; n <= a.K; ++n) {
+        iterations = static_cast<unsigned>(n);
+        // 1, 2: positions and samples
+        unsigned outside = 0;
+        double sum_g = 0.0;
+        for (int k = nd.lane; k < nd.n; k += 64) {
+            const int ky = k / nd.side, kx = k - ky * nd.side;
+            const double xi = static_cast<double>(kx - nd.R), eta = static_cast<double>(ky - nd.R);
+            const double X = static_cast<double>(left + kx) + ((p[0] + p[1] * xi) + p[2] * eta);
+            const double Y = static_cast<double>(top + ky) + ((p[3] + p[4] * xi) + p[5] * eta);
+            double g = 0.0;
+            if (X >= 0.0 && X <= xmax && Y >= 0.0 && Y <= ymax)
+                g = cubic_sample<Offset>(nd, X, Y);
+            else
+                outside = 1;
+            nd.g[k] = g;
+            sum_g += g;
+        }
+        if (wave_sum(outside) != 0) return kStateStrayed;
+        // 3: the residual and the step
+        const double gm = wave_sum(sum_g) / count;
+        double dg2 = 0.0, sfg = 0.0;
+        for (int k = nd.lane; k < nd.n; k += 64) {
+            const double gd = nd.g[k] - gm;
+            nd.g[k] = gd;
+            dg2 += gd * gd;
+            sfg += nd.fd[k] * gd;
+        }
+        dg2 = wave_sum(dg2);
+        sfg = wave_sum(sfg);
+        if (!(dg2 > 0.0)) return kStateFlat;
+        const double dg = sqrt(dg2);
+        score = sfg / (df * dg);
+        const double q = df / dg;
+        double b[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        for (int k = nd.lane; k < nd.n; k += 64) {
+            const double res = nd.fd[k] - q * nd.g[k];
+            double J[6];
+            jacobian(nd, k, J);
+#pragma unroll
+            for (int i = 0; i < 6; ++i) b[i] += J[i] * res;
+        }
+#pragma unroll
+        for (int i = 0; i < 6; ++i) b[i] = wave_sum(b[i]);
+        double x[6];
+        cholesky_solve(L, b, x);
+        const double du = -x[0], dux = -x[1], duy = -x[2], dv = -x[3], dvx = -x[4], dvy = -x[5];
+        // 4: p <- W(p) o W(dp)^-1
+        const double ma = 1.0 + dux, mb = duy, mc = dvx, md = 1.0 + dvy;
+        const double det = ma * md - mb * mc;
+        if (!(fabs(det) > 1e-12)) return kStateStrayed;
+        const double ia = md / det, ib = (-mb) / det, ic = (-mc) / det, id = ma / det;
+        const double tx = -(ia * du + ib * dv), ty = -(ic * du + id * dv);
+        const double p11 = 1.0 + p[1], p12 = p[2], p21 = p[4], p22 = 1.0 + p[5];
+        p[0] = (p11 * tx + p12 * ty) + p[0];
+        p[3] = (p21 * tx + p22 * ty) + p[3];
+        p[1] = (p11 * ia + p12 * ic) - 1.0;
+        p[2] = p11 * ib + p12 * id;
+        p[4] = p21 * ia + p22 * ic;
+        p[5] = (p21 * ib + p22 * id) - 1.0;
+        // 5: the bounds, then convergence
+        if (!(fabs(p[0] - u0) <= a.max_shift && fabs(p[3] - v0) <= a.max_shift && fabs(p[1]) <= a.max_gradient &&
+              fabs(p[2]) <= a.max_gradient && fabs(p[4]) <= a.max_gradient && fabs(p[5]) <= a.max_gradient))
+            return kStateStrayed;
+        const double step = sqrt(((((du * du + (radius * dux) * (radius * dux)) + (radius * duy) * (radius * duy)) + dv * dv) +
+                                  (radius * dvx) * (radius * dvx)) + (radius * dvy) * (radius * dvy));
+        if (step < a.epsilon) return n;
+    }
+    return 0;
+}
+
+template <typename Offset>
+__global__ __launch_bounds__(64 * kSubsetMaxWaves) void subset_refine_kernel(SubsetArgs a, BatchArg batch)
+{
+    extern __shared__ __attribute__((aligned(16))) double s_subset[];
+
+    const size_t inst = batch_offset(batch);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int node = blockIdx.x * (blockDim.x >> 6) + wave;
+    if (node >= a.nw * a.nh) return;  // (no barrier anywhere: the last workgroup's surplus waves leave)
+    const int jn = node / a.nw, in = node - jn * a.nw;
+
+    SubsetNode nd;
+    nd.f0 = a.f0 + inst;
+    nd.f1 = a.f1 + inst;
+    nd.fd = s_subset + static_cast<size_t>(wave) * 4u * a.slice;
+    nd.fx = nd.fd + a.slice;
+    nd.fy = nd.fx + a.slice;
+    nd.g = nd.fy + a.slice;
+    nd.w = a.w;
+    nd.h = a.h;
+    nd.pitch = a.pitch;
+    nd.cx = a.r + in * a.s;
+    nd.cy = a.r + jn * a.s;
+    nd.R = a.R;
+    nd.side = 2 * a.R + 1;
+    nd.n = nd.side * nd.side;
+    nd.lane = lane;
+
+    const size_t at = inst + static_cast<size_t>(jn) * static_cast<size_t>(a.npitch) + static_cast<size_t>(in);
+    const float u0 = a.u0[at], v0 = a.v0[at];
+    double p[6] = {static_cast<double>(u0), 0.0, 0.0, static_cast<double>(v0), 0.0, 0.0};
+    double score = 0.0;
+    unsigned iterations = 0;
+    int state;
+    if (!(fabsf(u0) < INFINITY && fabsf(v0) < INFINITY))
+        state = kStateNoInput;
+    else if (!(nd.cx - nd.R >= 0 && nd.cy - nd.R >= 0 && nd.cx + nd.R <= a.w - 1 && nd.cy + nd.R <= a.h - 1))
+        state = kStateStrayed;
+    else
+        state = refine_node<Offset>(nd, a, p, score, iterations);
+    if (lane != 0) return;
+
+    const float nan = __uint_as_float(0x7FC00000u);
+    float out[6], out_score = 0.f;
+    if (state >= 0) {
+#pragma unroll
+        for (int i = 0; i < 6; ++i) out[i] = static_cast<float>(p[i]);
+        out_score = static_cast<float>(score);
+    } else {
+#pragma unroll
+        for (int i = 0; i < 6; ++i) out[i] = state == kStateNoInput ? nan : 0.f;
+        if (state != kStateNoInput) {
+            out[0] = u0;
+            out[3] = v0;
+        }
+    }
+    a.u[at] = out[0];
+    a.v[at] = out[3];
+    if (a.ux) {
+        a.ux[at] = out[1];
+        a.uy[at] = out[2];
+        a.vx[at] = out[4];
+        a.vy[at] = out[5];
+    }
+    if (a.score) a.score[at] = out_score;
+    if (a.state) a.state[at] = static_cast<float>(state);
+    if (a.record) {
+        unsigned long long* rec = a.record + kSubsetRecordWords * static_cast<size_t>(blockIdx.z);
+        const unsigned counts[kSubsetCounts] = {1u, state >= 1, state == 0, state == kStateStrayed, state == kStateFlat,
+                                                state == kStateNoInput, iterations};
+#pragma unroll
+        for (int k = 0; k < kSubsetCounts; ++k)
+            if (counts[k]) atomicAdd(rec + k, static_cast<unsigned long long>(counts[k]));
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int flow2d_subset_refine_2d(flow2d_context* ctx, const float* frame_0, const float* frame_1, size_t width, size_t height,
+                            size_t pitch_bytes, const float* node_u0, const float* node_v0, size_t nw, size_t nh,
+                            size_t node_pitch_bytes, int grid_radius, int spacing, int subset_radius, int max_iterations, float epsilon,
+                            float max_shift, float max_gradient, float* out_u, float* out_v, float* out_ux, float* out_uy,
+                            float* out_vx, float* out_vy, float* out_score, float* out_state, flow2d_subset_record* record)
+{
+    if (ctx == nullptr) return FLOW2D_ERR_INVALID_ARGUMENT;
+    // (every check that needs no context field comes first: they hold without a device)
+    if (!flow2d::plane_args_ok(frame_0, width, height, pitch_bytes) || !flow2d::plane_args_ok(frame_1, width, height, pitch_bytes))
+        return FLOW2D_ERR_INVALID_ARGUMENT;
+    if (grid_radius < 1 || grid_radius > FLOW2D_CORRELATION_MAX_RADIUS || spacing < 1 || spacing > FLOW2D_CORRELATION_MAX_SPACING ||
+        subset_radius < 1 || subset_radius > FLOW2D_SUBSET_MAX_RADIUS || max_iterations < 1 || max_iterations > FLOW2D_SUBSET_MAX_ITERATIONS)
+        return FLOW2D_ERR_INVALID_ARGUMENT;
+    if (!(std::isfinite(epsilon) && epsilon >= 0.f) || !(std::isfinite(max_shift) && max_shift > 0.f) ||
+        !(std::isfinite(max_gradient) && max_gradient > 0.f))
+        return FLOW2D_ERR_INVALID_ARGUMENT;
+    float* const planes[] = {out_u, out_v, out_ux, out_uy, out_vx, out_vy, out_score, out_state};
+    const bool gradients = out_ux != nullptr;
+    if ((out_uy != nullptr) != gradients || (out_vx != nullptr) != gradients || (out_vy != nullptr) != gradients)
+        return FLOW2D_ERR_INVALID_ARGUMENT;
+    if (!flow2d::plane_args_ok(node_u0, nw, nh, node_pitch_bytes) || !flow2d::plane_args_ok(node_v0, nw, nh, node_pitch_bytes) ||
+        !flow2d::plane_args_ok(out_u, nw, nh, node_pitch_bytes) || !flow2d::plane_args_ok(out_v, nw, nh, node_pitch_bytes))
+        return FLOW2D_ERR_INVALID_ARGUMENT;
+    for (int k = 2; k < 8; ++k)
+        if (planes[k] && !flow2d::plane_args_ok(planes[k], nw, nh, node_pitch_bytes)) return FLOW2D_ERR_INVALID_ARGUMENT;
+    // the grid lies inside the frame, as flow2d_correlation_grid lays it
+    const size_t window = static_cast<size_t>(2 * grid_radius + 1);
+    if (width < window || height < window || nw - 1 > (width - window) / spacing || nh - 1 > (height - window) / spacing)
+        return FLOW2D_ERR_INVALID_ARGUMENT;
+    if ((reinterpret_cast<uintptr_t>(record) % alignof(flow2d_subset_record)) != 0) return FLOW2D_ERR_INVALID_ARGUMENT;
+    if (nw * nh >= (size_t(1) << 31)) return FLOW2D_ERR_UNSUPPORTED;  // (the kernel numbers the nodes in 32 bits)
+    // the kernel reads frames and nodes while other waves write: no written byte range may meet a read one or another written one
+    auto aliased = [&](size_t frame_span, size_t node_span, size_t instances) {
+        const flow2d::ByteRange written[] = {{out_u, node_span},  {out_v, node_span},  {out_ux, node_span},
+                                             {out_uy, node_span}, {out_vx, node_span}, {out_vy, node_span},
+                                             {out_score, node_span}, {out_state, node_span},
+                                             {record, instances * sizeof(flow2d_subset_record)}};
+        const flow2d::ByteRange read[] = {{frame_0, frame_span}, {frame_1, frame_span}, {node_u0, node_span}, {node_v0, node_span}};
+        return flow2d::any_overlap(written, read);
+    };
+    if (aliased(height * pitch_bytes, nh * node_pitch_bytes, 1)) return FLOW2D_ERR_INVALID_ARGUMENT;
+    FLOW2D_ENTER(ctx);
+    const size_t instances = ctx->batch_count;
+    if (aliased(flow2d::batch_span(ctx, height * pitch_bytes), flow2d::batch_span(ctx, nh * node_pitch_bytes), instances))
+        return FLOW2D_ERR_INVALID_ARGUMENT;
+    if (record) FLOW2D_HIP_TRY(hipMemsetAsync(record, 0, instances * sizeof(flow2d_subset_record), ctx->stream));
+    const unsigned side = static_cast<unsigned>(2 * subset_radius + 1);
+    const unsigned slice = (side * side + 1u) & ~1u;                       // at most 962 doubles
+    const unsigned wave_bytes = 4u * slice * sizeof(double);               // at most 30 784
+    const unsigned waves = std::min<unsigned>(kSubsetMaxWaves, kSubsetLdsBytes / wave_bytes);  // 4 up to R = 11, 3 at 12, 2 beyond
+    const SubsetArgs a = {frame_0, frame_1, node_u0, node_v0, out_u, out_v, out_ux, out_uy, out_vx, out_vy, out_score, out_state,
+                          reinterpret_cast<unsigned long long*>(record),
+                          static_cast<int>(width), static_cast<int>(height), static_cast<int>(pitch_bytes / 4),
+                          static_cast<int>(nw), static_cast<int>(nh), static_cast<int>(node_pitch_bytes / 4),
+                          grid_radius, spacing, subset_radius, max_iterations, slice,
+                          static_cast<double>(epsilon), static_cast<double>(max_shift), static_cast<double>(max_gradient)};
+    // (the largest offset a lane forms into a frame is below height * pitch_bytes; the node planes are addressed in 64 bits)
+    flow2d::launch_by_span(height * pitch_bytes, [&](auto offset) {
+        subset_refine_kernel<decltype(offset)><<<dim3(flow2d::div_up(nw * nh, waves), 1, flow2d::batch_z(ctx, 1)), dim3(64 * waves),
+                                                 waves * wave_bytes, ctx->stream>>>(a, flow2d::batch_arg(ctx, 1));
+    });
+    FLOW2D_CHECK_LAUNCH();
+    return FLOW2D_OK;
+}
+
+}  // extern "C"

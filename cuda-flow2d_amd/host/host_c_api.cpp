@@ -724,6 +724,114 @@ HOST_API int flow2d_host_correlate_multipass(flow2d_host_flow* h, const float* f
     return 0;
 }
 
+// ---- subset refinement of correlation nodes -----------------------------------------------------------------------------------
+namespace {
+OpticalFlow2D::SubsetOptions subset_options(int radius, int iterations, float epsilon, float max_shift, float max_gradient)
+{
+    OpticalFlow2D::SubsetOptions o;
+    o.radius = radius;
+    o.iterations = iterations;
+    o.epsilon = epsilon;
+    o.max_shift = max_shift;
+    o.max_gradient = max_gradient;
+    return o;
+}
+// eight device planes -- u, v, ux, uy, vx, vy, score, state -- each of which may be null, as may the array
+OpticalFlow2D::SubsetPlanes subset_planes(void* const* p)
+{
+    OpticalFlow2D::SubsetPlanes o;
+    if (p) o = {dp(p[0]), dp(p[1]), dp(p[2]), dp(p[3]), dp(p[4]), dp(p[5]), dp(p[6]), dp(p[7])};
+    return o;
+}
+}  // namespace
+
+// OpticalFlow2D::SubsetOptionsOk: 1 when the options are what RefineNodes* / CorrelateSubset* accept.  Needs no device.
+HOST_API int flow2d_host_subset_options_ok(int radius, int iterations, float epsilon, float max_shift, float max_gradient)
+{
+    return OpticalFlow2D::SubsetOptionsOk(subset_options(radius, iterations, epsilon, max_shift, max_gradient)) ? 1 : 0;
+}
+
+// OpticalFlow2D::RefineNodesDevice: device planes of the container's size; dev_out: eight planes (u, v, ux, uy, vx, vy, score, state),
+// each optional.  With a record (host) the call synchronises.  0 on success, 1 for a null or refused argument, 2 when the run failed.
+HOST_API int flow2d_host_refine_nodes_device(flow2d_host_flow* h, void* dev_frame_0, void* dev_frame_1, void* dev_node_u0,
+                                             void* dev_node_v0, int grid_radius, int spacing, int radius, int iterations, float epsilon,
+                                             float max_shift, float max_gradient, void* const* dev_out, flow2d_subset_record* record)
+{
+    const auto subset = subset_options(radius, iterations, epsilon, max_shift, max_gradient);
+    if (!h || !dev_frame_0 || !dev_frame_1 || !dev_node_u0 || !dev_node_v0 || !OpticalFlow2D::SubsetOptionsOk(subset)) return 1;
+    h->flow.timing_mode = 0;
+    return h->flow.RefineNodesDevice(dp(dev_frame_0), dp(dev_frame_1), dp(dev_node_u0), dp(dev_node_v0), grid_radius, spacing, subset,
+                                     subset_planes(dev_out), record)
+               ? 0
+               : 2;
+}
+
+// OpticalFlow2D::CorrelateSubsetDevice: the passes as for flow2d_host_correlate_multipass_device, then the refinement; dev_out as
+// above, reports (optional) one per pass, record (optional).  Synchronises.  0, 1 or 2 as above.
+HOST_API int flow2d_host_correlate_subset_device(flow2d_host_flow* h, void* dev_frame_0, void* dev_frame_1, float lo, float scale,
+                                                 const int* passes, int count, float min_score, float threshold, float epsilon,
+                                                 int min_neighbours, int radius, int iterations, float subset_epsilon, float max_shift,
+                                                 float max_gradient, void* dev_predictor_u, void* dev_predictor_v, void* const* dev_out,
+                                                 OpticalFlow2D::CorrelationPassReport* reports, flow2d_subset_record* record,
+                                                 void* dev_flow_u, void* dev_flow_v)
+{
+    const auto list = correlation_passes(passes, count);
+    const auto validation = validation_options(threshold, epsilon, min_neighbours, 1, 1);
+    const auto subset = subset_options(radius, iterations, subset_epsilon, max_shift, max_gradient);
+    if (!h || !dev_frame_0 || !dev_frame_1 || count < 0 || (dev_flow_u == nullptr) != (dev_flow_v == nullptr) ||
+        (dev_predictor_u == nullptr) != (dev_predictor_v == nullptr) ||
+        !OpticalFlow2D::CorrelationPassesOk(h->width, h->height, lo, scale, list.data(), list.size(), min_score, validation) ||
+        !OpticalFlow2D::SubsetOptionsOk(subset))
+        return 1;
+    h->flow.timing_mode = 0;
+    return h->flow.CorrelateSubsetDevice(dp(dev_frame_0), dp(dev_frame_1), lo, scale, list.data(), list.size(), min_score, validation, subset,
+                                         dp(dev_predictor_u), dp(dev_predictor_v), subset_planes(dev_out), reports, record,
+                                         dp(dev_flow_u), dp(dev_flow_v))
+               ? 0
+               : 2;
+}
+
+// OpticalFlow2D::CorrelateSubset on tight host images: nodes -- eight arrays (u, v, ux, uy, vx, vy, score, state; u and v needed, the
+// gradients all or none) -- get the last pass's nw * nh floats each; the rest as for flow2d_host_correlate_multipass.
+HOST_API int flow2d_host_correlate_subset(flow2d_host_flow* h, const float* frame_0, const float* frame_1, const int* passes, int count,
+                                          float min_score, float threshold, float epsilon, int min_neighbours, int radius, int iterations,
+                                          float subset_epsilon, float max_shift, float max_gradient, const float* predictor_u,
+                                          const float* predictor_v, float* const* nodes, OpticalFlow2D::CorrelationPassReport* reports,
+                                          flow2d_subset_record* record, float* flow_u, float* flow_v, float* lo_scale)
+{
+    const auto list = correlation_passes(passes, count);
+    const auto validation = validation_options(threshold, epsilon, min_neighbours, 1, 1);
+    const auto subset = subset_options(radius, iterations, subset_epsilon, max_shift, max_gradient);
+    if (!h || !frame_0 || !frame_1 || !nodes || !nodes[0] || !nodes[1] || count < 0 || (flow_u == nullptr) != (flow_v == nullptr) ||
+        (predictor_u == nullptr) != (predictor_v == nullptr))
+        return 1;
+    HostImages im(h);
+    Data2D *f0 = im.In(frame_0), *f1 = im.In(frame_1);
+    Data2D *pu = predictor_u ? im.In(predictor_u) : nullptr, *pv = predictor_v ? im.In(predictor_v) : nullptr;
+    Data2D *fu = im.Out(flow_u, im.AfterSuccess), *fv = im.Out(flow_v, im.AfterSuccess);
+    float lo = 0.f, scale = 1.f;
+    OpticalFlow2D::CorrelationRange(*f0, *f1, lo, scale);
+    if (!OpticalFlow2D::CorrelationPassesOk(h->width, h->height, lo, scale, list.data(), list.size(), min_score, validation) ||
+        !OpticalFlow2D::SubsetOptionsOk(subset))
+        return 1;
+    size_t nw = 0, nh = 0;
+    flow2d_correlation_grid(h->width, h->height, list.back().radius, list.back().spacing, &nw, &nh);
+    std::vector<Data2D> images;
+    for (int k = 0; k < 8; ++k) images.emplace_back(nw, nh);
+    Data2D* wanted[8];
+    for (int k = 0; k < 8; ++k) wanted[k] = nodes[k] ? &images[k] : nullptr;
+    h->flow.CorrelateSubset(*f0, *f1, list.data(), list.size(), min_score, validation, subset, wanted, reports, record, fu, fv, pu, pv);
+    const int rc = im.Finish(h->flow);
+    if (rc) return rc;
+    for (int k = 0; k < 8; ++k)
+        if (nodes[k]) std::memcpy(nodes[k], images[k].DataPtr(), nw * nh * sizeof(float));
+    if (lo_scale) {
+        lo_scale[0] = lo;
+        lo_scale[1] = scale;
+    }
+    return 0;
+}
+
 // ---- the pyramid started from a prior flow ------------------------------------------------------------------------------------
 // OpticalFlow2D::PriorReport as the facade hands it out
 struct flow2d_host_prior_report {

@@ -74,6 +74,15 @@
 // those of --correlation, from the last pass (whose outliers --validate-flag-only leaves as NaN instead of replacing them), and
 // one line "CorrelationPasses: {json}" -- the options and, per pass, the grid and both records -- is printed.  It excludes
 // --correlation and everything that runs or seeds the variational flow.  Without it nothing changes.
+// --subset-refine R (a subset radius of 1 .. 15) [--subset-iterations K, 1 .. 64, default 20] [--subset-epsilon E, >= 0, default
+// 1e-3] [--subset-max-shift M, > 0, default 2] [--subset-max-gradient G, > 0, default 0.5], valid only together with --correlation or
+// --correlation-passes, refines the nodes of the (last) pass by subsets (OpticalFlow2D::CorrelateSubset: the pass is validated with
+// replacement so that every node has a start, then flow2d_subset_refine_2d -- the affine Gauss-Newton iteration of digital image
+// correlation on the unquantised frames): node-u, node-v and the forward files then hold the refined field, node-score the
+// subsets' scores, and node-ux, node-uy, node-vx, node-vy (the displacement gradients) and node-state are written beside them.
+// One line "Subset: {json}" -- the options, the grid, "lo", "scale" and the record's "nodes", "converged", "unconverged", "strayed",
+// "flat", "no_input", "iterations_run" -- is printed in place of the "Correlation:" / "CorrelationPasses:" line.  Without the option
+// nothing changes.
 // --initial-flow FILE.flo | --correlation-prior R  [--prior-reach P, pixels, finite and > 0, default 2] [--prior-level L, >= 0]
 // start the variational pyramid from a prior flow instead of from zero at its coarsest level (OpticalFlow2D::ComputeFlowFromPrior /
 // ComputeFlowCorrelationSeeded): the prior is a Middlebury file of the frames' size, or the window correlation of the pair with
@@ -148,6 +157,8 @@ int main(int argc, char** argv)
     int correlation_radius = 0, correlation_range = 8, correlation_spacing = 8;
     float correlation_min_score = -1.f;
     std::vector<OpticalFlow2D::CorrelationPass> correlation_passes;  // --correlation-passes R:D:S[,R:D:S...]
+    OpticalFlow2D::SubsetOptions subset;  // --subset-refine R and the --subset-* options
+    bool subset_refine = false, subset_option = false;
     OpticalFlow2D::ValidationOptions validation;                     // --validate-threshold / -epsilon / -min-neighbours / -flag-only
     bool validate_option = false;
     std::string initial_flow_file;  // --initial-flow FILE.flo
@@ -381,6 +392,32 @@ int main(int argc, char** argv)
             }
             ++i;
         }
+        else if (!std::strcmp(argv[i], "--subset-refine") || !std::strcmp(argv[i], "--subset-iterations")) {
+            const bool radius = !std::strcmp(argv[i], "--subset-refine");
+            const int limit = radius ? FLOW2D_SUBSET_MAX_RADIUS : FLOW2D_SUBSET_MAX_ITERATIONS;
+            char* end = nullptr;
+            const long n = (i + 1 < argc) ? std::strtol(argv[i + 1], &end, 10) : 0;
+            if (i + 1 >= argc || end == argv[i + 1] || *end != '\0' || n < 1 || n > limit) {
+                std::printf("%s takes an integer of 1 .. %d.\n", argv[i], limit);
+                return 5;
+            }
+            (radius ? subset.radius : subset.iterations) = static_cast<int>(n);
+            (radius ? subset_refine : subset_option) = true;
+            ++i;
+        }
+        else if (!std::strcmp(argv[i], "--subset-epsilon") || !std::strcmp(argv[i], "--subset-max-shift") ||
+                 !std::strcmp(argv[i], "--subset-max-gradient")) {
+            const bool epsilon = !std::strcmp(argv[i], "--subset-epsilon");
+            char* end = nullptr;
+            const float value = (i + 1 < argc) ? std::strtof(argv[i + 1], &end) : 0.f;
+            if (i + 1 >= argc || end == argv[i + 1] || *end != '\0' || !std::isfinite(value) || !(epsilon ? value >= 0.f : value > 0.f)) {
+                std::printf("%s takes a finite number %s 0.\n", argv[i], epsilon ? ">=" : ">");
+                return 5;
+            }
+            (epsilon ? subset.epsilon : !std::strcmp(argv[i], "--subset-max-shift") ? subset.max_shift : subset.max_gradient) = value;
+            subset_option = true;
+            ++i;
+        }
         else if (!std::strcmp(argv[i], "--validate-threshold") || !std::strcmp(argv[i], "--validate-epsilon")) {
             char* end = nullptr;
             const float value = (i + 1 < argc) ? std::strtof(argv[i + 1], &end) : 0.f;
@@ -442,6 +479,11 @@ int main(int argc, char** argv)
                       deformation || refine_radius || prior_radius != 0 || !previous_flow_file.empty() || prior_option)) {
         std::printf("--correlation-passes replaces the variational flow: it does not combine with --correlation or with the options that "
                     "run or seed the flow (--initial-flow FILE.flo is its first pass's predictor).\n");
+        return 5;
+    }
+
+    if ((subset_refine || subset_option) && !(subset_refine && (multipass || method == Methods::Correlation))) {
+        std::printf("--subset-refine R refines the nodes of --correlation or --correlation-passes, and the --subset-* options belong to it.\n");
         return 5;
     }
 
@@ -622,7 +664,41 @@ int main(int argc, char** argv)
             occlusion_1 = Data2D(width, height);
         }
         Data2D node_u, node_v, node_score;
-        if (multipass) {
+        if (subset_refine) {
+            std::vector<OpticalFlow2D::CorrelationPass> schedule = correlation_passes;
+            if (!multipass) schedule.push_back({correlation_radius, correlation_range, correlation_spacing});
+            const OpticalFlow2D::CorrelationPass& fine = schedule.back();
+            float lo = 0.f, scale = 1.f;
+            OpticalFlow2D::CorrelationRange(frame_0, frame_1, lo, scale);
+            size_t nw = 0, nh = 0;
+            if (!OpticalFlow2D::CorrelationPassesOk(width, height, lo, scale, schedule.data(), schedule.size(), correlation_min_score,
+                                                    validation) ||
+                flow2d_correlation_grid(width, height, fine.radius, fine.spacing, &nw, &nh) != FLOW2D_OK) {
+                optical_flow.Destroy();
+                DestroyDeviceContext();
+                return 4;
+            }
+            const char* names[8] = {"node-u", "node-v", "node-ux", "node-uy", "node-vx", "node-vy", "node-score", "node-state"};
+            std::vector<Data2D> images;
+            for (int k = 0; k < 8; ++k) images.emplace_back(nw, nh);
+            Data2D* nodes[8];
+            for (int k = 0; k < 8; ++k) nodes[k] = &images[k];
+            flow2d_subset_record record = {};
+            const bool predicted = multipass && !initial_flow_file.empty();
+            optical_flow.CorrelateSubset(frame_0, frame_1, schedule.data(), schedule.size(), correlation_min_score, validation, subset, nodes,
+                                         nullptr, &record, &flow_u, &flow_v, predicted ? &prior_u : nullptr, predicted ? &prior_v : nullptr);
+            if (optical_flow.LastRunSucceeded()) {
+                const std::string size = "-" + std::to_string(nw) + "-" + std::to_string(nh) + ".raw";
+                for (int k = 0; k < 8; ++k) images[k].WriteRAWToFileF32((output_path + counter + names[k] + size).c_str());
+                std::printf("Subset: {\"radius\": %d, \"iterations\": %d, \"epsilon\": %.9g, \"max_shift\": %.9g, \"max_gradient\": %.9g, "
+                            "\"passes\": %zu, \"grid_radius\": %d, \"spacing\": %d, \"nw\": %zu, \"nh\": %zu, \"lo\": %.9g, \"scale\": %.9g, "
+                            "\"nodes\": %llu, \"converged\": %llu, \"unconverged\": %llu, \"strayed\": %llu, \"flat\": %llu, "
+                            "\"no_input\": %llu, \"iterations_run\": %llu}\n",
+                            subset.radius, subset.iterations, subset.epsilon, subset.max_shift, subset.max_gradient, schedule.size(),
+                            fine.radius, fine.spacing, nw, nh, lo, scale, record.nodes, record.converged, record.unconverged,
+                            record.strayed, record.flat, record.no_input, record.iterations);
+            }
+        } else if (multipass) {
             const OpticalFlow2D::CorrelationPass& fine = correlation_passes.back();
             float lo = 0.f, scale = 1.f;
             OpticalFlow2D::CorrelationRange(frame_0, frame_1, lo, scale);

@@ -328,6 +328,42 @@ public:
                             CorrelationPassReport* reports_out, Data2D* flow_u = nullptr, Data2D* flow_v = nullptr,
                             Data2D* predictor_u = nullptr, Data2D* predictor_v = nullptr);
 
+    // Subset refinement of correlation nodes (flow2d_subset_refine_2d: the inverse-compositional Gauss-Newton iteration with an
+    // affine shape function, on the fp32 frames): the second half of a digital image correlation.  All planes are planes of the
+    // CONTAINER's size and pitch whose first nw x nh floats hold a node field.
+    struct SubsetOptions {
+        int radius = 7, iterations = 20;
+        float epsilon = 1e-3f, max_shift = 2.f, max_gradient = 0.5f;
+    };
+    struct SubsetPlanes {
+        DevicePtr u = 0, v = 0;                    // both or neither: without them planes of the object's own are written
+        DevicePtr ux = 0, uy = 0, vx = 0, vy = 0;  // the four gradients: all or none
+        DevicePtr score = 0, state = 0;            // each optional
+    };
+    // prints what is wrong; needs no device
+    static bool SubsetOptionsOk(const SubsetOptions& subset);
+    // The nodes (dev_node_u0, dev_node_v0) of the grid (grid_radius, spacing) refined into `out`.  record_out (host, optional): the
+    // counts, read back -- the call then synchronises, otherwise it only queues.  Its planes and record are allocated at the first
+    // use and kept.  Not for lock-step groups.
+    bool RefineNodesDevice(DevicePtr dev_frame_0, DevicePtr dev_frame_1, DevicePtr dev_node_u0, DevicePtr dev_node_v0, int grid_radius,
+                           int spacing, const SubsetOptions& subset, const SubsetPlanes& out, flow2d_subset_record* record_out = nullptr);
+    // The whole chain: the passes of CorrelateMultiPassDevice (one pass without a predictor is CorrelateDevice's search) with the
+    // last pass validated in REPLACE mode whatever `validation` says of it, so that every node has a start; then the refinement on
+    // the last pass's grid into `out`; dev_flow_u / dev_flow_v (optional, both or neither) get the refined (u, v) on the frame's
+    // grid (flow2d_expand_nodes_2d).  reports_out (optional, one per pass) and record_out (optional) as there and above.  The call
+    // synchronises once, at the end.  Not for lock-step groups.
+    bool CorrelateSubsetDevice(DevicePtr dev_frame_0, DevicePtr dev_frame_1, float lo, float scale, const CorrelationPass* passes,
+                               size_t count, float min_score, const ValidationOptions& validation, const SubsetOptions& subset,
+                               DevicePtr dev_predictor_u, DevicePtr dev_predictor_v, const SubsetPlanes& out,
+                               CorrelationPassReport* reports_out, flow2d_subset_record* record_out, DevicePtr dev_flow_u = 0,
+                               DevicePtr dev_flow_v = 0);
+    // The host-image form (the CLI's --subset-refine): lo and scale from CorrelationRange; nodes[8] -- u, v, ux, uy, vx, vy, score,
+    // state; u and v are needed, the gradients come all or none -- are images of the LAST pass's grid.
+    void CorrelateSubset(Data2D& frame_0, Data2D& frame_1, const CorrelationPass* passes, size_t count, float min_score,
+                         const ValidationOptions& validation, const SubsetOptions& subset, Data2D* const* nodes,
+                         CorrelationPassReport* reports_out, flow2d_subset_record* record_out, Data2D* flow_u = nullptr,
+                         Data2D* flow_v = nullptr, Data2D* predictor_u = nullptr, Data2D* predictor_v = nullptr);
+
     // The pyramid started from a prior flow instead of from zero at the coarsest level (no reference counterpart; Brox & Malik's
     // large-displacement flow and the predictor-corrector passes of PIV start the variational solver from matches in the same
     // way).  dev_prior_u / dev_prior_v: a flow in full-resolution pixels in planes of the container's size, only read; a pixel
@@ -633,6 +669,18 @@ private:
     // CorrelateMultiPass*: a pass's raw nodes (u, v), its validated nodes (u, v), the predictor (u, v); the passes' records
     OwnedPlanes multipass_planes_{owned_, 6};
     DeviceScratch multipass_scratch_{owned_};
+    // CorrelateMultiPassDevice, whose synchronisation CorrelateSubsetDevice leaves out (it goes on on the same stream)
+    bool QueueCorrelationPasses(DevicePtr dev_frame_0, DevicePtr dev_frame_1, float lo, float scale, const CorrelationPass* passes,
+                                size_t count, float min_score, const ValidationOptions& validation, DevicePtr dev_predictor_u,
+                                DevicePtr dev_predictor_v, DevicePtr dev_node_u, DevicePtr dev_node_v, DevicePtr dev_node_score,
+                                CorrelationPassReport* reports_out, DevicePtr dev_flow_u, DevicePtr dev_flow_v, bool synchronise);
+    // RefineNodes* / CorrelateSubset*: the chain's nodes (u, v), the refined ones where the caller gave none (u, v); the record
+    OwnedPlanes subset_planes_{owned_, 4};
+    DeviceScratch subset_scratch_{owned_};
+    // RefineNodesDevice without its synchronisation; *refined gets the planes (u, v) that were written
+    bool QueueRefineNodes(DevicePtr dev_frame_0, DevicePtr dev_frame_1, DevicePtr dev_node_u0, DevicePtr dev_node_v0, int grid_radius,
+                          int spacing, const SubsetOptions& subset, const SubsetPlanes& out, flow2d_subset_record* record_out,
+                          DevicePtr* refined);
     // ComputeFlowFromPrior*: inside such a run the prior's planes and the start level (RunPyramid starts there, from them); the
     // device count of the prior's non-finite pixels; the expanded field of ComputeFlowCorrelationSeeded* (u, v; first use)
     DevicePtr prior_u_ = 0, prior_v_ = 0;

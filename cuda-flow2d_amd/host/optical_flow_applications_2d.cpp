@@ -654,6 +654,17 @@ bool OpticalFlow2D::CorrelateMultiPassDevice(DevicePtr dev_frame_0, DevicePtr de
                                              DevicePtr dev_node_u, DevicePtr dev_node_v, DevicePtr dev_node_score,
                                              CorrelationPassReport* reports_out, DevicePtr dev_flow_u, DevicePtr dev_flow_v)
 {
+    return QueueCorrelationPasses(dev_frame_0, dev_frame_1, lo, scale, passes, count, min_score, validation, dev_predictor_u,
+                                  dev_predictor_v, dev_node_u, dev_node_v, dev_node_score, reports_out, dev_flow_u, dev_flow_v, true);
+}
+
+bool OpticalFlow2D::QueueCorrelationPasses(DevicePtr dev_frame_0, DevicePtr dev_frame_1, float lo, float scale,
+                                           const CorrelationPass* passes, size_t count, float min_score,
+                                           const ValidationOptions& validation, DevicePtr dev_predictor_u, DevicePtr dev_predictor_v,
+                                           DevicePtr dev_node_u, DevicePtr dev_node_v, DevicePtr dev_node_score,
+                                           CorrelationPassReport* reports_out, DevicePtr dev_flow_u, DevicePtr dev_flow_v,
+                                           bool synchronise)
+{
     const size_t W = dev_container_size_.width, H = dev_container_size_.height, pitch = dev_container_size_.pitch;
     if (!CorrelationPassesOk(W, H, lo, scale, passes, count, min_score, validation)) return false;
     if (!IsInitialized() || !dev_frame_0 || !dev_frame_1 || (dev_flow_u == 0) != (dev_flow_v == 0) ||
@@ -719,7 +730,139 @@ bool OpticalFlow2D::CorrelateMultiPassDevice(DevicePtr dev_frame_0, DevicePtr de
                  (!validated || ReadRecord(&report.validation, checked, sizeof(report.validation)));
         }
     }
+    if (!synchronise) return ok;
     return !CheckFlow2DError(flow2d_synchronize(context_), "flow2d_synchronize") && ok;
+}
+
+bool OpticalFlow2D::SubsetOptionsOk(const SubsetOptions& subset)
+{
+    if (subset.radius >= 1 && subset.radius <= FLOW2D_SUBSET_MAX_RADIUS && subset.iterations >= 1 &&
+        subset.iterations <= FLOW2D_SUBSET_MAX_ITERATIONS && std::isfinite(subset.epsilon) && subset.epsilon >= 0.f &&
+        std::isfinite(subset.max_shift) && subset.max_shift > 0.f && std::isfinite(subset.max_gradient) && subset.max_gradient > 0.f)
+        return true;
+    std::printf("Error: subset refinement takes a radius of 1 .. %d (%d), 1 .. %d iterations (%d), a finite epsilon >= 0 (%g), a finite "
+                "largest shift > 0 (%g) and a finite largest gradient > 0 (%g).\n",
+                FLOW2D_SUBSET_MAX_RADIUS, subset.radius, FLOW2D_SUBSET_MAX_ITERATIONS, subset.iterations, subset.epsilon, subset.max_shift,
+                subset.max_gradient);
+    return false;
+}
+
+bool OpticalFlow2D::QueueRefineNodes(DevicePtr dev_frame_0, DevicePtr dev_frame_1, DevicePtr dev_node_u0, DevicePtr dev_node_v0,
+                                     int grid_radius, int spacing, const SubsetOptions& subset, const SubsetPlanes& out,
+                                     flow2d_subset_record* record_out, DevicePtr* refined)
+{
+    const size_t W = dev_container_size_.width, H = dev_container_size_.height, pitch = dev_container_size_.pitch;
+    if (!SubsetOptionsOk(subset)) return false;
+    size_t nw = 0, nh = 0;
+    if (flow2d_correlation_grid(W, H, grid_radius, spacing, &nw, &nh) != FLOW2D_OK) {
+        std::printf("Error: a %zu x %zu frame holds no node grid of radius %d and spacing %d.\n", W, H, grid_radius, spacing);
+        return false;
+    }
+    const bool gradients = out.ux != 0;
+    if (!IsInitialized() || !dev_frame_0 || !dev_frame_1 || !dev_node_u0 || !dev_node_v0 || (out.u == 0) != (out.v == 0) ||
+        (out.uy != 0) != gradients || (out.vx != 0) != gradients || (out.vy != 0) != gradients)
+        return false;
+    if (RefuseGroup("subset refinement")) return false;
+    if (!EnsurePlanes(subset_planes_, 4)) return false;
+    const DevicePtr u = out.u ? out.u : subset_planes_[2], v = out.v ? out.v : subset_planes_[3];
+    if (record_out && !subset_scratch_.Ensure(context_, sizeof(flow2d_subset_record))) return false;
+    flow2d_subset_record* record = record_out ? subset_scratch_.At<flow2d_subset_record>() : nullptr;
+    auto plane = [](DevicePtr p) { return p ? AsPlane(p) : nullptr; };
+    // (the node planes are containers: the frames' pitch; the entry refuses planes that meet)
+    bool ok = !CheckFlow2DError(flow2d_subset_refine_2d(context_, AsPlane(dev_frame_0), AsPlane(dev_frame_1), W, H, pitch, AsPlane(dev_node_u0),
+                                                        AsPlane(dev_node_v0), nw, nh, pitch, grid_radius, spacing, subset.radius,
+                                                        subset.iterations, subset.epsilon, subset.max_shift, subset.max_gradient, AsPlane(u),
+                                                        AsPlane(v), plane(out.ux), plane(out.uy), plane(out.vx), plane(out.vy),
+                                                        plane(out.score), plane(out.state), record),
+                                "flow2d_subset_refine_2d");
+    ok = ok && (!record_out || ReadRecord(record_out, record, sizeof(*record_out)));
+    if (refined) {
+        refined[0] = u;
+        refined[1] = v;
+    }
+    return ok;
+}
+
+bool OpticalFlow2D::RefineNodesDevice(DevicePtr dev_frame_0, DevicePtr dev_frame_1, DevicePtr dev_node_u0, DevicePtr dev_node_v0,
+                                      int grid_radius, int spacing, const SubsetOptions& subset, const SubsetPlanes& out,
+                                      flow2d_subset_record* record_out)
+{
+    const bool ok = QueueRefineNodes(dev_frame_0, dev_frame_1, dev_node_u0, dev_node_v0, grid_radius, spacing, subset, out, record_out, nullptr);
+    if (!ok || !record_out) return ok;
+    return !CheckFlow2DError(flow2d_synchronize(context_), "flow2d_synchronize");
+}
+
+bool OpticalFlow2D::CorrelateSubsetDevice(DevicePtr dev_frame_0, DevicePtr dev_frame_1, float lo, float scale, const CorrelationPass* passes,
+                                          size_t count, float min_score, const ValidationOptions& validation, const SubsetOptions& subset,
+                                          DevicePtr dev_predictor_u, DevicePtr dev_predictor_v, const SubsetPlanes& out,
+                                          CorrelationPassReport* reports_out, flow2d_subset_record* record_out, DevicePtr dev_flow_u,
+                                          DevicePtr dev_flow_v)
+{
+    const size_t W = dev_container_size_.width, H = dev_container_size_.height, pitch = dev_container_size_.pitch;
+    if (!CorrelationPassesOk(W, H, lo, scale, passes, count, min_score, validation) || !SubsetOptionsOk(subset)) return false;
+    const bool gradients = out.ux != 0;
+    if (!IsInitialized() || (dev_flow_u == 0) != (dev_flow_v == 0) || (out.u == 0) != (out.v == 0) || (out.uy != 0) != gradients ||
+        (out.vx != 0) != gradients || (out.vy != 0) != gradients)
+        return false;
+    if (RefuseGroup("subset refinement")) return false;
+    if (!EnsurePlanes(subset_planes_, 4)) return false;
+    ValidationOptions every_node = validation;  // the last pass fills what it did not find: every node gets a start
+    every_node.validate_last = true;
+    every_node.replace = true;
+    const CorrelationPass& fine = passes[count - 1];
+    DevicePtr refined[2] = {0, 0};
+    bool ok = QueueCorrelationPasses(dev_frame_0, dev_frame_1, lo, scale, passes, count, min_score, every_node, dev_predictor_u,
+                                     dev_predictor_v, subset_planes_[0], subset_planes_[1], 0, reports_out, 0, 0, false) &&
+              QueueRefineNodes(dev_frame_0, dev_frame_1, subset_planes_[0], subset_planes_[1], fine.radius, fine.spacing, subset, out,
+                               record_out, refined);
+    if (ok && dev_flow_u) {
+        size_t nw = 0, nh = 0;
+        flow2d_correlation_grid(W, H, fine.radius, fine.spacing, &nw, &nh);
+        ok = !CheckFlow2DError(flow2d_expand_nodes_2d(context_, AsPlane(refined[0]), AsPlane(refined[1]), nw, nh, pitch, fine.radius,
+                                                      fine.spacing, AsPlane(dev_flow_u), AsPlane(dev_flow_v), W, H, pitch),
+                               "flow2d_expand_nodes_2d");
+    }
+    return !CheckFlow2DError(flow2d_synchronize(context_), "flow2d_synchronize") && ok;
+}
+
+void OpticalFlow2D::CorrelateSubset(Data2D& frame_0, Data2D& frame_1, const CorrelationPass* passes, size_t count, float min_score,
+                                    const ValidationOptions& validation, const SubsetOptions& subset, Data2D* const* nodes,
+                                    CorrelationPassReport* reports_out, flow2d_subset_record* record_out, Data2D* flow_u, Data2D* flow_v,
+                                    Data2D* predictor_u, Data2D* predictor_v)
+{
+    last_run_ok_ = false;
+    if (!IsInitialized() || !nodes || !nodes[0] || !nodes[1] || (flow_u == nullptr) != (flow_v == nullptr) ||
+        (predictor_u == nullptr) != (predictor_v == nullptr))
+        return;
+    const bool gradients = nodes[2] != nullptr;
+    if ((nodes[3] != nullptr) != gradients || (nodes[4] != nullptr) != gradients || (nodes[5] != nullptr) != gradients) return;
+    CallPlanes planes(context_, dev_container_size_, GetName(), "frame / flow");
+    planes.Add(&frame_0, CallPlanes::In).Add(&frame_1, CallPlanes::In).Add(flow_u, CallPlanes::Out).Add(flow_v, CallPlanes::Out);
+    // the node planes: containers with no image of their size behind them, downloaded below
+    for (int k = 0; k < 8; ++k) planes.Add(nullptr, CallPlanes::Out, nodes[k] != nullptr);
+    if (predictor_u) planes.Add(predictor_u, CallPlanes::In).Add(predictor_v, CallPlanes::In);
+    if (!planes.SizesMatch()) return;
+    float lo = 0.f, scale = 1.f;
+    CorrelationRange(frame_0, frame_1, lo, scale);
+    const size_t W = dev_container_size_.width, H = dev_container_size_.height;
+    if (!CorrelationPassesOk(W, H, lo, scale, passes, count, min_score, validation) || !SubsetOptionsOk(subset)) return;
+    size_t nw = 0, nh = 0;
+    flow2d_correlation_grid(W, H, passes[count - 1].radius, passes[count - 1].spacing, &nw, &nh);
+    for (int k = 0; k < 8; ++k)
+        if (nodes[k] && (nodes[k]->Width() != nw || nodes[k]->Height() != nh)) {
+            std::printf("Error: '%s': the node images are not %zu x %zu.\n", GetName(), nw, nh);
+            return;
+        }
+    HostCall call(context_, last_total_ms_, planes.Allocate());
+    const DevicePtr* d = planes.data();
+    const SubsetPlanes out = {d[4], d[5], d[6], d[7], d[8], d[9], d[10], d[11]};
+    bool ok = planes.Upload() &&
+              CorrelateSubsetDevice(d[0], d[1], lo, scale, passes, count, min_score, validation, subset, predictor_u ? d[12] : 0,
+                                    predictor_u ? d[13] : 0, out, reports_out, record_out, d[2], d[3]) &&
+              planes.Download();
+    for (int k = 0; ok && k < 8; ++k)
+        if (nodes[k]) ok = CopyData2DFromDevice(d[4 + k], *nodes[k], H, dev_container_size_.pitch);
+    last_run_ok_ = ok;
 }
 
 void OpticalFlow2D::CorrelateMultiPass(Data2D& frame_0, Data2D& frame_1, const CorrelationPass* passes, size_t count, float min_score,

@@ -33,6 +33,8 @@ Speckle scenes (make_speckle_scene(motion, width, height, seed), motion one of S
 (flow2d_correlate_2d): the affine scenes' machinery on a Speckle texture, a seeded sum of Gaussian blobs as sprayed on a specimen
 for digital image correlation -- fine, aperiodic detail in every window, which the long sinusoids of Texture do not have.  They
 are NOT in SCENES: the tables and tests that iterate over that tuple are about the variational flow.
+Speckle deformations (make_speckle_deformation(name, width, height, seed), name one of SPECKLE_DEFORMATIONS), for the subset
+refinement (flow2d_subset_refine_2d): the same texture under a rotation, a stretch and a shear, each with a translation.
 Pure numpy: no device, no library.
 """
 import numpy as np
@@ -105,6 +107,26 @@ def make_speckle_scene(motion, width=96, height=80, seed=0):
     if motion == "large_translation":
         return _affine_scene("speckle_large_translation", width, height, texture, np.eye(2), (11.25, -7.5))
     raise ValueError("unknown speckle motion %r (one of %s)" % (motion, ", ".join(SPECKLE_MOTIONS)))
+
+
+SPECKLE_DEFORMATIONS = ("rotation", "stretch", "shear")
+
+
+def make_speckle_deformation(name, width=96, height=80, seed=0):
+    """A speckle pattern whose windows deform (one of SPECKLE_DEFORMATIONS), for the subset refinement (flow2d_subset_refine_2d):
+    a rotation by 5 degrees, a stretch by 1.06 x 0.97 and a shear of 0.08, each about the centre and followed by the translation
+    (1.6, -0.7).  They are NOT in SPECKLE_MOTIONS: the tests that iterate over that tuple are about the rigid window."""
+    texture = Speckle(seed)
+    if name == "rotation":
+        phi = np.radians(5.0)
+        a = [[np.cos(phi), -np.sin(phi)], [np.sin(phi), np.cos(phi)]]
+    elif name == "stretch":
+        a = [[1.06, 0.0], [0.0, 0.97]]
+    elif name == "shear":
+        a = [[1.0, 0.08], [0.0, 1.0]]
+    else:
+        raise ValueError("unknown speckle deformation %r (one of %s)" % (name, ", ".join(SPECKLE_DEFORMATIONS)))
+    return _affine_scene("speckle_" + name, width, height, texture, a, (1.6, -0.7))
 
 
 class Scene:

@@ -45,7 +45,8 @@ extern "C" {
  * pyramid started from a prior flow) and flow2d_propagate_flow_2d (a flow carried along itself: the prior of a warm-started
  * sequence) and flow2d_fused_packed_launches (a test hook: which build of the strip kernel a launch took) and
  * flow2d_correlate_offset_2d / flow2d_validate_nodes_2d (multi-pass window correlation: the search around a predictor's
- * offset and the normalised median test between passes) were added under 1. */
+ * offset and the normalised median test between passes) and flow2d_subset_refine_2d (affine Gauss-Newton refinement of
+ * correlation nodes) were added under 1. */
 #define FLOW2D_ABI_VERSION 1
 
 typedef enum flow2d_status {
@@ -972,6 +973,101 @@ FLOW2D_API int flow2d_validate_nodes_2d(flow2d_context* ctx, const float* node_u
                                         size_t node_pitch_bytes, float threshold, float epsilon, int min_neighbours, int mode,
                                         float* out_u, float* out_v, float* out_flag /* may be NULL */,
                                         flow2d_validation_record* record /* device, may be NULL */);
+
+/* Subset refinement of a node field (digital image correlation): the inverse-compositional Gauss-Newton iteration with a
+ * first-order shape function (Baker & Matthews 2004; Pan, Li & Tong 2013) on the zero-mean normalised sum of squared differences.
+ * Every node of a field that flow2d_correlate_2d, flow2d_correlate_offset_2d or flow2d_validate_nodes_2d delivered is refined from
+ * its vector (u0, v0) to a displacement with its four gradients, p = (u, ux, uy, v, vx, vy): the point (cx + xi, cy + eta) of
+ * frame 0 lies at (cx + xi + u + ux*xi + uy*eta, cy + eta + v + vx*xi + vy*eta) in frame 1.  Added to ABI version 1 without
+ * changing any existing entry.
+ *
+ * The frames are used as they are, fp32, not quantised.  Everything below is IEEE double (a sample or an argument is converted
+ * first, which is exact); every operation is rounded on its own, no fused multiply-add; division and square root correctly
+ * rounded.  Every test is written as a positive comparison, so that a NaN fails it.
+ * Nodes.  r = grid_radius (1 .. FLOW2D_CORRELATION_MAX_RADIUS) and s = spacing (1 .. FLOW2D_CORRELATION_MAX_SPACING) say where
+ * the nodes are: node (i, j) of the nw x nh planes is centred on pixel (cx, cy) = (r + i*s, r + j*s), and the grid must lie inside
+ * the frame as flow2d_correlation_grid would lay it: (nw - 1)*s + 2r + 1 <= width, (nh - 1)*s + 2r + 1 <= height.
+ * R = subset_radius (1 .. FLOW2D_SUBSET_MAX_RADIUS) is the subset's, N = (2R + 1)^2.  Pixel k = 0 .. N - 1 of the subset has
+ * xi = k mod (2R + 1) - R and eta = k div (2R + 1) - R.  K = max_iterations (1 .. FLOW2D_SUBSET_MAX_ITERATIONS).
+ * A *sum over the subset* is a sum of N terms; the order in which they are added is the one thing this text leaves open.
+ * State of a node (out_state, a float plane): n >= 1 converged in iteration n; 0 not converged after K iterations; -1 *no input*;
+ * -2 *flat*; -3 *strayed*.  The first that applies, in the order of this text, ends the node.
+ * No input.  u0 or v0 is not finite.
+ * Frame-0 window.  *Strayed* unless cx - R >= 0, cy - R >= 0, cx + R <= width - 1 and cy + R <= height - 1 (possible when R > r).
+ * Frame-0 quantities, per pixel k at (x, y) = (cx + xi, cy + eta):
+ *   f = frame_0[y][x];   fx = (frame_0[y][min(x + 1, width - 1)] - frame_0[y][max(x - 1, 0)]) * 0.5;   fy likewise with rows
+ *   fm = (sum of f) / N;   fd = f - fm;   Df2 = sum of fd*fd;   *flat* when !(Df2 > 0);   Df = sqrt(Df2)
+ * Hessian.  J = (J0 .. J5) = (fx, fx*xi, fx*eta, fy, fy*xi, fy*eta), each a rounded product;  H[a][b] = sum of J[a]*J[b].
+ * Cholesky H = L L^T, column k = 0 .. 5 in turn; every inner sum starts from 0 and adds its terms from m = 0 up:
+ *   d = H[k][k] - (sum over m < k of L[k][m]*L[k][m]);   *flat* when !(d > 1e-10 * H[k][k]);   L[k][k] = sqrt(d)
+ *   for i = k + 1 .. 5:   L[i][k] = (H[i][k] - (sum over m < k of L[i][m]*L[k][m])) / L[k][k]
+ * Solve(b), the x with H x = b; inner sums from 0, terms from the lowest m up:
+ *   for i = 0 .. 5:        y[i] = (b[i] - (sum over m < i of L[i][m]*y[m])) / L[i][i]
+ *   for i = 5 down to 0:   x[i] = (y[i] - (sum over m = i + 1 .. 5 of L[m][i]*x[m])) / L[i][i]
+ * Start.  p = (u0, 0, 0, v0, 0, 0).
+ * Iteration n = 1 .. K (it *begins* here):
+ *   1. Positions.  X = (double)(cx + xi) + ((u + ux*xi) + uy*eta);   Y = (double)(cy + eta) + ((v + vx*xi) + vy*eta).
+ *      *Strayed* unless every pixel of the subset has X >= 0, X <= width - 1, Y >= 0 and Y <= height - 1.
+ *   2. Sampling.  g = the Catmull-Rom sample of frame 1 at (X, Y).  ix = floor(X), t = X - ix; the taps are columns ix - 1 ..
+ *      ix + 2, each clamped to [0, width - 1], with the weights
+ *        w0 = ((-0.5*t + 1)*t - 0.5)*t;   w1 = ((1.5*t - 2.5)*t)*t + 1;   w2 = ((-1.5*t + 2)*t + 0.5)*t;   w3 = ((0.5*t - 0.5)*t)*t
+ *      A row a0 .. a3 gives ((w0*a0 + w1*a1) + w2*a2) + w3*a3.  Rows iy - 1 .. iy + 2 (iy = floor(Y), clamped to [0, height - 1])
+ *      are combined in the same way with the weights of Y - iy.
+ *   3. Residual.  gm = (sum of g) / N;   gd = g - gm;   Dg2 = sum of gd*gd;   *flat* when !(Dg2 > 0);   Dg = sqrt(Dg2);
+ *      c = (sum of fd*gd) / (Df*Dg);   q = Df / Dg;   res = fd - q*gd;   b[a] = sum of J[a]*res;   x = Solve(b);
+ *      (du, dux, duy, dv, dvx, dvy) = (-x[0], .. , -x[5]).
+ *   4. Update, p <- W(p) o W(dp)^-1.   a = 1 + dux, b = duy, c' = dvx, d = 1 + dvy;   det = a*d - b*c';
+ *      *strayed* when !(|det| > 1e-12);   ia = d/det, ib = (-b)/det, ic = (-c')/det, id = a/det;
+ *      tx = -(ia*du + ib*dv);   ty = -(ic*du + id*dv);   p11 = 1 + ux, p12 = uy, p21 = vx, p22 = 1 + vy;
+ *      u <- (p11*tx + p12*ty) + u;   v <- (p21*tx + p22*ty) + v;
+ *      ux <- (p11*ia + p12*ic) - 1;   uy <- p11*ib + p12*id;   vx <- p21*ia + p22*ic;   vy <- (p21*ib + p22*id) - 1
+ *      (all six from the old p).
+ *   5. Stop.  *Strayed* unless |u - u0| <= max_shift, |v - v0| <= max_shift and |ux|, |uy|, |vx|, |vy| <= max_gradient
+ *      (the new p).  Converged, state n, when
+ *        sqrt(((((du*du + (R*dux)*(R*dux)) + (R*duy)*(R*duy)) + dv*dv) + (R*dvx)*(R*dvx)) + (R*dvy)*(R*dvy)) < epsilon
+ *      (epsilon = 0: never, all K iterations run and the state is 0).
+ * Outputs.  State >= 0: u, v, the gradients and the last c (out_score), each cast to float.  No input: u, v and the gradients NaN
+ * (0x7FC00000), score 0.  Flat and strayed: u0 and v0 copied bit for bit, the gradients 0, score 0.  The four gradient planes
+ * are given all or none; out_score and out_state may be NULL.  All node planes are nw x nh floats with node_pitch_bytes per row.
+ * Record.  record[b] (DEVICE memory, may be NULL), 64 bytes: nodes (nw * nh); converged; unconverged (state 0); strayed; flat;
+ * no_input; iterations -- iterations begun, over all nodes --; one reserved word, written as 0.  Integers, added by integer
+ * atomics after the entry has zeroed the record on the stream: alone, in a batch and in a replayed graph the same bytes.
+ * Row padding and the containers beyond width x height and nw x nh are neither read into a result nor written.  One launch on the
+ * context's stream (and a 64-byte memset per instance with a record); no allocation, no synchronisation (graph-capturable).
+ * Honours flow2d_context_set_batch: frames and node planes of instance b at b * stride floats from their pointers, record + b.
+ * FLOW2D_ERR_INVALID_ARGUMENT, and nothing written, for a null frame, node_u0, node_v0, out_u or out_v, a zero size, a bad pitch
+ * (the rule of flow2d_consistency_2d, for node_pitch_bytes against nw), a grid_radius, spacing, subset_radius or max_iterations
+ * outside its limits, a grid that does not lie inside the frame, an epsilon that is not finite and >= 0, a max_shift or
+ * max_gradient that is not finite and > 0, gradient planes given in part, a misaligned record (8), or a written range -- the
+ * outputs, the records, over every instance of a batch -- that overlaps a frame, an input node plane or another written range;
+ * FLOW2D_ERR_UNSUPPORTED for 2^31 nodes or more. */
+#define FLOW2D_SUBSET_MAX_RADIUS 15
+#define FLOW2D_SUBSET_MAX_ITERATIONS 64
+typedef struct flow2d_subset_record {
+    unsigned long long nodes;       /* nw * nh */
+    unsigned long long converged;   /* state >= 1 */
+    unsigned long long unconverged; /* state 0: K iterations without convergence, p delivered */
+    unsigned long long strayed;     /* state -3 */
+    unsigned long long flat;        /* state -2 */
+    unsigned long long no_input;    /* state -1 */
+    unsigned long long iterations;  /* iterations begun, over all nodes */
+    unsigned long long reserved;    /* 0 */
+} flow2d_subset_record;
+
+#define FLOW2D_SUBSET_RECORD_BYTES 64
+#ifdef __cplusplus
+static_assert(sizeof(flow2d_subset_record) == FLOW2D_SUBSET_RECORD_BYTES, "flow2d_subset_record layout");
+#else
+_Static_assert(sizeof(flow2d_subset_record) == FLOW2D_SUBSET_RECORD_BYTES, "flow2d_subset_record layout");
+#endif
+
+FLOW2D_API int flow2d_subset_refine_2d(flow2d_context* ctx, const float* frame_0, const float* frame_1, size_t width, size_t height,
+                                       size_t pitch_bytes, const float* node_u0, const float* node_v0, size_t nw, size_t nh,
+                                       size_t node_pitch_bytes, int grid_radius, int spacing, int subset_radius, int max_iterations,
+                                       float epsilon, float max_shift, float max_gradient, float* out_u, float* out_v,
+                                       float* out_ux /* the four gradient planes: all or none */, float* out_uy, float* out_vx,
+                                       float* out_vy, float* out_score /* may be NULL */, float* out_state /* may be NULL */,
+                                       flow2d_subset_record* record /* device, may be NULL */);
 
 /* The flow of the previous pyramid level resampled to this level's size (the bits of flow2d_resample_xy_pair into out_u / out_v)
  * and frame_1 warped by it (the bits of flow2d_registration_2d into `output`) in one launch: replaces the
