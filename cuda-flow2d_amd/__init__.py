@@ -284,6 +284,30 @@ SUBSET_RECORD_BYTES = 64  # FLOW2D_SUBSET_RECORD_BYTES, checked by a static_asse
 assert C.sizeof(SubsetRecord) == SUBSET_RECORD_BYTES
 SUBSET_MAX_RADIUS, SUBSET_MAX_ITERATIONS = 15, 64  # FLOW2D_SUBSET_MAX_*
 SUBSET_NO_INPUT, SUBSET_FLAT, SUBSET_STRAYED = -1, -2, -3  # the negative states of flow2d_subset_refine_2d
+SUBSET_STATE_PREDICTED = 65  # FLOW2D_SUBSET_STATE_PREDICTED: the state flow2d_predict_nodes_2d gives a node it predicted
+
+
+class PredictRecord(C.Structure):
+    """flow2d_predict_record of include/flow2d_c_abi.h: the four counts flow2d_predict_nodes_2d writes per instance."""
+    _fields_ = [("nodes", C.c_ulonglong), ("kept", C.c_ulonglong), ("predicted", C.c_ulonglong), ("empty", C.c_ulonglong),
+                ("reserved", C.c_ulonglong * 4)]
+
+    def summary(self):
+        return {name: getattr(self, name) for name, _ in self._fields_[:4]}
+
+
+PREDICT_RECORD_BYTES = 64  # FLOW2D_PREDICT_RECORD_BYTES, checked by a static_assert in the header
+assert C.sizeof(PredictRecord) == PREDICT_RECORD_BYTES
+SEQUENCE_MAX_FILL = 4  # OpticalFlow2D::kSequenceMaxFill
+
+
+class SequenceStepReport(C.Structure):
+    """OpticalFlow2D::SequenceStepReport: one step of correlate_subset_sequence -- the refinement's record and the records of the
+    prediction passes that ran before it (zero in step 1 and beyond `fill`)."""
+    _fields_ = [("subset", SubsetRecord), ("prediction", PredictRecord * SEQUENCE_MAX_FILL)]
+
+    def summary(self, fill=SEQUENCE_MAX_FILL):
+        return {"subset": self.subset.summary(), "prediction": [self.prediction[k].summary() for k in range(fill)]}
 
 
 class CorrelationPassReport(C.Structure):
@@ -513,6 +537,9 @@ def hip_lib():
             L.flow2d_validate_nodes_2d.argtypes = [vp, vp, vp, sz, sz, sz, f, f, i, i, vp, vp, vp, vp]
         if hasattr(L, "flow2d_subset_refine_2d"):  # (absent from libraries of earlier rounds loaded for an A/B)
             L.flow2d_subset_refine_2d.argtypes = [vp, vp, vp, sz, sz, sz, vp, vp, sz, sz, sz, i, i, i, i, f, f, f] + [vp] * 9
+        if hasattr(L, "flow2d_subset_refine_from_2d"):  # (absent from libraries of earlier rounds loaded for an A/B)
+            L.flow2d_subset_refine_from_2d.argtypes = [vp, vp, vp, sz, sz, sz] + [vp] * 6 + [sz, sz, sz, i, i, i, i, f, f, f] + [vp] * 9
+            L.flow2d_predict_nodes_2d.argtypes = [vp] + [vp] * 7 + [sz, sz, sz, i, i, i] + [vp] * 8
         if hasattr(L, "flow2d_prior_registration_2d"):  # (absent from libraries of earlier rounds loaded for an A/B)
             L.flow2d_prior_registration_2d.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp, sz, sz, sz, f, f, vp, vp]
         if hasattr(L, "flow2d_propagate_flow_2d"):  # (absent from libraries of earlier rounds loaded for an A/B)
@@ -1242,6 +1269,83 @@ class Context:
                 q.free()
                 self._planes.remove(q)
 
+    def subset_refine_from(self, f0, f1, w, h, node_u0, node_v0, start_gradients, nw, nh, grid_radius, spacing, subset_radius,
+                           max_iterations=20, epsilon=1e-3, max_shift=4.0, max_gradient=0.5, out_u=None, out_v=None, out_gradients=None,
+                           out_score=None, out_state=None, record=True, instances=1):
+        """Subset refinement started from a whole deformation (flow2d_subset_refine_from_2d): subset_refine with the start's four
+        gradients, start_gradients = (ux0, uy0, vx0, vy0) Planes like node_u0 -- the previous step of a sequence against one
+        reference frame, through predict_nodes --, or None: then every byte is subset_refine's.  A node whose start holds a value
+        that is not finite is SUBSET_NO_INPUT; flat and strayed nodes hand back their whole start.  Outputs, record and the
+        return value as for subset_refine."""
+        own_planes = out_u is None and out_v is None
+        if not own_planes and (out_u is None or out_v is None):
+            raise ValueError("subset_refine_from takes both output planes or neither")
+        own_record = record is True
+        if own_record and instances != 1:
+            raise ValueError("a lock-step batch takes the caller's records")
+        start = list(start_gradients) if start_gradients is not None else [None] * 4
+        if len(start) != 4:
+            raise ValueError("subset_refine_from takes the four start gradients (ux0, uy0, vx0, vy0) or None")
+        if own_planes:
+            held = [self.plane(node_u0.pitch // 4, nh) for _ in range(8)]
+        else:
+            held = [out_u, out_v] + list(out_gradients if out_gradients is not None else (None,) * 4) + [out_score, out_state]
+        rec = self.subset_records(instances) if own_record else (record or None)
+        try:
+            _check(hip_lib().flow2d_subset_refine_from_2d(self.handle, f0.ptr, f1.ptr, w, h, f0.pitch, node_u0.ptr, node_v0.ptr,
+                                                          *[q.ptr if q is not None else None for q in start], nw, nh, node_u0.pitch,
+                                                          int(grid_radius), int(spacing), int(subset_radius), int(max_iterations),
+                                                          float(epsilon), float(max_shift), float(max_gradient),
+                                                          *[q.ptr if q is not None else None for q in held],
+                                                          rec.ptr if rec is not None else None), "flow2d_subset_refine_from_2d")
+            got = [q.download(nw, nh) for q in held] if own_planes else held
+            gradients = tuple(got[2:6]) if got[2] is not None else None
+            return got[0], got[1], gradients, got[6], got[7], (self.read_subset_record(rec, 1)[0] if own_record else None)
+        finally:
+            for q in (held if own_planes else []) + ([rec] if own_record else []):
+                q.free()
+                self._planes.remove(q)
+
+    def predict_records(self, instances=1):
+        """A Plane for `instances` flow2d_predict_record records (device memory)."""
+        return self.plane(instances * PREDICT_RECORD_BYTES // 4, 1)
+
+    def read_predict_record(self, record, instances=1):
+        """The records of a predict_records Plane as PredictRecord structures (synchronises)."""
+        return self._read_records(record, instances, PredictRecord)
+
+    def predict_nodes(self, nodes, state, nw, nh, spacing, min_state=1, min_neighbours=1, out=None, out_state=None, record=True,
+                      instances=1):
+        """The start of a sequence's next step from a step's result (flow2d_predict_nodes_2d), out of place: nodes = (u, v, ux, uy,
+        vx, vy) Planes and their `state` Plane, as subset_refine / subset_refine_from wrote them.  A node with state >= min_state
+        and six finite values is kept; any other takes, per value, the median of what its usable neighbours -- min_neighbours of
+        the eight at least -- extrapolate to it (u and v along the neighbour's gradients, `spacing` pixels per node), with the
+        state SUBSET_STATE_PREDICTED, or NaN and SUBSET_NO_INPUT where too few are usable: a second pass fills further.
+        out = six Planes of the caller's (and optionally out_state), which stay on the device; without them the call allocates
+        all seven, downloads them and returns arrays.  record: True, a predict_records Plane, or False / None.
+        Returns ((u, v, ux, uy, vx, vy), state or None, PredictRecord or None)."""
+        if len(nodes) != 6:
+            raise ValueError("predict_nodes takes the six planes (u, v, ux, uy, vx, vy)")
+        own_planes = out is None
+        if not own_planes and len(out) != 6:
+            raise ValueError("predict_nodes takes six output planes or none")
+        own_record = record is True
+        if own_record and instances != 1:
+            raise ValueError("a lock-step batch takes the caller's records")
+        held = [self.plane(nodes[0].pitch // 4, nh) for _ in range(7)] if own_planes else list(out) + [out_state]
+        rec = self.predict_records(instances) if own_record else (record or None)
+        try:
+            _check(hip_lib().flow2d_predict_nodes_2d(self.handle, *[q.ptr for q in nodes], state.ptr, nw, nh, nodes[0].pitch, int(spacing),
+                                                     int(min_state), int(min_neighbours),
+                                                     *[q.ptr if q is not None else None for q in held],
+                                                     rec.ptr if rec is not None else None), "flow2d_predict_nodes_2d")
+            got = [q.download(nw, nh) for q in held] if own_planes else held
+            return tuple(got[:6]), got[6], (self.read_predict_record(rec, 1)[0] if own_record else None)
+        finally:
+            for q in (held if own_planes else []) + ([rec] if own_record else []):
+                q.free()
+                self._planes.remove(q)
+
     def resample_x(self, src, dst, out_w, out_h, in_w):
         _check(hip_lib().flow2d_resample_x(self.handle, src.ptr, dst.ptr, out_w, out_h, in_w, src.pitch),
                "flow2d_resample_x")
@@ -1527,6 +1631,14 @@ def host_lib():
             L.flow2d_host_correlate_subset_device.argtypes = [vp, vp, vp, f, f, ip, i, f, f, f, i, i, i, f, f, f, vp, vp, C.POINTER(vp), rp, sr,
                                                               vp, vp]
             L.flow2d_host_correlate_subset.argtypes = [vp, fp, fp, ip, i, f, f, f, i, i, i, f, f, f, fp, fp, C.POINTER(fp), rp, sr, fp, fp, fp]
+        if hasattr(L, "flow2d_host_correlate_subset_sequence_device"):
+            ip, rp, sr, st = C.POINTER(C.c_int), C.POINTER(CorrelationPassReport), C.POINTER(SubsetRecord), C.POINTER(SequenceStepReport)
+            pvp, pfp = C.POINTER(vp), C.POINTER(fp)
+            L.flow2d_host_sequence_options_ok.argtypes = [i, i, i, f]
+            L.flow2d_host_refine_nodes_from_device.argtypes = [vp, vp, vp, pvp, i, i, i, i, f, f, f, pvp, sr]
+            L.flow2d_host_correlate_subset_sequence_device.argtypes = [vp, pvp, i, f, f, ip, i, f, f, f, i, i, i, f, f, f, i, i, i, f, pvp, rp, st,
+                                                                       pvp]
+            L.flow2d_host_correlate_subset_sequence.argtypes = [vp, pfp, i, ip, i, f, f, f, i, i, i, f, f, f, i, i, i, f, pfp, rp, st, pfp, fp]
         if hasattr(L, "flow2d_host_correlate"):
             cr = C.POINTER(CorrelationRecord)
             L.flow2d_host_correlation_args_ok.argtypes = [sz, sz, f, f, i, i, i, f]
@@ -2138,6 +2250,94 @@ class OpticalFlow:
         if rc:
             raise Flow2DError(rc, "OpticalFlow2D::CorrelateSubsetDevice")
         return list(reports)[:n], rec
+
+    @staticmethod
+    def sequence_options_ok(fill=2, min_state=1, predict_neighbours=1, sequence_max_shift=4.0):
+        """OpticalFlow2D::SequenceOptionsOk: whether correlate_subset_sequence* accept the options.  Needs no device."""
+        return bool(host_lib().flow2d_host_sequence_options_ok(int(fill), int(min_state), int(predict_neighbours), float(sequence_max_shift)))
+
+    def refine_nodes_from_device(self, dev_frame_0, dev_frame_1, dev_start, grid_radius, spacing, radius, iterations=20, epsilon=1e-3,
+                                 max_shift=4.0, max_gradient=0.5, dev_out=None, record=True):
+        """OpticalFlow2D::RefineNodesFromDevice: refine_nodes_device started from a whole deformation (flow2d_subset_refine_from_2d):
+        dev_start is a dict of the six device planes u, v, ux, uy, vx, vy (by the names of SUBSET_PLANES), all needed.  Returns the
+        SubsetRecord (the call then synchronises) or, without record, None (it only queues)."""
+        names = self.SUBSET_PLANES[:6]
+        if set(dev_start) != set(names) or not all(dev_start[n] for n in names):
+            raise ValueError("refine_nodes_from_device takes the six start planes %s" % ", ".join(names))
+        rec = SubsetRecord()
+        rc = host_lib().flow2d_host_refine_nodes_from_device(self.handle, dev_frame_0, dev_frame_1, (C.c_void_p * 6)(*[dev_start[n] for n in names]),
+                                                             int(grid_radius), int(spacing), int(radius), int(iterations), float(epsilon),
+                                                             float(max_shift), float(max_gradient), self._subset_planes(dev_out),
+                                                             C.byref(rec) if record else None)
+        if rc:
+            raise Flow2DError(rc, "OpticalFlow2D::RefineNodesFromDevice")
+        return rec if record else None
+
+    def correlate_subset_sequence(self, frames, passes, radius, iterations=20, epsilon=1e-3, max_shift=2.0, max_gradient=0.5, min_score=-1.0,
+                                  threshold=2.0, validate_epsilon=0.1, min_neighbours=3, fill=2, min_state=1, predict_neighbours=1,
+                                  sequence_max_shift=4.0, flow=False):
+        """OpticalFlow2D::CorrelateSubsetSequence: digital image correlation over a loading sequence.  frames[0] is the reference and
+        every later frame is correlated against it: step 1 is correlate_subset's chain; step k >= 2 takes the previous step's
+        deformation, gradients included, as its start -- `fill` passes of flow2d_predict_nodes_2d keep the nodes with a state of
+        min_state at least and refill the others from predict_neighbours usable neighbours, then flow2d_subset_refine_from_2d
+        with sequence_max_shift in place of max_shift -- and no window search runs.  Returns ([nodes per step], [CorrelationPassReport]
+        of step 1, [SequenceStepReport], (lo, scale)), nodes a dict of [nh, nw] arrays by the names of SUBSET_PLANES; with flow,
+        also [(u, v) per step], the refined field expanded to the frame's grid."""
+        images = [np.ascontiguousarray(q, np.float32) for q in frames]
+        if len(images) < 2 or any(q.shape != (self.height, self.width) for q in images):
+            raise ValueError("correlate_subset_sequence takes two or more frames of the object's size")
+        arr, n = self._passes(passes)
+        if not 1 <= n <= CORRELATION_MAX_PASSES:
+            raise Flow2DError(1, "OpticalFlow2D::CorrelateSubsetSequence")
+        steps = len(images) - 1
+        nw, nh = correlation_grid(self.width, self.height, passes[-1][0], passes[-1][2])
+        nodes = [np.empty((nh, nw), np.float32) for _ in range(8 * steps)]
+        uv = [np.empty_like(images[0]) for _ in range(2 * steps)] if flow else None
+        fpp = C.POINTER(C.c_float)
+        reports, reps, lo_scale = (CorrelationPassReport * n)(), (SequenceStepReport * steps)(), (C.c_float * 2)()
+        rc = host_lib().flow2d_host_correlate_subset_sequence(self.handle, (fpp * len(images))(*[_fptr(q) for q in images]), len(images), arr, n,
+                                                              float(min_score), float(threshold), float(validate_epsilon), int(min_neighbours),
+                                                              int(radius), int(iterations), float(epsilon), float(max_shift),
+                                                              float(max_gradient), int(fill), int(min_state), int(predict_neighbours),
+                                                              float(sequence_max_shift), (fpp * (8 * steps))(*[_fptr(q) for q in nodes]),
+                                                              reports, reps, (fpp * (2 * steps))(*[_fptr(q) for q in uv]) if flow else None,
+                                                              lo_scale)
+        if rc:
+            raise Flow2DError(rc, "OpticalFlow2D::CorrelateSubsetSequence")
+        per_step = [dict(zip(self.SUBSET_PLANES, nodes[8 * k:8 * k + 8])) for k in range(steps)]
+        out = (per_step, list(reports), list(reps), (lo_scale[0], lo_scale[1]))
+        return out + ([(uv[2 * k], uv[2 * k + 1]) for k in range(steps)],) if flow else out
+
+    def correlate_subset_sequence_device(self, dev_frames, lo, scale, passes, radius, dev_out, iterations=20, epsilon=1e-3, max_shift=2.0,
+                                         max_gradient=0.5, min_score=-1.0, threshold=2.0, validate_epsilon=0.1, min_neighbours=3, fill=2,
+                                         min_state=1, predict_neighbours=1, sequence_max_shift=4.0, dev_flows=None):
+        """OpticalFlow2D::CorrelateSubsetSequenceDevice: device frames in (the first is the reference); dev_out: per step a dict of
+        device planes by the names of SUBSET_PLANES, of which only the score may be missing; dev_flows: per step a (u, v) pair or
+        None.  Returns ([CorrelationPassReport] of step 1, [SequenceStepReport]); synchronises once."""
+        arr, n = self._passes(passes)
+        steps = len(dev_frames) - 1
+        if steps < 1 or len(dev_out) != steps or (dev_flows is not None and len(dev_flows) != steps):
+            raise ValueError("correlate_subset_sequence_device takes two or more frames and one set of planes per step")
+        planes = []
+        for step in dev_out:
+            planes += list(self._subset_planes(step))
+        flows = None
+        if dev_flows is not None:
+            flat = []
+            for pair in dev_flows:
+                flat += list(pair) if pair is not None else [None, None]
+            flows = (C.c_void_p * (2 * steps))(*flat)
+        reports, reps = (CorrelationPassReport * max(n, 1))(), (SequenceStepReport * steps)()
+        rc = host_lib().flow2d_host_correlate_subset_sequence_device(self.handle, (C.c_void_p * len(dev_frames))(*dev_frames), len(dev_frames),
+                                                                     float(lo), float(scale), arr, n, float(min_score), float(threshold),
+                                                                     float(validate_epsilon), int(min_neighbours), int(radius),
+                                                                     int(iterations), float(epsilon), float(max_shift), float(max_gradient),
+                                                                     int(fill), int(min_state), int(predict_neighbours),
+                                                                     float(sequence_max_shift), (C.c_void_p * (8 * steps))(*planes), reports,
+                                                                     reps, flows)
+        if rc:
+            raise Flow2DError(rc, "OpticalFlow2D::CorrelateSubsetSequenceDevice")
+        return list(reports)[:n], list(reps)
 
     @staticmethod
     def _prior_level(level):

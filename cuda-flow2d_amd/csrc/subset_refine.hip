@@ -123,7 +123,8 @@ __device__ __forceinline__ void cholesky_solve(const double (&L)[6][6], const do
 }
 
 // The node from the frame-0 quantities on: the state, with p, the last c and the iterations begun.  p = (u, ux, uy, v, vx, vy)
-// holds (u0, 0, 0, v0, 0, 0) on entry.  Every lane of the wave returns the same values.
+// holds the start on entry: (u0, 0, 0, v0, 0, 0), or (u0, ux0, uy0, v0, vx0, vy0) of flow2d_subset_refine_from_2d.  Every lane of
+// the wave returns the same values.
 template <typename Offset>
 __device__ __forceinline__ int refine_node(const SubsetNode& nd, const SubsetArgs& a, double (&p)[6], double& score, unsigned& iterations)
 {
@@ -262,9 +263,30 @@ __device__ __forceinline__ int refine_node(const SubsetNode& nd, const SubsetArg
     return 0;
 }
 
-template <typename Offset>
-__global__ __launch_bounds__(64 * kSubsetMaxWaves) void subset_refine_kernel(SubsetArgs a, BatchArg batch)
+// The four start gradients of flow2d_subset_refine_from_2d.
+struct SubsetStart {
+    const float *ux0, *uy0, *vx0, *vy0;
+};
+
+// Whether the start's gradients are finite; without a start there are none to look at.
+template <bool kFrom>
+__device__ __forceinline__ bool gradients_finite(const float (&g0)[4])
 {
+    if constexpr (kFrom)
+        return fabsf(g0[0]) < INFINITY && fabsf(g0[1]) < INFINITY && fabsf(g0[2]) < INFINITY && fabsf(g0[3]) < INFINITY;
+    else
+        return true;
+}
+
+// A wave's node from its inputs to its outputs.  Start: nothing -- flow2d_subset_refine_2d, whose instantiation is the kernel it
+// was before the pack, argument for argument and instruction for instruction -- or one SubsetStart, the start's gradients of
+// flow2d_subset_refine_from_2d.  (The body stays in the kernel itself: moved into a function that two kernels call, it compiled
+// to another instruction stream for the plain one; profiles/subset_sequence/README.md.)
+template <typename Offset, typename... Start>
+__global__ __launch_bounds__(64 * kSubsetMaxWaves) void subset_refine_kernel(SubsetArgs a, BatchArg batch, Start... start)
+{
+    static_assert(sizeof...(Start) <= 1, "nothing or one SubsetStart");
+    constexpr bool kFrom = sizeof...(Start) != 0;
     extern __shared__ __attribute__((aligned(16))) double s_subset[];
 
     const size_t inst = batch_offset(batch);
@@ -292,11 +314,20 @@ __global__ __launch_bounds__(64 * kSubsetMaxWaves) void subset_refine_kernel(Sub
 
     const size_t at = inst + static_cast<size_t>(jn) * static_cast<size_t>(a.npitch) + static_cast<size_t>(in);
     const float u0 = a.u0[at], v0 = a.v0[at];
-    double p[6] = {static_cast<double>(u0), 0.0, 0.0, static_cast<double>(v0), 0.0, 0.0};
+    float g0[4] = {0.f, 0.f, 0.f, 0.f};  // ux0, uy0, vx0, vy0
+    if constexpr (kFrom) {
+        const SubsetStart st = (start, ...);
+        g0[0] = st.ux0[at];
+        g0[1] = st.uy0[at];
+        g0[2] = st.vx0[at];
+        g0[3] = st.vy0[at];
+    }
+    double p[6] = {static_cast<double>(u0), static_cast<double>(g0[0]), static_cast<double>(g0[1]),
+                   static_cast<double>(v0), static_cast<double>(g0[2]), static_cast<double>(g0[3])};
     double score = 0.0;
     unsigned iterations = 0;
     int state;
-    if (!(fabsf(u0) < INFINITY && fabsf(v0) < INFINITY))
+    if (!(fabsf(u0) < INFINITY && fabsf(v0) < INFINITY) || !gradients_finite<kFrom>(g0))
         state = kStateNoInput;
     else if (!(nd.cx - nd.R >= 0 && nd.cy - nd.R >= 0 && nd.cx + nd.R <= a.w - 1 && nd.cy + nd.R <= a.h - 1))
         state = kStateStrayed;
@@ -316,6 +347,12 @@ __global__ __launch_bounds__(64 * kSubsetMaxWaves) void subset_refine_kernel(Sub
         if (state != kStateNoInput) {
             out[0] = u0;
             out[3] = v0;
+            if constexpr (kFrom) {  // flat and strayed hand the whole start back: the field stays the next step's input
+                out[1] = g0[0];
+                out[2] = g0[1];
+                out[4] = g0[2];
+                out[5] = g0[3];
+            }
         }
     }
     a.u[at] = out[0];
@@ -338,15 +375,12 @@ __global__ __launch_bounds__(64 * kSubsetMaxWaves) void subset_refine_kernel(Sub
     }
 }
 
-}  // namespace
-
-extern "C" {
-
-int flow2d_subset_refine_2d(flow2d_context* ctx, const float* frame_0, const float* frame_1, size_t width, size_t height,
-                            size_t pitch_bytes, const float* node_u0, const float* node_v0, size_t nw, size_t nh,
-                            size_t node_pitch_bytes, int grid_radius, int spacing, int subset_radius, int max_iterations, float epsilon,
-                            float max_shift, float max_gradient, float* out_u, float* out_v, float* out_ux, float* out_uy,
-                            float* out_vx, float* out_vy, float* out_score, float* out_state, flow2d_subset_record* record)
+// Both entries: flow2d_subset_refine_2d is `start` absent.
+int subset_refine_entry(flow2d_context* ctx, const float* frame_0, const float* frame_1, size_t width, size_t height, size_t pitch_bytes,
+                        const float* node_u0, const float* node_v0, const float* const (&start)[4], size_t nw, size_t nh,
+                        size_t node_pitch_bytes, int grid_radius, int spacing, int subset_radius, int max_iterations, float epsilon,
+                        float max_shift, float max_gradient, float* out_u, float* out_v, float* out_ux, float* out_uy, float* out_vx,
+                        float* out_vy, float* out_score, float* out_state, flow2d_subset_record* record)
 {
     if (ctx == nullptr) return FLOW2D_ERR_INVALID_ARGUMENT;
     // (every check that needs no context field comes first: they hold without a device)
@@ -362,11 +396,17 @@ int flow2d_subset_refine_2d(flow2d_context* ctx, const float* frame_0, const flo
     const bool gradients = out_ux != nullptr;
     if ((out_uy != nullptr) != gradients || (out_vx != nullptr) != gradients || (out_vy != nullptr) != gradients)
         return FLOW2D_ERR_INVALID_ARGUMENT;
+    // the start gradients: all or none
+    const bool started = start[0] != nullptr;
+    if ((start[1] != nullptr) != started || (start[2] != nullptr) != started || (start[3] != nullptr) != started)
+        return FLOW2D_ERR_INVALID_ARGUMENT;
     if (!flow2d::plane_args_ok(node_u0, nw, nh, node_pitch_bytes) || !flow2d::plane_args_ok(node_v0, nw, nh, node_pitch_bytes) ||
         !flow2d::plane_args_ok(out_u, nw, nh, node_pitch_bytes) || !flow2d::plane_args_ok(out_v, nw, nh, node_pitch_bytes))
         return FLOW2D_ERR_INVALID_ARGUMENT;
     for (int k = 2; k < 8; ++k)
         if (planes[k] && !flow2d::plane_args_ok(planes[k], nw, nh, node_pitch_bytes)) return FLOW2D_ERR_INVALID_ARGUMENT;
+    for (int k = 0; started && k < 4; ++k)
+        if (!flow2d::plane_args_ok(start[k], nw, nh, node_pitch_bytes)) return FLOW2D_ERR_INVALID_ARGUMENT;
     // the grid lies inside the frame, as flow2d_correlation_grid lays it
     const size_t window = static_cast<size_t>(2 * grid_radius + 1);
     if (width < window || height < window || nw - 1 > (width - window) / spacing || nh - 1 > (height - window) / spacing)
@@ -379,7 +419,8 @@ int flow2d_subset_refine_2d(flow2d_context* ctx, const float* frame_0, const flo
                                              {out_uy, node_span}, {out_vx, node_span}, {out_vy, node_span},
                                              {out_score, node_span}, {out_state, node_span},
                                              {record, instances * sizeof(flow2d_subset_record)}};
-        const flow2d::ByteRange read[] = {{frame_0, frame_span}, {frame_1, frame_span}, {node_u0, node_span}, {node_v0, node_span}};
+        const flow2d::ByteRange read[] = {{frame_0, frame_span}, {frame_1, frame_span}, {node_u0, node_span}, {node_v0, node_span},
+                                          {start[0], node_span}, {start[1], node_span}, {start[2], node_span}, {start[3], node_span}};
         return flow2d::any_overlap(written, read);
     };
     if (aliased(height * pitch_bytes, nh * node_pitch_bytes, 1)) return FLOW2D_ERR_INVALID_ARGUMENT;
@@ -398,13 +439,47 @@ int flow2d_subset_refine_2d(flow2d_context* ctx, const float* frame_0, const flo
                           static_cast<int>(nw), static_cast<int>(nh), static_cast<int>(node_pitch_bytes / 4),
                           grid_radius, spacing, subset_radius, max_iterations, slice,
                           static_cast<double>(epsilon), static_cast<double>(max_shift), static_cast<double>(max_gradient)};
+    const SubsetStart st = {start[0], start[1], start[2], start[3]};
     // (the largest offset a lane forms into a frame is below height * pitch_bytes; the node planes are addressed in 64 bits)
     flow2d::launch_by_span(height * pitch_bytes, [&](auto offset) {
-        subset_refine_kernel<decltype(offset)><<<dim3(flow2d::div_up(nw * nh, waves), 1, flow2d::batch_z(ctx, 1)), dim3(64 * waves),
-                                                 waves * wave_bytes, ctx->stream>>>(a, flow2d::batch_arg(ctx, 1));
+        const dim3 grid(flow2d::div_up(nw * nh, waves), 1, flow2d::batch_z(ctx, 1)), block(64 * waves);
+        if (started)
+            subset_refine_kernel<decltype(offset), SubsetStart><<<grid, block, waves * wave_bytes, ctx->stream>>>(a, flow2d::batch_arg(ctx, 1), st);
+        else  // (no start planes: the kernel, and so every byte, of flow2d_subset_refine_2d)
+            subset_refine_kernel<decltype(offset)><<<grid, block, waves * wave_bytes, ctx->stream>>>(a, flow2d::batch_arg(ctx, 1));
     });
     FLOW2D_CHECK_LAUNCH();
     return FLOW2D_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int flow2d_subset_refine_2d(flow2d_context* ctx, const float* frame_0, const float* frame_1, size_t width, size_t height,
+                            size_t pitch_bytes, const float* node_u0, const float* node_v0, size_t nw, size_t nh,
+                            size_t node_pitch_bytes, int grid_radius, int spacing, int subset_radius, int max_iterations, float epsilon,
+                            float max_shift, float max_gradient, float* out_u, float* out_v, float* out_ux, float* out_uy,
+                            float* out_vx, float* out_vy, float* out_score, float* out_state, flow2d_subset_record* record)
+{
+    const float* const none[4] = {nullptr, nullptr, nullptr, nullptr};
+    return subset_refine_entry(ctx, frame_0, frame_1, width, height, pitch_bytes, node_u0, node_v0, none, nw, nh, node_pitch_bytes,
+                               grid_radius, spacing, subset_radius, max_iterations, epsilon, max_shift, max_gradient, out_u, out_v, out_ux,
+                               out_uy, out_vx, out_vy, out_score, out_state, record);
+}
+
+int flow2d_subset_refine_from_2d(flow2d_context* ctx, const float* frame_0, const float* frame_1, size_t width, size_t height,
+                                 size_t pitch_bytes, const float* node_u0, const float* node_v0, const float* node_ux0,
+                                 const float* node_uy0, const float* node_vx0, const float* node_vy0, size_t nw, size_t nh,
+                                 size_t node_pitch_bytes, int grid_radius, int spacing, int subset_radius, int max_iterations,
+                                 float epsilon, float max_shift, float max_gradient, float* out_u, float* out_v, float* out_ux,
+                                 float* out_uy, float* out_vx, float* out_vy, float* out_score, float* out_state,
+                                 flow2d_subset_record* record)
+{
+    const float* const start[4] = {node_ux0, node_uy0, node_vx0, node_vy0};
+    return subset_refine_entry(ctx, frame_0, frame_1, width, height, pitch_bytes, node_u0, node_v0, start, nw, nh, node_pitch_bytes,
+                               grid_radius, spacing, subset_radius, max_iterations, epsilon, max_shift, max_gradient, out_u, out_v, out_ux,
+                               out_uy, out_vx, out_vy, out_score, out_state, record);
 }
 
 }  // extern "C"

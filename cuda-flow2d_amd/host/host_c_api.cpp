@@ -832,6 +832,137 @@ HOST_API int flow2d_host_correlate_subset(flow2d_host_flow* h, const float* fram
     return 0;
 }
 
+// ---- subset refinement over a sequence ------------------------------------------------------------------------------------------
+namespace {
+OpticalFlow2D::SequenceOptions sequence_options(int fill, int min_state, int min_neighbours, float max_shift)
+{
+    OpticalFlow2D::SequenceOptions o;
+    o.fill = fill;
+    o.min_state = min_state;
+    o.min_neighbours = min_neighbours;
+    o.max_shift = max_shift;
+    return o;
+}
+}  // namespace
+
+// OpticalFlow2D::SequenceOptionsOk.  Needs no device.
+HOST_API int flow2d_host_sequence_options_ok(int fill, int min_state, int min_neighbours, float max_shift)
+{
+    return OpticalFlow2D::SequenceOptionsOk(sequence_options(fill, min_state, min_neighbours, max_shift)) ? 1 : 0;
+}
+
+// OpticalFlow2D::RefineNodesFromDevice: dev_start -- six device planes u, v, ux, uy, vx, vy, all needed; the rest as for
+// flow2d_host_refine_nodes_device.
+HOST_API int flow2d_host_refine_nodes_from_device(flow2d_host_flow* h, void* dev_frame_0, void* dev_frame_1, void* const* dev_start,
+                                                  int grid_radius, int spacing, int radius, int iterations, float epsilon, float max_shift,
+                                                  float max_gradient, void* const* dev_out, flow2d_subset_record* record)
+{
+    const auto subset = subset_options(radius, iterations, epsilon, max_shift, max_gradient);
+    if (!h || !dev_frame_0 || !dev_frame_1 || !dev_start || !OpticalFlow2D::SubsetOptionsOk(subset)) return 1;
+    for (int k = 0; k < 6; ++k)
+        if (!dev_start[k]) return 1;
+    OpticalFlow2D::SubsetPlanes start;
+    start = {dp(dev_start[0]), dp(dev_start[1]), dp(dev_start[2]), dp(dev_start[3]), dp(dev_start[4]), dp(dev_start[5]), 0, 0};
+    h->flow.timing_mode = 0;
+    return h->flow.RefineNodesFromDevice(dp(dev_frame_0), dp(dev_frame_1), start, grid_radius, spacing, subset, subset_planes(dev_out), record)
+               ? 0
+               : 2;
+}
+
+// OpticalFlow2D::SequenceStepReport as the facade hands it out
+static_assert(sizeof(OpticalFlow2D::SequenceStepReport) == 64 + 64 * OpticalFlow2D::kSequenceMaxFill, "SequenceStepReport layout");
+
+// OpticalFlow2D::CorrelateSubsetSequenceDevice: dev_frames -- `frames` device planes, the first the reference; dev_out -- eight planes
+// per step (u, v, ux, uy, vx, vy, score, state; only the score may be null); dev_flows (optional) -- two per step, each pair optional;
+// reports (optional) one per pass of step 1, steps (optional) one per step.  Synchronises.  0, 1 or 2 as above.
+HOST_API int flow2d_host_correlate_subset_sequence_device(flow2d_host_flow* h, void* const* dev_frames, int frames, float lo, float scale,
+                                                          const int* passes, int count, float min_score, float threshold, float epsilon,
+                                                          int min_neighbours, int radius, int iterations, float subset_epsilon,
+                                                          float max_shift, float max_gradient, int fill, int min_state,
+                                                          int predict_neighbours, float sequence_max_shift, void* const* dev_out,
+                                                          OpticalFlow2D::CorrelationPassReport* reports,
+                                                          OpticalFlow2D::SequenceStepReport* steps, void* const* dev_flows)
+{
+    const auto list = correlation_passes(passes, count);
+    const auto validation = validation_options(threshold, epsilon, min_neighbours, 1, 1);
+    const auto subset = subset_options(radius, iterations, subset_epsilon, max_shift, max_gradient);
+    const auto sequence = sequence_options(fill, min_state, predict_neighbours, sequence_max_shift);
+    if (!h || !dev_frames || frames < 2 || count < 0 || !dev_out ||
+        !OpticalFlow2D::CorrelationPassesOk(h->width, h->height, lo, scale, list.data(), list.size(), min_score, validation) ||
+        !OpticalFlow2D::SubsetOptionsOk(subset) || !OpticalFlow2D::SequenceOptionsOk(sequence))
+        return 1;
+    const size_t n = static_cast<size_t>(frames), step_count = n - 1;
+    std::vector<DevicePtr> frame_list(n), flow_list(2 * step_count, 0);
+    for (size_t k = 0; k < n; ++k) {
+        if (!dev_frames[k]) return 1;
+        frame_list[k] = dp(dev_frames[k]);
+    }
+    std::vector<OpticalFlow2D::SubsetPlanes> out(step_count);
+    for (size_t k = 0; k < step_count; ++k) {
+        out[k] = subset_planes(dev_out + 8 * k);
+        for (int c = 0; c < 8; ++c)
+            if (c != 6 && !dev_out[8 * k + c]) return 1;
+        for (int c = 0; dev_flows && c < 2; ++c) flow_list[2 * k + c] = dp(dev_flows[2 * k + c]);
+        if ((flow_list[2 * k] == 0) != (flow_list[2 * k + 1] == 0)) return 1;
+    }
+    h->flow.timing_mode = 0;
+    return h->flow.CorrelateSubsetSequenceDevice(frame_list.data(), n, lo, scale, list.data(), list.size(), min_score, validation, subset,
+                                                 sequence, out.data(), reports, steps, dev_flows ? flow_list.data() : nullptr)
+               ? 0
+               : 2;
+}
+
+// OpticalFlow2D::CorrelateSubsetSequence on tight host images: frames -- `count_frames` images; nodes -- eight arrays per step, which
+// get the last pass's nw * nh floats each (only a score may be null); flows (optional) -- two images per step, each pair optional.
+HOST_API int flow2d_host_correlate_subset_sequence(flow2d_host_flow* h, const float* const* frames, int count_frames, const int* passes,
+                                                   int count, float min_score, float threshold, float epsilon, int min_neighbours, int radius,
+                                                   int iterations, float subset_epsilon, float max_shift, float max_gradient, int fill,
+                                                   int min_state, int predict_neighbours, float sequence_max_shift, float* const* nodes,
+                                                   OpticalFlow2D::CorrelationPassReport* reports, OpticalFlow2D::SequenceStepReport* steps,
+                                                   float* const* flows, float* lo_scale)
+{
+    const auto list = correlation_passes(passes, count);
+    const auto validation = validation_options(threshold, epsilon, min_neighbours, 1, 1);
+    const auto subset = subset_options(radius, iterations, subset_epsilon, max_shift, max_gradient);
+    const auto sequence = sequence_options(fill, min_state, predict_neighbours, sequence_max_shift);
+    if (!h || !frames || count_frames < 2 || !nodes || count < 0) return 1;
+    const size_t n = static_cast<size_t>(count_frames), step_count = n - 1;
+    for (size_t k = 0; k < n; ++k)
+        if (!frames[k]) return 1;
+    for (size_t k = 0; k < step_count; ++k) {
+        for (int c = 0; c < 8; ++c)
+            if (c != 6 && !nodes[8 * k + c]) return 1;
+        if (flows && (flows[2 * k] == nullptr) != (flows[2 * k + 1] == nullptr)) return 1;
+    }
+    HostImages im(h);
+    std::vector<Data2D*> in(n), flow_images(2 * step_count, nullptr);
+    for (size_t k = 0; k < n; ++k) in[k] = im.In(frames[k]);
+    for (size_t k = 0; flows && k < 2 * step_count; ++k) flow_images[k] = im.Out(flows[k], im.AfterSuccess);
+    float lo = 0.f, scale = 1.f;
+    OpticalFlow2D::CorrelationRange(*in[0], *in[1], lo, scale);
+    if (!OpticalFlow2D::CorrelationPassesOk(h->width, h->height, lo, scale, list.data(), list.size(), min_score, validation) ||
+        !OpticalFlow2D::SubsetOptionsOk(subset) || !OpticalFlow2D::SequenceOptionsOk(sequence))
+        return 1;
+    size_t nw = 0, nh = 0;
+    flow2d_correlation_grid(h->width, h->height, list.back().radius, list.back().spacing, &nw, &nh);
+    std::vector<Data2D> images;
+    images.reserve(8 * step_count);
+    for (size_t k = 0; k < 8 * step_count; ++k) images.emplace_back(nw, nh);
+    std::vector<Data2D*> wanted(8 * step_count);
+    for (size_t k = 0; k < 8 * step_count; ++k) wanted[k] = nodes[k] ? &images[k] : nullptr;
+    h->flow.CorrelateSubsetSequence(in.data(), n, list.data(), list.size(), min_score, validation, subset, sequence, wanted.data(), reports,
+                                    steps, flows ? flow_images.data() : nullptr);
+    const int rc = im.Finish(h->flow);
+    if (rc) return rc;
+    for (size_t k = 0; k < 8 * step_count; ++k)
+        if (nodes[k]) std::memcpy(nodes[k], images[k].DataPtr(), nw * nh * sizeof(float));
+    if (lo_scale) {
+        lo_scale[0] = lo;
+        lo_scale[1] = scale;
+    }
+    return 0;
+}
+
 // ---- the pyramid started from a prior flow ------------------------------------------------------------------------------------
 // OpticalFlow2D::PriorReport as the facade hands it out
 struct flow2d_host_prior_report {

@@ -83,6 +83,14 @@
 // One line "Subset: {json}" -- the options, the grid, "lo", "scale" and the record's "nodes", "converged", "unconverged", "strayed",
 // "flat", "no_input", "iterations_run" -- is printed in place of the "Correlation:" / "CorrelationPasses:" line.  Without the option
 // nothing changes.
+// --subset-previous PREFIX [--subset-fill F, 1 .. 4, default 2] [--subset-min-state 0|1, default 1] [--subset-predict-neighbours N,
+// 1 .. 8, default 1], valid only together with --subset-refine, is the next step of a loading sequence: FILE_0 is the sequence's
+// reference frame, FILE_1 its current frame, and PREFIXnode-u-NW-NH.raw, -v, -ux, -uy, -vx, -vy and -state are what a --subset-refine
+// run of the previous frame wrote under PREFIX (a missing file or another grid is refused like the other bad inputs).  In place of
+// the search, F passes of flow2d_predict_nodes_2d build the start from them and flow2d_subset_refine_from_2d refines it
+// (OpticalFlow2D::ContinueSubsetSequence), with --subset-max-shift defaulting to 4; the (last) pass of --correlation... gives the grid
+// only.  One line "Prediction: {json}" -- the options and per pass "nodes", "kept", "predicted", "empty" -- is printed before the
+// "Subset:" line, whose "passes" is then 0.  Without the option nothing changes.
 // --initial-flow FILE.flo | --correlation-prior R  [--prior-reach P, pixels, finite and > 0, default 2] [--prior-level L, >= 0]
 // start the variational pyramid from a prior flow instead of from zero at its coarsest level (OpticalFlow2D::ComputeFlowFromPrior /
 // ComputeFlowCorrelationSeeded): the prior is a Middlebury file of the frames' size, or the window correlation of the pair with
@@ -159,6 +167,9 @@ int main(int argc, char** argv)
     std::vector<OpticalFlow2D::CorrelationPass> correlation_passes;  // --correlation-passes R:D:S[,R:D:S...]
     OpticalFlow2D::SubsetOptions subset;  // --subset-refine R and the --subset-* options
     bool subset_refine = false, subset_option = false;
+    OpticalFlow2D::SequenceOptions sequence;  // --subset-previous PREFIX and its options
+    std::string subset_previous;
+    bool sequence_option = false, subset_max_shift_given = false;
     OpticalFlow2D::ValidationOptions validation;                     // --validate-threshold / -epsilon / -min-neighbours / -flag-only
     bool validate_option = false;
     std::string initial_flow_file;  // --initial-flow FILE.flo
@@ -415,7 +426,29 @@ int main(int argc, char** argv)
                 return 5;
             }
             (epsilon ? subset.epsilon : !std::strcmp(argv[i], "--subset-max-shift") ? subset.max_shift : subset.max_gradient) = value;
+            subset_max_shift_given = subset_max_shift_given || !std::strcmp(argv[i], "--subset-max-shift");
             subset_option = true;
+            ++i;
+        }
+        else if (!std::strcmp(argv[i], "--subset-previous")) {
+            if (i + 1 >= argc || !argv[i + 1][0]) {
+                std::printf("--subset-previous takes the prefix of the previous step's node files.\n");
+                return 5;
+            }
+            subset_previous = argv[++i];
+        }
+        else if (!std::strcmp(argv[i], "--subset-fill") || !std::strcmp(argv[i], "--subset-min-state") ||
+                 !std::strcmp(argv[i], "--subset-predict-neighbours")) {
+            const bool fill = !std::strcmp(argv[i], "--subset-fill"), state = !std::strcmp(argv[i], "--subset-min-state");
+            const long low = state ? 0 : 1, high = fill ? OpticalFlow2D::kSequenceMaxFill : state ? 1 : 8;
+            char* end = nullptr;
+            const long n = (i + 1 < argc) ? std::strtol(argv[i + 1], &end, 10) : -1;
+            if (i + 1 >= argc || end == argv[i + 1] || *end != '\0' || n < low || n > high) {
+                std::printf("%s takes an integer of %ld .. %ld.\n", argv[i], low, high);
+                return 5;
+            }
+            (fill ? sequence.fill : state ? sequence.min_state : sequence.min_neighbours) = static_cast<int>(n);
+            sequence_option = true;
             ++i;
         }
         else if (!std::strcmp(argv[i], "--validate-threshold") || !std::strcmp(argv[i], "--validate-epsilon")) {
@@ -486,6 +519,13 @@ int main(int argc, char** argv)
         std::printf("--subset-refine R refines the nodes of --correlation or --correlation-passes, and the --subset-* options belong to it.\n");
         return 5;
     }
+
+    if ((!subset_previous.empty() || sequence_option) && !(subset_refine && !subset_previous.empty())) {
+        std::printf("--subset-previous PREFIX continues a sequence of --subset-refine runs, and --subset-fill, --subset-min-state and "
+                    "--subset-predict-neighbours belong to it.\n");
+        return 5;
+    }
+    sequence.max_shift = subset_max_shift_given || subset_previous.empty() ? subset.max_shift : 4.f;
 
     // (with --correlation-passes the initial flow is the first pass's predictor, not the prior of a pyramid)
     const bool from_prior = (!initial_flow_file.empty() && !multipass) || prior_radius != 0 || !previous_flow_file.empty();
@@ -684,17 +724,50 @@ int main(int argc, char** argv)
             Data2D* nodes[8];
             for (int k = 0; k < 8; ++k) nodes[k] = &images[k];
             flow2d_subset_record record = {};
-            const bool predicted = multipass && !initial_flow_file.empty();
-            optical_flow.CorrelateSubset(frame_0, frame_1, schedule.data(), schedule.size(), correlation_min_score, validation, subset, nodes,
-                                         nullptr, &record, &flow_u, &flow_v, predicted ? &prior_u : nullptr, predicted ? &prior_v : nullptr);
+            const std::string size = "-" + std::to_string(nw) + "-" + std::to_string(nh) + ".raw";
+            if (!subset_previous.empty()) {
+                // the previous step's files, of this grid: u, v, the gradients and the state
+                const int from[7] = {0, 1, 2, 3, 4, 5, 7};
+                std::vector<Data2D> before(7);
+                Data2D* previous[7];
+                for (int k = 0; k < 7; ++k) {
+                    const std::string path = subset_previous + names[from[k]] + size;
+                    if (!before[k].ReadRAWFromFileF32(path.c_str(), nw, nh)) {
+                        std::printf("Cannot read '%s' (%zu x %zu float32: the previous step's nodes on this grid).\n", path.c_str(), nw, nh);
+                        optical_flow.Destroy();
+                        DestroyDeviceContext();
+                        return 2;
+                    }
+                    previous[k] = &before[k];
+                }
+                OpticalFlow2D::SequenceStepReport report = {};
+                optical_flow.ContinueSubsetSequence(frame_0, frame_1, previous, fine.radius, fine.spacing, subset, sequence, nodes, &report,
+                                                    &flow_u, &flow_v);
+                record = report.subset;
+                subset.max_shift = sequence.max_shift;
+                if (optical_flow.LastRunSucceeded()) {
+                    std::printf("Prediction: {\"fill\": %d, \"min_state\": %d, \"min_neighbours\": %d, \"passes\": [", sequence.fill,
+                                sequence.min_state, sequence.min_neighbours);
+                    for (int k = 0; k < sequence.fill; ++k)
+                        std::printf("%s{\"nodes\": %llu, \"kept\": %llu, \"predicted\": %llu, \"empty\": %llu}", k ? ", " : "",
+                                    report.prediction[k].nodes, report.prediction[k].kept, report.prediction[k].predicted,
+                                    report.prediction[k].empty);
+                    std::printf("]}\n");
+                }
+            } else {
+                const bool predicted = multipass && !initial_flow_file.empty();
+                optical_flow.CorrelateSubset(frame_0, frame_1, schedule.data(), schedule.size(), correlation_min_score, validation, subset,
+                                             nodes, nullptr, &record, &flow_u, &flow_v, predicted ? &prior_u : nullptr,
+                                             predicted ? &prior_v : nullptr);
+            }
             if (optical_flow.LastRunSucceeded()) {
-                const std::string size = "-" + std::to_string(nw) + "-" + std::to_string(nh) + ".raw";
                 for (int k = 0; k < 8; ++k) images[k].WriteRAWToFileF32((output_path + counter + names[k] + size).c_str());
                 std::printf("Subset: {\"radius\": %d, \"iterations\": %d, \"epsilon\": %.9g, \"max_shift\": %.9g, \"max_gradient\": %.9g, "
                             "\"passes\": %zu, \"grid_radius\": %d, \"spacing\": %d, \"nw\": %zu, \"nh\": %zu, \"lo\": %.9g, \"scale\": %.9g, "
                             "\"nodes\": %llu, \"converged\": %llu, \"unconverged\": %llu, \"strayed\": %llu, \"flat\": %llu, "
                             "\"no_input\": %llu, \"iterations_run\": %llu}\n",
-                            subset.radius, subset.iterations, subset.epsilon, subset.max_shift, subset.max_gradient, schedule.size(),
+                            subset.radius, subset.iterations, subset.epsilon, subset.max_shift, subset.max_gradient,
+                            subset_previous.empty() ? schedule.size() : size_t(0),
                             fine.radius, fine.spacing, nw, nh, lo, scale, record.nodes, record.converged, record.unconverged,
                             record.strayed, record.flat, record.no_input, record.iterations);
             }

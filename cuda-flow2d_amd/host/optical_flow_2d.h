@@ -364,6 +364,59 @@ public:
                          CorrelationPassReport* reports_out, flow2d_subset_record* record_out, Data2D* flow_u = nullptr,
                          Data2D* flow_v = nullptr, Data2D* predictor_u = nullptr, Data2D* predictor_v = nullptr);
 
+    // DIC over a loading sequence: every frame is correlated against the same reference frame, and from the second step on the
+    // start of a step is the previous step's deformation, gradients included (flow2d_predict_nodes_2d, then
+    // flow2d_subset_refine_from_2d), so that no window search runs and a subset that has rotated or stretched beyond a rigid
+    // window's reach is still followed.
+    // RefineNodesDevice started from a whole deformation: `start` gives u, v and the four gradients (score and state are not looked
+    // at); the rest as there.
+    bool RefineNodesFromDevice(DevicePtr dev_frame_0, DevicePtr dev_frame_1, const SubsetPlanes& start, int grid_radius, int spacing,
+                               const SubsetOptions& subset, const SubsetPlanes& out, flow2d_subset_record* record_out = nullptr);
+    static constexpr int kSequenceMaxFill = 4;
+    struct SequenceOptions {
+        int fill = 2;            // prediction passes per step, 1 .. kSequenceMaxFill: each refills the lost nodes one ring further
+        int min_state = 1;       // 1: converged nodes are kept; 0: also those that ran out of iterations
+        int min_neighbours = 1;  // usable neighbours a lost node needs to be predicted, 1 .. 8
+        float max_shift = 4.f;   // of the steps after the first, in place of subset.max_shift: the motion of one step
+    };
+    struct SequenceStepReport {
+        flow2d_subset_record subset;
+        flow2d_predict_record prediction[kSequenceMaxFill];  // of the passes that ran; zero in step 1 and beyond `fill`
+    };
+    // prints what is wrong; needs no device
+    static bool SequenceOptionsOk(const SequenceOptions& sequence);
+    // dev_frames[0 .. frame_count - 1], frame_count >= 2; dev_frames[0] is the reference.  Step 1 (frames 0, 1) is
+    // CorrelateSubsetDevice's chain.  Step k >= 2 (frames 0, k): sequence.fill passes of flow2d_predict_nodes_2d on step k - 1's
+    // planes, ping-pong between two sets of planes of the object's own, then flow2d_subset_refine_from_2d with
+    // sequence.max_shift.  out[k - 1] gets step k's planes: u, v, the gradients and the state are needed (they are the next step's
+    // input), the score is optional; no plane may serve two steps.  dev_flows (optional): 2 * (frame_count - 1) planes, u and v
+    // per step, each pair optional: the step's (u, v) on the frame's grid (flow2d_expand_nodes_2d).  first_reports (optional, one
+    // per pass) as for CorrelateSubsetDevice; steps_out (optional, frame_count - 1).  There is no new search when many nodes are
+    // lost: the records say so, and the caller decides.  Everything is queued on the stream, the records are read back after
+    // one synchronisation at the end.  Not for lock-step groups.
+    bool CorrelateSubsetSequenceDevice(const DevicePtr* dev_frames, size_t frame_count, float lo, float scale, const CorrelationPass* passes,
+                                       size_t count, float min_score, const ValidationOptions& validation, const SubsetOptions& subset,
+                                       const SequenceOptions& sequence, const SubsetPlanes* out, CorrelationPassReport* first_reports,
+                                       SequenceStepReport* steps_out, const DevicePtr* dev_flows = nullptr);
+    // The host-image form: lo and scale from CorrelationRange of frames 0 and 1; nodes[8 * (k - 1) + 0 .. 7] -- u, v, ux, uy, vx,
+    // vy, score, state of step k, images of the last pass's grid, all but the score needed; flows (optional): 2 per step.
+    void CorrelateSubsetSequence(Data2D* const* frames, size_t frame_count, const CorrelationPass* passes, size_t count, float min_score,
+                                 const ValidationOptions& validation, const SubsetOptions& subset, const SequenceOptions& sequence,
+                                 Data2D* const* nodes, CorrelationPassReport* first_reports, SequenceStepReport* steps_out,
+                                 Data2D* const* flows = nullptr);
+
+    // One later step on its own, for a sequence that arrives frame by frame (the CLI's --subset-previous): `previous` holds the
+    // last step's u, v, gradients and state (its score is not looked at); the prediction's passes and the refinement of
+    // (dev_frame_0, dev_frame_k) with sequence.max_shift into `out`, as CorrelateSubsetSequenceDevice runs them per step.
+    // report_out (optional).  Synchronises.
+    bool ContinueSubsetSequenceDevice(DevicePtr dev_frame_0, DevicePtr dev_frame_k, const SubsetPlanes& previous, int grid_radius,
+                                      int spacing, const SubsetOptions& subset, const SequenceOptions& sequence, const SubsetPlanes& out,
+                                      SequenceStepReport* report_out, DevicePtr dev_flow_u = 0, DevicePtr dev_flow_v = 0);
+    // Its host-image form: previous[7] -- u, v, ux, uy, vx, vy, state -- and nodes[8] as for CorrelateSubset, images of the grid.
+    void ContinueSubsetSequence(Data2D& frame_0, Data2D& frame_k, Data2D* const* previous, int grid_radius, int spacing,
+                                const SubsetOptions& subset, const SequenceOptions& sequence, Data2D* const* nodes,
+                                SequenceStepReport* report_out, Data2D* flow_u = nullptr, Data2D* flow_v = nullptr);
+
     // The pyramid started from a prior flow instead of from zero at the coarsest level (no reference counterpart; Brox & Malik's
     // large-displacement flow and the predictor-corrector passes of PIV start the variational solver from matches in the same
     // way).  dev_prior_u / dev_prior_v: a flow in full-resolution pixels in planes of the container's size, only read; a pixel
@@ -678,9 +731,24 @@ private:
     OwnedPlanes subset_planes_{owned_, 4};
     DeviceScratch subset_scratch_{owned_};
     // RefineNodesDevice without its synchronisation; *refined gets the planes (u, v) that were written
+    // start_gradients (optional): ux0, uy0, vx0, vy0 of flow2d_subset_refine_from_2d
     bool QueueRefineNodes(DevicePtr dev_frame_0, DevicePtr dev_frame_1, DevicePtr dev_node_u0, DevicePtr dev_node_v0, int grid_radius,
                           int spacing, const SubsetOptions& subset, const SubsetPlanes& out, flow2d_subset_record* record_out,
-                          DevicePtr* refined);
+                          DevicePtr* refined, const DevicePtr* start_gradients = nullptr);
+    // CorrelateSubsetDevice, whose synchronisation CorrelateSubsetSequenceDevice leaves out
+    bool QueueCorrelateSubset(DevicePtr dev_frame_0, DevicePtr dev_frame_1, float lo, float scale, const CorrelationPass* passes,
+                              size_t count, float min_score, const ValidationOptions& validation, const SubsetOptions& subset,
+                              DevicePtr dev_predictor_u, DevicePtr dev_predictor_v, const SubsetPlanes& out,
+                              CorrelationPassReport* reports_out, flow2d_subset_record* record_out, DevicePtr dev_flow_u,
+                              DevicePtr dev_flow_v, bool synchronise);
+    // one step after the first, queued: the prediction's passes, the refinement from them, the expansion; the step's device
+    // records lie at scratch_offset of sequence_scratch_
+    bool QueueSequenceStep(DevicePtr dev_frame_0, DevicePtr dev_frame_k, const SubsetPlanes& last, int grid_radius, int spacing,
+                           const SubsetOptions& subset, const SequenceOptions& sequence, const SubsetPlanes& out,
+                           SequenceStepReport* report_out, size_t scratch_offset, DevicePtr dev_flow_u, DevicePtr dev_flow_v);
+    // CorrelateSubsetSequence*: the prediction's two sets of seven planes (u, v, ux, uy, vx, vy, state); the passes' records
+    OwnedPlanes sequence_planes_{owned_, 14};
+    DeviceScratch sequence_scratch_{owned_};
     // ComputeFlowFromPrior*: inside such a run the prior's planes and the start level (RunPyramid starts there, from them); the
     // device count of the prior's non-finite pixels; the expanded field of ComputeFlowCorrelationSeeded* (u, v; first use)
     DevicePtr prior_u_ = 0, prior_v_ = 0;

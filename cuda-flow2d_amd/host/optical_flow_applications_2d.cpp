@@ -749,7 +749,7 @@ bool OpticalFlow2D::SubsetOptionsOk(const SubsetOptions& subset)
 
 bool OpticalFlow2D::QueueRefineNodes(DevicePtr dev_frame_0, DevicePtr dev_frame_1, DevicePtr dev_node_u0, DevicePtr dev_node_v0,
                                      int grid_radius, int spacing, const SubsetOptions& subset, const SubsetPlanes& out,
-                                     flow2d_subset_record* record_out, DevicePtr* refined)
+                                     flow2d_subset_record* record_out, DevicePtr* refined, const DevicePtr* start_gradients)
 {
     const size_t W = dev_container_size_.width, H = dev_container_size_.height, pitch = dev_container_size_.pitch;
     if (!SubsetOptionsOk(subset)) return false;
@@ -769,12 +769,23 @@ bool OpticalFlow2D::QueueRefineNodes(DevicePtr dev_frame_0, DevicePtr dev_frame_
     flow2d_subset_record* record = record_out ? subset_scratch_.At<flow2d_subset_record>() : nullptr;
     auto plane = [](DevicePtr p) { return p ? AsPlane(p) : nullptr; };
     // (the node planes are containers: the frames' pitch; the entry refuses planes that meet)
-    bool ok = !CheckFlow2DError(flow2d_subset_refine_2d(context_, AsPlane(dev_frame_0), AsPlane(dev_frame_1), W, H, pitch, AsPlane(dev_node_u0),
-                                                        AsPlane(dev_node_v0), nw, nh, pitch, grid_radius, spacing, subset.radius,
-                                                        subset.iterations, subset.epsilon, subset.max_shift, subset.max_gradient, AsPlane(u),
-                                                        AsPlane(v), plane(out.ux), plane(out.uy), plane(out.vx), plane(out.vy),
-                                                        plane(out.score), plane(out.state), record),
-                                "flow2d_subset_refine_2d");
+    bool ok;
+    if (start_gradients)
+        ok = !CheckFlow2DError(flow2d_subset_refine_from_2d(context_, AsPlane(dev_frame_0), AsPlane(dev_frame_1), W, H, pitch,
+                                                            AsPlane(dev_node_u0), AsPlane(dev_node_v0), plane(start_gradients[0]),
+                                                            plane(start_gradients[1]), plane(start_gradients[2]),
+                                                            plane(start_gradients[3]), nw, nh, pitch, grid_radius, spacing, subset.radius,
+                                                            subset.iterations, subset.epsilon, subset.max_shift, subset.max_gradient,
+                                                            AsPlane(u), AsPlane(v), plane(out.ux), plane(out.uy), plane(out.vx),
+                                                            plane(out.vy), plane(out.score), plane(out.state), record),
+                               "flow2d_subset_refine_from_2d");
+    else
+        ok = !CheckFlow2DError(flow2d_subset_refine_2d(context_, AsPlane(dev_frame_0), AsPlane(dev_frame_1), W, H, pitch,
+                                                       AsPlane(dev_node_u0), AsPlane(dev_node_v0), nw, nh, pitch, grid_radius, spacing,
+                                                       subset.radius, subset.iterations, subset.epsilon, subset.max_shift,
+                                                       subset.max_gradient, AsPlane(u), AsPlane(v), plane(out.ux), plane(out.uy),
+                                                       plane(out.vx), plane(out.vy), plane(out.score), plane(out.state), record),
+                               "flow2d_subset_refine_2d");
     ok = ok && (!record_out || ReadRecord(record_out, record, sizeof(*record_out)));
     if (refined) {
         refined[0] = u;
@@ -797,6 +808,16 @@ bool OpticalFlow2D::CorrelateSubsetDevice(DevicePtr dev_frame_0, DevicePtr dev_f
                                           DevicePtr dev_predictor_u, DevicePtr dev_predictor_v, const SubsetPlanes& out,
                                           CorrelationPassReport* reports_out, flow2d_subset_record* record_out, DevicePtr dev_flow_u,
                                           DevicePtr dev_flow_v)
+{
+    return QueueCorrelateSubset(dev_frame_0, dev_frame_1, lo, scale, passes, count, min_score, validation, subset, dev_predictor_u,
+                                dev_predictor_v, out, reports_out, record_out, dev_flow_u, dev_flow_v, true);
+}
+
+bool OpticalFlow2D::QueueCorrelateSubset(DevicePtr dev_frame_0, DevicePtr dev_frame_1, float lo, float scale, const CorrelationPass* passes,
+                                         size_t count, float min_score, const ValidationOptions& validation, const SubsetOptions& subset,
+                                         DevicePtr dev_predictor_u, DevicePtr dev_predictor_v, const SubsetPlanes& out,
+                                         CorrelationPassReport* reports_out, flow2d_subset_record* record_out, DevicePtr dev_flow_u,
+                                         DevicePtr dev_flow_v, bool synchronise)
 {
     const size_t W = dev_container_size_.width, H = dev_container_size_.height, pitch = dev_container_size_.pitch;
     if (!CorrelationPassesOk(W, H, lo, scale, passes, count, min_score, validation) || !SubsetOptionsOk(subset)) return false;
@@ -822,6 +843,7 @@ bool OpticalFlow2D::CorrelateSubsetDevice(DevicePtr dev_frame_0, DevicePtr dev_f
                                                       fine.spacing, AsPlane(dev_flow_u), AsPlane(dev_flow_v), W, H, pitch),
                                "flow2d_expand_nodes_2d");
     }
+    if (!synchronise) return ok;
     return !CheckFlow2DError(flow2d_synchronize(context_), "flow2d_synchronize") && ok;
 }
 
@@ -862,6 +884,238 @@ void OpticalFlow2D::CorrelateSubset(Data2D& frame_0, Data2D& frame_1, const Corr
               planes.Download();
     for (int k = 0; ok && k < 8; ++k)
         if (nodes[k]) ok = CopyData2DFromDevice(d[4 + k], *nodes[k], H, dev_container_size_.pitch);
+    last_run_ok_ = ok;
+}
+
+bool OpticalFlow2D::RefineNodesFromDevice(DevicePtr dev_frame_0, DevicePtr dev_frame_1, const SubsetPlanes& start, int grid_radius,
+                                          int spacing, const SubsetOptions& subset, const SubsetPlanes& out,
+                                          flow2d_subset_record* record_out)
+{
+    if (!start.u || !start.v || !start.ux || !start.uy || !start.vx || !start.vy) return false;
+    const DevicePtr gradients[4] = {start.ux, start.uy, start.vx, start.vy};
+    const bool ok = QueueRefineNodes(dev_frame_0, dev_frame_1, start.u, start.v, grid_radius, spacing, subset, out, record_out, nullptr, gradients);
+    if (!ok || !record_out) return ok;
+    return !CheckFlow2DError(flow2d_synchronize(context_), "flow2d_synchronize");
+}
+
+bool OpticalFlow2D::SequenceOptionsOk(const SequenceOptions& sequence)
+{
+    if (sequence.fill >= 1 && sequence.fill <= kSequenceMaxFill && (sequence.min_state == 0 || sequence.min_state == 1) &&
+        sequence.min_neighbours >= 1 && sequence.min_neighbours <= 8 && std::isfinite(sequence.max_shift) && sequence.max_shift > 0.f)
+        return true;
+    std::printf("Error: a subset sequence takes 1 .. %d prediction passes (%d), a least state of 0 or 1 (%d), 1 .. 8 neighbours at least "
+                "(%d) and a finite largest shift > 0 (%g).\n",
+                kSequenceMaxFill, sequence.fill, sequence.min_state, sequence.min_neighbours, sequence.max_shift);
+    return false;
+}
+
+bool OpticalFlow2D::QueueSequenceStep(DevicePtr dev_frame_0, DevicePtr dev_frame_k, const SubsetPlanes& last, int grid_radius, int spacing,
+                                      const SubsetOptions& subset, const SequenceOptions& sequence, const SubsetPlanes& out,
+                                      SequenceStepReport* report_out, size_t scratch_offset, DevicePtr dev_flow_u, DevicePtr dev_flow_v)
+{
+    const size_t W = dev_container_size_.width, H = dev_container_size_.height, pitch = dev_container_size_.pitch;
+    size_t nw = 0, nh = 0;
+    if (flow2d_correlation_grid(W, H, grid_radius, spacing, &nw, &nh) != FLOW2D_OK) {
+        std::printf("Error: a %zu x %zu frame holds no node grid of radius %d and spacing %d.\n", W, H, grid_radius, spacing);
+        return false;
+    }
+    // the prediction's passes: from the last step's planes into set 0, from there into set 1, and back
+    const float* in[7] = {AsPlane(last.u),  AsPlane(last.v),  AsPlane(last.ux),   AsPlane(last.uy),
+                          AsPlane(last.vx), AsPlane(last.vy), AsPlane(last.state)};
+    const DevicePtr* set = nullptr;
+    bool ok = true;
+    for (int pass = 0; ok && pass < sequence.fill; ++pass) {
+        set = sequence_planes_.data() + 7 * (pass & 1);
+        auto* record = sequence_scratch_.At<flow2d_predict_record>(scratch_offset + sizeof(flow2d_subset_record) +
+                                                                    pass * sizeof(flow2d_predict_record));
+        ok = !CheckFlow2DError(flow2d_predict_nodes_2d(context_, in[0], in[1], in[2], in[3], in[4], in[5], in[6], nw, nh, pitch, spacing,
+                                                       sequence.min_state, sequence.min_neighbours, AsPlane(set[0]), AsPlane(set[1]),
+                                                       AsPlane(set[2]), AsPlane(set[3]), AsPlane(set[4]), AsPlane(set[5]), AsPlane(set[6]),
+                                                       report_out ? record : nullptr),
+                               "flow2d_predict_nodes_2d");
+        if (ok && report_out) ok = ReadRecord(&report_out->prediction[pass], record, sizeof(*record));
+        for (int c = 0; c < 7; ++c) in[c] = AsPlane(set[c]);
+    }
+    if (!ok) return false;
+    DevicePtr refined[2] = {0, 0};
+    ok = QueueRefineNodes(dev_frame_0, dev_frame_k, set[0], set[1], grid_radius, spacing, subset, out, report_out ? &report_out->subset : nullptr,
+                          refined, set + 2);
+    if (ok && dev_flow_u)
+        ok = !CheckFlow2DError(flow2d_expand_nodes_2d(context_, AsPlane(refined[0]), AsPlane(refined[1]), nw, nh, pitch, grid_radius, spacing,
+                                                      AsPlane(dev_flow_u), AsPlane(dev_flow_v), W, H, pitch),
+                               "flow2d_expand_nodes_2d");
+    return ok;
+}
+
+bool OpticalFlow2D::ContinueSubsetSequenceDevice(DevicePtr dev_frame_0, DevicePtr dev_frame_k, const SubsetPlanes& previous, int grid_radius,
+                                                 int spacing, const SubsetOptions& subset, const SequenceOptions& sequence,
+                                                 const SubsetPlanes& out, SequenceStepReport* report_out, DevicePtr dev_flow_u,
+                                                 DevicePtr dev_flow_v)
+{
+    SubsetOptions later = subset;
+    later.max_shift = sequence.max_shift;
+    if (!SubsetOptionsOk(later) || !SequenceOptionsOk(sequence)) return false;
+    const bool gradients = out.ux != 0;
+    if (!IsInitialized() || !dev_frame_0 || !dev_frame_k || !previous.u || !previous.v || !previous.ux || !previous.uy || !previous.vx ||
+        !previous.vy || !previous.state || (dev_flow_u == 0) != (dev_flow_v == 0) || (out.u == 0) != (out.v == 0) ||
+        (out.uy != 0) != gradients || (out.vx != 0) != gradients || (out.vy != 0) != gradients)
+        return false;
+    if (RefuseGroup("a subset sequence")) return false;
+    {
+        const DevicePtr read[] = {dev_frame_0, dev_frame_k, previous.u, previous.v, previous.ux, previous.uy, previous.vx, previous.vy, previous.state};
+        std::vector<DevicePtr> written;
+        for (DevicePtr p : {out.u, out.v, out.ux, out.uy, out.vx, out.vy, out.score, out.state, dev_flow_u, dev_flow_v})
+            if (p) written.push_back(p);
+        if (!WrittenPlanesOk(read, 9, written.data(), written.size(), "node or flow plane")) return false;
+    }
+    if (!EnsurePlanes(sequence_planes_, 14)) return false;
+    if (!sequence_scratch_.Ensure(context_, sizeof(flow2d_subset_record) + kSequenceMaxFill * sizeof(flow2d_predict_record))) return false;
+    if (report_out) *report_out = SequenceStepReport{};
+    const bool ok = QueueSequenceStep(dev_frame_0, dev_frame_k, previous, grid_radius, spacing, later, sequence, out, report_out, 0, dev_flow_u,
+                                      dev_flow_v);
+    return !CheckFlow2DError(flow2d_synchronize(context_), "flow2d_synchronize") && ok;
+}
+
+void OpticalFlow2D::ContinueSubsetSequence(Data2D& frame_0, Data2D& frame_k, Data2D* const* previous, int grid_radius, int spacing,
+                                           const SubsetOptions& subset, const SequenceOptions& sequence, Data2D* const* nodes,
+                                           SequenceStepReport* report_out, Data2D* flow_u, Data2D* flow_v)
+{
+    last_run_ok_ = false;
+    if (!IsInitialized() || !previous || !nodes || !nodes[0] || !nodes[1] || (flow_u == nullptr) != (flow_v == nullptr)) return;
+    for (int k = 0; k < 7; ++k)
+        if (!previous[k]) return;
+    const bool gradients = nodes[2] != nullptr;
+    if ((nodes[3] != nullptr) != gradients || (nodes[4] != nullptr) != gradients || (nodes[5] != nullptr) != gradients) return;
+    const size_t W = dev_container_size_.width, H = dev_container_size_.height;
+    size_t nw = 0, nh = 0;
+    if (flow2d_correlation_grid(W, H, grid_radius, spacing, &nw, &nh) != FLOW2D_OK) {
+        std::printf("Error: a %zu x %zu frame holds no node grid of radius %d and spacing %d.\n", W, H, grid_radius, spacing);
+        return;
+    }
+    for (int k = 0; k < 15; ++k) {
+        Data2D* image = k < 7 ? previous[k] : nodes[k - 7];
+        if (image && (image->Width() != nw || image->Height() != nh)) {
+            std::printf("Error: '%s': the node images are not %zu x %zu.\n", GetName(), nw, nh);
+            return;
+        }
+    }
+    CallPlanes planes(context_, dev_container_size_, GetName(), "frame / flow");
+    planes.Add(&frame_0, CallPlanes::In).Add(&frame_k, CallPlanes::In).Add(flow_u, CallPlanes::Out).Add(flow_v, CallPlanes::Out);
+    // the node planes, read and written: containers with no image of their size behind them, uploaded and downloaded here
+    for (int k = 0; k < 7; ++k) planes.Add(nullptr, CallPlanes::Out, true);
+    for (int k = 0; k < 8; ++k) planes.Add(nullptr, CallPlanes::Out, nodes[k] != nullptr);
+    if (!planes.SizesMatch()) return;
+    HostCall call(context_, last_total_ms_, planes.Allocate());
+    const DevicePtr* d = planes.data();
+    bool ok = planes.Upload();
+    for (int k = 0; ok && k < 7; ++k) ok = CopyData2DtoDevice(*previous[k], d[4 + k], H, dev_container_size_.pitch);
+    const SubsetPlanes last = {d[4], d[5], d[6], d[7], d[8], d[9], 0, d[10]};
+    const SubsetPlanes out = {d[11], d[12], d[13], d[14], d[15], d[16], d[17], d[18]};
+    ok = ok && ContinueSubsetSequenceDevice(d[0], d[1], last, grid_radius, spacing, subset, sequence, out, report_out, d[2], d[3]) &&
+         planes.Download();
+    for (int k = 0; ok && k < 8; ++k)
+        if (nodes[k]) ok = CopyData2DFromDevice(d[11 + k], *nodes[k], H, dev_container_size_.pitch);
+    last_run_ok_ = ok;
+}
+
+bool OpticalFlow2D::CorrelateSubsetSequenceDevice(const DevicePtr* dev_frames, size_t frame_count, float lo, float scale,
+                                                  const CorrelationPass* passes, size_t count, float min_score,
+                                                  const ValidationOptions& validation, const SubsetOptions& subset,
+                                                  const SequenceOptions& sequence, const SubsetPlanes* out,
+                                                  CorrelationPassReport* first_reports, SequenceStepReport* steps_out,
+                                                  const DevicePtr* dev_flows)
+{
+    const size_t W = dev_container_size_.width, H = dev_container_size_.height;
+    if (!CorrelationPassesOk(W, H, lo, scale, passes, count, min_score, validation) || !SubsetOptionsOk(subset) ||
+        !SequenceOptionsOk(sequence))
+        return false;
+    if (!IsInitialized() || !dev_frames || frame_count < 2 || !out) return false;
+    if (RefuseGroup("a subset sequence")) return false;
+    const size_t steps = frame_count - 1;
+    {
+        // every step's planes are the next step's input and pass through the prediction, which knows no frame: checked here
+        std::vector<DevicePtr> written;
+        for (size_t k = 0; k < steps; ++k) {
+            const SubsetPlanes& o = out[k];
+            if (!o.u || !o.v || !o.ux || !o.uy || !o.vx || !o.vy || !o.state) {
+                std::printf("Error: '%s': step %zu of a subset sequence needs u, v, the four gradients and the state.\n", GetName(), k + 1);
+                return false;
+            }
+            for (DevicePtr p : {o.u, o.v, o.ux, o.uy, o.vx, o.vy, o.score, o.state})
+                if (p) written.push_back(p);
+            if (dev_flows && (dev_flows[2 * k] == 0) != (dev_flows[2 * k + 1] == 0)) return false;
+            for (int c = 0; dev_flows && c < 2; ++c)
+                if (dev_flows[2 * k + c]) written.push_back(dev_flows[2 * k + c]);
+        }
+        if (!WrittenPlanesOk(dev_frames, frame_count, written.data(), written.size(), "node or flow plane")) return false;
+    }
+    if (!EnsurePlanes(sequence_planes_, 14)) return false;
+    const size_t per_step = sizeof(flow2d_subset_record) + kSequenceMaxFill * sizeof(flow2d_predict_record);
+    if (!sequence_scratch_.Ensure(context_, steps * per_step)) return false;
+    const CorrelationPass& fine = passes[count - 1];
+    if (steps_out) std::fill(steps_out, steps_out + steps, SequenceStepReport{});
+    // step 1: the pair chain
+    bool ok = QueueCorrelateSubset(dev_frames[0], dev_frames[1], lo, scale, passes, count, min_score, validation, subset, 0, 0, out[0],
+                                   first_reports, steps_out ? &steps_out[0].subset : nullptr, dev_flows ? dev_flows[0] : 0,
+                                   dev_flows ? dev_flows[1] : 0, false);
+    SubsetOptions later = subset;
+    later.max_shift = sequence.max_shift;
+    for (size_t k = 1; ok && k < steps; ++k)
+        ok = QueueSequenceStep(dev_frames[0], dev_frames[k + 1], out[k - 1], fine.radius, fine.spacing, later, sequence, out[k],
+                               steps_out ? &steps_out[k] : nullptr, k * per_step, dev_flows ? dev_flows[2 * k] : 0,
+                               dev_flows ? dev_flows[2 * k + 1] : 0);
+    return !CheckFlow2DError(flow2d_synchronize(context_), "flow2d_synchronize") && ok;
+}
+
+void OpticalFlow2D::CorrelateSubsetSequence(Data2D* const* frames, size_t frame_count, const CorrelationPass* passes, size_t count,
+                                            float min_score, const ValidationOptions& validation, const SubsetOptions& subset,
+                                            const SequenceOptions& sequence, Data2D* const* nodes, CorrelationPassReport* first_reports,
+                                            SequenceStepReport* steps_out, Data2D* const* flows)
+{
+    last_run_ok_ = false;
+    if (!IsInitialized() || !frames || frame_count < 2 || !nodes) return;
+    const size_t steps = frame_count - 1;
+    for (size_t k = 0; k < frame_count; ++k)
+        if (!frames[k]) return;
+    for (size_t k = 0; k < steps; ++k) {
+        for (int c = 0; c < 8; ++c)
+            if (c != 6 && !nodes[8 * k + c]) return;
+        if (flows && (flows[2 * k] == nullptr) != (flows[2 * k + 1] == nullptr)) return;
+    }
+    CallPlanes planes(context_, dev_container_size_, GetName(), "frame / flow");
+    for (size_t k = 0; k < frame_count; ++k) planes.Add(frames[k], CallPlanes::In);
+    for (size_t k = 0; k < 2 * steps; ++k) planes.Add(flows ? flows[k] : nullptr, CallPlanes::Out);
+    // the node planes: containers with no image of their size behind them, downloaded below
+    for (size_t k = 0; k < 8 * steps; ++k) planes.Add(nullptr, CallPlanes::Out, nodes[k] != nullptr);
+    if (!planes.SizesMatch()) return;
+    float lo = 0.f, scale = 1.f;
+    CorrelationRange(*frames[0], *frames[1], lo, scale);
+    const size_t W = dev_container_size_.width, H = dev_container_size_.height;
+    if (!CorrelationPassesOk(W, H, lo, scale, passes, count, min_score, validation) || !SubsetOptionsOk(subset) ||
+        !SequenceOptionsOk(sequence))
+        return;
+    size_t nw = 0, nh = 0;
+    flow2d_correlation_grid(W, H, passes[count - 1].radius, passes[count - 1].spacing, &nw, &nh);
+    for (size_t k = 0; k < 8 * steps; ++k)
+        if (nodes[k] && (nodes[k]->Width() != nw || nodes[k]->Height() != nh)) {
+            std::printf("Error: '%s': the node images are not %zu x %zu.\n", GetName(), nw, nh);
+            return;
+        }
+    HostCall call(context_, last_total_ms_, planes.Allocate());
+    const DevicePtr* d = planes.data();
+    const DevicePtr* dev_flows = d + frame_count;
+    const DevicePtr* dev_nodes = dev_flows + 2 * steps;
+    std::vector<SubsetPlanes> out(steps);
+    for (size_t k = 0; k < steps; ++k) {
+        const DevicePtr* p = dev_nodes + 8 * k;
+        out[k] = {p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7]};
+    }
+    bool ok = planes.Upload() &&
+              CorrelateSubsetSequenceDevice(d, frame_count, lo, scale, passes, count, min_score, validation, subset, sequence, out.data(),
+                                            first_reports, steps_out, flows ? dev_flows : nullptr) &&
+              planes.Download();
+    for (size_t k = 0; ok && k < 8 * steps; ++k)
+        if (nodes[k]) ok = CopyData2DFromDevice(dev_nodes[k], *nodes[k], H, dev_container_size_.pitch);
     last_run_ok_ = ok;
 }
 

@@ -35,6 +35,8 @@ for digital image correlation -- fine, aperiodic detail in every window, which t
 are NOT in SCENES: the tables and tests that iterate over that tuple are about the variational flow.
 Speckle deformations (make_speckle_deformation(name, width, height, seed), name one of SPECKLE_DEFORMATIONS), for the subset
 refinement (flow2d_subset_refine_2d): the same texture under a rotation, a stretch and a shear, each with a translation.
+make_speckle_deformation_sequence(name, steps, step_size, ...) carries one of them on, k times per step k, every frame against
+frame 0: the loading sequence flow2d_subset_refine_from_2d is for.
 Pure numpy: no device, no library.
 """
 import numpy as np
@@ -127,6 +129,31 @@ def make_speckle_deformation(name, width=96, height=80, seed=0):
     else:
         raise ValueError("unknown speckle deformation %r (one of %s)" % (name, ", ".join(SPECKLE_DEFORMATIONS)))
     return _affine_scene("speckle_" + name, width, height, texture, a, (1.6, -0.7))
+
+
+def make_speckle_deformation_sequence(name, steps=6, step_size=None, width=96, height=80, seed=0, translation=(0.0, 0.0)):
+    """A loading sequence for the subset refinement over a sequence (flow2d_subset_refine_from_2d): the speckle pattern under k
+    times the deformation `name` (one of SPECKLE_DEFORMATIONS) about the centre, k = 1 .. steps, every frame against the same
+    frame 0.  step_size: the rotation's degrees per step (default 4), the stretch's e per step -- (1 + k e) x (1 - k e / 2),
+    default 0.03 -- or the shear per step (default 0.04); translation: per step, on top.  Returns the list of the `steps` scenes
+    of _affine_scene: scene k - 1 has frame_0, frame_1 = frame k and the exact displacement from frame 0 to frame k in gt_u, gt_v."""
+    if steps < 1:
+        raise ValueError("a deformation sequence has at least one step")
+    if name not in SPECKLE_DEFORMATIONS:
+        raise ValueError("unknown speckle deformation %r (one of %s)" % (name, ", ".join(SPECKLE_DEFORMATIONS)))
+    texture = Speckle(seed)
+    size = {"rotation": 4.0, "stretch": 0.03, "shear": 0.04}[name] if step_size is None else float(step_size)
+    out = []
+    for k in range(1, steps + 1):
+        if name == "rotation":
+            phi = np.radians(k * size)
+            a = [[np.cos(phi), -np.sin(phi)], [np.sin(phi), np.cos(phi)]]
+        elif name == "stretch":
+            a = [[1.0 + k * size, 0.0], [0.0, 1.0 - k * size / 2.0]]
+        else:
+            a = [[1.0, k * size], [0.0, 1.0]]
+        out.append(_affine_scene("speckle_%s_step_%d" % (name, k), width, height, texture, a, (k * translation[0], k * translation[1])))
+    return out
 
 
 class Scene:

@@ -46,7 +46,8 @@ extern "C" {
  * sequence) and flow2d_fused_packed_launches (a test hook: which build of the strip kernel a launch took) and
  * flow2d_correlate_offset_2d / flow2d_validate_nodes_2d (multi-pass window correlation: the search around a predictor's
  * offset and the normalised median test between passes) and flow2d_subset_refine_2d (affine Gauss-Newton refinement of
- * correlation nodes) were added under 1. */
+ * correlation nodes) and flow2d_subset_refine_from_2d / flow2d_predict_nodes_2d (DIC over a sequence: the refinement started
+ * from the previous step's deformation, and that start built from a step's result) were added under 1. */
 #define FLOW2D_ABI_VERSION 1
 
 typedef enum flow2d_status {
@@ -1068,6 +1069,83 @@ FLOW2D_API int flow2d_subset_refine_2d(flow2d_context* ctx, const float* frame_0
                                        float* out_ux /* the four gradient planes: all or none */, float* out_uy, float* out_vx,
                                        float* out_vy, float* out_score /* may be NULL */, float* out_state /* may be NULL */,
                                        flow2d_subset_record* record /* device, may be NULL */);
+
+/* Subset refinement started from a whole deformation: flow2d_subset_refine_2d with four more input planes, node_ux0, node_uy0,
+ * node_vx0 and node_vy0 -- the start's gradients, given all or none, nw x nh floats with node_pitch_bytes per row like node_u0.
+ * It is what a loading sequence needs: every frame is correlated against the same reference frame, and the previous step's
+ * result (through flow2d_predict_nodes_2d) is the next step's start, so that a subset that has rotated or stretched too far
+ * for a rigid window search is still found.  Added to ABI version 1 without changing any existing entry.
+ * The text of flow2d_subset_refine_2d holds word for word except at four places:
+ * No input.  u0, v0, ux0, uy0, vx0 or vy0 is not finite.
+ * Start.  p = (u0, ux0, uy0, v0, vx0, vy0), each converted to double.
+ *   (5. Stop is unchanged: the displacement is bounded against (u0, v0), the gradients absolutely by max_gradient, so a start
+ *   with a gradient beyond max_gradient strays in iteration 1 unless that iteration brings it back.)
+ * Outputs.  Flat and strayed: u0, v0 and the four start gradients copied bit for bit, score 0 -- the field stays usable as the
+ * next step's input.
+ * Refusals.  Also FLOW2D_ERR_INVALID_ARGUMENT, and nothing written, for start planes given in part, a start plane that breaks
+ * the node planes' rules, or a written range that overlaps a start plane.
+ * With all four start planes NULL every output byte and the record are those of flow2d_subset_refine_2d. */
+FLOW2D_API int flow2d_subset_refine_from_2d(flow2d_context* ctx, const float* frame_0, const float* frame_1, size_t width,
+                                            size_t height, size_t pitch_bytes, const float* node_u0, const float* node_v0,
+                                            const float* node_ux0 /* the four start gradients: all or none */,
+                                            const float* node_uy0, const float* node_vx0, const float* node_vy0, size_t nw, size_t nh,
+                                            size_t node_pitch_bytes, int grid_radius, int spacing, int subset_radius,
+                                            int max_iterations, float epsilon, float max_shift, float max_gradient, float* out_u,
+                                            float* out_v, float* out_ux /* the four gradient planes: all or none */, float* out_uy,
+                                            float* out_vx, float* out_vy, float* out_score /* may be NULL */,
+                                            float* out_state /* may be NULL */, flow2d_subset_record* record /* device, may be NULL */);
+
+/* The start of the next step of a sequence from a step's result, out of place: a node the refinement found is kept, every other
+ * node is predicted from its neighbours.  Every node is judged against the input, so the result depends on no order.
+ * Inputs: the six planes node_u, node_v, node_ux, node_uy, node_vx, node_vy and node_state (the outputs of
+ * flow2d_subset_refine_2d / flow2d_subset_refine_from_2d, or of an earlier call of this entry), nw x nh floats with
+ * node_pitch_bytes per row; s = spacing (1 .. FLOW2D_CORRELATION_MAX_SPACING), the pixels between neighbouring nodes;
+ * min_state (0 or 1); min_neighbours (1 .. 8).
+ * Usable.  A node is *usable* when state >= (float)min_state (a positive comparison: a NaN state fails) and its u, v, ux, uy, vx
+ * and vy are all finite.  min_state = 1 takes only converged (and predicted) nodes, 0 also those that ran out of iterations.
+ * Kept.  A usable node: the six values and the state copied bit for bit.
+ * Predicted.  Any other node (i, j) looks at its eight neighbours (i + di, j + dj) in the fixed order (di, dj) = (-1,-1), (0,-1),
+ * (1,-1), (-1,0), (1,0), (-1,1), (0,1), (1,1); those that lie inside the grid and are usable *in the input* count, m of them.
+ * Everything below is IEEE double (an input is converted first, which is exact), every operation rounded on its own, no fused
+ * multiply-add.  Neighbour n offers six candidates: with dx = (double)(-di*s) and dy = (double)(-dj*s) (the products in int)
+ *   cu = (u_n + ux_n*dx) + uy_n*dy;   cv = (v_n + vx_n*dx) + vy_n*dy;   ux_n, uy_n, vx_n, vy_n as they are.
+ * With m >= min_neighbours each of the six outputs is the median of its m candidates, cast to float: the candidates are put in
+ * order by < -- c comes before c' when c < c', and candidates of which neither is below the other (equal ones, -0 and +0)
+ * keep the neighbours' order -- into c[0 .. m-1]; the median is c[m div 2] for odd m and (c[m div 2 - 1] + c[m div 2]) * 0.5 for
+ * even m.  out_state = FLOW2D_SUBSET_STATE_PREDICTED (65, one above FLOW2D_SUBSET_MAX_ITERATIONS), so that a second pass
+ * treats the node as usable at either min_state.
+ * Empty.  With m < min_neighbours all six outputs are NaN (0x7FC00000) and out_state = -1 (no input).
+ * out_state may be NULL.  Record.  record[b] (DEVICE memory, may be NULL), 64 bytes: nodes (nw * nh); kept; predicted; empty;
+ * four reserved words, written as 0.  Integers, added by integer atomics after the entry has zeroed the record on the stream:
+ * alone, in a batch and in a replayed graph the same bytes.
+ * Row padding and the containers beyond nw x nh are neither read into a result nor written.  One launch on the context's stream
+ * (and a 64-byte memset per instance with a record); no allocation, no synchronisation (graph-capturable).  Honours
+ * flow2d_context_set_batch: every plane of instance b at b * stride floats, record + b.
+ * FLOW2D_ERR_INVALID_ARGUMENT, and nothing written, for a null input plane or a null one of the six output planes, a zero size,
+ * a bad pitch, a spacing, min_state or min_neighbours outside its limits, a misaligned record (8), or a written range -- outputs,
+ * state, records, over every instance of a batch -- that overlaps an input or another written range; FLOW2D_ERR_UNSUPPORTED for
+ * 2^31 nodes or more. */
+#define FLOW2D_SUBSET_STATE_PREDICTED 65
+typedef struct flow2d_predict_record {
+    unsigned long long nodes;       /* nw * nh */
+    unsigned long long kept;        /* usable nodes, copied */
+    unsigned long long predicted;   /* nodes that took their neighbours' medians: state 65 */
+    unsigned long long empty;       /* fewer than min_neighbours usable neighbours: NaN, state -1 */
+    unsigned long long reserved[4]; /* 0 */
+} flow2d_predict_record;
+
+#define FLOW2D_PREDICT_RECORD_BYTES 64
+#ifdef __cplusplus
+static_assert(sizeof(flow2d_predict_record) == FLOW2D_PREDICT_RECORD_BYTES, "flow2d_predict_record layout");
+#else
+_Static_assert(sizeof(flow2d_predict_record) == FLOW2D_PREDICT_RECORD_BYTES, "flow2d_predict_record layout");
+#endif
+
+FLOW2D_API int flow2d_predict_nodes_2d(flow2d_context* ctx, const float* node_u, const float* node_v, const float* node_ux,
+                                       const float* node_uy, const float* node_vx, const float* node_vy, const float* node_state,
+                                       size_t nw, size_t nh, size_t node_pitch_bytes, int spacing, int min_state, int min_neighbours,
+                                       float* out_u, float* out_v, float* out_ux, float* out_uy, float* out_vx, float* out_vy,
+                                       float* out_state /* may be NULL */, flow2d_predict_record* record /* device, may be NULL */);
 
 /* The flow of the previous pyramid level resampled to this level's size (the bits of flow2d_resample_xy_pair into out_u / out_v)
  * and frame_1 warped by it (the bits of flow2d_registration_2d into `output`) in one launch: replaces the
