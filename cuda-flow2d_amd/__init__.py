@@ -540,6 +540,10 @@ def hip_lib():
         if hasattr(L, "flow2d_subset_refine_from_2d"):  # (absent from libraries of earlier rounds loaded for an A/B)
             L.flow2d_subset_refine_from_2d.argtypes = [vp, vp, vp, sz, sz, sz] + [vp] * 6 + [sz, sz, sz, i, i, i, i, f, f, f] + [vp] * 9
             L.flow2d_predict_nodes_2d.argtypes = [vp] + [vp] * 7 + [sz, sz, sz, i, i, i] + [vp] * 8
+        if hasattr(L, "flow2d_node_strain_2d"):  # (absent from libraries of earlier rounds loaded for an A/B)
+            L.flow2d_node_strain_workspace_bytes.restype = sz
+            L.flow2d_node_strain_workspace_bytes.argtypes = [sz, sz, sz]
+            L.flow2d_node_strain_2d.argtypes = [vp] + [vp] * 7 + [sz, sz, sz, i, i, i, i, i, i, C.POINTER(DeformationPlanes), vp, vp, sz]
         if hasattr(L, "flow2d_prior_registration_2d"):  # (absent from libraries of earlier rounds loaded for an A/B)
             L.flow2d_prior_registration_2d.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp, sz, sz, sz, f, f, vp, vp]
         if hasattr(L, "flow2d_propagate_flow_2d"):  # (absent from libraries of earlier rounds loaded for an A/B)
@@ -1346,6 +1350,58 @@ class Context:
                 q.free()
                 self._planes.remove(q)
 
+    @staticmethod
+    def node_strain_workspace_bytes(nw, nh, instances=1):
+        """flow2d_node_strain_workspace_bytes: what node_strain needs beside a record (host logic, no device)."""
+        return hip_lib().flow2d_node_strain_workspace_bytes(nw, nh, instances)
+
+    def node_strain(self, node_u, node_v, nw, nh, spacing, window=2, order=1, min_nodes=0, min_state=1, measure=STRAIN_SMALL,
+                    state=None, gradients=None, planes=DEFORMATION_PLANES, stats=True, instances=1):
+        """Strain on the node grid (flow2d_node_strain_2d): the nine quantities of `deformation` at every node of the nw x nh
+        planes node_u, node_v, from the least-squares fit of a polynomial of `order` (1 or 2) to the usable nodes within
+        `window` nodes around each node, or, with window = 0, from `gradients` = the (ux, uy, vx, vy) Planes of a subset
+        refinement.  state: the refinement's state Plane -- a node below min_state is left out -- or None: every finite node
+        is usable.  min_nodes: the fewest usable nodes a window may hold, 0 = one more than the fit has coefficients.
+        planes / stats / the return value: as `deformation`, on the node grid; the record's reserved[0 .. 2] count the nodes
+        lost for their centre, for too few nodes and for a degenerate window."""
+        L = hip_lib()
+        if gradients is not None and len(gradients) != 4:
+            raise ValueError("node_strain takes the four gradient planes (ux, uy, vx, vy) or none")
+        if window > 0 and min_nodes == 0:
+            min_nodes = (6 if order == 2 else 3) + 1
+        own_planes = not isinstance(planes, dict)
+        held = {name: self.plane(node_u.width, node_u.height) for name in planes} if own_planes else dict(planes)
+        unknown = [name for name in held if name not in DEFORMATION_PLANES]
+        if unknown:
+            raise ValueError("deformation planes are %s, not %s" % (", ".join(DEFORMATION_PLANES), unknown))
+        out = DeformationPlanes(**{name: q.ptr for name, q in held.items()})
+        own_stats = stats is True
+        if own_stats and instances != 1:
+            raise ValueError("a lock-step batch takes the caller's records")
+        record = self.deformation_records(instances) if own_stats else (stats or None)
+        workspace, need = None, 0
+        if record is not None:
+            need = L.flow2d_node_strain_workspace_bytes(nw, nh, instances)
+            cached = getattr(self, "_node_strain_workspace", None)
+            if cached is None or cached[0] < need:
+                if cached is not None:
+                    cached[1].free()
+                    self._planes.remove(cached[1])
+                self._node_strain_workspace = cached = (need, self.plane(max(need // 4, 4), 1))
+            workspace = cached[1]
+        try:
+            _check(L.flow2d_node_strain_2d(self.handle, node_u.ptr, node_v.ptr, state.ptr if state is not None else None,
+                                           *([q.ptr for q in gradients] if gradients else [None] * 4), nw, nh, node_u.pitch, int(spacing),
+                                           int(window), int(order), int(min_nodes), int(min_state), int(measure), C.byref(out),
+                                           record.ptr if record is not None else None, workspace.ptr if workspace else None, need),
+                   "flow2d_node_strain_2d")
+            result = {name: q.download(nw, nh) for name, q in held.items()} if own_planes else held
+            return result, (self.read_deformation_stats(record, 1)[0] if own_stats else None)
+        finally:
+            for q in (list(held.values()) if own_planes else []) + ([record] if own_stats else []):
+                q.free()
+                self._planes.remove(q)
+
     def resample_x(self, src, dst, out_w, out_h, in_w):
         _check(hip_lib().flow2d_resample_x(self.handle, src.ptr, dst.ptr, out_w, out_h, in_w, src.pitch),
                "flow2d_resample_x")
@@ -1639,6 +1695,11 @@ def host_lib():
             L.flow2d_host_correlate_subset_sequence_device.argtypes = [vp, pvp, i, f, f, ip, i, f, f, f, i, i, i, f, f, f, i, i, i, f, pvp, rp, st,
                                                                        pvp]
             L.flow2d_host_correlate_subset_sequence.argtypes = [vp, pfp, i, ip, i, f, f, f, i, i, i, f, f, f, i, i, i, f, pfp, rp, st, pfp, fp]
+        if hasattr(L, "flow2d_host_node_strain_device"):
+            ds = C.POINTER(DeformationStats)
+            L.flow2d_host_strain_options_ok.argtypes = [i, i, i, i, i]
+            L.flow2d_host_node_strain_device.argtypes = [vp, C.POINTER(vp), i, sz, sz, i, i, i, i, i, i, C.POINTER(vp), ds]
+            L.flow2d_host_node_strain.argtypes = [vp, C.POINTER(fp), i, sz, sz, i, i, i, i, i, i, C.POINTER(fp), ds]
         if hasattr(L, "flow2d_host_correlate"):
             cr = C.POINTER(CorrelationRecord)
             L.flow2d_host_correlation_args_ok.argtypes = [sz, sz, f, f, i, i, i, f]
@@ -2338,6 +2399,77 @@ class OpticalFlow:
         if rc:
             raise Flow2DError(rc, "OpticalFlow2D::CorrelateSubsetSequenceDevice")
         return list(reports)[:n], list(reps)
+
+    NODE_PLANES = ("u", "v", "ux", "uy", "vx", "vy", "state")  # what node_strain* read of a step's SUBSET_PLANES
+
+    @staticmethod
+    def strain_options_ok(window=2, order=1, min_nodes=0, min_state=1, measure=STRAIN_SMALL):
+        """OpticalFlow2D::StrainOptionsOk: whether node_strain* accept the options.  Needs no device."""
+        return bool(host_lib().flow2d_host_strain_options_ok(int(window), int(order), int(min_nodes), int(min_state), int(measure)))
+
+    def node_strain(self, nodes, spacing, window=2, order=1, min_nodes=0, min_state=1, measure=STRAIN_SMALL, planes=DEFORMATION_PLANES,
+                    stats=True):
+        """OpticalFlow2D::NodeStrain: strain on the node grid (flow2d_node_strain_2d) of one result -- the dict of [nh, nw] arrays
+        by the names of SUBSET_PLANES that correlate_subset returns; u and v are needed, the gradients only with window 0, without a
+        state every finite node is usable -- or of the list of steps that correlate_subset_sequence returns.  `window` nodes around
+        each node are fitted by a polynomial of `order` (0: the node's own gradients); min_nodes 0 = one more than the fit has
+        coefficients.  Returns ({name: [nh, nw] array} for `planes`, DeformationStats or None), or the list of those per step."""
+        single = isinstance(nodes, dict)
+        steps = [nodes] if single else list(nodes)
+        if not steps or any("u" not in q or "v" not in q for q in steps):
+            raise ValueError("node_strain takes a node field with u and v, or a list of them")
+        unknown = [name for name in planes if name not in DEFORMATION_PLANES]
+        if unknown:
+            raise ValueError("deformation planes are %s, not %s" % (", ".join(DEFORMATION_PLANES), unknown))
+        nh, nw = np.shape(steps[0]["u"])
+        given = []
+        for q in steps:
+            for name in self.NODE_PLANES:
+                a = q.get(name)
+                if a is not None:
+                    a = np.ascontiguousarray(a, np.float32)
+                    if a.shape != (nh, nw):
+                        raise ValueError("node_strain: the node images are not %d x %d" % (nw, nh))
+                given.append(a)
+        out = [np.empty((nh, nw), np.float32) if name in planes else None for _ in steps for name in DEFORMATION_PLANES]
+        fpp = C.POINTER(C.c_float)
+        recs = (DeformationStats * len(steps))()
+        rc = host_lib().flow2d_host_node_strain(self.handle, (fpp * len(given))(*[_opt_fptr(a) for a in given]), len(steps), nw, nh,
+                                                int(spacing), int(window), int(order), int(min_nodes), int(min_state), int(measure),
+                                                (fpp * len(out))(*[_opt_fptr(a) for a in out]) if planes else None,
+                                                recs if stats else None)
+        if rc:
+            raise Flow2DError(rc, "OpticalFlow2D::NodeStrain")
+        per_step = [({name: out[9 * k + c] for c, name in enumerate(DEFORMATION_PLANES) if name in planes}, recs[k] if stats else None)
+                    for k in range(len(steps))]
+        return per_step[0] if single else per_step
+
+    def node_strain_device(self, dev_nodes, nw, nh, spacing, window=2, order=1, min_nodes=0, min_state=1, measure=STRAIN_SMALL,
+                           dev_planes=None, stats=True):
+        """OpticalFlow2D::NodeStrainDevice: dev_nodes -- a dict of device planes of the container's size by the names of
+        SUBSET_PLANES (as refine_nodes_device / correlate_subset*_device wrote them), or a list of them, one per step; dev_planes --
+        a dict of device planes by the names of DEFORMATION_PLANES (or a list, one per step), which stay on the device.  Returns the
+        DeformationStats (a list for a list) -- the call then synchronises once -- or, without stats, None (it only queues)."""
+        single = isinstance(dev_nodes, dict)
+        steps = [dev_nodes] if single else list(dev_nodes)
+        outs = [dev_planes] if single or dev_planes is None else list(dev_planes)
+        if dev_planes is not None and len(outs) != len(steps):
+            raise ValueError("node_strain_device takes one set of planes per step")
+        unknown = [name for q in outs if q for name in q if name not in DEFORMATION_PLANES]
+        if unknown:
+            raise ValueError("deformation planes are %s, not %s" % (", ".join(DEFORMATION_PLANES), unknown))
+        flat = [q.get(name) for q in steps for name in self.NODE_PLANES]
+        wanted = [q.get(name) for q in outs for name in DEFORMATION_PLANES] if dev_planes is not None else None
+        recs = (DeformationStats * len(steps))()
+        rc = host_lib().flow2d_host_node_strain_device(self.handle, (C.c_void_p * len(flat))(*flat), len(steps), nw, nh, int(spacing),
+                                                       int(window), int(order), int(min_nodes), int(min_state), int(measure),
+                                                       (C.c_void_p * len(wanted))(*wanted) if wanted is not None else None,
+                                                       recs if stats else None)
+        if rc:
+            raise Flow2DError(rc, "OpticalFlow2D::NodeStrainDevice")
+        if not stats:
+            return None
+        return recs[0] if single else list(recs)
 
     @staticmethod
     def _prior_level(level):

@@ -963,6 +963,79 @@ HOST_API int flow2d_host_correlate_subset_sequence(flow2d_host_flow* h, const fl
     return 0;
 }
 
+// ---- strain on the node grid ---------------------------------------------------------------------------------------------------
+namespace {
+OpticalFlow2D::StrainOptions strain_options(int window, int order, int min_nodes, int min_state, int measure)
+{
+    OpticalFlow2D::StrainOptions o;
+    o.window = window;
+    o.order = order;
+    o.min_nodes = min_nodes;
+    o.min_state = min_state;
+    o.measure = measure;
+    return o;
+}
+}  // namespace
+
+// OpticalFlow2D::StrainOptionsOk.  Needs no device.
+HOST_API int flow2d_host_strain_options_ok(int window, int order, int min_nodes, int min_state, int measure)
+{
+    return OpticalFlow2D::StrainOptionsOk(strain_options(window, order, min_nodes, min_state, measure)) ? 1 : 0;
+}
+
+// OpticalFlow2D::NodeStrainDevice: dev_nodes -- seven device planes per step (u, v, ux, uy, vx, vy, state; u and v needed, the
+// gradients all or none, the state optional), dev_planes -- nine per step in the order of flow2d_deformation_planes, each optional
+// (the array may be null with stats); stats (host, optional) -- one record per step: with it the call synchronises.  0, 1 or 2.
+HOST_API int flow2d_host_node_strain_device(flow2d_host_flow* h, void* const* dev_nodes, int steps, size_t nw, size_t nh, int spacing,
+                                            int window, int order, int min_nodes, int min_state, int measure, void* const* dev_planes,
+                                            flow2d_deformation_stats* stats)
+{
+    const auto strain = strain_options(window, order, min_nodes, min_state, measure);
+    if (!h || !dev_nodes || steps < 1 || (!dev_planes && !stats) || !OpticalFlow2D::StrainOptionsOk(strain)) return 1;
+    const size_t step_count = static_cast<size_t>(steps);
+    std::vector<OpticalFlow2D::SubsetPlanes> fields(step_count);
+    std::vector<DevicePtr> planes(9 * step_count, 0);
+    for (size_t k = 0; k < step_count; ++k) {
+        void* const* q = dev_nodes + 7 * k;
+        if (!q[0] || !q[1]) return 1;
+        fields[k] = {dp(q[0]), dp(q[1]), dp(q[2]), dp(q[3]), dp(q[4]), dp(q[5]), 0, dp(q[6])};
+        for (int c = 0; dev_planes && c < 9; ++c) planes[9 * k + c] = dp(dev_planes[9 * k + c]);
+    }
+    h->flow.timing_mode = 0;
+    return h->flow.NodeStrainDevice(fields.data(), step_count, nw, nh, spacing, strain, dev_planes ? planes.data() : nullptr, stats) ? 0 : 2;
+}
+
+// OpticalFlow2D::NodeStrain on tight host arrays of nw * nh floats: nodes -- seven per step, planes -- nine per step, as above.
+HOST_API int flow2d_host_node_strain(flow2d_host_flow* h, const float* const* nodes, int steps, size_t nw, size_t nh, int spacing, int window,
+                                     int order, int min_nodes, int min_state, int measure, float* const* planes,
+                                     flow2d_deformation_stats* stats)
+{
+    const auto strain = strain_options(window, order, min_nodes, min_state, measure);
+    if (!h || !nodes || steps < 1 || nw == 0 || nh == 0 || (!planes && !stats) || !OpticalFlow2D::StrainOptionsOk(strain)) return 1;
+    const size_t step_count = static_cast<size_t>(steps);
+    std::vector<Data2D> in, out;
+    in.reserve(7 * step_count);
+    out.reserve(9 * step_count);
+    std::vector<Data2D*> given(7 * step_count, nullptr), wanted(9 * step_count, nullptr);
+    for (size_t k = 0; k < 7 * step_count; ++k) {
+        in.emplace_back(nw, nh);
+        if (!nodes[k]) continue;
+        std::memcpy(in[k].DataPtr(), nodes[k], nw * nh * sizeof(float));
+        given[k] = &in[k];
+    }
+    for (size_t k = 0; k < 9 * step_count; ++k) {
+        out.emplace_back(nw, nh);
+        if (planes && planes[k]) wanted[k] = &out[k];
+    }
+    for (size_t k = 0; k < step_count; ++k)
+        if (!given[7 * k] || !given[7 * k + 1]) return 1;
+    h->flow.NodeStrain(given.data(), step_count, spacing, strain, planes ? wanted.data() : nullptr, stats);
+    if (!h->flow.LastRunSucceeded()) return 2;
+    for (size_t k = 0; planes && k < 9 * step_count; ++k)
+        if (planes[k]) std::memcpy(planes[k], out[k].DataPtr(), nw * nh * sizeof(float));
+    return 0;
+}
+
 // ---- the pyramid started from a prior flow ------------------------------------------------------------------------------------
 // OpticalFlow2D::PriorReport as the facade hands it out
 struct flow2d_host_prior_report {

@@ -83,6 +83,13 @@
 // One line "Subset: {json}" -- the options, the grid, "lo", "scale" and the record's "nodes", "converged", "unconverged", "strayed",
 // "flat", "no_input", "iterations_run" -- is printed in place of the "Correlation:" / "CorrelationPasses:" line.  Without the option
 // nothing changes.
+// --subset-strain M (a strain window of 0 .. 7 nodes) [--strain-order 1|2, default 1] [--strain-min-nodes N, default 0: one more
+// than the fit has coefficients] takes the strain of the node field (OpticalFlow2D::NodeStrain, flow2d_node_strain_2d): with
+// --subset-refine, on the pair chain and on --subset-previous, of the refined nodes with their states (M = 0: the subsets' own
+// gradients; M >= 1: a polynomial of the order fitted by least squares to the usable nodes within M nodes); with --correlation or
+// --correlation-passes alone and M >= 1, of the search's nodes, every finite one usable.  --strain small|green selects the measure.
+// node-divergence, node-vorticity, node-dilatation, node-exx, node-eyy, node-exy, node-e1, node-e2 and node-max-shear are written
+// beside the node files, and the record is printed as "NodeStrain: {...}".
 // --subset-previous PREFIX [--subset-fill F, 1 .. 4, default 2] [--subset-min-state 0|1, default 1] [--subset-predict-neighbours N,
 // 1 .. 8, default 1], valid only together with --subset-refine, is the next step of a loading sequence: FILE_0 is the sequence's
 // reference frame, FILE_1 its current frame, and PREFIXnode-u-NW-NH.raw, -v, -ux, -uy, -vx, -vy and -state are what a --subset-refine
@@ -170,6 +177,8 @@ int main(int argc, char** argv)
     OpticalFlow2D::SequenceOptions sequence;  // --subset-previous PREFIX and its options
     std::string subset_previous;
     bool sequence_option = false, subset_max_shift_given = false;
+    OpticalFlow2D::StrainOptions node_strain;  // --subset-strain M and --strain-order, --strain-min-nodes
+    bool subset_strain = false, strain_option = false;
     OpticalFlow2D::ValidationOptions validation;                     // --validate-threshold / -epsilon / -min-neighbours / -flag-only
     bool validate_option = false;
     std::string initial_flow_file;  // --initial-flow FILE.flo
@@ -437,6 +446,20 @@ int main(int argc, char** argv)
             }
             subset_previous = argv[++i];
         }
+        else if (!std::strcmp(argv[i], "--subset-strain") || !std::strcmp(argv[i], "--strain-order") ||
+                 !std::strcmp(argv[i], "--strain-min-nodes")) {
+            const bool window = !std::strcmp(argv[i], "--subset-strain"), order = !std::strcmp(argv[i], "--strain-order");
+            const long low = order ? 1 : 0, high = window ? FLOW2D_NODE_STRAIN_MAX_WINDOW : order ? 2 : 225;
+            char* end = nullptr;
+            const long n = (i + 1 < argc) ? std::strtol(argv[i + 1], &end, 10) : -1;
+            if (i + 1 >= argc || end == argv[i + 1] || *end != '\0' || n < low || n > high) {
+                std::printf("%s takes an integer of %ld .. %ld.\n", argv[i], low, high);
+                return 5;
+            }
+            (window ? node_strain.window : order ? node_strain.order : node_strain.min_nodes) = static_cast<int>(n);
+            (window ? subset_strain : strain_option) = true;
+            ++i;
+        }
         else if (!std::strcmp(argv[i], "--subset-fill") || !std::strcmp(argv[i], "--subset-min-state") ||
                  !std::strcmp(argv[i], "--subset-predict-neighbours")) {
             const bool fill = !std::strcmp(argv[i], "--subset-fill"), state = !std::strcmp(argv[i], "--subset-min-state");
@@ -526,6 +549,29 @@ int main(int argc, char** argv)
         return 5;
     }
     sequence.max_shift = subset_max_shift_given || subset_previous.empty() ? subset.max_shift : 4.f;
+
+    if (strain_option && !subset_strain) {
+        std::printf("--strain-order and --strain-min-nodes belong to --subset-strain M.\n");
+        return 5;
+    }
+    if (subset_strain && !(subset_refine || multipass || method == Methods::Correlation)) {
+        std::printf("--subset-strain M takes the strain of a node field: it goes with --subset-refine, or with --correlation or "
+                    "--correlation-passes alone.\n");
+        return 5;
+    }
+    if (subset_strain && !subset_refine && node_strain.window == 0) {
+        std::printf("--subset-strain 0 takes the gradients of --subset-refine; a search alone delivers none (M >= 1 fits them).\n");
+        return 5;
+    }
+    if (subset_strain) {
+        node_strain.measure = strain_measure;
+        node_strain.min_state = sequence.min_state;
+        if (node_strain.window == 0 && strain_option) {
+            std::printf("--strain-order and --strain-min-nodes describe a window fit: --subset-strain 0 has none.\n");
+            return 5;
+        }
+        if (!OpticalFlow2D::StrainOptionsOk(node_strain)) return 5;
+    }
 
     // (with --correlation-passes the initial flow is the first pass's predictor, not the prior of a pyramid)
     const bool from_prior = (!initial_flow_file.empty() && !multipass) || prior_radius != 0 || !previous_flow_file.empty();
@@ -704,6 +750,34 @@ int main(int argc, char** argv)
             occlusion_1 = Data2D(width, height);
         }
         Data2D node_u, node_v, node_score;
+        // --subset-strain: the nine planes of the node field fields[0 .. 6] (u, v, ux, uy, vx, vy, state; null = absent), written
+        // beside the node files, and the record
+        auto write_node_strain = [&](Data2D* const* fields, size_t nw, size_t nh, int spacing) {
+            const char* names[9] = {"node-divergence", "node-vorticity", "node-dilatation", "node-exx", "node-eyy", "node-exy", "node-e1",
+                                    "node-e2", "node-max-shear"};
+            std::vector<Data2D> images;
+            for (int k = 0; k < 9; ++k) images.emplace_back(nw, nh);
+            Data2D* planes[9];
+            for (int k = 0; k < 9; ++k) planes[k] = &images[k];
+            flow2d_deformation_stats stats = {};
+            optical_flow.NodeStrain(fields, 1, spacing, node_strain, planes, &stats);
+            if (!optical_flow.LastRunSucceeded()) return;
+            const std::string size = "-" + std::to_string(nw) + "-" + std::to_string(nh) + ".raw";
+            for (int k = 0; k < 9; ++k) images[k].WriteRAWToFileF32((output_path + counter + names[k] + size).c_str());
+            std::printf("NodeStrain: {\"window\": %d, \"order\": %d, \"min_nodes\": %d, \"min_state\": %d, \"measure\": \"%s\", "
+                        "\"spacing\": %d, \"nw\": %zu, \"nh\": %zu, \"valid\": %llu, \"invalid\": %llu, \"centre\": %llu, "
+                        "\"sparse\": %llu, \"degenerate\": %llu",
+                        node_strain.window, node_strain.order, node_strain.min_nodes, node_strain.min_state,
+                        node_strain.measure == FLOW2D_STRAIN_SMALL ? "small" : "green", spacing, nw, nh, stats.valid, stats.invalid,
+                        stats.reserved[0], stats.reserved[1], stats.reserved[2]);
+            const flow2d_deformation_moments* moments[6] = {&stats.divergence, &stats.vorticity, &stats.dilatation,
+                                                            &stats.e1,         &stats.e2,        &stats.max_shear};
+            const char* quantity[6] = {"divergence", "vorticity", "dilatation", "e1", "e2", "max_shear"};
+            for (int k = 0; k < 6; ++k)
+                std::printf(", \"%s\": {\"sum\": %.17g, \"sum_sq\": %.17g, \"min\": %.9g, \"max\": %.9g}", quantity[k], moments[k]->sum,
+                            moments[k]->sum_sq, moments[k]->min, moments[k]->max);
+            std::printf("}\n");
+        };
         if (subset_refine) {
             std::vector<OpticalFlow2D::CorrelationPass> schedule = correlation_passes;
             if (!multipass) schedule.push_back({correlation_radius, correlation_range, correlation_spacing});
@@ -770,6 +844,10 @@ int main(int argc, char** argv)
                             subset_previous.empty() ? schedule.size() : size_t(0),
                             fine.radius, fine.spacing, nw, nh, lo, scale, record.nodes, record.converged, record.unconverged,
                             record.strayed, record.flat, record.no_input, record.iterations);
+                if (subset_strain) {
+                    Data2D* fields[7] = {nodes[0], nodes[1], nodes[2], nodes[3], nodes[4], nodes[5], nodes[7]};
+                    write_node_strain(fields, nw, nh, fine.spacing);
+                }
             }
         } else if (multipass) {
             const OpticalFlow2D::CorrelationPass& fine = correlation_passes.back();
@@ -812,6 +890,10 @@ int main(int argc, char** argv)
                                 v.nodes, v.judged, v.outliers, v.filled, v.unjudged, v.remaining_invalid);
                 }
                 std::printf("]}\n");
+                if (subset_strain) {
+                    Data2D* fields[7] = {&node_u, &node_v, nullptr, nullptr, nullptr, nullptr, nullptr};
+                    write_node_strain(fields, nw, nh, fine.spacing);
+                }
             }
         } else if (method == Methods::Correlation) {
             size_t nw = 0, nh = 0;
@@ -840,6 +922,10 @@ int main(int argc, char** argv)
                             "\"unrefined\": %llu}\n",
                             correlation_radius, correlation_range, correlation_spacing, correlation_min_score, lo, scale, nw, nh,
                             record.nodes, record.invalid, record.rejected, record.unrefined);
+                if (subset_strain) {
+                    Data2D* fields[7] = {&node_u, &node_v, nullptr, nullptr, nullptr, nullptr, nullptr};
+                    write_node_strain(fields, nw, nh, correlation_spacing);
+                }
             }
         } else if (!initial_flow_file.empty()) {
             OpticalFlow2D::PriorReport report;

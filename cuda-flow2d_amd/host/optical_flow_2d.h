@@ -417,6 +417,29 @@ public:
                                 const SubsetOptions& subset, const SequenceOptions& sequence, Data2D* const* nodes,
                                 SequenceStepReport* report_out, Data2D* flow_u = nullptr, Data2D* flow_v = nullptr);
 
+    // Strain on the node grid (flow2d_node_strain_2d): the nine quantities of flow2d_deformation_2d at every node, from the
+    // gradients a refinement delivered (window 0) or from a polynomial of `order` fitted by least squares to the usable nodes
+    // within `window` nodes around each node (Pan et al. 2009); nodes below min_state, and nodes that are not finite, are left
+    // out of every fit.  min_nodes: the fewest usable nodes a window may hold, 0 = one more than the fit has coefficients.
+    struct StrainOptions {
+        int window = 2, order = 1, min_nodes = 0 /* 0: k + 1 */, min_state = 1, measure = FLOW2D_STRAIN_SMALL;
+    };
+    // prints what is wrong; needs no device
+    static bool StrainOptionsOk(const StrainOptions& strain);
+    // One node field, or every step of a sequence: steps[k] holds step k's planes as RefineNodesDevice / CorrelateSubset*Device
+    // wrote them -- u and v are needed, the gradients (all or none) only with window 0, the state is optional (without it every
+    // finite node is usable: a field that comes from the search alone), the score is not looked at.  nw x nh: the grid, in planes
+    // of the container's size and pitch.  out_planes: nine device planes per step in the order of flow2d_deformation_planes,
+    // 0 = not wanted (the array may be null when stats_out is given); stats_out (host, optional): step_count records.  One launch
+    // pair per step; the records and the workspace are allocated at the first use and kept; the call synchronises once, at the
+    // end, and only when stats_out is given.  Not for lock-step groups.
+    bool NodeStrainDevice(const SubsetPlanes* steps, size_t step_count, size_t nw, size_t nh, int spacing, const StrainOptions& strain,
+                          const DevicePtr* out_planes, flow2d_deformation_stats* stats_out);
+    // The host-image form: nodes[7 * k + 0 .. 6] -- u, v, ux, uy, vx, vy, state of step k, images of the nw x nh grid, of which u and
+    // v are needed -- and planes[9 * k + 0 .. 8], images of the grid, null = not wanted.
+    void NodeStrain(Data2D* const* nodes, size_t step_count, int spacing, const StrainOptions& strain, Data2D* const* planes,
+                    flow2d_deformation_stats* stats_out);
+
     // The pyramid started from a prior flow instead of from zero at the coarsest level (no reference counterpart; Brox & Malik's
     // large-displacement flow and the predictor-corrector passes of PIV start the variational solver from matches in the same
     // way).  dev_prior_u / dev_prior_v: a flow in full-resolution pixels in planes of the container's size, only read; a pixel
@@ -749,6 +772,8 @@ private:
     // CorrelateSubsetSequence*: the prediction's two sets of seven planes (u, v, ux, uy, vx, vy, state); the passes' records
     OwnedPlanes sequence_planes_{owned_, 14};
     DeviceScratch sequence_scratch_{owned_};
+    // NodeStrain*: per step the record and, behind it, the workspace
+    DeviceScratch strain_scratch_{owned_};
     // ComputeFlowFromPrior*: inside such a run the prior's planes and the start level (RunPyramid starts there, from them); the
     // device count of the prior's non-finite pixels; the expanded field of ComputeFlowCorrelationSeeded* (u, v; first use)
     DevicePtr prior_u_ = 0, prior_v_ = 0;

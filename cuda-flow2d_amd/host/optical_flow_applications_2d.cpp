@@ -1018,6 +1018,114 @@ void OpticalFlow2D::ContinueSubsetSequence(Data2D& frame_0, Data2D& frame_k, Dat
     last_run_ok_ = ok;
 }
 
+bool OpticalFlow2D::StrainOptionsOk(const StrainOptions& strain)
+{
+    const int k = strain.order == 2 ? 6 : 3, side = 2 * strain.window + 1;
+    if (strain.window >= 0 && strain.window <= FLOW2D_NODE_STRAIN_MAX_WINDOW && (strain.min_state == 0 || strain.min_state == 1) &&
+        (strain.measure == FLOW2D_STRAIN_SMALL || strain.measure == FLOW2D_STRAIN_GREEN_LAGRANGE) &&
+        (strain.window == 0 ||
+         ((strain.order == 1 || strain.order == 2) && (strain.min_nodes == 0 || (strain.min_nodes >= k && strain.min_nodes <= side * side)))))
+        return true;
+    std::printf("Error: node strain takes a window of 0 .. %d nodes (%d), with a window an order of 1 or 2 (%d) and a least node count "
+                "of 0 or between the fit's coefficients and the window's nodes (%d), a least state of 0 or 1 (%d) and a measure of 0 or "
+                "1 (%d).\n",
+                FLOW2D_NODE_STRAIN_MAX_WINDOW, strain.window, strain.order, strain.min_nodes, strain.min_state, strain.measure);
+    return false;
+}
+
+bool OpticalFlow2D::NodeStrainDevice(const SubsetPlanes* steps, size_t step_count, size_t nw, size_t nh, int spacing,
+                                     const StrainOptions& strain, const DevicePtr* out_planes, flow2d_deformation_stats* stats_out)
+{
+    const size_t W = dev_container_size_.width, H = dev_container_size_.height, pitch = dev_container_size_.pitch;
+    if (!StrainOptionsOk(strain)) return false;
+    if (!IsInitialized() || !steps || step_count == 0 || (!out_planes && !stats_out)) return false;
+    if (nw == 0 || nh == 0 || nw > W || nh > H) {
+        std::printf("Error: '%s': a %zu x %zu node grid does not lie in planes of %zu x %zu.\n", GetName(), nw, nh, W, H);
+        return false;
+    }
+    if (RefuseGroup("node strain")) return false;
+    for (size_t k = 0; k < step_count; ++k) {
+        const SubsetPlanes& q = steps[k];
+        const bool gradients = q.ux != 0;
+        if (!q.u || !q.v || (q.uy != 0) != gradients || (q.vx != 0) != gradients || (q.vy != 0) != gradients ||
+            (strain.window == 0 && !gradients)) {
+            std::printf("Error: '%s': step %zu of node strain needs u and v, the four gradients all or none, and all with window 0.\n",
+                        GetName(), k + 1);
+            return false;
+        }
+    }
+    const int min_nodes = strain.window > 0 && strain.min_nodes == 0 ? (strain.order == 2 ? 6 : 3) + 1 : strain.min_nodes;
+    const size_t workspace_bytes = stats_out ? flow2d_node_strain_workspace_bytes(nw, nh, 1) : 0;
+    const size_t per_step = sizeof(flow2d_deformation_stats) + workspace_bytes;
+    if (stats_out && !strain_scratch_.Ensure(context_, step_count * per_step)) return false;
+    auto plane = [](DevicePtr p) { return p ? AsPlane(p) : nullptr; };
+    bool ok = true;
+    for (size_t k = 0; ok && k < step_count; ++k) {
+        const SubsetPlanes& q = steps[k];
+        flow2d_deformation_planes out = {};
+        if (out_planes) {
+            const DevicePtr* d = out_planes + 9 * k;
+            out = {plane(d[0]), plane(d[1]), plane(d[2]), plane(d[3]), plane(d[4]), plane(d[5]), plane(d[6]), plane(d[7]), plane(d[8])};
+        }
+        auto* record = stats_out ? strain_scratch_.At<flow2d_deformation_stats>(k * per_step) : nullptr;
+        void* workspace = stats_out ? strain_scratch_.At<>(k * per_step + sizeof(flow2d_deformation_stats)) : nullptr;
+        // (the node planes are containers: the frames' pitch; the entry refuses planes that meet)
+        ok = !CheckFlow2DError(flow2d_node_strain_2d(context_, AsPlane(q.u), AsPlane(q.v), plane(q.state), plane(q.ux), plane(q.uy),
+                                                     plane(q.vx), plane(q.vy), nw, nh, pitch, spacing, strain.window, strain.order,
+                                                     min_nodes, strain.min_state, strain.measure, &out, record, workspace, workspace_bytes),
+                               "flow2d_node_strain_2d");
+        if (ok && stats_out) ok = ReadRecord(stats_out + k, record, sizeof(*record));
+    }
+    if (!stats_out) return ok;
+    return !CheckFlow2DError(flow2d_synchronize(context_), "flow2d_synchronize") && ok;
+}
+
+void OpticalFlow2D::NodeStrain(Data2D* const* nodes, size_t step_count, int spacing, const StrainOptions& strain, Data2D* const* planes,
+                               flow2d_deformation_stats* stats_out)
+{
+    last_run_ok_ = false;
+    if (!IsInitialized() || !nodes || step_count == 0 || !nodes[0] || (!planes && !stats_out) || !StrainOptionsOk(strain)) return;
+    const size_t nw = nodes[0]->Width(), nh = nodes[0]->Height(), H = dev_container_size_.height;
+    if (nw == 0 || nh == 0 || nw > dev_container_size_.width || nh > H) {
+        std::printf("Error: '%s': a %zu x %zu node grid does not lie in planes of %zu x %zu.\n", GetName(), nw, nh,
+                    dev_container_size_.width, H);
+        return;
+    }
+    for (size_t k = 0; k < step_count; ++k) {
+        if (!nodes[7 * k] || !nodes[7 * k + 1]) return;
+        for (int c = 0; c < 16; ++c) {
+            Data2D* image = c < 7 ? nodes[7 * k + c] : (planes ? planes[9 * k + c - 7] : nullptr);
+            if (image && (image->Width() != nw || image->Height() != nh)) {
+                std::printf("Error: '%s': the node images are not %zu x %zu.\n", GetName(), nw, nh);
+                return;
+            }
+        }
+    }
+    // the node planes, read and written: containers with no image of their size behind them, uploaded and downloaded here
+    CallPlanes call_planes(context_, dev_container_size_, GetName(), "node");
+    for (size_t k = 0; k < step_count; ++k) {
+        for (int c = 0; c < 7; ++c) call_planes.Add(nullptr, CallPlanes::Out, nodes[7 * k + c] != nullptr);
+        for (int c = 0; c < 9; ++c) call_planes.Add(nullptr, CallPlanes::Out, planes && planes[9 * k + c] != nullptr);
+    }
+    HostCall call(context_, last_total_ms_, call_planes.Allocate());
+    const DevicePtr* d = call_planes.data();
+    bool ok = call_planes.Upload();
+    std::vector<SubsetPlanes> steps(step_count);
+    std::vector<DevicePtr> out(9 * step_count, 0);
+    for (size_t k = 0; k < step_count; ++k) {
+        const DevicePtr* q = d + 16 * k;
+        for (int c = 0; ok && c < 7; ++c)
+            if (nodes[7 * k + c]) ok = CopyData2DtoDevice(*nodes[7 * k + c], q[c], H, dev_container_size_.pitch);
+        steps[k] = {q[0], q[1], q[2], q[3], q[4], q[5], 0, q[6]};
+        for (int c = 0; c < 9; ++c) out[9 * k + c] = q[7 + c];
+    }
+    ok = ok && NodeStrainDevice(steps.data(), step_count, nw, nh, spacing, strain, planes ? out.data() : nullptr, stats_out);
+    // (without a record the device call only queues: the downloads below are ordered behind it on the stream)
+    for (size_t k = 0; ok && planes && k < 9 * step_count; ++k)
+        if (planes[k]) ok = CopyData2DFromDevice(out[k], *planes[k], H, dev_container_size_.pitch);
+    last_run_ok_ = ok;
+}
+
 bool OpticalFlow2D::CorrelateSubsetSequenceDevice(const DevicePtr* dev_frames, size_t frame_count, float lo, float scale,
                                                   const CorrelationPass* passes, size_t count, float min_score,
                                                   const ValidationOptions& validation, const SubsetOptions& subset,

@@ -47,7 +47,8 @@ extern "C" {
  * flow2d_correlate_offset_2d / flow2d_validate_nodes_2d (multi-pass window correlation: the search around a predictor's
  * offset and the normalised median test between passes) and flow2d_subset_refine_2d (affine Gauss-Newton refinement of
  * correlation nodes) and flow2d_subset_refine_from_2d / flow2d_predict_nodes_2d (DIC over a sequence: the refinement started
- * from the previous step's deformation, and that start built from a step's result) were added under 1. */
+ * from the previous step's deformation, and that start built from a step's result) and flow2d_node_strain_2d /
+ * flow2d_node_strain_workspace_bytes (strain on the node grid from least-squares strain windows) were added under 1. */
 #define FLOW2D_ABI_VERSION 1
 
 typedef enum flow2d_status {
@@ -1146,6 +1147,72 @@ FLOW2D_API int flow2d_predict_nodes_2d(flow2d_context* ctx, const float* node_u,
                                        size_t nw, size_t nh, size_t node_pitch_bytes, int spacing, int min_state, int min_neighbours,
                                        float* out_u, float* out_v, float* out_ux, float* out_uy, float* out_vx, float* out_vy,
                                        float* out_state /* may be NULL */, flow2d_predict_record* record /* device, may be NULL */);
+
+/* Strain on the node grid (digital image correlation): the nine quantities of flow2d_deformation_2d from a node field's
+ * displacement gradients, which are either the gradients a subset refinement delivered (window = 0) or the gradient of a
+ * low-order polynomial fitted by least squares to the displacements of the usable nodes inside a *strain window* around each
+ * node (Pan, Asundi, Xie & Gao, Opt. Eng. 48 (2009): pointwise least squares).  Nodes that were lost are left out of the fit,
+ * so holes and the border of the grid are handled by the fit itself.  Added to ABI version 1 without changing any existing entry.
+ *
+ * Everything below is IEEE double (an input is converted first, which is exact); every operation is rounded on its own, no
+ * fused multiply-add; division and square root correctly rounded.  Every test is written as a positive comparison, so that a
+ * NaN fails it.
+ * Inputs.  node_u, node_v; node_state (may be NULL); node_ux, node_uy, node_vx, node_vy (all or none): nw x nh floats with
+ * node_pitch_bytes per row.  s = spacing (1 .. FLOW2D_CORRELATION_MAX_SPACING), the pixels between neighbouring nodes;
+ * m = window (0 .. FLOW2D_NODE_STRAIN_MAX_WINDOW), the strain window's radius in nodes; order (1 or 2); min_nodes; min_state
+ * (0 or 1); measure (a flow2d_strain_measure).
+ * Usable.  A node q is *usable* when it lies inside the grid, node_state == NULL or state[q] >= (float)min_state, u_q and v_q
+ * are finite and, when m = 0, its four gradients are finite.  A node that is not usable is *invalid*, with the reason *centre*.
+ * m = 0 (direct).  a, b, c, d = ux, uy, vx, vy of the node.  The gradient planes are required; order and min_nodes are not
+ * looked at.
+ * m >= 1 (window fit).  The gradient planes are not read and may be NULL.  The basis phi over a window offset (di, dj),
+ * |di|, |dj| <= m, is (1, di, dj) for order 1, k = 3, and (1, di, dj, di*di, di*dj, dj*dj) for order 2, k = 6; the products are
+ * formed in int.  min_nodes lies in k .. (2m + 1)^2.  The usable nodes q = (i + di, j + dj) of the window of node (i, j) are
+ * visited in raster order, dj ascending and within that di ascending; n is their count (the centre is one of them).
+ *   M[a][b] = sum of phi_a*phi_b, in 64-bit integers, then converted (exact);
+ *   wu = (double)u_q - (double)u_centre,  wv likewise;
+ *   bu[a] = sum of phi_a*wu, each product rounded, the terms added from 0 in the visiting order;  bv[a] likewise.
+ * *Sparse*, invalid, when !(n >= min_nodes).  Otherwise the Cholesky factorisation and Solve of flow2d_subset_refine_2d's text
+ * with M in the place of H and k in the place of 6 (columns 0 .. k - 1, i up to k - 1); the node is *degenerate*, invalid, where
+ * that text says *flat*: when !(d > 1e-10 * M[kk][kk]) in some column kk.  Collinear nodes end here.  Otherwise
+ *   cu = Solve(bu),  cv = Solve(bv);   a = cu[1]/s,  b = cu[2]/s,  c = cv[1]/s,  d = cv[2]/s,   s converted to double.
+ * Quantities, in double, each cast to float once at the end:
+ *   divergence = a + d;   vorticity = c - b;   dilatation = (a + d) + (a*d - b*c)
+ *   measure == FLOW2D_STRAIN_SMALL:           exx = a,  eyy = d,  exy = 0.5*(b + c)
+ *   measure == FLOW2D_STRAIN_GREEN_LAGRANGE:  exx = a + 0.5*(a*a + c*c),  eyy = d + 0.5*(b*b + d*d),
+ *                                             exy = 0.5*((b + c) + (a*b + c*d))
+ *   mean = 0.5*(exx + eyy),  half = 0.5*(exx - eyy),  max_shear = sqrt(half*half + exy*exy),  e1 = mean + max_shear,
+ *   e2 = mean - max_shear      (exx, eyy and exy enter these as doubles, before their cast)
+ * Outputs.  `out` is a HOST struct of nine device pointers to planes ON THE NODE GRID (nw x nh, node_pitch_bytes), each of which
+ * may be NULL; a requested plane gets its quantity at every valid node and NaN (0x7FC00000) at every other node of nw x nh.
+ * Row padding and the containers beyond nw x nh are neither read into a result nor written.  stats[b] (DEVICE memory, may be
+ * NULL) gets the record of instance b with the layout and meaning of flow2d_deformation_stats over the valid nodes -- valid,
+ * invalid (nw * nh - valid) and sum, sum_sq, min, max of the six floats that are (or would be) stored -- and three of the
+ * reserved words: reserved[0] = *centre* nodes, reserved[1] = *sparse* nodes, reserved[2] = *degenerate* nodes; the rest 0.
+ * Deterministic: per workgroup of 64 x 4 nodes a slab of partial sums in the caller's `workspace`, then one workgroup per
+ * instance adds the slabs in block order; no atomics.  The grid depends only on (nw, nh): repeated calls, a replayed graph and
+ * an instance alone or in its batch give the same bytes.  Two launches on the context's stream, one when stats == NULL (the
+ * workspace is then not used and may be NULL); no allocation, no synchronisation (graph-capturable).  `workspace` holds at
+ * least flow2d_node_strain_workspace_bytes(nw, nh, instances) bytes, 16-byte aligned.  Honours flow2d_context_set_batch: planes
+ * at b * stride, stats + b.
+ * FLOW2D_ERR_INVALID_ARGUMENT, and nothing written, for a null node_u or node_v, out == NULL or without a plane when stats ==
+ * NULL, a zero size, a bad pitch (the rule of flow2d_consistency_2d, for node_pitch_bytes against nw), a spacing, window,
+ * min_state or measure outside its limits, for m >= 1 an order or min_nodes outside its limits, m = 0 without the gradient
+ * planes, gradient planes given in part, a misaligned `stats` (8) or `workspace` (16), a null or too small workspace when stats
+ * != NULL, or a written range -- a requested plane, the records, the workspace, over every instance of a batch -- that overlaps
+ * an input plane or another written range; FLOW2D_ERR_UNSUPPORTED for 2^31 nodes or more. */
+#define FLOW2D_NODE_STRAIN_MAX_WINDOW 7
+/* Workspace bytes flow2d_node_strain_2d needs for `instances` lock-step instances of an nw x nh grid when it writes statistics
+ * (0 for a zero size; a multiple of 16).  Host logic only, needs no device. */
+FLOW2D_API size_t flow2d_node_strain_workspace_bytes(size_t nw, size_t nh, size_t instances);
+FLOW2D_API int flow2d_node_strain_2d(flow2d_context* ctx, const float* node_u, const float* node_v,
+                                     const float* node_state /* may be NULL */,
+                                     const float* node_ux /* the four gradient planes: all or none */, const float* node_uy,
+                                     const float* node_vx, const float* node_vy, size_t nw, size_t nh, size_t node_pitch_bytes,
+                                     int spacing, int window, int order, int min_nodes, int min_state, int measure,
+                                     const flow2d_deformation_planes* out /* host, may be NULL */,
+                                     flow2d_deformation_stats* stats /* device, may be NULL */, void* workspace,
+                                     size_t workspace_bytes);
 
 /* The flow of the previous pyramid level resampled to this level's size (the bits of flow2d_resample_xy_pair into out_u / out_v)
  * and frame_1 warped by it (the bits of flow2d_registration_2d into `output`) in one launch: replaces the
