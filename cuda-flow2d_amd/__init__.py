@@ -673,6 +673,15 @@ class Context:
             p.upload(data)
         return p
 
+    def _record_plane(self, bytes_per_record, instances, least=0):
+        """A Plane of `instances` records of `bytes_per_record` bytes, `least` floats wide at least."""
+        return self.plane(max(instances * bytes_per_record // 4, least), 1)
+
+    def _read_records(self, record, instances, kind):
+        """The first `instances` records of a record Plane as a list of `kind` (synchronises)."""
+        raw = record.download(instances * C.sizeof(kind) // 4, 1)
+        return list((kind * instances).from_buffer_copy(raw.tobytes()))
+
     def copy_planes(self, srcs, dsts, width, height):
         """flow2d_copy_planes: the planes srcs[i] -> dsts[i] (same pitch) with one launch."""
         n = len(srcs)
@@ -908,12 +917,11 @@ class Context:
 
     def motion_records(self, instances=1):
         """A Plane for `instances` flow2d_global_motion records (device memory; read_motion / upload_motion move them)."""
-        return self.plane(instances * GLOBAL_MOTION_BYTES // 4, 1)
+        return self._record_plane(GLOBAL_MOTION_BYTES, instances)
 
     def read_motion(self, motion, instances=1):
         """The records of a motion_records Plane as GlobalMotion structures (synchronises)."""
-        raw = motion.download(instances * GLOBAL_MOTION_BYTES // 4, 1)
-        return list((GlobalMotion * instances).from_buffer_copy(raw.tobytes()))
+        return self._read_records(motion, instances, GlobalMotion)
 
     def upload_motion(self, records, motion=None):
         """GlobalMotion structures into a motion_records Plane (a new one unless given), byte for byte."""
@@ -963,11 +971,11 @@ class Context:
 
     def region_records(self, max_regions=DEFAULT_MAX_REGIONS, instances=1):
         """A Plane for `instances` tables of `max_regions` flow2d_motion_region records (device memory)."""
-        return self.plane(max(instances * max_regions, 1) * MOTION_REGION_BYTES // 4, 1)
+        return self._record_plane(MOTION_REGION_BYTES, max(instances * max_regions, 1))
 
     def segment_summaries(self, instances=1):
         """A Plane for `instances` flow2d_segment_summary records (device memory)."""
-        return self.plane(instances * SEGMENT_SUMMARY_BYTES // 4, 1)
+        return self._record_plane(SEGMENT_SUMMARY_BYTES, instances)
 
     def read_regions(self, regions, count, max_regions=None, instance=0):
         """The first `count` records of instance `instance` of a region_records Plane whose tables hold `max_regions` records
@@ -980,8 +988,7 @@ class Context:
 
     def read_segment_summary(self, summary, instances=1):
         """The records of a segment_summaries Plane as SegmentSummary structures (synchronises)."""
-        raw = summary.download(instances * SEGMENT_SUMMARY_BYTES // 4, 1)
-        return list((SegmentSummary * instances).from_buffer_copy(raw.tobytes()))
+        return self._read_records(summary, instances, SegmentSummary)
 
     def segment_motion(self, ru, rv, w, h, threshold, join=float("inf"), min_area=1, mask=None, max_regions=DEFAULT_MAX_REGIONS,
                        instances=1, labels=None, regions=None, summary=None):
@@ -1022,12 +1029,11 @@ class Context:
 
     def deformation_records(self, instances=1):
         """A Plane for `instances` flow2d_deformation_stats records (device memory)."""
-        return self.plane(instances * DEFORMATION_STATS_BYTES // 4, 1)
+        return self._record_plane(DEFORMATION_STATS_BYTES, instances)
 
     def read_deformation_stats(self, stats, instances=1):
         """The records of a deformation_records Plane as DeformationStats structures (synchronises)."""
-        raw = stats.download(instances * DEFORMATION_STATS_BYTES // 4, 1)
-        return list((DeformationStats * instances).from_buffer_copy(raw.tobytes()))
+        return self._read_records(stats, instances, DeformationStats)
 
     def deformation(self, pu, pv, w, h, measure=STRAIN_SMALL, mask=None, planes=DEFORMATION_PLANES, stats=True, instances=1):
         """How the flow (pu, pv) deforms the material (flow2d_deformation_2d): divergence, vorticity, dilatation, the strain
@@ -1072,12 +1078,11 @@ class Context:
 
     def refine_records(self, instances=1):
         """A Plane for `instances` flow2d_refine_record records (device memory)."""
-        return self.plane(max(instances * REFINE_RECORD_BYTES // 4, 4), 1)
+        return self._record_plane(REFINE_RECORD_BYTES, instances, 4)
 
     def read_refine_record(self, record, instances=1):
         """The records of a refine_records Plane as RefineRecord structures (synchronises)."""
-        raw = record.download(instances * REFINE_RECORD_BYTES // 4, 1)
-        return list((RefineRecord * instances).from_buffer_copy(raw.tobytes()))
+        return self._read_records(record, instances, RefineRecord)
 
     def refine_flow(self, pu, pv, w, h, radius, guide=None, mask=None, sigma_guide=0.0, sigma_space=0.0, out_u=None, out_v=None,
                     record=True, instances=1):
@@ -1110,12 +1115,11 @@ class Context:
 
     def correlation_records(self, instances=1):
         """A Plane for `instances` flow2d_correlation_record records (device memory)."""
-        return self.plane(max(instances * CORRELATION_RECORD_BYTES // 4, 4), 1)
+        return self._record_plane(CORRELATION_RECORD_BYTES, instances, 4)
 
     def read_correlation_record(self, record, instances=1):
         """The records of a correlation_records Plane as CorrelationRecord structures (synchronises)."""
-        raw = record.download(instances * CORRELATION_RECORD_BYTES // 4, 1)
-        return list((CorrelationRecord * instances).from_buffer_copy(raw.tobytes()))
+        return self._read_records(record, instances, CorrelationRecord)
 
     def correlate(self, f0, f1, w, h, lo, scale, radius, search, spacing, min_score=-1.0, node_u=None, node_v=None,
                   node_score=None, record=True, instances=1):
@@ -1156,11 +1160,7 @@ class Context:
 
     def pass_records(self, instances=1):
         """A Plane for `instances` 64-byte records (flow2d_correlation_pass_record or flow2d_validation_record; device memory)."""
-        return self.plane(instances * CORRELATION_PASS_RECORD_BYTES // 4, 1)
-
-    def _read_records(self, record, instances, kind):
-        raw = record.download(instances * C.sizeof(kind) // 4, 1)
-        return list((kind * instances).from_buffer_copy(raw.tobytes()))
+        return self._record_plane(CORRELATION_PASS_RECORD_BYTES, instances)
 
     def read_correlation_pass_record(self, record, instances=1):
         """The records of a pass_records Plane as CorrelationPassRecord structures (synchronises)."""
@@ -1229,7 +1229,7 @@ class Context:
 
     def subset_records(self, instances=1):
         """A Plane for `instances` flow2d_subset_record records (device memory)."""
-        return self.plane(instances * SUBSET_RECORD_BYTES // 4, 1)
+        return self._record_plane(SUBSET_RECORD_BYTES, instances)
 
     def read_subset_record(self, record, instances=1):
         """The records of a subset_records Plane as SubsetRecord structures (synchronises)."""
@@ -1312,7 +1312,7 @@ class Context:
 
     def predict_records(self, instances=1):
         """A Plane for `instances` flow2d_predict_record records (device memory)."""
-        return self.plane(instances * PREDICT_RECORD_BYTES // 4, 1)
+        return self._record_plane(PREDICT_RECORD_BYTES, instances)
 
     def read_predict_record(self, record, instances=1):
         """The records of a predict_records Plane as PredictRecord structures (synchronises)."""
@@ -1430,11 +1430,11 @@ class Context:
 
     def prior_records(self, instances=1):
         """A Plane for the `instances` counts (one unsigned 64-bit integer each) of prior_registration, device memory."""
-        return self.plane(max(2 * instances, 4), 1)
+        return self._record_plane(8, instances, 4)
 
     def read_prior_records(self, record, instances=1):
         """The counts of a prior_records Plane as a list of ints (synchronises)."""
-        return [int(c) for c in record.download(max(2 * instances, 4), 1).view(np.uint64)[0, :instances]]
+        return self._read_records(record, instances, C.c_uint64)
 
     def prior_registration(self, prior_u, prior_v, in_w, in_h, out_u, out_v, f0, f1, w, h, hx, hy, out, record=True):
         """The first level of a pyramid started from a prior flow (flow2d_prior_registration_2d): the in_w x in_h prior (prior_u,
@@ -1456,12 +1456,11 @@ class Context:
 
     def propagate_records(self, instances=1):
         """A Plane for `instances` flow2d_propagate_record records (device memory)."""
-        return self.plane(max(instances * PROPAGATE_RECORD_BYTES // 4, 4), 1)
+        return self._record_plane(PROPAGATE_RECORD_BYTES, instances, 4)
 
     def read_propagate_record(self, record, instances=1):
         """The records of a propagate_records Plane as PropagateRecord structures (synchronises)."""
-        raw = record.download(instances * PROPAGATE_RECORD_BYTES // 4, 1)
-        return list((PropagateRecord * instances).from_buffer_copy(raw.tobytes()))
+        return self._read_records(record, instances, PropagateRecord)
 
     def propagate_workspace(self, w, h, instances=1):
         """A Plane of flow2d_propagate_flow_workspace_bytes(w, h, instances) bytes (device memory)."""

@@ -28,7 +28,7 @@
 #include <cmath>
 
 #include "correlate_score.hpp"
-#include "ordered_reduce.hpp"
+#include "node_grid.hpp"
 #include "plane_sample.hpp"
 
 namespace {
@@ -149,18 +149,15 @@ __global__ __launch_bounds__(kCorrThreads) void correlate_kernel(CorrArgs a, Bat
         n_rejected += res.rejected;
         n_unrefined += res.found && !res.rejected && !res.refined;
         if (lane == 0) {
-            const size_t at = inst + static_cast<size_t>(j_first + jn) * static_cast<size_t>(a.npitch) + static_cast<size_t>(i_first + in);
+            const size_t at = node_at(inst, i_first + in, j_first + jn, a.npitch);
             a.nu[at] = res.u;
             a.nv[at] = res.v;
             if (a.ns) a.ns[at] = res.score;
         }
     }
     if (a.record && lane == 0) {
-        unsigned long long* rec = a.record + 4 * static_cast<size_t>(blockIdx.z);
         const unsigned counts[4] = {n_nodes, n_invalid, n_rejected, n_unrefined};
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (counts[k]) atomicAdd(rec + k, static_cast<unsigned long long>(counts[k]));
+        add_counts<4>(a.record, blockIdx.z, counts);
     }
 }
 
@@ -199,23 +196,16 @@ __global__ __launch_bounds__(flow2d::kPixelBlockX* flow2d::kPixelBlockY) void ex
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const float u = load_at(nu, at[k]), v = load_at(nv, at[k]);
-            if (fabsf(u) < INFINITY && fabsf(v) < INFINITY) {
+            if (finite(u) && finite(v)) {
                 sw += wt[k];
                 su += wt[k] * u;
                 sv += wt[k] * v;
             }
         }
-        const float nan = __uint_as_float(0x7FC00000u);
         const Offset o = pixel_offset<Offset>(x, y, a.pitch);
-        store_at(a.u_out + inst, o, sw > 0.f ? su / sw : nan);
-        store_at(a.v_out + inst, o, sw > 0.f ? sv / sw : nan);
+        store_at(a.u_out + inst, o, sw > 0.f ? su / sw : quiet_nan());
+        store_at(a.v_out + inst, o, sw > 0.f ? sv / sw : quiet_nan());
     }
-}
-
-bool grid_ok(size_t width, size_t height, int radius, int spacing)
-{
-    return radius >= 1 && radius <= FLOW2D_CORRELATION_MAX_RADIUS && spacing >= 1 && spacing <= FLOW2D_CORRELATION_MAX_SPACING &&
-           width >= static_cast<size_t>(2 * radius + 1) && height >= static_cast<size_t>(2 * radius + 1);
 }
 
 }  // namespace
@@ -224,9 +214,9 @@ extern "C" {
 
 int flow2d_correlation_grid(size_t width, size_t height, int radius, int spacing, size_t* nw, size_t* nh)
 {
-    if (!nw || !nh || !grid_ok(width, height, radius, spacing)) return FLOW2D_ERR_INVALID_ARGUMENT;
-    *nw = (width - 2 * radius - 1) / spacing + 1;
-    *nh = (height - 2 * radius - 1) / spacing + 1;
+    if (!nw || !nh || !flow2d::correlation_grid_ok(width, height, radius, spacing)) return FLOW2D_ERR_INVALID_ARGUMENT;
+    *nw = flow2d::correlation_nodes(width, radius, spacing);
+    *nh = flow2d::correlation_nodes(height, radius, spacing);
     return FLOW2D_OK;
 }
 
@@ -236,16 +226,13 @@ int flow2d_correlate_2d(flow2d_context* ctx, const float* frame_0, const float* 
 {
     if (ctx == nullptr) return FLOW2D_ERR_INVALID_ARGUMENT;
     // (every check that needs no context field comes first: they hold without a device)
-    if (!flow2d::plane_args_ok(frame_0, width, height, pitch_bytes) || !flow2d::plane_args_ok(frame_1, width, height, pitch_bytes))
-        return FLOW2D_ERR_INVALID_ARGUMENT;
-    if (!grid_ok(width, height, radius, spacing) || range < 1 || range > FLOW2D_CORRELATION_MAX_RANGE)
+    if (!flow2d::planes_ok({frame_0, frame_1}, {}, width, height, pitch_bytes)) return FLOW2D_ERR_INVALID_ARGUMENT;
+    if (!flow2d::correlation_grid_ok(width, height, radius, spacing) || range < 1 || range > FLOW2D_CORRELATION_MAX_RANGE)
         return FLOW2D_ERR_INVALID_ARGUMENT;
     if (!(std::isfinite(scale) && scale > 0.f) || !std::isfinite(lo) || std::isnan(min_score)) return FLOW2D_ERR_INVALID_ARGUMENT;
-    const size_t nw = (width - 2 * radius - 1) / spacing + 1, nh = (height - 2 * radius - 1) / spacing + 1;
-    if (!flow2d::plane_args_ok(node_u, nw, nh, node_pitch_bytes) || !flow2d::plane_args_ok(node_v, nw, nh, node_pitch_bytes) ||
-        (node_score && !flow2d::plane_args_ok(node_score, nw, nh, node_pitch_bytes)))
+    const size_t nw = flow2d::correlation_nodes(width, radius, spacing), nh = flow2d::correlation_nodes(height, radius, spacing);
+    if (!flow2d::planes_ok({node_u, node_v}, {node_score}, nw, nh, node_pitch_bytes) || !flow2d::record_aligned(record))
         return FLOW2D_ERR_INVALID_ARGUMENT;
-    if ((reinterpret_cast<uintptr_t>(record) % alignof(flow2d_correlation_record)) != 0) return FLOW2D_ERR_INVALID_ARGUMENT;
     // the kernel marks the frames __restrict__: no written byte range may meet a frame or another written one
     auto aliased = [&](size_t frame_span, size_t node_span, size_t instances) {
         const flow2d::ByteRange written[] = {{node_u, node_span}, {node_v, node_span}, {node_score, node_span},
@@ -258,7 +245,7 @@ int flow2d_correlate_2d(flow2d_context* ctx, const float* frame_0, const float* 
     const size_t instances = ctx->batch_count;
     if (aliased(flow2d::batch_span(ctx, height * pitch_bytes), flow2d::batch_span(ctx, nh * node_pitch_bytes), instances))
         return FLOW2D_ERR_INVALID_ARGUMENT;
-    if (record) FLOW2D_HIP_TRY(hipMemsetAsync(record, 0, instances * sizeof(flow2d_correlation_record), ctx->stream));
+    FLOW2D_HIP_TRY(flow2d::clear_records(ctx, record));
     const int tile = corr_tile_nodes(spacing);
     const unsigned tiles_x = flow2d::div_up(nw, tile), tiles_y = flow2d::div_up(nh, tile);
     const CorrArgs a = {frame_0, frame_1, node_u, node_v, node_score, reinterpret_cast<unsigned long long*>(record),
@@ -278,8 +265,7 @@ int flow2d_expand_nodes_2d(flow2d_context* ctx, const float* node_u, const float
                            int radius, int spacing, float* out_u, float* out_v, size_t width, size_t height, size_t pitch_bytes)
 {
     if (ctx == nullptr) return FLOW2D_ERR_INVALID_ARGUMENT;
-    if (!flow2d::plane_args_ok(node_u, nw, nh, node_pitch_bytes) || !flow2d::plane_args_ok(node_v, nw, nh, node_pitch_bytes) ||
-        !flow2d::plane_args_ok(out_u, width, height, pitch_bytes) || !flow2d::plane_args_ok(out_v, width, height, pitch_bytes))
+    if (!flow2d::planes_ok({node_u, node_v}, {}, nw, nh, node_pitch_bytes) || !flow2d::planes_ok({out_u, out_v}, {}, width, height, pitch_bytes))
         return FLOW2D_ERR_INVALID_ARGUMENT;
     if (radius < 0 || radius > FLOW2D_CORRELATION_MAX_RADIUS || spacing < 1 || spacing > FLOW2D_CORRELATION_MAX_SPACING)
         return FLOW2D_ERR_INVALID_ARGUMENT;

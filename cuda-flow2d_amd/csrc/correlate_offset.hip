@@ -23,7 +23,7 @@
 #include <cmath>
 
 #include "correlate_score.hpp"
-#include "ordered_reduce.hpp"
+#include "node_grid.hpp"
 #include "plane_sample.hpp"
 
 namespace {
@@ -32,7 +32,6 @@ constexpr int kOffsetThreads = 256, kOffsetWaves = 4;
 constexpr int kValidateThreads = 256;
 constexpr int kPassCounts = 6;      // the counts of flow2d_correlation_pass_record that are written
 constexpr int kValidateCounts = 6;  // ... of flow2d_validation_record
-constexpr int kRecordWords = 8;     // both records: 64 bytes
 
 inline unsigned patch_bytes(int side) { return (static_cast<unsigned>(side * side) + 8u + 15u) & ~15u; }
 
@@ -74,7 +73,7 @@ __global__ __launch_bounds__(kOffsetThreads) void correlate_offset_kernel(Offset
     if (active && a.pu) {
         const Offset at = pixel_offset<Offset>(left + a.r, top + a.r, a.pitch);
         const float pu = load_at(a.pu + inst, at), pv = load_at(a.pv + inst, at);
-        if (fabsf(pu) < INFINITY && fabsf(pv) < INFINITY) {
+        if (finite(pu) && finite(pv)) {
             ox = node_offset(pu);
             oy = node_offset(pv);
         } else {
@@ -135,16 +134,13 @@ __global__ __launch_bounds__(kOffsetThreads) void correlate_offset_kernel(Offset
     }
     const CorrResult res = finish_node(nd, d, lane, best, bx, by, ox, oy, a.min_score);
     if (lane != 0) return;
-    const size_t at = inst + static_cast<size_t>(jn) * static_cast<size_t>(a.npitch) + static_cast<size_t>(in);
+    const size_t at = node_at(inst, in, jn, a.npitch);
     a.nu[at] = res.u;
     a.nv[at] = res.v;
     if (a.ns) a.ns[at] = res.score;
     if (a.record) {
-        unsigned long long* rec = a.record + kRecordWords * static_cast<size_t>(blockIdx.z);
         const unsigned counts[kPassCounts] = {1u, !res.found, res.rejected, res.found && !res.rejected && !res.refined, unpredicted, scored};
-#pragma unroll
-        for (int k = 0; k < kPassCounts; ++k)
-            if (counts[k]) atomicAdd(rec + k, static_cast<unsigned long long>(counts[k]));
+        add_counts<kCountRecordWords>(a.record, blockIdx.z, counts);
     }
 }
 
@@ -208,23 +204,24 @@ __global__ __launch_bounds__(kValidateThreads) void validate_kernel(ValidateArgs
         int k = 0;
 #pragma unroll
         for (int n = 0; n < 8; ++n) {
-            const int m = n < 4 ? n : n + 1;  // the ring: the 3 x 3 block without its centre, row by row
-            const int x = i + m % 3 - 1, y = j + m / 3 - 1;
+            int dx, dy;
+            ring_neighbour(n, dx, dy);
+            const int x = i + dx, y = j + dy;
             ku[n] = INT_MAX;
             kv[n] = INT_MAX;
             if (x >= 0 && y >= 0 && x < a.nw && y < a.nh) {
-                const size_t at = static_cast<size_t>(y) * static_cast<size_t>(a.npitch) + static_cast<size_t>(x);
+                const size_t at = node_at(0, x, y, a.npitch);
                 const float u = nu[at], v = nv[at];
-                if (fabsf(u) < INFINITY && fabsf(v) < INFINITY) {
+                if (finite(u) && finite(v)) {
                     ku[n] = float_key(u);
                     kv[n] = float_key(v);
                     k += 1;
                 }
             }
         }
-        const size_t at = static_cast<size_t>(j) * static_cast<size_t>(a.npitch) + static_cast<size_t>(i);
+        const size_t at = node_at(0, i, j, a.npitch);
         const float u = nu[at], v = nv[at];
-        const bool valid = fabsf(u) < INFINITY && fabsf(v) < INFINITY;
+        const bool valid = finite(u) && finite(v);
         float out_u = u, out_v = v, flag = 0.f;
         counts[0] = 1;
         if (k < a.min_neighbours) {
@@ -247,8 +244,8 @@ __global__ __launch_bounds__(kValidateThreads) void validate_kernel(ValidateArgs
                 if (tu > a.threshold || tv > a.threshold) {
                     counts[2] = 1;
                     flag = 1.f;
-                    out_u = a.replace ? mu : __uint_as_float(0x7FC00000u);
-                    out_v = a.replace ? mv : __uint_as_float(0x7FC00000u);
+                    out_u = a.replace ? mu : quiet_nan();
+                    out_v = a.replace ? mv : quiet_nan();
                 }
             } else if (a.replace) {
                 counts[3] = 1;
@@ -257,26 +254,12 @@ __global__ __launch_bounds__(kValidateThreads) void validate_kernel(ValidateArgs
                 out_v = mv;
             }
         }
-        counts[5] = !(fabsf(out_u) < INFINITY && fabsf(out_v) < INFINITY);
+        counts[5] = !(finite(out_u) && finite(out_v));
         a.ou[inst + at] = out_u;
         a.ov[inst + at] = out_v;
         if (a.flag) a.flag[inst + at] = flag;
     }
-    if (!a.record) return;
-#pragma unroll
-    for (int n = 0; n < kValidateCounts; ++n) counts[n] = wave_sum(counts[n]);
-    if (lane == 0) {
-        unsigned long long* rec = a.record + kRecordWords * static_cast<size_t>(blockIdx.z);
-#pragma unroll
-        for (int n = 0; n < kValidateCounts; ++n)
-            if (counts[n]) atomicAdd(rec + n, static_cast<unsigned long long>(counts[n]));
-    }
-}
-
-bool offset_grid_ok(size_t width, size_t height, int radius, int spacing)
-{
-    return radius >= 1 && radius <= FLOW2D_CORRELATION_MAX_RADIUS && spacing >= 1 && spacing <= FLOW2D_CORRELATION_MAX_SPACING &&
-           width >= static_cast<size_t>(2 * radius + 1) && height >= static_cast<size_t>(2 * radius + 1);
+    if (a.record) add_wave_counts<kCountRecordWords>(a.record, blockIdx.z, lane, counts);
 }
 
 }  // namespace
@@ -290,21 +273,15 @@ int flow2d_correlate_offset_2d(flow2d_context* ctx, const float* frame_0, const 
 {
     if (ctx == nullptr) return FLOW2D_ERR_INVALID_ARGUMENT;
     // (every check that needs no context field comes first: they hold without a device)
-    if (!flow2d::plane_args_ok(frame_0, width, height, pitch_bytes) || !flow2d::plane_args_ok(frame_1, width, height, pitch_bytes))
-        return FLOW2D_ERR_INVALID_ARGUMENT;
     if ((predictor_u == nullptr) != (predictor_v == nullptr)) return FLOW2D_ERR_INVALID_ARGUMENT;
-    if (predictor_u && (!flow2d::plane_args_ok(predictor_u, width, height, pitch_bytes) ||
-                        !flow2d::plane_args_ok(predictor_v, width, height, pitch_bytes)))
-        return FLOW2D_ERR_INVALID_ARGUMENT;
-    if (!offset_grid_ok(width, height, radius, spacing) || range < 1 || range > FLOW2D_CORRELATION_MAX_RANGE)
+    if (!flow2d::planes_ok({frame_0, frame_1}, {predictor_u, predictor_v}, width, height, pitch_bytes)) return FLOW2D_ERR_INVALID_ARGUMENT;
+    if (!flow2d::correlation_grid_ok(width, height, radius, spacing) || range < 1 || range > FLOW2D_CORRELATION_MAX_RANGE)
         return FLOW2D_ERR_INVALID_ARGUMENT;
     if (!(std::isfinite(scale) && scale > 0.f) || !std::isfinite(lo) || std::isnan(min_score)) return FLOW2D_ERR_INVALID_ARGUMENT;
-    const size_t nw = (width - 2 * radius - 1) / spacing + 1, nh = (height - 2 * radius - 1) / spacing + 1;
-    if (nw * nh >= (size_t(1) << 31)) return FLOW2D_ERR_UNSUPPORTED;  // (the kernel numbers the nodes in 32 bits)
-    if (!flow2d::plane_args_ok(node_u, nw, nh, node_pitch_bytes) || !flow2d::plane_args_ok(node_v, nw, nh, node_pitch_bytes) ||
-        (node_score && !flow2d::plane_args_ok(node_score, nw, nh, node_pitch_bytes)))
+    const size_t nw = flow2d::correlation_nodes(width, radius, spacing), nh = flow2d::correlation_nodes(height, radius, spacing);
+    if (!flow2d::node_count_ok(nw, nh)) return FLOW2D_ERR_UNSUPPORTED;
+    if (!flow2d::planes_ok({node_u, node_v}, {node_score}, nw, nh, node_pitch_bytes) || !flow2d::record_aligned(record))
         return FLOW2D_ERR_INVALID_ARGUMENT;
-    if ((reinterpret_cast<uintptr_t>(record) % alignof(flow2d_correlation_pass_record)) != 0) return FLOW2D_ERR_INVALID_ARGUMENT;
     // the kernel marks the frames __restrict__: no written byte range may meet a plane that is read or another written one
     auto aliased = [&](size_t frame_span, size_t node_span, size_t instances) {
         const flow2d::ByteRange written[] = {{node_u, node_span}, {node_v, node_span}, {node_score, node_span},
@@ -317,7 +294,7 @@ int flow2d_correlate_offset_2d(flow2d_context* ctx, const float* frame_0, const 
     const size_t instances = ctx->batch_count;
     if (aliased(flow2d::batch_span(ctx, height * pitch_bytes), flow2d::batch_span(ctx, nh * node_pitch_bytes), instances))
         return FLOW2D_ERR_INVALID_ARGUMENT;
-    if (record) FLOW2D_HIP_TRY(hipMemsetAsync(record, 0, instances * sizeof(flow2d_correlation_pass_record), ctx->stream));
+    FLOW2D_HIP_TRY(flow2d::clear_records(ctx, record));
     const int side = 2 * radius + 1;
     const unsigned patch0 = patch_bytes(side), wave_bytes = patch0 + patch_bytes(side + 2 * range);  // at most 976 + 9040
     const OffsetArgs a = {frame_0, frame_1, predictor_u, predictor_v, node_u, node_v, node_score,
@@ -340,15 +317,12 @@ int flow2d_validate_nodes_2d(flow2d_context* ctx, const float* node_u, const flo
                              float* out_v, float* out_flag, flow2d_validation_record* record)
 {
     if (ctx == nullptr) return FLOW2D_ERR_INVALID_ARGUMENT;
-    if (!flow2d::plane_args_ok(node_u, nw, nh, node_pitch_bytes) || !flow2d::plane_args_ok(node_v, nw, nh, node_pitch_bytes) ||
-        !flow2d::plane_args_ok(out_u, nw, nh, node_pitch_bytes) || !flow2d::plane_args_ok(out_v, nw, nh, node_pitch_bytes) ||
-        (out_flag && !flow2d::plane_args_ok(out_flag, nw, nh, node_pitch_bytes)))
-        return FLOW2D_ERR_INVALID_ARGUMENT;
+    if (!flow2d::planes_ok({node_u, node_v, out_u, out_v}, {out_flag}, nw, nh, node_pitch_bytes)) return FLOW2D_ERR_INVALID_ARGUMENT;
     if (min_neighbours < 1 || min_neighbours > 8 || !(std::isfinite(threshold) && threshold > 0.f) ||
         !(std::isfinite(epsilon) && epsilon > 0.f) || (mode != FLOW2D_VALIDATE_FLAG && mode != FLOW2D_VALIDATE_REPLACE))
         return FLOW2D_ERR_INVALID_ARGUMENT;
-    if ((reinterpret_cast<uintptr_t>(record) % alignof(flow2d_validation_record)) != 0) return FLOW2D_ERR_INVALID_ARGUMENT;
-    if (nw * nh >= (size_t(1) << 31)) return FLOW2D_ERR_UNSUPPORTED;  // (the kernel numbers the nodes in 32 bits)
+    if (!flow2d::record_aligned(record)) return FLOW2D_ERR_INVALID_ARGUMENT;
+    if (!flow2d::node_count_ok(nw, nh)) return FLOW2D_ERR_UNSUPPORTED;
     auto aliased = [&](size_t span, size_t instances) {
         const flow2d::ByteRange written[] = {{out_u, span}, {out_v, span}, {out_flag, span},
                                              {record, instances * sizeof(flow2d_validation_record)}};
@@ -359,7 +333,7 @@ int flow2d_validate_nodes_2d(flow2d_context* ctx, const float* node_u, const flo
     FLOW2D_ENTER(ctx);
     const size_t instances = ctx->batch_count;
     if (aliased(flow2d::batch_span(ctx, nh * node_pitch_bytes), instances)) return FLOW2D_ERR_INVALID_ARGUMENT;
-    if (record) FLOW2D_HIP_TRY(hipMemsetAsync(record, 0, instances * sizeof(flow2d_validation_record), ctx->stream));
+    FLOW2D_HIP_TRY(flow2d::clear_records(ctx, record));
     const ValidateArgs a = {node_u, node_v, out_u, out_v, out_flag, reinterpret_cast<unsigned long long*>(record),
                             static_cast<int>(nw), static_cast<int>(nh), static_cast<int>(node_pitch_bytes / 4),
                             threshold, epsilon, min_neighbours, mode == FLOW2D_VALIDATE_REPLACE ? 1 : 0};

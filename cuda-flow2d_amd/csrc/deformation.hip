@@ -19,55 +19,17 @@
 #include <cfloat>
 #include <cmath>
 
-#include "ordered_reduce.hpp"
+#include "node_grid.hpp"
 #include "plane_sample.hpp"
+#include "strain_sums.hpp"
 
 namespace {
 
 constexpr int kDeformRows = 4;  // consecutive rows per thread
 constexpr int kBlockCols = flow2d::kPixelBlockX;                 // 64
 constexpr int kBlockRows = flow2d::kPixelBlockY * kDeformRows;   // 16
-constexpr int kFinalThreads = 256;
-constexpr int kQuantities = 6;  // divergence, vorticity, dilatation, e1, e2, max_shear: the order of the record
 
 enum Set { kFirstOrder = 0, kStrain = 1, kPrincipal = 2 };
-
-struct DeformSums {
-    double sum[kQuantities], sum_sq[kQuantities];
-    float min[kQuantities], max[kQuantities];
-    unsigned long long valid, invalid;
-
-    __device__ __forceinline__ void combine(const DeformSums& q)
-    {
-#pragma unroll
-        for (int k = 0; k < kQuantities; ++k) {
-            sum[k] += q.sum[k];
-            sum_sq[k] += q.sum_sq[k];
-            min[k] = q.min[k] < min[k] ? q.min[k] : min[k];
-            max[k] = q.max[k] > max[k] ? q.max[k] : max[k];
-        }
-        valid += q.valid;
-        invalid += q.invalid;
-    }
-    __device__ __forceinline__ void across_lanes()
-    {
-#pragma unroll
-        for (int k = 0; k < kQuantities; ++k) {
-            sum[k] = wave_sum(sum[k]);
-            sum_sq[k] = wave_sum(sum_sq[k]);
-            // (no NaN ever enters min / max: x < min and x > max are false for one)
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                const float a = __shfl_xor(min[k], o, 64), b = __shfl_xor(max[k], o, 64);
-                min[k] = a < min[k] ? a : min[k];
-                max[k] = b > max[k] ? b : max[k];
-            }
-        }
-        valid = wave_sum(valid);
-        invalid = wave_sum(invalid);
-    }
-};
-static_assert(sizeof(DeformSums) % 16 == 0, "slabs stay 16-byte aligned");
 
 struct DeformArgs {
     const float *u, *v, *mask;
@@ -94,7 +56,7 @@ __global__ __launch_bounds__(256) void deformation_kernel(DeformArgs in, float* 
                                                           float* __restrict__ o_dil, float* __restrict__ o_exx,
                                                           float* __restrict__ o_eyy, float* __restrict__ o_exy,
                                                           float* __restrict__ o_e1, float* __restrict__ o_e2,
-                                                          float* __restrict__ o_shear, DeformSums* __restrict__ partials,
+                                                          float* __restrict__ o_shear, StrainSums* __restrict__ partials,
                                                           BatchArg batch)
 {
     static_assert(!Stats || kSet == kPrincipal, "the record holds the principal strains");
@@ -106,14 +68,8 @@ __global__ __launch_bounds__(256) void deformation_kernel(DeformArgs in, float* 
     const int gx = pixel_column();
     const int y0 = (blockIdx.y * flow2d::kPixelBlockY + threadIdx.y) * kDeformRows;
 
-    DeformSums acc;
-#pragma unroll
-    for (int k = 0; k < kQuantities; ++k) {
-        acc.sum[k] = acc.sum_sq[k] = 0.0;
-        acc.min[k] = INFINITY;
-        acc.max[k] = -INFINITY;
-    }
-    acc.valid = acc.invalid = 0;
+    StrainSums acc;
+    acc.clear();
 
     if (gx < w && y0 < h) {
         // every index is clamped into the frame before it is loaded: what lies outside is not ok and is selected away
@@ -180,12 +136,12 @@ __global__ __launch_bounds__(256) void deformation_kernel(DeformArgs in, float* 
             constexpr int kPlanes = kSet == kFirstOrder ? 3 : kSet == kStrain ? 6 : 9;
 #pragma unroll
             for (int k = 0; k < kPlanes; ++k)
-                if (planes[k]) store_at(planes[k] + inst, o, valid ? q[k] : __builtin_nanf(""));
+                if (planes[k]) store_at(planes[k] + inst, o, valid ? q[k] : quiet_nan());
             if (Stats) {
                 // predicated, not branched; adding +0.0 leaves a sum's bits as they are (the sums start at +0 and never become -0)
-                const float x[kQuantities] = {q[0], q[1], q[2], q[6], q[7], q[8]};
+                const float x[kStrainQuantities] = {q[0], q[1], q[2], q[6], q[7], q[8]};
 #pragma unroll
-                for (int k = 0; k < kQuantities; ++k) {
+                for (int k = 0; k < kStrainQuantities; ++k) {
                     const double t = valid ? static_cast<double>(x[k]) : 0.0;
                     acc.sum[k] += t;
                     acc.sum_sq[k] += t * t;
@@ -204,40 +160,13 @@ __global__ __launch_bounds__(256) void deformation_kernel(DeformArgs in, float* 
     }
 }
 
-// One workgroup per instance: thread t sums slabs t, t + 256, ... in order, then the reduction of ordered_reduce.hpp.
-__global__ __launch_bounds__(kFinalThreads) void deformation_final_kernel(const DeformSums* __restrict__ partials, unsigned blocks,
-                                                                          flow2d_deformation_stats* __restrict__ stats)
-{
-    const DeformSums* slab = partials + static_cast<size_t>(blockIdx.x) * blocks;
-    DeformSums t;
-    for (int k = 0; k < kQuantities; ++k) {
-        t.sum[k] = t.sum_sq[k] = 0.0;
-        t.min[k] = INFINITY;
-        t.max[k] = -INFINITY;
-    }
-    t.valid = t.invalid = 0;
-    for (unsigned j = threadIdx.x; j < blocks; j += kFinalThreads) t.combine(slab[j]);
-    if (!workgroup_reduce<kFinalThreads / 64>(t, threadIdx.x % 64, threadIdx.x / 64)) return;
-    flow2d_deformation_stats rec = {};
-    rec.valid = t.valid;
-    rec.invalid = t.invalid;
-    flow2d_deformation_moments* m[kQuantities] = {&rec.divergence, &rec.vorticity, &rec.dilatation, &rec.e1, &rec.e2, &rec.max_shear};
-    for (int k = 0; k < kQuantities; ++k) {
-        m[k]->sum = t.sum[k];
-        m[k]->sum_sq = t.sum_sq[k];
-        m[k]->min = t.valid ? t.min[k] : 0.f;
-        m[k]->max = t.valid ? t.max[k] : 0.f;
-    }
-    stats[blockIdx.x] = rec;
-}
-
 inline size_t partial_blocks(size_t width, size_t height)
 {
     return static_cast<size_t>(flow2d::div_up(width, kBlockCols)) * flow2d::div_up(height, kBlockRows);
 }
 
 template <typename Offset, bool HasMask, int kSet, bool Stats>
-void launch_set(flow2d_context* ctx, const DeformArgs& in, const flow2d_deformation_planes& p, DeformSums* partials, size_t width,
+void launch_set(flow2d_context* ctx, const DeformArgs& in, const flow2d_deformation_planes& p, StrainSums* partials, size_t width,
                 size_t height)
 {
     deformation_kernel<Offset, HasMask, kSet, Stats>
@@ -247,7 +176,7 @@ void launch_set(flow2d_context* ctx, const DeformArgs& in, const flow2d_deformat
 }
 
 template <typename Offset, bool HasMask>
-void launch_mask(flow2d_context* ctx, const DeformArgs& in, const flow2d_deformation_planes& p, DeformSums* partials, size_t width,
+void launch_mask(flow2d_context* ctx, const DeformArgs& in, const flow2d_deformation_planes& p, StrainSums* partials, size_t width,
                  size_t height)
 {
     if (partials)
@@ -267,7 +196,7 @@ extern "C" {
 size_t flow2d_deformation_workspace_bytes(size_t width, size_t height, size_t instances)
 {
     if (width == 0 || height == 0 || instances == 0) return 0;
-    return partial_blocks(width, height) * instances * sizeof(DeformSums);
+    return partial_blocks(width, height) * instances * sizeof(StrainSums);
 }
 
 int flow2d_deformation_2d(flow2d_context* ctx, const float* flow_u, const float* flow_v, const float* mask, size_t width,
@@ -276,22 +205,18 @@ int flow2d_deformation_2d(flow2d_context* ctx, const float* flow_u, const float*
 {
     if (ctx == nullptr) return FLOW2D_ERR_INVALID_ARGUMENT;
     // (every check that needs no context field comes first: they hold without a device)
-    if (!flow2d::plane_args_ok(flow_u, width, height, pitch_bytes) || !flow2d::plane_args_ok(flow_v, width, height, pitch_bytes) ||
-        (mask && !flow2d::plane_args_ok(mask, width, height, pitch_bytes)))
+    const flow2d_deformation_planes p = out ? *out : flow2d_deformation_planes{};
+    float* const planes[9] = {p.divergence, p.vorticity, p.dilatation, p.exx, p.eyy, p.exy, p.e1, p.e2, p.max_shear};
+    if (!flow2d::planes_ok({flow_u, flow_v},
+                           {mask, planes[0], planes[1], planes[2], planes[3], planes[4], planes[5], planes[6], planes[7], planes[8]},
+                           width, height, pitch_bytes))
         return FLOW2D_ERR_INVALID_ARGUMENT;
     if (width < 2 || height < 2) return FLOW2D_ERR_INVALID_ARGUMENT;  // no derivative exists
     if (measure != FLOW2D_STRAIN_SMALL && measure != FLOW2D_STRAIN_GREEN_LAGRANGE) return FLOW2D_ERR_INVALID_ARGUMENT;
-    const flow2d_deformation_planes p = out ? *out : flow2d_deformation_planes{};
-    float* const planes[9] = {p.divergence, p.vorticity, p.dilatation, p.exx, p.eyy, p.exy, p.e1, p.e2, p.max_shear};
     bool any = stats != nullptr;
-    for (float* q : planes) {
-        if (q && !flow2d::plane_args_ok(q, width, height, pitch_bytes)) return FLOW2D_ERR_INVALID_ARGUMENT;
-        any = any || q != nullptr;
-    }
+    for (float* q : planes) any = any || q != nullptr;
     if (!any) return FLOW2D_ERR_INVALID_ARGUMENT;
-    if ((reinterpret_cast<uintptr_t>(stats) % alignof(flow2d_deformation_stats)) != 0 ||
-        (reinterpret_cast<uintptr_t>(workspace) % 16) != 0)
-        return FLOW2D_ERR_INVALID_ARGUMENT;
+    if (!flow2d::record_aligned(stats) || (reinterpret_cast<uintptr_t>(workspace) % 16) != 0) return FLOW2D_ERR_INVALID_ARGUMENT;
     if (stats && (!workspace || workspace_bytes < flow2d_deformation_workspace_bytes(width, height, 1)))
         return FLOW2D_ERR_INVALID_ARGUMENT;
     // the kernel marks every plane __restrict__: no written byte range may meet a read one or another written one.  Without
@@ -311,7 +236,7 @@ int flow2d_deformation_2d(flow2d_context* ctx, const float* flow_u, const float*
     if (aliased(flow2d::batch_span(ctx, height * pitch_bytes), instances)) return FLOW2D_ERR_INVALID_ARGUMENT;
     const DeformArgs in = {flow_u, flow_v, mask, static_cast<int>(width), static_cast<int>(height),
                            static_cast<int>(pitch_bytes / 4), measure};
-    DeformSums* partials = stats ? static_cast<DeformSums*>(workspace) : nullptr;
+    StrainSums* partials = stats ? static_cast<StrainSums*>(workspace) : nullptr;
     // (the largest offset a lane forms is below height * pitch_bytes)
     flow2d::launch_by_span(height * pitch_bytes, [&](auto offset) {
         using Offset = decltype(offset);
@@ -322,7 +247,7 @@ int flow2d_deformation_2d(flow2d_context* ctx, const float* flow_u, const float*
     });
     FLOW2D_CHECK_LAUNCH();
     if (stats) {
-        deformation_final_kernel<<<dim3(static_cast<unsigned>(instances)), dim3(kFinalThreads), 0, ctx->stream>>>(
+        strain_final_kernel<<<dim3(static_cast<unsigned>(instances)), dim3(kStrainFinalThreads), 0, ctx->stream>>>(
             partials, static_cast<unsigned>(partial_blocks(width, height)), stats);
         FLOW2D_CHECK_LAUNCH();
     }

@@ -19,8 +19,10 @@
 #include <cfloat>
 #include <cmath>
 
-#include "ordered_reduce.hpp"
+#include "node_grid.hpp"
 #include "plane_sample.hpp"
+#include "small_cholesky.hpp"
+#include "strain_sums.hpp"
 
 namespace {
 
@@ -28,66 +30,41 @@ constexpr int kMaxWindow = FLOW2D_NODE_STRAIN_MAX_WINDOW;
 constexpr int kTileW = flow2d::kPixelBlockX + 2 * kMaxWindow;  // 78
 constexpr int kTileH = flow2d::kPixelBlockY + 2 * kMaxWindow;  // 18
 constexpr int kThreads = flow2d::kPixelBlockX * flow2d::kPixelBlockY;
-constexpr int kFinalThreads = 256;
-constexpr int kQuantities = 6;  // divergence, vorticity, dilatation, e1, e2, max_shear: the order of the record
 constexpr int kReasons = 3;     // centre, sparse, degenerate: reserved[0 .. 2] of the record
 
 enum Reason { kValid = -1, kCentre = 0, kSparse = 1, kDegenerate = 2 };
 
-struct StrainSums {
-    double sum[kQuantities], sum_sq[kQuantities];
-    float min[kQuantities], max[kQuantities];
-    unsigned long long valid, invalid;
+// StrainSums with the counts of the three reasons a node has no strain.
+struct NodeStrainSums : StrainSums {
     unsigned long long reasons[kReasons];
     unsigned long long pad;
 
     __device__ __forceinline__ void clear()
     {
-#pragma unroll
-        for (int k = 0; k < kQuantities; ++k) {
-            sum[k] = sum_sq[k] = 0.0;
-            min[k] = INFINITY;
-            max[k] = -INFINITY;
-        }
-        valid = invalid = pad = 0;
+        StrainSums::clear();
+        pad = 0;
 #pragma unroll
         for (int k = 0; k < kReasons; ++k) reasons[k] = 0;
     }
-    __device__ __forceinline__ void combine(const StrainSums& q)
+    __device__ __forceinline__ void combine(const NodeStrainSums& q)
     {
-#pragma unroll
-        for (int k = 0; k < kQuantities; ++k) {
-            sum[k] += q.sum[k];
-            sum_sq[k] += q.sum_sq[k];
-            min[k] = q.min[k] < min[k] ? q.min[k] : min[k];
-            max[k] = q.max[k] > max[k] ? q.max[k] : max[k];
-        }
-        valid += q.valid;
-        invalid += q.invalid;
+        StrainSums::combine(q);
 #pragma unroll
         for (int k = 0; k < kReasons; ++k) reasons[k] += q.reasons[k];
     }
     __device__ __forceinline__ void across_lanes()
     {
-#pragma unroll
-        for (int k = 0; k < kQuantities; ++k) {
-            sum[k] = wave_sum(sum[k]);
-            sum_sq[k] = wave_sum(sum_sq[k]);
-            // (no NaN ever enters min / max: x < min and x > max are false for one)
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                const float a = __shfl_xor(min[k], o, 64), b = __shfl_xor(max[k], o, 64);
-                min[k] = a < min[k] ? a : min[k];
-                max[k] = b > max[k] ? b : max[k];
-            }
-        }
-        valid = wave_sum(valid);
-        invalid = wave_sum(invalid);
+        StrainSums::across_lanes();
 #pragma unroll
         for (int k = 0; k < kReasons; ++k) reasons[k] = wave_sum(reasons[k]);
     }
+    __device__ __forceinline__ void fill(flow2d_deformation_stats& rec) const
+    {
+        StrainSums::fill(rec);
+        for (int k = 0; k < kReasons; ++k) rec.reserved[k] = reasons[k];
+    }
 };
-static_assert(sizeof(StrainSums) % 16 == 0, "slabs stay 16-byte aligned");
+static_assert(sizeof(NodeStrainSums) == 192, "flow2d_node_strain_workspace_bytes counts slabs of 192 bytes");
 
 struct StrainArgs {
     const float *u, *v, *state;  // state: null = absent
@@ -97,8 +74,6 @@ struct StrainArgs {
     int s, window, min_nodes, measure;
     float min_state;
 };
-
-__device__ __forceinline__ bool finite(float x) { return fabsf(x) < INFINITY; }
 
 // The nine quantities of the header from the gradients, each cast to float once.
 __device__ __forceinline__ void quantities(double a, double b, double c, double d, int measure, float (&q)[9])
@@ -126,53 +101,9 @@ __device__ __forceinline__ void quantities(double a, double b, double c, double 
 constexpr int exp_i(int a) { return a == 1 || a == 4 ? 1 : a == 3 ? 2 : 0; }
 constexpr int exp_j(int a) { return a == 2 || a == 4 ? 1 : a == 5 ? 2 : 0; }
 
-// Cholesky M = L L^T and the two solves of the header; false where a pivot test fails.  M's lower triangle comes in L.
-template <int K>
-__device__ __forceinline__ bool factor(double (&L)[K][K])
-{
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        const double mkk = L[k][k];
-        double sum = 0.0;
-#pragma unroll
-        for (int m = 0; m < k; ++m) sum += L[k][m] * L[k][m];
-        const double d = mkk - sum;
-        if (!(d > 1e-10 * mkk)) return false;
-        L[k][k] = sqrt(d);
-#pragma unroll
-        for (int i = k + 1; i < K; ++i) {
-            double inner = 0.0;
-#pragma unroll
-            for (int m = 0; m < k; ++m) inner += L[i][m] * L[k][m];
-            L[i][k] = (L[i][k] - inner) / L[k][k];
-        }
-    }
-    return true;
-}
-
-template <int K>
-__device__ __forceinline__ void solve(const double (&L)[K][K], const double (&b)[K], double (&x)[K])
-{
-    double y[K];
-#pragma unroll
-    for (int i = 0; i < K; ++i) {
-        double sum = 0.0;
-#pragma unroll
-        for (int m = 0; m < i; ++m) sum += L[i][m] * y[m];
-        y[i] = (b[i] - sum) / L[i][i];
-    }
-#pragma unroll
-    for (int i = K - 1; i >= 0; --i) {
-        double sum = 0.0;
-#pragma unroll
-        for (int m = i + 1; m < K; ++m) sum += L[m][i] * x[m];
-        x[i] = (y[i] - sum) / L[i][i];
-    }
-}
-
 // Order: 0 = direct (window 0), 1 / 2 = window fit of that order.
 template <int Order, bool Stats>
-__global__ __launch_bounds__(kThreads) void node_strain_kernel(StrainArgs in, StrainSums* __restrict__ partials, BatchArg batch)
+__global__ __launch_bounds__(kThreads) void node_strain_kernel(StrainArgs in, NodeStrainSums* __restrict__ partials, BatchArg batch)
 {
     constexpr int K = Order == 2 ? 6 : 3;
     constexpr int kTile = Order == 0 ? 1 : kTileW * kTileH;
@@ -183,7 +114,7 @@ __global__ __launch_bounds__(kThreads) void node_strain_kernel(StrainArgs in, St
     const int i = pixel_column();
     const int j = static_cast<int>(pixel_row(1, 0));
     const bool active = i < in.nw && j < in.nh;
-    const size_t at = inst + static_cast<size_t>(active ? j : 0) * static_cast<size_t>(in.npitch) + static_cast<size_t>(active ? i : 0);
+    const size_t at = node_at(inst, active ? i : 0, active ? j : 0, in.npitch);
 
     int reason = kCentre;
     double ga = 0.0, gb = 0.0, gc = 0.0, gd = 0.0;
@@ -212,7 +143,7 @@ __global__ __launch_bounds__(kThreads) void node_strain_kernel(StrainArgs in, St
             float u = 0.f, v = 0.f;
             bool ok = false;
             if (x >= 0 && y >= 0 && x < in.nw && y < in.nh) {
-                const size_t q = inst + static_cast<size_t>(y) * static_cast<size_t>(in.npitch) + static_cast<size_t>(x);
+                const size_t q = node_at(inst, x, y, in.npitch);
                 u = in.u[q];
                 v = in.v[q];
                 ok = (in.state ? in.state[q] >= in.min_state : true) && finite(u) && finite(v);
@@ -286,7 +217,7 @@ __global__ __launch_bounds__(kThreads) void node_strain_kernel(StrainArgs in, St
         }
     }
 
-    StrainSums acc;
+    NodeStrainSums acc;
     if (Stats) acc.clear();
     if (active) {
         const bool valid = reason == kValid;
@@ -294,11 +225,11 @@ __global__ __launch_bounds__(kThreads) void node_strain_kernel(StrainArgs in, St
         quantities(ga, gb, gc, gd, in.measure, q);
 #pragma unroll
         for (int k = 0; k < 9; ++k)
-            if (in.out[k]) in.out[k][at] = valid ? q[k] : __uint_as_float(0x7FC00000u);
+            if (in.out[k]) in.out[k][at] = valid ? q[k] : quiet_nan();
         if (Stats) {
-            const float x[kQuantities] = {q[0], q[1], q[2], q[6], q[7], q[8]};
+            const float x[kStrainQuantities] = {q[0], q[1], q[2], q[6], q[7], q[8]};
 #pragma unroll
-            for (int k = 0; k < kQuantities; ++k) {
+            for (int k = 0; k < kStrainQuantities; ++k) {
                 const double t = valid ? static_cast<double>(x[k]) : 0.0;
                 acc.sum[k] += t;
                 acc.sum_sq[k] += t * t;
@@ -318,36 +249,13 @@ __global__ __launch_bounds__(kThreads) void node_strain_kernel(StrainArgs in, St
     }
 }
 
-// One workgroup per instance: thread t sums slabs t, t + 256, ... in order, then the reduction of ordered_reduce.hpp.
-__global__ __launch_bounds__(kFinalThreads) void node_strain_final_kernel(const StrainSums* __restrict__ partials, unsigned blocks,
-                                                                          flow2d_deformation_stats* __restrict__ stats)
-{
-    const StrainSums* slab = partials + static_cast<size_t>(blockIdx.x) * blocks;
-    StrainSums t;
-    t.clear();
-    for (unsigned j = threadIdx.x; j < blocks; j += kFinalThreads) t.combine(slab[j]);
-    if (!workgroup_reduce<kFinalThreads / 64>(t, threadIdx.x % 64, threadIdx.x / 64)) return;
-    flow2d_deformation_stats rec = {};
-    rec.valid = t.valid;
-    rec.invalid = t.invalid;
-    flow2d_deformation_moments* m[kQuantities] = {&rec.divergence, &rec.vorticity, &rec.dilatation, &rec.e1, &rec.e2, &rec.max_shear};
-    for (int k = 0; k < kQuantities; ++k) {
-        m[k]->sum = t.sum[k];
-        m[k]->sum_sq = t.sum_sq[k];
-        m[k]->min = t.valid ? t.min[k] : 0.f;
-        m[k]->max = t.valid ? t.max[k] : 0.f;
-    }
-    for (int k = 0; k < kReasons; ++k) rec.reserved[k] = t.reasons[k];
-    stats[blockIdx.x] = rec;
-}
-
 inline size_t partial_blocks(size_t nw, size_t nh)
 {
     return static_cast<size_t>(flow2d::div_up(nw, flow2d::kPixelBlockX)) * flow2d::div_up(nh, flow2d::kPixelBlockY);
 }
 
 template <int Order>
-void launch_order(flow2d_context* ctx, const StrainArgs& a, StrainSums* partials, size_t nw, size_t nh)
+void launch_order(flow2d_context* ctx, const StrainArgs& a, NodeStrainSums* partials, size_t nw, size_t nh)
 {
     const dim3 grid = flow2d::pixel_grid(ctx, nw, nh, 1), block = flow2d::pixel_block();
     if (partials)
@@ -363,7 +271,7 @@ extern "C" {
 size_t flow2d_node_strain_workspace_bytes(size_t nw, size_t nh, size_t instances)
 {
     if (nw == 0 || nh == 0 || instances == 0) return 0;
-    return partial_blocks(nw, nh) * instances * sizeof(StrainSums);
+    return partial_blocks(nw, nh) * instances * sizeof(NodeStrainSums);
 }
 
 int flow2d_node_strain_2d(flow2d_context* ctx, const float* node_u, const float* node_v, const float* node_state, const float* node_ux,
@@ -374,15 +282,16 @@ int flow2d_node_strain_2d(flow2d_context* ctx, const float* node_u, const float*
 {
     if (ctx == nullptr) return FLOW2D_ERR_INVALID_ARGUMENT;
     // (every check that needs no context field comes first: they hold without a device)
-    if (!flow2d::plane_args_ok(node_u, nw, nh, node_pitch_bytes) || !flow2d::plane_args_ok(node_v, nw, nh, node_pitch_bytes) ||
-        (node_state && !flow2d::plane_args_ok(node_state, nw, nh, node_pitch_bytes)))
+    const flow2d_deformation_planes p = out ? *out : flow2d_deformation_planes{};
+    float* const planes[9] = {p.divergence, p.vorticity, p.dilatation, p.exx, p.eyy, p.exy, p.e1, p.e2, p.max_shear};
+    if (!flow2d::planes_ok({node_u, node_v},
+                           {node_state, node_ux, node_uy, node_vx, node_vy, planes[0], planes[1], planes[2], planes[3], planes[4],
+                            planes[5], planes[6], planes[7], planes[8]},
+                           nw, nh, node_pitch_bytes))
         return FLOW2D_ERR_INVALID_ARGUMENT;
     const float* const grads[4] = {node_ux, node_uy, node_vx, node_vy};
     int given = 0;
-    for (const float* g : grads) {
-        if (g && !flow2d::plane_args_ok(g, nw, nh, node_pitch_bytes)) return FLOW2D_ERR_INVALID_ARGUMENT;
-        given += g != nullptr;
-    }
+    for (const float* g : grads) given += g != nullptr;
     if (given != 0 && given != 4) return FLOW2D_ERR_INVALID_ARGUMENT;
     if (spacing < 1 || spacing > FLOW2D_CORRELATION_MAX_SPACING || window < 0 || window > FLOW2D_NODE_STRAIN_MAX_WINDOW ||
         min_state < 0 || min_state > 1 || (measure != FLOW2D_STRAIN_SMALL && measure != FLOW2D_STRAIN_GREEN_LAGRANGE))
@@ -394,18 +303,11 @@ int flow2d_node_strain_2d(flow2d_context* ctx, const float* node_u, const float*
         const int k = order == 2 ? 6 : 3, side = 2 * window + 1;
         if (min_nodes < k || min_nodes > side * side) return FLOW2D_ERR_INVALID_ARGUMENT;
     }
-    const flow2d_deformation_planes p = out ? *out : flow2d_deformation_planes{};
-    float* const planes[9] = {p.divergence, p.vorticity, p.dilatation, p.exx, p.eyy, p.exy, p.e1, p.e2, p.max_shear};
     bool any = stats != nullptr;
-    for (float* q : planes) {
-        if (q && !flow2d::plane_args_ok(q, nw, nh, node_pitch_bytes)) return FLOW2D_ERR_INVALID_ARGUMENT;
-        any = any || q != nullptr;
-    }
+    for (float* q : planes) any = any || q != nullptr;
     if (!any) return FLOW2D_ERR_INVALID_ARGUMENT;
-    if ((reinterpret_cast<uintptr_t>(stats) % alignof(flow2d_deformation_stats)) != 0 ||
-        (reinterpret_cast<uintptr_t>(workspace) % 16) != 0)
-        return FLOW2D_ERR_INVALID_ARGUMENT;
-    if (nw * nh >= (size_t(1) << 31)) return FLOW2D_ERR_UNSUPPORTED;  // (as the siblings, which number the nodes in 32 bits)
+    if (!flow2d::record_aligned(stats) || (reinterpret_cast<uintptr_t>(workspace) % 16) != 0) return FLOW2D_ERR_INVALID_ARGUMENT;
+    if (!flow2d::node_count_ok(nw, nh)) return FLOW2D_ERR_UNSUPPORTED;
     if (stats && (!workspace || workspace_bytes < flow2d_node_strain_workspace_bytes(nw, nh, 1))) return FLOW2D_ERR_INVALID_ARGUMENT;
     // the kernel reads its neighbours' inputs while their threads write: no written byte range may meet a read one or another
     // written one.  Without statistics the workspace is not touched and takes no part.
@@ -437,7 +339,7 @@ int flow2d_node_strain_2d(flow2d_context* ctx, const float* node_u, const float*
     a.min_nodes = min_nodes;
     a.measure = measure;
     a.min_state = static_cast<float>(min_state);
-    StrainSums* partials = stats ? static_cast<StrainSums*>(workspace) : nullptr;
+    NodeStrainSums* partials = stats ? static_cast<NodeStrainSums*>(workspace) : nullptr;
     if (window == 0)
         launch_order<0>(ctx, a, partials, nw, nh);
     else if (order == 1)
@@ -446,7 +348,7 @@ int flow2d_node_strain_2d(flow2d_context* ctx, const float* node_u, const float*
         launch_order<2>(ctx, a, partials, nw, nh);
     FLOW2D_CHECK_LAUNCH();
     if (stats) {
-        node_strain_final_kernel<<<dim3(static_cast<unsigned>(instances)), dim3(kFinalThreads), 0, ctx->stream>>>(
+        strain_final_kernel<<<dim3(static_cast<unsigned>(instances)), dim3(kStrainFinalThreads), 0, ctx->stream>>>(
             partials, static_cast<unsigned>(partial_blocks(nw, nh)), stats);
         FLOW2D_CHECK_LAUNCH();
     }

@@ -8,13 +8,12 @@
 // (seven loads each), then takes the six outputs in turn: the up to eight candidates of one output live in registers, and the
 // median is found by rank -- candidate i comes after candidate j when c[j] < c[i], or when neither is below the other and
 // j < i -- so that nothing is sorted and no array is indexed by a run-time value.
-#include "ordered_reduce.hpp"
+#include "node_grid.hpp"
 #include "plane_sample.hpp"
 
 namespace {
 
 constexpr int kPredictCounts = 4;  // nodes, kept, predicted, empty
-constexpr int kPredictRecordWords = 8;
 
 struct PredictArgs {
     const float* in[6];  // u, v, ux, uy, vx, vy
@@ -26,8 +25,6 @@ struct PredictArgs {
     int s, min_neighbours;
     float min_state;
 };
-
-__device__ __forceinline__ bool finite(float x) { return fabsf(x) < INFINITY; }
 
 // Whether the node at `at` is usable: its state at least min_state and its six values finite.
 __device__ __forceinline__ bool usable_at(const PredictArgs& a, size_t at)
@@ -67,7 +64,7 @@ __global__ __launch_bounds__(flow2d::kPixelBlockX* flow2d::kPixelBlockY) void pr
     const bool active = i < a.nw && j < a.nh;
     unsigned counts[kPredictCounts] = {0u, 0u, 0u, 0u};
     if (active) {
-        const size_t at = inst + static_cast<size_t>(j) * static_cast<size_t>(a.npitch) + static_cast<size_t>(i);
+        const size_t at = node_at(inst, i, j, a.npitch);
         counts[0] = 1;
         if (usable_at(a, at)) {
             counts[1] = 1;
@@ -80,11 +77,12 @@ __global__ __launch_bounds__(flow2d::kPixelBlockX* flow2d::kPixelBlockY) void pr
             size_t where[8];
 #pragma unroll
             for (int n = 0; n < 8; ++n) {
-                const int m = n < 4 ? n : n + 1;
-                const int x = i + m % 3 - 1, y = j + m / 3 - 1;
+                int di, dj;
+                ring_neighbour(n, di, dj);
+                const int x = i + di, y = j + dj;
                 where[n] = at;
                 if (x >= 0 && y >= 0 && x < a.nw && y < a.nh) {
-                    where[n] = inst + static_cast<size_t>(y) * static_cast<size_t>(a.npitch) + static_cast<size_t>(x);
+                    where[n] = node_at(inst, x, y, a.npitch);
                     mask |= usable_at(a, where[n]) ? 1u << n : 0u;
                 }
             }
@@ -97,8 +95,9 @@ __global__ __launch_bounds__(flow2d::kPixelBlockX* flow2d::kPixelBlockY) void pr
                 for (int q = 0; q < 2; ++q) {
 #pragma unroll
                     for (int n = 0; n < 8; ++n) {
-                        const int k = n < 4 ? n : n + 1;
-                        const double dx = static_cast<double>(-(k % 3 - 1) * a.s), dy = static_cast<double>(-(k / 3 - 1) * a.s);
+                        int di, dj;
+                        ring_neighbour(n, di, dj);
+                        const double dx = static_cast<double>(-di * a.s), dy = static_cast<double>(-dj * a.s);
                         c[n] = 0.0;
                         if ((mask >> n) & 1u)
                             c[n] = (static_cast<double>(a.in[q][where[n]]) + static_cast<double>(a.in[2 + 2 * q][where[n]]) * dx) +
@@ -116,20 +115,12 @@ __global__ __launch_bounds__(flow2d::kPixelBlockX* flow2d::kPixelBlockY) void pr
             } else {
                 counts[3] = 1;
 #pragma unroll
-                for (int q = 0; q < 6; ++q) a.out[q][at] = __uint_as_float(0x7FC00000u);
+                for (int q = 0; q < 6; ++q) a.out[q][at] = quiet_nan();
                 if (a.out_state) a.out_state[at] = -1.f;
             }
         }
     }
-    if (!a.record) return;
-#pragma unroll
-    for (int n = 0; n < kPredictCounts; ++n) counts[n] = wave_sum(counts[n]);
-    if ((threadIdx.x & 63) == 0) {
-        unsigned long long* rec = a.record + kPredictRecordWords * static_cast<size_t>(blockIdx.z);
-#pragma unroll
-        for (int n = 0; n < kPredictCounts; ++n)
-            if (counts[n]) atomicAdd(rec + n, static_cast<unsigned long long>(counts[n]));
-    }
+    if (a.record) add_wave_counts<kCountRecordWords>(a.record, blockIdx.z, threadIdx.x & 63, counts);
 }
 
 }  // namespace
@@ -142,18 +133,16 @@ int flow2d_predict_nodes_2d(flow2d_context* ctx, const float* node_u, const floa
                             float* out_ux, float* out_uy, float* out_vx, float* out_vy, float* out_state, flow2d_predict_record* record)
 {
     if (ctx == nullptr) return FLOW2D_ERR_INVALID_ARGUMENT;
-    const float* const in[] = {node_u, node_v, node_ux, node_uy, node_vx, node_vy, node_state};
+    const float* const in[] = {node_u, node_v, node_ux, node_uy, node_vx, node_vy};
     float* const out[] = {out_u, out_v, out_ux, out_uy, out_vx, out_vy};
-    for (const float* p : in)
-        if (!flow2d::plane_args_ok(p, nw, nh, node_pitch_bytes)) return FLOW2D_ERR_INVALID_ARGUMENT;
-    for (float* p : out)
-        if (!flow2d::plane_args_ok(p, nw, nh, node_pitch_bytes)) return FLOW2D_ERR_INVALID_ARGUMENT;
-    if (out_state && !flow2d::plane_args_ok(out_state, nw, nh, node_pitch_bytes)) return FLOW2D_ERR_INVALID_ARGUMENT;
+    if (!flow2d::planes_ok({node_u, node_v, node_ux, node_uy, node_vx, node_vy, node_state, out_u, out_v, out_ux, out_uy, out_vx, out_vy},
+                           {out_state}, nw, nh, node_pitch_bytes))
+        return FLOW2D_ERR_INVALID_ARGUMENT;
     if (spacing < 1 || spacing > FLOW2D_CORRELATION_MAX_SPACING || min_state < 0 || min_state > 1 || min_neighbours < 1 ||
         min_neighbours > 8)
         return FLOW2D_ERR_INVALID_ARGUMENT;
-    if ((reinterpret_cast<uintptr_t>(record) % alignof(flow2d_predict_record)) != 0) return FLOW2D_ERR_INVALID_ARGUMENT;
-    if (nw * nh >= (size_t(1) << 31)) return FLOW2D_ERR_UNSUPPORTED;  // (as the siblings, which number the nodes in 32 bits)
+    if (!flow2d::record_aligned(record)) return FLOW2D_ERR_INVALID_ARGUMENT;
+    if (!flow2d::node_count_ok(nw, nh)) return FLOW2D_ERR_UNSUPPORTED;
     // out of place: a thread reads its neighbours' inputs while their threads write
     auto aliased = [&](size_t span, size_t instances) {
         const flow2d::ByteRange written[] = {{out_u, span},  {out_v, span},  {out_ux, span},    {out_uy, span},
@@ -166,7 +155,7 @@ int flow2d_predict_nodes_2d(flow2d_context* ctx, const float* node_u, const floa
     FLOW2D_ENTER(ctx);
     const size_t instances = ctx->batch_count;
     if (aliased(flow2d::batch_span(ctx, nh * node_pitch_bytes), instances)) return FLOW2D_ERR_INVALID_ARGUMENT;
-    if (record) FLOW2D_HIP_TRY(hipMemsetAsync(record, 0, instances * sizeof(flow2d_predict_record), ctx->stream));
+    FLOW2D_HIP_TRY(flow2d::clear_records(ctx, record));
     PredictArgs a;
     for (int q = 0; q < 6; ++q) {
         a.in[q] = in[q];

@@ -5,7 +5,7 @@
 
 #include <cmath>
 
-#include "ordered_reduce.hpp"
+#include "node_grid.hpp"
 #include "plane_sample.hpp"
 
 struct RefineArgs {
@@ -178,12 +178,7 @@ __global__ __launch_bounds__(kThreads) void refine_kernel(RefineArgs a, BatchArg
     if (a.record) {
         // (every lane arrives here: the rows' loop has no early exit)
         const unsigned counts[4] = {wave_sum(n_pixels), wave_sum(n_unfilled), wave_sum(n_filled), wave_sum(n_changed)};
-        if (threadIdx.x == 0) {
-            unsigned long long* rec = a.record + 4 * static_cast<size_t>(blockIdx.z);
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (counts[k]) atomicAdd(rec + k, static_cast<unsigned long long>(counts[k]));
-        }
+        if (threadIdx.x == 0) add_counts<4>(a.record, blockIdx.z, counts);
     }
 }
 

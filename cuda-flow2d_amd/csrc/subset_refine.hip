@@ -17,14 +17,14 @@
 #include <algorithm>
 #include <cmath>
 
-#include "ordered_reduce.hpp"
+#include "node_grid.hpp"
 #include "plane_sample.hpp"
+#include "small_cholesky.hpp"
 
 namespace {
 
 constexpr int kSubsetMaxWaves = 4;
 constexpr int kSubsetCounts = 7;   // the counts of flow2d_subset_record that are written
-constexpr int kSubsetRecordWords = 8;
 constexpr unsigned kSubsetLdsBytes = 64u * 1024u;  // what a launch may ask for without hipFuncSetAttribute
 constexpr int kStateNoInput = -1, kStateFlat = -2, kStateStrayed = -3;
 
@@ -102,26 +102,6 @@ __device__ __forceinline__ void jacobian(const SubsetNode& nd, int k, double (&J
     J[5] = fy * eta;
 }
 
-// Solve(b) of the header with the factor L (lower triangle).
-__device__ __forceinline__ void cholesky_solve(const double (&L)[6][6], const double (&b)[6], double (&x)[6])
-{
-    double y[6];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-        double sum = 0.0;
-#pragma unroll
-        for (int m = 0; m < i; ++m) sum += L[i][m] * y[m];
-        y[i] = (b[i] - sum) / L[i][i];
-    }
-#pragma unroll
-    for (int i = 5; i >= 0; --i) {
-        double sum = 0.0;
-#pragma unroll
-        for (int m = i + 1; m < 6; ++m) sum += L[m][i] * x[m];
-        x[i] = (y[i] - sum) / L[i][i];
-    }
-}
-
 // The node from the frame-0 quantities on: the state, with p, the last c and the iterations begun.  p = (u, ux, uy, v, vx, vy)
 // holds the start on entry: (u0, 0, 0, v0, 0, 0), or (u0, ux0, uy0, v0, vx0, vy0) of flow2d_subset_refine_from_2d.  Every lane of
 // the wave returns the same values.
@@ -172,6 +152,7 @@ __device__ __forceinline__ int refine_node(const SubsetNode& nd, const SubsetArg
 #pragma unroll
             for (int j = 0; j <= i; ++j) L[i][j] = wave_sum(hs[at++]);
     }
+    // factor<6> of small_cholesky.hpp, kept written out: through the header the kernel timed 1.2 % slower at R = 15 (see there)
 #pragma unroll
     for (int k = 0; k < 6; ++k) {
         const double hkk = L[k][k];
@@ -237,7 +218,7 @@ __device__ __forceinline__ int refine_node(const SubsetNode& nd, const SubsetArg
 #pragma unroll
         for (int i = 0; i < 6; ++i) b[i] = wave_sum(b[i]);
         double x[6];
-        cholesky_solve(L, b, x);
+        solve<6>(L, b, x);
         const double du = -x[0], dux = -x[1], duy = -x[2], dv = -x[3], dvx = -x[4], dvy = -x[5];
         // 4: p <- W(p) o W(dp)^-1
         const double ma = 1.0 + dux, mb = duy, mc = dvx, md = 1.0 + dvy;
@@ -273,7 +254,7 @@ template <bool kFrom>
 __device__ __forceinline__ bool gradients_finite(const float (&g0)[4])
 {
     if constexpr (kFrom)
-        return fabsf(g0[0]) < INFINITY && fabsf(g0[1]) < INFINITY && fabsf(g0[2]) < INFINITY && fabsf(g0[3]) < INFINITY;
+        return finite(g0[0]) && finite(g0[1]) && finite(g0[2]) && finite(g0[3]);
     else
         return true;
 }
@@ -312,7 +293,7 @@ __global__ __launch_bounds__(64 * kSubsetMaxWaves) void subset_refine_kernel(Sub
     nd.n = nd.side * nd.side;
     nd.lane = lane;
 
-    const size_t at = inst + static_cast<size_t>(jn) * static_cast<size_t>(a.npitch) + static_cast<size_t>(in);
+    const size_t at = node_at(inst, in, jn, a.npitch);
     const float u0 = a.u0[at], v0 = a.v0[at];
     float g0[4] = {0.f, 0.f, 0.f, 0.f};  // ux0, uy0, vx0, vy0
     if constexpr (kFrom) {
@@ -327,7 +308,7 @@ __global__ __launch_bounds__(64 * kSubsetMaxWaves) void subset_refine_kernel(Sub
     double score = 0.0;
     unsigned iterations = 0;
     int state;
-    if (!(fabsf(u0) < INFINITY && fabsf(v0) < INFINITY) || !gradients_finite<kFrom>(g0))
+    if (!(finite(u0) && finite(v0)) || !gradients_finite<kFrom>(g0))
         state = kStateNoInput;
     else if (!(nd.cx - nd.R >= 0 && nd.cy - nd.R >= 0 && nd.cx + nd.R <= a.w - 1 && nd.cy + nd.R <= a.h - 1))
         state = kStateStrayed;
@@ -335,7 +316,6 @@ __global__ __launch_bounds__(64 * kSubsetMaxWaves) void subset_refine_kernel(Sub
         state = refine_node<Offset>(nd, a, p, score, iterations);
     if (lane != 0) return;
 
-    const float nan = __uint_as_float(0x7FC00000u);
     float out[6], out_score = 0.f;
     if (state >= 0) {
 #pragma unroll
@@ -343,7 +323,7 @@ __global__ __launch_bounds__(64 * kSubsetMaxWaves) void subset_refine_kernel(Sub
         out_score = static_cast<float>(score);
     } else {
 #pragma unroll
-        for (int i = 0; i < 6; ++i) out[i] = state == kStateNoInput ? nan : 0.f;
+        for (int i = 0; i < 6; ++i) out[i] = state == kStateNoInput ? quiet_nan() : 0.f;
         if (state != kStateNoInput) {
             out[0] = u0;
             out[3] = v0;
@@ -366,12 +346,9 @@ __global__ __launch_bounds__(64 * kSubsetMaxWaves) void subset_refine_kernel(Sub
     if (a.score) a.score[at] = out_score;
     if (a.state) a.state[at] = static_cast<float>(state);
     if (a.record) {
-        unsigned long long* rec = a.record + kSubsetRecordWords * static_cast<size_t>(blockIdx.z);
         const unsigned counts[kSubsetCounts] = {1u, state >= 1, state == 0, state == kStateStrayed, state == kStateFlat,
                                                 state == kStateNoInput, iterations};
-#pragma unroll
-        for (int k = 0; k < kSubsetCounts; ++k)
-            if (counts[k]) atomicAdd(rec + k, static_cast<unsigned long long>(counts[k]));
+        add_counts<kCountRecordWords>(a.record, blockIdx.z, counts);
     }
 }
 
@@ -384,15 +361,12 @@ int subset_refine_entry(flow2d_context* ctx, const float* frame_0, const float* 
 {
     if (ctx == nullptr) return FLOW2D_ERR_INVALID_ARGUMENT;
     // (every check that needs no context field comes first: they hold without a device)
-    if (!flow2d::plane_args_ok(frame_0, width, height, pitch_bytes) || !flow2d::plane_args_ok(frame_1, width, height, pitch_bytes))
-        return FLOW2D_ERR_INVALID_ARGUMENT;
-    if (grid_radius < 1 || grid_radius > FLOW2D_CORRELATION_MAX_RADIUS || spacing < 1 || spacing > FLOW2D_CORRELATION_MAX_SPACING ||
-        subset_radius < 1 || subset_radius > FLOW2D_SUBSET_MAX_RADIUS || max_iterations < 1 || max_iterations > FLOW2D_SUBSET_MAX_ITERATIONS)
+    if (!flow2d::planes_ok({frame_0, frame_1}, {}, width, height, pitch_bytes)) return FLOW2D_ERR_INVALID_ARGUMENT;
+    if (subset_radius < 1 || subset_radius > FLOW2D_SUBSET_MAX_RADIUS || max_iterations < 1 || max_iterations > FLOW2D_SUBSET_MAX_ITERATIONS)
         return FLOW2D_ERR_INVALID_ARGUMENT;
     if (!(std::isfinite(epsilon) && epsilon >= 0.f) || !(std::isfinite(max_shift) && max_shift > 0.f) ||
         !(std::isfinite(max_gradient) && max_gradient > 0.f))
         return FLOW2D_ERR_INVALID_ARGUMENT;
-    float* const planes[] = {out_u, out_v, out_ux, out_uy, out_vx, out_vy, out_score, out_state};
     const bool gradients = out_ux != nullptr;
     if ((out_uy != nullptr) != gradients || (out_vx != nullptr) != gradients || (out_vy != nullptr) != gradients)
         return FLOW2D_ERR_INVALID_ARGUMENT;
@@ -400,19 +374,16 @@ int subset_refine_entry(flow2d_context* ctx, const float* frame_0, const float* 
     const bool started = start[0] != nullptr;
     if ((start[1] != nullptr) != started || (start[2] != nullptr) != started || (start[3] != nullptr) != started)
         return FLOW2D_ERR_INVALID_ARGUMENT;
-    if (!flow2d::plane_args_ok(node_u0, nw, nh, node_pitch_bytes) || !flow2d::plane_args_ok(node_v0, nw, nh, node_pitch_bytes) ||
-        !flow2d::plane_args_ok(out_u, nw, nh, node_pitch_bytes) || !flow2d::plane_args_ok(out_v, nw, nh, node_pitch_bytes))
+    if (!flow2d::planes_ok({node_u0, node_v0, out_u, out_v},
+                           {out_ux, out_uy, out_vx, out_vy, out_score, out_state, start[0], start[1], start[2], start[3]}, nw, nh,
+                           node_pitch_bytes))
         return FLOW2D_ERR_INVALID_ARGUMENT;
-    for (int k = 2; k < 8; ++k)
-        if (planes[k] && !flow2d::plane_args_ok(planes[k], nw, nh, node_pitch_bytes)) return FLOW2D_ERR_INVALID_ARGUMENT;
-    for (int k = 0; started && k < 4; ++k)
-        if (!flow2d::plane_args_ok(start[k], nw, nh, node_pitch_bytes)) return FLOW2D_ERR_INVALID_ARGUMENT;
-    // the grid lies inside the frame, as flow2d_correlation_grid lays it
-    const size_t window = static_cast<size_t>(2 * grid_radius + 1);
-    if (width < window || height < window || nw - 1 > (width - window) / spacing || nh - 1 > (height - window) / spacing)
+    // the grid lies inside the frame, as flow2d_correlation_grid lays it; it may be smaller than the full one
+    if (!flow2d::correlation_grid_ok(width, height, grid_radius, spacing) ||
+        nw > flow2d::correlation_nodes(width, grid_radius, spacing) || nh > flow2d::correlation_nodes(height, grid_radius, spacing))
         return FLOW2D_ERR_INVALID_ARGUMENT;
-    if ((reinterpret_cast<uintptr_t>(record) % alignof(flow2d_subset_record)) != 0) return FLOW2D_ERR_INVALID_ARGUMENT;
-    if (nw * nh >= (size_t(1) << 31)) return FLOW2D_ERR_UNSUPPORTED;  // (the kernel numbers the nodes in 32 bits)
+    if (!flow2d::record_aligned(record)) return FLOW2D_ERR_INVALID_ARGUMENT;
+    if (!flow2d::node_count_ok(nw, nh)) return FLOW2D_ERR_UNSUPPORTED;
     // the kernel reads frames and nodes while other waves write: no written byte range may meet a read one or another written one
     auto aliased = [&](size_t frame_span, size_t node_span, size_t instances) {
         const flow2d::ByteRange written[] = {{out_u, node_span},  {out_v, node_span},  {out_ux, node_span},
@@ -428,7 +399,7 @@ int subset_refine_entry(flow2d_context* ctx, const float* frame_0, const float* 
     const size_t instances = ctx->batch_count;
     if (aliased(flow2d::batch_span(ctx, height * pitch_bytes), flow2d::batch_span(ctx, nh * node_pitch_bytes), instances))
         return FLOW2D_ERR_INVALID_ARGUMENT;
-    if (record) FLOW2D_HIP_TRY(hipMemsetAsync(record, 0, instances * sizeof(flow2d_subset_record), ctx->stream));
+    FLOW2D_HIP_TRY(flow2d::clear_records(ctx, record));
     const unsigned side = static_cast<unsigned>(2 * subset_radius + 1);
     const unsigned slice = (side * side + 1u) & ~1u;                       // at most 962 doubles
     const unsigned wave_bytes = 4u * slice * sizeof(double);               // at most 30 784
