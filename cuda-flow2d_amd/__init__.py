@@ -537,6 +537,8 @@ def hip_lib():
             L.flow2d_validate_nodes_2d.argtypes = [vp, vp, vp, sz, sz, sz, f, f, i, i, vp, vp, vp, vp]
         if hasattr(L, "flow2d_subset_refine_2d"):  # (absent from libraries of earlier rounds loaded for an A/B)
             L.flow2d_subset_refine_2d.argtypes = [vp, vp, vp, sz, sz, sz, vp, vp, sz, sz, sz, i, i, i, i, f, f, f] + [vp] * 9
+        if hasattr(L, "flow2d_subset_refine2_2d"):  # (absent from libraries of earlier rounds loaded for an A/B)
+            L.flow2d_subset_refine2_2d.argtypes = [vp, vp, vp, sz, sz, sz] + [vp] * 4 + [sz, sz, sz, i, i, i, i, f, f, f, f] + [vp] * 7
         if hasattr(L, "flow2d_subset_refine_from_2d"):  # (absent from libraries of earlier rounds loaded for an A/B)
             L.flow2d_subset_refine_from_2d.argtypes = [vp, vp, vp, sz, sz, sz] + [vp] * 6 + [sz, sz, sz, i, i, i, i, f, f, f] + [vp] * 9
             L.flow2d_predict_nodes_2d.argtypes = [vp] + [vp] * 7 + [sz, sz, sz, i, i, i] + [vp] * 8
@@ -1310,6 +1312,60 @@ class Context:
                 q.free()
                 self._planes.remove(q)
 
+    def subset_refine2(self, f0, f1, w, h, node_u0, node_v0, nw, nh, grid_radius, spacing, subset_radius, max_iterations=20,
+                       epsilon=1e-3, max_shift=2.0, max_gradient=0.5, max_curvature=0.05, start_gradients=None, start_curvatures=None,
+                       out_u=None, out_v=None, out_gradients=None, out_curvatures=None, out_score=None, out_state=None, record=True,
+                       instances=1):
+        """Subset refinement with a second-order shape function (flow2d_subset_refine2_2d): subset_refine_from with twelve
+        parameters per node -- the displacement, its four gradients and the six curvatures (uxx, uxy, uyy, vxx, vxy, vyy) -- for
+        subsets that bend; subset_radius from 2.  start_gradients = (ux0, uy0, vx0, vy0) and start_curvatures = (uxx0, uxy0, uyy0,
+        vxx0, vxy0, vyy0): Planes like node_u0, or None (0); the curvatures only with the gradients.  A curvature beyond
+        max_curvature (per pixel) strays.  out_u, out_v (and optionally out_gradients, out_curvatures, out_score, out_state): the
+        caller's Planes; without them the call allocates all fourteen, downloads them and returns arrays.  record as for
+        subset_refine.  Returns (u, v, (ux, uy, vx, vy) or None, (uxx, uxy, uyy, vxx, vxy, vyy) or None, score or None, state or
+        None, SubsetRecord or None)."""
+        own_planes = out_u is None and out_v is None
+        if not own_planes and (out_u is None or out_v is None):
+            raise ValueError("subset_refine2 takes both output planes or neither")
+        own_record = record is True
+        if own_record and instances != 1:
+            raise ValueError("a lock-step batch takes the caller's records")
+
+        def group(planes, n, what):
+            if planes is None:
+                return None
+            planes = list(planes)
+            if len(planes) != n:
+                raise ValueError("subset_refine2 takes %d %s or None" % (n, what))
+            return (C.c_void_p * n)(*[q.ptr if q is not None else None for q in planes])
+
+        if own_planes:
+            held = [self.plane(node_u0.pitch // 4, nh) for _ in range(14)]
+        else:
+            held = ([out_u, out_v] + list(out_gradients if out_gradients is not None else (None,) * 4) +
+                    list(out_curvatures if out_curvatures is not None else (None,) * 6) + [out_score, out_state])
+            if len(held) != 14:
+                raise ValueError("subset_refine2 takes four gradient planes and six curvature planes")
+        rec = self.subset_records(instances) if own_record else (record or None)
+        try:
+            _check(hip_lib().flow2d_subset_refine2_2d(self.handle, f0.ptr, f1.ptr, w, h, f0.pitch, node_u0.ptr, node_v0.ptr,
+                                                      group(start_gradients, 4, "start gradients"),
+                                                      group(start_curvatures, 6, "start curvatures"), nw, nh, node_u0.pitch,
+                                                      int(grid_radius), int(spacing), int(subset_radius), int(max_iterations),
+                                                      float(epsilon), float(max_shift), float(max_gradient), float(max_curvature),
+                                                      held[0].ptr, held[1].ptr, group(held[2:6], 4, "gradients"),
+                                                      group(held[6:12], 6, "curvatures"), held[12].ptr if held[12] is not None else None,
+                                                      held[13].ptr if held[13] is not None else None,
+                                                      rec.ptr if rec is not None else None), "flow2d_subset_refine2_2d")
+            got = [q.download(nw, nh) for q in held] if own_planes else held
+            gradients = tuple(got[2:6]) if got[2] is not None else None
+            curvatures = tuple(got[6:12]) if got[6] is not None else None
+            return got[0], got[1], gradients, curvatures, got[12], got[13], (self.read_subset_record(rec, 1)[0] if own_record else None)
+        finally:
+            for q in (held if own_planes else []) + ([rec] if own_record else []):
+                q.free()
+                self._planes.remove(q)
+
     def predict_records(self, instances=1):
         """A Plane for `instances` flow2d_predict_record records (device memory)."""
         return self._record_plane(PREDICT_RECORD_BYTES, instances)
@@ -1686,6 +1742,19 @@ def host_lib():
             L.flow2d_host_correlate_subset_device.argtypes = [vp, vp, vp, f, f, ip, i, f, f, f, i, i, i, f, f, f, vp, vp, C.POINTER(vp), rp, sr,
                                                               vp, vp]
             L.flow2d_host_correlate_subset.argtypes = [vp, fp, fp, ip, i, f, f, f, i, i, i, f, f, f, fp, fp, C.POINTER(fp), rp, sr, fp, fp, fp]
+        if hasattr(L, "flow2d_host_correlate_subset2_device"):  # the same calls with SubsetOptions::order and max_curvature
+            ip, rp, sr, st = C.POINTER(C.c_int), C.POINTER(CorrelationPassReport), C.POINTER(SubsetRecord), C.POINTER(SequenceStepReport)
+            pvp = C.POINTER(vp)
+            L.flow2d_host_subset2_options_ok.argtypes = [i, i, f, f, f, i, f]
+            L.flow2d_host_refine_nodes2_device.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, f, f, f, i, f, pvp, sr]
+            L.flow2d_host_refine_nodes_from2_device.argtypes = [vp, vp, vp, pvp, i, i, i, i, f, f, f, i, f, pvp, sr]
+            L.flow2d_host_correlate_subset2_device.argtypes = [vp, vp, vp, f, f, ip, i, f, f, f, i, i, i, f, f, f, i, f, vp, vp, pvp, rp, sr, vp, vp]
+            fpp = C.POINTER(fp)
+            L.flow2d_host_correlate_subset2.argtypes = [vp, fp, fp, ip, i, f, f, f, i, i, i, f, f, f, i, f, fp, fp, fpp, rp, sr, fp, fp, fp]
+            L.flow2d_host_correlate_subset2_sequence.argtypes = [vp, fpp, i, ip, i, f, f, f, i, i, i, f, f, f, i, f, i, i, i, f, fpp, rp, st,
+                                                                 fpp, fp]
+            L.flow2d_host_correlate_subset2_sequence_device.argtypes = [vp, pvp, i, f, f, ip, i, f, f, f, i, i, i, f, f, f, i, f, i, i, i, f, pvp,
+                                                                        rp, st, pvp]
         if hasattr(L, "flow2d_host_correlate_subset_sequence_device"):
             ip, rp, sr, st = C.POINTER(C.c_int), C.POINTER(CorrelationPassReport), C.POINTER(SubsetRecord), C.POINTER(SequenceStepReport)
             pvp, pfp = C.POINTER(vp), C.POINTER(fp)
@@ -2240,10 +2309,25 @@ class OpticalFlow:
 
     SUBSET_PLANES = ("u", "v", "ux", "uy", "vx", "vy", "score", "state")
 
+    # ... and with order=2 (the second-order refinement, flow2d_subset_refine2_2d) the six curvatures behind them
+    SUBSET2_PLANES = SUBSET_PLANES + ("uxx", "uxy", "uyy", "vxx", "vxy", "vyy")
+
     @staticmethod
-    def subset_options_ok(radius, iterations=20, epsilon=1e-3, max_shift=2.0, max_gradient=0.5):
+    def subset_options_ok(radius, iterations=20, epsilon=1e-3, max_shift=2.0, max_gradient=0.5, order=1, max_curvature=0.05):
         """OpticalFlow2D::SubsetOptionsOk: whether refine_nodes_device / correlate_subset* accept the options.  Needs no device."""
-        return bool(host_lib().flow2d_host_subset_options_ok(int(radius), int(iterations), float(epsilon), float(max_shift), float(max_gradient)))
+        if order == 1 and max_curvature == 0.05:
+            return bool(host_lib().flow2d_host_subset_options_ok(int(radius), int(iterations), float(epsilon), float(max_shift), float(max_gradient)))
+        return bool(host_lib().flow2d_host_subset2_options_ok(int(radius), int(iterations), float(epsilon), float(max_shift), float(max_gradient),
+                                                              int(order), float(max_curvature)))
+
+    @staticmethod
+    def _subset2_planes(dev_out):
+        """The fourteen device planes of SUBSET2_PLANES from a dict name -> address (absent or None: not wanted)."""
+        dev_out = dev_out or {}
+        unknown = set(dev_out) - set(OpticalFlow.SUBSET2_PLANES)
+        if unknown:
+            raise ValueError("unknown subset planes %s (of %s)" % (sorted(unknown), ", ".join(OpticalFlow.SUBSET2_PLANES)))
+        return (C.c_void_p * 14)(*[dev_out.get(name) for name in OpticalFlow.SUBSET2_PLANES])
 
     @staticmethod
     def _subset_planes(dev_out):
@@ -2255,12 +2339,22 @@ class OpticalFlow:
         return (C.c_void_p * 8)(*[dev_out.get(name) for name in OpticalFlow.SUBSET_PLANES])
 
     def refine_nodes_device(self, dev_frame_0, dev_frame_1, dev_node_u0, dev_node_v0, grid_radius, spacing, radius, iterations=20,
-                            epsilon=1e-3, max_shift=2.0, max_gradient=0.5, dev_out=None, record=True):
+                            epsilon=1e-3, max_shift=2.0, max_gradient=0.5, dev_out=None, record=True, order=1, max_curvature=0.05):
         """OpticalFlow2D::RefineNodesDevice: the node field (dev_node_u0, dev_node_v0) of the grid (grid_radius, spacing) -- planes of
         the container's size -- refined by subsets of `radius` (flow2d_subset_refine_2d).  dev_out: a dict of device planes by the
         names of SUBSET_PLANES (u and v both or neither, the four gradients all or none).  Returns the SubsetRecord (the call then
-        synchronises) or, without record, None (it only queues)."""
+        synchronises) or, without record, None (it only queues).  order=2: the second-order refinement (flow2d_subset_refine2_2d),
+        radius from 2, a curvature beyond max_curvature strays; dev_out by the names of SUBSET2_PLANES, the six curvatures all or
+        none.  order=1 is the call it always was."""
         rec = SubsetRecord()
+        if order != 1:
+            rc = host_lib().flow2d_host_refine_nodes2_device(self.handle, dev_frame_0, dev_frame_1, dev_node_u0, dev_node_v0, int(grid_radius),
+                                                             int(spacing), int(radius), int(iterations), float(epsilon), float(max_shift),
+                                                             float(max_gradient), int(order), float(max_curvature),
+                                                             self._subset2_planes(dev_out), C.byref(rec) if record else None)
+            if rc:
+                raise Flow2DError(rc, "OpticalFlow2D::RefineNodesDevice")
+            return rec if record else None
         rc = host_lib().flow2d_host_refine_nodes_device(self.handle, dev_frame_0, dev_frame_1, dev_node_u0, dev_node_v0, int(grid_radius),
                                                         int(spacing), int(radius), int(iterations), float(epsilon), float(max_shift),
                                                         float(max_gradient), self._subset_planes(dev_out), C.byref(rec) if record else None)
@@ -2269,20 +2363,34 @@ class OpticalFlow:
         return rec if record else None
 
     def correlate_subset(self, frame_0, frame_1, passes, radius, iterations=20, epsilon=1e-3, max_shift=2.0, max_gradient=0.5,
-                         min_score=-1.0, threshold=2.0, validate_epsilon=0.1, min_neighbours=3, predictor=None, flow=False):
+                         min_score=-1.0, threshold=2.0, validate_epsilon=0.1, min_neighbours=3, predictor=None, flow=False, order=1,
+                         max_curvature=0.05):
         """OpticalFlow2D::CorrelateSubset: the host pair through `passes` as in correlate_multipass -- the last pass validated with
         replacement, so that every node has a start --, then every node of the last pass's grid refined by subsets of `radius` on
         the unquantised frames.  Returns (nodes, [CorrelationPassReport], SubsetRecord, (lo, scale)), nodes a dict of [nh, nw]
-        arrays by the names of SUBSET_PLANES; with flow, also the (u, v) of the refined field expanded to the frame's grid."""
+        arrays by the names of SUBSET_PLANES; with flow, also the (u, v) of the refined field expanded to the frame's grid.
+        order=2: the second-order refinement (radius from 2, a curvature beyond max_curvature strays), nodes by the names of
+        SUBSET2_PLANES; order=1 is the call it always was."""
         f0, f1 = self._pair(frame_0, frame_1)
         arr, n = self._passes(passes)
         if not 1 <= n <= CORRELATION_MAX_PASSES:
             raise Flow2DError(1, "OpticalFlow2D::CorrelateSubset")
         nw, nh = correlation_grid(self.width, self.height, passes[-1][0], passes[-1][2])
-        nodes = [np.empty((nh, nw), np.float32) for _ in range(8)]
+        nodes = [np.empty((nh, nw), np.float32) for _ in range(8 if order == 1 else 14)]
         uv = [np.empty_like(f0) for _ in range(2)] if flow else [None, None]
         pred = [np.ascontiguousarray(q, np.float32) for q in predictor] if predictor is not None else [None, None]
         reports, rec, lo_scale = (CorrelationPassReport * n)(), SubsetRecord(), (C.c_float * 2)()
+        if order != 1:
+            rc = host_lib().flow2d_host_correlate_subset2(self.handle, _fptr(f0), _fptr(f1), arr, n, float(min_score), float(threshold),
+                                                          float(validate_epsilon), int(min_neighbours), int(radius), int(iterations),
+                                                          float(epsilon), float(max_shift), float(max_gradient), int(order),
+                                                          float(max_curvature), _opt_fptr(pred[0]), _opt_fptr(pred[1]),
+                                                          (C.POINTER(C.c_float) * 14)(*[_fptr(q) for q in nodes]), reports, C.byref(rec),
+                                                          _opt_fptr(uv[0]), _opt_fptr(uv[1]), lo_scale)
+            if rc:
+                raise Flow2DError(rc, "OpticalFlow2D::CorrelateSubset")
+            out = (dict(zip(self.SUBSET2_PLANES, nodes)), list(reports), rec, (lo_scale[0], lo_scale[1]))
+            return out + (tuple(uv),) if flow else out
         rc = host_lib().flow2d_host_correlate_subset(self.handle, _fptr(f0), _fptr(f1), arr, n, float(min_score), float(threshold),
                                                      float(validate_epsilon), int(min_neighbours), int(radius), int(iterations),
                                                      float(epsilon), float(max_shift), float(max_gradient), _opt_fptr(pred[0]),
@@ -2295,13 +2403,22 @@ class OpticalFlow:
 
     def correlate_subset_device(self, dev_frame_0, dev_frame_1, lo, scale, passes, radius, iterations=20, epsilon=1e-3, max_shift=2.0,
                                 max_gradient=0.5, min_score=-1.0, threshold=2.0, validate_epsilon=0.1, min_neighbours=3, dev_predictor=None,
-                                dev_out=None, dev_flow=None):
+                                dev_out=None, dev_flow=None, order=1, max_curvature=0.05):
         """OpticalFlow2D::CorrelateSubsetDevice: device frames in; dev_predictor and dev_flow as for correlate_multipass_device (the
-        flow is the refined field's), dev_out as for refine_nodes_device.  Returns ([CorrelationPassReport], SubsetRecord);
-        synchronises once."""
+        flow is the refined field's), dev_out, order and max_curvature as for refine_nodes_device.  Returns
+        ([CorrelationPassReport], SubsetRecord); synchronises once."""
         arr, n = self._passes(passes)
         reports, rec = (CorrelationPassReport * max(n, 1))(), SubsetRecord()
         pr, fl = dev_predictor or (None, None), dev_flow or (None, None)
+        if order != 1:
+            rc = host_lib().flow2d_host_correlate_subset2_device(self.handle, dev_frame_0, dev_frame_1, float(lo), float(scale), arr, n,
+                                                                 float(min_score), float(threshold), float(validate_epsilon),
+                                                                 int(min_neighbours), int(radius), int(iterations), float(epsilon),
+                                                                 float(max_shift), float(max_gradient), int(order), float(max_curvature),
+                                                                 pr[0], pr[1], self._subset2_planes(dev_out), reports, C.byref(rec), fl[0], fl[1])
+            if rc:
+                raise Flow2DError(rc, "OpticalFlow2D::CorrelateSubsetDevice")
+            return list(reports)[:n], rec
         rc = host_lib().flow2d_host_correlate_subset_device(self.handle, dev_frame_0, dev_frame_1, float(lo), float(scale), arr, n,
                                                             float(min_score), float(threshold), float(validate_epsilon), int(min_neighbours),
                                                             int(radius), int(iterations), float(epsilon), float(max_shift),
@@ -2317,14 +2434,24 @@ class OpticalFlow:
         return bool(host_lib().flow2d_host_sequence_options_ok(int(fill), int(min_state), int(predict_neighbours), float(sequence_max_shift)))
 
     def refine_nodes_from_device(self, dev_frame_0, dev_frame_1, dev_start, grid_radius, spacing, radius, iterations=20, epsilon=1e-3,
-                                 max_shift=4.0, max_gradient=0.5, dev_out=None, record=True):
+                                 max_shift=4.0, max_gradient=0.5, dev_out=None, record=True, order=1, max_curvature=0.05):
         """OpticalFlow2D::RefineNodesFromDevice: refine_nodes_device started from a whole deformation (flow2d_subset_refine_from_2d):
         dev_start is a dict of the six device planes u, v, ux, uy, vx, vy (by the names of SUBSET_PLANES), all needed.  Returns the
-        SubsetRecord (the call then synchronises) or, without record, None (it only queues)."""
+        SubsetRecord (the call then synchronises) or, without record, None (it only queues).  order and max_curvature as for
+        refine_nodes_device; at order 2 the start's curvatures are 0."""
         names = self.SUBSET_PLANES[:6]
         if set(dev_start) != set(names) or not all(dev_start[n] for n in names):
             raise ValueError("refine_nodes_from_device takes the six start planes %s" % ", ".join(names))
         rec = SubsetRecord()
+        if order != 1:
+            rc = host_lib().flow2d_host_refine_nodes_from2_device(self.handle, dev_frame_0, dev_frame_1,
+                                                                  (C.c_void_p * 6)(*[dev_start[n] for n in names]), int(grid_radius),
+                                                                  int(spacing), int(radius), int(iterations), float(epsilon), float(max_shift),
+                                                                  float(max_gradient), int(order), float(max_curvature),
+                                                                  self._subset2_planes(dev_out), C.byref(rec) if record else None)
+            if rc:
+                raise Flow2DError(rc, "OpticalFlow2D::RefineNodesFromDevice")
+            return rec if record else None
         rc = host_lib().flow2d_host_refine_nodes_from_device(self.handle, dev_frame_0, dev_frame_1, (C.c_void_p * 6)(*[dev_start[n] for n in names]),
                                                              int(grid_radius), int(spacing), int(radius), int(iterations), float(epsilon),
                                                              float(max_shift), float(max_gradient), self._subset_planes(dev_out),
@@ -2335,8 +2462,10 @@ class OpticalFlow:
 
     def correlate_subset_sequence(self, frames, passes, radius, iterations=20, epsilon=1e-3, max_shift=2.0, max_gradient=0.5, min_score=-1.0,
                                   threshold=2.0, validate_epsilon=0.1, min_neighbours=3, fill=2, min_state=1, predict_neighbours=1,
-                                  sequence_max_shift=4.0, flow=False):
-        """OpticalFlow2D::CorrelateSubsetSequence: digital image correlation over a loading sequence.  frames[0] is the reference and
+                                  sequence_max_shift=4.0, flow=False, order=1, max_curvature=0.05):
+        """OpticalFlow2D::CorrelateSubsetSequence: digital image correlation over a loading sequence.  (order=2: every step refines
+        at second order, the steps after the first from the prediction's first-order planes with zero curvatures; the nodes then
+        go by the names of SUBSET2_PLANES.)  frames[0] is the reference and
         every later frame is correlated against it: step 1 is correlate_subset's chain; step k >= 2 takes the previous step's
         deformation, gradients included, as its start -- `fill` passes of flow2d_predict_nodes_2d keep the nodes with a state of
         min_state at least and refill the others from predict_neighbours usable neighbours, then flow2d_subset_refine_from_2d
@@ -2351,10 +2480,24 @@ class OpticalFlow:
             raise Flow2DError(1, "OpticalFlow2D::CorrelateSubsetSequence")
         steps = len(images) - 1
         nw, nh = correlation_grid(self.width, self.height, passes[-1][0], passes[-1][2])
-        nodes = [np.empty((nh, nw), np.float32) for _ in range(8 * steps)]
+        per = 8 if order == 1 else 14
+        nodes = [np.empty((nh, nw), np.float32) for _ in range(per * steps)]
         uv = [np.empty_like(images[0]) for _ in range(2 * steps)] if flow else None
         fpp = C.POINTER(C.c_float)
         reports, reps, lo_scale = (CorrelationPassReport * n)(), (SequenceStepReport * steps)(), (C.c_float * 2)()
+        if order != 1:
+            rc = host_lib().flow2d_host_correlate_subset2_sequence(self.handle, (fpp * len(images))(*[_fptr(q) for q in images]), len(images),
+                                                                   arr, n, float(min_score), float(threshold), float(validate_epsilon),
+                                                                   int(min_neighbours), int(radius), int(iterations), float(epsilon),
+                                                                   float(max_shift), float(max_gradient), int(order), float(max_curvature),
+                                                                   int(fill), int(min_state), int(predict_neighbours), float(sequence_max_shift),
+                                                                   (fpp * (per * steps))(*[_fptr(q) for q in nodes]), reports, reps,
+                                                                   (fpp * (2 * steps))(*[_fptr(q) for q in uv]) if flow else None, lo_scale)
+            if rc:
+                raise Flow2DError(rc, "OpticalFlow2D::CorrelateSubsetSequence")
+            per_step = [dict(zip(self.SUBSET2_PLANES, nodes[per * k:per * k + per])) for k in range(steps)]
+            out = (per_step, list(reports), list(reps), (lo_scale[0], lo_scale[1]))
+            return out + ([(uv[2 * k], uv[2 * k + 1]) for k in range(steps)],) if flow else out
         rc = host_lib().flow2d_host_correlate_subset_sequence(self.handle, (fpp * len(images))(*[_fptr(q) for q in images]), len(images), arr, n,
                                                               float(min_score), float(threshold), float(validate_epsilon), int(min_neighbours),
                                                               int(radius), int(iterations), float(epsilon), float(max_shift),
@@ -2370,17 +2513,20 @@ class OpticalFlow:
 
     def correlate_subset_sequence_device(self, dev_frames, lo, scale, passes, radius, dev_out, iterations=20, epsilon=1e-3, max_shift=2.0,
                                          max_gradient=0.5, min_score=-1.0, threshold=2.0, validate_epsilon=0.1, min_neighbours=3, fill=2,
-                                         min_state=1, predict_neighbours=1, sequence_max_shift=4.0, dev_flows=None):
+                                         min_state=1, predict_neighbours=1, sequence_max_shift=4.0, dev_flows=None, order=1,
+                                         max_curvature=0.05):
         """OpticalFlow2D::CorrelateSubsetSequenceDevice: device frames in (the first is the reference); dev_out: per step a dict of
         device planes by the names of SUBSET_PLANES, of which only the score may be missing; dev_flows: per step a (u, v) pair or
-        None.  Returns ([CorrelationPassReport] of step 1, [SequenceStepReport]); synchronises once."""
+        None.  Returns ([CorrelationPassReport] of step 1, [SequenceStepReport]); synchronises once.  order=2: every step refines
+        at second order -- the steps after the first from the prediction's six first-order planes with zero curvatures --, dev_out
+        by the names of SUBSET2_PLANES, the six curvatures all or none per step."""
         arr, n = self._passes(passes)
         steps = len(dev_frames) - 1
         if steps < 1 or len(dev_out) != steps or (dev_flows is not None and len(dev_flows) != steps):
             raise ValueError("correlate_subset_sequence_device takes two or more frames and one set of planes per step")
         planes = []
         for step in dev_out:
-            planes += list(self._subset_planes(step))
+            planes += list(self._subset_planes(step) if order == 1 else self._subset2_planes(step))
         flows = None
         if dev_flows is not None:
             flat = []
@@ -2388,6 +2534,17 @@ class OpticalFlow:
                 flat += list(pair) if pair is not None else [None, None]
             flows = (C.c_void_p * (2 * steps))(*flat)
         reports, reps = (CorrelationPassReport * max(n, 1))(), (SequenceStepReport * steps)()
+        if order != 1:
+            rc = host_lib().flow2d_host_correlate_subset2_sequence_device(self.handle, (C.c_void_p * len(dev_frames))(*dev_frames),
+                                                                          len(dev_frames), float(lo), float(scale), arr, n, float(min_score),
+                                                                          float(threshold), float(validate_epsilon), int(min_neighbours),
+                                                                          int(radius), int(iterations), float(epsilon), float(max_shift),
+                                                                          float(max_gradient), int(order), float(max_curvature), int(fill),
+                                                                          int(min_state), int(predict_neighbours), float(sequence_max_shift),
+                                                                          (C.c_void_p * (14 * steps))(*planes), reports, reps, flows)
+            if rc:
+                raise Flow2DError(rc, "OpticalFlow2D::CorrelateSubsetSequenceDevice")
+            return list(reports)[:n], list(reps)
         rc = host_lib().flow2d_host_correlate_subset_sequence_device(self.handle, (C.c_void_p * len(dev_frames))(*dev_frames), len(dev_frames),
                                                                      float(lo), float(scale), arr, n, float(min_score), float(threshold),
                                                                      float(validate_epsilon), int(min_neighbours), int(radius),

@@ -736,11 +736,29 @@ OpticalFlow2D::SubsetOptions subset_options(int radius, int iterations, float ep
     o.max_gradient = max_gradient;
     return o;
 }
+OpticalFlow2D::SubsetOptions subset_options(int radius, int iterations, float epsilon, float max_shift, float max_gradient, int order,
+                                            float max_curvature)
+{
+    OpticalFlow2D::SubsetOptions o = subset_options(radius, iterations, epsilon, max_shift, max_gradient);
+    o.order = order;
+    o.max_curvature = max_curvature;
+    return o;
+}
 // eight device planes -- u, v, ux, uy, vx, vy, score, state -- each of which may be null, as may the array
 OpticalFlow2D::SubsetPlanes subset_planes(void* const* p)
 {
     OpticalFlow2D::SubsetPlanes o;
     if (p) o = {dp(p[0]), dp(p[1]), dp(p[2]), dp(p[3]), dp(p[4]), dp(p[5]), dp(p[6]), dp(p[7])};
+    return o;
+}
+// fourteen: those eight, then uxx, uxy, uyy, vxx, vxy, vyy
+constexpr int kSubset2Planes = 14;
+OpticalFlow2D::SubsetPlanes subset2_planes(void* const* p)
+{
+    OpticalFlow2D::SubsetPlanes o;
+    if (p)
+        o = {dp(p[0]), dp(p[1]), dp(p[2]),  dp(p[3]),  dp(p[4]),  dp(p[5]),  dp(p[6]),
+             dp(p[7]), dp(p[8]), dp(p[9]), dp(p[10]), dp(p[11]), dp(p[12]), dp(p[13])};
     return o;
 }
 }  // namespace
@@ -751,33 +769,57 @@ HOST_API int flow2d_host_subset_options_ok(int radius, int iterations, float eps
     return OpticalFlow2D::SubsetOptionsOk(subset_options(radius, iterations, epsilon, max_shift, max_gradient)) ? 1 : 0;
 }
 
+HOST_API int flow2d_host_subset2_options_ok(int radius, int iterations, float epsilon, float max_shift, float max_gradient, int order,
+                                            float max_curvature)
+{
+    return OpticalFlow2D::SubsetOptionsOk(subset_options(radius, iterations, epsilon, max_shift, max_gradient, order, max_curvature)) ? 1 : 0;
+}
+
 // OpticalFlow2D::RefineNodesDevice: device planes of the container's size; dev_out: eight planes (u, v, ux, uy, vx, vy, score, state),
 // each optional.  With a record (host) the call synchronises.  0 on success, 1 for a null or refused argument, 2 when the run failed.
+namespace {
+int refine_nodes_device(flow2d_host_flow* h, void* dev_frame_0, void* dev_frame_1, void* dev_node_u0, void* dev_node_v0, int grid_radius,
+                        int spacing, const OpticalFlow2D::SubsetOptions& subset, const OpticalFlow2D::SubsetPlanes& out,
+                        flow2d_subset_record* record)
+{
+    if (!h || !dev_frame_0 || !dev_frame_1 || !dev_node_u0 || !dev_node_v0 || !OpticalFlow2D::SubsetOptionsOk(subset)) return 1;
+    h->flow.timing_mode = 0;
+    return h->flow.RefineNodesDevice(dp(dev_frame_0), dp(dev_frame_1), dp(dev_node_u0), dp(dev_node_v0), grid_radius, spacing, subset, out,
+                                     record)
+               ? 0
+               : 2;
+}
+}  // namespace
+
 HOST_API int flow2d_host_refine_nodes_device(flow2d_host_flow* h, void* dev_frame_0, void* dev_frame_1, void* dev_node_u0,
                                              void* dev_node_v0, int grid_radius, int spacing, int radius, int iterations, float epsilon,
                                              float max_shift, float max_gradient, void* const* dev_out, flow2d_subset_record* record)
 {
-    const auto subset = subset_options(radius, iterations, epsilon, max_shift, max_gradient);
-    if (!h || !dev_frame_0 || !dev_frame_1 || !dev_node_u0 || !dev_node_v0 || !OpticalFlow2D::SubsetOptionsOk(subset)) return 1;
-    h->flow.timing_mode = 0;
-    return h->flow.RefineNodesDevice(dp(dev_frame_0), dp(dev_frame_1), dp(dev_node_u0), dp(dev_node_v0), grid_radius, spacing, subset,
-                                     subset_planes(dev_out), record)
-               ? 0
-               : 2;
+    return refine_nodes_device(h, dev_frame_0, dev_frame_1, dev_node_u0, dev_node_v0, grid_radius, spacing,
+                               subset_options(radius, iterations, epsilon, max_shift, max_gradient), subset_planes(dev_out), record);
+}
+
+// ... with SubsetOptions::order and max_curvature; dev_out: fourteen planes, the eight and uxx, uxy, uyy, vxx, vxy, vyy.
+HOST_API int flow2d_host_refine_nodes2_device(flow2d_host_flow* h, void* dev_frame_0, void* dev_frame_1, void* dev_node_u0,
+                                              void* dev_node_v0, int grid_radius, int spacing, int radius, int iterations, float epsilon,
+                                              float max_shift, float max_gradient, int order, float max_curvature, void* const* dev_out,
+                                              flow2d_subset_record* record)
+{
+    return refine_nodes_device(h, dev_frame_0, dev_frame_1, dev_node_u0, dev_node_v0, grid_radius, spacing,
+                               subset_options(radius, iterations, epsilon, max_shift, max_gradient, order, max_curvature),
+                               subset2_planes(dev_out), record);
 }
 
 // OpticalFlow2D::CorrelateSubsetDevice: the passes as for flow2d_host_correlate_multipass_device, then the refinement; dev_out as
 // above, reports (optional) one per pass, record (optional).  Synchronises.  0, 1 or 2 as above.
-HOST_API int flow2d_host_correlate_subset_device(flow2d_host_flow* h, void* dev_frame_0, void* dev_frame_1, float lo, float scale,
-                                                 const int* passes, int count, float min_score, float threshold, float epsilon,
-                                                 int min_neighbours, int radius, int iterations, float subset_epsilon, float max_shift,
-                                                 float max_gradient, void* dev_predictor_u, void* dev_predictor_v, void* const* dev_out,
-                                                 OpticalFlow2D::CorrelationPassReport* reports, flow2d_subset_record* record,
-                                                 void* dev_flow_u, void* dev_flow_v)
+namespace {
+int correlate_subset_device(flow2d_host_flow* h, void* dev_frame_0, void* dev_frame_1, float lo, float scale, const int* passes, int count,
+                            float min_score, float threshold, float epsilon, int min_neighbours, const OpticalFlow2D::SubsetOptions& subset,
+                            void* dev_predictor_u, void* dev_predictor_v, const OpticalFlow2D::SubsetPlanes& out,
+                            OpticalFlow2D::CorrelationPassReport* reports, flow2d_subset_record* record, void* dev_flow_u, void* dev_flow_v)
 {
     const auto list = correlation_passes(passes, count);
     const auto validation = validation_options(threshold, epsilon, min_neighbours, 1, 1);
-    const auto subset = subset_options(radius, iterations, subset_epsilon, max_shift, max_gradient);
     if (!h || !dev_frame_0 || !dev_frame_1 || count < 0 || (dev_flow_u == nullptr) != (dev_flow_v == nullptr) ||
         (dev_predictor_u == nullptr) != (dev_predictor_v == nullptr) ||
         !OpticalFlow2D::CorrelationPassesOk(h->width, h->height, lo, scale, list.data(), list.size(), min_score, validation) ||
@@ -785,23 +827,48 @@ HOST_API int flow2d_host_correlate_subset_device(flow2d_host_flow* h, void* dev_
         return 1;
     h->flow.timing_mode = 0;
     return h->flow.CorrelateSubsetDevice(dp(dev_frame_0), dp(dev_frame_1), lo, scale, list.data(), list.size(), min_score, validation, subset,
-                                         dp(dev_predictor_u), dp(dev_predictor_v), subset_planes(dev_out), reports, record,
-                                         dp(dev_flow_u), dp(dev_flow_v))
+                                         dp(dev_predictor_u), dp(dev_predictor_v), out, reports, record, dp(dev_flow_u), dp(dev_flow_v))
                ? 0
                : 2;
+}
+}  // namespace
+
+HOST_API int flow2d_host_correlate_subset_device(flow2d_host_flow* h, void* dev_frame_0, void* dev_frame_1, float lo, float scale,
+                                                 const int* passes, int count, float min_score, float threshold, float epsilon,
+                                                 int min_neighbours, int radius, int iterations, float subset_epsilon, float max_shift,
+                                                 float max_gradient, void* dev_predictor_u, void* dev_predictor_v, void* const* dev_out,
+                                                 OpticalFlow2D::CorrelationPassReport* reports, flow2d_subset_record* record,
+                                                 void* dev_flow_u, void* dev_flow_v)
+{
+    return correlate_subset_device(h, dev_frame_0, dev_frame_1, lo, scale, passes, count, min_score, threshold, epsilon, min_neighbours,
+                                   subset_options(radius, iterations, subset_epsilon, max_shift, max_gradient), dev_predictor_u,
+                                   dev_predictor_v, subset_planes(dev_out), reports, record, dev_flow_u, dev_flow_v);
+}
+
+// ... with SubsetOptions::order and max_curvature; dev_out: fourteen planes.
+HOST_API int flow2d_host_correlate_subset2_device(flow2d_host_flow* h, void* dev_frame_0, void* dev_frame_1, float lo, float scale,
+                                                  const int* passes, int count, float min_score, float threshold, float epsilon,
+                                                  int min_neighbours, int radius, int iterations, float subset_epsilon, float max_shift,
+                                                  float max_gradient, int order, float max_curvature, void* dev_predictor_u,
+                                                  void* dev_predictor_v, void* const* dev_out, OpticalFlow2D::CorrelationPassReport* reports,
+                                                  flow2d_subset_record* record, void* dev_flow_u, void* dev_flow_v)
+{
+    return correlate_subset_device(h, dev_frame_0, dev_frame_1, lo, scale, passes, count, min_score, threshold, epsilon, min_neighbours,
+                                   subset_options(radius, iterations, subset_epsilon, max_shift, max_gradient, order, max_curvature),
+                                   dev_predictor_u, dev_predictor_v, subset2_planes(dev_out), reports, record, dev_flow_u, dev_flow_v);
 }
 
 // OpticalFlow2D::CorrelateSubset on tight host images: nodes -- eight arrays (u, v, ux, uy, vx, vy, score, state; u and v needed, the
 // gradients all or none) -- get the last pass's nw * nh floats each; the rest as for flow2d_host_correlate_multipass.
-HOST_API int flow2d_host_correlate_subset(flow2d_host_flow* h, const float* frame_0, const float* frame_1, const int* passes, int count,
-                                          float min_score, float threshold, float epsilon, int min_neighbours, int radius, int iterations,
-                                          float subset_epsilon, float max_shift, float max_gradient, const float* predictor_u,
-                                          const float* predictor_v, float* const* nodes, OpticalFlow2D::CorrelationPassReport* reports,
-                                          flow2d_subset_record* record, float* flow_u, float* flow_v, float* lo_scale)
+namespace {
+// node_count: 8, or kSubset2Planes with the curvatures behind them
+int correlate_subset(flow2d_host_flow* h, const float* frame_0, const float* frame_1, const int* passes, int count, float min_score,
+                     float threshold, float epsilon, int min_neighbours, const OpticalFlow2D::SubsetOptions& subset, const float* predictor_u,
+                     const float* predictor_v, float* const* nodes, int node_count, OpticalFlow2D::CorrelationPassReport* reports,
+                     flow2d_subset_record* record, float* flow_u, float* flow_v, float* lo_scale)
 {
     const auto list = correlation_passes(passes, count);
     const auto validation = validation_options(threshold, epsilon, min_neighbours, 1, 1);
-    const auto subset = subset_options(radius, iterations, subset_epsilon, max_shift, max_gradient);
     if (!h || !frame_0 || !frame_1 || !nodes || !nodes[0] || !nodes[1] || count < 0 || (flow_u == nullptr) != (flow_v == nullptr) ||
         (predictor_u == nullptr) != (predictor_v == nullptr))
         return 1;
@@ -817,19 +884,45 @@ HOST_API int flow2d_host_correlate_subset(flow2d_host_flow* h, const float* fram
     size_t nw = 0, nh = 0;
     flow2d_correlation_grid(h->width, h->height, list.back().radius, list.back().spacing, &nw, &nh);
     std::vector<Data2D> images;
-    for (int k = 0; k < 8; ++k) images.emplace_back(nw, nh);
-    Data2D* wanted[8];
-    for (int k = 0; k < 8; ++k) wanted[k] = nodes[k] ? &images[k] : nullptr;
+    for (int k = 0; k < node_count; ++k) images.emplace_back(nw, nh);
+    Data2D* wanted[kSubset2Planes] = {};
+    for (int k = 0; k < node_count; ++k) wanted[k] = nodes[k] ? &images[k] : nullptr;
     h->flow.CorrelateSubset(*f0, *f1, list.data(), list.size(), min_score, validation, subset, wanted, reports, record, fu, fv, pu, pv);
     const int rc = im.Finish(h->flow);
     if (rc) return rc;
-    for (int k = 0; k < 8; ++k)
+    for (int k = 0; k < node_count; ++k)
         if (nodes[k]) std::memcpy(nodes[k], images[k].DataPtr(), nw * nh * sizeof(float));
     if (lo_scale) {
         lo_scale[0] = lo;
         lo_scale[1] = scale;
     }
     return 0;
+}
+}  // namespace
+
+HOST_API int flow2d_host_correlate_subset(flow2d_host_flow* h, const float* frame_0, const float* frame_1, const int* passes, int count,
+                                          float min_score, float threshold, float epsilon, int min_neighbours, int radius, int iterations,
+                                          float subset_epsilon, float max_shift, float max_gradient, const float* predictor_u,
+                                          const float* predictor_v, float* const* nodes, OpticalFlow2D::CorrelationPassReport* reports,
+                                          flow2d_subset_record* record, float* flow_u, float* flow_v, float* lo_scale)
+{
+    return correlate_subset(h, frame_0, frame_1, passes, count, min_score, threshold, epsilon, min_neighbours,
+                            subset_options(radius, iterations, subset_epsilon, max_shift, max_gradient), predictor_u, predictor_v, nodes, 8,
+                            reports, record, flow_u, flow_v, lo_scale);
+}
+
+// ... with SubsetOptions::order and max_curvature; nodes: fourteen arrays, the six curvatures all or none.
+HOST_API int flow2d_host_correlate_subset2(flow2d_host_flow* h, const float* frame_0, const float* frame_1, const int* passes, int count,
+                                           float min_score, float threshold, float epsilon, int min_neighbours, int radius, int iterations,
+                                           float subset_epsilon, float max_shift, float max_gradient, int order, float max_curvature,
+                                           const float* predictor_u, const float* predictor_v, float* const* nodes,
+                                           OpticalFlow2D::CorrelationPassReport* reports, flow2d_subset_record* record, float* flow_u,
+                                           float* flow_v, float* lo_scale)
+{
+    const auto subset = subset_options(radius, iterations, subset_epsilon, max_shift, max_gradient, order, max_curvature);
+    if (!OpticalFlow2D::SubsetOptionsOk(subset)) return 1;
+    return correlate_subset(h, frame_0, frame_1, passes, count, min_score, threshold, epsilon, min_neighbours, subset, predictor_u,
+                            predictor_v, nodes, subset.order == 2 ? kSubset2Planes : 8, reports, record, flow_u, flow_v, lo_scale);
 }
 
 // ---- subset refinement over a sequence ------------------------------------------------------------------------------------------
@@ -853,20 +946,37 @@ HOST_API int flow2d_host_sequence_options_ok(int fill, int min_state, int min_ne
 
 // OpticalFlow2D::RefineNodesFromDevice: dev_start -- six device planes u, v, ux, uy, vx, vy, all needed; the rest as for
 // flow2d_host_refine_nodes_device.
-HOST_API int flow2d_host_refine_nodes_from_device(flow2d_host_flow* h, void* dev_frame_0, void* dev_frame_1, void* const* dev_start,
-                                                  int grid_radius, int spacing, int radius, int iterations, float epsilon, float max_shift,
-                                                  float max_gradient, void* const* dev_out, flow2d_subset_record* record)
+namespace {
+int refine_nodes_from_device(flow2d_host_flow* h, void* dev_frame_0, void* dev_frame_1, void* const* dev_start, int grid_radius, int spacing,
+                             const OpticalFlow2D::SubsetOptions& subset, const OpticalFlow2D::SubsetPlanes& out, flow2d_subset_record* record)
 {
-    const auto subset = subset_options(radius, iterations, epsilon, max_shift, max_gradient);
     if (!h || !dev_frame_0 || !dev_frame_1 || !dev_start || !OpticalFlow2D::SubsetOptionsOk(subset)) return 1;
     for (int k = 0; k < 6; ++k)
         if (!dev_start[k]) return 1;
     OpticalFlow2D::SubsetPlanes start;
     start = {dp(dev_start[0]), dp(dev_start[1]), dp(dev_start[2]), dp(dev_start[3]), dp(dev_start[4]), dp(dev_start[5]), 0, 0};
     h->flow.timing_mode = 0;
-    return h->flow.RefineNodesFromDevice(dp(dev_frame_0), dp(dev_frame_1), start, grid_radius, spacing, subset, subset_planes(dev_out), record)
-               ? 0
-               : 2;
+    return h->flow.RefineNodesFromDevice(dp(dev_frame_0), dp(dev_frame_1), start, grid_radius, spacing, subset, out, record) ? 0 : 2;
+}
+}  // namespace
+
+HOST_API int flow2d_host_refine_nodes_from_device(flow2d_host_flow* h, void* dev_frame_0, void* dev_frame_1, void* const* dev_start,
+                                                  int grid_radius, int spacing, int radius, int iterations, float epsilon, float max_shift,
+                                                  float max_gradient, void* const* dev_out, flow2d_subset_record* record)
+{
+    return refine_nodes_from_device(h, dev_frame_0, dev_frame_1, dev_start, grid_radius, spacing,
+                                    subset_options(radius, iterations, epsilon, max_shift, max_gradient), subset_planes(dev_out), record);
+}
+
+// ... with SubsetOptions::order and max_curvature; dev_out: fourteen planes.  The start's curvatures are 0.
+HOST_API int flow2d_host_refine_nodes_from2_device(flow2d_host_flow* h, void* dev_frame_0, void* dev_frame_1, void* const* dev_start,
+                                                   int grid_radius, int spacing, int radius, int iterations, float epsilon, float max_shift,
+                                                   float max_gradient, int order, float max_curvature, void* const* dev_out,
+                                                   flow2d_subset_record* record)
+{
+    return refine_nodes_from_device(h, dev_frame_0, dev_frame_1, dev_start, grid_radius, spacing,
+                                    subset_options(radius, iterations, epsilon, max_shift, max_gradient, order, max_curvature),
+                                    subset2_planes(dev_out), record);
 }
 
 // OpticalFlow2D::SequenceStepReport as the facade hands it out
@@ -875,17 +985,17 @@ static_assert(sizeof(OpticalFlow2D::SequenceStepReport) == 64 + 64 * OpticalFlow
 // OpticalFlow2D::CorrelateSubsetSequenceDevice: dev_frames -- `frames` device planes, the first the reference; dev_out -- eight planes
 // per step (u, v, ux, uy, vx, vy, score, state; only the score may be null); dev_flows (optional) -- two per step, each pair optional;
 // reports (optional) one per pass of step 1, steps (optional) one per step.  Synchronises.  0, 1 or 2 as above.
-HOST_API int flow2d_host_correlate_subset_sequence_device(flow2d_host_flow* h, void* const* dev_frames, int frames, float lo, float scale,
-                                                          const int* passes, int count, float min_score, float threshold, float epsilon,
-                                                          int min_neighbours, int radius, int iterations, float subset_epsilon,
-                                                          float max_shift, float max_gradient, int fill, int min_state,
-                                                          int predict_neighbours, float sequence_max_shift, void* const* dev_out,
-                                                          OpticalFlow2D::CorrelationPassReport* reports,
-                                                          OpticalFlow2D::SequenceStepReport* steps, void* const* dev_flows)
+namespace {
+// planes_per_step: 8, or kSubset2Planes with the curvatures behind them (which may be null)
+int correlate_subset_sequence_device(flow2d_host_flow* h, void* const* dev_frames, int frames, float lo, float scale, const int* passes,
+                                     int count, float min_score, float threshold, float epsilon, int min_neighbours,
+                                     const OpticalFlow2D::SubsetOptions& subset, int fill, int min_state, int predict_neighbours,
+                                     float sequence_max_shift, void* const* dev_out, int planes_per_step,
+                                     OpticalFlow2D::CorrelationPassReport* reports, OpticalFlow2D::SequenceStepReport* steps,
+                                     void* const* dev_flows)
 {
     const auto list = correlation_passes(passes, count);
     const auto validation = validation_options(threshold, epsilon, min_neighbours, 1, 1);
-    const auto subset = subset_options(radius, iterations, subset_epsilon, max_shift, max_gradient);
     const auto sequence = sequence_options(fill, min_state, predict_neighbours, sequence_max_shift);
     if (!h || !dev_frames || frames < 2 || count < 0 || !dev_out ||
         !OpticalFlow2D::CorrelationPassesOk(h->width, h->height, lo, scale, list.data(), list.size(), min_score, validation) ||
@@ -899,9 +1009,10 @@ HOST_API int flow2d_host_correlate_subset_sequence_device(flow2d_host_flow* h, v
     }
     std::vector<OpticalFlow2D::SubsetPlanes> out(step_count);
     for (size_t k = 0; k < step_count; ++k) {
-        out[k] = subset_planes(dev_out + 8 * k);
+        void* const* step = dev_out + planes_per_step * k;
+        out[k] = planes_per_step == 8 ? subset_planes(step) : subset2_planes(step);
         for (int c = 0; c < 8; ++c)
-            if (c != 6 && !dev_out[8 * k + c]) return 1;
+            if (c != 6 && !step[c]) return 1;
         for (int c = 0; dev_flows && c < 2; ++c) flow_list[2 * k + c] = dp(dev_flows[2 * k + c]);
         if ((flow_list[2 * k] == 0) != (flow_list[2 * k + 1] == 0)) return 1;
     }
@@ -911,19 +1022,48 @@ HOST_API int flow2d_host_correlate_subset_sequence_device(flow2d_host_flow* h, v
                ? 0
                : 2;
 }
+}  // namespace
+
+HOST_API int flow2d_host_correlate_subset_sequence_device(flow2d_host_flow* h, void* const* dev_frames, int frames, float lo, float scale,
+                                                          const int* passes, int count, float min_score, float threshold, float epsilon,
+                                                          int min_neighbours, int radius, int iterations, float subset_epsilon,
+                                                          float max_shift, float max_gradient, int fill, int min_state,
+                                                          int predict_neighbours, float sequence_max_shift, void* const* dev_out,
+                                                          OpticalFlow2D::CorrelationPassReport* reports,
+                                                          OpticalFlow2D::SequenceStepReport* steps, void* const* dev_flows)
+{
+    return correlate_subset_sequence_device(h, dev_frames, frames, lo, scale, passes, count, min_score, threshold, epsilon, min_neighbours,
+                                            subset_options(radius, iterations, subset_epsilon, max_shift, max_gradient), fill, min_state,
+                                            predict_neighbours, sequence_max_shift, dev_out, 8, reports, steps, dev_flows);
+}
+
+// ... with SubsetOptions::order and max_curvature; dev_out: fourteen planes per step, the six curvatures all or none.
+HOST_API int flow2d_host_correlate_subset2_sequence_device(flow2d_host_flow* h, void* const* dev_frames, int frames, float lo, float scale,
+                                                           const int* passes, int count, float min_score, float threshold, float epsilon,
+                                                           int min_neighbours, int radius, int iterations, float subset_epsilon,
+                                                           float max_shift, float max_gradient, int order, float max_curvature, int fill,
+                                                           int min_state, int predict_neighbours, float sequence_max_shift,
+                                                           void* const* dev_out, OpticalFlow2D::CorrelationPassReport* reports,
+                                                           OpticalFlow2D::SequenceStepReport* steps, void* const* dev_flows)
+{
+    return correlate_subset_sequence_device(h, dev_frames, frames, lo, scale, passes, count, min_score, threshold, epsilon, min_neighbours,
+                                            subset_options(radius, iterations, subset_epsilon, max_shift, max_gradient, order, max_curvature),
+                                            fill, min_state, predict_neighbours, sequence_max_shift, dev_out, kSubset2Planes, reports, steps,
+                                            dev_flows);
+}
 
 // OpticalFlow2D::CorrelateSubsetSequence on tight host images: frames -- `count_frames` images; nodes -- eight arrays per step, which
 // get the last pass's nw * nh floats each (only a score may be null); flows (optional) -- two images per step, each pair optional.
-HOST_API int flow2d_host_correlate_subset_sequence(flow2d_host_flow* h, const float* const* frames, int count_frames, const int* passes,
-                                                   int count, float min_score, float threshold, float epsilon, int min_neighbours, int radius,
-                                                   int iterations, float subset_epsilon, float max_shift, float max_gradient, int fill,
-                                                   int min_state, int predict_neighbours, float sequence_max_shift, float* const* nodes,
-                                                   OpticalFlow2D::CorrelationPassReport* reports, OpticalFlow2D::SequenceStepReport* steps,
-                                                   float* const* flows, float* lo_scale)
+namespace {
+// per_step: 8 node arrays per step, or kSubset2Planes with the curvatures behind them
+int correlate_subset_sequence(flow2d_host_flow* h, const float* const* frames, int count_frames, const int* passes, int count, float min_score,
+                              float threshold, float epsilon, int min_neighbours, const OpticalFlow2D::SubsetOptions& subset, int fill,
+                              int min_state, int predict_neighbours, float sequence_max_shift, float* const* nodes, size_t per_step,
+                              OpticalFlow2D::CorrelationPassReport* reports, OpticalFlow2D::SequenceStepReport* steps, float* const* flows,
+                              float* lo_scale)
 {
     const auto list = correlation_passes(passes, count);
     const auto validation = validation_options(threshold, epsilon, min_neighbours, 1, 1);
-    const auto subset = subset_options(radius, iterations, subset_epsilon, max_shift, max_gradient);
     const auto sequence = sequence_options(fill, min_state, predict_neighbours, sequence_max_shift);
     if (!h || !frames || count_frames < 2 || !nodes || count < 0) return 1;
     const size_t n = static_cast<size_t>(count_frames), step_count = n - 1;
@@ -931,7 +1071,7 @@ HOST_API int flow2d_host_correlate_subset_sequence(flow2d_host_flow* h, const fl
         if (!frames[k]) return 1;
     for (size_t k = 0; k < step_count; ++k) {
         for (int c = 0; c < 8; ++c)
-            if (c != 6 && !nodes[8 * k + c]) return 1;
+            if (c != 6 && !nodes[per_step * k + c]) return 1;
         if (flows && (flows[2 * k] == nullptr) != (flows[2 * k + 1] == nullptr)) return 1;
     }
     HostImages im(h);
@@ -946,21 +1086,50 @@ HOST_API int flow2d_host_correlate_subset_sequence(flow2d_host_flow* h, const fl
     size_t nw = 0, nh = 0;
     flow2d_correlation_grid(h->width, h->height, list.back().radius, list.back().spacing, &nw, &nh);
     std::vector<Data2D> images;
-    images.reserve(8 * step_count);
-    for (size_t k = 0; k < 8 * step_count; ++k) images.emplace_back(nw, nh);
-    std::vector<Data2D*> wanted(8 * step_count);
-    for (size_t k = 0; k < 8 * step_count; ++k) wanted[k] = nodes[k] ? &images[k] : nullptr;
+    images.reserve(per_step * step_count);
+    for (size_t k = 0; k < per_step * step_count; ++k) images.emplace_back(nw, nh);
+    std::vector<Data2D*> wanted(per_step * step_count);
+    for (size_t k = 0; k < per_step * step_count; ++k) wanted[k] = nodes[k] ? &images[k] : nullptr;
     h->flow.CorrelateSubsetSequence(in.data(), n, list.data(), list.size(), min_score, validation, subset, sequence, wanted.data(), reports,
                                     steps, flows ? flow_images.data() : nullptr);
     const int rc = im.Finish(h->flow);
     if (rc) return rc;
-    for (size_t k = 0; k < 8 * step_count; ++k)
+    for (size_t k = 0; k < per_step * step_count; ++k)
         if (nodes[k]) std::memcpy(nodes[k], images[k].DataPtr(), nw * nh * sizeof(float));
     if (lo_scale) {
         lo_scale[0] = lo;
         lo_scale[1] = scale;
     }
     return 0;
+}
+}  // namespace
+
+HOST_API int flow2d_host_correlate_subset_sequence(flow2d_host_flow* h, const float* const* frames, int count_frames, const int* passes,
+                                                   int count, float min_score, float threshold, float epsilon, int min_neighbours, int radius,
+                                                   int iterations, float subset_epsilon, float max_shift, float max_gradient, int fill,
+                                                   int min_state, int predict_neighbours, float sequence_max_shift, float* const* nodes,
+                                                   OpticalFlow2D::CorrelationPassReport* reports, OpticalFlow2D::SequenceStepReport* steps,
+                                                   float* const* flows, float* lo_scale)
+{
+    return correlate_subset_sequence(h, frames, count_frames, passes, count, min_score, threshold, epsilon, min_neighbours,
+                                     subset_options(radius, iterations, subset_epsilon, max_shift, max_gradient), fill, min_state,
+                                     predict_neighbours, sequence_max_shift, nodes, 8, reports, steps, flows, lo_scale);
+}
+
+// ... with SubsetOptions::order and max_curvature; nodes: fourteen arrays per step, the six curvatures all or none.
+HOST_API int flow2d_host_correlate_subset2_sequence(flow2d_host_flow* h, const float* const* frames, int count_frames, const int* passes,
+                                                    int count, float min_score, float threshold, float epsilon, int min_neighbours, int radius,
+                                                    int iterations, float subset_epsilon, float max_shift, float max_gradient, int order,
+                                                    float max_curvature, int fill, int min_state, int predict_neighbours,
+                                                    float sequence_max_shift, float* const* nodes,
+                                                    OpticalFlow2D::CorrelationPassReport* reports, OpticalFlow2D::SequenceStepReport* steps,
+                                                    float* const* flows, float* lo_scale)
+{
+    const auto subset = subset_options(radius, iterations, subset_epsilon, max_shift, max_gradient, order, max_curvature);
+    if (!OpticalFlow2D::SubsetOptionsOk(subset)) return 1;
+    return correlate_subset_sequence(h, frames, count_frames, passes, count, min_score, threshold, epsilon, min_neighbours, subset, fill,
+                                     min_state, predict_neighbours, sequence_max_shift, nodes, subset.order == 2 ? kSubset2Planes : 8, reports,
+                                     steps, flows, lo_scale);
 }
 
 // ---- strain on the node grid ---------------------------------------------------------------------------------------------------

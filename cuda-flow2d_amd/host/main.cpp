@@ -80,6 +80,9 @@
 // replacement so that every node has a start, then flow2d_subset_refine_2d -- the affine Gauss-Newton iteration of digital image
 // correlation on the unquantised frames): node-u, node-v and the forward files then hold the refined field, node-score the
 // subsets' scores, and node-ux, node-uy, node-vx, node-vy (the displacement gradients) and node-state are written beside them.
+// With --subset-order 2 [--subset-max-curvature C, > 0, default 0.05] the refinement is the second-order one
+// (flow2d_subset_refine2_2d, R from 2): node-uxx, node-uxy, node-uyy, node-vxx, node-vxy and node-vyy are written beside the node files
+// and one more line, "SubsetOrder: {json}", is printed; --subset-order 1 is the run without the option.
 // One line "Subset: {json}" -- the options, the grid, "lo", "scale" and the record's "nodes", "converged", "unconverged", "strayed",
 // "flat", "no_input", "iterations_run" -- is printed in place of the "Correlation:" / "CorrelationPasses:" line.  Without the option
 // nothing changes.
@@ -176,7 +179,7 @@ int main(int argc, char** argv)
     bool subset_refine = false, subset_option = false;
     OpticalFlow2D::SequenceOptions sequence;  // --subset-previous PREFIX and its options
     std::string subset_previous;
-    bool sequence_option = false, subset_max_shift_given = false;
+    bool sequence_option = false, subset_max_shift_given = false, subset_curvature_given = false;
     OpticalFlow2D::StrainOptions node_strain;  // --subset-strain M and --strain-order, --strain-min-nodes
     bool subset_strain = false, strain_option = false;
     OpticalFlow2D::ValidationOptions validation;                     // --validate-threshold / -epsilon / -min-neighbours / -flag-only
@@ -439,6 +442,28 @@ int main(int argc, char** argv)
             subset_option = true;
             ++i;
         }
+        else if (!std::strcmp(argv[i], "--subset-order")) {
+            char* end = nullptr;
+            const long n = (i + 1 < argc) ? std::strtol(argv[i + 1], &end, 10) : 0;
+            if (i + 1 >= argc || end == argv[i + 1] || *end != '\0' || (n != 1 && n != 2)) {
+                std::printf("--subset-order takes 1 or 2.\n");
+                return 5;
+            }
+            subset.order = static_cast<int>(n);
+            subset_option = true;
+            ++i;
+        }
+        else if (!std::strcmp(argv[i], "--subset-max-curvature")) {
+            char* end = nullptr;
+            const float value = (i + 1 < argc) ? std::strtof(argv[i + 1], &end) : 0.f;
+            if (i + 1 >= argc || end == argv[i + 1] || *end != '\0' || !std::isfinite(value) || !(value > 0.f)) {
+                std::printf("--subset-max-curvature takes a finite number > 0.\n");
+                return 5;
+            }
+            subset.max_curvature = value;
+            subset_option = subset_curvature_given = true;
+            ++i;
+        }
         else if (!std::strcmp(argv[i], "--subset-previous")) {
             if (i + 1 >= argc || !argv[i + 1][0]) {
                 std::printf("--subset-previous takes the prefix of the previous step's node files.\n");
@@ -543,6 +568,11 @@ int main(int argc, char** argv)
         return 5;
     }
 
+    if (subset_refine && ((subset.order == 2 && subset.radius < FLOW2D_SUBSET2_MIN_RADIUS) || (subset_curvature_given && subset.order != 2))) {
+        std::printf("--subset-order 2 takes a subset radius of %d at least, and --subset-max-curvature belongs to it.\n",
+                    FLOW2D_SUBSET2_MIN_RADIUS);
+        return 5;
+    }
     if ((!subset_previous.empty() || sequence_option) && !(subset_refine && !subset_previous.empty())) {
         std::printf("--subset-previous PREFIX continues a sequence of --subset-refine runs, and --subset-fill, --subset-min-state and "
                     "--subset-predict-neighbours belong to it.\n");
@@ -792,11 +822,13 @@ int main(int argc, char** argv)
                 DestroyDeviceContext();
                 return 4;
             }
-            const char* names[8] = {"node-u", "node-v", "node-ux", "node-uy", "node-vx", "node-vy", "node-score", "node-state"};
+            const char* names[14] = {"node-u",     "node-v",   "node-ux",  "node-uy",  "node-vx",  "node-vy",  "node-score",
+                                     "node-state", "node-uxx", "node-uxy", "node-uyy", "node-vxx", "node-vxy", "node-vyy"};
+            const int node_images = subset.order == 2 ? 14 : 8;  // --subset-order 2: the six curvatures beside the eight
             std::vector<Data2D> images;
-            for (int k = 0; k < 8; ++k) images.emplace_back(nw, nh);
-            Data2D* nodes[8];
-            for (int k = 0; k < 8; ++k) nodes[k] = &images[k];
+            for (int k = 0; k < node_images; ++k) images.emplace_back(nw, nh);
+            Data2D* nodes[14] = {};
+            for (int k = 0; k < node_images; ++k) nodes[k] = &images[k];
             flow2d_subset_record record = {};
             const std::string size = "-" + std::to_string(nw) + "-" + std::to_string(nh) + ".raw";
             if (!subset_previous.empty()) {
@@ -835,7 +867,8 @@ int main(int argc, char** argv)
                                              predicted ? &prior_v : nullptr);
             }
             if (optical_flow.LastRunSucceeded()) {
-                for (int k = 0; k < 8; ++k) images[k].WriteRAWToFileF32((output_path + counter + names[k] + size).c_str());
+                for (int k = 0; k < node_images; ++k) images[k].WriteRAWToFileF32((output_path + counter + names[k] + size).c_str());
+                if (subset.order == 2) std::printf("SubsetOrder: {\"order\": 2, \"max_curvature\": %.9g}\n", subset.max_curvature);
                 std::printf("Subset: {\"radius\": %d, \"iterations\": %d, \"epsilon\": %.9g, \"max_shift\": %.9g, \"max_gradient\": %.9g, "
                             "\"passes\": %zu, \"grid_radius\": %d, \"spacing\": %d, \"nw\": %zu, \"nh\": %zu, \"lo\": %.9g, \"scale\": %.9g, "
                             "\"nodes\": %llu, \"converged\": %llu, \"unconverged\": %llu, \"strayed\": %llu, \"flat\": %llu, "

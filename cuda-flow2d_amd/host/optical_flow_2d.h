@@ -334,11 +334,16 @@ public:
     struct SubsetOptions {
         int radius = 7, iterations = 20;
         float epsilon = 1e-3f, max_shift = 2.f, max_gradient = 0.5f;
+        // order 2: the twelve-parameter refinement (flow2d_subset_refine2_2d) in every call that refines, radius from 2; a
+        // curvature beyond max_curvature (per pixel; a bound, not a tuned value) strays.  Order 1 takes the calls it always took.
+        int order = 1;
+        float max_curvature = 0.05f;
     };
     struct SubsetPlanes {
         DevicePtr u = 0, v = 0;                    // both or neither: without them planes of the object's own are written
         DevicePtr ux = 0, uy = 0, vx = 0, vy = 0;  // the four gradients: all or none
         DevicePtr score = 0, state = 0;            // each optional
+        DevicePtr uxx = 0, uxy = 0, uyy = 0, vxx = 0, vxy = 0, vyy = 0;  // the six curvatures, order 2 only: all or none
     };
     // prints what is wrong; needs no device
     static bool SubsetOptionsOk(const SubsetOptions& subset);
@@ -358,7 +363,8 @@ public:
                                CorrelationPassReport* reports_out, flow2d_subset_record* record_out, DevicePtr dev_flow_u = 0,
                                DevicePtr dev_flow_v = 0);
     // The host-image form (the CLI's --subset-refine): lo and scale from CorrelationRange; nodes[8] -- u, v, ux, uy, vx, vy, score,
-    // state; u and v are needed, the gradients come all or none -- are images of the LAST pass's grid.
+    // state; u and v are needed, the gradients come all or none -- are images of the LAST pass's grid.  With subset.order == 2 this
+    // and the two other host-image forms below take nodes[14] per step: those eight, then uxx, uxy, uyy, vxx, vxy, vyy, all or none.
     void CorrelateSubset(Data2D& frame_0, Data2D& frame_1, const CorrelationPass* passes, size_t count, float min_score,
                          const ValidationOptions& validation, const SubsetOptions& subset, Data2D* const* nodes,
                          CorrelationPassReport* reports_out, flow2d_subset_record* record_out, Data2D* flow_u = nullptr,
@@ -367,7 +373,8 @@ public:
     // DIC over a loading sequence: every frame is correlated against the same reference frame, and from the second step on the
     // start of a step is the previous step's deformation, gradients included (flow2d_predict_nodes_2d, then
     // flow2d_subset_refine_from_2d), so that no window search runs and a subset that has rotated or stretched beyond a rigid
-    // window's reach is still followed.
+    // window's reach is still followed.  At order 2 the steps after the first start from the prediction's six first-order planes
+    // with zero curvatures (flow2d_predict_nodes_2d knows no curvature; the refinement finds it again in about one iteration more).
     // RefineNodesDevice started from a whole deformation: `start` gives u, v and the four gradients (score and state are not looked
     // at); the rest as there.
     bool RefineNodesFromDevice(DevicePtr dev_frame_0, DevicePtr dev_frame_1, const SubsetPlanes& start, int grid_radius, int spacing,

@@ -734,16 +734,44 @@ bool OpticalFlow2D::QueueCorrelationPasses(DevicePtr dev_frame_0, DevicePtr dev_
     return !CheckFlow2DError(flow2d_synchronize(context_), "flow2d_synchronize") && ok;
 }
 
+namespace {
+// The node images of the host forms: eight -- u, v, ux, uy, vx, vy, score, state --, and at order 2 the six curvatures behind them.
+int NodeImages(const OpticalFlow2D::SubsetOptions& subset) { return subset.order == 2 ? 14 : 8; }
+// Whether the curvature images (order 2) come all or none.
+bool CurvatureImagesOk(Data2D* const* nodes, int count)
+{
+    for (int k = 9; k < count; ++k)
+        if ((nodes[k] != nullptr) != (nodes[8] != nullptr)) return false;
+    return true;
+}
+OpticalFlow2D::SubsetPlanes NodePlanes(const DevicePtr* d, int count)
+{
+    OpticalFlow2D::SubsetPlanes out = {d[0], d[1], d[2], d[3], d[4], d[5], d[6], d[7]};
+    if (count == 14) {
+        out.uxx = d[8];
+        out.uxy = d[9];
+        out.uyy = d[10];
+        out.vxx = d[11];
+        out.vxy = d[12];
+        out.vyy = d[13];
+    }
+    return out;
+}
+}  // namespace
+
 bool OpticalFlow2D::SubsetOptionsOk(const SubsetOptions& subset)
 {
     if (subset.radius >= 1 && subset.radius <= FLOW2D_SUBSET_MAX_RADIUS && subset.iterations >= 1 &&
         subset.iterations <= FLOW2D_SUBSET_MAX_ITERATIONS && std::isfinite(subset.epsilon) && subset.epsilon >= 0.f &&
-        std::isfinite(subset.max_shift) && subset.max_shift > 0.f && std::isfinite(subset.max_gradient) && subset.max_gradient > 0.f)
+        std::isfinite(subset.max_shift) && subset.max_shift > 0.f && std::isfinite(subset.max_gradient) && subset.max_gradient > 0.f &&
+        (subset.order == 1 || (subset.order == 2 && subset.radius >= FLOW2D_SUBSET2_MIN_RADIUS)) && std::isfinite(subset.max_curvature) &&
+        subset.max_curvature > 0.f)
         return true;
     std::printf("Error: subset refinement takes a radius of 1 .. %d (%d), 1 .. %d iterations (%d), a finite epsilon >= 0 (%g), a finite "
-                "largest shift > 0 (%g) and a finite largest gradient > 0 (%g).\n",
+                "largest shift > 0 (%g) and a finite largest gradient > 0 (%g); an order of 1 or 2 (%d), at order 2 a radius from %d, and a "
+                "finite largest curvature > 0 (%g).\n",
                 FLOW2D_SUBSET_MAX_RADIUS, subset.radius, FLOW2D_SUBSET_MAX_ITERATIONS, subset.iterations, subset.epsilon, subset.max_shift,
-                subset.max_gradient);
+                subset.max_gradient, subset.order, FLOW2D_SUBSET2_MIN_RADIUS, subset.max_curvature);
     return false;
 }
 
@@ -758,10 +786,15 @@ bool OpticalFlow2D::QueueRefineNodes(DevicePtr dev_frame_0, DevicePtr dev_frame_
         std::printf("Error: a %zu x %zu frame holds no node grid of radius %d and spacing %d.\n", W, H, grid_radius, spacing);
         return false;
     }
-    const bool gradients = out.ux != 0;
+    const bool gradients = out.ux != 0, curvatures = out.uxx != 0;
     if (!IsInitialized() || !dev_frame_0 || !dev_frame_1 || !dev_node_u0 || !dev_node_v0 || (out.u == 0) != (out.v == 0) ||
-        (out.uy != 0) != gradients || (out.vx != 0) != gradients || (out.vy != 0) != gradients)
+        (out.uy != 0) != gradients || (out.vx != 0) != gradients || (out.vy != 0) != gradients || (out.uxy != 0) != curvatures ||
+        (out.uyy != 0) != curvatures || (out.vxx != 0) != curvatures || (out.vxy != 0) != curvatures || (out.vyy != 0) != curvatures)
         return false;
+    if (curvatures && subset.order != 2) {
+        std::printf("Error: '%s': curvature planes are written by the second-order refinement only.\n", GetName());
+        return false;
+    }
     if (RefuseGroup("subset refinement")) return false;
     if (!EnsurePlanes(subset_planes_, 4)) return false;
     const DevicePtr u = out.u ? out.u : subset_planes_[2], v = out.v ? out.v : subset_planes_[3];
@@ -770,7 +803,19 @@ bool OpticalFlow2D::QueueRefineNodes(DevicePtr dev_frame_0, DevicePtr dev_frame_
     auto plane = [](DevicePtr p) { return p ? AsPlane(p) : nullptr; };
     // (the node planes are containers: the frames' pitch; the entry refuses planes that meet)
     bool ok;
-    if (start_gradients)
+    if (subset.order == 2) {
+        // the start: the gradients where the caller has them, no curvatures (0)
+        const float* start[4] = {nullptr, nullptr, nullptr, nullptr};
+        for (int k = 0; start_gradients && k < 4; ++k) start[k] = plane(start_gradients[k]);
+        float* const out_gradients[4] = {plane(out.ux), plane(out.uy), plane(out.vx), plane(out.vy)};
+        float* const out_curvatures[6] = {plane(out.uxx), plane(out.uxy), plane(out.uyy), plane(out.vxx), plane(out.vxy), plane(out.vyy)};
+        ok = !CheckFlow2DError(flow2d_subset_refine2_2d(context_, AsPlane(dev_frame_0), AsPlane(dev_frame_1), W, H, pitch,
+                                                        AsPlane(dev_node_u0), AsPlane(dev_node_v0), start_gradients ? start : nullptr, nullptr,
+                                                        nw, nh, pitch, grid_radius, spacing, subset.radius, subset.iterations, subset.epsilon,
+                                                        subset.max_shift, subset.max_gradient, subset.max_curvature, AsPlane(u), AsPlane(v),
+                                                        out_gradients, out_curvatures, plane(out.score), plane(out.state), record),
+                               "flow2d_subset_refine2_2d");
+    } else if (start_gradients)
         ok = !CheckFlow2DError(flow2d_subset_refine_from_2d(context_, AsPlane(dev_frame_0), AsPlane(dev_frame_1), W, H, pitch,
                                                             AsPlane(dev_node_u0), AsPlane(dev_node_v0), plane(start_gradients[0]),
                                                             plane(start_gradients[1]), plane(start_gradients[2]),
@@ -858,10 +903,12 @@ void OpticalFlow2D::CorrelateSubset(Data2D& frame_0, Data2D& frame_1, const Corr
         return;
     const bool gradients = nodes[2] != nullptr;
     if ((nodes[3] != nullptr) != gradients || (nodes[4] != nullptr) != gradients || (nodes[5] != nullptr) != gradients) return;
+    const int images = NodeImages(subset);
+    if (!CurvatureImagesOk(nodes, images)) return;
     CallPlanes planes(context_, dev_container_size_, GetName(), "frame / flow");
     planes.Add(&frame_0, CallPlanes::In).Add(&frame_1, CallPlanes::In).Add(flow_u, CallPlanes::Out).Add(flow_v, CallPlanes::Out);
     // the node planes: containers with no image of their size behind them, downloaded below
-    for (int k = 0; k < 8; ++k) planes.Add(nullptr, CallPlanes::Out, nodes[k] != nullptr);
+    for (int k = 0; k < images; ++k) planes.Add(nullptr, CallPlanes::Out, nodes[k] != nullptr);
     if (predictor_u) planes.Add(predictor_u, CallPlanes::In).Add(predictor_v, CallPlanes::In);
     if (!planes.SizesMatch()) return;
     float lo = 0.f, scale = 1.f;
@@ -870,19 +917,19 @@ void OpticalFlow2D::CorrelateSubset(Data2D& frame_0, Data2D& frame_1, const Corr
     if (!CorrelationPassesOk(W, H, lo, scale, passes, count, min_score, validation) || !SubsetOptionsOk(subset)) return;
     size_t nw = 0, nh = 0;
     flow2d_correlation_grid(W, H, passes[count - 1].radius, passes[count - 1].spacing, &nw, &nh);
-    for (int k = 0; k < 8; ++k)
+    for (int k = 0; k < images; ++k)
         if (nodes[k] && (nodes[k]->Width() != nw || nodes[k]->Height() != nh)) {
             std::printf("Error: '%s': the node images are not %zu x %zu.\n", GetName(), nw, nh);
             return;
         }
     HostCall call(context_, last_total_ms_, planes.Allocate());
     const DevicePtr* d = planes.data();
-    const SubsetPlanes out = {d[4], d[5], d[6], d[7], d[8], d[9], d[10], d[11]};
+    const SubsetPlanes out = NodePlanes(d + 4, images);
     bool ok = planes.Upload() &&
-              CorrelateSubsetDevice(d[0], d[1], lo, scale, passes, count, min_score, validation, subset, predictor_u ? d[12] : 0,
-                                    predictor_u ? d[13] : 0, out, reports_out, record_out, d[2], d[3]) &&
+              CorrelateSubsetDevice(d[0], d[1], lo, scale, passes, count, min_score, validation, subset, predictor_u ? d[4 + images] : 0,
+                                    predictor_u ? d[5 + images] : 0, out, reports_out, record_out, d[2], d[3]) &&
               planes.Download();
-    for (int k = 0; ok && k < 8; ++k)
+    for (int k = 0; ok && k < images; ++k)
         if (nodes[k]) ok = CopyData2DFromDevice(d[4 + k], *nodes[k], H, dev_container_size_.pitch);
     last_run_ok_ = ok;
 }
@@ -964,7 +1011,8 @@ bool OpticalFlow2D::ContinueSubsetSequenceDevice(DevicePtr dev_frame_0, DevicePt
     {
         const DevicePtr read[] = {dev_frame_0, dev_frame_k, previous.u, previous.v, previous.ux, previous.uy, previous.vx, previous.vy, previous.state};
         std::vector<DevicePtr> written;
-        for (DevicePtr p : {out.u, out.v, out.ux, out.uy, out.vx, out.vy, out.score, out.state, dev_flow_u, dev_flow_v})
+        for (DevicePtr p : {out.u, out.v, out.ux, out.uy, out.vx, out.vy, out.score, out.state, dev_flow_u, dev_flow_v, out.uxx, out.uxy,
+                            out.uyy, out.vxx, out.vxy, out.vyy})
             if (p) written.push_back(p);
         if (!WrittenPlanesOk(read, 9, written.data(), written.size(), "node or flow plane")) return false;
     }
@@ -986,13 +1034,15 @@ void OpticalFlow2D::ContinueSubsetSequence(Data2D& frame_0, Data2D& frame_k, Dat
         if (!previous[k]) return;
     const bool gradients = nodes[2] != nullptr;
     if ((nodes[3] != nullptr) != gradients || (nodes[4] != nullptr) != gradients || (nodes[5] != nullptr) != gradients) return;
+    const int images = NodeImages(subset);
+    if (!CurvatureImagesOk(nodes, images)) return;
     const size_t W = dev_container_size_.width, H = dev_container_size_.height;
     size_t nw = 0, nh = 0;
     if (flow2d_correlation_grid(W, H, grid_radius, spacing, &nw, &nh) != FLOW2D_OK) {
         std::printf("Error: a %zu x %zu frame holds no node grid of radius %d and spacing %d.\n", W, H, grid_radius, spacing);
         return;
     }
-    for (int k = 0; k < 15; ++k) {
+    for (int k = 0; k < 7 + images; ++k) {
         Data2D* image = k < 7 ? previous[k] : nodes[k - 7];
         if (image && (image->Width() != nw || image->Height() != nh)) {
             std::printf("Error: '%s': the node images are not %zu x %zu.\n", GetName(), nw, nh);
@@ -1003,17 +1053,17 @@ void OpticalFlow2D::ContinueSubsetSequence(Data2D& frame_0, Data2D& frame_k, Dat
     planes.Add(&frame_0, CallPlanes::In).Add(&frame_k, CallPlanes::In).Add(flow_u, CallPlanes::Out).Add(flow_v, CallPlanes::Out);
     // the node planes, read and written: containers with no image of their size behind them, uploaded and downloaded here
     for (int k = 0; k < 7; ++k) planes.Add(nullptr, CallPlanes::Out, true);
-    for (int k = 0; k < 8; ++k) planes.Add(nullptr, CallPlanes::Out, nodes[k] != nullptr);
+    for (int k = 0; k < images; ++k) planes.Add(nullptr, CallPlanes::Out, nodes[k] != nullptr);
     if (!planes.SizesMatch()) return;
     HostCall call(context_, last_total_ms_, planes.Allocate());
     const DevicePtr* d = planes.data();
     bool ok = planes.Upload();
     for (int k = 0; ok && k < 7; ++k) ok = CopyData2DtoDevice(*previous[k], d[4 + k], H, dev_container_size_.pitch);
     const SubsetPlanes last = {d[4], d[5], d[6], d[7], d[8], d[9], 0, d[10]};
-    const SubsetPlanes out = {d[11], d[12], d[13], d[14], d[15], d[16], d[17], d[18]};
+    const SubsetPlanes out = NodePlanes(d + 11, images);
     ok = ok && ContinueSubsetSequenceDevice(d[0], d[1], last, grid_radius, spacing, subset, sequence, out, report_out, d[2], d[3]) &&
          planes.Download();
-    for (int k = 0; ok && k < 8; ++k)
+    for (int k = 0; ok && k < images; ++k)
         if (nodes[k]) ok = CopyData2DFromDevice(d[11 + k], *nodes[k], H, dev_container_size_.pitch);
     last_run_ok_ = ok;
 }
@@ -1149,7 +1199,7 @@ bool OpticalFlow2D::CorrelateSubsetSequenceDevice(const DevicePtr* dev_frames, s
                 std::printf("Error: '%s': step %zu of a subset sequence needs u, v, the four gradients and the state.\n", GetName(), k + 1);
                 return false;
             }
-            for (DevicePtr p : {o.u, o.v, o.ux, o.uy, o.vx, o.vy, o.score, o.state})
+            for (DevicePtr p : {o.u, o.v, o.ux, o.uy, o.vx, o.vy, o.score, o.state, o.uxx, o.uxy, o.uyy, o.vxx, o.vxy, o.vyy})
                 if (p) written.push_back(p);
             if (dev_flows && (dev_flows[2 * k] == 0) != (dev_flows[2 * k + 1] == 0)) return false;
             for (int c = 0; dev_flows && c < 2; ++c)
@@ -1182,19 +1232,20 @@ void OpticalFlow2D::CorrelateSubsetSequence(Data2D* const* frames, size_t frame_
 {
     last_run_ok_ = false;
     if (!IsInitialized() || !frames || frame_count < 2 || !nodes) return;
-    const size_t steps = frame_count - 1;
+    const size_t steps = frame_count - 1, images = static_cast<size_t>(NodeImages(subset));
     for (size_t k = 0; k < frame_count; ++k)
         if (!frames[k]) return;
     for (size_t k = 0; k < steps; ++k) {
         for (int c = 0; c < 8; ++c)
-            if (c != 6 && !nodes[8 * k + c]) return;
+            if (c != 6 && !nodes[images * k + c]) return;
+        if (!CurvatureImagesOk(nodes + images * k, static_cast<int>(images))) return;
         if (flows && (flows[2 * k] == nullptr) != (flows[2 * k + 1] == nullptr)) return;
     }
     CallPlanes planes(context_, dev_container_size_, GetName(), "frame / flow");
     for (size_t k = 0; k < frame_count; ++k) planes.Add(frames[k], CallPlanes::In);
     for (size_t k = 0; k < 2 * steps; ++k) planes.Add(flows ? flows[k] : nullptr, CallPlanes::Out);
     // the node planes: containers with no image of their size behind them, downloaded below
-    for (size_t k = 0; k < 8 * steps; ++k) planes.Add(nullptr, CallPlanes::Out, nodes[k] != nullptr);
+    for (size_t k = 0; k < images * steps; ++k) planes.Add(nullptr, CallPlanes::Out, nodes[k] != nullptr);
     if (!planes.SizesMatch()) return;
     float lo = 0.f, scale = 1.f;
     CorrelationRange(*frames[0], *frames[1], lo, scale);
@@ -1204,7 +1255,7 @@ void OpticalFlow2D::CorrelateSubsetSequence(Data2D* const* frames, size_t frame_
         return;
     size_t nw = 0, nh = 0;
     flow2d_correlation_grid(W, H, passes[count - 1].radius, passes[count - 1].spacing, &nw, &nh);
-    for (size_t k = 0; k < 8 * steps; ++k)
+    for (size_t k = 0; k < images * steps; ++k)
         if (nodes[k] && (nodes[k]->Width() != nw || nodes[k]->Height() != nh)) {
             std::printf("Error: '%s': the node images are not %zu x %zu.\n", GetName(), nw, nh);
             return;
@@ -1215,14 +1266,13 @@ void OpticalFlow2D::CorrelateSubsetSequence(Data2D* const* frames, size_t frame_
     const DevicePtr* dev_nodes = dev_flows + 2 * steps;
     std::vector<SubsetPlanes> out(steps);
     for (size_t k = 0; k < steps; ++k) {
-        const DevicePtr* p = dev_nodes + 8 * k;
-        out[k] = {p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7]};
+        out[k] = NodePlanes(dev_nodes + images * k, static_cast<int>(images));
     }
     bool ok = planes.Upload() &&
               CorrelateSubsetSequenceDevice(d, frame_count, lo, scale, passes, count, min_score, validation, subset, sequence, out.data(),
                                             first_reports, steps_out, flows ? dev_flows : nullptr) &&
               planes.Download();
-    for (size_t k = 0; ok && k < 8 * steps; ++k)
+    for (size_t k = 0; ok && k < images * steps; ++k)
         if (nodes[k]) ok = CopyData2DFromDevice(dev_nodes[k], *nodes[k], H, dev_container_size_.pitch);
     last_run_ok_ = ok;
 }

@@ -131,6 +131,46 @@ def make_speckle_deformation(name, width=96, height=80, seed=0):
     return _affine_scene("speckle_" + name, width, height, texture, a, (1.6, -0.7))
 
 
+SPECKLE_BENDINGS = ("bend", "bulge")
+
+
+def make_speckle_bending(name, width=96, height=80, seed=0, kappa=0.004):
+    """A speckle pattern whose windows bend (one of SPECKLE_BENDINGS), for the second-order subset refinement
+    (flow2d_subset_refine2_2d): frame_0 = T(x, y) and frame_1(X, Y) = T(X - U, Y - V) with the displacement given at the frame-1
+    position, a = X - (width - 1) / 2, b = Y - (height - 1) / 2:
+      bend:   U = 1.6 + kappa a b,       V = -0.7 - kappa a^2 / 2   (a beam's bending: uxy = kappa, vxx = -kappa)
+      bulge:  U = 1.6 + kappa a^2 / 2,   V = -0.7 + kappa b^2 / 2   (uxx = vyy = kappa).
+    gt_u, gt_v on frame 0's grid are the fixed point of (X, Y) = (x, y) + (U, V)(X, Y), 60 rounds -- a contraction by
+    kappa * max(width, height) per round.  The names are in none of the other tuples of scene names."""
+    if name not in SPECKLE_BENDINGS:
+        raise ValueError("unknown speckle bending %r (one of %s)" % (name, ", ".join(SPECKLE_BENDINGS)))
+    texture = Speckle(seed)
+    kappa = float(kappa)
+    cx, cy = (width - 1) / 2.0, (height - 1) / 2.0
+
+    def displacement(x, y):
+        a, b = np.asarray(x, np.float64) - cx, np.asarray(y, np.float64) - cy
+        if name == "bend":
+            return 1.6 + kappa * a * b, -0.7 - 0.5 * kappa * a * a
+        return 1.6 + 0.5 * kappa * a * a, -0.7 + 0.5 * kappa * b * b
+
+    def frame_1_at(x, y):
+        du, dv = displacement(x, y)
+        return texture(np.asarray(x, np.float64) - du, np.asarray(y, np.float64) - dv)
+
+    def back_flow_at(x, y):
+        du, dv = displacement(x, y)
+        return -du, -dv
+
+    ys, xs = np.mgrid[0:height, 0:width].astype(np.float64)
+    px, py = xs, ys
+    for _ in range(60):
+        du, dv = displacement(px, py)
+        px, py = xs + du, ys + dv
+    return Scene("speckle_" + name, texture(xs, ys).astype(np.float32), frame_1_at(xs, ys).astype(np.float32), (px - xs).astype(np.float32),
+                 (py - ys).astype(np.float32), None, frame_1_at, frame_0_at=texture, back_flow_at=back_flow_at)
+
+
 def make_speckle_deformation_sequence(name, steps=6, step_size=None, width=96, height=80, seed=0, translation=(0.0, 0.0)):
     """A loading sequence for the subset refinement over a sequence (flow2d_subset_refine_from_2d): the speckle pattern under k
     times the deformation `name` (one of SPECKLE_DEFORMATIONS) about the centre, k = 1 .. steps, every frame against the same

@@ -1096,6 +1096,81 @@ FLOW2D_API int flow2d_subset_refine_from_2d(flow2d_context* ctx, const float* fr
                                             float* out_vx, float* out_vy, float* out_score /* may be NULL */,
                                             float* out_state /* may be NULL */, flow2d_subset_record* record /* device, may be NULL */);
 
+/* Subset refinement with a second-order shape function (Lu & Cary 2000; Gao, Cheng, Su, Xu, Zhang & Zhang 2015): the
+ * inverse-compositional Gauss-Newton iteration of flow2d_subset_refine_2d with twelve parameters,
+ *   p = (u, ux, uy, uxx, uxy, uyy, v, vx, vy, vxx, vxy, vyy) = (p0 .. p11):
+ * the point (cx + xi, cy + eta) of frame 0 lies at
+ *   X = cx + xi + u + ux*xi + uy*eta + uxx*xi^2/2 + uxy*xi*eta + uyy*eta^2/2,   Y likewise with v,
+ * in frame 1 -- a subset that bends, where the first-order refinement is biased by the mean of the quadratic term over the
+ * subset.  Added to ABI version 1 without changing any existing entry.
+ * Everything not named here is the text of flow2d_subset_refine_2d word for word: the node and grid rules, the frame-0
+ * quantities, the residual and the Catmull-Rom sampling, the five states and their order, positive comparisons everywhere, IEEE
+ * double with every operation rounded on its own, the order of a sum over the subset as the one thing left open, the record,
+ * batches, graph capture and the refusals.  What differs:
+ * R = subset_radius runs from 2 to FLOW2D_SUBSET_MAX_RADIUS: nine pixels cannot carry twelve unknowns.
+ * Shape.  phi = (phi0 .. phi5) = (1, xi, eta, 0.5*xi*xi, xi*eta, 0.5*eta*eta) -- every one exact, as is every product
+ *   phi[a]*phi[b] (at most 15^4 / 4).
+ * No input.  u0, v0 or a start value that is given is not finite.
+ * Hessian, 12 x 12.  J[a] = fx*phi[a] and J[6 + a] = fy*phi[a] (a = 0 .. 5), each a rounded product, are what b is formed from;
+ *   H is formed from the products of the gradients first:  wxx = fx*fx, wxy = fx*fy, wyy = fy*fy, each rounded, and
+ *   H[a][b] = sum of wxx*(phi[a]*phi[b]);   H[a][6 + b] = H[6 + b][a] = sum of wxy*(phi[a]*phi[b]);
+ *   H[6 + a][6 + b] = sum of wyy*(phi[a]*phi[b])        (a, b = 0 .. 5).
+ *   phi[a]*phi[b] = phi[b]*phi[a] bit for bit, so each of the three 6 x 6 blocks is symmetric in (a, b) as stated, not only up
+ *   to rounding: 3 x 21 different sums, not 78.
+ * Cholesky and Solve: the text's with 12 in the place of 6 (k = 0 .. 11, i up to 11), the same pivot test, *flat*.
+ * Start.  p = (u0, ux0, uy0, uxx0, uxy0, uyy0, v0, vx0, vy0, vxx0, vxy0, vyy0), each converted to double; the four start
+ *   gradients are given all or none, the six start curvatures all or none and only with the gradients; an absent value is 0.
+ * Iteration n = 1 .. K:
+ *   1. Positions.  X = (double)(cx + xi) + (((((u + ux*phi1) + uy*phi2) + uxx*phi3) + uxy*phi4) + uyy*phi5);   Y likewise with
+ *      (double)(cy + eta) and v, vx, ...  *Strayed* as in the text.
+ *   2. Sampling: the text's.
+ *   3. Residual: the text's, with b[a] = sum of J[a]*res for a = 0 .. 11, x = Solve(b), dp[a] = -x[a].
+ *   4. Update, p <- W(p) o W(dp)^-1.  A warp acts on the monomials (xi^2, xi*eta, eta^2, xi, eta, 1) as a 6 x 6 matrix.  For a
+ *      parameter vector q let A(q) = (a1 .. a6) = (0.5*uxx, uxy, 0.5*uyy, 1 + ux, uy, u) and B(q) = (b1 .. b6) =
+ *      (0.5*vxx, vxy, 0.5*vyy, vx, 1 + vy, v).  The rows W0 .. W5 of W(dp), from A = A(dp) and B = B(dp), each product of two
+ *      rows truncated at second order in (xi, eta):
+ *        W0 = (a4*a4 + 2*(a1*a6),  2*(a4*a5) + 2*(a2*a6),  a5*a5 + 2*(a3*a6),  2*(a4*a6),  2*(a5*a6),  a6*a6)
+ *        W1 = ((a4*b4 + a1*b6) + a6*b1,  ((a4*b5 + a5*b4) + a2*b6) + a6*b2,  (a5*b5 + a3*b6) + a6*b3,  a4*b6 + a6*b4,
+ *              a5*b6 + a6*b5,  a6*b6)
+ *        W2 = W0 with b in the place of a;   W3 = A;   W4 = B;   W5 = (0, 0, 0, 0, 0, 1).
+ *      Only the rows A and B of W(p) W(dp)^-1 are needed: the z with z W(dp) = A(p), and the z' with z' W(dp) = B(p) (the old
+ *      p).  W5 leaves z5 out of the first five columns, so z0 .. z4 solve the 5 x 5 system M z = rhs with M[j][i] = W_i[j] and
+ *      rhs[j] = A(p)[j] (i, j = 0 .. 4), by elimination without pivoting -- W(dp) is a perturbation of the identity --, both
+ *      right-hand sides at once:
+ *        for k = 0 .. 4:   *strayed* when !(|M[k][k]| > 1e-6);   for j = k + 1 .. 4:   f = M[j][k] / M[k][k];
+ *          M[j][i] = M[j][i] - f*M[k][i] for i = k + 1 .. 4;   rhs[j] = rhs[j] - f*rhs[k]
+ *        for i = 4 down to 0:   z[i] = (rhs[i] - (sum over m = i + 1 .. 4 of M[i][m]*z[m])) / M[i][i]
+ *          (the sum from 0, terms from the lowest m up)
+ *        z[5] = A(p)[5] - ((((z[0]*W0[5] + z[1]*W1[5]) + z[2]*W2[5]) + z[3]*W3[5]) + z[4]*W4[5])
+ *      All five pivots are tested -- the k = 4 one too, which has no row below it -- before anything is divided by them.
+ *      The new p:  uxx = 2*z[0], uxy = z[1], uyy = 2*z[2], ux = z[3] - 1, uy = z[4], u = z[5];
+ *      vxx = 2*z'[0], vxy = z'[1], vyy = 2*z'[2], vx = z'[3], vy = z'[4] - 1, v = z'[5].
+ *   5. Stop.  *Strayed* unless |u - u0| <= max_shift, |v - v0| <= max_shift, |ux|, |uy|, |vx|, |vy| <= max_gradient and
+ *      |uxx|, |uxy|, |uyy|, |vxx|, |vxy|, |vyy| <= max_curvature (the new p).  With R2 = (double)(R*R), hR2 = 0.5*R2 and
+ *      t = (dp0, R*dp1, R*dp2, hR2*dp3, R2*dp4, hR2*dp5, dp6, R*dp7, R*dp8, hR2*dp9, R2*dp10, hR2*dp11), converged, state n, when
+ *        sqrt(((..((t0*t0 + t1*t1) + t2*t2) + ..) + t11*t11) < epsilon       (the squares added in the order 0 .. 11).
+ * Outputs.  out_u, out_v; the four gradient planes out_ux, out_uy, out_vx, out_vy, all or none; the six curvature planes
+ * out_uxx, out_uxy, out_uyy, out_vxx, out_vxy, out_vyy, all or none (with or without the gradient planes); out_score and
+ * out_state, each optional.  State >= 0: p and the last c, each cast to float.  No input: the twelve NaN (0x7FC00000), score 0.
+ * Flat and strayed: the whole start copied bit for bit -- a start value that was absent comes back as 0 --, score 0.
+ * The four plane groups -- start_gradients, start_curvatures, out_gradients, out_curvatures -- are HOST arrays of four or six
+ * device pointers, read during the call and not kept; a NULL array and an array of NULLs both mean that the group is absent.
+ * Refusals.  Those of flow2d_subset_refine_from_2d, with subset_radius < 2 among them, and also: a max_curvature that is not
+ * finite and > 0, curvature planes or start curvatures given in part, start curvatures without start gradients, a start or
+ * output plane that breaks the node planes' rules, and a written range that overlaps any start plane or another written one. */
+#define FLOW2D_SUBSET2_MIN_RADIUS 2
+FLOW2D_API int flow2d_subset_refine2_2d(flow2d_context* ctx, const float* frame_0, const float* frame_1, size_t width, size_t height,
+                                        size_t pitch_bytes, const float* node_u0, const float* node_v0,
+                                        const float* const* start_gradients /* NULL, or ux0, uy0, vx0, vy0: all or none */,
+                                        const float* const* start_curvatures /* NULL, or uxx0, uxy0, uyy0, vxx0, vxy0, vyy0 */,
+                                        size_t nw, size_t nh, size_t node_pitch_bytes, int grid_radius, int spacing,
+                                        int subset_radius, int max_iterations, float epsilon, float max_shift, float max_gradient,
+                                        float max_curvature, float* out_u, float* out_v,
+                                        float* const* out_gradients /* NULL, or ux, uy, vx, vy: all or none */,
+                                        float* const* out_curvatures /* NULL, or uxx, uxy, uyy, vxx, vxy, vyy: all or none */,
+                                        float* out_score /* may be NULL */, float* out_state /* may be NULL */,
+                                        flow2d_subset_record* record /* device, may be NULL */);
+
 /* The start of the next step of a sequence from a step's result, out of place: a node the refinement found is kept, every other
  * node is predicted from its neighbours.  Every node is judged against the input, so the result depends on no order.
  * Inputs: the six planes node_u, node_v, node_ux, node_uy, node_vx, node_vy and node_state (the outputs of
