@@ -279,11 +279,26 @@ class SubsetRecord(C.Structure):
     def summary(self):
         return {name: getattr(self, name) for name, _ in self._fields_[:7]}
 
+    @property
+    def masked(self):
+        """The masked nodes (state SUBSET_MASKED): what flow2d_subset_refine_masked_2d writes into the word the other entries
+        leave 0.  Read-only."""
+        return self.reserved
+
 
 SUBSET_RECORD_BYTES = 64  # FLOW2D_SUBSET_RECORD_BYTES, checked by a static_assert in the header
 assert C.sizeof(SubsetRecord) == SUBSET_RECORD_BYTES
 SUBSET_MAX_RADIUS, SUBSET_MAX_ITERATIONS = 15, 64  # FLOW2D_SUBSET_MAX_*
 SUBSET_NO_INPUT, SUBSET_FLAT, SUBSET_STRAYED = -1, -2, -3  # the negative states of flow2d_subset_refine_2d
+SUBSET_MASKED = -4  # FLOW2D_SUBSET_STATE_MASKED: flow2d_subset_refine_masked_2d's, a node off the region of interest
+SUBSET_MIN_PIXELS = 6  # FLOW2D_SUBSET_MIN_PIXELS
+
+
+def subset_min_pixels(subset_radius):
+    """The default min_pixels of a masked refinement (OpticalFlow2D::SubsetOptions::min_pixels = 0): a quarter of the subset,
+    rounded up, and six at least."""
+    side = 2 * int(subset_radius) + 1
+    return max(SUBSET_MIN_PIXELS, (side * side + 3) // 4)
 SUBSET_STATE_PREDICTED = 65  # FLOW2D_SUBSET_STATE_PREDICTED: the state flow2d_predict_nodes_2d gives a node it predicted
 
 
@@ -542,6 +557,8 @@ def hip_lib():
         if hasattr(L, "flow2d_subset_refine_from_2d"):  # (absent from libraries of earlier rounds loaded for an A/B)
             L.flow2d_subset_refine_from_2d.argtypes = [vp, vp, vp, sz, sz, sz] + [vp] * 6 + [sz, sz, sz, i, i, i, i, f, f, f] + [vp] * 9
             L.flow2d_predict_nodes_2d.argtypes = [vp] + [vp] * 7 + [sz, sz, sz, i, i, i] + [vp] * 8
+        if hasattr(L, "flow2d_subset_refine_masked_2d"):  # (absent from libraries of earlier rounds loaded for an A/B)
+            L.flow2d_subset_refine_masked_2d.argtypes = [vp, vp, vp, sz, sz, sz] + [vp] * 6 + [sz, sz, sz, i, i, i, i, f, f, f, vp, i] + [vp] * 9
         if hasattr(L, "flow2d_node_strain_2d"):  # (absent from libraries of earlier rounds loaded for an A/B)
             L.flow2d_node_strain_workspace_bytes.restype = sz
             L.flow2d_node_strain_workspace_bytes.argtypes = [sz, sz, sz]
@@ -1312,6 +1329,47 @@ class Context:
                 q.free()
                 self._planes.remove(q)
 
+    def subset_refine_masked(self, f0, f1, w, h, node_u0, node_v0, start_gradients, nw, nh, grid_radius, spacing, subset_radius, mask,
+                             min_pixels=None, max_iterations=20, epsilon=1e-3, max_shift=4.0, max_gradient=0.5, out_u=None, out_v=None,
+                             out_gradients=None, out_score=None, out_state=None, record=True, instances=1):
+        """Masked subset refinement, DIC on a region of interest (flow2d_subset_refine_masked_2d): subset_refine_from with `mask`, a
+        Plane of the frames' size and pitch in frame 0's coordinates whose values of 0.5 and more (and NaN) mean "not the
+        specimen".  A subset is refined on its usable pixels -- those whose own value and whose four gradient-stencil neighbours
+        are not excluded --; a node whose centre is excluded or that has fewer than min_pixels usable pixels (None:
+        subset_min_pixels(subset_radius)) is SUBSET_MASKED, NaN in all six planes, and counted in the record's `masked`.  mask =
+        None: every byte is subset_refine_from's.  Outputs, record and the return value as for subset_refine."""
+        own_planes = out_u is None and out_v is None
+        if not own_planes and (out_u is None or out_v is None):
+            raise ValueError("subset_refine_masked takes both output planes or neither")
+        own_record = record is True
+        if own_record and instances != 1:
+            raise ValueError("a lock-step batch takes the caller's records")
+        start = list(start_gradients) if start_gradients is not None else [None] * 4
+        if len(start) != 4:
+            raise ValueError("subset_refine_masked takes the four start gradients (ux0, uy0, vx0, vy0) or None")
+        if min_pixels is None:
+            min_pixels = subset_min_pixels(subset_radius)
+        if own_planes:
+            held = [self.plane(node_u0.pitch // 4, nh) for _ in range(8)]
+        else:
+            held = [out_u, out_v] + list(out_gradients if out_gradients is not None else (None,) * 4) + [out_score, out_state]
+        rec = self.subset_records(instances) if own_record else (record or None)
+        try:
+            _check(hip_lib().flow2d_subset_refine_masked_2d(self.handle, f0.ptr, f1.ptr, w, h, f0.pitch, node_u0.ptr, node_v0.ptr,
+                                                            *[q.ptr if q is not None else None for q in start], nw, nh, node_u0.pitch,
+                                                            int(grid_radius), int(spacing), int(subset_radius), int(max_iterations),
+                                                            float(epsilon), float(max_shift), float(max_gradient),
+                                                            mask.ptr if mask is not None else None, int(min_pixels),
+                                                            *[q.ptr if q is not None else None for q in held],
+                                                            rec.ptr if rec is not None else None), "flow2d_subset_refine_masked_2d")
+            got = [q.download(nw, nh) for q in held] if own_planes else held
+            gradients = tuple(got[2:6]) if got[2] is not None else None
+            return got[0], got[1], gradients, got[6], got[7], (self.read_subset_record(rec, 1)[0] if own_record else None)
+        finally:
+            for q in (held if own_planes else []) + ([rec] if own_record else []):
+                q.free()
+                self._planes.remove(q)
+
     def subset_refine2(self, f0, f1, w, h, node_u0, node_v0, nw, nh, grid_radius, spacing, subset_radius, max_iterations=20,
                        epsilon=1e-3, max_shift=2.0, max_gradient=0.5, max_curvature=0.05, start_gradients=None, start_curvatures=None,
                        out_u=None, out_v=None, out_gradients=None, out_curvatures=None, out_score=None, out_state=None, record=True,
@@ -1755,6 +1813,20 @@ def host_lib():
                                                                  fpp, fp]
             L.flow2d_host_correlate_subset2_sequence_device.argtypes = [vp, pvp, i, f, f, ip, i, f, f, f, i, i, i, f, f, f, i, f, i, i, i, f, pvp,
                                                                         rp, st, pvp]
+        if hasattr(L, "flow2d_host_correlate_subset_masked_device"):  # the first-order calls with SubsetOptions::mask and min_pixels
+            ip, rp, sr, st = C.POINTER(C.c_int), C.POINTER(CorrelationPassReport), C.POINTER(SubsetRecord), C.POINTER(SequenceStepReport)
+            pvp, fpp = C.POINTER(vp), C.POINTER(fp)
+            L.flow2d_host_subset_mask_options_ok.argtypes = [i, i, f, f, f, i, f, i]
+            L.flow2d_host_subset_min_pixels.argtypes = [i]
+            L.flow2d_host_refine_nodes_masked_device.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, f, f, f, vp, i, pvp, sr]
+            L.flow2d_host_refine_nodes_from_masked_device.argtypes = [vp, vp, vp, pvp, i, i, i, i, f, f, f, vp, i, pvp, sr]
+            L.flow2d_host_correlate_subset_masked_device.argtypes = [vp, vp, vp, f, f, ip, i, f, f, f, i, i, i, f, f, f, vp, i, vp, vp, pvp, rp, sr,
+                                                                     vp, vp]
+            L.flow2d_host_correlate_subset_masked.argtypes = [vp, fp, fp, ip, i, f, f, f, i, i, i, f, f, f, fp, i, fp, fp, fpp, rp, sr, fp, fp, fp]
+            L.flow2d_host_correlate_subset_masked_sequence_device.argtypes = [vp, pvp, i, f, f, ip, i, f, f, f, i, i, i, f, f, f, vp, i, i, i, i, f,
+                                                                              pvp, rp, st, pvp]
+            L.flow2d_host_correlate_subset_masked_sequence.argtypes = [vp, fpp, i, ip, i, f, f, f, i, i, i, f, f, f, fp, i, i, i, i, f, fpp, rp, st,
+                                                                       fpp, fp]
         if hasattr(L, "flow2d_host_correlate_subset_sequence_device"):
             ip, rp, sr, st = C.POINTER(C.c_int), C.POINTER(CorrelationPassReport), C.POINTER(SubsetRecord), C.POINTER(SequenceStepReport)
             pvp, pfp = C.POINTER(vp), C.POINTER(fp)
@@ -2313,12 +2385,38 @@ class OpticalFlow:
     SUBSET2_PLANES = SUBSET_PLANES + ("uxx", "uxy", "uyy", "vxx", "vxy", "vyy")
 
     @staticmethod
-    def subset_options_ok(radius, iterations=20, epsilon=1e-3, max_shift=2.0, max_gradient=0.5, order=1, max_curvature=0.05):
-        """OpticalFlow2D::SubsetOptionsOk: whether refine_nodes_device / correlate_subset* accept the options.  Needs no device."""
+    def subset_options_ok(radius, iterations=20, epsilon=1e-3, max_shift=2.0, max_gradient=0.5, order=1, max_curvature=0.05, mask=False,
+                          min_pixels=0):
+        """OpticalFlow2D::SubsetOptionsOk: whether refine_nodes_device / correlate_subset* accept the options; mask=True: together
+        with a mask and min_pixels (a mask with order 2 is refused).  Needs no device."""
+        if mask:
+            return bool(host_lib().flow2d_host_subset_mask_options_ok(int(radius), int(iterations), float(epsilon), float(max_shift),
+                                                                      float(max_gradient), int(order), float(max_curvature), int(min_pixels)))
         if order == 1 and max_curvature == 0.05:
             return bool(host_lib().flow2d_host_subset_options_ok(int(radius), int(iterations), float(epsilon), float(max_shift), float(max_gradient)))
         return bool(host_lib().flow2d_host_subset2_options_ok(int(radius), int(iterations), float(epsilon), float(max_shift), float(max_gradient),
                                                               int(order), float(max_curvature)))
+
+    @staticmethod
+    def _takes_mask(mask, min_pixels, order, where):
+        """Whether a call that refines goes to its masked entry (OpticalFlow2D::SubsetOptions::mask and min_pixels): mask -- the
+        region of interest in frame 0's coordinates, values of 0.5 and more (and NaN) meaning "not the specimen"; a device plane of
+        the container's size for a *_device method, else an image of the frames' size --, min_pixels -- the fewest usable pixels a
+        node may have, 0 = subset_min_pixels(radius).  A masked node has the state SUBSET_MASKED and NaN in its six planes, and the
+        SubsetRecord counts it in `masked`.  Order 1 only.  Without a mask the method is the call it always was."""
+        if mask is None:
+            if min_pixels:
+                raise ValueError("min_pixels goes with a mask")
+            return False
+        if order != 1:
+            raise Flow2DError(1, where, "a subset mask goes with order 1 only")
+        return True
+
+    def _mask_image(self, mask):
+        image = np.ascontiguousarray(mask, np.float32)
+        if image.shape != (self.height, self.width):
+            raise ValueError("the subset mask is an image of the object's size")
+        return image
 
     @staticmethod
     def _subset2_planes(dev_out):
@@ -2339,14 +2437,23 @@ class OpticalFlow:
         return (C.c_void_p * 8)(*[dev_out.get(name) for name in OpticalFlow.SUBSET_PLANES])
 
     def refine_nodes_device(self, dev_frame_0, dev_frame_1, dev_node_u0, dev_node_v0, grid_radius, spacing, radius, iterations=20,
-                            epsilon=1e-3, max_shift=2.0, max_gradient=0.5, dev_out=None, record=True, order=1, max_curvature=0.05):
+                            epsilon=1e-3, max_shift=2.0, max_gradient=0.5, dev_out=None, record=True, order=1, max_curvature=0.05, mask=None,
+                            min_pixels=0):
         """OpticalFlow2D::RefineNodesDevice: the node field (dev_node_u0, dev_node_v0) of the grid (grid_radius, spacing) -- planes of
         the container's size -- refined by subsets of `radius` (flow2d_subset_refine_2d).  dev_out: a dict of device planes by the
         names of SUBSET_PLANES (u and v both or neither, the four gradients all or none).  Returns the SubsetRecord (the call then
         synchronises) or, without record, None (it only queues).  order=2: the second-order refinement (flow2d_subset_refine2_2d),
         radius from 2, a curvature beyond max_curvature strays; dev_out by the names of SUBSET2_PLANES, the six curvatures all or
-        none.  order=1 is the call it always was."""
+        none.  order=1 is the call it always was.  mask (a device plane) / min_pixels: see _takes_mask."""
         rec = SubsetRecord()
+        if self._takes_mask(mask, min_pixels, order, "OpticalFlow2D::RefineNodesDevice"):
+            rc = host_lib().flow2d_host_refine_nodes_masked_device(self.handle, dev_frame_0, dev_frame_1, dev_node_u0, dev_node_v0,
+                                                                   int(grid_radius), int(spacing), int(radius), int(iterations), float(epsilon),
+                                                                   float(max_shift), float(max_gradient), mask, int(min_pixels),
+                                                                   self._subset_planes(dev_out), C.byref(rec) if record else None)
+            if rc:
+                raise Flow2DError(rc, "OpticalFlow2D::RefineNodesDevice")
+            return rec if record else None
         if order != 1:
             rc = host_lib().flow2d_host_refine_nodes2_device(self.handle, dev_frame_0, dev_frame_1, dev_node_u0, dev_node_v0, int(grid_radius),
                                                              int(spacing), int(radius), int(iterations), float(epsilon), float(max_shift),
@@ -2364,13 +2471,13 @@ class OpticalFlow:
 
     def correlate_subset(self, frame_0, frame_1, passes, radius, iterations=20, epsilon=1e-3, max_shift=2.0, max_gradient=0.5,
                          min_score=-1.0, threshold=2.0, validate_epsilon=0.1, min_neighbours=3, predictor=None, flow=False, order=1,
-                         max_curvature=0.05):
+                         max_curvature=0.05, mask=None, min_pixels=0):
         """OpticalFlow2D::CorrelateSubset: the host pair through `passes` as in correlate_multipass -- the last pass validated with
         replacement, so that every node has a start --, then every node of the last pass's grid refined by subsets of `radius` on
         the unquantised frames.  Returns (nodes, [CorrelationPassReport], SubsetRecord, (lo, scale)), nodes a dict of [nh, nw]
         arrays by the names of SUBSET_PLANES; with flow, also the (u, v) of the refined field expanded to the frame's grid.
         order=2: the second-order refinement (radius from 2, a curvature beyond max_curvature strays), nodes by the names of
-        SUBSET2_PLANES; order=1 is the call it always was."""
+        SUBSET2_PLANES; order=1 is the call it always was.  mask (an image, uploaded once) / min_pixels: see _takes_mask."""
         f0, f1 = self._pair(frame_0, frame_1)
         arr, n = self._passes(passes)
         if not 1 <= n <= CORRELATION_MAX_PASSES:
@@ -2380,6 +2487,18 @@ class OpticalFlow:
         uv = [np.empty_like(f0) for _ in range(2)] if flow else [None, None]
         pred = [np.ascontiguousarray(q, np.float32) for q in predictor] if predictor is not None else [None, None]
         reports, rec, lo_scale = (CorrelationPassReport * n)(), SubsetRecord(), (C.c_float * 2)()
+        if self._takes_mask(mask, min_pixels, order, "OpticalFlow2D::CorrelateSubset"):
+            image = self._mask_image(mask)
+            rc = host_lib().flow2d_host_correlate_subset_masked(self.handle, _fptr(f0), _fptr(f1), arr, n, float(min_score), float(threshold),
+                                                                float(validate_epsilon), int(min_neighbours), int(radius), int(iterations),
+                                                                float(epsilon), float(max_shift), float(max_gradient), _fptr(image),
+                                                                int(min_pixels), _opt_fptr(pred[0]), _opt_fptr(pred[1]),
+                                                                (C.POINTER(C.c_float) * 8)(*[_fptr(q) for q in nodes]), reports, C.byref(rec),
+                                                                _opt_fptr(uv[0]), _opt_fptr(uv[1]), lo_scale)
+            if rc:
+                raise Flow2DError(rc, "OpticalFlow2D::CorrelateSubset")
+            out = (dict(zip(self.SUBSET_PLANES, nodes)), list(reports), rec, (lo_scale[0], lo_scale[1]))
+            return out + (tuple(uv),) if flow else out
         if order != 1:
             rc = host_lib().flow2d_host_correlate_subset2(self.handle, _fptr(f0), _fptr(f1), arr, n, float(min_score), float(threshold),
                                                           float(validate_epsilon), int(min_neighbours), int(radius), int(iterations),
@@ -2403,13 +2522,22 @@ class OpticalFlow:
 
     def correlate_subset_device(self, dev_frame_0, dev_frame_1, lo, scale, passes, radius, iterations=20, epsilon=1e-3, max_shift=2.0,
                                 max_gradient=0.5, min_score=-1.0, threshold=2.0, validate_epsilon=0.1, min_neighbours=3, dev_predictor=None,
-                                dev_out=None, dev_flow=None, order=1, max_curvature=0.05):
+                                dev_out=None, dev_flow=None, order=1, max_curvature=0.05, mask=None, min_pixels=0):
         """OpticalFlow2D::CorrelateSubsetDevice: device frames in; dev_predictor and dev_flow as for correlate_multipass_device (the
         flow is the refined field's), dev_out, order and max_curvature as for refine_nodes_device.  Returns
-        ([CorrelationPassReport], SubsetRecord); synchronises once."""
+        ([CorrelationPassReport], SubsetRecord); synchronises once.  mask (a device plane) / min_pixels: see _takes_mask."""
         arr, n = self._passes(passes)
         reports, rec = (CorrelationPassReport * max(n, 1))(), SubsetRecord()
         pr, fl = dev_predictor or (None, None), dev_flow or (None, None)
+        if self._takes_mask(mask, min_pixels, order, "OpticalFlow2D::CorrelateSubsetDevice"):
+            rc = host_lib().flow2d_host_correlate_subset_masked_device(self.handle, dev_frame_0, dev_frame_1, float(lo), float(scale), arr, n,
+                                                                       float(min_score), float(threshold), float(validate_epsilon),
+                                                                       int(min_neighbours), int(radius), int(iterations), float(epsilon),
+                                                                       float(max_shift), float(max_gradient), mask, int(min_pixels), pr[0],
+                                                                       pr[1], self._subset_planes(dev_out), reports, C.byref(rec), fl[0], fl[1])
+            if rc:
+                raise Flow2DError(rc, "OpticalFlow2D::CorrelateSubsetDevice")
+            return list(reports)[:n], rec
         if order != 1:
             rc = host_lib().flow2d_host_correlate_subset2_device(self.handle, dev_frame_0, dev_frame_1, float(lo), float(scale), arr, n,
                                                                  float(min_score), float(threshold), float(validate_epsilon),
@@ -2434,15 +2562,25 @@ class OpticalFlow:
         return bool(host_lib().flow2d_host_sequence_options_ok(int(fill), int(min_state), int(predict_neighbours), float(sequence_max_shift)))
 
     def refine_nodes_from_device(self, dev_frame_0, dev_frame_1, dev_start, grid_radius, spacing, radius, iterations=20, epsilon=1e-3,
-                                 max_shift=4.0, max_gradient=0.5, dev_out=None, record=True, order=1, max_curvature=0.05):
+                                 max_shift=4.0, max_gradient=0.5, dev_out=None, record=True, order=1, max_curvature=0.05, mask=None,
+                                 min_pixels=0):
         """OpticalFlow2D::RefineNodesFromDevice: refine_nodes_device started from a whole deformation (flow2d_subset_refine_from_2d):
         dev_start is a dict of the six device planes u, v, ux, uy, vx, vy (by the names of SUBSET_PLANES), all needed.  Returns the
         SubsetRecord (the call then synchronises) or, without record, None (it only queues).  order and max_curvature as for
-        refine_nodes_device; at order 2 the start's curvatures are 0."""
+        refine_nodes_device; at order 2 the start's curvatures are 0.  mask (a device plane) / min_pixels: see _takes_mask."""
         names = self.SUBSET_PLANES[:6]
         if set(dev_start) != set(names) or not all(dev_start[n] for n in names):
             raise ValueError("refine_nodes_from_device takes the six start planes %s" % ", ".join(names))
         rec = SubsetRecord()
+        if self._takes_mask(mask, min_pixels, order, "OpticalFlow2D::RefineNodesFromDevice"):
+            rc = host_lib().flow2d_host_refine_nodes_from_masked_device(self.handle, dev_frame_0, dev_frame_1,
+                                                                        (C.c_void_p * 6)(*[dev_start[n] for n in names]), int(grid_radius),
+                                                                        int(spacing), int(radius), int(iterations), float(epsilon),
+                                                                        float(max_shift), float(max_gradient), mask, int(min_pixels),
+                                                                        self._subset_planes(dev_out), C.byref(rec) if record else None)
+            if rc:
+                raise Flow2DError(rc, "OpticalFlow2D::RefineNodesFromDevice")
+            return rec if record else None
         if order != 1:
             rc = host_lib().flow2d_host_refine_nodes_from2_device(self.handle, dev_frame_0, dev_frame_1,
                                                                   (C.c_void_p * 6)(*[dev_start[n] for n in names]), int(grid_radius),
@@ -2462,7 +2600,7 @@ class OpticalFlow:
 
     def correlate_subset_sequence(self, frames, passes, radius, iterations=20, epsilon=1e-3, max_shift=2.0, max_gradient=0.5, min_score=-1.0,
                                   threshold=2.0, validate_epsilon=0.1, min_neighbours=3, fill=2, min_state=1, predict_neighbours=1,
-                                  sequence_max_shift=4.0, flow=False, order=1, max_curvature=0.05):
+                                  sequence_max_shift=4.0, flow=False, order=1, max_curvature=0.05, mask=None, min_pixels=0):
         """OpticalFlow2D::CorrelateSubsetSequence: digital image correlation over a loading sequence.  (order=2: every step refines
         at second order, the steps after the first from the prediction's first-order planes with zero curvatures; the nodes then
         go by the names of SUBSET2_PLANES.)  frames[0] is the reference and
@@ -2471,7 +2609,8 @@ class OpticalFlow:
         min_state at least and refill the others from predict_neighbours usable neighbours, then flow2d_subset_refine_from_2d
         with sequence_max_shift in place of max_shift -- and no window search runs.  Returns ([nodes per step], [CorrelationPassReport]
         of step 1, [SequenceStepReport], (lo, scale)), nodes a dict of [nh, nw] arrays by the names of SUBSET_PLANES; with flow,
-        also [(u, v) per step], the refined field expanded to the frame's grid."""
+        also [(u, v) per step], the refined field expanded to the frame's grid.  mask (an image, uploaded once and used by every
+        step) / min_pixels: see _takes_mask."""
         images = [np.ascontiguousarray(q, np.float32) for q in frames]
         if len(images) < 2 or any(q.shape != (self.height, self.width) for q in images):
             raise ValueError("correlate_subset_sequence takes two or more frames of the object's size")
@@ -2485,6 +2624,22 @@ class OpticalFlow:
         uv = [np.empty_like(images[0]) for _ in range(2 * steps)] if flow else None
         fpp = C.POINTER(C.c_float)
         reports, reps, lo_scale = (CorrelationPassReport * n)(), (SequenceStepReport * steps)(), (C.c_float * 2)()
+        if self._takes_mask(mask, min_pixels, order, "OpticalFlow2D::CorrelateSubsetSequence"):
+            image = self._mask_image(mask)
+            rc = host_lib().flow2d_host_correlate_subset_masked_sequence(self.handle, (fpp * len(images))(*[_fptr(q) for q in images]),
+                                                                         len(images), arr, n, float(min_score), float(threshold),
+                                                                         float(validate_epsilon), int(min_neighbours), int(radius),
+                                                                         int(iterations), float(epsilon), float(max_shift),
+                                                                         float(max_gradient), _fptr(image), int(min_pixels), int(fill),
+                                                                         int(min_state), int(predict_neighbours), float(sequence_max_shift),
+                                                                         (fpp * (8 * steps))(*[_fptr(q) for q in nodes]), reports, reps,
+                                                                         (fpp * (2 * steps))(*[_fptr(q) for q in uv]) if flow else None,
+                                                                         lo_scale)
+            if rc:
+                raise Flow2DError(rc, "OpticalFlow2D::CorrelateSubsetSequence")
+            per_step = [dict(zip(self.SUBSET_PLANES, nodes[8 * k:8 * k + 8])) for k in range(steps)]
+            out = (per_step, list(reports), list(reps), (lo_scale[0], lo_scale[1]))
+            return out + ([(uv[2 * k], uv[2 * k + 1]) for k in range(steps)],) if flow else out
         if order != 1:
             rc = host_lib().flow2d_host_correlate_subset2_sequence(self.handle, (fpp * len(images))(*[_fptr(q) for q in images]), len(images),
                                                                    arr, n, float(min_score), float(threshold), float(validate_epsilon),
@@ -2514,12 +2669,13 @@ class OpticalFlow:
     def correlate_subset_sequence_device(self, dev_frames, lo, scale, passes, radius, dev_out, iterations=20, epsilon=1e-3, max_shift=2.0,
                                          max_gradient=0.5, min_score=-1.0, threshold=2.0, validate_epsilon=0.1, min_neighbours=3, fill=2,
                                          min_state=1, predict_neighbours=1, sequence_max_shift=4.0, dev_flows=None, order=1,
-                                         max_curvature=0.05):
+                                         max_curvature=0.05, mask=None, min_pixels=0):
         """OpticalFlow2D::CorrelateSubsetSequenceDevice: device frames in (the first is the reference); dev_out: per step a dict of
         device planes by the names of SUBSET_PLANES, of which only the score may be missing; dev_flows: per step a (u, v) pair or
         None.  Returns ([CorrelationPassReport] of step 1, [SequenceStepReport]); synchronises once.  order=2: every step refines
         at second order -- the steps after the first from the prediction's six first-order planes with zero curvatures --, dev_out
-        by the names of SUBSET2_PLANES, the six curvatures all or none per step."""
+        by the names of SUBSET2_PLANES, the six curvatures all or none per step.  mask (a device plane, used by every step) /
+        min_pixels: see _takes_mask."""
         arr, n = self._passes(passes)
         steps = len(dev_frames) - 1
         if steps < 1 or len(dev_out) != steps or (dev_flows is not None and len(dev_flows) != steps):
@@ -2534,6 +2690,18 @@ class OpticalFlow:
                 flat += list(pair) if pair is not None else [None, None]
             flows = (C.c_void_p * (2 * steps))(*flat)
         reports, reps = (CorrelationPassReport * max(n, 1))(), (SequenceStepReport * steps)()
+        if self._takes_mask(mask, min_pixels, order, "OpticalFlow2D::CorrelateSubsetSequenceDevice"):
+            rc = host_lib().flow2d_host_correlate_subset_masked_sequence_device(self.handle, (C.c_void_p * len(dev_frames))(*dev_frames),
+                                                                                len(dev_frames), float(lo), float(scale), arr, n,
+                                                                                float(min_score), float(threshold), float(validate_epsilon),
+                                                                                int(min_neighbours), int(radius), int(iterations),
+                                                                                float(epsilon), float(max_shift), float(max_gradient), mask,
+                                                                                int(min_pixels), int(fill), int(min_state),
+                                                                                int(predict_neighbours), float(sequence_max_shift),
+                                                                                (C.c_void_p * (8 * steps))(*planes), reports, reps, flows)
+            if rc:
+                raise Flow2DError(rc, "OpticalFlow2D::CorrelateSubsetSequenceDevice")
+            return list(reports)[:n], list(reps)
         if order != 1:
             rc = host_lib().flow2d_host_correlate_subset2_sequence_device(self.handle, (C.c_void_p * len(dev_frames))(*dev_frames),
                                                                           len(dev_frames), float(lo), float(scale), arr, n, float(min_score),

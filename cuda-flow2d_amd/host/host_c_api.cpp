@@ -763,6 +763,37 @@ OpticalFlow2D::SubsetPlanes subset2_planes(void* const* p)
 }
 }  // namespace
 
+namespace {
+// SubsetOptions::mask and min_pixels beside the first-order options: what the *_masked entries below pass on.  has_mask_image: a
+// host-image call, whose mask travels as an image; the options then only carry the mark the checks look at.
+OpticalFlow2D::SubsetOptions masked_options(int radius, int iterations, float epsilon, float max_shift, float max_gradient, void* dev_mask,
+                                            bool has_mask_image, int min_pixels)
+{
+    OpticalFlow2D::SubsetOptions o = subset_options(radius, iterations, epsilon, max_shift, max_gradient);
+    o.mask = dev_mask ? dp(dev_mask) : has_mask_image ? 1 : 0;
+    o.min_pixels = min_pixels;
+    return o;
+}
+}  // namespace
+
+// OpticalFlow2D::SubsetOptionsOk with a mask of min_pixels (0: the default) beside the options: 1 when accepted.  Needs no device.
+HOST_API int flow2d_host_subset_mask_options_ok(int radius, int iterations, float epsilon, float max_shift, float max_gradient, int order,
+                                                float max_curvature, int min_pixels)
+{
+    OpticalFlow2D::SubsetOptions o = subset_options(radius, iterations, epsilon, max_shift, max_gradient, order, max_curvature);
+    o.mask = 1;
+    o.min_pixels = min_pixels;
+    return OpticalFlow2D::SubsetOptionsOk(o) ? 1 : 0;
+}
+
+// OpticalFlow2D::SubsetMinPixels: the default min_pixels of a radius.
+HOST_API int flow2d_host_subset_min_pixels(int radius)
+{
+    OpticalFlow2D::SubsetOptions o;
+    o.radius = radius;
+    return OpticalFlow2D::SubsetMinPixels(o);
+}
+
 // OpticalFlow2D::SubsetOptionsOk: 1 when the options are what RefineNodes* / CorrelateSubset* accept.  Needs no device.
 HOST_API int flow2d_host_subset_options_ok(int radius, int iterations, float epsilon, float max_shift, float max_gradient)
 {
@@ -797,6 +828,19 @@ HOST_API int flow2d_host_refine_nodes_device(flow2d_host_flow* h, void* dev_fram
 {
     return refine_nodes_device(h, dev_frame_0, dev_frame_1, dev_node_u0, dev_node_v0, grid_radius, spacing,
                                subset_options(radius, iterations, epsilon, max_shift, max_gradient), subset_planes(dev_out), record);
+}
+
+// ... with SubsetOptions::mask (dev_mask: a device plane of the container's size, needed) and min_pixels (0: the default): the
+// first-order refinement on a region of interest (flow2d_subset_refine_masked_2d); dev_out: the eight planes.
+HOST_API int flow2d_host_refine_nodes_masked_device(flow2d_host_flow* h, void* dev_frame_0, void* dev_frame_1, void* dev_node_u0,
+                                                    void* dev_node_v0, int grid_radius, int spacing, int radius, int iterations,
+                                                    float epsilon, float max_shift, float max_gradient, void* dev_mask, int min_pixels,
+                                                    void* const* dev_out, flow2d_subset_record* record)
+{
+    if (!dev_mask) return 1;
+    return refine_nodes_device(h, dev_frame_0, dev_frame_1, dev_node_u0, dev_node_v0, grid_radius, spacing,
+                               masked_options(radius, iterations, epsilon, max_shift, max_gradient, dev_mask, false, min_pixels),
+                               subset_planes(dev_out), record);
 }
 
 // ... with SubsetOptions::order and max_curvature; dev_out: fourteen planes, the eight and uxx, uxy, uyy, vxx, vxy, vyy.
@@ -845,6 +889,21 @@ HOST_API int flow2d_host_correlate_subset_device(flow2d_host_flow* h, void* dev_
                                    dev_predictor_v, subset_planes(dev_out), reports, record, dev_flow_u, dev_flow_v);
 }
 
+// ... with SubsetOptions::mask (a device plane, needed) and min_pixels; dev_out: the eight planes.
+HOST_API int flow2d_host_correlate_subset_masked_device(flow2d_host_flow* h, void* dev_frame_0, void* dev_frame_1, float lo, float scale,
+                                                        const int* passes, int count, float min_score, float threshold, float epsilon,
+                                                        int min_neighbours, int radius, int iterations, float subset_epsilon,
+                                                        float max_shift, float max_gradient, void* dev_mask, int min_pixels,
+                                                        void* dev_predictor_u, void* dev_predictor_v, void* const* dev_out,
+                                                        OpticalFlow2D::CorrelationPassReport* reports, flow2d_subset_record* record,
+                                                        void* dev_flow_u, void* dev_flow_v)
+{
+    if (!dev_mask) return 1;
+    return correlate_subset_device(h, dev_frame_0, dev_frame_1, lo, scale, passes, count, min_score, threshold, epsilon, min_neighbours,
+                                   masked_options(radius, iterations, subset_epsilon, max_shift, max_gradient, dev_mask, false, min_pixels),
+                                   dev_predictor_u, dev_predictor_v, subset_planes(dev_out), reports, record, dev_flow_u, dev_flow_v);
+}
+
 // ... with SubsetOptions::order and max_curvature; dev_out: fourteen planes.
 HOST_API int flow2d_host_correlate_subset2_device(flow2d_host_flow* h, void* dev_frame_0, void* dev_frame_1, float lo, float scale,
                                                   const int* passes, int count, float min_score, float threshold, float epsilon,
@@ -865,7 +924,7 @@ namespace {
 int correlate_subset(flow2d_host_flow* h, const float* frame_0, const float* frame_1, const int* passes, int count, float min_score,
                      float threshold, float epsilon, int min_neighbours, const OpticalFlow2D::SubsetOptions& subset, const float* predictor_u,
                      const float* predictor_v, float* const* nodes, int node_count, OpticalFlow2D::CorrelationPassReport* reports,
-                     flow2d_subset_record* record, float* flow_u, float* flow_v, float* lo_scale)
+                     flow2d_subset_record* record, float* flow_u, float* flow_v, float* lo_scale, const float* mask_image = nullptr)
 {
     const auto list = correlation_passes(passes, count);
     const auto validation = validation_options(threshold, epsilon, min_neighbours, 1, 1);
@@ -876,6 +935,7 @@ int correlate_subset(flow2d_host_flow* h, const float* frame_0, const float* fra
     Data2D *f0 = im.In(frame_0), *f1 = im.In(frame_1);
     Data2D *pu = predictor_u ? im.In(predictor_u) : nullptr, *pv = predictor_v ? im.In(predictor_v) : nullptr;
     Data2D *fu = im.Out(flow_u, im.AfterSuccess), *fv = im.Out(flow_v, im.AfterSuccess);
+    Data2D* mask = mask_image ? im.In(mask_image) : nullptr;
     float lo = 0.f, scale = 1.f;
     OpticalFlow2D::CorrelationRange(*f0, *f1, lo, scale);
     if (!OpticalFlow2D::CorrelationPassesOk(h->width, h->height, lo, scale, list.data(), list.size(), min_score, validation) ||
@@ -887,7 +947,7 @@ int correlate_subset(flow2d_host_flow* h, const float* frame_0, const float* fra
     for (int k = 0; k < node_count; ++k) images.emplace_back(nw, nh);
     Data2D* wanted[kSubset2Planes] = {};
     for (int k = 0; k < node_count; ++k) wanted[k] = nodes[k] ? &images[k] : nullptr;
-    h->flow.CorrelateSubset(*f0, *f1, list.data(), list.size(), min_score, validation, subset, wanted, reports, record, fu, fv, pu, pv);
+    h->flow.CorrelateSubset(*f0, *f1, list.data(), list.size(), min_score, validation, subset, wanted, reports, record, fu, fv, pu, pv, mask);
     const int rc = im.Finish(h->flow);
     if (rc) return rc;
     for (int k = 0; k < node_count; ++k)
@@ -909,6 +969,20 @@ HOST_API int flow2d_host_correlate_subset(flow2d_host_flow* h, const float* fram
     return correlate_subset(h, frame_0, frame_1, passes, count, min_score, threshold, epsilon, min_neighbours,
                             subset_options(radius, iterations, subset_epsilon, max_shift, max_gradient), predictor_u, predictor_v, nodes, 8,
                             reports, record, flow_u, flow_v, lo_scale);
+}
+
+// ... with a mask image (a tight host image of the frames' size, needed; the object uploads it once) and min_pixels; nodes: eight arrays.
+HOST_API int flow2d_host_correlate_subset_masked(flow2d_host_flow* h, const float* frame_0, const float* frame_1, const int* passes,
+                                                 int count, float min_score, float threshold, float epsilon, int min_neighbours, int radius,
+                                                 int iterations, float subset_epsilon, float max_shift, float max_gradient,
+                                                 const float* mask, int min_pixels, const float* predictor_u, const float* predictor_v,
+                                                 float* const* nodes, OpticalFlow2D::CorrelationPassReport* reports,
+                                                 flow2d_subset_record* record, float* flow_u, float* flow_v, float* lo_scale)
+{
+    if (!mask) return 1;
+    return correlate_subset(h, frame_0, frame_1, passes, count, min_score, threshold, epsilon, min_neighbours,
+                            masked_options(radius, iterations, subset_epsilon, max_shift, max_gradient, nullptr, true, min_pixels),
+                            predictor_u, predictor_v, nodes, 8, reports, record, flow_u, flow_v, lo_scale, mask);
 }
 
 // ... with SubsetOptions::order and max_curvature; nodes: fourteen arrays, the six curvatures all or none.
@@ -966,6 +1040,18 @@ HOST_API int flow2d_host_refine_nodes_from_device(flow2d_host_flow* h, void* dev
 {
     return refine_nodes_from_device(h, dev_frame_0, dev_frame_1, dev_start, grid_radius, spacing,
                                     subset_options(radius, iterations, epsilon, max_shift, max_gradient), subset_planes(dev_out), record);
+}
+
+// ... with SubsetOptions::mask (a device plane, needed) and min_pixels; dev_out: the eight planes.
+HOST_API int flow2d_host_refine_nodes_from_masked_device(flow2d_host_flow* h, void* dev_frame_0, void* dev_frame_1, void* const* dev_start,
+                                                         int grid_radius, int spacing, int radius, int iterations, float epsilon,
+                                                         float max_shift, float max_gradient, void* dev_mask, int min_pixels,
+                                                         void* const* dev_out, flow2d_subset_record* record)
+{
+    if (!dev_mask) return 1;
+    return refine_nodes_from_device(h, dev_frame_0, dev_frame_1, dev_start, grid_radius, spacing,
+                                    masked_options(radius, iterations, epsilon, max_shift, max_gradient, dev_mask, false, min_pixels),
+                                    subset_planes(dev_out), record);
 }
 
 // ... with SubsetOptions::order and max_curvature; dev_out: fourteen planes.  The start's curvatures are 0.
@@ -1037,6 +1123,23 @@ HOST_API int flow2d_host_correlate_subset_sequence_device(flow2d_host_flow* h, v
                                             predict_neighbours, sequence_max_shift, dev_out, 8, reports, steps, dev_flows);
 }
 
+// ... with SubsetOptions::mask (a device plane, needed: every step uses it) and min_pixels; dev_out: eight planes per step.
+HOST_API int flow2d_host_correlate_subset_masked_sequence_device(flow2d_host_flow* h, void* const* dev_frames, int frames, float lo,
+                                                                 float scale, const int* passes, int count, float min_score,
+                                                                 float threshold, float epsilon, int min_neighbours, int radius,
+                                                                 int iterations, float subset_epsilon, float max_shift, float max_gradient,
+                                                                 void* dev_mask, int min_pixels, int fill, int min_state,
+                                                                 int predict_neighbours, float sequence_max_shift, void* const* dev_out,
+                                                                 OpticalFlow2D::CorrelationPassReport* reports,
+                                                                 OpticalFlow2D::SequenceStepReport* steps, void* const* dev_flows)
+{
+    if (!dev_mask) return 1;
+    return correlate_subset_sequence_device(h, dev_frames, frames, lo, scale, passes, count, min_score, threshold, epsilon, min_neighbours,
+                                            masked_options(radius, iterations, subset_epsilon, max_shift, max_gradient, dev_mask, false,
+                                                           min_pixels),
+                                            fill, min_state, predict_neighbours, sequence_max_shift, dev_out, 8, reports, steps, dev_flows);
+}
+
 // ... with SubsetOptions::order and max_curvature; dev_out: fourteen planes per step, the six curvatures all or none.
 HOST_API int flow2d_host_correlate_subset2_sequence_device(flow2d_host_flow* h, void* const* dev_frames, int frames, float lo, float scale,
                                                            const int* passes, int count, float min_score, float threshold, float epsilon,
@@ -1060,7 +1163,7 @@ int correlate_subset_sequence(flow2d_host_flow* h, const float* const* frames, i
                               float threshold, float epsilon, int min_neighbours, const OpticalFlow2D::SubsetOptions& subset, int fill,
                               int min_state, int predict_neighbours, float sequence_max_shift, float* const* nodes, size_t per_step,
                               OpticalFlow2D::CorrelationPassReport* reports, OpticalFlow2D::SequenceStepReport* steps, float* const* flows,
-                              float* lo_scale)
+                              float* lo_scale, const float* mask_image = nullptr)
 {
     const auto list = correlation_passes(passes, count);
     const auto validation = validation_options(threshold, epsilon, min_neighbours, 1, 1);
@@ -1078,6 +1181,7 @@ int correlate_subset_sequence(flow2d_host_flow* h, const float* const* frames, i
     std::vector<Data2D*> in(n), flow_images(2 * step_count, nullptr);
     for (size_t k = 0; k < n; ++k) in[k] = im.In(frames[k]);
     for (size_t k = 0; flows && k < 2 * step_count; ++k) flow_images[k] = im.Out(flows[k], im.AfterSuccess);
+    Data2D* mask = mask_image ? im.In(mask_image) : nullptr;
     float lo = 0.f, scale = 1.f;
     OpticalFlow2D::CorrelationRange(*in[0], *in[1], lo, scale);
     if (!OpticalFlow2D::CorrelationPassesOk(h->width, h->height, lo, scale, list.data(), list.size(), min_score, validation) ||
@@ -1091,7 +1195,7 @@ int correlate_subset_sequence(flow2d_host_flow* h, const float* const* frames, i
     std::vector<Data2D*> wanted(per_step * step_count);
     for (size_t k = 0; k < per_step * step_count; ++k) wanted[k] = nodes[k] ? &images[k] : nullptr;
     h->flow.CorrelateSubsetSequence(in.data(), n, list.data(), list.size(), min_score, validation, subset, sequence, wanted.data(), reports,
-                                    steps, flows ? flow_images.data() : nullptr);
+                                    steps, flows ? flow_images.data() : nullptr, mask);
     const int rc = im.Finish(h->flow);
     if (rc) return rc;
     for (size_t k = 0; k < per_step * step_count; ++k)
@@ -1114,6 +1218,23 @@ HOST_API int flow2d_host_correlate_subset_sequence(flow2d_host_flow* h, const fl
     return correlate_subset_sequence(h, frames, count_frames, passes, count, min_score, threshold, epsilon, min_neighbours,
                                      subset_options(radius, iterations, subset_epsilon, max_shift, max_gradient), fill, min_state,
                                      predict_neighbours, sequence_max_shift, nodes, 8, reports, steps, flows, lo_scale);
+}
+
+// ... with a mask image (a tight host image of the frames' size, needed; uploaded once for all steps) and min_pixels; nodes: eight
+// arrays per step.
+HOST_API int flow2d_host_correlate_subset_masked_sequence(flow2d_host_flow* h, const float* const* frames, int count_frames,
+                                                          const int* passes, int count, float min_score, float threshold, float epsilon,
+                                                          int min_neighbours, int radius, int iterations, float subset_epsilon,
+                                                          float max_shift, float max_gradient, const float* mask, int min_pixels, int fill,
+                                                          int min_state, int predict_neighbours, float sequence_max_shift,
+                                                          float* const* nodes, OpticalFlow2D::CorrelationPassReport* reports,
+                                                          OpticalFlow2D::SequenceStepReport* steps, float* const* flows, float* lo_scale)
+{
+    if (!mask) return 1;
+    return correlate_subset_sequence(h, frames, count_frames, passes, count, min_score, threshold, epsilon, min_neighbours,
+                                     masked_options(radius, iterations, subset_epsilon, max_shift, max_gradient, nullptr, true, min_pixels),
+                                     fill, min_state, predict_neighbours, sequence_max_shift, nodes, 8, reports, steps, flows, lo_scale,
+                                     mask);
 }
 
 // ... with SubsetOptions::order and max_curvature; nodes: fourteen arrays per step, the six curvatures all or none.

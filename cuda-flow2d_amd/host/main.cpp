@@ -101,6 +101,12 @@
 // (OpticalFlow2D::ContinueSubsetSequence), with --subset-max-shift defaulting to 4; the (last) pass of --correlation... gives the grid
 // only.  One line "Prediction: {json}" -- the options and per pass "nodes", "kept", "predicted", "empty" -- is printed before the
 // "Subset:" line, whose "passes" is then 0.  Without the option nothing changes.
+// --subset-mask FILE [--subset-mask-invert] [--subset-min-pixels N, 6 .. (2R + 1)^2, default a quarter of the subset], valid only
+// together with --subset-refine (order 1), is digital image correlation on a region of interest (flow2d_subset_refine_masked_2d): FILE
+// is a raw image of the frames' size and format, read like them, in FILE_0's coordinates, whose values of 0.5 and more mean "not the
+// specimen"; with --subset-mask-invert it is a region image, non-zero meaning "inside".  A subset is refined on its usable pixels; a
+// node off the specimen, or with fewer than N usable pixels, is masked: state -4 and NaN in the node files.  One more line,
+// "SubsetMask: {json}" -- "masked", the masked nodes, and "min_pixels" -- is printed.  Without the option no byte of any output changes.
 // --initial-flow FILE.flo | --correlation-prior R  [--prior-reach P, pixels, finite and > 0, default 2] [--prior-level L, >= 0]
 // start the variational pyramid from a prior flow instead of from zero at its coarsest level (OpticalFlow2D::ComputeFlowFromPrior /
 // ComputeFlowCorrelationSeeded): the prior is a Middlebury file of the frames' size, or the window correlation of the pair with
@@ -180,6 +186,8 @@ int main(int argc, char** argv)
     OpticalFlow2D::SequenceOptions sequence;  // --subset-previous PREFIX and its options
     std::string subset_previous;
     bool sequence_option = false, subset_max_shift_given = false, subset_curvature_given = false;
+    std::string subset_mask_file;  // --subset-mask FILE, --subset-mask-invert, --subset-min-pixels N
+    bool subset_mask_invert = false, subset_mask_option = false;
     OpticalFlow2D::StrainOptions node_strain;  // --subset-strain M and --strain-order, --strain-min-nodes
     bool subset_strain = false, strain_option = false;
     OpticalFlow2D::ValidationOptions validation;                     // --validate-threshold / -epsilon / -min-neighbours / -flag-only
@@ -464,6 +472,26 @@ int main(int argc, char** argv)
             subset_option = subset_curvature_given = true;
             ++i;
         }
+        else if (!std::strcmp(argv[i], "--subset-mask")) {
+            if (i + 1 >= argc || !argv[i + 1][0]) {
+                std::printf("--subset-mask takes the file of the mask image.\n");
+                return 5;
+            }
+            subset_mask_file = argv[++i];
+        }
+        else if (!std::strcmp(argv[i], "--subset-mask-invert")) subset_mask_invert = subset_mask_option = true;
+        else if (!std::strcmp(argv[i], "--subset-min-pixels")) {
+            char* end = nullptr;
+            const long n = (i + 1 < argc) ? std::strtol(argv[i + 1], &end, 10) : 0;
+            const long largest = (2 * FLOW2D_SUBSET_MAX_RADIUS + 1) * (2 * FLOW2D_SUBSET_MAX_RADIUS + 1);
+            if (i + 1 >= argc || end == argv[i + 1] || *end != '\0' || n < FLOW2D_SUBSET_MIN_PIXELS || n > largest) {
+                std::printf("--subset-min-pixels takes a whole number of %d .. %ld.\n", FLOW2D_SUBSET_MIN_PIXELS, largest);
+                return 5;
+            }
+            subset.min_pixels = static_cast<int>(n);
+            subset_mask_option = true;
+            ++i;
+        }
         else if (!std::strcmp(argv[i], "--subset-previous")) {
             if (i + 1 >= argc || !argv[i + 1][0]) {
                 std::printf("--subset-previous takes the prefix of the previous step's node files.\n");
@@ -571,6 +599,15 @@ int main(int argc, char** argv)
     if (subset_refine && ((subset.order == 2 && subset.radius < FLOW2D_SUBSET2_MIN_RADIUS) || (subset_curvature_given && subset.order != 2))) {
         std::printf("--subset-order 2 takes a subset radius of %d at least, and --subset-max-curvature belongs to it.\n",
                     FLOW2D_SUBSET2_MIN_RADIUS);
+        return 5;
+    }
+    if ((!subset_mask_file.empty() || subset_mask_option) && !(subset_refine && !subset_mask_file.empty())) {
+        std::printf("--subset-mask FILE gives --subset-refine a region of interest, and --subset-mask-invert and --subset-min-pixels belong "
+                    "to it.\n");
+        return 5;
+    }
+    if (!subset_mask_file.empty() && subset.order == 2) {
+        std::printf("--subset-mask goes with the first-order refinement only: --subset-order 2 takes no mask.\n");
         return 5;
     }
     if ((!subset_previous.empty() || sequence_option) && !(subset_refine && !subset_previous.empty())) {
@@ -718,6 +755,14 @@ int main(int argc, char** argv)
         }
     }
 
+    Data2D subset_mask;  // --subset-mask: 1 = not the specimen
+    if (!subset_mask_file.empty()) {
+        if (!LoadFrame(subset_mask, input_path, subset_mask_file, u8, width, height)) return 2;
+        if (subset_mask_invert)  // a region image: non-zero means inside
+            for (size_t k = 0; k < width * height; ++k) subset_mask.DataPtr()[k] = subset_mask.DataPtr()[k] != 0.f ? 0.f : 1.f;
+    }
+    Data2D* const subset_mask_image = subset_mask_file.empty() ? nullptr : &subset_mask;
+
     Data2D prior_u, prior_v;
     if (!initial_flow_file.empty()) {
         if (!IOUtils::ReadFlowFLO(initial_flow_file, prior_u, prior_v)) {
@@ -848,7 +893,7 @@ int main(int argc, char** argv)
                 }
                 OpticalFlow2D::SequenceStepReport report = {};
                 optical_flow.ContinueSubsetSequence(frame_0, frame_1, previous, fine.radius, fine.spacing, subset, sequence, nodes, &report,
-                                                    &flow_u, &flow_v);
+                                                    &flow_u, &flow_v, subset_mask_image);
                 record = report.subset;
                 subset.max_shift = sequence.max_shift;
                 if (optical_flow.LastRunSucceeded()) {
@@ -864,9 +909,11 @@ int main(int argc, char** argv)
                 const bool predicted = multipass && !initial_flow_file.empty();
                 optical_flow.CorrelateSubset(frame_0, frame_1, schedule.data(), schedule.size(), correlation_min_score, validation, subset,
                                              nodes, nullptr, &record, &flow_u, &flow_v, predicted ? &prior_u : nullptr,
-                                             predicted ? &prior_v : nullptr);
+                                             predicted ? &prior_v : nullptr, subset_mask_image);
             }
             if (optical_flow.LastRunSucceeded()) {
+                if (subset_mask_image)
+                    std::printf("SubsetMask: {\"masked\": %llu, \"min_pixels\": %d}\n", record.reserved, OpticalFlow2D::SubsetMinPixels(subset));
                 for (int k = 0; k < node_images; ++k) images[k].WriteRAWToFileF32((output_path + counter + names[k] + size).c_str());
                 if (subset.order == 2) std::printf("SubsetOrder: {\"order\": 2, \"max_curvature\": %.9g}\n", subset.max_curvature);
                 std::printf("Subset: {\"radius\": %d, \"iterations\": %d, \"epsilon\": %.9g, \"max_shift\": %.9g, \"max_gradient\": %.9g, "

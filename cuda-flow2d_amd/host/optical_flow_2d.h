@@ -338,7 +338,17 @@ public:
         // curvature beyond max_curvature (per pixel; a bound, not a tuned value) strays.  Order 1 takes the calls it always took.
         int order = 1;
         float max_curvature = 0.05f;
+        // A region of interest (flow2d_subset_refine_masked_2d): mask, a device plane of the frames' size and pitch in frame 0's
+        // coordinates, 0 = none, whose values of 0.5 and more (and NaN) mean "not the specimen"; a node with fewer than min_pixels
+        // usable pixels is masked (state -4, NaN), 0 = max(6, ((2 radius + 1)^2 + 3) / 4).  Every call that refines passes them
+        // on.  In a sequence every step uses the same mask, frame 0's: a masked node comes out of flow2d_predict_nodes_2d
+        // predicted from its neighbours and goes back to masked in the refinement, so it never serves a later step as a start of
+        // its own.  Order 1 only: SubsetOptionsOk refuses a mask with order 2.
+        DevicePtr mask = 0;
+        int min_pixels = 0;
     };
+    // min_pixels as the refinement gets it: the default where it is 0
+    static int SubsetMinPixels(const SubsetOptions& subset);
     struct SubsetPlanes {
         DevicePtr u = 0, v = 0;                    // both or neither: without them planes of the object's own are written
         DevicePtr ux = 0, uy = 0, vx = 0, vy = 0;  // the four gradients: all or none
@@ -368,7 +378,9 @@ public:
     void CorrelateSubset(Data2D& frame_0, Data2D& frame_1, const CorrelationPass* passes, size_t count, float min_score,
                          const ValidationOptions& validation, const SubsetOptions& subset, Data2D* const* nodes,
                          CorrelationPassReport* reports_out, flow2d_subset_record* record_out, Data2D* flow_u = nullptr,
-                         Data2D* flow_v = nullptr, Data2D* predictor_u = nullptr, Data2D* predictor_v = nullptr);
+                         Data2D* flow_v = nullptr, Data2D* predictor_u = nullptr, Data2D* predictor_v = nullptr, Data2D* mask = nullptr);
+    // (mask, here and in the two other host-image forms below: an image of the frames' size in place of subset.mask, which these
+    // forms do not look at; the object uploads it once per call)
 
     // DIC over a loading sequence: every frame is correlated against the same reference frame, and from the second step on the
     // start of a step is the previous step's deformation, gradients included (flow2d_predict_nodes_2d, then
@@ -410,7 +422,7 @@ public:
     void CorrelateSubsetSequence(Data2D* const* frames, size_t frame_count, const CorrelationPass* passes, size_t count, float min_score,
                                  const ValidationOptions& validation, const SubsetOptions& subset, const SequenceOptions& sequence,
                                  Data2D* const* nodes, CorrelationPassReport* first_reports, SequenceStepReport* steps_out,
-                                 Data2D* const* flows = nullptr);
+                                 Data2D* const* flows = nullptr, Data2D* mask = nullptr);
 
     // One later step on its own, for a sequence that arrives frame by frame (the CLI's --subset-previous): `previous` holds the
     // last step's u, v, gradients and state (its score is not looked at); the prediction's passes and the refinement of
@@ -422,7 +434,7 @@ public:
     // Its host-image form: previous[7] -- u, v, ux, uy, vx, vy, state -- and nodes[8] as for CorrelateSubset, images of the grid.
     void ContinueSubsetSequence(Data2D& frame_0, Data2D& frame_k, Data2D* const* previous, int grid_radius, int spacing,
                                 const SubsetOptions& subset, const SequenceOptions& sequence, Data2D* const* nodes,
-                                SequenceStepReport* report_out, Data2D* flow_u = nullptr, Data2D* flow_v = nullptr);
+                                SequenceStepReport* report_out, Data2D* flow_u = nullptr, Data2D* flow_v = nullptr, Data2D* mask = nullptr);
 
     // Strain on the node grid (flow2d_node_strain_2d): the nine quantities of flow2d_deformation_2d at every node, from the
     // gradients a refinement delivered (window 0) or from a polynomial of `order` fitted by least squares to the usable nodes

@@ -759,8 +759,27 @@ OpticalFlow2D::SubsetPlanes NodePlanes(const DevicePtr* d, int count)
 }
 }  // namespace
 
+int OpticalFlow2D::SubsetMinPixels(const SubsetOptions& subset)
+{
+    const int side = 2 * subset.radius + 1;
+    return subset.min_pixels ? subset.min_pixels : std::max(FLOW2D_SUBSET_MIN_PIXELS, (side * side + 3) / 4);
+}
+
 bool OpticalFlow2D::SubsetOptionsOk(const SubsetOptions& subset)
 {
+    if (subset.mask && subset.order == 2) {
+        std::printf("Error: a subset mask goes with the first-order refinement only (order %d): flow2d_subset_refine2_2d takes no mask.\n",
+                    subset.order);
+        return false;
+    }
+    if (subset.min_pixels != 0 && (subset.min_pixels < FLOW2D_SUBSET_MIN_PIXELS ||
+                                   (subset.radius >= 1 && subset.radius <= FLOW2D_SUBSET_MAX_RADIUS &&
+                                    subset.min_pixels > (2 * subset.radius + 1) * (2 * subset.radius + 1)))) {
+        std::printf("Error: a masked subset refinement takes %d .. (2 radius + 1)^2 pixels at least (%d at radius %d), or 0 for a quarter "
+                    "of the subset.\n",
+                    FLOW2D_SUBSET_MIN_PIXELS, subset.min_pixels, subset.radius);
+        return false;
+    }
     if (subset.radius >= 1 && subset.radius <= FLOW2D_SUBSET_MAX_RADIUS && subset.iterations >= 1 &&
         subset.iterations <= FLOW2D_SUBSET_MAX_ITERATIONS && std::isfinite(subset.epsilon) && subset.epsilon >= 0.f &&
         std::isfinite(subset.max_shift) && subset.max_shift > 0.f && std::isfinite(subset.max_gradient) && subset.max_gradient > 0.f &&
@@ -815,6 +834,18 @@ bool OpticalFlow2D::QueueRefineNodes(DevicePtr dev_frame_0, DevicePtr dev_frame_
                                                         subset.max_shift, subset.max_gradient, subset.max_curvature, AsPlane(u), AsPlane(v),
                                                         out_gradients, out_curvatures, plane(out.score), plane(out.state), record),
                                "flow2d_subset_refine2_2d");
+    } else if (subset.mask) {
+        // (without a start the entry takes the zero gradients of flow2d_subset_refine_2d)
+        const DevicePtr none[4] = {0, 0, 0, 0};
+        const DevicePtr* g = start_gradients ? start_gradients : none;
+        ok = !CheckFlow2DError(flow2d_subset_refine_masked_2d(context_, AsPlane(dev_frame_0), AsPlane(dev_frame_1), W, H, pitch,
+                                                              AsPlane(dev_node_u0), AsPlane(dev_node_v0), plane(g[0]), plane(g[1]), plane(g[2]),
+                                                              plane(g[3]), nw, nh, pitch, grid_radius, spacing, subset.radius,
+                                                              subset.iterations, subset.epsilon, subset.max_shift, subset.max_gradient,
+                                                              AsPlane(subset.mask), SubsetMinPixels(subset), AsPlane(u), AsPlane(v),
+                                                              plane(out.ux), plane(out.uy), plane(out.vx), plane(out.vy), plane(out.score),
+                                                              plane(out.state), record),
+                               "flow2d_subset_refine_masked_2d");
     } else if (start_gradients)
         ok = !CheckFlow2DError(flow2d_subset_refine_from_2d(context_, AsPlane(dev_frame_0), AsPlane(dev_frame_1), W, H, pitch,
                                                             AsPlane(dev_node_u0), AsPlane(dev_node_v0), plane(start_gradients[0]),
@@ -895,7 +926,7 @@ bool OpticalFlow2D::QueueCorrelateSubset(DevicePtr dev_frame_0, DevicePtr dev_fr
 void OpticalFlow2D::CorrelateSubset(Data2D& frame_0, Data2D& frame_1, const CorrelationPass* passes, size_t count, float min_score,
                                     const ValidationOptions& validation, const SubsetOptions& subset, Data2D* const* nodes,
                                     CorrelationPassReport* reports_out, flow2d_subset_record* record_out, Data2D* flow_u, Data2D* flow_v,
-                                    Data2D* predictor_u, Data2D* predictor_v)
+                                    Data2D* predictor_u, Data2D* predictor_v, Data2D* mask)
 {
     last_run_ok_ = false;
     if (!IsInitialized() || !nodes || !nodes[0] || !nodes[1] || (flow_u == nullptr) != (flow_v == nullptr) ||
@@ -910,11 +941,15 @@ void OpticalFlow2D::CorrelateSubset(Data2D& frame_0, Data2D& frame_1, const Corr
     // the node planes: containers with no image of their size behind them, downloaded below
     for (int k = 0; k < images; ++k) planes.Add(nullptr, CallPlanes::Out, nodes[k] != nullptr);
     if (predictor_u) planes.Add(predictor_u, CallPlanes::In).Add(predictor_v, CallPlanes::In);
+    const int mask_at = 4 + images + (predictor_u ? 2 : 0);  // the mask, uploaded once, behind everything else
+    if (mask) planes.Add(mask, CallPlanes::In);
     if (!planes.SizesMatch()) return;
     float lo = 0.f, scale = 1.f;
     CorrelationRange(frame_0, frame_1, lo, scale);
     const size_t W = dev_container_size_.width, H = dev_container_size_.height;
-    if (!CorrelationPassesOk(W, H, lo, scale, passes, count, min_score, validation) || !SubsetOptionsOk(subset)) return;
+    SubsetOptions masked = subset;
+    masked.mask = mask ? 1 : 0;  // (for the check; the plane's address below)
+    if (!CorrelationPassesOk(W, H, lo, scale, passes, count, min_score, validation) || !SubsetOptionsOk(masked)) return;
     size_t nw = 0, nh = 0;
     flow2d_correlation_grid(W, H, passes[count - 1].radius, passes[count - 1].spacing, &nw, &nh);
     for (int k = 0; k < images; ++k)
@@ -925,8 +960,9 @@ void OpticalFlow2D::CorrelateSubset(Data2D& frame_0, Data2D& frame_1, const Corr
     HostCall call(context_, last_total_ms_, planes.Allocate());
     const DevicePtr* d = planes.data();
     const SubsetPlanes out = NodePlanes(d + 4, images);
+    masked.mask = mask ? d[mask_at] : 0;
     bool ok = planes.Upload() &&
-              CorrelateSubsetDevice(d[0], d[1], lo, scale, passes, count, min_score, validation, subset, predictor_u ? d[4 + images] : 0,
+              CorrelateSubsetDevice(d[0], d[1], lo, scale, passes, count, min_score, validation, masked, predictor_u ? d[4 + images] : 0,
                                     predictor_u ? d[5 + images] : 0, out, reports_out, record_out, d[2], d[3]) &&
               planes.Download();
     for (int k = 0; ok && k < images; ++k)
@@ -1026,7 +1062,7 @@ bool OpticalFlow2D::ContinueSubsetSequenceDevice(DevicePtr dev_frame_0, DevicePt
 
 void OpticalFlow2D::ContinueSubsetSequence(Data2D& frame_0, Data2D& frame_k, Data2D* const* previous, int grid_radius, int spacing,
                                            const SubsetOptions& subset, const SequenceOptions& sequence, Data2D* const* nodes,
-                                           SequenceStepReport* report_out, Data2D* flow_u, Data2D* flow_v)
+                                           SequenceStepReport* report_out, Data2D* flow_u, Data2D* flow_v, Data2D* mask)
 {
     last_run_ok_ = false;
     if (!IsInitialized() || !previous || !nodes || !nodes[0] || !nodes[1] || (flow_u == nullptr) != (flow_v == nullptr)) return;
@@ -1054,6 +1090,7 @@ void OpticalFlow2D::ContinueSubsetSequence(Data2D& frame_0, Data2D& frame_k, Dat
     // the node planes, read and written: containers with no image of their size behind them, uploaded and downloaded here
     for (int k = 0; k < 7; ++k) planes.Add(nullptr, CallPlanes::Out, true);
     for (int k = 0; k < images; ++k) planes.Add(nullptr, CallPlanes::Out, nodes[k] != nullptr);
+    if (mask) planes.Add(mask, CallPlanes::In);  // uploaded once, behind everything else
     if (!planes.SizesMatch()) return;
     HostCall call(context_, last_total_ms_, planes.Allocate());
     const DevicePtr* d = planes.data();
@@ -1061,7 +1098,9 @@ void OpticalFlow2D::ContinueSubsetSequence(Data2D& frame_0, Data2D& frame_k, Dat
     for (int k = 0; ok && k < 7; ++k) ok = CopyData2DtoDevice(*previous[k], d[4 + k], H, dev_container_size_.pitch);
     const SubsetPlanes last = {d[4], d[5], d[6], d[7], d[8], d[9], 0, d[10]};
     const SubsetPlanes out = NodePlanes(d + 11, images);
-    ok = ok && ContinueSubsetSequenceDevice(d[0], d[1], last, grid_radius, spacing, subset, sequence, out, report_out, d[2], d[3]) &&
+    SubsetOptions masked = subset;
+    masked.mask = mask ? d[11 + images] : 0;
+    ok = ok && ContinueSubsetSequenceDevice(d[0], d[1], last, grid_radius, spacing, masked, sequence, out, report_out, d[2], d[3]) &&
          planes.Download();
     for (int k = 0; ok && k < images; ++k)
         if (nodes[k]) ok = CopyData2DFromDevice(d[11 + k], *nodes[k], H, dev_container_size_.pitch);
@@ -1228,7 +1267,7 @@ bool OpticalFlow2D::CorrelateSubsetSequenceDevice(const DevicePtr* dev_frames, s
 void OpticalFlow2D::CorrelateSubsetSequence(Data2D* const* frames, size_t frame_count, const CorrelationPass* passes, size_t count,
                                             float min_score, const ValidationOptions& validation, const SubsetOptions& subset,
                                             const SequenceOptions& sequence, Data2D* const* nodes, CorrelationPassReport* first_reports,
-                                            SequenceStepReport* steps_out, Data2D* const* flows)
+                                            SequenceStepReport* steps_out, Data2D* const* flows, Data2D* mask)
 {
     last_run_ok_ = false;
     if (!IsInitialized() || !frames || frame_count < 2 || !nodes) return;
@@ -1246,11 +1285,14 @@ void OpticalFlow2D::CorrelateSubsetSequence(Data2D* const* frames, size_t frame_
     for (size_t k = 0; k < 2 * steps; ++k) planes.Add(flows ? flows[k] : nullptr, CallPlanes::Out);
     // the node planes: containers with no image of their size behind them, downloaded below
     for (size_t k = 0; k < images * steps; ++k) planes.Add(nullptr, CallPlanes::Out, nodes[k] != nullptr);
+    if (mask) planes.Add(mask, CallPlanes::In);  // uploaded once for all steps, behind everything else
     if (!planes.SizesMatch()) return;
     float lo = 0.f, scale = 1.f;
     CorrelationRange(*frames[0], *frames[1], lo, scale);
     const size_t W = dev_container_size_.width, H = dev_container_size_.height;
-    if (!CorrelationPassesOk(W, H, lo, scale, passes, count, min_score, validation) || !SubsetOptionsOk(subset) ||
+    SubsetOptions masked = subset;
+    masked.mask = mask ? 1 : 0;  // (for the check; the plane's address below)
+    if (!CorrelationPassesOk(W, H, lo, scale, passes, count, min_score, validation) || !SubsetOptionsOk(masked) ||
         !SequenceOptionsOk(sequence))
         return;
     size_t nw = 0, nh = 0;
@@ -1268,8 +1310,9 @@ void OpticalFlow2D::CorrelateSubsetSequence(Data2D* const* frames, size_t frame_
     for (size_t k = 0; k < steps; ++k) {
         out[k] = NodePlanes(dev_nodes + images * k, static_cast<int>(images));
     }
+    masked.mask = mask ? dev_nodes[images * steps] : 0;
     bool ok = planes.Upload() &&
-              CorrelateSubsetSequenceDevice(d, frame_count, lo, scale, passes, count, min_score, validation, subset, sequence, out.data(),
+              CorrelateSubsetSequenceDevice(d, frame_count, lo, scale, passes, count, min_score, validation, masked, sequence, out.data(),
                                             first_reports, steps_out, flows ? dev_flows : nullptr) &&
               planes.Download();
     for (size_t k = 0; ok && k < images * steps; ++k)

@@ -36,7 +36,9 @@ are NOT in SCENES: the tables and tests that iterate over that tuple are about t
 Speckle deformations (make_speckle_deformation(name, width, height, seed), name one of SPECKLE_DEFORMATIONS), for the subset
 refinement (flow2d_subset_refine_2d): the same texture under a rotation, a stretch and a shear, each with a translation.
 make_speckle_deformation_sequence(name, steps, step_size, ...) carries one of them on, k times per step k, every frame against
-frame 0: the loading sequence flow2d_subset_refine_from_2d is for.
+frame 0: the loading sequence flow2d_subset_refine_from_2d is for.  make_speckle_specimen(name, width, height, seed) puts the
+same deformations on a plate with a hole in front of a static background and returns the scene with its mask: what
+flow2d_subset_refine_masked_2d is for.
 Pure numpy: no device, no library.
 """
 import numpy as np
@@ -129,6 +131,41 @@ def make_speckle_deformation(name, width=96, height=80, seed=0):
     else:
         raise ValueError("unknown speckle deformation %r (one of %s)" % (name, ", ".join(SPECKLE_DEFORMATIONS)))
     return _affine_scene("speckle_" + name, width, height, texture, a, (1.6, -0.7))
+
+
+def make_speckle_specimen(name, width=96, height=80, seed=0):
+    """A specimen in front of a background that does not move with it, for the masked subset refinement
+    (flow2d_subset_refine_masked_2d): the deformation `name` (one of SPECKLE_DEFORMATIONS) of make_speckle_deformation, W about
+    the centre c = ((width - 1) / 2, (height - 1) / 2), applied to a plate with a hole.  A point is *inside* when |x - c0| <=
+    30.5 width / 96, |y - c1| <= 24.5 height / 80 and (x - c0)^2 + (y - c1)^2 > (9.5 min(width / 96, height / 80))^2.  T =
+    Speckle(seed) is the specimen's texture, B = 0.3 Speckle(seed + 7) + 5 the static background:
+      frame_0(x) = inside(x) ? T(x) : B(x);   frame_1(X) = inside(W^-1 X) ? T(W^-1 X) : B(X).
+    Returns (scene, mask): the Scene of make_speckle_deformation with these frames (float32; gt_u, gt_v are W(x) - x everywhere,
+    true on the specimen) and the mask in frame 0's coordinates, float32, 1 where not inside, else 0."""
+    plain = make_speckle_deformation(name, width, height, seed)
+    texture, background = Speckle(seed), Speckle(seed + 7)
+    c0, c1 = (width - 1) / 2.0, (height - 1) / 2.0
+    half_w, half_h, hole = 30.5 * width / 96.0, 24.5 * height / 80.0, 9.5 * min(width / 96.0, height / 80.0)
+
+    def inside(x, y):
+        x, y = np.asarray(x, np.float64), np.asarray(y, np.float64)
+        return (np.abs(x - c0) <= half_w) & (np.abs(y - c1) <= half_h) & ((x - c0) ** 2 + (y - c1) ** 2 > hole ** 2)
+
+    def ground(x, y):
+        return 0.3 * background(x, y) + 5.0
+
+    def frame_0_at(x, y):
+        return np.where(inside(x, y), texture(x, y), ground(x, y))
+
+    def frame_1_at(x, y):
+        x, y = np.asarray(x, np.float64), np.asarray(y, np.float64)
+        bu, bv = plain.back_flow_at(x, y)
+        return np.where(inside(x + bu, y + bv), texture(x + bu, y + bv), ground(x, y))
+
+    ys, xs = np.mgrid[0:height, 0:width].astype(np.float64)
+    scene = Scene("specimen_" + name, frame_0_at(xs, ys).astype(np.float32), frame_1_at(xs, ys).astype(np.float32), plain.gt_u, plain.gt_v,
+                  None, frame_1_at, frame_0_at=frame_0_at, back_flow_at=plain.back_flow_at)
+    return scene, np.where(inside(xs, ys), 0.0, 1.0).astype(np.float32)
 
 
 SPECKLE_BENDINGS = ("bend", "bulge")

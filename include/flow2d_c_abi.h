@@ -48,7 +48,8 @@ extern "C" {
  * offset and the normalised median test between passes) and flow2d_subset_refine_2d (affine Gauss-Newton refinement of
  * correlation nodes) and flow2d_subset_refine_from_2d / flow2d_predict_nodes_2d (DIC over a sequence: the refinement started
  * from the previous step's deformation, and that start built from a step's result) and flow2d_node_strain_2d /
- * flow2d_node_strain_workspace_bytes (strain on the node grid from least-squares strain windows) were added under 1. */
+ * flow2d_node_strain_workspace_bytes (strain on the node grid from least-squares strain windows) and
+ * flow2d_subset_refine_masked_2d (the refinement on a region of interest) were added under 1. */
 #define FLOW2D_ABI_VERSION 1
 
 typedef enum flow2d_status {
@@ -1053,7 +1054,7 @@ typedef struct flow2d_subset_record {
     unsigned long long flat;        /* state -2 */
     unsigned long long no_input;    /* state -1 */
     unsigned long long iterations;  /* iterations begun, over all nodes */
-    unsigned long long reserved;    /* 0 */
+    unsigned long long reserved;    /* 0; flow2d_subset_refine_masked_2d: the masked nodes, state -4 */
 } flow2d_subset_record;
 
 #define FLOW2D_SUBSET_RECORD_BYTES 64
@@ -1095,6 +1096,49 @@ FLOW2D_API int flow2d_subset_refine_from_2d(flow2d_context* ctx, const float* fr
                                             float* out_v, float* out_ux /* the four gradient planes: all or none */, float* out_uy,
                                             float* out_vx, float* out_vy, float* out_score /* may be NULL */,
                                             float* out_state /* may be NULL */, flow2d_subset_record* record /* device, may be NULL */);
+
+/* Masked subset refinement, digital image correlation on a region of interest: flow2d_subset_refine_from_2d with one more input
+ * plane, mask, which says which pixels of frame 0 are not the specimen -- the background beside a dog-bone, the inside of a hole
+ * --, and min_pixels.  A subset that reaches across the specimen's edge is refined on its specimen pixels alone.  Added to ABI
+ * version 1 without changing any existing entry.
+ * mask holds width x height floats with the frames' pitch_bytes, in frame 0's coordinates; in a batch instance b lies at
+ * b * stride floats, like the frames.
+ * Everything not named here is the text of flow2d_subset_refine_from_2d word for word: the arithmetic in IEEE double with every
+ * operation rounded on its own, the positive comparisons, the Catmull-Rom sample, Cholesky and Solve, the update, the stop test
+ * with R, the outputs of the states >= 0, -1, -2 and -3, batches and graph capture.
+ * Excluded.  A pixel is *excluded* when !(m < 0.5), m its mask value compared as a float: 1 means "do not use" (the convention of
+ * the occlusion masks), and a NaN is excluded.
+ * Usable.  Pixel (x, y) is *usable* when none of (x, y), (min(x + 1, width - 1), y), (max(x - 1, 0), y), (x, min(y + 1, height - 1))
+ * and (x, max(y - 1, 0)) is excluded: the pixel itself and the four its fx and fy read.
+ * States.  One more, -4 *masked* (FLOW2D_SUBSET_STATE_MASKED).  The tests run in this order:
+ *   1. *Masked* when the centre pixel (cx, cy) is excluded -- before *no input*: an off-specimen node is masked whatever its start holds.
+ *   2. *No input*, as flow2d_subset_refine_from_2d has it.
+ *   3. The frame-0 window test (*strayed*), as there.
+ *   4. Nv = the number of usable pixels of the subset.  *Masked* when !(Nv >= min_pixels).
+ * Sums.  The usable pixels form a list m = 0 .. Nv - 1 in ascending k.  Every *sum over the subset* is a sum over that list, of
+ * Nv terms, and Nv stands where N stood (fm, gm).  Positions are formed, tested against the frame (1. Positions) and sampled only
+ * for the usable pixels.  The order in which a sum's terms are added stays the one thing this text leaves open.
+ * Outputs.  Masked: u, v and the four gradients NaN (0x7FC00000), score 0, state -4; the node adds no iterations.
+ * Record.  The eighth word of record[b], which the other entries write as 0 (flow2d_subset_record::reserved: the struct stays as it
+ * is), holds the count of masked nodes here.
+ * Equivalences.  mask == NULL (min_pixels is then not looked at): every output byte and the record are those of
+ * flow2d_subset_refine_from_2d -- the call is forwarded.  A mask that excludes nothing: every output byte and the record are again
+ * those of flow2d_subset_refine_from_2d; the list is then k itself.
+ * Refusals.  Those of flow2d_subset_refine_from_2d, and with a mask also FLOW2D_ERR_INVALID_ARGUMENT, nothing written, for a
+ * min_pixels outside FLOW2D_SUBSET_MIN_PIXELS .. (2R + 1)^2 (six unknowns need six pixels), a mask that breaks the frames' plane
+ * rules, or a written range that overlaps the mask. */
+#define FLOW2D_SUBSET_STATE_MASKED (-4)
+#define FLOW2D_SUBSET_MIN_PIXELS 6
+FLOW2D_API int flow2d_subset_refine_masked_2d(flow2d_context* ctx, const float* frame_0, const float* frame_1, size_t width,
+                                              size_t height, size_t pitch_bytes, const float* node_u0, const float* node_v0,
+                                              const float* node_ux0 /* the four start gradients: all or none */,
+                                              const float* node_uy0, const float* node_vx0, const float* node_vy0, size_t nw, size_t nh,
+                                              size_t node_pitch_bytes, int grid_radius, int spacing, int subset_radius,
+                                              int max_iterations, float epsilon, float max_shift, float max_gradient,
+                                              const float* mask /* device, may be NULL */, int min_pixels, float* out_u, float* out_v,
+                                              float* out_ux /* the four gradient planes: all or none */, float* out_uy, float* out_vx,
+                                              float* out_vy, float* out_score /* may be NULL */, float* out_state /* may be NULL */,
+                                              flow2d_subset_record* record /* device, may be NULL */);
 
 /* Subset refinement with a second-order shape function (Lu & Cary 2000; Gao, Cheng, Su, Xu, Zhang & Zhang 2015): the
  * inverse-compositional Gauss-Newton iteration of flow2d_subset_refine_2d with twelve parameters,
