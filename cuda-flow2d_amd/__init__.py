@@ -325,6 +325,14 @@ class SequenceStepReport(C.Structure):
         return {"subset": self.subset.summary(), "prediction": [self.prediction[k].summary() for k in range(fill)]}
 
 
+class SubsetOptions(C.Structure):
+    """flow2d_host_subset_options of host/host_c_api.cpp: OpticalFlow2D::SubsetOptions as every host entry that refines takes it.
+    mask: a device plane for a *_device entry, a host image otherwise, None for none."""
+    _fields_ = [("radius", C.c_int), ("iterations", C.c_int), ("epsilon", C.c_float), ("max_shift", C.c_float),
+                ("max_gradient", C.c_float), ("order", C.c_int), ("max_curvature", C.c_float), ("min_pixels", C.c_int),
+                ("mask", C.c_void_p)]
+
+
 class CorrelationPassReport(C.Structure):
     """OpticalFlow2D::CorrelationPassReport: one pass of correlate_multipass -- its grid, the correlation's record and the
     validation's (zero where the pass was not validated)."""
@@ -1267,26 +1275,43 @@ class Context:
         written and stay on the device; without them the call allocates all eight, downloads them and returns arrays.  record:
         True -- the counts are read back (synchronises) --, a subset_records Plane of the caller's, or False / None.
         Returns (u, v, (ux, uy, vx, vy) or None, score or None, state or None, SubsetRecord or None)."""
+        def issue(held, rec):
+            _check(hip_lib().flow2d_subset_refine_2d(self.handle, f0.ptr, f1.ptr, w, h, f0.pitch, node_u0.ptr, node_v0.ptr, nw, nh,
+                                                     node_u0.pitch, int(grid_radius), int(spacing), int(subset_radius),
+                                                     int(max_iterations), float(epsilon), float(max_shift), float(max_gradient),
+                                                     *held, rec), "flow2d_subset_refine_2d")
+
+        return self._subset_refine_call("subset_refine", issue, node_u0, nw, nh, out_u, out_v, [(out_gradients, 4)], out_score,
+                                        out_state, record, instances)
+
+    def _subset_refine_call(self, name, issue, node_u0, nw, nh, out_u, out_v, out_groups, out_score, out_state, record, instances):
+        """What subset_refine, subset_refine_from, subset_refine_masked and subset_refine2 do around their entry: the planes --
+        the caller's out_u, out_v, groups (each a (planes or None, count) pair: the gradients, at order 2 the curvatures too),
+        out_score and out_state, or as many of the call's own --, the record, issue(held, rec) with their addresses (None: absent)
+        in that order, the download of the call's own planes, and the result: (u, v, a tuple or None per group, score, state,
+        SubsetRecord or None)."""
         own_planes = out_u is None and out_v is None
         if not own_planes and (out_u is None or out_v is None):
-            raise ValueError("subset_refine takes both output planes or neither")
+            raise ValueError("%s takes both output planes or neither" % name)
         own_record = record is True
         if own_record and instances != 1:
             raise ValueError("a lock-step batch takes the caller's records")
         if own_planes:
-            held = [self.plane(node_u0.pitch // 4, nh) for _ in range(8)]
+            held = [self.plane(node_u0.pitch // 4, nh) for _ in range(4 + sum(n for _, n in out_groups))]
         else:
-            held = [out_u, out_v] + list(out_gradients if out_gradients is not None else (None,) * 4) + [out_score, out_state]
+            held = [out_u, out_v]
+            for planes, n in out_groups:
+                held += list(planes if planes is not None else (None,) * n)
+            held += [out_score, out_state]
         rec = self.subset_records(instances) if own_record else (record or None)
         try:
-            _check(hip_lib().flow2d_subset_refine_2d(self.handle, f0.ptr, f1.ptr, w, h, f0.pitch, node_u0.ptr, node_v0.ptr, nw, nh,
-                                                     node_u0.pitch, int(grid_radius), int(spacing), int(subset_radius),
-                                                     int(max_iterations), float(epsilon), float(max_shift), float(max_gradient),
-                                                     *[q.ptr if q is not None else None for q in held],
-                                                     rec.ptr if rec is not None else None), "flow2d_subset_refine_2d")
+            issue([q.ptr if q is not None else None for q in held], rec.ptr if rec is not None else None)
             got = [q.download(nw, nh) for q in held] if own_planes else held
-            gradients = tuple(got[2:6]) if got[2] is not None else None
-            return got[0], got[1], gradients, got[6], got[7], (self.read_subset_record(rec, 1)[0] if own_record else None)
+            groups, at = [], 2
+            for _, n in out_groups:
+                groups.append(tuple(got[at:at + n]) if got[at] is not None else None)
+                at += n
+            return (got[0], got[1], *groups, got[at], got[at + 1], self.read_subset_record(rec, 1)[0] if own_record else None)
         finally:
             for q in (held if own_planes else []) + ([rec] if own_record else []):
                 q.free()
@@ -1300,34 +1325,18 @@ class Context:
         reference frame, through predict_nodes --, or None: then every byte is subset_refine's.  A node whose start holds a value
         that is not finite is SUBSET_NO_INPUT; flat and strayed nodes hand back their whole start.  Outputs, record and the
         return value as for subset_refine."""
-        own_planes = out_u is None and out_v is None
-        if not own_planes and (out_u is None or out_v is None):
-            raise ValueError("subset_refine_from takes both output planes or neither")
-        own_record = record is True
-        if own_record and instances != 1:
-            raise ValueError("a lock-step batch takes the caller's records")
-        start = list(start_gradients) if start_gradients is not None else [None] * 4
-        if len(start) != 4:
-            raise ValueError("subset_refine_from takes the four start gradients (ux0, uy0, vx0, vy0) or None")
-        if own_planes:
-            held = [self.plane(node_u0.pitch // 4, nh) for _ in range(8)]
-        else:
-            held = [out_u, out_v] + list(out_gradients if out_gradients is not None else (None,) * 4) + [out_score, out_state]
-        rec = self.subset_records(instances) if own_record else (record or None)
-        try:
+        def issue(held, rec):
+            start = list(start_gradients) if start_gradients is not None else [None] * 4
+            if len(start) != 4:
+                raise ValueError("subset_refine_from takes the four start gradients (ux0, uy0, vx0, vy0) or None")
             _check(hip_lib().flow2d_subset_refine_from_2d(self.handle, f0.ptr, f1.ptr, w, h, f0.pitch, node_u0.ptr, node_v0.ptr,
                                                           *[q.ptr if q is not None else None for q in start], nw, nh, node_u0.pitch,
                                                           int(grid_radius), int(spacing), int(subset_radius), int(max_iterations),
-                                                          float(epsilon), float(max_shift), float(max_gradient),
-                                                          *[q.ptr if q is not None else None for q in held],
-                                                          rec.ptr if rec is not None else None), "flow2d_subset_refine_from_2d")
-            got = [q.download(nw, nh) for q in held] if own_planes else held
-            gradients = tuple(got[2:6]) if got[2] is not None else None
-            return got[0], got[1], gradients, got[6], got[7], (self.read_subset_record(rec, 1)[0] if own_record else None)
-        finally:
-            for q in (held if own_planes else []) + ([rec] if own_record else []):
-                q.free()
-                self._planes.remove(q)
+                                                          float(epsilon), float(max_shift), float(max_gradient), *held, rec),
+                   "flow2d_subset_refine_from_2d")
+
+        return self._subset_refine_call("subset_refine_from", issue, node_u0, nw, nh, out_u, out_v, [(out_gradients, 4)], out_score,
+                                        out_state, record, instances)
 
     def subset_refine_masked(self, f0, f1, w, h, node_u0, node_v0, start_gradients, nw, nh, grid_radius, spacing, subset_radius, mask,
                              min_pixels=None, max_iterations=20, epsilon=1e-3, max_shift=4.0, max_gradient=0.5, out_u=None, out_v=None,
@@ -1338,37 +1347,20 @@ class Context:
         are not excluded --; a node whose centre is excluded or that has fewer than min_pixels usable pixels (None:
         subset_min_pixels(subset_radius)) is SUBSET_MASKED, NaN in all six planes, and counted in the record's `masked`.  mask =
         None: every byte is subset_refine_from's.  Outputs, record and the return value as for subset_refine."""
-        own_planes = out_u is None and out_v is None
-        if not own_planes and (out_u is None or out_v is None):
-            raise ValueError("subset_refine_masked takes both output planes or neither")
-        own_record = record is True
-        if own_record and instances != 1:
-            raise ValueError("a lock-step batch takes the caller's records")
-        start = list(start_gradients) if start_gradients is not None else [None] * 4
-        if len(start) != 4:
-            raise ValueError("subset_refine_masked takes the four start gradients (ux0, uy0, vx0, vy0) or None")
-        if min_pixels is None:
-            min_pixels = subset_min_pixels(subset_radius)
-        if own_planes:
-            held = [self.plane(node_u0.pitch // 4, nh) for _ in range(8)]
-        else:
-            held = [out_u, out_v] + list(out_gradients if out_gradients is not None else (None,) * 4) + [out_score, out_state]
-        rec = self.subset_records(instances) if own_record else (record or None)
-        try:
+        def issue(held, rec):
+            start = list(start_gradients) if start_gradients is not None else [None] * 4
+            if len(start) != 4:
+                raise ValueError("subset_refine_masked takes the four start gradients (ux0, uy0, vx0, vy0) or None")
+            pixels = subset_min_pixels(subset_radius) if min_pixels is None else min_pixels
             _check(hip_lib().flow2d_subset_refine_masked_2d(self.handle, f0.ptr, f1.ptr, w, h, f0.pitch, node_u0.ptr, node_v0.ptr,
                                                             *[q.ptr if q is not None else None for q in start], nw, nh, node_u0.pitch,
                                                             int(grid_radius), int(spacing), int(subset_radius), int(max_iterations),
                                                             float(epsilon), float(max_shift), float(max_gradient),
-                                                            mask.ptr if mask is not None else None, int(min_pixels),
-                                                            *[q.ptr if q is not None else None for q in held],
-                                                            rec.ptr if rec is not None else None), "flow2d_subset_refine_masked_2d")
-            got = [q.download(nw, nh) for q in held] if own_planes else held
-            gradients = tuple(got[2:6]) if got[2] is not None else None
-            return got[0], got[1], gradients, got[6], got[7], (self.read_subset_record(rec, 1)[0] if own_record else None)
-        finally:
-            for q in (held if own_planes else []) + ([rec] if own_record else []):
-                q.free()
-                self._planes.remove(q)
+                                                            mask.ptr if mask is not None else None, int(pixels), *held, rec),
+                   "flow2d_subset_refine_masked_2d")
+
+        return self._subset_refine_call("subset_refine_masked", issue, node_u0, nw, nh, out_u, out_v, [(out_gradients, 4)], out_score,
+                                        out_state, record, instances)
 
     def subset_refine2(self, f0, f1, w, h, node_u0, node_v0, nw, nh, grid_radius, spacing, subset_radius, max_iterations=20,
                        epsilon=1e-3, max_shift=2.0, max_gradient=0.5, max_curvature=0.05, start_gradients=None, start_curvatures=None,
@@ -1382,14 +1374,7 @@ class Context:
         caller's Planes; without them the call allocates all fourteen, downloads them and returns arrays.  record as for
         subset_refine.  Returns (u, v, (ux, uy, vx, vy) or None, (uxx, uxy, uyy, vxx, vxy, vyy) or None, score or None, state or
         None, SubsetRecord or None)."""
-        own_planes = out_u is None and out_v is None
-        if not own_planes and (out_u is None or out_v is None):
-            raise ValueError("subset_refine2 takes both output planes or neither")
-        own_record = record is True
-        if own_record and instances != 1:
-            raise ValueError("a lock-step batch takes the caller's records")
-
-        def group(planes, n, what):
+        def start(planes, n, what):
             if planes is None:
                 return None
             planes = list(planes)
@@ -1397,32 +1382,19 @@ class Context:
                 raise ValueError("subset_refine2 takes %d %s or None" % (n, what))
             return (C.c_void_p * n)(*[q.ptr if q is not None else None for q in planes])
 
-        if own_planes:
-            held = [self.plane(node_u0.pitch // 4, nh) for _ in range(14)]
-        else:
-            held = ([out_u, out_v] + list(out_gradients if out_gradients is not None else (None,) * 4) +
-                    list(out_curvatures if out_curvatures is not None else (None,) * 6) + [out_score, out_state])
+        def issue(held, rec):
             if len(held) != 14:
                 raise ValueError("subset_refine2 takes four gradient planes and six curvature planes")
-        rec = self.subset_records(instances) if own_record else (record or None)
-        try:
             _check(hip_lib().flow2d_subset_refine2_2d(self.handle, f0.ptr, f1.ptr, w, h, f0.pitch, node_u0.ptr, node_v0.ptr,
-                                                      group(start_gradients, 4, "start gradients"),
-                                                      group(start_curvatures, 6, "start curvatures"), nw, nh, node_u0.pitch,
+                                                      start(start_gradients, 4, "start gradients"),
+                                                      start(start_curvatures, 6, "start curvatures"), nw, nh, node_u0.pitch,
                                                       int(grid_radius), int(spacing), int(subset_radius), int(max_iterations),
                                                       float(epsilon), float(max_shift), float(max_gradient), float(max_curvature),
-                                                      held[0].ptr, held[1].ptr, group(held[2:6], 4, "gradients"),
-                                                      group(held[6:12], 6, "curvatures"), held[12].ptr if held[12] is not None else None,
-                                                      held[13].ptr if held[13] is not None else None,
-                                                      rec.ptr if rec is not None else None), "flow2d_subset_refine2_2d")
-            got = [q.download(nw, nh) for q in held] if own_planes else held
-            gradients = tuple(got[2:6]) if got[2] is not None else None
-            curvatures = tuple(got[6:12]) if got[6] is not None else None
-            return got[0], got[1], gradients, curvatures, got[12], got[13], (self.read_subset_record(rec, 1)[0] if own_record else None)
-        finally:
-            for q in (held if own_planes else []) + ([rec] if own_record else []):
-                q.free()
-                self._planes.remove(q)
+                                                      held[0], held[1], (C.c_void_p * 4)(*held[2:6]), (C.c_void_p * 6)(*held[6:12]),
+                                                      held[12], held[13], rec), "flow2d_subset_refine2_2d")
+
+        return self._subset_refine_call("subset_refine2", issue, node_u0, nw, nh, out_u, out_v, [(out_gradients, 4), (out_curvatures, 6)],
+                                        out_score, out_state, record, instances)
 
     def predict_records(self, instances=1):
         """A Plane for `instances` flow2d_predict_record records (device memory)."""
@@ -1794,47 +1766,19 @@ def host_lib():
             L.flow2d_host_correlate_multipass_device.argtypes = [vp, vp, vp, f, f, ip, i, f, f, f, i, i, i, vp, vp, vp, vp, vp, rp, vp, vp]
             L.flow2d_host_correlate_multipass.argtypes = [vp, fp, fp, ip, i, f, f, f, i, i, i, fp, fp, fp, fp, fp, rp, fp, fp, fp]
         if hasattr(L, "flow2d_host_correlate_subset_device"):
-            ip, rp, sr = C.POINTER(C.c_int), C.POINTER(CorrelationPassReport), C.POINTER(SubsetRecord)
-            L.flow2d_host_subset_options_ok.argtypes = [i, i, f, f, f]
-            L.flow2d_host_refine_nodes_device.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, f, f, f, C.POINTER(vp), sr]
-            L.flow2d_host_correlate_subset_device.argtypes = [vp, vp, vp, f, f, ip, i, f, f, f, i, i, i, f, f, f, vp, vp, C.POINTER(vp), rp, sr,
-                                                              vp, vp]
-            L.flow2d_host_correlate_subset.argtypes = [vp, fp, fp, ip, i, f, f, f, i, i, i, f, f, f, fp, fp, C.POINTER(fp), rp, sr, fp, fp, fp]
-        if hasattr(L, "flow2d_host_correlate_subset2_device"):  # the same calls with SubsetOptions::order and max_curvature
-            ip, rp, sr, st = C.POINTER(C.c_int), C.POINTER(CorrelationPassReport), C.POINTER(SubsetRecord), C.POINTER(SequenceStepReport)
-            pvp = C.POINTER(vp)
-            L.flow2d_host_subset2_options_ok.argtypes = [i, i, f, f, f, i, f]
-            L.flow2d_host_refine_nodes2_device.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, f, f, f, i, f, pvp, sr]
-            L.flow2d_host_refine_nodes_from2_device.argtypes = [vp, vp, vp, pvp, i, i, i, i, f, f, f, i, f, pvp, sr]
-            L.flow2d_host_correlate_subset2_device.argtypes = [vp, vp, vp, f, f, ip, i, f, f, f, i, i, i, f, f, f, i, f, vp, vp, pvp, rp, sr, vp, vp]
-            fpp = C.POINTER(fp)
-            L.flow2d_host_correlate_subset2.argtypes = [vp, fp, fp, ip, i, f, f, f, i, i, i, f, f, f, i, f, fp, fp, fpp, rp, sr, fp, fp, fp]
-            L.flow2d_host_correlate_subset2_sequence.argtypes = [vp, fpp, i, ip, i, f, f, f, i, i, i, f, f, f, i, f, i, i, i, f, fpp, rp, st,
-                                                                 fpp, fp]
-            L.flow2d_host_correlate_subset2_sequence_device.argtypes = [vp, pvp, i, f, f, ip, i, f, f, f, i, i, i, f, f, f, i, f, i, i, i, f, pvp,
-                                                                        rp, st, pvp]
-        if hasattr(L, "flow2d_host_correlate_subset_masked_device"):  # the first-order calls with SubsetOptions::mask and min_pixels
-            ip, rp, sr, st = C.POINTER(C.c_int), C.POINTER(CorrelationPassReport), C.POINTER(SubsetRecord), C.POINTER(SequenceStepReport)
+            rp, sr, st, so = C.POINTER(CorrelationPassReport), C.POINTER(SubsetRecord), C.POINTER(SequenceStepReport), C.POINTER(SubsetOptions)
             pvp, fpp = C.POINTER(vp), C.POINTER(fp)
-            L.flow2d_host_subset_mask_options_ok.argtypes = [i, i, f, f, f, i, f, i]
+            passes = [C.POINTER(C.c_int), i, f, f, f, i]  # the schedule, min_score, threshold, epsilon, min_neighbours
+            sequence = [i, i, i, f]  # fill, min_state, predict_neighbours, sequence_max_shift
+            L.flow2d_host_subset_options_ok.argtypes = [so]
             L.flow2d_host_subset_min_pixels.argtypes = [i]
-            L.flow2d_host_refine_nodes_masked_device.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, f, f, f, vp, i, pvp, sr]
-            L.flow2d_host_refine_nodes_from_masked_device.argtypes = [vp, vp, vp, pvp, i, i, i, i, f, f, f, vp, i, pvp, sr]
-            L.flow2d_host_correlate_subset_masked_device.argtypes = [vp, vp, vp, f, f, ip, i, f, f, f, i, i, i, f, f, f, vp, i, vp, vp, pvp, rp, sr,
-                                                                     vp, vp]
-            L.flow2d_host_correlate_subset_masked.argtypes = [vp, fp, fp, ip, i, f, f, f, i, i, i, f, f, f, fp, i, fp, fp, fpp, rp, sr, fp, fp, fp]
-            L.flow2d_host_correlate_subset_masked_sequence_device.argtypes = [vp, pvp, i, f, f, ip, i, f, f, f, i, i, i, f, f, f, vp, i, i, i, i, f,
-                                                                              pvp, rp, st, pvp]
-            L.flow2d_host_correlate_subset_masked_sequence.argtypes = [vp, fpp, i, ip, i, f, f, f, i, i, i, f, f, f, fp, i, i, i, i, f, fpp, rp, st,
-                                                                       fpp, fp]
-        if hasattr(L, "flow2d_host_correlate_subset_sequence_device"):
-            ip, rp, sr, st = C.POINTER(C.c_int), C.POINTER(CorrelationPassReport), C.POINTER(SubsetRecord), C.POINTER(SequenceStepReport)
-            pvp, pfp = C.POINTER(vp), C.POINTER(fp)
-            L.flow2d_host_sequence_options_ok.argtypes = [i, i, i, f]
-            L.flow2d_host_refine_nodes_from_device.argtypes = [vp, vp, vp, pvp, i, i, i, i, f, f, f, pvp, sr]
-            L.flow2d_host_correlate_subset_sequence_device.argtypes = [vp, pvp, i, f, f, ip, i, f, f, f, i, i, i, f, f, f, i, i, i, f, pvp, rp, st,
-                                                                       pvp]
-            L.flow2d_host_correlate_subset_sequence.argtypes = [vp, pfp, i, ip, i, f, f, f, i, i, i, f, f, f, i, i, i, f, pfp, rp, st, pfp, fp]
+            L.flow2d_host_sequence_options_ok.argtypes = sequence
+            L.flow2d_host_refine_nodes_device.argtypes = [vp, vp, vp, vp, vp, i, i, so, pvp, sr]
+            L.flow2d_host_refine_nodes_from_device.argtypes = [vp, vp, vp, pvp, i, i, so, pvp, sr]
+            L.flow2d_host_correlate_subset_device.argtypes = [vp, vp, vp, f, f] + passes + [so, vp, vp, pvp, rp, sr, vp, vp]
+            L.flow2d_host_correlate_subset.argtypes = [vp, fp, fp] + passes + [so, fp, fp, fpp, rp, sr, fp, fp, fp]
+            L.flow2d_host_correlate_subset_sequence_device.argtypes = [vp, pvp, i, f, f] + passes + [so] + sequence + [pvp, rp, st, pvp]
+            L.flow2d_host_correlate_subset_sequence.argtypes = [vp, fpp, i] + passes + [so] + sequence + [fpp, rp, st, fpp, fp]
         if hasattr(L, "flow2d_host_node_strain_device"):
             ds = C.POINTER(DeformationStats)
             L.flow2d_host_strain_options_ok.argtypes = [i, i, i, i, i]
@@ -2389,17 +2333,13 @@ class OpticalFlow:
                           min_pixels=0):
         """OpticalFlow2D::SubsetOptionsOk: whether refine_nodes_device / correlate_subset* accept the options; mask=True: together
         with a mask and min_pixels (a mask with order 2 is refused).  Needs no device."""
-        if mask:
-            return bool(host_lib().flow2d_host_subset_mask_options_ok(int(radius), int(iterations), float(epsilon), float(max_shift),
-                                                                      float(max_gradient), int(order), float(max_curvature), int(min_pixels)))
-        if order == 1 and max_curvature == 0.05:
-            return bool(host_lib().flow2d_host_subset_options_ok(int(radius), int(iterations), float(epsilon), float(max_shift), float(max_gradient)))
-        return bool(host_lib().flow2d_host_subset2_options_ok(int(radius), int(iterations), float(epsilon), float(max_shift), float(max_gradient),
-                                                              int(order), float(max_curvature)))
+        options = SubsetOptions(int(radius), int(iterations), float(epsilon), float(max_shift), float(max_gradient), int(order),
+                                float(max_curvature), int(min_pixels), 1 if mask else None)
+        return bool(host_lib().flow2d_host_subset_options_ok(C.byref(options)))
 
     @staticmethod
     def _takes_mask(mask, min_pixels, order, where):
-        """Whether a call that refines goes to its masked entry (OpticalFlow2D::SubsetOptions::mask and min_pixels): mask -- the
+        """Whether a call that refines has a mask (OpticalFlow2D::SubsetOptions::mask and min_pixels): mask -- the
         region of interest in frame 0's coordinates, values of 0.5 and more (and NaN) meaning "not the specimen"; a device plane of
         the container's size for a *_device method, else an image of the frames' size --, min_pixels -- the fewest usable pixels a
         node may have, 0 = subset_min_pixels(radius).  A masked node has the state SUBSET_MASKED and NaN in its six planes, and the
@@ -2418,23 +2358,37 @@ class OpticalFlow:
             raise ValueError("the subset mask is an image of the object's size")
         return image
 
+    def _subset_options(self, where, radius, iterations, epsilon, max_shift, max_gradient, order, max_curvature, mask, min_pixels,
+                        image=False):
+        """The SubsetOptions record of a call that refines, by the rules of _takes_mask.  image: the mask is an image and not a
+        device plane; the record then holds the float32 array it points into, which lives as long as the record."""
+        held = None
+        if self._takes_mask(mask, min_pixels, order, where) and image:
+            held = self._mask_image(mask)
+            mask = held.ctypes.data
+        options = SubsetOptions(int(radius), int(iterations), float(epsilon), float(max_shift), float(max_gradient), int(order),
+                                float(max_curvature), int(min_pixels), mask)
+        options.held = held
+        return options
+
     @staticmethod
-    def _subset2_planes(dev_out):
-        """The fourteen device planes of SUBSET2_PLANES from a dict name -> address (absent or None: not wanted)."""
+    def _subset_planes(dev_out, order=1):
+        """The fourteen device planes of SUBSET2_PLANES from a dict name -> address (absent or None: not wanted) by the names of
+        SUBSET_PLANES or, with order=2, of SUBSET2_PLANES."""
         dev_out = dev_out or {}
-        unknown = set(dev_out) - set(OpticalFlow.SUBSET2_PLANES)
+        names = OpticalFlow.SUBSET_PLANES if order == 1 else OpticalFlow.SUBSET2_PLANES
+        unknown = set(dev_out) - set(names)
         if unknown:
-            raise ValueError("unknown subset planes %s (of %s)" % (sorted(unknown), ", ".join(OpticalFlow.SUBSET2_PLANES)))
+            raise ValueError("unknown subset planes %s (of %s)" % (sorted(unknown), ", ".join(names)))
         return (C.c_void_p * 14)(*[dev_out.get(name) for name in OpticalFlow.SUBSET2_PLANES])
 
     @staticmethod
-    def _subset_planes(dev_out):
-        """The eight device planes of SUBSET_PLANES from a dict name -> address (absent or None: not wanted)."""
-        dev_out = dev_out or {}
-        unknown = set(dev_out) - set(OpticalFlow.SUBSET_PLANES)
-        if unknown:
-            raise ValueError("unknown subset planes %s (of %s)" % (sorted(unknown), ", ".join(OpticalFlow.SUBSET_PLANES)))
-        return (C.c_void_p * 8)(*[dev_out.get(name) for name in OpticalFlow.SUBSET_PLANES])
+    def _node_arrays(nodes, per):
+        """The fourteen array slots per step of a host-image call from its `per` arrays per step (the other slots: not wanted)."""
+        slots = (C.POINTER(C.c_float) * (14 * (len(nodes) // per)))()
+        for k, q in enumerate(nodes):
+            slots[14 * (k // per) + k % per] = _fptr(q)
+        return slots
 
     def refine_nodes_device(self, dev_frame_0, dev_frame_1, dev_node_u0, dev_node_v0, grid_radius, spacing, radius, iterations=20,
                             epsilon=1e-3, max_shift=2.0, max_gradient=0.5, dev_out=None, record=True, order=1, max_curvature=0.05, mask=None,
@@ -2446,25 +2400,11 @@ class OpticalFlow:
         radius from 2, a curvature beyond max_curvature strays; dev_out by the names of SUBSET2_PLANES, the six curvatures all or
         none.  order=1 is the call it always was.  mask (a device plane) / min_pixels: see _takes_mask."""
         rec = SubsetRecord()
-        if self._takes_mask(mask, min_pixels, order, "OpticalFlow2D::RefineNodesDevice"):
-            rc = host_lib().flow2d_host_refine_nodes_masked_device(self.handle, dev_frame_0, dev_frame_1, dev_node_u0, dev_node_v0,
-                                                                   int(grid_radius), int(spacing), int(radius), int(iterations), float(epsilon),
-                                                                   float(max_shift), float(max_gradient), mask, int(min_pixels),
-                                                                   self._subset_planes(dev_out), C.byref(rec) if record else None)
-            if rc:
-                raise Flow2DError(rc, "OpticalFlow2D::RefineNodesDevice")
-            return rec if record else None
-        if order != 1:
-            rc = host_lib().flow2d_host_refine_nodes2_device(self.handle, dev_frame_0, dev_frame_1, dev_node_u0, dev_node_v0, int(grid_radius),
-                                                             int(spacing), int(radius), int(iterations), float(epsilon), float(max_shift),
-                                                             float(max_gradient), int(order), float(max_curvature),
-                                                             self._subset2_planes(dev_out), C.byref(rec) if record else None)
-            if rc:
-                raise Flow2DError(rc, "OpticalFlow2D::RefineNodesDevice")
-            return rec if record else None
+        options = self._subset_options("OpticalFlow2D::RefineNodesDevice", radius, iterations, epsilon, max_shift, max_gradient, order,
+                                       max_curvature, mask, min_pixels)
         rc = host_lib().flow2d_host_refine_nodes_device(self.handle, dev_frame_0, dev_frame_1, dev_node_u0, dev_node_v0, int(grid_radius),
-                                                        int(spacing), int(radius), int(iterations), float(epsilon), float(max_shift),
-                                                        float(max_gradient), self._subset_planes(dev_out), C.byref(rec) if record else None)
+                                                        int(spacing), C.byref(options), self._subset_planes(dev_out, order),
+                                                        C.byref(rec) if record else None)
         if rc:
             raise Flow2DError(rc, "OpticalFlow2D::RefineNodesDevice")
         return rec if record else None
@@ -2483,41 +2423,20 @@ class OpticalFlow:
         if not 1 <= n <= CORRELATION_MAX_PASSES:
             raise Flow2DError(1, "OpticalFlow2D::CorrelateSubset")
         nw, nh = correlation_grid(self.width, self.height, passes[-1][0], passes[-1][2])
-        nodes = [np.empty((nh, nw), np.float32) for _ in range(8 if order == 1 else 14)]
+        names = self.SUBSET_PLANES if order == 1 else self.SUBSET2_PLANES
+        nodes = [np.empty((nh, nw), np.float32) for _ in names]
         uv = [np.empty_like(f0) for _ in range(2)] if flow else [None, None]
         pred = [np.ascontiguousarray(q, np.float32) for q in predictor] if predictor is not None else [None, None]
         reports, rec, lo_scale = (CorrelationPassReport * n)(), SubsetRecord(), (C.c_float * 2)()
-        if self._takes_mask(mask, min_pixels, order, "OpticalFlow2D::CorrelateSubset"):
-            image = self._mask_image(mask)
-            rc = host_lib().flow2d_host_correlate_subset_masked(self.handle, _fptr(f0), _fptr(f1), arr, n, float(min_score), float(threshold),
-                                                                float(validate_epsilon), int(min_neighbours), int(radius), int(iterations),
-                                                                float(epsilon), float(max_shift), float(max_gradient), _fptr(image),
-                                                                int(min_pixels), _opt_fptr(pred[0]), _opt_fptr(pred[1]),
-                                                                (C.POINTER(C.c_float) * 8)(*[_fptr(q) for q in nodes]), reports, C.byref(rec),
-                                                                _opt_fptr(uv[0]), _opt_fptr(uv[1]), lo_scale)
-            if rc:
-                raise Flow2DError(rc, "OpticalFlow2D::CorrelateSubset")
-            out = (dict(zip(self.SUBSET_PLANES, nodes)), list(reports), rec, (lo_scale[0], lo_scale[1]))
-            return out + (tuple(uv),) if flow else out
-        if order != 1:
-            rc = host_lib().flow2d_host_correlate_subset2(self.handle, _fptr(f0), _fptr(f1), arr, n, float(min_score), float(threshold),
-                                                          float(validate_epsilon), int(min_neighbours), int(radius), int(iterations),
-                                                          float(epsilon), float(max_shift), float(max_gradient), int(order),
-                                                          float(max_curvature), _opt_fptr(pred[0]), _opt_fptr(pred[1]),
-                                                          (C.POINTER(C.c_float) * 14)(*[_fptr(q) for q in nodes]), reports, C.byref(rec),
-                                                          _opt_fptr(uv[0]), _opt_fptr(uv[1]), lo_scale)
-            if rc:
-                raise Flow2DError(rc, "OpticalFlow2D::CorrelateSubset")
-            out = (dict(zip(self.SUBSET2_PLANES, nodes)), list(reports), rec, (lo_scale[0], lo_scale[1]))
-            return out + (tuple(uv),) if flow else out
+        options = self._subset_options("OpticalFlow2D::CorrelateSubset", radius, iterations, epsilon, max_shift, max_gradient, order,
+                                       max_curvature, mask, min_pixels, image=True)
         rc = host_lib().flow2d_host_correlate_subset(self.handle, _fptr(f0), _fptr(f1), arr, n, float(min_score), float(threshold),
-                                                     float(validate_epsilon), int(min_neighbours), int(radius), int(iterations),
-                                                     float(epsilon), float(max_shift), float(max_gradient), _opt_fptr(pred[0]),
-                                                     _opt_fptr(pred[1]), (C.POINTER(C.c_float) * 8)(*[_fptr(q) for q in nodes]), reports,
-                                                     C.byref(rec), _opt_fptr(uv[0]), _opt_fptr(uv[1]), lo_scale)
+                                                     float(validate_epsilon), int(min_neighbours), C.byref(options), _opt_fptr(pred[0]),
+                                                     _opt_fptr(pred[1]), self._node_arrays(nodes, len(names)), reports, C.byref(rec),
+                                                     _opt_fptr(uv[0]), _opt_fptr(uv[1]), lo_scale)
         if rc:
             raise Flow2DError(rc, "OpticalFlow2D::CorrelateSubset")
-        out = (dict(zip(self.SUBSET_PLANES, nodes)), list(reports), rec, (lo_scale[0], lo_scale[1]))
+        out = (dict(zip(names, nodes)), list(reports), rec, (lo_scale[0], lo_scale[1]))
         return out + (tuple(uv),) if flow else out
 
     def correlate_subset_device(self, dev_frame_0, dev_frame_1, lo, scale, passes, radius, iterations=20, epsilon=1e-3, max_shift=2.0,
@@ -2529,28 +2448,11 @@ class OpticalFlow:
         arr, n = self._passes(passes)
         reports, rec = (CorrelationPassReport * max(n, 1))(), SubsetRecord()
         pr, fl = dev_predictor or (None, None), dev_flow or (None, None)
-        if self._takes_mask(mask, min_pixels, order, "OpticalFlow2D::CorrelateSubsetDevice"):
-            rc = host_lib().flow2d_host_correlate_subset_masked_device(self.handle, dev_frame_0, dev_frame_1, float(lo), float(scale), arr, n,
-                                                                       float(min_score), float(threshold), float(validate_epsilon),
-                                                                       int(min_neighbours), int(radius), int(iterations), float(epsilon),
-                                                                       float(max_shift), float(max_gradient), mask, int(min_pixels), pr[0],
-                                                                       pr[1], self._subset_planes(dev_out), reports, C.byref(rec), fl[0], fl[1])
-            if rc:
-                raise Flow2DError(rc, "OpticalFlow2D::CorrelateSubsetDevice")
-            return list(reports)[:n], rec
-        if order != 1:
-            rc = host_lib().flow2d_host_correlate_subset2_device(self.handle, dev_frame_0, dev_frame_1, float(lo), float(scale), arr, n,
-                                                                 float(min_score), float(threshold), float(validate_epsilon),
-                                                                 int(min_neighbours), int(radius), int(iterations), float(epsilon),
-                                                                 float(max_shift), float(max_gradient), int(order), float(max_curvature),
-                                                                 pr[0], pr[1], self._subset2_planes(dev_out), reports, C.byref(rec), fl[0], fl[1])
-            if rc:
-                raise Flow2DError(rc, "OpticalFlow2D::CorrelateSubsetDevice")
-            return list(reports)[:n], rec
+        options = self._subset_options("OpticalFlow2D::CorrelateSubsetDevice", radius, iterations, epsilon, max_shift, max_gradient, order,
+                                       max_curvature, mask, min_pixels)
         rc = host_lib().flow2d_host_correlate_subset_device(self.handle, dev_frame_0, dev_frame_1, float(lo), float(scale), arr, n,
                                                             float(min_score), float(threshold), float(validate_epsilon), int(min_neighbours),
-                                                            int(radius), int(iterations), float(epsilon), float(max_shift),
-                                                            float(max_gradient), pr[0], pr[1], self._subset_planes(dev_out), reports,
+                                                            C.byref(options), pr[0], pr[1], self._subset_planes(dev_out, order), reports,
                                                             C.byref(rec), fl[0], fl[1])
         if rc:
             raise Flow2DError(rc, "OpticalFlow2D::CorrelateSubsetDevice")
@@ -2572,28 +2474,11 @@ class OpticalFlow:
         if set(dev_start) != set(names) or not all(dev_start[n] for n in names):
             raise ValueError("refine_nodes_from_device takes the six start planes %s" % ", ".join(names))
         rec = SubsetRecord()
-        if self._takes_mask(mask, min_pixels, order, "OpticalFlow2D::RefineNodesFromDevice"):
-            rc = host_lib().flow2d_host_refine_nodes_from_masked_device(self.handle, dev_frame_0, dev_frame_1,
-                                                                        (C.c_void_p * 6)(*[dev_start[n] for n in names]), int(grid_radius),
-                                                                        int(spacing), int(radius), int(iterations), float(epsilon),
-                                                                        float(max_shift), float(max_gradient), mask, int(min_pixels),
-                                                                        self._subset_planes(dev_out), C.byref(rec) if record else None)
-            if rc:
-                raise Flow2DError(rc, "OpticalFlow2D::RefineNodesFromDevice")
-            return rec if record else None
-        if order != 1:
-            rc = host_lib().flow2d_host_refine_nodes_from2_device(self.handle, dev_frame_0, dev_frame_1,
-                                                                  (C.c_void_p * 6)(*[dev_start[n] for n in names]), int(grid_radius),
-                                                                  int(spacing), int(radius), int(iterations), float(epsilon), float(max_shift),
-                                                                  float(max_gradient), int(order), float(max_curvature),
-                                                                  self._subset2_planes(dev_out), C.byref(rec) if record else None)
-            if rc:
-                raise Flow2DError(rc, "OpticalFlow2D::RefineNodesFromDevice")
-            return rec if record else None
+        options = self._subset_options("OpticalFlow2D::RefineNodesFromDevice", radius, iterations, epsilon, max_shift, max_gradient, order,
+                                       max_curvature, mask, min_pixels)
         rc = host_lib().flow2d_host_refine_nodes_from_device(self.handle, dev_frame_0, dev_frame_1, (C.c_void_p * 6)(*[dev_start[n] for n in names]),
-                                                             int(grid_radius), int(spacing), int(radius), int(iterations), float(epsilon),
-                                                             float(max_shift), float(max_gradient), self._subset_planes(dev_out),
-                                                             C.byref(rec) if record else None)
+                                                             int(grid_radius), int(spacing), C.byref(options),
+                                                             self._subset_planes(dev_out, order), C.byref(rec) if record else None)
         if rc:
             raise Flow2DError(rc, "OpticalFlow2D::RefineNodesFromDevice")
         return rec if record else None
@@ -2619,50 +2504,22 @@ class OpticalFlow:
             raise Flow2DError(1, "OpticalFlow2D::CorrelateSubsetSequence")
         steps = len(images) - 1
         nw, nh = correlation_grid(self.width, self.height, passes[-1][0], passes[-1][2])
-        per = 8 if order == 1 else 14
+        names = self.SUBSET_PLANES if order == 1 else self.SUBSET2_PLANES
+        per = len(names)
         nodes = [np.empty((nh, nw), np.float32) for _ in range(per * steps)]
         uv = [np.empty_like(images[0]) for _ in range(2 * steps)] if flow else None
         fpp = C.POINTER(C.c_float)
         reports, reps, lo_scale = (CorrelationPassReport * n)(), (SequenceStepReport * steps)(), (C.c_float * 2)()
-        if self._takes_mask(mask, min_pixels, order, "OpticalFlow2D::CorrelateSubsetSequence"):
-            image = self._mask_image(mask)
-            rc = host_lib().flow2d_host_correlate_subset_masked_sequence(self.handle, (fpp * len(images))(*[_fptr(q) for q in images]),
-                                                                         len(images), arr, n, float(min_score), float(threshold),
-                                                                         float(validate_epsilon), int(min_neighbours), int(radius),
-                                                                         int(iterations), float(epsilon), float(max_shift),
-                                                                         float(max_gradient), _fptr(image), int(min_pixels), int(fill),
-                                                                         int(min_state), int(predict_neighbours), float(sequence_max_shift),
-                                                                         (fpp * (8 * steps))(*[_fptr(q) for q in nodes]), reports, reps,
-                                                                         (fpp * (2 * steps))(*[_fptr(q) for q in uv]) if flow else None,
-                                                                         lo_scale)
-            if rc:
-                raise Flow2DError(rc, "OpticalFlow2D::CorrelateSubsetSequence")
-            per_step = [dict(zip(self.SUBSET_PLANES, nodes[8 * k:8 * k + 8])) for k in range(steps)]
-            out = (per_step, list(reports), list(reps), (lo_scale[0], lo_scale[1]))
-            return out + ([(uv[2 * k], uv[2 * k + 1]) for k in range(steps)],) if flow else out
-        if order != 1:
-            rc = host_lib().flow2d_host_correlate_subset2_sequence(self.handle, (fpp * len(images))(*[_fptr(q) for q in images]), len(images),
-                                                                   arr, n, float(min_score), float(threshold), float(validate_epsilon),
-                                                                   int(min_neighbours), int(radius), int(iterations), float(epsilon),
-                                                                   float(max_shift), float(max_gradient), int(order), float(max_curvature),
-                                                                   int(fill), int(min_state), int(predict_neighbours), float(sequence_max_shift),
-                                                                   (fpp * (per * steps))(*[_fptr(q) for q in nodes]), reports, reps,
-                                                                   (fpp * (2 * steps))(*[_fptr(q) for q in uv]) if flow else None, lo_scale)
-            if rc:
-                raise Flow2DError(rc, "OpticalFlow2D::CorrelateSubsetSequence")
-            per_step = [dict(zip(self.SUBSET2_PLANES, nodes[per * k:per * k + per])) for k in range(steps)]
-            out = (per_step, list(reports), list(reps), (lo_scale[0], lo_scale[1]))
-            return out + ([(uv[2 * k], uv[2 * k + 1]) for k in range(steps)],) if flow else out
+        options = self._subset_options("OpticalFlow2D::CorrelateSubsetSequence", radius, iterations, epsilon, max_shift, max_gradient, order,
+                                       max_curvature, mask, min_pixels, image=True)
         rc = host_lib().flow2d_host_correlate_subset_sequence(self.handle, (fpp * len(images))(*[_fptr(q) for q in images]), len(images), arr, n,
                                                               float(min_score), float(threshold), float(validate_epsilon), int(min_neighbours),
-                                                              int(radius), int(iterations), float(epsilon), float(max_shift),
-                                                              float(max_gradient), int(fill), int(min_state), int(predict_neighbours),
-                                                              float(sequence_max_shift), (fpp * (8 * steps))(*[_fptr(q) for q in nodes]),
-                                                              reports, reps, (fpp * (2 * steps))(*[_fptr(q) for q in uv]) if flow else None,
-                                                              lo_scale)
+                                                              C.byref(options), int(fill), int(min_state), int(predict_neighbours),
+                                                              float(sequence_max_shift), self._node_arrays(nodes, per), reports, reps,
+                                                              (fpp * (2 * steps))(*[_fptr(q) for q in uv]) if flow else None, lo_scale)
         if rc:
             raise Flow2DError(rc, "OpticalFlow2D::CorrelateSubsetSequence")
-        per_step = [dict(zip(self.SUBSET_PLANES, nodes[8 * k:8 * k + 8])) for k in range(steps)]
+        per_step = [dict(zip(names, nodes[per * k:per * k + per])) for k in range(steps)]
         out = (per_step, list(reports), list(reps), (lo_scale[0], lo_scale[1]))
         return out + ([(uv[2 * k], uv[2 * k + 1]) for k in range(steps)],) if flow else out
 
@@ -2682,7 +2539,7 @@ class OpticalFlow:
             raise ValueError("correlate_subset_sequence_device takes two or more frames and one set of planes per step")
         planes = []
         for step in dev_out:
-            planes += list(self._subset_planes(step) if order == 1 else self._subset2_planes(step))
+            planes += list(self._subset_planes(step, order))
         flows = None
         if dev_flows is not None:
             flat = []
@@ -2690,39 +2547,17 @@ class OpticalFlow:
                 flat += list(pair) if pair is not None else [None, None]
             flows = (C.c_void_p * (2 * steps))(*flat)
         reports, reps = (CorrelationPassReport * max(n, 1))(), (SequenceStepReport * steps)()
-        if self._takes_mask(mask, min_pixels, order, "OpticalFlow2D::CorrelateSubsetSequenceDevice"):
-            rc = host_lib().flow2d_host_correlate_subset_masked_sequence_device(self.handle, (C.c_void_p * len(dev_frames))(*dev_frames),
-                                                                                len(dev_frames), float(lo), float(scale), arr, n,
-                                                                                float(min_score), float(threshold), float(validate_epsilon),
-                                                                                int(min_neighbours), int(radius), int(iterations),
-                                                                                float(epsilon), float(max_shift), float(max_gradient), mask,
-                                                                                int(min_pixels), int(fill), int(min_state),
-                                                                                int(predict_neighbours), float(sequence_max_shift),
-                                                                                (C.c_void_p * (8 * steps))(*planes), reports, reps, flows)
-            if rc:
-                raise Flow2DError(rc, "OpticalFlow2D::CorrelateSubsetSequenceDevice")
-            return list(reports)[:n], list(reps)
-        if order != 1:
-            rc = host_lib().flow2d_host_correlate_subset2_sequence_device(self.handle, (C.c_void_p * len(dev_frames))(*dev_frames),
-                                                                          len(dev_frames), float(lo), float(scale), arr, n, float(min_score),
-                                                                          float(threshold), float(validate_epsilon), int(min_neighbours),
-                                                                          int(radius), int(iterations), float(epsilon), float(max_shift),
-                                                                          float(max_gradient), int(order), float(max_curvature), int(fill),
-                                                                          int(min_state), int(predict_neighbours), float(sequence_max_shift),
-                                                                          (C.c_void_p * (14 * steps))(*planes), reports, reps, flows)
-            if rc:
-                raise Flow2DError(rc, "OpticalFlow2D::CorrelateSubsetSequenceDevice")
-            return list(reports)[:n], list(reps)
+        options = self._subset_options("OpticalFlow2D::CorrelateSubsetSequenceDevice", radius, iterations, epsilon, max_shift, max_gradient,
+                                       order, max_curvature, mask, min_pixels)
         rc = host_lib().flow2d_host_correlate_subset_sequence_device(self.handle, (C.c_void_p * len(dev_frames))(*dev_frames), len(dev_frames),
                                                                      float(lo), float(scale), arr, n, float(min_score), float(threshold),
-                                                                     float(validate_epsilon), int(min_neighbours), int(radius),
-                                                                     int(iterations), float(epsilon), float(max_shift), float(max_gradient),
-                                                                     int(fill), int(min_state), int(predict_neighbours),
-                                                                     float(sequence_max_shift), (C.c_void_p * (8 * steps))(*planes), reports,
-                                                                     reps, flows)
+                                                                     float(validate_epsilon), int(min_neighbours), C.byref(options), int(fill),
+                                                                     int(min_state), int(predict_neighbours), float(sequence_max_shift),
+                                                                     (C.c_void_p * (14 * steps))(*planes), reports, reps, flows)
         if rc:
             raise Flow2DError(rc, "OpticalFlow2D::CorrelateSubsetSequenceDevice")
         return list(reports)[:n], list(reps)
+
 
     NODE_PLANES = ("u", "v", "ux", "uy", "vx", "vy", "state")  # what node_strain* read of a step's SUBSET_PLANES
 

@@ -77,6 +77,26 @@ hipError_t clear_records(const flow2d_context* ctx, Record* record)
     return record ? hipMemsetAsync(record, 0, ctx->batch_count * sizeof(Record), ctx->stream) : hipSuccess;
 }
 
+// What the subset refinement's entries (subset_refine.hip, subset_refine2.hip, subset_refine_masked.hip) check alike, in their
+// order: the subset's radius from `min_radius`, the iterations, the bounds (finite and positive; the epsilon may be 0), the grid
+// inside the frame as flow2d_correlation_grid lays it -- it may be smaller than the full one --, the record's alignment and
+// the node count.  FLOW2D_ERR_UNSUPPORTED is the last of them: an entry hands on FLOW2D_ERR_INVALID_ARGUMENT at once and
+// anything else behind the plane checks of its own, which all come before the node count.
+inline int subset_refine_args_status(size_t width, size_t height, size_t nw, size_t nh, int grid_radius, int spacing, int min_radius,
+                                     int subset_radius, int max_iterations, float epsilon, std::initializer_list<float> bounds,
+                                     const flow2d_subset_record* record)
+{
+    if (subset_radius < min_radius || subset_radius > FLOW2D_SUBSET_MAX_RADIUS || max_iterations < 1 ||
+        max_iterations > FLOW2D_SUBSET_MAX_ITERATIONS || !(std::isfinite(epsilon) && epsilon >= 0.f))
+        return FLOW2D_ERR_INVALID_ARGUMENT;
+    for (const float bound : bounds)
+        if (!(std::isfinite(bound) && bound > 0.f)) return FLOW2D_ERR_INVALID_ARGUMENT;
+    if (!correlation_grid_ok(width, height, grid_radius, spacing) || nw > correlation_nodes(width, grid_radius, spacing) ||
+        nh > correlation_nodes(height, grid_radius, spacing) || !record_aligned(record))
+        return FLOW2D_ERR_INVALID_ARGUMENT;
+    return node_count_ok(nw, nh) ? FLOW2D_OK : FLOW2D_ERR_UNSUPPORTED;
+}
+
 // plane_args_ok for every plane of one shape: the required ones, and the optional ones that are there.
 inline bool planes_ok(std::initializer_list<const void*> required, std::initializer_list<const void*> optional, size_t w, size_t h,
                       size_t pitch_bytes)

@@ -362,11 +362,9 @@ int subset_refine_entry(flow2d_context* ctx, const float* frame_0, const float* 
     if (ctx == nullptr) return FLOW2D_ERR_INVALID_ARGUMENT;
     // (every check that needs no context field comes first: they hold without a device)
     if (!flow2d::planes_ok({frame_0, frame_1}, {}, width, height, pitch_bytes)) return FLOW2D_ERR_INVALID_ARGUMENT;
-    if (subset_radius < 1 || subset_radius > FLOW2D_SUBSET_MAX_RADIUS || max_iterations < 1 || max_iterations > FLOW2D_SUBSET_MAX_ITERATIONS)
-        return FLOW2D_ERR_INVALID_ARGUMENT;
-    if (!(std::isfinite(epsilon) && epsilon >= 0.f) || !(std::isfinite(max_shift) && max_shift > 0.f) ||
-        !(std::isfinite(max_gradient) && max_gradient > 0.f))
-        return FLOW2D_ERR_INVALID_ARGUMENT;
+    const int shared = flow2d::subset_refine_args_status(width, height, nw, nh, grid_radius, spacing, 1, subset_radius, max_iterations,
+                                                         epsilon, {max_shift, max_gradient}, record);
+    if (shared == FLOW2D_ERR_INVALID_ARGUMENT) return shared;
     const bool gradients = out_ux != nullptr;
     if ((out_uy != nullptr) != gradients || (out_vx != nullptr) != gradients || (out_vy != nullptr) != gradients)
         return FLOW2D_ERR_INVALID_ARGUMENT;
@@ -378,12 +376,7 @@ int subset_refine_entry(flow2d_context* ctx, const float* frame_0, const float* 
                            {out_ux, out_uy, out_vx, out_vy, out_score, out_state, start[0], start[1], start[2], start[3]}, nw, nh,
                            node_pitch_bytes))
         return FLOW2D_ERR_INVALID_ARGUMENT;
-    // the grid lies inside the frame, as flow2d_correlation_grid lays it; it may be smaller than the full one
-    if (!flow2d::correlation_grid_ok(width, height, grid_radius, spacing) ||
-        nw > flow2d::correlation_nodes(width, grid_radius, spacing) || nh > flow2d::correlation_nodes(height, grid_radius, spacing))
-        return FLOW2D_ERR_INVALID_ARGUMENT;
-    if (!flow2d::record_aligned(record)) return FLOW2D_ERR_INVALID_ARGUMENT;
-    if (!flow2d::node_count_ok(nw, nh)) return FLOW2D_ERR_UNSUPPORTED;
+    if (shared != FLOW2D_OK) return shared;  // (the node count)
     // the kernel reads frames and nodes while other waves write: no written byte range may meet a read one or another written one
     auto aliased = [&](size_t frame_span, size_t node_span, size_t instances) {
         const flow2d::ByteRange written[] = {{out_u, node_span},  {out_v, node_span},  {out_ux, node_span},

@@ -446,12 +446,9 @@ extern "C" int flow2d_subset_refine2_2d(flow2d_context* ctx, const float* frame_
     if (ctx == nullptr) return FLOW2D_ERR_INVALID_ARGUMENT;
     // (every check that needs no context field comes first: they hold without a device)
     if (!flow2d::planes_ok({frame_0, frame_1}, {}, width, height, pitch_bytes)) return FLOW2D_ERR_INVALID_ARGUMENT;
-    if (subset_radius < FLOW2D_SUBSET2_MIN_RADIUS || subset_radius > FLOW2D_SUBSET_MAX_RADIUS || max_iterations < 1 ||
-        max_iterations > FLOW2D_SUBSET_MAX_ITERATIONS)
-        return FLOW2D_ERR_INVALID_ARGUMENT;
-    if (!(std::isfinite(epsilon) && epsilon >= 0.f) || !(std::isfinite(max_shift) && max_shift > 0.f) ||
-        !(std::isfinite(max_gradient) && max_gradient > 0.f) || !(std::isfinite(max_curvature) && max_curvature > 0.f))
-        return FLOW2D_ERR_INVALID_ARGUMENT;
+    const int shared = flow2d::subset_refine_args_status(width, height, nw, nh, grid_radius, spacing, FLOW2D_SUBSET2_MIN_RADIUS, subset_radius,
+                                                         max_iterations, epsilon, {max_shift, max_gradient, max_curvature}, record);
+    if (shared == FLOW2D_ERR_INVALID_ARGUMENT) return shared;
     const int gradients = all_or_none(out_gradients, 4), curvatures = all_or_none(out_curvatures, 6);
     const int started = all_or_none(start_gradients, 4), curved = all_or_none(start_curvatures, 6);
     if (gradients < 0 || curvatures < 0 || started < 0 || curved < 0 || (curved == 1 && started == 0)) return FLOW2D_ERR_INVALID_ARGUMENT;
@@ -472,12 +469,7 @@ extern "C" int flow2d_subset_refine2_2d(flow2d_context* ctx, const float* frame_
         return FLOW2D_ERR_INVALID_ARGUMENT;
     for (int i = 0; i < 12; ++i)
         if (!flow2d::planes_ok({}, {start[i], out[i]}, nw, nh, node_pitch_bytes)) return FLOW2D_ERR_INVALID_ARGUMENT;
-    // the grid lies inside the frame, as flow2d_correlation_grid lays it; it may be smaller than the full one
-    if (!flow2d::correlation_grid_ok(width, height, grid_radius, spacing) ||
-        nw > flow2d::correlation_nodes(width, grid_radius, spacing) || nh > flow2d::correlation_nodes(height, grid_radius, spacing))
-        return FLOW2D_ERR_INVALID_ARGUMENT;
-    if (!flow2d::record_aligned(record)) return FLOW2D_ERR_INVALID_ARGUMENT;
-    if (!flow2d::node_count_ok(nw, nh)) return FLOW2D_ERR_UNSUPPORTED;
+    if (shared != FLOW2D_OK) return shared;  // (the node count)
     // the kernel reads frames and nodes while other waves write: no written byte range may meet a read one or another written one
     auto aliased = [&](size_t frame_span, size_t node_span, size_t instances) {
         flow2d::ByteRange written[15], read[14];

@@ -725,65 +725,69 @@ HOST_API int flow2d_host_correlate_multipass(flow2d_host_flow* h, const float* f
 }
 
 // ---- subset refinement of correlation nodes -----------------------------------------------------------------------------------
+// Every entry that refines takes OpticalFlow2D::SubsetOptions as one record (null: refused) and its outputs as the fourteen slots
+// of OpticalFlow2D::SubsetPlanes -- u, v, ux, uy, vx, vy, score, state, then uxx, uxy, uyy, vxx, vxy, vyy --, per step in the
+// sequence forms.  The six curvatures go with order 2: at order 1 a slot of theirs that is set is refused, and the host-image
+// forms allocate and copy the eight images only.  A new field of SubsetOptions is a new field of the record, not a new entry.
+struct flow2d_host_subset_options {
+    int radius, iterations;
+    float epsilon, max_shift, max_gradient;
+    int order;  // 1 or 2
+    float max_curvature;
+    int min_pixels;    // 0: the default of the radius
+    const void* mask;  // null: none.  *_device entries: a device plane of the container's size; host-image entries: a tight host
+                       // image of the frames' size; flow2d_host_subset_options_ok: any non-null value means "with a mask"
+};
+
 namespace {
-OpticalFlow2D::SubsetOptions subset_options(int radius, int iterations, float epsilon, float max_shift, float max_gradient)
+constexpr int kSubsetSlots = 14;
+
+// (the mask of a host-image entry stays its host address here: the mark SubsetOptionsOk looks at -- CorrelateSubset* take the
+// image itself and do not look at the field)
+OpticalFlow2D::SubsetOptions subset_options(const flow2d_host_subset_options& record)
 {
     OpticalFlow2D::SubsetOptions o;
-    o.radius = radius;
-    o.iterations = iterations;
-    o.epsilon = epsilon;
-    o.max_shift = max_shift;
-    o.max_gradient = max_gradient;
+    o.radius = record.radius;
+    o.iterations = record.iterations;
+    o.epsilon = record.epsilon;
+    o.max_shift = record.max_shift;
+    o.max_gradient = record.max_gradient;
+    o.order = record.order;
+    o.max_curvature = record.max_curvature;
+    o.mask = dp(const_cast<void*>(record.mask));
+    o.min_pixels = record.min_pixels;
     return o;
 }
-OpticalFlow2D::SubsetOptions subset_options(int radius, int iterations, float epsilon, float max_shift, float max_gradient, int order,
-                                            float max_curvature)
-{
-    OpticalFlow2D::SubsetOptions o = subset_options(radius, iterations, epsilon, max_shift, max_gradient);
-    o.order = order;
-    o.max_curvature = max_curvature;
-    return o;
-}
-// eight device planes -- u, v, ux, uy, vx, vy, score, state -- each of which may be null, as may the array
+
+// fourteen device planes, each of which may be null, as may the array
 OpticalFlow2D::SubsetPlanes subset_planes(void* const* p)
 {
     OpticalFlow2D::SubsetPlanes o;
-    if (p) o = {dp(p[0]), dp(p[1]), dp(p[2]), dp(p[3]), dp(p[4]), dp(p[5]), dp(p[6]), dp(p[7])};
-    return o;
-}
-// fourteen: those eight, then uxx, uxy, uyy, vxx, vxy, vyy
-constexpr int kSubset2Planes = 14;
-OpticalFlow2D::SubsetPlanes subset2_planes(void* const* p)
-{
-    OpticalFlow2D::SubsetPlanes o;
     if (p)
-        o = {dp(p[0]), dp(p[1]), dp(p[2]),  dp(p[3]),  dp(p[4]),  dp(p[5]),  dp(p[6]),
+        o = {dp(p[0]), dp(p[1]), dp(p[2]), dp(p[3]),  dp(p[4]),  dp(p[5]),  dp(p[6]),
              dp(p[7]), dp(p[8]), dp(p[9]), dp(p[10]), dp(p[11]), dp(p[12]), dp(p[13])};
     return o;
 }
-}  // namespace
 
-namespace {
-// SubsetOptions::mask and min_pixels beside the first-order options: what the *_masked entries below pass on.  has_mask_image: a
-// host-image call, whose mask travels as an image; the options then only carry the mark the checks look at.
-OpticalFlow2D::SubsetOptions masked_options(int radius, int iterations, float epsilon, float max_shift, float max_gradient, void* dev_mask,
-                                            bool has_mask_image, int min_pixels)
+// the node images of a step: what the host-image forms of OpticalFlow2D take per step
+int node_images(const OpticalFlow2D::SubsetOptions& subset) { return subset.order == 2 ? kSubsetSlots : 8; }
+
+// OpticalFlow2D::SubsetOptionsOk, and no curvature slot of the `steps` sets of fourteen (null: none) set at order 1
+template <typename Pointer>
+bool subset_accepted(const OpticalFlow2D::SubsetOptions& subset, Pointer const* slots, size_t steps = 1)
 {
-    OpticalFlow2D::SubsetOptions o = subset_options(radius, iterations, epsilon, max_shift, max_gradient);
-    o.mask = dev_mask ? dp(dev_mask) : has_mask_image ? 1 : 0;
-    o.min_pixels = min_pixels;
-    return o;
+    if (!OpticalFlow2D::SubsetOptionsOk(subset)) return false;
+    for (size_t k = 0; slots && subset.order != 2 && k < steps; ++k)
+        for (int c = 8; c < kSubsetSlots; ++c)
+            if (slots[kSubsetSlots * k + c]) return false;
+    return true;
 }
 }  // namespace
 
-// OpticalFlow2D::SubsetOptionsOk with a mask of min_pixels (0: the default) beside the options: 1 when accepted.  Needs no device.
-HOST_API int flow2d_host_subset_mask_options_ok(int radius, int iterations, float epsilon, float max_shift, float max_gradient, int order,
-                                                float max_curvature, int min_pixels)
+// OpticalFlow2D::SubsetOptionsOk: 1 when the options are what RefineNodes* / CorrelateSubset* accept.  Needs no device.
+HOST_API int flow2d_host_subset_options_ok(const flow2d_host_subset_options* options)
 {
-    OpticalFlow2D::SubsetOptions o = subset_options(radius, iterations, epsilon, max_shift, max_gradient, order, max_curvature);
-    o.mask = 1;
-    o.min_pixels = min_pixels;
-    return OpticalFlow2D::SubsetOptionsOk(o) ? 1 : 0;
+    return options && OpticalFlow2D::SubsetOptionsOk(subset_options(*options)) ? 1 : 0;
 }
 
 // OpticalFlow2D::SubsetMinPixels: the default min_pixels of a radius.
@@ -794,158 +798,78 @@ HOST_API int flow2d_host_subset_min_pixels(int radius)
     return OpticalFlow2D::SubsetMinPixels(o);
 }
 
-// OpticalFlow2D::SubsetOptionsOk: 1 when the options are what RefineNodes* / CorrelateSubset* accept.  Needs no device.
-HOST_API int flow2d_host_subset_options_ok(int radius, int iterations, float epsilon, float max_shift, float max_gradient)
+// OpticalFlow2D::RefineNodesDevice: device planes of the container's size; dev_out: the fourteen slots, each optional.  With a
+// record (host) the call synchronises.  0 on success, 1 for a null or refused argument, 2 when the run failed.
+HOST_API int flow2d_host_refine_nodes_device(flow2d_host_flow* h, void* dev_frame_0, void* dev_frame_1, void* dev_node_u0,
+                                             void* dev_node_v0, int grid_radius, int spacing, const flow2d_host_subset_options* options,
+                                             void* const* dev_out, flow2d_subset_record* record)
 {
-    return OpticalFlow2D::SubsetOptionsOk(subset_options(radius, iterations, epsilon, max_shift, max_gradient)) ? 1 : 0;
-}
-
-HOST_API int flow2d_host_subset2_options_ok(int radius, int iterations, float epsilon, float max_shift, float max_gradient, int order,
-                                            float max_curvature)
-{
-    return OpticalFlow2D::SubsetOptionsOk(subset_options(radius, iterations, epsilon, max_shift, max_gradient, order, max_curvature)) ? 1 : 0;
-}
-
-// OpticalFlow2D::RefineNodesDevice: device planes of the container's size; dev_out: eight planes (u, v, ux, uy, vx, vy, score, state),
-// each optional.  With a record (host) the call synchronises.  0 on success, 1 for a null or refused argument, 2 when the run failed.
-namespace {
-int refine_nodes_device(flow2d_host_flow* h, void* dev_frame_0, void* dev_frame_1, void* dev_node_u0, void* dev_node_v0, int grid_radius,
-                        int spacing, const OpticalFlow2D::SubsetOptions& subset, const OpticalFlow2D::SubsetPlanes& out,
-                        flow2d_subset_record* record)
-{
-    if (!h || !dev_frame_0 || !dev_frame_1 || !dev_node_u0 || !dev_node_v0 || !OpticalFlow2D::SubsetOptionsOk(subset)) return 1;
+    if (!h || !dev_frame_0 || !dev_frame_1 || !dev_node_u0 || !dev_node_v0 || !options) return 1;
+    const auto subset = subset_options(*options);
+    if (!subset_accepted(subset, dev_out)) return 1;
     h->flow.timing_mode = 0;
-    return h->flow.RefineNodesDevice(dp(dev_frame_0), dp(dev_frame_1), dp(dev_node_u0), dp(dev_node_v0), grid_radius, spacing, subset, out,
-                                     record)
+    return h->flow.RefineNodesDevice(dp(dev_frame_0), dp(dev_frame_1), dp(dev_node_u0), dp(dev_node_v0), grid_radius, spacing, subset,
+                                     subset_planes(dev_out), record)
                ? 0
                : 2;
-}
-}  // namespace
-
-HOST_API int flow2d_host_refine_nodes_device(flow2d_host_flow* h, void* dev_frame_0, void* dev_frame_1, void* dev_node_u0,
-                                             void* dev_node_v0, int grid_radius, int spacing, int radius, int iterations, float epsilon,
-                                             float max_shift, float max_gradient, void* const* dev_out, flow2d_subset_record* record)
-{
-    return refine_nodes_device(h, dev_frame_0, dev_frame_1, dev_node_u0, dev_node_v0, grid_radius, spacing,
-                               subset_options(radius, iterations, epsilon, max_shift, max_gradient), subset_planes(dev_out), record);
-}
-
-// ... with SubsetOptions::mask (dev_mask: a device plane of the container's size, needed) and min_pixels (0: the default): the
-// first-order refinement on a region of interest (flow2d_subset_refine_masked_2d); dev_out: the eight planes.
-HOST_API int flow2d_host_refine_nodes_masked_device(flow2d_host_flow* h, void* dev_frame_0, void* dev_frame_1, void* dev_node_u0,
-                                                    void* dev_node_v0, int grid_radius, int spacing, int radius, int iterations,
-                                                    float epsilon, float max_shift, float max_gradient, void* dev_mask, int min_pixels,
-                                                    void* const* dev_out, flow2d_subset_record* record)
-{
-    if (!dev_mask) return 1;
-    return refine_nodes_device(h, dev_frame_0, dev_frame_1, dev_node_u0, dev_node_v0, grid_radius, spacing,
-                               masked_options(radius, iterations, epsilon, max_shift, max_gradient, dev_mask, false, min_pixels),
-                               subset_planes(dev_out), record);
-}
-
-// ... with SubsetOptions::order and max_curvature; dev_out: fourteen planes, the eight and uxx, uxy, uyy, vxx, vxy, vyy.
-HOST_API int flow2d_host_refine_nodes2_device(flow2d_host_flow* h, void* dev_frame_0, void* dev_frame_1, void* dev_node_u0,
-                                              void* dev_node_v0, int grid_radius, int spacing, int radius, int iterations, float epsilon,
-                                              float max_shift, float max_gradient, int order, float max_curvature, void* const* dev_out,
-                                              flow2d_subset_record* record)
-{
-    return refine_nodes_device(h, dev_frame_0, dev_frame_1, dev_node_u0, dev_node_v0, grid_radius, spacing,
-                               subset_options(radius, iterations, epsilon, max_shift, max_gradient, order, max_curvature),
-                               subset2_planes(dev_out), record);
 }
 
 // OpticalFlow2D::CorrelateSubsetDevice: the passes as for flow2d_host_correlate_multipass_device, then the refinement; dev_out as
 // above, reports (optional) one per pass, record (optional).  Synchronises.  0, 1 or 2 as above.
-namespace {
-int correlate_subset_device(flow2d_host_flow* h, void* dev_frame_0, void* dev_frame_1, float lo, float scale, const int* passes, int count,
-                            float min_score, float threshold, float epsilon, int min_neighbours, const OpticalFlow2D::SubsetOptions& subset,
-                            void* dev_predictor_u, void* dev_predictor_v, const OpticalFlow2D::SubsetPlanes& out,
-                            OpticalFlow2D::CorrelationPassReport* reports, flow2d_subset_record* record, void* dev_flow_u, void* dev_flow_v)
+HOST_API int flow2d_host_correlate_subset_device(flow2d_host_flow* h, void* dev_frame_0, void* dev_frame_1, float lo, float scale,
+                                                 const int* passes, int count, float min_score, float threshold, float epsilon,
+                                                 int min_neighbours, const flow2d_host_subset_options* options, void* dev_predictor_u,
+                                                 void* dev_predictor_v, void* const* dev_out, OpticalFlow2D::CorrelationPassReport* reports,
+                                                 flow2d_subset_record* record, void* dev_flow_u, void* dev_flow_v)
 {
     const auto list = correlation_passes(passes, count);
     const auto validation = validation_options(threshold, epsilon, min_neighbours, 1, 1);
-    if (!h || !dev_frame_0 || !dev_frame_1 || count < 0 || (dev_flow_u == nullptr) != (dev_flow_v == nullptr) ||
-        (dev_predictor_u == nullptr) != (dev_predictor_v == nullptr) ||
-        !OpticalFlow2D::CorrelationPassesOk(h->width, h->height, lo, scale, list.data(), list.size(), min_score, validation) ||
-        !OpticalFlow2D::SubsetOptionsOk(subset))
+    if (!h || !dev_frame_0 || !dev_frame_1 || !options || count < 0 || (dev_flow_u == nullptr) != (dev_flow_v == nullptr) ||
+        (dev_predictor_u == nullptr) != (dev_predictor_v == nullptr))
+        return 1;
+    const auto subset = subset_options(*options);
+    if (!OpticalFlow2D::CorrelationPassesOk(h->width, h->height, lo, scale, list.data(), list.size(), min_score, validation) ||
+        !subset_accepted(subset, dev_out))
         return 1;
     h->flow.timing_mode = 0;
     return h->flow.CorrelateSubsetDevice(dp(dev_frame_0), dp(dev_frame_1), lo, scale, list.data(), list.size(), min_score, validation, subset,
-                                         dp(dev_predictor_u), dp(dev_predictor_v), out, reports, record, dp(dev_flow_u), dp(dev_flow_v))
+                                         dp(dev_predictor_u), dp(dev_predictor_v), subset_planes(dev_out), reports, record, dp(dev_flow_u),
+                                         dp(dev_flow_v))
                ? 0
                : 2;
 }
-}  // namespace
 
-HOST_API int flow2d_host_correlate_subset_device(flow2d_host_flow* h, void* dev_frame_0, void* dev_frame_1, float lo, float scale,
-                                                 const int* passes, int count, float min_score, float threshold, float epsilon,
-                                                 int min_neighbours, int radius, int iterations, float subset_epsilon, float max_shift,
-                                                 float max_gradient, void* dev_predictor_u, void* dev_predictor_v, void* const* dev_out,
-                                                 OpticalFlow2D::CorrelationPassReport* reports, flow2d_subset_record* record,
-                                                 void* dev_flow_u, void* dev_flow_v)
-{
-    return correlate_subset_device(h, dev_frame_0, dev_frame_1, lo, scale, passes, count, min_score, threshold, epsilon, min_neighbours,
-                                   subset_options(radius, iterations, subset_epsilon, max_shift, max_gradient), dev_predictor_u,
-                                   dev_predictor_v, subset_planes(dev_out), reports, record, dev_flow_u, dev_flow_v);
-}
-
-// ... with SubsetOptions::mask (a device plane, needed) and min_pixels; dev_out: the eight planes.
-HOST_API int flow2d_host_correlate_subset_masked_device(flow2d_host_flow* h, void* dev_frame_0, void* dev_frame_1, float lo, float scale,
-                                                        const int* passes, int count, float min_score, float threshold, float epsilon,
-                                                        int min_neighbours, int radius, int iterations, float subset_epsilon,
-                                                        float max_shift, float max_gradient, void* dev_mask, int min_pixels,
-                                                        void* dev_predictor_u, void* dev_predictor_v, void* const* dev_out,
-                                                        OpticalFlow2D::CorrelationPassReport* reports, flow2d_subset_record* record,
-                                                        void* dev_flow_u, void* dev_flow_v)
-{
-    if (!dev_mask) return 1;
-    return correlate_subset_device(h, dev_frame_0, dev_frame_1, lo, scale, passes, count, min_score, threshold, epsilon, min_neighbours,
-                                   masked_options(radius, iterations, subset_epsilon, max_shift, max_gradient, dev_mask, false, min_pixels),
-                                   dev_predictor_u, dev_predictor_v, subset_planes(dev_out), reports, record, dev_flow_u, dev_flow_v);
-}
-
-// ... with SubsetOptions::order and max_curvature; dev_out: fourteen planes.
-HOST_API int flow2d_host_correlate_subset2_device(flow2d_host_flow* h, void* dev_frame_0, void* dev_frame_1, float lo, float scale,
-                                                  const int* passes, int count, float min_score, float threshold, float epsilon,
-                                                  int min_neighbours, int radius, int iterations, float subset_epsilon, float max_shift,
-                                                  float max_gradient, int order, float max_curvature, void* dev_predictor_u,
-                                                  void* dev_predictor_v, void* const* dev_out, OpticalFlow2D::CorrelationPassReport* reports,
-                                                  flow2d_subset_record* record, void* dev_flow_u, void* dev_flow_v)
-{
-    return correlate_subset_device(h, dev_frame_0, dev_frame_1, lo, scale, passes, count, min_score, threshold, epsilon, min_neighbours,
-                                   subset_options(radius, iterations, subset_epsilon, max_shift, max_gradient, order, max_curvature),
-                                   dev_predictor_u, dev_predictor_v, subset2_planes(dev_out), reports, record, dev_flow_u, dev_flow_v);
-}
-
-// OpticalFlow2D::CorrelateSubset on tight host images: nodes -- eight arrays (u, v, ux, uy, vx, vy, score, state; u and v needed, the
-// gradients all or none) -- get the last pass's nw * nh floats each; the rest as for flow2d_host_correlate_multipass.
-namespace {
-// node_count: 8, or kSubset2Planes with the curvatures behind them
-int correlate_subset(flow2d_host_flow* h, const float* frame_0, const float* frame_1, const int* passes, int count, float min_score,
-                     float threshold, float epsilon, int min_neighbours, const OpticalFlow2D::SubsetOptions& subset, const float* predictor_u,
-                     const float* predictor_v, float* const* nodes, int node_count, OpticalFlow2D::CorrelationPassReport* reports,
-                     flow2d_subset_record* record, float* flow_u, float* flow_v, float* lo_scale, const float* mask_image = nullptr)
+// OpticalFlow2D::CorrelateSubset on tight host images: nodes -- the fourteen slots as arrays (u and v needed, the gradients all or
+// none, at order 2 the curvatures all or none) -- get the last pass's nw * nh floats each; options->mask: an image, which the object
+// uploads once; the rest as for flow2d_host_correlate_multipass.
+HOST_API int flow2d_host_correlate_subset(flow2d_host_flow* h, const float* frame_0, const float* frame_1, const int* passes, int count,
+                                          float min_score, float threshold, float epsilon, int min_neighbours,
+                                          const flow2d_host_subset_options* options, const float* predictor_u, const float* predictor_v,
+                                          float* const* nodes, OpticalFlow2D::CorrelationPassReport* reports, flow2d_subset_record* record,
+                                          float* flow_u, float* flow_v, float* lo_scale)
 {
     const auto list = correlation_passes(passes, count);
     const auto validation = validation_options(threshold, epsilon, min_neighbours, 1, 1);
-    if (!h || !frame_0 || !frame_1 || !nodes || !nodes[0] || !nodes[1] || count < 0 || (flow_u == nullptr) != (flow_v == nullptr) ||
-        (predictor_u == nullptr) != (predictor_v == nullptr))
+    if (!h || !frame_0 || !frame_1 || !options || !nodes || !nodes[0] || !nodes[1] || count < 0 ||
+        (flow_u == nullptr) != (flow_v == nullptr) || (predictor_u == nullptr) != (predictor_v == nullptr))
         return 1;
+    const auto subset = subset_options(*options);
     HostImages im(h);
     Data2D *f0 = im.In(frame_0), *f1 = im.In(frame_1);
     Data2D *pu = predictor_u ? im.In(predictor_u) : nullptr, *pv = predictor_v ? im.In(predictor_v) : nullptr;
     Data2D *fu = im.Out(flow_u, im.AfterSuccess), *fv = im.Out(flow_v, im.AfterSuccess);
-    Data2D* mask = mask_image ? im.In(mask_image) : nullptr;
+    Data2D* mask = options->mask ? im.In(static_cast<const float*>(options->mask)) : nullptr;
     float lo = 0.f, scale = 1.f;
     OpticalFlow2D::CorrelationRange(*f0, *f1, lo, scale);
     if (!OpticalFlow2D::CorrelationPassesOk(h->width, h->height, lo, scale, list.data(), list.size(), min_score, validation) ||
-        !OpticalFlow2D::SubsetOptionsOk(subset))
+        !subset_accepted(subset, nodes))
         return 1;
     size_t nw = 0, nh = 0;
     flow2d_correlation_grid(h->width, h->height, list.back().radius, list.back().spacing, &nw, &nh);
+    const int node_count = node_images(subset);
     std::vector<Data2D> images;
     for (int k = 0; k < node_count; ++k) images.emplace_back(nw, nh);
-    Data2D* wanted[kSubset2Planes] = {};
+    Data2D* wanted[kSubsetSlots] = {};
     for (int k = 0; k < node_count; ++k) wanted[k] = nodes[k] ? &images[k] : nullptr;
     h->flow.CorrelateSubset(*f0, *f1, list.data(), list.size(), min_score, validation, subset, wanted, reports, record, fu, fv, pu, pv, mask);
     const int rc = im.Finish(h->flow);
@@ -957,46 +881,6 @@ int correlate_subset(flow2d_host_flow* h, const float* frame_0, const float* fra
         lo_scale[1] = scale;
     }
     return 0;
-}
-}  // namespace
-
-HOST_API int flow2d_host_correlate_subset(flow2d_host_flow* h, const float* frame_0, const float* frame_1, const int* passes, int count,
-                                          float min_score, float threshold, float epsilon, int min_neighbours, int radius, int iterations,
-                                          float subset_epsilon, float max_shift, float max_gradient, const float* predictor_u,
-                                          const float* predictor_v, float* const* nodes, OpticalFlow2D::CorrelationPassReport* reports,
-                                          flow2d_subset_record* record, float* flow_u, float* flow_v, float* lo_scale)
-{
-    return correlate_subset(h, frame_0, frame_1, passes, count, min_score, threshold, epsilon, min_neighbours,
-                            subset_options(radius, iterations, subset_epsilon, max_shift, max_gradient), predictor_u, predictor_v, nodes, 8,
-                            reports, record, flow_u, flow_v, lo_scale);
-}
-
-// ... with a mask image (a tight host image of the frames' size, needed; the object uploads it once) and min_pixels; nodes: eight arrays.
-HOST_API int flow2d_host_correlate_subset_masked(flow2d_host_flow* h, const float* frame_0, const float* frame_1, const int* passes,
-                                                 int count, float min_score, float threshold, float epsilon, int min_neighbours, int radius,
-                                                 int iterations, float subset_epsilon, float max_shift, float max_gradient,
-                                                 const float* mask, int min_pixels, const float* predictor_u, const float* predictor_v,
-                                                 float* const* nodes, OpticalFlow2D::CorrelationPassReport* reports,
-                                                 flow2d_subset_record* record, float* flow_u, float* flow_v, float* lo_scale)
-{
-    if (!mask) return 1;
-    return correlate_subset(h, frame_0, frame_1, passes, count, min_score, threshold, epsilon, min_neighbours,
-                            masked_options(radius, iterations, subset_epsilon, max_shift, max_gradient, nullptr, true, min_pixels),
-                            predictor_u, predictor_v, nodes, 8, reports, record, flow_u, flow_v, lo_scale, mask);
-}
-
-// ... with SubsetOptions::order and max_curvature; nodes: fourteen arrays, the six curvatures all or none.
-HOST_API int flow2d_host_correlate_subset2(flow2d_host_flow* h, const float* frame_0, const float* frame_1, const int* passes, int count,
-                                           float min_score, float threshold, float epsilon, int min_neighbours, int radius, int iterations,
-                                           float subset_epsilon, float max_shift, float max_gradient, int order, float max_curvature,
-                                           const float* predictor_u, const float* predictor_v, float* const* nodes,
-                                           OpticalFlow2D::CorrelationPassReport* reports, flow2d_subset_record* record, float* flow_u,
-                                           float* flow_v, float* lo_scale)
-{
-    const auto subset = subset_options(radius, iterations, subset_epsilon, max_shift, max_gradient, order, max_curvature);
-    if (!OpticalFlow2D::SubsetOptionsOk(subset)) return 1;
-    return correlate_subset(h, frame_0, frame_1, passes, count, min_score, threshold, epsilon, min_neighbours, subset, predictor_u,
-                            predictor_v, nodes, subset.order == 2 ? kSubset2Planes : 8, reports, record, flow_u, flow_v, lo_scale);
 }
 
 // ---- subset refinement over a sequence ------------------------------------------------------------------------------------------
@@ -1018,76 +902,49 @@ HOST_API int flow2d_host_sequence_options_ok(int fill, int min_state, int min_ne
     return OpticalFlow2D::SequenceOptionsOk(sequence_options(fill, min_state, min_neighbours, max_shift)) ? 1 : 0;
 }
 
-// OpticalFlow2D::RefineNodesFromDevice: dev_start -- six device planes u, v, ux, uy, vx, vy, all needed; the rest as for
-// flow2d_host_refine_nodes_device.
-namespace {
-int refine_nodes_from_device(flow2d_host_flow* h, void* dev_frame_0, void* dev_frame_1, void* const* dev_start, int grid_radius, int spacing,
-                             const OpticalFlow2D::SubsetOptions& subset, const OpticalFlow2D::SubsetPlanes& out, flow2d_subset_record* record)
+// OpticalFlow2D::RefineNodesFromDevice: dev_start -- six device planes u, v, ux, uy, vx, vy, all needed (at order 2 the start's
+// curvatures are 0); the rest as for flow2d_host_refine_nodes_device.
+HOST_API int flow2d_host_refine_nodes_from_device(flow2d_host_flow* h, void* dev_frame_0, void* dev_frame_1, void* const* dev_start,
+                                                  int grid_radius, int spacing, const flow2d_host_subset_options* options,
+                                                  void* const* dev_out, flow2d_subset_record* record)
 {
-    if (!h || !dev_frame_0 || !dev_frame_1 || !dev_start || !OpticalFlow2D::SubsetOptionsOk(subset)) return 1;
+    if (!h || !dev_frame_0 || !dev_frame_1 || !dev_start || !options) return 1;
+    const auto subset = subset_options(*options);
+    if (!subset_accepted(subset, dev_out)) return 1;
     for (int k = 0; k < 6; ++k)
         if (!dev_start[k]) return 1;
     OpticalFlow2D::SubsetPlanes start;
     start = {dp(dev_start[0]), dp(dev_start[1]), dp(dev_start[2]), dp(dev_start[3]), dp(dev_start[4]), dp(dev_start[5]), 0, 0};
     h->flow.timing_mode = 0;
-    return h->flow.RefineNodesFromDevice(dp(dev_frame_0), dp(dev_frame_1), start, grid_radius, spacing, subset, out, record) ? 0 : 2;
-}
-}  // namespace
-
-HOST_API int flow2d_host_refine_nodes_from_device(flow2d_host_flow* h, void* dev_frame_0, void* dev_frame_1, void* const* dev_start,
-                                                  int grid_radius, int spacing, int radius, int iterations, float epsilon, float max_shift,
-                                                  float max_gradient, void* const* dev_out, flow2d_subset_record* record)
-{
-    return refine_nodes_from_device(h, dev_frame_0, dev_frame_1, dev_start, grid_radius, spacing,
-                                    subset_options(radius, iterations, epsilon, max_shift, max_gradient), subset_planes(dev_out), record);
+    return h->flow.RefineNodesFromDevice(dp(dev_frame_0), dp(dev_frame_1), start, grid_radius, spacing, subset, subset_planes(dev_out), record)
+               ? 0
+               : 2;
 }
 
-// ... with SubsetOptions::mask (a device plane, needed) and min_pixels; dev_out: the eight planes.
-HOST_API int flow2d_host_refine_nodes_from_masked_device(flow2d_host_flow* h, void* dev_frame_0, void* dev_frame_1, void* const* dev_start,
-                                                         int grid_radius, int spacing, int radius, int iterations, float epsilon,
-                                                         float max_shift, float max_gradient, void* dev_mask, int min_pixels,
-                                                         void* const* dev_out, flow2d_subset_record* record)
-{
-    if (!dev_mask) return 1;
-    return refine_nodes_from_device(h, dev_frame_0, dev_frame_1, dev_start, grid_radius, spacing,
-                                    masked_options(radius, iterations, epsilon, max_shift, max_gradient, dev_mask, false, min_pixels),
-                                    subset_planes(dev_out), record);
-}
-
-// ... with SubsetOptions::order and max_curvature; dev_out: fourteen planes.  The start's curvatures are 0.
-HOST_API int flow2d_host_refine_nodes_from2_device(flow2d_host_flow* h, void* dev_frame_0, void* dev_frame_1, void* const* dev_start,
-                                                   int grid_radius, int spacing, int radius, int iterations, float epsilon, float max_shift,
-                                                   float max_gradient, int order, float max_curvature, void* const* dev_out,
-                                                   flow2d_subset_record* record)
-{
-    return refine_nodes_from_device(h, dev_frame_0, dev_frame_1, dev_start, grid_radius, spacing,
-                                    subset_options(radius, iterations, epsilon, max_shift, max_gradient, order, max_curvature),
-                                    subset2_planes(dev_out), record);
-}
-
-// OpticalFlow2D::SequenceStepReport as the facade hands it out
+// the records as the facade takes them and hands them out
+static_assert(sizeof(flow2d_host_subset_options) == 40, "flow2d_host_subset_options layout");
 static_assert(sizeof(OpticalFlow2D::SequenceStepReport) == 64 + 64 * OpticalFlow2D::kSequenceMaxFill, "SequenceStepReport layout");
 
-// OpticalFlow2D::CorrelateSubsetSequenceDevice: dev_frames -- `frames` device planes, the first the reference; dev_out -- eight planes
-// per step (u, v, ux, uy, vx, vy, score, state; only the score may be null); dev_flows (optional) -- two per step, each pair optional;
-// reports (optional) one per pass of step 1, steps (optional) one per step.  Synchronises.  0, 1 or 2 as above.
-namespace {
-// planes_per_step: 8, or kSubset2Planes with the curvatures behind them (which may be null)
-int correlate_subset_sequence_device(flow2d_host_flow* h, void* const* dev_frames, int frames, float lo, float scale, const int* passes,
-                                     int count, float min_score, float threshold, float epsilon, int min_neighbours,
-                                     const OpticalFlow2D::SubsetOptions& subset, int fill, int min_state, int predict_neighbours,
-                                     float sequence_max_shift, void* const* dev_out, int planes_per_step,
-                                     OpticalFlow2D::CorrelationPassReport* reports, OpticalFlow2D::SequenceStepReport* steps,
-                                     void* const* dev_flows)
+// OpticalFlow2D::CorrelateSubsetSequenceDevice: dev_frames -- `frames` device planes, the first the reference; dev_out -- the
+// fourteen slots per step (of the first eight only the score may be null; at order 2 the curvatures all or none); dev_flows
+// (optional) -- two per step, each pair optional; options->mask: every step uses it; reports (optional) one per pass of step 1,
+// steps (optional) one per step.  Synchronises.  0, 1 or 2 as above.
+HOST_API int flow2d_host_correlate_subset_sequence_device(flow2d_host_flow* h, void* const* dev_frames, int frames, float lo, float scale,
+                                                          const int* passes, int count, float min_score, float threshold, float epsilon,
+                                                          int min_neighbours, const flow2d_host_subset_options* options, int fill,
+                                                          int min_state, int predict_neighbours, float sequence_max_shift,
+                                                          void* const* dev_out, OpticalFlow2D::CorrelationPassReport* reports,
+                                                          OpticalFlow2D::SequenceStepReport* steps, void* const* dev_flows)
 {
     const auto list = correlation_passes(passes, count);
     const auto validation = validation_options(threshold, epsilon, min_neighbours, 1, 1);
     const auto sequence = sequence_options(fill, min_state, predict_neighbours, sequence_max_shift);
-    if (!h || !dev_frames || frames < 2 || count < 0 || !dev_out ||
-        !OpticalFlow2D::CorrelationPassesOk(h->width, h->height, lo, scale, list.data(), list.size(), min_score, validation) ||
-        !OpticalFlow2D::SubsetOptionsOk(subset) || !OpticalFlow2D::SequenceOptionsOk(sequence))
-        return 1;
+    if (!h || !dev_frames || frames < 2 || count < 0 || !dev_out || !options) return 1;
+    const auto subset = subset_options(*options);
     const size_t n = static_cast<size_t>(frames), step_count = n - 1;
+    if (!OpticalFlow2D::CorrelationPassesOk(h->width, h->height, lo, scale, list.data(), list.size(), min_score, validation) ||
+        !subset_accepted(subset, dev_out, step_count) || !OpticalFlow2D::SequenceOptionsOk(sequence))
+        return 1;
     std::vector<DevicePtr> frame_list(n), flow_list(2 * step_count, 0);
     for (size_t k = 0; k < n; ++k) {
         if (!dev_frames[k]) return 1;
@@ -1095,8 +952,8 @@ int correlate_subset_sequence_device(flow2d_host_flow* h, void* const* dev_frame
     }
     std::vector<OpticalFlow2D::SubsetPlanes> out(step_count);
     for (size_t k = 0; k < step_count; ++k) {
-        void* const* step = dev_out + planes_per_step * k;
-        out[k] = planes_per_step == 8 ? subset_planes(step) : subset2_planes(step);
+        void* const* step = dev_out + kSubsetSlots * k;
+        out[k] = subset_planes(step);
         for (int c = 0; c < 8; ++c)
             if (c != 6 && !step[c]) return 1;
         for (int c = 0; dev_flows && c < 2; ++c) flow_list[2 * k + c] = dp(dev_flows[2 * k + c]);
@@ -1108,149 +965,61 @@ int correlate_subset_sequence_device(flow2d_host_flow* h, void* const* dev_frame
                ? 0
                : 2;
 }
-}  // namespace
 
-HOST_API int flow2d_host_correlate_subset_sequence_device(flow2d_host_flow* h, void* const* dev_frames, int frames, float lo, float scale,
-                                                          const int* passes, int count, float min_score, float threshold, float epsilon,
-                                                          int min_neighbours, int radius, int iterations, float subset_epsilon,
-                                                          float max_shift, float max_gradient, int fill, int min_state,
-                                                          int predict_neighbours, float sequence_max_shift, void* const* dev_out,
-                                                          OpticalFlow2D::CorrelationPassReport* reports,
-                                                          OpticalFlow2D::SequenceStepReport* steps, void* const* dev_flows)
-{
-    return correlate_subset_sequence_device(h, dev_frames, frames, lo, scale, passes, count, min_score, threshold, epsilon, min_neighbours,
-                                            subset_options(radius, iterations, subset_epsilon, max_shift, max_gradient), fill, min_state,
-                                            predict_neighbours, sequence_max_shift, dev_out, 8, reports, steps, dev_flows);
-}
-
-// ... with SubsetOptions::mask (a device plane, needed: every step uses it) and min_pixels; dev_out: eight planes per step.
-HOST_API int flow2d_host_correlate_subset_masked_sequence_device(flow2d_host_flow* h, void* const* dev_frames, int frames, float lo,
-                                                                 float scale, const int* passes, int count, float min_score,
-                                                                 float threshold, float epsilon, int min_neighbours, int radius,
-                                                                 int iterations, float subset_epsilon, float max_shift, float max_gradient,
-                                                                 void* dev_mask, int min_pixels, int fill, int min_state,
-                                                                 int predict_neighbours, float sequence_max_shift, void* const* dev_out,
-                                                                 OpticalFlow2D::CorrelationPassReport* reports,
-                                                                 OpticalFlow2D::SequenceStepReport* steps, void* const* dev_flows)
-{
-    if (!dev_mask) return 1;
-    return correlate_subset_sequence_device(h, dev_frames, frames, lo, scale, passes, count, min_score, threshold, epsilon, min_neighbours,
-                                            masked_options(radius, iterations, subset_epsilon, max_shift, max_gradient, dev_mask, false,
-                                                           min_pixels),
-                                            fill, min_state, predict_neighbours, sequence_max_shift, dev_out, 8, reports, steps, dev_flows);
-}
-
-// ... with SubsetOptions::order and max_curvature; dev_out: fourteen planes per step, the six curvatures all or none.
-HOST_API int flow2d_host_correlate_subset2_sequence_device(flow2d_host_flow* h, void* const* dev_frames, int frames, float lo, float scale,
-                                                           const int* passes, int count, float min_score, float threshold, float epsilon,
-                                                           int min_neighbours, int radius, int iterations, float subset_epsilon,
-                                                           float max_shift, float max_gradient, int order, float max_curvature, int fill,
-                                                           int min_state, int predict_neighbours, float sequence_max_shift,
-                                                           void* const* dev_out, OpticalFlow2D::CorrelationPassReport* reports,
-                                                           OpticalFlow2D::SequenceStepReport* steps, void* const* dev_flows)
-{
-    return correlate_subset_sequence_device(h, dev_frames, frames, lo, scale, passes, count, min_score, threshold, epsilon, min_neighbours,
-                                            subset_options(radius, iterations, subset_epsilon, max_shift, max_gradient, order, max_curvature),
-                                            fill, min_state, predict_neighbours, sequence_max_shift, dev_out, kSubset2Planes, reports, steps,
-                                            dev_flows);
-}
-
-// OpticalFlow2D::CorrelateSubsetSequence on tight host images: frames -- `count_frames` images; nodes -- eight arrays per step, which
-// get the last pass's nw * nh floats each (only a score may be null); flows (optional) -- two images per step, each pair optional.
-namespace {
-// per_step: 8 node arrays per step, or kSubset2Planes with the curvatures behind them
-int correlate_subset_sequence(flow2d_host_flow* h, const float* const* frames, int count_frames, const int* passes, int count, float min_score,
-                              float threshold, float epsilon, int min_neighbours, const OpticalFlow2D::SubsetOptions& subset, int fill,
-                              int min_state, int predict_neighbours, float sequence_max_shift, float* const* nodes, size_t per_step,
-                              OpticalFlow2D::CorrelationPassReport* reports, OpticalFlow2D::SequenceStepReport* steps, float* const* flows,
-                              float* lo_scale, const float* mask_image = nullptr)
+// OpticalFlow2D::CorrelateSubsetSequence on tight host images: frames -- `count_frames` images; nodes -- the fourteen slots per step
+// as arrays, which get the last pass's nw * nh floats each (of the first eight only a score may be null); flows (optional) -- two
+// images per step, each pair optional; options->mask: an image, uploaded once for all steps.
+HOST_API int flow2d_host_correlate_subset_sequence(flow2d_host_flow* h, const float* const* frames, int count_frames, const int* passes,
+                                                   int count, float min_score, float threshold, float epsilon, int min_neighbours,
+                                                   const flow2d_host_subset_options* options, int fill, int min_state,
+                                                   int predict_neighbours, float sequence_max_shift, float* const* nodes,
+                                                   OpticalFlow2D::CorrelationPassReport* reports, OpticalFlow2D::SequenceStepReport* steps,
+                                                   float* const* flows, float* lo_scale)
 {
     const auto list = correlation_passes(passes, count);
     const auto validation = validation_options(threshold, epsilon, min_neighbours, 1, 1);
     const auto sequence = sequence_options(fill, min_state, predict_neighbours, sequence_max_shift);
-    if (!h || !frames || count_frames < 2 || !nodes || count < 0) return 1;
+    if (!h || !frames || count_frames < 2 || !nodes || count < 0 || !options) return 1;
+    const auto subset = subset_options(*options);
     const size_t n = static_cast<size_t>(count_frames), step_count = n - 1;
     for (size_t k = 0; k < n; ++k)
         if (!frames[k]) return 1;
     for (size_t k = 0; k < step_count; ++k) {
         for (int c = 0; c < 8; ++c)
-            if (c != 6 && !nodes[per_step * k + c]) return 1;
+            if (c != 6 && !nodes[kSubsetSlots * k + c]) return 1;
         if (flows && (flows[2 * k] == nullptr) != (flows[2 * k + 1] == nullptr)) return 1;
     }
     HostImages im(h);
     std::vector<Data2D*> in(n), flow_images(2 * step_count, nullptr);
     for (size_t k = 0; k < n; ++k) in[k] = im.In(frames[k]);
     for (size_t k = 0; flows && k < 2 * step_count; ++k) flow_images[k] = im.Out(flows[k], im.AfterSuccess);
-    Data2D* mask = mask_image ? im.In(mask_image) : nullptr;
+    Data2D* mask = options->mask ? im.In(static_cast<const float*>(options->mask)) : nullptr;
     float lo = 0.f, scale = 1.f;
     OpticalFlow2D::CorrelationRange(*in[0], *in[1], lo, scale);
     if (!OpticalFlow2D::CorrelationPassesOk(h->width, h->height, lo, scale, list.data(), list.size(), min_score, validation) ||
-        !OpticalFlow2D::SubsetOptionsOk(subset) || !OpticalFlow2D::SequenceOptionsOk(sequence))
+        !subset_accepted(subset, nodes, step_count) || !OpticalFlow2D::SequenceOptionsOk(sequence))
         return 1;
     size_t nw = 0, nh = 0;
     flow2d_correlation_grid(h->width, h->height, list.back().radius, list.back().spacing, &nw, &nh);
+    // image per_step * k + c is slot c of step k: OpticalFlow2D::CorrelateSubsetSequence takes the steps' images side by side
+    const size_t per_step = static_cast<size_t>(node_images(subset));
+    auto slot = [&](size_t image) { return nodes[kSubsetSlots * (image / per_step) + image % per_step]; };
     std::vector<Data2D> images;
     images.reserve(per_step * step_count);
     for (size_t k = 0; k < per_step * step_count; ++k) images.emplace_back(nw, nh);
     std::vector<Data2D*> wanted(per_step * step_count);
-    for (size_t k = 0; k < per_step * step_count; ++k) wanted[k] = nodes[k] ? &images[k] : nullptr;
+    for (size_t k = 0; k < per_step * step_count; ++k) wanted[k] = slot(k) ? &images[k] : nullptr;
     h->flow.CorrelateSubsetSequence(in.data(), n, list.data(), list.size(), min_score, validation, subset, sequence, wanted.data(), reports,
                                     steps, flows ? flow_images.data() : nullptr, mask);
     const int rc = im.Finish(h->flow);
     if (rc) return rc;
     for (size_t k = 0; k < per_step * step_count; ++k)
-        if (nodes[k]) std::memcpy(nodes[k], images[k].DataPtr(), nw * nh * sizeof(float));
+        if (slot(k)) std::memcpy(slot(k), images[k].DataPtr(), nw * nh * sizeof(float));
     if (lo_scale) {
         lo_scale[0] = lo;
         lo_scale[1] = scale;
     }
     return 0;
-}
-}  // namespace
-
-HOST_API int flow2d_host_correlate_subset_sequence(flow2d_host_flow* h, const float* const* frames, int count_frames, const int* passes,
-                                                   int count, float min_score, float threshold, float epsilon, int min_neighbours, int radius,
-                                                   int iterations, float subset_epsilon, float max_shift, float max_gradient, int fill,
-                                                   int min_state, int predict_neighbours, float sequence_max_shift, float* const* nodes,
-                                                   OpticalFlow2D::CorrelationPassReport* reports, OpticalFlow2D::SequenceStepReport* steps,
-                                                   float* const* flows, float* lo_scale)
-{
-    return correlate_subset_sequence(h, frames, count_frames, passes, count, min_score, threshold, epsilon, min_neighbours,
-                                     subset_options(radius, iterations, subset_epsilon, max_shift, max_gradient), fill, min_state,
-                                     predict_neighbours, sequence_max_shift, nodes, 8, reports, steps, flows, lo_scale);
-}
-
-// ... with a mask image (a tight host image of the frames' size, needed; uploaded once for all steps) and min_pixels; nodes: eight
-// arrays per step.
-HOST_API int flow2d_host_correlate_subset_masked_sequence(flow2d_host_flow* h, const float* const* frames, int count_frames,
-                                                          const int* passes, int count, float min_score, float threshold, float epsilon,
-                                                          int min_neighbours, int radius, int iterations, float subset_epsilon,
-                                                          float max_shift, float max_gradient, const float* mask, int min_pixels, int fill,
-                                                          int min_state, int predict_neighbours, float sequence_max_shift,
-                                                          float* const* nodes, OpticalFlow2D::CorrelationPassReport* reports,
-                                                          OpticalFlow2D::SequenceStepReport* steps, float* const* flows, float* lo_scale)
-{
-    if (!mask) return 1;
-    return correlate_subset_sequence(h, frames, count_frames, passes, count, min_score, threshold, epsilon, min_neighbours,
-                                     masked_options(radius, iterations, subset_epsilon, max_shift, max_gradient, nullptr, true, min_pixels),
-                                     fill, min_state, predict_neighbours, sequence_max_shift, nodes, 8, reports, steps, flows, lo_scale,
-                                     mask);
-}
-
-// ... with SubsetOptions::order and max_curvature; nodes: fourteen arrays per step, the six curvatures all or none.
-HOST_API int flow2d_host_correlate_subset2_sequence(flow2d_host_flow* h, const float* const* frames, int count_frames, const int* passes,
-                                                    int count, float min_score, float threshold, float epsilon, int min_neighbours, int radius,
-                                                    int iterations, float subset_epsilon, float max_shift, float max_gradient, int order,
-                                                    float max_curvature, int fill, int min_state, int predict_neighbours,
-                                                    float sequence_max_shift, float* const* nodes,
-                                                    OpticalFlow2D::CorrelationPassReport* reports, OpticalFlow2D::SequenceStepReport* steps,
-                                                    float* const* flows, float* lo_scale)
-{
-    const auto subset = subset_options(radius, iterations, subset_epsilon, max_shift, max_gradient, order, max_curvature);
-    if (!OpticalFlow2D::SubsetOptionsOk(subset)) return 1;
-    return correlate_subset_sequence(h, frames, count_frames, passes, count, min_score, threshold, epsilon, min_neighbours, subset, fill,
-                                     min_state, predict_neighbours, sequence_max_shift, nodes, subset.order == 2 ? kSubset2Planes : 8, reports,
-                                     steps, flows, lo_scale);
 }
 
 // ---- strain on the node grid ---------------------------------------------------------------------------------------------------

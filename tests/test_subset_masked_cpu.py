@@ -486,5 +486,41 @@ def test_subset_options_with_a_mask(flow2d):
     assert ok(1, mask=True) and ok(1, mask=True, min_pixels=9) and not ok(1, mask=True, min_pixels=10) and not ok(16, mask=True)
     host = flow2d.host_lib()
     assert [host.flow2d_host_subset_min_pixels(R) for R in (1, 2, 7, 15)] == [default_min_pixels(R) for R in (1, 2, 7, 15)]
-    # the masked host entries refuse a call without a mask
-    assert host.flow2d_host_refine_nodes_masked_device(None, None, None, None, None, 7, 8, 7, 20, 1e-3, 2.0, 0.5, None, 0, None, None) == 1
+    # the one host entry refuses a call without its options; min_pixels goes with a mask, and a mask with order 1 (both before any call)
+    assert host.flow2d_host_refine_nodes_device(None, None, None, None, None, 7, 8, None, None, None) == 1
+    flow = flow2d.OpticalFlow.__new__(flow2d.OpticalFlow)  # (no object of the host layer: neither call gets as far as one)
+    with pytest.raises(ValueError):
+        flow.refine_nodes_device(None, None, None, None, 7, 8, 7, min_pixels=57)
+    with pytest.raises(flow2d.Flow2DError) as refused:
+        flow.refine_nodes_device(None, None, None, None, 7, 8, 7, mask=1 << 20, order=2)
+    assert refused.value.status == 1
+
+
+def test_the_options_record_has_the_host_layers_fields(flow2d):
+    """flow2d_host_subset_options as ctypes lays it out against the C++ struct: one field made invalid at a time (the values are
+    those OpticalFlow2D::SubsetOptionsOk refuses) is refused, and a refusal that follows each field alone shows that the offsets
+    agree."""
+    assert ctypes.sizeof(flow2d.SubsetOptions) == 40
+    ok = flow2d.host_lib().flow2d_host_subset_options_ok
+    assert ok(None) == 0
+    R = 7
+    default = dict(radius=R, iterations=20, epsilon=1e-3, max_shift=2.0, max_gradient=0.5, order=1, max_curvature=0.05, min_pixels=0, mask=None)
+    assert [name for name, _ in flow2d.SubsetOptions._fields_] == list(default)
+
+    def accepted(**fields):
+        return ok(ctypes.byref(flow2d.SubsetOptions(**dict(default, **fields))))
+
+    assert accepted() == 1 and accepted(mask=1) == 1
+    nan = float("nan")
+    bad = [dict(radius=0), dict(radius=16), dict(iterations=0), dict(epsilon=nan), dict(max_shift=0.0), dict(max_gradient=-1.0), dict(order=3),
+           dict(max_curvature=nan), dict(min_pixels=5), dict(min_pixels=(2 * R + 1) ** 2 + 1), dict(mask=1, order=2)]
+    for fields in bad:
+        assert accepted(**fields) == 0, fields
+    # ... and the same fields at the other end of what is accepted, with and without the mask's mark
+    good = [dict(radius=1), dict(radius=15), dict(iterations=1), dict(iterations=64), dict(epsilon=0.0), dict(max_shift=1e-3),
+            dict(max_gradient=1e-3), dict(order=2), dict(radius=2, order=2), dict(max_curvature=1e-3), dict(min_pixels=6),
+            dict(min_pixels=(2 * R + 1) ** 2)]
+    for fields in good:
+        assert accepted(**fields) == 1, fields
+        if fields.get("order") != 2:
+            assert accepted(mask=1, **fields) == 1, fields
