@@ -8,7 +8,7 @@
 // over the iterations -- fd, fx, fy of a lane's pixels -- and the samples g of the current iteration live in the wave's slice
 // of dynamic LDS, four doubles per pixel, each element read and written by its own lane only: 7.2 KB per wave at R = 7, 30.8 KB
 // at R = 15.  The entry sizes the workgroup so that the slices fit the 64 KB every launch may ask for without an attribute
-// call: four waves up to R = 11, three at R = 12, two from R = 13.
+// call: four waves up to R = 10, three at R = 11 and 12 (16 960 bytes per wave at R = 11), two from R = 13.
 // A *sum over the subset* is the lane's partial over its pixels in ascending order, from 0, then wave_sum's butterfly: every
 // lane ends with the same bits, so H, its Cholesky factor, b and p are the same in every lane -- the 6 x 6 algebra runs
 // redundantly in all lanes, nothing is broadcast, and every branch on a node's state is uniform over the wave.
@@ -396,7 +396,7 @@ int subset_refine_entry(flow2d_context* ctx, const float* frame_0, const float* 
     const unsigned side = static_cast<unsigned>(2 * subset_radius + 1);
     const unsigned slice = (side * side + 1u) & ~1u;                       // at most 962 doubles
     const unsigned wave_bytes = 4u * slice * sizeof(double);               // at most 30 784
-    const unsigned waves = std::min<unsigned>(kSubsetMaxWaves, kSubsetLdsBytes / wave_bytes);  // 4 up to R = 11, 3 at 12, 2 beyond
+    const unsigned waves = std::min<unsigned>(kSubsetMaxWaves, kSubsetLdsBytes / wave_bytes);  // 4 up to R = 10, 3 at 11 and 12, 2 beyond
     const SubsetArgs a = {frame_0, frame_1, node_u0, node_v0, out_u, out_v, out_ux, out_uy, out_vx, out_vy, out_score, out_state,
                           reinterpret_cast<unsigned long long*>(record),
                           static_cast<int>(width), static_cast<int>(height), static_cast<int>(pitch_bytes / 4),

@@ -125,6 +125,32 @@ def test_largest_subset(flow2d, ctx):
     assert counts(want)["converged"] >= 1
 
 
+_small_specimen = []
+
+
+def small_specimen():
+    """40 x 36, grid (3, s 4), 9 x 8 nodes: the stretched specimen's frames at that size and the truth rounded to whole pixels as the
+    start -- the case of test_gpu_subset_masked.py's large radii, made once."""
+    if not _small_specimen:
+        scene, _ = scenes_module().make_speckle_specimen("stretch", 40, 36, seed=0)
+        nw, nh = grid(40, 36, 3, 4)
+        cy, cx = 3 + np.arange(nh) * 4, 3 + np.arange(nw) * 4
+        _small_specimen.append((scene.frame_0, scene.frame_1, np.rint(scene.gt_u[np.ix_(cy, cx)]).astype(F32),
+                                np.rint(scene.gt_v[np.ix_(cy, cx)]).astype(F32)))
+    return _small_specimen[0]
+
+
+@pytest.mark.parametrize("R", [10, 11, 12, 13, 15])
+def test_the_large_radii(flow2d, ctx, R):
+    """The radii around every change of the waves per workgroup: four at R = 10, three at 11 and 12 (node = blockIdx.x * 3 + wave),
+    two from 13.  40 x 36: only the inner nodes' subsets lie inside frame 0, the others stray."""
+    f0, f1, u0, v0 = small_specimen()
+    assert u0.shape == (8, 9) and u0.size % 3 == 0 and u0.size % 4 == 0  # (72 nodes: 18, 24 and 36 full workgroups)
+    want = check_subset(ctx, f0, f1, u0, v0, 3, 4, R, "40x36 specimen, R = %d" % R)
+    c = counts(want)
+    assert (want.state >= 0).sum() >= 1 and c["strayed"] >= 20
+
+
 def test_several_workgroups(flow2d, ctx):
     f0, f1, u0, v0 = speckle_case(130, 37, 7, 8)
     assert u0.shape == (3, 15) and u0.size % 4 != 0

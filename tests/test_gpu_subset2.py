@@ -13,7 +13,7 @@ import pytest
 from test_correlate_cpu import F32, U32, bits, correlate_reference, frame_range, grid, random_frames, scenes_module
 from test_gpu_batch_kernels import Tall, pitch_of, stride_of
 from test_gpu_multipass import POISON, padded, release
-from test_gpu_subset import speckle_case
+from test_gpu_subset import small_specimen, speckle_case
 from test_subset2_cpu import CURVATURES, GRADIENTS, P_NAMES, Refined2, all_orders2
 from test_subset_cpu import FLAT, NO_INPUT, STRAYED, SUBSET_DTYPE
 
@@ -129,6 +129,16 @@ def test_largest_subset(flow2d, ctx):
     assert u0.shape == (3, 3)
     want = check_subset2(ctx, f0, f1, u0, v0, 15, 33, 15, "97x99, R = 15, N = 961")
     assert counts(want)["converged"] >= 1
+
+
+@pytest.mark.parametrize("R", [10, 11, 12, 13, 15])
+def test_the_large_radii(flow2d, ctx, R):
+    """The radii around every change of the waves per workgroup: four at R = 10, three at 11 and 12 (node = blockIdx.x * 3 + wave),
+    two from 13.  40 x 36: only the inner nodes' subsets lie inside frame 0, the others stray."""
+    f0, f1, u0, v0 = small_specimen()
+    assert u0.shape == (8, 9)
+    want = check_subset2(ctx, f0, f1, u0, v0, 3, 4, R, "40x36 specimen, R = %d" % R)
+    assert (want.state >= 0).sum() >= 1 and counts(want)["strayed"] >= 20
 
 
 def test_several_workgroups(flow2d, ctx):

@@ -143,6 +143,15 @@ def test_refine_from_with_the_largest_subset(flow2d, ctx):
     assert counts(want)["converged"] >= 20 and counts(want)["strayed"] >= 30
 
 
+def test_refine_from_with_three_waves_per_workgroup(flow2d, ctx):
+    """R = 11 > r = 7: 16 960 bytes of LDS per wave, so three waves per workgroup (node = blockIdx.x * 3 + wave); 99 nodes are 33
+    full workgroups."""
+    f0, _, f2, first = affine_steps(96, 80, 7, 8, 7)
+    start = start_of(first, 8)
+    want = check_from(ctx, f0, f2, start, 7, 8, 11, "96x80, R = 11 > r = 7")
+    assert counts(want)["converged"] >= 30 and counts(want)["strayed"] >= 30
+
+
 def test_starts_that_are_not_finite_or_beyond_the_bounds_come_back(flow2d, ctx):
     f0, _, f2, first = affine_steps(50, 41, 3, 5, 3)
     start = [q.copy() for q in start_of(first, 5)]
