@@ -509,6 +509,7 @@ def hip_lib():
         L.flow2d_solve_2d_grad.argtypes = [vp] * 9 + [sz, sz, sz, f, f, f, vp, vp]
         L.flow2d_solve_2d_grad_untiled.argtypes = [vp] * 9 + [sz, sz, sz, f, f, f, vp, vp]
         L.flow2d_solve_2d_log.argtypes = [vp] * 9 + [sz, sz, sz, f, f, f, vp, vp]
+        L.flow2d_log_frame_2d.argtypes = [vp, vp, vp, sz, sz, sz]
         L.flow2d_solver_algorithm_for.argtypes = [i, sz, sz, sz, sz, sz, i]
         L.flow2d_solve_2d_sor.argtypes = [vp] * 9 + [sz, sz, sz, f, f, f, f, i]
         L.flow2d_solve_level.argtypes = [vp] * 11 + [C.POINTER(SolveParams), C.POINTER(i)]
@@ -1638,6 +1639,10 @@ class Context:
               LOG_DERIVATIVES: hip_lib().flow2d_solve_2d_log}[constancy]
         _check(fn(self.handle, f0.ptr, f1.ptr, u.ptr, v.ptr, du.ptr, dv.ptr, phi.ptr, ksi.ptr, w, h, f0.pitch, hx, hy,
                   alpha, tdu.ptr, tdv.ptr), "flow2d_solve_2d*")
+
+    def log_frame(self, src, dst, w, h):
+        """dst = log(src + 1) over w x h as the log-derivative kernels form it (flow2d_log_frame_2d): for checkers"""
+        _check(hip_lib().flow2d_log_frame_2d(self.handle, src.ptr, dst.ptr, w, h, src.pitch), "flow2d_log_frame_2d")
 
     def sor_iteration(self, f0, f1, u, v, du, dv, phi, ksi, w, h, hx, hy, alpha, omega, constancy=GREY):
         _check(hip_lib().flow2d_solve_2d_sor(self.handle, f0.ptr, f1.ptr, u.ptr, v.ptr, du.ptr, dv.ptr, phi.ptr, ksi.ptr,

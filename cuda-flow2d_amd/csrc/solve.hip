@@ -602,6 +602,20 @@ __global__ __launch_bounds__(512) void sor_grad_kernel(const float* __restrict__
     jacobi_update<true>(u, v, du, dv, phi, ksi, n, x, y, w, h, hx, hy, alpha, J11, J22, J12, J13, J23, du, dv, omega);
 }
 
+// ---- log(I + 1) of a frame, as every kernel of the log-derivative term forms it (flow2d_log_frame_2d) ----------
+// Not a step of the flow: it hands a checker the device's own logarithms, so that a CPU restatement of solve_2d_log can
+// be compared bit for bit without its libm in the way.
+__global__ __launch_bounds__(256) void log_frame_kernel(const float* __restrict__ in, float* __restrict__ out, int w, int h,
+                                                        int pitch)
+{
+    const int x = blockIdx.x * kBlockX + threadIdx.x;
+    if (x >= w) return;
+    for (int y = blockIdx.y * kBlockY + threadIdx.y; y < h; y += gridDim.y * kBlockY) {  // (grid.y is capped by the entry)
+        const size_t at = static_cast<size_t>(y) * pitch + x;
+        out[at] = flow2d_math::log1p_frame(in[at]);
+    }
+}
+
 bool solver_planes_ok(const float* const* planes, int count, size_t w, size_t h, size_t pitch_bytes)
 {
     for (int i = 0; i < count; ++i)
@@ -831,6 +845,19 @@ int flow2d_solve_2d_log(flow2d_context* ctx, const float* frame_0, const float* 
 {
     return sweep_entry(ctx, FLOW2D_CONSTANCY_LOG_DERIVATIVES, frame_0, frame_1, flow_u, flow_v, flow_du, flow_dv, phi,
                        ksi, width, height, pitch_bytes, hx, hy, equation_alpha, temp_du, temp_dv);
+}
+
+int flow2d_log_frame_2d(flow2d_context* ctx, const float* in, float* out, size_t width, size_t height, size_t pitch_bytes)
+{
+    FLOW2D_ENTER(ctx);
+    if (!flow2d::plane_args_ok(in, width, height, pitch_bytes) || !flow2d::plane_args_ok(out, width, height, pitch_bytes))
+        return FLOW2D_ERR_INVALID_ARGUMENT;
+    const size_t extent = (height - 1) * pitch_bytes + width * sizeof(float);
+    if (flow2d::ranges_overlap(in, extent, out, extent)) return FLOW2D_ERR_INVALID_ARGUMENT;
+    const dim3 grid(flow2d::div_up(width, kBlockX), std::min(flow2d::div_up(height, kBlockY), 65535u));
+    log_frame_kernel<<<grid, dim3(kBlockX, kBlockY), 0, ctx->stream>>>(in, out, (int)width, (int)height, (int)(pitch_bytes / 4));
+    FLOW2D_CHECK_LAUNCH();
+    return FLOW2D_OK;
 }
 
 int flow2d_solve_2d_grad_untiled(flow2d_context* ctx, const float* frame_0, const float* frame_1, const float* flow_u,

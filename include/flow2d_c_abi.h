@@ -1579,6 +1579,14 @@ FLOW2D_API int flow2d_solve_2d_log(flow2d_context* ctx, const float* frame_0, co
                                    size_t height, size_t pitch_bytes, float hx, float hy, float equation_alpha,
                                    float* temp_du, float* temp_dv);
 
+/* out[y][x] = log(in[y][x] + 1.0f) over width x height, formed by the function every kernel of the log-derivative term
+ * calls (the device library's logf).  Not a step of the flow: it hands a checker the device's own logarithms, so that a
+ * CPU restatement of solve_2d_log can be held to the kernels bit for bit (a CPU's libm differs from the device library
+ * in the last place).  One plane, on the context's stream; `in` and `out` share the pitch and must not overlap; nothing
+ * outside width x height is written.  Not batch-aware. */
+FLOW2D_API int flow2d_log_frame_2d(flow2d_context* ctx, const float* in, float* out, size_t width, size_t height,
+                                   size_t pitch_bytes);
+
 /* Opt-in red-black successive over-relaxation: ONE iteration = the pixels with even (x + y), then the odd
  * ones, relaxed in place on flow_du / flow_dv with factor omega in (0, 2).  NOT a reference kernel: the
  * reference relaxes with Jacobi sweeps, so this mode has no parity with it at equal iteration

@@ -16,7 +16,9 @@
  *       bit for bit (tests/test_oracle.py::test_ref_golden_*), NaN / signed-zero median windows included.
  *       Two documented exceptions: solve_2d_grad / solve_2d_log where the image edge falls inside a 16x8 block
  *       (the reference reads unwritten shared memory there; see oracle_solve_2d_grad), and solve_2d_log's logf
- *       (device library there, libm here: last-place differences).
+ *       (device library there, libm here: last-place differences) -- unless the logarithm is handed in: with a GPU's
+ *       own log(I + 1) behind oracle_set_log_source this file reproduces solve_2d_log bit for bit as well
+ *       (tests/golden/device_log_golden.npz on the CPU, oracle.device_logs on the GPU box).
  *   (2) its host code: GetMaxWarpLevel, ComputeGaussianKernel (and, for the product's host layer, Data2D IO,
  *       the colour-wheel writers, Settings, OperationParameters) are compiled from where they lie into
  *       oracle/_ref/ref_host_probe and run in the build container; outputs in tests/golden/ref_host_golden.npz.
@@ -48,6 +50,7 @@
  * -k -> k, n-1+k -> n-1-k   (solve_2d.cu:75-76,88-89,101-102; median_2d.cu:107-108,115-116,123-124) */
 static inline long mirror_index(long i, long n)
 {
+    if (n == 1) return 0; /* an axis of one pixel has nothing to reflect onto (the reference's index leaves the plane there) */
     if (i < 0) i = -i;
     if (i >= n) i = 2 * n - i - 2;
     return i;
@@ -370,10 +373,39 @@ static void log_neighbours(long i, long n, long tile, long* lo, long* hi)
     *hi = (i % tile == tile - 1) ? i : mirror_index(i + 1, n);
 }
 
+/* ------------------------------------------------------------------------------------------
+ * Where solve_2d_log's log(I + 1.0f) comes from.  Default: logf of the CPU's libm, which is within an ulp of, but not
+ * bit-identical to, a GPU's device library.  oracle_set_log_source(fn, user) makes every log plane of this file come
+ * from fn(in, out, w, h, pitch, user) instead (it fills out[y * pitch + x] for x < w, y < h); fn == NULL restores libm.
+ * fn is called on the calling thread, outside any OpenMP region.  This is the ONLY logarithm of the file: a test that
+ * hands in a GPU's own logarithms compares everything else bit for bit.
+ * ---------------------------------------------------------------------------------------- */
+typedef void (*oracle_log_fn)(const float* in, float* out, size_t w, size_t h, size_t pitch, void* user);
+static oracle_log_fn log_source = NULL;
+static void* log_source_user = NULL;
+
+ORACLE_API void oracle_set_log_source(oracle_log_fn fn, void* user)
+{
+    log_source = fn;
+    log_source_user = fn ? user : NULL;
+}
+
+/* out = log(in + 1.0f) over w x h (solve_2d.cu:509-524) */
+static void log_plane(const float* in, float* out, size_t w, size_t h, size_t pitch)
+{
+    if (log_source) {
+        log_source(in, out, w, h, pitch, log_source_user);
+        return;
+    }
+#pragma omp parallel for schedule(static)
+    for (long y = 0; y < (long)h; ++y)
+        for (long x = 0; x < (long)w; ++x) out[y * pitch + x] = logf(in[y * pitch + x] + 1.0f);
+}
+
 /* mode 0: Gradient over true neighbours (not a reference mode); 1: solve_2d_grad (:683-952);
  * 2: solve_2d_log (:391-669) -- as 1 on log(I + 1.0f), with the block-edge replication applied to the frames,
  * u, v, du, dv, phi and ksi as well.  lg0 / lg1, when non-NULL, are precomputed log(I + 1) planes of frame_0 /
- * frame_1 (same pitch); NULL -> logf from libm, which is within an ulp of, but not bit-identical to, a GPU's. */
+ * frame_1 (same pitch); NULL -> formed here by log_plane (libm, or the source set with oracle_set_log_source). */
 static void solve_2d_grad_any(const float* f0, const float* f1, const float* u, const float* v, const float* du,
                               const float* dv, const float* phi, const float* ksi, size_t w, size_t h, size_t pitch,
                               float hx, float hy, float alpha, float* tdu, float* tdv, int mode, const float* lg0,
@@ -391,12 +423,8 @@ static void solve_2d_grad_any(const float* f0, const float* f1, const float* u, 
     if (logm && !(lg0 && lg1)) {
         l0 = (float*)malloc(sizeof(float) * pitch * h);
         l1 = (float*)malloc(sizeof(float) * pitch * h);
-#pragma omp parallel for schedule(static)
-        for (long y = 0; y < (long)h; ++y)
-            for (long x = 0; x < (long)w; ++x) {
-                l0[y * pitch + x] = logf(f0[y * pitch + x] + 1.0f);
-                l1[y * pitch + x] = logf(f1[y * pitch + x] + 1.0f);
-            }
+        log_plane(f0, l0, w, h, pitch);
+        log_plane(f1, l1, w, h, pitch);
         lg0 = l0;
         lg1 = l1;
     }
@@ -660,6 +688,16 @@ ORACLE_API void oracle_solve_level(const float* f0, const float* f1, const float
         memset(*du + y * pitch, 0, w * sizeof(float));
         memset(*dv + y * pitch, 0, w * sizeof(float));
     }
+    /* LogDerivatives: the frames do not change inside a level, so log(I + 1) is formed once and every sweep goes through
+     * oracle_solve_2d_log_planes -- the arithmetic of oracle_solve_2d_log, one call of the log source per frame and level */
+    float* lg0 = NULL;
+    float* lg1 = NULL;
+    if (constancy == 3 && outer > 0 && inner > 0) {
+        lg0 = (float*)malloc(sizeof(float) * pitch * h);
+        lg1 = (float*)malloc(sizeof(float) * pitch * h);
+        log_plane(f0, lg0, w, h, pitch);
+        log_plane(f1, lg1, w, h, pitch);
+    }
     for (size_t i = 0; i < outer; ++i) {
         oracle_compute_phi_ksi(f0, f1, u, v, *du, *dv, w, h, pitch, hx, hy, e_smooth, e_data, phi, ksi);
         for (size_t j = 0; j < inner; ++j) {
@@ -668,13 +706,15 @@ ORACLE_API void oracle_solve_level(const float* f0, const float* f1, const float
             else if (constancy == 2)
                 oracle_solve_2d_grad_untiled(f0, f1, u, v, *du, *dv, phi, ksi, w, h, pitch, hx, hy, alpha, *tdu, *tdv);
             else if (constancy == 3)
-                oracle_solve_2d_log(f0, f1, u, v, *du, *dv, phi, ksi, w, h, pitch, hx, hy, alpha, *tdu, *tdv);
+                oracle_solve_2d_log_planes(lg0, lg1, u, v, *du, *dv, phi, ksi, w, h, pitch, hx, hy, alpha, *tdu, *tdv);
             else
                 oracle_solve_2d(f0, f1, u, v, *du, *dv, phi, ksi, w, h, pitch, hx, hy, alpha, *tdu, *tdv);
             float* t = *du; *du = *tdu; *tdu = t;
             t = *dv; *dv = *tdv; *tdv = t;
         }
     }
+    free(lg0);
+    free(lg1);
 }
 
 /* ------------------------------------------------------------------------------------------

@@ -219,6 +219,80 @@ def solve_sweep(f0, f1, u, v, du, dv, phi, ksi, hx, hy, alpha, gradient=False):
     return r_du.astype(F), r_dv.astype(F)
 
 
+def _log_block_neighbours(n, tile):
+    """solve_2d.cu:428-500: which pixel a thread of solve_2d_log finds beside it in shared memory, per axis.  The halo
+    slices are loaded from `global - 1 + 1` and `global + 1 - 1` (:448,462,476,490), i.e. from the block's own edge
+    pixel, so the first / last pixel of a 16 (8) block sees ITSELF on that side.  Inside a block the neighbour is the
+    thread next door; when that thread lies past the image it has loaded the reflected pixel 2n - i - 2 (:433-434),
+    which for i = n is n - 2.  (An axis of one pixel: that index leaves the plane; own value here.)"""
+    i = np.arange(n)
+    lo = np.where(i % tile == 0, i, i - 1)
+    beyond = np.maximum(2 * n - (i + 1) - 2, 0)
+    hi = np.where(i % tile == tile - 1, i, np.where(i + 1 < n, i + 1, beyond))
+    return lo, hi
+
+
+def solve_sweep_log(lg0, lg1, u, v, du, dv, phi, ksi, hx, hy, alpha):
+    """solve_2d.cu:391-669 (solve_2d_log): one Jacobi sweep on the logarithmic derivatives, given lg = log(frame + 1.0f).
+    Blocks of 16 x 8 threads anchored at the image origin (cuda_operation_solve_2d.cpp:164,234-235).  Every plane the
+    kernel stages in shared memory -- both frames, u, v, du, dv, phi (ksi is only read at the pixel) -- is read through
+    _log_block_neighbours.  fx, fy, ft are then differentiated inside the block with the block's own edge value written
+    into their halo (:531-557); where the image ends inside a block, the slot past the last pixel is one no thread
+    wrote (the threads past the image skip :505-558): defined here as the pixel's own value, the block-edge rule."""
+    hx, hy, alpha = F(hx), F(hy), F(alpha)
+    h, w = lg0.shape
+    xl, xr = _log_block_neighbours(w, 16)
+    yu, yd = _log_block_neighbours(h, 8)
+    left = lambda a: a[:, xl]
+    right = lambda a: a[:, xr]
+    above = lambda a: a[yu, :]
+    below = lambda a: a[yd, :]
+    # :508-524
+    fx = (right(lg0) - left(lg0) + right(lg1) - left(lg1)) / (F(4.0) * hx)
+    fy = (below(lg0) - above(lg0) + below(lg1) - above(lg1)) / (F(4.0) * hy)
+    ft = lg1 - lg0
+    # :531-557 and the unwritten slot at the image edge
+    xs, ys = np.arange(w), np.arange(h)
+    xa = np.where(xs % 16 == 0, xs, xs - 1)
+    xb = np.where((xs % 16 == 15) | (xs == w - 1), xs, xs + 1)
+    ya = np.where(ys % 8 == 0, ys, ys - 1)
+    yb = np.where((ys % 8 == 7) | (ys == h - 1), ys, ys + 1)
+    # :584-600
+    hx_1 = F(1.0 / (2.0 * float(hx)))
+    hy_1 = F(1.0 / (2.0 * float(hy)))
+    fxx = (fx[:, xb] - fx[:, xa]) * hx_1
+    fxy = (fx[yb, :] - fx[ya, :]) * hy_1
+    fyy = (fy[yb, :] - fy[ya, :]) * hy_1
+    fxt = (ft[:, xb] - ft[:, xa]) * hx_1
+    fyt = (ft[yb, :] - ft[ya, :]) * hy_1
+    J11 = fxx * fxx + fxy * fxy
+    J22 = fxy * fxy + fyy * fyy
+    J12 = fxx * fxy + fxy * fyy
+    J13 = fxx * fxt + fxy * fyt
+    J23 = fxy * fxt + fyy * fyt
+    # :606-640
+    hx_2 = alpha / (hx * hx)
+    hy_2 = alpha / (hy * hy)
+    xp = (xs[None, :] < w - 1).astype(F) * hx_2 * np.ones((h, 1), F)
+    xm = (xs[None, :] > 0).astype(F) * hx_2 * np.ones((h, 1), F)
+    yp = (ys[:, None] < h - 1).astype(F) * hy_2 * np.ones((1, w), F)
+    ym = (ys[:, None] > 0).astype(F) * hy_2 * np.ones((1, w), F)
+    two = F(2.0)
+    phi_xp = (right(phi) + phi) / two
+    phi_xm = (left(phi) + phi) / two
+    phi_yp = (below(phi) + phi) / two
+    phi_ym = (above(phi) + phi) / two
+    sumH = xp * phi_xp + xm * phi_xm + yp * phi_yp + ym * phi_ym
+    sumU = (phi_xp * xp * (right(u) + right(du) - u) + phi_xm * xm * (left(u) + left(du) - u)
+            + phi_yp * yp * (below(u) + below(du) - u) + phi_ym * ym * (above(u) + above(du) - u))
+    sumV = (phi_xp * xp * (right(v) + right(dv) - v) + phi_xm * xm * (left(v) + left(dv) - v)
+            + phi_yp * yp * (below(v) + below(dv) - v) + phi_ym * ym * (above(v) + above(dv) - v))
+    with np.errstate(all="ignore"):
+        r_du = (ksi * (-J13 - J12 * dv) + sumU) / (ksi * J11 + sumH)
+        r_dv = (ksi * (-J23 - J12 * r_du) + sumV) / (ksi * J22 + sumH)
+    return r_du.astype(F), r_dv.astype(F)
+
+
 def median(img, radius):
     """median_2d.cu:87-299: r x r window, mirror borders, element r*r/2 of the sorted window."""
     r2 = radius // 2
@@ -230,8 +304,10 @@ def median(img, radius):
 
 
 def compute_flow(frame_0, frame_1, levels, scale, outer, inner, alpha, e_smooth, e_data, median_radius, sigma,
-                 gradient=False):
-    """optical_flow_2d.cpp:142-569 + cuda_operation_solve_2d.cpp:229-300 (tight images, no containers)."""
+                 gradient=False, log=None):
+    """optical_flow_2d.cpp:142-569 + cuda_operation_solve_2d.cpp:229-300 (tight images, no containers).
+    log: a callable plane -> log(plane + 1.0f) in float32 selects DataConstancy::LogDerivatives (solve_2d_log,
+    cuda_operation_solve_2d.cpp:75-77); it is applied to the level's two frames, once per level."""
     f0 = np.asarray(frame_0, F)
     f1 = np.asarray(frame_1, F)
     H, W = f0.shape
@@ -251,10 +327,15 @@ def compute_flow(frame_0, frame_1, levels, scale, outer, inner, alpha, e_smooth,
             u, v = resample(u, cw, ch), resample(v, cw, ch)
         g1 = registration(g0, g1, u, v, hx, hy)
         du, dv = np.zeros((ch, cw), F), np.zeros((ch, cw), F)
+        if log is not None:
+            lg0, lg1 = np.asarray(log(g0), F), np.asarray(log(g1), F)
         for _ in range(outer):
             phi, ksi = compute_phi_ksi(g0, g1, u, v, du, dv, hx, hy, e_smooth, e_data)
             for _ in range(inner):
-                du, dv = solve_sweep(g0, g1, u, v, du, dv, phi, ksi, hx, hy, alpha, gradient)
+                if log is not None:
+                    du, dv = solve_sweep_log(lg0, lg1, u, v, du, dv, phi, ksi, hx, hy, alpha)
+                else:
+                    du, dv = solve_sweep(g0, g1, u, v, du, dv, phi, ksi, hx, hy, alpha, gradient)
         u, v = u + du, v + dv
         if median_radius != 1:
             r = median_radius - 1 if median_radius % 2 == 0 else median_radius

@@ -8,6 +8,7 @@ its own host code run in the build container: tests/golden/ref_*_golden.npz).
 Planes are C-contiguous float32 arrays of shape (container_h, pitch); a level occupies the
 top-left w x h corner, like the reference's pitched containers.
 """
+import contextlib
 import ctypes as C
 import os
 import subprocess
@@ -46,6 +47,7 @@ class FlowParams(C.Structure):
 
 
 DUMP_FN = C.CFUNCTYPE(None, C.c_char_p, C.c_int, C.POINTER(C.c_float), C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p)
+LOG_FN = C.CFUNCTYPE(None, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p)
 
 
 def usable_cpus():
@@ -97,6 +99,8 @@ def lib():
         L.oracle_solve_2d_grad_untiled.argtypes = [fp] * 8 + [sz, sz, sz, f, f, f, fp, fp]
         L.oracle_solve_2d_log.argtypes = [fp] * 8 + [sz, sz, sz, f, f, f, fp, fp]
         L.oracle_solve_2d_log_planes.argtypes = [fp] * 8 + [sz, sz, sz, f, f, f, fp, fp]
+        L.oracle_set_log_source.restype = None
+        L.oracle_set_log_source.argtypes = [LOG_FN, C.c_void_p]
         L.oracle_solve_2d_sor.argtypes = [fp] * 8 + [sz, sz, sz, f, f, f, f, C.c_int]
         L.oracle_solve_level_sor.argtypes = [fp] * 8 + [sz, sz, sz, sz, f, f, f, f, f, sz, sz, C.c_int, f]
         L.oracle_add_2d.argtypes = [fp, fp, sz, sz, sz]
@@ -223,6 +227,52 @@ def solve_sweep_log_planes(lg0, lg1, u, v, du, dv, phi, ksi, w, h, hx, hy, alpha
     lib().oracle_solve_2d_log_planes(_p(lg0), _p(lg1), _p(u), _p(v), _p(du), _p(dv), _p(phi), _p(ksi), w, h,
                                      _pitch(lg0), hx, hy, alpha, _p(tdu), _p(tdv))
     return tdu, tdv
+
+
+@contextlib.contextmanager
+def log_source(fn):
+    """Inside the block every log(I + 1) plane of the oracle's LogDerivatives term (sweep, level, compute_flow) comes from
+    fn(plane[h, w] float32) -> float32 [h, w] instead of the CPU's libm (oracle_set_log_source); libm is restored on exit,
+    and an exception fn raised inside the C call is raised again there."""
+    failure = []
+
+    def _cb(src, dst, w, h, pitch, _user):
+        try:
+            n = (h - 1) * pitch + w
+            view = lambda p: np.lib.stride_tricks.as_strided(np.ctypeslib.as_array(p, shape=(n,)), (h, w), (pitch * 4, 4))
+            out = np.asarray(fn(np.ascontiguousarray(view(src))), np.float32)
+            assert out.shape == (h, w), "the log source returned shape %r for a %d x %d plane" % (out.shape, w, h)
+            view(dst)[...] = out
+        except BaseException as e:  # (ctypes would only print it)
+            failure.append(e)
+            view(dst)[...] = np.nan
+
+    cb = LOG_FN(_cb)
+    lib().oracle_set_log_source(cb, None)
+    try:
+        yield
+    finally:
+        lib().oracle_set_log_source(C.cast(None, LOG_FN), None)
+    if failure:
+        raise failure[0]
+
+
+def device_logs(ctx):
+    """`with oracle.device_logs(ctx):` -- the oracle's log(I + 1) planes come from the device behind `ctx` (a product Context:
+    upload, Context.log_frame, download), i.e. from the function the HIP kernels of the log-derivative term call.  What is left
+    of a comparison with those kernels is then the oracle's own arithmetic and neighbour rule: bit for bit."""
+    def fn(plane):
+        h, w = plane.shape
+        src, dst = ctx.plane(w, h, plane), ctx.plane(w, h)
+        try:
+            ctx.log_frame(src, dst, w, h)
+            return dst.download(w, h)
+        finally:
+            for p in (src, dst):
+                p.free()
+                ctx._planes.remove(p)
+
+    return log_source(fn)
 
 
 def sor_iteration(f0, f1, u, v, du, dv, phi, ksi, w, h, hx, hy, alpha, omega, constancy=GREY):

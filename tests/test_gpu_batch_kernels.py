@@ -26,11 +26,12 @@ Which test holds which entry of include/flow2d_c_abi.h (every FLOW2D_API functio
   flow2d_solve_2d_grad, flow2d_solve_2d_grad_untiled,
   flow2d_solve_2d_sor                                    test_solver_pieces
   flow2d_solve_2d_log                                    test_solve_2d_log_against_the_reference_kernel (levels on the 16 x 8
-                                                         grid), test_solve_2d_log_batch_equals_lone_calls (off it: a
-                                                         consistency check of product against product, not a correctness one)
+                                                         grid), test_solve_2d_log_batch_equals_lone_calls (off it: the lone
+                                                         call against the oracle fed the device's logarithms, the batch
+                                                         against the lone call)
   flow2d_solve_level                                     test_solve_level, test_solve_level_auto_leaves_the_tiles_in_a_group,
                                                          test_solve_level_log_batch_equals_lone_calls (the LogDerivatives term:
-                                                         product against product, as for flow2d_solve_2d_log)
+                                                         as for flow2d_solve_2d_log)
   flow2d_memset_2d, flow2d_copy_d2d                      test_memset_2d, test_copy_d2d
   flow2d_consistency_2d, flow2d_interpolate_2d,
   flow2d_flow_error_2d                                   test_newest_entries_padded_strides (contiguous strides: their own files)
@@ -427,9 +428,10 @@ def test_solve_2d_log_against_the_reference_kernel(ctx, flow2d, oracle, RK, w, h
 @pytest.mark.parametrize("count,kind", [(2, "rows"), (3, "bytes"), (5, "contiguous")])
 @pytest.mark.parametrize("w,h,cw,ch", SIZES[:3])
 def test_solve_2d_log_batch_equals_lone_calls(ctx, flow2d, oracle, w, h, cw, ch, count, kind):
-    """Off the reference's 16 x 8 grid nothing checks solve_2d_log bit for bit (the reference's kernel reads a shared-memory
-    slot no thread wrote there).  A CONSISTENCY check, not a correctness one: instance b of the batched call against the
-    product's own unbatched call on instance b's planes alone, exactly."""
+    """Off the reference's 16 x 8 grid the reference's kernel is no checker (it reads a shared-memory slot no thread wrote
+    there); the oracle is, once its log(I + 1) comes from the device (oracle.device_logs): the product's unbatched call on
+    instance b's planes alone equals the oracle's sweep of instance b word for word, and instance b of the batched call
+    equals that unbatched call, exactly."""
     stride = stride_of(kind, pitch_of(cw), ch)
     per = fields(oracle, w, h, count, 19)
     coeff = [oracle.compute_phi_ksi(*q, w, h, HX, HY, 0.001, 0.001) for q in zip(*per)]
@@ -441,6 +443,10 @@ def test_solve_2d_log_batch_equals_lone_calls(ctx, flow2d, oracle, w, h, cw, ch,
         ctx.solve_sweep(*one, w, h, HX, HY, 35.0, o_du, o_dv, flow2d.LOG_DERIVATIVES)
         ctx.synchronize()
         lone.append([o.rects(o.download())[0, :h, :w].view(F32).copy() for o in (o_du, o_dv)])
+        with oracle.device_logs(ctx):
+            want = oracle.solve_sweep(*[np.ascontiguousarray(x[b], F32) for x in per], w, h, HX, HY, 35.0, oracle.LOG_DERIVATIVES)
+        for got, o in zip(lone[b], want):
+            assert np.array_equal(got.view(np.uint32), o.view(np.uint32)), ("solve_2d_log against the oracle", b)
     d = [t.fill(x) for t, x in zip(talls(ctx, cw, ch, count, stride, 8), per)]
     tdu, tdv = talls(ctx, cw, ch, count, stride, 2)
     drive(ctx, count, stride, lambda: ctx.solve_sweep(*d, w, h, HX, HY, 35.0, tdu, tdv, flow2d.LOG_DERIVATIVES),
@@ -576,11 +582,10 @@ _LONE_LOG_LEVELS = {}  # (algorithm, outer, inner, instance) -> (du, dv, result_
 @pytest.mark.parametrize("outer,inner", ITERATIONS[:2])
 @pytest.mark.parametrize("algorithm", [1, 2, 3, 4, 0])
 def test_solve_level_log_batch_equals_lone_calls(ctx, flow2d, oracle, algorithm, outer, inner, count, kind, omega):
-    """The level loop with the LogDerivatives term under a batch.  The oracle takes its log from the CPU's libm, so like
-    test_solve_2d_log_batch_equals_lone_calls this is a CONSISTENCY check (lone calls are held to the reference's own kernel
-    by tests/test_gpu_reference.py::test_solve_level): every instance of the group's call is the lone call on that instance's
-    planes, bit for bit, *result_in_temp is the lone call's, and nothing outside the level rectangles is written
-    (check_level).  The term has neither LDS tiles nor a red-black form: those requests are refused with
+    """The level loop with the LogDerivatives term under a batch.  Every lone call equals the oracle's level word for word
+    (the oracle's log(I + 1) taken from the device: oracle.device_logs), every instance of the group's call is the lone call
+    on that instance's planes, bit for bit, *result_in_temp is the lone call's, and nothing outside the level rectangles is
+    written (check_level).  The term has neither LDS tiles nor a red-black form: those requests are refused with
     FLOW2D_ERR_UNSUPPORTED and leave the context in batch mode."""
     w, h, cw, ch = LEVEL_SIZES[1]
     stride, lone_stride = stride_of(kind, pitch_of(cw), ch), pitch_of(cw) * ch
@@ -611,6 +616,11 @@ def test_solve_level_log_batch_equals_lone_calls(ctx, flow2d, oracle, algorithm,
             ctx.synchronize()
             assert pair in ((o[0], o[1]), (o[4], o[5]))
             _LONE_LOG_LEVELS[algorithm, outer, inner, b] = tuple(t.rects(t.download())[0, :h, :w].view(F32).copy() for t in pair) + (pair[0] is o[4],)
+            with oracle.device_logs(ctx):  # the lone call itself: the oracle's words, its log(I + 1) taken from the device
+                want = oracle.solve_level(*[in_container(x[b], cw, ch) for x in (f0, f1, u, v)], w, h, HX, HY, 3.5, 0.001, 0.001, outer,
+                                          inner, oracle.LOG_DERIVATIVES)[:2]
+            for got, o_ in zip(_LONE_LOG_LEVELS[algorithm, outer, inner, b][:2], want):
+                assert np.array_equal(got.view(U32), o_[:h, :w].view(U32)), what + ": lone call of instance %d against the oracle" % b
     lone = [_LONE_LOG_LEVELS[algorithm, outer, inner, b] for b in range(count)]
     with ctx.set_batch(count, stride):
         pair = solve(d, written)

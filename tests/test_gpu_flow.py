@@ -346,8 +346,8 @@ def test_lock_step_groups_match_single_pairs(flow2d, oracle, constancy, sigma, m
     LogDerivatives (per-instance launches of the single-workgroup kernel), with and without the pre-blur."""
     p = (4, 0.5, 3, 5, 35.0, 0.001, 0.001, median, sigma)
     pairs = [oracle.synthetic_pair(w, h, 1.5 * np.cos(k), -1.0 + 0.5 * k, seed=k, noise=True) for k in range(2 * G)]
-    if constancy == 3:  # log(I + 1): the CPU libm and the device library differ in the last place; compare with the
-        want = None     # product's own single-pair runs instead (those are pinned to the reference's kernel elsewhere)
+    if constancy == 3:  # log(I + 1): the CPU libm and the device library differ in the last place; the product's own
+        want = None     # single-pair runs are compared with the oracle fed the device's logarithms, the groups with them
     else:
         want = [oracle.compute_flow(f0, f1, *p, constancy)[:2] for f0, f1 in pairs]
     c = flow2d.Context(0)
@@ -362,6 +362,10 @@ def test_lock_step_groups_match_single_pairs(flow2d, oracle, constancy, sigma, m
                 single.compute_flow_device(*[q.ptr for q in pl], single.params(*p))
                 c.synchronize()
                 want.append((pl[2].download(), pl[3].download()))
+                with oracle.device_logs(c):
+                    ou, ov, _ = oracle.compute_flow(f0, f1, *p, constancy)
+                assert np.array_equal(want[-1][0].view(np.uint32), ou.view(np.uint32)), "single pair against the oracle: u"
+                assert np.array_equal(want[-1][1].view(np.uint32), ov.view(np.uint32)), "single pair against the oracle: v"
         groups = []
         for g in range(2):
             mine = pairs[g * G:(g + 1) * G]
@@ -698,13 +702,17 @@ def test_groups_formed_from_scattered_planes(flow2d, oracle, constancy, sigma):
         us = [c.plane(w, h) for _ in pairs]
         vs = [c.plane(w, h) for _ in pairs]
         c.synchronize()
-        if constancy == 3:  # the CPU's logf differs from the device's in the last place: Log pairs against single-pair runs
-            single = flow2d.OpticalFlow(w, h, constancy, ctx=c)
+        if constancy == 3:  # the CPU's logf differs from the device's in the last place: Log pairs against single-pair runs,
+            single = flow2d.OpticalFlow(w, h, constancy, ctx=c)  # and those against the oracle fed the device's logarithms
             want = []
             for k in range(n):
                 single.compute_flow_device(f0s[k].ptr, f1s[k].ptr, us[k].ptr, vs[k].ptr, single.params(*p))
                 c.synchronize()
                 want.append((us[k].download(), vs[k].download()))
+                with oracle.device_logs(c):
+                    ou, ov, _ = oracle.compute_flow(*pairs[k], *p, constancy)
+                assert np.array_equal(want[k][0].view(np.uint32), ou.view(np.uint32)), ("single pair against the oracle: u", k)
+                assert np.array_equal(want[k][1].view(np.uint32), ov.view(np.uint32)), ("single pair against the oracle: v", k)
             single.close()
         else:
             want = [oracle.compute_flow(f0, f1, *p, constancy)[:2] for f0, f1 in pairs]

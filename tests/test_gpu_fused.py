@@ -262,7 +262,7 @@ def test_zero_regularisers_match_the_per_sweep_kernels(ctx, flow2d, oracle, buil
     build.served(2)  # (the strips' two outer iterations; the per-sweep kernels have one build)
 
 
-@pytest.mark.parametrize("constancy", [0, 1, 2])  # (solve_2d_log with such spacings: test_gpu_reference.py, against the reference's kernel)
+@pytest.mark.parametrize("constancy", [0, 1, 2])  # (solve_2d_log, this and every other guard: test_gpu_log_derivatives.py::test_strip_guard_*)
 @pytest.mark.parametrize("hx,hy", [(1.1, 0.9), (3.7, 1.0), (0.013, 0.02)])
 def test_spacings_that_are_no_powers_of_two(ctx, oracle, build, hx, hy, constancy):
     """The six divisions by 2h and 4h of a row step go through the three-step division with the host's RN(1 / (2h)),

@@ -3,6 +3,8 @@
 Each case places the level in the top-left corner of a larger container, like the reference's
 full-resolution pitched planes, and uses sizes that are not tile multiples.
 """
+import contextlib
+
 import numpy as np
 import pytest
 
@@ -252,17 +254,28 @@ def test_phi_ksi_and_sweeps(ctx, flow2d, oracle, w, h, cw, ch, hx, hy):
         odu, odv = oracle.solve_sweep(f0, f1, u, v, du, dv, ophi, oksi, w, h, hx, hy, 35.0, constancy)
         assert np.array_equal(tdu.download(w, h), odu), "du constancy %d" % constancy
         assert np.array_equal(tdv.download(w, h), odv), "dv constancy %d" % constancy
+    # solve_2d_log: the oracle's log(I + 1) from the device, so that its words are the kernel's; two sweeps in a row
+    tdu.fill_bytes(0x7f), tdv.fill_bytes(0x7f)
+    ctx.solve_sweep(*d, phi, ksi, w, h, hx, hy, 35.0, tdu, tdv, flow2d.LOG_DERIVATIVES)
+    ctx.solve_sweep(d[0], d[1], d[2], d[3], tdu, tdv, phi, ksi, w, h, hx, hy, 35.0, d[4], d[5], flow2d.LOG_DERIVATIVES)
+    with oracle.device_logs(ctx):
+        odu, odv = oracle.solve_sweep(f0, f1, u, v, du, dv, ophi, oksi, w, h, hx, hy, 35.0, oracle.LOG_DERIVATIVES)
+        odu2, odv2 = oracle.solve_sweep(f0, f1, u, v, odu, odv, ophi, oksi, w, h, hx, hy, 35.0, oracle.LOG_DERIVATIVES)
+    for got, want, name in ((tdu, odu, "du"), (tdv, odv, "dv"), (d[4], odu2, "du, second sweep"), (d[5], odv2, "dv, second sweep")):
+        assert np.array_equal(got.download(w, h).view(np.uint32), want.view(np.uint32)), name + " constancy 3"
+    full = tdu.download()
+    assert np.all(full[h:, :].view(np.uint32) == 0x7f7f7f7f) and np.all(full[:h, w:].view(np.uint32) == 0x7f7f7f7f)
 
 
 @pytest.mark.parametrize("w,h,cw,ch,hx,hy", [(4096, 2050, 4096, 2050, 1.0, 1.0), (2777, 3100, 2816, 3104, 1.25, 1.1),
                                               (16000, 530, 16000, 530, 7.3, 5.5), (1000, 300, 1024, 300, 1.0, 1.0)])
 def test_sweep_streaming_strips(ctx, flow2d, oracle, w, h, cw, ch, hx, hy):
-    """solve_2d and solve_2d_grad at level sizes that take the streaming form (8 Mpixel and more: strips of 64 aligned columns
+    """solve_2d, solve_2d_grad and solve_2d_log at level sizes that take the streaming form (8 Mpixel and more: strips of 64 aligned columns
     walking down the level, windows in registers, lane shifts for the x neighbours with the strip's halo columns from two-lane
     loads, mirrored halo loads instead of border selects): partial last strips, strip heights that do not divide the level,
     levels inside larger containers, spacings that are no powers of two -- bit-identical to the oracle's sweep, two sweeps in
-    a row (the second reads what the first wrote), then a red-black SOR iteration in place (its half-sweeps stream too).  (The
-    last size stays on the tile form: the same checks.)"""
+    a row (the second reads what the first wrote), then a red-black SOR iteration in place (its half-sweeps stream too;
+    solve_2d_log has none).  (The last size stays on the tile form: the same checks.)"""
     f0, f1, u, v, du, dv = level_fields(oracle, w, h, 71)
     d = [up(ctx, a, cw, ch, 3.0) for a in (f0, f1, u, v, du, dv)]
     phi, ksi, tdu, tdv = (ctx.plane(cw, ch).fill_bytes(0x7f) for _ in range(4))
@@ -272,19 +285,22 @@ def test_sweep_streaming_strips(ctx, flow2d, oracle, w, h, cw, ch, hx, hy):
         d[4].upload(in_container(du, cw, ch, 3.0)), d[5].upload(in_container(dv, cw, ch, 3.0))
         tdu.fill_bytes(0x7f), tdv.fill_bytes(0x7f)
         ctx.solve_sweep(*d, phi, ksi, w, h, hx, hy, 35.0, tdu, tdv, constancy)
-        odu, odv = oracle.solve_sweep(f0, f1, u, v, du, dv, ophi, oksi, w, h, hx, hy, 35.0, constancy)
-        if constancy == flow2d.LOG_DERIVATIVES:
-            # log(I + 1) comes from the device library here and from the CPU's libm in the oracle (last-place differences);
-            # the bit-for-bit check of the streaming log form is against the reference's own kernel (test_gpu_reference.py)
-            assert float(np.abs(tdu.download(w, h) - odu).max()) < 1e-5 and float(np.abs(tdv.download(w, h) - odv).max()) < 1e-5
-            continue
-        assert np.array_equal(tdu.download(w, h), odu) and np.array_equal(tdv.download(w, h), odv), constancy
+        # solve_2d_log: log(I + 1) comes from the device library in the kernels and from the CPU's libm in the oracle (last-place
+        # differences), so the oracle is handed the device's logarithms of the frames: then its words are the kernel's
+        logs = oracle.device_logs(ctx) if constancy == flow2d.LOG_DERIVATIVES else contextlib.nullcontext()
+        with logs:
+            odu, odv = oracle.solve_sweep(f0, f1, u, v, du, dv, ophi, oksi, w, h, hx, hy, 35.0, constancy)
+            odu2, odv2 = oracle.solve_sweep(f0, f1, u, v, odu, odv, ophi, oksi, w, h, hx, hy, 35.0, constancy)
+        assert np.array_equal(tdu.download(w, h).view(np.uint32), odu.view(np.uint32)), constancy
+        assert np.array_equal(tdv.download(w, h).view(np.uint32), odv.view(np.uint32)), constancy
         # nothing outside the level is written
         full = tdu.download()
         assert np.all(full[h:, :].view(np.uint32) == 0x7f7f7f7f) and np.all(full[:h, w:].view(np.uint32) == 0x7f7f7f7f)
         ctx.solve_sweep(d[0], d[1], d[2], d[3], tdu, tdv, phi, ksi, w, h, hx, hy, 35.0, d[4], d[5], constancy)
-        odu2, odv2 = oracle.solve_sweep(f0, f1, u, v, odu, odv, ophi, oksi, w, h, hx, hy, 35.0, constancy)
-        assert np.array_equal(d[4].download(w, h), odu2) and np.array_equal(d[5].download(w, h), odv2), constancy
+        assert np.array_equal(d[4].download(w, h).view(np.uint32), odu2.view(np.uint32)), constancy
+        assert np.array_equal(d[5].download(w, h).view(np.uint32), odv2.view(np.uint32)), constancy
+        if constancy == flow2d.LOG_DERIVATIVES:
+            continue  # (solve_2d_log has no red-black form)
         # opt-in red-black SOR, in place on what the two sweeps left
         ctx.sor_iteration(*d, phi, ksi, w, h, hx, hy, 35.0, 1.6, constancy)
         odu3, odv3 = oracle.sor_iteration(f0, f1, u, v, odu2, odv2, ophi, oksi, w, h, hx, hy, 35.0, 1.6, constancy)

@@ -107,6 +107,123 @@ def test_cross_end_to_end(oracle, gradient):
     assert np.array_equal(uo, un) and np.array_equal(vo, vn)
 
 
+# ---- LogDerivatives: the C oracle against the numpy restatement, and the oracle's log source --------------------
+# 96 x 64 and 16 x 8 lie on the reference's 16 x 8 block grid; every other size ends inside a block in x, in y or in both
+# (the rule for the slot no thread wrote), 17 x 9 and 33 x 17 one pixel past a block edge, 15 x 7 one short of it.
+LOG_SIZES = [(96, 64), (100, 70), (37, 20), (17, 9), (16, 8), (15, 7), (33, 17), (2, 3), (1, 1)]
+
+
+def np_log(plane):
+    """Some float32 logarithm: which one does not matter where both sides are fed its planes."""
+    with np.errstate(all="ignore"):
+        return np.log(plane + np.float32(1.0)).astype(np.float32)
+
+
+def libm_log(plane):
+    """logf of the C library, pixel by pixel: what the oracle calls when no source is set."""
+    import ctypes
+    import ctypes.util
+    logf = ctypes.CDLL(ctypes.util.find_library("m")).logf
+    logf.restype, logf.argtypes = ctypes.c_float, [ctypes.c_float]
+    s = (plane + np.float32(1.0)).astype(np.float32)
+    return np.array([logf(float(x)) for x in s.ravel()], np.float32).reshape(plane.shape)
+
+
+def libm_log_moved(plane):
+    """libm_log with every seventh pixel's logarithm moved to the next float."""
+    out = libm_log(plane)
+    flat = out.reshape(-1)
+    flat[::7] = np.nextafter(flat[::7], np.float32(np.inf))
+    return out
+
+
+@pytest.mark.parametrize("w,h", LOG_SIZES)
+def test_cross_log_sweep_and_level(oracle, w, h):
+    """solve_2d_log off and on the 16 x 8 grid: flow2d_oracle.c and np_restatement.py, written separately from
+    solve_2d.cu:391-669, give the same words for one sweep and for a 2 x 3 level, the level inside a larger container."""
+    from conftest import in_container
+    from oracle import np_restatement as N
+    f0, f1, u, v, du, dv = level_fields(oracle, w, h, 61)
+    cw, ch = w + 5, h + 3
+    box = lambda a: in_container(a, cw, ch, 3.0)
+    lg0, lg1 = np_log(f0), np_log(f1)
+    for hx, hy in ((1.0, 1.0), (1.25, 1.1)):
+        phi, ksi = N.compute_phi_ksi(f0, f1, u, v, du, dv, hx, hy, 0.001, 0.001)
+        for alpha in (0.001, 35.0):
+            a, b = oracle.solve_sweep_log_planes(*[box(p) for p in (lg0, lg1, u, v, du, dv, phi, ksi)], w, h, hx, hy, alpha)
+            a2, b2 = N.solve_sweep_log(lg0, lg1, u, v, du, dv, phi, ksi, hx, hy, alpha)
+            assert bits_equal(a[:h, :w], a2) and bits_equal(b[:h, :w], b2), (hx, hy, alpha)
+            assert np.all(a[h:, :] == 0) and np.all(a[:, w:] == 0)  # only the level is written
+        with oracle.log_source(np_log):
+            sdu, sdv, sphi, sksi = oracle.solve_level(box(f0), box(f1), box(u), box(v), w, h, hx, hy, 0.001, 0.001, 0.001, 2, 3,
+                                                      oracle.LOG_DERIVATIVES)
+        ndu, ndv = np.zeros_like(u), np.zeros_like(v)
+        for _ in range(2):
+            nphi, nksi = N.compute_phi_ksi(f0, f1, u, v, ndu, ndv, hx, hy, 0.001, 0.001)
+            for _ in range(3):
+                ndu, ndv = N.solve_sweep_log(lg0, lg1, u, v, ndu, ndv, nphi, nksi, hx, hy, 0.001)
+        assert bits_equal(sdu[:h, :w], ndu) and bits_equal(sdv[:h, :w], ndv), (hx, hy)
+        assert bits_equal(sphi[:h, :w], nphi) and bits_equal(sksi[:h, :w], nksi)
+
+
+def test_cross_end_to_end_log(oracle):
+    """A whole LogDerivatives pyramid, 100 x 70 with scale 0.8 (levels 100 x 70, 80 x 56, 64 x 45, 52 x 36: none on the
+    16 x 8 grid), the same Python callable as logarithm on both sides: every word of u and v."""
+    from oracle import np_restatement as N
+    f0, f1, *_ = level_fields(oracle, 100, 70, 13)
+    p = (4, 0.8, 2, 3, 0.001, 0.001, 0.001, 5, 0.45)
+    with oracle.log_source(np_log):
+        uo, vo, _ = oracle.compute_flow(f0, f1, *p, oracle.LOG_DERIVATIVES)
+    un, vn = N.compute_flow(f0, f1, *p, log=np_log)
+    assert float(np.abs(uo).max()) > 0.01
+    assert bits_equal(uo, un) and bits_equal(vo, vn)
+
+
+def test_log_source_is_the_only_logarithm(oracle):
+    """oracle_set_log_source replaces every logf of the LogDerivatives term and nothing else: a source that calls libm's logf
+    reproduces the bytes of the oracle without a source (sweep, level, pyramid), one that moves some logarithms by an ulp
+    changes all three, oracle_solve_2d_log_planes fed the source's planes is the hooked oracle_solve_2d_log, and the source
+    is gone after the block."""
+    w, h = 100, 70
+    f0, f1, u, v, du, dv = level_fields(oracle, w, h, 62)
+    phi, ksi = oracle.compute_phi_ksi(f0, f1, u, v, du, dv, w, h, 1.25, 1.1, 0.001, 0.001)
+    p = (4, 0.8, 2, 3, 0.001, 0.001, 0.001, 5, 0.45)
+
+    def three():
+        s = oracle.solve_sweep(f0, f1, u, v, du, dv, phi, ksi, w, h, 1.25, 1.1, 0.001, oracle.LOG_DERIVATIVES)
+        l = oracle.solve_level(f0, f1, u, v, w, h, 1.25, 1.1, 0.001, 0.001, 0.001, 2, 3, oracle.LOG_DERIVATIVES)[:2]
+        c = oracle.compute_flow(f0, f1, *p, oracle.LOG_DERIVATIVES)[:2]
+        return s, l, c
+
+    plain = three()
+    with oracle.log_source(libm_log):
+        hooked = three()
+        planes = oracle.solve_sweep_log_planes(libm_log(f0), libm_log(f1), u, v, du, dv, phi, ksi, w, h, 1.25, 1.1, 0.001)
+    for a, b in zip(plain, hooked):
+        assert bits_equal(a[0], b[0]) and bits_equal(a[1], b[1])
+    assert bits_equal(planes[0], hooked[0][0]) and bits_equal(planes[1], hooked[0][1])
+    with oracle.log_source(libm_log_moved):
+        moved = three()
+    for a, b in zip(plain, moved):
+        assert not bits_equal(a[0], b[0]) and not bits_equal(a[1], b[1])
+    after = three()
+    for a, b in zip(plain, after):
+        assert bits_equal(a[0], b[0]) and bits_equal(a[1], b[1])
+    with pytest.raises(ZeroDivisionError):  # a failing source is reported, and libm is back afterwards
+        with oracle.log_source(lambda plane: 1 / 0):
+            three()
+    assert bits_equal(three()[0][0], plain[0][0])
+
+
+def test_device_log_entry_is_part_of_the_abi(flow2d):
+    """flow2d_log_frame_2d, what oracle.device_logs stands on: exported under the same ABI version, and it refuses a call
+    without a context before it touches a device."""
+    lib = flow2d.hip_lib()
+    assert lib.flow2d_abi_version() == 1  # an addition: the version stays
+    assert lib.flow2d_log_frame_2d(None, None, None, 4, 4, 16) == 1
+    assert hasattr(flow2d.Context, "log_frame")
+
+
 def test_median_matches_scipy(oracle):
     from scipy.ndimage import median_filter
     _, _, u, *_ = level_fields(oracle, 50, 31, 14)
@@ -231,7 +348,8 @@ def test_ref_golden_gradient_off_the_tile_grid(oracle, ref_golden):
 def test_ref_golden_log_derivatives(oracle, ref_golden):
     """solve_2d_log: same structure as the reference's kernel; logf comes from the CPU's libm here and from the
     device library there, so the comparison allows last-place differences of log(I + 1) (most pixels are
-    bit-identical, the rest differ by a few ulp of the result)."""
+    bit-identical, the rest differ by a few ulp of the result).  Handed the device's recorded logarithms of the two
+    frames instead, the oracle gives the reference kernel's words exactly."""
     g = ref_golden
     w, h = 96, 64
     hx, hy = (np.float32(x) for x in g["tile_h"])
@@ -243,6 +361,26 @@ def test_ref_golden_log_derivatives(oracle, ref_golden):
     sdu, sdv, _, _ = oracle.solve_level(f0, f1, u, v, w, h, hx, hy, 35.0, 0.001, 0.001, 3, 5, oracle.LOG_DERIVATIVES)
     assert float(np.abs(sdu - g["tile_solve_log_du"]).max()) < 1e-5
     assert float(np.abs(sdv - g["tile_solve_log_dv"]).max()) < 1e-5
+    # With the device's own logarithms of the two frames (tests/golden/device_log_golden.npz: flow2d_log_frame_2d on an
+    # MI355X, tests/golden/make_device_log_golden.py) nothing but the oracle's arithmetic and block rule is left: the
+    # reference kernel's recorded words, one sweep and the 3 x 5 level.
+    d = np.load(os.path.join(GOLDEN_DIR, "device_log_golden.npz"))
+    assert d["log_f0"].shape == f0.shape and d["log_f1"].shape == f1.shape
+
+    def recorded(plane):
+        for frame, logs in ((f0, d["log_f0"]), (f1, d["log_f1"])):
+            if bits_equal(plane, frame[:h, :w]):
+                return logs[:h, :w]
+        raise AssertionError("the oracle asked for the logarithm of a plane that is neither frame")
+
+    a, b = oracle.solve_sweep_log_planes(recorded(f0), recorded(f1), u, v, du, dv, g["tile_phi"], g["tile_ksi"], w, h, hx, hy,
+                                         35.0)
+    assert bits_equal(a, g["tile_sweep_log_du"]) and bits_equal(b, g["tile_sweep_log_dv"])
+    with oracle.log_source(recorded):
+        a, b = oracle.solve_sweep(f0, f1, u, v, du, dv, g["tile_phi"], g["tile_ksi"], w, h, hx, hy, 35.0, oracle.LOG_DERIVATIVES)
+        sdu, sdv, _, _ = oracle.solve_level(f0, f1, u, v, w, h, hx, hy, 35.0, 0.001, 0.001, 3, 5, oracle.LOG_DERIVATIVES)
+    assert bits_equal(a, g["tile_sweep_log_du"]) and bits_equal(b, g["tile_sweep_log_dv"])
+    assert bits_equal(sdu, g["tile_solve_log_du"]) and bits_equal(sdv, g["tile_solve_log_dv"])
 
 
 FLOW_RUNS = ["rub_short", "rub_settings", "rub_main_defaults", "syn_grey", "syn_grad", "odd_grey"]
@@ -274,8 +412,9 @@ def test_ref_golden_compute_flow_log(oracle, ref_golden, name, gate):
     """LogDerivatives through a whole pyramid.  The reference's kernel takes logf from the GPU's device library (built
     on the hardware's log2 instruction), the oracle from the CPU's libm; they differ in the last place for some
     inputs, and a pyramid amplifies that by the conditioning of the run (alpha 0.0005: RMSE ~5e-4 on a 0.9 px flow;
-    alpha 0.02: below the 1e-4 gate).  Bit-exactness in this mode is asserted where it is meaningful: HIP path vs
-    the reference's kernels on the same GPU (tests/test_gpu_reference.py)."""
+    alpha 0.02: below the 1e-4 gate).  This is the libm path.  Bit-exactness in this mode is asserted with the device's
+    logarithms handed to the oracle (test_ref_golden_log_derivatives here, tests/test_gpu_log_derivatives.py on the GPU)
+    and between the HIP path and the reference's kernels on the same GPU (tests/test_gpu_reference.py)."""
     g = ref_golden
     p = g[name + "_params"]
     u, v, _ = oracle.compute_flow(g["syn_f0"], g["syn_f1"], int(p[0]), float(p[1]), int(p[2]), int(p[3]), float(p[4]),
