@@ -289,7 +289,10 @@ class SubsetRecord(C.Structure):
 SUBSET_RECORD_BYTES = 64  # FLOW2D_SUBSET_RECORD_BYTES, checked by a static_assert in the header
 assert C.sizeof(SubsetRecord) == SUBSET_RECORD_BYTES
 SUBSET_MAX_RADIUS, SUBSET_MAX_ITERATIONS = 15, 64  # FLOW2D_SUBSET_MAX_*
+BSPLINE_HORIZON = 16  # FLOW2D_BSPLINE_HORIZON
 SUBSET_NO_INPUT, SUBSET_FLAT, SUBSET_STRAYED = -1, -2, -3  # the negative states of flow2d_subset_refine_2d
+SUBSET_CATMULL_ROM, SUBSET_BSPLINE = 0, 1  # OpticalFlow2D::SubsetOptions::Interpolation
+SUBSET_INTERPOLATIONS = {"catmull-rom": SUBSET_CATMULL_ROM, "bspline": SUBSET_BSPLINE}
 SUBSET_MASKED = -4  # FLOW2D_SUBSET_STATE_MASKED: flow2d_subset_refine_masked_2d's, a node off the region of interest
 SUBSET_MIN_PIXELS = 6  # FLOW2D_SUBSET_MIN_PIXELS
 
@@ -568,6 +571,10 @@ def hip_lib():
             L.flow2d_predict_nodes_2d.argtypes = [vp] + [vp] * 7 + [sz, sz, sz, i, i, i] + [vp] * 8
         if hasattr(L, "flow2d_subset_refine_masked_2d"):  # (absent from libraries of earlier rounds loaded for an A/B)
             L.flow2d_subset_refine_masked_2d.argtypes = [vp, vp, vp, sz, sz, sz] + [vp] * 6 + [sz, sz, sz, i, i, i, i, f, f, f, vp, i] + [vp] * 9
+        if hasattr(L, "flow2d_bspline_prefilter_2d"):  # (absent from libraries of earlier rounds loaded for an A/B)
+            L.flow2d_bspline_prefilter_2d.argtypes = [vp, vp, vp, sz, sz, sz]
+            L.flow2d_subset_refine_spline_2d.argtypes = L.flow2d_subset_refine_masked_2d.argtypes
+            L.flow2d_subset_refine2_spline_2d.argtypes = L.flow2d_subset_refine2_2d.argtypes
         if hasattr(L, "flow2d_node_strain_2d"):  # (absent from libraries of earlier rounds loaded for an A/B)
             L.flow2d_node_strain_workspace_bytes.restype = sz
             L.flow2d_node_strain_workspace_bytes.argtypes = [sz, sz, sz]
@@ -1348,25 +1355,54 @@ class Context:
         are not excluded --; a node whose centre is excluded or that has fewer than min_pixels usable pixels (None:
         subset_min_pixels(subset_radius)) is SUBSET_MASKED, NaN in all six planes, and counted in the record's `masked`.  mask =
         None: every byte is subset_refine_from's.  Outputs, record and the return value as for subset_refine."""
+        return self._subset_refine_masked_entry("subset_refine_masked", "flow2d_subset_refine_masked_2d", f0, f1, w, h, node_u0, node_v0,
+                                                start_gradients, nw, nh, grid_radius, spacing, subset_radius, mask, min_pixels,
+                                                max_iterations, epsilon, max_shift, max_gradient, out_u, out_v, out_gradients, out_score,
+                                                out_state, record, instances)
+
+    def _subset_refine_masked_entry(self, name, entry, f0, f1, w, h, node_u0, node_v0, start_gradients, nw, nh, grid_radius, spacing,
+                                    subset_radius, mask, min_pixels, max_iterations, epsilon, max_shift, max_gradient, out_u, out_v,
+                                    out_gradients, out_score, out_state, record, instances):
+        """subset_refine_masked and subset_refine_spline: one signature, `entry` of the library; f1 is frame 1 or its coefficients."""
         def issue(held, rec):
             start = list(start_gradients) if start_gradients is not None else [None] * 4
             if len(start) != 4:
-                raise ValueError("subset_refine_masked takes the four start gradients (ux0, uy0, vx0, vy0) or None")
+                raise ValueError("%s takes the four start gradients (ux0, uy0, vx0, vy0) or None" % name)
             pixels = subset_min_pixels(subset_radius) if min_pixels is None else min_pixels
-            _check(hip_lib().flow2d_subset_refine_masked_2d(self.handle, f0.ptr, f1.ptr, w, h, f0.pitch, node_u0.ptr, node_v0.ptr,
-                                                            *[q.ptr if q is not None else None for q in start], nw, nh, node_u0.pitch,
-                                                            int(grid_radius), int(spacing), int(subset_radius), int(max_iterations),
-                                                            float(epsilon), float(max_shift), float(max_gradient),
-                                                            mask.ptr if mask is not None else None, int(pixels), *held, rec),
-                   "flow2d_subset_refine_masked_2d")
+            _check(getattr(hip_lib(), entry)(self.handle, f0.ptr, f1.ptr, w, h, f0.pitch, node_u0.ptr, node_v0.ptr,
+                                             *[q.ptr if q is not None else None for q in start], nw, nh, node_u0.pitch,
+                                             int(grid_radius), int(spacing), int(subset_radius), int(max_iterations), float(epsilon),
+                                             float(max_shift), float(max_gradient), mask.ptr if mask is not None else None, int(pixels),
+                                             *held, rec), entry)
 
-        return self._subset_refine_call("subset_refine_masked", issue, node_u0, nw, nh, out_u, out_v, [(out_gradients, 4)], out_score,
-                                        out_state, record, instances)
+        return self._subset_refine_call(name, issue, node_u0, nw, nh, out_u, out_v, [(out_gradients, 4)], out_score, out_state, record,
+                                        instances)
+
+    def bspline_prefilter(self, src, w, h, out=None):
+        """The cubic B-spline coefficients of the Plane `src` (flow2d_bspline_prefilter_2d), times 36: what subset_refine_spline and
+        subset_refine2_spline sample in the place of frame 1.  The recursive prefilter's symmetric impulse response truncated at
+        BSPLINE_HORIZON, rows then columns in double, whole-sample mirroring at the borders; one launch, which honours set_batch.
+        out: a Plane of src's pitch that is written and returned, or None: the call allocates one (the caller frees it)."""
+        dst = out if out is not None else self.plane(src.width, src.height)
+        _check(hip_lib().flow2d_bspline_prefilter_2d(self.handle, src.ptr, dst.ptr, w, h, src.pitch), "flow2d_bspline_prefilter_2d")
+        return dst
+
+    def subset_refine_spline(self, f0, coeff_1, w, h, node_u0, node_v0, start_gradients, nw, nh, grid_radius, spacing, subset_radius,
+                             mask=None, min_pixels=None, max_iterations=20, epsilon=1e-3, max_shift=4.0, max_gradient=0.5, out_u=None,
+                             out_v=None, out_gradients=None, out_score=None, out_state=None, record=True, instances=1):
+        """subset_refine_masked with the cubic B-spline sample of frame 1 in the place of the Catmull-Rom one
+        (flow2d_subset_refine_spline_2d): coeff_1 is the Plane bspline_prefilter made from frame 1.  A tenth of the interpolation
+        bias in the displacement for the same sixteen taps.  mask = None: the bytes of a mask that excludes nothing.  Everything
+        else, outputs, record and the return value as for subset_refine_masked."""
+        return self._subset_refine_masked_entry("subset_refine_spline", "flow2d_subset_refine_spline_2d", f0, coeff_1, w, h, node_u0,
+                                                node_v0, start_gradients, nw, nh, grid_radius, spacing, subset_radius, mask, min_pixels,
+                                                max_iterations, epsilon, max_shift, max_gradient, out_u, out_v, out_gradients, out_score,
+                                                out_state, record, instances)
 
     def subset_refine2(self, f0, f1, w, h, node_u0, node_v0, nw, nh, grid_radius, spacing, subset_radius, max_iterations=20,
                        epsilon=1e-3, max_shift=2.0, max_gradient=0.5, max_curvature=0.05, start_gradients=None, start_curvatures=None,
                        out_u=None, out_v=None, out_gradients=None, out_curvatures=None, out_score=None, out_state=None, record=True,
-                       instances=1):
+                       instances=1, _entry="flow2d_subset_refine2_2d"):
         """Subset refinement with a second-order shape function (flow2d_subset_refine2_2d): subset_refine_from with twelve
         parameters per node -- the displacement, its four gradients and the six curvatures (uxx, uxy, uyy, vxx, vxy, vyy) -- for
         subsets that bend; subset_radius from 2.  start_gradients = (ux0, uy0, vx0, vy0) and start_curvatures = (uxx0, uxy0, uyy0,
@@ -1386,16 +1422,24 @@ class Context:
         def issue(held, rec):
             if len(held) != 14:
                 raise ValueError("subset_refine2 takes four gradient planes and six curvature planes")
-            _check(hip_lib().flow2d_subset_refine2_2d(self.handle, f0.ptr, f1.ptr, w, h, f0.pitch, node_u0.ptr, node_v0.ptr,
-                                                      start(start_gradients, 4, "start gradients"),
-                                                      start(start_curvatures, 6, "start curvatures"), nw, nh, node_u0.pitch,
-                                                      int(grid_radius), int(spacing), int(subset_radius), int(max_iterations),
-                                                      float(epsilon), float(max_shift), float(max_gradient), float(max_curvature),
-                                                      held[0], held[1], (C.c_void_p * 4)(*held[2:6]), (C.c_void_p * 6)(*held[6:12]),
-                                                      held[12], held[13], rec), "flow2d_subset_refine2_2d")
+            _check(getattr(hip_lib(), _entry)(self.handle, f0.ptr, f1.ptr, w, h, f0.pitch, node_u0.ptr, node_v0.ptr,
+                                              start(start_gradients, 4, "start gradients"),
+                                              start(start_curvatures, 6, "start curvatures"), nw, nh, node_u0.pitch,
+                                              int(grid_radius), int(spacing), int(subset_radius), int(max_iterations),
+                                              float(epsilon), float(max_shift), float(max_gradient), float(max_curvature),
+                                              held[0], held[1], (C.c_void_p * 4)(*held[2:6]), (C.c_void_p * 6)(*held[6:12]),
+                                              held[12], held[13], rec), _entry)
 
         return self._subset_refine_call("subset_refine2", issue, node_u0, nw, nh, out_u, out_v, [(out_gradients, 4), (out_curvatures, 6)],
                                         out_score, out_state, record, instances)
+
+    def subset_refine2_spline(self, f0, coeff_1, w, h, node_u0, node_v0, nw, nh, grid_radius, spacing, subset_radius, **options):
+        """subset_refine2 with the cubic B-spline sample of frame 1 (flow2d_subset_refine2_spline_2d): coeff_1 is the Plane
+        bspline_prefilter made from frame 1.  Options, outputs and the return value as for subset_refine2."""
+        if "_entry" in options:
+            raise TypeError("subset_refine2_spline() got an unexpected keyword argument '_entry'")
+        return self.subset_refine2(f0, coeff_1, w, h, node_u0, node_v0, nw, nh, grid_radius, spacing, subset_radius,
+                                   _entry="flow2d_subset_refine2_spline_2d", **options)
 
     def predict_records(self, instances=1):
         """A Plane for `instances` flow2d_predict_record records (device memory)."""
@@ -1777,6 +1821,8 @@ def host_lib():
             sequence = [i, i, i, f]  # fill, min_state, predict_neighbours, sequence_max_shift
             L.flow2d_host_subset_options_ok.argtypes = [so]
             L.flow2d_host_subset_min_pixels.argtypes = [i]
+            L.flow2d_host_subset_interpolation_ok.argtypes = [i]
+            L.flow2d_host_set_subset_interpolation.argtypes = [vp, i]
             L.flow2d_host_sequence_options_ok.argtypes = sequence
             L.flow2d_host_refine_nodes_device.argtypes = [vp, vp, vp, vp, vp, i, i, so, pvp, sr]
             L.flow2d_host_refine_nodes_from_device.argtypes = [vp, vp, vp, pvp, i, i, so, pvp, sr]
@@ -2364,9 +2410,15 @@ class OpticalFlow:
         return image
 
     def _subset_options(self, where, radius, iterations, epsilon, max_shift, max_gradient, order, max_curvature, mask, min_pixels,
-                        image=False):
+                        image=False, interpolation="catmull-rom"):
         """The SubsetOptions record of a call that refines, by the rules of _takes_mask.  image: the mask is an image and not a
-        device plane; the record then holds the float32 array it points into, which lives as long as the record."""
+        device plane; the record then holds the float32 array it points into, which lives as long as the record.
+        interpolation -- "catmull-rom" or "bspline", OpticalFlow2D::SubsetOptions::interpolation: how frame 1 is sampled.  With
+        "bspline" the call prefilters its frame 1 (a sequence: every step its frame k) into a plane of the object's own and runs the
+        spline entry of its order; mask and order go with both.  It travels beside the record (which keeps its 40 bytes): every call
+        sets it in the object, so the default restores Catmull-Rom."""
+        if interpolation not in SUBSET_INTERPOLATIONS:
+            raise ValueError("interpolation is one of %s" % ", ".join(sorted(SUBSET_INTERPOLATIONS)))
         held = None
         if self._takes_mask(mask, min_pixels, order, where) and image:
             held = self._mask_image(mask)
@@ -2374,6 +2426,8 @@ class OpticalFlow:
         options = SubsetOptions(int(radius), int(iterations), float(epsilon), float(max_shift), float(max_gradient), int(order),
                                 float(max_curvature), int(min_pixels), mask)
         options.held = held
+        if host_lib().flow2d_host_set_subset_interpolation(self.handle, SUBSET_INTERPOLATIONS[interpolation]):
+            raise Flow2DError(1, where, "the subset interpolation was refused")
         return options
 
     @staticmethod
@@ -2397,16 +2451,18 @@ class OpticalFlow:
 
     def refine_nodes_device(self, dev_frame_0, dev_frame_1, dev_node_u0, dev_node_v0, grid_radius, spacing, radius, iterations=20,
                             epsilon=1e-3, max_shift=2.0, max_gradient=0.5, dev_out=None, record=True, order=1, max_curvature=0.05, mask=None,
-                            min_pixels=0):
+                            min_pixels=0, interpolation="catmull-rom"):
         """OpticalFlow2D::RefineNodesDevice: the node field (dev_node_u0, dev_node_v0) of the grid (grid_radius, spacing) -- planes of
         the container's size -- refined by subsets of `radius` (flow2d_subset_refine_2d).  dev_out: a dict of device planes by the
         names of SUBSET_PLANES (u and v both or neither, the four gradients all or none).  Returns the SubsetRecord (the call then
         synchronises) or, without record, None (it only queues).  order=2: the second-order refinement (flow2d_subset_refine2_2d),
         radius from 2, a curvature beyond max_curvature strays; dev_out by the names of SUBSET2_PLANES, the six curvatures all or
-        none.  order=1 is the call it always was.  mask (a device plane) / min_pixels: see _takes_mask."""
+        none.  order=1 is the call it always was.  mask (a device plane) / min_pixels: see _takes_mask.  interpolation ("catmull-rom", the
+        call it always was, or "bspline": frame 1 prefiltered and sampled as a cubic B-spline), here and on every method below that
+        refines: see _subset_options."""
         rec = SubsetRecord()
         options = self._subset_options("OpticalFlow2D::RefineNodesDevice", radius, iterations, epsilon, max_shift, max_gradient, order,
-                                       max_curvature, mask, min_pixels)
+                                       max_curvature, mask, min_pixels, interpolation=interpolation)
         rc = host_lib().flow2d_host_refine_nodes_device(self.handle, dev_frame_0, dev_frame_1, dev_node_u0, dev_node_v0, int(grid_radius),
                                                         int(spacing), C.byref(options), self._subset_planes(dev_out, order),
                                                         C.byref(rec) if record else None)
@@ -2416,7 +2472,7 @@ class OpticalFlow:
 
     def correlate_subset(self, frame_0, frame_1, passes, radius, iterations=20, epsilon=1e-3, max_shift=2.0, max_gradient=0.5,
                          min_score=-1.0, threshold=2.0, validate_epsilon=0.1, min_neighbours=3, predictor=None, flow=False, order=1,
-                         max_curvature=0.05, mask=None, min_pixels=0):
+                         max_curvature=0.05, mask=None, min_pixels=0, interpolation="catmull-rom"):
         """OpticalFlow2D::CorrelateSubset: the host pair through `passes` as in correlate_multipass -- the last pass validated with
         replacement, so that every node has a start --, then every node of the last pass's grid refined by subsets of `radius` on
         the unquantised frames.  Returns (nodes, [CorrelationPassReport], SubsetRecord, (lo, scale)), nodes a dict of [nh, nw]
@@ -2434,7 +2490,7 @@ class OpticalFlow:
         pred = [np.ascontiguousarray(q, np.float32) for q in predictor] if predictor is not None else [None, None]
         reports, rec, lo_scale = (CorrelationPassReport * n)(), SubsetRecord(), (C.c_float * 2)()
         options = self._subset_options("OpticalFlow2D::CorrelateSubset", radius, iterations, epsilon, max_shift, max_gradient, order,
-                                       max_curvature, mask, min_pixels, image=True)
+                                       max_curvature, mask, min_pixels, image=True, interpolation=interpolation)
         rc = host_lib().flow2d_host_correlate_subset(self.handle, _fptr(f0), _fptr(f1), arr, n, float(min_score), float(threshold),
                                                      float(validate_epsilon), int(min_neighbours), C.byref(options), _opt_fptr(pred[0]),
                                                      _opt_fptr(pred[1]), self._node_arrays(nodes, len(names)), reports, C.byref(rec),
@@ -2446,7 +2502,8 @@ class OpticalFlow:
 
     def correlate_subset_device(self, dev_frame_0, dev_frame_1, lo, scale, passes, radius, iterations=20, epsilon=1e-3, max_shift=2.0,
                                 max_gradient=0.5, min_score=-1.0, threshold=2.0, validate_epsilon=0.1, min_neighbours=3, dev_predictor=None,
-                                dev_out=None, dev_flow=None, order=1, max_curvature=0.05, mask=None, min_pixels=0):
+                                dev_out=None, dev_flow=None, order=1, max_curvature=0.05, mask=None, min_pixels=0,
+                                interpolation="catmull-rom"):
         """OpticalFlow2D::CorrelateSubsetDevice: device frames in; dev_predictor and dev_flow as for correlate_multipass_device (the
         flow is the refined field's), dev_out, order and max_curvature as for refine_nodes_device.  Returns
         ([CorrelationPassReport], SubsetRecord); synchronises once.  mask (a device plane) / min_pixels: see _takes_mask."""
@@ -2454,7 +2511,7 @@ class OpticalFlow:
         reports, rec = (CorrelationPassReport * max(n, 1))(), SubsetRecord()
         pr, fl = dev_predictor or (None, None), dev_flow or (None, None)
         options = self._subset_options("OpticalFlow2D::CorrelateSubsetDevice", radius, iterations, epsilon, max_shift, max_gradient, order,
-                                       max_curvature, mask, min_pixels)
+                                       max_curvature, mask, min_pixels, interpolation=interpolation)
         rc = host_lib().flow2d_host_correlate_subset_device(self.handle, dev_frame_0, dev_frame_1, float(lo), float(scale), arr, n,
                                                             float(min_score), float(threshold), float(validate_epsilon), int(min_neighbours),
                                                             C.byref(options), pr[0], pr[1], self._subset_planes(dev_out, order), reports,
@@ -2470,7 +2527,7 @@ class OpticalFlow:
 
     def refine_nodes_from_device(self, dev_frame_0, dev_frame_1, dev_start, grid_radius, spacing, radius, iterations=20, epsilon=1e-3,
                                  max_shift=4.0, max_gradient=0.5, dev_out=None, record=True, order=1, max_curvature=0.05, mask=None,
-                                 min_pixels=0):
+                                 min_pixels=0, interpolation="catmull-rom"):
         """OpticalFlow2D::RefineNodesFromDevice: refine_nodes_device started from a whole deformation (flow2d_subset_refine_from_2d):
         dev_start is a dict of the six device planes u, v, ux, uy, vx, vy (by the names of SUBSET_PLANES), all needed.  Returns the
         SubsetRecord (the call then synchronises) or, without record, None (it only queues).  order and max_curvature as for
@@ -2480,7 +2537,7 @@ class OpticalFlow:
             raise ValueError("refine_nodes_from_device takes the six start planes %s" % ", ".join(names))
         rec = SubsetRecord()
         options = self._subset_options("OpticalFlow2D::RefineNodesFromDevice", radius, iterations, epsilon, max_shift, max_gradient, order,
-                                       max_curvature, mask, min_pixels)
+                                       max_curvature, mask, min_pixels, interpolation=interpolation)
         rc = host_lib().flow2d_host_refine_nodes_from_device(self.handle, dev_frame_0, dev_frame_1, (C.c_void_p * 6)(*[dev_start[n] for n in names]),
                                                              int(grid_radius), int(spacing), C.byref(options),
                                                              self._subset_planes(dev_out, order), C.byref(rec) if record else None)
@@ -2490,7 +2547,8 @@ class OpticalFlow:
 
     def correlate_subset_sequence(self, frames, passes, radius, iterations=20, epsilon=1e-3, max_shift=2.0, max_gradient=0.5, min_score=-1.0,
                                   threshold=2.0, validate_epsilon=0.1, min_neighbours=3, fill=2, min_state=1, predict_neighbours=1,
-                                  sequence_max_shift=4.0, flow=False, order=1, max_curvature=0.05, mask=None, min_pixels=0):
+                                  sequence_max_shift=4.0, flow=False, order=1, max_curvature=0.05, mask=None, min_pixels=0,
+                                  interpolation="catmull-rom"):
         """OpticalFlow2D::CorrelateSubsetSequence: digital image correlation over a loading sequence.  (order=2: every step refines
         at second order, the steps after the first from the prediction's first-order planes with zero curvatures; the nodes then
         go by the names of SUBSET2_PLANES.)  frames[0] is the reference and
@@ -2516,7 +2574,7 @@ class OpticalFlow:
         fpp = C.POINTER(C.c_float)
         reports, reps, lo_scale = (CorrelationPassReport * n)(), (SequenceStepReport * steps)(), (C.c_float * 2)()
         options = self._subset_options("OpticalFlow2D::CorrelateSubsetSequence", radius, iterations, epsilon, max_shift, max_gradient, order,
-                                       max_curvature, mask, min_pixels, image=True)
+                                       max_curvature, mask, min_pixels, image=True, interpolation=interpolation)
         rc = host_lib().flow2d_host_correlate_subset_sequence(self.handle, (fpp * len(images))(*[_fptr(q) for q in images]), len(images), arr, n,
                                                               float(min_score), float(threshold), float(validate_epsilon), int(min_neighbours),
                                                               C.byref(options), int(fill), int(min_state), int(predict_neighbours),
@@ -2531,7 +2589,7 @@ class OpticalFlow:
     def correlate_subset_sequence_device(self, dev_frames, lo, scale, passes, radius, dev_out, iterations=20, epsilon=1e-3, max_shift=2.0,
                                          max_gradient=0.5, min_score=-1.0, threshold=2.0, validate_epsilon=0.1, min_neighbours=3, fill=2,
                                          min_state=1, predict_neighbours=1, sequence_max_shift=4.0, dev_flows=None, order=1,
-                                         max_curvature=0.05, mask=None, min_pixels=0):
+                                         max_curvature=0.05, mask=None, min_pixels=0, interpolation="catmull-rom"):
         """OpticalFlow2D::CorrelateSubsetSequenceDevice: device frames in (the first is the reference); dev_out: per step a dict of
         device planes by the names of SUBSET_PLANES, of which only the score may be missing; dev_flows: per step a (u, v) pair or
         None.  Returns ([CorrelationPassReport] of step 1, [SequenceStepReport]); synchronises once.  order=2: every step refines
@@ -2553,7 +2611,7 @@ class OpticalFlow:
             flows = (C.c_void_p * (2 * steps))(*flat)
         reports, reps = (CorrelationPassReport * max(n, 1))(), (SequenceStepReport * steps)()
         options = self._subset_options("OpticalFlow2D::CorrelateSubsetSequenceDevice", radius, iterations, epsilon, max_shift, max_gradient,
-                                       order, max_curvature, mask, min_pixels)
+                                       order, max_curvature, mask, min_pixels, interpolation=interpolation)
         rc = host_lib().flow2d_host_correlate_subset_sequence_device(self.handle, (C.c_void_p * len(dev_frames))(*dev_frames), len(dev_frames),
                                                                      float(lo), float(scale), arr, n, float(min_score), float(threshold),
                                                                      float(validate_epsilon), int(min_neighbours), C.byref(options), int(fill),

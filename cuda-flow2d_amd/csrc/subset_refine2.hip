@@ -14,6 +14,8 @@
 //   at R = 15 two waves' slices still fit the 64 KB).  Lane 0 writes an element, every lane reads it back as a broadcast: the
 //   LDS serves a wave's accesses in order, and __builtin_amdgcn_wave_barrier keeps the compiler from moving one across another.
 // Frame 1 is gathered from global memory, 16 taps per pixel and iteration, clamped to the frame.
+// The sample of the deformed frame is a template parameter (subset_sample.hpp): CatmullRom is flow2d_subset_refine2_2d, BSpline on
+// frame 1's coefficients flow2d_subset_refine2_spline_2d, whose taps are reflected.  Both entries share one host body.
 #include <algorithm>
 #include <cmath>
 
@@ -245,7 +247,7 @@ __device__ __forceinline__ bool compose(double (&p)[12], const double (&dp)[12])
 
 // The node from the frame-0 quantities on: the state, with p, the last c and the iterations begun.  p holds the start on entry.
 // Every lane of the wave returns the same values.
-template <typename Offset>
+template <typename Offset, typename Sampler>
 __device__ __forceinline__ int refine_node(const Subset2Node& nd, const Subset2Args& a, double (&p)[12], double& score, unsigned& iterations)
 {
     const double u0 = p[0], v0 = p[6];
@@ -294,7 +296,7 @@ __device__ __forceinline__ int refine_node(const Subset2Node& nd, const Subset2A
             const double Y = static_cast<double>(top + ky) + (((((p[6] + p[7] * phi[1]) + p[8] * phi[2]) + p[9] * phi[3]) + p[10] * phi[4]) + p[11] * phi[5]);
             double g = 0.0;
             if (X >= 0.0 && X <= xmax && Y >= 0.0 && Y <= ymax)
-                g = cubic_sample<Offset>(nd, X, Y);
+                g = Sampler::template sample<Offset>(nd, X, Y);
             else
                 outside = 1;
             nd.g[k] = g;
@@ -359,7 +361,7 @@ __device__ __forceinline__ int refine_node(const Subset2Node& nd, const Subset2A
 
 // Compiled for three waves per SIMD, the occupancy of subset_refine_kernel: 164 / 166 VGPRs and no scratch.  Left to itself the
 // compiler takes 256 (one wave); asked for four it spills (profiles/subset2/resource_usage.txt).
-template <typename Offset>
+template <typename Offset, typename Sampler>
 __global__ __launch_bounds__(64 * kSubset2MaxWaves) __attribute__((amdgpu_waves_per_eu(3, 3))) void subset_refine2_kernel(Subset2Args a, BatchArg batch)
 {
     extern __shared__ __attribute__((aligned(16))) double s_subset2[];
@@ -407,7 +409,7 @@ __global__ __launch_bounds__(64 * kSubset2MaxWaves) __attribute__((amdgpu_waves_
     else if (!(nd.cx - nd.R >= 0 && nd.cy - nd.R >= 0 && nd.cx + nd.R <= a.w - 1 && nd.cy + nd.R <= a.h - 1))
         state = kStateStrayed;
     else
-        state = refine_node<Offset>(nd, a, p, score, iterations);
+        state = refine_node<Offset, Sampler>(nd, a, p, score, iterations);
     if (lane != 0) return;
 
     const float out_score = state >= 0 ? static_cast<float>(score) : 0.f;
@@ -433,15 +435,14 @@ int all_or_none(Pointer const* planes, int n)
     return there == n ? 1 : there == 0 ? 0 : -1;
 }
 
-}  // namespace
-
-extern "C" int flow2d_subset_refine2_2d(flow2d_context* ctx, const float* frame_0, const float* frame_1, size_t width, size_t height,
-                                        size_t pitch_bytes, const float* node_u0, const float* node_v0,
-                                        const float* const* start_gradients, const float* const* start_curvatures, size_t nw, size_t nh,
-                                        size_t node_pitch_bytes, int grid_radius, int spacing, int subset_radius, int max_iterations,
-                                        float epsilon, float max_shift, float max_gradient, float max_curvature, float* out_u,
-                                        float* out_v, float* const* out_gradients, float* const* out_curvatures, float* out_score,
-                                        float* out_state, flow2d_subset_record* record)
+// The body of both entries; frame_1 is the frame for CatmullRom and its coefficients for BSpline.
+template <typename Sampler>
+int subset_refine2(flow2d_context* ctx, const float* frame_0, const float* frame_1, size_t width, size_t height, size_t pitch_bytes,
+                   const float* node_u0, const float* node_v0, const float* const* start_gradients,
+                   const float* const* start_curvatures, size_t nw, size_t nh, size_t node_pitch_bytes, int grid_radius, int spacing,
+                   int subset_radius, int max_iterations, float epsilon, float max_shift, float max_gradient, float max_curvature,
+                   float* out_u, float* out_v, float* const* out_gradients, float* const* out_curvatures, float* out_score,
+                   float* out_state, flow2d_subset_record* record)
 {
     if (ctx == nullptr) return FLOW2D_ERR_INVALID_ARGUMENT;
     // (every check that needs no context field comes first: they hold without a device)
@@ -522,8 +523,41 @@ extern "C" int flow2d_subset_refine2_2d(flow2d_context* ctx, const float* frame_
     // (the largest offset a lane forms into a frame is below height * pitch_bytes; the node planes are addressed in 64 bits)
     flow2d::launch_by_span(height * pitch_bytes, [&](auto offset) {
         const dim3 grid(flow2d::div_up(nw * nh, waves), 1, flow2d::batch_z(ctx, 1)), block(64 * waves);
-        subset_refine2_kernel<decltype(offset)><<<grid, block, waves * wave_bytes, ctx->stream>>>(a, flow2d::batch_arg(ctx, 1));
+        subset_refine2_kernel<decltype(offset), Sampler><<<grid, block, waves * wave_bytes, ctx->stream>>>(a, flow2d::batch_arg(ctx, 1));
     });
     FLOW2D_CHECK_LAUNCH();
     return FLOW2D_OK;
 }
+
+}  // namespace
+
+extern "C" {
+
+int flow2d_subset_refine2_2d(flow2d_context* ctx, const float* frame_0, const float* frame_1, size_t width, size_t height,
+                             size_t pitch_bytes, const float* node_u0, const float* node_v0, const float* const* start_gradients,
+                             const float* const* start_curvatures, size_t nw, size_t nh, size_t node_pitch_bytes, int grid_radius,
+                             int spacing, int subset_radius, int max_iterations, float epsilon, float max_shift, float max_gradient,
+                             float max_curvature, float* out_u, float* out_v, float* const* out_gradients,
+                             float* const* out_curvatures, float* out_score, float* out_state, flow2d_subset_record* record)
+{
+    return subset_refine2<CatmullRom>(ctx, frame_0, frame_1, width, height, pitch_bytes, node_u0, node_v0, start_gradients,
+                                      start_curvatures, nw, nh, node_pitch_bytes, grid_radius, spacing, subset_radius, max_iterations,
+                                      epsilon, max_shift, max_gradient, max_curvature, out_u, out_v, out_gradients, out_curvatures,
+                                      out_score, out_state, record);
+}
+
+int flow2d_subset_refine2_spline_2d(flow2d_context* ctx, const float* frame_0, const float* coeff_1, size_t width, size_t height,
+                                    size_t pitch_bytes, const float* node_u0, const float* node_v0,
+                                    const float* const* start_gradients, const float* const* start_curvatures, size_t nw, size_t nh,
+                                    size_t node_pitch_bytes, int grid_radius, int spacing, int subset_radius, int max_iterations,
+                                    float epsilon, float max_shift, float max_gradient, float max_curvature, float* out_u,
+                                    float* out_v, float* const* out_gradients, float* const* out_curvatures, float* out_score,
+                                    float* out_state, flow2d_subset_record* record)
+{
+    return subset_refine2<BSpline>(ctx, frame_0, coeff_1, width, height, pitch_bytes, node_u0, node_v0, start_gradients,
+                                   start_curvatures, nw, nh, node_pitch_bytes, grid_radius, spacing, subset_radius, max_iterations,
+                                   epsilon, max_shift, max_gradient, max_curvature, out_u, out_v, out_gradients, out_curvatures,
+                                   out_score, out_state, record);
+}
+
+}  // extern "C"

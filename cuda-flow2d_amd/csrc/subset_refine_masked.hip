@@ -18,10 +18,15 @@
 // Every branch on a node's state is uniform over the wave: the centre's mask value is loaded by all lanes, Nv comes from ballots.
 // The workgroup is sized so that the slices fit the 64 KB every launch may ask for without an attribute call: four waves up to
 // R = 10 (15 032 bytes per wave there), three at R = 11 and 12, two from R = 13 (32 712 bytes at R = 15).
+// The sample of the deformed frame and whether there is a mask are template parameters: <CatmullRom, true> is
+// flow2d_subset_refine_masked_2d; <BSpline, true> and <BSpline, false> are flow2d_subset_refine_spline_2d on frame 1's coefficients
+// (subset_sample.hpp), with and without a mask.  Without one the compaction is compiled out -- no mask loads, no ballots, no index
+// list read: the list is k itself, element m is pixel m, and the sums are those of a mask that excludes nothing, bit for bit.
 // subset_refine.hip is left as it is (its instruction streams are measured ones); the sampling helpers are subset_sample.hpp's, which
 // subset_refine2.hip shares, the factorisation and the solve small_cholesky.hpp's.
 #include <algorithm>
 #include <cmath>
+#include <type_traits>
 
 #include "node_grid.hpp"
 #include "plane_sample.hpp"
@@ -68,6 +73,16 @@ template <typename Offset>
 __device__ __forceinline__ bool excluded_at(const float* mask, int x, int y, int pitch)
 {
     return !(load_at(mask, pixel_offset<Offset>(x, y, pitch)) < 0.5f);
+}
+
+// Pixel k of element m of the list.
+template <bool kMasked>
+__device__ __forceinline__ int pixel_of(const MaskedNode& nd, int m)
+{
+    if constexpr (kMasked)
+        return nd.index[m];
+    else
+        return m;
 }
 
 // J of the header for element m of the list, pixel k.
@@ -126,9 +141,25 @@ __device__ __forceinline__ int compact_usable(const MaskedNode& nd)
     return nv;
 }
 
+// compact_usable without a mask: every pixel is usable and slot k is pixel k's, filled by the lane that reads it afterwards.
+template <typename Offset>
+__device__ __forceinline__ int fill_all(const MaskedNode& nd)
+{
+    const int left = nd.cx - nd.R, top = nd.cy - nd.R;
+    for (int k = nd.lane; k < nd.n; k += 64) {
+        const int ky = k / nd.side, kx = k - ky * nd.side;
+        const int x = left + kx, y = top + ky;
+        const int xp = min(x + 1, nd.w - 1), xm = max(x - 1, 0), yp = min(y + 1, nd.h - 1), ym = max(y - 1, 0);
+        nd.fd[k] = sample_at<Offset>(nd.f0, x, y, nd.pitch);
+        nd.fx[k] = (sample_at<Offset>(nd.f0, xp, y, nd.pitch) - sample_at<Offset>(nd.f0, xm, y, nd.pitch)) * 0.5;
+        nd.fy[k] = (sample_at<Offset>(nd.f0, x, yp, nd.pitch) - sample_at<Offset>(nd.f0, x, ym, nd.pitch)) * 0.5;
+    }
+    return nd.n;
+}
+
 // The node from the frame-0 quantities compact_usable left in LDS on, over the nd.nv usable pixels: the state, with p, the last c
 // and the iterations begun.  p = (u, ux, uy, v, vx, vy) holds the start on entry.  Every lane of the wave returns the same values.
-template <typename Offset>
+template <typename Offset, typename Sampler, bool kMasked>
 __device__ __forceinline__ int refine_node(const MaskedNode& nd, const MaskedArgs& a, double (&p)[6], double& score, unsigned& iterations)
 {
     const double u0 = p[0], v0 = p[3];
@@ -149,7 +180,7 @@ __device__ __forceinline__ int refine_node(const MaskedNode& nd, const MaskedArg
         nd.fd[m] = fd;
         df2 += fd * fd;
         double J[6];
-        jacobian(nd, m, nd.index[m], J);
+        jacobian(nd, m, pixel_of<kMasked>(nd, m), J);
         int at = 0;
 #pragma unroll
         for (int i = 0; i < 6; ++i)
@@ -177,14 +208,14 @@ __device__ __forceinline__ int refine_node(const MaskedNode& nd, const MaskedArg
         unsigned outside = 0;
         double sum_g = 0.0;
         for (int m = nd.lane; m < nd.nv; m += 64) {
-            const int k = nd.index[m];
+            const int k = pixel_of<kMasked>(nd, m);
             const int ky = k / nd.side, kx = k - ky * nd.side;
             const double xi = static_cast<double>(kx - nd.R), eta = static_cast<double>(ky - nd.R);
             const double X = static_cast<double>(left + kx) + ((p[0] + p[1] * xi) + p[2] * eta);
             const double Y = static_cast<double>(top + ky) + ((p[3] + p[4] * xi) + p[5] * eta);
             double g = 0.0;
             if (X >= 0.0 && X <= xmax && Y >= 0.0 && Y <= ymax)
-                g = cubic_sample<Offset>(nd, X, Y);
+                g = Sampler::template sample<Offset>(nd, X, Y);
             else
                 outside = 1;
             nd.g[m] = g;
@@ -210,7 +241,7 @@ __device__ __forceinline__ int refine_node(const MaskedNode& nd, const MaskedArg
         for (int m = nd.lane; m < nd.nv; m += 64) {
             const double res = nd.fd[m] - q * nd.g[m];
             double J[6];
-            jacobian(nd, m, nd.index[m], J);
+            jacobian(nd, m, pixel_of<kMasked>(nd, m), J);
 #pragma unroll
             for (int i = 0; i < 6; ++i) b[i] += J[i] * res;
         }
@@ -244,7 +275,7 @@ __device__ __forceinline__ int refine_node(const MaskedNode& nd, const MaskedArg
 }
 
 // A wave's node from its inputs to its outputs.
-template <typename Offset>
+template <typename Offset, typename Sampler, bool kMasked>
 __global__ __launch_bounds__(64 * kMaskedMaxWaves) void subset_refine_masked_kernel(MaskedArgs a, BatchArg batch)
 {
     extern __shared__ __attribute__((aligned(16))) double s_masked[];
@@ -258,7 +289,7 @@ __global__ __launch_bounds__(64 * kMaskedMaxWaves) void subset_refine_masked_ker
     MaskedNode nd;
     nd.f0 = a.f0 + inst;
     nd.f1 = a.f1 + inst;
-    nd.mask = a.mask + inst;
+    nd.mask = kMasked ? a.mask + inst : nullptr;
     nd.fd = s_masked + static_cast<size_t>(wave) * (a.wave_bytes / sizeof(double));
     nd.fx = nd.fd + a.slice;
     nd.fy = nd.fx + a.slice;
@@ -290,18 +321,18 @@ __global__ __launch_bounds__(64 * kMaskedMaxWaves) void subset_refine_masked_ker
     unsigned iterations = 0;
     int state;
     // (the centre lies inside the frame: the grid does; every lane loads the same word, so the branch is the wave's)
-    if (excluded_at<Offset>(nd.mask, nd.cx, nd.cy, nd.pitch))
+    if (kMasked && excluded_at<Offset>(nd.mask, nd.cx, nd.cy, nd.pitch))
         state = kStateMasked;
     else if (!(finite(u0) && finite(v0) && finite(g0[0]) && finite(g0[1]) && finite(g0[2]) && finite(g0[3])))
         state = kStateNoInput;
     else if (!(nd.cx - nd.R >= 0 && nd.cy - nd.R >= 0 && nd.cx + nd.R <= a.w - 1 && nd.cy + nd.R <= a.h - 1))
         state = kStateStrayed;
     else {
-        nd.nv = compact_usable<Offset>(nd);
-        if (!(nd.nv >= a.min_pixels))
+        nd.nv = kMasked ? compact_usable<Offset>(nd) : fill_all<Offset>(nd);
+        if (kMasked && !(nd.nv >= a.min_pixels))
             state = kStateMasked;
         else
-            state = refine_node<Offset>(nd, a, p, score, iterations);
+            state = refine_node<Offset, Sampler, kMasked>(nd, a, p, score, iterations);
     }
     if (lane != 0) return;
 
@@ -338,31 +369,24 @@ __global__ __launch_bounds__(64 * kMaskedMaxWaves) void subset_refine_masked_ker
     }
 }
 
-}  // namespace
-
-extern "C" {
-
-int flow2d_subset_refine_masked_2d(flow2d_context* ctx, const float* frame_0, const float* frame_1, size_t width, size_t height,
-                                   size_t pitch_bytes, const float* node_u0, const float* node_v0, const float* node_ux0,
-                                   const float* node_uy0, const float* node_vx0, const float* node_vy0, size_t nw, size_t nh,
-                                   size_t node_pitch_bytes, int grid_radius, int spacing, int subset_radius, int max_iterations,
-                                   float epsilon, float max_shift, float max_gradient, const float* mask, int min_pixels, float* out_u,
-                                   float* out_v, float* out_ux, float* out_uy, float* out_vx, float* out_vy, float* out_score,
-                                   float* out_state, flow2d_subset_record* record)
+// The body of both entries; frame_1 is the frame for CatmullRom and its coefficients for BSpline.  mask may be null (the spline
+// entry's; flow2d_subset_refine_masked_2d forwards such a call before it gets here): min_pixels is then not looked at.
+template <typename Sampler>
+int subset_refine_masked(flow2d_context* ctx, const float* frame_0, const float* frame_1, size_t width, size_t height,
+                         size_t pitch_bytes, const float* node_u0, const float* node_v0, const float* node_ux0, const float* node_uy0,
+                         const float* node_vx0, const float* node_vy0, size_t nw, size_t nh, size_t node_pitch_bytes, int grid_radius,
+                         int spacing, int subset_radius, int max_iterations, float epsilon, float max_shift, float max_gradient,
+                         const float* mask, int min_pixels, float* out_u, float* out_v, float* out_ux, float* out_uy, float* out_vx,
+                         float* out_vy, float* out_score, float* out_state, flow2d_subset_record* record)
 {
-    if (mask == nullptr)  // (min_pixels is not looked at) every byte and the record of flow2d_subset_refine_from_2d: its kernel
-        return flow2d_subset_refine_from_2d(ctx, frame_0, frame_1, width, height, pitch_bytes, node_u0, node_v0, node_ux0, node_uy0,
-                                            node_vx0, node_vy0, nw, nh, node_pitch_bytes, grid_radius, spacing, subset_radius,
-                                            max_iterations, epsilon, max_shift, max_gradient, out_u, out_v, out_ux, out_uy, out_vx, out_vy,
-                                            out_score, out_state, record);
     if (ctx == nullptr) return FLOW2D_ERR_INVALID_ARGUMENT;
     // (every check that needs no context field comes first: they hold without a device)
-    if (!flow2d::planes_ok({frame_0, frame_1, mask}, {}, width, height, pitch_bytes)) return FLOW2D_ERR_INVALID_ARGUMENT;
+    if (!flow2d::planes_ok({frame_0, frame_1}, {mask}, width, height, pitch_bytes)) return FLOW2D_ERR_INVALID_ARGUMENT;
     const int shared = flow2d::subset_refine_args_status(width, height, nw, nh, grid_radius, spacing, 1, subset_radius, max_iterations,
                                                          epsilon, {max_shift, max_gradient}, record);
     if (shared == FLOW2D_ERR_INVALID_ARGUMENT) return shared;
     const int pixels = (2 * subset_radius + 1) * (2 * subset_radius + 1);
-    if (min_pixels < FLOW2D_SUBSET_MIN_PIXELS || min_pixels > pixels) return FLOW2D_ERR_INVALID_ARGUMENT;
+    if (mask != nullptr && (min_pixels < FLOW2D_SUBSET_MIN_PIXELS || min_pixels > pixels)) return FLOW2D_ERR_INVALID_ARGUMENT;
     const bool gradients = out_ux != nullptr;
     if ((out_uy != nullptr) != gradients || (out_vx != nullptr) != gradients || (out_vy != nullptr) != gradients)
         return FLOW2D_ERR_INVALID_ARGUMENT;
@@ -405,10 +429,50 @@ int flow2d_subset_refine_masked_2d(flow2d_context* ctx, const float* frame_0, co
     // (the largest offset a lane forms into a frame or the mask is below height * pitch_bytes; the node planes are addressed in 64 bits)
     flow2d::launch_by_span(height * pitch_bytes, [&](auto offset) {
         const dim3 grid(flow2d::div_up(nw * nh, waves), 1, flow2d::batch_z(ctx, 1)), block(64 * waves);
-        subset_refine_masked_kernel<decltype(offset)><<<grid, block, waves * wave_bytes, ctx->stream>>>(a, flow2d::batch_arg(ctx, 1));
+        if (mask != nullptr)
+            subset_refine_masked_kernel<decltype(offset), Sampler, true><<<grid, block, waves * wave_bytes, ctx->stream>>>(a, flow2d::batch_arg(ctx, 1));
+        else if constexpr (std::is_same_v<Sampler, BSpline>)  // (the Catmull-Rom entry forwards a call without a mask: no such kernel)
+            subset_refine_masked_kernel<decltype(offset), Sampler, false><<<grid, block, waves * wave_bytes, ctx->stream>>>(a, flow2d::batch_arg(ctx, 1));
     });
     FLOW2D_CHECK_LAUNCH();
     return FLOW2D_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int flow2d_subset_refine_masked_2d(flow2d_context* ctx, const float* frame_0, const float* frame_1, size_t width, size_t height,
+                                   size_t pitch_bytes, const float* node_u0, const float* node_v0, const float* node_ux0,
+                                   const float* node_uy0, const float* node_vx0, const float* node_vy0, size_t nw, size_t nh,
+                                   size_t node_pitch_bytes, int grid_radius, int spacing, int subset_radius, int max_iterations,
+                                   float epsilon, float max_shift, float max_gradient, const float* mask, int min_pixels, float* out_u,
+                                   float* out_v, float* out_ux, float* out_uy, float* out_vx, float* out_vy, float* out_score,
+                                   float* out_state, flow2d_subset_record* record)
+{
+    if (mask == nullptr)  // (min_pixels is not looked at) every byte and the record of flow2d_subset_refine_from_2d: its kernel
+        return flow2d_subset_refine_from_2d(ctx, frame_0, frame_1, width, height, pitch_bytes, node_u0, node_v0, node_ux0, node_uy0,
+                                            node_vx0, node_vy0, nw, nh, node_pitch_bytes, grid_radius, spacing, subset_radius,
+                                            max_iterations, epsilon, max_shift, max_gradient, out_u, out_v, out_ux, out_uy, out_vx, out_vy,
+                                            out_score, out_state, record);
+    return subset_refine_masked<CatmullRom>(ctx, frame_0, frame_1, width, height, pitch_bytes, node_u0, node_v0, node_ux0, node_uy0,
+                                            node_vx0, node_vy0, nw, nh, node_pitch_bytes, grid_radius, spacing, subset_radius,
+                                            max_iterations, epsilon, max_shift, max_gradient, mask, min_pixels, out_u, out_v, out_ux,
+                                            out_uy, out_vx, out_vy, out_score, out_state, record);
+}
+
+int flow2d_subset_refine_spline_2d(flow2d_context* ctx, const float* frame_0, const float* coeff_1, size_t width, size_t height,
+                                   size_t pitch_bytes, const float* node_u0, const float* node_v0, const float* node_ux0,
+                                   const float* node_uy0, const float* node_vx0, const float* node_vy0, size_t nw, size_t nh,
+                                   size_t node_pitch_bytes, int grid_radius, int spacing, int subset_radius, int max_iterations,
+                                   float epsilon, float max_shift, float max_gradient, const float* mask, int min_pixels, float* out_u,
+                                   float* out_v, float* out_ux, float* out_uy, float* out_vx, float* out_vy, float* out_score,
+                                   float* out_state, flow2d_subset_record* record)
+{
+    return subset_refine_masked<BSpline>(ctx, frame_0, coeff_1, width, height, pitch_bytes, node_u0, node_v0, node_ux0, node_uy0,
+                                         node_vx0, node_vy0, nw, nh, node_pitch_bytes, grid_radius, spacing, subset_radius,
+                                         max_iterations, epsilon, max_shift, max_gradient, mask, min_pixels, out_u, out_v, out_ux,
+                                         out_uy, out_vx, out_vy, out_score, out_state, record);
 }
 
 }  // extern "C"

@@ -32,6 +32,7 @@ struct flow2d_host_params {
 struct flow2d_host_flow {
     OpticalFlow2D flow;
     size_t width = 0, height = 0;
+    int subset_interpolation = OpticalFlow2D::SubsetOptions::CatmullRom;  // flow2d_host_set_subset_interpolation
 };
 
 namespace {
@@ -728,7 +729,10 @@ HOST_API int flow2d_host_correlate_multipass(flow2d_host_flow* h, const float* f
 // Every entry that refines takes OpticalFlow2D::SubsetOptions as one record (null: refused) and its outputs as the fourteen slots
 // of OpticalFlow2D::SubsetPlanes -- u, v, ux, uy, vx, vy, score, state, then uxx, uxy, uyy, vxx, vxy, vyy --, per step in the
 // sequence forms.  The six curvatures go with order 2: at order 1 a slot of theirs that is set is refused, and the host-image
-// forms allocate and copy the eight images only.  A new field of SubsetOptions is a new field of the record, not a new entry.
+// forms allocate and copy the eight images only.  A new field of SubsetOptions is a new field of the record, not a new entry --
+// with one exception, SubsetOptions::interpolation: the record's size and field list are what callers built against the library
+// hold (40 bytes, nine fields), so the choice travels beside it, kept in the object by flow2d_host_set_subset_interpolation and
+// copied into the SubsetOptions every entry below builds.
 struct flow2d_host_subset_options {
     int radius, iterations;
     float epsilon, max_shift, max_gradient;
@@ -744,9 +748,10 @@ constexpr int kSubsetSlots = 14;
 
 // (the mask of a host-image entry stays its host address here: the mark SubsetOptionsOk looks at -- CorrelateSubset* take the
 // image itself and do not look at the field)
-OpticalFlow2D::SubsetOptions subset_options(const flow2d_host_subset_options& record)
+OpticalFlow2D::SubsetOptions subset_options(const flow2d_host_subset_options& record, const flow2d_host_flow* h = nullptr)
 {
     OpticalFlow2D::SubsetOptions o;
+    if (h) o.interpolation = h->subset_interpolation;
     o.radius = record.radius;
     o.iterations = record.iterations;
     o.epsilon = record.epsilon;
@@ -790,6 +795,21 @@ HOST_API int flow2d_host_subset_options_ok(const flow2d_host_subset_options* opt
     return options && OpticalFlow2D::SubsetOptionsOk(subset_options(*options)) ? 1 : 0;
 }
 
+// Whether `kind` is a value of OpticalFlow2D::SubsetOptions::Interpolation.  Needs no device.
+HOST_API int flow2d_host_subset_interpolation_ok(int kind)
+{
+    return kind == OpticalFlow2D::SubsetOptions::CatmullRom || kind == OpticalFlow2D::SubsetOptions::BSpline ? 1 : 0;
+}
+
+// OpticalFlow2D::SubsetOptions::interpolation of every later call of this object that refines: 0 Catmull-Rom (what a new object
+// has), 1 cubic B-spline.  0 on success, 1 for a null object or an unknown kind, which changes nothing.
+HOST_API int flow2d_host_set_subset_interpolation(flow2d_host_flow* h, int kind)
+{
+    if (!h || !flow2d_host_subset_interpolation_ok(kind)) return 1;
+    h->subset_interpolation = kind;
+    return 0;
+}
+
 // OpticalFlow2D::SubsetMinPixels: the default min_pixels of a radius.
 HOST_API int flow2d_host_subset_min_pixels(int radius)
 {
@@ -805,7 +825,7 @@ HOST_API int flow2d_host_refine_nodes_device(flow2d_host_flow* h, void* dev_fram
                                              void* const* dev_out, flow2d_subset_record* record)
 {
     if (!h || !dev_frame_0 || !dev_frame_1 || !dev_node_u0 || !dev_node_v0 || !options) return 1;
-    const auto subset = subset_options(*options);
+    const auto subset = subset_options(*options, h);
     if (!subset_accepted(subset, dev_out)) return 1;
     h->flow.timing_mode = 0;
     return h->flow.RefineNodesDevice(dp(dev_frame_0), dp(dev_frame_1), dp(dev_node_u0), dp(dev_node_v0), grid_radius, spacing, subset,
@@ -827,7 +847,7 @@ HOST_API int flow2d_host_correlate_subset_device(flow2d_host_flow* h, void* dev_
     if (!h || !dev_frame_0 || !dev_frame_1 || !options || count < 0 || (dev_flow_u == nullptr) != (dev_flow_v == nullptr) ||
         (dev_predictor_u == nullptr) != (dev_predictor_v == nullptr))
         return 1;
-    const auto subset = subset_options(*options);
+    const auto subset = subset_options(*options, h);
     if (!OpticalFlow2D::CorrelationPassesOk(h->width, h->height, lo, scale, list.data(), list.size(), min_score, validation) ||
         !subset_accepted(subset, dev_out))
         return 1;
@@ -853,7 +873,7 @@ HOST_API int flow2d_host_correlate_subset(flow2d_host_flow* h, const float* fram
     if (!h || !frame_0 || !frame_1 || !options || !nodes || !nodes[0] || !nodes[1] || count < 0 ||
         (flow_u == nullptr) != (flow_v == nullptr) || (predictor_u == nullptr) != (predictor_v == nullptr))
         return 1;
-    const auto subset = subset_options(*options);
+    const auto subset = subset_options(*options, h);
     HostImages im(h);
     Data2D *f0 = im.In(frame_0), *f1 = im.In(frame_1);
     Data2D *pu = predictor_u ? im.In(predictor_u) : nullptr, *pv = predictor_v ? im.In(predictor_v) : nullptr;
@@ -909,7 +929,7 @@ HOST_API int flow2d_host_refine_nodes_from_device(flow2d_host_flow* h, void* dev
                                                   void* const* dev_out, flow2d_subset_record* record)
 {
     if (!h || !dev_frame_0 || !dev_frame_1 || !dev_start || !options) return 1;
-    const auto subset = subset_options(*options);
+    const auto subset = subset_options(*options, h);
     if (!subset_accepted(subset, dev_out)) return 1;
     for (int k = 0; k < 6; ++k)
         if (!dev_start[k]) return 1;
@@ -940,7 +960,7 @@ HOST_API int flow2d_host_correlate_subset_sequence_device(flow2d_host_flow* h, v
     const auto validation = validation_options(threshold, epsilon, min_neighbours, 1, 1);
     const auto sequence = sequence_options(fill, min_state, predict_neighbours, sequence_max_shift);
     if (!h || !dev_frames || frames < 2 || count < 0 || !dev_out || !options) return 1;
-    const auto subset = subset_options(*options);
+    const auto subset = subset_options(*options, h);
     const size_t n = static_cast<size_t>(frames), step_count = n - 1;
     if (!OpticalFlow2D::CorrelationPassesOk(h->width, h->height, lo, scale, list.data(), list.size(), min_score, validation) ||
         !subset_accepted(subset, dev_out, step_count) || !OpticalFlow2D::SequenceOptionsOk(sequence))
@@ -980,7 +1000,7 @@ HOST_API int flow2d_host_correlate_subset_sequence(flow2d_host_flow* h, const fl
     const auto validation = validation_options(threshold, epsilon, min_neighbours, 1, 1);
     const auto sequence = sequence_options(fill, min_state, predict_neighbours, sequence_max_shift);
     if (!h || !frames || count_frames < 2 || !nodes || count < 0 || !options) return 1;
-    const auto subset = subset_options(*options);
+    const auto subset = subset_options(*options, h);
     const size_t n = static_cast<size_t>(count_frames), step_count = n - 1;
     for (size_t k = 0; k < n; ++k)
         if (!frames[k]) return 1;

@@ -107,6 +107,11 @@
 // specimen"; with --subset-mask-invert it is a region image, non-zero meaning "inside".  A subset is refined on its usable pixels; a
 // node off the specimen, or with fewer than N usable pixels, is masked: state -4 and NaN in the node files.  One more line,
 // "SubsetMask: {json}" -- "masked", the masked nodes, and "min_pixels" -- is printed.  Without the option no byte of any output changes.
+// --subset-interpolation catmull-rom|bspline, valid only together with --subset-refine, says how frame 1 is sampled
+// (OpticalFlow2D::SubsetOptions::interpolation): with bspline the run prefilters FILE_1 into its cubic B-spline coefficients
+// (flow2d_bspline_prefilter_2d) and refines with flow2d_subset_refine_spline_2d or, with --subset-order 2,
+// flow2d_subset_refine2_spline_2d; it goes with --subset-mask and --subset-previous.  One more line, "SubsetInterpolation: {json}" --
+// "interpolation" and, for bspline, "horizon" -- is printed.  Without the option no byte of any output changes.
 // --initial-flow FILE.flo | --correlation-prior R  [--prior-reach P, pixels, finite and > 0, default 2] [--prior-level L, >= 0]
 // start the variational pyramid from a prior flow instead of from zero at its coarsest level (OpticalFlow2D::ComputeFlowFromPrior /
 // ComputeFlowCorrelationSeeded): the prior is a Middlebury file of the frames' size, or the window correlation of the pair with
@@ -183,6 +188,7 @@ int main(int argc, char** argv)
     std::vector<OpticalFlow2D::CorrelationPass> correlation_passes;  // --correlation-passes R:D:S[,R:D:S...]
     OpticalFlow2D::SubsetOptions subset;  // --subset-refine R and the --subset-* options
     bool subset_refine = false, subset_option = false;
+    bool subset_interpolation_given = false;  // --subset-interpolation catmull-rom|bspline
     OpticalFlow2D::SequenceOptions sequence;  // --subset-previous PREFIX and its options
     std::string subset_previous;
     bool sequence_option = false, subset_max_shift_given = false, subset_curvature_given = false;
@@ -459,6 +465,19 @@ int main(int argc, char** argv)
             }
             subset.order = static_cast<int>(n);
             subset_option = true;
+            ++i;
+        }
+        else if (!std::strcmp(argv[i], "--subset-interpolation")) {
+            const char* kind = (i + 1 < argc) ? argv[i + 1] : "";
+            if (!std::strcmp(kind, "catmull-rom"))
+                subset.interpolation = OpticalFlow2D::SubsetOptions::CatmullRom;
+            else if (!std::strcmp(kind, "bspline"))
+                subset.interpolation = OpticalFlow2D::SubsetOptions::BSpline;
+            else {
+                std::printf("--subset-interpolation takes catmull-rom or bspline.\n");
+                return 5;
+            }
+            subset_option = subset_interpolation_given = true;
             ++i;
         }
         else if (!std::strcmp(argv[i], "--subset-max-curvature")) {
@@ -915,6 +934,12 @@ int main(int argc, char** argv)
                 if (subset_mask_image)
                     std::printf("SubsetMask: {\"masked\": %llu, \"min_pixels\": %d}\n", record.reserved, OpticalFlow2D::SubsetMinPixels(subset));
                 for (int k = 0; k < node_images; ++k) images[k].WriteRAWToFileF32((output_path + counter + names[k] + size).c_str());
+                if (subset_interpolation_given) {
+                    if (subset.interpolation == OpticalFlow2D::SubsetOptions::BSpline)
+                        std::printf("SubsetInterpolation: {\"interpolation\": \"bspline\", \"horizon\": %d}\n", FLOW2D_BSPLINE_HORIZON);
+                    else
+                        std::printf("SubsetInterpolation: {\"interpolation\": \"catmull-rom\"}\n");
+                }
                 if (subset.order == 2) std::printf("SubsetOrder: {\"order\": 2, \"max_curvature\": %.9g}\n", subset.max_curvature);
                 std::printf("Subset: {\"radius\": %d, \"iterations\": %d, \"epsilon\": %.9g, \"max_shift\": %.9g, \"max_gradient\": %.9g, "
                             "\"passes\": %zu, \"grid_radius\": %d, \"spacing\": %d, \"nw\": %zu, \"nh\": %zu, \"lo\": %.9g, \"scale\": %.9g, "

@@ -346,6 +346,12 @@ public:
         // its own.  Order 1 only: SubsetOptionsOk refuses a mask with order 2.
         DevicePtr mask = 0;
         int min_pixels = 0;
+        // How frame 1 is sampled.  BSpline: every call that refines prefilters its frame 1 -- in a sequence every step its frame k
+        // -- into a plane of the object's own (flow2d_bspline_prefilter_2d) and calls the spline entry of its order
+        // (flow2d_subset_refine_spline_2d, flow2d_subset_refine2_spline_2d); mask and start gradients go through.  A tenth of the
+        // Catmull-Rom sample's interpolation bias for the same sixteen taps and one more launch per frame.
+        enum Interpolation { CatmullRom = 0, BSpline = 1 };
+        int interpolation = CatmullRom;
     };
     // min_pixels as the refinement gets it: the default where it is 0
     static int SubsetMinPixels(const SubsetOptions& subset);
@@ -771,6 +777,8 @@ private:
                                 CorrelationPassReport* reports_out, DevicePtr dev_flow_u, DevicePtr dev_flow_v, bool synchronise);
     // RefineNodes* / CorrelateSubset*: the chain's nodes (u, v), the refined ones where the caller gave none (u, v); the record
     OwnedPlanes subset_planes_{owned_, 4};
+    // SubsetOptions::BSpline: the coefficients of the frame 1 of the call under way (first use)
+    OwnedPlanes spline_plane_{owned_, 1};
     DeviceScratch subset_scratch_{owned_};
     // RefineNodesDevice without its synchronisation; *refined gets the planes (u, v) that were written
     // start_gradients (optional): ux0, uy0, vx0, vy0 of flow2d_subset_refine_from_2d

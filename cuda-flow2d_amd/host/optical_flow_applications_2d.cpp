@@ -780,6 +780,11 @@ bool OpticalFlow2D::SubsetOptionsOk(const SubsetOptions& subset)
                     FLOW2D_SUBSET_MIN_PIXELS, subset.min_pixels, subset.radius);
         return false;
     }
+    if (subset.interpolation != SubsetOptions::CatmullRom && subset.interpolation != SubsetOptions::BSpline) {
+        std::printf("Error: subset refinement samples frame 1 with Catmull-Rom weights (%d) or a cubic B-spline (%d), not %d.\n",
+                    SubsetOptions::CatmullRom, SubsetOptions::BSpline, subset.interpolation);
+        return false;
+    }
     if (subset.radius >= 1 && subset.radius <= FLOW2D_SUBSET_MAX_RADIUS && subset.iterations >= 1 &&
         subset.iterations <= FLOW2D_SUBSET_MAX_ITERATIONS && std::isfinite(subset.epsilon) && subset.epsilon >= 0.f &&
         std::isfinite(subset.max_shift) && subset.max_shift > 0.f && std::isfinite(subset.max_gradient) && subset.max_gradient > 0.f &&
@@ -822,18 +827,48 @@ bool OpticalFlow2D::QueueRefineNodes(DevicePtr dev_frame_0, DevicePtr dev_frame_
     auto plane = [](DevicePtr p) { return p ? AsPlane(p) : nullptr; };
     // (the node planes are containers: the frames' pitch; the entry refuses planes that meet)
     bool ok;
+    const bool spline = subset.interpolation == SubsetOptions::BSpline;
+    if (spline) {
+        // frame 1's coefficients, on the same stream in front of the refinement that samples them
+        if (!EnsurePlanes(spline_plane_, 1) ||
+            CheckFlow2DError(flow2d_bspline_prefilter_2d(context_, AsPlane(dev_frame_1), AsPlane(spline_plane_[0]), W, H, pitch),
+                             "flow2d_bspline_prefilter_2d"))
+            return false;
+    }
     if (subset.order == 2) {
         // the start: the gradients where the caller has them, no curvatures (0)
         const float* start[4] = {nullptr, nullptr, nullptr, nullptr};
         for (int k = 0; start_gradients && k < 4; ++k) start[k] = plane(start_gradients[k]);
         float* const out_gradients[4] = {plane(out.ux), plane(out.uy), plane(out.vx), plane(out.vy)};
         float* const out_curvatures[6] = {plane(out.uxx), plane(out.uxy), plane(out.uyy), plane(out.vxx), plane(out.vxy), plane(out.vyy)};
-        ok = !CheckFlow2DError(flow2d_subset_refine2_2d(context_, AsPlane(dev_frame_0), AsPlane(dev_frame_1), W, H, pitch,
-                                                        AsPlane(dev_node_u0), AsPlane(dev_node_v0), start_gradients ? start : nullptr, nullptr,
-                                                        nw, nh, pitch, grid_radius, spacing, subset.radius, subset.iterations, subset.epsilon,
-                                                        subset.max_shift, subset.max_gradient, subset.max_curvature, AsPlane(u), AsPlane(v),
-                                                        out_gradients, out_curvatures, plane(out.score), plane(out.state), record),
-                               "flow2d_subset_refine2_2d");
+        if (spline)
+            ok = !CheckFlow2DError(flow2d_subset_refine2_spline_2d(context_, AsPlane(dev_frame_0), AsPlane(spline_plane_[0]), W, H, pitch,
+                                                                   AsPlane(dev_node_u0), AsPlane(dev_node_v0), start_gradients ? start : nullptr,
+                                                                   nullptr, nw, nh, pitch, grid_radius, spacing, subset.radius,
+                                                                   subset.iterations, subset.epsilon, subset.max_shift, subset.max_gradient,
+                                                                   subset.max_curvature, AsPlane(u), AsPlane(v), out_gradients, out_curvatures,
+                                                                   plane(out.score), plane(out.state), record),
+                                   "flow2d_subset_refine2_spline_2d");
+        else
+            ok = !CheckFlow2DError(flow2d_subset_refine2_2d(context_, AsPlane(dev_frame_0), AsPlane(dev_frame_1), W, H, pitch,
+                                                            AsPlane(dev_node_u0), AsPlane(dev_node_v0), start_gradients ? start : nullptr,
+                                                            nullptr, nw, nh, pitch, grid_radius, spacing, subset.radius, subset.iterations,
+                                                            subset.epsilon, subset.max_shift, subset.max_gradient, subset.max_curvature,
+                                                            AsPlane(u), AsPlane(v), out_gradients, out_curvatures, plane(out.score),
+                                                            plane(out.state), record),
+                                   "flow2d_subset_refine2_2d");
+    } else if (spline) {
+        // (one entry for every first-order call: mask and start gradients may both be absent)
+        const DevicePtr none[4] = {0, 0, 0, 0};
+        const DevicePtr* g = start_gradients ? start_gradients : none;
+        ok = !CheckFlow2DError(flow2d_subset_refine_spline_2d(context_, AsPlane(dev_frame_0), AsPlane(spline_plane_[0]), W, H, pitch,
+                                                              AsPlane(dev_node_u0), AsPlane(dev_node_v0), plane(g[0]), plane(g[1]), plane(g[2]),
+                                                              plane(g[3]), nw, nh, pitch, grid_radius, spacing, subset.radius,
+                                                              subset.iterations, subset.epsilon, subset.max_shift, subset.max_gradient,
+                                                              plane(subset.mask), SubsetMinPixels(subset), AsPlane(u), AsPlane(v),
+                                                              plane(out.ux), plane(out.uy), plane(out.vx), plane(out.vy), plane(out.score),
+                                                              plane(out.state), record),
+                               "flow2d_subset_refine_spline_2d");
     } else if (subset.mask) {
         // (without a start the entry takes the zero gradients of flow2d_subset_refine_2d)
         const DevicePtr none[4] = {0, 0, 0, 0};

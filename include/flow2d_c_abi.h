@@ -49,7 +49,9 @@ extern "C" {
  * correlation nodes) and flow2d_subset_refine_from_2d / flow2d_predict_nodes_2d (DIC over a sequence: the refinement started
  * from the previous step's deformation, and that start built from a step's result) and flow2d_node_strain_2d /
  * flow2d_node_strain_workspace_bytes (strain on the node grid from least-squares strain windows) and
- * flow2d_subset_refine_masked_2d (the refinement on a region of interest) were added under 1. */
+ * flow2d_subset_refine_masked_2d (the refinement on a region of interest) and flow2d_bspline_prefilter_2d /
+ * flow2d_subset_refine_spline_2d / flow2d_subset_refine2_spline_2d (the refinement with a cubic B-spline interpolation of the
+ * deformed frame) were added under 1. */
 #define FLOW2D_ABI_VERSION 1
 
 typedef enum flow2d_status {
@@ -1214,6 +1216,71 @@ FLOW2D_API int flow2d_subset_refine2_2d(flow2d_context* ctx, const float* frame_
                                         float* const* out_curvatures /* NULL, or uxx, uxy, uyy, vxx, vxy, vyy: all or none */,
                                         float* out_score /* may be NULL */, float* out_state /* may be NULL */,
                                         flow2d_subset_record* record /* device, may be NULL */);
+
+/* Cubic B-spline interpolation of the deformed frame (Unser, Aldroubi & Eden 1993; Schreier, Braasch & Sutton 2000 on the
+ * interpolation bias of DIC): the coefficients of a plane, and the two subset refinements sampling them in the place of the
+ * Catmull-Rom sample of frame 1.  Added to ABI version 1 without changing any existing entry.
+ * The arithmetic follows the rule of flow2d_subset_refine_2d's text: IEEE double, every operation rounded on its own, no fused
+ * multiply-add, positive comparisons.
+ *
+ * flow2d_bspline_prefilter_2d: dst = the cubic B-spline coefficients of src, times 36 -- see *Scale*.  The recursive filter is
+ * replaced by its symmetric impulse response truncated at H = FLOW2D_BSPLINE_HORIZON = 16 (|Z|^16 is about 7e-10, far below an
+ * fp32 ulp): every output depends on 33 x 33 inputs only, and nothing depends on a scan order.
+ * reflect(i, n): 0 when n = 1; otherwise p = 2(n - 1), m = i mod p taken non-negative, and the result is m when m <= n - 1, else
+ *   p - m.  Whole-sample mirroring, as often as it takes (n may be below 16).
+ * Constants, in double:  Z = sqrt(3.0) - 2.0;   z[0] = 1, z[j] = z[j - 1] * Z for j = 1 .. 16;   G = sqrt(3.0) / 6.0.
+ * A line s[0 .. n - 1] gives d[k], k = 0 .. n - 1:
+ *   acc = 0;   for j = 16 down to 1:  acc = acc + z[j] * (s[reflect(k - j, n)] + s[reflect(k + j, n)]);
+ *   acc = acc + s[k];   d[k] = G * acc.
+ * Rows first, on the floats converted to double; then columns on the rows' doubles, which are not rounded to float in between;
+ * the result is cast to float.
+ * Scale.  With G per axis a constant plane c gives c / 36: the sampler's weights below are six times the B-spline's per axis, so
+ *   that no division occurs per sample.
+ * One launch on the context's stream, no allocation, no synchronisation (graph-capturable); no atomics: alone, in a batch and in
+ * a replayed graph the same bytes.  Honours flow2d_context_set_batch (src and dst of instance b at b * stride floats).  Row
+ * padding and the containers beyond width x height are neither read into a result nor written.
+ * FLOW2D_ERR_INVALID_ARGUMENT, and nothing written, for a null pointer, a zero size, a bad pitch (the rule of
+ * flow2d_consistency_2d) or a dst that overlaps src, over every instance of a batch. */
+#define FLOW2D_BSPLINE_HORIZON 16
+FLOW2D_API int flow2d_bspline_prefilter_2d(flow2d_context* ctx, const float* src, float* dst, size_t width, size_t height,
+                                           size_t pitch_bytes);
+
+/* flow2d_subset_refine_masked_2d on the coefficients of frame 1: coeff_1, where frame_1 stands there, is a plane that
+ * flow2d_bspline_prefilter_2d made from frame 1 (same width, height and pitch_bytes; in a batch instance b at b * stride floats).
+ * The text of flow2d_subset_refine_masked_2d (and through it that of flow2d_subset_refine_from_2d) holds word for word except
+ *   2. Sampling.  g = the cubic B-spline sample of coeff_1 at (X, Y).  ix = floor(X), t = X - ix, u = 1.0 - t;
+ *        W0 = (u*u)*u;   W1 = ((3.0*t - 6.0)*t)*t + 4.0;   W2 = ((3.0*u - 6.0)*u)*u + 4.0;   W3 = (t*t)*t
+ *      The taps are columns reflect(ix - 1 + i, width), i = 0 .. 3, of coeff_1 -- reflected, not clamped: the extension the
+ *      prefilter assumed.  A row a0 .. a3 gives ((W0*a0 + W1*a1) + W2*a2) + W3*a3.  Rows reflect(iy - 1 + j, height) (iy =
+ *      floor(Y)) are combined in the same way with the weights of Y - iy.
+ * Frame 0's quantities, the central differences fx and fy among them, do not change.  The start gradients are given all or none.
+ * mask == NULL (min_pixels is then not looked at): the bytes of a mask that excludes nothing.
+ * Refusals.  Those of flow2d_subset_refine_masked_2d with coeff_1 in the place of frame_1: a coeff_1 that is null or breaks the
+ * frames' plane rules, or that meets a written range. */
+FLOW2D_API int flow2d_subset_refine_spline_2d(flow2d_context* ctx, const float* frame_0, const float* coeff_1, size_t width,
+                                              size_t height, size_t pitch_bytes, const float* node_u0, const float* node_v0,
+                                              const float* node_ux0 /* the four start gradients: all or none */,
+                                              const float* node_uy0, const float* node_vx0, const float* node_vy0, size_t nw, size_t nh,
+                                              size_t node_pitch_bytes, int grid_radius, int spacing, int subset_radius,
+                                              int max_iterations, float epsilon, float max_shift, float max_gradient,
+                                              const float* mask /* device, may be NULL */, int min_pixels, float* out_u, float* out_v,
+                                              float* out_ux /* the four gradient planes: all or none */, float* out_uy, float* out_vx,
+                                              float* out_vy, float* out_score /* may be NULL */, float* out_state /* may be NULL */,
+                                              flow2d_subset_record* record /* device, may be NULL */);
+
+/* flow2d_subset_refine2_2d on the coefficients of frame 1: its text word for word with coeff_1 in the place of frame_1 and
+ * 2. Sampling replaced by that of flow2d_subset_refine_spline_2d.  It takes no mask. */
+FLOW2D_API int flow2d_subset_refine2_spline_2d(flow2d_context* ctx, const float* frame_0, const float* coeff_1, size_t width,
+                                               size_t height, size_t pitch_bytes, const float* node_u0, const float* node_v0,
+                                               const float* const* start_gradients /* NULL, or ux0, uy0, vx0, vy0: all or none */,
+                                               const float* const* start_curvatures /* NULL, or uxx0, uxy0, uyy0, vxx0, vxy0, vyy0 */,
+                                               size_t nw, size_t nh, size_t node_pitch_bytes, int grid_radius, int spacing,
+                                               int subset_radius, int max_iterations, float epsilon, float max_shift,
+                                               float max_gradient, float max_curvature, float* out_u, float* out_v,
+                                               float* const* out_gradients /* NULL, or ux, uy, vx, vy: all or none */,
+                                               float* const* out_curvatures /* NULL, or uxx, uxy, uyy, vxx, vxy, vyy: all or none */,
+                                               float* out_score /* may be NULL */, float* out_state /* may be NULL */,
+                                               flow2d_subset_record* record /* device, may be NULL */);
 
 /* The start of the next step of a sequence from a step's result, out of place: a node the refinement found is kept, every other
  * node is predicted from its neighbours.  Every node is judged against the input, so the result depends on no order.
