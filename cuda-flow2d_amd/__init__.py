@@ -317,6 +317,20 @@ class PredictRecord(C.Structure):
 PREDICT_RECORD_BYTES = 64  # FLOW2D_PREDICT_RECORD_BYTES, checked by a static_assert in the header
 assert C.sizeof(PredictRecord) == PREDICT_RECORD_BYTES
 SEQUENCE_MAX_FILL = 4  # OpticalFlow2D::kSequenceMaxFill
+SUBSET_STATE_COMPOSED = 66  # FLOW2D_SUBSET_STATE_COMPOSED: the state flow2d_compose_nodes_2d gives a node it composed
+
+
+class ComposeRecord(C.Structure):
+    """flow2d_compose_record of include/flow2d_c_abi.h: the five counts flow2d_compose_nodes_2d writes per instance."""
+    _fields_ = [("nodes", C.c_ulonglong), ("composed", C.c_ulonglong), ("no_base", C.c_ulonglong), ("outside", C.c_ulonglong),
+                ("no_increment", C.c_ulonglong), ("reserved", C.c_ulonglong * 3)]
+
+    def summary(self):
+        return {name: getattr(self, name) for name, _ in self._fields_[:5]}
+
+
+COMPOSE_RECORD_BYTES = 64  # FLOW2D_COMPOSE_RECORD_BYTES, checked by a static_assert in the header
+assert C.sizeof(ComposeRecord) == COMPOSE_RECORD_BYTES
 
 
 class SequenceStepReport(C.Structure):
@@ -579,6 +593,8 @@ def hip_lib():
             L.flow2d_node_strain_workspace_bytes.restype = sz
             L.flow2d_node_strain_workspace_bytes.argtypes = [sz, sz, sz]
             L.flow2d_node_strain_2d.argtypes = [vp] + [vp] * 7 + [sz, sz, sz, i, i, i, i, i, i, C.POINTER(DeformationPlanes), vp, vp, sz]
+        if hasattr(L, "flow2d_compose_nodes_2d"):  # (absent from libraries of earlier rounds loaded for an A/B)
+            L.flow2d_compose_nodes_2d.argtypes = [vp, vp, vp, vp, sz, sz, sz, i, i, i, vp, vp, vp, vp]
         if hasattr(L, "flow2d_prior_registration_2d"):  # (absent from libraries of earlier rounds loaded for an A/B)
             L.flow2d_prior_registration_2d.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp, sz, sz, sz, f, f, vp, vp]
         if hasattr(L, "flow2d_propagate_flow_2d"):  # (absent from libraries of earlier rounds loaded for an A/B)
@@ -1481,6 +1497,53 @@ class Context:
                 q.free()
                 self._planes.remove(q)
 
+    def compose_records(self, instances=1):
+        """A Plane for `instances` flow2d_compose_record records (device memory)."""
+        return self._record_plane(COMPOSE_RECORD_BYTES, instances)
+
+    def read_compose_record(self, record, instances=1):
+        """The records of a compose_records Plane as ComposeRecord structures (synchronises)."""
+        return self._read_records(record, instances, ComposeRecord)
+
+    def compose_nodes(self, base, increment, nw, nh, grid_radius, spacing, min_state=1, score=None, out=None, out_state=None,
+                      out_score=None, record=True, instances=1):
+        """The composition of two node fields across a moved reference frame (flow2d_compose_nodes_2d), out of place: base =
+        (u, v, ux, uy, vx, vy, state) Planes of frame 0 -> frame r at the nodes of frame 0, increment = the same seven of
+        frame r -> frame k on the same grid (grid_radius, spacing) laid in frame r, `score` the increment's score Plane or None.
+        The increment is sampled where the base carries each node -- over the usable corners of its cell, each extrapolated along
+        its gradients -- and the deformation gradients are multiplied; a composed node gets the state SUBSET_STATE_COMPOSED, a
+        node without a usable base, carried more than half a cell off the grid or without a usable corner NaN and SUBSET_NO_INPUT.
+        out = six Planes of the caller's (and optionally out_state, and out_score with `score`), which stay on the device;
+        without them the call allocates them all, downloads them and returns arrays.  record: True, a compose_records Plane, or
+        False / None.
+        Returns ((u, v, ux, uy, vx, vy), state or None, score or None, ComposeRecord or None)."""
+        if len(base) != 7 or len(increment) != 7:
+            raise ValueError("compose_nodes takes the seven planes (u, v, ux, uy, vx, vy, state) of the base and of the increment")
+        own_planes = out is None
+        if not own_planes and len(out) != 6:
+            raise ValueError("compose_nodes takes six output planes or none")
+        own_record = record is True
+        if own_record and instances != 1:
+            raise ValueError("a lock-step batch takes the caller's records")
+        if own_planes:
+            held = [self.plane(base[0].pitch // 4, nh) for _ in range(7 if score is None else 8)] + ([None] if score is None else [])
+        else:
+            held = list(out) + [out_state, out_score]
+        rec = self.compose_records(instances) if own_record else (record or None)
+        ptr = lambda q: q.ptr if q is not None else None  # noqa: E731
+        try:
+            _check(hip_lib().flow2d_compose_nodes_2d(self.handle, (C.c_void_p * 7)(*[q.ptr for q in base]),
+                                                     (C.c_void_p * 7)(*[q.ptr for q in increment]), ptr(score), nw, nh, base[0].pitch,
+                                                     int(grid_radius), int(spacing), int(min_state),
+                                                     (C.c_void_p * 6)(*[q.ptr for q in held[:6]]), ptr(held[6]), ptr(held[7]), ptr(rec)),
+                   "flow2d_compose_nodes_2d")
+            got = [q.download(nw, nh) if q is not None else None for q in held] if own_planes else held
+            return tuple(got[:6]), got[6], got[7], (self.read_compose_record(rec, 1)[0] if own_record else None)
+        finally:
+            for q in ([q for q in held if q is not None] if own_planes else []) + ([rec] if own_record else []):
+                q.free()
+                self._planes.remove(q)
+
     @staticmethod
     def node_strain_workspace_bytes(nw, nh, instances=1):
         """flow2d_node_strain_workspace_bytes: what node_strain needs beside a record (host logic, no device)."""
@@ -1830,6 +1893,12 @@ def host_lib():
             L.flow2d_host_correlate_subset.argtypes = [vp, fp, fp] + passes + [so, fp, fp, fpp, rp, sr, fp, fp, fp]
             L.flow2d_host_correlate_subset_sequence_device.argtypes = [vp, pvp, i, f, f] + passes + [so] + sequence + [pvp, rp, st, pvp]
             L.flow2d_host_correlate_subset_sequence.argtypes = [vp, fpp, i] + passes + [so] + sequence + [fpp, rp, st, fpp, fp]
+        if hasattr(L, "flow2d_host_compose_nodes_device"):
+            cp = C.POINTER(ComposeRecord)
+            L.flow2d_host_set_reference_every.argtypes = [vp, i]
+            L.flow2d_host_compose_records.argtypes = [vp, cp, i]
+            L.flow2d_host_compose_nodes_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), i, i, i, C.POINTER(vp), cp]
+            L.flow2d_host_compose_nodes.argtypes = [vp, C.POINTER(fp), C.POINTER(fp), i, i, i, C.POINTER(fp), cp]
         if hasattr(L, "flow2d_host_node_strain_device"):
             ds = C.POINTER(DeformationStats)
             L.flow2d_host_strain_options_ok.argtypes = [i, i, i, i, i]
@@ -2548,7 +2617,7 @@ class OpticalFlow:
     def correlate_subset_sequence(self, frames, passes, radius, iterations=20, epsilon=1e-3, max_shift=2.0, max_gradient=0.5, min_score=-1.0,
                                   threshold=2.0, validate_epsilon=0.1, min_neighbours=3, fill=2, min_state=1, predict_neighbours=1,
                                   sequence_max_shift=4.0, flow=False, order=1, max_curvature=0.05, mask=None, min_pixels=0,
-                                  interpolation="catmull-rom"):
+                                  interpolation="catmull-rom", reference_every=0):
         """OpticalFlow2D::CorrelateSubsetSequence: digital image correlation over a loading sequence.  (order=2: every step refines
         at second order, the steps after the first from the prediction's first-order planes with zero curvatures; the nodes then
         go by the names of SUBSET2_PLANES.)  frames[0] is the reference and
@@ -2558,7 +2627,8 @@ class OpticalFlow:
         with sequence_max_shift in place of max_shift -- and no window search runs.  Returns ([nodes per step], [CorrelationPassReport]
         of step 1, [SequenceStepReport], (lo, scale)), nodes a dict of [nh, nw] arrays by the names of SUBSET_PLANES; with flow,
         also [(u, v) per step], the refined field expanded to the frame's grid.  mask (an image, uploaded once and used by every
-        step) / min_pixels: see _takes_mask."""
+        step) / min_pixels: see _takes_mask.  reference_every: see _moving_reference; the composition's records are left in
+        self.compose_records."""
         images = [np.ascontiguousarray(q, np.float32) for q in frames]
         if len(images) < 2 or any(q.shape != (self.height, self.width) for q in images):
             raise ValueError("correlate_subset_sequence takes two or more frames of the object's size")
@@ -2575,6 +2645,7 @@ class OpticalFlow:
         reports, reps, lo_scale = (CorrelationPassReport * n)(), (SequenceStepReport * steps)(), (C.c_float * 2)()
         options = self._subset_options("OpticalFlow2D::CorrelateSubsetSequence", radius, iterations, epsilon, max_shift, max_gradient, order,
                                        max_curvature, mask, min_pixels, image=True, interpolation=interpolation)
+        self._moving_reference("OpticalFlow2D::CorrelateSubsetSequence", reference_every)
         rc = host_lib().flow2d_host_correlate_subset_sequence(self.handle, (fpp * len(images))(*[_fptr(q) for q in images]), len(images), arr, n,
                                                               float(min_score), float(threshold), float(validate_epsilon), int(min_neighbours),
                                                               C.byref(options), int(fill), int(min_state), int(predict_neighbours),
@@ -2582,6 +2653,7 @@ class OpticalFlow:
                                                               (fpp * (2 * steps))(*[_fptr(q) for q in uv]) if flow else None, lo_scale)
         if rc:
             raise Flow2DError(rc, "OpticalFlow2D::CorrelateSubsetSequence")
+        self.compose_records = self._read_compose_records(steps)
         per_step = [dict(zip(names, nodes[per * k:per * k + per])) for k in range(steps)]
         out = (per_step, list(reports), list(reps), (lo_scale[0], lo_scale[1]))
         return out + ([(uv[2 * k], uv[2 * k + 1]) for k in range(steps)],) if flow else out
@@ -2589,13 +2661,14 @@ class OpticalFlow:
     def correlate_subset_sequence_device(self, dev_frames, lo, scale, passes, radius, dev_out, iterations=20, epsilon=1e-3, max_shift=2.0,
                                          max_gradient=0.5, min_score=-1.0, threshold=2.0, validate_epsilon=0.1, min_neighbours=3, fill=2,
                                          min_state=1, predict_neighbours=1, sequence_max_shift=4.0, dev_flows=None, order=1,
-                                         max_curvature=0.05, mask=None, min_pixels=0, interpolation="catmull-rom"):
+                                         max_curvature=0.05, mask=None, min_pixels=0, interpolation="catmull-rom", reference_every=0):
         """OpticalFlow2D::CorrelateSubsetSequenceDevice: device frames in (the first is the reference); dev_out: per step a dict of
         device planes by the names of SUBSET_PLANES, of which only the score may be missing; dev_flows: per step a (u, v) pair or
         None.  Returns ([CorrelationPassReport] of step 1, [SequenceStepReport]); synchronises once.  order=2: every step refines
         at second order -- the steps after the first from the prediction's six first-order planes with zero curvatures --, dev_out
         by the names of SUBSET2_PLANES, the six curvatures all or none per step.  mask (a device plane, used by every step) /
-        min_pixels: see _takes_mask."""
+        min_pixels: see _takes_mask.  reference_every: see _moving_reference; the composition's records are left in
+        self.compose_records."""
         arr, n = self._passes(passes)
         steps = len(dev_frames) - 1
         if steps < 1 or len(dev_out) != steps or (dev_flows is not None and len(dev_flows) != steps):
@@ -2612,6 +2685,7 @@ class OpticalFlow:
         reports, reps = (CorrelationPassReport * max(n, 1))(), (SequenceStepReport * steps)()
         options = self._subset_options("OpticalFlow2D::CorrelateSubsetSequenceDevice", radius, iterations, epsilon, max_shift, max_gradient,
                                        order, max_curvature, mask, min_pixels, interpolation=interpolation)
+        self._moving_reference("OpticalFlow2D::CorrelateSubsetSequenceDevice", reference_every)
         rc = host_lib().flow2d_host_correlate_subset_sequence_device(self.handle, (C.c_void_p * len(dev_frames))(*dev_frames), len(dev_frames),
                                                                      float(lo), float(scale), arr, n, float(min_score), float(threshold),
                                                                      float(validate_epsilon), int(min_neighbours), C.byref(options), int(fill),
@@ -2619,7 +2693,68 @@ class OpticalFlow:
                                                                      (C.c_void_p * (14 * steps))(*planes), reports, reps, flows)
         if rc:
             raise Flow2DError(rc, "OpticalFlow2D::CorrelateSubsetSequenceDevice")
+        self.compose_records = self._read_compose_records(steps)
         return list(reports)[:n], list(reps)
+
+    def _moving_reference(self, where, reference_every):
+        """SequenceOptions::reference_every of the sequence call that follows: 0 -- every step against frame 0, what it always was --
+        or N >= 1: step k is measured against frame N * floor((k - 1) / N) and composed with the field up to that frame
+        (flow2d_compose_nodes_2d), so that every delivered field is still frame 0 -> frame k at the nodes of frame 0, with the
+        state SUBSET_STATE_COMPOSED or SUBSET_NO_INPUT.  Refused with a mask and with curvature planes.  The value is the object's
+        (flow2d_host_set_reference_every) and is set before every sequence call, so that a call without the keyword is never
+        moved by an earlier one."""
+        if host_lib().flow2d_host_set_reference_every(self.handle, int(reference_every)):
+            raise Flow2DError(1, where)
+
+    def _read_compose_records(self, steps):
+        """The composition records of the sequence call just made: one ComposeRecord per step, zero where the step was measured
+        against frame 0."""
+        records = (ComposeRecord * steps)()
+        host_lib().flow2d_host_compose_records(self.handle, records, steps)
+        return list(records)
+
+    COMPOSE_BASE = ("u", "v", "ux", "uy", "vx", "vy", "state")  # what compose_nodes* read of the base's SUBSET_PLANES
+
+    def compose_nodes(self, base, increment, grid_radius, spacing, min_state=1, record=True):
+        """OpticalFlow2D::ComposeNodes: the composition of two node fields across a moved reference (flow2d_compose_nodes_2d).  base --
+        frame 0 -> frame r at the nodes of frame 0 -- and increment -- frame r -> frame k on the same grid laid in frame r -- are
+        dicts of [nh, nw] arrays by the names of SUBSET_PLANES, as correlate_subset* return them; u, v, the gradients and the state
+        are needed, the increment's score is blended when it is there.  Returns ({name: [nh, nw] array} by the names of
+        SUBSET_PLANES -- without "score" when the increment has none --, ComposeRecord or None)."""
+        nw, nh = correlation_grid(self.width, self.height, grid_radius, spacing)
+        need = self.COMPOSE_BASE
+        if any(n not in base for n in need) or any(n not in increment for n in need):
+            raise ValueError("compose_nodes takes %s of base and increment" % ", ".join(need))
+        a = [np.ascontiguousarray(base[n], np.float32) for n in need]
+        names = [n for n in self.SUBSET_PLANES if n != "score" or increment.get("score") is not None]
+        b = {n: np.ascontiguousarray(increment[n], np.float32) for n in names}
+        if any(q.shape != (nh, nw) for q in a + list(b.values())):
+            raise ValueError("compose_nodes takes node fields of the %d x %d grid" % (nw, nh))
+        out = {n: np.empty((nh, nw), np.float32) for n in names}
+        fp = C.POINTER(C.c_float)
+        rec = ComposeRecord()
+        rc = host_lib().flow2d_host_compose_nodes(self.handle, (fp * 7)(*[_fptr(q) for q in a]),
+                                                  (fp * 8)(*[_opt_fptr(b.get(n)) for n in self.SUBSET_PLANES]), int(grid_radius), int(spacing),
+                                                  int(min_state), (fp * 8)(*[_opt_fptr(out.get(n)) for n in self.SUBSET_PLANES]),
+                                                  C.byref(rec) if record else None)
+        if rc:
+            raise Flow2DError(rc, "OpticalFlow2D::ComposeNodes")
+        return out, (rec if record else None)
+
+    def compose_nodes_device(self, dev_base, dev_increment, grid_radius, spacing, dev_out, min_state=1, record=True):
+        """OpticalFlow2D::ComposeNodesDevice: dicts of device planes by the names of SUBSET_PLANES -- of the base u, v, the gradients
+        and the state, of the increment those and optionally the score, of dev_out u, v and the gradients and optionally state and
+        score (a score only with the increment's).  Returns the ComposeRecord (the call then synchronises) or, without record,
+        None (it only queues)."""
+        rec = ComposeRecord()
+        vp = C.c_void_p
+        rc = host_lib().flow2d_host_compose_nodes_device(self.handle, (vp * 7)(*[dev_base.get(n) for n in self.COMPOSE_BASE]),
+                                                         (vp * 8)(*[dev_increment.get(n) for n in self.SUBSET_PLANES]), int(grid_radius),
+                                                         int(spacing), int(min_state), (vp * 8)(*[dev_out.get(n) for n in self.SUBSET_PLANES]),
+                                                         C.byref(rec) if record else None)
+        if rc:
+            raise Flow2DError(rc, "OpticalFlow2D::ComposeNodesDevice")
+        return rec if record else None
 
 
     NODE_PLANES = ("u", "v", "ux", "uy", "vx", "vy", "state")  # what node_strain* read of a step's SUBSET_PLANES

@@ -33,6 +33,8 @@ struct flow2d_host_flow {
     OpticalFlow2D flow;
     size_t width = 0, height = 0;
     int subset_interpolation = OpticalFlow2D::SubsetOptions::CatmullRom;  // flow2d_host_set_subset_interpolation
+    int reference_every = 0;                                              // flow2d_host_set_reference_every
+    std::vector<flow2d_compose_record> compose_records;                   // of the last sequence call: flow2d_host_compose_records
 };
 
 namespace {
@@ -905,16 +907,89 @@ HOST_API int flow2d_host_correlate_subset(flow2d_host_flow* h, const float* fram
 
 // ---- subset refinement over a sequence ------------------------------------------------------------------------------------------
 namespace {
-OpticalFlow2D::SequenceOptions sequence_options(int fill, int min_state, int min_neighbours, float max_shift)
+// (SequenceOptions::reference_every travels beside the entries' arguments the way SubsetOptions::interpolation does: kept in the
+// object by flow2d_host_set_reference_every, so that the sequence entries keep the arguments callers built against)
+OpticalFlow2D::SequenceOptions sequence_options(int fill, int min_state, int min_neighbours, float max_shift,
+                                                const flow2d_host_flow* h = nullptr)
 {
     OpticalFlow2D::SequenceOptions o;
     o.fill = fill;
     o.min_state = min_state;
     o.min_neighbours = min_neighbours;
     o.max_shift = max_shift;
+    if (h) o.reference_every = h->reference_every;
     return o;
 }
 }  // namespace
+
+// SequenceOptions::reference_every of every later sequence call of this object: 0 never (what a new object has), N >= 1 a new
+// reference frame every N steps.  0 on success, 1 for a null object or a negative value, which changes nothing.
+HOST_API int flow2d_host_set_reference_every(flow2d_host_flow* h, int every)
+{
+    if (!h || every < 0) return 1;
+    h->reference_every = every;
+    return 0;
+}
+
+// The composition records of the object's last sequence call, one per step (zero for a step measured against frame 0): up to
+// `count` of them are copied into `records`; returns how many steps that call had.
+HOST_API int flow2d_host_compose_records(const flow2d_host_flow* h, flow2d_compose_record* records, int count)
+{
+    if (!h) return 0;
+    for (int k = 0; records && k < count && k < static_cast<int>(h->compose_records.size()); ++k) records[k] = h->compose_records[k];
+    return static_cast<int>(h->compose_records.size());
+}
+
+// OpticalFlow2D::ComposeNodesDevice: dev_base -- seven device planes u, v, ux, uy, vx, vy, state --, dev_increment and dev_out -- the
+// first eight slots of OpticalFlow2D::SubsetPlanes (u, v, ux, uy, vx, vy, score, state; the increment's score and the output's
+// score and state optional).  With a record (host) the call synchronises.  0 on success, 1 for a null or refused argument, 2 when
+// the run failed.
+HOST_API int flow2d_host_compose_nodes_device(flow2d_host_flow* h, void* const* dev_base, void* const* dev_increment, int grid_radius,
+                                              int spacing, int min_state, void* const* dev_out, flow2d_compose_record* record)
+{
+    if (!h || !dev_base || !dev_increment || !dev_out || min_state < 0 || min_state > 1) return 1;
+    for (int k = 0; k < 7; ++k)
+        if (!dev_base[k] || (k != 6 && !dev_increment[k]) || (k < 6 && !dev_out[k])) return 1;
+    if (!dev_increment[7] || (dev_out[6] && !dev_increment[6])) return 1;
+    OpticalFlow2D::SubsetPlanes base, increment, out;
+    base = {dp(dev_base[0]), dp(dev_base[1]), dp(dev_base[2]), dp(dev_base[3]), dp(dev_base[4]), dp(dev_base[5]), 0, dp(dev_base[6])};
+    increment = {dp(dev_increment[0]), dp(dev_increment[1]), dp(dev_increment[2]), dp(dev_increment[3]),
+                 dp(dev_increment[4]), dp(dev_increment[5]), dp(dev_increment[6]), dp(dev_increment[7])};
+    out = {dp(dev_out[0]), dp(dev_out[1]), dp(dev_out[2]), dp(dev_out[3]), dp(dev_out[4]), dp(dev_out[5]), dp(dev_out[6]), dp(dev_out[7])};
+    h->flow.timing_mode = 0;
+    return h->flow.ComposeNodesDevice(base, increment, grid_radius, spacing, min_state, out, record) ? 0 : 2;
+}
+
+// OpticalFlow2D::ComposeNodes on tight host arrays of nw * nh floats (the grid of the object's frames): base -- seven --, increment
+// and nodes -- eight each, as above.
+HOST_API int flow2d_host_compose_nodes(flow2d_host_flow* h, const float* const* base, const float* const* increment, int grid_radius,
+                                       int spacing, int min_state, float* const* nodes, flow2d_compose_record* record)
+{
+    if (!h || !base || !increment || !nodes || min_state < 0 || min_state > 1) return 1;
+    for (int k = 0; k < 7; ++k)
+        if (!base[k] || (k != 6 && !increment[k]) || (k < 6 && !nodes[k])) return 1;
+    if (!increment[7] || (nodes[6] && !increment[6])) return 1;
+    size_t nw = 0, nh = 0;
+    if (flow2d_correlation_grid(h->width, h->height, grid_radius, spacing, &nw, &nh) != FLOW2D_OK) return 1;
+    std::vector<Data2D> images;
+    images.reserve(23);
+    for (int k = 0; k < 23; ++k) images.emplace_back(nw, nh);
+    Data2D *a[7], *b[8], *o[8];
+    for (int k = 0; k < 7; ++k) {
+        std::memcpy(images[k].DataPtr(), base[k], nw * nh * sizeof(float));
+        a[k] = &images[k];
+    }
+    for (int k = 0; k < 8; ++k) {
+        if (increment[k]) std::memcpy(images[7 + k].DataPtr(), increment[k], nw * nh * sizeof(float));
+        b[k] = increment[k] ? &images[7 + k] : nullptr;
+        o[k] = nodes[k] ? &images[15 + k] : nullptr;
+    }
+    h->flow.ComposeNodes(a, b, grid_radius, spacing, min_state, o, record);
+    if (!h->flow.LastRunSucceeded()) return 2;
+    for (int k = 0; k < 8; ++k)
+        if (nodes[k]) std::memcpy(nodes[k], images[15 + k].DataPtr(), nw * nh * sizeof(float));
+    return 0;
+}
 
 // OpticalFlow2D::SequenceOptionsOk.  Needs no device.
 HOST_API int flow2d_host_sequence_options_ok(int fill, int min_state, int min_neighbours, float max_shift)
@@ -958,7 +1033,7 @@ HOST_API int flow2d_host_correlate_subset_sequence_device(flow2d_host_flow* h, v
 {
     const auto list = correlation_passes(passes, count);
     const auto validation = validation_options(threshold, epsilon, min_neighbours, 1, 1);
-    const auto sequence = sequence_options(fill, min_state, predict_neighbours, sequence_max_shift);
+    const auto sequence = sequence_options(fill, min_state, predict_neighbours, sequence_max_shift, h);
     if (!h || !dev_frames || frames < 2 || count < 0 || !dev_out || !options) return 1;
     const auto subset = subset_options(*options, h);
     const size_t n = static_cast<size_t>(frames), step_count = n - 1;
@@ -980,8 +1055,10 @@ HOST_API int flow2d_host_correlate_subset_sequence_device(flow2d_host_flow* h, v
         if ((flow_list[2 * k] == 0) != (flow_list[2 * k + 1] == 0)) return 1;
     }
     h->flow.timing_mode = 0;
+    h->compose_records.assign(step_count, flow2d_compose_record{});
     return h->flow.CorrelateSubsetSequenceDevice(frame_list.data(), n, lo, scale, list.data(), list.size(), min_score, validation, subset,
-                                                 sequence, out.data(), reports, steps, dev_flows ? flow_list.data() : nullptr)
+                                                 sequence, out.data(), reports, steps, dev_flows ? flow_list.data() : nullptr,
+                                                 h->compose_records.data())
                ? 0
                : 2;
 }
@@ -998,7 +1075,7 @@ HOST_API int flow2d_host_correlate_subset_sequence(flow2d_host_flow* h, const fl
 {
     const auto list = correlation_passes(passes, count);
     const auto validation = validation_options(threshold, epsilon, min_neighbours, 1, 1);
-    const auto sequence = sequence_options(fill, min_state, predict_neighbours, sequence_max_shift);
+    const auto sequence = sequence_options(fill, min_state, predict_neighbours, sequence_max_shift, h);
     if (!h || !frames || count_frames < 2 || !nodes || count < 0 || !options) return 1;
     const auto subset = subset_options(*options, h);
     const size_t n = static_cast<size_t>(count_frames), step_count = n - 1;
@@ -1029,8 +1106,9 @@ HOST_API int flow2d_host_correlate_subset_sequence(flow2d_host_flow* h, const fl
     for (size_t k = 0; k < per_step * step_count; ++k) images.emplace_back(nw, nh);
     std::vector<Data2D*> wanted(per_step * step_count);
     for (size_t k = 0; k < per_step * step_count; ++k) wanted[k] = slot(k) ? &images[k] : nullptr;
+    h->compose_records.assign(step_count, flow2d_compose_record{});
     h->flow.CorrelateSubsetSequence(in.data(), n, list.data(), list.size(), min_score, validation, subset, sequence, wanted.data(), reports,
-                                    steps, flows ? flow_images.data() : nullptr, mask);
+                                    steps, flows ? flow_images.data() : nullptr, mask, h->compose_records.data());
     const int rc = im.Finish(h->flow);
     if (rc) return rc;
     for (size_t k = 0; k < per_step * step_count; ++k)

@@ -101,6 +101,16 @@
 // (OpticalFlow2D::ContinueSubsetSequence), with --subset-max-shift defaulting to 4; the (last) pass of --correlation... gives the grid
 // only.  One line "Prediction: {json}" -- the options and per pass "nodes", "kept", "predicted", "empty" -- is printed before the
 // "Subset:" line, whose "passes" is then 0.  Without the option nothing changes.
+// --subset-base PREFIX, valid only together with --subset-refine (with or without --subset-previous), is a step of a sequence whose
+// reference frame has moved: FILE_0 is the current reference frame r, not frame 0, and PREFIXnode-u-NW-NH.raw, -v, -ux, -uy, -vx, -vy
+// and -state are the field frame 0 -> frame r on this grid (what an earlier run delivered for frame r; refill its holes first if it
+// is to serve many steps).  The refined field, frame r -> FILE_1, is the *increment*: its files are written with "increment-" in front
+// of their names (increment-node-u-NW-NH.raw, ...), so that the next run's --subset-previous can start from them, and the node files
+// themselves are the composition of base and increment (OpticalFlow2D::ComposeNodes, flow2d_compose_nodes_2d, with the least state
+// of --subset-previous's --subset-min-state, 1 without it): frame 0 -> FILE_1 at the nodes of frame 0, state 66 or -1, the score blended.  --subset-strain works on the
+// composed field; the dense flow files stay the increment's.  One more line, "Compose: {json}" -- "nodes", "composed", "no_base",
+// "outside", "no_increment" -- is printed.  With --subset-order 2 the curvatures are the increment's alone.  Without the option
+// nothing changes.
 // --subset-mask FILE [--subset-mask-invert] [--subset-min-pixels N, 6 .. (2R + 1)^2, default a quarter of the subset], valid only
 // together with --subset-refine (order 1), is digital image correlation on a region of interest (flow2d_subset_refine_masked_2d): FILE
 // is a raw image of the frames' size and format, read like them, in FILE_0's coordinates, whose values of 0.5 and more mean "not the
@@ -191,6 +201,7 @@ int main(int argc, char** argv)
     bool subset_interpolation_given = false;  // --subset-interpolation catmull-rom|bspline
     OpticalFlow2D::SequenceOptions sequence;  // --subset-previous PREFIX and its options
     std::string subset_previous;
+    std::string subset_base;  // --subset-base PREFIX: the field up to the reference frame, composed with the refined one
     bool sequence_option = false, subset_max_shift_given = false, subset_curvature_given = false;
     std::string subset_mask_file;  // --subset-mask FILE, --subset-mask-invert, --subset-min-pixels N
     bool subset_mask_invert = false, subset_mask_option = false;
@@ -518,6 +529,13 @@ int main(int argc, char** argv)
             }
             subset_previous = argv[++i];
         }
+        else if (!std::strcmp(argv[i], "--subset-base")) {
+            if (i + 1 >= argc || !argv[i + 1][0]) {
+                std::printf("--subset-base takes the prefix of the node files of the field up to the reference frame.\n");
+                return 5;
+            }
+            subset_base = argv[++i];
+        }
         else if (!std::strcmp(argv[i], "--subset-strain") || !std::strcmp(argv[i], "--strain-order") ||
                  !std::strcmp(argv[i], "--strain-min-nodes")) {
             const bool window = !std::strcmp(argv[i], "--subset-strain"), order = !std::strcmp(argv[i], "--strain-order");
@@ -635,6 +653,10 @@ int main(int argc, char** argv)
         return 5;
     }
     sequence.max_shift = subset_max_shift_given || subset_previous.empty() ? subset.max_shift : 4.f;
+    if (!subset_base.empty() && !subset_refine) {
+        std::printf("--subset-base PREFIX composes the field of --subset-refine with the one up to its reference frame.\n");
+        return 5;
+    }
 
     if (strain_option && !subset_strain) {
         std::printf("--strain-order and --strain-min-nodes belong to --subset-strain M.\n");
@@ -930,10 +952,43 @@ int main(int argc, char** argv)
                                              nodes, nullptr, &record, &flow_u, &flow_v, predicted ? &prior_u : nullptr,
                                              predicted ? &prior_v : nullptr, subset_mask_image);
             }
+            flow2d_compose_record composition = {};
+            std::vector<Data2D> composed;
+            if (optical_flow.LastRunSucceeded() && !subset_base.empty()) {
+                // the refined field is an increment from the reference frame: written under its own names, then composed with the
+                // field up to the reference into the eight node images
+                for (int k = 0; k < node_images; ++k)
+                    images[k].WriteRAWToFileF32((output_path + counter + "increment-" + names[k] + size).c_str());
+                const int from[7] = {0, 1, 2, 3, 4, 5, 7};
+                std::vector<Data2D> before(7);
+                Data2D *base[7], *out[8];
+                for (int k = 0; k < 7; ++k) {
+                    const std::string path = subset_base + names[from[k]] + size;
+                    if (!before[k].ReadRAWFromFileF32(path.c_str(), nw, nh)) {
+                        std::printf("Cannot read '%s' (%zu x %zu float32: the field up to the reference frame on this grid).\n", path.c_str(), nw,
+                                    nh);
+                        optical_flow.Destroy();
+                        DestroyDeviceContext();
+                        return 2;
+                    }
+                    base[k] = &before[k];
+                }
+                for (int k = 0; k < 8; ++k) composed.emplace_back(nw, nh);
+                for (int k = 0; k < 8; ++k) out[k] = &composed[k];
+                optical_flow.ComposeNodes(base, nodes, fine.radius, fine.spacing, sequence.min_state, out, &composition);
+                for (int k = 0; k < 8; ++k) nodes[k] = out[k];  // what is written and strained below
+            }
             if (optical_flow.LastRunSucceeded()) {
                 if (subset_mask_image)
                     std::printf("SubsetMask: {\"masked\": %llu, \"min_pixels\": %d}\n", record.reserved, OpticalFlow2D::SubsetMinPixels(subset));
-                for (int k = 0; k < node_images; ++k) images[k].WriteRAWToFileF32((output_path + counter + names[k] + size).c_str());
+                if (!subset_base.empty())
+                    std::printf("Compose: {\"min_state\": %d, \"nodes\": %llu, \"composed\": %llu, \"no_base\": %llu, \"outside\": %llu, "
+                                "\"no_increment\": %llu}\n",
+                                sequence.min_state, composition.nodes, composition.composed, composition.no_base, composition.outside,
+                                composition.no_increment);
+                // (with --subset-base and order 2 the curvature files would be the increment's: they are written with it alone)
+                for (int k = 0; k < (subset_base.empty() ? node_images : 8); ++k)
+                    nodes[k]->WriteRAWToFileF32((output_path + counter + names[k] + size).c_str());
                 if (subset_interpolation_given) {
                     if (subset.interpolation == OpticalFlow2D::SubsetOptions::BSpline)
                         std::printf("SubsetInterpolation: {\"interpolation\": \"bspline\", \"horizon\": %d}\n", FLOW2D_BSPLINE_HORIZON);

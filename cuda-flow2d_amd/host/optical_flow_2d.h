@@ -403,6 +403,10 @@ public:
         int min_state = 1;       // 1: converged nodes are kept; 0: also those that ran out of iterations
         int min_neighbours = 1;  // usable neighbours a lost node needs to be predicted, 1 .. 8
         float max_shift = 4.f;   // of the steps after the first, in place of subset.max_shift: the motion of one step
+        // Incremental correlation: 0 = never (every step against frame 0); N >= 1: step k is measured against frame
+        // ref(k) = N * floor((k - 1) / N), on the same grid laid in that frame, and composed with the deformation up to it
+        // (flow2d_compose_nodes_2d), so that what is delivered stays "frame 0 -> frame k at the nodes of frame 0".
+        int reference_every = 0;
     };
     struct SequenceStepReport {
         flow2d_subset_record subset;
@@ -419,21 +423,53 @@ public:
     // per pass) as for CorrelateSubsetDevice; steps_out (optional, frame_count - 1).  There is no new search when many nodes are
     // lost: the records say so, and the caller decides.  Everything is queued on the stream, the records are read back after
     // one synchronisation at the end.  Not for lock-step groups.
+    //
+    // With sequence.reference_every = N >= 1 the reference moves: step k is measured against frame ref(k) = N * floor((k - 1) / N).
+    // The steps with ref = 0 are the ones above, bit for bit.  At a step with ref(k) = k - 1 > 0, the first after a change, the
+    // *base* of the new reference is built once -- sequence.fill passes of flow2d_predict_nodes_2d over the delivered planes of
+    // step ref, so that its holes are refilled -- and the *increment* is CorrelateSubsetDevice's chain on (frame ref, frame k), the
+    // way step 1 runs, with the caller's passes, lo and scale; the later steps of the same reference are the prediction passes and
+    // the refinement from the previous increment, with sequence.max_shift.  The increments stay in planes of the object's own
+    // (each is the next step's start); out[k - 1] gets flow2d_compose_nodes_2d of base and increment with sequence.min_state: the
+    // six planes and the state, state FLOW2D_SUBSET_STATE_COMPOSED or -1, and the increment's score blended where a score plane is
+    // given; dev_flows the composed (u, v).  steps_out[k - 1].subset is the increment's refinement; its prediction records are those
+    // of the increment's start, or at a reference change those of the base.  compose_out (optional, frame_count - 1): the
+    // composition's record per step, zero for the steps with ref = 0.  A moving reference is refused with a mask (it lies in frame
+    // 0's coordinates, and the later references' subsets do not) and with curvature planes in `out` (order 2 itself runs: the
+    // composition knows gradients only).  Still everything is queued and the call synchronises once.
     bool CorrelateSubsetSequenceDevice(const DevicePtr* dev_frames, size_t frame_count, float lo, float scale, const CorrelationPass* passes,
                                        size_t count, float min_score, const ValidationOptions& validation, const SubsetOptions& subset,
                                        const SequenceOptions& sequence, const SubsetPlanes* out, CorrelationPassReport* first_reports,
-                                       SequenceStepReport* steps_out, const DevicePtr* dev_flows = nullptr);
+                                       SequenceStepReport* steps_out, const DevicePtr* dev_flows = nullptr,
+                                       flow2d_compose_record* compose_out = nullptr);
     // The host-image form: lo and scale from CorrelationRange of frames 0 and 1; nodes[8 * (k - 1) + 0 .. 7] -- u, v, ux, uy, vx,
     // vy, score, state of step k, images of the last pass's grid, all but the score needed; flows (optional): 2 per step.
     void CorrelateSubsetSequence(Data2D* const* frames, size_t frame_count, const CorrelationPass* passes, size_t count, float min_score,
                                  const ValidationOptions& validation, const SubsetOptions& subset, const SequenceOptions& sequence,
                                  Data2D* const* nodes, CorrelationPassReport* first_reports, SequenceStepReport* steps_out,
-                                 Data2D* const* flows = nullptr, Data2D* mask = nullptr);
+                                 Data2D* const* flows = nullptr, Data2D* mask = nullptr, flow2d_compose_record* compose_out = nullptr);
+
+    // The composition of two node fields across a moved reference (flow2d_compose_nodes_2d): `base` -- frame 0 -> frame r at the
+    // nodes of frame 0 -- and `increment` -- frame r -> frame k on the same grid (grid_radius, spacing) laid in frame r -- give u, v,
+    // the four gradients and the state each; `out` gets frame 0 -> frame k: u, v and the gradients are needed, the state is
+    // optional, the score goes with increment.score (without out.score the increment's is not looked at).  min_state as in
+    // SequenceOptions.  record_out (host, optional): the counts, read back -- the call then synchronises, otherwise it only
+    // queues.  Not for lock-step groups.
+    bool ComposeNodesDevice(const SubsetPlanes& base, const SubsetPlanes& increment, int grid_radius, int spacing, int min_state,
+                            const SubsetPlanes& out, flow2d_compose_record* record_out = nullptr);
+    // The host-image form: base[7] -- u, v, ux, uy, vx, vy, state --, increment[8] and nodes[8] -- u, v, ux, uy, vx, vy, score, state,
+    // of which the increment's score and the nodes' score and state are optional --, images of the grid.
+    void ComposeNodes(Data2D* const* base, Data2D* const* increment, int grid_radius, int spacing, int min_state, Data2D* const* nodes,
+                      flow2d_compose_record* record_out = nullptr);
 
     // One later step on its own, for a sequence that arrives frame by frame (the CLI's --subset-previous): `previous` holds the
     // last step's u, v, gradients and state (its score is not looked at); the prediction's passes and the refinement of
     // (dev_frame_0, dev_frame_k) with sequence.max_shift into `out`, as CorrelateSubsetSequenceDevice runs them per step.
-    // report_out (optional).  Synchronises.
+    // report_out (optional).  Synchronises.  dev_frame_0 may be any frame: with a moved reference the caller passes the reference
+    // frame and the previous INCREMENT (not the composed field) as `previous`, and composes `out` with the base of that reference
+    // by ComposeNodesDevice; sequence.reference_every is not looked at here.  The composition's record tells when the reference
+    // should move again (many nodes outside or without an increment); there is no automatic policy, which would need the
+    // device's counts on the host at every step.
     bool ContinueSubsetSequenceDevice(DevicePtr dev_frame_0, DevicePtr dev_frame_k, const SubsetPlanes& previous, int grid_radius,
                                       int spacing, const SubsetOptions& subset, const SequenceOptions& sequence, const SubsetPlanes& out,
                                       SequenceStepReport* report_out, DevicePtr dev_flow_u = 0, DevicePtr dev_flow_v = 0);
@@ -799,6 +835,14 @@ private:
     // CorrelateSubsetSequence*: the prediction's two sets of seven planes (u, v, ux, uy, vx, vy, state); the passes' records
     OwnedPlanes sequence_planes_{owned_, 14};
     DeviceScratch sequence_scratch_{owned_};
+    // ... with a moving reference (first use): two sets of eight planes for the increments (u, v, ux, uy, vx, vy, score, state),
+    // written in turn, and the base's seven (u, v, ux, uy, vx, vy, state)
+    OwnedPlanes reference_planes_{owned_, 23};
+    // the composition alone, without the checks of the plane sets and without a synchronisation; `record`: device, optional
+    bool QueueComposeNodes(const SubsetPlanes& base, const SubsetPlanes& increment, int grid_radius, int spacing, int min_state,
+                           const SubsetPlanes& out, flow2d_compose_record* record);
+    // ComposeNodesDevice: its record
+    DeviceScratch compose_scratch_{owned_};
     // NodeStrain*: per step the record and, behind it, the workspace
     DeviceScratch strain_scratch_{owned_};
     // ComputeFlowFromPrior*: inside such a run the prior's planes and the start level (RunPyramid starts there, from them); the

@@ -1018,6 +1018,11 @@ bool OpticalFlow2D::RefineNodesFromDevice(DevicePtr dev_frame_0, DevicePtr dev_f
 
 bool OpticalFlow2D::SequenceOptionsOk(const SequenceOptions& sequence)
 {
+    if (sequence.reference_every < 0) {
+        std::printf("Error: a subset sequence takes a new reference frame every N >= 1 steps, or 0 for never (%d).\n",
+                    sequence.reference_every);
+        return false;
+    }
     if (sequence.fill >= 1 && sequence.fill <= kSequenceMaxFill && (sequence.min_state == 0 || sequence.min_state == 1) &&
         sequence.min_neighbours >= 1 && sequence.min_neighbours <= 8 && std::isfinite(sequence.max_shift) && sequence.max_shift > 0.f)
         return true;
@@ -1255,15 +1260,29 @@ bool OpticalFlow2D::CorrelateSubsetSequenceDevice(const DevicePtr* dev_frames, s
                                                   const ValidationOptions& validation, const SubsetOptions& subset,
                                                   const SequenceOptions& sequence, const SubsetPlanes* out,
                                                   CorrelationPassReport* first_reports, SequenceStepReport* steps_out,
-                                                  const DevicePtr* dev_flows)
+                                                  const DevicePtr* dev_flows, flow2d_compose_record* compose_out)
 {
-    const size_t W = dev_container_size_.width, H = dev_container_size_.height;
+    const size_t W = dev_container_size_.width, H = dev_container_size_.height, pitch = dev_container_size_.pitch;
     if (!CorrelationPassesOk(W, H, lo, scale, passes, count, min_score, validation) || !SubsetOptionsOk(subset) ||
         !SequenceOptionsOk(sequence))
         return false;
     if (!IsInitialized() || !dev_frames || frame_count < 2 || !out) return false;
     if (RefuseGroup("a subset sequence")) return false;
     const size_t steps = frame_count - 1;
+    const size_t every = static_cast<size_t>(sequence.reference_every);
+    if (every > 0 && subset.mask) {
+        std::printf("Error: '%s': a subset mask lies in frame 0's coordinates, and with a new reference frame every %zu steps the later "
+                    "references' subsets do not: a moving reference takes no mask.\n",
+                    GetName(), every);
+        return false;
+    }
+    for (size_t k = 0; every > 0 && k < steps; ++k)
+        if (out[k].uxx || out[k].uxy || out[k].uyy || out[k].vxx || out[k].vxy || out[k].vyy) {
+            std::printf("Error: '%s': with a moving reference the delivered fields are compositions, which know gradients only: step %zu "
+                        "takes no curvature planes.\n",
+                        GetName(), k + 1);
+            return false;
+        }
     {
         // every step's planes are the next step's input and pass through the prediction, which knows no frame: checked here
         std::vector<DevicePtr> written;
@@ -1283,26 +1302,165 @@ bool OpticalFlow2D::CorrelateSubsetSequenceDevice(const DevicePtr* dev_frames, s
     }
     if (!EnsurePlanes(sequence_planes_, 14)) return false;
     const size_t per_step = sizeof(flow2d_subset_record) + kSequenceMaxFill * sizeof(flow2d_predict_record);
-    if (!sequence_scratch_.Ensure(context_, steps * per_step)) return false;
+    // (with a moving reference the compositions' records lie behind the steps')
+    if (!sequence_scratch_.Ensure(context_, steps * per_step + (every > 0 && compose_out ? steps * sizeof(flow2d_compose_record) : 0)))
+        return false;
+    if (every > 0 && every < steps && !EnsurePlanes(reference_planes_, 23)) return false;
     const CorrelationPass& fine = passes[count - 1];
     if (steps_out) std::fill(steps_out, steps_out + steps, SequenceStepReport{});
+    if (compose_out) std::fill(compose_out, compose_out + steps, flow2d_compose_record{});
     // step 1: the pair chain
     bool ok = QueueCorrelateSubset(dev_frames[0], dev_frames[1], lo, scale, passes, count, min_score, validation, subset, 0, 0, out[0],
                                    first_reports, steps_out ? &steps_out[0].subset : nullptr, dev_flows ? dev_flows[0] : 0,
                                    dev_flows ? dev_flows[1] : 0, false);
     SubsetOptions later = subset;
     later.max_shift = sequence.max_shift;
-    for (size_t k = 1; ok && k < steps; ++k)
-        ok = QueueSequenceStep(dev_frames[0], dev_frames[k + 1], out[k - 1], fine.radius, fine.spacing, later, sequence, out[k],
-                               steps_out ? &steps_out[k] : nullptr, k * per_step, dev_flows ? dev_flows[2 * k] : 0,
-                               dev_flows ? dev_flows[2 * k + 1] : 0);
+    size_t nw = 0, nh = 0;
+    flow2d_correlation_grid(W, H, fine.radius, fine.spacing, &nw, &nh);
+    auto set_of = [](const DevicePtr* d) { return SubsetPlanes{d[0], d[1], d[2], d[3], d[4], d[5], d[6], d[7]}; };
+    int written = 0;  // the set of reference_planes_ the last increment lies in
+    for (size_t k = 1; ok && k < steps; ++k) {
+        const size_t ref = every > 0 ? every * (k / every) : 0;  // step k + 1 against frame ref
+        SequenceStepReport* report = steps_out ? &steps_out[k] : nullptr;
+        const DevicePtr flow_u = dev_flows ? dev_flows[2 * k] : 0, flow_v = dev_flows ? dev_flows[2 * k + 1] : 0;
+        if (ref == 0) {
+            ok = QueueSequenceStep(dev_frames[0], dev_frames[k + 1], out[k - 1], fine.radius, fine.spacing, later, sequence, out[k], report,
+                                   k * per_step, flow_u, flow_v);
+            continue;
+        }
+        const DevicePtr* base = reference_planes_.data() + 16;
+        const SubsetPlanes increment = set_of(reference_planes_.data() + 8 * (written ^ 1));
+        if (ref == k) {
+            // the reference moves to frame `ref`: its base is the delivered field of step `ref`, refilled, the last pass into the
+            // base's planes; then the pair chain from the new reference
+            const SubsetPlanes& field = out[ref - 1];
+            const float* in[7] = {AsPlane(field.u),  AsPlane(field.v),  AsPlane(field.ux),   AsPlane(field.uy),
+                                  AsPlane(field.vx), AsPlane(field.vy), AsPlane(field.state)};
+            for (int pass = 0; ok && pass < sequence.fill; ++pass) {
+                const DevicePtr* set = pass == sequence.fill - 1 ? base : sequence_planes_.data() + 7 * (pass & 1);
+                auto* record = sequence_scratch_.At<flow2d_predict_record>(k * per_step + sizeof(flow2d_subset_record) +
+                                                                            pass * sizeof(flow2d_predict_record));
+                ok = !CheckFlow2DError(flow2d_predict_nodes_2d(context_, in[0], in[1], in[2], in[3], in[4], in[5], in[6], nw, nh, pitch,
+                                                               fine.spacing, sequence.min_state, sequence.min_neighbours, AsPlane(set[0]),
+                                                               AsPlane(set[1]), AsPlane(set[2]), AsPlane(set[3]), AsPlane(set[4]),
+                                                               AsPlane(set[5]), AsPlane(set[6]), report ? record : nullptr),
+                                       "flow2d_predict_nodes_2d");
+                if (ok && report) ok = ReadRecord(&report->prediction[pass], record, sizeof(*record));
+                for (int c = 0; c < 7; ++c) in[c] = AsPlane(set[c]);
+            }
+            ok = ok && QueueCorrelateSubset(dev_frames[ref], dev_frames[k + 1], lo, scale, passes, count, min_score, validation, subset, 0, 0,
+                                            increment, nullptr, report ? &report->subset : nullptr, 0, 0, false);
+        } else {
+            ok = QueueSequenceStep(dev_frames[ref], dev_frames[k + 1], set_of(reference_planes_.data() + 8 * written), fine.radius,
+                                   fine.spacing, later, sequence, increment, report, k * per_step, 0, 0);
+        }
+        written ^= 1;
+        auto* record = compose_out ? sequence_scratch_.At<flow2d_compose_record>(steps * per_step + k * sizeof(flow2d_compose_record)) : nullptr;
+        ok = ok && QueueComposeNodes(SubsetPlanes{base[0], base[1], base[2], base[3], base[4], base[5], 0, base[6]}, increment, fine.radius,
+                                     fine.spacing, sequence.min_state, out[k], record);
+        if (ok && compose_out) ok = ReadRecord(compose_out + k, record, sizeof(*record));
+        if (ok && flow_u)
+            ok = !CheckFlow2DError(flow2d_expand_nodes_2d(context_, AsPlane(out[k].u), AsPlane(out[k].v), nw, nh, pitch, fine.radius,
+                                                          fine.spacing, AsPlane(flow_u), AsPlane(flow_v), W, H, pitch),
+                                   "flow2d_expand_nodes_2d");
+    }
     return !CheckFlow2DError(flow2d_synchronize(context_), "flow2d_synchronize") && ok;
+}
+
+bool OpticalFlow2D::QueueComposeNodes(const SubsetPlanes& base, const SubsetPlanes& increment, int grid_radius, int spacing, int min_state,
+                                      const SubsetPlanes& out, flow2d_compose_record* record)
+{
+    const size_t W = dev_container_size_.width, H = dev_container_size_.height, pitch = dev_container_size_.pitch;
+    size_t nw = 0, nh = 0;
+    if (flow2d_correlation_grid(W, H, grid_radius, spacing, &nw, &nh) != FLOW2D_OK) {
+        std::printf("Error: a %zu x %zu frame holds no node grid of radius %d and spacing %d.\n", W, H, grid_radius, spacing);
+        return false;
+    }
+    auto plane = [](DevicePtr p) { return p ? AsPlane(p) : nullptr; };
+    // (the node planes are containers: the frames' pitch; the entry refuses planes that meet)
+    const float* const a[7] = {plane(base.u), plane(base.v), plane(base.ux), plane(base.uy), plane(base.vx), plane(base.vy), plane(base.state)};
+    const float* const b[7] = {plane(increment.u),  plane(increment.v),  plane(increment.ux),   plane(increment.uy),
+                               plane(increment.vx), plane(increment.vy), plane(increment.state)};
+    float* const o[6] = {plane(out.u), plane(out.v), plane(out.ux), plane(out.uy), plane(out.vx), plane(out.vy)};
+    return !CheckFlow2DError(flow2d_compose_nodes_2d(context_, a, b, out.score ? plane(increment.score) : nullptr, nw, nh, pitch, grid_radius,
+                                                     spacing, min_state, o, plane(out.state), plane(out.score), record),
+                             "flow2d_compose_nodes_2d");
+}
+
+bool OpticalFlow2D::ComposeNodesDevice(const SubsetPlanes& base, const SubsetPlanes& increment, int grid_radius, int spacing, int min_state,
+                                       const SubsetPlanes& out, flow2d_compose_record* record_out)
+{
+    if (!IsInitialized()) return false;
+    if (min_state != 0 && min_state != 1) {
+        std::printf("Error: '%s': a composition takes a least state of 0 or 1 (%d).\n", GetName(), min_state);
+        return false;
+    }
+    for (const SubsetPlanes* q : {&base, &increment})
+        if (!q->u || !q->v || !q->ux || !q->uy || !q->vx || !q->vy || !q->state) {
+            std::printf("Error: '%s': base and increment of a composition need u, v, the four gradients and the state.\n", GetName());
+            return false;
+        }
+    if (!out.u || !out.v || !out.ux || !out.uy || !out.vx || !out.vy || (out.score && !increment.score) || out.uxx || out.uxy || out.uyy ||
+        out.vxx || out.vxy || out.vyy) {
+        std::printf("Error: '%s': a composition writes u, v and the four gradients, a score only from the increment's, and no "
+                    "curvatures.\n",
+                    GetName());
+        return false;
+    }
+    if (RefuseGroup("a composition of node fields")) return false;
+    if (record_out && !compose_scratch_.Ensure(context_, sizeof(flow2d_compose_record))) return false;
+    flow2d_compose_record* record = record_out ? compose_scratch_.At<flow2d_compose_record>() : nullptr;
+    bool ok = QueueComposeNodes(base, increment, grid_radius, spacing, min_state, out, record);
+    if (!ok || !record_out) return ok;
+    ok = ReadRecord(record_out, record, sizeof(*record_out));
+    return !CheckFlow2DError(flow2d_synchronize(context_), "flow2d_synchronize") && ok;
+}
+
+void OpticalFlow2D::ComposeNodes(Data2D* const* base, Data2D* const* increment, int grid_radius, int spacing, int min_state,
+                                 Data2D* const* nodes, flow2d_compose_record* record_out)
+{
+    last_run_ok_ = false;
+    if (!IsInitialized() || !base || !increment || !nodes) return;
+    for (int k = 0; k < 7; ++k)
+        if (!base[k] || (k != 6 && !increment[k]) || (k < 6 && !nodes[k])) return;
+    if (!increment[7] || (nodes[6] && !increment[6])) return;
+    const size_t W = dev_container_size_.width, H = dev_container_size_.height;
+    size_t nw = 0, nh = 0;
+    if (flow2d_correlation_grid(W, H, grid_radius, spacing, &nw, &nh) != FLOW2D_OK) {
+        std::printf("Error: a %zu x %zu frame holds no node grid of radius %d and spacing %d.\n", W, H, grid_radius, spacing);
+        return;
+    }
+    for (int k = 0; k < 23; ++k) {
+        Data2D* image = k < 7 ? base[k] : (k < 15 ? increment[k - 7] : nodes[k - 15]);
+        if (image && (image->Width() != nw || image->Height() != nh)) {
+            std::printf("Error: '%s': the node images are not %zu x %zu.\n", GetName(), nw, nh);
+            return;
+        }
+    }
+    // the node planes, read and written: containers with no image of their size behind them, uploaded and downloaded here
+    CallPlanes planes(context_, dev_container_size_, GetName(), "node");
+    for (int k = 0; k < 7; ++k) planes.Add(nullptr, CallPlanes::Out, true);
+    for (int k = 0; k < 8; ++k) planes.Add(nullptr, CallPlanes::Out, increment[k] != nullptr);
+    for (int k = 0; k < 8; ++k) planes.Add(nullptr, CallPlanes::Out, nodes[k] != nullptr);
+    HostCall call(context_, last_total_ms_, planes.Allocate());
+    const DevicePtr* d = planes.data();
+    bool ok = planes.Upload();
+    for (int k = 0; ok && k < 7; ++k) ok = CopyData2DtoDevice(*base[k], d[k], H, dev_container_size_.pitch);
+    for (int k = 0; ok && k < 8; ++k)
+        if (increment[k]) ok = CopyData2DtoDevice(*increment[k], d[7 + k], H, dev_container_size_.pitch);
+    const SubsetPlanes a = {d[0], d[1], d[2], d[3], d[4], d[5], 0, d[6]};
+    ok = ok && ComposeNodesDevice(a, NodePlanes(d + 7, 8), grid_radius, spacing, min_state, NodePlanes(d + 15, 8), record_out);
+    // (without a record the device call only queues: the downloads below are ordered behind it on the stream)
+    for (int k = 0; ok && k < 8; ++k)
+        if (nodes[k]) ok = CopyData2DFromDevice(d[15 + k], *nodes[k], H, dev_container_size_.pitch);
+    last_run_ok_ = ok;
 }
 
 void OpticalFlow2D::CorrelateSubsetSequence(Data2D* const* frames, size_t frame_count, const CorrelationPass* passes, size_t count,
                                             float min_score, const ValidationOptions& validation, const SubsetOptions& subset,
                                             const SequenceOptions& sequence, Data2D* const* nodes, CorrelationPassReport* first_reports,
-                                            SequenceStepReport* steps_out, Data2D* const* flows, Data2D* mask)
+                                            SequenceStepReport* steps_out, Data2D* const* flows, Data2D* mask,
+                                            flow2d_compose_record* compose_out)
 {
     last_run_ok_ = false;
     if (!IsInitialized() || !frames || frame_count < 2 || !nodes) return;
@@ -1348,7 +1506,7 @@ void OpticalFlow2D::CorrelateSubsetSequence(Data2D* const* frames, size_t frame_
     masked.mask = mask ? dev_nodes[images * steps] : 0;
     bool ok = planes.Upload() &&
               CorrelateSubsetSequenceDevice(d, frame_count, lo, scale, passes, count, min_score, validation, masked, sequence, out.data(),
-                                            first_reports, steps_out, flows ? dev_flows : nullptr) &&
+                                            first_reports, steps_out, flows ? dev_flows : nullptr, compose_out) &&
               planes.Download();
     for (size_t k = 0; ok && k < images * steps; ++k)
         if (nodes[k]) ok = CopyData2DFromDevice(dev_nodes[k], *nodes[k], H, dev_container_size_.pitch);

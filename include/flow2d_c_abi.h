@@ -1400,6 +1400,76 @@ FLOW2D_API int flow2d_node_strain_2d(flow2d_context* ctx, const float* node_u, c
                                      flow2d_deformation_stats* stats /* device, may be NULL */, void* workspace,
                                      size_t workspace_bytes);
 
+/* The composition of two node fields of a sequence whose reference frame has moved (incremental DIC), out of place.  The *base* A
+ * is frame 0 -> frame r at the nodes of frame 0; the *increment* B is frame r -> frame k on the same grid laid in frame r.  The
+ * result is frame 0 -> frame k at the nodes of frame 0: B sampled where A carries each node, and the two deformation gradients
+ * multiplied.  Added to ABI version 1 without changing any existing entry.
+ * Inputs.  base[0 .. 6] and increment[0 .. 6]: HOST arrays of seven device pointers each, the planes u, v, ux, uy, vx, vy and
+ * state (the outputs of the subset refinement's entries, of flow2d_predict_nodes_2d or of an earlier call of this entry), nw x nh
+ * floats with node_pitch_bytes per row; increment_score (may be NULL), B's score plane; r = grid_radius
+ * (1 .. FLOW2D_CORRELATION_MAX_RADIUS) and s = spacing (1 .. FLOW2D_CORRELATION_MAX_SPACING) of the grid, whose node (i, j) is
+ * centred on pixel (r + i*s, r + j*s); min_state (0 or 1).  nw >= 2 and nh >= 2.
+ * Everything below is IEEE double (an input is converted first, which is exact; r, s, nw, nh, i and j too); every operation is
+ * rounded on its own, no fused multiply-add; division correctly rounded.  Every test is written as a positive comparison, so that
+ * a NaN fails it.
+ * Usable.  A node of A or of B is *usable* as in flow2d_predict_nodes_2d: state >= (float)min_state and its u, v, ux, uy, vx and
+ * vy all finite.
+ * No base.  A's node (i, j) is not usable.
+ * Position.  Otherwise X = (r + i*s) + uA,  Y = (r + j*s) + vA (the bracket is exact),  a = (X - r)/s,  b = (Y - r)/s.  The node is
+ * *outside* unless a >= -0.5, a <= nw - 0.5, b >= -0.5 and b <= nh - 0.5.
+ * Cell.  i0 = floor(a) clamped to [0, nw - 2],  tx = a - i0 clamped to [0, 1] (below 0: 0; above 1: 1);  j0 and ty likewise from
+ * b and nh.  Corner n = 0, 1, 2, 3 is node (i0 + di, j0 + dj) with (di, dj) = (0,0), (1,0), (0,1), (1,1) and has the weight
+ *   w_n = (di ? tx : 1 - tx) * (dj ? ty : 1 - ty).
+ * Only the corners that are usable in B count.  Every sum below starts from 0 and adds the terms of the usable corners in the
+ * order of n.  W = sum of w_n.  The node has *no increment* when !(W > 0).
+ * Sampling B.  With dx = X - (r + (i0 + di)*s) and dy = Y - (r + (j0 + dj)*s), corner n offers
+ *   cu_n = (u_n + ux_n*dx) + uy_n*dy;   cv_n = (v_n + vx_n*dx) + vy_n*dy;   ux_n, uy_n, vx_n, vy_n as they are
+ * (its first-order extrapolation to (X, Y): with the clamped weights it makes sampling up to half a cell beyond the grid's hull
+ * safe, and dropping lost corners never divides by a sum of weights of both signs).  Each of the six values of B is
+ *   (sum of w_n*c_n) / W,   each product rounded;   and with a score  scoreB = (sum of w_n*score_n) / W.
+ * Composition, F = F_B * F_A, each result cast to float once:
+ *   u = uA + uB;   v = vA + vB;
+ *   ux = (((1 + uxB)*(1 + uxA)) + uyB*vxA) - 1;      uy = (1 + uxB)*uyA + uyB*(1 + vyA);
+ *   vx = vxB*(1 + uxA) + (1 + vyB)*vxA;              vy = ((vxB*uyA) + (1 + vyB)*(1 + vyA)) - 1;
+ * out_score = (float)scoreB.  out_state = FLOW2D_SUBSET_STATE_COMPOSED (66): usable at either min_state, like 65.  (A value too
+ * large for a float becomes an infinity, and the node is then not usable to whoever reads it; a result that is a NaN -- a NaN score
+ * of a usable corner, infinities that cancel -- is stored as 0x7FC00000.)
+ * A node with no base, outside or with no increment gets NaN (0x7FC00000) in the six planes and the score, and out_state = -1.
+ * Outputs.  out[0 .. 5]: HOST array of six device pointers, u, v, ux, uy, vx, vy; out_state (may be NULL); out_score (given exactly
+ * when increment_score is).  Record.  record[b] (DEVICE memory, may be NULL), 64 bytes: nodes (nw * nh); composed; no_base;
+ * outside; no_increment; three reserved words, written as 0.  Integers, added by integer atomics after the entry has zeroed the
+ * record on the stream: alone, in a batch and in a replayed graph the same bytes.
+ * Row padding and the containers beyond nw x nh are neither read into a result nor written.  One launch on the context's stream
+ * (and a 64-byte memset per instance with a record); no allocation, no synchronisation (graph-capturable).  Honours
+ * flow2d_context_set_batch: every plane of instance b at b * stride floats, record + b.
+ * FLOW2D_ERR_INVALID_ARGUMENT, and nothing written, for a null array, a null input plane or a null one of the six output planes, a
+ * zero size, nw < 2 or nh < 2, a bad pitch, a grid_radius, spacing or min_state outside its limits, a score input without a score
+ * output or the reverse, a misaligned record (8), or a written range -- outputs, state, score, records, over every instance of a
+ * batch -- that overlaps an input or another written range; FLOW2D_ERR_UNSUPPORTED for 2^31 nodes or more. */
+#define FLOW2D_SUBSET_STATE_COMPOSED 66
+typedef struct flow2d_compose_record {
+    unsigned long long nodes;        /* nw * nh */
+    unsigned long long composed;     /* nodes that got a composed value: state 66 */
+    unsigned long long no_base;      /* the base's node is not usable: NaN, state -1 */
+    unsigned long long outside;      /* carried more than half a cell beyond the grid: NaN, state -1 */
+    unsigned long long no_increment; /* no usable corner with a positive weight: NaN, state -1 */
+    unsigned long long reserved[3];  /* 0 */
+} flow2d_compose_record;
+
+#define FLOW2D_COMPOSE_RECORD_BYTES 64
+#ifdef __cplusplus
+static_assert(sizeof(flow2d_compose_record) == FLOW2D_COMPOSE_RECORD_BYTES, "flow2d_compose_record layout");
+#else
+_Static_assert(sizeof(flow2d_compose_record) == FLOW2D_COMPOSE_RECORD_BYTES, "flow2d_compose_record layout");
+#endif
+
+FLOW2D_API int flow2d_compose_nodes_2d(flow2d_context* ctx, const float* const* base /* u, v, ux, uy, vx, vy, state */,
+                                       const float* const* increment /* the same seven */,
+                                       const float* increment_score /* may be NULL */, size_t nw, size_t nh, size_t node_pitch_bytes,
+                                       int grid_radius, int spacing, int min_state, float* const* out /* u, v, ux, uy, vx, vy */,
+                                       float* out_state /* may be NULL */, float* out_score /* with increment_score */,
+                                       flow2d_compose_record* record /* device, may be NULL */);
+
 /* The flow of the previous pyramid level resampled to this level's size (the bits of flow2d_resample_xy_pair into out_u / out_v)
  * and frame_1 warped by it (the bits of flow2d_registration_2d into `output`) in one launch: replaces the
  * CudaOperationResample2D::Execute + CudaOperationRegistration2D::Execute pair of optical_flow_2d.cpp:314-362 at every
