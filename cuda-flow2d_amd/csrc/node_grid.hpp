@@ -77,8 +77,8 @@ hipError_t clear_records(const flow2d_context* ctx, Record* record)
     return record ? hipMemsetAsync(record, 0, ctx->batch_count * sizeof(Record), ctx->stream) : hipSuccess;
 }
 
-// What the subset refinement's entries (subset_refine.hip, subset_refine2.hip, subset_refine_masked.hip) check alike, in their
-// order: the subset's radius from `min_radius`, the iterations, the bounds (finite and positive; the epsilon may be 0), the grid
+// What the subset refinement's entries (subset_refine.hip, subset_refine2.hip, subset_refine_masked.hip; all through
+// flow2d::subset_refine_enter of subset_node.hpp) check alike, in their order: the subset's radius from `min_radius`, the iterations, the bounds (finite and positive; the epsilon may be 0), the grid
 // inside the frame as flow2d_correlation_grid lays it -- it may be smaller than the full one --, the record's alignment and
 // the node count.  FLOW2D_ERR_UNSUPPORTED is the last of them: an entry hands on FLOW2D_ERR_INVALID_ARGUMENT at once and
 // anything else behind the plane checks of its own, which all come before the node count.

@@ -3,6 +3,10 @@
 //
 // The normative definition is the one of flow2d_subset_refine_2d in flow2d_c_abi.h, in IEEE double.  Built -ffp-contract=off.
 //
+// The kernel here serves flow2d_subset_refine_2d and flow2d_subset_refine_from_2d; subset_refine_masked.hip states the same iteration
+// over a list of pixels, and its instantiation without a mask gives these entries' bytes, but timed 0.7 to 1.6 % behind this kernel
+// at R = 15 (profiles/subset_unified/README.md), so this one stays.  Both take their node, the frame-0 fill, the window test and
+// the host body from subset_node.hpp and the samplers from subset_sample.hpp.
 // As in correlate_offset_kernel a wave owns a node and shares nothing with the other waves of its workgroup (no barrier at all
 // here).  A lane owns the subset's pixels lane, lane + 64, ... (at most 16 at R = 15; with N < 64 lanes idle).  What is constant
 // over the iterations -- fd, fx, fy of a lane's pixels -- and the samples g of the current iteration live in the wave's slice
@@ -14,19 +18,12 @@
 // redundantly in all lanes, nothing is broadcast, and every branch on a node's state is uniform over the wave.
 // Frame 1 is gathered from global memory, 16 taps per pixel and iteration, clamped to the frame; nothing of it is staged (a patch
 // per node in LDS was built and measured no faster: DESIGN.md 3.17).
-#include <algorithm>
 #include <cmath>
 
-#include "node_grid.hpp"
-#include "plane_sample.hpp"
 #include "small_cholesky.hpp"
+#include "subset_node.hpp"
 
 namespace {
-
-constexpr int kSubsetMaxWaves = 4;
-constexpr int kSubsetCounts = 7;   // the counts of flow2d_subset_record that are written
-constexpr unsigned kSubsetLdsBytes = 64u * 1024u;  // what a launch may ask for without hipFuncSetAttribute
-constexpr int kStateNoInput = -1, kStateFlat = -2, kStateStrayed = -3;
 
 struct SubsetArgs {
     const float *f0, *f1;
@@ -40,53 +37,6 @@ struct SubsetArgs {
     unsigned slice;  // doubles of one of a wave's four LDS arrays: N rounded up to a multiple of 2
     double epsilon, max_shift, max_gradient;
 };
-
-struct SubsetNode {
-    const float* f0;
-    const float* f1;
-    double *fd, *fx, *fy, *g;  // the wave's LDS arrays
-    int w, h, pitch;
-    int cx, cy, R, side, n;
-    int lane;
-};
-
-template <typename Offset>
-__device__ __forceinline__ double sample_at(const float* f, int x, int y, int pitch)
-{
-    return static_cast<double>(load_at(f, pixel_offset<Offset>(x, y, pitch)));
-}
-
-// The four Catmull-Rom weights of the header for t in [0, 1).
-__device__ __forceinline__ void cubic_weights(double t, double (&wt)[4])
-{
-    wt[0] = ((-0.5 * t + 1.0) * t - 0.5) * t;
-    wt[1] = ((1.5 * t - 2.5) * t) * t + 1.0;
-    wt[2] = ((-1.5 * t + 2.0) * t + 0.5) * t;
-    wt[3] = ((0.5 * t - 0.5) * t) * t;
-}
-
-// g of the header at (X, Y), which lies inside [0, w - 1] x [0, h - 1].
-template <typename Offset>
-__device__ __forceinline__ double cubic_sample(const SubsetNode& nd, double X, double Y)
-{
-    const double fx = floor(X), fy = floor(Y);
-    const int ix = static_cast<int>(fx), iy = static_cast<int>(fy);
-    double wx[4], wy[4];
-    cubic_weights(X - fx, wx);
-    cubic_weights(Y - fy, wy);
-    int col[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) col[i] = min(max(ix - 1 + i, 0), nd.w - 1);
-    double rows[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int y = min(max(iy - 1 + j, 0), nd.h - 1);
-        const double a0 = sample_at<Offset>(nd.f1, col[0], y, nd.pitch), a1 = sample_at<Offset>(nd.f1, col[1], y, nd.pitch),
-                     a2 = sample_at<Offset>(nd.f1, col[2], y, nd.pitch), a3 = sample_at<Offset>(nd.f1, col[3], y, nd.pitch);
-        rows[j] = ((wx[0] * a0 + wx[1] * a1) + wx[2] * a2) + wx[3] * a3;
-    }
-    return ((wy[0] * rows[0] + wy[1] * rows[1]) + wy[2] * rows[2]) + wy[3] * rows[3];
-}
 
 // J of the header for pixel k.
 __device__ __forceinline__ void jacobian(const SubsetNode& nd, int k, double (&J)[6])
@@ -113,17 +63,7 @@ __device__ __forceinline__ int refine_node(const SubsetNode& nd, const SubsetArg
     const int left = nd.cx - nd.R, top = nd.cy - nd.R;
 
     // frame 0: f into the fd array first, its gradients, the mean
-    double sum_f = 0.0;
-    for (int k = nd.lane; k < nd.n; k += 64) {
-        const int ky = k / nd.side, kx = k - ky * nd.side;
-        const int x = left + kx, y = top + ky;
-        const double f = sample_at<Offset>(nd.f0, x, y, nd.pitch);
-        nd.fd[k] = f;
-        nd.fx[k] = (sample_at<Offset>(nd.f0, min(x + 1, nd.w - 1), y, nd.pitch) - sample_at<Offset>(nd.f0, max(x - 1, 0), y, nd.pitch)) * 0.5;
-        nd.fy[k] = (sample_at<Offset>(nd.f0, x, min(y + 1, nd.h - 1), nd.pitch) - sample_at<Offset>(nd.f0, x, max(y - 1, 0), nd.pitch)) * 0.5;
-        sum_f += f;
-    }
-    const double fm = wave_sum(sum_f) / count;
+    const double fm = wave_sum(fill_frame_0<Offset>(nd)) / count;
 
     double df2 = 0.0;
     double hs[21];
@@ -310,7 +250,7 @@ __global__ __launch_bounds__(64 * kSubsetMaxWaves) void subset_refine_kernel(Sub
     int state;
     if (!(finite(u0) && finite(v0)) || !gradients_finite<kFrom>(g0))
         state = kStateNoInput;
-    else if (!(nd.cx - nd.R >= 0 && nd.cy - nd.R >= 0 && nd.cx + nd.R <= a.w - 1 && nd.cy + nd.R <= a.h - 1))
+    else if (!subset_inside_frame(nd.cx, nd.cy, nd.R, a.w, a.h))
         state = kStateStrayed;
     else
         state = refine_node<Offset>(nd, a, p, score, iterations);
@@ -359,44 +299,15 @@ int subset_refine_entry(flow2d_context* ctx, const float* frame_0, const float* 
                         float max_shift, float max_gradient, float* out_u, float* out_v, float* out_ux, float* out_uy, float* out_vx,
                         float* out_vy, float* out_score, float* out_state, flow2d_subset_record* record)
 {
-    if (ctx == nullptr) return FLOW2D_ERR_INVALID_ARGUMENT;
-    // (every check that needs no context field comes first: they hold without a device)
-    if (!flow2d::planes_ok({frame_0, frame_1}, {}, width, height, pitch_bytes)) return FLOW2D_ERR_INVALID_ARGUMENT;
-    const int shared = flow2d::subset_refine_args_status(width, height, nw, nh, grid_radius, spacing, 1, subset_radius, max_iterations,
-                                                         epsilon, {max_shift, max_gradient}, record);
-    if (shared == FLOW2D_ERR_INVALID_ARGUMENT) return shared;
-    const bool gradients = out_ux != nullptr;
-    if ((out_uy != nullptr) != gradients || (out_vx != nullptr) != gradients || (out_vy != nullptr) != gradients)
-        return FLOW2D_ERR_INVALID_ARGUMENT;
-    // the start gradients: all or none
+    const float* const starts[6] = {node_u0, start[0], start[1], node_v0, start[2], start[3]};
+    float* const outs[6] = {out_u, out_ux, out_uy, out_v, out_vx, out_vy};
+    flow2d::SubsetWaves lds;
+    const int status = flow2d::subset_refine_enter(ctx, frame_0, frame_1, nullptr, width, height, pitch_bytes, starts, outs, 6, out_score,
+                                                   out_state, record, nw, nh, node_pitch_bytes, grid_radius, spacing, 1, subset_radius,
+                                                   max_iterations, epsilon, {max_shift, max_gradient}, 0, lds);
+    if (status != FLOW2D_OK) return status;
     const bool started = start[0] != nullptr;
-    if ((start[1] != nullptr) != started || (start[2] != nullptr) != started || (start[3] != nullptr) != started)
-        return FLOW2D_ERR_INVALID_ARGUMENT;
-    if (!flow2d::planes_ok({node_u0, node_v0, out_u, out_v},
-                           {out_ux, out_uy, out_vx, out_vy, out_score, out_state, start[0], start[1], start[2], start[3]}, nw, nh,
-                           node_pitch_bytes))
-        return FLOW2D_ERR_INVALID_ARGUMENT;
-    if (shared != FLOW2D_OK) return shared;  // (the node count)
-    // the kernel reads frames and nodes while other waves write: no written byte range may meet a read one or another written one
-    auto aliased = [&](size_t frame_span, size_t node_span, size_t instances) {
-        const flow2d::ByteRange written[] = {{out_u, node_span},  {out_v, node_span},  {out_ux, node_span},
-                                             {out_uy, node_span}, {out_vx, node_span}, {out_vy, node_span},
-                                             {out_score, node_span}, {out_state, node_span},
-                                             {record, instances * sizeof(flow2d_subset_record)}};
-        const flow2d::ByteRange read[] = {{frame_0, frame_span}, {frame_1, frame_span}, {node_u0, node_span}, {node_v0, node_span},
-                                          {start[0], node_span}, {start[1], node_span}, {start[2], node_span}, {start[3], node_span}};
-        return flow2d::any_overlap(written, read);
-    };
-    if (aliased(height * pitch_bytes, nh * node_pitch_bytes, 1)) return FLOW2D_ERR_INVALID_ARGUMENT;
-    FLOW2D_ENTER(ctx);
-    const size_t instances = ctx->batch_count;
-    if (aliased(flow2d::batch_span(ctx, height * pitch_bytes), flow2d::batch_span(ctx, nh * node_pitch_bytes), instances))
-        return FLOW2D_ERR_INVALID_ARGUMENT;
-    FLOW2D_HIP_TRY(flow2d::clear_records(ctx, record));
-    const unsigned side = static_cast<unsigned>(2 * subset_radius + 1);
-    const unsigned slice = (side * side + 1u) & ~1u;                       // at most 962 doubles
-    const unsigned wave_bytes = 4u * slice * sizeof(double);               // at most 30 784
-    const unsigned waves = std::min<unsigned>(kSubsetMaxWaves, kSubsetLdsBytes / wave_bytes);  // 4 up to R = 10, 3 at 11 and 12, 2 beyond
+    const unsigned slice = lds.slice, wave_bytes = lds.wave_bytes, waves = lds.waves;
     const SubsetArgs a = {frame_0, frame_1, node_u0, node_v0, out_u, out_v, out_ux, out_uy, out_vx, out_vy, out_score, out_state,
                           reinterpret_cast<unsigned long long*>(record),
                           static_cast<int>(width), static_cast<int>(height), static_cast<int>(pitch_bytes / 4),

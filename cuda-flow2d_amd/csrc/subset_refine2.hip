@@ -16,20 +16,13 @@
 // Frame 1 is gathered from global memory, 16 taps per pixel and iteration, clamped to the frame.
 // The sample of the deformed frame is a template parameter (subset_sample.hpp): CatmullRom is flow2d_subset_refine2_2d, BSpline on
 // frame 1's coefficients flow2d_subset_refine2_spline_2d, whose taps are reflected.  Both entries share one host body.
-#include <algorithm>
 #include <cmath>
 
-#include "node_grid.hpp"
-#include "plane_sample.hpp"
-#include "subset_sample.hpp"
+#include "subset_node.hpp"
 
 namespace {
 
-constexpr int kSubset2MaxWaves = 4;
-constexpr int kSubset2Counts = 7;                   // the counts of flow2d_subset_record that are written
-constexpr unsigned kSubset2LdsBytes = 64u * 1024u;  // what a launch may ask for without hipFuncSetAttribute
-constexpr unsigned kFactorDoubles = 78;             // the lower triangle of a 12 x 12 matrix
-constexpr int kStateNoInput = -1, kStateFlat = -2, kStateStrayed = -3;
+constexpr unsigned kFactorDoubles = 78;  // the lower triangle of a 12 x 12 matrix
 
 struct Subset2Args {
     const float *f0, *f1;
@@ -44,14 +37,8 @@ struct Subset2Args {
     double epsilon, max_shift, max_gradient, max_curvature;
 };
 
-struct Subset2Node {
-    const float* f0;
-    const float* f1;
-    double *fd, *fx, *fy, *g;  // the wave's pixel arrays
-    double* L;                 // H's lower triangle, then the factor's: element (i, j) at i*(i + 1)/2 + j
-    int w, h, pitch;
-    int cx, cy, R, side, n;
-    int lane;
+struct Subset2Node : SubsetNode {
+    double* L;  // H's lower triangle, then the factor's, behind the pixel arrays: element (i, j) at i*(i + 1)/2 + j
 };
 
 // phi of the header for pixel k.
@@ -255,17 +242,7 @@ __device__ __forceinline__ int refine_node(const Subset2Node& nd, const Subset2A
     const int left = nd.cx - nd.R, top = nd.cy - nd.R;
 
     // frame 0: f into the fd array first, its gradients, the mean
-    double sum_f = 0.0;
-    for (int k = nd.lane; k < nd.n; k += 64) {
-        const int ky = k / nd.side, kx = k - ky * nd.side;
-        const int x = left + kx, y = top + ky;
-        const double f = sample_at<Offset>(nd.f0, x, y, nd.pitch);
-        nd.fd[k] = f;
-        nd.fx[k] = (sample_at<Offset>(nd.f0, min(x + 1, nd.w - 1), y, nd.pitch) - sample_at<Offset>(nd.f0, max(x - 1, 0), y, nd.pitch)) * 0.5;
-        nd.fy[k] = (sample_at<Offset>(nd.f0, x, min(y + 1, nd.h - 1), nd.pitch) - sample_at<Offset>(nd.f0, x, max(y - 1, 0), nd.pitch)) * 0.5;
-        sum_f += f;
-    }
-    const double fm = wave_sum(sum_f) / count;
+    const double fm = wave_sum(fill_frame_0<Offset>(nd)) / count;
     double df2 = 0.0;
     for (int k = nd.lane; k < nd.n; k += 64) {
         const double fd = nd.fd[k] - fm;
@@ -362,7 +339,7 @@ __device__ __forceinline__ int refine_node(const Subset2Node& nd, const Subset2A
 // Compiled for three waves per SIMD, the occupancy of subset_refine_kernel: 164 / 166 VGPRs and no scratch.  Left to itself the
 // compiler takes 256 (one wave); asked for four it spills (profiles/subset2/resource_usage.txt).
 template <typename Offset, typename Sampler>
-__global__ __launch_bounds__(64 * kSubset2MaxWaves) __attribute__((amdgpu_waves_per_eu(3, 3))) void subset_refine2_kernel(Subset2Args a, BatchArg batch)
+__global__ __launch_bounds__(64 * kSubsetMaxWaves) __attribute__((amdgpu_waves_per_eu(3, 3))) void subset_refine2_kernel(Subset2Args a, BatchArg batch)
 {
     extern __shared__ __attribute__((aligned(16))) double s_subset2[];
 
@@ -373,6 +350,7 @@ __global__ __launch_bounds__(64 * kSubset2MaxWaves) __attribute__((amdgpu_waves_
     const int jn = node / a.nw, in = node - jn * a.nw;
 
     Subset2Node nd;
+    // (set-up and record stay written out here as in subset_refine_kernel: through a shared helper this kernel's registers moved)
     nd.f0 = a.f0 + inst;
     nd.f1 = a.f1 + inst;
     nd.fd = s_subset2 + static_cast<size_t>(wave) * (4u * a.slice + kFactorDoubles);
@@ -406,7 +384,7 @@ __global__ __launch_bounds__(64 * kSubset2MaxWaves) __attribute__((amdgpu_waves_
     int state;
     if (!is_finite)
         state = kStateNoInput;
-    else if (!(nd.cx - nd.R >= 0 && nd.cy - nd.R >= 0 && nd.cx + nd.R <= a.w - 1 && nd.cy + nd.R <= a.h - 1))
+    else if (!subset_inside_frame(nd.cx, nd.cy, nd.R, a.w, a.h))
         state = kStateStrayed;
     else
         state = refine_node<Offset, Sampler>(nd, a, p, score, iterations);
@@ -419,20 +397,10 @@ __global__ __launch_bounds__(64 * kSubset2MaxWaves) __attribute__((amdgpu_waves_
     if (a.score) a.score[at] = out_score;
     if (a.state) a.state[at] = static_cast<float>(state);
     if (a.record) {
-        const unsigned counts[kSubset2Counts] = {1u, state >= 1, state == 0, state == kStateStrayed, state == kStateFlat,
-                                                 state == kStateNoInput, iterations};
+        const unsigned counts[kSubsetCounts] = {1u, state >= 1, state == 0, state == kStateStrayed, state == kStateFlat,
+                                                state == kStateNoInput, iterations};
         add_counts<kCountRecordWords>(a.record, blockIdx.z, counts);
     }
-}
-
-// Whether the n pointers are all there (1), all absent (0) or given in part (-1); a null array is all absent.
-template <typename Pointer>
-int all_or_none(Pointer const* planes, int n)
-{
-    if (planes == nullptr) return 0;
-    int there = 0;
-    for (int i = 0; i < n; ++i) there += planes[i] != nullptr;
-    return there == n ? 1 : there == 0 ? 0 : -1;
 }
 
 // The body of both entries; frame_1 is the frame for CatmullRom and its coefficients for BSpline.
@@ -444,64 +412,31 @@ int subset_refine2(flow2d_context* ctx, const float* frame_0, const float* frame
                    float* out_u, float* out_v, float* const* out_gradients, float* const* out_curvatures, float* out_score,
                    float* out_state, flow2d_subset_record* record)
 {
-    if (ctx == nullptr) return FLOW2D_ERR_INVALID_ARGUMENT;
-    // (every check that needs no context field comes first: they hold without a device)
-    if (!flow2d::planes_ok({frame_0, frame_1}, {}, width, height, pitch_bytes)) return FLOW2D_ERR_INVALID_ARGUMENT;
-    const int shared = flow2d::subset_refine_args_status(width, height, nw, nh, grid_radius, spacing, FLOW2D_SUBSET2_MIN_RADIUS, subset_radius,
-                                                         max_iterations, epsilon, {max_shift, max_gradient, max_curvature}, record);
-    if (shared == FLOW2D_ERR_INVALID_ARGUMENT) return shared;
-    const int gradients = all_or_none(out_gradients, 4), curvatures = all_or_none(out_curvatures, 6);
-    const int started = all_or_none(start_gradients, 4), curved = all_or_none(start_curvatures, 6);
-    if (gradients < 0 || curvatures < 0 || started < 0 || curved < 0 || (curved == 1 && started == 0)) return FLOW2D_ERR_INVALID_ARGUMENT;
-    // the planes in the order of p; what is absent stays null
-    const float* start[12] = {node_u0, nullptr, nullptr, nullptr, nullptr, nullptr, node_v0, nullptr, nullptr, nullptr, nullptr, nullptr};
-    float* out[12] = {out_u, nullptr, nullptr, nullptr, nullptr, nullptr, out_v, nullptr, nullptr, nullptr, nullptr, nullptr};
+    // the planes in the order of p; a group that is absent, or a place in it, stays null
+    Subset2Args a = {};
+    a.start[0] = node_u0;
+    a.start[6] = node_v0;
+    a.out[0] = out_u;
+    a.out[6] = out_v;
     for (int half = 0; half < 2; ++half) {
         for (int i = 0; i < 2; ++i) {
-            if (started == 1) start[6 * half + 1 + i] = start_gradients[2 * half + i];
-            if (gradients == 1) out[6 * half + 1 + i] = out_gradients[2 * half + i];
+            if (start_gradients) a.start[6 * half + 1 + i] = start_gradients[2 * half + i];
+            if (out_gradients) a.out[6 * half + 1 + i] = out_gradients[2 * half + i];
         }
         for (int i = 0; i < 3; ++i) {
-            if (curved == 1) start[6 * half + 3 + i] = start_curvatures[3 * half + i];
-            if (curvatures == 1) out[6 * half + 3 + i] = out_curvatures[3 * half + i];
+            if (start_curvatures) a.start[6 * half + 3 + i] = start_curvatures[3 * half + i];
+            if (out_curvatures) a.out[6 * half + 3 + i] = out_curvatures[3 * half + i];
         }
     }
-    if (!flow2d::planes_ok({node_u0, node_v0, out_u, out_v}, {out_score, out_state}, nw, nh, node_pitch_bytes))
-        return FLOW2D_ERR_INVALID_ARGUMENT;
-    for (int i = 0; i < 12; ++i)
-        if (!flow2d::planes_ok({}, {start[i], out[i]}, nw, nh, node_pitch_bytes)) return FLOW2D_ERR_INVALID_ARGUMENT;
-    if (shared != FLOW2D_OK) return shared;  // (the node count)
-    // the kernel reads frames and nodes while other waves write: no written byte range may meet a read one or another written one
-    auto aliased = [&](size_t frame_span, size_t node_span, size_t instances) {
-        flow2d::ByteRange written[15], read[14];
-        for (int i = 0; i < 12; ++i) {
-            written[i] = {out[i], node_span};
-            read[i] = {start[i], node_span};
-        }
-        written[12] = {out_score, node_span};
-        written[13] = {out_state, node_span};
-        written[14] = {record, instances * sizeof(flow2d_subset_record)};
-        read[12] = {frame_0, frame_span};
-        read[13] = {frame_1, frame_span};
-        return flow2d::any_overlap(written, read);
-    };
-    if (aliased(height * pitch_bytes, nh * node_pitch_bytes, 1)) return FLOW2D_ERR_INVALID_ARGUMENT;
-    FLOW2D_ENTER(ctx);
-    const size_t instances = ctx->batch_count;
-    if (aliased(flow2d::batch_span(ctx, height * pitch_bytes), flow2d::batch_span(ctx, nh * node_pitch_bytes), instances))
-        return FLOW2D_ERR_INVALID_ARGUMENT;
-    FLOW2D_HIP_TRY(flow2d::clear_records(ctx, record));
-    const unsigned side = static_cast<unsigned>(2 * subset_radius + 1);
-    const unsigned slice = (side * side + 1u) & ~1u;                                      // at most 962 doubles
-    const unsigned wave_bytes = (4u * slice + kFactorDoubles) * sizeof(double);           // at most 31 408
-    const unsigned waves = std::min<unsigned>(kSubset2MaxWaves, kSubset2LdsBytes / wave_bytes);  // 4 up to R = 10, 3 at 11 and 12, 2 beyond
-    Subset2Args a;
+    flow2d::SubsetWaves lds;  // (a wave's bytes: at most 31 408)
+    const int status = flow2d::subset_refine_enter(ctx, frame_0, frame_1, nullptr, width, height, pitch_bytes, a.start, a.out, 12, out_score,
+                                                   out_state, record, nw, nh, node_pitch_bytes, grid_radius, spacing,
+                                                   FLOW2D_SUBSET2_MIN_RADIUS, subset_radius, max_iterations, epsilon,
+                                                   {max_shift, max_gradient, max_curvature}, kFactorDoubles * sizeof(double), lds);
+    if (status != FLOW2D_OK) return status;
+    const unsigned slice = lds.slice, wave_bytes = lds.wave_bytes, waves = lds.waves;
     a.f0 = frame_0;
     a.f1 = frame_1;
-    for (int i = 0; i < 12; ++i) {
-        a.start[i] = start[i];
-        a.out[i] = out[i];
-    }
     a.score = out_score;
     a.state = out_state;
     a.record = reinterpret_cast<unsigned long long*>(record);

@@ -22,23 +22,18 @@
 // flow2d_subset_refine_masked_2d; <BSpline, true> and <BSpline, false> are flow2d_subset_refine_spline_2d on frame 1's coefficients
 // (subset_sample.hpp), with and without a mask.  Without one the compaction is compiled out -- no mask loads, no ballots, no index
 // list read: the list is k itself, element m is pixel m, and the sums are those of a mask that excludes nothing, bit for bit.
-// subset_refine.hip is left as it is (its instruction streams are measured ones); the sampling helpers are subset_sample.hpp's, which
-// subset_refine2.hip shares, the factorisation and the solve small_cholesky.hpp's.
-#include <algorithm>
+// <CatmullRom, false> is not instantiated: it gives subset_refine.hip's bytes, but that file's kernel is the faster one at R = 15
+// (profiles/subset_unified/README.md).  The node, the frame-0 fill, the window test and the host body are subset_node.hpp's, the
+// samplers subset_sample.hpp's, the factorisation and the solve small_cholesky.hpp's.
 #include <cmath>
 #include <type_traits>
 
-#include "node_grid.hpp"
-#include "plane_sample.hpp"
-#include "subset_sample.hpp"
 #include "small_cholesky.hpp"
+#include "subset_node.hpp"
 
 namespace {
 
-constexpr int kMaskedMaxWaves = 4;
-constexpr int kMaskedCounts = 8;                    // the seven counts of flow2d_subset_record and the masked nodes
-constexpr unsigned kMaskedLdsBytes = 64u * 1024u;   // what a launch may ask for without hipFuncSetAttribute
-constexpr int kStateNoInput = -1, kStateFlat = -2, kStateStrayed = -3, kStateMasked = FLOW2D_SUBSET_STATE_MASKED;
+constexpr int kMaskedCounts = kSubsetCounts + 1;  // the seven counts of flow2d_subset_record and the masked nodes
 
 struct MaskedArgs {
     const float *f0, *f1, *mask;
@@ -56,16 +51,10 @@ struct MaskedArgs {
     double epsilon, max_shift, max_gradient;
 };
 
-struct MaskedNode {
-    const float* f0;
-    const float* f1;
+struct MaskedNode : SubsetNode {  // (the LDS arrays compacted: element m belongs to pixel index[m])
     const float* mask;
-    double *fd, *fx, *fy, *g;  // the wave's LDS arrays, compacted: element m belongs to pixel index[m]
-    unsigned short* index;     // the usable pixels' k in ascending order
-    int w, h, pitch;
-    int cx, cy, R, side, n;
-    int nv;                    // the usable pixels
-    int lane;
+    unsigned short* index;  // the usable pixels' k in ascending order
+    int nv;                 // the usable pixels
 };
 
 // *Excluded* of the header: 1 means "do not use", and a NaN is excluded.
@@ -139,22 +128,6 @@ __device__ __forceinline__ int compact_usable(const MaskedNode& nd)
     }
     __builtin_amdgcn_wave_barrier();  // the reads of the slots below stay below these writes
     return nv;
-}
-
-// compact_usable without a mask: every pixel is usable and slot k is pixel k's, filled by the lane that reads it afterwards.
-template <typename Offset>
-__device__ __forceinline__ int fill_all(const MaskedNode& nd)
-{
-    const int left = nd.cx - nd.R, top = nd.cy - nd.R;
-    for (int k = nd.lane; k < nd.n; k += 64) {
-        const int ky = k / nd.side, kx = k - ky * nd.side;
-        const int x = left + kx, y = top + ky;
-        const int xp = min(x + 1, nd.w - 1), xm = max(x - 1, 0), yp = min(y + 1, nd.h - 1), ym = max(y - 1, 0);
-        nd.fd[k] = sample_at<Offset>(nd.f0, x, y, nd.pitch);
-        nd.fx[k] = (sample_at<Offset>(nd.f0, xp, y, nd.pitch) - sample_at<Offset>(nd.f0, xm, y, nd.pitch)) * 0.5;
-        nd.fy[k] = (sample_at<Offset>(nd.f0, x, yp, nd.pitch) - sample_at<Offset>(nd.f0, x, ym, nd.pitch)) * 0.5;
-    }
-    return nd.n;
 }
 
 // The node from the frame-0 quantities compact_usable left in LDS on, over the nd.nv usable pixels: the state, with p, the last c
@@ -276,7 +249,7 @@ __device__ __forceinline__ int refine_node(const MaskedNode& nd, const MaskedArg
 
 // A wave's node from its inputs to its outputs.
 template <typename Offset, typename Sampler, bool kMasked>
-__global__ __launch_bounds__(64 * kMaskedMaxWaves) void subset_refine_masked_kernel(MaskedArgs a, BatchArg batch)
+__global__ __launch_bounds__(64 * kSubsetMaxWaves) void subset_refine_masked_kernel(MaskedArgs a, BatchArg batch)
 {
     extern __shared__ __attribute__((aligned(16))) double s_masked[];
 
@@ -325,10 +298,15 @@ __global__ __launch_bounds__(64 * kMaskedMaxWaves) void subset_refine_masked_ker
         state = kStateMasked;
     else if (!(finite(u0) && finite(v0) && finite(g0[0]) && finite(g0[1]) && finite(g0[2]) && finite(g0[3])))
         state = kStateNoInput;
-    else if (!(nd.cx - nd.R >= 0 && nd.cy - nd.R >= 0 && nd.cx + nd.R <= a.w - 1 && nd.cy + nd.R <= a.h - 1))
+    else if (!subset_inside_frame(nd.cx, nd.cy, nd.R, a.w, a.h))
         state = kStateStrayed;
     else {
-        nd.nv = kMasked ? compact_usable<Offset>(nd) : fill_all<Offset>(nd);
+        if constexpr (kMasked) {
+            nd.nv = compact_usable<Offset>(nd);
+        } else {  // every pixel is usable and slot k is pixel k's, filled by the lane that reads it afterwards
+            fill_frame_0<Offset>(nd);
+            nd.nv = nd.n;
+        }
         if (kMasked && !(nd.nv >= a.min_pixels))
             state = kStateMasked;
         else
@@ -379,46 +357,17 @@ int subset_refine_masked(flow2d_context* ctx, const float* frame_0, const float*
                          const float* mask, int min_pixels, float* out_u, float* out_v, float* out_ux, float* out_uy, float* out_vx,
                          float* out_vy, float* out_score, float* out_state, flow2d_subset_record* record)
 {
-    if (ctx == nullptr) return FLOW2D_ERR_INVALID_ARGUMENT;
-    // (every check that needs no context field comes first: they hold without a device)
-    if (!flow2d::planes_ok({frame_0, frame_1}, {mask}, width, height, pitch_bytes)) return FLOW2D_ERR_INVALID_ARGUMENT;
-    const int shared = flow2d::subset_refine_args_status(width, height, nw, nh, grid_radius, spacing, 1, subset_radius, max_iterations,
-                                                         epsilon, {max_shift, max_gradient}, record);
-    if (shared == FLOW2D_ERR_INVALID_ARGUMENT) return shared;
-    const int pixels = (2 * subset_radius + 1) * (2 * subset_radius + 1);
+    const long long pixels = (2LL * subset_radius + 1) * (2LL * subset_radius + 1);
     if (mask != nullptr && (min_pixels < FLOW2D_SUBSET_MIN_PIXELS || min_pixels > pixels)) return FLOW2D_ERR_INVALID_ARGUMENT;
-    const bool gradients = out_ux != nullptr;
-    if ((out_uy != nullptr) != gradients || (out_vx != nullptr) != gradients || (out_vy != nullptr) != gradients)
-        return FLOW2D_ERR_INVALID_ARGUMENT;
-    // the start gradients: all or none
-    const bool started = node_ux0 != nullptr;
-    if ((node_uy0 != nullptr) != started || (node_vx0 != nullptr) != started || (node_vy0 != nullptr) != started)
-        return FLOW2D_ERR_INVALID_ARGUMENT;
-    if (!flow2d::planes_ok({node_u0, node_v0, out_u, out_v},
-                           {out_ux, out_uy, out_vx, out_vy, out_score, out_state, node_ux0, node_uy0, node_vx0, node_vy0}, nw, nh,
-                           node_pitch_bytes))
-        return FLOW2D_ERR_INVALID_ARGUMENT;
-    if (shared != FLOW2D_OK) return shared;  // (the node count)
-    // the kernel reads frames, mask and nodes while other waves write: no written byte range may meet a read one or another written one
-    auto aliased = [&](size_t frame_span, size_t node_span, size_t instances) {
-        const flow2d::ByteRange written[] = {{out_u, node_span},  {out_v, node_span},  {out_ux, node_span},
-                                             {out_uy, node_span}, {out_vx, node_span}, {out_vy, node_span},
-                                             {out_score, node_span}, {out_state, node_span},
-                                             {record, instances * sizeof(flow2d_subset_record)}};
-        const flow2d::ByteRange read[] = {{frame_0, frame_span}, {frame_1, frame_span}, {mask, frame_span}, {node_u0, node_span},
-                                          {node_v0, node_span}, {node_ux0, node_span}, {node_uy0, node_span}, {node_vx0, node_span},
-                                          {node_vy0, node_span}};
-        return flow2d::any_overlap(written, read);
-    };
-    if (aliased(height * pitch_bytes, nh * node_pitch_bytes, 1)) return FLOW2D_ERR_INVALID_ARGUMENT;
-    FLOW2D_ENTER(ctx);
-    const size_t instances = ctx->batch_count;
-    if (aliased(flow2d::batch_span(ctx, height * pitch_bytes), flow2d::batch_span(ctx, nh * node_pitch_bytes), instances))
-        return FLOW2D_ERR_INVALID_ARGUMENT;
-    FLOW2D_HIP_TRY(flow2d::clear_records(ctx, record));
-    const unsigned slice = (static_cast<unsigned>(pixels) + 1u) & ~1u;                      // at most 962 doubles
-    const unsigned wave_bytes = 4u * slice * sizeof(double) + ((2u * slice + 7u) & ~7u);    // at most 30 784 + 1 928
-    const unsigned waves = std::min<unsigned>(kMaskedMaxWaves, kMaskedLdsBytes / wave_bytes);  // 4 up to R = 10, 3 at 11 and 12, 2 beyond
+    const float* const starts[6] = {node_u0, node_ux0, node_uy0, node_v0, node_vx0, node_vy0};
+    float* const outs[6] = {out_u, out_ux, out_uy, out_v, out_vx, out_vy};
+    flow2d::SubsetWaves lds;  // (behind the four arrays the index list, two bytes per pixel: at most 1 928)
+    const int status = flow2d::subset_refine_enter(ctx, frame_0, frame_1, mask, width, height, pitch_bytes, starts, outs, 6, out_score,
+                                                   out_state, record, nw, nh, node_pitch_bytes, grid_radius, spacing, 1, subset_radius,
+                                                   max_iterations, epsilon, {max_shift, max_gradient},
+                                                   (2u * static_cast<unsigned>(pixels + 1) + 7u) & ~7u, lds);
+    if (status != FLOW2D_OK) return status;
+    const unsigned slice = lds.slice, wave_bytes = lds.wave_bytes, waves = lds.waves;
     const MaskedArgs a = {frame_0, frame_1, mask, node_u0, node_v0, node_ux0, node_uy0, node_vx0, node_vy0,
                           out_u, out_v, out_ux, out_uy, out_vx, out_vy, out_score, out_state,
                           reinterpret_cast<unsigned long long*>(record),

@@ -1,9 +1,8 @@
-// What the subset refinements that came after flow2d_subset_refine_2d share (subset_refine2.hip, subset_refine_masked.hip): a frame
-// sample as a double and the two samples of the deformed frame -- the Catmull-Rom sample of frame 1, as flow2d_subset_refine_2d's
-// text in flow2d_c_abi.h states it, and the cubic B-spline sample of frame 1's coefficients, as flow2d_subset_refine_spline_2d's
-// does.  Node: the kernel's own description of its node, of which f1 (the frame, or its coefficients), w, h and pitch (in floats)
-// are read.  The kernels take the sample as a template parameter, CatmullRom or BSpline.
-// subset_refine.hip keeps its own copy: its instruction streams are measured ones and the file is left as it is.
+// The samples the subset refinements share (subset_refine.hip, subset_refine2.hip, subset_refine_masked.hip): a frame sample as a double and the two samples
+// of the deformed frame -- the Catmull-Rom sample of frame 1, as flow2d_subset_refine_2d's text in flow2d_c_abi.h states it, and the
+// cubic B-spline sample of frame 1's coefficients, as flow2d_subset_refine_spline_2d's does.  Node: the kernel's own description of
+// its node (subset_node.hpp), of which f1 (the frame, or its coefficients), w, h and pitch (in floats) are read.  The kernels take
+// the sample as a template parameter, CatmullRom or BSpline.
 #pragma once
 
 #include "plane_sample.hpp"

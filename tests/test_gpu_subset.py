@@ -205,6 +205,37 @@ def test_the_wrapper_allocates_and_downloads(flow2d, ctx):
 
 
 # ---- the same bytes -------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("R", [3, 7])
+def test_four_entries_give_the_same_bytes(flow2d, ctx, R):
+    """flow2d_subset_refine_2d, flow2d_subset_refine_from_2d with four all-zero start planes and flow2d_subset_refine_masked_2d
+    without a mask and with an all-zero one: the same eight planes and the same record, byte for byte, the record's eighth word 0.
+    48 x 40 with the grid (7, s 8), 5 x 4 nodes: R = 3 leaves lanes idle (N = 49), R = 7 gives a lane several pixels; one node
+    without input, one whose start takes its subset out of the frame, one on a flat patch of frame 0."""
+    from test_gpu_subset_masked import run_masked  # (those modules import this one)
+    from test_gpu_subset_sequence import run_from
+
+    f0, f1, u0, v0 = speckle_case(48, 40, 7, 8)
+    assert u0.shape == (4, 5)
+    f0, u0 = f0.copy(), u0.copy()
+    u0[1, 1], u0[0, 0] = np.nan, -20.0
+    f0[23 - 8:23 + 9, 31 - 8:31 + 9] = 100.0  # node (3, 2), centre (31, 23): its subset and the stencil around it
+    zeros = [np.zeros_like(u0) for _ in range(4)]
+    got = {"plain": run_subset(ctx, f0, f1, u0, v0, 7, 8, R, max_shift=2.0),
+           "from, zero start": run_from(ctx, f0, f1, [u0, v0] + zeros, 7, 8, R, max_shift=2.0),
+           "masked, no mask": run_masked(ctx, f0, f1, (u0, v0), None, 0, 7, 8, R, max_shift=2.0),
+           "masked, zero mask": run_masked(ctx, f0, f1, (u0, v0), np.zeros_like(f0), (2 * R + 1) ** 2, 7, 8, R, max_shift=2.0)}
+    planes, raw = got["plain"]
+    state = planes[7].view(F32)
+    assert state[1, 1] == NO_INPUT and state[0, 0] == STRAYED and state[2, 3] == FLAT and (state >= 1).sum() >= 5
+    assert np.isnan(planes[0].view(F32)[1, 1]) and planes[0].view(F32)[0, 0] == -20.0 and not planes[2][0, 0] and not planes[5][2, 3]
+    record = np.frombuffer(raw, SUBSET_DTYPE)[0]
+    assert record["nodes"] == 20 and record["no_input"] == 1 and record["flat"] >= 1 and record["strayed"] >= 1
+    for what, (other, other_raw) in got.items():
+        for name, a, b in zip(Refined.NAMES, other, planes):
+            assert np.array_equal(a, b), "%s: %s" % (what, name)
+        assert other_raw == raw and np.frombuffer(other_raw, SUBSET_DTYPE)["reserved"][0] == 0, what
+
+
 def test_repeated_calls_and_a_replayed_graph(flow2d, ctx):
     w, h, r, s, R = 130, 37, 7, 8, 7
     lib = flow2d.hip_lib()

@@ -416,6 +416,61 @@ def test_refusals_without_a_device(flow2d):
     # (only refusals here: an accepted call would go on to launch on these made-up addresses where there is a device)
 
 
+def subset_entries(lib):
+    """Every subset refinement entry as a function of one dictionary of arguments (g, c: the out gradients and curvatures; sg, sc:
+    the start's, lists or None), each entry taking those it has."""
+    def group(planes, n):
+        return (ctypes.c_void_p * n)(*planes) if planes is not None else None
+
+    def order_1(entry, start, mask):
+        def call(a):
+            sg = a["sg"] if a["sg"] is not None else [None] * 4
+            return entry(a["ctx"], a["f0"], a["f1"], a["w"], a["h"], a["pitch"], a["u0"], a["v0"], *(sg if start else []), a["nw"], a["nh"],
+                         a["npitch"], a["r"], a["s"], a["R"], a["K"], a["eps"], a["shift"], a["grad"],
+                         *([a["mask"] if mask == "mask" else None, a["min_pixels"]] if mask else []), a["u"], a["v"], *a["g"], a["score"],
+                         a["state"], a["record"])
+        return call
+
+    def order_2(entry):
+        def call(a):
+            return entry(a["ctx"], a["f0"], a["f1"], a["w"], a["h"], a["pitch"], a["u0"], a["v0"], group(a["sg"], 4), group(a["sc"], 6),
+                         a["nw"], a["nh"], a["npitch"], a["r"], a["s"], a["R"], a["K"], a["eps"], a["shift"], a["grad"], a["curv"], a["u"],
+                         a["v"], group(a["g"], 4), group(a["c"], 6), a["score"], a["state"], a["record"])
+        return call
+
+    return {"plain": order_1(lib.flow2d_subset_refine_2d, False, None), "from": order_1(lib.flow2d_subset_refine_from_2d, True, None),
+            "masked": order_1(lib.flow2d_subset_refine_masked_2d, True, "mask"),
+            "masked, no mask": order_1(lib.flow2d_subset_refine_masked_2d, True, "none"),
+            "spline": order_1(lib.flow2d_subset_refine_spline_2d, True, "mask"),
+            "spline, no mask": order_1(lib.flow2d_subset_refine_spline_2d, True, "none"),
+            "order 2": order_2(lib.flow2d_subset_refine2_2d), "order 2, spline": order_2(lib.flow2d_subset_refine2_spline_2d)}
+
+
+NODES_2_31 = dict(w=(1 << 16) + 4, h=(1 << 15) + 4, pitch=4 * ((1 << 16) + 4), nw=1 << 16, nh=1 << 15, npitch=4 << 16, r=2, s=1, R=2, min_pixels=6)
+
+
+@pytest.mark.parametrize("change,status", [
+    (dict(R=0), 1), (dict(K=0), 1), (dict(eps=float("nan")), 1), (dict(record="misaligned"), 1), (dict(nw=12), 1), (dict(g="partial"), 1),
+    (dict(u="frame 1"), 1), (NODES_2_31, 5), (dict(NODES_2_31, f0="misaligned"), 1), (dict(NODES_2_31, v=None), 1)],
+    ids=["radius 0", "no iteration", "NaN epsilon", "misaligned record", "nw beyond the grid", "gradient planes in part",
+         "an out plane in frame 1", "2^31 nodes", "2^31 nodes, a misaligned frame", "2^31 nodes, no out_v"])
+def test_every_entry_refuses_alike(flow2d, change, status):
+    """One invalid argument to every subset refinement entry: the same status from each.  FLOW2D_ERR_UNSUPPORTED (5), the node count,
+    comes behind every plane check.  Nothing is launched: an accepted call would go on to made-up addresses."""
+    fake = ctypes.create_string_buffer(4096)
+    w, h, pitch, npitch = 100, 40, 512, 64
+    at = lambda k: (1 << 20) + k * (pitch * h + 4096)  # noqa: E731  (addresses only: nothing is dereferenced before the device is entered)
+    a = dict(ctx=ctypes.addressof(fake), f0=at(0), f1=at(1), w=w, h=h, pitch=pitch, u0=at(2), v0=at(3), sg=[at(20 + k) for k in range(4)],
+             sc=[at(24 + k) for k in range(6)], nw=11, nh=4, npitch=npitch, r=7, s=8, R=7, K=20, eps=1e-3, shift=2.0, grad=0.5, curv=0.05,
+             mask=at(19), min_pixels=57, u=at(4), v=at(5), g=[at(6 + k) for k in range(4)], c=[at(10 + k) for k in range(6)], score=at(16),
+             state=at(17), record=at(18))
+    named = {"misaligned": lambda key: a[key] + 4, "partial": lambda key: [None] + a[key][1:], "frame 1": lambda key: at(1) + pitch}
+    a.update({key: named[value](key) if isinstance(value, str) else value for key, value in change.items()})
+    got = {name: call(a) for name, call in subset_entries(flow2d.hip_lib()).items()}
+    print(got)
+    assert got == dict.fromkeys(got, status)
+
+
 def test_python_record_matches_the_restatement_layout(flow2d):
     rec = flow2d.SubsetRecord()
     rec.nodes, rec.converged, rec.unconverged, rec.strayed, rec.flat, rec.no_input, rec.iterations = 9, 1, 2, 3, 4, 5, 6
