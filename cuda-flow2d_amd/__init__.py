@@ -8,6 +8,7 @@ no algorithm and has NO CPU fallback: a missing library or a failing call raises
 The directory name carries a hyphen, so import it with
     importlib.import_module("cuda-flow2d_amd")
 """
+import collections
 import ctypes as C
 import math
 import os
@@ -533,6 +534,12 @@ def hip_lib():
         L.flow2d_timing_enable.argtypes = [vp, i]
         L.flow2d_fused_fallbacks.argtypes = [vp, C.POINTER(C.c_ulonglong)]
         L.flow2d_context_set_lone.argtypes = [vp, i]
+        if hasattr(L, "flow2d_context_set_planning_cus"):  # (absent from libraries of earlier rounds loaded for an A/B)
+            L.flow2d_context_set_planning_cus.argtypes = [vp, i]
+            L.flow2d_context_planning_cus.argtypes = [vp, C.POINTER(i)]
+            L.flow2d_fused_block_order_for_cus.argtypes = [i, sz, sz, sz, sz, C.POINTER(i), sz, C.POINTER(sz)]
+            L.flow2d_fused_plan_for_cus.argtypes = [i, sz, sz, sz, sz, C.POINTER(i), C.POINTER(i)]
+            L.flow2d_stream_rows_for_cus.argtypes = [i, i, sz, sz, i, sz]
         L.flow2d_resample_y_levels.argtypes = [vp, vp, vp, vp, vp, sz, sz, sz, C.POINTER(sz), C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]
         L.flow2d_resample_xy_levels.argtypes = [vp, vp, vp, vp, vp, sz, sz, sz, sz, C.POINTER(sz), C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]
         L.flow2d_resample_xy_levels_launches.argtypes = []
@@ -629,6 +636,45 @@ def half_base_flow_launches():
 def fused_packed_launches():
     """strip launches of this process so far that the packed build of the strip kernel served (flow2d_fused_packed_launches)"""
     return int(hip_lib().flow2d_fused_packed_launches())
+
+
+STREAM_GAUSSIAN, STREAM_MEDIAN = 0, 1
+
+
+def fused_block_order_for_cus(cus, width, height, inner, instances=1):
+    """Context.fused_block_order for a device of `cus` compute units; needs neither a context nor a device
+    (flow2d_fused_block_order_for_cus)."""
+    grid = C.c_size_t(0)
+    cap = 1 << 17
+    buf = (C.c_int * (4 * cap))()
+    _check(hip_lib().flow2d_fused_block_order_for_cus(cus, width, height, inner, instances, buf, cap, C.byref(grid)),
+           "flow2d_fused_block_order_for_cus")
+    return np.frombuffer(buf, np.int32, 4 * grid.value).reshape(-1, 4).copy()
+
+
+class FusedPlan(collections.namedtuple("FusedPlan", "rows_interior rows_edge strips_interior blocks_x blocks side_blocks")):
+    """The strip plan of a level (flow2d_fused_plan_for_cus).  side_blocks: the first and last block column's blocks when the
+    launch order deals them over the eight runs, 0 when it does not (or the plan is uniform)."""
+
+    @property
+    def uniform(self):
+        return self.rows_interior == self.rows_edge
+
+
+def fused_plan_for_cus(cus, width, height, inner, instances=1):
+    """The strip plan a device of `cus` compute units gives a level; needs neither a context nor a device."""
+    plan, side = (C.c_int * 5)(), C.c_int(0)
+    _check(hip_lib().flow2d_fused_plan_for_cus(cus, width, height, inner, instances, plan, C.byref(side)), "flow2d_fused_plan_for_cus")
+    return FusedPlan(*plan, side.value)
+
+
+def stream_rows_for_cus(cus, kind, width, height, radius, instances=1):
+    """Rows per strip of a streaming Gaussian (STREAM_GAUSSIAN, radius 1 ... 6) or median (STREAM_MEDIAN, radius 1 ... 3) launch
+    on a device of `cus` compute units (flow2d_stream_rows_for_cus); needs neither a context nor a device."""
+    rows = hip_lib().flow2d_stream_rows_for_cus(cus, kind, width, height, radius, instances)
+    if rows < 0:
+        raise ValueError("flow2d_stream_rows_for_cus(%r, %r, %r, %r, %r, %r)" % (cus, kind, width, height, radius, instances))
+    return rows
 
 
 def resample_xy_levels_launches():
@@ -756,6 +802,17 @@ class Context:
     def set_lone(self, lone):
         """flow2d_context_set_lone: this context's launches run alone on the device (packed strip build for under-filled launches)"""
         _check(hip_lib().flow2d_context_set_lone(self.handle, int(bool(lone))), "flow2d_context_set_lone")
+
+    def set_planning_cus(self, cus):
+        """flow2d_context_set_planning_cus: the launch planners of this context plan for `cus` compute units from now on (0: the
+        device's own count again).  A hint: the same bytes whatever the value, only the launch geometry changes."""
+        _check(hip_lib().flow2d_context_set_planning_cus(self.handle, int(cus)), "flow2d_context_set_planning_cus")
+
+    def planning_cus(self):
+        """The compute units this context's launch planners plan for (flow2d_context_planning_cus)."""
+        n = C.c_int(0)
+        _check(hip_lib().flow2d_context_planning_cus(self.handle, C.byref(n)), "flow2d_context_planning_cus")
+        return n.value
 
     def set_batch(self, count, stride_bytes=0):
         """flow2d_context_set_batch: from now on every batch-aware launcher of this context acts on `count` instances of its

@@ -24,7 +24,8 @@ struct flow2d_context {
     size_t timing_min_w = 0, timing_min_h = 0;  // flow2d_timing_launch_filter
     std::vector<hipEvent_t> event_pool;          // recycled timing events
     std::vector<flow2d_timing_slot> timings;
-    int num_cus = 256;
+    int num_cus = 256;     // what the launch planners plan for: the device's count, or flow2d_context_set_planning_cus's
+    int device_cus = 256;  // the device's own count (what flow2d_context_set_planning_cus(ctx, 0) goes back to)
     // flow2d_context_set_batch: every launch runs `batch_count` instances, instance b on plane pointers + b * stride
     unsigned batch_count = 1;
     // flow2d_context_set_lone: nothing else of the caller's job runs beside this context's launches
@@ -62,6 +63,20 @@ inline bool plane_args_ok(const void* p, size_t w, size_t h, size_t pitch_bytes)
 }
 
 inline unsigned div_up(size_t a, size_t b) { return static_cast<unsigned>((a + b - 1) / b); }
+
+// Rows per strip of the streaming kernels (the Gaussian blur; the 3 / 5 / 7 medians): halved from max_rows down to min_rows
+// until the launch has four waves per SIMD of `cus` CUs (a context without a count plans for 256).  The launchers and
+// flow2d_stream_rows_for_cus -- what tells a test which strips a launch ran -- go through the two functions below, which
+// go through this one.
+inline int stream_rows_per_strip(int cus, long strips_x, size_t h, size_t instances, long max_rows, long min_rows)
+{
+    const long want_waves = (cus > 0 ? cus : 256) * 4 * 4;  // four waves per SIMD
+    long rows = max_rows;
+    while (rows > min_rows && strips_x * (long)div_up(h, rows) * (long)instances < want_waves) rows /= 2;
+    return (int)rows;
+}
+int gauss_stream_rows(int cus, size_t w, size_t h, int radius, size_t instances);  // pyramid_ops.hip: 16 ... 128
+int median_stream_rows(int cus, size_t w, size_t h, size_t instances);             // median.hip: 8 ... 64, every window
 
 inline BatchArg batch_arg(const flow2d_context* ctx, unsigned planes)
 {

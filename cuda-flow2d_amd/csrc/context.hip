@@ -147,7 +147,7 @@ static int create_context(int device_ordinal, void* stream, bool adopt, flow2d_c
     }
     int cus = 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device_ordinal) == hipSuccess && cus > 0)
-        ctx->num_cus = cus;
+        ctx->num_cus = ctx->device_cus = cus;
     *out_ctx = ctx;
     return FLOW2D_OK;
 }
@@ -396,6 +396,29 @@ int flow2d_context_set_lone(flow2d_context* ctx, int lone)
     if (!ctx) return FLOW2D_ERR_INVALID_ARGUMENT;
     ctx->lone = lone != 0;
     return FLOW2D_OK;
+}
+
+// (host logic only, like the two setters above: nothing here needs the device)
+int flow2d_context_set_planning_cus(flow2d_context* ctx, int cus)
+{
+    if (!ctx || cus < 0 || cus > FLOW2D_PLANNING_CUS_MAX) return FLOW2D_ERR_INVALID_ARGUMENT;
+    ctx->num_cus = cus == 0 ? ctx->device_cus : cus;
+    return FLOW2D_OK;
+}
+
+int flow2d_context_planning_cus(const flow2d_context* ctx, int* cus)
+{
+    if (!ctx || !cus) return FLOW2D_ERR_INVALID_ARGUMENT;
+    *cus = ctx->num_cus > 0 ? ctx->num_cus : 256;  // (a context without a count: what the planners take then)
+    return FLOW2D_OK;
+}
+
+int flow2d_stream_rows_for_cus(int cus, int kind, size_t width, size_t height, int radius, size_t instances)
+{
+    if (cus < 1 || cus > FLOW2D_PLANNING_CUS_MAX || width == 0 || height == 0 || instances == 0 || instances > FLOW2D_BATCH_MAX) return -1;
+    if (kind == FLOW2D_STREAM_GAUSSIAN) return radius >= 1 && radius <= 6 ? flow2d::gauss_stream_rows(cus, width, height, radius, instances) : -1;
+    if (kind == FLOW2D_STREAM_MEDIAN) return radius >= 1 && radius <= 3 ? flow2d::median_stream_rows(cus, width, height, instances) : -1;
+    return -1;
 }
 
 int flow2d_capture_begin(flow2d_context* ctx)

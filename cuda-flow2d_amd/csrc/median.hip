@@ -730,14 +730,16 @@ __global__ __launch_bounds__(256) void median7_stream_kernel(const float* __rest
 // rows per strip: even, tall enough that the four start-up rows are noise, short enough to fill the chip
 int median5_rows_per_strip(const flow2d_context* ctx, size_t w, size_t h)
 {
-    const long strips_x = flow2d::div_up(w, kStreamValid);
-    const long want_waves = (ctx->num_cus > 0 ? ctx->num_cus : 256) * 4 * 4;  // four waves per SIMD
-    long rows = 64;
-    while (rows > 8 && strips_x * (long)flow2d::div_up(h, rows) * (long)ctx->batch_count < want_waves) rows /= 2;
-    return (int)rows;
+    return flow2d::median_stream_rows(ctx->num_cus, w, h, ctx->batch_count);
 }
 
 }  // namespace
+
+// (the three windows share the 5 x 5 filter's count of wave columns: launch_median and flow2d_stream_rows_for_cus)
+int flow2d::median_stream_rows(int cus, size_t w, size_t h, size_t instances)
+{
+    return flow2d::stream_rows_per_strip(cus, flow2d::div_up(w, kStreamValid), h, instances, 64, 8);
+}
 
 template <int ADD>
 static int launch_median(flow2d_context* ctx, const float* input, const float* input_b, const float* addend,

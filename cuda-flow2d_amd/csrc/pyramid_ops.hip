@@ -241,9 +241,7 @@ void launch_gauss_stream(flow2d_context* ctx, float* dst, const float* src, size
                          size_t pitch_bytes, const GaussTaps& t)
 {
     const long strips = flow2d::div_up(width, 64 - 2 * R);
-    const long want_waves = (ctx->num_cus > 0 ? ctx->num_cus : 256) * 4 * 4;  // four waves per SIMD
-    long rows = 128;
-    while (rows > 16 && strips * (long)flow2d::div_up(height, rows) * (long)ctx->batch_count < want_waves) rows /= 2;
+    const long rows = flow2d::gauss_stream_rows(ctx->num_cus, width, height, R, ctx->batch_count);
     const dim3 grid(flow2d::div_up(strips, 4), flow2d::div_up(height, rows), flow2d::batch_z(ctx, 1));
     gauss_stream_kernel<R><<<grid, 256, 0, ctx->stream>>>(dst, src, (int)width, (int)height, (int)(pitch_bytes / 4),
                                                           (int)rows, t, flow2d::batch_arg(ctx, 1));
@@ -805,6 +803,12 @@ __global__ __launch_bounds__(256) void upsample_registration_kernel(const float*
 }
 
 }  // namespace
+
+// rows per strip of gauss_stream_kernel<radius> (launch_gauss_stream and flow2d_stream_rows_for_cus)
+int flow2d::gauss_stream_rows(int cus, size_t w, size_t h, int radius, size_t instances)
+{
+    return flow2d::stream_rows_per_strip(cus, flow2d::div_up(w, 64 - 2 * radius), h, instances, 128, 16);
+}
 
 namespace {
 // ---- the y passes of several levels in one launch (round 6) -----------------------------------------------------------

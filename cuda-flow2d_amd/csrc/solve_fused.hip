@@ -107,27 +107,29 @@ struct FusedPlan {
 // EDGE body / interior body: 1.2-1.26 in VALU instructions per row step (swept 1.0 ... 1.38 in rounds 3 and 5: 1.22)
 static const double kEdgeCost = 1.22;
 
-static FusedPlan fused_plan_search(const flow2d_context* ctx, size_t w, size_t h, size_t inner, long instances);
+static FusedPlan fused_plan_search(long cus, size_t w, size_t h, size_t inner, long instances);
 
 // The plan is a pure function of (w, h, inner, instances, CUs) and its search walks O(h) candidates: memoised per host thread
 // (a thread drives the lanes of one device; eager paths -- no graph, timing modes -- call this before every launch).
-FusedPlan fused_plan(const flow2d_context* ctx, size_t w, size_t h, size_t inner, long instances)
+// `num_cus` is the context's planning count (flow2d_context_set_planning_cus) on the launch path and whatever count
+// flow2d_fused_block_order_for_cus is asked about; none (<= 0) plans for 256.
+FusedPlan fused_plan(int num_cus, size_t w, size_t h, size_t inner, long instances)
 {
     thread_local std::map<std::array<long, 5>, FusedPlan> cache;
-    const std::array<long, 5> key{(long)w, (long)h, (long)inner, instances, (long)ctx->num_cus};
+    const long cus = num_cus > 0 ? num_cus : 256;
+    const std::array<long, 5> key{(long)w, (long)h, (long)inner, instances, cus};
     auto it = cache.find(key);
     if (it == cache.end()) {
         if (cache.size() > 4096) cache.clear();
-        it = cache.emplace(key, fused_plan_search(ctx, w, h, inner, instances)).first;
+        it = cache.emplace(key, fused_plan_search(cus, w, h, inner, instances)).first;
     }
     return it->second;
 }
 
-static FusedPlan fused_plan_search(const flow2d_context* ctx, size_t w, size_t h, size_t inner, long instances)
+static FusedPlan fused_plan_search(long cus, size_t w, size_t h, size_t inner, long instances)
 {
     const int valid = probe::kNoHalo ? 64 : 64 - 2 * ((int)inner + 1);
     const long blocks_x = (div_up(w, valid) + 3) / 4;
-    const long cus = ctx->num_cus > 0 ? ctx->num_cus : 256;
     const long cap = cus * 2;
     const int peel = 3 + 2 * (int)inner;  // run_strip's start-up steps
     double saved = 2 * 102.0 + 3 * 20.0;
@@ -237,9 +239,9 @@ int launch_fused_outer(const flow2d_context* ctx, const SolveLevel& l, ConstPair
     // up) is launched instance by instance: nothing is gained by one launch of several rounds, and the strips are then
     // planned -- and show in a kernel trace -- exactly as for a single pair.  Smaller levels share a launch (grid.z),
     // which lets the planner give them longer strips.
-    const bool split = ctx->batch_count > 1 && fused_plan(ctx, w, h, inner, 1).rows_interior >= 128;
+    const bool split = ctx->batch_count > 1 && fused_plan(ctx->num_cus, w, h, inner, 1).rows_interior >= 128;
     const unsigned instances_per_launch = split ? 1u : ctx->batch_count;
-    FusedPlan plan = fused_plan(ctx, w, h, inner, (long)instances_per_launch);
+    FusedPlan plan = fused_plan(ctx->num_cus, w, h, inner, (long)instances_per_launch);
     if (rows_per_strip > 0)
         plan = FusedPlan{rows_per_strip, rows_per_strip, (int)div_up(h, rows_per_strip), plan.blocks_x,
                          plan.blocks_x * (int)div_up(h, rows_per_strip)};
@@ -310,18 +312,26 @@ int launch_fused_outer(const flow2d_context* ctx, const SolveLevel& l, ConstPair
 
 // Diagnostics: the blocks a strip launch of this geometry would run, in launch order -- (block column, strip, first row, end row)
 // per launch block id, -1 for ids beyond the plan (the grid is a multiple of eight).  tests/test_gpu_fused.py checks that the order
-// is a permutation of the plan and the rows a partition of the image.
-extern "C" FLOW2D_API int flow2d_fused_block_order(flow2d_context* ctx, size_t width, size_t height, size_t inner, size_t instances,
-                                                   int* out, size_t capacity_blocks, size_t* grid_blocks)
+// is a permutation of the plan and the rows a partition of the image; tests/test_planning_cus_cpu.py does so for other CU counts.
+// Host logic only: the plan of `cus` CUs through the same fused_plan, fused_order_for and fused_block_of as a launch.
+static int fused_block_order_for(int cus, size_t width, size_t height, size_t inner, size_t instances, int* out, size_t capacity_blocks,
+                                 size_t* grid_blocks, int* plan_out, int* side_blocks)
 {
-    if (!ctx || !out || !grid_blocks || !flow2d::fused_supports(inner) || width == 0 || height == 0 || instances == 0)
+    if (cus < 0 || cus > FLOW2D_PLANNING_CUS_MAX || !flow2d::fused_supports(inner) || width == 0 || height == 0 || instances == 0 ||
+        width >= (1u << 30) || height >= (1u << 30) || instances > FLOW2D_BATCH_MAX)
         return FLOW2D_ERR_INVALID_ARGUMENT;
-    const flow2d::FusedPlan plan = flow2d::fused_plan(ctx, width, height, inner, (long)instances);
+    const flow2d::FusedPlan plan = flow2d::fused_plan(cus, width, height, inner, (long)instances);
     flow2d::FusedArgs a{};
     a.w = (int)width, a.h = (int)height;
     a.rows_interior = plan.rows_interior, a.rows_edge = plan.rows_edge, a.strips_interior = plan.strips_interior, a.blocks_x = plan.blocks_x;
     a.blocks = plan.blocks;
     flow2d::fused_order_for(plan, a);
+    if (plan_out)
+        plan_out[0] = plan.rows_interior, plan_out[1] = plan.rows_edge, plan_out[2] = plan.strips_interior, plan_out[3] = plan.blocks_x,
+        plan_out[4] = plan.blocks;
+    if (side_blocks) *side_blocks = a.side_blocks;
+    if (!out && !grid_blocks) return FLOW2D_OK;  // the plan alone
+    if (!out || !grid_blocks) return FLOW2D_ERR_INVALID_ARGUMENT;
     const size_t grid = (size_t)a.blocks_per_xcd * 8;
     *grid_blocks = grid;
     if (grid > capacity_blocks) return FLOW2D_ERR_INVALID_ARGUMENT;
@@ -331,6 +341,27 @@ extern "C" FLOW2D_API int flow2d_fused_block_order(flow2d_context* ctx, size_t w
         out[4 * id + 0] = bx, out[4 * id + 1] = by, out[4 * id + 2] = y0, out[4 * id + 3] = y1;
     }
     return FLOW2D_OK;
+}
+
+extern "C" FLOW2D_API int flow2d_fused_block_order(flow2d_context* ctx, size_t width, size_t height, size_t inner, size_t instances,
+                                                   int* out, size_t capacity_blocks, size_t* grid_blocks)
+{
+    if (!ctx || !out || !grid_blocks) return FLOW2D_ERR_INVALID_ARGUMENT;
+    return fused_block_order_for(ctx->num_cus, width, height, inner, instances, out, capacity_blocks, grid_blocks, nullptr, nullptr);
+}
+
+extern "C" FLOW2D_API int flow2d_fused_block_order_for_cus(int cus, size_t width, size_t height, size_t inner, size_t instances,
+                                                           int* out, size_t capacity_blocks, size_t* grid_blocks)
+{
+    if (cus < 1 || !out || !grid_blocks) return FLOW2D_ERR_INVALID_ARGUMENT;
+    return fused_block_order_for(cus, width, height, inner, instances, out, capacity_blocks, grid_blocks, nullptr, nullptr);
+}
+
+extern "C" FLOW2D_API int flow2d_fused_plan_for_cus(int cus, size_t width, size_t height, size_t inner, size_t instances, int* plan,
+                                                    int* side_blocks)
+{
+    if (cus < 1 || !plan) return FLOW2D_ERR_INVALID_ARGUMENT;
+    return fused_block_order_for(cus, width, height, inner, instances, nullptr, 0, nullptr, plan, side_blocks);
 }
 
 extern "C" FLOW2D_API unsigned long long flow2d_fused_packed_launches(void)

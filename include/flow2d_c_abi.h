@@ -51,7 +51,9 @@ extern "C" {
  * flow2d_node_strain_workspace_bytes (strain on the node grid from least-squares strain windows) and
  * flow2d_subset_refine_masked_2d (the refinement on a region of interest) and flow2d_bspline_prefilter_2d /
  * flow2d_subset_refine_spline_2d / flow2d_subset_refine2_spline_2d (the refinement with a cubic B-spline interpolation of the
- * deformed frame) were added under 1. */
+ * deformed frame) and flow2d_context_set_planning_cus / flow2d_context_planning_cus (the CU count the launch planners plan
+ * for) with the host-only diagnostics flow2d_fused_block_order_for_cus / flow2d_fused_plan_for_cus /
+ * flow2d_stream_rows_for_cus (which plan a CU count gives) were added under 1. */
 #define FLOW2D_ABI_VERSION 1
 
 typedef enum flow2d_status {
@@ -125,6 +127,18 @@ FLOW2D_API int flow2d_context_set_batch(flow2d_context* ctx, size_t count, size_
  * device's wave slots empty then take the build of the strip kernel with packed arithmetic (a wave alone on its SIMD has nothing
  * to share issue turns with; the same IEEE operations, the same bits).  Default 0. */
 FLOW2D_API int flow2d_context_set_lone(flow2d_context* ctx, int lone);
+/* A hint, not a mode (no reference counterpart; added to ABI version 1 without changing any existing entry): the number of
+ * compute units this context's launch planners plan for -- the strip plan of the fused solver (strip heights, launch order,
+ * whether a lock-step group shares a launch, and the size up to which a lone context takes the packed build) and the rows per
+ * strip of the streaming Gaussian and median kernels.  Every value gives the same bytes; only the launch geometry changes.  A
+ * context starts with its device's own count; cus = 0 goes back to it, 1 ... FLOW2D_PLANNING_CUS_MAX is taken as given (it need
+ * not be a count any device has: a test runs the plans of a small or partitioned device on whatever device it finds).  A null
+ * context or any other value is FLOW2D_ERR_INVALID_ARGUMENT and leaves the count as it was.  A plan is fixed when a launch is
+ * queued, so a recorded graph (flow2d_capture_begin) keeps the plans it was captured with whatever is set when it is replayed.
+ * flow2d_context_planning_cus reads the count the planners use now.  Neither call touches the device. */
+#define FLOW2D_PLANNING_CUS_MAX 4096
+FLOW2D_API int flow2d_context_set_planning_cus(flow2d_context* ctx, int cus);
+FLOW2D_API int flow2d_context_planning_cus(const flow2d_context* ctx, int* cus);
 /* cuMemGetInfo, optical_flow_2d.cpp:91 */
 FLOW2D_API int flow2d_mem_info(flow2d_context* ctx, size_t* free_bytes, size_t* total_bytes);
 FLOW2D_API int flow2d_device_name(flow2d_context* ctx, char* buf, size_t buf_len);
@@ -1839,6 +1853,27 @@ FLOW2D_API int flow2d_clock_probe_read(flow2d_context* ctx, double* ghz_per_xcd)
  * (*grid_blocks is set).  A test hook: the order must be a permutation of the plan, the strips a partition of the level. */
 FLOW2D_API int flow2d_fused_block_order(flow2d_context* ctx, size_t width, size_t height, size_t inner, size_t instances,
                                         int* out, size_t capacity_blocks, size_t* grid_blocks);
+/* The same for a device of `cus` compute units (1 ... FLOW2D_PLANNING_CUS_MAX), without a context or a device: what
+ * flow2d_fused_block_order answers on a context after flow2d_context_set_planning_cus(ctx, cus) (it reflects the planning
+ * count).  flow2d_fused_plan_for_cus gives the plan itself: plan[0 .. 4] = rows of an interior strip, rows of a strip on the
+ * first or last row of strips (equal: uniform strips; different: a border-aware plan, whose first and last block column are cut
+ * into strips of the second height throughout), strips per interior block column, block columns, blocks of the launch (per
+ * instance); *side_blocks (may be null) = the blocks of the first and last block column when the launch order deals them over
+ * the eight runs, 0 when it leaves them at the end of the order or the plan is uniform.  `instances` is what shares the launch:
+ * a lock-step group whose single-pair plan (instances = 1) has interior strips of 128 rows and more is launched instance by
+ * instance with that plan.  Added to ABI version 1 without changing any existing entry; test hooks like the entry above. */
+FLOW2D_API int flow2d_fused_block_order_for_cus(int cus, size_t width, size_t height, size_t inner, size_t instances, int* out,
+                                                size_t capacity_blocks, size_t* grid_blocks);
+FLOW2D_API int flow2d_fused_plan_for_cus(int cus, size_t width, size_t height, size_t inner, size_t instances, int* plan,
+                                         int* side_blocks);
+/* Rows per strip of a streaming launch on a device of `cus` compute units: kind FLOW2D_STREAM_GAUSSIAN -- flow2d_gaussian_blur
+ * with a radius of 1 ... 6 (larger radii do not stream), 16 ... 128 rows -- or FLOW2D_STREAM_MEDIAN -- flow2d_median_2d and its
+ * pair and add forms with radius 1, 2, 3 for the windows 3, 5, 7, 8 ... 64 rows --, for `instances` lock-step instances.  The
+ * launchers take their strips from the same function.  -1 for arguments outside those ranges.  No context, no device; a test
+ * hook (added to ABI version 1 without changing any existing entry). */
+#define FLOW2D_STREAM_GAUSSIAN 0
+#define FLOW2D_STREAM_MEDIAN 1
+FLOW2D_API int flow2d_stream_rows_for_cus(int cus, int kind, size_t width, size_t height, int radius, size_t instances);
 /* Strip launches queued by this process so far that the packed build of the strip kernel served: the launches of a lone context
  * (flow2d_context_set_lone) with at most one workgroup per CU whose data term, sweep count and kind the packed build holds -- a
  * launch it does not hold (the LogDerivatives term, the continued sweeps of an outer iteration) goes to the pipeline's build and

@@ -42,7 +42,8 @@ Which test holds which entry of include/flow2d_c_abi.h (every FLOW2D_API functio
 
 Not reached here: the branch of the fused strip launcher that launches a group instance by instance once a single pair's strips
 reach 128 rows.  The planner only gives such strips to levels of about 4096 x 4096 and more, which is beyond the small planes
-of this file; the lock-step pipeline tests of tests/test_gpu_flow.py are what runs it.
+of this file; the lock-step pipeline tests of tests/test_gpu_flow.py run it at full size, and
+tests/test_gpu_planning_cus.py::test_groups at 417 x 900 under the plan of an 8-CU device, per instance and with padded strides.
 """
 import importlib
 
