@@ -257,6 +257,11 @@ class CorrelationPassRecord(C.Structure):
     def summary(self):
         return {name: getattr(self, name) for name, _ in self._fields_[:6]}
 
+    @property
+    def masked(self):
+        """The masked nodes: what flow2d_correlate_masked_2d writes into the word the other entries leave 0.  Read-only."""
+        return self.reserved[0]
+
 
 class ValidationRecord(C.Structure):
     """flow2d_validation_record of include/flow2d_c_abi.h: the six counts flow2d_validate_nodes_2d writes per instance."""
@@ -265,6 +270,12 @@ class ValidationRecord(C.Structure):
 
     def summary(self):
         return {name: getattr(self, name) for name, _ in self._fields_[:6]}
+
+    @property
+    def masked(self):
+        """The off-specimen nodes (flag VALIDATE_FLAG_MASKED): what flow2d_validate_nodes_masked_2d writes into the word the other
+        entries leave 0.  Read-only."""
+        return self.reserved[0]
 
 
 CORRELATION_PASS_RECORD_BYTES = VALIDATION_RECORD_BYTES = 64  # FLOW2D_*_RECORD_BYTES, checked by static_asserts in the header
@@ -359,6 +370,14 @@ class CorrelationPassReport(C.Structure):
     def summary(self):
         return {"nw": self.nw, "nh": self.nh, "correlation": self.correlation.summary(), "validation": self.validation.summary()}
 VALIDATE_FLAG, VALIDATE_REPLACE = 0, 1  # FLOW2D_VALIDATE_*
+VALIDATE_FLAG_MASKED = 3  # FLOW2D_VALIDATE_FLAG_MASKED: the flag flow2d_validate_nodes_masked_2d gives a node off the specimen
+
+
+def correlation_min_pixels(radius):
+    """The default min_pixels of a masked window search (OpticalFlow2D::ValidationOptions::min_pixels = 0): a quarter of the
+    window, rounded up, and six at least."""
+    side = 2 * int(radius) + 1
+    return max(6, (side * side + 3) // 4)
 
 
 class PriorReport(C.Structure):
@@ -583,6 +602,9 @@ def hip_lib():
         if hasattr(L, "flow2d_correlate_offset_2d"):
             L.flow2d_correlate_offset_2d.argtypes = [vp, vp, vp, vp, vp, sz, sz, sz, f, f, i, i, i, f, vp, vp, vp, sz, vp]
             L.flow2d_validate_nodes_2d.argtypes = [vp, vp, vp, sz, sz, sz, f, f, i, i, vp, vp, vp, vp]
+        if hasattr(L, "flow2d_correlate_masked_2d"):  # (absent from libraries of earlier rounds loaded for an A/B)
+            L.flow2d_correlate_masked_2d.argtypes = [vp, vp, vp, vp, vp, sz, sz, sz, f, f, i, i, i, f, vp, i, vp, vp, vp, sz, vp]
+            L.flow2d_validate_nodes_masked_2d.argtypes = [vp, vp, vp, sz, sz, sz, f, f, i, i, vp, sz, sz, sz, i, i, vp, vp, vp, vp]
         if hasattr(L, "flow2d_subset_refine_2d"):  # (absent from libraries of earlier rounds loaded for an A/B)
             L.flow2d_subset_refine_2d.argtypes = [vp, vp, vp, sz, sz, sz, vp, vp, sz, sz, sz, i, i, i, i, f, f, f] + [vp] * 9
         if hasattr(L, "flow2d_subset_refine2_2d"):  # (absent from libraries of earlier rounds loaded for an A/B)
@@ -1335,6 +1357,67 @@ class Context:
                 q.free()
                 self._planes.remove(q)
 
+    def correlate_masked(self, f0, f1, w, h, lo, scale, radius, search, spacing, mask, min_pixels=None, min_score=-1.0, predictor=None,
+                         node_u=None, node_v=None, node_score=None, record=True, instances=1):
+        """correlate_offset on a region of interest (flow2d_correlate_masked_2d): `mask` is a Plane of the frames' size in frame
+        0's coordinates whose pixels with !(m < 0.5) are not the specimen -- or None, which forwards to correlate_offset.  The sums
+        of a window run over its pixels that are not excluded; a node whose centre is excluded or whose window keeps fewer than
+        min_pixels (None: correlation_min_pixels(radius)) is masked: NaN, score 0, counted in the record's `masked`.
+        Returns (u, v, score or None, CorrelationPassRecord or None)."""
+        own_planes = node_u is None and node_v is None
+        if not own_planes and (node_u is None or node_v is None):
+            raise ValueError("correlate_masked takes both node planes or neither")
+        own_record = record is True
+        if own_record and instances != 1:
+            raise ValueError("a lock-step batch takes the caller's records")
+        pu, pv = predictor if predictor is not None else (None, None)
+        nw, nh = correlation_grid(w, h, radius, spacing)
+        held = [self.plane(nw, nh) for _ in range(3)] if own_planes else [node_u, node_v, node_score]
+        rec = self.pass_records(instances) if own_record else (record or None)
+        try:
+            _check(hip_lib().flow2d_correlate_masked_2d(self.handle, f0.ptr, f1.ptr, pu.ptr if pu is not None else None,
+                                                        pv.ptr if pv is not None else None, w, h, f0.pitch, float(lo), float(scale),
+                                                        int(radius), int(search), int(spacing), float(min_score),
+                                                        mask.ptr if mask is not None else None,
+                                                        correlation_min_pixels(radius) if min_pixels is None else int(min_pixels),
+                                                        held[0].ptr, held[1].ptr, held[2].ptr if held[2] is not None else None,
+                                                        held[0].pitch, rec.ptr if rec is not None else None),
+                   "flow2d_correlate_masked_2d")
+            u, v, score = (q.download(nw, nh) for q in held) if own_planes else held
+            return u, v, score, (self.read_correlation_pass_record(rec, 1)[0] if own_record else None)
+        finally:
+            for q in (held if own_planes else []) + ([rec] if own_record else []):
+                q.free()
+                self._planes.remove(q)
+
+    def validate_nodes_masked(self, node_u, node_v, nw, nh, mask, w, h, radius, spacing, threshold=2.0, epsilon=0.1, min_neighbours=3,
+                              mode=VALIDATE_REPLACE, out_u=None, out_v=None, out_flag=None, record=True, instances=1):
+        """validate_nodes on a region of interest (flow2d_validate_nodes_masked_2d): `mask` is the w x h Plane of correlate_masked
+        and (radius, spacing) the grid the nw x nh nodes lie on.  A node whose centre pixel is excluded is off the specimen: never
+        a neighbour, NaN with flag VALIDATE_FLAG_MASKED, counted in the record's `masked` only.  mask None forwards to
+        validate_nodes.  Returns (u, v, flag or None, ValidationRecord or None)."""
+        own_planes = out_u is None and out_v is None
+        if not own_planes and (out_u is None or out_v is None):
+            raise ValueError("validate_nodes_masked takes both output planes or neither")
+        own_record = record is True
+        if own_record and instances != 1:
+            raise ValueError("a lock-step batch takes the caller's records")
+        held = [self.plane(node_u.pitch // 4, nh) for _ in range(3)] if own_planes else [out_u, out_v, out_flag]
+        rec = self.pass_records(instances) if own_record else (record or None)
+        try:
+            _check(hip_lib().flow2d_validate_nodes_masked_2d(self.handle, node_u.ptr, node_v.ptr, nw, nh, node_u.pitch, float(threshold),
+                                                             float(epsilon), int(min_neighbours), int(mode),
+                                                             mask.ptr if mask is not None else None, w, h,
+                                                             mask.pitch if mask is not None else 0, int(radius), int(spacing),
+                                                             held[0].ptr, held[1].ptr, held[2].ptr if held[2] is not None else None,
+                                                             rec.ptr if rec is not None else None), "flow2d_validate_nodes_masked_2d")
+            u, v, flag = (q.download(nw, nh) for q in held) if own_planes else held
+            return u, v, flag, (self.read_validation_record(rec, 1)[0] if own_record else None)
+        finally:
+            for q in (held if own_planes else []) + ([rec] if own_record else []):
+                q.free()
+                self._planes.remove(q)
+
     def subset_records(self, instances=1):
         """A Plane for `instances` flow2d_subset_record records (device memory)."""
         return self._record_plane(SUBSET_RECORD_BYTES, instances)
@@ -1943,6 +2026,14 @@ def host_lib():
             L.flow2d_host_subset_min_pixels.argtypes = [i]
             L.flow2d_host_subset_interpolation_ok.argtypes = [i]
             L.flow2d_host_set_subset_interpolation.argtypes = [vp, i]
+        if hasattr(L, "flow2d_host_correlate_multipass_masked_device"):  # (absent from libraries of earlier rounds loaded for an A/B)
+            ip, rp = C.POINTER(C.c_int), C.POINTER(CorrelationPassReport)
+            L.flow2d_host_correlation_passes_masked_ok.argtypes = [sz, sz, f, f, ip, i, f, f, f, i, i]
+            L.flow2d_host_correlate_multipass_masked_device.argtypes = [vp, vp, vp, f, f, ip, i, f, f, f, i, i, i, vp, i, vp, vp, vp, vp, vp, rp,
+                                                                        vp, vp]
+            L.flow2d_host_correlate_multipass_masked.argtypes = [vp, fp, fp, ip, i, f, f, f, i, i, i, fp, i, fp, fp, fp, fp, fp, rp, fp, fp, fp]
+            L.flow2d_host_set_subset_mask_search.argtypes = [vp, i]
+            L.flow2d_host_subset_mask_search_ok.argtypes = [C.POINTER(SubsetOptions)]
             L.flow2d_host_sequence_options_ok.argtypes = sequence
             L.flow2d_host_refine_nodes_device.argtypes = [vp, vp, vp, vp, vp, i, i, so, pvp, sr]
             L.flow2d_host_refine_nodes_from_device.argtypes = [vp, vp, vp, pvp, i, i, so, pvp, sr]
@@ -2452,18 +2543,29 @@ class OpticalFlow:
         return (C.c_int * max(len(flat), 1))(*flat), len(passes)
 
     @staticmethod
-    def correlation_passes_ok(width, height, lo, scale, passes, min_score=-1.0, threshold=2.0, epsilon=0.1, min_neighbours=3):
-        """OpticalFlow2D::CorrelationPassesOk: whether correlate_multipass* accepts the schedule.  Needs no device."""
+    def correlation_passes_ok(width, height, lo, scale, passes, min_score=-1.0, threshold=2.0, epsilon=0.1, min_neighbours=3, min_pixels=0):
+        """OpticalFlow2D::CorrelationPassesOk: whether correlate_multipass* accepts the schedule -- and, for a masked search, the
+        min_pixels, which must fit every pass's window (0: the default per pass).  Needs no device."""
         arr, n = OpticalFlow._passes(passes)
+        if min_pixels:
+            return bool(host_lib().flow2d_host_correlation_passes_masked_ok(width, height, float(lo), float(scale), arr, n, float(min_score),
+                                                                            float(threshold), float(epsilon), int(min_neighbours),
+                                                                            int(min_pixels)))
         return bool(host_lib().flow2d_host_correlation_passes_ok(width, height, float(lo), float(scale), arr, n, float(min_score),
                                                                  float(threshold), float(epsilon), int(min_neighbours)))
 
     def correlate_multipass(self, frame_0, frame_1, passes, min_score=-1.0, threshold=2.0, epsilon=0.1, min_neighbours=3, replace=True,
-                            validate_last=True, predictor=None, flow=False):
+                            validate_last=True, predictor=None, flow=False, mask=None, min_pixels=0):
         """OpticalFlow2D::CorrelateMultiPass: the host pair through `passes` -- 1 .. CORRELATION_MAX_PASSES triples (radius, range,
         spacing), coarse to fine --, every pass searching around the validated, expanded field of the one before (the first around
         `predictor`, a (u, v) pair of images, or around nothing).  Returns (node_u, node_v, node_score, [CorrelationPassReport],
-        (lo, scale)) on the last pass's grid; with flow, also the (u, v) of the field expanded to the frame's grid."""
+        (lo, scale)) on the last pass's grid; with flow, also the (u, v) of the field expanded to the frame's grid.
+        mask (an image of the frames' size in frame 0's coordinates, uploaded once; values of 0.5 and more, and NaN, mean "not the
+        specimen") / min_pixels (0: correlation_min_pixels of each pass's radius): the region of interest -- every pass then runs
+        flow2d_correlate_masked_2d and flow2d_validate_nodes_masked_2d, and the reports' records count the masked nodes in
+        `masked`.  Without a mask the method is the call it always was."""
+        if mask is None and min_pixels:
+            raise ValueError("min_pixels goes with a mask")
         f0, f1 = self._pair(frame_0, frame_1)
         arr, n = self._passes(passes)
         if not 1 <= n <= CORRELATION_MAX_PASSES:
@@ -2474,10 +2576,18 @@ class OpticalFlow:
         pred = [np.ascontiguousarray(q, np.float32) for q in predictor] if predictor is not None else [None, None]
         reports = (CorrelationPassReport * n)()
         lo_scale = (C.c_float * 2)()
-        rc = host_lib().flow2d_host_correlate_multipass(self.handle, _fptr(f0), _fptr(f1), arr, n, float(min_score), float(threshold),
-                                                        float(epsilon), int(min_neighbours), int(bool(replace)), int(bool(validate_last)),
-                                                        _opt_fptr(pred[0]), _opt_fptr(pred[1]), _fptr(nodes[0]), _fptr(nodes[1]),
-                                                        _fptr(nodes[2]), reports, _opt_fptr(uv[0]), _opt_fptr(uv[1]), lo_scale)
+        if mask is not None:
+            region = self._mask_image(mask)
+            rc = host_lib().flow2d_host_correlate_multipass_masked(self.handle, _fptr(f0), _fptr(f1), arr, n, float(min_score),
+                                                                   float(threshold), float(epsilon), int(min_neighbours), int(bool(replace)),
+                                                                   int(bool(validate_last)), _fptr(region), int(min_pixels),
+                                                                   _opt_fptr(pred[0]), _opt_fptr(pred[1]), _fptr(nodes[0]), _fptr(nodes[1]),
+                                                                   _fptr(nodes[2]), reports, _opt_fptr(uv[0]), _opt_fptr(uv[1]), lo_scale)
+        else:
+            rc = host_lib().flow2d_host_correlate_multipass(self.handle, _fptr(f0), _fptr(f1), arr, n, float(min_score), float(threshold),
+                                                            float(epsilon), int(min_neighbours), int(bool(replace)), int(bool(validate_last)),
+                                                            _opt_fptr(pred[0]), _opt_fptr(pred[1]), _fptr(nodes[0]), _fptr(nodes[1]),
+                                                            _fptr(nodes[2]), reports, _opt_fptr(uv[0]), _opt_fptr(uv[1]), lo_scale)
         if rc:
             raise Flow2DError(rc, "OpticalFlow2D::CorrelateMultiPass")
         out = (nodes[0], nodes[1], nodes[2], list(reports), (lo_scale[0], lo_scale[1]))
@@ -2485,17 +2595,27 @@ class OpticalFlow:
 
     def correlate_multipass_device(self, dev_frame_0, dev_frame_1, lo, scale, passes, min_score=-1.0, threshold=2.0, epsilon=0.1,
                                    min_neighbours=3, replace=True, validate_last=True, dev_predictor=None, dev_nodes=None, dev_score=None,
-                                   dev_flow=None):
+                                   dev_flow=None, mask=None, min_pixels=0):
         """OpticalFlow2D::CorrelateMultiPassDevice: device frames in.  dev_predictor (a (u, v) pair of planes of the container's
         size, optional): the first pass's predictor; dev_nodes, dev_score, dev_flow as for correlate_device, from the last pass.
-        Returns one CorrelationPassReport per pass; synchronises."""
+        Returns one CorrelationPassReport per pass; synchronises.  mask (a device plane of the container's size) / min_pixels: the
+        region of interest, as for correlate_multipass."""
         arr, n = self._passes(passes)
         reports = (CorrelationPassReport * max(n, 1))()
         pr, nd, fl = dev_predictor or (None, None), dev_nodes or (None, None), dev_flow or (None, None)
-        rc = host_lib().flow2d_host_correlate_multipass_device(self.handle, dev_frame_0, dev_frame_1, float(lo), float(scale), arr, n,
-                                                               float(min_score), float(threshold), float(epsilon), int(min_neighbours),
-                                                               int(bool(replace)), int(bool(validate_last)), pr[0], pr[1], nd[0], nd[1],
-                                                               dev_score, reports, fl[0], fl[1])
+        if mask is None and min_pixels:
+            raise ValueError("min_pixels goes with a mask")
+        if mask is not None:
+            rc = host_lib().flow2d_host_correlate_multipass_masked_device(self.handle, dev_frame_0, dev_frame_1, float(lo), float(scale), arr,
+                                                                          n, float(min_score), float(threshold), float(epsilon),
+                                                                          int(min_neighbours), int(bool(replace)), int(bool(validate_last)),
+                                                                          mask, int(min_pixels), pr[0], pr[1], nd[0], nd[1], dev_score,
+                                                                          reports, fl[0], fl[1])
+        else:
+            rc = host_lib().flow2d_host_correlate_multipass_device(self.handle, dev_frame_0, dev_frame_1, float(lo), float(scale), arr, n,
+                                                                   float(min_score), float(threshold), float(epsilon), int(min_neighbours),
+                                                                   int(bool(replace)), int(bool(validate_last)), pr[0], pr[1], nd[0], nd[1],
+                                                                   dev_score, reports, fl[0], fl[1])
         if rc:
             raise Flow2DError(rc, "OpticalFlow2D::CorrelateMultiPassDevice")
         return list(reports)[:n]
@@ -2536,13 +2656,19 @@ class OpticalFlow:
         return image
 
     def _subset_options(self, where, radius, iterations, epsilon, max_shift, max_gradient, order, max_curvature, mask, min_pixels,
-                        image=False, interpolation="catmull-rom"):
+                        image=False, interpolation="catmull-rom", mask_search=False):
         """The SubsetOptions record of a call that refines, by the rules of _takes_mask.  image: the mask is an image and not a
         device plane; the record then holds the float32 array it points into, which lives as long as the record.
         interpolation -- "catmull-rom" or "bspline", OpticalFlow2D::SubsetOptions::interpolation: how frame 1 is sampled.  With
         "bspline" the call prefilters its frame 1 (a sequence: every step its frame k) into a plane of the object's own and runs the
         spline entry of its order; mask and order go with both.  It travels beside the record (which keeps its 40 bytes): every call
-        sets it in the object, so the default restores Catmull-Rom."""
+        sets it in the object, so the default restores Catmull-Rom.
+        mask_search -- OpticalFlow2D::SubsetOptions::mask_search, on the methods that run the passes of a pair (correlate_subset*):
+        with a mask, the passes in front of the refinement run the masked search and the masked validation with it
+        (flow2d_correlate_masked_2d, flow2d_validate_nodes_masked_2d), so that an edge node starts from the specimen's motion.
+        False is the call it always was; True without a mask is refused.  It travels beside the record like the interpolation."""
+        if mask_search and mask is None:
+            raise Flow2DError(1, where, "mask_search needs a mask")
         if interpolation not in SUBSET_INTERPOLATIONS:
             raise ValueError("interpolation is one of %s" % ", ".join(sorted(SUBSET_INTERPOLATIONS)))
         held = None
@@ -2554,6 +2680,8 @@ class OpticalFlow:
         options.held = held
         if host_lib().flow2d_host_set_subset_interpolation(self.handle, SUBSET_INTERPOLATIONS[interpolation]):
             raise Flow2DError(1, where, "the subset interpolation was refused")
+        if host_lib().flow2d_host_set_subset_mask_search(self.handle, int(bool(mask_search))):
+            raise Flow2DError(1, where, "the subset mask search was refused")
         return options
 
     @staticmethod
@@ -2598,13 +2726,13 @@ class OpticalFlow:
 
     def correlate_subset(self, frame_0, frame_1, passes, radius, iterations=20, epsilon=1e-3, max_shift=2.0, max_gradient=0.5,
                          min_score=-1.0, threshold=2.0, validate_epsilon=0.1, min_neighbours=3, predictor=None, flow=False, order=1,
-                         max_curvature=0.05, mask=None, min_pixels=0, interpolation="catmull-rom"):
+                         max_curvature=0.05, mask=None, min_pixels=0, interpolation="catmull-rom", mask_search=False):
         """OpticalFlow2D::CorrelateSubset: the host pair through `passes` as in correlate_multipass -- the last pass validated with
         replacement, so that every node has a start --, then every node of the last pass's grid refined by subsets of `radius` on
         the unquantised frames.  Returns (nodes, [CorrelationPassReport], SubsetRecord, (lo, scale)), nodes a dict of [nh, nw]
         arrays by the names of SUBSET_PLANES; with flow, also the (u, v) of the refined field expanded to the frame's grid.
         order=2: the second-order refinement (radius from 2, a curvature beyond max_curvature strays), nodes by the names of
-        SUBSET2_PLANES; order=1 is the call it always was.  mask (an image, uploaded once) / min_pixels: see _takes_mask."""
+        SUBSET2_PLANES; order=1 is the call it always was.  mask (an image, uploaded once) / min_pixels: see _takes_mask; mask_search: see _subset_options."""
         f0, f1 = self._pair(frame_0, frame_1)
         arr, n = self._passes(passes)
         if not 1 <= n <= CORRELATION_MAX_PASSES:
@@ -2616,7 +2744,7 @@ class OpticalFlow:
         pred = [np.ascontiguousarray(q, np.float32) for q in predictor] if predictor is not None else [None, None]
         reports, rec, lo_scale = (CorrelationPassReport * n)(), SubsetRecord(), (C.c_float * 2)()
         options = self._subset_options("OpticalFlow2D::CorrelateSubset", radius, iterations, epsilon, max_shift, max_gradient, order,
-                                       max_curvature, mask, min_pixels, image=True, interpolation=interpolation)
+                                       max_curvature, mask, min_pixels, image=True, interpolation=interpolation, mask_search=mask_search)
         rc = host_lib().flow2d_host_correlate_subset(self.handle, _fptr(f0), _fptr(f1), arr, n, float(min_score), float(threshold),
                                                      float(validate_epsilon), int(min_neighbours), C.byref(options), _opt_fptr(pred[0]),
                                                      _opt_fptr(pred[1]), self._node_arrays(nodes, len(names)), reports, C.byref(rec),
@@ -2629,15 +2757,15 @@ class OpticalFlow:
     def correlate_subset_device(self, dev_frame_0, dev_frame_1, lo, scale, passes, radius, iterations=20, epsilon=1e-3, max_shift=2.0,
                                 max_gradient=0.5, min_score=-1.0, threshold=2.0, validate_epsilon=0.1, min_neighbours=3, dev_predictor=None,
                                 dev_out=None, dev_flow=None, order=1, max_curvature=0.05, mask=None, min_pixels=0,
-                                interpolation="catmull-rom"):
+                                interpolation="catmull-rom", mask_search=False):
         """OpticalFlow2D::CorrelateSubsetDevice: device frames in; dev_predictor and dev_flow as for correlate_multipass_device (the
         flow is the refined field's), dev_out, order and max_curvature as for refine_nodes_device.  Returns
-        ([CorrelationPassReport], SubsetRecord); synchronises once.  mask (a device plane) / min_pixels: see _takes_mask."""
+        ([CorrelationPassReport], SubsetRecord); synchronises once.  mask (a device plane) / min_pixels: see _takes_mask; mask_search: see _subset_options."""
         arr, n = self._passes(passes)
         reports, rec = (CorrelationPassReport * max(n, 1))(), SubsetRecord()
         pr, fl = dev_predictor or (None, None), dev_flow or (None, None)
         options = self._subset_options("OpticalFlow2D::CorrelateSubsetDevice", radius, iterations, epsilon, max_shift, max_gradient, order,
-                                       max_curvature, mask, min_pixels, interpolation=interpolation)
+                                       max_curvature, mask, min_pixels, interpolation=interpolation, mask_search=mask_search)
         rc = host_lib().flow2d_host_correlate_subset_device(self.handle, dev_frame_0, dev_frame_1, float(lo), float(scale), arr, n,
                                                             float(min_score), float(threshold), float(validate_epsilon), int(min_neighbours),
                                                             C.byref(options), pr[0], pr[1], self._subset_planes(dev_out, order), reports,
@@ -2674,7 +2802,7 @@ class OpticalFlow:
     def correlate_subset_sequence(self, frames, passes, radius, iterations=20, epsilon=1e-3, max_shift=2.0, max_gradient=0.5, min_score=-1.0,
                                   threshold=2.0, validate_epsilon=0.1, min_neighbours=3, fill=2, min_state=1, predict_neighbours=1,
                                   sequence_max_shift=4.0, flow=False, order=1, max_curvature=0.05, mask=None, min_pixels=0,
-                                  interpolation="catmull-rom", reference_every=0):
+                                  interpolation="catmull-rom", reference_every=0, mask_search=False):
         """OpticalFlow2D::CorrelateSubsetSequence: digital image correlation over a loading sequence.  (order=2: every step refines
         at second order, the steps after the first from the prediction's first-order planes with zero curvatures; the nodes then
         go by the names of SUBSET2_PLANES.)  frames[0] is the reference and
@@ -2684,7 +2812,7 @@ class OpticalFlow:
         with sequence_max_shift in place of max_shift -- and no window search runs.  Returns ([nodes per step], [CorrelationPassReport]
         of step 1, [SequenceStepReport], (lo, scale)), nodes a dict of [nh, nw] arrays by the names of SUBSET_PLANES; with flow,
         also [(u, v) per step], the refined field expanded to the frame's grid.  mask (an image, uploaded once and used by every
-        step) / min_pixels: see _takes_mask.  reference_every: see _moving_reference; the composition's records are left in
+        step) / min_pixels: see _takes_mask; mask_search: see _subset_options.  reference_every: see _moving_reference; the composition's records are left in
         self.compose_records."""
         images = [np.ascontiguousarray(q, np.float32) for q in frames]
         if len(images) < 2 or any(q.shape != (self.height, self.width) for q in images):
@@ -2701,7 +2829,7 @@ class OpticalFlow:
         fpp = C.POINTER(C.c_float)
         reports, reps, lo_scale = (CorrelationPassReport * n)(), (SequenceStepReport * steps)(), (C.c_float * 2)()
         options = self._subset_options("OpticalFlow2D::CorrelateSubsetSequence", radius, iterations, epsilon, max_shift, max_gradient, order,
-                                       max_curvature, mask, min_pixels, image=True, interpolation=interpolation)
+                                       max_curvature, mask, min_pixels, image=True, interpolation=interpolation, mask_search=mask_search)
         self._moving_reference("OpticalFlow2D::CorrelateSubsetSequence", reference_every)
         rc = host_lib().flow2d_host_correlate_subset_sequence(self.handle, (fpp * len(images))(*[_fptr(q) for q in images]), len(images), arr, n,
                                                               float(min_score), float(threshold), float(validate_epsilon), int(min_neighbours),
@@ -2718,13 +2846,13 @@ class OpticalFlow:
     def correlate_subset_sequence_device(self, dev_frames, lo, scale, passes, radius, dev_out, iterations=20, epsilon=1e-3, max_shift=2.0,
                                          max_gradient=0.5, min_score=-1.0, threshold=2.0, validate_epsilon=0.1, min_neighbours=3, fill=2,
                                          min_state=1, predict_neighbours=1, sequence_max_shift=4.0, dev_flows=None, order=1,
-                                         max_curvature=0.05, mask=None, min_pixels=0, interpolation="catmull-rom", reference_every=0):
+                                         max_curvature=0.05, mask=None, min_pixels=0, interpolation="catmull-rom", reference_every=0, mask_search=False):
         """OpticalFlow2D::CorrelateSubsetSequenceDevice: device frames in (the first is the reference); dev_out: per step a dict of
         device planes by the names of SUBSET_PLANES, of which only the score may be missing; dev_flows: per step a (u, v) pair or
         None.  Returns ([CorrelationPassReport] of step 1, [SequenceStepReport]); synchronises once.  order=2: every step refines
         at second order -- the steps after the first from the prediction's six first-order planes with zero curvatures --, dev_out
         by the names of SUBSET2_PLANES, the six curvatures all or none per step.  mask (a device plane, used by every step) /
-        min_pixels: see _takes_mask.  reference_every: see _moving_reference; the composition's records are left in
+        min_pixels: see _takes_mask; mask_search: see _subset_options.  reference_every: see _moving_reference; the composition's records are left in
         self.compose_records."""
         arr, n = self._passes(passes)
         steps = len(dev_frames) - 1
@@ -2741,7 +2869,7 @@ class OpticalFlow:
             flows = (C.c_void_p * (2 * steps))(*flat)
         reports, reps = (CorrelationPassReport * max(n, 1))(), (SequenceStepReport * steps)()
         options = self._subset_options("OpticalFlow2D::CorrelateSubsetSequenceDevice", radius, iterations, epsilon, max_shift, max_gradient,
-                                       order, max_curvature, mask, min_pixels, interpolation=interpolation)
+                                       order, max_curvature, mask, min_pixels, interpolation=interpolation, mask_search=mask_search)
         self._moving_reference("OpticalFlow2D::CorrelateSubsetSequenceDevice", reference_every)
         rc = host_lib().flow2d_host_correlate_subset_sequence_device(self.handle, (C.c_void_p * len(dev_frames))(*dev_frames), len(dev_frames),
                                                                      float(lo), float(scale), arr, n, float(min_score), float(threshold),

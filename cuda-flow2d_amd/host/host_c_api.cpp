@@ -33,6 +33,7 @@ struct flow2d_host_flow {
     OpticalFlow2D flow;
     size_t width = 0, height = 0;
     int subset_interpolation = OpticalFlow2D::SubsetOptions::CatmullRom;  // flow2d_host_set_subset_interpolation
+    bool subset_mask_search = false;                                      // flow2d_host_set_subset_mask_search
     int reference_every = 0;                                              // flow2d_host_set_reference_every
     std::vector<flow2d_compose_record> compose_records;                   // of the last sequence call: flow2d_host_compose_records
 };
@@ -727,6 +728,83 @@ HOST_API int flow2d_host_correlate_multipass(flow2d_host_flow* h, const float* f
     return 0;
 }
 
+// OpticalFlow2D::CorrelationPassesOk with ValidationOptions::min_pixels: 1 when the schedule takes that min_pixels (0: the default
+// per pass) beside everything flow2d_host_correlation_passes_ok checks.  Needs no device.
+HOST_API int flow2d_host_correlation_passes_masked_ok(size_t width, size_t height, float lo, float scale, const int* passes, int count,
+                                                      float min_score, float threshold, float epsilon, int min_neighbours, int min_pixels)
+{
+    const auto list = correlation_passes(passes, count);
+    auto validation = validation_options(threshold, epsilon, min_neighbours, 1, 1);
+    validation.min_pixels = min_pixels;
+    return count >= 0 && OpticalFlow2D::CorrelationPassesOk(width, height, lo, scale, list.data(), list.size(), min_score, validation) ? 1 : 0;
+}
+
+// flow2d_host_correlate_multipass_device on a region of interest (ValidationOptions::mask, min_pixels): dev_mask is a device plane
+// of the container's size, null for none -- the call is then that entry's --, min_pixels 0 the default per pass.  The masked
+// counts are the seventh words of the reports' records.
+HOST_API int flow2d_host_correlate_multipass_masked_device(flow2d_host_flow* h, void* dev_frame_0, void* dev_frame_1, float lo, float scale,
+                                                           const int* passes, int count, float min_score, float threshold, float epsilon,
+                                                           int min_neighbours, int replace, int validate_last, void* dev_mask,
+                                                           int min_pixels, void* dev_predictor_u, void* dev_predictor_v, void* dev_node_u,
+                                                           void* dev_node_v, void* dev_node_score,
+                                                           OpticalFlow2D::CorrelationPassReport* reports, void* dev_flow_u, void* dev_flow_v)
+{
+    const auto list = correlation_passes(passes, count);
+    auto validation = validation_options(threshold, epsilon, min_neighbours, replace, validate_last);
+    validation.mask = dp(dev_mask);
+    validation.min_pixels = min_pixels;
+    if (!h || !dev_frame_0 || !dev_frame_1 || count < 0 || (dev_flow_u == nullptr) != (dev_flow_v == nullptr) ||
+        (dev_predictor_u == nullptr) != (dev_predictor_v == nullptr) || (dev_node_u == nullptr) != (dev_node_v == nullptr) ||
+        !OpticalFlow2D::CorrelationPassesOk(h->width, h->height, lo, scale, list.data(), list.size(), min_score, validation))
+        return 1;
+    h->flow.timing_mode = 0;
+    return h->flow.CorrelateMultiPassDevice(dp(dev_frame_0), dp(dev_frame_1), lo, scale, list.data(), list.size(), min_score, validation,
+                                            dp(dev_predictor_u), dp(dev_predictor_v), dp(dev_node_u), dp(dev_node_v), dp(dev_node_score),
+                                            reports, dp(dev_flow_u), dp(dev_flow_v))
+               ? 0
+               : 2;
+}
+
+// flow2d_host_correlate_multipass on a region of interest: mask is a tight host image of the frames' size (null: none), which the
+// object uploads once; the rest as there and above.
+HOST_API int flow2d_host_correlate_multipass_masked(flow2d_host_flow* h, const float* frame_0, const float* frame_1, const int* passes,
+                                                    int count, float min_score, float threshold, float epsilon, int min_neighbours,
+                                                    int replace, int validate_last, const float* mask, int min_pixels,
+                                                    const float* predictor_u, const float* predictor_v, float* node_u, float* node_v,
+                                                    float* node_score, OpticalFlow2D::CorrelationPassReport* reports, float* flow_u,
+                                                    float* flow_v, float* lo_scale)
+{
+    const auto list = correlation_passes(passes, count);
+    auto validation = validation_options(threshold, epsilon, min_neighbours, replace, validate_last);
+    validation.min_pixels = min_pixels;
+    if (!h || !frame_0 || !frame_1 || !node_u || !node_v || count < 0 || (flow_u == nullptr) != (flow_v == nullptr) ||
+        (predictor_u == nullptr) != (predictor_v == nullptr))
+        return 1;
+    HostImages im(h);
+    Data2D *f0 = im.In(frame_0), *f1 = im.In(frame_1);
+    Data2D *pu = predictor_u ? im.In(predictor_u) : nullptr, *pv = predictor_v ? im.In(predictor_v) : nullptr;
+    Data2D *fu = im.Out(flow_u, im.AfterSuccess), *fv = im.Out(flow_v, im.AfterSuccess);
+    Data2D* region = mask ? im.In(mask) : nullptr;
+    float lo = 0.f, scale = 1.f;
+    OpticalFlow2D::CorrelationRange(*f0, *f1, lo, scale);
+    if (!OpticalFlow2D::CorrelationPassesOk(h->width, h->height, lo, scale, list.data(), list.size(), min_score, validation)) return 1;
+    size_t nw = 0, nh = 0;
+    flow2d_correlation_grid(h->width, h->height, list.back().radius, list.back().spacing, &nw, &nh);
+    Data2D nodes[3] = {Data2D(nw, nh), Data2D(nw, nh), Data2D(nw, nh)};
+    h->flow.CorrelateMultiPass(*f0, *f1, list.data(), list.size(), min_score, validation, nodes[0], nodes[1],
+                               node_score ? &nodes[2] : nullptr, reports, fu, fv, pu, pv, region);
+    const int rc = im.Finish(h->flow);
+    if (rc) return rc;
+    float* dst[3] = {node_u, node_v, node_score};
+    for (int k = 0; k < 3; ++k)
+        if (dst[k]) std::memcpy(dst[k], nodes[k].DataPtr(), nw * nh * sizeof(float));
+    if (lo_scale) {
+        lo_scale[0] = lo;
+        lo_scale[1] = scale;
+    }
+    return 0;
+}
+
 // ---- subset refinement of correlation nodes -----------------------------------------------------------------------------------
 // Every entry that refines takes OpticalFlow2D::SubsetOptions as one record (null: refused) and its outputs as the fourteen slots
 // of OpticalFlow2D::SubsetPlanes -- u, v, ux, uy, vx, vy, score, state, then uxx, uxy, uyy, vxx, vxy, vyy --, per step in the
@@ -763,6 +841,7 @@ OpticalFlow2D::SubsetOptions subset_options(const flow2d_host_subset_options& re
     o.max_curvature = record.max_curvature;
     o.mask = dp(const_cast<void*>(record.mask));
     o.min_pixels = record.min_pixels;
+    o.mask_search = h && h->subset_mask_search;
     return o;
 }
 
@@ -810,6 +889,26 @@ HOST_API int flow2d_host_set_subset_interpolation(flow2d_host_flow* h, int kind)
     if (!h || !flow2d_host_subset_interpolation_ok(kind)) return 1;
     h->subset_interpolation = kind;
     return 0;
+}
+
+// OpticalFlow2D::SubsetOptions::mask_search of every later call of this object that runs the passes of a pair in front of a
+// refinement with a mask (it travels beside the 40-byte options record, like the interpolation): 0 off (what a new object has),
+// 1 on -- every entry below then refuses options without a mask, as SubsetOptionsOk does.  0 on success, 1 for a null object or
+// another value, which changes nothing.
+HOST_API int flow2d_host_set_subset_mask_search(flow2d_host_flow* h, int on)
+{
+    if (!h || (on != 0 && on != 1)) return 1;
+    h->subset_mask_search = on == 1;
+    return 0;
+}
+
+// Whether OpticalFlow2D::SubsetOptionsOk accepts the options with mask_search set: 1 only with a mask.  Needs no device.
+HOST_API int flow2d_host_subset_mask_search_ok(const flow2d_host_subset_options* options)
+{
+    if (!options) return 0;
+    auto subset = subset_options(*options);
+    subset.mask_search = true;
+    return OpticalFlow2D::SubsetOptionsOk(subset) ? 1 : 0;
 }
 
 // OpticalFlow2D::SubsetMinPixels: the default min_pixels of a radius.

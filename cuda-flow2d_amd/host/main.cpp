@@ -117,6 +117,17 @@
 // specimen"; with --subset-mask-invert it is a region image, non-zero meaning "inside".  A subset is refined on its usable pixels; a
 // node off the specimen, or with fewer than N usable pixels, is masked: state -4 and NaN in the node files.  One more line,
 // "SubsetMask: {json}" -- "masked", the masked nodes, and "min_pixels" -- is printed.  Without the option no byte of any output changes.
+// --correlation-mask FILE [--correlation-mask-invert] [--correlation-min-pixels N, 1 .. (2r + 1)^2 of every pass, default a quarter
+// of each pass's window], valid only together with --correlation-passes and without --subset-refine, is the window search on a
+// region of interest (OpticalFlow2D::ValidationOptions::mask: flow2d_correlate_masked_2d and flow2d_validate_nodes_masked_2d in every
+// pass): FILE as for --subset-mask.  A window is correlated on its specimen pixels alone; a node whose centre is off the specimen, or
+// whose window keeps fewer than N pixels, is masked: NaN in the node files, no vote in the median test.  One more line,
+// "CorrelationMask: {json}" -- "min_pixels" as given (0: the default) and per pass "min_pixels", "masked" (the search's masked nodes)
+// and "validation_masked" (the nodes off the specimen) -- is printed behind the "CorrelationPasses:" line.
+// --subset-mask-search, valid only together with --subset-mask and not with --subset-previous (which runs no passes), hands the
+// subset mask to the passes in front of the refinement (OpticalFlow2D::SubsetOptions::mask_search), so that an edge node starts from
+// the specimen's motion; the "CorrelationMask:" line is printed before the "SubsetMask:" line.  Without these options no byte of any
+// output changes.
 // --subset-interpolation catmull-rom|bspline, valid only together with --subset-refine, says how frame 1 is sampled
 // (OpticalFlow2D::SubsetOptions::interpolation): with bspline the run prefilters FILE_1 into its cubic B-spline coefficients
 // (flow2d_bspline_prefilter_2d) and refines with flow2d_subset_refine_spline_2d or, with --subset-order 2,
@@ -172,6 +183,20 @@ static bool LoadFrame(Data2D& frame, const std::string& input_path, const std::s
     return false;
 }
 
+// The line a masked chain of passes adds, "CorrelationMask: {json}": min_pixels as given (0: the default per pass) and, per pass, the
+// min_pixels it ran with and the masked counts of the search and of the validation (the records' seventh words).
+static void print_correlation_mask(const std::vector<OpticalFlow2D::CorrelationPass>& passes,
+                                   const std::vector<OpticalFlow2D::CorrelationPassReport>& reports,
+                                   const OpticalFlow2D::ValidationOptions& validation)
+{
+    std::printf("CorrelationMask: {\"min_pixels\": %d, \"passes\": [", validation.min_pixels);
+    for (size_t k = 0; k < reports.size(); ++k)
+        std::printf("%s{\"min_pixels\": %d, \"masked\": %llu, \"validation_masked\": %llu}", k ? ", " : "",
+                    OpticalFlow2D::CorrelationMinPixels(validation, passes[k].radius), reports[k].correlation.reserved[0],
+                    reports[k].validation.reserved[0]);
+    std::printf("]}\n");
+}
+
 int main(int argc, char** argv)
 {
     // optional flags first (supersets), then the reference's positional forms
@@ -205,6 +230,9 @@ int main(int argc, char** argv)
     bool sequence_option = false, subset_max_shift_given = false, subset_curvature_given = false;
     std::string subset_mask_file;  // --subset-mask FILE, --subset-mask-invert, --subset-min-pixels N
     bool subset_mask_invert = false, subset_mask_option = false;
+    std::string correlation_mask_file;  // --correlation-mask FILE, --correlation-mask-invert, --correlation-min-pixels N
+    bool correlation_mask_invert = false, correlation_mask_option = false;
+    int correlation_min_pixels = 0;
     OpticalFlow2D::StrainOptions node_strain;  // --subset-strain M and --strain-order, --strain-min-nodes
     bool subset_strain = false, strain_option = false;
     OpticalFlow2D::ValidationOptions validation;                     // --validate-threshold / -epsilon / -min-neighbours / -flag-only
@@ -510,6 +538,27 @@ int main(int argc, char** argv)
             subset_mask_file = argv[++i];
         }
         else if (!std::strcmp(argv[i], "--subset-mask-invert")) subset_mask_invert = subset_mask_option = true;
+        else if (!std::strcmp(argv[i], "--subset-mask-search")) subset.mask_search = subset_mask_option = true;
+        else if (!std::strcmp(argv[i], "--correlation-mask")) {
+            if (i + 1 >= argc || !argv[i + 1][0]) {
+                std::printf("--correlation-mask takes the file of the mask image.\n");
+                return 5;
+            }
+            correlation_mask_file = argv[++i];
+        }
+        else if (!std::strcmp(argv[i], "--correlation-mask-invert")) correlation_mask_invert = correlation_mask_option = true;
+        else if (!std::strcmp(argv[i], "--correlation-min-pixels")) {
+            char* end = nullptr;
+            const long n = (i + 1 < argc) ? std::strtol(argv[i + 1], &end, 10) : 0;
+            const long largest = (2 * FLOW2D_CORRELATION_MAX_RADIUS + 1) * (2 * FLOW2D_CORRELATION_MAX_RADIUS + 1);
+            if (i + 1 >= argc || end == argv[i + 1] || *end != '\0' || n < 1 || n > largest) {
+                std::printf("--correlation-min-pixels takes a whole number of 1 .. %ld.\n", largest);
+                return 5;
+            }
+            correlation_min_pixels = static_cast<int>(n);
+            correlation_mask_option = true;
+            ++i;
+        }
         else if (!std::strcmp(argv[i], "--subset-min-pixels")) {
             char* end = nullptr;
             const long n = (i + 1 < argc) ? std::strtol(argv[i + 1], &end, 10) : 0;
@@ -639,8 +688,23 @@ int main(int argc, char** argv)
         return 5;
     }
     if ((!subset_mask_file.empty() || subset_mask_option) && !(subset_refine && !subset_mask_file.empty())) {
-        std::printf("--subset-mask FILE gives --subset-refine a region of interest, and --subset-mask-invert and --subset-min-pixels belong "
-                    "to it.\n");
+        std::printf("--subset-mask FILE gives --subset-refine a region of interest, and --subset-mask-invert, --subset-min-pixels and "
+                    "--subset-mask-search belong to it.\n");
+        return 5;
+    }
+    if (subset.mask_search && !subset_previous.empty()) {
+        std::printf("--subset-mask-search masks the passes in front of the refinement: --subset-previous runs none.\n");
+        return 5;
+    }
+    if ((!correlation_mask_file.empty() || correlation_mask_option) && !(multipass && !correlation_mask_file.empty())) {
+        std::printf("--correlation-mask FILE gives --correlation-passes a region of interest, and --correlation-mask-invert and "
+                    "--correlation-min-pixels belong to it.\n");
+        return 5;
+    }
+    validation.min_pixels = correlation_min_pixels;
+    if (!correlation_mask_file.empty() && subset_refine) {
+        std::printf("--correlation-mask goes with --correlation-passes alone: with --subset-refine the region of interest is --subset-mask, "
+                    "and --subset-mask-search hands it to the passes.\n");
         return 5;
     }
     if (!subset_mask_file.empty() && subset.order == 2) {
@@ -803,6 +867,13 @@ int main(int argc, char** argv)
             for (size_t k = 0; k < width * height; ++k) subset_mask.DataPtr()[k] = subset_mask.DataPtr()[k] != 0.f ? 0.f : 1.f;
     }
     Data2D* const subset_mask_image = subset_mask_file.empty() ? nullptr : &subset_mask;
+    Data2D correlation_mask;  // --correlation-mask: 1 = not the specimen
+    if (!correlation_mask_file.empty()) {
+        if (!LoadFrame(correlation_mask, input_path, correlation_mask_file, u8, width, height)) return 2;
+        if (correlation_mask_invert)  // a region image: non-zero means inside
+            for (size_t k = 0; k < width * height; ++k) correlation_mask.DataPtr()[k] = correlation_mask.DataPtr()[k] != 0.f ? 0.f : 1.f;
+    }
+    Data2D* const correlation_mask_image = correlation_mask_file.empty() ? nullptr : &correlation_mask;
 
     Data2D prior_u, prior_v;
     if (!initial_flow_file.empty()) {
@@ -948,9 +1019,11 @@ int main(int argc, char** argv)
                 }
             } else {
                 const bool predicted = multipass && !initial_flow_file.empty();
+                std::vector<OpticalFlow2D::CorrelationPassReport> searched(subset.mask_search ? schedule.size() : 0);
                 optical_flow.CorrelateSubset(frame_0, frame_1, schedule.data(), schedule.size(), correlation_min_score, validation, subset,
-                                             nodes, nullptr, &record, &flow_u, &flow_v, predicted ? &prior_u : nullptr,
-                                             predicted ? &prior_v : nullptr, subset_mask_image);
+                                             nodes, subset.mask_search ? searched.data() : nullptr, &record, &flow_u, &flow_v,
+                                             predicted ? &prior_u : nullptr, predicted ? &prior_v : nullptr, subset_mask_image);
+                if (subset.mask_search && optical_flow.LastRunSucceeded()) print_correlation_mask(schedule, searched, validation);
             }
             flow2d_compose_record composition = {};
             std::vector<Data2D> composed;
@@ -1028,7 +1101,7 @@ int main(int argc, char** argv)
             const bool predicted = !initial_flow_file.empty();
             optical_flow.CorrelateMultiPass(frame_0, frame_1, correlation_passes.data(), correlation_passes.size(), correlation_min_score,
                                             validation, node_u, node_v, &node_score, reports.data(), &flow_u, &flow_v,
-                                            predicted ? &prior_u : nullptr, predicted ? &prior_v : nullptr);
+                                            predicted ? &prior_u : nullptr, predicted ? &prior_v : nullptr, correlation_mask_image);
             if (optical_flow.LastRunSucceeded()) {
                 const std::string nodes = "-" + std::to_string(nw) + "-" + std::to_string(nh) + ".raw";
                 node_u.WriteRAWToFileF32((output_path + counter + "node-u" + nodes).c_str());
@@ -1050,6 +1123,7 @@ int main(int argc, char** argv)
                                 v.nodes, v.judged, v.outliers, v.filled, v.unjudged, v.remaining_invalid);
                 }
                 std::printf("]}\n");
+                if (correlation_mask_image) print_correlation_mask(correlation_passes, reports, validation);
                 if (subset_strain) {
                     Data2D* fields[7] = {&node_u, &node_v, nullptr, nullptr, nullptr, nullptr, nullptr};
                     write_node_strain(fields, nw, nh, fine.spacing);

@@ -309,7 +309,17 @@ public:
         float threshold = 2.f, epsilon = 0.1f;
         int min_neighbours = 3;
         bool replace = true, validate_last = true;
+        // A region of interest through the passes (flow2d_correlate_masked_2d, flow2d_validate_nodes_masked_2d in place of the two
+        // entries above, in every pass; the expansion is unchanged): mask, a device plane of the frames' size and pitch in frame
+        // 0's coordinates, 0 = none -- the calls there always were --, whose values of 0.5 and more (and NaN) mean "not the
+        // specimen".  A node whose centre is excluded or whose window keeps fewer than min_pixels pixels is masked (NaN); 0 = per
+        // pass max(6, ((2 radius + 1)^2 + 3) / 4), an explicit value must fit every pass's window.  The masked counts are the
+        // seventh words of the reports' records (reserved[0]).
+        DevicePtr mask = 0;
+        int min_pixels = 0;
     };
+    // min_pixels as a pass of `radius` gets it: the default where it is 0
+    static int CorrelationMinPixels(const ValidationOptions& validation, int radius);
     struct CorrelationPassReport {
         size_t nw, nh;
         flow2d_correlation_pass_record correlation;
@@ -322,11 +332,13 @@ public:
                                   DevicePtr dev_predictor_v, DevicePtr dev_node_u, DevicePtr dev_node_v, DevicePtr dev_node_score,
                                   CorrelationPassReport* reports_out, DevicePtr dev_flow_u = 0, DevicePtr dev_flow_v = 0);
     // The host-image form (the CLI's --correlation-passes): lo and scale from CorrelationRange; node_u / node_v (and node_score,
-    // optional) are images of the LAST pass's grid; predictor_u / predictor_v (optional, both or neither): the initial predictor.
+    // optional) are images of the LAST pass's grid; predictor_u / predictor_v (optional, both or neither): the initial predictor;
+    // mask (optional): an image of the frames' size in place of validation.mask, which this form does not look at; the object
+    // uploads it once per call.
     void CorrelateMultiPass(Data2D& frame_0, Data2D& frame_1, const CorrelationPass* passes, size_t count, float min_score,
                             const ValidationOptions& validation, Data2D& node_u, Data2D& node_v, Data2D* node_score,
                             CorrelationPassReport* reports_out, Data2D* flow_u = nullptr, Data2D* flow_v = nullptr,
-                            Data2D* predictor_u = nullptr, Data2D* predictor_v = nullptr);
+                            Data2D* predictor_u = nullptr, Data2D* predictor_v = nullptr, Data2D* mask = nullptr);
 
     // Subset refinement of correlation nodes (flow2d_subset_refine_2d: the inverse-compositional Gauss-Newton iteration with an
     // affine shape function, on the fp32 frames): the second half of a digital image correlation.  All planes are planes of the
@@ -346,6 +358,12 @@ public:
         // its own.  Order 1 only: SubsetOptionsOk refuses a mask with order 2.
         DevicePtr mask = 0;
         int min_pixels = 0;
+        // The region of interest through the whole chain: with a mask, the calls that run the passes of a pair -- CorrelateSubset*,
+        // step 1 of CorrelateSubsetSequence* and every later step that runs the pair chain -- hand it to their passes
+        // (ValidationOptions::mask; the search's min_pixels stays validation.min_pixels), so that an edge node starts from the
+        // specimen's motion and not the background's.  False keeps the calls there always were, byte for byte: that is why it is a
+        // flag and not implied by the mask.  SubsetOptionsOk refuses it without a mask.
+        bool mask_search = false;
         // How frame 1 is sampled.  BSpline: every call that refines prefilters its frame 1 -- in a sequence every step its frame k
         // -- into a plane of the object's own (flow2d_bspline_prefilter_2d) and calls the spline entry of its order
         // (flow2d_subset_refine_spline_2d, flow2d_subset_refine2_spline_2d); mask and start gradients go through.  A tenth of the

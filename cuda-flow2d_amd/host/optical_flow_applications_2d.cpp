@@ -645,7 +645,22 @@ bool OpticalFlow2D::CorrelationPassesOk(size_t width, size_t height, float lo, f
                     passes[k].range, passes[k].spacing);
         return false;
     }
+    // an explicit min_pixels has to fit every pass's window (looked at whether or not there is a mask: it needs no device)
+    for (size_t k = 0; validation.min_pixels != 0 && k < count; ++k) {
+        const int side = 2 * passes[k].radius + 1;
+        if (validation.min_pixels >= 1 && validation.min_pixels <= side * side) continue;
+        std::printf("Error: a masked window search takes 1 .. (2 radius + 1)^2 pixels at least (%d at radius %d in pass %zu), or 0 for a "
+                    "quarter of each pass's window.\n",
+                    validation.min_pixels, passes[k].radius, k + 1);
+        return false;
+    }
     return true;
+}
+
+int OpticalFlow2D::CorrelationMinPixels(const ValidationOptions& validation, int radius)
+{
+    const int side = 2 * radius + 1;
+    return validation.min_pixels ? validation.min_pixels : std::max(6, (side * side + 3) / 4);
 }
 
 bool OpticalFlow2D::CorrelateMultiPassDevice(DevicePtr dev_frame_0, DevicePtr dev_frame_1, float lo, float scale,
@@ -674,7 +689,7 @@ bool OpticalFlow2D::QueueCorrelationPasses(DevicePtr dev_frame_0, DevicePtr dev_
     {
         // the caller's written planes pass through the validation and the expansion, which know no frame: checked here
         std::vector<DevicePtr> read = {dev_frame_0, dev_frame_1}, written;
-        for (DevicePtr p : {dev_predictor_u, dev_predictor_v})
+        for (DevicePtr p : {dev_predictor_u, dev_predictor_v, validation.mask})
             if (p) read.push_back(p);
         for (DevicePtr p : {dev_node_u, dev_node_v, dev_node_score, dev_flow_u, dev_flow_v})
             if (p) written.push_back(p);
@@ -699,16 +714,32 @@ bool OpticalFlow2D::QueueCorrelationPasses(DevicePtr dev_frame_0, DevicePtr dev_
         DevicePtr final_v = last && dev_node_v ? dev_node_v : own[validated ? 3 : 1];
         DevicePtr raw_u = validated ? own[0] : final_u, raw_v = validated ? own[1] : final_v;
         // (the node planes are containers: the frames' pitch)
-        ok = !CheckFlow2DError(flow2d_correlate_offset_2d(context_, AsPlane(dev_frame_0), AsPlane(dev_frame_1), predictor[0], predictor[1], W,
-                                                          H, pitch, lo, scale, pass.radius, pass.range, pass.spacing, min_score,
-                                                          AsPlane(raw_u), AsPlane(raw_v),
-                                                          last && dev_node_score ? AsPlane(dev_node_score) : nullptr, pitch, record),
-                               "flow2d_correlate_offset_2d");
-        if (ok && validated)
+        // With a region of interest both steps are the masked entries, in every pass; the expansion stays as it is: it skips the NaN
+        // of a masked node, so the predictor continues the specimen's motion outward.  Without one: the calls there always were.
+        if (validation.mask)
+            ok = !CheckFlow2DError(flow2d_correlate_masked_2d(context_, AsPlane(dev_frame_0), AsPlane(dev_frame_1), predictor[0],
+                                                              predictor[1], W, H, pitch, lo, scale, pass.radius, pass.range, pass.spacing,
+                                                              min_score, AsPlane(validation.mask),
+                                                              CorrelationMinPixels(validation, pass.radius), AsPlane(raw_u), AsPlane(raw_v),
+                                                              last && dev_node_score ? AsPlane(dev_node_score) : nullptr, pitch, record),
+                                   "flow2d_correlate_masked_2d");
+        else
+            ok = !CheckFlow2DError(flow2d_correlate_offset_2d(context_, AsPlane(dev_frame_0), AsPlane(dev_frame_1), predictor[0], predictor[1],
+                                                              W, H, pitch, lo, scale, pass.radius, pass.range, pass.spacing, min_score,
+                                                              AsPlane(raw_u), AsPlane(raw_v),
+                                                              last && dev_node_score ? AsPlane(dev_node_score) : nullptr, pitch, record),
+                                   "flow2d_correlate_offset_2d");
+        const int mode = !last || validation.replace ? FLOW2D_VALIDATE_REPLACE : FLOW2D_VALIDATE_FLAG;
+        if (ok && validated && validation.mask)
+            ok = !CheckFlow2DError(flow2d_validate_nodes_masked_2d(context_, AsPlane(raw_u), AsPlane(raw_v), nw, nh, pitch,
+                                                                   validation.threshold, validation.epsilon, validation.min_neighbours, mode,
+                                                                   AsPlane(validation.mask), W, H, pitch, pass.radius, pass.spacing,
+                                                                   AsPlane(final_u), AsPlane(final_v), nullptr, checked),
+                                   "flow2d_validate_nodes_masked_2d");
+        else if (ok && validated)
             ok = !CheckFlow2DError(flow2d_validate_nodes_2d(context_, AsPlane(raw_u), AsPlane(raw_v), nw, nh, pitch, validation.threshold,
-                                                            validation.epsilon, validation.min_neighbours,
-                                                            !last || validation.replace ? FLOW2D_VALIDATE_REPLACE : FLOW2D_VALIDATE_FLAG,
-                                                            AsPlane(final_u), AsPlane(final_v), nullptr, checked),
+                                                            validation.epsilon, validation.min_neighbours, mode, AsPlane(final_u),
+                                                            AsPlane(final_v), nullptr, checked),
                                    "flow2d_validate_nodes_2d");
         if (ok && !last) {
             ok = !CheckFlow2DError(flow2d_expand_nodes_2d(context_, AsPlane(final_u), AsPlane(final_v), nw, nh, pitch, pass.radius,
@@ -770,6 +801,10 @@ bool OpticalFlow2D::SubsetOptionsOk(const SubsetOptions& subset)
     if (subset.mask && subset.order == 2) {
         std::printf("Error: a subset mask goes with the first-order refinement only (order %d): flow2d_subset_refine2_2d takes no mask.\n",
                     subset.order);
+        return false;
+    }
+    if (subset.mask_search && !subset.mask) {
+        std::printf("Error: a masked window search in front of the subset refinement needs the subset mask.\n");
         return false;
     }
     if (subset.min_pixels != 0 && (subset.min_pixels < FLOW2D_SUBSET_MIN_PIXELS ||
@@ -941,6 +976,7 @@ bool OpticalFlow2D::QueueCorrelateSubset(DevicePtr dev_frame_0, DevicePtr dev_fr
     ValidationOptions every_node = validation;  // the last pass fills what it did not find: every node gets a start
     every_node.validate_last = true;
     every_node.replace = true;
+    if (subset.mask_search) every_node.mask = subset.mask;  // (SubsetOptionsOk: there is one)
     const CorrelationPass& fine = passes[count - 1];
     DevicePtr refined[2] = {0, 0};
     bool ok = QueueCorrelationPasses(dev_frame_0, dev_frame_1, lo, scale, passes, count, min_score, every_node, dev_predictor_u,
@@ -1516,7 +1552,7 @@ void OpticalFlow2D::CorrelateSubsetSequence(Data2D* const* frames, size_t frame_
 void OpticalFlow2D::CorrelateMultiPass(Data2D& frame_0, Data2D& frame_1, const CorrelationPass* passes, size_t count, float min_score,
                                        const ValidationOptions& validation, Data2D& node_u, Data2D& node_v, Data2D* node_score,
                                        CorrelationPassReport* reports_out, Data2D* flow_u, Data2D* flow_v, Data2D* predictor_u,
-                                       Data2D* predictor_v)
+                                       Data2D* predictor_v, Data2D* mask)
 {
     last_run_ok_ = false;
     if (!IsInitialized() || (flow_u == nullptr) != (flow_v == nullptr) || (predictor_u == nullptr) != (predictor_v == nullptr)) return;
@@ -1525,6 +1561,8 @@ void OpticalFlow2D::CorrelateMultiPass(Data2D& frame_0, Data2D& frame_1, const C
     // the node planes: containers with no image of their size behind them, downloaded below
     planes.Add(nullptr, CallPlanes::Out, true).Add(nullptr, CallPlanes::Out, true).Add(nullptr, CallPlanes::Out, node_score != nullptr);
     if (predictor_u) planes.Add(predictor_u, CallPlanes::In).Add(predictor_v, CallPlanes::In);
+    const int mask_at = 7 + (predictor_u ? 2 : 0);  // the mask, uploaded once, behind everything else
+    if (mask) planes.Add(mask, CallPlanes::In);
     if (!planes.SizesMatch()) return;
     float lo = 0.f, scale = 1.f;
     CorrelationRange(frame_0, frame_1, lo, scale);
@@ -1540,8 +1578,10 @@ void OpticalFlow2D::CorrelateMultiPass(Data2D& frame_0, Data2D& frame_1, const C
         }
     HostCall call(context_, last_total_ms_, planes.Allocate());
     const DevicePtr* d = planes.data();
+    ValidationOptions masked = validation;
+    masked.mask = mask ? d[mask_at] : 0;
     bool ok = planes.Upload() &&
-              CorrelateMultiPassDevice(d[0], d[1], lo, scale, passes, count, min_score, validation, predictor_u ? d[7] : 0, predictor_u ? d[8] : 0, d[4],
+              CorrelateMultiPassDevice(d[0], d[1], lo, scale, passes, count, min_score, masked, predictor_u ? d[7] : 0, predictor_u ? d[8] : 0, d[4],
                                        d[5], d[6],
                                        reports_out, d[2], d[3]) &&
               planes.Download();

@@ -116,10 +116,10 @@ def make_speckle_scene(motion, width=96, height=80, seed=0):
 SPECKLE_DEFORMATIONS = ("rotation", "stretch", "shear")
 
 
-def make_speckle_deformation(name, width=96, height=80, seed=0):
+def make_speckle_deformation(name, width=96, height=80, seed=0, translation=(1.6, -0.7)):
     """A speckle pattern whose windows deform (one of SPECKLE_DEFORMATIONS), for the subset refinement (flow2d_subset_refine_2d):
-    a rotation by 5 degrees, a stretch by 1.06 x 0.97 and a shear of 0.08, each about the centre and followed by the translation
-    (1.6, -0.7).  They are NOT in SPECKLE_MOTIONS: the tests that iterate over that tuple are about the rigid window."""
+    a rotation by 5 degrees, a stretch by 1.06 x 0.97 and a shear of 0.08, each about the centre and followed by `translation`,
+    (1.6, -0.7) by default.  They are NOT in SPECKLE_MOTIONS: the tests that iterate over that tuple are about the rigid window."""
     texture = Speckle(seed)
     if name == "rotation":
         phi = np.radians(5.0)
@@ -130,20 +130,24 @@ def make_speckle_deformation(name, width=96, height=80, seed=0):
         a = [[1.0, 0.08], [0.0, 1.0]]
     else:
         raise ValueError("unknown speckle deformation %r (one of %s)" % (name, ", ".join(SPECKLE_DEFORMATIONS)))
-    return _affine_scene("speckle_" + name, width, height, texture, a, (1.6, -0.7))
+    return _affine_scene("speckle_" + name, width, height, texture, a, (float(translation[0]), float(translation[1])))
 
 
-def make_speckle_specimen(name, width=96, height=80, seed=0):
+def make_speckle_specimen(name, width=96, height=80, seed=0, translation=(1.6, -0.7), background_gain=0.3, background_offset=5.0):
     """A specimen in front of a background that does not move with it, for the masked subset refinement
     (flow2d_subset_refine_masked_2d): the deformation `name` (one of SPECKLE_DEFORMATIONS) of make_speckle_deformation, W about
     the centre c = ((width - 1) / 2, (height - 1) / 2), applied to a plate with a hole.  A point is *inside* when |x - c0| <=
     30.5 width / 96, |y - c1| <= 24.5 height / 80 and (x - c0)^2 + (y - c1)^2 > (9.5 min(width / 96, height / 80))^2.  T =
-    Speckle(seed) is the specimen's texture, B = 0.3 Speckle(seed + 7) + 5 the static background:
+    Speckle(seed) is the specimen's texture, B = background_gain Speckle(seed + 7) + background_offset the static background
+    (0.3 and 5 by default: dim; 1 and 0 give it the specimen's own contrast):
       frame_0(x) = inside(x) ? T(x) : B(x);   frame_1(X) = inside(W^-1 X) ? T(W^-1 X) : B(X).
+    `translation` is the one W ends with, (1.6, -0.7) by default: a larger one moves the plate further than a window search's
+    edge nodes can follow while their windows are half background (flow2d_correlate_masked_2d).
     Returns (scene, mask): the Scene of make_speckle_deformation with these frames (float32; gt_u, gt_v are W(x) - x everywhere,
     true on the specimen) and the mask in frame 0's coordinates, float32, 1 where not inside, else 0."""
-    plain = make_speckle_deformation(name, width, height, seed)
+    plain = make_speckle_deformation(name, width, height, seed, translation)
     texture, background = Speckle(seed), Speckle(seed + 7)
+    background_gain, background_offset = float(background_gain), float(background_offset)
     c0, c1 = (width - 1) / 2.0, (height - 1) / 2.0
     half_w, half_h, hole = 30.5 * width / 96.0, 24.5 * height / 80.0, 9.5 * min(width / 96.0, height / 80.0)
 
@@ -152,7 +156,7 @@ def make_speckle_specimen(name, width=96, height=80, seed=0):
         return (np.abs(x - c0) <= half_w) & (np.abs(y - c1) <= half_h) & ((x - c0) ** 2 + (y - c1) ** 2 > hole ** 2)
 
     def ground(x, y):
-        return 0.3 * background(x, y) + 5.0
+        return background_gain * background(x, y) + background_offset
 
     def frame_0_at(x, y):
         return np.where(inside(x, y), texture(x, y), ground(x, y))

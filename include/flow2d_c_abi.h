@@ -53,7 +53,8 @@ extern "C" {
  * flow2d_subset_refine_spline_2d / flow2d_subset_refine2_spline_2d (the refinement with a cubic B-spline interpolation of the
  * deformed frame) and flow2d_context_set_planning_cus / flow2d_context_planning_cus (the CU count the launch planners plan
  * for) with the host-only diagnostics flow2d_fused_block_order_for_cus / flow2d_fused_plan_for_cus /
- * flow2d_stream_rows_for_cus (which plan a CU count gives) were added under 1. */
+ * flow2d_stream_rows_for_cus (which plan a CU count gives) and flow2d_correlate_masked_2d / flow2d_validate_nodes_masked_2d (the
+ * window search and the median test on a region of interest) were added under 1. */
 #define FLOW2D_ABI_VERSION 1
 
 typedef enum flow2d_status {
@@ -923,7 +924,7 @@ typedef struct flow2d_correlation_pass_record {
     unsigned long long unrefined;   /* delivered vectors without a sub-pixel part */
     unsigned long long unpredicted; /* nodes whose predictor was not finite: offset 0 */
     unsigned long long candidates;  /* (node, displacement) pairs scored */
-    unsigned long long reserved[2]; /* 0 */
+    unsigned long long reserved[2]; /* 0; flow2d_correlate_masked_2d: reserved[0] holds the masked nodes */
 } flow2d_correlation_pass_record;
 
 #define FLOW2D_CORRELATION_PASS_RECORD_BYTES 64
@@ -978,7 +979,7 @@ typedef struct flow2d_validation_record {
     unsigned long long filled;            /* invalid nodes that took their neighbours' median: flag 2 */
     unsigned long long unjudged;          /* k < min_neighbours: copied */
     unsigned long long remaining_invalid; /* output nodes that are not finite */
-    unsigned long long reserved[2];       /* 0 */
+    unsigned long long reserved[2];       /* 0; flow2d_validate_nodes_masked_2d: reserved[0] holds the off-specimen nodes */
 } flow2d_validation_record;
 
 #define FLOW2D_VALIDATION_RECORD_BYTES 64
@@ -992,6 +993,68 @@ FLOW2D_API int flow2d_validate_nodes_2d(flow2d_context* ctx, const float* node_u
                                         size_t node_pitch_bytes, float threshold, float epsilon, int min_neighbours, int mode,
                                         float* out_u, float* out_v, float* out_flag /* may be NULL */,
                                         flow2d_validation_record* record /* device, may be NULL */);
+
+/* The window search and the median test on a region of interest: flow2d_correlate_offset_2d and flow2d_validate_nodes_2d with a
+ * pixel mask that says which pixels of frame 0 are not the specimen, so that a region of interest holds through the whole chain
+ * and not only in flow2d_subset_refine_masked_2d.  A window that reaches across the specimen's edge is correlated on its specimen
+ * pixels alone, and a node off the specimen neither votes in the median test nor is judged by it.  Added to ABI version 1 without
+ * changing any existing entry.
+ *
+ * flow2d_correlate_masked_2d: flow2d_correlate_offset_2d with mask and min_pixels.  Everything not restated here is that entry's
+ * text (and through it flow2d_correlate_2d's).
+ * mask holds width x height floats with the frames' pitch_bytes, in frame 0's coordinates; in a batch instance b lies at
+ * b * stride floats, like the frames.  Frame 1 carries no mask.
+ * Excluded.  A pixel is *excluded* when !(m < 0.5), m its mask value compared as a float: 1 means "not the specimen" (the
+ * convention of flow2d_subset_refine_masked_2d), and a NaN is excluded.  There is no stencil rule here: the search takes no
+ * gradients.
+ * Masked.  Nv = the number of pixels of the node's window in frame 0 that are not excluded.  A node is *masked* when its centre
+ * pixel (cx, cy) is excluded or !(Nv >= min_pixels).  This test comes before everything else: a masked node reads no predictor
+ * (it is never unpredicted), has u = v = NaN (0x7FC00000) and score 0, and counts in `nodes` and in `masked` only.
+ * Sums.  S0, S00, S1, S11 and S01 run over the pixels (wx, wy) of the window whose pixel of FRAME 0's window is not excluded --
+ * for S1 and S11 the pixels of the candidate's window in frame 1 at the same (wx, wy) -- and Nv stands in the place of N:
+ *   A = Nv * S01 - S0 * S1,   V0 = Nv * S00 - S0 * S0,   V1 = Nv * S11 - S1 * S1
+ * still exact 64-bit integers (Nv * S01 < 2^36).  Candidates, the score, the order of the peak, the parabola -- whose four
+ * neighbours are scored with the same masked sums --, invalid, rejected, unrefined and unpredicted nodes are unchanged.
+ * Record.  flow2d_correlation_pass_record, the struct as it is: its seventh word, reserved[0], which the other entries write as
+ * 0, holds the count of masked nodes here.  `candidates` counts over the nodes that are neither masked nor have V0 <= 0.
+ * Equivalences.  mask == NULL (min_pixels is then not looked at): the call is forwarded to flow2d_correlate_offset_2d.  A mask
+ * that excludes nothing: that entry's node planes and all eight record words.
+ * One launch on the context's stream (and a 64-byte memset per instance with a record); no allocation, no synchronisation, no
+ * host round trip (graph-capturable).  Honours flow2d_context_set_batch: the mask of instance b at b * stride floats, like every
+ * other plane.
+ * Refusals.  Those of flow2d_correlate_offset_2d, and with a mask also FLOW2D_ERR_INVALID_ARGUMENT, nothing written, for a mask
+ * that breaks the frames' plane rules, a written range -- over every instance of a batch -- that overlaps the mask, or a
+ * min_pixels outside 1 .. (2r + 1)^2. */
+FLOW2D_API int flow2d_correlate_masked_2d(flow2d_context* ctx, const float* frame_0, const float* frame_1,
+                                          const float* predictor_u /* may be NULL */, const float* predictor_v /* with predictor_u */,
+                                          size_t width, size_t height, size_t pitch_bytes, float lo, float scale, int radius,
+                                          int range, int spacing, float min_score, const float* mask /* device, may be NULL */,
+                                          int min_pixels, float* node_u, float* node_v, float* node_score /* may be NULL */,
+                                          size_t node_pitch_bytes, flow2d_correlation_pass_record* record /* device, may be NULL */);
+
+/* flow2d_validate_nodes_masked_2d: flow2d_validate_nodes_2d with the pixel mask and the geometry of the grid the nodes lie on:
+ * mask is a plane of width x height floats with pitch_bytes per row (in a batch instance b at b * stride floats), and node (i, j)
+ * is centred on pixel (cx, cy) = (radius + i * spacing, radius + j * spacing).  nw x nh must be what flow2d_correlation_grid
+ * answers for (width, height, radius, spacing).
+ * Off the specimen.  A node is *off the specimen* when mask[cy][cx] is excluded (!(m < 0.5)).  Such a node is never a neighbour,
+ * whatever its vector holds.  It comes out as NaN (0x7FC00000), NaN with flag 3 (FLOW2D_VALIDATE_FLAG_MASKED) in either mode, and
+ * counts in `nodes` and in the record's seventh word, reserved[0] ("masked": the other entries write it as 0; the struct stays
+ * as it is), and in no other word: `remaining_invalid` counts on-specimen outputs only.
+ * Every other node gets the text of flow2d_validate_nodes_2d over the neighbours that remain.
+ * Equivalences.  mask == NULL (the geometry is then not looked at): the call is forwarded to flow2d_validate_nodes_2d.  A mask
+ * that excludes no node centre: that entry's bytes, the record included.
+ * One launch; graph-capturable; honours flow2d_context_set_batch.
+ * Refusals.  Those of flow2d_validate_nodes_2d, and with a mask also FLOW2D_ERR_INVALID_ARGUMENT, nothing written, for a mask that
+ * breaks the plane rules with (width, height, pitch_bytes), a radius or spacing outside its limits, a frame smaller than one
+ * window, an nw x nh that is not the grid of that geometry, or a written range -- over every instance of a batch -- that overlaps
+ * the mask. */
+#define FLOW2D_VALIDATE_FLAG_MASKED 3
+FLOW2D_API int flow2d_validate_nodes_masked_2d(flow2d_context* ctx, const float* node_u, const float* node_v, size_t nw, size_t nh,
+                                               size_t node_pitch_bytes, float threshold, float epsilon, int min_neighbours, int mode,
+                                               const float* mask /* device, may be NULL */, size_t width, size_t height,
+                                               size_t pitch_bytes, int radius, int spacing, float* out_u, float* out_v,
+                                               float* out_flag /* may be NULL */,
+                                               flow2d_validation_record* record /* device, may be NULL */);
 
 /* Subset refinement of a node field (digital image correlation): the inverse-compositional Gauss-Newton iteration with a
  * first-order shape function (Baker & Matthews 2004; Pan, Li & Tong 2013) on the zero-mean normalised sum of squared differences.
