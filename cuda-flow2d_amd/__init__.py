@@ -218,6 +218,22 @@ class DeformationStats(C.Structure):
 DEFORMATION_STATS_BYTES = 256  # FLOW2D_DEFORMATION_STATS_BYTES, checked by a static_assert in the header
 assert C.sizeof(DeformationStats) == DEFORMATION_STATS_BYTES
 
+# the diagnostic planes of flow2d_node_strain_robust_2d in the order of flow2d_node_strain_diagnostics
+NODE_STRAIN_DIAGNOSTICS = ("residual", "rejected", "centre")
+NODE_STRAIN_MAX_ITERATIONS = 16  # FLOW2D_NODE_STRAIN_MAX_ITERATIONS
+
+
+class NodeStrainDiagnostics(C.Structure):
+    """flow2d_node_strain_diagnostics: a host struct of three device pointers, NULL = not requested."""
+    _fields_ = [(name, C.c_void_p) for name in NODE_STRAIN_DIAGNOSTICS]
+
+
+def node_strain_robust_counts(stats):
+    """The three words a robust node strain adds to its DeformationStats record, over the nodes whose passes ran to the end
+    (valid, or sparse by what they kept): {"touched": nodes that rejected a tap, "rejected": the taps they rejected, "suspect":
+    nodes whose own tap was not kept}."""
+    return {"touched": int(stats.reserved[3]), "rejected": int(stats.reserved[4]), "suspect": int(stats.reserved[5])}
+
 
 REFINE_MAX_RADIUS = 7  # FLOW2D_REFINE_MAX_RADIUS
 
@@ -622,6 +638,11 @@ def hip_lib():
             L.flow2d_node_strain_workspace_bytes.restype = sz
             L.flow2d_node_strain_workspace_bytes.argtypes = [sz, sz, sz]
             L.flow2d_node_strain_2d.argtypes = [vp] + [vp] * 7 + [sz, sz, sz, i, i, i, i, i, i, C.POINTER(DeformationPlanes), vp, vp, sz]
+        if hasattr(L, "flow2d_node_strain_robust_2d"):
+            L.flow2d_node_strain_robust_workspace_bytes.restype = sz
+            L.flow2d_node_strain_robust_workspace_bytes.argtypes = [sz, sz, sz]
+            L.flow2d_node_strain_robust_2d.argtypes = [vp] + [vp] * 3 + [sz, sz, sz, i, i, i, i, i, i, C.c_float, i,
+                                                                        C.POINTER(DeformationPlanes), C.POINTER(NodeStrainDiagnostics), vp, vp, sz]
         if hasattr(L, "flow2d_compose_nodes_2d"):  # (absent from libraries of earlier rounds loaded for an A/B)
             L.flow2d_compose_nodes_2d.argtypes = [vp, vp, vp, vp, sz, sz, sz, i, i, i, vp, vp, vp, vp]
         if hasattr(L, "flow2d_prior_registration_2d"):  # (absent from libraries of earlier rounds loaded for an A/B)
@@ -1736,6 +1757,61 @@ class Context:
                 q.free()
                 self._planes.remove(q)
 
+    @staticmethod
+    def node_strain_robust_workspace_bytes(nw, nh, instances=1):
+        """flow2d_node_strain_robust_workspace_bytes: what node_strain_robust needs beside a record (host logic, no device)."""
+        return hip_lib().flow2d_node_strain_robust_workspace_bytes(nw, nh, instances)
+
+    def node_strain_robust(self, node_u, node_v, nw, nh, spacing, window=2, order=1, min_nodes=0, min_state=1, measure=STRAIN_SMALL,
+                           sigma=0.05, iterations=8, state=None, planes=DEFORMATION_PLANES, diagnostics=NODE_STRAIN_DIAGNOSTICS,
+                           stats=True, instances=1):
+        """Robust strain windows (flow2d_node_strain_robust_2d): `node_strain` with window >= 1 as `iterations` passes of
+        reweighted least squares with a Cauchy weight of scale `sigma` pixels; a tap further than sigma from the last fit is
+        not kept, a window that keeps fewer than min_nodes is sparse.  diagnostics: names of NODE_STRAIN_DIAGNOSTICS (downloaded
+        into the returned dict beside the planes) or a dict of the caller's Planes by those names.  The record's
+        reserved[3 .. 5] are read by node_strain_robust_counts.  Otherwise as `node_strain`."""
+        L = hip_lib()
+        if min_nodes == 0:
+            min_nodes = (6 if order == 2 else 3) + 1
+        own_planes = not isinstance(planes, dict)
+        own_diagnostics = not isinstance(diagnostics, dict)
+        held = {name: self.plane(node_u.width, node_u.height) for name in planes} if own_planes else dict(planes)
+        held_diag = {name: self.plane(node_u.width, node_u.height) for name in diagnostics} if own_diagnostics else dict(diagnostics)
+        unknown = [name for name in held if name not in DEFORMATION_PLANES] + [name for name in held_diag if name not in NODE_STRAIN_DIAGNOSTICS]
+        if unknown:
+            raise ValueError("deformation planes are %s and diagnostics %s, not %s" %
+                             (", ".join(DEFORMATION_PLANES), ", ".join(NODE_STRAIN_DIAGNOSTICS), unknown))
+        out = DeformationPlanes(**{name: q.ptr for name, q in held.items()})
+        diag = NodeStrainDiagnostics(**{name: q.ptr for name, q in held_diag.items()})
+        own_stats = stats is True
+        if own_stats and instances != 1:
+            raise ValueError("a lock-step batch takes the caller's records")
+        record = self.deformation_records(instances) if own_stats else (stats or None)
+        workspace, need = None, 0
+        if record is not None:
+            need = L.flow2d_node_strain_robust_workspace_bytes(nw, nh, instances)
+            cached = getattr(self, "_node_strain_robust_workspace", None)
+            if cached is None or cached[0] < need:
+                if cached is not None:
+                    cached[1].free()
+                    self._planes.remove(cached[1])
+                self._node_strain_robust_workspace = cached = (need, self.plane(max(need // 4, 4), 1))
+            workspace = cached[1]
+        own = (list(held.values()) if own_planes else []) + (list(held_diag.values()) if own_diagnostics else [])
+        try:
+            _check(L.flow2d_node_strain_robust_2d(self.handle, node_u.ptr, node_v.ptr, state.ptr if state is not None else None, nw, nh,
+                                                  node_u.pitch, int(spacing), int(window), int(order), int(min_nodes), int(min_state),
+                                                  int(measure), float(sigma), int(iterations), C.byref(out), C.byref(diag),
+                                                  record.ptr if record is not None else None, workspace.ptr if workspace else None, need),
+                   "flow2d_node_strain_robust_2d")
+            result = {name: q.download(nw, nh) for name, q in held.items()} if own_planes else dict(held)
+            result.update({name: q.download(nw, nh) for name, q in held_diag.items()} if own_diagnostics else held_diag)
+            return result, (self.read_deformation_stats(record, 1)[0] if own_stats else None)
+        finally:
+            for q in own + ([record] if own_stats else []):
+                q.free()
+                self._planes.remove(q)
+
     def resample_x(self, src, dst, out_w, out_h, in_w):
         _check(hip_lib().flow2d_resample_x(self.handle, src.ptr, dst.ptr, out_w, out_h, in_w, src.pitch),
                "flow2d_resample_x")
@@ -2052,6 +2128,10 @@ def host_lib():
             L.flow2d_host_strain_options_ok.argtypes = [i, i, i, i, i]
             L.flow2d_host_node_strain_device.argtypes = [vp, C.POINTER(vp), i, sz, sz, i, i, i, i, i, i, C.POINTER(vp), ds]
             L.flow2d_host_node_strain.argtypes = [vp, C.POINTER(fp), i, sz, sz, i, i, i, i, i, i, C.POINTER(fp), ds]
+        if hasattr(L, "flow2d_host_set_strain_robust"):
+            L.flow2d_host_strain_robust_options_ok.argtypes = [i, i, i, i, i, C.c_float, i]
+            L.flow2d_host_set_strain_robust.argtypes = [vp, C.c_float, i]
+            L.flow2d_host_set_strain_diagnostics.argtypes = [vp, C.POINTER(vp), i]
         if hasattr(L, "flow2d_host_correlate"):
             cr = C.POINTER(CorrelationRecord)
             L.flow2d_host_correlation_args_ok.argtypes = [sz, sz, f, f, i, i, i, f]
@@ -2945,17 +3025,33 @@ class OpticalFlow:
     NODE_PLANES = ("u", "v", "ux", "uy", "vx", "vy", "state")  # what node_strain* read of a step's SUBSET_PLANES
 
     @staticmethod
-    def strain_options_ok(window=2, order=1, min_nodes=0, min_state=1, measure=STRAIN_SMALL):
+    def strain_options_ok(window=2, order=1, min_nodes=0, min_state=1, measure=STRAIN_SMALL, sigma=0.0, iterations=8):
         """OpticalFlow2D::StrainOptionsOk: whether node_strain* accept the options.  Needs no device."""
-        return bool(host_lib().flow2d_host_strain_options_ok(int(window), int(order), int(min_nodes), int(min_state), int(measure)))
+        if sigma == 0.0:
+            return bool(host_lib().flow2d_host_strain_options_ok(int(window), int(order), int(min_nodes), int(min_state), int(measure)))
+        return bool(host_lib().flow2d_host_strain_robust_options_ok(int(window), int(order), int(min_nodes), int(min_state), int(measure),
+                                                                    float(sigma), int(iterations)))
+
+    def _set_strain_robust(self, sigma, iterations, diagnostics, steps):
+        """The robust scale and passes of the node-strain call that follows, and its diagnostic planes (3 * steps pointers or None)."""
+        L = host_lib()
+        if L.flow2d_host_set_strain_robust(self.handle, float(sigma), int(iterations)):
+            raise ValueError("node_strain: sigma is finite and >= 0 (0 = off), iterations 0 .. %d" % NODE_STRAIN_MAX_ITERATIONS)
+        if diagnostics is not None and sigma == 0.0:
+            raise ValueError("node_strain: the diagnostic planes go with sigma > 0")
+        L.flow2d_host_set_strain_diagnostics(self.handle, (C.c_void_p * len(diagnostics))(*diagnostics) if diagnostics else None,
+                                             steps if diagnostics else 0)
 
     def node_strain(self, nodes, spacing, window=2, order=1, min_nodes=0, min_state=1, measure=STRAIN_SMALL, planes=DEFORMATION_PLANES,
-                    stats=True):
+                    stats=True, sigma=0.0, iterations=8, diagnostics=()):
         """OpticalFlow2D::NodeStrain: strain on the node grid (flow2d_node_strain_2d) of one result -- the dict of [nh, nw] arrays
         by the names of SUBSET_PLANES that correlate_subset returns; u and v are needed, the gradients only with window 0, without a
         state every finite node is usable -- or of the list of steps that correlate_subset_sequence returns.  `window` nodes around
         each node are fitted by a polynomial of `order` (0: the node's own gradients); min_nodes 0 = one more than the fit has
-        coefficients.  Returns ({name: [nh, nw] array} for `planes`, DeformationStats or None), or the list of those per step."""
+        coefficients.  sigma > 0: the robust fit (flow2d_node_strain_robust_2d) with `iterations` reweighted passes; diagnostics --
+        names of NODE_STRAIN_DIAGNOSTICS -- then come back in the dict beside the planes, and node_strain_robust_counts reads the
+        record's further words.  Returns ({name: [nh, nw] array} for `planes`, DeformationStats or None), or the list of those per
+        step."""
         single = isinstance(nodes, dict)
         steps = [nodes] if single else list(nodes)
         if not steps or any("u" not in q or "v" not in q for q in steps):
@@ -2974,6 +3070,12 @@ class OpticalFlow:
                         raise ValueError("node_strain: the node images are not %d x %d" % (nw, nh))
                 given.append(a)
         out = [np.empty((nh, nw), np.float32) if name in planes else None for _ in steps for name in DEFORMATION_PLANES]
+        unknown = [name for name in diagnostics if name not in NODE_STRAIN_DIAGNOSTICS]
+        if unknown:
+            raise ValueError("node strain diagnostics are %s, not %s" % (", ".join(NODE_STRAIN_DIAGNOSTICS), unknown))
+        diag = [np.empty((nh, nw), np.float32) if name in diagnostics else None for _ in steps for name in NODE_STRAIN_DIAGNOSTICS]
+        self._set_strain_robust(sigma, iterations, [a.ctypes.data if a is not None else None for a in diag] if diagnostics else None,
+                                len(steps))
         fpp = C.POINTER(C.c_float)
         recs = (DeformationStats * len(steps))()
         rc = host_lib().flow2d_host_node_strain(self.handle, (fpp * len(given))(*[_opt_fptr(a) for a in given]), len(steps), nw, nh,
@@ -2984,14 +3086,18 @@ class OpticalFlow:
             raise Flow2DError(rc, "OpticalFlow2D::NodeStrain")
         per_step = [({name: out[9 * k + c] for c, name in enumerate(DEFORMATION_PLANES) if name in planes}, recs[k] if stats else None)
                     for k in range(len(steps))]
+        for k, (got, _) in enumerate(per_step):
+            got.update({name: diag[3 * k + c] for c, name in enumerate(NODE_STRAIN_DIAGNOSTICS) if name in diagnostics})
         return per_step[0] if single else per_step
 
     def node_strain_device(self, dev_nodes, nw, nh, spacing, window=2, order=1, min_nodes=0, min_state=1, measure=STRAIN_SMALL,
-                           dev_planes=None, stats=True):
+                           dev_planes=None, stats=True, sigma=0.0, iterations=8, diagnostics=None):
         """OpticalFlow2D::NodeStrainDevice: dev_nodes -- a dict of device planes of the container's size by the names of
         SUBSET_PLANES (as refine_nodes_device / correlate_subset*_device wrote them), or a list of them, one per step; dev_planes --
         a dict of device planes by the names of DEFORMATION_PLANES (or a list, one per step), which stay on the device.  Returns the
-        DeformationStats (a list for a list) -- the call then synchronises once -- or, without stats, None (it only queues)."""
+        DeformationStats (a list for a list) -- the call then synchronises once -- or, without stats, None (it only queues).
+        sigma > 0: the robust fit; diagnostics -- a dict of device planes by the names of NODE_STRAIN_DIAGNOSTICS (or a list, one
+        per step), which stay on the device."""
         single = isinstance(dev_nodes, dict)
         steps = [dev_nodes] if single else list(dev_nodes)
         outs = [dev_planes] if single or dev_planes is None else list(dev_planes)
@@ -3002,6 +3108,14 @@ class OpticalFlow:
             raise ValueError("deformation planes are %s, not %s" % (", ".join(DEFORMATION_PLANES), unknown))
         flat = [q.get(name) for q in steps for name in self.NODE_PLANES]
         wanted = [q.get(name) for q in outs for name in DEFORMATION_PLANES] if dev_planes is not None else None
+        diags = None if diagnostics is None else ([diagnostics] if single else list(diagnostics))
+        if diags is not None and len(diags) != len(steps):
+            raise ValueError("node_strain_device takes one set of diagnostic planes per step")
+        unknown = [name for q in diags or () for name in q if name not in NODE_STRAIN_DIAGNOSTICS]
+        if unknown:
+            raise ValueError("node strain diagnostics are %s, not %s" % (", ".join(NODE_STRAIN_DIAGNOSTICS), unknown))
+        self._set_strain_robust(sigma, iterations, [q.get(name) for q in diags for name in NODE_STRAIN_DIAGNOSTICS] if diags else None,
+                                len(steps))
         recs = (DeformationStats * len(steps))()
         rc = host_lib().flow2d_host_node_strain_device(self.handle, (C.c_void_p * len(flat))(*flat), len(steps), nw, nh, int(spacing),
                                                        int(window), int(order), int(min_nodes), int(min_state), int(measure),

@@ -1,5 +1,6 @@
 // C facade over the C++ host layer, for the Python tests and bench.py (plumbing only).
 // It drives the same OpticalFlow2D / OperationParameters objects a C++ caller would.
+#include <cmath>
 #include <cstdint>
 #include <cstring>
 #include <deque>
@@ -35,6 +36,9 @@ struct flow2d_host_flow {
     int subset_interpolation = OpticalFlow2D::SubsetOptions::CatmullRom;  // flow2d_host_set_subset_interpolation
     bool subset_mask_search = false;                                      // flow2d_host_set_subset_mask_search
     int reference_every = 0;                                              // flow2d_host_set_reference_every
+    float strain_sigma = 0.f;                                             // flow2d_host_set_strain_robust
+    int strain_iterations = 8;
+    std::vector<void*> strain_diagnostics;  // flow2d_host_set_strain_diagnostics: of the next node-strain call, which forgets them
     std::vector<flow2d_compose_record> compose_records;                   // of the last sequence call: flow2d_host_compose_records
 };
 
@@ -1221,7 +1225,10 @@ HOST_API int flow2d_host_correlate_subset_sequence(flow2d_host_flow* h, const fl
 
 // ---- strain on the node grid ---------------------------------------------------------------------------------------------------
 namespace {
-OpticalFlow2D::StrainOptions strain_options(int window, int order, int min_nodes, int min_state, int measure)
+// The entries below were there before the robust fit, and their argument lists stay: its scale and passes travel beside them, kept
+// in the object by flow2d_host_set_strain_robust, and the diagnostic planes of the next call by flow2d_host_set_strain_diagnostics.
+OpticalFlow2D::StrainOptions strain_options(int window, int order, int min_nodes, int min_state, int measure,
+                                            const flow2d_host_flow* h = nullptr)
 {
     OpticalFlow2D::StrainOptions o;
     o.window = window;
@@ -1229,9 +1236,53 @@ OpticalFlow2D::StrainOptions strain_options(int window, int order, int min_nodes
     o.min_nodes = min_nodes;
     o.min_state = min_state;
     o.measure = measure;
+    if (h) {
+        o.robust_sigma = h->strain_sigma;
+        o.robust_iterations = h->strain_iterations;
+    }
     return o;
 }
+
+// The diagnostic planes handed in for this call (three per step, or none), taken out of the object.
+std::vector<void*> take_diagnostics(flow2d_host_flow* h, size_t step_count, bool& ok)
+{
+    std::vector<void*> given;
+    given.swap(h->strain_diagnostics);
+    ok = given.empty() || given.size() == 3 * step_count;
+    return given;
+}
 }  // namespace
+
+// OpticalFlow2D::StrainOptionsOk with the robust fields.  Needs no device.
+HOST_API int flow2d_host_strain_robust_options_ok(int window, int order, int min_nodes, int min_state, int measure, float sigma,
+                                                  int iterations)
+{
+    auto o = strain_options(window, order, min_nodes, min_state, measure);
+    o.robust_sigma = sigma;
+    o.robust_iterations = iterations;
+    return OpticalFlow2D::StrainOptionsOk(o) ? 1 : 0;
+}
+
+// StrainOptions::robust_sigma and robust_iterations of the node-strain calls that follow; sigma 0 = the plain fit (the default).
+// 1 for a scale that is negative or not finite, or iterations outside 0 .. FLOW2D_NODE_STRAIN_MAX_ITERATIONS.
+HOST_API int flow2d_host_set_strain_robust(flow2d_host_flow* h, float sigma, int iterations)
+{
+    if (!h || !(std::isfinite(sigma) && sigma >= 0.f) || iterations < 0 || iterations > FLOW2D_NODE_STRAIN_MAX_ITERATIONS) return 1;
+    h->strain_sigma = sigma;
+    h->strain_iterations = iterations;
+    return 0;
+}
+
+// The diagnostic planes of the NEXT flow2d_host_node_strain (tight host arrays of nw * nh floats) or
+// flow2d_host_node_strain_device (device planes) call: three per step -- residual, rejected, centre --, each optional; that call
+// must have `steps` steps and a robust scale, and forgets them.  planes == NULL or steps == 0 withdraws them.
+HOST_API int flow2d_host_set_strain_diagnostics(flow2d_host_flow* h, void* const* planes, int steps)
+{
+    if (!h || steps < 0) return 1;
+    h->strain_diagnostics.clear();
+    if (planes && steps > 0) h->strain_diagnostics.assign(planes, planes + 3 * static_cast<size_t>(steps));
+    return 0;
+}
 
 // OpticalFlow2D::StrainOptionsOk.  Needs no device.
 HOST_API int flow2d_host_strain_options_ok(int window, int order, int min_nodes, int min_state, int measure)
@@ -1246,9 +1297,15 @@ HOST_API int flow2d_host_node_strain_device(flow2d_host_flow* h, void* const* de
                                             int window, int order, int min_nodes, int min_state, int measure, void* const* dev_planes,
                                             flow2d_deformation_stats* stats)
 {
-    const auto strain = strain_options(window, order, min_nodes, min_state, measure);
-    if (!h || !dev_nodes || steps < 1 || (!dev_planes && !stats) || !OpticalFlow2D::StrainOptionsOk(strain)) return 1;
+    const auto strain = strain_options(window, order, min_nodes, min_state, measure, h);
+    if (!h) return 1;
+    bool diagnostics_ok = false;
+    const std::vector<void*> given_diagnostics = take_diagnostics(h, steps < 1 ? 0 : static_cast<size_t>(steps), diagnostics_ok);
+    if (!diagnostics_ok || (!given_diagnostics.empty() && strain.robust_sigma == 0.f)) return 1;
+    if (!dev_nodes || steps < 1 || (!dev_planes && !stats && given_diagnostics.empty()) || !OpticalFlow2D::StrainOptionsOk(strain)) return 1;
     const size_t step_count = static_cast<size_t>(steps);
+    std::vector<DevicePtr> diagnostics;
+    for (void* q : given_diagnostics) diagnostics.push_back(dp(q));
     std::vector<OpticalFlow2D::SubsetPlanes> fields(step_count);
     std::vector<DevicePtr> planes(9 * step_count, 0);
     for (size_t k = 0; k < step_count; ++k) {
@@ -1258,7 +1315,10 @@ HOST_API int flow2d_host_node_strain_device(flow2d_host_flow* h, void* const* de
         for (int c = 0; dev_planes && c < 9; ++c) planes[9 * k + c] = dp(dev_planes[9 * k + c]);
     }
     h->flow.timing_mode = 0;
-    return h->flow.NodeStrainDevice(fields.data(), step_count, nw, nh, spacing, strain, dev_planes ? planes.data() : nullptr, stats) ? 0 : 2;
+    return h->flow.NodeStrainDevice(fields.data(), step_count, nw, nh, spacing, strain, dev_planes ? planes.data() : nullptr, stats,
+                                    diagnostics.empty() ? nullptr : diagnostics.data())
+               ? 0
+               : 2;
 }
 
 // OpticalFlow2D::NodeStrain on tight host arrays of nw * nh floats: nodes -- seven per step, planes -- nine per step, as above.
@@ -1266,12 +1326,23 @@ HOST_API int flow2d_host_node_strain(flow2d_host_flow* h, const float* const* no
                                      int order, int min_nodes, int min_state, int measure, float* const* planes,
                                      flow2d_deformation_stats* stats)
 {
-    const auto strain = strain_options(window, order, min_nodes, min_state, measure);
-    if (!h || !nodes || steps < 1 || nw == 0 || nh == 0 || (!planes && !stats) || !OpticalFlow2D::StrainOptionsOk(strain)) return 1;
+    const auto strain = strain_options(window, order, min_nodes, min_state, measure, h);
+    if (!h) return 1;
+    bool diagnostics_ok = false;
+    const std::vector<void*> diagnostics = take_diagnostics(h, steps < 1 ? 0 : static_cast<size_t>(steps), diagnostics_ok);
+    if (!diagnostics_ok || (!diagnostics.empty() && strain.robust_sigma == 0.f)) return 1;
+    if (!nodes || steps < 1 || nw == 0 || nh == 0 || (!planes && !stats && diagnostics.empty()) || !OpticalFlow2D::StrainOptionsOk(strain))
+        return 1;
     const size_t step_count = static_cast<size_t>(steps);
-    std::vector<Data2D> in, out;
+    std::vector<Data2D> in, out, diag;
     in.reserve(7 * step_count);
     out.reserve(9 * step_count);
+    diag.reserve(3 * step_count);
+    std::vector<Data2D*> wanted_diagnostics(diagnostics.size(), nullptr);
+    for (size_t k = 0; k < diagnostics.size(); ++k) {
+        diag.emplace_back(nw, nh);
+        if (diagnostics[k]) wanted_diagnostics[k] = &diag[k];
+    }
     std::vector<Data2D*> given(7 * step_count, nullptr), wanted(9 * step_count, nullptr);
     for (size_t k = 0; k < 7 * step_count; ++k) {
         in.emplace_back(nw, nh);
@@ -1285,8 +1356,11 @@ HOST_API int flow2d_host_node_strain(flow2d_host_flow* h, const float* const* no
     }
     for (size_t k = 0; k < step_count; ++k)
         if (!given[7 * k] || !given[7 * k + 1]) return 1;
-    h->flow.NodeStrain(given.data(), step_count, spacing, strain, planes ? wanted.data() : nullptr, stats);
+    h->flow.NodeStrain(given.data(), step_count, spacing, strain, planes ? wanted.data() : nullptr, stats,
+                       diagnostics.empty() ? nullptr : wanted_diagnostics.data());
     if (!h->flow.LastRunSucceeded()) return 2;
+    for (size_t k = 0; k < diagnostics.size(); ++k)
+        if (diagnostics[k]) std::memcpy(diagnostics[k], diag[k].DataPtr(), nw * nh * sizeof(float));
     for (size_t k = 0; planes && k < 9 * step_count; ++k)
         if (planes[k]) std::memcpy(planes[k], out[k].DataPtr(), nw * nh * sizeof(float));
     return 0;

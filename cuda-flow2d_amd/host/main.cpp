@@ -93,6 +93,12 @@
 // --correlation-passes alone and M >= 1, of the search's nodes, every finite one usable.  --strain small|green selects the measure.
 // node-divergence, node-vorticity, node-dilatation, node-exx, node-eyy, node-exy, node-e1, node-e2 and node-max-shear are written
 // beside the node files, and the record is printed as "NodeStrain: {...}".
+// --strain-sigma S (pixels, finite and > 0) [--strain-iterations K, 0 .. 16, default 8], with --subset-strain M and M >= 1, makes the
+// window fit the robust one (flow2d_node_strain_robust_2d): K reweighted passes with a Cauchy weight of scale S, so that a node
+// which converged to a wrong place does not bend the windows that hold it.  node-strain-residual, node-strain-rejected and
+// node-strain-centre are written beside the nine files and one more line, "NodeStrainRobust: {json}" -- "sigma", "iterations" and
+// the record's "touched" (nodes that rejected a tap), "rejected" (taps) and "suspect" (nodes whose own tap was not kept) -- is
+// printed behind "NodeStrain:", which keeps its format.  Without the option nothing changes.
 // --subset-previous PREFIX [--subset-fill F, 1 .. 4, default 2] [--subset-min-state 0|1, default 1] [--subset-predict-neighbours N,
 // 1 .. 8, default 1], valid only together with --subset-refine, is the next step of a loading sequence: FILE_0 is the sequence's
 // reference frame, FILE_1 its current frame, and PREFIXnode-u-NW-NH.raw, -v, -ux, -uy, -vx, -vy and -state are what a --subset-refine
@@ -233,7 +239,8 @@ int main(int argc, char** argv)
     std::string correlation_mask_file;  // --correlation-mask FILE, --correlation-mask-invert, --correlation-min-pixels N
     bool correlation_mask_invert = false, correlation_mask_option = false;
     int correlation_min_pixels = 0;
-    OpticalFlow2D::StrainOptions node_strain;  // --subset-strain M and --strain-order, --strain-min-nodes
+    OpticalFlow2D::StrainOptions node_strain;  // --subset-strain M and --strain-order, --strain-min-nodes, --strain-sigma, --strain-iterations
+    bool strain_iterations_given = false;
     bool subset_strain = false, strain_option = false;
     OpticalFlow2D::ValidationOptions validation;                     // --validate-threshold / -epsilon / -min-neighbours / -flag-only
     bool validate_option = false;
@@ -599,6 +606,27 @@ int main(int argc, char** argv)
             (window ? subset_strain : strain_option) = true;
             ++i;
         }
+        else if (!std::strcmp(argv[i], "--strain-sigma")) {
+            char* end = nullptr;
+            const float sigma = (i + 1 < argc) ? std::strtof(argv[i + 1], &end) : 0.f;
+            if (i + 1 >= argc || end == argv[i + 1] || *end != '\0' || !(std::isfinite(sigma) && sigma > 0.f)) {
+                std::printf("--strain-sigma takes the scale of the robust weight in pixels: finite and above 0.\n");
+                return 5;
+            }
+            node_strain.robust_sigma = sigma;
+            ++i;
+        }
+        else if (!std::strcmp(argv[i], "--strain-iterations")) {
+            char* end = nullptr;
+            const long n = (i + 1 < argc) ? std::strtol(argv[i + 1], &end, 10) : -1;
+            if (i + 1 >= argc || end == argv[i + 1] || *end != '\0' || n < 0 || n > FLOW2D_NODE_STRAIN_MAX_ITERATIONS) {
+                std::printf("--strain-iterations takes an integer of 0 .. %d.\n", FLOW2D_NODE_STRAIN_MAX_ITERATIONS);
+                return 5;
+            }
+            node_strain.robust_iterations = static_cast<int>(n);
+            strain_iterations_given = true;
+            ++i;
+        }
         else if (!std::strcmp(argv[i], "--subset-fill") || !std::strcmp(argv[i], "--subset-min-state") ||
                  !std::strcmp(argv[i], "--subset-predict-neighbours")) {
             const bool fill = !std::strcmp(argv[i], "--subset-fill"), state = !std::strcmp(argv[i], "--subset-min-state");
@@ -724,6 +752,14 @@ int main(int argc, char** argv)
 
     if (strain_option && !subset_strain) {
         std::printf("--strain-order and --strain-min-nodes belong to --subset-strain M.\n");
+        return 5;
+    }
+    if (strain_iterations_given && node_strain.robust_sigma == 0.f) {
+        std::printf("--strain-iterations belongs to --strain-sigma S.\n");
+        return 5;
+    }
+    if (node_strain.robust_sigma != 0.f && (!subset_strain || node_strain.window == 0)) {
+        std::printf("--strain-sigma S reweights a strain window: it goes with --subset-strain M, M >= 1.\n");
         return 5;
     }
     if (subset_strain && !(subset_refine || multipass || method == Methods::Correlation)) {
@@ -944,13 +980,20 @@ int main(int argc, char** argv)
                                     "node-e2", "node-max-shear"};
             std::vector<Data2D> images;
             for (int k = 0; k < 9; ++k) images.emplace_back(nw, nh);
+            const bool robust = node_strain.robust_sigma != 0.f;
+            const char* diagnostic_names[3] = {"node-strain-residual", "node-strain-rejected", "node-strain-centre"};
+            for (int k = 0; robust && k < 3; ++k) images.emplace_back(nw, nh);
             Data2D* planes[9];
+            Data2D* diagnostics[3];
             for (int k = 0; k < 9; ++k) planes[k] = &images[k];
+            for (int k = 0; robust && k < 3; ++k) diagnostics[k] = &images[9 + k];
             flow2d_deformation_stats stats = {};
-            optical_flow.NodeStrain(fields, 1, spacing, node_strain, planes, &stats);
+            optical_flow.NodeStrain(fields, 1, spacing, node_strain, planes, &stats, robust ? diagnostics : nullptr);
             if (!optical_flow.LastRunSucceeded()) return;
             const std::string size = "-" + std::to_string(nw) + "-" + std::to_string(nh) + ".raw";
             for (int k = 0; k < 9; ++k) images[k].WriteRAWToFileF32((output_path + counter + names[k] + size).c_str());
+            for (int k = 0; robust && k < 3; ++k)
+                images[9 + k].WriteRAWToFileF32((output_path + counter + diagnostic_names[k] + size).c_str());
             std::printf("NodeStrain: {\"window\": %d, \"order\": %d, \"min_nodes\": %d, \"min_state\": %d, \"measure\": \"%s\", "
                         "\"spacing\": %d, \"nw\": %zu, \"nh\": %zu, \"valid\": %llu, \"invalid\": %llu, \"centre\": %llu, "
                         "\"sparse\": %llu, \"degenerate\": %llu",
@@ -964,6 +1007,11 @@ int main(int argc, char** argv)
                 std::printf(", \"%s\": {\"sum\": %.17g, \"sum_sq\": %.17g, \"min\": %.9g, \"max\": %.9g}", quantity[k], moments[k]->sum,
                             moments[k]->sum_sq, moments[k]->min, moments[k]->max);
             std::printf("}\n");
+            if (robust)
+                std::printf("NodeStrainRobust: {\"sigma\": %.9g, \"iterations\": %d, \"touched\": %llu, \"rejected\": %llu, "
+                            "\"suspect\": %llu}\n",
+                            static_cast<double>(node_strain.robust_sigma), node_strain.robust_iterations, stats.reserved[3],
+                            stats.reserved[4], stats.reserved[5]);
         };
         if (subset_refine) {
             std::vector<OpticalFlow2D::CorrelationPass> schedule = correlation_passes;

@@ -500,8 +500,14 @@ public:
     // gradients a refinement delivered (window 0) or from a polynomial of `order` fitted by least squares to the usable nodes
     // within `window` nodes around each node (Pan et al. 2009); nodes below min_state, and nodes that are not finite, are left
     // out of every fit.  min_nodes: the fewest usable nodes a window may hold, 0 = one more than the fit has coefficients.
+    // robust_sigma > 0 (pixels; with a window of 1 or more) makes the fit the reweighted one of flow2d_node_strain_robust_2d:
+    // robust_iterations passes with a Cauchy weight of that scale, taps further than it from the last fit not kept, a window
+    // that keeps fewer than min_nodes sparse.  8 passes are what an order-2 fit at m = 2 needs; order 1 settles within 4
+    // (profiles/robust_strain/README.md).  0 = off: the plain entry, the iterations are not looked at.
     struct StrainOptions {
         int window = 2, order = 1, min_nodes = 0 /* 0: k + 1 */, min_state = 1, measure = FLOW2D_STRAIN_SMALL;
+        float robust_sigma = 0.f;
+        int robust_iterations = 8;
     };
     // prints what is wrong; needs no device
     static bool StrainOptionsOk(const StrainOptions& strain);
@@ -512,12 +518,15 @@ public:
     // 0 = not wanted (the array may be null when stats_out is given); stats_out (host, optional): step_count records.  One launch
     // pair per step; the records and the workspace are allocated at the first use and kept; the call synchronises once, at the
     // end, and only when stats_out is given.  Not for lock-step groups.
+    // diagnostics (optional, with robust_sigma > 0 only): three device planes per step -- residual, rejected, centre of
+    // flow2d_node_strain_diagnostics --, 0 = not wanted; they count as wanted planes.  The records then carry reserved[3 .. 5].
     bool NodeStrainDevice(const SubsetPlanes* steps, size_t step_count, size_t nw, size_t nh, int spacing, const StrainOptions& strain,
-                          const DevicePtr* out_planes, flow2d_deformation_stats* stats_out);
+                          const DevicePtr* out_planes, flow2d_deformation_stats* stats_out, const DevicePtr* diagnostics = nullptr);
     // The host-image form: nodes[7 * k + 0 .. 6] -- u, v, ux, uy, vx, vy, state of step k, images of the nw x nh grid, of which u and
     // v are needed -- and planes[9 * k + 0 .. 8], images of the grid, null = not wanted.
+    // diagnostics[3 * k + 0 .. 2] (optional, with robust_sigma > 0 only): images of the grid, null = not wanted.
     void NodeStrain(Data2D* const* nodes, size_t step_count, int spacing, const StrainOptions& strain, Data2D* const* planes,
-                    flow2d_deformation_stats* stats_out);
+                    flow2d_deformation_stats* stats_out, Data2D* const* diagnostics = nullptr);
 
     // The pyramid started from a prior flow instead of from zero at the coarsest level (no reference counterpart; Brox & Malik's
     // large-displacement flow and the predictor-corrector passes of PIV start the variational solver from matches in the same

@@ -1189,8 +1189,17 @@ bool OpticalFlow2D::StrainOptionsOk(const StrainOptions& strain)
     if (strain.window >= 0 && strain.window <= FLOW2D_NODE_STRAIN_MAX_WINDOW && (strain.min_state == 0 || strain.min_state == 1) &&
         (strain.measure == FLOW2D_STRAIN_SMALL || strain.measure == FLOW2D_STRAIN_GREEN_LAGRANGE) &&
         (strain.window == 0 ||
-         ((strain.order == 1 || strain.order == 2) && (strain.min_nodes == 0 || (strain.min_nodes >= k && strain.min_nodes <= side * side)))))
-        return true;
+         ((strain.order == 1 || strain.order == 2) && (strain.min_nodes == 0 || (strain.min_nodes >= k && strain.min_nodes <= side * side))))) {
+        // robust_sigma 0 is the plain fit; anything else has to be a scale the robust entry takes, with a window to reweight
+        if (strain.robust_sigma == 0.f) return true;
+        if (std::isfinite(strain.robust_sigma) && strain.robust_sigma > 0.f && strain.window >= 1 && strain.robust_iterations >= 0 &&
+            strain.robust_iterations <= FLOW2D_NODE_STRAIN_MAX_ITERATIONS)
+            return true;
+        std::printf("Error: robust node strain takes a scale that is finite and positive (%g), a window of 1 or more nodes (%d) and "
+                    "0 .. %d reweighted passes (%d).\n",
+                    static_cast<double>(strain.robust_sigma), strain.window, FLOW2D_NODE_STRAIN_MAX_ITERATIONS, strain.robust_iterations);
+        return false;
+    }
     std::printf("Error: node strain takes a window of 0 .. %d nodes (%d), with a window an order of 1 or 2 (%d) and a least node count "
                 "of 0 or between the fit's coefficients and the window's nodes (%d), a least state of 0 or 1 (%d) and a measure of 0 or "
                 "1 (%d).\n",
@@ -1199,11 +1208,17 @@ bool OpticalFlow2D::StrainOptionsOk(const StrainOptions& strain)
 }
 
 bool OpticalFlow2D::NodeStrainDevice(const SubsetPlanes* steps, size_t step_count, size_t nw, size_t nh, int spacing,
-                                     const StrainOptions& strain, const DevicePtr* out_planes, flow2d_deformation_stats* stats_out)
+                                     const StrainOptions& strain, const DevicePtr* out_planes, flow2d_deformation_stats* stats_out,
+                                     const DevicePtr* diagnostics)
 {
     const size_t W = dev_container_size_.width, H = dev_container_size_.height, pitch = dev_container_size_.pitch;
     if (!StrainOptionsOk(strain)) return false;
-    if (!IsInitialized() || !steps || step_count == 0 || (!out_planes && !stats_out)) return false;
+    const bool robust = strain.robust_sigma != 0.f;
+    if (diagnostics && !robust) {
+        std::printf("Error: '%s': the diagnostic planes of node strain go with a robust scale.\n", GetName());
+        return false;
+    }
+    if (!IsInitialized() || !steps || step_count == 0 || (!out_planes && !stats_out && !diagnostics)) return false;
     if (nw == 0 || nh == 0 || nw > W || nh > H) {
         std::printf("Error: '%s': a %zu x %zu node grid does not lie in planes of %zu x %zu.\n", GetName(), nw, nh, W, H);
         return false;
@@ -1220,7 +1235,8 @@ bool OpticalFlow2D::NodeStrainDevice(const SubsetPlanes* steps, size_t step_coun
         }
     }
     const int min_nodes = strain.window > 0 && strain.min_nodes == 0 ? (strain.order == 2 ? 6 : 3) + 1 : strain.min_nodes;
-    const size_t workspace_bytes = stats_out ? flow2d_node_strain_workspace_bytes(nw, nh, 1) : 0;
+    const size_t workspace_bytes =
+        !stats_out ? 0 : robust ? flow2d_node_strain_robust_workspace_bytes(nw, nh, 1) : flow2d_node_strain_workspace_bytes(nw, nh, 1);
     const size_t per_step = sizeof(flow2d_deformation_stats) + workspace_bytes;
     if (stats_out && !strain_scratch_.Ensure(context_, step_count * per_step)) return false;
     auto plane = [](DevicePtr p) { return p ? AsPlane(p) : nullptr; };
@@ -1235,6 +1251,17 @@ bool OpticalFlow2D::NodeStrainDevice(const SubsetPlanes* steps, size_t step_coun
         auto* record = stats_out ? strain_scratch_.At<flow2d_deformation_stats>(k * per_step) : nullptr;
         void* workspace = stats_out ? strain_scratch_.At<>(k * per_step + sizeof(flow2d_deformation_stats)) : nullptr;
         // (the node planes are containers: the frames' pitch; the entry refuses planes that meet)
+        if (robust) {
+            flow2d_node_strain_diagnostics diag = {};
+            if (diagnostics) diag = {plane(diagnostics[3 * k]), plane(diagnostics[3 * k + 1]), plane(diagnostics[3 * k + 2])};
+            ok = !CheckFlow2DError(flow2d_node_strain_robust_2d(context_, AsPlane(q.u), AsPlane(q.v), plane(q.state), nw, nh, pitch, spacing,
+                                                                strain.window, strain.order, min_nodes, strain.min_state, strain.measure,
+                                                                strain.robust_sigma, strain.robust_iterations, &out, &diag, record,
+                                                                workspace, workspace_bytes),
+                                   "flow2d_node_strain_robust_2d");
+            if (ok && stats_out) ok = ReadRecord(stats_out + k, record, sizeof(*record));
+            continue;
+        }
         ok = !CheckFlow2DError(flow2d_node_strain_2d(context_, AsPlane(q.u), AsPlane(q.v), plane(q.state), plane(q.ux), plane(q.uy),
                                                      plane(q.vx), plane(q.vy), nw, nh, pitch, spacing, strain.window, strain.order,
                                                      min_nodes, strain.min_state, strain.measure, &out, record, workspace, workspace_bytes),
@@ -1246,10 +1273,11 @@ bool OpticalFlow2D::NodeStrainDevice(const SubsetPlanes* steps, size_t step_coun
 }
 
 void OpticalFlow2D::NodeStrain(Data2D* const* nodes, size_t step_count, int spacing, const StrainOptions& strain, Data2D* const* planes,
-                               flow2d_deformation_stats* stats_out)
+                               flow2d_deformation_stats* stats_out, Data2D* const* diagnostics)
 {
     last_run_ok_ = false;
-    if (!IsInitialized() || !nodes || step_count == 0 || !nodes[0] || (!planes && !stats_out) || !StrainOptionsOk(strain)) return;
+    if (!IsInitialized() || !nodes || step_count == 0 || !nodes[0] || (!planes && !stats_out && !diagnostics) || !StrainOptionsOk(strain))
+        return;
     const size_t nw = nodes[0]->Width(), nh = nodes[0]->Height(), H = dev_container_size_.height;
     if (nw == 0 || nh == 0 || nw > dev_container_size_.width || nh > H) {
         std::printf("Error: '%s': a %zu x %zu node grid does not lie in planes of %zu x %zu.\n", GetName(), nw, nh,
@@ -1258,8 +1286,10 @@ void OpticalFlow2D::NodeStrain(Data2D* const* nodes, size_t step_count, int spac
     }
     for (size_t k = 0; k < step_count; ++k) {
         if (!nodes[7 * k] || !nodes[7 * k + 1]) return;
-        for (int c = 0; c < 16; ++c) {
-            Data2D* image = c < 7 ? nodes[7 * k + c] : (planes ? planes[9 * k + c - 7] : nullptr);
+        for (int c = 0; c < 19; ++c) {
+            Data2D* image = c < 7    ? nodes[7 * k + c]
+                            : c < 16 ? (planes ? planes[9 * k + c - 7] : nullptr)
+                                     : (diagnostics ? diagnostics[3 * k + c - 16] : nullptr);
             if (image && (image->Width() != nw || image->Height() != nh)) {
                 std::printf("Error: '%s': the node images are not %zu x %zu.\n", GetName(), nw, nh);
                 return;
@@ -1272,6 +1302,8 @@ void OpticalFlow2D::NodeStrain(Data2D* const* nodes, size_t step_count, int spac
         for (int c = 0; c < 7; ++c) call_planes.Add(nullptr, CallPlanes::Out, nodes[7 * k + c] != nullptr);
         for (int c = 0; c < 9; ++c) call_planes.Add(nullptr, CallPlanes::Out, planes && planes[9 * k + c] != nullptr);
     }
+    // (the diagnostic planes lie behind every step's sixteen, so that those keep their places)
+    for (size_t k = 0; diagnostics && k < 3 * step_count; ++k) call_planes.Add(nullptr, CallPlanes::Out, diagnostics[k] != nullptr);
     HostCall call(context_, last_total_ms_, call_planes.Allocate());
     const DevicePtr* d = call_planes.data();
     bool ok = call_planes.Upload();
@@ -1284,10 +1316,13 @@ void OpticalFlow2D::NodeStrain(Data2D* const* nodes, size_t step_count, int spac
         steps[k] = {q[0], q[1], q[2], q[3], q[4], q[5], 0, q[6]};
         for (int c = 0; c < 9; ++c) out[9 * k + c] = q[7 + c];
     }
-    ok = ok && NodeStrainDevice(steps.data(), step_count, nw, nh, spacing, strain, planes ? out.data() : nullptr, stats_out);
+    const DevicePtr* diag = diagnostics ? d + 16 * step_count : nullptr;
+    ok = ok && NodeStrainDevice(steps.data(), step_count, nw, nh, spacing, strain, planes ? out.data() : nullptr, stats_out, diag);
     // (without a record the device call only queues: the downloads below are ordered behind it on the stream)
     for (size_t k = 0; ok && planes && k < 9 * step_count; ++k)
         if (planes[k]) ok = CopyData2DFromDevice(out[k], *planes[k], H, dev_container_size_.pitch);
+    for (size_t k = 0; ok && diagnostics && k < 3 * step_count; ++k)
+        if (diagnostics[k]) ok = CopyData2DFromDevice(diag[k], *diagnostics[k], H, dev_container_size_.pitch);
     last_run_ok_ = ok;
 }
 

@@ -54,7 +54,9 @@ extern "C" {
  * deformed frame) and flow2d_context_set_planning_cus / flow2d_context_planning_cus (the CU count the launch planners plan
  * for) with the host-only diagnostics flow2d_fused_block_order_for_cus / flow2d_fused_plan_for_cus /
  * flow2d_stream_rows_for_cus (which plan a CU count gives) and flow2d_correlate_masked_2d / flow2d_validate_nodes_masked_2d (the
- * window search and the median test on a region of interest) were added under 1. */
+ * window search and the median test on a region of interest) and flow2d_node_strain_robust_2d /
+ * flow2d_node_strain_robust_workspace_bytes (the strain windows as reweighted least squares, with diagnostic planes) were added
+ * under 1. */
 #define FLOW2D_ABI_VERSION 1
 
 typedef enum flow2d_status {
@@ -1476,6 +1478,58 @@ FLOW2D_API int flow2d_node_strain_2d(flow2d_context* ctx, const float* node_u, c
                                      const flow2d_deformation_planes* out /* host, may be NULL */,
                                      flow2d_deformation_stats* stats /* device, may be NULL */, void* workspace,
                                      size_t workspace_bytes);
+
+/* Robust strain windows: the window fit of flow2d_node_strain_2d as iteratively reweighted least squares with a Cauchy weight
+ * (Holland & Welsch, Commun. Stat. A6 (1977)), so that a node which was delivered as usable but lies in a wrong place neither
+ * bends the windows that hold it nor goes unnoticed.  Added to ABI version 1 without changing any existing entry.
+ *
+ * Everything flow2d_node_strain_2d defines for m >= 1 holds -- IEEE double, every operation rounded on its own, every test a
+ * positive comparison; the inputs (without the gradient planes, which a window fit does not read), usable nodes, the basis, the
+ * visiting order, wu and wv against the centre, n, *sparse* when !(n >= min_nodes) before anything is factored, the
+ * factorisation, the solves, the quantities, the planes, the record and its reduction -- with these additions.
+ * Inputs in addition.  sigma, a float, finite and > 0, in pixels; s2 = sigma*sigma after converting sigma to double.
+ * K = iterations (0 .. FLOW2D_NODE_STRAIN_MAX_ITERATIONS), the reweighted passes.  window = 0 is refused: the direct form has
+ * nothing to reweight.
+ * Passes t = 0 .. K.  Every tap q (a usable node of the window) carries a weight w_q in double; in pass 0, w_q = 1.
+ *   M[a][b] = sum of w_q * (double)(phi_a*phi_b), the product of the basis formed in int;
+ *   bu[a] = sum of (w_q * (double)phi_a) * wu,  bv[a] likewise;   every term rounded as written, added from 0 in visiting order.
+ * Factor M and solve cu = Solve(bu), cv = Solve(bv) as in flow2d_node_strain_2d; a failed pivot test in any pass makes the node
+ * *degenerate*.  The residuals of the pass, per tap:
+ *   ru = wu - (sum over a ascending, from 0, of cu[a]*(double)phi_a),  rv likewise,  r2 = ru*ru + rv*rv;
+ * for t < K the next pass has w_q = s2 / (s2 + r2).  (With every w_q = 1.0 the sums are flow2d_node_strain_2d's: integers below
+ * 2^53 and products by 1.0.  K = 0 with a sigma no residual reaches gives that entry's planes and record.)
+ * After pass K.  A tap is *kept* when r2 <= s2, with the residuals of pass K; kept is their count.  A node with
+ * !(kept >= min_nodes) is *sparse* (the existing reason and counter).  Otherwise a, b, c, d come from cu, cv of pass K as in
+ * flow2d_node_strain_2d.  A node that reached this point -- valid, or sparse by its kept count -- is *finished*.  A finished node
+ * whose own centre tap is not kept is *suspect*; a valid one still gets its strain, which is its neighbours' fit.
+ * Outputs in addition.  `diagnostics` (a HOST struct of three device pointers, may be NULL, each may be NULL): planes on the node
+ * grid like those of `out`, NaN (0x7FC00000) at an invalid node and at a valid one
+ *   residual = (float)sqrt((sum of r2 over the kept taps, from 0 in visiting order) / (double)kept),
+ *   rejected = (float)(n - kept),     centre = (float)sqrt(r2 of the centre tap).
+ * stats[b]: the record of flow2d_node_strain_2d and, counted over the finished nodes, reserved[3] = nodes with n - kept > 0,
+ * reserved[4] = the sum of their rejected taps n - kept, reserved[5] = suspect nodes; the rest 0.  (Not over the valid nodes
+ * alone: a window whose passes lock onto its outlier keeps too few taps and is sparse, and that is the node these words are
+ * there to report; the planes hold NaN there like at every invalid node.)  The same two ordered launches with
+ * slabs of flow2d_node_strain_robust_workspace_bytes: the same bytes alone, in a lock-step batch and under graph replay.
+ * FLOW2D_ERR_INVALID_ARGUMENT, and nothing written, for what flow2d_node_strain_2d refuses (a diagnostic plane counts as a
+ * requested plane: alone it is output enough, and it may overlap neither an input nor another written range), for window = 0,
+ * a sigma that is not finite or <= 0, or iterations outside their limits; FLOW2D_ERR_UNSUPPORTED for 2^31 nodes or more. */
+#define FLOW2D_NODE_STRAIN_MAX_ITERATIONS 16
+typedef struct flow2d_node_strain_diagnostics {
+    float* residual; /* RMS residual of the kept taps, pixels */
+    float* rejected; /* usable taps of the window that were not kept */
+    float* centre;   /* the node's own residual, pixels */
+} flow2d_node_strain_diagnostics;
+/* Workspace bytes flow2d_node_strain_robust_2d needs for `instances` lock-step instances of an nw x nh grid when it writes
+ * statistics (0 for a zero size; a multiple of 16).  Host logic only, needs no device. */
+FLOW2D_API size_t flow2d_node_strain_robust_workspace_bytes(size_t nw, size_t nh, size_t instances);
+FLOW2D_API int flow2d_node_strain_robust_2d(flow2d_context* ctx, const float* node_u, const float* node_v,
+                                            const float* node_state /* may be NULL */, size_t nw, size_t nh, size_t node_pitch_bytes,
+                                            int spacing, int window, int order, int min_nodes, int min_state, int measure, float sigma,
+                                            int iterations, const flow2d_deformation_planes* out /* host, may be NULL */,
+                                            const flow2d_node_strain_diagnostics* diagnostics /* host, may be NULL */,
+                                            flow2d_deformation_stats* stats /* device, may be NULL */, void* workspace,
+                                            size_t workspace_bytes);
 
 /* The composition of two node fields of a sequence whose reference frame has moved (incremental DIC), out of place.  The *base* A
  * is frame 0 -> frame r at the nodes of frame 0; the *increment* B is frame r -> frame k on the same grid laid in frame r.  The
