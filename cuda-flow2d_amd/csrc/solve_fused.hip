@@ -86,8 +86,9 @@ bool fused_weights_ok(float hx, float hy, float alpha)
     return ok(wx) && ok(wy);
 }
 
-// The fused kernel addresses a plane through a buffer descriptor with 32-bit byte offsets (row offset as the scalar
-// offset, column as a 32-bit vector offset): the plane, height x pitch bytes, must stay below 4 GiB.
+// The fused kernel addresses a plane as a scalar base pointer plus one unsigned 32-bit per-lane byte offset, (row * pitch +
+// column) * 4 (global_load / global_store ... saddr; solve_fused_kernel.hpp, plane_load): the plane, height x pitch bytes, must
+// stay below 4 GiB.
 bool fused_addressable(size_t h, size_t pitch_bytes) { return h != 0 && pitch_bytes <= 0xffffffffull / h; }
 
 // Strip heights of a launch.  A wave spends (rows + 2*inner + 3) row steps on `rows` stored rows, so tall strips

@@ -203,7 +203,7 @@ static int solver_algorithm_for(int requested, size_t width, size_t height, size
         if (flow2d::small_level_supports(width, height) && height <= 32) return FLOW2D_SOLVER_SINGLE_WORKGROUP;
         // Everything else goes through the fused strip kernel (above 512^2 it wins over per-sweep launches by 1.7-2.9x).
         // A single sweep per outer iteration leaves nothing to fuse, and a plane of 4 GiB or more is beyond the fused
-        // kernel's 32-bit buffer offsets: both take the per-sweep kernels.
+        // kernel's 32-bit byte offsets: both take the per-sweep kernels.
         return (inner >= 2 && flow2d::fused_addressable(height, pitch_bytes)) ? FLOW2D_SOLVER_FUSED : FLOW2D_SOLVER_PER_SWEEP;
     }
     if (requested == FLOW2D_SOLVER_TILED && !flow2d::tiled_supports(data_constancy, inner)) return -1;

@@ -16,7 +16,7 @@ from test_correlate_masked_cpu import (FLAG_MASKED, correlate_masked_reference, 
                                        off_specimen, validate_masked_reference)
 from test_gpu_batch_kernels import Tall, pitch_of, stride_of
 from test_gpu_multipass import POISON, WAVES, constant, node_field, padded, release, run_offset, run_validate
-from test_gpu_wide_planes import H as TALL_H, LINE, W as TALL_W, node_bits, node_poison, on_both, record_bytes, wrapped_rows_differ
+from test_gpu_wide_planes import H as TALL_H, HIGH_LINE, LINE, W as TALL_W, node_bits, node_poison, on_both, record_bytes, wrapped_rows_differ
 from test_multipass_cpu import FLAG, PASS_DTYPE, REPLACE, VALIDATION_DTYPE
 from test_subset_masked_cpu import random_mask
 
@@ -339,7 +339,9 @@ def test_planes_of_4_gib(flow2d, ctx):
     """correlate_masked_kernel<size_t> and the masked validation's 64-bit mask addressing: the 100 x 4200 frame of
     tests/test_gpu_wide_planes.py in planes with a pitch of 1 MiB (only the frame's columns are touched), grid (10, s 64), range 3:
     node row 63 (rows 4032 .. 4052) is sent 50 rows down, across row 4096; row 64 (rows 4096 .. 4116) six rows up, across it; row 65
-    lies beyond.  The same bytes as on planes with a pitch of 512 bytes, and the restatement's."""
+    lies beyond.  The same bytes as on planes with a pitch of 512 bytes, and the restatement's.  And the same bytes from
+    correlate_masked_kernel<unsigned> on planes just below 4 GiB, where row 2101 is the first whose byte offset has bit 31 set: node
+    row 32 (rows 2048 .. 2068) is sent 50 rows down, across it; row 33 (rows 2112 .. 2132) twenty rows up; row 34 lies beyond."""
     r, d, s = 10, 3, 64
     f0, f1 = random_frames(TALL_W, TALL_H, seed=52, shift=(2, -1))
     lo, scale = 0.0, 1.0
@@ -348,10 +350,12 @@ def test_planes_of_4_gib(flow2d, ctx):
     rng = np.random.default_rng(53)
     pu, pv = (rng.uniform(-3, 3, (TALL_H, TALL_W)).astype(F32) for _ in range(2))
     pv[cy[63] - 2:cy[63] + 3], pv[cy[64] - 2:cy[64] + 3] = 50.0, -6.0
+    pv[cy[32] - 2:cy[32] + 3], pv[cy[33] - 2:cy[33] + 3] = 50.0, -20.0
     mask = random_mask((TALL_H, TALL_W), 0.2, seed=56)
     mask[cy[:40], r] = 1          # off the specimen below the line ...
     mask[cy[65], r + s] = 1       # ... and beyond it
     mask[cy[63], :], mask[cy[64], :] = 0, 0
+    mask[cy[32], :], mask[cy[33], :] = 0, 0
     min_pixels = default_min_pixels(r)
     wu, wv, ws, record = correlate_masked_reference(f0, f1, lo, scale, r, d, s, mask, min_pixels, -1.0, pu, pv)
     vu, vv, vf, vrecord = validate_masked_reference(wu, wv, mask, r, s, mode=REPLACE)
@@ -359,12 +363,19 @@ def test_planes_of_4_gib(flow2d, ctx):
     assert cy[63] < LINE <= cy[63] + r + 50 - d and cy[64] - r - 6 - d < LINE <= cy[64] and cy[65] - r - 3 - d >= LINE
     for j in (63, 64):
         assert np.isfinite(wu[j]).all() and np.isfinite(wv[j]).all() and not np.array_equal(wv[j], wv[j - 63])
+    assert cy[32] < HIGH_LINE <= cy[32] + r + 50 - d and cy[33] - r - 20 - d < HIGH_LINE <= cy[33] - r and cy[34] - r - 3 - d >= HIGH_LINE
+    for j in (32, 33):
+        assert np.isfinite(wu[j]).all() and np.isfinite(wv[j]).all() and not np.array_equal(wv[j], wv[j - 32])
+    assert np.unique(wu[34:63][np.isfinite(wu[34:63])]).size > 1  # (nodes wholly between the two lines: column 0 is masked there)
     assert np.isfinite(wu[65, 0]) and bits(wu)[65, 1] == NAN_BITS and vf[65, 1] == FLAG_MASKED and vf[0, 0] == FLAG_MASKED
     below = correlate_masked_reference(f0[:LINE], f1[:LINE], lo, scale, r, d, s, mask[:LINE], min_pixels, -1.0, pu[:LINE], pv[:LINE])[3]
     assert below.tobytes() != record.tobytes()
     # (a mask whose rows from 4096 on were rows 0 .. again would give another field: the wrapped mask's restatement differs)
     wrapped = mask.copy()
     wrapped[LINE:] = mask[:TALL_H - LINE]
+    assert not np.array_equal(bits(correlate_masked_reference(f0, f1, lo, scale, r, d, s, wrapped, min_pixels, -1.0, pu, pv)[0]), bits(wu))
+    wrapped = mask.copy()
+    wrapped[HIGH_LINE:] = mask[:TALL_H - HIGH_LINE]
     assert not np.array_equal(bits(correlate_masked_reference(f0, f1, lo, scale, r, d, s, wrapped, min_pixels, -1.0, pu, pv)[0]), bits(wu))
 
     def run(rig):

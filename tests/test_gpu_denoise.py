@@ -427,34 +427,47 @@ def test_table_gpu_rows_equal_numpy_rows(flow2d):
 def test_planes_of_4_gib_and_more(flow2d, ctx):
     """Both kernels' 64-bit offset instantiations: a 40-pixel-wide frame in planes with a pitch of 1 MiB and 4200 rows, so a
     plane spans more than 4 GiB and the byte offsets of the rows from 4096 on do not fit 32 bits.  Bit for bit against the
-    restatements, like every other size."""
-    w, h, wide = 40, 4200, 262144
+    restatements, like every other size.  Then the same data in planes with a pitch of 255 616 floats, 4 294 348 800 bytes a plane:
+    below 4 GiB, so both kernels take their 32-bit offsets, and from row 2101 on those have bit 31 set (2 148 196 864 at the start of
+    row 2101; the frame's columns of row 2100 lie below 2^31).  The same bytes as the first run."""
+    w, h = 40, 4200
+    high = 255616
+    assert (4 * high * h, 4 * high * 2101) == (4294348800, 2148196864) and 4 * high * h < 1 << 32 and 4 * high * 2100 + 4 * w < 1 << 31 <= 4 * high * 2101
     rng = np.random.default_rng(77)
-
-    def plane(a=None):
-        p = ctx.plane(wide, h)
-        assert p.pitch * h >= 1 << 32
-        return p.upload(a if a is not None else np.full((h, w), POISON, F32))
-
     centre, frames, us, vs, occs = random_case(rng, w, h, 1)
-    pc, pf, pu, pv, po, out, wsum = plane(centre), plane(frames[0]), plane(us[0]), plane(vs[0]), plane(occs[0]), plane(), plane()
-    ctx.denoise(pc, [pf], [pu], [pv], w, h, out, [po], 12.5, wsum)
-    ctx.synchronize()
     want, want_sum = denoise_reference(centre, frames, us, vs, occs, 12.5)
-    assert (want_sum[4096:] > 1).any()  # rows past 4 GiB gather
-    assert_same(out.download(w, h), want, "denoise, 4 GiB planes")
-    assert_same(wsum.download(w, h), want_sum, "denoise, 4 GiB planes: weight_sum")
-    for p in (pc, pf, out, wsum):
-        p.free()
-    # the composition: (pu, pv) scaled down as the first step, a second flow and both masks
     case = compose_case(rng, w, h)
-    planes = [plane(a) for a in case]
-    outs = [plane() for _ in range(3)]
-    ctx.compose_flow(*planes[:4], w, h, outs[0], outs[1], planes[4], planes[5], outs[2])
-    ctx.synchronize()
     cwant = compose_reference(*case)
-    assert np.isfinite(cwant[0][4096:]).any()
-    for o, x, name in zip(outs, cwant, ("u", "v", "mask")):
-        assert_same(o.download(w, h), x, "compose, 4 GiB planes: %s" % name)
-    for p in planes + outs + [pu, pv, po]:
-        p.free()
+    for line in (4096, 2101):
+        assert (want_sum[line:] > 1).any()  # rows past the line gather
+        assert np.isfinite(cwant[0][line:]).any()
+        assert not np.array_equal(centre[line:], centre[:h - line]) and not np.array_equal(want[line:], want[:h - line])
+    runs = []
+    for wide in (262144, high):
+        def plane(a=None):
+            p = ctx.plane(wide, h)
+            assert p.pitch == 4 * wide and (p.pitch * h >= 1 << 32) == (wide != high)
+            return p.upload(a if a is not None else np.full((h, w), POISON, F32))
+
+        pc, pf, pu, pv, po, out, wsum = plane(centre), plane(frames[0]), plane(us[0]), plane(vs[0]), plane(occs[0]), plane(), plane()
+        ctx.denoise(pc, [pf], [pu], [pv], w, h, out, [po], 12.5, wsum)
+        ctx.synchronize()
+        got = [out.download(w, h), wsum.download(w, h)]
+        for p in (pc, pf, out, wsum):
+            p.free()
+        # the composition: (pu, pv) scaled down as the first step, a second flow and both masks
+        planes = [plane(a) for a in case]
+        outs = [plane() for _ in range(3)]
+        ctx.compose_flow(*planes[:4], w, h, outs[0], outs[1], planes[4], planes[5], outs[2])
+        ctx.synchronize()
+        got += [o.download(w, h) for o in outs]
+        for p in planes + outs + [pu, pv, po]:
+            p.free()
+        runs.append(got)
+    for got, kind in zip(runs, ("4 GiB planes", "planes just below 4 GiB")):
+        assert_same(got[0], want, "denoise, %s" % kind)
+        assert_same(got[1], want_sum, "denoise, %s: weight_sum" % kind)
+        for g, x, name in zip(got[2:], cwant, ("u", "v", "mask")):
+            assert_same(g, x, "compose, %s: %s" % (kind, name))
+    for a, b in zip(*runs):
+        assert a.tobytes() == b.tobytes(), "the run on planes just below 4 GiB differs from the run on planes of 4 GiB"

@@ -16,7 +16,7 @@ from test_gpu_batch_kernels import Tall, pitch_of, stride_of
 from test_gpu_multipass import POISON, padded, release
 from test_gpu_subset import compare, speckle_case
 from test_gpu_subset2 import OUT_NAMES, compare2
-from test_gpu_wide_planes import (GRID_R, GRID_S, H as TALL_H, LINE, W as TALL_W, below_the_line, node_bits, on_both, record_bytes,
+from test_gpu_wide_planes import (GRID_R, GRID_S, H as TALL_H, HIGH_LINE, LINE, W as TALL_W, below_the_line, node_bits, on_both, record_bytes,
                                   speckle_case as tall_speckle_case, subset_outputs, subsets_show_a_wrap, wrapped_rows_differ)
 from test_subset_cpu import SUBSET_DTYPE, Refined, small_case
 from test_subset_masked_cpu import all_orders_masked, random_mask
@@ -152,11 +152,14 @@ def test_prefilter_refusals_write_nothing(flow2d, ctx):
 
 def test_prefilter_on_planes_of_4_gib(flow2d, ctx):
     """100 x 4200 at a pitch of 1 MiB (bspline_prefilter_kernel<size_t>): the bytes of the run at a pitch of 512 bytes and the
-    restatement's; the rows from 4096 on differ from the rows a 32-bit offset would wrap them onto.  Two tall planes."""
+    restatement's; the rows from 4096 on differ from the rows a 32-bit offset would wrap them onto.  Two tall planes.  A third run
+    on planes just below 4 GiB (bspline_prefilter_kernel<unsigned> with byte offsets of 2^31 and more from row 2101 on): the same
+    bytes, and the rows from 2101 on differ from rows 0 .. ."""
     f1 = tall_speckle_case()[1]
     want = shared("tall coefficients", lambda: S.bspline_prefilter_reference(tall_speckle_case()[1]))
     wrapped_rows_differ(f1, want)
     assert np.isfinite(want[LINE:]).all() and np.unique(want[LINE:]).size > 1000
+    assert np.isfinite(want[HIGH_LINE:]).all() and np.unique(want[HIGH_LINE:LINE]).size > 1000
 
     def run(rig):
         src, dst = rig.load(f1), rig.out()
@@ -415,7 +418,9 @@ def test_refusals_on_a_real_context_write_nothing(flow2d, ctx):
 
 
 def test_first_order_on_planes_of_4_gib(flow2d, ctx):
-    """subset_refine_masked_kernel<size_t, BSpline, false> at R = 15: frame 0 and the coefficients in tall planes (two of them)."""
+    """subset_refine_masked_kernel<size_t, BSpline, false> at R = 15: frame 0 and the coefficients in tall planes (two of them), and
+    the <unsigned, BSpline, false> kernel on planes just below 4 GiB, where the subsets of the node rows 130 and 131 lie across the
+    first row whose byte offset has bit 31 set."""
     R = 15
     f0, f1, u0, v0 = tall_speckle_case()
     nh, nw = u0.shape
@@ -512,7 +517,8 @@ def test_order_2_lock_step_batch_of_three(flow2d, ctx):
 
 
 def test_order_2_on_planes_of_4_gib(flow2d, ctx):
-    """subset_refine2_kernel<size_t, BSpline>, R = 15.  Two tall planes."""
+    """subset_refine2_kernel<size_t, BSpline>, R = 15.  Two tall planes; subset_refine2_kernel<unsigned, BSpline> on planes just below
+    4 GiB."""
     R = 15
     f0, f1, u0, v0 = tall_speckle_case()
     nh, nw = u0.shape

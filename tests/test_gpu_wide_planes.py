@@ -3,11 +3,17 @@ median.hip's offsets_fit, on planes that span 4 GiB and more: a frame of 100 x 4
 test_gpu_denoise.py::test_planes_of_4_gib_and_more, so the byte offset of row 4096 is 2^32 and a 32-bit intermediate anywhere wraps
 row 4096 + k onto row k.  Only the frame's columns of a plane are ever touched (inputs uploaded, outputs poisoned there).
 
+And the 32-bit forms of the same entries in the upper half of their range: the same frame in "high" planes with a pitch of 255 616
+floats, 4 294 348 800 bytes a plane -- below 2^32, so every entry takes its `unsigned` instantiation and the medians their streaming
+kernels -- where the byte offset of row 2101 is 2 148 196 864 >= 2^31: a signed intermediate addresses memory below the plane from
+there on, and a shift or a mask that drops bit 31 reads row k for row 2101 + k.
+
 Every entry is held to the restatement and the checker of its own GPU test, with that test's tolerances, and runs a second time on
-the same data in planes with a pitch of 512 bytes (the 32-bit instantiation): the two runs' outputs and records are the same bytes.
-Before a device result is looked at, the inputs and the expected outputs are shown to make a wrap visible: rows 4096 .. 4199 differ
-from rows 0 .. 103, the expected rows from 4096 on are live, what gathers does so across the line 4095 | 4096 in both directions,
-and what reduces to a record gives another record for the rows 0 .. 4095 alone."""
+high planes and a third time on the same data in planes with a pitch of 512 bytes (the 32-bit instantiation far below 2^31): the
+three runs' outputs and records are the same bytes.  Before a device result is looked at, the inputs and the expected outputs are
+shown to make a wrap visible at either line (4095 | 4096 of the tall planes, 2100 | 2101 of the high ones): the rows from the line
+on differ from rows 0 .., the expected rows from the line on are live, what gathers does so across the line in both directions, and
+what reduces to a record gives another record for the rows 0 .. 4095 alone."""
 import numpy as np
 import pytest
 
@@ -40,20 +46,30 @@ pytestmark = pytest.mark.gpu
 
 W, H = 100, 4200          # the frame: two 64-column tiles, 104 rows past the line
 WIDE = 262144             # floats per row of a tall plane: a pitch of exactly 1 MiB
+HIGH = 255616             # floats per row of a high plane: a pitch of 1 022 464 bytes, 4200 rows of it just below 4 GiB
 NARROW = 128              # floats per row of an ordinary plane: a pitch of 512 bytes
-LINE = (1 << 32) // (4 * WIDE)  # 4096: the first row whose byte offset does not fit 32 bits
+PITCH = {"tall": WIDE, "high": HIGH, "ordinary": NARROW}
+KINDS = ("tall", "high", "ordinary")
+LINE = (1 << 32) // (4 * WIDE)  # 4096: the first row of a tall plane whose byte offset does not fit 32 bits
+HIGH_LINE = -(-(1 << 31) // (4 * HIGH))  # 2101: the first row of a high plane whose byte offset has bit 31 set
+LINES = (LINE, HIGH_LINE)
 TALL_BYTES = 4 * WIDE * H
-# the node grid of the subset kernels: centres 10 + 16 j, so row 255 (cy = 4090) lies below the line and row 256 (cy = 4106) beyond it
+HIGH_BYTES = 4 * HIGH * H
+assert (4 * HIGH, HIGH_BYTES, HIGH_LINE, 4 * HIGH * HIGH_LINE) == (1022464, 4294348800, 2101, 2148196864)
+assert HIGH_BYTES < 1 << 32 and 4 * HIGH * (HIGH_LINE - 1) + 4 * W < 1 << 31 <= 4 * HIGH * HIGH_LINE  # (the frame's columns of row 2100 lie below 2^31)
+# the node grid of the subset kernels: centres 10 + 16 j, so row 255 (cy = 4090) lies below the line and row 256 (cy = 4106) beyond it;
+# rows 130 (cy = 2090) and 131 (cy = 2106) lie on either side of the high planes' line
 GRID_R, GRID_S = 10, 16
 
 
 # ---- planes ---------------------------------------------------------------------------------------------------------------------------
 class Rig:
-    """The planes of one run: tall (pitch 1 MiB) or ordinary (pitch 512 bytes).  `peak` tall planes are alive at most."""
+    """The planes of one run: tall (pitch 1 MiB), high (pitch 1 022 464 bytes) or ordinary (pitch 512 bytes).  `peak` tall or high
+    planes are alive at most."""
 
-    def __init__(self, ctx, tall, peak):
-        self.ctx, self.tall, self.held = ctx, tall, []
-        if tall:
+    def __init__(self, ctx, kind, peak):
+        self.ctx, self.kind, self.tall, self.held = ctx, kind, kind == "tall", []
+        if kind != "ordinary":
             free, total = ctx.mem_info()
             need = peak * TALL_BYTES + (1 << 30)
             if need > free:
@@ -63,10 +79,12 @@ class Rig:
         """A plane of `rows` rows with `a` in its first columns; nothing else of it is touched."""
         if a is None:
             return None
-        p = self.ctx.plane(WIDE if self.tall else NARROW, rows)
-        assert p.pitch == 4 * (WIDE if self.tall else NARROW)
+        p = self.ctx.plane(PITCH[self.kind], rows)
+        assert p.pitch == 4 * PITCH[self.kind]  # (the allocator leaves these pitches as they are: multiples of 256 bytes)
         if self.tall and rows == H:
             assert p.pitch * rows >= 1 << 32
+        if self.kind == "high" and rows == H:
+            assert 1 << 31 < p.pitch * (rows - 1) and p.pitch * rows == HIGH_BYTES < 1 << 32
         self.held.append(p)
         return p.upload(a)
 
@@ -86,19 +104,21 @@ class Rig:
 
 
 def on_both(ctx, peak, run):
-    """run(rig) -> {name: array or bytes} on tall planes, then on ordinary ones: the same bytes.  Returns the tall run's result."""
+    """run(rig) -> {name: array or bytes} on tall planes, then on high planes, then on ordinary ones: the same bytes.  Returns the tall
+    run's result."""
     got = []
-    for tall in (True, False):
-        rig = Rig(ctx, tall, peak)
+    for kind in KINDS:
+        rig = Rig(ctx, kind, peak)
         try:
             got.append(run(rig))
             ctx.synchronize()
         finally:
             rig.free()
-    assert got[0].keys() == got[1].keys()
+    assert got[0].keys() == got[1].keys() == got[2].keys()
     for name in got[0]:
-        a, b = (g[name] if isinstance(g[name], bytes) else np.ascontiguousarray(g[name]).tobytes() for g in got)
-        assert a == b, "%s: the run on planes of 4 GiB differs from the run on ordinary planes" % name
+        a, b, c = (g[name] if isinstance(g[name], bytes) else np.ascontiguousarray(g[name]).tobytes() for g in got)
+        assert a == c, "%s: the run on planes of 4 GiB differs from the run on ordinary planes" % name
+        assert b == c, "%s: the run on planes just below 4 GiB differs from the run on ordinary planes" % name
     return got[0]
 
 
@@ -108,33 +128,38 @@ def record_bytes(plane, count):
 
 # ---- what makes a wrap visible (the reference alone) --------------------------------------------------------------------------------
 def wrapped_rows_differ(*arrays, h=H):
-    """Rows 4096 .. of every input are not rows 0 .. again."""
+    """Rows 4096 .. of every input are not rows 0 .. again, and neither are rows 2101 .. ."""
     for a in arrays:
         if a is not None:
-            assert not np.array_equal(bits(a[LINE:h]), bits(a[:h - LINE]))
+            for line in LINES:
+                assert not np.array_equal(bits(a[line:h]), bits(a[:h - line]))
 
 
 def live(*arrays, invalid=None):
-    """The expected rows from 4096 on: finite values, more than one of them, beyond `invalid` too, and not those of rows 0 .. 103."""
+    """The expected rows from 4096 on, and those from 2101 on: finite values, more than one of them, beyond `invalid` too, and not
+    those of rows 0 .. ."""
     for a in arrays:
         a = np.asarray(a)
-        top = a[LINE:]
-        values = top[np.isfinite(top)]
-        if invalid is not None:
-            values = values[values != invalid]
-        assert values.size and np.unique(values).size > 1
-        assert not np.array_equal(top.tobytes(), a[:a.shape[0] - LINE].tobytes())
+        for line in LINES:
+            top = a[line:]
+            values = top[np.isfinite(top)]
+            if invalid is not None:
+                values = values[values != invalid]
+            assert values.size and np.unique(values).size > 1
+            assert not np.array_equal(top.tobytes(), a[:a.shape[0] - line].tobytes())
 
 
 def crosses_the_line(v, u=None, scale=1.0):
     """Some pixel below the line points (by its vertical component times `scale`) to a row of the frame from 4096 on, some pixel from
-    4096 on to a row of the frame below 4095: a gather along these vectors reads across the line in both directions."""
+    4096 on to a row of the frame below 4095: a gather along these vectors reads across the line in both directions.  The same at
+    the line 2100 | 2101."""
     ys, xs = np.mgrid[0:v.shape[0], 0:v.shape[1]]
     with np.errstate(invalid="ignore", over="ignore"):
         ty = ys + scale * v.astype(np.float64)
         tx = xs + scale * (u.astype(np.float64) if u is not None else 0.0)
         inside = (tx >= 0) & (tx <= v.shape[1] - 1) & (ty >= 0) & (ty <= v.shape[0] - 1)
-        assert (inside & (ys < LINE) & (ty >= LINE)).any() and (inside & (ys >= LINE) & (ty < LINE - 1)).any()
+        for line in LINES:
+            assert (inside & (ys < line) & (ty >= line)).any() and (inside & (ys >= line) & (ty < line - 1)).any()
 
 
 # ---- per-pixel entries ---------------------------------------------------------------------------------------------------------------
@@ -360,9 +385,11 @@ def test_prior_registration(flow2d, ctx):
     first = -((-LINE * h) // in_h)  # the first level row that reads prior rows from 4096 on only
     assert 4 * WIDE * h < 1 << 32 <= 4 * WIDE * in_h and first < h - 64
     wrapped_rows_differ(pu, pv)
+    first_high = -((-HIGH_LINE * h) // in_h)  # the same for prior rows from 2101 on, the high planes' line
     for a in (want_u, want_v, want_out):
-        top = a[first:]
-        assert np.isfinite(top).all() and np.unique(top).size > 1 and not np.array_equal(top, a[:h - first])
+        for start in (first, first_high):
+            top = a[start:]
+            assert np.isfinite(top).all() and np.unique(top).size > 1 and not np.array_equal(top, a[:h - start])
     assert count >= 6 and count != prior_restatement(pu[:LINE], pv[:LINE], f0[:3900], f1[:3900], w, 3900)[3]
     held = []
 
@@ -415,7 +442,8 @@ def test_propagate_flow(flow2d, ctx):
 def test_median(flow2d, ctx, oracle):
     """flow2d_median_2d for the windows 3, 5 and 7 and flow2d_add_median_2d_pair on planes of 4 GiB: median.hip's offsets_fit sends
     them to the generic kernel (a streaming kernel's 32-bit byte offsets would give rows 0 .. 103 from row 4096 on); the ordinary
-    planes of the second run take the streaming kernels.  Six tall planes; 66 columns and the pair form at window 5 alone keep the
+    planes of the third run take the streaming kernels far below 2^31, and the high planes of the second run take them with byte
+    offsets up to 2^32: a streaming kernel that dropped bit 31 would give rows 0 .. from row 2101 on.  Six tall planes; 66 columns and the pair form at window 5 alone keep the
     oracle's share of the time down."""
     w = 66
     rng = np.random.default_rng(49)
@@ -469,12 +497,12 @@ def release(ctx, planes):
         ctx._planes.remove(q)
 
 
-def straddling_and_beyond(cy, reach):
-    """Of the node rows with centres `cy` and rows cy - reach .. cy + reach: (those below the line that reach rows from 4096 on, those
-    from the line on that reach rows below it, those wholly beyond it)."""
-    down = (cy < LINE) & (cy + reach >= LINE)
-    up = (cy >= LINE) & (cy - reach < LINE)
-    return down, up, cy - reach >= LINE
+def straddling_and_beyond(cy, reach, line=LINE):
+    """Of the node rows with centres `cy` and rows cy - reach .. cy + reach: (those below the line that reach rows from `line` on,
+    those from the line on that reach rows below it, those wholly beyond it)."""
+    down = (cy < line) & (cy + reach >= line)
+    up = (cy >= line) & (cy - reach < line)
+    return down, up, cy - reach >= line
 
 
 def test_correlate_and_expand(flow2d, ctx):
@@ -488,10 +516,10 @@ def test_correlate_and_expand(flow2d, ctx):
     eu, ev = expand_reference(wu, wv, r, s, W, H)
     nw, nh = grid(W, H, r, s)
     cy = r + np.arange(nh) * s
-    down, up, beyond = straddling_and_beyond(cy, r + d)
     wrapped_rows_differ(f0, f1)
-    for rows in (down, up, beyond):
-        assert rows.any() and np.isfinite(wu[rows]).all() and np.unique(wu[rows]).size > 1
+    for line in LINES:
+        for rows in straddling_and_beyond(cy, r + d, line):
+            assert rows.any() and np.isfinite(wu[rows]).all() and np.unique(wu[rows]).size > 1
     live(eu, ev)
     assert correlate_reference(f0[:LINE], f1[:LINE], lo, scale, r, d, s)[3].tobytes() != record.tobytes()
 
@@ -521,7 +549,7 @@ def test_expand_nodes_into_tall_planes(flow2d, ctx):
     nu, nv = (rng.normal(0, 3, (nh, nw)).astype(F32) for _ in range(2))
     nu[3, 0], nv[nh - 2, 1], nu[nh - 1, :] = np.nan, np.inf, np.nan
     eu, ev = expand_reference(nu, nv, r, s, W, H)
-    assert nh == 66 and r + (nh - 2) * s >= LINE
+    assert nh == 66 and r + (nh - 2) * s >= LINE and r + 32 * s < HIGH_LINE <= r + 33 * s
     live(eu, ev)
 
     def run(rig):
@@ -541,8 +569,9 @@ def test_expand_nodes_into_tall_planes(flow2d, ctx):
 
 def test_correlate_offset(flow2d, ctx):
     """flow2d_correlate_offset_2d with a dense predictor: correlate_offset_kernel<size_t>.  Grid (10, s 64), range 3: node row 63 (rows
-    4032 .. 4052) is sent 50 rows down, across the line; row 64 (rows 4096 .. 4116) six rows up, across it; row 65 lies beyond.  Four
-    tall planes."""
+    4032 .. 4052) is sent 50 rows down, across the line; row 64 (rows 4096 .. 4116) six rows up, across it; row 65 lies beyond.  At
+    the high planes' line node row 32 (rows 2048 .. 2068) is sent 50 rows down, row 33 (rows 2112 .. 2132) twenty rows up, and row 34
+    lies beyond.  Four tall planes."""
     r, d, s = 10, 3, 64
     f0, f1 = random_frames(W, H, seed=52, shift=(2, -1))
     lo, scale = frame_range(f0, f1)
@@ -551,11 +580,15 @@ def test_correlate_offset(flow2d, ctx):
     rng = np.random.default_rng(53)
     pu, pv = (rng.uniform(-3, 3, (H, W)).astype(F32) for _ in range(2))
     pv[cy[63] - 2:cy[63] + 3], pv[cy[64] - 2:cy[64] + 3] = 50.0, -6.0
+    pv[cy[32] - 2:cy[32] + 3], pv[cy[33] - 2:cy[33] + 3] = 50.0, -20.0
     wu, wv, ws, record = correlate_offset_reference(f0, f1, lo, scale, r, d, s, -1.0, pu, pv)
     wrapped_rows_differ(f0, f1, pu, pv)
     assert cy[63] < LINE <= cy[63] + r + 50 - d and cy[64] - r - 6 - d < LINE <= cy[64] and cy[65] - r - 3 - d >= LINE
+    assert cy[32] < HIGH_LINE <= cy[32] + r + 50 - d and cy[33] - r - 20 - d < HIGH_LINE <= cy[33] - r and cy[34] - r - 3 - d >= HIGH_LINE
     for j in (63, 64, 65):
         assert np.isfinite(wu[j]).all() and np.isfinite(wv[j]).all() and not np.array_equal(wv[j], wv[j - 63])
+    for j in (32, 33, 34):
+        assert np.isfinite(wu[j]).all() and np.isfinite(wv[j]).all() and not np.array_equal(wv[j], wv[j - 32])
     below = correlate_offset_reference(f0[:LINE], f1[:LINE], lo, scale, r, d, s, -1.0, pu[:LINE], pv[:LINE])[3]
     assert below.tobytes() != record.tobytes()
 
@@ -578,12 +611,12 @@ def test_correlate_offset(flow2d, ctx):
 
 # ---- the subset refinements -----------------------------------------------------------------------------------------------------------
 _speckle = []
-LIVE_ROWS = [0, 1, 100, 254, 255, 256, 257, 258]  # the node rows that have a start; every other node is SUBSET_NO_INPUT
+LIVE_ROWS = [0, 1, 100, 130, 131, 132, 254, 255, 256, 257, 258]  # the node rows that have a start; every other node is SUBSET_NO_INPUT
 
 
 def speckle_case():
     """The translated speckle pattern at 100 x 4200 and the start of the grid (10, s 16), 5 x 262 nodes: the truth (2.3, -1.4) rounded
-    to whole pixels in the node rows LIVE_ROWS, NaN in every other, which keeps the restatement to forty nodes.  Made once."""
+    to whole pixels in the node rows LIVE_ROWS, NaN in every other, which keeps the restatement to fifty-five nodes.  Made once."""
     if not _speckle:
         scene = scenes_module().make_speckle_scene("translation", W, H, seed=3)
         nw, nh = grid(W, H, GRID_R, GRID_S)
@@ -596,13 +629,18 @@ def speckle_case():
 def subsets_show_a_wrap(want, R, f0, f1, reference_below):
     """The node rows 255 (cy = 4090) and 256 (cy = 4106): at R = 15 both subsets hold rows of both sides of the line, at R = 5 row 255
     reaches row 4096 with its gradient stencil; rows 257 and 258 lie wholly beyond the line.  All of them hold refined nodes, and the
-    rows 0 .. 4095 alone give another record."""
+    rows 0 .. 4095 alone give another record.  The node rows 130 (cy = 2090), 131 (cy = 2106) and 132 are the same to the line
+    2100 | 2101 of the high planes: at R = 15 the subsets of rows 130 and 131 hold rows of both sides, at R = 5 row 131 reaches down
+    to row 2100 and row 130 lies below the line; row 132 lies wholly beyond."""
     nh = want.state.shape[0]
     cy = GRID_R + np.arange(nh) * GRID_S
     down, up, beyond = straddling_and_beyond(cy, R + 1)
     assert down[255] and (up[256] or R < 15) and beyond[257] and beyond[258] and cy[258] + R + 2 < H
-    for j in (255, 256, 257, 258):
+    down, up, beyond = straddling_and_beyond(cy, R + 1, HIGH_LINE)
+    assert (down[130] or R < 15) and up[131] and beyond[132] and not beyond[131]
+    for j in (130, 131, 132, 255, 256, 257, 258):
         assert (want.state[j] >= 1).any(), "no node of row %d converged" % j
+    assert not np.array_equal(want.u[131:133], want.u[0:2]) and np.unique(want.u[131:133][want.state[131:133] >= 1]).size > 1
     assert not np.array_equal(want.u[256:259], want.u[0:3]) and np.unique(want.u[256:259][want.state[256:259] >= 1]).size > 1
     wrapped_rows_differ(f0, f1)
     assert reference_below.record.tobytes() != want.record.tobytes()
@@ -702,6 +740,7 @@ def test_subset_refine_masked(flow2d, ctx):
     subsets_show_a_wrap(want, R, f0, f1, below)
     wrapped_rows_differ(mask)
     assert (mask[LINE - 16:LINE] == 1).any() and (mask[LINE:LINE + 16] == 1).any()
+    assert (mask[HIGH_LINE - 16:HIGH_LINE] == 1).any() and (mask[HIGH_LINE:HIGH_LINE + 16] == 1).any()
 
     def run(rig):
         p0, p1, pm = rig.load(f0), rig.load(f1), rig.load(mask)

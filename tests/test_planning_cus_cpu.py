@@ -276,3 +276,33 @@ def test_setter_and_getter_on_a_stand_in_context(flow2d):
     assert lib.flow2d_fused_plan_for_cus(8, 64, 64, 5, 1, None, None) == 1
     assert lib.flow2d_fused_block_order_for_cus(8, 417, 900, 5, 1, buf, 8, ctypes.byref(grid)) == 1 and grid.value == 16  # too small
     assert flow2d.Context.set_planning_cus.__doc__ and flow2d.Context.planning_cus.__doc__
+
+
+def test_the_strips_end_where_their_32_bit_offsets_do(flow2d):
+    """flow2d_solver_algorithm_for at the line height * pitch_bytes = 2^32 (fused_addressable, csrc/solve_fused.hip): a plane one
+    row, or one pitch step, short of 4 GiB is the strips', a plane of exactly 4 GiB or more is the per-sweep kernels' under AUTO and
+    refused where the strips are asked for.  tests/test_gpu_high_offsets.py runs the planes of the first two lines on the device."""
+    AUTO, PER_SWEEP, FUSED = flow2d.SOLVER_AUTO, flow2d.SOLVER_PER_SWEEP, flow2d.SOLVER_FUSED
+    pick = flow2d.hip_lib().flow2d_solver_algorithm_for
+    MIB = 1 << 20
+    # (width, height, pitch in bytes, the plane's bytes against 2^32)
+    below = [(100, 4095, MIB, -MIB), (100, 4095, MIB + 256, -256), (200, 2048, 2 * MIB - 256, -2048 * 256), (100, 4096, MIB - 4, -4 * 4096)]
+    beyond = [(100, 4096, MIB, 0), (100, 4095, MIB + 512, 4095 * 512 - MIB), (200, 2048, 2 * MIB, 0), (100, 4097, MIB - 4, MIB - 4 * 4097),
+              (100, 4200, MIB, 104 * MIB)]
+    for w, h, pitch, distance in below + beyond:
+        assert h * pitch - (1 << 32) == distance, (h, pitch)
+        assert w * h > 600 * 600  # (above the tiles' crossover: AUTO chooses between the strips and the per-sweep kernels)
+    for constancy in (flow2d.GREY, flow2d.GRADIENT, flow2d.LOG_DERIVATIVES):
+        for w, h, pitch, _ in below:
+            for inner in (2, 5):
+                assert pick(AUTO, w, h, pitch, 3, inner, constancy) == FUSED, (w, h, pitch, inner, constancy)
+                assert pick(FUSED, w, h, pitch, 3, inner, constancy) == FUSED, (w, h, pitch, inner, constancy)
+            assert pick(AUTO, w, h, pitch, 3, 1, constancy) == PER_SWEEP  # (a single sweep leaves nothing to fuse)
+        for w, h, pitch, _ in beyond:
+            for inner in (2, 5):
+                assert pick(AUTO, w, h, pitch, 3, inner, constancy) == PER_SWEEP, (w, h, pitch, inner, constancy)
+                assert pick(FUSED, w, h, pitch, 3, inner, constancy) == -1, (w, h, pitch, inner, constancy)
+            assert pick(PER_SWEEP, w, h, pitch, 3, 5, constancy) == PER_SWEEP
+    # the frame of the device test at inner 5 and 2: at most one workgroup per CU, the launch the packed build takes on a lone context
+    for inner in (2, 5):
+        assert flow2d.fused_plan_for_cus(256, 100, 4095, inner).blocks <= 256
