@@ -361,6 +361,22 @@ COMPOSE_RECORD_BYTES = 64  # FLOW2D_COMPOSE_RECORD_BYTES, checked by a static_as
 assert C.sizeof(ComposeRecord) == COMPOSE_RECORD_BYTES
 
 
+class UncertaintyRecord(C.Structure):
+    """flow2d_uncertainty_record of include/flow2d_c_abi.h: the seven counts flow2d_subset_uncertainty_2d writes per instance."""
+    _fields_ = [("nodes", C.c_ulonglong), ("evaluated", C.c_ulonglong), ("skipped", C.c_ulonglong), ("masked", C.c_ulonglong),
+                ("outside", C.c_ulonglong), ("flat", C.c_ulonglong), ("thin", C.c_ulonglong), ("reserved", C.c_ulonglong)]
+
+    def summary(self):
+        return {name: getattr(self, name) for name, _ in self._fields_[:7]}
+
+
+UNCERTAINTY_RECORD_BYTES = 64  # FLOW2D_UNCERTAINTY_RECORD_BYTES, checked by a static_assert in the header
+assert C.sizeof(UncertaintyRecord) == UNCERTAINTY_RECORD_BYTES
+# the planes of flow2d_subset_uncertainty_2d in the order of its arguments; sigma_u and sigma_v are required, the four gradient
+# sigmas go all or none
+SUBSET_UNCERTAINTY_PLANES = ("sigma_u", "sigma_v", "rho", "sigma_ux", "sigma_uy", "sigma_vx", "sigma_vy", "noise")
+
+
 class SequenceStepReport(C.Structure):
     """OpticalFlow2D::SequenceStepReport: one step of correlate_subset_sequence -- the refinement's record and the records of the
     prediction passes that ran before it (zero in step 1 and beyond `fill`)."""
@@ -643,6 +659,8 @@ def hip_lib():
             L.flow2d_node_strain_robust_workspace_bytes.argtypes = [sz, sz, sz]
             L.flow2d_node_strain_robust_2d.argtypes = [vp] + [vp] * 3 + [sz, sz, sz, i, i, i, i, i, i, C.c_float, i,
                                                                         C.POINTER(DeformationPlanes), C.POINTER(NodeStrainDiagnostics), vp, vp, sz]
+        if hasattr(L, "flow2d_subset_uncertainty_2d"):  # (absent from libraries of earlier rounds loaded for an A/B)
+            L.flow2d_subset_uncertainty_2d.argtypes = [vp, vp, vp, i, sz, sz, sz] + [vp] * 7 + [sz, sz, sz, i, i, i, i, vp, i] + [vp] * 9
         if hasattr(L, "flow2d_compose_nodes_2d"):  # (absent from libraries of earlier rounds loaded for an A/B)
             L.flow2d_compose_nodes_2d.argtypes = [vp, vp, vp, vp, sz, sz, sz, i, i, i, vp, vp, vp, vp]
         if hasattr(L, "flow2d_prior_registration_2d"):  # (absent from libraries of earlier rounds loaded for an A/B)
@@ -1618,6 +1636,54 @@ class Context:
         return self.subset_refine2(f0, coeff_1, w, h, node_u0, node_v0, nw, nh, grid_radius, spacing, subset_radius,
                                    _entry="flow2d_subset_refine2_spline_2d", **options)
 
+    def uncertainty_records(self, instances=1):
+        """A Plane for `instances` flow2d_uncertainty_record records (device memory)."""
+        return self._record_plane(UNCERTAINTY_RECORD_BYTES, instances)
+
+    def read_uncertainty_record(self, record, instances=1):
+        """The records of an uncertainty_records Plane as UncertaintyRecord structures (synchronises)."""
+        return self._read_records(record, instances, UncertaintyRecord)
+
+    def subset_uncertainty(self, f0, f1, w, h, nodes, state, nw, nh, grid_radius, spacing, subset_radius, min_state=1,
+                           interpolation=SUBSET_CATMULL_ROM, mask=None, min_pixels=None, out=None, record=True, instances=1):
+        """The uncertainty of a first-order refinement's nodes (flow2d_subset_uncertainty_2d): per node the covariance s2 * H^-1 of
+        p at nodes = (u, v, ux, uy, vx, vy) Planes with their `state` Plane, as subset_refine and its siblings wrote them -- s2 the
+        residual variance of the ZNSSD there over N - 8 degrees of freedom, H the refinement's Hessian.  f1 is frame 1, or with
+        interpolation = SUBSET_BSPLINE the Plane bspline_prefilter made from it; mask and min_pixels (None:
+        subset_min_pixels(subset_radius)) as for subset_refine_masked.  A node with a state below min_state or a value that is not
+        finite, off the mask, out of the frame, flat or with fewer than nine usable pixels gets NaN in every plane and is counted
+        in the record.  The sigmas estimate the random error that the frames' noise puts into p, in pixels (gradients: per
+        pixel); `noise` is sqrt(s2) in grey values, `rho` the correlation of u and v.  They say nothing about interpolation bias.
+        out: eight Planes of the caller's in the order of SUBSET_UNCERTAINTY_PLANES, None where a plane is not wanted (sigma_u and
+        sigma_v are required, the four gradient sigmas go all or none), which are written and stay on the device; without `out`
+        the call allocates all eight, downloads them and returns arrays.  record: True -- the counts are read back
+        (synchronises) --, an uncertainty_records Plane of the caller's, or False / None.
+        Returns (a tuple of the eight planes, UncertaintyRecord or None)."""
+        if len(nodes) != 6:
+            raise ValueError("subset_uncertainty takes the six planes (u, v, ux, uy, vx, vy)")
+        own_planes = out is None
+        if not own_planes and len(out) != len(SUBSET_UNCERTAINTY_PLANES):
+            raise ValueError("subset_uncertainty takes eight output planes (None: absent) or none")
+        own_record = record is True
+        if own_record and instances != 1:
+            raise ValueError("a lock-step batch takes the caller's records")
+        held = [self.plane(nodes[0].pitch // 4, nh) for _ in SUBSET_UNCERTAINTY_PLANES] if own_planes else list(out)
+        rec = self.uncertainty_records(instances) if own_record else (record or None)
+        pixels = subset_min_pixels(subset_radius) if min_pixels is None else min_pixels
+        try:
+            _check(hip_lib().flow2d_subset_uncertainty_2d(self.handle, f0.ptr, f1.ptr, int(interpolation), w, h, f0.pitch,
+                                                          *[q.ptr for q in nodes], state.ptr, nw, nh, nodes[0].pitch, int(grid_radius),
+                                                          int(spacing), int(subset_radius), int(min_state),
+                                                          mask.ptr if mask is not None else None, int(pixels),
+                                                          *[q.ptr if q is not None else None for q in held],
+                                                          rec.ptr if rec is not None else None), "flow2d_subset_uncertainty_2d")
+            got = [q.download(nw, nh) for q in held] if own_planes else held
+            return tuple(got), (self.read_uncertainty_record(rec, 1)[0] if own_record else None)
+        finally:
+            for q in (held if own_planes else []) + ([rec] if own_record else []):
+                q.free()
+                self._planes.remove(q)
+
     def predict_records(self, instances=1):
         """A Plane for `instances` flow2d_predict_record records (device memory)."""
         return self._record_plane(PREDICT_RECORD_BYTES, instances)
@@ -2123,6 +2189,11 @@ def host_lib():
             L.flow2d_host_compose_records.argtypes = [vp, cp, i]
             L.flow2d_host_compose_nodes_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), i, i, i, C.POINTER(vp), cp]
             L.flow2d_host_compose_nodes.argtypes = [vp, C.POINTER(fp), C.POINTER(fp), i, i, i, C.POINTER(fp), cp]
+        if hasattr(L, "flow2d_host_node_uncertainty_device"):
+            ur = C.POINTER(UncertaintyRecord)
+            L.flow2d_host_uncertainty_options_ok.argtypes = [so, i]
+            L.flow2d_host_node_uncertainty_device.argtypes = [vp, vp, vp, C.POINTER(vp), i, i, so, i, C.POINTER(vp), ur]
+            L.flow2d_host_node_uncertainty.argtypes = [vp, fp, fp, C.POINTER(fp), i, i, so, i, C.POINTER(fp), ur]
         if hasattr(L, "flow2d_host_node_strain_device"):
             ds = C.POINTER(DeformationStats)
             L.flow2d_host_strain_options_ok.argtypes = [i, i, i, i, i]
@@ -3019,6 +3090,66 @@ class OpticalFlow:
                                                          C.byref(rec) if record else None)
         if rc:
             raise Flow2DError(rc, "OpticalFlow2D::ComposeNodesDevice")
+        return rec if record else None
+
+    UNCERTAINTY_PLANES = SUBSET_UNCERTAINTY_PLANES  # what node_uncertainty* write: sigma_u and sigma_v needed, the gradient sigmas all or none
+
+    def node_uncertainty(self, frame_0, frame_1, nodes, grid_radius, spacing, radius, min_state=1, mask=None, min_pixels=0,
+                         interpolation="catmull-rom", record=True):
+        """OpticalFlow2D::NodeUncertainty: the uncertainty of a first-order refinement's nodes (flow2d_subset_uncertainty_2d).  nodes
+        -- a dict of [nh, nw] arrays by the names of SUBSET_PLANES, as correlate_subset* return them (u, v, the gradients and the
+        state are needed) -- is the refinement of (frame_0, frame_1) on the grid (grid_radius, spacing); `radius`, mask (an image) /
+        min_pixels and interpolation are the refinement's.  Per node the covariance s2 * H^-1 of the Gauss-Newton least squares at
+        the node's p: sigma_u, sigma_v and the four gradient sigmas estimate the random error the frames' noise puts into p (not
+        the sample's interpolation bias), rho is the correlation of u and v, noise is sqrt(s2) in grey values.  A node below
+        min_state, off the mask, out of the frame or flat is NaN.  Returns ({name: [nh, nw] array} by the names of
+        UNCERTAINTY_PLANES, UncertaintyRecord or None)."""
+        f0, f1 = self._pair(frame_0, frame_1)
+        nw, nh = correlation_grid(self.width, self.height, grid_radius, spacing)
+        need = self.COMPOSE_BASE
+        if any(n not in nodes for n in need):
+            raise ValueError("node_uncertainty takes %s of the refinement" % ", ".join(need))
+        a = [np.ascontiguousarray(nodes[n], np.float32) for n in need]
+        if any(q.shape != (nh, nw) for q in a):
+            raise ValueError("node_uncertainty takes a node field of the %d x %d grid" % (nw, nh))
+        out = {n: np.empty((nh, nw), np.float32) for n in self.UNCERTAINTY_PLANES}
+        options = self._subset_options("OpticalFlow2D::NodeUncertainty", radius, 20, 1e-3, 2.0, 0.5, 1, 0.05, mask, min_pixels, image=True,
+                                       interpolation=interpolation)
+        fp = C.POINTER(C.c_float)
+        rec = UncertaintyRecord()
+        rc = host_lib().flow2d_host_node_uncertainty(self.handle, _fptr(f0), _fptr(f1), (fp * 7)(*[_fptr(q) for q in a]), int(grid_radius),
+                                                     int(spacing), C.byref(options), int(min_state),
+                                                     (fp * 8)(*[_fptr(out[n]) for n in self.UNCERTAINTY_PLANES]),
+                                                     C.byref(rec) if record else None)
+        if rc:
+            raise Flow2DError(rc, "OpticalFlow2D::NodeUncertainty")
+        return out, (rec if record else None)
+
+    def node_uncertainty_device(self, dev_frame_0, dev_frame_1, dev_nodes, grid_radius, spacing, radius, dev_out, min_state=1, mask=None,
+                                min_pixels=0, interpolation="catmull-rom", record=True, order=1):
+        """OpticalFlow2D::NodeUncertaintyDevice: dev_nodes -- a dict of device planes by the names of SUBSET_PLANES, of which u, v,
+        the gradients and the state are needed --, dev_out -- a dict of device planes by the names of UNCERTAINTY_PLANES (sigma_u
+        and sigma_v needed, the four gradient sigmas all or none) --, planes of the container's size.  mask: a device plane.
+        order=2 is refused: twelve parameters need a 12 x 12 covariance.  Returns the UncertaintyRecord (the call then
+        synchronises) or, without record, None (it only queues)."""
+        unknown = set(dev_out) - set(self.UNCERTAINTY_PLANES)
+        if unknown:
+            raise ValueError("unknown uncertainty planes %s (of %s)" % (sorted(unknown), ", ".join(self.UNCERTAINTY_PLANES)))
+        if order != 1:  # (before the mask's rule: the reason printed is the uncertainty's own)
+            options = SubsetOptions(int(radius), 20, 1e-3, 2.0, 0.5, int(order), 0.05, 0, None)
+            if not host_lib().flow2d_host_uncertainty_options_ok(C.byref(options), int(min_state)):
+                raise Flow2DError(1, "OpticalFlow2D::NodeUncertaintyDevice", "the node uncertainty goes with order 1 only")
+        options = self._subset_options("OpticalFlow2D::NodeUncertaintyDevice", radius, 20, 1e-3, 2.0, 0.5, order, 0.05, mask, min_pixels,
+                                       interpolation=interpolation)
+        rec = UncertaintyRecord()
+        vp = C.c_void_p
+        rc = host_lib().flow2d_host_node_uncertainty_device(self.handle, dev_frame_0, dev_frame_1,
+                                                            (vp * 7)(*[dev_nodes.get(n) for n in self.COMPOSE_BASE]), int(grid_radius),
+                                                            int(spacing), C.byref(options), int(min_state),
+                                                            (vp * 8)(*[dev_out.get(n) for n in self.UNCERTAINTY_PLANES]),
+                                                            C.byref(rec) if record else None)
+        if rc:
+            raise Flow2DError(rc, "OpticalFlow2D::NodeUncertaintyDevice")
         return rec if record else None
 
 

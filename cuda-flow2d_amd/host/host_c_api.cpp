@@ -1094,6 +1094,71 @@ HOST_API int flow2d_host_compose_nodes(flow2d_host_flow* h, const float* const* 
     return 0;
 }
 
+// OpticalFlow2D::UncertaintyOptionsOk: 1 when NodeUncertainty* accept the options (order 1 among it).  Needs no device.
+HOST_API int flow2d_host_uncertainty_options_ok(const flow2d_host_subset_options* options, int min_state)
+{
+    return options && OpticalFlow2D::UncertaintyOptionsOk(subset_options(*options), min_state) ? 1 : 0;
+}
+
+// OpticalFlow2D::NodeUncertaintyDevice: dev_nodes -- seven device planes u, v, ux, uy, vx, vy, state of a first-order refinement, all
+// needed --, dev_out -- eight device planes sigma_u, sigma_v, rho, sigma_ux, sigma_uy, sigma_vx, sigma_vy, noise, of which sigma_u and
+// sigma_v are needed and the four gradient sigmas go all or none.  Of the options the radius, the mask with min_pixels and (beside
+// them, in the object) the interpolation are used; order 2 is refused.  With a record (host) the call synchronises.  0 on success, 1
+// for a null or refused argument, 2 when the run failed.
+HOST_API int flow2d_host_node_uncertainty_device(flow2d_host_flow* h, void* dev_frame_0, void* dev_frame_1, void* const* dev_nodes,
+                                                 int grid_radius, int spacing, const flow2d_host_subset_options* options, int min_state,
+                                                 void* const* dev_out, flow2d_uncertainty_record* record)
+{
+    if (!h || !dev_frame_0 || !dev_frame_1 || !dev_nodes || !options || !dev_out || min_state < 0 || min_state > 1) return 1;
+    for (int k = 0; k < 7; ++k)
+        if (!dev_nodes[k]) return 1;
+    const int gradients = (dev_out[3] != nullptr) + (dev_out[4] != nullptr) + (dev_out[5] != nullptr) + (dev_out[6] != nullptr);
+    if (!dev_out[0] || !dev_out[1] || (gradients != 0 && gradients != 4)) return 1;
+    const auto subset = subset_options(*options, h);
+    if (!OpticalFlow2D::UncertaintyOptionsOk(subset, min_state)) return 1;
+    OpticalFlow2D::SubsetPlanes nodes;
+    nodes = {dp(dev_nodes[0]), dp(dev_nodes[1]), dp(dev_nodes[2]), dp(dev_nodes[3]), dp(dev_nodes[4]), dp(dev_nodes[5]), 0, dp(dev_nodes[6])};
+    const OpticalFlow2D::UncertaintyPlanes out = {dp(dev_out[0]), dp(dev_out[1]), dp(dev_out[2]), dp(dev_out[3]),
+                                                  dp(dev_out[4]), dp(dev_out[5]), dp(dev_out[6]), dp(dev_out[7])};
+    h->flow.timing_mode = 0;
+    return h->flow.NodeUncertaintyDevice(dp(dev_frame_0), dp(dev_frame_1), nodes, grid_radius, spacing, subset, min_state, out, record) ? 0 : 2;
+}
+
+// OpticalFlow2D::NodeUncertainty on tight host arrays: the frames, nodes -- seven arrays of nw * nh floats as above -- and out --
+// eight, as above; options->mask: an image of the frames' size, which the object uploads.
+HOST_API int flow2d_host_node_uncertainty(flow2d_host_flow* h, const float* frame_0, const float* frame_1, const float* const* nodes,
+                                          int grid_radius, int spacing, const flow2d_host_subset_options* options, int min_state,
+                                          float* const* out, flow2d_uncertainty_record* record)
+{
+    if (!h || !frame_0 || !frame_1 || !nodes || !options || !out || min_state < 0 || min_state > 1) return 1;
+    for (int k = 0; k < 7; ++k)
+        if (!nodes[k]) return 1;
+    const int gradients = (out[3] != nullptr) + (out[4] != nullptr) + (out[5] != nullptr) + (out[6] != nullptr);
+    if (!out[0] || !out[1] || (gradients != 0 && gradients != 4)) return 1;
+    const auto subset = subset_options(*options, h);
+    if (!OpticalFlow2D::UncertaintyOptionsOk(subset, min_state)) return 1;
+    size_t nw = 0, nh = 0;
+    if (flow2d_correlation_grid(h->width, h->height, grid_radius, spacing, &nw, &nh) != FLOW2D_OK) return 1;
+    HostImages im(h);
+    Data2D *f0 = im.In(frame_0), *f1 = im.In(frame_1);
+    Data2D* mask = options->mask ? im.In(static_cast<const float*>(options->mask)) : nullptr;
+    std::vector<Data2D> images;
+    images.reserve(15);
+    for (int k = 0; k < 15; ++k) images.emplace_back(nw, nh);
+    Data2D *field[8], *wanted[8];
+    for (int k = 0; k < 7; ++k) {
+        std::memcpy(images[k].DataPtr(), nodes[k], nw * nh * sizeof(float));
+        field[k < 6 ? k : 7] = &images[k];
+    }
+    field[6] = nullptr;  // (the score is not looked at)
+    for (int k = 0; k < 8; ++k) wanted[k] = out[k] ? &images[7 + k] : nullptr;
+    h->flow.NodeUncertainty(*f0, *f1, field, grid_radius, spacing, subset, min_state, wanted, record, mask);
+    if (!h->flow.LastRunSucceeded()) return 2;
+    for (int k = 0; k < 8; ++k)
+        if (out[k]) std::memcpy(out[k], images[7 + k].DataPtr(), nw * nh * sizeof(float));
+    return 0;
+}
+
 // OpticalFlow2D::SequenceOptionsOk.  Needs no device.
 HOST_API int flow2d_host_sequence_options_ok(int fill, int min_state, int min_neighbours, float max_shift)
 {

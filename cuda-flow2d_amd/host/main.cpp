@@ -134,6 +134,12 @@
 // subset mask to the passes in front of the refinement (OpticalFlow2D::SubsetOptions::mask_search), so that an edge node starts from
 // the specimen's motion; the "CorrelationMask:" line is printed before the "SubsetMask:" line.  Without these options no byte of any
 // output changes.
+// --subset-uncertainty, valid only together with --subset-refine at order 1 and not with --subset-base (a composed field's covariance
+// would need both fields'), on the pair chain and on --subset-previous: the covariance s2 * H^-1 of every refined node
+// (flow2d_subset_uncertainty_2d, with the refinement's radius, mask and interpolation).  node-sigma-u, node-sigma-v, node-rho,
+// node-sigma-ux, -uy, -vx, -vy and node-noise are written beside the node files, and one more line, "SubsetUncertainty: {json}" with
+// the counts, is printed last.  The sigmas estimate the random error from the frames' noise, not the interpolation bias.  Without
+// the option no byte of any output changes.
 // --subset-interpolation catmull-rom|bspline, valid only together with --subset-refine, says how frame 1 is sampled
 // (OpticalFlow2D::SubsetOptions::interpolation): with bspline the run prefilters FILE_1 into its cubic B-spline coefficients
 // (flow2d_bspline_prefilter_2d) and refines with flow2d_subset_refine_spline_2d or, with --subset-order 2,
@@ -229,6 +235,7 @@ int main(int argc, char** argv)
     std::vector<OpticalFlow2D::CorrelationPass> correlation_passes;  // --correlation-passes R:D:S[,R:D:S...]
     OpticalFlow2D::SubsetOptions subset;  // --subset-refine R and the --subset-* options
     bool subset_refine = false, subset_option = false;
+    bool subset_uncertainty = false;  // --subset-uncertainty
     bool subset_interpolation_given = false;  // --subset-interpolation catmull-rom|bspline
     OpticalFlow2D::SequenceOptions sequence;  // --subset-previous PREFIX and its options
     std::string subset_previous;
@@ -546,6 +553,7 @@ int main(int argc, char** argv)
         }
         else if (!std::strcmp(argv[i], "--subset-mask-invert")) subset_mask_invert = subset_mask_option = true;
         else if (!std::strcmp(argv[i], "--subset-mask-search")) subset.mask_search = subset_mask_option = true;
+        else if (!std::strcmp(argv[i], "--subset-uncertainty")) subset_uncertainty = subset_option = true;
         else if (!std::strcmp(argv[i], "--correlation-mask")) {
             if (i + 1 >= argc || !argv[i + 1][0]) {
                 std::printf("--correlation-mask takes the file of the mask image.\n");
@@ -747,6 +755,11 @@ int main(int argc, char** argv)
     sequence.max_shift = subset_max_shift_given || subset_previous.empty() ? subset.max_shift : 4.f;
     if (!subset_base.empty() && !subset_refine) {
         std::printf("--subset-base PREFIX composes the field of --subset-refine with the one up to its reference frame.\n");
+        return 5;
+    }
+    if (subset_uncertainty && (subset.order != 1 || !subset_base.empty())) {
+        std::printf("--subset-uncertainty gives the covariance of the first-order refinement (--subset-order 2 would need a 12 x 12 one), "
+                    "and not of a field composed by --subset-base, which would need both fields'.\n");
         return 5;
     }
 
@@ -1128,6 +1141,25 @@ int main(int argc, char** argv)
                 if (subset_strain) {
                     Data2D* fields[7] = {nodes[0], nodes[1], nodes[2], nodes[3], nodes[4], nodes[5], nodes[7]};
                     write_node_strain(fields, nw, nh, fine.spacing);
+                }
+                if (subset_uncertainty && optical_flow.LastRunSucceeded()) {
+                    const char* sigma_names[8] = {"node-sigma-u",  "node-sigma-v",  "node-rho",      "node-sigma-ux",
+                                                  "node-sigma-uy", "node-sigma-vx", "node-sigma-vy", "node-noise"};
+                    std::vector<Data2D> sigmas;
+                    for (int k = 0; k < 8; ++k) sigmas.emplace_back(nw, nh);
+                    Data2D* wanted[8];
+                    for (int k = 0; k < 8; ++k) wanted[k] = &sigmas[k];
+                    flow2d_uncertainty_record counts = {};
+                    // (on --subset-previous the nodes below --subset-min-state were not a start either; the pair chain keeps 1)
+                    optical_flow.NodeUncertainty(frame_0, frame_1, nodes, fine.radius, fine.spacing, subset, sequence.min_state, wanted, &counts,
+                                                 subset_mask_image);
+                    if (optical_flow.LastRunSucceeded()) {
+                        for (int k = 0; k < 8; ++k) sigmas[k].WriteRAWToFileF32((output_path + counter + sigma_names[k] + size).c_str());
+                        std::printf("SubsetUncertainty: {\"radius\": %d, \"min_state\": %d, \"nodes\": %llu, \"evaluated\": %llu, "
+                                    "\"skipped\": %llu, \"masked\": %llu, \"outside\": %llu, \"flat\": %llu, \"thin\": %llu}\n",
+                                    subset.radius, sequence.min_state, counts.nodes, counts.evaluated, counts.skipped, counts.masked,
+                                    counts.outside, counts.flat, counts.thin);
+                    }
                 }
             }
         } else if (multipass) {

@@ -480,6 +480,32 @@ public:
     void ComposeNodes(Data2D* const* base, Data2D* const* increment, int grid_radius, int spacing, int min_state, Data2D* const* nodes,
                       flow2d_compose_record* record_out = nullptr);
 
+    // The uncertainty of a first-order refinement's nodes (flow2d_subset_uncertainty_2d): per node the covariance s2 * H^-1 of
+    // p -- the standard deviations of u, v and the four gradients, the correlation of u and v, and sqrt(s2) in grey values.  They
+    // estimate the random error the frames' noise puts into p and say nothing about the sample's interpolation bias.
+    struct UncertaintyPlanes {
+        DevicePtr sigma_u = 0, sigma_v = 0;                                // needed
+        DevicePtr rho = 0;                                                 // optional
+        DevicePtr sigma_ux = 0, sigma_uy = 0, sigma_vx = 0, sigma_vy = 0;  // all or none
+        DevicePtr noise = 0;                                               // optional
+    };
+    // `nodes` holds u, v, the four gradients and the state of a first-order refinement of (dev_frame_0, dev_frame_1) on the grid
+    // (grid_radius, spacing); a node below min_state (0 or 1) is skipped.  Of `subset` the radius, the mask with min_pixels (0: the
+    // default) and the interpolation are used: with BSpline frame 1 is prefiltered into the object's coefficient plane first.
+    // Refused, with a printed reason, for subset.order == 2 and for curvature planes: twelve parameters need a 12 x 12
+    // covariance, which is not built here.  record_out (host, optional): the counts, read back -- the call then synchronises,
+    // otherwise it only queues.  Not for lock-step groups.
+    // prints what is wrong (order 2 among it); needs no device
+    static bool UncertaintyOptionsOk(const SubsetOptions& subset, int min_state);
+    bool NodeUncertaintyDevice(DevicePtr dev_frame_0, DevicePtr dev_frame_1, const SubsetPlanes& nodes, int grid_radius, int spacing,
+                               const SubsetOptions& subset, int min_state, const UncertaintyPlanes& out,
+                               flow2d_uncertainty_record* record_out = nullptr);
+    // The host-image form: nodes[8] -- u, v, ux, uy, vx, vy, score, state as CorrelateSubset delivers them, the score not looked at
+    // and optional -- and out[8] -- sigma_u, sigma_v, rho, sigma_ux, sigma_uy, sigma_vx, sigma_vy, noise --, images of the grid;
+    // mask (optional): an image of the frames' size in place of subset.mask, which this form does not look at.
+    void NodeUncertainty(Data2D& frame_0, Data2D& frame_1, Data2D* const* nodes, int grid_radius, int spacing, const SubsetOptions& subset,
+                         int min_state, Data2D* const* out, flow2d_uncertainty_record* record_out = nullptr, Data2D* mask = nullptr);
+
     // One later step on its own, for a sequence that arrives frame by frame (the CLI's --subset-previous): `previous` holds the
     // last step's u, v, gradients and state (its score is not looked at); the prediction's passes and the refinement of
     // (dev_frame_0, dev_frame_k) with sequence.max_shift into `out`, as CorrelateSubsetSequenceDevice runs them per step.
@@ -870,6 +896,8 @@ private:
                            const SubsetPlanes& out, flow2d_compose_record* record);
     // ComposeNodesDevice: its record
     DeviceScratch compose_scratch_{owned_};
+    // NodeUncertaintyDevice: its record
+    DeviceScratch uncertainty_scratch_{owned_};
     // NodeStrain*: per step the record and, behind it, the workspace
     DeviceScratch strain_scratch_{owned_};
     // ComputeFlowFromPrior*: inside such a run the prior's planes and the start level (RunPyramid starts there, from them); the

@@ -1527,6 +1527,121 @@ void OpticalFlow2D::ComposeNodes(Data2D* const* base, Data2D* const* increment, 
     last_run_ok_ = ok;
 }
 
+bool OpticalFlow2D::UncertaintyOptionsOk(const SubsetOptions& subset, int min_state)
+{
+    if (subset.order == 2) {
+        std::printf("Error: the node uncertainty is that of the first-order refinement: twelve parameters need a 12 x 12 covariance, "
+                    "which is not built here (order %d).\n",
+                    subset.order);
+        return false;
+    }
+    if (!SubsetOptionsOk(subset)) return false;
+    if (min_state != 0 && min_state != 1) {
+        std::printf("Error: the node uncertainty takes a least state of 0 or 1 (%d).\n", min_state);
+        return false;
+    }
+    return true;
+}
+
+bool OpticalFlow2D::NodeUncertaintyDevice(DevicePtr dev_frame_0, DevicePtr dev_frame_1, const SubsetPlanes& nodes, int grid_radius,
+                                          int spacing, const SubsetOptions& subset, int min_state, const UncertaintyPlanes& out,
+                                          flow2d_uncertainty_record* record_out)
+{
+    const size_t W = dev_container_size_.width, H = dev_container_size_.height, pitch = dev_container_size_.pitch;
+    if (!UncertaintyOptionsOk(subset, min_state)) return false;
+    if (nodes.uxx || nodes.uxy || nodes.uyy || nodes.vxx || nodes.vxy || nodes.vyy) {
+        std::printf("Error: '%s': the node uncertainty takes no curvature planes: twelve parameters need a 12 x 12 covariance, which is "
+                    "not built here.\n",
+                    GetName());
+        return false;
+    }
+    size_t nw = 0, nh = 0;
+    if (flow2d_correlation_grid(W, H, grid_radius, spacing, &nw, &nh) != FLOW2D_OK) {
+        std::printf("Error: a %zu x %zu frame holds no node grid of radius %d and spacing %d.\n", W, H, grid_radius, spacing);
+        return false;
+    }
+    if (!IsInitialized() || !dev_frame_0 || !dev_frame_1) return false;
+    if (!nodes.u || !nodes.v || !nodes.ux || !nodes.uy || !nodes.vx || !nodes.vy || !nodes.state) {
+        std::printf("Error: '%s': the node uncertainty needs u, v, the four gradients and the state of a refinement.\n", GetName());
+        return false;
+    }
+    const bool gradients = out.sigma_ux != 0;
+    if (!out.sigma_u || !out.sigma_v || (out.sigma_uy != 0) != gradients || (out.sigma_vx != 0) != gradients ||
+        (out.sigma_vy != 0) != gradients) {
+        std::printf("Error: '%s': the node uncertainty writes sigma_u and sigma_v, and the four gradient sigmas all or none.\n", GetName());
+        return false;
+    }
+    if (RefuseGroup("the node uncertainty")) return false;
+    if (record_out && !uncertainty_scratch_.Ensure(context_, sizeof(flow2d_uncertainty_record))) return false;
+    flow2d_uncertainty_record* record = record_out ? uncertainty_scratch_.At<flow2d_uncertainty_record>() : nullptr;
+    auto plane = [](DevicePtr p) { return p ? AsPlane(p) : nullptr; };
+    const bool spline = subset.interpolation == SubsetOptions::BSpline;
+    if (spline) {
+        // frame 1's coefficients, on the same stream in front of the kernel that samples them
+        if (!EnsurePlanes(spline_plane_, 1) ||
+            CheckFlow2DError(flow2d_bspline_prefilter_2d(context_, AsPlane(dev_frame_1), AsPlane(spline_plane_[0]), W, H, pitch),
+                             "flow2d_bspline_prefilter_2d"))
+            return false;
+    }
+    // (the node planes are containers: the frames' pitch; the entry refuses planes that meet)
+    bool ok = !CheckFlow2DError(
+        flow2d_subset_uncertainty_2d(context_, AsPlane(dev_frame_0), AsPlane(spline ? spline_plane_[0] : dev_frame_1), spline ? 1 : 0, W, H,
+                                     pitch, AsPlane(nodes.u), AsPlane(nodes.v), AsPlane(nodes.ux), AsPlane(nodes.uy), AsPlane(nodes.vx),
+                                     AsPlane(nodes.vy), AsPlane(nodes.state), nw, nh, pitch, grid_radius, spacing, subset.radius, min_state,
+                                     plane(subset.mask), SubsetMinPixels(subset), AsPlane(out.sigma_u), AsPlane(out.sigma_v), plane(out.rho),
+                                     plane(out.sigma_ux), plane(out.sigma_uy), plane(out.sigma_vx), plane(out.sigma_vy), plane(out.noise),
+                                     record),
+        "flow2d_subset_uncertainty_2d");
+    if (!ok || !record_out) return ok;
+    ok = ReadRecord(record_out, record, sizeof(*record_out));
+    return !CheckFlow2DError(flow2d_synchronize(context_), "flow2d_synchronize") && ok;
+}
+
+void OpticalFlow2D::NodeUncertainty(Data2D& frame_0, Data2D& frame_1, Data2D* const* nodes, int grid_radius, int spacing,
+                                    const SubsetOptions& subset, int min_state, Data2D* const* out, flow2d_uncertainty_record* record_out,
+                                    Data2D* mask)
+{
+    last_run_ok_ = false;
+    if (!IsInitialized() || !nodes || !out || !out[0] || !out[1]) return;
+    for (int k = 0; k < 8; ++k)
+        if (k != 6 && !nodes[k]) return;
+    const size_t W = dev_container_size_.width, H = dev_container_size_.height;
+    size_t nw = 0, nh = 0;
+    if (flow2d_correlation_grid(W, H, grid_radius, spacing, &nw, &nh) != FLOW2D_OK) {
+        std::printf("Error: a %zu x %zu frame holds no node grid of radius %d and spacing %d.\n", W, H, grid_radius, spacing);
+        return;
+    }
+    for (int k = 0; k < 16; ++k) {
+        Data2D* image = k < 8 ? (k == 6 ? nullptr : nodes[k]) : out[k - 8];
+        if (image && (image->Width() != nw || image->Height() != nh)) {
+            std::printf("Error: '%s': the node images are not %zu x %zu.\n", GetName(), nw, nh);
+            return;
+        }
+    }
+    CallPlanes planes(context_, dev_container_size_, GetName(), "frame");
+    planes.Add(&frame_0, CallPlanes::In).Add(&frame_1, CallPlanes::In);
+    // the node planes, read and written: containers with no image of their size behind them, uploaded and downloaded here
+    for (int k = 0; k < 8; ++k) planes.Add(nullptr, CallPlanes::Out, k != 6);
+    for (int k = 0; k < 8; ++k) planes.Add(nullptr, CallPlanes::Out, out[k] != nullptr);
+    if (mask) planes.Add(mask, CallPlanes::In);  // behind everything else
+    if (!planes.SizesMatch()) return;
+    HostCall call(context_, last_total_ms_, planes.Allocate());
+    const DevicePtr* d = planes.data();
+    bool ok = planes.Upload();
+    for (int k = 0; ok && k < 8; ++k)
+        if (k != 6) ok = CopyData2DtoDevice(*nodes[k], d[2 + k], H, dev_container_size_.pitch);
+    SubsetPlanes field;
+    field = {d[2], d[3], d[4], d[5], d[6], d[7], 0, d[9]};
+    const UncertaintyPlanes planes_out = {d[10], d[11], d[12], d[13], d[14], d[15], d[16], d[17]};
+    SubsetOptions masked = subset;
+    masked.mask = mask ? d[18] : 0;
+    ok = ok && NodeUncertaintyDevice(d[0], d[1], field, grid_radius, spacing, masked, min_state, planes_out, record_out);
+    // (without a record the device call only queues: the downloads below are ordered behind it on the stream)
+    for (int k = 0; ok && k < 8; ++k)
+        if (out[k]) ok = CopyData2DFromDevice(d[10 + k], *out[k], H, dev_container_size_.pitch);
+    last_run_ok_ = ok;
+}
+
 void OpticalFlow2D::CorrelateSubsetSequence(Data2D* const* frames, size_t frame_count, const CorrelationPass* passes, size_t count,
                                             float min_score, const ValidationOptions& validation, const SubsetOptions& subset,
                                             const SequenceOptions& sequence, Data2D* const* nodes, CorrelationPassReport* first_reports,

@@ -1361,6 +1361,88 @@ FLOW2D_API int flow2d_subset_refine2_spline_2d(flow2d_context* ctx, const float*
                                                float* out_score /* may be NULL */, float* out_state /* may be NULL */,
                                                flow2d_subset_record* record /* device, may be NULL */);
 
+/* The uncertainty of a first-order refinement's nodes: per node the covariance of p = (u, ux, uy, v, vx, vy) as the Gauss-Newton
+ * least squares gives it, Cov(p) ~ s2 * H^-1 (Sutton, Orteu & Schreier 2009, ch. 5; Wang, Sutton et al. 2009) -- the residual
+ * variance s2 of the ZNSSD at the node's p times the inverse of the Hessian the refinement factors.  One evaluation per node, no
+ * iteration.  It estimates the RANDOM error the frames' noise puts into p; it says nothing about the interpolation bias of the
+ * sample (a noise-free pair gives the interpolation residual's small s2, not 0 bias).  Added to ABI version 1 without changing
+ * any existing entry.
+ * Inputs.  frame_0; frame_1, which is frame 1 with interpolation = 0 (the Catmull-Rom sample, the sampling rules of
+ * flow2d_subset_refine_masked_2d word for word) and frame 1's coefficients, as flow2d_bspline_prefilter_2d made them, with
+ * interpolation = 1 (the cubic B-spline sample, the rules of flow2d_subset_refine_spline_2d word for word).  The six node planes
+ * node_u, node_v, node_ux, node_uy, node_vx, node_vy of a first-order refinement and its state plane node_state, all required,
+ * nw x nh floats with node_pitch_bytes per row.  grid_radius, spacing and subset_radius (1 .. FLOW2D_SUBSET_MAX_RADIUS) as in
+ * flow2d_subset_refine_2d; min_state (0 or 1).  mask (may be NULL) and min_pixels as in flow2d_subset_refine_masked_2d: *excluded*
+ * and *usable* are that text's, and without a mask every pixel of the subset is usable and min_pixels is not looked at.
+ * Everything below is IEEE double with every operation rounded on its own, no fused multiply-add, division and square root
+ * correctly rounded, every test a positive comparison, as in flow2d_subset_refine_2d's text; the order in which the terms of a
+ * *sum over the subset* are added is again the one thing left open.
+ * Per node, the first rule that applies ends it:
+ *   1. *Masked*: the centre pixel (cx, cy) is excluded (only with a mask).
+ *   2. *Skipped*: !(state >= (float)min_state), or any of the six inputs is not finite.  The states
+ *      FLOW2D_SUBSET_STATE_PREDICTED (65) and FLOW2D_SUBSET_STATE_COMPOSED (66) pass, so that a predicted or composed field can
+ *      be evaluated against the frames it refers to.
+ *   3. *Outside*: the frame-0 window test of flow2d_subset_refine_2d fails.
+ *   4. With a mask: Nv = the number of usable pixels; *masked* when !(Nv >= min_pixels).  N stands for Nv below and every sum
+ *      runs over the list of usable pixels in ascending k.
+ *   5. *Thin*: !(N >= 9).  The degrees of freedom are N - 8: the six shape parameters, and the offset and the scale of the ZNSSD.
+ *   6. The frame-0 quantities, J, H, Cholesky and Solve exactly as flow2d_subset_refine_2d's text has them.  *Flat* when
+ *      !(Df2 > 0) or when a pivot fails its test.
+ *   7. p = the six inputs, each converted to double.  Positions X, Y as in step 1 of that text's iteration.  *Outside* unless
+ *      every one of them has X >= 0, X <= width - 1, Y >= 0 and Y <= height - 1.
+ *   8. g sampled at (X, Y).  gm = (sum of g) / N;   gd = g - gm;   Dg2 = sum of gd*gd;   *flat* when !(Dg2 > 0);
+ *      Dg = sqrt(Dg2);   q = Df / Dg;   res = fd - q*gd.
+ *   9. S = sum of res*res;   s2 = S / (double)(N - 8).
+ *  10. x_a = Solve(e_a) for a = 0 .. 5, e_a the a-th unit vector: the columns of H^-1.
+ *  11. sigma_u = sqrt(s2 * x_0[0]);   sigma_v = sqrt(s2 * x_3[3]);   sigma_ux, sigma_uy, sigma_vx, sigma_vy likewise from
+ *      x_1[1], x_2[2], x_4[4], x_5[5].
+ *  12. rho = x_0[3] / sqrt(x_0[0] * x_3[3]), the correlation of u and v.
+ *  13. noise = sqrt(s2), in grey values: what the residual says the noise of fd - q*gd is.  Each output is cast to float.
+ * Outputs, nw x nh floats with node_pitch_bytes per row: out_sigma_u, out_sigma_v (required); out_rho (may be NULL); the four
+ * gradient sigmas, all or none; out_noise (may be NULL).  A node that ends early gets NaN (0x7FC00000) in every plane given.
+ * Record.  record[b] (DEVICE memory, may be NULL), 64 bytes: nodes (nw * nh); evaluated; skipped; masked; outside; flat; thin;
+ * one reserved word, written as 0.  Integers, added by integer atomics after the entry has zeroed the record on the stream:
+ * alone, in a batch and in a replayed graph the same bytes.
+ * Row padding and the containers beyond width x height and nw x nh are neither read into a result nor written.  One launch on the
+ * context's stream (and a 64-byte memset per instance with a record); no allocation, no synchronisation (graph-capturable).
+ * Honours flow2d_context_set_batch: frames, mask and node planes of instance b at b * stride floats, record + b.
+ * FLOW2D_ERR_INVALID_ARGUMENT, and nothing written, for a null frame, input plane, out_sigma_u or out_sigma_v, a zero size, a bad
+ * pitch (the rule of flow2d_consistency_2d), an interpolation or min_state that is neither 0 nor 1, a grid_radius, spacing or
+ * subset_radius outside its limits, a grid that does not lie inside the frame, with a mask a min_pixels outside
+ * FLOW2D_SUBSET_MIN_PIXELS .. (2R + 1)^2 or a mask that breaks the frames' plane rules, gradient sigmas given in part, a
+ * misaligned record (8), or a written range -- the outputs, the records, over every instance of a batch -- that overlaps a
+ * frame, the mask, an input plane or another written range; FLOW2D_ERR_UNSUPPORTED for 2^31 nodes or more. */
+typedef struct flow2d_uncertainty_record {
+    unsigned long long nodes;     /* nw * nh */
+    unsigned long long evaluated; /* nodes with a covariance */
+    unsigned long long skipped;   /* state below min_state, or an input that is not finite */
+    unsigned long long masked;    /* centre excluded, or fewer than min_pixels usable pixels */
+    unsigned long long outside;   /* the subset leaves frame 0, or a position leaves frame 1 */
+    unsigned long long flat;      /* Df2 or Dg2 not positive, or a pivot failed */
+    unsigned long long thin;      /* fewer than nine usable pixels */
+    unsigned long long reserved;  /* 0 */
+} flow2d_uncertainty_record;
+
+#define FLOW2D_UNCERTAINTY_RECORD_BYTES 64
+#ifdef __cplusplus
+static_assert(sizeof(flow2d_uncertainty_record) == FLOW2D_UNCERTAINTY_RECORD_BYTES, "flow2d_uncertainty_record layout");
+#else
+_Static_assert(sizeof(flow2d_uncertainty_record) == FLOW2D_UNCERTAINTY_RECORD_BYTES, "flow2d_uncertainty_record layout");
+#endif
+
+FLOW2D_API int flow2d_subset_uncertainty_2d(flow2d_context* ctx, const float* frame_0,
+                                            const float* frame_1 /* interpolation 1: its B-spline coefficients */,
+                                            int interpolation /* 0 Catmull-Rom, 1 B-spline */, size_t width, size_t height,
+                                            size_t pitch_bytes, const float* node_u, const float* node_v, const float* node_ux,
+                                            const float* node_uy, const float* node_vx, const float* node_vy,
+                                            const float* node_state, size_t nw, size_t nh, size_t node_pitch_bytes, int grid_radius,
+                                            int spacing, int subset_radius, int min_state,
+                                            const float* mask /* device, may be NULL */, int min_pixels, float* out_sigma_u,
+                                            float* out_sigma_v, float* out_rho /* may be NULL */,
+                                            float* out_sigma_ux /* the four gradient sigmas: all or none */, float* out_sigma_uy,
+                                            float* out_sigma_vx, float* out_sigma_vy, float* out_noise /* may be NULL */,
+                                            flow2d_uncertainty_record* record /* device, may be NULL */);
+
 /* The start of the next step of a sequence from a step's result, out of place: a node the refinement found is kept, every other
  * node is predicted from its neighbours.  Every node is judged against the input, so the result depends on no order.
  * Inputs: the six planes node_u, node_v, node_ux, node_uy, node_vx, node_vy and node_state (the outputs of
