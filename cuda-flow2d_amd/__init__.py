@@ -235,6 +235,22 @@ def node_strain_robust_counts(stats):
     return {"touched": int(stats.reserved[3]), "rejected": int(stats.reserved[4]), "suspect": int(stats.reserved[5])}
 
 
+# the planes of flow2d_node_strain_weighted_2d's standard deviations in the order of flow2d_strain_sigma_planes
+STRAIN_SIGMA_PLANES = ("sigma_ux", "sigma_uy", "sigma_vx", "sigma_vy", "sigma_divergence", "sigma_vorticity", "sigma_exx", "sigma_eyy",
+                       "sigma_exy")
+
+
+class StrainSigmaPlanes(C.Structure):
+    """flow2d_strain_sigma_planes: a host struct of nine device pointers, NULL = not requested."""
+    _fields_ = [(name, C.c_void_p) for name in STRAIN_SIGMA_PLANES]
+
+
+def node_strain_weighted_counts(stats):
+    """The four words a weighted node strain adds to its DeformationStats record: those of node_strain_robust_counts and
+    "unweighable", the nodes of the grid that are usable but have no variance to weight them by."""
+    return dict(node_strain_robust_counts(stats), unweighable=int(stats.reserved[6]))
+
+
 REFINE_MAX_RADIUS = 7  # FLOW2D_REFINE_MAX_RADIUS
 
 
@@ -659,6 +675,12 @@ def hip_lib():
             L.flow2d_node_strain_robust_workspace_bytes.argtypes = [sz, sz, sz]
             L.flow2d_node_strain_robust_2d.argtypes = [vp] + [vp] * 3 + [sz, sz, sz, i, i, i, i, i, i, C.c_float, i,
                                                                         C.POINTER(DeformationPlanes), C.POINTER(NodeStrainDiagnostics), vp, vp, sz]
+        if hasattr(L, "flow2d_node_strain_weighted_2d"):
+            L.flow2d_node_strain_weighted_workspace_bytes.restype = sz
+            L.flow2d_node_strain_weighted_workspace_bytes.argtypes = [sz, sz, sz]
+            L.flow2d_node_strain_weighted_2d.argtypes = [vp] + [vp] * 5 + [sz, sz, sz, i, i, i, i, i, i, C.c_float, C.c_float, i,
+                                                                          C.POINTER(DeformationPlanes), C.POINTER(NodeStrainDiagnostics),
+                                                                          C.POINTER(StrainSigmaPlanes), vp, vp, sz]
         if hasattr(L, "flow2d_subset_uncertainty_2d"):  # (absent from libraries of earlier rounds loaded for an A/B)
             L.flow2d_subset_uncertainty_2d.argtypes = [vp, vp, vp, i, sz, sz, sz] + [vp] * 7 + [sz, sz, sz, i, i, i, i, vp, i] + [vp] * 9
         if hasattr(L, "flow2d_compose_nodes_2d"):  # (absent from libraries of earlier rounds loaded for an A/B)
@@ -1878,6 +1900,68 @@ class Context:
                 q.free()
                 self._planes.remove(q)
 
+    @staticmethod
+    def node_strain_weighted_workspace_bytes(nw, nh, instances=1):
+        """flow2d_node_strain_weighted_workspace_bytes: what node_strain_weighted needs beside a record (host logic, no device)."""
+        return hip_lib().flow2d_node_strain_weighted_workspace_bytes(nw, nh, instances)
+
+    def node_strain_weighted(self, node_u, node_v, sigma_u, sigma_v, nw, nh, spacing, window=2, order=1, min_nodes=0, min_state=1,
+                             measure=STRAIN_SMALL, sigma_floor=0.0, threshold=0.0, iterations=0, state=None, planes=DEFORMATION_PLANES,
+                             diagnostics=(), sigmas=STRAIN_SIGMA_PLANES, stats=True, instances=1):
+        """Weighted strain windows (flow2d_node_strain_weighted_2d): `node_strain` with window >= 1 as a Gauss-Markov fit whose
+        weights are 1 / (sigma^2 + sigma_floor^2) from the Planes sigma_u, sigma_v of `subset_uncertainty`, with the standard
+        deviations of the strain.  threshold > 0: `iterations` reweighted passes as in `node_strain_robust`, the scale in sigmas.
+        sigmas: names of STRAIN_SIGMA_PLANES (downloaded into the returned dict) or a dict of the caller's Planes by those names;
+        diagnostics likewise.  The record's reserved[3 .. 6] are read by node_strain_weighted_counts.  Otherwise as `node_strain`."""
+        L = hip_lib()
+        if min_nodes == 0:
+            min_nodes = (6 if order == 2 else 3) + 1
+        groups = []
+        for given, names in ((planes, DEFORMATION_PLANES), (diagnostics, NODE_STRAIN_DIAGNOSTICS), (sigmas, STRAIN_SIGMA_PLANES)):
+            own = not isinstance(given, dict)
+            held = {name: self.plane(node_u.width, node_u.height) for name in given} if own else dict(given)
+            groups.append((own, held, names))
+        unknown = [name for _, held, names in groups for name in held if name not in names]
+        if unknown:
+            for own, held, _ in groups:
+                for q in (held.values() if own else ()):
+                    q.free()
+                    self._planes.remove(q)
+            raise ValueError("deformation planes are %s, diagnostics %s and sigmas %s, not %s" %
+                             (", ".join(DEFORMATION_PLANES), ", ".join(NODE_STRAIN_DIAGNOSTICS), ", ".join(STRAIN_SIGMA_PLANES), unknown))
+        out = DeformationPlanes(**{name: q.ptr for name, q in groups[0][1].items()})
+        diag = NodeStrainDiagnostics(**{name: q.ptr for name, q in groups[1][1].items()})
+        sig = StrainSigmaPlanes(**{name: q.ptr for name, q in groups[2][1].items()})
+        own_stats = stats is True
+        if own_stats and instances != 1:
+            raise ValueError("a lock-step batch takes the caller's records")
+        record = self.deformation_records(instances) if own_stats else (stats or None)
+        workspace, need = None, 0
+        if record is not None:
+            need = L.flow2d_node_strain_weighted_workspace_bytes(nw, nh, instances)
+            cached = getattr(self, "_node_strain_weighted_workspace", None)
+            if cached is None or cached[0] < need:
+                if cached is not None:
+                    cached[1].free()
+                    self._planes.remove(cached[1])
+                self._node_strain_weighted_workspace = cached = (need, self.plane(max(need // 4, 4), 1))
+            workspace = cached[1]
+        try:
+            _check(L.flow2d_node_strain_weighted_2d(self.handle, node_u.ptr, node_v.ptr, state.ptr if state is not None else None,
+                                                    sigma_u.ptr, sigma_v.ptr, nw, nh, node_u.pitch, int(spacing), int(window), int(order),
+                                                    int(min_nodes), int(min_state), int(measure), float(sigma_floor), float(threshold),
+                                                    int(iterations), C.byref(out), C.byref(diag), C.byref(sig),
+                                                    record.ptr if record is not None else None, workspace.ptr if workspace else None, need),
+                   "flow2d_node_strain_weighted_2d")
+            result = {}
+            for own, held, _ in groups:
+                result.update({name: q.download(nw, nh) for name, q in held.items()} if own else held)
+            return result, (self.read_deformation_stats(record, 1)[0] if own_stats else None)
+        finally:
+            for q in [q for own, held, _ in groups if own for q in held.values()] + ([record] if own_stats else []):
+                q.free()
+                self._planes.remove(q)
+
     def resample_x(self, src, dst, out_w, out_h, in_w):
         _check(hip_lib().flow2d_resample_x(self.handle, src.ptr, dst.ptr, out_w, out_h, in_w, src.pitch),
                "flow2d_resample_x")
@@ -2203,6 +2287,13 @@ def host_lib():
             L.flow2d_host_strain_robust_options_ok.argtypes = [i, i, i, i, i, C.c_float, i]
             L.flow2d_host_set_strain_robust.argtypes = [vp, C.c_float, i]
             L.flow2d_host_set_strain_diagnostics.argtypes = [vp, C.POINTER(vp), i]
+        if hasattr(L, "flow2d_host_set_strain_weighting"):
+            L.flow2d_host_strain_weighted_options_ok.argtypes = [i, i, i, i, i, C.c_float, C.c_float, C.c_float, i]
+            L.flow2d_host_set_strain_weighting.argtypes = [vp, i, C.c_float, C.c_float, i]
+            L.flow2d_host_node_strain_weighted_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), i, sz, sz, i, i, i, i, i, i,
+                                                                  C.POINTER(vp), C.POINTER(vp), ds]
+            L.flow2d_host_node_strain_weighted.argtypes = [vp, C.POINTER(fp), C.POINTER(fp), i, sz, sz, i, i, i, i, i, i, C.POINTER(fp),
+                                                           C.POINTER(fp), ds]
         if hasattr(L, "flow2d_host_correlate"):
             cr = C.POINTER(CorrelationRecord)
             L.flow2d_host_correlation_args_ok.argtypes = [sz, sz, f, f, i, i, i, f]
@@ -3156,8 +3247,14 @@ class OpticalFlow:
     NODE_PLANES = ("u", "v", "ux", "uy", "vx", "vy", "state")  # what node_strain* read of a step's SUBSET_PLANES
 
     @staticmethod
-    def strain_options_ok(window=2, order=1, min_nodes=0, min_state=1, measure=STRAIN_SMALL, sigma=0.0, iterations=8):
-        """OpticalFlow2D::StrainOptionsOk: whether node_strain* accept the options.  Needs no device."""
+    def strain_options_ok(window=2, order=1, min_nodes=0, min_state=1, measure=STRAIN_SMALL, sigma=0.0, iterations=8, weighted=False,
+                          sigma_floor=0.0, threshold=0.0):
+        """OpticalFlow2D::StrainOptionsOk: whether node_strain* accept the options.  Needs no device.  weighted: the options of a
+        call with uncertainty= (a robust sigma beside it is refused: one scale is in pixels, the other in sigmas)."""
+        if weighted:
+            return bool(host_lib().flow2d_host_strain_weighted_options_ok(int(window), int(order), int(min_nodes), int(min_state),
+                                                                          int(measure), float(sigma), float(sigma_floor), float(threshold),
+                                                                          int(iterations)))
         if sigma == 0.0:
             return bool(host_lib().flow2d_host_strain_options_ok(int(window), int(order), int(min_nodes), int(min_state), int(measure)))
         return bool(host_lib().flow2d_host_strain_robust_options_ok(int(window), int(order), int(min_nodes), int(min_state), int(measure),
@@ -3173,8 +3270,22 @@ class OpticalFlow:
         L.flow2d_host_set_strain_diagnostics(self.handle, (C.c_void_p * len(diagnostics))(*diagnostics) if diagnostics else None,
                                              steps if diagnostics else 0)
 
+    def _set_strain_weighting(self, sigma, sigma_floor, threshold, iterations, diagnostics, steps):
+        """The weighting of the weighted node-strain call that follows and its diagnostic planes; afterwards the object is as it
+        was, so that a later plain or robust call is not weighted."""
+        L = host_lib()
+        if L.flow2d_host_set_strain_robust(self.handle, float(sigma), int(iterations)) or \
+                L.flow2d_host_set_strain_weighting(self.handle, 1, float(sigma_floor), float(threshold), int(iterations) if threshold > 0 else 0):
+            raise ValueError("node_strain: sigma_floor and threshold are finite and >= 0, iterations 0 .. %d" % NODE_STRAIN_MAX_ITERATIONS)
+        L.flow2d_host_set_strain_diagnostics(self.handle, (C.c_void_p * len(diagnostics))(*diagnostics) if diagnostics else None,
+                                             steps if diagnostics else 0)
+
+    def _clear_strain_weighting(self):
+        host_lib().flow2d_host_set_strain_weighting(self.handle, 0, 0.0, 0.0, 0)
+
     def node_strain(self, nodes, spacing, window=2, order=1, min_nodes=0, min_state=1, measure=STRAIN_SMALL, planes=DEFORMATION_PLANES,
-                    stats=True, sigma=0.0, iterations=8, diagnostics=()):
+                    stats=True, sigma=0.0, iterations=8, diagnostics=(), uncertainty=None, sigma_floor=0.0, threshold=0.0,
+                    strain_sigmas=()):
         """OpticalFlow2D::NodeStrain: strain on the node grid (flow2d_node_strain_2d) of one result -- the dict of [nh, nw] arrays
         by the names of SUBSET_PLANES that correlate_subset returns; u and v are needed, the gradients only with window 0, without a
         state every finite node is usable -- or of the list of steps that correlate_subset_sequence returns.  `window` nodes around
@@ -3182,7 +3293,11 @@ class OpticalFlow:
         coefficients.  sigma > 0: the robust fit (flow2d_node_strain_robust_2d) with `iterations` reweighted passes; diagnostics --
         names of NODE_STRAIN_DIAGNOSTICS -- then come back in the dict beside the planes, and node_strain_robust_counts reads the
         record's further words.  Returns ({name: [nh, nw] array} for `planes`, DeformationStats or None), or the list of those per
-        step."""
+        step.
+        uncertainty -- the dict node_uncertainty returned (sigma_u and sigma_v are read), or a list of them, one per step: the
+        weighted fit (flow2d_node_strain_weighted_2d) with sigma_floor in pixels and `threshold` in sigmas (0: no robust part;
+        above 0: `iterations` reweighted passes); strain_sigmas -- names of STRAIN_SIGMA_PLANES -- come back in the dict, and
+        node_strain_weighted_counts reads the record's further words.  Not together with sigma > 0."""
         single = isinstance(nodes, dict)
         steps = [nodes] if single else list(nodes)
         if not steps or any("u" not in q or "v" not in q for q in steps):
@@ -3191,6 +3306,55 @@ class OpticalFlow:
         if unknown:
             raise ValueError("deformation planes are %s, not %s" % (", ".join(DEFORMATION_PLANES), unknown))
         nh, nw = np.shape(steps[0]["u"])
+        if uncertainty is None and (strain_sigmas or sigma_floor or threshold):
+            raise ValueError("node_strain: sigma_floor, threshold and strain_sigmas go with uncertainty=")
+        if uncertainty is not None:
+            sig_steps = [uncertainty] if isinstance(uncertainty, dict) else list(uncertainty)
+            if len(sig_steps) != len(steps) or any("sigma_u" not in q or "sigma_v" not in q for q in sig_steps):
+                raise ValueError("node_strain takes one uncertainty with sigma_u and sigma_v per step")
+            unknown = [n for n in diagnostics if n not in NODE_STRAIN_DIAGNOSTICS] + [n for n in strain_sigmas if n not in STRAIN_SIGMA_PLANES]
+            if unknown:
+                raise ValueError("node strain diagnostics are %s and strain sigmas %s, not %s" %
+                                 (", ".join(NODE_STRAIN_DIAGNOSTICS), ", ".join(STRAIN_SIGMA_PLANES), unknown))
+
+            def images(fields, names):
+                held = []
+                for q in fields:
+                    for name in names:
+                        a = q.get(name)
+                        if a is not None:
+                            a = np.ascontiguousarray(a, np.float32)
+                            if a.shape != (nh, nw):
+                                raise ValueError("node_strain: the node images are not %d x %d" % (nw, nh))
+                        held.append(a)
+                return held
+
+            def wanted(names, every):
+                return [np.empty((nh, nw), np.float32) if name in names else None for _ in steps for name in every]
+
+            given, sig_in = images(steps, self.NODE_PLANES), images(sig_steps, ("sigma_u", "sigma_v"))
+            out, diag, sig_out = wanted(planes, DEFORMATION_PLANES), wanted(diagnostics, NODE_STRAIN_DIAGNOSTICS), wanted(strain_sigmas, STRAIN_SIGMA_PLANES)
+            fpp = C.POINTER(C.c_float)
+            array = lambda held: (fpp * len(held))(*[_opt_fptr(a) for a in held])  # noqa: E731
+            recs = (DeformationStats * len(steps))()
+            self._set_strain_weighting(sigma, sigma_floor, threshold, iterations,
+                                       [a.ctypes.data if a is not None else None for a in diag] if diagnostics else None, len(steps))
+            try:
+                rc = host_lib().flow2d_host_node_strain_weighted(self.handle, array(given), array(sig_in), len(steps), nw, nh, int(spacing),
+                                                                 int(window), int(order), int(min_nodes), int(min_state), int(measure),
+                                                                 array(out) if planes else None, array(sig_out) if strain_sigmas else None,
+                                                                 recs if stats else None)
+            finally:
+                self._clear_strain_weighting()
+            if rc:
+                raise Flow2DError(rc, "OpticalFlow2D::NodeStrain (weighted)")
+            per_step = []
+            for k in range(len(steps)):
+                got = {name: out[9 * k + c] for c, name in enumerate(DEFORMATION_PLANES) if name in planes}
+                got.update({name: diag[3 * k + c] for c, name in enumerate(NODE_STRAIN_DIAGNOSTICS) if name in diagnostics})
+                got.update({name: sig_out[9 * k + c] for c, name in enumerate(STRAIN_SIGMA_PLANES) if name in strain_sigmas})
+                per_step.append((got, recs[k] if stats else None))
+            return per_step[0] if single else per_step
         given = []
         for q in steps:
             for name in self.NODE_PLANES:
@@ -3222,15 +3386,21 @@ class OpticalFlow:
         return per_step[0] if single else per_step
 
     def node_strain_device(self, dev_nodes, nw, nh, spacing, window=2, order=1, min_nodes=0, min_state=1, measure=STRAIN_SMALL,
-                           dev_planes=None, stats=True, sigma=0.0, iterations=8, diagnostics=None):
+                           dev_planes=None, stats=True, sigma=0.0, iterations=8, diagnostics=None, uncertainty=None, sigma_floor=0.0,
+                           threshold=0.0, strain_sigmas=None):
         """OpticalFlow2D::NodeStrainDevice: dev_nodes -- a dict of device planes of the container's size by the names of
         SUBSET_PLANES (as refine_nodes_device / correlate_subset*_device wrote them), or a list of them, one per step; dev_planes --
         a dict of device planes by the names of DEFORMATION_PLANES (or a list, one per step), which stay on the device.  Returns the
         DeformationStats (a list for a list) -- the call then synchronises once -- or, without stats, None (it only queues).
         sigma > 0: the robust fit; diagnostics -- a dict of device planes by the names of NODE_STRAIN_DIAGNOSTICS (or a list, one
-        per step), which stay on the device."""
+        per step), which stay on the device.
+        uncertainty -- a dict of device planes with sigma_u and sigma_v as node_uncertainty_device wrote them (or a list, one per
+        step): the weighted fit, with sigma_floor, threshold and iterations as in node_strain; strain_sigmas -- a dict of device
+        planes by the names of STRAIN_SIGMA_PLANES (or a list, one per step), which stay on the device."""
         single = isinstance(dev_nodes, dict)
         steps = [dev_nodes] if single else list(dev_nodes)
+        if uncertainty is None and (strain_sigmas is not None or sigma_floor or threshold):
+            raise ValueError("node_strain_device: sigma_floor, threshold and strain_sigmas go with uncertainty=")
         outs = [dev_planes] if single or dev_planes is None else list(dev_planes)
         if dev_planes is not None and len(outs) != len(steps):
             raise ValueError("node_strain_device takes one set of planes per step")
@@ -3245,6 +3415,35 @@ class OpticalFlow:
         unknown = [name for q in diags or () for name in q if name not in NODE_STRAIN_DIAGNOSTICS]
         if unknown:
             raise ValueError("node strain diagnostics are %s, not %s" % (", ".join(NODE_STRAIN_DIAGNOSTICS), unknown))
+        if uncertainty is not None:
+            per = lambda given, what: [given] if single else list(given)  # noqa: E731
+            sig_steps = per(uncertainty, "uncertainty")
+            sig_outs = None if strain_sigmas is None else per(strain_sigmas, "strain sigmas")
+            if len(sig_steps) != len(steps) or (sig_outs is not None and len(sig_outs) != len(steps)) or \
+                    any(not q.get("sigma_u") or not q.get("sigma_v") for q in sig_steps):
+                raise ValueError("node_strain_device takes one uncertainty with sigma_u and sigma_v, and one set of strain sigmas, per step")
+            unknown = [name for q in sig_outs or () for name in q if name not in STRAIN_SIGMA_PLANES]
+            if unknown:
+                raise ValueError("strain sigmas are %s, not %s" % (", ".join(STRAIN_SIGMA_PLANES), unknown))
+            vps = lambda held: (C.c_void_p * len(held))(*held)  # noqa: E731
+            sig_in = [q.get(name) for q in sig_steps for name in ("sigma_u", "sigma_v")]
+            sig_wanted = None if sig_outs is None else [q.get(name) for q in sig_outs for name in STRAIN_SIGMA_PLANES]
+            recs = (DeformationStats * len(steps))()
+            self._set_strain_weighting(sigma, sigma_floor, threshold, iterations,
+                                       [q.get(name) for q in diags for name in NODE_STRAIN_DIAGNOSTICS] if diags else None, len(steps))
+            try:
+                rc = host_lib().flow2d_host_node_strain_weighted_device(self.handle, vps(flat), vps(sig_in), len(steps), nw, nh, int(spacing),
+                                                                        int(window), int(order), int(min_nodes), int(min_state),
+                                                                        int(measure), vps(wanted) if wanted is not None else None,
+                                                                        vps(sig_wanted) if sig_wanted is not None else None,
+                                                                        recs if stats else None)
+            finally:
+                self._clear_strain_weighting()
+            if rc:
+                raise Flow2DError(rc, "OpticalFlow2D::NodeStrainDevice (weighted)")
+            if not stats:
+                return None
+            return recs[0] if single else list(recs)
         self._set_strain_robust(sigma, iterations, [q.get(name) for q in diags for name in NODE_STRAIN_DIAGNOSTICS] if diags else None,
                                 len(steps))
         recs = (DeformationStats * len(steps))()

@@ -38,6 +38,9 @@ struct flow2d_host_flow {
     int reference_every = 0;                                              // flow2d_host_set_reference_every
     float strain_sigma = 0.f;                                             // flow2d_host_set_strain_robust
     int strain_iterations = 8;
+    bool strain_weighted = false;                                         // flow2d_host_set_strain_weighting
+    float strain_floor = 0.f, strain_threshold = 0.f;
+    int strain_weight_iterations = 0;
     std::vector<void*> strain_diagnostics;  // flow2d_host_set_strain_diagnostics: of the next node-strain call, which forgets them
     std::vector<flow2d_compose_record> compose_records;                   // of the last sequence call: flow2d_host_compose_records
 };
@@ -1304,6 +1307,12 @@ OpticalFlow2D::StrainOptions strain_options(int window, int order, int min_nodes
     if (h) {
         o.robust_sigma = h->strain_sigma;
         o.robust_iterations = h->strain_iterations;
+        if (h->strain_weighted) {
+            o.weighted = true;
+            o.sigma_floor = h->strain_floor;
+            o.weight_threshold = h->strain_threshold;
+            o.robust_iterations = h->strain_weight_iterations;
+        }
     }
     return o;
 }
@@ -1335,6 +1344,35 @@ HOST_API int flow2d_host_set_strain_robust(flow2d_host_flow* h, float sigma, int
     if (!h || !(std::isfinite(sigma) && sigma >= 0.f) || iterations < 0 || iterations > FLOW2D_NODE_STRAIN_MAX_ITERATIONS) return 1;
     h->strain_sigma = sigma;
     h->strain_iterations = iterations;
+    return 0;
+}
+
+// OpticalFlow2D::StrainOptionsOk with the weighted fields (and a robust scale, which they exclude).  Needs no device.
+HOST_API int flow2d_host_strain_weighted_options_ok(int window, int order, int min_nodes, int min_state, int measure, float robust_sigma,
+                                                    float sigma_floor, float threshold, int iterations)
+{
+    auto o = strain_options(window, order, min_nodes, min_state, measure);
+    o.robust_sigma = robust_sigma;
+    o.weighted = true;
+    o.sigma_floor = sigma_floor;
+    o.weight_threshold = threshold;
+    o.robust_iterations = iterations;
+    return OpticalFlow2D::StrainOptionsOk(o) ? 1 : 0;
+}
+
+// StrainOptions::weighted, sigma_floor, weight_threshold and the passes of the weighted node-strain calls that follow
+// (flow2d_host_node_strain_weighted*); weighted 0 = off (the default).  1 for a floor or threshold that is negative or not finite,
+// or iterations outside 0 .. FLOW2D_NODE_STRAIN_MAX_ITERATIONS.  A robust scale set beside it makes those calls fail: the two
+// exclude each other.
+HOST_API int flow2d_host_set_strain_weighting(flow2d_host_flow* h, int weighted, float sigma_floor, float threshold, int iterations)
+{
+    if (!h || !(std::isfinite(sigma_floor) && sigma_floor >= 0.f) || !(std::isfinite(threshold) && threshold >= 0.f) || iterations < 0 ||
+        iterations > FLOW2D_NODE_STRAIN_MAX_ITERATIONS)
+        return 1;
+    h->strain_weighted = weighted != 0;
+    h->strain_floor = sigma_floor;
+    h->strain_threshold = threshold;
+    h->strain_weight_iterations = iterations;
     return 0;
 }
 
@@ -1428,6 +1466,100 @@ HOST_API int flow2d_host_node_strain(flow2d_host_flow* h, const float* const* no
         if (diagnostics[k]) std::memcpy(diagnostics[k], diag[k].DataPtr(), nw * nh * sizeof(float));
     for (size_t k = 0; planes && k < 9 * step_count; ++k)
         if (planes[k]) std::memcpy(planes[k], out[k].DataPtr(), nw * nh * sizeof(float));
+    return 0;
+}
+
+// OpticalFlow2D::NodeStrainDevice, the weighted form (after flow2d_host_set_strain_weighting): dev_nodes and dev_planes as for
+// flow2d_host_node_strain_device, dev_uncertainty -- two device planes per step, sigma_u and sigma_v, both needed --, dev_sigmas --
+// nine per step in the order of flow2d_strain_sigma_planes, each optional, the array may be null.  The diagnostic planes of
+// flow2d_host_set_strain_diagnostics go with it.  0, 1 or 2.
+HOST_API int flow2d_host_node_strain_weighted_device(flow2d_host_flow* h, void* const* dev_nodes, void* const* dev_uncertainty, int steps,
+                                                     size_t nw, size_t nh, int spacing, int window, int order, int min_nodes, int min_state,
+                                                     int measure, void* const* dev_planes, void* const* dev_sigmas,
+                                                     flow2d_deformation_stats* stats)
+{
+    const auto strain = strain_options(window, order, min_nodes, min_state, measure, h);
+    if (!h) return 1;
+    bool diagnostics_ok = false;
+    const std::vector<void*> given_diagnostics = take_diagnostics(h, steps < 1 ? 0 : static_cast<size_t>(steps), diagnostics_ok);
+    if (!diagnostics_ok || !strain.weighted) return 1;
+    if (!dev_nodes || !dev_uncertainty || steps < 1 || (!dev_planes && !dev_sigmas && !stats && given_diagnostics.empty()) ||
+        !OpticalFlow2D::StrainOptionsOk(strain))
+        return 1;
+    const size_t step_count = static_cast<size_t>(steps);
+    std::vector<DevicePtr> diagnostics, uncertainty(2 * step_count, 0), planes(9 * step_count, 0);
+    for (void* q : given_diagnostics) diagnostics.push_back(dp(q));
+    std::vector<OpticalFlow2D::SubsetPlanes> fields(step_count);
+    std::vector<OpticalFlow2D::StrainSigmaPlanes> sigmas(step_count);
+    for (size_t k = 0; k < step_count; ++k) {
+        void* const* q = dev_nodes + 7 * k;
+        if (!q[0] || !q[1] || !dev_uncertainty[2 * k] || !dev_uncertainty[2 * k + 1]) return 1;
+        fields[k] = {dp(q[0]), dp(q[1]), dp(q[2]), dp(q[3]), dp(q[4]), dp(q[5]), 0, dp(q[6])};
+        uncertainty[2 * k] = dp(dev_uncertainty[2 * k]);
+        uncertainty[2 * k + 1] = dp(dev_uncertainty[2 * k + 1]);
+        for (int c = 0; dev_planes && c < 9; ++c) planes[9 * k + c] = dp(dev_planes[9 * k + c]);
+        if (dev_sigmas) {
+            void* const* e = dev_sigmas + 9 * k;
+            sigmas[k] = {dp(e[0]), dp(e[1]), dp(e[2]), dp(e[3]), dp(e[4]), dp(e[5]), dp(e[6]), dp(e[7]), dp(e[8])};
+        }
+    }
+    h->flow.timing_mode = 0;
+    return h->flow.NodeStrainDevice(fields.data(), step_count, nw, nh, spacing, strain, uncertainty.data(),
+                                    dev_planes ? planes.data() : nullptr, stats, diagnostics.empty() ? nullptr : diagnostics.data(),
+                                    dev_sigmas ? sigmas.data() : nullptr)
+               ? 0
+               : 2;
+}
+
+// OpticalFlow2D::NodeStrain, the weighted form, on tight host arrays of nw * nh floats: nodes -- seven per step, uncertainty -- two per
+// step, planes -- nine per step, sigmas -- nine per step, as above.
+HOST_API int flow2d_host_node_strain_weighted(flow2d_host_flow* h, const float* const* nodes, const float* const* uncertainty, int steps,
+                                              size_t nw, size_t nh, int spacing, int window, int order, int min_nodes, int min_state,
+                                              int measure, float* const* planes, float* const* sigmas, flow2d_deformation_stats* stats)
+{
+    const auto strain = strain_options(window, order, min_nodes, min_state, measure, h);
+    if (!h) return 1;
+    bool diagnostics_ok = false;
+    const std::vector<void*> diagnostics = take_diagnostics(h, steps < 1 ? 0 : static_cast<size_t>(steps), diagnostics_ok);
+    if (!diagnostics_ok || !strain.weighted) return 1;
+    if (!nodes || !uncertainty || steps < 1 || nw == 0 || nh == 0 || (!planes && !sigmas && !stats && diagnostics.empty()) ||
+        !OpticalFlow2D::StrainOptionsOk(strain))
+        return 1;
+    const size_t step_count = static_cast<size_t>(steps);
+    // the images of one kind: `per` per step, copied from `from` (read) or handed back into `to` (written), null = absent
+    struct Kind {
+        size_t per;
+        const float* const* from;
+        void* const* to;
+        std::vector<Data2D> images;
+        std::vector<Data2D*> given;
+    };
+    Kind kinds[5] = {{7, nodes, nullptr, {}, {}},
+                     {2, uncertainty, nullptr, {}, {}},
+                     {9, nullptr, reinterpret_cast<void* const*>(planes), {}, {}},
+                     {3, nullptr, diagnostics.empty() ? nullptr : diagnostics.data(), {}, {}},
+                     {9, nullptr, reinterpret_cast<void* const*>(sigmas), {}, {}}};
+    for (Kind& kind : kinds) {
+        const size_t count = kind.per * step_count;
+        kind.images.reserve(count);
+        kind.given.assign(count, nullptr);
+        for (size_t k = 0; k < count; ++k) {
+            kind.images.emplace_back(nw, nh);
+            if (kind.from && kind.from[k]) {
+                std::memcpy(kind.images[k].DataPtr(), kind.from[k], nw * nh * sizeof(float));
+                kind.given[k] = &kind.images[k];
+            }
+            if (kind.to && kind.to[k]) kind.given[k] = &kind.images[k];
+        }
+    }
+    for (size_t k = 0; k < step_count; ++k)
+        if (!kinds[0].given[7 * k] || !kinds[0].given[7 * k + 1] || !kinds[1].given[2 * k] || !kinds[1].given[2 * k + 1]) return 1;
+    h->flow.NodeStrain(kinds[0].given.data(), step_count, spacing, strain, kinds[1].given.data(), planes ? kinds[2].given.data() : nullptr,
+                       stats, diagnostics.empty() ? nullptr : kinds[3].given.data(), sigmas ? kinds[4].given.data() : nullptr);
+    if (!h->flow.LastRunSucceeded()) return 2;
+    for (Kind& kind : kinds)
+        for (size_t k = 0; kind.to && k < kind.per * step_count; ++k)
+            if (kind.to[k]) std::memcpy(kind.to[k], kind.images[k].DataPtr(), nw * nh * sizeof(float));
     return 0;
 }
 

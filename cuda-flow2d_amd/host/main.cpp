@@ -99,6 +99,12 @@
 // node-strain-centre are written beside the nine files and one more line, "NodeStrainRobust: {json}" -- "sigma", "iterations" and
 // the record's "touched" (nodes that rejected a tap), "rejected" (taps) and "suspect" (nodes whose own tap was not kept) -- is
 // printed behind "NodeStrain:", which keeps its format.  Without the option nothing changes.
+// --strain-weighted [--strain-sigma-floor F, pixels, default 0] [--strain-threshold T, sigmas, default 0: no robust part]
+// [--strain-iterations K, with T > 0, default 8], with --subset-uncertainty and --subset-strain M, M >= 1, weights every tap of the
+// window fit by 1 / (sigma^2 + F^2) of its node (flow2d_node_strain_weighted_2d), taken from the uncertainty that is computed first.
+// The three diagnostic files (residual and centre in sigmas) and node-sigma-exx, -eyy, -exy, -divergence, -vorticity and
+// node-sigma-strain-ux, -uy, -vx, -vy (the fitted gradients' sigmas; node-sigma-ux ... are the subsets' own) are written beside the
+// nine files, and one more line, "WeightedStrain: {json}" with the record's four counts.  Not together with --strain-sigma.
 // --subset-previous PREFIX [--subset-fill F, 1 .. 4, default 2] [--subset-min-state 0|1, default 1] [--subset-predict-neighbours N,
 // 1 .. 8, default 1], valid only together with --subset-refine, is the next step of a loading sequence: FILE_0 is the sequence's
 // reference frame, FILE_1 its current frame, and PREFIXnode-u-NW-NH.raw, -v, -ux, -uy, -vx, -vy and -state are what a --subset-refine
@@ -248,6 +254,7 @@ int main(int argc, char** argv)
     int correlation_min_pixels = 0;
     OpticalFlow2D::StrainOptions node_strain;  // --subset-strain M and --strain-order, --strain-min-nodes, --strain-sigma, --strain-iterations
     bool strain_iterations_given = false;
+    bool strain_floor_given = false, strain_threshold_given = false;  // --strain-sigma-floor, --strain-threshold (with --strain-weighted)
     bool subset_strain = false, strain_option = false;
     OpticalFlow2D::ValidationOptions validation;                     // --validate-threshold / -epsilon / -min-neighbours / -flag-only
     bool validate_option = false;
@@ -624,6 +631,22 @@ int main(int argc, char** argv)
             node_strain.robust_sigma = sigma;
             ++i;
         }
+        else if (!std::strcmp(argv[i], "--strain-weighted")) node_strain.weighted = true;
+        else if (!std::strcmp(argv[i], "--strain-sigma-floor") || !std::strcmp(argv[i], "--strain-threshold")) {
+            const bool floor = !std::strcmp(argv[i], "--strain-sigma-floor");
+            char* end = nullptr;
+            const float x = (i + 1 < argc) ? std::strtof(argv[i + 1], &end) : -1.f;
+            if (i + 1 >= argc || end == argv[i + 1] || *end != '\0' || !(std::isfinite(x) && x >= 0.f)) {
+                std::printf("%s\n", floor ? "--strain-sigma-floor takes a standard deviation in pixels that every node has beside its own: "
+                                            "finite and not negative."
+                                          : "--strain-threshold takes the scale of the robust weight in sigmas: finite and not negative "
+                                            "(0: no robust part).");
+                return 5;
+            }
+            (floor ? node_strain.sigma_floor : node_strain.weight_threshold) = x;
+            (floor ? strain_floor_given : strain_threshold_given) = true;
+            ++i;
+        }
         else if (!std::strcmp(argv[i], "--strain-iterations")) {
             char* end = nullptr;
             const long n = (i + 1 < argc) ? std::strtol(argv[i + 1], &end, 10) : -1;
@@ -767,7 +790,24 @@ int main(int argc, char** argv)
         std::printf("--strain-order and --strain-min-nodes belong to --subset-strain M.\n");
         return 5;
     }
-    if (strain_iterations_given && node_strain.robust_sigma == 0.f) {
+    if ((strain_floor_given || strain_threshold_given) && !node_strain.weighted) {
+        std::printf("--strain-sigma-floor and --strain-threshold belong to --strain-weighted.\n");
+        return 5;
+    }
+    if (node_strain.weighted && (!subset_uncertainty || !subset_strain || node_strain.window == 0)) {
+        std::printf("--strain-weighted weights a strain window by the nodes' variances: it goes with --subset-uncertainty and "
+                    "--subset-strain M, M >= 1.\n");
+        return 5;
+    }
+    if (node_strain.weighted && node_strain.robust_sigma != 0.f) {
+        std::printf("--strain-weighted takes its scale in sigmas (--strain-threshold T); --strain-sigma S is in pixels: give one of them.\n");
+        return 5;
+    }
+    if (strain_iterations_given && node_strain.weighted && node_strain.weight_threshold == 0.f) {
+        std::printf("--strain-iterations with --strain-weighted belongs to --strain-threshold T, T > 0.\n");
+        return 5;
+    }
+    if (strain_iterations_given && node_strain.robust_sigma == 0.f && !node_strain.weighted) {
         std::printf("--strain-iterations belongs to --strain-sigma S.\n");
         return 5;
     }
@@ -988,20 +1028,31 @@ int main(int argc, char** argv)
         Data2D node_u, node_v, node_score;
         // --subset-strain: the nine planes of the node field fields[0 .. 6] (u, v, ux, uy, vx, vy, state; null = absent), written
         // beside the node files, and the record
-        auto write_node_strain = [&](Data2D* const* fields, size_t nw, size_t nh, int spacing) {
+        // With --strain-weighted: `uncertainty` holds the nodes' sigma_u and sigma_v, the nine sigma planes are written too.
+        auto write_node_strain = [&](Data2D* const* fields, size_t nw, size_t nh, int spacing, Data2D* const* uncertainty = nullptr) {
             const char* names[9] = {"node-divergence", "node-vorticity", "node-dilatation", "node-exx", "node-eyy", "node-exy", "node-e1",
                                     "node-e2", "node-max-shear"};
             std::vector<Data2D> images;
             for (int k = 0; k < 9; ++k) images.emplace_back(nw, nh);
-            const bool robust = node_strain.robust_sigma != 0.f;
+            const bool weighted = node_strain.weighted && uncertainty;
+            const bool robust = node_strain.robust_sigma != 0.f || weighted;
             const char* diagnostic_names[3] = {"node-strain-residual", "node-strain-rejected", "node-strain-centre"};
+            const char* sigma_names[9] = {"node-sigma-strain-ux", "node-sigma-strain-uy", "node-sigma-strain-vx", "node-sigma-strain-vy",
+                                          "node-sigma-divergence", "node-sigma-vorticity", "node-sigma-exx",      "node-sigma-eyy",
+                                          "node-sigma-exy"};
             for (int k = 0; robust && k < 3; ++k) images.emplace_back(nw, nh);
+            for (int k = 0; weighted && k < 9; ++k) images.emplace_back(nw, nh);
             Data2D* planes[9];
             Data2D* diagnostics[3];
+            Data2D* strain_sigmas[9];
             for (int k = 0; k < 9; ++k) planes[k] = &images[k];
             for (int k = 0; robust && k < 3; ++k) diagnostics[k] = &images[9 + k];
+            for (int k = 0; weighted && k < 9; ++k) strain_sigmas[k] = &images[12 + k];
             flow2d_deformation_stats stats = {};
-            optical_flow.NodeStrain(fields, 1, spacing, node_strain, planes, &stats, robust ? diagnostics : nullptr);
+            if (weighted)
+                optical_flow.NodeStrain(fields, 1, spacing, node_strain, uncertainty, planes, &stats, diagnostics, strain_sigmas);
+            else
+                optical_flow.NodeStrain(fields, 1, spacing, node_strain, planes, &stats, robust ? diagnostics : nullptr);
             if (!optical_flow.LastRunSucceeded()) return;
             const std::string size = "-" + std::to_string(nw) + "-" + std::to_string(nh) + ".raw";
             for (int k = 0; k < 9; ++k) images[k].WriteRAWToFileF32((output_path + counter + names[k] + size).c_str());
@@ -1020,7 +1071,14 @@ int main(int argc, char** argv)
                 std::printf(", \"%s\": {\"sum\": %.17g, \"sum_sq\": %.17g, \"min\": %.9g, \"max\": %.9g}", quantity[k], moments[k]->sum,
                             moments[k]->sum_sq, moments[k]->min, moments[k]->max);
             std::printf("}\n");
-            if (robust)
+            for (int k = 0; weighted && k < 9; ++k) images[12 + k].WriteRAWToFileF32((output_path + counter + sigma_names[k] + size).c_str());
+            if (weighted)
+                std::printf("WeightedStrain: {\"sigma_floor\": %.9g, \"threshold\": %.9g, \"iterations\": %d, \"touched\": %llu, "
+                            "\"rejected\": %llu, \"suspect\": %llu, \"unweighable\": %llu}\n",
+                            static_cast<double>(node_strain.sigma_floor), static_cast<double>(node_strain.weight_threshold),
+                            node_strain.weight_threshold > 0.f ? node_strain.robust_iterations : 0, stats.reserved[3], stats.reserved[4],
+                            stats.reserved[5], stats.reserved[6]);
+            else if (robust)
                 std::printf("NodeStrainRobust: {\"sigma\": %.9g, \"iterations\": %d, \"touched\": %llu, \"rejected\": %llu, "
                             "\"suspect\": %llu}\n",
                             static_cast<double>(node_strain.robust_sigma), node_strain.robust_iterations, stats.reserved[3],
@@ -1138,7 +1196,7 @@ int main(int argc, char** argv)
                             subset_previous.empty() ? schedule.size() : size_t(0),
                             fine.radius, fine.spacing, nw, nh, lo, scale, record.nodes, record.converged, record.unconverged,
                             record.strayed, record.flat, record.no_input, record.iterations);
-                if (subset_strain) {
+                if (subset_strain && !node_strain.weighted) {
                     Data2D* fields[7] = {nodes[0], nodes[1], nodes[2], nodes[3], nodes[4], nodes[5], nodes[7]};
                     write_node_strain(fields, nw, nh, fine.spacing);
                 }
@@ -1159,6 +1217,11 @@ int main(int argc, char** argv)
                                     "\"skipped\": %llu, \"masked\": %llu, \"outside\": %llu, \"flat\": %llu, \"thin\": %llu}\n",
                                     subset.radius, sequence.min_state, counts.nodes, counts.evaluated, counts.skipped, counts.masked,
                                     counts.outside, counts.flat, counts.thin);
+                        // (--strain-weighted: the strain comes behind the uncertainty it is weighted by)
+                        if (subset_strain && node_strain.weighted) {
+                            Data2D* fields[7] = {nodes[0], nodes[1], nodes[2], nodes[3], nodes[4], nodes[5], nodes[7]};
+                            write_node_strain(fields, nw, nh, fine.spacing, wanted);
+                        }
                     }
                 }
             }

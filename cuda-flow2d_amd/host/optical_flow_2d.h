@@ -530,10 +530,22 @@ public:
     // robust_iterations passes with a Cauchy weight of that scale, taps further than it from the last fit not kept, a window
     // that keeps fewer than min_nodes sparse.  8 passes are what an order-2 fit at m = 2 needs; order 1 settles within 4
     // (profiles/robust_strain/README.md).  0 = off: the plain entry, the iterations are not looked at.
+    // weighted (with a window of 1 or more, and the forms below that take the nodes' sigma planes) makes the fit the Gauss-Markov
+    // one of flow2d_node_strain_weighted_2d: every tap weighted by 1 / (sigma^2 + sigma_floor^2) of its node, sigma_floor in
+    // pixels (finite, >= 0: what the uncertainty does not see, the sampler's bias above all).  weight_threshold T > 0 adds that
+    // entry's reweighted passes with the scale in sigmas, robust_iterations of them; T = 0: none, the iterations are not looked
+    // at.  robust_sigma and weighted exclude each other: one scale is in pixels and the other in sigmas.
     struct StrainOptions {
         int window = 2, order = 1, min_nodes = 0 /* 0: k + 1 */, min_state = 1, measure = FLOW2D_STRAIN_SMALL;
         float robust_sigma = 0.f;
         int robust_iterations = 8;
+        bool weighted = false;
+        float sigma_floor = 0.f, weight_threshold = 0.f;
+    };
+    // The nine planes of flow2d_strain_sigma_planes as device planes of the container's size, 0 = not wanted.
+    struct StrainSigmaPlanes {
+        DevicePtr sigma_ux = 0, sigma_uy = 0, sigma_vx = 0, sigma_vy = 0, sigma_divergence = 0, sigma_vorticity = 0, sigma_exx = 0,
+                  sigma_eyy = 0, sigma_exy = 0;
     };
     // prints what is wrong; needs no device
     static bool StrainOptionsOk(const StrainOptions& strain);
@@ -553,6 +565,15 @@ public:
     // diagnostics[3 * k + 0 .. 2] (optional, with robust_sigma > 0 only): images of the grid, null = not wanted.
     void NodeStrain(Data2D* const* nodes, size_t step_count, int spacing, const StrainOptions& strain, Data2D* const* planes,
                     flow2d_deformation_stats* stats_out, Data2D* const* diagnostics = nullptr);
+    // The weighted forms (strain.weighted; flow2d_node_strain_weighted_2d): as above, with uncertainty[2 * k + 0 .. 1] -- sigma_u and
+    // sigma_v of step k as NodeUncertainty[Device] wrote them, both needed -- and strain_sigmas (optional): one StrainSigmaPlanes
+    // per step, or images strain_sigmas[9 * k + 0 .. 8] in that struct's order, null = not wanted; they count as wanted planes,
+    // and so do the diagnostic planes, whose residual and centre are in sigmas here.  The records carry reserved[3 .. 6].
+    bool NodeStrainDevice(const SubsetPlanes* steps, size_t step_count, size_t nw, size_t nh, int spacing, const StrainOptions& strain,
+                          const DevicePtr* uncertainty, const DevicePtr* out_planes, flow2d_deformation_stats* stats_out,
+                          const DevicePtr* diagnostics, const StrainSigmaPlanes* strain_sigmas);
+    void NodeStrain(Data2D* const* nodes, size_t step_count, int spacing, const StrainOptions& strain, Data2D* const* uncertainty,
+                    Data2D* const* planes, flow2d_deformation_stats* stats_out, Data2D* const* diagnostics, Data2D* const* strain_sigmas);
 
     // The pyramid started from a prior flow instead of from zero at the coarsest level (no reference counterpart; Brox & Malik's
     // large-displacement flow and the predictor-corrector passes of PIV start the variational solver from matches in the same

@@ -1190,6 +1190,24 @@ bool OpticalFlow2D::StrainOptionsOk(const StrainOptions& strain)
         (strain.measure == FLOW2D_STRAIN_SMALL || strain.measure == FLOW2D_STRAIN_GREEN_LAGRANGE) &&
         (strain.window == 0 ||
          ((strain.order == 1 || strain.order == 2) && (strain.min_nodes == 0 || (strain.min_nodes >= k && strain.min_nodes <= side * side))))) {
+        if (strain.weighted) {
+            if (strain.robust_sigma != 0.f) {
+                std::printf("Error: weighted node strain takes its threshold in sigmas (%g) and a robust scale is in pixels (%g): the two "
+                            "exclude each other.\n",
+                            static_cast<double>(strain.weight_threshold), static_cast<double>(strain.robust_sigma));
+                return false;
+            }
+            if (strain.window >= 1 && std::isfinite(strain.sigma_floor) && strain.sigma_floor >= 0.f &&
+                std::isfinite(strain.weight_threshold) && strain.weight_threshold >= 0.f &&
+                (strain.weight_threshold == 0.f ||
+                 (strain.robust_iterations >= 0 && strain.robust_iterations <= FLOW2D_NODE_STRAIN_MAX_ITERATIONS)))
+                return true;
+            std::printf("Error: weighted node strain takes a window of 1 or more nodes (%d), a floor (%g) and a threshold (%g) that are "
+                        "finite and not negative and, with a threshold, 0 .. %d reweighted passes (%d).\n",
+                        strain.window, static_cast<double>(strain.sigma_floor), static_cast<double>(strain.weight_threshold),
+                        FLOW2D_NODE_STRAIN_MAX_ITERATIONS, strain.robust_iterations);
+            return false;
+        }
         // robust_sigma 0 is the plain fit; anything else has to be a scale the robust entry takes, with a window to reweight
         if (strain.robust_sigma == 0.f) return true;
         if (std::isfinite(strain.robust_sigma) && strain.robust_sigma > 0.f && strain.window >= 1 && strain.robust_iterations >= 0 &&
@@ -1213,6 +1231,10 @@ bool OpticalFlow2D::NodeStrainDevice(const SubsetPlanes* steps, size_t step_coun
 {
     const size_t W = dev_container_size_.width, H = dev_container_size_.height, pitch = dev_container_size_.pitch;
     if (!StrainOptionsOk(strain)) return false;
+    if (strain.weighted) {
+        std::printf("Error: '%s': weighted node strain needs the nodes' sigma planes: the form that takes them.\n", GetName());
+        return false;
+    }
     const bool robust = strain.robust_sigma != 0.f;
     if (diagnostics && !robust) {
         std::printf("Error: '%s': the diagnostic planes of node strain go with a robust scale.\n", GetName());
@@ -1323,6 +1345,137 @@ void OpticalFlow2D::NodeStrain(Data2D* const* nodes, size_t step_count, int spac
         if (planes[k]) ok = CopyData2DFromDevice(out[k], *planes[k], H, dev_container_size_.pitch);
     for (size_t k = 0; ok && diagnostics && k < 3 * step_count; ++k)
         if (diagnostics[k]) ok = CopyData2DFromDevice(diag[k], *diagnostics[k], H, dev_container_size_.pitch);
+    last_run_ok_ = ok;
+}
+
+bool OpticalFlow2D::NodeStrainDevice(const SubsetPlanes* steps, size_t step_count, size_t nw, size_t nh, int spacing,
+                                     const StrainOptions& strain, const DevicePtr* uncertainty, const DevicePtr* out_planes,
+                                     flow2d_deformation_stats* stats_out, const DevicePtr* diagnostics,
+                                     const StrainSigmaPlanes* strain_sigmas)
+{
+    const size_t W = dev_container_size_.width, H = dev_container_size_.height, pitch = dev_container_size_.pitch;
+    if (!StrainOptionsOk(strain)) return false;
+    if (!strain.weighted) {
+        std::printf("Error: '%s': the nodes' sigma planes go with weighted node strain.\n", GetName());
+        return false;
+    }
+    if (!IsInitialized() || !steps || step_count == 0 || (!out_planes && !stats_out && !diagnostics && !strain_sigmas)) return false;
+    if (nw == 0 || nh == 0 || nw > W || nh > H) {
+        std::printf("Error: '%s': a %zu x %zu node grid does not lie in planes of %zu x %zu.\n", GetName(), nw, nh, W, H);
+        return false;
+    }
+    if (RefuseGroup("node strain")) return false;
+    for (size_t k = 0; k < step_count; ++k) {
+        if (!steps[k].u || !steps[k].v || !uncertainty || !uncertainty[2 * k] || !uncertainty[2 * k + 1]) {
+            std::printf("Error: '%s': step %zu of weighted node strain needs u, v, sigma_u and sigma_v.\n", GetName(), k + 1);
+            return false;
+        }
+    }
+    const int min_nodes = strain.min_nodes == 0 ? (strain.order == 2 ? 6 : 3) + 1 : strain.min_nodes;
+    const int passes = strain.weight_threshold > 0.f ? strain.robust_iterations : 0;
+    const size_t workspace_bytes = stats_out ? flow2d_node_strain_weighted_workspace_bytes(nw, nh, 1) : 0;
+    const size_t per_step = sizeof(flow2d_deformation_stats) + workspace_bytes;
+    if (stats_out && !strain_scratch_.Ensure(context_, step_count * per_step)) return false;
+    auto plane = [](DevicePtr p) { return p ? AsPlane(p) : nullptr; };
+    bool ok = true;
+    for (size_t k = 0; ok && k < step_count; ++k) {
+        const SubsetPlanes& q = steps[k];
+        flow2d_deformation_planes out = {};
+        if (out_planes) {
+            const DevicePtr* d = out_planes + 9 * k;
+            out = {plane(d[0]), plane(d[1]), plane(d[2]), plane(d[3]), plane(d[4]), plane(d[5]), plane(d[6]), plane(d[7]), plane(d[8])};
+        }
+        flow2d_node_strain_diagnostics diag = {};
+        if (diagnostics) diag = {plane(diagnostics[3 * k]), plane(diagnostics[3 * k + 1]), plane(diagnostics[3 * k + 2])};
+        flow2d_strain_sigma_planes sig = {};
+        if (strain_sigmas) {
+            const StrainSigmaPlanes& e = strain_sigmas[k];
+            sig = {plane(e.sigma_ux),         plane(e.sigma_uy),        plane(e.sigma_vx),  plane(e.sigma_vy), plane(e.sigma_divergence),
+                   plane(e.sigma_vorticity), plane(e.sigma_exx),       plane(e.sigma_eyy), plane(e.sigma_exy)};
+        }
+        auto* record = stats_out ? strain_scratch_.At<flow2d_deformation_stats>(k * per_step) : nullptr;
+        void* workspace = stats_out ? strain_scratch_.At<>(k * per_step + sizeof(flow2d_deformation_stats)) : nullptr;
+        // (the node planes are containers: the frames' pitch; the entry refuses planes that meet)
+        ok = !CheckFlow2DError(flow2d_node_strain_weighted_2d(context_, AsPlane(q.u), AsPlane(q.v), plane(q.state), AsPlane(uncertainty[2 * k]),
+                                                              AsPlane(uncertainty[2 * k + 1]), nw, nh, pitch, spacing, strain.window,
+                                                              strain.order, min_nodes, strain.min_state, strain.measure, strain.sigma_floor,
+                                                              strain.weight_threshold, passes, &out, &diag, &sig, record, workspace,
+                                                              workspace_bytes),
+                               "flow2d_node_strain_weighted_2d");
+        if (ok && stats_out) ok = ReadRecord(stats_out + k, record, sizeof(*record));
+    }
+    if (!stats_out) return ok;
+    return !CheckFlow2DError(flow2d_synchronize(context_), "flow2d_synchronize") && ok;
+}
+
+void OpticalFlow2D::NodeStrain(Data2D* const* nodes, size_t step_count, int spacing, const StrainOptions& strain,
+                               Data2D* const* uncertainty, Data2D* const* planes, flow2d_deformation_stats* stats_out,
+                               Data2D* const* diagnostics, Data2D* const* strain_sigmas)
+{
+    last_run_ok_ = false;
+    if (!IsInitialized() || !nodes || step_count == 0 || !nodes[0] || !uncertainty ||
+        (!planes && !stats_out && !diagnostics && !strain_sigmas) || !StrainOptionsOk(strain))
+        return;
+    if (!strain.weighted) {
+        std::printf("Error: '%s': the nodes' sigma planes go with weighted node strain.\n", GetName());
+        return;
+    }
+    const size_t nw = nodes[0]->Width(), nh = nodes[0]->Height(), H = dev_container_size_.height;
+    if (nw == 0 || nh == 0 || nw > dev_container_size_.width || nh > H) {
+        std::printf("Error: '%s': a %zu x %zu node grid does not lie in planes of %zu x %zu.\n", GetName(), nw, nh,
+                    dev_container_size_.width, H);
+        return;
+    }
+    // per step: u, v, state, sigma_u, sigma_v read (the gradients are not: a window fit), then 9 + 3 + 9 written
+    constexpr int kIn = 5, kOut = 21, kPer = kIn + kOut;
+    std::vector<Data2D*> images(kPer * step_count, nullptr);
+    for (size_t k = 0; k < step_count; ++k) {
+        Data2D** q = images.data() + kPer * k;
+        q[0] = nodes[7 * k];
+        q[1] = nodes[7 * k + 1];
+        q[2] = nodes[7 * k + 6];
+        q[3] = uncertainty[2 * k];
+        q[4] = uncertainty[2 * k + 1];
+        if (!q[0] || !q[1] || !q[3] || !q[4]) {
+            std::printf("Error: '%s': step %zu of weighted node strain needs u, v, sigma_u and sigma_v.\n", GetName(), k + 1);
+            return;
+        }
+        for (int c = 0; c < 9; ++c) q[kIn + c] = planes ? planes[9 * k + c] : nullptr;
+        for (int c = 0; c < 3; ++c) q[kIn + 9 + c] = diagnostics ? diagnostics[3 * k + c] : nullptr;
+        for (int c = 0; c < 9; ++c) q[kIn + 12 + c] = strain_sigmas ? strain_sigmas[9 * k + c] : nullptr;
+        for (int c = 0; c < kPer; ++c)
+            if (q[c] && (q[c]->Width() != nw || q[c]->Height() != nh)) {
+                std::printf("Error: '%s': the node images are not %zu x %zu.\n", GetName(), nw, nh);
+                return;
+            }
+    }
+    // the node planes, read and written: containers with no image of their size behind them, uploaded and downloaded here
+    CallPlanes call_planes(context_, dev_container_size_, GetName(), "node");
+    for (Data2D* image : images) call_planes.Add(nullptr, CallPlanes::Out, image != nullptr);
+    HostCall call(context_, last_total_ms_, call_planes.Allocate());
+    const DevicePtr* d = call_planes.data();
+    bool ok = call_planes.Upload();
+    std::vector<SubsetPlanes> steps(step_count);
+    std::vector<DevicePtr> sigma_in(2 * step_count, 0), out(9 * step_count, 0), diag(3 * step_count, 0);
+    std::vector<StrainSigmaPlanes> sig(step_count);
+    for (size_t k = 0; k < step_count; ++k) {
+        const DevicePtr* q = d + kPer * k;
+        for (int c = 0; ok && c < kIn; ++c)
+            if (images[kPer * k + c]) ok = CopyData2DtoDevice(*images[kPer * k + c], q[c], H, dev_container_size_.pitch);
+        steps[k] = {q[0], q[1], 0, 0, 0, 0, 0, q[2]};
+        sigma_in[2 * k] = q[3];
+        sigma_in[2 * k + 1] = q[4];
+        for (int c = 0; c < 9; ++c) out[9 * k + c] = q[kIn + c];
+        for (int c = 0; c < 3; ++c) diag[3 * k + c] = q[kIn + 9 + c];
+        const DevicePtr* e = q + kIn + 12;
+        sig[k] = {e[0], e[1], e[2], e[3], e[4], e[5], e[6], e[7], e[8]};
+    }
+    ok = ok && NodeStrainDevice(steps.data(), step_count, nw, nh, spacing, strain, sigma_in.data(), planes ? out.data() : nullptr, stats_out,
+                                diagnostics ? diag.data() : nullptr, strain_sigmas ? sig.data() : nullptr);
+    // (without a record the device call only queues: the downloads below are ordered behind it on the stream)
+    for (size_t k = 0; ok && k < step_count; ++k)
+        for (int c = kIn; ok && c < kPer; ++c)
+            if (images[kPer * k + c]) ok = CopyData2DFromDevice(d[kPer * k + c], *images[kPer * k + c], H, dev_container_size_.pitch);
     last_run_ok_ = ok;
 }
 

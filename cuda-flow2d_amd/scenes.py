@@ -38,7 +38,9 @@ refinement (flow2d_subset_refine_2d): the same texture under a rotation, a stret
 make_speckle_deformation_sequence(name, steps, step_size, ...) carries one of them on, k times per step k, every frame against
 frame 0: the loading sequence flow2d_subset_refine_from_2d is for.  make_speckle_specimen(name, width, height, seed) puts the
 same deformations on a plate with a hole in front of a static background and returns the scene with its mask: what
-flow2d_subset_refine_masked_2d is for.
+flow2d_subset_refine_masked_2d is for.  make_speckle_patchy(name, width, height, seed) puts them on a pattern whose contrast
+varies by a decade from one 16-pixel patch to the next, so that the nodes' uncertainties do: what
+flow2d_node_strain_weighted_2d is for.
 Pure numpy: no device, no library.
 """
 import numpy as np
@@ -120,17 +122,45 @@ def make_speckle_deformation(name, width=96, height=80, seed=0, translation=(1.6
     """A speckle pattern whose windows deform (one of SPECKLE_DEFORMATIONS), for the subset refinement (flow2d_subset_refine_2d):
     a rotation by 5 degrees, a stretch by 1.06 x 0.97 and a shear of 0.08, each about the centre and followed by `translation`,
     (1.6, -0.7) by default.  They are NOT in SPECKLE_MOTIONS: the tests that iterate over that tuple are about the rigid window."""
-    texture = Speckle(seed)
+    return _affine_scene("speckle_" + name, width, height, Speckle(seed), _speckle_deformation_matrix(name),
+                         (float(translation[0]), float(translation[1])))
+
+
+def _speckle_deformation_matrix(name):
     if name == "rotation":
         phi = np.radians(5.0)
-        a = [[np.cos(phi), -np.sin(phi)], [np.sin(phi), np.cos(phi)]]
-    elif name == "stretch":
-        a = [[1.06, 0.0], [0.0, 0.97]]
-    elif name == "shear":
-        a = [[1.0, 0.08], [0.0, 1.0]]
-    else:
-        raise ValueError("unknown speckle deformation %r (one of %s)" % (name, ", ".join(SPECKLE_DEFORMATIONS)))
-    return _affine_scene("speckle_" + name, width, height, texture, a, (float(translation[0]), float(translation[1])))
+        return [[np.cos(phi), -np.sin(phi)], [np.sin(phi), np.cos(phi)]]
+    if name == "stretch":
+        return [[1.06, 0.0], [0.0, 0.97]]
+    if name == "shear":
+        return [[1.0, 0.08], [0.0, 1.0]]
+    raise ValueError("unknown speckle deformation %r (one of %s)" % (name, ", ".join(SPECKLE_DEFORMATIONS)))
+
+
+class PatchySpeckle(Speckle):
+    """Speckle whose contrast varies patchwise: over the ground, the blobs of the `patch`-pixel cell (i, j) are scaled by a seeded
+    gain, log-uniform over `gain` = (0.1, 1) by default, from the same hash (stream 5).  A subset's displacement noise goes with
+    noise / contrast, so that nodes on neighbouring patches differ in sigma by up to a decade: what a weighted strain window
+    (flow2d_node_strain_weighted_2d) is for.  The gain belongs to the material and moves with it."""
+
+    def __init__(self, seed, patch=16.0, gain=(0.1, 1.0), **speckle):
+        super().__init__(seed, **speckle)
+        self.patch, self.gain = float(patch), (float(gain[0]), float(gain[1]))
+
+    def gain_at(self, x, y):
+        x, y = np.broadcast_arrays(np.asarray(x, np.float64), np.asarray(y, np.float64))
+        lo, hi = self.gain
+        return lo * (hi / lo) ** self._uniform(np.floor(x / self.patch), np.floor(y / self.patch), 5)
+
+    def __call__(self, x, y):
+        return self.ground + self.gain_at(x, y) * (super().__call__(x, y) - self.ground)
+
+
+def make_speckle_patchy(name, width=96, height=80, seed=0, translation=(1.6, -0.7), patch=16.0, gain=(0.1, 1.0)):
+    """make_speckle_deformation on a PatchySpeckle: the same motions and ground truth, the pattern's contrast varying by `gain` from
+    one `patch`-pixel cell to the next.  With the grid of radius 7 and spacing 8 every other node's subset lies inside one cell."""
+    return _affine_scene("patchy_" + name, width, height, PatchySpeckle(seed, patch, gain), _speckle_deformation_matrix(name),
+                         (float(translation[0]), float(translation[1])))
 
 
 def make_speckle_specimen(name, width=96, height=80, seed=0, translation=(1.6, -0.7), background_gain=0.3, background_offset=5.0):

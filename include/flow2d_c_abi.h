@@ -55,8 +55,9 @@ extern "C" {
  * for) with the host-only diagnostics flow2d_fused_block_order_for_cus / flow2d_fused_plan_for_cus /
  * flow2d_stream_rows_for_cus (which plan a CU count gives) and flow2d_correlate_masked_2d / flow2d_validate_nodes_masked_2d (the
  * window search and the median test on a region of interest) and flow2d_node_strain_robust_2d /
- * flow2d_node_strain_robust_workspace_bytes (the strain windows as reweighted least squares, with diagnostic planes) were added
- * under 1. */
+ * flow2d_node_strain_robust_workspace_bytes (the strain windows as reweighted least squares, with diagnostic planes) and
+ * flow2d_node_strain_weighted_2d / flow2d_node_strain_weighted_workspace_bytes (the strain windows weighted by the nodes' own
+ * variances, with the standard deviations of the strain) were added under 1. */
 #define FLOW2D_ABI_VERSION 1
 
 typedef enum flow2d_status {
@@ -1612,6 +1613,93 @@ FLOW2D_API int flow2d_node_strain_robust_2d(flow2d_context* ctx, const float* no
                                             const flow2d_node_strain_diagnostics* diagnostics /* host, may be NULL */,
                                             flow2d_deformation_stats* stats /* device, may be NULL */, void* workspace,
                                             size_t workspace_bytes);
+
+/* Weighted strain windows: the window fit of flow2d_node_strain_2d as a Gauss-Markov fit whose weights are the inverse variances
+ * flow2d_subset_uncertainty_2d delivers per node (Aitken, Proc. R. Soc. Edinburgh 55 (1935)), the standard deviations of the
+ * strain from the inverse of the matrices the fit factors, and optionally the reweighted passes of flow2d_node_strain_robust_2d
+ * with a scale in sigmas instead of pixels.  Added to ABI version 1 without changing any existing entry.
+ *
+ * Everything flow2d_node_strain_2d defines for m >= 1 holds -- IEEE double, every operation rounded on its own, no fused
+ * multiply-add, every test a positive comparison, taps visited in raster order; the inputs (without the gradient planes), usable
+ * nodes, the basis, wu and wv against the centre, the Cholesky factorisation, Solve, the quantities, the planes, the record and
+ * its reduction -- with these additions.
+ * Inputs in addition.  node_sigma_u, node_sigma_v (required): planes on the node grid, the out_sigma_u and out_sigma_v of
+ * flow2d_subset_uncertainty_2d, in pixels.  sigma_floor, a float, finite and >= 0, in pixels: a variance every node has beside
+ * the one reported (the uncertainty estimates the random error only: an exact match reports +0, and the sampler's bias is not
+ * in it); f2 = sigma_floor*sigma_floor after converting it to double.  T = threshold, a float, finite and >= 0, in sigmas;
+ * t2 = T*T after converting T to double; T = 0: no robust part.  K = iterations (0 .. FLOW2D_NODE_STRAIN_MAX_ITERATIONS), which
+ * must be 0 when T = 0.  window = 0 is refused.
+ * Weighable.  For a usable node q, with sigma_u and sigma_v converted to double,
+ *   vu_q = sigma_u*sigma_u + f2,   vv_q = sigma_v*sigma_v + f2.
+ * q is *weighable* when vu_q > 0, vv_q > 0, vu_q < +inf and vv_q < +inf (a NaN sigma fails; a sigma of 0 needs a floor; only
+ * the square of a sigma is looked at), and then pu_q = 1.0 / vu_q,  pv_q = 1.0 / vv_q.  Only weighable nodes of the window are
+ * taps and are visited; n is their count.  A node that is not weighable is invalid with the reason *centre*, like one that is
+ * not usable.  *Sparse* when !(n >= min_nodes), before anything is factored.
+ * Passes t = 0 .. K.  Every tap carries c_q in double; in pass 0, c_q = 1.  u and v are separate least-squares fits:
+ *   Mu[a][b] = sum of (c_q*pu_q) * (double)(phi_a*phi_b), the product of the basis formed in int;
+ *   bu[a] = sum of ((c_q*pu_q) * (double)phi_a) * wu;
+ *   Mv and bv likewise with pv_q and wv;   every term rounded as written, added from 0 in visiting order.
+ * Factor Mu and solve cu = Solve_Mu(bu); factor Mv and solve cv = Solve_Mv(bv); a failed pivot test in either matrix in any pass
+ * makes the node *degenerate*.  The residuals of the pass, per tap, ru and rv as in flow2d_node_strain_robust_2d, and
+ *   r2 = (ru*ru)*pu_q + (rv*rv)*pv_q      (dimensionless: the squared distance from the fit in the tap's own sigmas);
+ * for t < K the next pass has c_q = t2 / (t2 + r2).
+ * After pass K.  With T > 0 a tap is *kept* when r2 <= t2, with the residuals of pass K; with T = 0 every tap is kept.  *Sparse*
+ * by !(kept >= min_nodes), *finished* and *suspect* (a finished node whose own tap is not kept: never with T = 0) are those of
+ * flow2d_node_strain_robust_2d; a, b, c, d come from cu and cv of pass K as in flow2d_node_strain_2d.
+ * Covariance.  With the factors of pass K and e_1, e_2 the unit vectors of the two slopes: xu1 = Solve_Mu(e_1), xu2 =
+ * Solve_Mu(e_2), ss = s*s in double,
+ *   Vaa = xu1[1]/ss,  Vab = xu1[2]/ss,  Vbb = xu2[2]/ss;     Vcc, Vcd, Vdd from Mv the same way.
+ * With weights 1/variance the inverse of the normal matrix IS the covariance of the coefficients (for K > 0 that of the last
+ * pass's weights taken as given).  The u and the v fit are treated as independent: the rho of flow2d_subset_uncertainty_2d is
+ * not propagated, and neither is the correlation between overlapping subsets of neighbouring nodes.
+ * Standard deviations, in double, each the square root of a variance, cast to float once:
+ *   sigma_ux = sqrt(Vaa),  sigma_uy = sqrt(Vbb),  sigma_vx = sqrt(Vcc),  sigma_vy = sqrt(Vdd),
+ *   sigma_divergence = sqrt(Vaa + Vdd),   sigma_vorticity = sqrt(Vbb + Vcc),
+ *   measure == FLOW2D_STRAIN_SMALL:  sigma_exx = sqrt(Vaa),  sigma_eyy = sqrt(Vdd),  sigma_exy = sqrt(0.25*(Vbb + Vcc));
+ *   measure == FLOW2D_STRAIN_GREEN_LAGRANGE, to first order through the Jacobian of that measure's formulas, with
+ *   ja = 1.0 + a and jd = 1.0 + d:
+ *     sigma_exx = sqrt((ja*ja)*Vaa + (c*c)*Vcc),     sigma_eyy = sqrt((b*b)*Vbb + (jd*jd)*Vdd),
+ *     Qu = ((b*b)*Vaa + (2.0*(b*ja))*Vab) + (ja*ja)*Vbb,     Qv = ((jd*jd)*Vcc + (2.0*(jd*c))*Vcd) + (c*c)*Vdd,
+ *     sigma_exy = sqrt(0.25*(Qu + Qv)).
+ * Outputs in addition.  `sigmas` (a HOST struct of nine device pointers, may be NULL, each may be NULL): planes on the node grid
+ * like those of `out`, NaN (0x7FC00000) at an invalid node.  `diagnostics` as in flow2d_node_strain_robust_2d, with residual and
+ * centre now in sigmas (square roots of r2 as defined here).  A sigma plane or a diagnostic plane alone is output enough.
+ * stats[b]: the record of flow2d_node_strain_robust_2d, reserved[0 .. 5] with its meanings, and reserved[6] = the nodes of the
+ * grid that are usable but not weighable (they are among the *centre* nodes of reserved[0]); the rest 0.  The same two ordered
+ * launches with slabs of flow2d_node_strain_weighted_workspace_bytes: the same bytes alone, in a lock-step batch and under graph
+ * replay.
+ * What follows from the text: (a) with both sigma planes 1.0f everywhere, sigma_floor = 0 and T = 0 every weight is 1.0, and the
+ * nine planes of `out` and every word of the record but reserved[3 .. 6] are flow2d_node_strain_2d's; (b) with T = 0, doubling
+ * both sigma planes and sigma_floor scales every sum by the power of two 1/4, so -- short of overflow and underflow -- `out`
+ * does not change by a bit and every sigma plane doubles exactly.
+ * FLOW2D_ERR_INVALID_ARGUMENT, and nothing written, for what flow2d_node_strain_robust_2d refuses apart from its sigma (a sigma
+ * plane counts as a requested plane), for a null node_sigma_u or node_sigma_v or one that breaks the plane rules, a sigma_floor or
+ * threshold that is not finite or < 0, iterations outside their limits or > 0 with T = 0, or a written range that overlaps a
+ * sigma input; FLOW2D_ERR_UNSUPPORTED for 2^31 nodes or more. */
+typedef struct flow2d_strain_sigma_planes {
+    float* sigma_ux; /* standard deviations of the four gradients, 1 (pixels per pixel) */
+    float* sigma_uy;
+    float* sigma_vx;
+    float* sigma_vy;
+    float* sigma_divergence;
+    float* sigma_vorticity;
+    float* sigma_exx; /* of the chosen measure's strains */
+    float* sigma_eyy;
+    float* sigma_exy;
+} flow2d_strain_sigma_planes;
+/* Workspace bytes flow2d_node_strain_weighted_2d needs for `instances` lock-step instances of an nw x nh grid when it writes
+ * statistics (0 for a zero size; a multiple of 16).  Host logic only, needs no device. */
+FLOW2D_API size_t flow2d_node_strain_weighted_workspace_bytes(size_t nw, size_t nh, size_t instances);
+FLOW2D_API int flow2d_node_strain_weighted_2d(flow2d_context* ctx, const float* node_u, const float* node_v,
+                                              const float* node_state /* may be NULL */, const float* node_sigma_u,
+                                              const float* node_sigma_v, size_t nw, size_t nh, size_t node_pitch_bytes, int spacing,
+                                              int window, int order, int min_nodes, int min_state, int measure, float sigma_floor,
+                                              float threshold, int iterations,
+                                              const flow2d_deformation_planes* out /* host, may be NULL */,
+                                              const flow2d_node_strain_diagnostics* diagnostics /* host, may be NULL */,
+                                              const flow2d_strain_sigma_planes* sigmas /* host, may be NULL */,
+                                              flow2d_deformation_stats* stats /* device, may be NULL */, void* workspace,
+                                              size_t workspace_bytes);
 
 /* The composition of two node fields of a sequence whose reference frame has moved (incremental DIC), out of place.  The *base* A
  * is frame 0 -> frame r at the nodes of frame 0; the *increment* B is frame r -> frame k on the same grid laid in frame r.  The
