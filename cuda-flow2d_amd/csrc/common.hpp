@@ -7,6 +7,7 @@
 #include <cstdint>
 #include <vector>
 
+#include "byte_ranges.hpp"
 #include "flow2d_c_abi.h"
 
 struct flow2d_timing_slot {
@@ -89,35 +90,10 @@ inline size_t batch_span(const flow2d_context* ctx, size_t plane_bytes)
     return plane_bytes + (ctx->batch_count - 1) * ctx->batch_stride_floats * sizeof(float);
 }
 
-// The alias check of the entries whose kernels mark every pointer __restrict__: a whole byte range, not only its base.
-struct ByteRange {
-    const void* p;  // null: an optional argument that is absent, skipped
-    size_t bytes;
-};
-
-inline bool ranges_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes)
+// The alias check of the entries (byte_ranges.hpp): the instances of this context's launches.
+inline Instances batch_instances(const flow2d_context* ctx)
 {
-    const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
-    return pa < pb + b_bytes && pb < pa + a_bytes;
-}
-
-// Whether any written range meets a read one or another written one.  An entry checks twice: the plane extents before
-// FLOW2D_ENTER (no context field is needed: it holds without a device), the batch_span extents after it.
-inline bool any_overlap(const ByteRange* written, size_t n_written, const ByteRange* read, size_t n_read)
-{
-    for (size_t i = 0; i < n_written; ++i) {
-        if (!written[i].p) continue;
-        for (size_t j = 0; j < n_read; ++j)
-            if (read[j].p && ranges_overlap(written[i].p, written[i].bytes, read[j].p, read[j].bytes)) return true;
-        for (size_t j = i + 1; j < n_written; ++j)
-            if (written[j].p && ranges_overlap(written[i].p, written[i].bytes, written[j].p, written[j].bytes)) return true;
-    }
-    return false;
-}
-template <size_t W, size_t R>
-bool any_overlap(const ByteRange (&written)[W], const ByteRange (&read)[R])
-{
-    return any_overlap(written, W, read, R);
+    return Instances{ctx->batch_count, ctx->batch_stride_floats * sizeof(float)};
 }
 
 }  // namespace flow2d

@@ -749,23 +749,18 @@ static int launch_median(flow2d_context* ctx, const float* input, const float* i
     FLOW2D_ENTER(ctx);
     // (a half-size base: (height + 1) / 2 rows of (width + 1) / 2 pixels, in the same pitch)
     const size_t in_width = ADD == kAddHalfBase ? (width + 1) / 2 : width, in_height = ADD == kAddHalfBase ? (height + 1) / 2 : height;
-    if (!flow2d::plane_args_ok(input, in_width, in_height, pitch_bytes) ||
-        !flow2d::plane_args_ok(output, width, height, pitch_bytes) || input == output)
+    if (!flow2d::plane_args_ok(input, in_width, in_height, pitch_bytes) || !flow2d::plane_args_ok(output, width, height, pitch_bytes))
         return FLOW2D_ERR_INVALID_ARGUMENT;
     const bool pair = input_b || output_b;
-    if (pair && (!flow2d::plane_args_ok(input_b, in_width, in_height, pitch_bytes) ||
-                 !flow2d::plane_args_ok(output_b, width, height, pitch_bytes) || input_b == output_b ||
-                 output_b == output || output_b == input || output == input_b))
+    if (pair && (!flow2d::plane_args_ok(input_b, in_width, in_height, pitch_bytes) || !flow2d::plane_args_ok(output_b, width, height, pitch_bytes)))
         return FLOW2D_ERR_INVALID_ARGUMENT;
-    if (ADD && (!flow2d::plane_args_ok(addend, width, height, pitch_bytes) || addend == output || addend == output_b ||
-                (pair && (!flow2d::plane_args_ok(addend_b, width, height, pitch_bytes) || addend_b == output ||
-                          addend_b == output_b))))
+    if (ADD && (!flow2d::plane_args_ok(addend, width, height, pitch_bytes) || (pair && !flow2d::plane_args_ok(addend_b, width, height, pitch_bytes))))
         return FLOW2D_ERR_INVALID_ARGUMENT;
-    if (ADD == kAddHalfBase && ctx->batch_count > 1) {  // the entry's byte-range check again, over every instance of a lock-step group
-        const size_t half_span = flow2d::batch_span(ctx, in_height * pitch_bytes), full_span = flow2d::batch_span(ctx, height * pitch_bytes);
-        const flow2d::ByteRange written[] = {{output, full_span}, {output_b, full_span}};
-        const flow2d::ByteRange read[] = {{input, half_span}, {input_b, half_span}, {addend, full_span}, {addend_b, full_span}};
-        if (flow2d::any_overlap(written, read)) return FLOW2D_ERR_INVALID_ARGUMENT;
+    {   // no output may meet an input, an addend or the other output, over every instance of a lock-step group
+        const size_t in_bytes = in_height * pitch_bytes, bytes = height * pitch_bytes;
+        const flow2d::ByteRange written[] = {{output, bytes}, {output_b, bytes}};
+        const flow2d::ByteRange read[] = {{input, in_bytes}, {input_b, in_bytes}, {addend, bytes}, {addend_b, bytes}};
+        if (flow2d::any_overlap(written, read, flow2d::batch_instances(ctx))) return FLOW2D_ERR_INVALID_ARGUMENT;
     }
     if (window != 3 && window != 5 && window != 7) return FLOW2D_ERR_UNSUPPORTED;
     // the mirror rule needs every reflected index inside the image

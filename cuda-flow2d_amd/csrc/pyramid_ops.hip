@@ -1191,9 +1191,18 @@ static int launch_add(flow2d_context* ctx, float* operand_0, const float* operan
         return FLOW2D_ERR_INVALID_ARGUMENT;
     const bool pair = operand_0_b || operand_1_b;
     if (pair && (!flow2d::plane_args_ok(operand_0_b, width, height, pitch_bytes) ||
-                 !flow2d::plane_args_ok(operand_1_b, width, height, pitch_bytes) || operand_0_b == operand_0 ||
-                 operand_0_b == operand_1 || operand_0 == operand_1_b))
+                 !flow2d::plane_args_ok(operand_1_b, width, height, pitch_bytes)))
         return FLOW2D_ERR_INVALID_ARGUMENT;
+    {   // in place on operand_0: its own operand_1 may be the same plane (x += x), and nothing else may meet it
+        const flow2d::Instances n = flow2d::batch_instances(ctx);
+        const size_t bytes = height * pitch_bytes;
+        const flow2d::ByteRange written[] = {{operand_0, bytes}, {operand_0_b, bytes}};
+        const flow2d::ByteRange crossed_a[] = {{operand_1_b, bytes}}, crossed_b[] = {{operand_1, bytes}};
+        if (flow2d::any_overlap(written, 2, nullptr, 0, n) || flow2d::any_overlap(written, 1, crossed_a, 1, n) ||
+            flow2d::any_overlap(written + 1, 1, crossed_b, 1, n) || flow2d::overlap_unless_identical(operand_0, operand_1, bytes, n) ||
+            flow2d::overlap_unless_identical(operand_0_b, operand_1_b, bytes, n))
+            return FLOW2D_ERR_INVALID_ARGUMENT;
+    }
     const unsigned planes = pair ? 2 : 1;
     dim3 grid(flow2d::div_up(width, kBlockX * 4), flow2d::div_up(height, kBlockY), flow2d::batch_z(ctx, planes));
     add_2d_kernel<<<grid, dim3(kBlockX, kBlockY), 0, ctx->stream>>>(operand_0, operand_1, operand_0_b, operand_1_b,
@@ -1248,10 +1257,18 @@ int flow2d_copy_planes(flow2d_context* ctx, size_t count, const void* const* src
     PlaneTable t{};
     for (size_t i = 0; i < count; ++i) {
         if (!flow2d::plane_args_ok(src_planes[i], width, height, pitch_bytes) ||
-            !flow2d::plane_args_ok(dst_planes[i], width, height, pitch_bytes) || src_planes[i] == dst_planes[i])
+            !flow2d::plane_args_ok(dst_planes[i], width, height, pitch_bytes))
             return FLOW2D_ERR_INVALID_ARGUMENT;
         t.src[i] = static_cast<const float*>(src_planes[i]);
         t.dst[i] = static_cast<float*>(dst_planes[i]);
+    }
+    {   // no destination may meet a source (its own or another plane's) or another destination; no batch: the tables name every plane
+        flow2d::ByteRange written[FLOW2D_COPY_PLANES_MAX], read[FLOW2D_COPY_PLANES_MAX];
+        for (size_t i = 0; i < count; ++i) {
+            written[i] = flow2d::ByteRange{dst_planes[i], height * pitch_bytes};
+            read[i] = flow2d::ByteRange{src_planes[i], height * pitch_bytes};
+        }
+        if (flow2d::any_overlap(written, count, read, count)) return FLOW2D_ERR_INVALID_ARGUMENT;
     }
     const unsigned bx = std::max(1u, std::min(8u, flow2d::div_up(width / 4 + 1, 256)));
     const unsigned by = static_cast<unsigned>(std::min<size_t>(height, 1024));
@@ -1287,8 +1304,12 @@ static int launch_gauss(flow2d_context* ctx, bool rows, float* dst, const float*
 {
     FLOW2D_ENTER(ctx);
     if (!flow2d::plane_args_ok(dst, width, height, pitch_bytes) ||
-        !flow2d::plane_args_ok(src, width, height, pitch_bytes) || !taps || dst == src)
+        !flow2d::plane_args_ok(src, width, height, pitch_bytes) || !taps)
         return FLOW2D_ERR_INVALID_ARGUMENT;
+    {
+        const flow2d::ByteRange written[] = {{dst, height * pitch_bytes}}, read[] = {{src, height * pitch_bytes}};
+        if (flow2d::any_overlap(written, read, flow2d::batch_instances(ctx))) return FLOW2D_ERR_INVALID_ARGUMENT;
+    }
     if (radius < 0 || 2 * radius + 1 > 51) return FLOW2D_ERR_UNSUPPORTED;
     GaussTaps t;
     for (int i = 0; i < 51; ++i) t.t[i] = i < 2 * radius + 1 ? taps[i] : 0.f;
@@ -1322,8 +1343,12 @@ int flow2d_gaussian_blur(flow2d_context* ctx, float* dst, const float* src, size
 {
     FLOW2D_ENTER(ctx);
     if (!flow2d::plane_args_ok(dst, width, height, pitch_bytes) ||
-        !flow2d::plane_args_ok(src, width, height, pitch_bytes) || !taps || dst == src)
+        !flow2d::plane_args_ok(src, width, height, pitch_bytes) || !taps)
         return FLOW2D_ERR_INVALID_ARGUMENT;
+    {
+        const flow2d::ByteRange written[] = {{dst, height * pitch_bytes}}, read[] = {{src, height * pitch_bytes}};
+        if (flow2d::any_overlap(written, read, flow2d::batch_instances(ctx))) return FLOW2D_ERR_INVALID_ARGUMENT;
+    }
     if (radius < 0 || radius > kBlurMaxRadius) return FLOW2D_ERR_UNSUPPORTED;
     GaussTaps t;
     for (int i = 0; i < 51; ++i) t.t[i] = i < 2 * radius + 1 ? taps[i] : 0.f;
@@ -1354,13 +1379,19 @@ static int launch_resample(flow2d_context* ctx, bool along_x, const float* input
     const size_t in_w = along_x ? in_extent : out_width;
     const size_t in_h = along_x ? out_height : in_extent;
     if (!flow2d::plane_args_ok(input, in_w, in_h, pitch_bytes) ||
-        !flow2d::plane_args_ok(output, out_width, out_height, pitch_bytes) || input == output)
+        !flow2d::plane_args_ok(output, out_width, out_height, pitch_bytes))
         return FLOW2D_ERR_INVALID_ARGUMENT;
     const bool pair = input_b || output_b;
     if (pair && (!flow2d::plane_args_ok(input_b, in_w, in_h, pitch_bytes) ||
-                 !flow2d::plane_args_ok(output_b, out_width, out_height, pitch_bytes) || input_b == output_b ||
-                 output_b == output || output_b == input || output == input_b))
+                 !flow2d::plane_args_ok(output_b, out_width, out_height, pitch_bytes)))
         return FLOW2D_ERR_INVALID_ARGUMENT;
+    {   // The input of the y pass may be a column segment of a packed plane (flow2d_resample_x_levels), whose last row ends with
+        // the segment and not a pitch further on: that pass reads columns below out_width only, and its range ends there.
+        const size_t in_bytes = along_x ? in_h * pitch_bytes : (in_h - 1) * pitch_bytes + (out_width * sizeof(float) + 15) / 16 * 16;
+        const size_t out_bytes = out_height * pitch_bytes;
+        const flow2d::ByteRange written[] = {{output, out_bytes}, {output_b, out_bytes}}, read[] = {{input, in_bytes}, {input_b, in_bytes}};
+        if (flow2d::any_overlap(written, read, flow2d::batch_instances(ctx))) return FLOW2D_ERR_INVALID_ARGUMENT;
+    }
     const unsigned planes = pair ? 2 : 1;
     const unsigned z = flow2d::batch_z(ctx, planes);
     const BatchArg batch = flow2d::batch_arg(ctx, planes);
@@ -1395,13 +1426,17 @@ int flow2d_resample_x_levels(flow2d_context* ctx, const float* input_a, float* p
     if (!out_widths || !column_offsets || level_count == 0) return FLOW2D_ERR_INVALID_ARGUMENT;
     if (level_count > FLOW2D_RESAMPLE_MAX_LEVELS || in_width > 15360) return FLOW2D_ERR_UNSUPPORTED;
     const bool pair = input_b || packed_b;
-    if (!flow2d::plane_args_ok(input_a, in_width, height, pitch_bytes) || !packed_a || input_a == packed_a ||
+    if (!flow2d::plane_args_ok(input_a, in_width, height, pitch_bytes) || !packed_a ||
         (reinterpret_cast<uintptr_t>(packed_a) % 16) != 0)
         return FLOW2D_ERR_INVALID_ARGUMENT;
-    if (pair && (!flow2d::plane_args_ok(input_b, in_width, height, pitch_bytes) || !packed_b || input_b == packed_b ||
-                 packed_b == packed_a || packed_b == input_a || packed_a == input_b ||
+    if (pair && (!flow2d::plane_args_ok(input_b, in_width, height, pitch_bytes) || !packed_b ||
                  (reinterpret_cast<uintptr_t>(packed_b) % 16) != 0))
         return FLOW2D_ERR_INVALID_ARGUMENT;
+    {   // (a packed plane counts with all its rows, whichever segments the levels take)
+        const size_t bytes = height * pitch_bytes;
+        const flow2d::ByteRange written[] = {{packed_a, bytes}, {packed_b, bytes}}, read[] = {{input_a, bytes}, {input_b, bytes}};
+        if (flow2d::any_overlap(written, read, flow2d::batch_instances(ctx))) return FLOW2D_ERR_INVALID_ARGUMENT;
+    }
     ResampleLevels lv{};
     lv.count = static_cast<int>(level_count);
     const size_t pitch = pitch_bytes / 4;
@@ -1448,12 +1483,11 @@ int flow2d_resample_y_levels(flow2d_context* ctx, const float* packed_a, float* 
 {
     FLOW2D_ENTER(ctx);
     if (!out_widths || !out_heights || !column_offsets || !output_rows || level_count == 0 || !packed_a || !output_a ||
-        packed_a == output_a || pitch_bytes == 0 || pitch_bytes % 16 != 0 || in_height == 0)
+        pitch_bytes == 0 || pitch_bytes % 16 != 0 || in_height == 0)
         return FLOW2D_ERR_INVALID_ARGUMENT;
     if (level_count > FLOW2D_RESAMPLE_MAX_LEVELS) return FLOW2D_ERR_UNSUPPORTED;
     const bool pair = packed_b || output_b;
-    if (pair && (!packed_b || !output_b || packed_b == output_b || output_b == output_a || output_b == packed_a || output_a == packed_b))
-        return FLOW2D_ERR_INVALID_ARGUMENT;
+    if (pair && (!packed_b || !output_b)) return FLOW2D_ERR_INVALID_ARGUMENT;
     const size_t pitch = pitch_bytes / 4;
     ResampleYLevels lv{};
     lv.count = static_cast<int>(level_count);
@@ -1479,6 +1513,17 @@ int flow2d_resample_y_levels(flow2d_context* ctx, const float* packed_a, float* 
         lv.blocks_x[l] = static_cast<int>(flow2d::div_up(out_widths[l], kBlockX));
         blocks += static_cast<long>(lv.blocks_x[l]) * static_cast<long>(flow2d::div_up(flow2d::div_up(out_heights[l], lv.rows_per_thread[l]), kBlockY));
         if (blocks >= 0x7fffffffl) return FLOW2D_ERR_UNSUPPORTED;
+    }
+    {   // an output plane is written between its first and its last region row; the packed planes are read with all their rows
+        size_t first_row = ~size_t{0}, end_row = 0;
+        for (size_t l = 0; l < level_count; ++l) {
+            first_row = std::min(first_row, output_rows[l]);
+            end_row = std::max(end_row, output_rows[l] + out_heights[l]);
+        }
+        const size_t out_bytes = (end_row - first_row) * pitch_bytes, in_bytes = in_height * pitch_bytes;
+        const flow2d::ByteRange written[] = {{output_a + first_row * pitch, out_bytes}, {pair ? output_b + first_row * pitch : nullptr, out_bytes}};
+        const flow2d::ByteRange read[] = {{packed_a, in_bytes}, {packed_b, in_bytes}};
+        if (flow2d::any_overlap(written, read, flow2d::batch_instances(ctx))) return FLOW2D_ERR_INVALID_ARGUMENT;
     }
     const unsigned planes = pair ? 2 : 1;
     resample_y_levels_kernel<<<dim3(static_cast<unsigned>(blocks), 1, flow2d::batch_z(ctx, planes)), dim3(kBlockX, kBlockY), 0, ctx->stream>>>(
@@ -1532,11 +1577,10 @@ int flow2d_resample_xy_levels(flow2d_context* ctx, const float* input_a, float* 
         end_row = std::max(end_row, output_rows[l] + out_heights[l]);
     }
     {   // the kernel marks every plane __restrict__: no written byte range [p, p + rows * pitch) may meet a read one or the other written one
-        const size_t written_span = flow2d::batch_span(ctx, (end_row - first_row) * pitch_bytes);
-        const size_t read_span = flow2d::batch_span(ctx, in_height * pitch_bytes);
-        const flow2d::ByteRange written[] = {{output_a + first_row * pitch, written_span}, {pair ? output_b + first_row * pitch : nullptr, written_span}};
-        const flow2d::ByteRange read[] = {{input_a, read_span}, {input_b, read_span}};
-        if (flow2d::any_overlap(written, read)) return FLOW2D_ERR_INVALID_ARGUMENT;
+        const size_t written_bytes = (end_row - first_row) * pitch_bytes, read_bytes = in_height * pitch_bytes;
+        const flow2d::ByteRange written[] = {{output_a + first_row * pitch, written_bytes}, {pair ? output_b + first_row * pitch : nullptr, written_bytes}};
+        const flow2d::ByteRange read[] = {{input_a, read_bytes}, {input_b, read_bytes}};
+        if (flow2d::any_overlap(written, read, flow2d::batch_instances(ctx))) return FLOW2D_ERR_INVALID_ARGUMENT;
     }
     for (int k = 1; k <= kXYMaxLog; ++k) {
         if (level_of[k] < 0) continue;
@@ -1605,13 +1649,17 @@ int flow2d_resample_xy_pair(flow2d_context* ctx, const float* input_a, float* ou
 {
     FLOW2D_ENTER(ctx);
     if (!flow2d::plane_args_ok(input_a, in_width, in_height, pitch_bytes) ||
-        !flow2d::plane_args_ok(output_a, out_width, out_height, pitch_bytes) || input_a == output_a)
+        !flow2d::plane_args_ok(output_a, out_width, out_height, pitch_bytes))
         return FLOW2D_ERR_INVALID_ARGUMENT;
     const bool pair = input_b || output_b;
     if (pair && (!flow2d::plane_args_ok(input_b, in_width, in_height, pitch_bytes) ||
-                 !flow2d::plane_args_ok(output_b, out_width, out_height, pitch_bytes) || input_b == output_b ||
-                 output_b == output_a || output_b == input_a || output_a == input_b))
+                 !flow2d::plane_args_ok(output_b, out_width, out_height, pitch_bytes)))
         return FLOW2D_ERR_INVALID_ARGUMENT;
+    {
+        const size_t in_bytes = in_height * pitch_bytes, out_bytes = out_height * pitch_bytes;
+        const flow2d::ByteRange written[] = {{output_a, out_bytes}, {output_b, out_bytes}}, read[] = {{input_a, in_bytes}, {input_b, in_bytes}};
+        if (flow2d::any_overlap(written, read, flow2d::batch_instances(ctx))) return FLOW2D_ERR_INVALID_ARGUMENT;
+    }
     const unsigned planes = pair ? 2 : 1;
     dim3 grid = grid_for(out_width, flow2d::div_up(out_height, kResampleXYRows));
     grid.z = flow2d::batch_z(ctx, planes);
@@ -1635,9 +1683,13 @@ int flow2d_registration_2d(flow2d_context* ctx, const float* frame_0, const floa
         !flow2d::plane_args_ok(frame_1, width, height, pitch_bytes) ||
         !flow2d::plane_args_ok(flow_u, width, height, pitch_bytes) ||
         !flow2d::plane_args_ok(flow_v, width, height, pitch_bytes) ||
-        !flow2d::plane_args_ok(output, width, height, pitch_bytes) || output == frame_1 || output == frame_0 ||
-        !(hx > 0.f) || !(hy > 0.f))
+        !flow2d::plane_args_ok(output, width, height, pitch_bytes) || !(hx > 0.f) || !(hy > 0.f))
         return FLOW2D_ERR_INVALID_ARGUMENT;
+    {
+        const size_t bytes = height * pitch_bytes;
+        const flow2d::ByteRange written[] = {{output, bytes}}, read[] = {{frame_0, bytes}, {frame_1, bytes}, {flow_u, bytes}, {flow_v, bytes}};
+        if (flow2d::any_overlap(written, read, flow2d::batch_instances(ctx))) return FLOW2D_ERR_INVALID_ARGUMENT;
+    }
     dim3 grid = grid_for(width, flow2d::div_up(height, kRegistrationRows));
     grid.z = flow2d::batch_z(ctx, 1);
     registration_kernel<<<grid, dim3(kBlockX, kBlockY), 0, ctx->stream>>>(
@@ -1661,13 +1713,11 @@ int flow2d_upsample_registration_2d(flow2d_context* ctx, const float* flow_u, co
         !flow2d::plane_args_ok(frame_0, width, height, pitch_bytes) || !flow2d::plane_args_ok(frame_1, width, height, pitch_bytes) ||
         !flow2d::plane_args_ok(output, width, height, pitch_bytes) || !(hx > 0.f) || !(hy > 0.f))
         return FLOW2D_ERR_INVALID_ARGUMENT;
-    const float* reads[] = {flow_u, flow_v, frame_0, frame_1};
-    const float* writes[] = {out_u, out_v, output};
-    for (int i = 0; i < 3; ++i) {
-        for (const float* r : reads)
-            if (writes[i] == r) return FLOW2D_ERR_INVALID_ARGUMENT;
-        for (int j = i + 1; j < 3; ++j)
-            if (writes[i] == writes[j]) return FLOW2D_ERR_INVALID_ARGUMENT;
+    {
+        const size_t in_bytes = in_height * pitch_bytes, bytes = height * pitch_bytes;
+        const flow2d::ByteRange written[] = {{out_u, bytes}, {out_v, bytes}, {output, bytes}};
+        const flow2d::ByteRange read[] = {{flow_u, in_bytes}, {flow_v, in_bytes}, {frame_0, bytes}, {frame_1, bytes}};
+        if (flow2d::any_overlap(written, read, flow2d::batch_instances(ctx))) return FLOW2D_ERR_INVALID_ARGUMENT;
     }
     dim3 grid = grid_for(width, flow2d::div_up(height, kRegistrationRows));
     grid.z = flow2d::batch_z(ctx, 1);
@@ -1715,10 +1765,9 @@ int flow2d_upsample_registration_half_2d(flow2d_context* ctx, const float* flow_
     }
     FLOW2D_ENTER(ctx);
     {   // ... over every instance of a lock-step group
-        const size_t half_span = flow2d::batch_span(ctx, half_bytes), full_span = flow2d::batch_span(ctx, full_bytes);
-        const flow2d::ByteRange written[] = {{out_u, half_span}, {out_v, half_span}, {output, full_span}};
-        const flow2d::ByteRange read[] = {{flow_u, half_span}, {flow_v, half_span}, {frame_0, full_span}, {frame_1, full_span}};
-        if (ctx->batch_count > 1 && flow2d::any_overlap(written, read)) return FLOW2D_ERR_INVALID_ARGUMENT;
+        const flow2d::ByteRange written[] = {{out_u, half_bytes}, {out_v, half_bytes}, {output, full_bytes}};
+        const flow2d::ByteRange read[] = {{flow_u, half_bytes}, {flow_v, half_bytes}, {frame_0, full_bytes}, {frame_1, full_bytes}};
+        if (flow2d::any_overlap(written, read, flow2d::batch_instances(ctx))) return FLOW2D_ERR_INVALID_ARGUMENT;
     }
     dim3 grid = grid_for(width, flow2d::div_up(height, kRegistrationRows));
     grid.z = flow2d::batch_z(ctx, 1);

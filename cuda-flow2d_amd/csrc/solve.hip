@@ -623,6 +623,17 @@ bool solver_planes_ok(const float* const* planes, int count, size_t w, size_t h,
     return w >= 2 && h >= 2;
 }
 
+// Whether a written plane meets a read one or another written one, over every instance of the context's batch: all are
+// h rows of pitch_bytes.
+bool solver_planes_meet(const flow2d_context* ctx, const float* const* read, size_t n_read, const float* const* written, size_t n_written,
+                        size_t h, size_t pitch_bytes)
+{
+    flow2d::ByteRange r[8], w[2];
+    for (size_t i = 0; i < n_read; ++i) r[i] = flow2d::ByteRange{read[i], h * pitch_bytes};
+    for (size_t i = 0; i < n_written; ++i) w[i] = flow2d::ByteRange{written[i], h * pitch_bytes};
+    return flow2d::any_overlap(w, n_written, r, n_read, flow2d::batch_instances(ctx));
+}
+
 // The tile forms of a data term, Jacobi and red-black half-sweep: the kernel and its block height (the block is kBlockX wide).
 using SweepKernel = void (*)(const float*, const float*, const float*, const float*, const float*, const float*, const float*,
                              const float*, XcdTiles, int, int, int, float, float, float, float*, float*);
@@ -775,10 +786,9 @@ int flow2d_compute_phi_ksi(flow2d_context* ctx, const float* frame_0, const floa
 {
     FLOW2D_ENTER(ctx);
     const float* planes[] = {frame_0, frame_1, flow_u, flow_v, flow_du, flow_dv, phi, ksi};
-    if (!solver_planes_ok(planes, 8, width, height, pitch_bytes) || !(hx > 0.f) || !(hy > 0.f) || phi == ksi)
+    if (!solver_planes_ok(planes, 8, width, height, pitch_bytes) || !(hx > 0.f) || !(hy > 0.f) ||
+        solver_planes_meet(ctx, planes, 6, planes + 6, 2, height, pitch_bytes))
         return FLOW2D_ERR_INVALID_ARGUMENT;
-    for (int i = 0; i < 6; ++i)
-        if (planes[i] == phi || planes[i] == ksi) return FLOW2D_ERR_INVALID_ARGUMENT;
     const flow2d::SolveLevel level{FLOW2D_CONSTANCY_GREY, frame_0, frame_1, flow_u, flow_v, width, height, pitch_bytes, hx, hy, 0.f,
                                    equation_smoothness, equation_data, 0.f, 0};  // (neither data term nor alpha enter phi, ksi)
     return flow2d::launch_phi_ksi(ctx, level, {flow_du, flow_dv}, {phi, ksi});
@@ -792,10 +802,8 @@ static int sweep_entry(flow2d_context* ctx, int constancy, const float* frame_0,
     FLOW2D_ENTER(ctx);
     const float* planes[] = {frame_0, frame_1, flow_u, flow_v, flow_du, flow_dv, phi, ksi, temp_du, temp_dv};
     if (!solver_planes_ok(planes, 10, width, height, pitch_bytes) || !(hx > 0.f) || !(hy > 0.f) ||
-        temp_du == temp_dv)
+        solver_planes_meet(ctx, planes, 8, planes + 8, 2, height, pitch_bytes))  // Jacobi: the sweep must not write a plane it reads
         return FLOW2D_ERR_INVALID_ARGUMENT;
-    for (int i = 0; i < 8; ++i)  // Jacobi: the sweep must not write a plane it reads
-        if (planes[i] == temp_du || planes[i] == temp_dv) return FLOW2D_ERR_INVALID_ARGUMENT;
     const flow2d::SolveLevel level{constancy, frame_0, frame_1, flow_u, flow_v, width, height, pitch_bytes, hx, hy, alpha, 0.f, 0.f, 0.f, 0};
     return flow2d::launch_sweep(ctx, level, {flow_du, flow_dv}, {phi, ksi}, {temp_du, temp_dv});
 }
@@ -807,11 +815,10 @@ int flow2d_solve_2d_sor(flow2d_context* ctx, const float* frame_0, const float* 
 {
     FLOW2D_ENTER(ctx);
     const float* planes[] = {frame_0, frame_1, flow_u, flow_v, flow_du, flow_dv, phi, ksi};
-    if (!solver_planes_ok(planes, 8, width, height, pitch_bytes) || !(hx > 0.f) || !(hy > 0.f) || flow_du == flow_dv ||
-        !(omega > 0.f) || !(omega < 2.f))
+    const float* others[] = {frame_0, frame_1, flow_u, flow_v, phi, ksi};  // (in place on flow_du / flow_dv: nothing else may meet them)
+    if (!solver_planes_ok(planes, 8, width, height, pitch_bytes) || !(hx > 0.f) || !(hy > 0.f) || !(omega > 0.f) || !(omega < 2.f) ||
+        solver_planes_meet(ctx, others, 6, planes + 4, 2, height, pitch_bytes))
         return FLOW2D_ERR_INVALID_ARGUMENT;
-    for (int i = 0; i < 8; ++i)
-        if (i != 4 && i != 5 && (planes[i] == flow_du || planes[i] == flow_dv)) return FLOW2D_ERR_INVALID_ARGUMENT;
     if (data_constancy != FLOW2D_CONSTANCY_GREY && data_constancy != FLOW2D_CONSTANCY_GRADIENT &&
         data_constancy != FLOW2D_CONSTANCY_GRADIENT_UNTILED)
         return FLOW2D_ERR_UNSUPPORTED;

@@ -282,8 +282,6 @@ int flow2d_solve_level(flow2d_context* ctx, const float* frame_0, const float* f
     for (int i = 0; i < 10; ++i) {
         // (flow_u and flow_v hold fewer rows and columns with base_flow_shift = 1; what is checked here does not depend on that)
         if (!flow2d::plane_args_ok(planes[i], p->width, p->height, p->pitch_bytes)) return FLOW2D_ERR_INVALID_ARGUMENT;
-        for (int j = 4; j < 10; ++j)  // the six written planes must be distinct from everything else
-            if (i != j && planes[i] == planes[j]) return FLOW2D_ERR_INVALID_ARGUMENT;
     }
     const bool sor = p->sor_omega != 0.f;
     int algorithm = -1;
@@ -293,6 +291,18 @@ int flow2d_solve_level(flow2d_context* ctx, const float* frame_0, const float* f
     }
     // a half-size base flow is read by the strips only
     if (p->base_flow_shift != 0 && (p->base_flow_shift != 1 || algorithm != FLOW2D_SOLVER_FUSED)) return FLOW2D_ERR_UNSUPPORTED;
+    // du = dv = 0 over level width x container height (cuda_operation_solve_2d.cpp:229-232).  The fused path
+    // starts its first outer iteration from zero increments without reading the planes, so it needs no memset.
+    const bool one_per_outer = algorithm == FLOW2D_SOLVER_FUSED || algorithm == FLOW2D_SOLVER_TILED;
+    const bool zero_increments = algorithm == FLOW2D_SOLVER_PER_SWEEP || (one_per_outer && p->outer_iterations_count == 0);
+    {   // The six written planes may meet nothing, over every instance of a lock-step group: whichever algorithm runs, it gets its
+        // planes from here.  (flow_du / flow_dv count with the rows of the memset where there is one; a half-size base flow with its own.)
+        const size_t bytes = p->height * p->pitch_bytes, base_bytes = (p->base_flow_shift ? (p->height + 1) / 2 : p->height) * p->pitch_bytes;
+        const size_t zeroed = (zero_increments ? p->container_height : p->height) * p->pitch_bytes;
+        const flow2d::ByteRange written[] = {{flow_du, zeroed}, {flow_dv, zeroed}, {phi, bytes}, {ksi, bytes}, {temp_du, bytes}, {temp_dv, bytes}};
+        const flow2d::ByteRange read[] = {{frame_0, bytes}, {frame_1, bytes}, {flow_u, base_bytes}, {flow_v, base_bytes}};
+        if (flow2d::any_overlap(written, read, flow2d::batch_instances(ctx))) return FLOW2D_ERR_INVALID_ARGUMENT;
+    }
 
     flow2d_timing_slot* slot = nullptr;
     if (ctx->timing) {
@@ -304,10 +314,7 @@ int flow2d_solve_level(flow2d_context* ctx, const float* frame_0, const float* f
         FLOW2D_HIP_TRY(hipEventRecord(slot->start, ctx->stream));
     }
 
-    // du = dv = 0 over level width x container height (cuda_operation_solve_2d.cpp:229-232).  The fused path
-    // starts its first outer iteration from zero increments without reading the planes, so it needs no memset.
-    const bool one_per_outer = algorithm == FLOW2D_SOLVER_FUSED || algorithm == FLOW2D_SOLVER_TILED;
-    if (algorithm == FLOW2D_SOLVER_PER_SWEEP || (one_per_outer && p->outer_iterations_count == 0)) {
+    if (zero_increments) {
         for (unsigned b = 0; b < ctx->batch_count; ++b) {
             FLOW2D_HIP_TRY(hipMemset2DAsync(flow_du + b * ctx->batch_stride_floats, p->pitch_bytes, 0,
                                             p->width * sizeof(float), p->container_height, ctx->stream));

@@ -207,6 +207,31 @@ FLOW2D_API int flow2d_graph_destroy(flow2d_context* ctx, void* graph_exec);
 
 /* ---- kernel launchers: one per `extern "C" __global__` symbol of src/kernels/ -------------- */
 
+/* The core entries: the launchers of the reference's kernels and their fused forms, the hot path of the flow --
+ *   flow2d_add_2d, flow2d_add_2d_pair, flow2d_copy_planes, flow2d_convolution_rows, flow2d_convolution_columns,
+ *   flow2d_gaussian_blur, flow2d_median_2d, flow2d_median_2d_pair, flow2d_add_median_2d_pair, flow2d_add_median_2d_pair_half,
+ *   flow2d_registration_2d, flow2d_upsample_registration_2d, flow2d_upsample_registration_half_2d, flow2d_resample_x,
+ *   flow2d_resample_y, flow2d_resample_x_pair, flow2d_resample_y_pair, flow2d_resample_xy_pair, flow2d_resample_x_levels,
+ *   flow2d_resample_y_levels, flow2d_resample_xy_levels, flow2d_compute_phi_ksi, flow2d_solve_2d, flow2d_solve_2d_grad,
+ *   flow2d_solve_2d_grad_untiled, flow2d_solve_2d_log, flow2d_solve_2d_sor, flow2d_solve_level.
+ * Their alias rule, stated once.  A plane argument of `rows` rows stands for the bytes [p, p + rows * pitch_bytes) -- with
+ * flow2d_context_set_batch for those bytes of every instance, [p + b * stride, p + b * stride + rows * pitch_bytes), b < count --
+ * and pitch_bytes covers every byte a kernel may read or write for the plane: a kernel reads a row beyond its width only inside
+ * the row's pitch (the second column of a pair at width 1, the tail of a 16-byte load), never into another row's bytes that the
+ * call does not own, and writes inside width x rows only.  rows is the height the entry is given for the plane (in_height for
+ * the smaller input of a resample or an up-sampling, (height + 1) / 2 for a half-size base flow, the rows between the first and
+ * the last region of a plane written in regions; flow_du / flow_dv of flow2d_solve_level count with container_height rows where
+ * the per-sweep path zeroes them).  One exception: the input of flow2d_resample_y / flow2d_resample_y_pair may be a column segment
+ * of a packed plane, `packed + column_offsets[l]`; its last row ends with the segment (out_width floats, rounded up to 16 bytes).
+ * No written range may share a byte with a read range, with another written range or with another instance of itself:
+ * FLOW2D_ERR_INVALID_ARGUMENT before anything is launched or copied, whatever the base pointers are -- an output that starts one
+ * row, one instance or sixteen bytes into an input is refused like one on the input's base.  The test is exact per instance, not
+ * a test of the hulls: groups laid out A0 B0 A1 B1 (stride = two planes) share no byte and pass.  Read planes may meet each
+ * other freely.  In place, on exactly the same base and only there: operand_0 of flow2d_add_2d / flow2d_add_2d_pair is read and
+ * written, and its own operand_1 may be that same plane; flow2d_solve_2d_sor relaxes flow_du / flow_dv in place.  No other
+ * argument of a core entry may be a plane the call writes.  flow2d_copy_planes applies the rule to all its destinations against
+ * all its sources and each other, without a batch. */
+
 /* add_2d (src/kernels/add_2d.cu:33-46): operand_0 += operand_1 on w x h. */
 FLOW2D_API int flow2d_add_2d(flow2d_context* ctx, float* operand_0, const float* operand_1, size_t width,
                              size_t height, size_t pitch_bytes);
